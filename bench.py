@@ -25,6 +25,10 @@ The JSON line also carries
                      MIOpen / rocBLAS) on the same GPU, fp32 and bf16-autocast — the ">= 3x" comparison, measured here;
   cpu_baseline       the oracle (torch-CPU fp32) on this box's host cores, bounded sample, at 8 threads and at all
                      cores (rank 0, N = 1 only).  Baseline only, not the target.
+
+--dump-outputs DIR writes what rank 0's last timed step returned (sample, trajectory, mean, control, logp, sigma,
+logp_terminal) as DIR/<name>.npy in float32.  Weights and noise are seeded, so the same arguments give the same inputs on
+every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -64,7 +68,12 @@ def parse_args():
                          "reference's TRAINING semantics, per-rank batch = --batch // N (train_cifar10.py:298-301: `batchsize // ngpus`)")
     ap.add_argument("--no-graph", action="store_true", help="issue every launch from python (no hipGraph replay: dxmi_hip/graph.py); same as DXMI_GRAPH=0")
     ap.add_argument("--no-small-batch", action="store_true", help="skip the 1-GPU legs at the per-rank batches of an 8-GPU / 4-GPU reference run (32 @ T=10, 128 @ T=4)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------- self-launch
@@ -448,6 +457,32 @@ def class_rooflines(summ, step_seconds):
 CLASS_MAIN_KERNEL = {"groupnorm": "gn_apply_kernel<4>", "attention": "attention256_kernel<true>", "wgrad": "conv_wgrad_ws_kernel<3>",
                      "groupnorm_bwd": "gn_silu_bwd_kernel<4, 16>", "conv_stem": "conv_stem_kernel", "conv_other": "conv_head_kernel"}
 
+DUMP_BUDGET_BYTES = 60_000_000      # under 64 MB with the .npy headers, in decimal or binary megabytes
+DUMP_ROW_SEED = 0
+
+
+def dump_outputs(d, out_dir):
+    """Write the dict a VARSampler.sample call returned as out_dir/<name>.npy (float32).  Per-step lists are stacked on a new
+    leading axis, so the batch axis is 0 for tensors and 1 for lists.  When the whole output exceeds DUMP_BUDGET_BYTES, every
+    array keeps the same fixed, seeded subset of batch rows (sorted), the most that fits.  Called right after the timed steps:
+    a replayed hipGraph returns static buffers, which its next call overwrites."""
+    import numpy as np
+    import torch
+    arrays = {k: (torch.stack(v), 1) if isinstance(v, list) else (v, 0) for k, v in d.items() if not k.startswith("_")}
+    batch = d["sample"].shape[0]
+    total = sum(a.numel() * 4 for a, _ in arrays.values())
+    keep = min(batch, DUMP_BUDGET_BYTES // -(-total // batch))
+    rows = np.sort(np.random.default_rng(DUMP_ROW_SEED).choice(batch, keep, replace=False)) if keep < batch else np.arange(batch)
+    idx = torch.from_numpy(rows).to(d["sample"].device)
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for k, (a, axis) in arrays.items():
+        h = a.detach().index_select(axis, idx).float().cpu().numpy()
+        np.save(os.path.join(out_dir, k + ".npy"), h)
+        shapes[k] = list(h.shape)
+    return {"dir": out_dir, "dtype": "float32", "arrays": shapes,
+            "batch_rows": "all" if keep == batch else f"{keep} of {batch}: numpy default_rng({DUMP_ROW_SEED}).choice({batch}, {keep}, replace=False), sorted"}
+
 
 # ----------------------------------------------------------------------------------------------- main (one rank)
 def main():
@@ -530,6 +565,7 @@ def main():
         rank_elapsed = tt.tolist()
     per_step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     assert torch.isfinite(out["sample"]).all()
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # ---- roofline leg (rank 0, outside the timed region): HIP events bracket every kernel launch of two more steps.
     # An event pair costs ~2 us of stream time and a step has ~2500 launches, so bracketing inside the timed region
@@ -613,6 +649,8 @@ def main():
     from dxmi_hip import _lib
     line["library"] = {"path": os.path.relpath(_lib.LIB_PATH, ROOT), "dxmi_version": int(_lib.load().dxmi_version()),
                        "selected_by_DXMI_LIB": bool(os.environ.get("DXMI_LIB"))}
+    if dumped:
+        line["dump_outputs"] = dumped
     if world > 1:
         wire = getattr(getattr(tr, "sync_sampler", None), "wire_dtype", None) if args.train_steps > 0 else None
         line["rccl"] = {"world": world, "backend": torch.distributed.get_backend(),

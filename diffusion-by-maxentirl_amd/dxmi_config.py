@@ -2,7 +2,7 @@
 (train_cifar10.py:228-259, generate_cifar10.py:119-151): YAML load, recursive merge, attribute
 access, `_target_` instantiation.  Neither omegaconf nor hydra is installed in the target image,
 and the reference's YAML files must be accepted unchanged
-(tests/test_cli_config.py loads all ten of them when the reference checkout is present)."""
+(tests/test_cli_config.py checks the scalar rules and the scripts' two-file config path)."""
 import importlib
 import re
 

@@ -1,6 +1,6 @@
 """Round-5 kernels through the C-ABI: the 16x16 AttnBlock as one launch (dxmi_attn_block_fwd: GroupNorm on load, folded
 Wk^T Wq / Wproj Wv, the raw input tile as K, V and residual) against the reference block in torch fp32
-(/root/reference models/DxMI/unet_small.py:167-191) and against the three launches it replaces."""
+(reference models/DxMI/unet_small.py:167-191) and against the three launches it replaces."""
 import pytest
 import torch
 import torch.nn.functional as F
