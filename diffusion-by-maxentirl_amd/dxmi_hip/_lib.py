@@ -60,6 +60,12 @@ SIGNATURES = {
     "dxmi_gn_ss_grads": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dxmi_fid_stats_workspace_bytes": (c_int64, [c_int64, c_int]),
     "dxmi_fid_stats": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dxmi_knn_radii_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "dxmi_knn_radii": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dxmi_pr_membership_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "dxmi_pr_membership": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dxmi_inception_score_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "dxmi_inception_score": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dxmi_packed_conv_weight_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "dxmi_pack_conv_weights": (c_int, [ctypes.POINTER(PackItem), c_int, c_void_p]),
     "dxmi_pack_conv_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

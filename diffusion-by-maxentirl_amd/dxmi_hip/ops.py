@@ -1161,6 +1161,77 @@ def fid_stats(act):
     return mu, sigma
 
 
+# ------------------------------------------------------------------------------------------ evaluator metrics
+KNN_KMAX = 7
+
+
+def _rows_f32(x, what):
+    _need_cuda(x)
+    if not (x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()):
+        raise ValueError(f"{what}: need a contiguous float32 [N, D] device tensor, got {tuple(x.shape)} {x.dtype}")
+    return x.shape
+
+
+def knn_radii(x, k=3, splits=0, workspace=None):
+    """k-NN radii of ManifoldEstimator.manifold_radii (evaluations/evaluator.py:243-280): x fp32 [N, D] (device) -> fp32 [N],
+    radii[i] = np.partition(d(x_i, x_*), k)[k] over the squared distances of x_i to every row (itself included), on the f32
+    MFMA (csrc/eval_metrics.hip).  `splits` (0: automatic) and `workspace` (a uint8 device tensor) do not change the result."""
+    N, D = _rows_f32(x, "knn_radii")
+    lib = load()
+    radii = torch.empty(N, dtype=torch.float32, device=x.device)
+    need = lib.dxmi_knn_radii_workspace_bytes(N, D, k, splits)
+    if workspace is None:
+        workspace = _workspace(max(256, need), x.device)
+    elif workspace.numel() < need:
+        raise ValueError(f"knn_radii: workspace of {workspace.numel()} bytes, need {need}")
+    _prof("eval_metrics", f"radii_d{D}", 2.0 * N * N * D, 4.0 * N * D * ((N + 127) // 128), lambda: check(
+        lib.dxmi_knn_radii(_ptr(x), N, D, k, splits, _ptr(radii), _ptr(workspace), _stream()), "dxmi_knn_radii"))
+    return radii
+
+
+def pr_membership(a, ra, b, rb):
+    """Manifold membership of ManifoldEstimator.evaluate_pr (evaluator.py:328-417): reference rows a fp32 [NA, D] with radii ra,
+    sample rows b fp32 [NB, D] with radii rb -> (a_in_b int32 [NA], b_in_a int32 [NB]) 0 / 1 flags:
+    a_in_b[i] = any_j d(a_i, b_j) <= rb[j] (its mean is the recall), b_in_a[j] = any_i d(a_i, b_j) <= ra[i] (the precision)."""
+    NA, D = _rows_f32(a, "pr_membership")
+    NB, DB = _rows_f32(b, "pr_membership")
+    if DB != D:
+        raise ValueError(f"pr_membership: feature sizes differ ({D} vs {DB})")
+    _need_cuda(ra, rb)
+    if ra.shape != (NA,) or rb.shape != (NB,) or ra.dtype != torch.float32 or rb.dtype != torch.float32:
+        raise ValueError("pr_membership: radii must be float32 [NA] and [NB]")
+    ra, rb = ra.contiguous(), rb.contiguous()
+    lib = load()
+    a_in_b = torch.empty(NA, dtype=torch.int32, device=a.device)
+    b_in_a = torch.empty(NB, dtype=torch.int32, device=a.device)
+    ws = _workspace(max(256, lib.dxmi_pr_membership_workspace_bytes(NA, NB)), a.device)
+    _prof("eval_metrics", f"member_d{D}", 2.0 * NA * NB * D, 4.0 * D * (NA * ((NB + 127) // 128) + NB * ((NA + 127) // 128)), lambda: check(
+        lib.dxmi_pr_membership(_ptr(a), NA, _ptr(ra), _ptr(b), NB, _ptr(rb), D, _ptr(a_in_b), _ptr(b_in_a), _ptr(ws), _stream()),
+        "dxmi_pr_membership"))
+    return a_in_b, b_in_a
+
+
+def inception_score_kl(pool, w, split_size=5000):
+    """Per-split mean KL of Evaluator.compute_inception_score (evaluator.py:179-193): pool fp32 [N, D], w fp32 [C, D] (fc.weight
+    layout, no bias) -> fp64 [ceil(N / split_size)] (device): mean_r sum_c p (log p - log p_bar), p = softmax(pool . w^T) in f32,
+    p_bar the split's marginal, the reductions in fp64.  The score is exp(kl).mean()."""
+    N, D = _rows_f32(pool, "inception_score")
+    C, DW = _rows_f32(w, "inception_score")
+    if DW != D:
+        raise ValueError(f"inception_score: pool has {D} features, the weight {DW}")
+    lib = load()
+    kl = torch.empty((N + split_size - 1) // split_size, dtype=torch.float64, device=pool.device)
+    ws = _workspace(max(256, lib.dxmi_inception_score_workspace_bytes(N, C, split_size)), pool.device)
+    _prof("eval_metrics", f"is_c{C}", 2.0 * N * D * C, 4.0 * (N * D + 4 * N * C), lambda: check(
+        lib.dxmi_inception_score(_ptr(pool), N, D, _ptr(w), C, split_size, _ptr(kl), _ptr(ws), _stream()), "dxmi_inception_score"))
+    return kl
+
+
+def inception_score(pool, w, split_size=5000):
+    """Inception Score: mean over splits of exp(mean KL) (float, host)."""
+    return float(torch.exp(inception_score_kl(pool, w, split_size).cpu()).mean())
+
+
 def nchw_f32_to_nhwc_bf16(x, out=None):
     _need_cuda(x, out)
     N, C, H, W = x.shape

@@ -228,3 +228,50 @@ class FIDInceptionV3(InceptionV3):
             raise DxmiError("DXMI_FID_WEIGHTS must name the FID Inception weight file (pt_inception-2015-12-05-6726825d.pth); "
                             "it cannot be downloaded into this image")
         super().__init__([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], weights=path)
+
+
+class EvalInceptionV3(InceptionV3):
+    """The feature extractor of `evaluations/evaluator.py` (the ADM evaluator's three Inception taps, reference
+    evaluations/evaluator.py:23-24, 584-616), on the FID weights named by DXMI_FID_WEIGHTS; raises without the file.
+
+    Extractor contract the evaluator relies on (a weight-free stand-in only has to meet it):
+      __call__(images)  images uint8 [B, H, W, 3] (NHWC, the `arr_0` batches of an evaluator .npz) on the device
+                        -> (pool fp32 [B, 2048], spatial fp32 [B, S]) on the device
+      softmax_weight    fp32 [2048, C] device tensor: pool . softmax_weight are the classifier logits (no bias)
+
+    pool is `pool_3:0`.  spatial is `mixed_6/conv:0[..., :7]` flattened NHWC (17 x 17 x 7 = 2023): the TF graph numbers its
+    mixed blocks mixed, mixed_1 ... mixed_10 for torchvision's Mixed_5b, 5c, 5d, 6a, 6b, 6c, 6d, 6e, 7a, 7b, 7c (eleven blocks
+    both ways; mixed_3 / Mixed_6a is the 35 -> 17 reduction and mixed_8 / Mixed_7a the 17 -> 8 one), so mixed_6 is Mixed_6d, a
+    17 x 17 block, and its `conv` is the un-prefixed first branch, the 1x1 conv + BN + ReLU that torchvision calls
+    `Mixed_6d.branch1x1` (192 channels, written first into the block's concatenation).  2023 = 17 * 17 * 7 is the sFID feature
+    size of the reference, which only a 17 x 17 tap gives.  softmax_weight is `fc.weight`^T (`softmax/logits/MatMul`'s
+    operand; the reference drops the bias, evaluator.py:603-616)."""
+
+    SPATIAL_CHANNELS = 7
+
+    def __init__(self, weights=None):
+        path = weights or os.environ.get("DXMI_FID_WEIGHTS")
+        if not path or not os.path.exists(path):
+            raise DxmiError("DXMI_FID_WEIGHTS must name the FID Inception weight file (pt_inception-2015-12-05-6726825d.pth, with "
+                            "its fc.weight); it cannot be downloaded into this image")
+        sd = torch.load(path, map_location="cpu")
+        if "fc.weight" not in sd:
+            raise DxmiError(f"{path}: no fc.weight (the Inception Score needs the classifier weight)")
+        super().__init__([InceptionV3.DEFAULT_BLOCK_INDEX], weights=sd)
+        self.softmax_weight = sd["fc.weight"].float().t().contiguous().cuda()
+        self._tap = None
+
+    def _mixed(self, pk, m, x):
+        out = super()._mixed(pk, m, x)
+        if m is self._by_name["Mixed_6d"]:
+            self._tap = out[..., :self.SPATIAL_CHANNELS].float().reshape(out.shape[0], -1)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, images):
+        if not images.is_cuda:
+            raise DxmiError("EvalInceptionV3 runs only on the HIP device path (no CPU fallback)")
+        x = images.permute(0, 3, 1, 2).float().div_(255.0)
+        pool = self.forward(x)[0].reshape(x.shape[0], -1)
+        spatial, self._tap = self._tap, None
+        return pool, spatial

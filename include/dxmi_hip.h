@@ -603,6 +603,39 @@ int dxmi_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t n_r
 int64_t dxmi_fid_stats_workspace_bytes(int64_t N, int32_t D);
 int dxmi_fid_stats(const float* act, int64_t N, int32_t D, double* mu, double* sigma, void* workspace, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Sample-quality metrics of the ADM evaluator (reference evaluations/evaluator.py), csrc/eval_metrics.hip.
+ * Every pairwise distance is d(u, v) = max((|u|^2 + |v|^2) - 2 u.v, 0) in f32, u.v a K-ordered fmaf chain on the f32-input MFMA
+ * and |u|^2 the same chain: a pair's value is bitwise the same in every kernel, tile, column split and argument order.
+ *
+ * dxmi_knn_radii: ManifoldEstimator.manifold_radii (evaluator.py:243-280, one nhood size, clamp_to_percentile=None).
+ * x fp32 [N, D] row-major -> radii fp32 [N]: radii[i] = np.partition(d(x_i, x_*), k)[k] (the self-distance 0 and duplicates
+ * count).  1 <= k <= 7, N >= k + 1.  splits: the number of column ranges the N x N work is cut into (0: automatic); the
+ * result does not depend on it.  Nothing N x N is allocated: workspace dxmi_knn_radii_workspace_bytes(N, D, k, splits)
+ * = N row norms + 2 * splits * N * (k + 1) floats.
+ * ---------------------------------------------------------------------------------------- */
+int64_t dxmi_knn_radii_workspace_bytes(int64_t N, int32_t D, int32_t k, int32_t splits);
+int dxmi_knn_radii(const float* x, int64_t N, int32_t D, int32_t k, int32_t splits, float* radii, void* workspace, void* stream);
+
+/* dxmi_pr_membership: ManifoldEstimator.evaluate_pr / DistanceBlock.less_thans (evaluator.py:328-417).  Reference set A fp32
+ * [NA, D] with radii rA [NA], sample set B fp32 [NB, D] with radii rB [NB] ->
+ *     a_in_b[i] = any_j d(a_i, b_j) <= rB[j]     (int32 0 / 1 [NA]; mean = recall)
+ *     b_in_a[j] = any_i d(a_i, b_j) <= rA[i]     (int32 0 / 1 [NB]; mean = precision)
+ * in one launch over 128 x 128 tiles of the NA x NB distances (nothing materialised).  workspace:
+ * dxmi_pr_membership_workspace_bytes(NA, NB) (the row norms of both sets). */
+int64_t dxmi_pr_membership_workspace_bytes(int64_t NA, int64_t NB);
+int dxmi_pr_membership(const float* A, int64_t NA, const float* rA, const float* B, int64_t NB, const float* rB, int32_t D,
+                       int32_t* a_in_b, int32_t* b_in_a, void* workspace, void* stream);
+
+/* dxmi_inception_score: Evaluator.compute_inception_score (evaluator.py:179-193) with the classifier weight only
+ * (`softmax/logits/MatMul`, evaluator.py:603-616: no bias).  pool fp32 [N, D], w fp32 [C, D] (fc.weight layout) ->
+ * kl_mean fp64 [ceil(N / split)] (device): for each split of `split` rows, mean_r sum_c p (log p - log p_bar) with
+ * p = softmax(pool . w^T) in f32 and p_bar the split's marginal; the sums in fp64 in a fixed order (bitwise reproducible).
+ * The score is mean_s exp(kl_mean[s]) (host).  workspace: dxmi_inception_score_workspace_bytes(N, C, split). */
+int64_t dxmi_inception_score_workspace_bytes(int64_t N, int32_t C, int32_t split);
+int dxmi_inception_score(const float* pool, int64_t N, int32_t D, const float* w, int32_t C, int32_t split, double* kl_mean,
+                         void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
