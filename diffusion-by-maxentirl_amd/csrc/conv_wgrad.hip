@@ -812,14 +812,14 @@ extern "C" int64_t dxmi_conv2d_wgrad_workspace_bytes(int32_t N, int32_t OH, int3
 }
 
 // the fixed-order reduce of the S split partials (+ the bias partials) behind every weight-gradient kernel
+// reduce: the DXMI_WGRAD_REDUCE_* variant wgrad_plan chose
 static int wgrad_reduce_launch(const WgradArgs& a, void* workspace, float* dw_oihw, float* dbias, int S, int ksize, int Cout, int Cin,
-                               int accumulate, hipStream_t st) {
-    const long total = (long)ksize * ksize * Cout * Cin;
-    const bool wide = S >= 64;                 // 16 slices of the partials per block (layers of one or two 64 x 64 blocks)
+                               int accumulate, int reduce, hipStream_t st) {
+    const bool wide = reduce == DXMI_WGRAD_REDUCE_TAPS16 || reduce == DXMI_WGRAD_REDUCE_FLAT16;   // 16 slices of the partials per block
     const int np = wide ? 16 : 64;
     const int taps = ksize * ksize;
     const int bblocks = dbias ? (Cout + 15) / 16 : 0;
-    if ((long)Cout * Cin >= 65536) {
+    if (reduce == DXMI_WGRAD_REDUCE_TAPS4 || reduce == DXMI_WGRAD_REDUCE_TAPS16) {
         // all taps of a (co, 4 ci) position per thread: contiguous OIHW runs out (>= 256 workgroups from 256 x 256 channels up)
         const long positions = (long)Cout * Cin / 4;
         const int wblocks = (int)((positions + np - 1) / np);
@@ -849,18 +849,99 @@ static int wgrad_reduce_launch(const WgradArgs& a, void* workspace, float* dw_oi
     return DXMI_OK;
 }
 
-static int wgrad_impl(const void* x0, int32_t C0, const void* x1, int32_t C1, const void* dy, float* dw_oihw, float* dbias,
-                      void* workspace, int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW, int32_t Cout,
-                      int32_t ksize, int32_t stride, int32_t pad, int32_t upsample, int32_t accumulate, void* stream) {
+// The kernel choice of one weight-gradient launch, made from the shape alone (plus the process-wide DXMI_WGRAD_* tuning
+// overrides): wgrad_impl launches what this returns and dxmi_conv2d_wgrad_plan reports it, so the two cannot disagree.
+struct WgradPlan {
+    int family;                 // DXMI_WGRAD_* kernel family (include/dxmi_hip.h)
+    int reduce;                 // DXMI_WGRAD_REDUCE_* variant of the fixed-order split reduce
+    int TWl, THl, SUBS, HH, HWd, PT, S, CIB, COB;
+    int xpieces;                // 1-KiB halo pieces per tile (DMA-staged kernels)
+};
+
+static int wgrad_plan(int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW, int32_t C0, int32_t C1, int32_t Cout, int32_t ksize,
+                      int32_t stride, int32_t pad, int32_t upsample, WgradPlan* pl) {
     DXMI_CHECK_ARG(stride == 1 || stride == 2, "dxmi_conv2d_wgrad: stride %d unsupported", stride);
-    DXMI_CHECK_ARG(x0 && dy && dw_oihw && workspace, "dxmi_conv2d_wgrad: null pointer");
     const int Cin = C0 + C1;
     DXMI_CHECK_ARG(N > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0 && C0 > 0 && C1 >= 0 && Cout > 0,
                    "dxmi_conv2d_wgrad: empty or negative shape (N %d, in %dx%dx(%d+%d), out %dx%dx%d)", N, IH, IW, C0, C1, OH, OW, Cout);
     DXMI_CHECK_ARG(ksize == 1 || ksize == 3, "dxmi_conv2d_wgrad: ksize %d unsupported", ksize);
     DXMI_CHECK_ARG(Cin % 64 == 0 && Cout % 64 == 0 && C0 % 64 == 0, "dxmi_conv2d_wgrad: Cin (%d+%d) and Cout (%d) must be multiples of 64", C0, C1, Cout);
     DXMI_CHECK_ARG((OW & (OW - 1)) == 0 && (OH & (OH - 1)) == 0 && OW >= 4 && OH >= 4, "dxmi_conv2d_wgrad: OH/OW must be powers of two >= 4");
+    const int TW = OW < 32 ? OW : 32;
+    int TH = 128 / TW; if (TH > OH) TH = OH;
+    pl->TWl = ilog2w(TW); pl->THl = ilog2w(TH); pl->SUBS = 128 / (TW * TH);
+    pl->HH = (TH - 1) * stride + ksize; pl->HWd = (TW - 1) * stride + ksize;
+    const int ngroups = (N + pl->SUBS - 1) / pl->SUBS;
+    pl->PT = ngroups * (OH / TH) * (OW / TW);
+    pl->xpieces = 0;
+    static const int b128_env = getenv("DXMI_WGRAD_B128") ? atoi(getenv("DXMI_WGRAD_B128")) : 1;     // 0: 64 x 64 blocks for every 1x1 layer
+    const long npix = (long)N * OH * OW;
+    int S;
+    if (b128_env && ksize == 1 && stride == 1 && !upsample && pad == 0 && IH == OH && IW == OW && Cin % 128 == 0 && C0 % 128 == 0 &&
+        Cout % 128 == 0 && npix % 64 == 0 && npix * (C0 > C1 ? C0 : C1) * 2 < (1L << 31) && npix * Cout * 2 < (1L << 31)) {
+        pl->family = DXMI_WGRAD_1X1_B128;
+        pl->CIB = Cin / 128; pl->COB = Cout / 128;
+        pl->PT = (int)(npix / 64);               // 64-pixel tiles
+        S = 256 / (pl->CIB * pl->COB);              // one 768-thread workgroup per CU
+    } else {
+        pl->CIB = Cin / 64; pl->COB = Cout / 64;
+        // pixel splits: the kernel holds one workgroup per CU (368 registers per lane), so 256 workgroups fill the chip; more
+        // splits only add partial-sum traffic (each split writes and the reduce re-reads taps x Cout x Cin floats)
+        // (the 1x1 kernel's single accumulator block lets two workgroups share a CU: 512 there; fewer, longer splits on the 4x4
+        // maps measured slower: 64 workgroups instead of 256)
+        static const int wgs_env = getenv("DXMI_WGRAD_WGS") ? atoi(getenv("DXMI_WGRAD_WGS")) : 0;      // tuning override
+        const int wgs = wgs_env > 0 ? wgs_env : (ksize == 3 ? 256 : 512);
+        S = wgs / (pl->CIB * pl->COB);
+        // wave-specialised DMA-staged kernel: stride 1, tile rows of >= 8 pixels, halo tile of <= 32 one-KiB pieces
+        static const int dma_env = getenv("DXMI_WGRAD_DMA") ? atoi(getenv("DXMI_WGRAD_DMA")) : 1;     // 0: register-staged kernels only
+        const int hpx = pl->SUBS * pl->HH * pl->HWd;
+        const int xpieces = (hpx + 7) / 8;
+        const bool dma = dma_env && stride == 1 && TW >= 8 && xpieces <= 32 && (long)N * IH * IW * (C0 > C1 ? C0 : C1) * 2 < (1L << 31) &&
+                         (long)N * OH * OW * Cout * 2 < (1L << 31);
+        static const int pf_env = getenv("DXMI_WGRAD_PF") ? atoi(getenv("DXMI_WGRAD_PF")) : 1;   // tuning override
+        const bool pf = pf_env && (long)hpx * 8 <= 8 * 256;   // halo pieces per thread <= 8: prefetching kernel
+        if (dma) {
+            pl->family = ksize == 3 ? DXMI_WGRAD_WS3 : DXMI_WGRAD_WS1;
+            pl->xpieces = xpieces;
+        } else if (ksize == 3) {
+            pl->family = pf ? DXMI_WGRAD_REG3_PF : DXMI_WGRAD_REG3;
+        } else {
+            pl->family = pf ? DXMI_WGRAD_REG1_PF : DXMI_WGRAD_REG1;
+        }
+        const size_t lds = (size_t)(128 + hpx) * WG_PITCH;
+        DXMI_CHECK_ARG(lds <= 160 * 1024, "dxmi_conv2d_wgrad: LDS %zu too large", lds);
+    }
+    if (S < 1) S = 1;
+    if (S > pl->PT) S = pl->PT;
+    DXMI_CHECK_ARG(S <= wgrad_split_bound(npix, Cin, Cout, ksize), "dxmi_conv2d_wgrad: %d splits exceed the workspace bound (DXMI_WGRAD_WGS?)", S);
+    pl->S = S;
+    // the fixed-order reduce: 16 slices of the partials per block for the layers of one or two 64 x 64 blocks (S >= 64), else 4;
+    // all taps of a (co, 4 ci) position per thread (contiguous OIHW runs out) from 256 x 256 channels up, else one tap per position
+    const bool wide = S >= 64;
+    pl->reduce = (long)Cout * Cin >= 65536 ? (wide ? DXMI_WGRAD_REDUCE_TAPS16 : DXMI_WGRAD_REDUCE_TAPS4)
+                                          : (wide ? DXMI_WGRAD_REDUCE_FLAT16 : DXMI_WGRAD_REDUCE_FLAT4);
+    return DXMI_OK;
+}
+
+extern "C" int dxmi_conv2d_wgrad_plan(int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW, int32_t C0, int32_t C1, int32_t Cout,
+                                      int32_t ksize, int32_t stride, int32_t pad, int32_t upsample, int32_t* out4) {
+    DXMI_CHECK_ARG(out4, "dxmi_conv2d_wgrad_plan: out4 is NULL");
+    WgradPlan pl;
+    const int rc = wgrad_plan(N, IH, IW, OH, OW, C0, C1, Cout, ksize, stride, pad, upsample, &pl);
+    if (rc != DXMI_OK) return rc;
+    out4[0] = pl.family; out4[1] = pl.S; out4[2] = pl.PT; out4[3] = pl.reduce;
+    return DXMI_OK;
+}
+
+static int wgrad_impl(const void* x0, int32_t C0, const void* x1, int32_t C1, const void* dy, float* dw_oihw, float* dbias,
+                      void* workspace, int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW, int32_t Cout,
+                      int32_t ksize, int32_t stride, int32_t pad, int32_t upsample, int32_t accumulate, void* stream) {
+    DXMI_CHECK_ARG(x0 && dy && dw_oihw && workspace, "dxmi_conv2d_wgrad: null pointer");
     DXMI_CHECK_ARG(C1 == 0 || x1, "dxmi_conv2d_wgrad: C1>0 but x1 NULL");
+    WgradPlan pl;
+    const int rc = wgrad_plan(N, IH, IW, OH, OW, C0, C1, Cout, ksize, stride, pad, upsample, &pl);
+    if (rc != DXMI_OK) return rc;
+    const int Cin = C0 + C1;
     WgradArgs a;
     static const int xcd_env = getenv("DXMI_WGRAD_XCD") ? atoi(getenv("DXMI_WGRAD_XCD")) : 1;
     // measured (tools/wgrad_time.py, same box alternating): 1x1 256 -> 768 @16x16 57.5 -> 35.7 us, 256 -> 256 28.5 -> 20.2 us, 3x3 384 -> 128
@@ -870,63 +951,28 @@ static int wgrad_impl(const void* x0, int32_t C0, const void* x1, int32_t C1, co
     a.x0 = (const bf16*)x0; a.x1 = (const bf16*)x1; a.dy = (const bf16*)dy; a.partial = (float*)workspace;
     a.N = N; a.IH = IH; a.IW = IW; a.C0 = C0; a.C1 = C1; a.OH = OH; a.OW = OW; a.Cout = Cout;
     a.ksize = ksize; a.pad = pad; a.ups = upsample ? 1 : 0; a.stride = stride;
-    const int TW = OW < 32 ? OW : 32;
-    int TH = 128 / TW; if (TH > OH) TH = OH;
-    a.TWl = ilog2w(TW); a.THl = ilog2w(TH); a.SUBS = 128 / (TW * TH);
-    a.HH = (TH - 1) * stride + ksize; a.HWd = (TW - 1) * stride + ksize;
-    const int ngroups = (N + a.SUBS - 1) / a.SUBS;
-    a.PT = ngroups * (OH / TH) * (OW / TW);
-    static const int b128_env = getenv("DXMI_WGRAD_B128") ? atoi(getenv("DXMI_WGRAD_B128")) : 1;     // 0: 64 x 64 blocks for every 1x1 layer
-    const long npix = (long)N * OH * OW;
-    if (b128_env && ksize == 1 && stride == 1 && !upsample && pad == 0 && IH == OH && IW == OW && Cin % 128 == 0 && C0 % 128 == 0 &&
-        Cout % 128 == 0 && npix % 64 == 0 && npix * (C0 > C1 ? C0 : C1) * 2 < (1L << 31) && npix * Cout * 2 < (1L << 31)) {
-        a.CIB = Cin / 128; a.COB = Cout / 128;
-        a.PT = (int)(npix / 64);               // 64-pixel tiles
-        int S = 256 / (a.CIB * a.COB);              // one 768-thread workgroup per CU
-        if (S < 1) S = 1;
-        if (S > a.PT) S = a.PT;
-        DXMI_CHECK_ARG(S <= wgrad_split_bound(npix, Cin, Cout, ksize), "dxmi_conv2d_wgrad: %d splits exceed the workspace bound", S);
-        a.S = S;
+    a.TWl = pl.TWl; a.THl = pl.THl; a.SUBS = pl.SUBS; a.HH = pl.HH; a.HWd = pl.HWd;
+    a.PT = pl.PT; a.S = pl.S; a.CIB = pl.CIB; a.COB = pl.COB;
+    const int S = pl.S;
+    hipStream_t st = (hipStream_t)stream;
+    if (pl.family == DXMI_WGRAD_1X1_B128) {
         a.bpart = dbias ? reinterpret_cast<float*>(workspace) + (size_t)S * Cout * Cin : nullptr;
-        hipStream_t st = (hipStream_t)stream;
         static bool attr = false;
         if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad1x1_b128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
         hipLaunchKernelGGL(conv_wgrad1x1_b128_kernel, dim3(S * a.CIB * a.COB), dim3(768), (size_t)4 * 4 * 64 * 128, st, a);
         DXMI_CHECK_LAUNCH("dxmi_conv2d_wgrad(1x1 b128)");
-        return wgrad_reduce_launch(a, workspace, dw_oihw, dbias, S, ksize, Cout, Cin, accumulate, st);
+        return wgrad_reduce_launch(a, workspace, dw_oihw, dbias, S, ksize, Cout, Cin, accumulate, pl.reduce, st);
     }
-    a.CIB = Cin / 64; a.COB = Cout / 64;
-    // pixel splits: the kernel holds one workgroup per CU (368 registers per lane), so 256 workgroups fill the chip; more
-    // splits only add partial-sum traffic (each split writes and the reduce re-reads taps x Cout x Cin floats)
-    // (the 1x1 kernel's single accumulator block lets two workgroups share a CU: 512 there; fewer, longer splits on the 4x4
-    // maps measured slower: 64 workgroups instead of 256)
-    static const int wgs_env = getenv("DXMI_WGRAD_WGS") ? atoi(getenv("DXMI_WGRAD_WGS")) : 0;      // tuning override
-    const int wgs = wgs_env > 0 ? wgs_env : (ksize == 3 ? 256 : 512);
-    int S = wgs / (a.CIB * a.COB);
-    if (S < 1) S = 1;
-    if (S > a.PT) S = a.PT;
-    DXMI_CHECK_ARG(S <= wgrad_split_bound(npix, Cin, Cout, ksize), "dxmi_conv2d_wgrad: %d splits exceed the workspace bound (DXMI_WGRAD_WGS?)", S);
-    a.S = S;
     a.bpart = dbias ? reinterpret_cast<float*>(workspace) + (size_t)S * ksize * ksize * Cout * Cin : nullptr;
     const size_t lds = (size_t)(128 + a.SUBS * a.HH * a.HWd) * WG_PITCH;
-    DXMI_CHECK_ARG(lds <= 160 * 1024, "dxmi_conv2d_wgrad: LDS %zu too large", lds);
-    hipStream_t st = (hipStream_t)stream;
     dim3 grid(S * a.CIB * a.COB), block(256);
-    static const int pf_env = getenv("DXMI_WGRAD_PF") ? atoi(getenv("DXMI_WGRAD_PF")) : 1;   // tuning override
-    const bool pf = pf_env && (long)a.SUBS * a.HH * a.HWd * 8 <= 8 * 256;   // halo pieces per thread <= 8: prefetching kernel
 #define DXMI_WG_LAUNCH(KS_, PF_)                                                                                              \
     do {                                                                                                                      \
         static bool attr = false;                                                                                             \
         if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<KS_, PF_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
         hipLaunchKernelGGL((conv_wgrad_kernel<KS_, PF_>), grid, block, lds, st, a);                                            \
     } while (0)
-    // wave-specialised DMA-staged kernel: stride 1, tile rows of >= 8 pixels, halo tile of <= 32 one-KiB pieces
-    static const int dma_env = getenv("DXMI_WGRAD_DMA") ? atoi(getenv("DXMI_WGRAD_DMA")) : 1;     // 0: register-staged kernels only
-    const int hpx = a.SUBS * a.HH * a.HWd;
-    const int xpieces = (hpx + 7) / 8;
-    const bool dma = dma_env && stride == 1 && TW >= 8 && xpieces <= 32 && (long)N * IH * IW * (C0 > C1 ? C0 : C1) * 2 < (1L << 31) &&
-                     (long)N * OH * OW * Cout * 2 < (1L << 31);
-    if (dma) {
+    if (pl.family == DXMI_WGRAD_WS3 || pl.family == DXMI_WGRAD_WS1) {
         static const void* zero_page = nullptr;
         if (!zero_page) {
             void* zp = nullptr;
@@ -936,6 +982,7 @@ static int wgrad_impl(const void* x0, int32_t C0, const void* x1, int32_t C1, co
             }
             zero_page = zp;
         }
+        const int xpieces = pl.xpieces;
         const int buf_bytes = 128 * 128 + xpieces * 1024;
         const size_t lds2 = 2 * (size_t)buf_bytes;
 #define DXMI_WG_DMA(KS_)                                                                                                       \
@@ -944,13 +991,15 @@ static int wgrad_impl(const void* x0, int32_t C0, const void* x1, int32_t C1, co
         if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_ws_kernel<KS_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
         hipLaunchKernelGGL((conv_wgrad_ws_kernel<KS_>), grid, dim3(512), lds2, st, a, (const char*)zero_page, xpieces, buf_bytes);    \
     } while (0)
-        if (ksize == 3) DXMI_WG_DMA(3); else DXMI_WG_DMA(1);
+        if (pl.family == DXMI_WGRAD_WS3) DXMI_WG_DMA(3); else DXMI_WG_DMA(1);
 #undef DXMI_WG_DMA
-    } else if (ksize == 3) { if (pf) DXMI_WG_LAUNCH(3, true); else DXMI_WG_LAUNCH(3, false); }
-    else { if (pf) DXMI_WG_LAUNCH(1, true); else DXMI_WG_LAUNCH(1, false); }
+    } else if (pl.family == DXMI_WGRAD_REG3_PF) DXMI_WG_LAUNCH(3, true);
+    else if (pl.family == DXMI_WGRAD_REG3) DXMI_WG_LAUNCH(3, false);
+    else if (pl.family == DXMI_WGRAD_REG1_PF) DXMI_WG_LAUNCH(1, true);
+    else DXMI_WG_LAUNCH(1, false);
 #undef DXMI_WG_LAUNCH
     DXMI_CHECK_LAUNCH("dxmi_conv2d_wgrad");
-    return wgrad_reduce_launch(a, workspace, dw_oihw, dbias, S, ksize, Cout, Cin, accumulate, st);
+    return wgrad_reduce_launch(a, workspace, dw_oihw, dbias, S, ksize, Cout, Cin, accumulate, pl.reduce, st);
 }
 
 extern "C" int dxmi_conv2d_wgrad(const void* x0, int32_t C0, const void* x1, int32_t C1, const void* dy, float* dw_oihw,

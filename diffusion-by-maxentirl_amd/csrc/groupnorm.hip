@@ -1495,6 +1495,28 @@ extern "C" int64_t dxmi_groupnorm_generic_bwd_workspace_bytes(int32_t N, int32_t
     return fused > two_launch ? fused : two_launch;
 }
 
+// Launch form of the generic backward: 0 = the reduce + apply launches, else KMAX of the one-launch form (gn_gen_bwd_fused_kernel).
+static int gn_bwd_form(int N, int HW, int C, int* wrows, int* wchunks) {
+    // knob gn_bwd_fused: 1 = where the one-launch form measured faster (maps of <= 256 pixels: every workgroup reads the image's
+    // wchunks x 32 group granules with agent-scope loads, a cost that grows with the SQUARE of the chunk count — 16 x 64x64x192:
+    // 52 chunks 85 us, 104 chunks 153 us, against 49 us for the two launches; 16 x 8x8x1536: 29 against 80 us), 2 = wherever it
+    // fits (tests), 0 = never
+    const int fused_knob = dxmi_tuning("gn_bwd_fused");
+    int kmax = (fused_knob >= 2 || (fused_knob == 1 && HW <= 256)) ? gn_fused_plan(HW, C, wrows, wchunks) : 0;
+    // ... and only while the launch is ONE round of resident workgroups (two per CU: 190 registers): it is the latency chain of a small
+    // launch that the hand-off shortens; at 256 images x 16x16x384 (1 792 workgroups) it measured 121 us against 79 us
+    if (fused_knob == 1 && (long)N * *wchunks > 512) kmax = 0;
+    // residency: the workgroups of an image wait for each other, so an image's work chunks must fit the device at one workgroup per CU
+    // whatever else holds (a 32-CU partition of the chip included); otherwise the two launches
+    if (kmax && *wchunks > dxmi_device_cus()) kmax = 0;
+    return kmax;
+}
+
+extern "C" int dxmi_groupnorm_generic_bwd_plan(int32_t N, int32_t HW, int32_t C) {
+    int wrows = 0, wchunks = 0;
+    return N > 0 && HW > 0 && C >= 8 ? gn_bwd_form(N, HW, C, &wrows, &wchunks) : 0;
+}
+
 // g_out: fp32 [2][N][C] (G0, G1 above).  dx1 / add0 / add1 / scale_shift may be NULL.
 // fwd_stats: the statistics partials the forward left at the start of ITS workspace (dxmi_groupnorm_generic_workspace_bytes of
 // them), kept by the caller — the statistics pass over the input is then skipped; NULL: recomputed here.
@@ -1523,18 +1545,7 @@ extern "C" int dxmi_groupnorm_generic_bwd_saved(const void* in0, int32_t C0, con
     a.ss_ld = ss_ld; a.N = N; a.eps = eps; a.silu = apply_silu;
     hipStream_t st = (hipStream_t)stream;
     int wrows = 0, wchunks = 0;
-    // knob gn_bwd_fused: 1 = where the one-launch form measured faster (maps of <= 256 pixels: every workgroup reads the image's
-    // wchunks x 32 group granules with agent-scope loads, a cost that grows with the SQUARE of the chunk count — 16 x 64x64x192:
-    // 52 chunks 85 us, 104 chunks 153 us, against 49 us for the two launches; 16 x 8x8x1536: 29 against 80 us), 2 = wherever it
-    // fits (tests), 0 = never
-    const int fused_knob = dxmi_tuning("gn_bwd_fused");
-    int kmax = (fused_knob >= 2 || (fused_knob == 1 && HW <= 256)) ? gn_fused_plan(HW, C, &wrows, &wchunks) : 0;
-    // ... and only while the launch is ONE round of resident workgroups (two per CU: 190 registers): it is the latency chain of a small
-    // launch that the hand-off shortens; at 256 images x 16x16x384 (1 792 workgroups) it measured 121 us against 79 us
-    if (fused_knob == 1 && (long)N * wchunks > 512) kmax = 0;
-    // residency: the workgroups of an image wait for each other, so an image's work chunks must fit the device at one workgroup per CU
-    // whatever else holds (a 32-CU partition of the chip included); otherwise the two launches
-    if (kmax && wchunks > dxmi_device_cus()) kmax = 0;
+    const int kmax = gn_bwd_form(N, HW, C, &wrows, &wchunks);
     if (kmax) {
         // one launch (gn_gen_bwd_fused_kernel) behind the node that zeroes the arrival counters
         char* base = (char*)workspace;

@@ -153,12 +153,13 @@ def conv_ws_clock_ghz():
 
 
 class PackedConvWeight:
-    """bf16 MFMA-fragment-ordered copy of an OIHW fp32 weight."""
+    """bf16 MFMA-fragment-ordered copy of an OIHW fp32 weight (transpose_flip: packed as the data-gradient weight of that conv)."""
 
-    __slots__ = ("buf", "Cout", "Cin", "ksize", "k27")
+    __slots__ = ("buf", "Cout", "Cin", "ksize", "k27", "transpose_flip")
 
-    def __init__(self, buf, Cout, Cin, ksize, k27):
+    def __init__(self, buf, Cout, Cin, ksize, k27, transpose_flip=False):
         self.buf, self.Cout, self.Cin, self.ksize, self.k27 = buf, Cout, Cin, ksize, k27
+        self.transpose_flip = bool(transpose_flip)
 
 
 _PACK_BATCH = None
@@ -266,7 +267,7 @@ def pack_conv_weight(w, transpose_flip=False, k27=False, out=None):
     else:
         check(lib.dxmi_pack_conv_weight(_ptr(w), _ptr(out), Cout, Cin, k, int(transpose_flip), int(k27), _stream()),
               "dxmi_pack_conv_weight")
-    return PackedConvWeight(out, Cout, Cin, k, k27)
+    return PackedConvWeight(out, Cout, Cin, k, k27, transpose_flip)
 
 
 class BlockStats:
@@ -515,6 +516,29 @@ def _conv2d_wgrad(x, dy, ksize, *, in1=None, pad=None, stride=1, upsample=False,
         lib.dxmi_conv2d_wgrad(_ptr(x), C0, _ptr(in1), C1, _ptr(dy), _ptr(out), _ptr(ws), N, IH, IW, OH, OW, Cout, ksize,
                               stride, pad, int(upsample), int(accumulate), _stream()), "dxmi_conv2d_wgrad"))
     return out
+
+
+WGRAD_FAMILIES = {0: "b128_1x1", 1: "ws3", 2: "ws1", 3: "reg3_pf", 4: "reg3", 5: "reg1_pf", 6: "reg1"}
+WGRAD_REDUCES = {0: "taps4", 1: "taps16", 2: "flat4", 3: "flat16"}
+WGRAD_TILE_PIXELS = {"b128_1x1": 64}          # every other family: 128-pixel tiles
+
+
+def conv2d_wgrad_plan(N, IH, IW, OH, OW, C0, C1, Cout, ksize, stride=1, pad=None, upsample=False):
+    """The kernel choice of dxmi_conv2d_wgrad for a shape (dxmi_conv2d_wgrad_plan: the launch decides through the same function)
+    -> dict(family, S, PT, reduce, tile_px); split s of the S sums the pixel tiles s, s + S, ... < PT.  Needs no device."""
+    if pad is None:
+        pad = ksize // 2
+    out = (ctypes.c_int32 * 4)()
+    check(load().dxmi_conv2d_wgrad_plan(N, IH, IW, OH, OW, C0, C1, Cout, ksize, stride, pad, int(bool(upsample)), out),
+          "dxmi_conv2d_wgrad_plan")
+    fam = WGRAD_FAMILIES[out[0]]
+    return {"family": fam, "S": out[1], "PT": out[2], "reduce": WGRAD_REDUCES[out[3]], "tile_px": WGRAD_TILE_PIXELS.get(fam, 128)}
+
+
+def groupnorm_generic_bwd_plan(N, HW, C):
+    """Launch form of groupnorm_generic_bwd for the shape under the current knobs: 0 = reduce + apply launches, 8 / 16 = the
+    one-launch form (dxmi_groupnorm_generic_bwd_plan; the device's CU count enters its residency guard)."""
+    return int(load().dxmi_groupnorm_generic_bwd_plan(N, HW, C))
 
 
 def colsum(x2d, out=None, accumulate=False):

@@ -171,6 +171,23 @@ int dxmi_conv2d_wgrad(const void* x0, int32_t C0, const void* x1, int32_t C1, co
                       float* dw_oihw, void* workspace, int32_t N, int32_t IH, int32_t IW, int32_t OH,
                       int32_t OW, int32_t Cout, int32_t ksize, int32_t stride, int32_t pad, int32_t upsample,
                       int32_t accumulate, void* stream);
+/* The kernel dxmi_conv2d_wgrad[_bias] launches for a shape (the launch makes its choice through this same function):
+ * out4 = {family, S, PT, reduce}.  S: pixel splits (partial sums added by the reduce in split order), PT: pixel tiles (128
+ * pixels, zero-padded past the last image; 64 for DXMI_WGRAD_1X1_B128), split s sums tiles s, s + S, ...  Reflects the
+ * DXMI_WGRAD_* environment overrides.  DXMI_EINVAL for the shapes the launch rejects. */
+#define DXMI_WGRAD_1X1_B128      0   /* conv_wgrad1x1_b128_kernel: 128 co x 128 ci blocks, DMA-staged 64-pixel tiles */
+#define DXMI_WGRAD_WS3           1   /* conv_wgrad_ws_kernel<3>: wave-specialised, DMA-staged */
+#define DXMI_WGRAD_WS1           2   /* conv_wgrad_ws_kernel<1> */
+#define DXMI_WGRAD_REG3_PF       3   /* conv_wgrad_kernel<3, true>: register-staged, next tile prefetched */
+#define DXMI_WGRAD_REG3          4   /* conv_wgrad_kernel<3, false> */
+#define DXMI_WGRAD_REG1_PF       5   /* conv_wgrad_kernel<1, true> */
+#define DXMI_WGRAD_REG1          6   /* conv_wgrad_kernel<1, false> */
+#define DXMI_WGRAD_REDUCE_TAPS4  0   /* wgrad_reduce_kernel<4, taps>: all taps per thread, S in 4 slices */
+#define DXMI_WGRAD_REDUCE_TAPS16 1   /* wgrad_reduce_kernel<16, taps> */
+#define DXMI_WGRAD_REDUCE_FLAT4  2   /* wgrad_reduce_flat_kernel<4> */
+#define DXMI_WGRAD_REDUCE_FLAT16 3   /* wgrad_reduce_flat_kernel<16> */
+int dxmi_conv2d_wgrad_plan(int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW, int32_t C0, int32_t C1, int32_t Cout,
+                           int32_t ksize, int32_t stride, int32_t pad, int32_t upsample, int32_t* out4);
 /* Same plus the bias gradient dbias[co] = sum_p dY[p][co] (fp32 [Cout]), summed from the dY tiles the kernel stages
  * anyway (replaces a separate column-sum pass over dY; trainer.py's loss.backward() for nn.Conv2d.bias). */
 int dxmi_conv2d_wgrad_bias(const void* x0, int32_t C0, const void* x1, int32_t C1, const void* dy, float* dw_oihw,
@@ -427,6 +444,9 @@ int dxmi_groupnorm_generic_fwd(const void* in0, int32_t C0, const void* in1, int
  * g_out fp32 [2][N][C] = per-image sums of dyy and dyy*xhat, from which the caller forms dgamma, dbeta and the FiLM
  * gradients (dscale = G1*gamma + G0*beta, dshift = G0).  Replaces autograd through models/cm/unet.py:228-260. */
 int64_t dxmi_groupnorm_generic_bwd_workspace_bytes(int32_t N, int32_t HW, int32_t C);
+/* Launch form dxmi_groupnorm_generic_bwd[_saved] takes for the shape under the current "gn_bwd_fused" knob and device:
+ * 0 = the reduce + apply launches, 8 or 16 = the one-launch form with that many rows per thread (its residency guard passed). */
+int dxmi_groupnorm_generic_bwd_plan(int32_t N, int32_t HW, int32_t C);
 int dxmi_groupnorm_generic_bwd(const void* in0, int32_t C0, const void* in1, int32_t C1, const void* dy,
                                const void* add0, const void* add1, const float* gamma, const float* beta,
                                const float* scale_shift, int32_t ss_ld, void* dx0, void* dx1, float* g_out,

@@ -1,0 +1,718 @@
+"""Every backward launch of the two training steps against an fp64 reference, at the shapes the training steps use.
+
+CASES below is the census of the backward launches of one eager iteration of each training program (tests/backward_census.py):
+the ImageNet-64 EDM step (imagenet64_T10, per-GPU batch 16, ops.throughput_tuning()) and the CIFAR-10 step (cifar10_T10 U-Net
+and value net, batch 128).  test_census_is_covered re-records the census and fails when a model change adds a launch shape the
+table does not hold.  Each row is then checked on seeded bf16 inputs against stock torch in float64 on the device (F.unfold +
+matmul for convolutions and weight gradients, softmax attention and F.group_norm under autograd), with the element-wise bounds
+of tests/backward_bounds.py; none of this project's kernels takes part in a reference.  test_report prints the largest
+|err| / bound seen per op.
+"""
+import zlib
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from backward_bounds import U16, U32, Checker, attention_bwd_ref, groupnorm_bwd_ref, unfold_nhwc, wgrad_depth, wgrad_ref
+
+DEV = "cuda:0"
+CHECK = Checker()
+
+CASES = {
+    'wgrad': [
+        # (op, x NHWC, C1, dy NHWC, k, pad, stride, upsample, accumulate, with_bias)
+        ('wgrad', (1, 4, 16, 192), 0, (1, 4, 16, 768), 1, 0, 1, 0, False, False),
+        ('wgrad', (1, 4, 16, 768), 0, (1, 4, 16, 35712), 1, 0, 1, 0, False, False),
+        ('wgrad', (1, 4, 16, 768), 0, (1, 4, 16, 768), 1, 0, 1, 0, False, False),
+        ('wgrad', (1, 8, 16, 128), 0, (1, 8, 16, 512), 1, 0, 1, 0, False, False),
+        ('wgrad', (1, 8, 16, 512), 0, (1, 8, 16, 4992), 1, 0, 1, 0, False, False),
+        ('wgrad', (1, 8, 16, 512), 0, (1, 8, 16, 512), 1, 0, 1, 0, False, False),
+        ('wgrad', (128, 16, 16, 128), 0, (128, 16, 16, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 128), 0, (128, 16, 16, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (128, 16, 16, 128), 0, (128, 16, 16, 256), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 128), 0, (128, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 256), 0, (128, 16, 16, 256), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 256), 0, (128, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 256), 0, (128, 16, 16, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 256), 0, (128, 32, 32, 256), 3, 1, 1, 1, False, True),
+        ('wgrad', (128, 16, 16, 256), 0, (128, 8, 8, 256), 3, 0, 2, 0, False, True),
+        ('wgrad', (128, 16, 16, 256), 128, (128, 16, 16, 256), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 256), 256, (128, 16, 16, 256), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 384), 0, (128, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 16, 16, 512), 0, (128, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 32, 32, 128), 0, (128, 16, 16, 128), 3, 0, 2, 0, False, True),
+        ('wgrad', (128, 32, 32, 128), 0, (128, 32, 32, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (128, 32, 32, 128), 0, (128, 32, 32, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 32, 32, 128), 0, (128, 32, 32, 64), 3, 1, 1, 0, False, False),
+        ('wgrad', (128, 32, 32, 128), 128, (128, 32, 32, 128), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 32, 32, 256), 0, (128, 32, 32, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 32, 32, 256), 128, (128, 32, 32, 128), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 32, 32, 384), 0, (128, 32, 32, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 32, 32, 64), 0, (128, 32, 32, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (128, 4, 4, 256), 0, (128, 4, 4, 256), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 4, 4, 256), 0, (128, 4, 4, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 4, 4, 256), 0, (128, 4, 4, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 4, 4, 256), 0, (128, 8, 8, 256), 3, 1, 1, 1, False, True),
+        ('wgrad', (128, 4, 4, 256), 256, (128, 4, 4, 256), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 4, 4, 512), 0, (128, 4, 4, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 8, 8, 256), 0, (128, 16, 16, 256), 3, 1, 1, 1, False, True),
+        ('wgrad', (128, 8, 8, 256), 0, (128, 4, 4, 256), 3, 0, 2, 0, False, True),
+        ('wgrad', (128, 8, 8, 256), 0, (128, 8, 8, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (128, 8, 8, 256), 0, (128, 8, 8, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (128, 8, 8, 256), 256, (128, 8, 8, 256), 1, 0, 1, 0, False, True),
+        ('wgrad', (128, 8, 8, 512), 0, (128, 8, 8, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 1152), 0, (16, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 1344), 0, (16, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 256), 0, (16, 16, 16, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (16, 16, 16, 256), 0, (16, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 384), 0, (16, 16, 16, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 384), 0, (16, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 384), 0, (16, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 576), 0, (16, 16, 16, 1728), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 576), 0, (16, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 576), 0, (16, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 576), 0, (16, 32, 32, 576), 3, 1, 1, 1, False, True),
+        ('wgrad', (16, 16, 16, 576), 384, (16, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 576), 576, (16, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 768), 0, (16, 16, 16, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 768), 576, (16, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 16, 16, 960), 0, (16, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 128), 0, (16, 32, 32, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 128), 0, (16, 32, 32, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (16, 32, 32, 128), 0, (16, 32, 32, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 192), 0, (16, 32, 32, 192), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 192), 0, (16, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 192), 0, (16, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 256), 0, (16, 32, 32, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 384), 0, (16, 32, 32, 1152), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 384), 0, (16, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 384), 0, (16, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 384), 0, (16, 64, 64, 384), 3, 1, 1, 1, False, True),
+        ('wgrad', (16, 32, 32, 384), 192, (16, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 384), 384, (16, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 576), 0, (16, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 576), 0, (16, 32, 32, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 576), 384, (16, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 768), 0, (16, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 32, 32, 960), 0, (16, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 128), 0, (16, 64, 64, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (16, 64, 64, 128), 0, (16, 64, 64, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 192), 0, (16, 64, 64, 192), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 192), 0, (16, 64, 64, 64), 3, 1, 1, 0, False, False),
+        ('wgrad', (16, 64, 64, 192), 192, (16, 64, 64, 192), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 384), 0, (16, 64, 64, 192), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 384), 0, (16, 64, 64, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 384), 192, (16, 64, 64, 192), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 576), 0, (16, 64, 64, 192), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 64, 64, 64), 0, (16, 64, 64, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (16, 64, 64, 64), 0, (16, 64, 64, 192), 1, 0, 1, 0, False, False),
+        ('wgrad', (16, 8, 8, 1344), 0, (16, 8, 8, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 1536), 0, (16, 8, 8, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 256), 0, (16, 8, 8, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 576), 0, (16, 8, 8, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 576), 0, (16, 8, 8, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 576), 0, (16, 8, 8, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 768), 0, (16, 16, 16, 768), 3, 1, 1, 1, False, True),
+        ('wgrad', (16, 8, 8, 768), 0, (16, 8, 8, 2304), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 768), 0, (16, 8, 8, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 768), 0, (16, 8, 8, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 768), 576, (16, 8, 8, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (16, 8, 8, 768), 768, (16, 8, 8, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (256, 16, 16, 128), 0, (256, 16, 16, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (256, 16, 16, 128), 0, (256, 16, 16, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (256, 16, 16, 128), 0, (256, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (256, 16, 16, 256), 0, (256, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (256, 32, 32, 128), 0, (256, 32, 32, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (256, 32, 32, 128), 0, (256, 32, 32, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (256, 32, 32, 64), 0, (256, 32, 32, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (256, 4, 4, 256), 0, (256, 4, 4, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (256, 8, 8, 256), 0, (256, 8, 8, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (256, 8, 8, 256), 0, (256, 8, 8, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 256), 0, (32, 16, 16, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (32, 16, 16, 256), 0, (32, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 128), 0, (32, 32, 32, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 128), 0, (32, 32, 32, 256), 1, 0, 1, 0, False, False),
+        ('wgrad', (32, 32, 32, 128), 0, (32, 32, 32, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 256), 0, (32, 32, 32, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 128), 0, (32, 64, 64, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (32, 64, 64, 128), 0, (32, 64, 64, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 64), 0, (32, 64, 64, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (32, 8, 8, 256), 0, (32, 8, 8, 256), 3, 1, 1, 0, False, True),
+    ],
+    'stem_wgrad': [
+        # (op, x NCHW, dy NHWC)
+        ('stem_wgrad', (128, 3, 32, 32), (128, 32, 32, 128)),
+        ('stem_wgrad', (16, 3, 64, 64), (16, 64, 64, 128)),
+        ('stem_wgrad', (16, 3, 64, 64), (16, 64, 64, 192)),
+        ('stem_wgrad', (256, 3, 32, 32), (256, 32, 32, 128)),
+        ('stem_wgrad', (32, 3, 64, 64), (32, 64, 64, 128)),
+    ],
+    'linear_bwd': [
+        # (op, x [P, K], dy [P, M], need_dx)
+        ('linear_bwd', (128, 128), (128, 512), False),
+        ('linear_bwd', (128, 512), (128, 4992), True),
+        ('linear_bwd', (128, 512), (128, 512), True),
+        ('linear_bwd', (16, 192), (16, 768), False),
+        ('linear_bwd', (16, 768), (16, 35712), True),
+        ('linear_bwd', (16, 768), (16, 768), True),
+    ],
+    'conv2d': [
+        # (op, x NHWC, C1, Cout, k, transpose-flipped pack, stride, pad, pad_br, upsample, residual, mask_src, bias, act, out_nchw_f32)
+        ('conv2d', (128, 16, 16, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (128, 16, 16, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 128), 0, 128, 3, True, 1, 2, 0, 2, False, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 128, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 128, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 256, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 256), 0, 512, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 16, 16, 768), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 128, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 256, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 256, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 128), 0, 3, 3, True, 1, 1, None, 0, False, False, False, 0, True),
+        ('conv2d', (128, 32, 32, 128), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 256), 0, 256, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 32, 32, 64), 0, 128, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 4, 4, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 4, 4, 256), 0, 256, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 4, 4, 256), 0, 256, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 4, 4, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (128, 4, 4, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 4, 4, 256), 0, 256, 3, True, 1, 2, 0, 2, False, False, False, 0, False),
+        ('conv2d', (128, 4, 4, 256), 0, 512, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 4, 4, 768), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 8, 8, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 8, 8, 256), 0, 256, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (128, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (128, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (128, 8, 8, 256), 0, 256, 3, True, 1, 2, 0, 2, False, False, False, 0, False),
+        ('conv2d', (128, 8, 8, 256), 0, 512, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 1728), 0, 576, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (16, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 384), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 1152, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 1344, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 384, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 576, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 576, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 768, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 576), 0, 960, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 16, 16, 768), 0, 768, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 1152), 0, 384, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (16, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 192), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 256), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 256), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 192, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 384, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 384, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 576, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 768, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 384), 0, 960, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 32, 32, 576), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 128), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (16, 64, 64, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 128), 0, 3, 3, True, 1, 1, None, 0, False, False, False, 0, True),
+        ('conv2d', (16, 64, 64, 192), 0, 192, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 192), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 192), 0, 384, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 192), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 192), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 384), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 64, 64, 64), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 2304), 0, 768, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (16, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 576), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 768), 0, 1344, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 768), 0, 1536, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 768), 0, 576, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 768), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 768), 0, 768, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 768), 0, 768, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (16, 8, 8, 768), 0, 768, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (256, 16, 16, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (256, 16, 16, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (256, 16, 16, 256), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (256, 16, 16, 256), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (256, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (256, 32, 32, 128), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (256, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (256, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (256, 4, 4, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (256, 4, 4, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (256, 8, 8, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (256, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (256, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (32, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (32, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 256), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 256), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (32, 64, 64, 128), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (32, 64, 64, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (32, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+    ],
+    'groupnorm_generic_bwd': [
+        # (op, x NHWC, C1, add0, add1, groups, silu, scale_shift, fwd_stats)
+        ('groupnorm_generic_bwd', (128, 16, 16, 256), 128, False, False, 32, True, False, False),
+        ('groupnorm_generic_bwd', (128, 32, 32, 256), 128, False, False, 32, True, False, False),
+        ('groupnorm_generic_bwd', (16, 16, 16, 384), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 384), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 576), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 576), 0, True, False, 32, False, False, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 576), 0, True, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 576), 384, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 576), 576, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 768), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 16, 16, 768), 576, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 192), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 192), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 384), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 384), 0, True, False, 32, False, False, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 384), 0, True, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 384), 192, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 384), 384, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 576), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 32, 32, 576), 384, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 64, 64, 192), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 64, 64, 192), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 64, 64, 192), 0, True, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 64, 64, 192), 192, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 64, 64, 384), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 64, 64, 384), 192, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 8, 8, 576), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 8, 8, 576), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 8, 8, 768), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (16, 8, 8, 768), 0, True, False, 32, False, False, False),
+        ('groupnorm_generic_bwd', (16, 8, 8, 768), 0, True, False, 32, True, False, False),
+        ('groupnorm_generic_bwd', (16, 8, 8, 768), 576, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (16, 8, 8, 768), 768, False, False, 32, True, False, False),
+    ],
+    'groupnorm_silu_bwd': [
+        # (op, x NHWC, C1, add0, add1, groups, silu, scale_shift, fwd_stats)
+        ('groupnorm_silu_bwd', (128, 16, 16, 128), 0, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 16, 16, 256), 0, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 16, 16, 256), 0, True, False, 32, False, False, False),
+        ('groupnorm_silu_bwd', (128, 16, 16, 256), 0, True, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 16, 16, 256), 128, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 16, 16, 256), 256, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 32, 32, 128), 0, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 32, 32, 128), 0, True, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 32, 32, 128), 128, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 32, 32, 256), 128, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 4, 4, 256), 0, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 4, 4, 256), 0, True, False, 32, False, False, False),
+        ('groupnorm_silu_bwd', (128, 4, 4, 256), 0, True, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 4, 4, 256), 256, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 8, 8, 256), 0, False, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 8, 8, 256), 0, True, False, 32, True, False, False),
+        ('groupnorm_silu_bwd', (128, 8, 8, 256), 256, False, False, 32, True, False, False),
+    ],
+    'attention_bwd': [
+        # (op, qkv [N, T, 3C], heads, o, lse)
+        ('attention_bwd', (128, 16, 768), 1, False, False),
+        ('attention_bwd', (128, 256, 768), 1, False, False),
+        ('attention_bwd', (16, 1024, 1152), 6, True, True),
+        ('attention_bwd', (16, 256, 1728), 9, True, True),
+        ('attention_bwd', (16, 64, 2304), 12, True, True),
+    ],
+    'colsum': [
+        # (op, x, accumulate)
+        ('colsum', (128, 32, 32, 128), False),
+        ('colsum', (16, 64, 64, 128), False),
+        ('colsum', (16, 64, 64, 192), False),
+        ('colsum', (256, 32, 32, 128), False),
+        ('colsum', (32, 64, 64, 128), False),
+    ],
+    'colsum_per_image': [
+        # (op, x NHWC)
+        ('colsum_per_image', (128, 16, 16, 256)),
+        ('colsum_per_image', (128, 32, 32, 128)),
+        ('colsum_per_image', (128, 4, 4, 256)),
+        ('colsum_per_image', (128, 8, 8, 256)),
+    ],
+    'pool_act_bwd': [
+        # (op, dout NHWC, pool)
+        ('pool_act_bwd', (128, 16, 16, 128), False),
+        ('pool_act_bwd', (128, 16, 16, 128), True),
+        ('pool_act_bwd', (128, 32, 32, 128), False),
+        ('pool_act_bwd', (128, 4, 4, 256), False),
+        ('pool_act_bwd', (128, 4, 4, 256), True),
+        ('pool_act_bwd', (128, 8, 8, 256), False),
+        ('pool_act_bwd', (128, 8, 8, 256), True),
+        ('pool_act_bwd', (16, 16, 16, 256), False),
+        ('pool_act_bwd', (16, 16, 16, 256), True),
+        ('pool_act_bwd', (16, 32, 32, 128), False),
+        ('pool_act_bwd', (16, 32, 32, 128), True),
+        ('pool_act_bwd', (16, 64, 64, 128), False),
+        ('pool_act_bwd', (16, 8, 8, 256), False),
+        ('pool_act_bwd', (16, 8, 8, 256), True),
+        ('pool_act_bwd', (256, 16, 16, 128), False),
+        ('pool_act_bwd', (256, 16, 16, 128), True),
+        ('pool_act_bwd', (256, 32, 32, 128), False),
+        ('pool_act_bwd', (256, 4, 4, 256), False),
+        ('pool_act_bwd', (256, 4, 4, 256), True),
+        ('pool_act_bwd', (256, 8, 8, 256), False),
+        ('pool_act_bwd', (256, 8, 8, 256), True),
+        ('pool_act_bwd', (32, 16, 16, 256), False),
+        ('pool_act_bwd', (32, 16, 16, 256), True),
+        ('pool_act_bwd', (32, 32, 32, 128), False),
+        ('pool_act_bwd', (32, 32, 32, 128), True),
+        ('pool_act_bwd', (32, 64, 64, 128), False),
+        ('pool_act_bwd', (32, 8, 8, 256), False),
+        ('pool_act_bwd', (32, 8, 8, 256), True),
+    ],
+}
+
+# 1x1 / 3x3 weight-gradient shapes outside the training steps that reach the register-staged families the census does not
+# (4x4-wide maps, stride-2 1x1): every family the plan query can return is launched by some case
+EXTRA_WGRAD = [
+    ("wgrad", (8, 4, 4, 192), 0, (8, 4, 4, 128), 1, 0, 1, 0, False, True),          # conv_wgrad_kernel<1, true>
+    ("wgrad", (4, 64, 64, 192), 0, (4, 32, 32, 128), 1, 0, 2, 0, False, True),      # conv_wgrad_kernel<1, false>
+    ("wgrad", (6, 8, 4, 128), 64, (6, 8, 4, 128), 3, 1, 1, 0, False, True),          # conv_wgrad_kernel<3, true>
+]
+ALL_FAMILIES = {"b128_1x1", "ws3", "ws1", "reg3_pf", "reg3", "reg1_pf", "reg1"}
+
+
+def _plan(ops, r):
+    _, xs, c1, dys, k, pad, stride, ups, _, _ = r
+    N, IH, IW, C0 = xs
+    _, OH, OW, Co = dys
+    return ops.conv2d_wgrad_plan(N, IH, IW, OH, OW, C0, c1, Co, k, stride, pad, ups)
+
+
+def _id(r):
+    return "-".join(str(v).replace(" ", "") for v in r[1:])
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from dxmi_hip import ops as o
+    return o
+
+
+def bf(t):
+    return t.to(torch.bfloat16)
+
+
+def rnd(g, *shape, scale=1.0):
+    return torch.randn(*shape, generator=g, device=DEV) * scale
+
+
+def test_table_reaches_every_wgrad_family(ops):
+    """The cases launch every family dxmi_conv2d_wgrad_plan can return; the training steps themselves reach these four."""
+    fam_train = {_plan(ops, r)["family"] for r in CASES["wgrad"]}
+    assert {"b128_1x1", "ws1", "ws3", "reg3"} <= fam_train
+    fam_all = fam_train | {_plan(ops, r)["family"] for r in EXTRA_WGRAD}
+    assert fam_all == ALL_FAMILIES, fam_all
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["imagenet64", "cifar10"])
+def test_census_is_covered(ops, which):
+    import backward_census
+    ops.device_check()
+    rows = backward_census.record(ops, which)
+    table = {r for v in CASES.values() for r in v if not isinstance(r, str)}
+    missing = sorted(rows - table, key=repr)
+    assert not missing, f"{which}: backward launches not in CASES (add them): {missing}"
+    assert {r[0] for r in rows} >= {"wgrad", "conv2d", "stem_wgrad", "linear_bwd", "attention_bwd", "colsum", "pool_act_bwd"}
+    torch.cuda.empty_cache()
+
+
+# ------------------------------------------------------------------------------------------ weight gradients
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["wgrad"] + EXTRA_WGRAD, ids=_id)
+def test_wgrad(ops, r):
+    """dW (and db) of dxmi_conv2d_wgrad[_bias] element by element within c * u32 * sum|dy||x|, c from the plan's chain
+    length; accumulate=True must give bitwise twice the first result."""
+    _, xs, c1, dys, k, pad, stride, ups, _, with_bias = r
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    x0 = bf(rnd(g, *xs))
+    x1 = bf(rnd(g, *xs[:3], c1, scale=2.0)) if c1 else None
+    dy = bf(rnd(g, *dys))
+    plan = _plan(ops, r)
+    c = wgrad_depth(plan)
+    xc = torch.cat([x0, x1], 3) if c1 else x0
+    ref, A = wgrad_ref(xc, dy, k, stride, pad, ups)
+    tag = f"wgrad[{plan['family']}]"
+    if with_bias:
+        dw, db = ops._conv2d_wgrad(x0, dy, k, in1=x1, pad=pad, stride=stride, upsample=bool(ups), with_bias=True)
+        d = dy.double().reshape(-1, dy.shape[3])
+        CHECK.fp32("wgrad_db", db, d.sum(0), d.abs().sum(0), c)
+    else:
+        dw = ops._conv2d_wgrad(x0, dy, k, in1=x1, pad=pad, stride=stride, upsample=bool(ups))
+    CHECK.fp32(tag, dw, ref, A, c)
+    acc = dw.clone()
+    ops._conv2d_wgrad(x0, dy, k, in1=x1, pad=pad, stride=stride, upsample=bool(ups), out=acc, accumulate=True)
+    torch.cuda.synchronize()
+    assert torch.equal(acc, dw * 2), "accumulate=True is not bitwise 2x the first result"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["stem_wgrad"], ids=_id)
+def test_stem_conv_wgrad(ops, r):
+    _, xs, dys = r
+    g = torch.Generator(device=DEV).manual_seed(7)
+    x = rnd(g, *xs)
+    dy = bf(rnd(g, *dys))
+    N, _, H, W = xs
+    got = ops.stem_conv_wgrad(x, dy)
+    xb = bf(x).permute(0, 2, 3, 1)                              # the im2col operand is the bf16-rounded image
+    ref, A = wgrad_ref(xb, dy, 3)
+    plan = ops.conv2d_wgrad_plan(N, H, W, H, W, 64, 0, dys[3], 1)
+    CHECK.fp32("stem_wgrad", got, ref, A, wgrad_depth(plan))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["linear_bwd"], ids=_id)
+def test_linear_bwd(ops, r):
+    """linear_bwd at the emb_layers / temb MLP sizes: dW through the 1x1 weight gradient on zero-padded rows, dx through the
+    transposed-pack linear (bf16 operands, fp32 out), db."""
+    _, xs, dys, need_dx = r
+    P, K = xs
+    M = dys[1]
+    g = torch.Generator(device=DEV).manual_seed(11)
+    x = rnd(g, P, K)
+    dy = rnd(g, P, M, scale=0.1)
+    W = rnd(g, M, K, scale=K ** -0.5)
+    pw_t = ops.pack_conv_weight(W, transpose_flip=True) if need_dx else None
+    dx, dw, db = ops.linear_bwd(x, dy, pw_t, need_dx=need_dx)
+    xb, dyb = bf(x).double(), bf(dy).double()
+    rows = 64
+    while rows < P:
+        rows *= 2
+    plan = ops.conv2d_wgrad_plan(1, rows // 16, 16, rows // 16, 16, K, 0, M, 1)
+    CHECK.fp32("linear_bwd_dw", dw, dyb.T @ xb, dyb.abs().T @ xb.abs(), wgrad_depth(plan))
+    # db is dy.sum(0), a stock torch reduction inside linear_bwd (no project kernel): checked, not reported as kernel coverage
+    Checker().fp32("linear_bwd_db", db, dy.double().sum(0), dy.double().abs().sum(0), P + 2)
+    if need_dx:
+        Wb = bf(W).double()
+        CHECK.fp32("linear_bwd_dx", dx, dyb @ Wb, dyb.abs() @ Wb.abs(), 2 * M + 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["colsum"] + CASES["colsum_per_image"], ids=_id)
+def test_colsums(ops, r):
+    g = torch.Generator(device=DEV).manual_seed(13)
+    x = bf(rnd(g, *r[1]))
+    N, H, W, C = x.shape
+    xd = x.double()
+    if r[0] == "colsum":
+        got = ops.colsum(x)
+        CHECK.fp32("colsum", got, xd.reshape(-1, C).sum(0), xd.abs().reshape(-1, C).sum(0), N * H * W + 2)
+    else:
+        got = ops.colsum_per_image(x)
+        CHECK.fp32("colsum_per_image", got, xd.sum((1, 2)), xd.abs().sum((1, 2)), H * W + 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["pool_act_bwd"], ids=_id)
+def test_pool_act_bwd(ops, r):
+    """Value-net pool / LeakyReLU backward: din = (pool ? 0.25 * nearest-x2(g) : g), g = dout * (act_out > 0 ? 1 : 0.2), element
+    by element: one fp32 product, one bf16 rounding."""
+    _, ds, pool = r
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    dout = bf(rnd(g, *ds))
+    act = bf(rnd(g, *ds))
+    got = ops.pool_act_bwd(dout, act, pool, 0.2)
+    ref = dout.double() * torch.where(act > 0, 1.0, 0.2).double()
+    if pool:
+        ref = 0.25 * ref.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    CHECK.bf16("pool_act_bwd", got, ref, ref.abs(), 2)
+
+
+# ------------------------------------------------------------------------------------------ data gradients
+def conv_ref(x, Wt, stride, pad, pad_br, ups, residual, mask, slope):
+    """fp64 conv of the data-gradient launch: x NHWC, Wt [Cout, Cin, k, k] (the transpose-flipped forward weight)."""
+    k = Wt.shape[2]
+    xd = x.double()
+    if ups == 1:
+        xd = xd.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    elif ups == 2:
+        z = torch.zeros(xd.shape[0], 2 * xd.shape[1], 2 * xd.shape[2], xd.shape[3], dtype=xd.dtype, device=xd.device)
+        z[:, ::2, ::2] = xd
+        xd = z
+    N, VH, VW, _ = xd.shape
+    pb = pad if pad_br is None else pad_br
+    OH, OW = (VH + pad + pb - k) // stride + 1, (VW + pad + pb - k) // stride + 1
+    cols = unfold_nhwc(xd, k, stride, pad, pb)                    # [N, Cin*k*k, OH*OW]
+    Wm = Wt.double().reshape(Wt.shape[0], -1)
+    out = torch.einsum("ok,nkp->npo", Wm, cols).reshape(N, OH, OW, -1)
+    A = torch.einsum("ok,nkp->npo", Wm.abs(), cols.abs()).reshape(N, OH, OW, -1)
+    if residual is not None:
+        out, A = out + residual.double(), A + residual.double().abs()
+    if mask is not None:
+        f = torch.where(mask > 0, 1.0, slope).double()
+        out, A = out * f, A * f
+    return out, A
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tuning", ["default", "throughput"])
+@pytest.mark.parametrize("r", CASES["conv2d"], ids=_id)
+def test_conv_dgrad(ops, r, tuning):
+    """The data-gradient convs (transpose-flipped packs, residual / activation-mask epilogues, zero-stuffed stride-2 transposes)
+    element by element: c = Cin * k * k + 2, one bf16 rounding of the output.  The pack is made the way the census saw it
+    (transpose-flipped or plain)."""
+    _, xs, c1, Cout, k, tflip, stride, pad, pad_br, ups, has_res, has_mask, has_bias, act, nchw = r
+    assert c1 == 0 and not has_bias and act == 0
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    x = bf(rnd(g, *xs))
+    Cin = xs[3]
+    if tflip:
+        Wf = rnd(g, Cin, Cout, k, k, scale=(Cin * k * k) ** -0.5)  # the forward layer's weight [Cin_dg, Cout_dg, k, k]
+        Wt = bf(Wf).float().transpose(0, 1).flip(2, 3)           # its transpose-flip: the weight of this launch
+    else:
+        Wf = rnd(g, Cout, Cin, k, k, scale=(Cin * k * k) ** -0.5)
+        Wt = bf(Wf).float()
+    pw = ops.pack_conv_weight(Wf, transpose_flip=tflip)
+    assert pw.transpose_flip == tflip
+    N, IH, IW, _ = xs
+    VH, VW = (2 * IH, 2 * IW) if ups else (IH, IW)
+    pb = pad if pad_br is None else pad_br
+    OH, OW = (VH + pad + pb - k) // stride + 1, (VW + pad + pb - k) // stride + 1
+    res = bf(rnd(g, N, OH, OW, Cout)) if has_res else None
+    mask = bf(rnd(g, N, OH, OW, Cout)) if has_mask else None
+    kw = dict(stride=stride, pad=pad, pad_br=pad_br, upsample=ups, residual=res, mask_src=mask, mask_slope=0.2, out_nchw_f32=nchw)
+    if tuning == "throughput":
+        with ops.throughput_tuning():
+            got = ops.conv2d(x, pw, **kw)
+    else:
+        got = ops.conv2d(x, pw, **kw)
+    ref, A = conv_ref(x, Wt, stride, pad, pad_br, ups, res, mask, 0.2)
+    c = Cin * k * k + 2
+    if nchw:
+        CHECK.fp32("conv_dgrad_f32", got.permute(0, 2, 3, 1), ref, A, c)
+    else:
+        CHECK.bf16("conv_dgrad", got, ref, A, c)
+
+
+# ------------------------------------------------------------------------------------------ GroupNorm
+def _gn_case(ops, r, form):
+    op, xs, c1, has_add0, has_add1, groups, silu, has_ss, has_saved = r
+    N, H, W, C0 = xs
+    C = C0 + c1
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    x0 = bf(rnd(g, *xs) * 1.5 + 0.25)
+    x1 = bf(rnd(g, N, H, W, c1)) if c1 else None
+    dy = bf(rnd(g, N, H, W, C))
+    gamma, beta = 1 + 0.3 * rnd(g, C), 0.3 * rnd(g, C)
+    add0 = bf(rnd(g, N, H, W, C0)) if has_add0 else None
+    add1 = bf(rnd(g, N, H, W, c1)) if has_add1 else None
+    ss = (0.3 * rnd(g, N, 3 * C))[:, C // 2: C // 2 + 2 * C] if has_ss else None     # a row-strided slice, as emb_all's
+    eps = 1e-5 if op == "groupnorm_generic_bwd" else 1e-6
+    kw = dict(in1=x1, add0=add0, add1=add1, groups=groups, eps=eps, silu=silu)
+    if op == "groupnorm_generic_bwd":
+        saved = []
+        if has_saved:
+            ops.groupnorm_generic(x0, gamma, beta, in1=x1, groups=groups, eps=eps, silu=silu, scale_shift=ss, saved=saved)
+        dx0, dx1, dg, db, dss = ops.groupnorm_generic_bwd(x0, dy, gamma, beta, scale_shift=ss, fwd_stats=saved[0] if saved else None, **kw)
+    else:
+        dx0, dx1, dg, db = ops.groupnorm_silu_bwd(x0, dy, gamma, beta, **kw)
+        dss = None
+    xc = torch.cat([x0, x1], 3) if c1 else x0
+    addc = None
+    if has_add0 or has_add1:
+        addc = torch.cat([add0 if add0 is not None else torch.zeros_like(x0), add1 if add1 is not None else torch.zeros_like(x1)], 3) \
+            if c1 else add0
+    (rdx, rdg, rdb, rdss), (Adx, Adg, Adb, Ass) = groupnorm_bwd_ref(xc, dy, gamma, beta, groups, eps, silu, scale_shift=ss, add=addc)
+    cpg = C // groups
+    tag = f"{op}[{form}]"
+    dx = torch.cat([dx0, dx1], 3) if c1 else dx0
+    CHECK.bf16(tag + "_dx", dx, rdx, Adx, H * W * cpg + 16)
+    CHECK.fp32(tag + "_dgamma", dg, rdg, Adg, N * H * W + 16)
+    CHECK.fp32(tag + "_dbeta", db, rdb, Adb, N * H * W + 16)
+    if has_ss:
+        CHECK.fp32(tag + "_dscale_shift", dss, rdss, Ass, H * W + 16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["groupnorm_generic_bwd"] + CASES["groupnorm_silu_bwd"], ids=_id)
+def test_groupnorm_bwd(ops, r):
+    """dx (both concat sources, fused adds), dgamma, dbeta and the FiLM scale-shift gradient; the generic backward on every
+    launch form its residency guard allows for the shape (knob gn_bwd_fused 0: two launches, 2: one launch where it fits)."""
+    N, H, W, C0 = r[1]
+    C = C0 + r[2]
+    if r[0] == "groupnorm_silu_bwd":
+        _gn_case(ops, r, "resident")
+        return
+    old = ops.get_tuning("gn_bwd_fused")
+    try:
+        forms = []
+        for knob in (0, 2):
+            ops.set_tuning("gn_bwd_fused", knob)
+            f = ops.groupnorm_generic_bwd_plan(N, H * W, C)
+            if f not in forms:
+                forms.append(f)
+                _gn_case(ops, r, "one-launch" if f else "two-launch")
+        assert 0 in forms
+    finally:
+        ops.set_tuning("gn_bwd_fused", old)
+
+
+# ------------------------------------------------------------------------------------------ attention
+ATTN_EXTRA = [("attention_bwd", (16, 1024, 1152), 6, True, True), ("attention_bwd", (16, 256, 1728), 9, True, True),
+              ("attention_bwd", (16, 64, 2304), 12, True, True)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", sorted(set(CASES["attention_bwd"]) | set(ATTN_EXTRA), key=repr), ids=_id)
+def test_attention_bwd(ops, r):
+    """dqkv per (image, q|k|v, head, 128-row block) within rel-L2 8 u16: P and dS are bf16 MFMA operands in the kernels, so the
+    bound is per block at the kernel's tile size rather than per element.  With lse: the training path (o and the forward's
+    log-sum-exp handed over)."""
+    _, qs, heads, with_o, with_lse = r
+    N, T, C3 = qs
+    C = C3 // 3
+    D = C // heads
+    scale = D ** -0.5
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    qkv = bf(rnd(g, N, T, C3))
+    do = bf(rnd(g, N, T, C))
+    ref, o64 = attention_bwd_ref(qkv, do, heads, scale)
+    if with_lse:
+        o, lse = ops.attention(qkv, heads, scale, want_lse=True)
+        got = ops.attention_bwd(qkv, do, heads, scale, o=o, lse=lse)
+    elif with_o:
+        got = ops.attention_bwd(qkv, do, heads, scale, o=bf(o64))
+    else:
+        got = ops.attention_bwd(qkv, do, heads, scale)
+    rb = 128 if T >= 128 else T
+    blk = lambda d: d.reshape(N, T // rb, rb, 3, heads, D).permute(0, 3, 4, 1, 2, 5)
+    CHECK.blocks(f"attention_bwd[T{T},h{heads}{',lse' if with_lse else ''}]", blk(got), blk(ref), 8 * U16, 4)
+
+
+@pytest.mark.gpu
+def test_report():
+    """Largest |err| / bound per op over the cases above (printed; run with -s)."""
+    for k, v in CHECK.report().items():
+        print(f"{k:48s} {v:.4f}")

@@ -506,6 +506,48 @@ def test_pack_plan_replay_equals_a_fresh_pack(ops, tag):
         assert torch.equal(replayed[k], fresh[k]), k
 
 
+def test_imagenet64_unet_backward_full_size_vs_oracle():
+    """Every parameter gradient of the full configs/imagenet64 network (295.9M parameters, 64x64, N = 2) against torch autograd
+    through the pinned oracle on the CPU in fp32, with the bound of the shrunken-net test: 2 x the oracle's own bf16-storage-model
+    noise floor + 1.5e-2 per parameter tensor.  The only check that the per-launch results are put together into the right
+    parameter gradients at full size (concatenated skip sources, emb_layers rows, accumulation across res blocks)."""
+    import time
+    from oracle import Precision, edm
+    t0 = time.perf_counter()
+    net, _, sd = build(IMAGENET64_KW)
+    g = torch.Generator().manual_seed(18)
+    x = torch.randn(2, 3, 64, 64, generator=g)
+    t = torch.tensor([700.0, -900.0])
+    y = torch.tensor([5, 321])
+    w_out = torch.randn(2, 3, 64, 64, generator=g)
+    for p in net.parameters():
+        p.requires_grad_(True)
+    out = net(x.to(DEV), t.to(DEV), y=y.to(DEV))
+    assert out.requires_grad
+    (out * w_out.to(DEV)).sum().backward()
+    torch.cuda.synchronize()
+    t_dev = time.perf_counter() - t0
+    ref = {}
+    for mode in ("fp32", "bf16"):
+        leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+        yo = edm.unet_forward(leaves, edm.EDMConfig(), x, t, prec=Precision(mode), y=y)
+        (yo * w_out).sum().backward()
+        ref[mode] = {k: leaves[k].grad for k in leaves}
+        del leaves, yo
+    P = dict(net.named_parameters())
+    assert len(P) == len(ref["fp32"])
+    worst = ("", 0.0)
+    for k, p in P.items():
+        assert p.grad is not None and p.grad.shape == ref["fp32"][k].shape, k
+        r = rel_l2(p.grad.cpu(), ref["fp32"][k])
+        fl = rel_l2(ref["bf16"][k], ref["fp32"][k])
+        assert r < 2.0 * fl + 1.5e-2, (k, r, fl)
+        if r > worst[1]:
+            worst = (k, r)
+    print(f"imagenet64 unet backward: worst parameter-gradient rel-L2 vs oracle fp32 = {worst[1]:.2e} ({worst[0]}); "
+          f"{len(P)} tensors; device part {t_dev:.1f} s, total {time.perf_counter() - t0:.1f} s")
+
+
 @pytest.mark.parametrize("tag", ["", "_plain"])
 def test_unet_backward_vs_oracle(golden_dir, tag):
     """Every parameter gradient of the shrunken ADM U-Net (both variants) against torch autograd through the pinned
