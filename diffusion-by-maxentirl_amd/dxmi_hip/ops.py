@@ -904,6 +904,27 @@ def edm_step(x, model_out, z, sigma, sigma_down, sigma_up, sigma_data=0.5, outs=
     return sample, mean
 
 
+# dxmi_karras_stage modes and table columns (include/dxmi_hip.h)
+KARRAS_FIRST, KARRAS_PRED, KARRAS_HEUN_CORR, KARRAS_DPM_CORR, KARRAS_EULER, KARRAS_ANCESTRAL = range(6)
+KT_SIGMA, KT_CSKIP, KT_COUT, KT_DT, KT_SIGMA_UP, KT_CHURN, KT_SNOISE, KT_CIN, KT_T, KT_XSCALE, KT_CLIP = range(11)
+KT_COLS = 16
+
+
+def karras_stage(mode, last, tab, row, x, x2=None, d=None, model_out=None, noise=None, x_in=None, t=None, out=None, denoised=None):
+    """One stage of the Karras samplers between two network evaluations (dxmi_karras_stage).  tab: fp32 [rows, KT_COLS] on the
+    device; x / x2 / d: the sampler state, read and written in place; every tensor fp32 [N, C, H, W] contiguous (t: [N])."""
+    _need_cuda(tab, x, x2, d, model_out, noise, x_in, t, out, denoised)
+    for v in (tab, x, x2, d, model_out, noise, x_in, t, out, denoised):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous()), "karras_stage: fp32 contiguous tensors only"
+    for v in (x2, d, model_out, noise, x_in, out, denoised):
+        assert v is None or v.shape == x.shape, "karras_stage: every image tensor has the state's shape"
+    assert tab.dim() == 2 and tab.shape[1] == KT_COLS and 0 <= row < tab.shape[0], "karras_stage: table row out of range"
+    N = x.shape[0]
+    assert t is None or t.shape == (N,)
+    check(load().dxmi_karras_stage(int(mode), int(bool(last)), _ptr(tab), int(row), _ptr(x), _ptr(x2), _ptr(d), _ptr(model_out),
+                                   _ptr(noise), _ptr(x_in), _ptr(t), _ptr(out), _ptr(denoised), N, x.numel() // N, _stream()),
+          "dxmi_karras_stage")
+
 def attention(qkv, heads, scale, out=None, want_lse=False):
     """qkv: [N, T, 3C] bf16 laid out [q|k|v]; returns [N, T, C] bf16.  want_lse: -> (out, lse | None): the row log-sum-exp the
     kernel leaves for attention_bwd(lse=...) (fp32 [N, heads, T], log2 domain; None for the shapes that have no such kernel)."""

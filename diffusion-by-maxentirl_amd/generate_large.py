@@ -10,6 +10,11 @@ only to broadcast weights; here every rank loads the same checkpoint), so the on
 gather of uint8 images for the FID npz.  FID itself (pytorch_fid + Inception weights + dataset statistics) is
 outside the accelerated path and runs only when those are present; --skip_fid writes PNGs as images are produced.
 `--synthetic NAME` builds the net of a built-in config with random weights (benchmark / smoke use).
+
+`--karras_sampler {heun,dpm,euler,ancestral}` samples the EDM teacher instead (models.cm.karras_diffusion.karras_sample,
+reference models/cm/karras_diffusion.py:354-420): `--karras_steps` (40), `--rho`, `--s_churn`, `--s_tmin`, `--s_tmax`,
+`--s_noise`.  Weights: `--pretrained [PATH]` loads a plain U-Net state dict (PATH, or the config's training.pretrained_path),
+otherwise `sampler.pth` from --log_dir without its `log_betas` entry.  Class-conditional nets draw one label per image.
 """
 import argparse
 import os
@@ -26,7 +31,10 @@ from models.DxMI.openai_diffusion import OpenAIDiffusion
 from utils import mkdir_p, print0, to_uint8_nhwc, write_png_batch
 
 
-def main():
+KARRAS_FLAGS = ("karras_steps", "rho", "s_churn", "s_tmin", "s_tmax", "s_noise", "pretrained")
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log_dir", type=str, required=True, help="path to logdir")
     ap.add_argument("--n_sample", type=int, required=True)
@@ -41,7 +49,55 @@ def main():
     ap.add_argument("--synthetic", type=str, default=None, help="builtin config name, e.g. imagenet64_T10 (random weights)")
     ap.add_argument("--no_graph", action="store_true", help="issue every launch from python instead of replaying the T-step loop of a "
                                                            "batch as one hipGraph (dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
-    args, unknown = ap.parse_known_args()
+    ap.add_argument("--karras_sampler", type=str, default=None, choices=("heun", "dpm", "euler", "ancestral"),
+                    help="sample the EDM teacher with this Karras sampler instead of the DxMI sampler")
+    ap.add_argument("--karras_steps", type=int, default=None, help="Karras sampler steps (default 40)")
+    ap.add_argument("--rho", type=float, default=None, help="Karras schedule rho (default 7.0)")
+    ap.add_argument("--s_churn", type=float, default=None, help="Karras churn (default 0)")
+    ap.add_argument("--s_tmin", type=float, default=None, help="churn window lower end (default 0)")
+    ap.add_argument("--s_tmax", type=float, default=None, help="churn window upper end (default inf)")
+    ap.add_argument("--s_noise", type=float, default=None, help="churn noise scale (default 1)")
+    ap.add_argument("--pretrained", type=str, nargs="?", const="", default=None,
+                    help="with --karras_sampler: load a plain U-Net state dict from PATH, or from the config's "
+                         "training.pretrained_path when PATH is omitted")
+    return ap
+
+
+def parse_args(argv=None):
+    """-> (args, unknown); checks the Karras flags: they need --karras_sampler, which excludes --guidance_scale."""
+    ap = build_parser()
+    args, unknown = ap.parse_known_args(argv)
+    if args.karras_sampler is None:
+        given = [f"--{k}" for k in KARRAS_FLAGS if getattr(args, k) is not None]
+        if given:
+            ap.error(f"{', '.join(given)} only apply with --karras_sampler")
+    else:
+        if args.guidance_scale is not None:
+            ap.error("--karras_sampler samples the EDM teacher: it cannot be combined with --guidance_scale")
+        for k, v in (("karras_steps", 40), ("rho", 7.0), ("s_churn", 0.0), ("s_tmin", 0.0), ("s_tmax", float("inf")),
+                     ("s_noise", 1.0)):
+            if getattr(args, k) is None:
+                setattr(args, k, v)
+        if args.karras_steps < 1:
+            ap.error("--karras_steps must be >= 1")
+    return args, unknown
+
+
+def resolve_weights(args, cfg):
+    """Weights of the Karras path: -> (path, kind) with kind 'plain' (a U-Net state dict) or 'sampler' (sampler.pth), or
+    (None, None) for --synthetic without --pretrained."""
+    if args.pretrained is not None:
+        path = args.pretrained or cfg.training.get("pretrained_path")
+        if not path:
+            raise ValueError("--pretrained without PATH needs training.pretrained_path in the config")
+        return path, "plain"
+    if args.synthetic:
+        return None, None
+    return os.path.join(args.log_dir, "sampler.pth"), "sampler"
+
+
+def main():
+    args, unknown = parse_args()
 
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -59,9 +115,11 @@ def main():
     random.seed(seed + local_rank)
 
     unet, diffusion = create_model_and_diffusion(**cfg.diffusion)
-    sampler = OpenAIDiffusion(unet, diffusion, **cfg.sampler)
     output_path = os.path.join(args.log_dir, "generated")
     mkdir_p(output_path)
+    if args.karras_sampler is not None:
+        return main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_path)
+    sampler = OpenAIDiffusion(unet, diffusion, **cfg.sampler)
     if not args.synthetic:
         ckpt_path = os.path.join(args.log_dir, "sampler.pth")
         ckpt = torch.load(ckpt_path, map_location="cpu")
@@ -116,6 +174,11 @@ def main():
            f"{n_batches * args.batchsize / max(dt, 1e-9):.1f} images/s/rank")
     if args.skip_fid:
         return
+    finish(args, l_sample, device, local_rank, world)
+
+
+def finish(args, l_sample, device, local_rank, world):
+    """All-gather of the uint8 batches, samples_N.npz on rank 0 and FID."""
     samples = torch.cat(l_sample)
     if world > 1:
         gathered = [torch.zeros_like(samples) for _ in range(world)]
@@ -136,6 +199,57 @@ def main():
     m2, s2 = load_statistics(args.fid_stats)
     fid = fid_from_images(samples[local_rank::world], extractor, m2, s2, batch_size=50, dims=args.fid_dims, device=device)
     print0(f"FID from {len(samples)} samples: {fid}")
+
+
+def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_path):
+    """--karras_sampler: the EDM teacher, no OpenAIDiffusion wrapper; the output stage is the DxMI path's."""
+    from dxmi_hip import graph as hip_graph
+    from dxmi_hip import ops
+    from models.cm.karras_diffusion import karras_nfe, karras_sample
+    from utils import ImageWriter
+    path, kind = resolve_weights(args, cfg)
+    if path is not None:
+        sd = torch.load(path, map_location="cpu")
+        if kind == "sampler":
+            sd = {k: v for k, v in sd["state_dict"].items() if k != "log_betas"}
+        unet.load_state_dict(sd)
+        print0(f"EDM weights loaded from {path}")
+    unet.to(device)
+    if cfg.diffusion.use_fp16:
+        unet.convert_to_fp16()
+    unet.eval()
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")  # RCCL
+    shape = (args.batchsize,) + tuple(cfg.sampler.sample_shape)
+    use_graph = hip_graph.default_enabled() and not args.no_graph
+    nfe = karras_nfe(args.karras_sampler, args.karras_steps)
+    n_batches = int(args.n_sample / args.batchsize / world)
+    l_sample, i_img = [], 0
+    writer = ImageWriter()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n_batches):
+        kw = {}
+        if unet.num_classes is not None:        # one uniform label per image, as OpenAIDiffusion._sample draws them
+            kw["y"] = torch.randint(0, unet.num_classes, (args.batchsize,), device=device)
+        sample = karras_sample(diffusion, unet, shape, args.karras_steps, model_kwargs=kw, device=device,
+                               sigma_min=diffusion.sigma_min, sigma_max=diffusion.sigma_max, rho=args.rho,
+                               sampler=args.karras_sampler, s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax,
+                               s_noise=args.s_noise, use_graph=use_graph)
+        if args.skip_fid:
+            writer.submit(sample, [os.path.join(output_path, f"{local_rank}_{i_img + k}.png") for k in range(len(sample))])
+            i_img += len(sample)
+        else:
+            l_sample.append(ops.quantize_u8(sample, mode=1, nhwc=False))
+    writer.close()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print0(f"generated {n_batches * args.batchsize} images/rank x {world} ranks, "
+           f"{n_batches * args.batchsize / max(dt, 1e-9):.1f} images/s/rank, {nfe} NFE/image "
+           f"({args.karras_sampler}, {args.karras_steps} steps)")
+    if not args.skip_fid:
+        finish(args, l_sample, device, local_rank, world)
 
 
 if __name__ == "__main__":

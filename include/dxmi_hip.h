@@ -656,6 +656,49 @@ int64_t dxmi_inception_score_workspace_bytes(int64_t N, int32_t C, int32_t split
 int dxmi_inception_score(const float* pool, int64_t N, int32_t D, const float* w, int32_t C, int32_t split, double* kl_mean,
                          void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Karras samplers of the EDM teacher: karras_sample / sample_heun / sample_dpm / sample_euler / sample_euler_ancestral
+ * (models/cm/karras_diffusion.py:354-420, :447-640; scalings :64-68, denoise :337-351, to_d :432-434).
+ * dxmi_karras_stage is the ONE launch between two network evaluations.  With F the output of the evaluation just done at
+ * the point x_e (x, or x2 for the correctors) and noise level s = tab[row][SIGMA], per element in fp32 and in the reference's
+ * operation order (no fused multiply-add):
+ *     denoised = c_out F + c_skip x_e, clamped to [-1, 1] if CLIP != 0 (clip_denoised, :408-412) -> denoised (if not NULL)
+ *     d        = (x_e - denoised) / s
+ *   DXMI_KARRAS_FIRST      x = x * XSCALE                    (x_T = randn * sigma_max; F unused)
+ *   DXMI_KARRAS_PRED       d -> d;  x2 = x + d DT            (heun :541-542 with DT = sigma_next - sigma_hat;
+ *                                                             dpm :614-617 with DT = sigma_mid - sigma_hat)
+ *   DXMI_KARRAS_HEUN_CORR  x' = x + ((d_saved + d) / 2) DT   (:543-546; x_e = x2)
+ *   DXMI_KARRAS_DPM_CORR   x' = x + d DT                     (:618-620; x_e = x2, DT = dt_2)
+ *   DXMI_KARRAS_EULER      x' = x + d DT                     (:576-577; heun's last step :537-539)
+ *   DXMI_KARRAS_ANCESTRAL  x' = x + d DT; x' = x' + z SIGMA_UP (:476-478; DT = sigma_down - sigma; z = noise, NULL = 0)
+ * then, except after PRED:  last ? out = clamp(x', -1, 1)  (:420)
+ *                                : x = x' + (eps SNOISE) CHURN  (next step's churn :523-527, only when noise = eps is not NULL
+ *                                                                and the mode is not ANCESTRAL);
+ * and, unless last, the next evaluation's input x_in = CIN x (x2 after PRED) and t[n] = T.  tab: fp32 [rows][DXMI_KT_COLS],
+ * device; row: the row of this launch.  x, x2, d, model_out, noise, x_in, out, denoised: fp32 [N, CHW] (x, x2, d read and
+ * written in place).  CHW must be a multiple of 4. */
+#define DXMI_KARRAS_FIRST      0
+#define DXMI_KARRAS_PRED       1
+#define DXMI_KARRAS_HEUN_CORR  2
+#define DXMI_KARRAS_DPM_CORR   3
+#define DXMI_KARRAS_EULER      4
+#define DXMI_KARRAS_ANCESTRAL  5
+#define DXMI_KT_SIGMA     0   /* noise level of the evaluation the launch follows (the divisor of d) */
+#define DXMI_KT_CSKIP     1   /* c_skip(SIGMA) */
+#define DXMI_KT_COUT      2   /* c_out(SIGMA) */
+#define DXMI_KT_DT        3   /* step of the update */
+#define DXMI_KT_SIGMA_UP  4   /* ancestral noise scale */
+#define DXMI_KT_CHURN     5   /* (sigma_hat^2 - sigma^2)^0.5 of the next step */
+#define DXMI_KT_SNOISE    6   /* s_noise */
+#define DXMI_KT_CIN       7   /* c_in of the next evaluation's noise level */
+#define DXMI_KT_T         8   /* 250 ln(next noise level + 1e-44) */
+#define DXMI_KT_XSCALE    9   /* scale of the initial draw: sigma_max for karras_sample, 1 when x is given (FIRST) */
+#define DXMI_KT_CLIP     10   /* 1: clip_denoised */
+#define DXMI_KT_COLS      16
+int dxmi_karras_stage(int32_t mode, int32_t last, const float* tab, int32_t row, float* x, float* x2, float* d,
+                      const float* model_out, const float* noise, float* x_in, float* t_out, float* out, float* denoised,
+                      int32_t N, int32_t CHW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
