@@ -925,6 +925,34 @@ def karras_stage(mode, last, tab, row, x, x2=None, d=None, model_out=None, noise
                                    _ptr(noise), _ptr(x_in), _ptr(t), _ptr(out), _ptr(denoised), N, x.numel() // N, _stream()),
           "dxmi_karras_stage")
 
+
+# dxmi_cm_stage modes, edit kinds and table columns (include/dxmi_hip.h)
+CM_FIRST, CM_STEP = range(2)
+CM_EDIT_NONE, CM_EDIT_MASK, CM_EDIT_COLOUR, CM_EDIT_PATCH = range(4)
+CT_CSKIP, CT_COUT, CT_NOISE, CT_CIN, CT_T, CT_XSCALE, CT_CLIP, CT_OUTCLAMP = range(8)
+CT_COLS = 8
+
+
+def cm_stage(mode, last, tab, row, x, edit=CM_EDIT_NONE, Q=None, model_out=None, noise=None, ref=None, mask=None, x_in=None,
+             t=None, out=None, denoised=None):
+    """One stage of the consistency-model samplers and editing loops between two network evaluations (dxmi_cm_stage).
+    tab: fp32 [rows, CT_COLS] on the device; x: the state [N, C, H, W], read and written in place; Q: fp32 3x3 (colour) or
+    64x64 (patch); every tensor fp32 contiguous (t: [N])."""
+    _need_cuda(tab, x, Q, model_out, noise, ref, mask, x_in, t, out, denoised)
+    for v in (tab, x, Q, model_out, noise, ref, mask, x_in, t, out, denoised):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous()), "cm_stage: fp32 contiguous tensors only"
+    assert x.dim() == 4, "cm_stage: x is [N, C, H, W]"
+    for v in (model_out, noise, ref, mask, x_in, out, denoised):
+        assert v is None or v.shape == x.shape, "cm_stage: every image tensor has the state's shape"
+    assert tab.dim() == 2 and tab.shape[1] == CT_COLS and 0 <= row < tab.shape[0], "cm_stage: table row out of range"
+    dim = {CM_EDIT_COLOUR: 3, CM_EDIT_PATCH: 64}.get(edit)
+    assert Q is None or dim is None or Q.shape == (dim, dim), f"cm_stage: Q must be {dim}x{dim}"
+    N, C, H, W = x.shape
+    assert t is None or t.shape == (N,)
+    check(load().dxmi_cm_stage(int(mode), int(edit), int(bool(last)), _ptr(tab), int(row), _ptr(Q), _ptr(x), _ptr(model_out),
+                               _ptr(noise), _ptr(ref), _ptr(mask), _ptr(x_in), _ptr(t), _ptr(out), _ptr(denoised), N, C, H, W,
+                               _stream()), "dxmi_cm_stage")
+
 def attention(qkv, heads, scale, out=None, want_lse=False):
     """qkv: [N, T, 3C] bf16 laid out [q|k|v]; returns [N, T, C] bf16.  want_lse: -> (out, lse | None): the row log-sum-exp the
     kernel leaves for attention_bwd(lse=...) (fp32 [N, heads, T], log2 domain; None for the shapes that have no such kernel)."""

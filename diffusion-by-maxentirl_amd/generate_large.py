@@ -15,6 +15,10 @@ outside the accelerated path and runs only when those are present; --skip_fid wr
 reference models/cm/karras_diffusion.py:354-420): `--karras_steps` (40), `--rho`, `--s_churn`, `--s_tmin`, `--s_tmax`,
 `--s_noise`.  Weights: `--pretrained [PATH]` loads a plain U-Net state dict (PATH, or the config's training.pretrained_path),
 otherwise `sampler.pth` from --log_dir without its `log_betas` entry.  Class-conditional nets draw one label per image.
+
+`--cm_sampler {onestep,multistep}` samples a consistency-distilled model the same way (karras_sample's onestep /
+multistep branch, reference :644-683): the diffusion is built with distillation=True; `--ts 0,22,39` (required for
+multistep), `--cm_steps` (40); `--pretrained [PATH]` as above.  It excludes --karras_sampler and --guidance_scale.
 """
 import argparse
 import os
@@ -32,6 +36,7 @@ from utils import mkdir_p, print0, to_uint8_nhwc, write_png_batch
 
 
 KARRAS_FLAGS = ("karras_steps", "rho", "s_churn", "s_tmin", "s_tmax", "s_noise", "pretrained")
+CM_FLAGS = ("ts", "cm_steps")
 
 
 def build_parser():
@@ -60,13 +65,23 @@ def build_parser():
     ap.add_argument("--pretrained", type=str, nargs="?", const="", default=None,
                     help="with --karras_sampler: load a plain U-Net state dict from PATH, or from the config's "
                          "training.pretrained_path when PATH is omitted")
+    ap.add_argument("--cm_sampler", type=str, default=None, choices=("onestep", "multistep"),
+                    help="sample a consistency-distilled model (distillation=True) with this sampler")
+    ap.add_argument("--ts", type=str, default=None, help="multistep: comma-separated step indices, e.g. 0,22,39")
+    ap.add_argument("--cm_steps", type=int, default=None, help="consistency sampler steps: the ts index range (default 40)")
     return ap
 
 
 def parse_args(argv=None):
-    """-> (args, unknown); checks the Karras flags: they need --karras_sampler, which excludes --guidance_scale."""
+    """-> (args, unknown); checks the Karras flags: they need --karras_sampler, which excludes --guidance_scale; and the
+    consistency flags: they need --cm_sampler, which excludes --karras_sampler and --guidance_scale."""
     ap = build_parser()
     args, unknown = ap.parse_known_args(argv)
+    if args.cm_sampler is not None:
+        return parse_cm_args(ap, args), unknown
+    given = [f"--{k}" for k in CM_FLAGS if getattr(args, k) is not None]
+    if given:
+        ap.error(f"{', '.join(given)} only apply with --cm_sampler")
     if args.karras_sampler is None:
         given = [f"--{k}" for k in KARRAS_FLAGS if getattr(args, k) is not None]
         if given:
@@ -81,6 +96,34 @@ def parse_args(argv=None):
         if args.karras_steps < 1:
             ap.error("--karras_steps must be >= 1")
     return args, unknown
+
+
+def parse_cm_args(ap, args):
+    if args.karras_sampler is not None:
+        ap.error("--cm_sampler and --karras_sampler exclude each other")
+    if args.guidance_scale is not None:
+        ap.error("--cm_sampler samples a consistency-distilled model: it cannot be combined with --guidance_scale")
+    given = [f"--{k}" for k in KARRAS_FLAGS if k != "pretrained" and getattr(args, k) is not None]
+    if given:
+        ap.error(f"{', '.join(given)} only apply with --karras_sampler")
+    if args.cm_steps is None:
+        args.cm_steps = 40
+    if args.cm_steps < 2:
+        ap.error("--cm_steps must be >= 2")
+    if args.cm_sampler == "onestep":
+        if args.ts is not None:
+            ap.error("--ts applies to --cm_sampler multistep only")
+        return args
+    if args.ts is None:
+        ap.error("--cm_sampler multistep needs --ts, e.g. --ts 0,22,39")
+    try:
+        ts = tuple(int(v) for v in args.ts.split(","))
+    except ValueError:
+        ap.error(f"--ts {args.ts!r}: comma-separated integers expected")
+    if len(ts) < 2 or any(not 0 <= v <= args.cm_steps - 1 for v in ts):
+        ap.error(f"--ts needs at least two indices in [0, --cm_steps - 1] = [0, {args.cm_steps - 1}]")
+    args.ts = ts
+    return args
 
 
 def resolve_weights(args, cfg):
@@ -117,7 +160,7 @@ def main():
     unet, diffusion = create_model_and_diffusion(**cfg.diffusion)
     output_path = os.path.join(args.log_dir, "generated")
     mkdir_p(output_path)
-    if args.karras_sampler is not None:
+    if args.karras_sampler is not None or args.cm_sampler is not None:
         return main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_path)
     sampler = OpenAIDiffusion(unet, diffusion, **cfg.sampler)
     if not args.synthetic:
@@ -202,10 +245,11 @@ def finish(args, l_sample, device, local_rank, world):
 
 
 def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_path):
-    """--karras_sampler: the EDM teacher, no OpenAIDiffusion wrapper; the output stage is the DxMI path's."""
+    """--karras_sampler: the EDM teacher, no OpenAIDiffusion wrapper; the output stage is the DxMI path's.  --cm_sampler: a
+    consistency-distilled model through the same path, with distillation=True."""
     from dxmi_hip import graph as hip_graph
     from dxmi_hip import ops
-    from models.cm.karras_diffusion import karras_nfe, karras_sample
+    from models.cm.karras_diffusion import cm_nfe, karras_nfe, karras_sample
     from utils import ImageWriter
     path, kind = resolve_weights(args, cfg)
     if path is not None:
@@ -223,7 +267,13 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")  # RCCL
     shape = (args.batchsize,) + tuple(cfg.sampler.sample_shape)
     use_graph = hip_graph.default_enabled() and not args.no_graph
-    nfe = karras_nfe(args.karras_sampler, args.karras_steps)
+    if args.cm_sampler is not None:
+        diffusion.distillation = True          # boundary-condition scalings (the diffusion block's distillation: True)
+        sampler, steps, nfe = args.cm_sampler, args.cm_steps, cm_nfe(args.cm_sampler, args.ts)
+        extra = dict(ts=args.ts)
+    else:
+        sampler, steps, nfe = args.karras_sampler, args.karras_steps, karras_nfe(args.karras_sampler, args.karras_steps)
+        extra = dict(rho=args.rho, s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax, s_noise=args.s_noise)
     n_batches = int(args.n_sample / args.batchsize / world)
     l_sample, i_img = [], 0
     writer = ImageWriter()
@@ -233,10 +283,8 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         kw = {}
         if unet.num_classes is not None:        # one uniform label per image, as OpenAIDiffusion._sample draws them
             kw["y"] = torch.randint(0, unet.num_classes, (args.batchsize,), device=device)
-        sample = karras_sample(diffusion, unet, shape, args.karras_steps, model_kwargs=kw, device=device,
-                               sigma_min=diffusion.sigma_min, sigma_max=diffusion.sigma_max, rho=args.rho,
-                               sampler=args.karras_sampler, s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax,
-                               s_noise=args.s_noise, use_graph=use_graph)
+        sample = karras_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
+                               sigma_max=diffusion.sigma_max, sampler=sampler, use_graph=use_graph, **extra)
         if args.skip_fid:
             writer.submit(sample, [os.path.join(output_path, f"{local_rank}_{i_img + k}.png") for k in range(len(sample))])
             i_img += len(sample)
@@ -247,7 +295,7 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
     dt = time.perf_counter() - t0
     print0(f"generated {n_batches * args.batchsize} images/rank x {world} ranks, "
            f"{n_batches * args.batchsize / max(dt, 1e-9):.1f} images/s/rank, {nfe} NFE/image "
-           f"({args.karras_sampler}, {args.karras_steps} steps)")
+           f"({sampler}, {steps} steps{'' if args.cm_sampler is None or args.ts is None else ', ts ' + str(list(args.ts))})")
     if not args.skip_fid:
         finish(args, l_sample, device, local_rank, world)
 

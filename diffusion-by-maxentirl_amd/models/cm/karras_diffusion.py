@@ -2,19 +2,25 @@
 
 Reference: models/cm/karras_diffusion.py — KarrasDenoiser.__init__/get_snr/get_scalings (:33-68),
 denoise (:337-351), karras_sample (:354-420), get_sigmas_karras (:423-429), get_ancestral_step (:437-444),
-sample_euler_ancestral / sample_heun / sample_euler / sample_dpm (:447-640).  The consistency-distillation
-losses and samplers (onestep, multistep, progdist) and the inpainting / super-resolution paths stay out of scope.
+sample_euler_ancestral / sample_heun / sample_euler / sample_dpm (:447-640), and the consistency-model samplers
+sample_onestep / stochastic_iterative_sampler (:644-683) with the zero-shot editing loops iterative_colorization /
+iterative_inpainting / iterative_superres (:722-951).  The consistency-distillation losses and progdist stay out of scope.
 
 denoise() keeps the reference signature for any callable `model`; neither sampler calls it on the hot path.
 OpenAIDiffusion (the DxMI few-step sampler) uses the fused dxmi_edm_precond / dxmi_edm_step_fwd kernels.
 karras_sample builds its schedule ONCE on the host, in fp32 torch with the reference's expressions (tables
 bit-identical to the reference's), uploads it as one small device table, and runs ONE dxmi_karras_stage launch
 between two network evaluations (denoised, clamp, d, the Heun / DPM-2 / Euler / ancestral update, the next step's
-churn and the next preconditioned input; the clamped sample after the last evaluation).
+churn and the next preconditioned input; the clamped sample after the last evaluation).  The consistency-model samplers
+and editing loops follow the same pattern with their own table (CMSchedule) and stage kernel (dxmi_cm_stage).
+
+Pairing (a deliberate restriction of the device path; the reference allows any combination): onestep and multistep run
+only for a diffusion with distillation=True (boundary-condition scalings), and the EDM samplers only with distillation=False.
 """
 import math
 import weakref
 
+import numpy as np
 import torch
 
 from .nn import append_dims, append_zero
@@ -71,6 +77,7 @@ def get_ancestral_step(sigma_from, sigma_to):
 # ------------------------------------------------------------------------------------------------------------- Karras samplers
 KARRAS_SAMPLERS = ("heun", "dpm", "euler", "ancestral")
 _DISTILLED_SAMPLERS = ("onestep", "multistep", "progdist")
+CM_SAMPLERS = ("onestep", "multistep")
 _GRAPHS = weakref.WeakKeyDictionary()       # model -> {graph key: StepGraph}
 _SCHEDULES = {}
 
@@ -80,15 +87,19 @@ class KarrasDenoiserFn:
     arithmetic (scalings, clip) into their stage kernels and call only `model(c_in x, 250 ln(sigma + 1e-44), **model_kwargs)`."""
 
     def __init__(self, diffusion, model, clip_denoised=True, model_kwargs=None):
-        if getattr(diffusion, "distillation", False):
-            raise NotImplementedError("karras_sample on the device supports distillation=False only: the boundary-condition "
-                                      "scalings belong to consistency-distilled models, which no config here builds")
         self.diffusion, self.model = diffusion, model
         self.clip_denoised, self.model_kwargs = bool(clip_denoised), dict(model_kwargs or {})
 
     def __call__(self, *a, **k):
         raise TypeError("KarrasDenoiserFn is not called directly: pass it to sample_heun / sample_dpm / sample_euler / "
-                        "sample_euler_ancestral, which fuse its arithmetic into dxmi_karras_stage")
+                        "sample_euler_ancestral, which fuse its arithmetic into dxmi_karras_stage, or to the consistency "
+                        "samplers and editing loops, which fuse it into dxmi_cm_stage")
+
+
+def _refuse_distillation(diffusion):
+    if getattr(diffusion, "distillation", False):
+        raise NotImplementedError("the EDM samplers on the device support distillation=False only: the boundary-condition "
+                                  "scalings belong to consistency-distilled models, which sample with onestep / multistep")
 
 
 class KarrasSchedule:
@@ -260,10 +271,19 @@ def _run(sch, denoiser, x0, shape, device, generator, callback=None, progress=Fa
     return out
 
 
-def _check_sampler_args(denoiser, x):
+def _check_sampler_args(denoiser, x, edm=True):
     if not isinstance(denoiser, KarrasDenoiserFn):
         raise TypeError("the device Karras samplers take a KarrasDenoiserFn (diffusion, model, clip_denoised, model_kwargs): "
-                        "they fuse the denoiser's arithmetic into dxmi_karras_stage")
+                        "they fuse the denoiser's arithmetic into dxmi_karras_stage / dxmi_cm_stage")
+    if edm:
+        _refuse_distillation(denoiser.diffusion)
+    elif not getattr(denoiser.diffusion, "distillation", False):
+        raise NotImplementedError("the consistency samplers on the device need a consistency-distilled model: a diffusion "
+                                  "with distillation=True (boundary-condition scalings)")
+    _check_device(x)
+
+
+def _check_device(x):
     if not x.is_cuda:
         from dxmi_hip._lib import DxmiError
         raise DxmiError("the Karras samplers run only on the HIP device path (no CPU fallback)")
@@ -320,12 +340,18 @@ def karras_sample(diffusion, model, shape, steps, clip_denoised=True, progress=F
     per ancestral step): a generator that replays recorded draws reproduces the reference's trajectory.
     use_graph: replay the whole loop of a key (sampler, steps, sigma and churn settings, shape, device, labels given) as one
     hipGraph: the first call of a key runs eagerly, the second is captured.  The returned tensor is then STATIC: the next call
-    of the same key overwrites it.  Off with callback, progress or a generator, and for model_kwargs other than `y`."""
+    of the same key overwrites it.  Off with callback, progress or a generator, and for model_kwargs other than `y`.
+    sampler onestep / multistep (ts: the multistep step indices in [0, steps - 1]): consistency-model sampling, only for a
+    diffusion with distillation=True (see the module docstring); multistep uses diffusion.rho, as the reference does (:400)."""
+    if sampler in CM_SAMPLERS and getattr(diffusion, "distillation", False):
+        return _karras_sample_cm(diffusion, model, shape, steps, clip_denoised, progress, callback, model_kwargs, device,
+                                 sigma_min, sigma_max, rho, sampler, generator, ts, use_graph)
     if sampler in _DISTILLED_SAMPLERS:
         raise NotImplementedError(f"sampler {sampler!r} needs a consistency-distilled model (`ts`, boundary-condition scalings), "
                                   "which no config here builds; the device path runs heun, dpm, euler and ancestral")
     if sampler not in KARRAS_SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}")
+    _refuse_distillation(diffusion)
     denoiser = KarrasDenoiserFn(diffusion, model, clip_denoised, model_kwargs)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if device.type != "cuda":
@@ -360,3 +386,335 @@ def karras_sample(diffusion, model, shape, steps, clip_denoised=True, progress=F
             return g(kw["y"]) if "y" in kw else g()
     with torch.no_grad():
         return _run(sch, denoiser, None, shape, device, generator, callback, progress)
+
+
+# ------------------------------------------------------------------------------------------------- consistency-model samplers
+_CM_SCHEDULES = {}
+_Q_CACHE = {}
+
+
+def cm_nfe(sampler, ts=None):
+    """Network evaluations per image: onestep 1, multistep len(ts) - 1."""
+    return 1 if sampler == "onestep" else len(ts) - 1
+
+
+def _check_ts(ts, steps):
+    if ts is None or len(ts) < 2:
+        raise ValueError("the multistep sampler needs ts: at least two step indices in [0, steps - 1]")
+    for v in ts:
+        if not 0 <= v <= steps - 1:
+            raise ValueError(f"ts entry {v} outside [0, steps - 1] = [0, {steps - 1}]")
+    return tuple(ts)
+
+
+class CMSchedule:
+    """Host table of the consistency-model samplers (reference :644-683) and editing loops (:722-951).
+
+    onestep evaluates once at sigma0 (karras_sample: sigmas[0] = sigma_max of the fp32 Karras ladder).  multistep evaluates at
+    t_i = (t_max^(1/rho) + ts[i] / (steps - 1) (t_min^(1/rho) - t_max^(1/rho)))^rho for i < len(ts) - 1, in float64 python as
+    the reference, and after each evaluation adds z sqrt(next_t^2 - t_min^2) with next_t the next index's t clipped to
+    [t_min, t_max] (np.clip / np.sqrt, float64; nonzero after the last evaluation unless ts[-1] = steps - 1).  The network sees
+    fp32(t) (t * s_in); the scalings are the diffusion's boundary-condition ones when distillation is set, else the plain ones,
+    evaluated on that fp32 sigma as denoise() does.  Row 0 is the FIRST launch, row k the launch after evaluation k
+    (include/dxmi_hip.h, DXMI_CT_*)."""
+
+    def __init__(self, sampler, diffusion, ts=None, steps=40, t_min=0.002, t_max=80.0, rho=7.0, clip_denoised=True,
+                 x_scale=1.0, out_clamp=False, sigma0=None):
+        from dxmi_hip import ops
+        if sampler == "onestep":
+            self.t = [float(sigma0)]
+            self.noise = [0.0]
+            self.ts = None
+        elif sampler == "multistep":
+            ts = self.ts = _check_ts(ts, steps)
+            t_max_rho, t_min_rho = t_max ** (1 / rho), t_min ** (1 / rho)
+            self.t, self.noise = [], []
+            for i in range(len(ts) - 1):
+                self.t.append((t_max_rho + ts[i] / (steps - 1) * (t_min_rho - t_max_rho)) ** rho)
+                next_t = (t_max_rho + ts[i + 1] / (steps - 1) * (t_min_rho - t_max_rho)) ** rho
+                next_t = np.clip(next_t, t_min, t_max)
+                self.noise.append(np.sqrt(next_t ** 2 - t_min ** 2))
+        else:
+            raise ValueError(f"unknown consistency sampler {sampler!r}; the device path runs onestep and multistep")
+        self.sampler, self.nfe = sampler, len(self.t)
+        self.eval_sigmas = torch.stack([torch.tensor([t], dtype=torch.float32)[0] for t in self.t])   # fp32(t): t * s_in
+        scal = diffusion.get_scalings_for_boundary_condition if diffusion.distillation else diffusion.get_scalings
+        tab = torch.zeros((self.nfe + 1, ops.CT_COLS), dtype=torch.float32)
+        for k in range(self.nfe + 1):
+            if k > 0:
+                c_skip, c_out, _ = scal(self.eval_sigmas[k - 1].reshape(1))
+                tab[k, ops.CT_CSKIP], tab[k, ops.CT_COUT] = c_skip[0], c_out[0]
+                tab[k, ops.CT_NOISE] = float(self.noise[k - 1])          # randn_like(x) * np.float64: fp32 multiplier
+            if k < self.nfe:
+                s = self.eval_sigmas[k].reshape(1)
+                tab[k, ops.CT_CIN] = scal(s)[2][0]
+                tab[k, ops.CT_T] = (1000 * 0.25 * torch.log(s + 1e-44))[0]    # denoise() (:348)
+            tab[k, ops.CT_XSCALE] = x_scale
+            tab[k, ops.CT_CLIP] = 1.0 if clip_denoised else 0.0
+            tab[k, ops.CT_OUTCLAMP] = 1.0 if out_clamp else 0.0
+        self.table = tab
+        self._dev = {}
+
+    def device_table(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self.table.to(device)
+        return self._dev[key]
+
+
+def _cm_schedule(sampler, diffusion, ts, steps, t_min, t_max, rho, clip, x_scale, out_clamp, sigma0=None):
+    key = (sampler, None if ts is None else tuple(float(v) for v in ts), int(steps), float(t_min), float(t_max), float(rho),
+           float(diffusion.sigma_data), float(diffusion.sigma_min), bool(diffusion.distillation), bool(clip), float(x_scale),
+           bool(out_clamp), None if sigma0 is None else float(sigma0))
+    sch = _CM_SCHEDULES.get(key)
+    if sch is None:
+        if len(_CM_SCHEDULES) > 64:
+            _CM_SCHEDULES.clear()
+        sch = _CM_SCHEDULES[key] = CMSchedule(sampler, diffusion, ts, steps, t_min, t_max, rho, clip, x_scale, out_clamp, sigma0)
+    return sch
+
+
+def _orthogonal(vector):
+    """The reference's basis of iterative_colorization / iterative_superres (:731-739, :850-858): QR of the identity whose first
+    column is the normalised vector, sign-fixed so that column 0 sums positive; float64 numpy, then fp32."""
+    vec = np.asarray(vector)
+    vec = vec / np.linalg.norm(vec)
+    m = np.eye(len(vec))
+    m[:, 0] = vec
+    m = np.linalg.qr(m)[0]
+    if np.sum(m[:, 0]) < 0:
+        m = -m
+    return torch.from_numpy(m).to(torch.float32)
+
+
+def colour_basis():
+    """3x3 Q of iterative_colorization: column 0 along the luma weights (0.2989, 0.5870, 0.1140)."""
+    if "colour" not in _Q_CACHE:
+        _Q_CACHE["colour"] = _orthogonal([0.2989, 0.5870, 0.1140])
+    return _Q_CACHE["colour"]
+
+
+def patch_basis():
+    """64x64 Q of iterative_superres: column 0 along the 8x8 patch mean."""
+    if "patch" not in _Q_CACHE:
+        _Q_CACHE["patch"] = _orthogonal([1] * 64)
+    return _Q_CACHE["patch"]
+
+
+def _run_cm(sch, denoiser, x0, shape, device, generator, edit=None, Q=None, ref=None, mask=None, callback=None,
+            progress=False):
+    """FIRST, then per network evaluation one dxmi_cm_stage launch.  x0: the initial state (scaled by XSCALE), or None to draw
+    it (generator.randn, else on the device).  -> the output (a new tensor, static under graph capture)."""
+    from dxmi_hip import ops
+    edit = ops.CM_EDIT_NONE if edit is None else edit
+    f32 = dict(dtype=torch.float32, device=device)
+    tab = sch.device_table(device)
+    x = torch.empty(shape, **f32)
+    if x0 is not None:
+        x.copy_(x0)
+    elif generator is not None:
+        x.copy_(generator.randn(*shape, device=device))
+    else:
+        x.normal_()
+    x_in, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
+    ops.cm_stage(ops.CM_FIRST, False, tab, 0, x, x_in=x_in, t=t)
+    noise_buf = None
+    model, kw = denoiser.model, denoiser.model_kwargs
+    evals = range(1, sch.nfe + 1)
+    if progress:
+        try:
+            from tqdm.auto import tqdm
+            evals = tqdm(evals)
+        except ImportError:
+            pass
+    for k in evals:
+        last = k == sch.nfe
+        F = model(x_in, t, **kw)
+        if F.dtype != torch.float32 or not F.is_contiguous() or F.device != x.device:
+            F = _as_f32(F, device)
+        assert F.shape == x.shape, f"model output {tuple(F.shape)} != sample shape {tuple(x.shape)}"
+        noise = None
+        used = float(sch.noise[k - 1]) != 0.0
+        if sch.sampler == "multistep" and generator is not None:     # one randn_like per step, the last included (:681)
+            draw = generator.randn_like(x)
+            noise = _as_f32(draw, device) if used else None
+        elif sch.sampler == "multistep" and used:
+            if noise_buf is None:
+                noise_buf = torch.empty(shape, **f32)
+            noise = noise_buf.normal_()
+        den, cb_x = None, None
+        if callback is not None:
+            den, cb_x = torch.empty(shape, **f32), x.clone()
+        ops.cm_stage(ops.CM_STEP, last, tab, k, x, edit=edit, Q=Q, model_out=F, noise=noise, ref=ref, mask=mask,
+                     x_in=None if last else x_in, t=None if last else t, out=out if last else None, denoised=den)
+        if den is not None:
+            callback({"x": cb_x, "i": k - 1, "sigma": sch.eval_sigmas[k - 1], "denoised": den})
+    return out
+
+
+def _check_cm_args(distiller, x):
+    _check_sampler_args(distiller, x, edm=False)
+
+
+@torch.no_grad()
+def sample_onestep(distiller, x, sigmas, generator=None, progress=False, callback=None):
+    """Single-step generation from a distilled model (reference :644-655): the denoiser at sigmas[0].  distiller: a
+    KarrasDenoiserFn whose diffusion has distillation=True.  callback, if given, sees {x, i, sigma, denoised} once per
+    evaluation (the reference accepts and ignores it)."""
+    _check_cm_args(distiller, x)
+    sch = _cm_schedule("onestep", distiller.diffusion, None, 1, 0.002, 80.0, 7.0, distiller.clip_denoised, 1.0, False,
+                       sigma0=float(torch.as_tensor(sigmas[0], dtype=torch.float32)))
+    return _run_cm(sch, distiller, x, tuple(x.shape), x.device, generator, callback=callback, progress=progress)
+
+
+@torch.no_grad()
+def stochastic_iterative_sampler(distiller, x, sigmas, generator, ts, progress=False, callback=None, t_min=0.002, t_max=80.0,
+                                 rho=7.0, steps=40):
+    """The multistep consistency sampler (reference :658-683).  NFE = len(ts) - 1; returns x after the last step's noise,
+    unclamped.  generator: None draws on the device (skipping a draw whose factor is 0); else one randn_like per step."""
+    _check_ts(ts, steps)
+    _check_cm_args(distiller, x)
+    sch = _cm_schedule("multistep", distiller.diffusion, ts, steps, t_min, t_max, rho, distiller.clip_denoised, 1.0, False)
+    return _run_cm(sch, distiller, x, tuple(x.shape), x.device, generator, callback=callback, progress=progress)
+
+
+def _karras_sample_cm(diffusion, model, shape, steps, clip_denoised, progress, callback, model_kwargs, device, sigma_min,
+                      sigma_max, rho, sampler, generator, ts, use_graph):
+    """karras_sample's onestep / multistep branch (distillation=True): x_T = randn * sigma_max, clamp(x_0, -1, 1)."""
+    if sampler == "multistep":
+        ts = _check_ts(ts, steps)
+    denoiser = KarrasDenoiserFn(diffusion, model, clip_denoised, model_kwargs)
+    if sampler == "onestep":
+        sigma0 = float(get_sigmas_karras(steps, sigma_min, sigma_max, rho)[0])
+        sch = _cm_schedule("onestep", diffusion, None, steps, sigma_min, sigma_max, rho, clip_denoised, sigma_max, True, sigma0)
+    else:
+        sch = _cm_schedule("multistep", diffusion, ts, steps, sigma_min, sigma_max, diffusion.rho, clip_denoised, sigma_max,
+                           True)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        from dxmi_hip._lib import DxmiError
+        raise DxmiError("karras_sample runs only on the HIP device path (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    shape = tuple(int(s) for s in shape)
+    from dxmi_hip import graph as _graph
+    kw = denoiser.model_kwargs
+    if use_graph and callback is None and not progress and generator is None and set(kw) <= {"y"} \
+            and not _graph.capturing():
+        key = (sampler, steps, ts, float(sigma_min), float(sigma_max), float(rho), float(diffusion.rho),
+               bool(diffusion.distillation), bool(clip_denoised), float(diffusion.sigma_data), shape, device.index, "y" in kw)
+        try:
+            graphs = _GRAPHS.setdefault(model, {})
+        except TypeError:        # not weak-referenceable: no cache, so no replay
+            graphs = {}
+        g = graphs.get(key)
+        if g is None:
+            from models.DxMI.trainer import _pack_modules
+            if "y" in kw:
+                fn = lambda y: _run_cm(sch, KarrasDenoiserFn(diffusion, model, clip_denoised, {"y": y}), None, shape, device, None)
+            else:
+                fn = lambda: _run_cm(sch, denoiser, None, shape, device, None)
+            g = graphs[key] = _graph.StepGraph(fn, device, modules=_pack_modules(model), name=f"cm_sample{key}")
+        with torch.no_grad():
+            return g(kw["y"]) if "y" in kw else g()
+    with torch.no_grad():
+        return _run_cm(sch, denoiser, None, shape, device, generator, callback=callback, progress=progress)
+
+
+# ------------------------------------------------------------------------------------------------------ zero-shot editing
+def _patches(v):
+    """[N, C, H, W] -> [N, C, H/8, W/8, 64] view order of the reference's permute(0, 1, 2, 4, 3, 5) flattening."""
+    N, C, H, W = v.shape
+    return v.reshape(N, C, H // 8, 8, W // 8, 8).permute(0, 1, 2, 4, 3, 5).reshape(N, C, H // 8, W // 8, 64)
+
+
+def _unpatches(p, shape):
+    N, C, H, W = shape
+    return p.reshape(N, C, H // 8, W // 8, 8, 8).permute(0, 1, 2, 4, 3, 5).reshape(N, C, H, W)
+
+
+def inpainting_mask(n, image_size, font_path=None):
+    """The reference's inpainting mask (:781-801): the letter "S" drawn at (50, 0) in a 250-point TrueType font on a white
+    image_size x image_size image; groups of 7 images alternate between keeping the letter's background and the letter
+    itself.  -> fp32 [n, 3, image_size, image_size].  The reference hard-codes arial.ttf: pass the font file here."""
+    import os
+    if n % 7 != 0:
+        raise ValueError(f"the letter mask alternates groups of 7 images: n ({n}) must be a multiple of 7 (or pass mask=)")
+    if not font_path:
+        raise ValueError("inpainting_mask needs font_path: a TrueType font file to draw the letter with (the reference uses "
+                         "arial.ttf)")
+    if not os.path.isfile(font_path):
+        raise FileNotFoundError(f"inpainting_mask: font file {font_path!r} not found")
+    from PIL import Image, ImageDraw, ImageFont
+    img = Image.new("RGB", (image_size, image_size), color="white")
+    ImageDraw.Draw(img).text((50, 0), "S", font=ImageFont.truetype(font_path, 250), fill=(0, 0, 0))
+    img_th = torch.from_numpy(np.array(img).transpose(2, 0, 1).copy())
+    mask = torch.zeros(n // 7, 7, 3, image_size, image_size)
+    mask[::2, :, img_th > 0.5] = 1.0
+    mask[1::2, :, img_th < 0.5] = 1.0
+    return mask.reshape(n, 3, image_size, image_size)
+
+
+def _edit_args(distiller, images, x, ts, steps, generator):
+    ts = _check_ts(ts, steps)
+    if images.shape != x.shape:
+        raise ValueError(f"images {tuple(images.shape)} and x {tuple(x.shape)} differ in shape")
+    return ts, _as_f32(images, x.device)
+
+
+def _edit(distiller, x, ts, t_min, t_max, rho, steps, generator, edit, Q, ref, mask=None):
+    # the editing loops clamp x0 themselves (:758, :819, :938): CLIP is on whatever clip_denoised says
+    sch = _cm_schedule("multistep", distiller.diffusion, ts, steps, t_min, t_max, rho, True, 1.0, False)
+    return _run_cm(sch, distiller, x, tuple(x.shape), x.device, generator, edit=edit, Q=Q, ref=ref, mask=mask)
+
+
+@torch.no_grad()
+def iterative_colorization(distiller, images, x, ts, t_min=0.002, t_max=80.0, rho=7.0, steps=40, generator=None):
+    """Zero-shot colourisation (reference :722-771): keep the luma coefficient of `images`, let the model fill the two chroma
+    coefficients.  -> (x, the greyscale view of images), unclamped.  generator=None draws on the device."""
+    from dxmi_hip import ops
+    if x.shape[1] != 3:
+        raise ValueError("iterative_colorization needs 3 channels")
+    _check_cm_args(distiller, x)
+    ts, images = _edit_args(distiller, images, x, ts, steps, generator)
+    Q = colour_basis().to(x.device)
+    y = torch.einsum("bchw,cd->bdhw", images, Q)
+    y[:, 1:] = 0.0
+    images = torch.einsum("bdhw,cd->bchw", y, Q).contiguous()          # replacement(images, 0)
+    return _edit(distiller, x, ts, t_min, t_max, rho, steps, generator, ops.CM_EDIT_COLOUR, Q, images), images
+
+
+@torch.no_grad()
+def iterative_inpainting(distiller, images, x, ts, t_min=0.002, t_max=80.0, rho=7.0, steps=40, generator=None, mask=None,
+                         font_path=None):
+    """Zero-shot inpainting (reference :774-832): where mask = 1 keep `images`, elsewhere let the model fill.  mask: fp32
+    [N, C, H, W]; without it the reference's letter mask (inpainting_mask, needs font_path and N % 7 == 0).
+    -> (x, images with the masked-out part set to -1), unclamped."""
+    from dxmi_hip import ops
+    ts = _check_ts(ts, steps)
+    if mask is None:
+        if x.shape[-1] != x.shape[-2] or x.shape[1] != 3:
+            raise ValueError("the letter mask needs square 3-channel images; pass mask=")
+        mask = inpainting_mask(x.shape[0], x.shape[-1], font_path)
+    if tuple(mask.shape) != tuple(x.shape):
+        raise ValueError(f"mask {tuple(mask.shape)} must have the images' shape {tuple(x.shape)}")
+    _check_cm_args(distiller, x)
+    ts, images = _edit_args(distiller, images, x, ts, steps, generator)
+    mask = _as_f32(mask, x.device)
+    images = (images * mask + (-torch.ones_like(images)) * (1 - mask)).contiguous()     # replacement(images, -1)
+    return _edit(distiller, x, ts, t_min, t_max, rho, steps, generator, ops.CM_EDIT_MASK, None, images, mask), images
+
+
+@torch.no_grad()
+def iterative_superres(distiller, images, x, ts, t_min=0.002, t_max=80.0, rho=7.0, steps=40, generator=None):
+    """Zero-shot 8x super-resolution (reference :835-951): keep each 8x8 patch's mean of `images`, let the model fill the other
+    63 coefficients of the patch basis.  H and W must be multiples of 8.  -> (x, the patch-averaged images), unclamped."""
+    from dxmi_hip import ops
+    if x.dim() != 4 or x.shape[-1] % 8 or x.shape[-2] % 8:
+        raise ValueError(f"iterative_superres needs H and W multiples of 8 (got {tuple(x.shape)})")
+    _check_cm_args(distiller, x)
+    ts, images = _edit_args(distiller, images, x, ts, steps, generator)
+    p = _patches(images)
+    images = _unpatches(p.mean(dim=-1, keepdim=True).expand_as(p), images.shape).contiguous()   # average_image_patches
+    Q = patch_basis().to(x.device)
+    return _edit(distiller, x, ts, t_min, t_max, rho, steps, generator, ops.CM_EDIT_PATCH, Q, images), images

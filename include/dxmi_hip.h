@@ -699,6 +699,47 @@ int dxmi_karras_stage(int32_t mode, int32_t last, const float* tab, int32_t row,
                       const float* model_out, const float* noise, float* x_in, float* t_out, float* out, float* denoised,
                       int32_t N, int32_t CHW, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Consistency-model sampling and zero-shot editing: sample_onestep / stochastic_iterative_sampler (the `multistep` sampler) /
+ * iterative_colorization / iterative_inpainting / iterative_superres (models/cm/karras_diffusion.py:644-683, :722-951;
+ * boundary-condition scalings :70-80, chosen by denoise :336-351; dispatch karras_sample :354-420).
+ * dxmi_cm_stage is the ONE launch between two network evaluations.  With F the output of the evaluation just done at the
+ * state x, per element in fp32 and in the reference's operation order (no fused multiply-add):
+ *   DXMI_CM_FIRST  x = x * XSCALE                           (x_T = randn * sigma_max; F unused, no edit, no noise)
+ *   DXMI_CM_STEP   x0 = c_out F + c_skip x, clamped to [-1, 1] if CLIP != 0            -> denoised (if not NULL)
+ *                  edit:  NONE    x0
+ *                         MASK    ref m + x0 (1 - m)                                   (iterative_inpainting :803-805)
+ *                         COLOUR  per pixel y = v^T Q over the 3 channel planes (Q: 3x3), y_0 from ref, y_1..2 from x0,
+ *                                 x0 = Q y                                             (iterative_colorization :741-747)
+ *                         PATCH   per 8x8 patch of each plane, in-patch index d = 8 row + col, y = v^T Q (Q: 64x64),
+ *                                 y_0 from ref, y_1..63 from x0, x0 = Q y              (iterative_superres :858-900)
+ *                  x' = x0 + z NOISE                       (z = noise; NULL = 0: the draw is skipped)
+ *                  last ? out = x', clamped to [-1, 1] if OUTCLAMP != 0 (karras_sample :420)
+ *                       : x = x'
+ * and, unless last, the next evaluation's input x_in = CIN x and t[n] = T.  tab: fp32 [rows][DXMI_CT_COLS], device; row: the
+ * row of this launch.  Q: fp32 row-major (Q[d][e] at Q + d * dim + e), device.  x, model_out, noise, ref, mask, x_in, out,
+ * denoised: fp32 [N, C, H, W] (x read and written in place).  C*H*W must be a multiple of 4 (NONE, MASK); COLOUR needs C = 3
+ * and H*W a multiple of 4; PATCH needs H and W multiples of 8.  The Q transforms sum in another order than the reference's
+ * einsum: per element |err| <= c u32 sum|Q||v|. */
+#define DXMI_CM_FIRST        0
+#define DXMI_CM_STEP         1
+#define DXMI_CM_EDIT_NONE    0
+#define DXMI_CM_EDIT_MASK    1
+#define DXMI_CM_EDIT_COLOUR  2
+#define DXMI_CM_EDIT_PATCH   3
+#define DXMI_CT_CSKIP     0   /* c_skip of the evaluation the launch follows (boundary-condition or plain) */
+#define DXMI_CT_COUT      1   /* c_out of that evaluation */
+#define DXMI_CT_NOISE     2   /* sqrt(next_t^2 - t_min^2), float64 then rounded once (0 for onestep) */
+#define DXMI_CT_CIN       3   /* c_in of the next evaluation's noise level */
+#define DXMI_CT_T         4   /* 250 ln(next noise level + 1e-44) */
+#define DXMI_CT_XSCALE    5   /* scale of the initial draw: sigma_max for karras_sample, 1 when x is given (FIRST) */
+#define DXMI_CT_CLIP      6   /* 1: clamp denoised (clip_denoised, and always in the editing loops) */
+#define DXMI_CT_OUTCLAMP  7   /* 1: clamp the final output (karras_sample) */
+#define DXMI_CT_COLS      8
+int dxmi_cm_stage(int32_t mode, int32_t edit, int32_t last, const float* tab, int32_t row, const float* Q, float* x,
+                  const float* model_out, const float* noise, const float* ref, const float* mask, float* x_in, float* t_out,
+                  float* out, float* denoised, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
