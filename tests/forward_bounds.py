@@ -1,0 +1,245 @@
+"""Error bounds for the forward kernels, checked element by element against an fp64 reference of the same operation.
+
+The references use stock torch only, in float64 on the device (F.unfold + einsum for convolutions, F.group_norm-style group
+statistics, softmax attention, a plain matmul for `linear`); none of this project's kernels takes part.  u32 = 2^-24 and
+u16 = 2^-8 are the unit roundoffs of fp32 and bf16; `Checker` (backward_bounds) keeps the worst |err| / bound per op.
+
+Conv forward (bf16 operands, fp32 MFMA accumulation, fused adds, activation, one bf16 store).  Every product of two bf16
+values is exact in fp32, so the accumulation of the K = Cin * k * k products plus the fused adds (bias, addvec, residual: up
+to three more terms) is a recursive fp32 sum of c = K + 3 terms, |fl(s) - s| <= c u32 sum|x_i| (Higham 4.2), whatever the
+order.  With A = sum |w||x| + |bias| + |addvec| + |residual| (fp64, same operands) the pre-activation error is c u32 A.  The
+activation act is Lipschitz with constant L (1 for none / ReLU / LeakyReLU, 1.1 for SiLU: max |silu'| = 1.0998) and is itself
+evaluated in fp32 to a few ulps; the store rounds once more to bf16 (round to nearest even: relative error <= u16; a
+truncating store errs by up to 2 u16, and by more than u16 for about half of all values).  So
+
+    |got - act(ref64)| <= L c u32 A (1 + u16) + (u16 + 4 u32) |act(ref64)|
+
+An fp32-output conv (conv_out, NCHW fp32) drops the bf16 term.
+
+Block statistics (sum, sum of squares per channel pair).  The kernels sum the STORED bf16 outputs; a bf16 square is exact
+in fp32.  One partial adds 2 * pixels-per-partial terms; a fold pass adds `group` partials; summing the remaining partials
+(done here in fp64) is exact enough.  So per image and channel pair, with the sums taken over the stored tensor:
+
+    |sum_p st[p] - S64| <= (2 * HW / P0 + 32 * folds + 2) u32 S64abs
+
+GroupNorm forward.  The kernels compute the group statistics in one fp32 pass: m = s / n, var = q / n - m^2 with s, q fp32
+sums of depth d.  The streaming apply adds the P partials of each channel pair, then the cpg / 2 pairs of a group: nested
+sums whose depths add, d = max(P0, P1) + cpg / 2 (+ 2 for the rounding of given partials); the resident and generic kernels
+are charged the group size, valid for any order of their partial sums.  With E|x|, E[x^2] the group means of |x|, x^2:
+    dm <= d u32 E|x|,   dq <= d u32 E[x^2],   dvar <= dq + 2 |m| dm + 2 u32 E[x^2] <= (3 d + 2) u32 E[x^2]
+(|m| E|x| <= E[x^2]).  rstd = (var + eps)^-1/2 then has relative error (1.5 d + 1) u32 kappa + 4 u32 with the conditioning
+term kappa = E[x^2] / (var + eps) = (m^2 + var) / (var + eps), carried explicitly, eps included.  xhat = (x - m) rstd:
+    dxhat <= |xhat| drstd + rstd dm + 4 u32 (|x| + |m|) rstd
+and y = act(film(gamma xhat + beta)) propagates it with L |gamma| |1 + scale|, plus 4 u32 of the affine terms; one bf16 store:
+    |got - y64| <= L |gamma| |1 + scale| dxhat (1 + u16) + 4 u32 (|gamma xhat| + |beta|) |1 + scale| + (u16 + 4 u32) |y64|
+A fused GroupNorm in a conv epilogue normalises the conv's bf16-ROUNDED outputs: when the raw tensor is kept, the reference
+normalises exactly that stored tensor; when it is not, the propagated term is carried instead (gn_fused_bound): the input
+error dh = c u32 A + u16 |h| of every element goes through the linearised GroupNorm, rstd (dh_i + mean_g dh +
+|xhat_i| mean_g |xhat| dh).
+
+linear (linear_small_kernel and the tiled path).  pre_act(x) is evaluated in fp32 and rounded to bf16 (the MFMA operand);
+the reference rounds at the same point (bf16 of the fp64 pre-activation).  Where the fp64 pre-activation lies within 8 u32
+of a bf16 rounding midpoint the kernel's fp32 value may round the other way: such operands carry u16 |pre| |w| in the bound.
+Depth K plus the bias add; post_act as for the conv; fp32 output:  |got - ref| <= L (K + 2) u32 A + 4 u32 |ref| + tie term.
+
+Attention.  P is rounded to bf16 before the P V product (an MFMA operand), so the output is judged by rel-L2 per (image, head,
+128-row block) within 8 u16, as the backward is.  The row log-sum-exp the kernels keep is in the LOG2 domain:
+lse2 = log2 sum_j 2^(s_ij log2 e), s = scale q.k.  A score is an fp32 sum of D exact products (error D u32 scale sum|q||k|),
+2^x is evaluated to ~2 ulp and summed over T keys, so element-wise
+    |got - lse2| <= log2(e) (D + 2) u32 scale max_j sum_d |q_id k_jd| + (T + 8) u32 log2(e) + 4 u32 |lse2|
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from backward_bounds import U16, U32, BoundError, Checker, unfold_nhwc
+
+LOG2E = 1.0 / math.log(2.0)
+ACT_L = {0: 1.0, 1: 1.0, 2: 1.0, 3: 1.1}         # Lipschitz constant per ops.ACT_* (none, leaky 0.2, relu, silu)
+
+
+class FwdChecker(Checker):
+    def within(self, name, got, ref, bound):
+        """Element-wise |got - ref| <= bound (all fp64 of the same shape)."""
+        got, ref = got.double(), ref.double()
+        if got.shape != ref.shape:
+            raise BoundError(f"{name}: shape {tuple(got.shape)} != {tuple(ref.shape)}")
+        return self._judge(name, got, ref, bound.double() + 1e-300)
+
+
+def act64(v, act):
+    if act == 1:
+        return torch.where(v > 0, v, 0.2 * v)
+    if act == 2:
+        return v.clamp_min(0)
+    if act == 3:
+        return v * torch.sigmoid(v)
+    return v
+
+
+def store_bound(core, ref, bf16_out=True):
+    """core: propagated fp32 error; + one bf16 (round-to-nearest) store and a few ulps of fp32 epilogue arithmetic."""
+    if bf16_out:
+        return core * (1 + U16) + (U16 + 4 * U32) * ref.abs()
+    return core + 4 * U32 * ref.abs()
+
+
+# ------------------------------------------------------------------------------------------ conv
+def conv_fwd_ref(x, W, bias=None, addvec=None, residual=None, stride=1, pad=None, pad_br=None, upsample=0, chunk_bytes=1 << 29):
+    """fp64 pre-activation conv and A = sum |w||x| + |fused adds|: x NHWC (concat applied, any dtype), W [Cout, Cin, k, k],
+    bias [Cout], addvec [N, Cout] (a shared row expanded by the caller), residual NHWC.  Computed a few images at a time."""
+    k = W.shape[2]
+    pad = k // 2 if pad is None else pad
+    pb = pad if pad_br is None else pad_br
+    N, IH, IW, Cin = x.shape
+    VH, VW = (2 * IH, 2 * IW) if upsample else (IH, IW)
+    OH, OW = (VH + pad + pb - k) // stride + 1, (VW + pad + pb - k) // stride + 1
+    Co = W.shape[0]
+    Wm = W.double().reshape(Co, -1)
+    Wa = Wm.abs()
+    out = torch.empty(N, OH, OW, Co, dtype=torch.float64, device=x.device)
+    A = torch.empty_like(out)
+    per = max(1, chunk_bytes // (Cin * k * k * OH * OW * 8 * 2))
+    for n0 in range(0, N, per):
+        xd = x[n0:n0 + per].double()
+        if upsample:
+            xd = xd.repeat_interleave(2, 1).repeat_interleave(2, 2)
+        cols = unfold_nhwc(xd, k, stride, pad, pb)                          # [n, Cin*k*k, OH*OW]
+        out[n0:n0 + per] = torch.einsum("ok,nkp->npo", Wm, cols).reshape(-1, OH, OW, Co)
+        A[n0:n0 + per] = torch.einsum("ok,nkp->npo", Wa, cols.abs_()).reshape(-1, OH, OW, Co)
+        del cols
+    for t in (bias, addvec, residual):
+        if t is None:
+            continue
+        t = t.double()
+        t = t[:, None, None, :] if t.dim() == 2 else t
+        out += t
+        A += t.abs()
+    return out, A
+
+
+def conv_bound(ref_post, A, K, act, bf16_out=True):
+    """Bound of a conv forward output around act(ref64): depth K + 3 (fused adds), activation Lipschitz, one bf16 store."""
+    return store_bound(ACT_L[act] * (K + 3) * U32 * A, ref_post, bf16_out)
+
+
+def stats_ref(o, pairs=True):
+    """Per image and channel pair of a stored NHWC tensor: (sum, sum of squares) and their absolute sums, fp64."""
+    od = o.double()
+    N, H, W, C = od.shape
+    s = od.reshape(N, H * W, C // 2, 2).sum((1, 3))
+    q = od.square().reshape(N, H * W, C // 2, 2).sum((1, 3))
+    sa = od.abs().reshape(N, H * W, C // 2, 2).sum((1, 3))
+    return torch.stack([s, q], -1), torch.stack([sa, q], -1)
+
+
+def stats_depth(HW, P0, folds):
+    return 2 * -(-HW // P0) + 32 * folds + 2
+
+
+# ------------------------------------------------------------------------------------------ GroupNorm
+def gn_ref(x, gamma, beta, groups, eps, silu, scale_shift=None):
+    """fp64 GroupNorm(+FiLM)(+SiLU) of an NHWC tensor and the per-element pieces the bound needs."""
+    xd = x.double()
+    N, H, W, C = xd.shape
+    y = F.group_norm(xd.permute(0, 3, 1, 2), groups, gamma.double(), beta.double(), eps).permute(0, 2, 3, 1)
+    g = xd.reshape(N, H * W, groups, C // groups)
+    m = g.mean((1, 3), keepdim=True)
+    var = (g - m).square().mean((1, 3), keepdim=True)
+    ex2 = g.square().mean((1, 3), keepdim=True)
+    exa = g.abs().mean((1, 3), keepdim=True)
+    rstd = (var + eps).rsqrt()
+    xhat = ((g - m) * rstd).reshape(N, H, W, C)
+    film = torch.ones(N, 1, 1, C, dtype=torch.float64, device=x.device)
+    shift = torch.zeros_like(film)
+    if scale_shift is not None:
+        film = 1 + scale_shift[:, :C].double()[:, None, None, :]
+        shift = scale_shift[:, C:].double()[:, None, None, :]
+        y = y * film + shift
+    yo = act64(y, 3) if silu else y
+    parts = dict(eps=eps, m=m, var=var, ex2=ex2, exa=exa, rstd=rstd, xhat=xhat, film=film, shift=shift, g=g, y=y)
+    return yo, parts
+
+
+def gn_bound(yo, parts, gamma, beta, d, silu):
+    """Element-wise bound of a GroupNorm forward whose statistics are fp32 sums of depth d (see the module docstring)."""
+    p = parts
+    N, H, W, C = yo.shape
+    kappa = p["ex2"] / (p["var"] + p["eps"])                 # E[x^2] / (var + eps): the conditioning term
+    drstd = (1.5 * d + 1) * U32 * kappa + 4 * U32
+    dm = d * U32 * p["exa"]
+    x = p["g"]
+    dxh = ((x - p["m"]).abs() * p["rstd"] * drstd + p["rstd"] * dm + 4 * U32 * (x.abs() + p["m"].abs()) * p["rstd"]).reshape(N, H, W, C)
+    L = 1.1 if silu else 1.0
+    ga, ba = gamma.double().abs(), beta.double().abs()
+    core = L * (ga * p["film"].abs() * dxh + 4 * U32 * ((ga * p["xhat"].abs() + ba) * p["film"].abs() + p["shift"].abs()))
+    return store_bound(core, yo)
+
+
+def gn_fused_bound(yo, parts, gamma, beta, d, silu, dh):
+    """gn_bound plus the propagated error dh (per element) of the GroupNorm's input through the linearised GroupNorm."""
+    p = parts
+    N, H, W, C = yo.shape
+    G = p["g"].shape[2]
+    dhg = dh.reshape(N, H * W, G, C // G)
+    xh = p["xhat"].reshape(N, H * W, G, C // G).abs()
+    lin = (p["rstd"] * (dhg + dhg.mean((1, 3), keepdim=True) + xh * (xh * dhg).mean((1, 3), keepdim=True))).reshape(N, H, W, C)
+    L = 1.1 if silu else 1.0
+    return gn_bound(yo, parts, gamma, beta, d, silu) + L * gamma.double().abs() * p["film"].abs() * lin * (1 + U16)
+
+
+# ------------------------------------------------------------------------------------------ linear
+def bf16_near_tie(v):
+    """Mask of fp64 values within 8 u32 |v| of a bf16 rounding midpoint (an fp32 evaluation may round them either way)."""
+    b = v.to(torch.bfloat16).double()
+    e = torch.floor(torch.log2(b.abs().clamp_min(1e-38)))
+    half = 2.0 ** (e - 8)
+    return ((v - b).abs() - half).abs() <= 8 * U32 * v.abs() + 1e-300
+
+
+def linear_ref(x, W, bias, pre_act, post_act):
+    """fp64 reference of ops.linear and its element-wise bound: x fp32 [P, K], W fp32 [M, K] (bf16-rounded by the pack)."""
+    pre = act64(x.double(), pre_act)
+    a = pre.to(torch.bfloat16).double()
+    Wb = W.to(torch.bfloat16).double()
+    y = a @ Wb.T
+    A = a.abs() @ Wb.abs().T
+    if bias is not None:
+        y, A = y + bias.double(), A + bias.double().abs()
+    tie = (bf16_near_tie(pre) * pre.abs() * U16) @ Wb.abs().T
+    ref = act64(y, post_act)
+    K = x.shape[1]
+    bound = ACT_L[post_act] * ((K + 2) * U32 * A + tie) + 4 * U32 * ref.abs()
+    return ref, bound
+
+
+# ------------------------------------------------------------------------------------------ attention
+def attention_ref(qkv, heads, scale, chunk=4):
+    """fp64 softmax attention of qkv [N, T, 3C] (heads as contiguous channel blocks): o [N, T, C], lse2 [N, heads, T] (log2
+    domain) and the per-row score magnitude max_j sum_d |q_id k_jd| [N, heads, T]."""
+    N, T, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    o = torch.empty(N, T, C, dtype=torch.float64, device=qkv.device)
+    lse = torch.empty(N, heads, T, dtype=torch.float64, device=qkv.device)
+    smag = torch.empty_like(lse)
+    for n0 in range(0, N, chunk):
+        x = qkv[n0:n0 + chunk].double()
+        q, k, v = (x[:, :, i * C:(i + 1) * C].reshape(-1, T, heads, D).transpose(1, 2) for i in range(3))
+        s = scale * q @ k.transpose(-1, -2)
+        lse[n0:n0 + chunk] = torch.logsumexp(s, -1) * LOG2E
+        smag[n0:n0 + chunk] = (scale * q.abs() @ k.abs().transpose(-1, -2)).amax(-1)
+        o[n0:n0 + chunk] = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(-1, T, C)
+    return o, lse, smag
+
+
+def lse_bound(lse2, smag, D, T):
+    return LOG2E * (D + 2) * U32 * smag + (T + 8) * U32 * LOG2E + 4 * U32 * lse2.abs()
+
+
+def attn_blocks(t, heads, rb=128):
+    """[N, T, C] -> (image, head, 128-row block) blocks for Checker.blocks(..., block_dims=3)."""
+    N, T, C = t.shape
+    rb = min(rb, T)
+    return t.reshape(N, T // rb, rb, heads, C // heads).permute(0, 3, 1, 2, 4)

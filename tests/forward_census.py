@@ -1,0 +1,285 @@
+"""Shape census of the forward launches of the sampling and training programs (used by test_hip_forward_shapes.py).
+
+`FwdCensus` wraps the forward `ops` entry points the models call and records a signature for every call made OUTSIDE the
+backward() methods of _EDMUNetFn, _UNetFn and _ValueNetFn: operand shapes plus every field that takes part in choosing a kernel
+or an epilogue, including the conv kernel id dxmi_conv2d_kernel_id reports for the launch (read through an ops.PROFILER, as
+tools/conv_shapes.py does) and the knobs in effect.  The programs (PROGRAMS) run eagerly with graphs off, each under the tuning
+it really uses.  For every GroupNorm row the census also keeps the largest |mean| / std over (image, group) of the activation
+it normalised (`cond`): these are random-init nets, not trained weights, so this measures the conditioning of the census's own
+activations only.
+"""
+import ctypes
+import inspect
+
+import torch
+
+import backward_census
+
+FWD_OPS = ("conv2d", "linear", "groupnorm_silu", "groupnorm_apply", "groupnorm_generic", "block_stats", "fold_stats",
+           "gn_blockstats_to_generic", "attention", "attention_proj", "attn_block", "timestep_embedding", "upsample2x", "pool_act",
+           "value_head")
+THROUGHPUT_KNOBS = (96, 13)          # (conv_ws_min_tiles, conv_sm_mask) under ops.throughput_tuning()
+
+
+def _c(t):
+    return 0 if t is None else int(t.shape[-1])
+
+
+# Dispatch overrides that would make attention_kernel() name a kernel that did not run (csrc/attention.hip attention_fwd_impl)
+ATTN_ENV = ("DXMI_ATTN64", "DXMI_ATTN_GENERIC")
+
+
+def attention_kernel(T, C, heads, proj=False):
+    """The attention kernel dxmi_attention_fwd / dxmi_attention_proj_fwd launch for the shape.  The library exports no query for
+    this choice, so this mirrors attention_fwd_impl (csrc/attention.hip: 256 x 256 single head -> attention256_kernel, D = 256 /
+    128 -> attention_kernel<D>, D = 64 with T % 256 == 0 -> attention64_kernel, else attention_kernel<64>); FwdCensus refuses
+    to record while an ATTN_ENV override is set, and a change of that dispatch must be mirrored here."""
+    D = C // heads
+    if proj:
+        return "attention256<true>"
+    if D == 256 and T == 256 and heads == 1:
+        return "attention256<false>"
+    if D == 64 and T % 256 == 0:
+        return "attention64"
+    return f"attention_kernel<{D}>"
+
+
+class FwdCensus(backward_census.Census):
+    """`with FwdCensus(ops) as c:` ... c.rows = set of forward launch signatures, c.cond[row] = largest |mean| / std seen."""
+
+    def __init__(self, ops):
+        super().__init__(ops)
+        self.cond, self.kid, self.gn_frames = {}, None, []
+        self.sigs = {n: inspect.signature(getattr(ops, n)) for n in FWD_OPS}
+
+    def tuning(self):
+        knobs = (self.ops.get_tuning("conv_ws_min_tiles"), self.ops.get_tuning("conv_sm_mask"))
+        return "throughput" if knobs == THROUGHPUT_KNOBS else "default"
+
+    def _gn_cond(self, row, x, in1, groups):
+        xc = torch.cat([x, in1], -1) if in1 is not None else x
+        N, C = xc.shape[0], xc.shape[-1]
+        g = xc.reshape(N, -1, groups, C // groups).float()
+        m = g.mean((1, 3))
+        sd = (g - m[:, None, :, None]).square().mean((1, 3)).sqrt()
+        r = float((m.abs() / sd.clamp_min(1e-30)).max())
+        self.cond[row] = max(self.cond.get(row, 0.0), round(r, 3))
+
+    def _wrap(self, name, fn):
+        sig = self.sigs[name]
+
+        def w(*a, **kw):
+            if self.depth:
+                return fn(*a, **kw)
+            b = sig.bind(*a, **kw)
+            b.apply_defaults()
+            p = b.arguments
+            if name == "groupnorm_silu":
+                self.gn_frames.append(False)
+                try:
+                    out = fn(*a, **kw)
+                finally:
+                    served = self.gn_frames.pop()
+                if not served:
+                    x, in1 = p["x"], p["in1"]
+                    row = ("gn", "resident", tuple(x.shape), _c(in1), int(p["groups"]), float(p["eps"]), bool(p["silu"]), False, False,
+                           0, 0)
+                    self.rows.add(row)
+                    self._gn_cond(row, x, in1, int(p["groups"]))
+                return out
+            if name == "conv2d":
+                self.kid = None
+                out = fn(*a, **kw)
+                self.rows.add(self._conv_row(p, out))
+                return out
+            out = fn(*a, **kw)
+            row = self._row(name, p, out)
+            self.rows.add(row)
+            if row[0] == "gn":
+                if self.gn_frames:
+                    self.gn_frames[-1] = True
+                self._gn_cond(row, p["x"], p["in1"], int(p["groups"]))
+            return out
+        return w
+
+    def _conv_row(self, p, out):
+        x, pw = p["x"], p["pw"]
+        k = pw.ksize
+        pad = k // 2 if p["pad"] is None else int(p["pad"])
+        av = p["addvec"]
+        addvec = "-" if av is None else ("image" if av.dim() == 2 else "shared")
+        fg = p["fuse_gn"]
+        fuse = None if fg is None else (int(fg[2]), bool(fg[4]), bool(fg[5]))
+        P = 0
+        if p["want_stats"] and out[1] is not None:
+            P = out[1].P
+        kid, gn_out = self.kid
+        if fg is not None:
+            fuse = fuse + (bool(gn_out),)                    # whether the selected kernel wrote the normalised tensor itself
+        return ("conv2d", tuple(x.shape), _c(p["in1"]), pw.Cout, k, bool(pw.k27), int(p["stride"]), pad, p["pad_br"],
+                int(p["upsample"] or 0), p["bias"] is not None, addvec, p["residual"] is not None, p["mask_src"] is not None,
+                int(p["act"]), bool(p["out_nchw_f32"]), bool(p["want_stats"]), fuse, int(p["variant"]), P, self.tuning(), kid)
+
+    def _row(self, name, p, out):
+        ops = self.ops
+        if name == "linear":
+            x, pw = p["x"], p["pw"]
+            P, K = x.shape
+            S = int(ops.load().dxmi_linear_splitk_slices(P, K, pw.Cout)) if (p["splitk"] and p["post_act"] == ops.ACT_NONE) else 1
+            form = "small" if (P <= 4096 and pw.Cout % 4 == 0) else "tiled"      # mirrors dxmi_linear_fwd (csrc/conv_igemm.hip)
+            return ("linear", int(P), int(K), pw.Cout, int(p["pre_act"]), int(p["post_act"]), p["bias"] is not None, form, S)
+        if name in ("groupnorm_apply", "groupnorm_generic"):
+            x, in1 = p["x"], p["in1"]
+            if name == "groupnorm_apply":
+                path, saved, P0, P1 = "apply", False, p["st"].P, (p["st1"].P if p["st1"] is not None else 0)
+            else:
+                path, saved, P0, P1 = "generic", p["saved"] is not None, 0, 0
+            return ("gn", path, tuple(x.shape), _c(in1), int(p["groups"]), float(p["eps"]), bool(p["silu"]),
+                    p["scale_shift"] is not None, saved, P0, P1)
+        if name == "block_stats":
+            return ("block_stats", tuple(p["x"].shape), int(ops.load().dxmi_gn_block_stats_partials(p["x"].shape[1] * p["x"].shape[2])))
+        if name == "fold_stats":
+            N, P, C2, _ = p["st"].buf.shape
+            return ("fold_stats", int(N), int(P), int(C2) * 2, int(p["group"]))
+        if name == "gn_blockstats_to_generic":
+            return ("gn_bs2gen", int(p["N"]), int(p["HW"]), int(p["C0"]), int(p["C1"]), int(p["groups"]), p["st0"].P,
+                    p["st1"].P if p["st1"] is not None else 0)
+        if name == "attention":
+            N, T, C3 = p["qkv"].shape
+            lse = out[1] is not None if p["want_lse"] else False
+            return ("attention", int(N), int(T), C3 // 3, int(p["heads"]), bool(p["want_lse"]), lse,
+                    attention_kernel(T, C3 // 3, int(p["heads"])))
+        if name == "attention_proj":
+            N, T, C3 = p["qkv"].shape
+            return ("attention_proj", int(N), int(T), C3 // 3, int(p["heads"]), bool(p["want_stats"]))
+        if name == "attn_block":
+            return ("attn_block", tuple(p["x"].shape), p["stats"].P, bool(p["want_stats"]))
+        if name == "timestep_embedding":
+            return ("timestep_embedding", int(p["t"].numel()), int(p["dim"]), int(p["order"]), float(p["max_period"]))
+        if name == "upsample2x":
+            return ("upsample2x", tuple(p["x"].shape))
+        if name == "pool_act":
+            return ("pool_act", tuple(p["x"].shape), bool(p["pool"]), int(p["act"]))
+        if name == "value_head":
+            return ("value_head", tuple(p["x"].shape), p["out_w"] is not None)
+        raise KeyError(name)
+
+    def __enter__(self):
+        import os
+        assert not [v for v in ATTN_ENV if v in os.environ], f"unset {ATTN_ENV}: attention_kernel() names the default dispatch"
+        from models.cm import unet_train
+        from models.DxMI import unet_small_train
+        from models import value_train
+        ops, census = self.ops, self
+
+        class _KernelIdProbe(ops.OpProfiler):
+            """Launches unchanged; the conv launch notes the kernel id it runs (tools/conv_shapes.py reads it the same way)."""
+
+            def bracket(self, cls, name, flops, nbytes, fn):
+                return fn()
+
+            def launch_conv(self, d):
+                lib = ops.load()
+                census.kid = (int(lib.dxmi_conv2d_kernel_id(ctypes.byref(d))), bool(d.gn_out))
+                ops.check(lib.dxmi_conv2d_fwd(ctypes.byref(d), ops._stream()), "dxmi_conv2d_fwd")
+
+        self.saved[(ops, "PROFILER")] = ops.PROFILER
+        ops.PROFILER = _KernelIdProbe()
+        for n in FWD_OPS:
+            self.saved[(ops, n)] = getattr(ops, n)
+            setattr(ops, n, self._wrap(n, getattr(ops, n)))
+        for cls in (unet_train._EDMUNetFn, unet_small_train._UNetFn, value_train._ValueNetFn):
+            self.saved[(cls, "backward")] = cls.__dict__["backward"]
+            cls.backward = self._wrap_bwd(cls.__dict__["backward"].__func__)
+        return self
+
+
+def conv_kernel_id(ops, r):
+    """dxmi_conv2d_kernel_id of a conv2d census row under its recorded tuning: a host-side query (no launch, no device memory)."""
+    (_, xs, c1, Cout, k, k27, stride, pad, pad_br, ups, has_bias, addvec, has_res, has_mask, act, nchw, want_stats, fuse, variant,
+     P, tuning, kid) = r
+    d = ops.ConvDesc()
+    if k27:
+        N, _, IH, IW = xs
+        C0 = 3
+    else:
+        N, IH, IW, C0 = xs
+    pb = pad if pad_br is None else pad_br
+    VH, VW = (2 * IH, 2 * IW) if ups else (IH, IW)
+    d.in0, d.in1, d.wpacked, d.out = 16, (16 if c1 else None), 16, 16
+    d.bias = 16 if has_bias else None
+    d.addvec, d.addvec_ld = (16 if addvec != "-" else None), (3 * Cout if addvec == "image" else 0)
+    d.residual, d.mask_src, d.gn_stats, d.gn_out = (16 if has_res else None), (16 if has_mask else None), None, None
+    d.N, d.IH, d.IW, d.C0, d.C1, d.Cout = N, IH, IW, C0, c1, Cout
+    d.OH, d.OW = (VH + pad + pb - k) // stride + 1, (VW + pad + pb - k) // stride + 1
+    d.ksize, d.stride, d.pad, d.upsample, d.act = k, stride, pad, ups, act
+    d.in_mode = ops.IN_NCHW_F32_K27 if k27 else ops.IN_NHWC_BF16
+    d.out_mode = ops.OUT_NCHW_F32 if nchw else ops.OUT_NHWC_BF16
+    d.variant = variant
+    tune = ops.throughput_tuning() if tuning == "throughput" else backward_census._nullctx()
+    with tune:
+        return int(ops.load().dxmi_conv2d_kernel_id(ctypes.byref(d)))
+
+
+def cifar10_sample(device, B, T):
+    """VARSampler.sample of generate_cifar10.py (cifar10_T10 DDPM U-Net) at batch B, T steps, random init."""
+    import configs_builtin
+    from models.DxMI.unet_small import Model
+    from models.DxMI.var_sampler import VARSampler
+    kw = {k: v for k, v in configs_builtin.CONFIGS["cifar10_T10"]["sampler_net"].items() if k != "_target_"}
+    torch.manual_seed(0)
+    sampler = VARSampler(Model(**kw), T, [3, 32, 32], trainable_beta="fix_last").to(device).eval()
+    sampler.use_graph = False
+    with torch.no_grad():
+        sampler.sample(B, device=device)
+    torch.cuda.synchronize()
+
+
+def edm_sample(device, name, B, class_cond):
+    """OpenAIDiffusion.sample of generate_large.py on the named EDM / ADM net, set up as bench.py's generation leg sets it up
+    (random init, zero-initialised layers given weights); class_cond: one random label per image."""
+    import configs_builtin
+    from models.cm.script_util import create_model_and_diffusion
+    from models.DxMI.openai_diffusion import OpenAIDiffusion
+    cfg = configs_builtin.get(name)
+    torch.manual_seed(0)
+    with torch.device(device):
+        net, diffusion = create_model_and_diffusion(**cfg.diffusion)
+    with torch.no_grad():
+        for p in net.parameters():
+            if float(p.abs().max()) == 0:
+                torch.nn.init.normal_(p, std=0.02)
+    s = OpenAIDiffusion(net, diffusion, **cfg.sampler)
+    net.to(device).eval()
+    s.use_graph = False
+    kw = {}
+    if class_cond:
+        kw["i_class"] = torch.randint(0, 1000, (B,), device=device, generator=torch.Generator(device=device).manual_seed(1))
+    with torch.no_grad():
+        s.sample(B, device=device, **kw)
+    torch.cuda.synchronize()
+    del s, net
+
+
+# program -> (runner(device), tuning)
+PROGRAMS = {
+    "cifar10_sample_T10_b256": (lambda d: cifar10_sample(d, 256, 10), "default"),
+    "cifar10_sample_T10_b32": (lambda d: cifar10_sample(d, 32, 10), "default"),
+    "cifar10_sample_T4_b128": (lambda d: cifar10_sample(d, 128, 4), "default"),
+    "cifar10_train_b256": (lambda d: backward_census.cifar10_step(d, 256), "throughput"),
+    "cifar10_train_b128": (lambda d: backward_census.cifar10_step(d, 128), "throughput"),
+    "cifar10_train_b32": (lambda d: backward_census.cifar10_step(d, 32), "throughput"),
+    "imagenet64_sample_b100": (lambda d: edm_sample(d, "imagenet64_T10", 100, True), "default"),
+    "imagenet64_train_b16": (lambda d: backward_census.imagenet64_step(d, 16), "throughput"),
+    "lsun_sample_T4_b16": (lambda d: edm_sample(d, "lsun_bedroom_T4", 16, False), "default"),
+}
+
+
+def record(ops, program, device="cuda:0"):
+    """(rows, cond) of one program's forward launches, under the tuning the program uses."""
+    run, tuning = PROGRAMS[program]
+    tune = ops.throughput_tuning() if tuning == "throughput" else backward_census._nullctx()
+    with tune, FwdCensus(ops) as c:
+        run(device)
+    torch.cuda.empty_cache()
+    return c.rows, c.cond

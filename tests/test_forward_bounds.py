@@ -1,0 +1,281 @@
+"""The forward error bounds (tests/forward_bounds.py) are tight enough to catch the bugs a forward kernel typically has.
+
+CPU only.  Each case builds the fp64 reference, an fp32 computation organised the way the kernel organises it (bf16 operands,
+fp32 accumulation, one bf16 store; one-pass fp32 GroupNorm statistics; bf16 P in attention), and mutants that model real
+kernel bugs, judged at the depth of a real census row.  The checker must accept the fp32 computation and reject every mutant.
+"""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from backward_bounds import BoundError
+from forward_bounds import (LOG2E, FwdChecker, act64, attention_ref, attn_blocks, conv_bound, conv_fwd_ref, gn_bound, gn_ref,
+                            linear_ref, lse_bound, stats_depth, stats_ref)
+from backward_bounds import U16
+
+
+def bf(t):
+    return t.to(torch.bfloat16).double()
+
+
+def must_reject(fn):
+    with pytest.raises(BoundError):
+        fn()
+
+
+def trunc_bf16(t):
+    """bf16 by truncation (round toward zero) instead of round to nearest even."""
+    i = t.float().contiguous().view(torch.int32) & ~0xFFFF
+    return i.view(torch.float32).double()
+
+
+# ------------------------------------------------------------------------------------------ conv
+def conv_fp32(x, W, bias=None, addvec=None, residual=None, stride=1, pad=1, pad_br=None, act=0):
+    """fp32 conv on bf16 operands + fused adds + activation, one round-to-nearest bf16 store (the kernel's arithmetic)."""
+    pb = pad if pad_br is None else pad_br
+    xn = F.pad(x.float().permute(0, 3, 1, 2), (pad, pb, pad, pb))
+    y = F.conv2d(xn, W.float(), stride=stride).permute(0, 2, 3, 1)
+    for t in (bias, addvec, residual):
+        if t is not None:
+            t = t.float()
+            y = y + (t[:, None, None, :] if t.dim() == 2 else t)
+    return bf(act64(y.double(), act).float())
+
+
+def _conv_case(g, N, H, W, C0, Co, C1=0, k=3):
+    x0 = bf(torch.randn(N, H, W, C0, generator=g))
+    x1 = bf(torch.randn(N, H, W, C1, generator=g) * 2) if C1 else None
+    x = torch.cat([x0, x1], 3) if C1 else x0
+    Wt = bf(torch.randn(Co, C0 + C1, k, k, generator=g) * ((C0 + C1) * k * k) ** -0.5)
+    bias = torch.randn(Co, generator=g).double() * 0.1
+    return x0, x1, x, Wt, bias
+
+
+def test_conv_bound_rejects_halo_tile_block_and_store_bugs():
+    """Depth of the CIFAR-10 / LSUN 256 -> 256 3x3 rows (K = 2304); tiles of 256 pixels (8 rows x 32 columns of a 32x32 map)."""
+    g = torch.Generator().manual_seed(0)
+    N, H, W, C, Co = 2, 32, 32, 256, 128
+    x, _, _, Wt, bias = _conv_case(g, N, H, W, C, Co)
+    av = torch.randn(N, Co, generator=g).double() * 0.3
+    ref, A = conv_fwd_ref(x, Wt, bias, av)
+    K = C * 9
+    bound = conv_bound(ref, A, K, 0)
+    ck = FwdChecker()
+    got = conv_fp32(x, Wt, bias, av)
+    assert ck.within("conv", got, ref, bound) <= 1.0
+    # one halo row read one pixel to the left at a single tile seam: image 1, the tile of output rows 8..15 reads input row 7
+    xm = x[1:2].clone()
+    xm[0, 7, 1:] = x[1, 7, :-1]
+    bad = ref.clone()
+    bad[1, 8] = conv_fwd_ref(xm, Wt, bias, av[1:2])[0][0, 8]
+    must_reject(lambda: ck.within("conv", bad, ref, bound))
+    # two 64-cout blocks swapped
+    sw = ref.clone()
+    sw[..., :64], sw[..., 64:128] = ref[..., 64:128], ref[..., :64]
+    must_reject(lambda: ck.within("conv", sw, ref, bound))
+    # the addvec row of the neighbouring image
+    must_reject(lambda: ck.within("conv", conv_fwd_ref(x, Wt, bias, av.flip(0))[0], ref, bound))
+    # the bf16 store truncating instead of rounding to nearest even
+    must_reject(lambda: ck.within("conv", trunc_bf16(conv_fwd_ref(x, Wt, bias, av)[0]), ref, bound))
+
+
+def test_conv_bound_rejects_a_dropped_ragged_tile():
+    """Five 8x8 images are 1.25 tiles of 256 pixels: the last tile holds one image and zero padding."""
+    g = torch.Generator().manual_seed(1)
+    x, _, _, Wt, bias = _conv_case(g, 5, 8, 8, 256, 128)
+    ref, A = conv_fwd_ref(x, Wt, bias)
+    bound = conv_bound(ref, A, 256 * 9, 0)
+    ck = FwdChecker()
+    assert ck.within("conv", conv_fp32(x, Wt, bias), ref, bound) <= 1.0
+    bad = ref.clone()
+    bad[4] = 0
+    must_reject(lambda: ck.within("conv", bad, ref, bound))
+
+
+def test_conv_bound_rejects_a_zero_upper_half_of_the_last_cout_tile():
+    """576 couts (ImageNet-64) are 4.5 tiles of 128: the half-empty last tile's upper 32 couts left at zero."""
+    g = torch.Generator().manual_seed(2)
+    x, _, _, Wt, bias = _conv_case(g, 2, 8, 8, 192, 576)
+    ref, A = conv_fwd_ref(x, Wt, bias)
+    bound = conv_bound(ref, A, 192 * 9, 0)
+    ck = FwdChecker()
+    assert ck.within("conv", conv_fp32(x, Wt, bias), ref, bound) <= 1.0
+    bad = ref.clone()
+    bad[..., 544:] = 0
+    must_reject(lambda: ck.within("conv", bad, ref, bound))
+
+
+def test_conv_bound_rejects_the_wrong_source_and_stride2_padding_side():
+    g = torch.Generator().manual_seed(3)
+    x0, x1, x, Wt, bias = _conv_case(g, 2, 16, 16, 128, 128, C1=128, k=1)
+    ref, A = conv_fwd_ref(x, Wt, bias)
+    bound = conv_bound(ref, A, 256, 0)
+    ck = FwdChecker()
+    assert ck.within("conv1x1", conv_fp32(x, Wt, bias, pad=0), ref, bound) <= 1.0
+    must_reject(lambda: ck.within("conv1x1", conv_fwd_ref(torch.cat([x0, x0], 3), Wt, bias)[0], ref, bound))
+    # DDPM downsample: 3x3 stride 2, zeros at the bottom / right only (pad 0, pad_br 1); the bug pads top / left
+    xs, _, _, Ws, bs = _conv_case(g, 2, 16, 16, 256, 128)
+    ref, A = conv_fwd_ref(xs, Ws, bs, stride=2, pad=0, pad_br=1)
+    bound = conv_bound(ref, A, 256 * 9, 0)
+    assert ck.within("conv_s2", conv_fp32(xs, Ws, bs, stride=2, pad=0, pad_br=1), ref, bound) <= 1.0
+    must_reject(lambda: ck.within("conv_s2", conv_fwd_ref(xs, Ws, bs, stride=2, pad=1, pad_br=0)[0], ref, bound))
+
+
+def test_stats_bound_rejects_a_dropped_partial():
+    g = torch.Generator().manual_seed(4)
+    o = bf(torch.randn(2, 64, 64, 128, generator=g) + 3)
+    P = 32
+    parts = o.float().reshape(2, P, -1, 64, 2)
+    st = torch.stack([parts.sum((2, 4)), parts.square().sum((2, 4))], -1)      # fp32 partials [N, P, C/2, 2]
+    S, Sa = stats_ref(o)
+    ck = FwdChecker()
+    c = stats_depth(64 * 64, P, 1)
+    assert ck.fp32("stats", st.double().sum(1), S, Sa, c) <= 1.0
+    must_reject(lambda: ck.fp32("stats", st.double().sum(1) - st[:, 7].double(), S, Sa, c))
+
+
+# ------------------------------------------------------------------------------------------ GroupNorm
+def gn_fp32(x, gamma, beta, groups, eps, silu, ss=None, stats=None):
+    """One-pass fp32 statistics (sum and sum of squares), var = q / n - m^2, then the affine, FiLM, SiLU in fp32, bf16 store."""
+    xf = x.float()
+    N, H, W, C = xf.shape
+    g = xf.reshape(N, H * W, groups, C // groups)
+    n = H * W * (C // groups)
+    s, q = (g.sum((1, 3)), g.square().sum((1, 3))) if stats is None else stats
+    m = s / n
+    var = q / n - m * m
+    rstd = torch.rsqrt(var + eps)
+    y = ((g - m[:, None, :, None]) * rstd[:, None, :, None]).reshape(N, H, W, C) * gamma.float() + beta.float()
+    if ss is not None:
+        y = y * (1 + ss[:, None, None, :C].float()) + ss[:, None, None, C:].float()
+    if silu:
+        y = F.silu(y)
+    return bf(y)
+
+
+def _gn_x(g, N, H, W, C, cond, G=32):
+    """One offset per group, uniform in [-cond, cond], the largest of each image set to cond: (image, group) |mean| / std spreads
+    up to cond.  Image 0's first group is zero-mean with a tiny variance, where eps matters."""
+    off = (torch.rand(N, G, generator=g) * 2 - 1) * cond
+    off[torch.arange(N), off.abs().argmax(1)] = cond
+    x = torch.randn(N, H, W, C, generator=g) + off.repeat_interleave(C // G, 1)[:, None, None, :]
+    x[0, :, :, :C // G] = 0.003 * torch.randn(H, W, C // G, generator=g)
+    return bf(x)
+
+
+def test_groupnorm_bound_accepts_one_pass_statistics_and_rejects_statistics_bugs():
+    """ImageNet-64's 192 channels in 32 groups of 6 on 16x16 maps, with a mean offset (|mean| / std up to ~50), FiLM, SiLU."""
+    g = torch.Generator().manual_seed(5)
+    N, H, W, C, G, eps = 3, 16, 16, 192, 32, 1e-5
+    x = _gn_x(g, N, H, W, C, 50.0)
+    gamma, beta = (1 + 0.3 * torch.randn(C, generator=g)).double(), (0.3 * torch.randn(C, generator=g)).double()
+    ss = 0.3 * torch.randn(N, 2 * C, generator=g).double()
+    yo, parts = gn_ref(x, gamma, beta, G, eps, True, ss)
+    assert float((parts["m"].abs() / parts["var"].sqrt()).max()) > 45          # the conditioning really reaches ~50
+    d = H * W * C // G + 2
+    bound = gn_bound(yo, parts, gamma, beta, d, True)
+    ck = FwdChecker()
+    assert ck.within("gn", gn_fp32(x, gamma, beta, G, eps, True, ss), yo, bound) <= 1.0
+    # image 1 normalised with image 2's statistics
+    xf = x.float()
+    gg = xf.reshape(N, -1, G, C // G)
+    s, q = gg.sum((1, 3)), gg.square().sum((1, 3))
+    s2, q2 = s.clone(), q.clone()
+    s2[1], q2[1] = s[2], q[2]
+    must_reject(lambda: ck.within("gn", gn_fp32(x, gamma, beta, G, eps, True, ss, stats=(s2, q2)), yo, bound))
+    # group boundaries off by one channel (groups of 6 read channels 1..6, 7..12, ...)
+    sh = torch.roll(x, -1, dims=3)
+    bad = torch.roll(gn_ref(sh, gamma.roll(-1), beta.roll(-1), G, eps, True, torch.cat([ss[:, :C].roll(-1, 1), ss[:, C:].roll(-1, 1)], 1))[0], 1, dims=3)
+    must_reject(lambda: ck.within("gn", bad, yo, bound))
+    # eps 1e-6 in place of 1e-5 (image 0's first group has a tiny variance)
+    must_reject(lambda: ck.within("gn", gn_fp32(x, gamma, beta, G, 1e-6, True, ss), yo, bound))
+    # the neighbouring image's FiLM scale
+    ss_bad = ss.clone()
+    ss_bad[1, :C] = ss[2, :C]
+    must_reject(lambda: ck.within("gn", gn_fp32(x, gamma, beta, G, eps, True, ss_bad), yo, bound))
+
+
+def test_groupnorm_bound_rejects_a_dropped_source_share_and_a_dropped_partial():
+    """[in0 | in1] with C0 = 64, C1 = 128 in groups of 6: group 10 (channels 60..65) straddles the boundary.  The streaming apply
+    with P = 8 statistics partials per source."""
+    g = torch.Generator().manual_seed(6)
+    N, H, W, C0, C1, G, eps, P = 2, 16, 16, 64, 128, 32, 1e-6, 8
+    C = C0 + C1
+    x = _gn_x(g, N, H, W, C, 8.0)
+    gamma, beta = (1 + 0.3 * torch.randn(C, generator=g)).double(), (0.3 * torch.randn(C, generator=g)).double()
+    yo, parts = gn_ref(x, gamma, beta, G, eps, True)
+    bound = gn_bound(yo, parts, gamma, beta, P + C // G // 2 + 2, True)
+    ck = FwdChecker()
+    pix = x.float().reshape(N, P, -1, G, C // G)
+    ps, pq = pix.sum((2, 4)), pix.square().sum((2, 4))                        # fp32 partials per group
+    assert ck.within("gn_apply", gn_fp32(x, gamma, beta, G, eps, True, stats=(ps.sum(1), pq.sum(1))), yo, bound) <= 1.0
+    # partial 3 of every group left out
+    must_reject(lambda: ck.within("gn_apply", gn_fp32(x, gamma, beta, G, eps, True,
+                                                       stats=(ps.sum(1) - ps[:, 3], pq.sum(1) - pq[:, 3])), yo, bound))
+    # the straddling group's in1 share (channels 64, 65) dropped from its statistics
+    xf = x.float().reshape(N, H * W, C)
+    s, q = ps.sum(1).clone(), pq.sum(1).clone()
+    s[:, 10] -= xf[:, :, 64:66].sum((1, 2))
+    q[:, 10] -= xf[:, :, 64:66].square().sum((1, 2))
+    must_reject(lambda: ck.within("gn_apply", gn_fp32(x, gamma, beta, G, eps, True, stats=(s, q)), yo, bound))
+
+
+# ------------------------------------------------------------------------------------------ attention
+def attention_fp32(qkv, heads, scale, kswap=False):
+    """fp32 scores, exp2 with the row max, P rounded to bf16 for P V, fp32 row sums; lse in the log2 domain; bf16 output."""
+    N, T, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    q, k, v = (qkv[:, :, i * C:(i + 1) * C].float().reshape(N, T, heads, D).transpose(1, 2) for i in range(3))
+    if kswap:
+        k = k.roll(1, dims=1)
+    s2 = (scale * q @ k.transpose(-1, -2)) * LOG2E
+    m = s2.amax(-1, keepdim=True)
+    p = torch.exp2(s2 - m)
+    l = p.sum(-1, keepdim=True)
+    o = (p.to(torch.bfloat16).float() @ v) / l
+    return bf(o.transpose(1, 2).reshape(N, T, C)), (m + torch.log2(l)).squeeze(-1).double()
+
+
+def test_attention_bounds_reject_head_and_lse_bugs():
+    """T = 256 (16x16 maps), 4 heads of 64 (the ImageNet-64 widths are 64 per head)."""
+    g = torch.Generator().manual_seed(7)
+    N, T, heads, D = 2, 256, 4, 64
+    C = heads * D
+    qkv = bf(torch.randn(N, T, 3 * C, generator=g))
+    scale = D ** -0.5
+    o, lse2, smag = attention_ref(qkv, heads, scale)
+    tol = 8 * U16
+    ck = FwdChecker()
+    got, lse = attention_fp32(qkv, heads, scale)
+    assert ck.blocks("attn", attn_blocks(got, heads), attn_blocks(o, heads), tol, 3) <= 1.0
+    lb = lse_bound(lse2, smag, D, T)
+    assert ck.within("lse2", lse, lse2, lb) <= 1.0
+    bad, _ = attention_fp32(qkv, heads, scale, kswap=True)
+    must_reject(lambda: ck.blocks("attn", attn_blocks(bad, heads), attn_blocks(o, heads), tol, 3))
+    lb_bad = lse.clone()
+    lb_bad[1, 2, 128:] = lse[1, 3, 128:]
+    must_reject(lambda: ck.within("lse2", lb_bad, lse2, lb))
+    must_reject(lambda: ck.within("lse2", lse / LOG2E, lse2, lb))      # natural log instead of log2
+
+
+# ------------------------------------------------------------------------------------------ linear
+def test_linear_bound_rejects_the_dropped_last_round_of_k_steps():
+    """K = 192 (the ImageNet-64 timestep MLP's input) is 12 k16 steps: one round of eight loads in flight plus a partial round
+    of four, which the `ks` clamp of linear_small_kernel keeps in range; dropping that partial round loses K 128..191."""
+    g = torch.Generator().manual_seed(8)
+    P, K, M = 100, 192, 768
+    x = torch.randn(P, K, generator=g)
+    W = torch.randn(M, K, generator=g) * K ** -0.5
+    b = torch.randn(M, generator=g) * 0.1
+    for pre, post in ((0, 3), (3, 0)):
+        ref, bound = linear_ref(x, W, b, pre, post)
+        ck = FwdChecker()
+        a = bf(act64(x.double(), pre).float()).float()
+        Wb = bf(W).float()
+        got = act64((a @ Wb.T + b).double(), post).float()
+        assert ck.within("linear", got, ref, bound) <= 1.0
+        short = act64((a[:, :128] @ Wb[:, :128].T + b).double(), post)
+        must_reject(lambda: ck.within("linear", short, ref, bound))
