@@ -17,7 +17,17 @@
 // vmcnt retires in order: every wait below counts exactly the DMAs / stores that are younger than the chunk it needs.
 // The CT cout tiles of one pixel stream sit on one XCD, adjacent in dispatch order (they read the same input from that
 // XCD's L2 at about the same time: measured 18 MB of HBM fetch for the 33.5 MB q|k|v input read by six cout tiles).
+//
+// GN = true (dxmi_groupnorm_silu_shortcut): the nin_shortcut of a ResnetBlock whose channel count changes reads the same input
+// [x0 | x1] as its norm1 GroupNorm(+SiLU) (models/DxMI/unet_small.py _resblock).  Here the chunks that land in LDS for the MFMAs are
+// also normalised: after a chunk's MFMAs are issued, every thread reads its 16-byte pieces back (ds_read_b128), applies the
+// per-(image, channel) (scale, offset) of the table gn_finalize_kernel formed (the same bits as gn_apply_kernel's prologue,
+// gn_common.h), SiLU, rounds to bf16 and stores y — 16 lanes per pixel row, two whole 128-byte lines.  The CT cout tiles of a pixel
+// stream walk the same tiles, so they split each chunk's 64 pixels between them (64 / CT each): every input element is normalised
+// and stored exactly once.  The chunk's 1 KB slice of the table rides the ring as a fifth DMA per wave (256 B each).  The y stores
+// are vector-memory ops too: each chunk wait below also counts those issued after the awaited chunk's DMAs.
 #include "conv_common.h"
+#include "gn_common.h"
 #include <stdlib.h>
 
 namespace {
@@ -29,12 +39,33 @@ __device__ __forceinline__ void rw_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 
 constexpr int RW_CHUNK = 64 * 256;      // 64 pixels x 128 channels bf16
 constexpr int RW_RO = 64 * 256;         // 64 pixels x 128 couts bf16 (4 KB per wave)
+constexpr int RW_TBL = 128 * 8;         // GN: (scale, offset) fp32 pairs of one chunk's 128 channels, per ring slot
+
+// GN side output (see above); unused when GN = false
+struct RwGn {
+    const float* ab;     // [N][K][2] per-(image, input channel) scale / offset (gn_finalize_launch)
+    bf16* y;             // [N * HW][K]: GroupNorm(+SiLU) of [in0 | in1]
+    int HW, silu;
+};
+
+// s_waitcnt vmcnt(n) for a wave-uniform n known only at run time (0 <= n <= 63)
+__device__ __forceinline__ void rw_wait_vm(int n) {
+    switch (__builtin_amdgcn_readfirstlane(n)) {
+#define RW_C(k) case k: RW_WAIT_VM(k); break;
+#define RW_C8(k) RW_C(k) RW_C(k + 1) RW_C(k + 2) RW_C(k + 3) RW_C(k + 4) RW_C(k + 5) RW_C(k + 6) RW_C(k + 7)
+    RW_C8(0) RW_C8(8) RW_C8(16) RW_C8(24) RW_C8(32) RW_C8(40) RW_C8(48) RW_C8(56)
+#undef RW_C8
+#undef RW_C
+    default: RW_WAIT_VM(0);
+    }
+}
 
 // NCH: 128-channel chunks per tile (K / 128); R: ring slots (R - 1 <= 2 NCH: the stream runs up to two tiles ahead);
-// RES: residual present
-template <int NCH, int R, bool RES>
-__global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_kernel(ConvArgs p) {
+// RES: residual present; GN: GroupNorm(+SiLU) side output of the input (no residual then)
+template <int NCH, int R, bool RES, bool GN>
+__global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_kernel(ConvArgs p, RwGn q) {
     static_assert(R - 1 <= 4 * NCH && R >= 3 && 4 * (R - 2) + 4 * (RES ? 8 : 4) < 64, "ring depth");
+    static_assert(!(GN && RES) && (!GN || 5 * (R - 2) + 4 * 4 + 4 * (R - 1) < 64), "GN side output: no residual, vmcnt range");
     constexpr int BOPS = RES ? 8 : 4;            // per-wave vmem ops at a tile boundary: 4 row stores (+ 4 residual DMAs)
     constexpr int NYOUNG = 4 * (R - 2);          // DMAs of the R-2 chunks issued after the one being awaited
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -43,6 +74,7 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     char* const ro = smem + R * RW_CHUNK + wave * 4096;       // this wave's [64 px][32 co] slice
+    char* const tbl = smem + R * RW_CHUNK + RW_RO;             // GN: R table slices, one per ring slot
     // block -> (cout tile, pixel stream): blocks b, b+8, .. share an XCD
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
     const int cot = j % p.CT;
@@ -82,6 +114,11 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
         const bf16* src = first ? p.in0 : p.in1;
         const int Cs = first ? p.C0 : p.C1;
         const int coff = first ? cbase : cbase - p.C0;
+        if constexpr (GN) {          // the chunk's table slice: wave w moves its bytes 256 w .. 256 w + 255, 4 per lane
+            const int n = (int)P0 / q.HW;
+            __builtin_amdgcn_global_load_lds(RW_GPTR(q.ab + ((size_t)n * (NCH * 128) + cbase) * 2 + wave * 64 + lane),
+                                             RW_LPTR(tbl + slot * RW_TBL + wave * 256), 4, 0, 0);
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             __builtin_amdgcn_global_load_lds(RW_GPTR(src + (P0 + dpx[u]) * Cs + coff + ds8[u]),
@@ -120,6 +157,10 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
         for (int ks = 0; ks < 8; ++ks) boff[ks] = px * 256 + (((ks * 2 + h) ^ (px & 15)) << 4);
     }
 
+    // GN: this thread's pieces of every chunk — channels 8 gs .. 8 gs + 7 of pixels gpx0 + 16 i, i < gnp (the cout tile's share)
+    const int gnp = GN ? 4 / p.CT : 0;
+    const int gs = tid & 15, gpx0 = cot * (64 / p.CT) + (tid >> 4);
+
     int slot = 0;                                // ring slot of the chunk being consumed
     for (int ti = 0; ti < ntiles; ++ti) {
         f32x16 acc[2];
@@ -136,6 +177,7 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
             const int kmax = R - 1 - c > 0 ? (R - 1 - c + NCH - 1) / NCH : 0;
             const int nbnd = ti < kmax ? ti : kmax;
             if (g + R - 2 >= gtot) RW_WAIT_VM(0);
+            else if (GN) rw_wait_vm(5 * (R - 2) + nbnd * BOPS + (g < R - 1 ? g : R - 1) * gnp);   // + the y stores of the last R-1 chunks
             else if (nbnd == 0) RW_WAIT_VM(NYOUNG);
             else if (nbnd == 1) RW_WAIT_VM(NYOUNG + BOPS);
             else if (nbnd == 2) RW_WAIT_VM(NYOUNG + 2 * BOPS);
@@ -155,6 +197,21 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
                     const bf16x8 b = *reinterpret_cast<const bf16x8*>(img + boff[ks] + nb * (32 * 256));
                     acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[c * 8 + ks], b, acc[nb], 0, 0, 0);
                 }
+            if constexpr (GN) {
+                float ga[8], gb[8];
+                const f32x4* t = reinterpret_cast<const f32x4*>(tbl + slot * RW_TBL + gs * 64);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4 v = t[i];
+                    ga[2 * i] = v[0]; gb[2 * i] = v[1]; ga[2 * i + 1] = v[2]; gb[2 * i + 1] = v[3];
+                }
+                bf16* const yt = q.y + (size_t)(stream + ti * nstreams) * 64 * (NCH * 128) + c * 128 + gs * 8;
+                for (int i = 0; i < gnp; ++i) {
+                    const int px = gpx0 + 16 * i;
+                    const bf16x8 v = *reinterpret_cast<const bf16x8*>(img + px * 256 + ((gs ^ (px & 15)) << 4));
+                    *reinterpret_cast<bf16x8*>(yt + (size_t)px * (NCH * 128)) = gn_norm8(v, ga, gb, q.silu);
+                }
+            }
             slot = slot + 1 == R ? 0 : slot + 1;
         }
         // ---- tile end, wave-private.  The residual DMAs of this tile are older than the 4*NCH chunk DMAs issued since
@@ -200,14 +257,38 @@ int rw_launch(const ConvArgs& b, int grid, hipStream_t st) {
     const size_t lds = (size_t)R * RW_CHUNK + RW_RO;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw_kernel<NCH, R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw_kernel<NCH, R, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw_kernel<NCH, R, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw_kernel<NCH, R, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    if (b.residual) hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, true>), dim3(grid), dim3(256), lds, st, b);
-    else hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, false>), dim3(grid), dim3(256), lds, st, b);
+    const RwGn none = {};
+    if (b.residual) hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, true, false>), dim3(grid), dim3(256), lds, st, b, none);
+    else hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, false, false>), dim3(grid), dim3(256), lds, st, b, none);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(1x1 rw)");
     return DXMI_OK;
+}
+
+template <int NCH, int R>
+int rw_launch_gn(const ConvArgs& b, const RwGn& g, int grid, hipStream_t st) {
+    const size_t lds = (size_t)R * (RW_CHUNK + RW_TBL) + RW_RO;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw_kernel<NCH, R, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, false, true>), dim3(grid), dim3(256), lds, st, b, g);
+    DXMI_CHECK_LAUNCH("dxmi_groupnorm_silu_shortcut");
+    return DXMI_OK;
+}
+
+// Tiling of conv1x1_rw_kernel: pixel tiles, cout tiles, and whole XCD groups of CT cout tiles with one / two workgroups per CU
+int rw_grid(ConvArgs& b) {
+    const int K = b.C0 + b.C1;
+    b.PT = (int)((long)b.N * b.OH * b.OW / 64);
+    b.CT = b.Cout / 128;
+    b.tile_px = 64;
+    const int per_xcd = K > 384 ? 32 : 64;                // co-resident workgroups per XCD (one / two per CU)
+    return 8 * b.CT * (per_xcd / b.CT);
 }
 
 }  // namespace
@@ -228,12 +309,8 @@ int conv1x1_rw_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
         return DXMI_OK;
     }
     ConvArgs b = a;
-    b.PT = (int)(px / 64);
-    b.CT = a.Cout / 128;
-    b.tile_px = 64;
-    if (b.CT > 32) return 1;
-    const int per_xcd = K > 384 ? 32 : 64;                // co-resident workgroups per XCD (one / two per CU)
-    const int grid = 8 * b.CT * (per_xcd / b.CT);         // whole XCD groups of CT cout tiles
+    if (a.Cout / 128 > 32) return 1;
+    const int grid = rw_grid(b);
     switch (K / 128) {
     // two chunks (32 KB) in flight per workgroup, 64 KB of LDS -> two workgroups per CU.  Measured at 256 -> 768 @16x16, B = 256:
     // one workgroup per CU with seven chunks in flight 60 us, two with two chunks each 42 us — a workgroup's own issue
@@ -242,5 +319,52 @@ int conv1x1_rw_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
     case 2: return rw_launch<2, 3>(b, grid, st);
     case 3: return rw_launch<3, 3>(b, grid, st);
     default: return rw_launch<4, 6>(b, grid, st);         // K = 512: 128 weight registers, one workgroup per CU, deeper ring
+    }
+}
+
+// dxmi_groupnorm_silu_shortcut: K / 128 when `d` is a shortcut conv dxmi_conv2d_fwd runs on conv1x1_rw_kernel<K/128, R, false> (so
+// sc is that kernel's bits) and the GroupNorm of its input fits the side output; 0 otherwise
+static int gn_shortcut_nch(const dxmi_conv_desc* d, int groups) {
+    if (!d || d->ksize != 1 || d->stride != 1 || d->pad != 0 || d->upsample || d->residual || d->addvec || d->mask_src || d->gn_stats ||
+        d->gn_out || d->act != DXMI_ACT_NONE || d->variant != 0 || d->in_mode != DXMI_IN_NHWC_BF16 || d->out_mode != DXMI_OUT_NHWC_BF16)
+        return 0;
+    const int K = d->C0 + d->C1, CT = d->Cout / 128;
+    if (d->IH != d->OH || d->IW != d->OW || (d->OH * d->OW) % 64 != 0) return 0;       // 64-pixel tiles inside one image
+    if (CT != 1 && CT != 2 && CT != 4) return 0;                                          // the CT tiles split a chunk's 64 pixels
+    if (groups <= 0 || groups > 32 || K % groups != 0 || (K / groups) % 2 != 0 || d->C1 % 8 != 0) return 0;
+    const int id = dxmi_conv2d_kernel_id(d);
+    const int nch = K / 128;
+    if (K % 128 != 0 || nch < 1 || nch > 4 || id != 500000 + nch * 1000 + (nch > 3 ? 6 : 3) * 10) return 0;
+    return nch;
+}
+
+extern "C" int dxmi_groupnorm_silu_shortcut_supported(const dxmi_conv_desc* d, int32_t groups) {
+    return gn_shortcut_nch(d, groups) > 0 ? 1 : 0;
+}
+
+extern "C" int dxmi_groupnorm_silu_shortcut(const dxmi_conv_desc* d, const float* stats0, int32_t P0, const float* stats1, int32_t P1,
+                                            const float* gamma, const float* beta, int32_t groups, float eps, int32_t apply_silu, void* y,
+                                            float* ab_workspace, void* stream) {
+    DXMI_CHECK_ARG(d && d->in0 && d->wpacked && d->out && y && ab_workspace && stats0 && gamma && beta && P0 > 0,
+                   "dxmi_groupnorm_silu_shortcut: null pointer");
+    DXMI_CHECK_ARG(d->C1 == 0 || (d->in1 && stats1 && P1 > 0), "dxmi_groupnorm_silu_shortcut: C1>0 needs in1 and stats1");
+    const int nch = gn_shortcut_nch(d, groups);
+    if (nch == 0) return 1;                                  // out of scope: nothing launched, the caller runs the two ops
+    const int HW = d->OH * d->OW;
+    int rc = gn_finalize_launch(stats0, P0, d->C0, stats1, P1, d->C1, gamma, beta, ab_workspace, d->N, HW, groups, eps, (hipStream_t)stream);
+    if (rc != DXMI_OK) return rc;
+    ConvArgs b = {};
+    b.in0 = (const bf16*)d->in0; b.in1 = (const bf16*)d->in1; b.w = (const bf16*)d->wpacked; b.bias = d->bias; b.out = d->out;
+    b.N = d->N; b.IH = d->IH; b.IW = d->IW; b.C0 = d->C0; b.C1 = d->C1; b.OH = d->OH; b.OW = d->OW; b.Cout = d->Cout;
+    b.ksize = 1; b.stride = 1; b.act = DXMI_ACT_NONE; b.in_mode = DXMI_IN_NHWC_BF16; b.out_mode = DXMI_OUT_NHWC_BF16;
+    b.CB = (d->Cout + 31) / 32;
+    const int grid = rw_grid(b);
+    const RwGn g = {ab_workspace, (bf16*)y, HW, apply_silu ? 1 : 0};
+    const hipStream_t st = (hipStream_t)stream;
+    switch (nch) {
+    case 1: return rw_launch_gn<1, 3>(b, g, grid, st);
+    case 2: return rw_launch_gn<2, 3>(b, g, grid, st);
+    case 3: return rw_launch_gn<3, 3>(b, g, grid, st);
+    default: return rw_launch_gn<4, 6>(b, g, grid, st);
     }
 }

@@ -11,6 +11,7 @@
 // Reference: Normalize()/nonlinearity, models/DxMI/unet_small.py:30-36,119-126,169,329-330;
 // GroupNorm32, models/cm/nn.py:19-21.
 #include "conv_common.h"
+#include "gn_common.h"
 #include <stdlib.h>
 
 namespace {
@@ -377,8 +378,6 @@ struct GnApplyArgs {
                    // the statistics prologue (dxmi_groupnorm_apply_split)
 };
 
-constexpr int GN_APPLY_MAXP = 8;        // partials per image the prologue keeps in flight (ops.MAX_APPLY_PARTIALS folds larger P)
-
 typedef int gn_i4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bf16x8 gn_ld(const bf16* ptr, bool nt) {
     const gn_i4* q = reinterpret_cast<const gn_i4*>(ptr);
@@ -434,30 +433,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs p) {
     } else {
     // statistics prologue, one memory latency deep: every thread sums the <= GN_APPLY_MAXP partials of one channel pair (all
     // loads in flight together, added in partial order), then 32 threads add each group's pairs in channel order through LDS
-    auto pair_sums = [&](const float* st, int P, int nbs, int off) {        // uniform base + 32-bit lane offsets
-        const float2* const base = reinterpret_cast<const float2*>(st) + (size_t)n * P * nbs;
-        for (int b = tid; b < nbs; b += 256) {
-            float2 t[GN_APPLY_MAXP];
-#pragma unroll
-            for (int k = 0; k < GN_APPLY_MAXP; ++k)
-                if (k < P) t[k] = base[(unsigned)(k * nbs + b)];
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int k = 0; k < GN_APPLY_MAXP; ++k)
-                if (k < P) {
-                    s += t[k].x;
-                    q += t[k].y;
-                }
-            for (int k = GN_APPLY_MAXP; k < P; ++k) {       // more partials than the host folds to: correct, just serial
-                const float2 tk = base[(unsigned)(k * nbs + b)];
-                s += tk.x;
-                q += tk.y;
-            }
-            pair_s[off + b] = make_float2(s, q);
-        }
-    };
-    pair_sums(p.st0, p.P0, p.C0 >> 1, 0);
-    if (p.C1) pair_sums(p.st1, p.P1, p.C1 >> 1, p.C0 >> 1);
+    gn_pair_sums(pair_s, p.st0, n, p.P0, p.C0 >> 1, 0, tid);
+    if (p.C1) gn_pair_sums(pair_s, p.st1, n, p.P1, p.C1 >> 1, p.C0 >> 1, tid);
     __syncthreads();
     // gamma / beta are requested before the group reduction (the partials' registers are free again)
     f32x4 g0, g1, b0, b1;
@@ -478,33 +455,15 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs p) {
         sh0 = *reinterpret_cast<const f32x4*>(ssn + C);
         sh1 = *reinterpret_cast<const f32x4*>(ssn + C + 4);
     }
-    if (tid < p.groups) {
-        const int bpg = p.cpg >> 1;
-        float s = 0.f, q = 0.f;
-        for (int b = tid * bpg; b < (tid + 1) * bpg; ++b) {
-            s += pair_s[b].x;
-            q += pair_s[b].y;
-        }
-        const float cnt = (float)p.HW * (float)p.cpg;
-        const float m = s / cnt;
-        mean_s[tid] = m;
-        rstd_s[tid] = rsqrtf(fmaxf(q / cnt - m * m, 0.f) + p.eps);
-    }
+    if (tid < p.groups) gn_group_moments(pair_s, tid, p.cpg, p.HW, p.eps, mean_s, rstd_s);
     __syncthreads();
     if (!active) return;
     {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int g = (c + e) / p.cpg;
-            float a = rstd_s[g] * (e < 4 ? g0[e] : g1[e - 4]);
-            float b = (e < 4 ? b0[e] : b1[e - 4]) - mean_s[g] * a;
-            if (p.ss) {
-                const float sc = 1.f + (e < 4 ? sc0[e] : sc1[e - 4]);
-                a *= sc;
-                b = b * sc + (e < 4 ? sh0[e] : sh1[e - 4]);
-            }
-            A[e] = a;
-            Bv[e] = b;
+            gn_channel_ab(mean_s[g], rstd_s[g], e < 4 ? g0[e] : g1[e - 4], e < 4 ? b0[e] : b1[e - 4], A[e], Bv[e]);
+            if (p.ss) gn_film(A[e], Bv[e], e < 4 ? sc0[e] : sc1[e - 4], e < 4 ? sh0[e] : sh1[e - 4]);
         }
     }
     }
@@ -513,14 +472,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnApplyArgs p) {
         for (int u = 0; u < U; ++u) {
             const int rr = r + u * rows_par;
             if (rr < row1) {
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float y = (float)v[u][e] * A[e] + Bv[e];
-                    if (p.silu) y = dxmi_silu_fast(y);
-                    o[e] = (bf16)y;
-                }
-                gn_st(dst + (size_t)rr * C, o, p.nt & 2);
+                gn_st(dst + (size_t)rr * C, gn_norm8(v[u], A, Bv, p.silu), p.nt & 2);
             }
         }
         r += U * rows_par;
@@ -1601,53 +1553,16 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(GnApplyArgs p) {
     __shared__ float2 pair_s[1024];
     const int C = p.C0 + p.C1;
     const int n = blockIdx.x, tid = threadIdx.x;
-    auto pair_sums = [&](const float* st, int P, int nbs, int off) {
-        const float2* const base = reinterpret_cast<const float2*>(st) + (size_t)n * P * nbs;
-        for (int b = tid; b < nbs; b += 256) {
-            float2 t[GN_APPLY_MAXP];
-#pragma unroll
-            for (int k = 0; k < GN_APPLY_MAXP; ++k)
-                if (k < P) t[k] = base[(unsigned)(k * nbs + b)];
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int k = 0; k < GN_APPLY_MAXP; ++k)
-                if (k < P) {
-                    s += t[k].x;
-                    q += t[k].y;
-                }
-            for (int k = GN_APPLY_MAXP; k < P; ++k) {
-                const float2 tk = base[(unsigned)(k * nbs + b)];
-                s += tk.x;
-                q += tk.y;
-            }
-            pair_s[off + b] = make_float2(s, q);
-        }
-    };
-    pair_sums(p.st0, p.P0, p.C0 >> 1, 0);
-    if (p.C1) pair_sums(p.st1, p.P1, p.C1 >> 1, p.C0 >> 1);
+    gn_pair_sums(pair_s, p.st0, n, p.P0, p.C0 >> 1, 0, tid);
+    if (p.C1) gn_pair_sums(pair_s, p.st1, n, p.P1, p.C1 >> 1, p.C0 >> 1, tid);
     __syncthreads();
-    if (tid < p.groups) {
-        const int bpg = p.cpg >> 1;
-        float s = 0.f, q = 0.f;
-        for (int b = tid * bpg; b < (tid + 1) * bpg; ++b) {
-            s += pair_s[b].x;
-            q += pair_s[b].y;
-        }
-        const float cnt = (float)p.HW * (float)p.cpg;
-        const float m = s / cnt;
-        mean_s[tid] = m;
-        rstd_s[tid] = rsqrtf(fmaxf(q / cnt - m * m, 0.f) + p.eps);
-    }
+    if (tid < p.groups) gn_group_moments(pair_s, tid, p.cpg, p.HW, p.eps, mean_s, rstd_s);
     __syncthreads();
     for (int c = tid; c < C; c += 256) {
         const int g = c / p.cpg;
-        float a = rstd_s[g] * p.gamma[c];
-        float b = p.beta[c] - mean_s[g] * a;
-        if (p.ss) {
-            const float sc = 1.f + p.ss[(size_t)n * p.ss_ld + c];
-            a *= sc;
-            b = b * sc + p.ss[(size_t)n * p.ss_ld + C + c];
-        }
+        float a, b;
+        gn_channel_ab(mean_s[g], rstd_s[g], p.gamma[c], p.beta[c], a, b);
+        if (p.ss) gn_film(a, b, p.ss[(size_t)n * p.ss_ld + c], p.ss[(size_t)n * p.ss_ld + C + c]);
         reinterpret_cast<float2*>(p.ab)[(size_t)n * C + c] = make_float2(a, b);
     }
 }
@@ -1832,5 +1747,21 @@ static int gn_apply_impl(const void* in0, int32_t C0, const float* stats0, int32
     else if (U == 2) hipLaunchKernelGGL(gn_apply_kernel<2>, dim3(N * a.chunks), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(gn_apply_kernel<4>, dim3(N * a.chunks), dim3(256), 0, (hipStream_t)stream, a);
     DXMI_CHECK_LAUNCH("dxmi_groupnorm_apply");
+    return DXMI_OK;
+}
+
+// The (scale, offset) table alone (gn_common.h): the fused norm1 + nin_shortcut kernel (conv1x1_rw.hip) reads it
+int gn_finalize_launch(const float* stats0, int P0, int C0, const float* stats1, int P1, int C1, const float* gamma, const float* beta,
+                       float* ab, int N, int HW, int groups, float eps, hipStream_t st) {
+    DXMI_CHECK_ARG(stats0 && gamma && beta && ab && P0 > 0 && N > 0 && HW > 0, "gn_finalize: null pointer / empty shape");
+    DXMI_CHECK_ARG(C1 == 0 || (stats1 && P1 > 0), "gn_finalize: C1>0 needs stats1");
+    const int C = C0 + C1;
+    DXMI_CHECK_ARG(groups > 0 && groups <= 32 && C % groups == 0 && (C / groups) % 2 == 0 && C0 % 8 == 0 && C1 % 8 == 0 && C <= 2048,
+                   "gn_finalize: C0=%d C1=%d groups=%d (even channels per group)", C0, C1, groups);
+    GnApplyArgs a = {};
+    a.st0 = stats0; a.st1 = stats1; a.gamma = gamma; a.beta = beta; a.ss = nullptr; a.ab = ab;
+    a.C0 = C0; a.C1 = C1; a.HW = HW; a.groups = groups; a.cpg = C / groups; a.P0 = P0; a.P1 = P1; a.eps = eps;
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(N), dim3(256), 0, st, a);
+    DXMI_CHECK_LAUNCH("gn_finalize");
     return DXMI_OK;
 }

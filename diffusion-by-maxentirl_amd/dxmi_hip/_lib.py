@@ -53,6 +53,9 @@ SIGNATURES = {
                                      c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "dxmi_groupnorm_apply_split": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                            c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "dxmi_groupnorm_silu_shortcut_supported": (c_int, [ctypes.POINTER(ConvDesc), c_int]),
+    "dxmi_groupnorm_silu_shortcut": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_float,
+                                             c_int, c_void_p, c_void_p, c_void_p]),
     "dxmi_gn_blockstats_to_generic": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dxmi_attention_fwd_lse_supported": (c_int, [c_int, c_int, c_int]),
     "dxmi_attention_fwd_lse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),

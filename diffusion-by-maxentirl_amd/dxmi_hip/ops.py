@@ -808,6 +808,50 @@ def groupnorm_silu(x, gamma, beta, *, in1=None, groups=32, eps=1e-6, silu=True, 
     return out
 
 
+def groupnorm_silu_shortcut(x, gamma, beta, pw, *, in1=None, bias=None, groups=32, eps=1e-6, silu=True, stats=None):
+    """GroupNorm(+SiLU) of [x | in1] from their block statistics `stats` (groupnorm_silu's streaming path) AND the 1x1 conv pw of the
+    same input (conv2d(x, pw, in1=in1, bias=bias): a ResnetBlock's nin_shortcut) in one pass over the input
+    (dxmi_groupnorm_silu_shortcut) -> (y, sc), bitwise the two ops' results.  None where the pair is out of the kernel's scope:
+    the caller runs the two ops."""
+    _need_cuda(x, in1, gamma, beta, bias)
+    if stats is None or stats[0] is None or (in1 is not None and stats[1] is None) or pw.k27 or pw.ksize != 1:
+        return None
+    N, H, W, C0 = x.shape
+    C1 = in1.shape[3] if in1 is not None else 0
+    C = C0 + C1
+    if (C // groups) % 2 != 0 or C0 % 8 != 0 or C1 % 8 != 0:
+        return None
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and C == pw.Cin
+    assert in1 is None or (in1.dtype == torch.bfloat16 and in1.is_contiguous() and in1.shape[:3] == x.shape[:3])
+    assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == C and beta.numel() == C
+    st0, st1 = stats[0], (stats[1] if in1 is not None else None)
+    assert tuple(st0.buf.shape) == (N, st0.P, C0 // 2, 2) and (st1 is None or tuple(st1.buf.shape) == (N, st1.P, C1 // 2, 2))
+    Cout = pw.Cout
+    sc = torch.empty((N, H, W, Cout), dtype=torch.bfloat16, device=x.device)
+    d = ConvDesc()
+    d.in0, d.in1, d.wpacked = x.data_ptr(), (in1.data_ptr() if in1 is not None else None), pw.buf.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.out = sc.data_ptr()
+    d.N, d.IH, d.IW, d.C0, d.C1, d.OH, d.OW, d.Cout = N, H, W, C0, C1, H, W, Cout
+    d.ksize, d.stride, d.pad, d.upsample, d.act = 1, 1, 0, 0, ACT_NONE
+    d.in_mode, d.out_mode = IN_NHWC_BF16, OUT_NHWC_BF16
+    lib = load()
+    key = ("gn_shortcut", N, H, W, C0, C1, Cout, groups, bias is not None)
+    ok = _STATS_P.get(key)
+    if ok is None:
+        ok = _STATS_P[key] = int(lib.dxmi_groupnorm_silu_shortcut_supported(ctypes.byref(d), groups))
+    if not ok:
+        return None
+    y = torch.empty((N, H, W, C), dtype=torch.bfloat16, device=x.device)
+    ab = torch.empty((N, C, 2), dtype=torch.float32, device=x.device)
+    px = N * H * W
+    _prof("groupnorm", "gn_shortcut", 2.0 * px * C * Cout, 2.0 * (2 * px * C + px * Cout + C * Cout), lambda: check(
+        lib.dxmi_groupnorm_silu_shortcut(ctypes.byref(d), _ptr(st0.buf), st0.P, _ptr(st1.buf) if st1 is not None else None,
+                                         st1.P if st1 is not None else 0, _ptr(gamma), _ptr(beta), groups, float(eps), int(silu),
+                                         _ptr(y), _ptr(ab), _stream()), "dxmi_groupnorm_silu_shortcut"))
+    return y, sc
+
+
 def gn_blockstats_to_generic(st0, st1, N, HW, C0, C1, groups=32):
     """BlockStats of x (| in1) -> the fp32 statistics tensor groupnorm_generic_bwd(fwd_stats=...) takes (dxmi_gn_blockstats_to_generic)."""
     lib = load()

@@ -12,6 +12,8 @@ initialisation order).  forward() never calls them: it runs a fused HIP program 
 over NHWC bf16 activations, from bf16 weight fragments that are re-packed only when a
 parameter's version counter changes.  No CPU path: non-device tensors raise.
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -258,6 +260,7 @@ class Model(nn.Module):
     # GroupNorm block statistics of what it stores, so every Normalize() on them is one streaming read + write
     # (ops.groupnorm_apply).  Smaller maps (8x8, 4x4: 8 % of the GroupNorm bytes) keep the one-pass resident kernel.
     FUSE_ATTN_PROJ = True             # proj_out + residual of the 16x16 AttnBlocks behind the attention kernel
+    FUSE_GN_SHORTCUT = os.environ.get("DXMI_GN_SHORTCUT", "1") != "0"   # a changing ResnetBlock's norm1 and nin_shortcut from one read of its input (ops.groupnorm_silu_shortcut)
     FUSE_ATTN_BLOCK = True            # the 16x16 AttnBlocks as ONE launch (norm, q|k|v, attention, proj_out, residual: ops.attn_block)
     FUSE_GN_SMALL = True              # norm2 of the 4x4 ResnetBlocks from conv1's epilogue (instance override: A-B timing)
     STREAM_GN_MIN_HW = 256            # instance attribute override (tests / A-B timing): 1 << 30 = one-pass GroupNorm everywhere
@@ -275,13 +278,21 @@ class Model(nn.Module):
         statistics (None: one-pass GroupNorm) or, for s0, a _Normed(x0) some producer's epilogue already wrote for norm1.
         nxt = (GroupNorm module, silu) of the ONLY-normalising next reader of the output: where conv2's kernel can, it writes that
         normalisation too.  Returns (h, BlockStats | _Normed | None)."""
+        stream = x0.shape[1] * x0.shape[2] >= self.STREAM_GN_MIN_HW
+        fused = None
         if isinstance(s0, _Normed):
             assert s0.norm is b.norm1 and x1 is None
             a0 = s0.y
         else:
-            a0 = ops.groupnorm_silu(x0, b.norm1.weight, b.norm1.bias, in1=x1, eps=1e-6, silu=True, stats=(s0, s1))
+            if self.FUSE_GN_SHORTCUT and stream and b.in_channels != b.out_channels and not b.use_conv_shortcut:
+                # norm1 and the nin_shortcut from one read of [x0 | x1] (None where the kernel does not take the shape)
+                fused = ops.groupnorm_silu_shortcut(x0, b.norm1.weight, b.norm1.bias, pk[id(b), "short"], in1=x1, bias=b.nin_shortcut.bias,
+                                                    eps=1e-6, silu=True, stats=(s0, s1))
+            if fused is not None:
+                a0, sc = fused
+            else:
+                a0 = ops.groupnorm_silu(x0, b.norm1.weight, b.norm1.bias, in1=x1, eps=1e-6, silu=True, stats=(s0, s1))
         off = pk[id(b), "toff"]
-        stream = x0.shape[1] * x0.shape[2] >= self.STREAM_GN_MIN_HW
         a = None
         if not stream and self.FUSE_GN_SMALL:
             # 4x4 maps: conv1's epilogue normalises its own output (whole images and groups per tile); h has no other reader.
@@ -296,8 +307,9 @@ class Model(nn.Module):
         if a is None:
             a = ops.groupnorm_silu(h, b.norm2.weight, b.norm2.bias, eps=1e-6, silu=True, stats=(sh, None))
         if b.in_channels != b.out_channels:
-            sc_mod = b.conv_shortcut if b.use_conv_shortcut else b.nin_shortcut
-            sc = ops.conv2d(x0, pk[id(b), "short"], in1=x1, bias=sc_mod.bias)
+            if fused is None:
+                sc_mod = b.conv_shortcut if b.use_conv_shortcut else b.nin_shortcut
+                sc = ops.conv2d(x0, pk[id(b), "short"], in1=x1, bias=sc_mod.bias)
         else:
             assert x1 is None
             sc = x0

@@ -300,6 +300,16 @@ int dxmi_groupnorm_apply_split(const void* in0, int32_t C0, const float* stats0,
                                const float* scale_shift, int32_t ss_ld, void* out, float* ab_workspace, int32_t N, int32_t HW,
                                int32_t groups, float eps, int32_t apply_silu, void* stream);
 
+/* GroupNorm(+SiLU) of [in0 | in1] AND the 1x1 convolution `d` of the same input in one pass over it (a ResnetBlock's norm1 and
+ * nin_shortcut): d is the shortcut's descriptor as dxmi_conv2d_fwd takes it (in0 / in1 / C0 / C1 the input, out the shortcut
+ * output), stats0 / stats1 the input's block statistics as dxmi_groupnorm_apply takes them, y the normalised tensor [N, H, W, C0 + C1],
+ * ab_workspace N * (C0 + C1) * 2 floats.  y is bitwise dxmi_groupnorm_apply's output, out bitwise dxmi_conv2d_fwd's.  Returns 1 and
+ * launches nothing when the pair is out of scope (dxmi_groupnorm_silu_shortcut_supported returns 0): the caller runs the two ops. */
+int dxmi_groupnorm_silu_shortcut_supported(const dxmi_conv_desc* d, int32_t groups);
+int dxmi_groupnorm_silu_shortcut(const dxmi_conv_desc* d, const float* stats0, int32_t P0, const float* stats1, int32_t P1,
+                                 const float* gamma, const float* beta, int32_t groups, float eps, int32_t apply_silu, void* y,
+                                 float* ab_workspace, void* stream);
+
 /* Block statistics ([N][P][C/2][2], as dxmi_conv_desc.gn_stats / dxmi_gn_block_stats write them; st1 for the second part of a virtual
  * concat or NULL) -> the statistics partials of the generic GroupNorm kernels (dxmi_groupnorm_generic_workspace_bytes(N, HW, C) bytes:
  * what dxmi_groupnorm_generic_bwd_saved takes as fwd_stats): a training forward that normalised with dxmi_groupnorm_apply hands the
