@@ -28,7 +28,6 @@
 // are vector-memory ops too: each chunk wait below also counts those issued after the awaited chunk's DMAs.
 #include "conv_common.h"
 #include "gn_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -253,8 +252,7 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
 }
 
 template <int NCH, int R>
-int rw_launch(const ConvArgs& b, int grid, hipStream_t st) {
-    const size_t lds = (size_t)R * RW_CHUNK + RW_RO;
+int rw_launch(const ConvPlan& p, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw_kernel<NCH, R, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -262,8 +260,8 @@ int rw_launch(const ConvArgs& b, int grid, hipStream_t st) {
         attr_set = true;
     }
     const RwGn none = {};
-    if (b.residual) hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, true, false>), dim3(grid), dim3(256), lds, st, b, none);
-    else hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, false, false>), dim3(grid), dim3(256), lds, st, b, none);
+    if (p.args.residual) hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, true, false>), dim3(p.grid), dim3(256), p.lds, st, p.args, none);
+    else hipLaunchKernelGGL((conv1x1_rw_kernel<NCH, R, false, false>), dim3(p.grid), dim3(256), p.lds, st, p.args, none);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(1x1 rw)");
     return DXMI_OK;
 }
@@ -293,32 +291,31 @@ int rw_grid(ConvArgs& b) {
 
 }  // namespace
 
-// Launches the register-weights 1x1 kernel when the shape is in its scope; returns 1 otherwise (caller falls back).
-int conv1x1_rw_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
-    static const int enabled = getenv("DXMI_CONV1X1_RW") ? atoi(getenv("DXMI_CONV1X1_RW")) : 1;   // 0: conv1x1_stream_kernel for every shape
-    if (!enabled) return 1;
-    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return 1;
-    if (a.ksize != 1 || a.stride != 1 || a.pad != 0 || a.ups != 0 || a.mask_src || a.addvec || a.act == DXMI_ACT_SILU) return 1;
+// The register-weights 1x1 kernel's scope and tiling.
+bool conv1x1_rw_select(const ConvArgs& a, ConvPlan* p) {
+    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return false;
+    if (a.ksize != 1 || a.stride != 1 || a.pad != 0 || a.ups != 0 || a.mask_src || a.addvec || a.act == DXMI_ACT_SILU) return false;
     const int K = a.C0 + a.C1;
-    if (K % 128 != 0 || a.C0 % 128 != 0 || K > 512 || a.Cout % 128 != 0) return 1;
+    if (K % 128 != 0 || a.C0 % 128 != 0 || K > 512 || a.Cout % 128 != 0 || a.Cout / 128 > 32) return false;
     const long px = (long)a.N * a.OH * a.OW;
-    if (px % 64 != 0 || px / 64 < 512) return 1;          // small maps: the per-tile kernel fills the chip better
-    if (kernel_id) {
-        const int nch = K / 128;
-        *kernel_id = 500000 + nch * 1000 + (nch > 3 ? 6 : 3) * 10 + (a.residual ? 1 : 0);   // conv1x1_rw_kernel<NCH, R, RES>
-        return DXMI_OK;
-    }
-    ConvArgs b = a;
-    if (a.Cout / 128 > 32) return 1;
-    const int grid = rw_grid(b);
-    switch (K / 128) {
+    if (px % 64 != 0 || px / 64 < 512) return false;          // small maps: the per-tile kernel fills the chip better
+    const int nch = K / 128;
+    p->kind = ConvKernel::rw; p->t0 = nch; p->t1 = nch > 3 ? 6 : 3;
+    p->grid = rw_grid(p->args);
+    p->lds = (size_t)p->t1 * RW_CHUNK + RW_RO;
+    p->id = 500000 + nch * 1000 + p->t1 * 10 + (a.residual ? 1 : 0);   // conv1x1_rw_kernel<NCH, R, RES>
+    return true;
+}
+
+int conv1x1_rw_launch(const ConvPlan& p, hipStream_t st) {
+    switch (p.t0) {
     // two chunks (32 KB) in flight per workgroup, 64 KB of LDS -> two workgroups per CU.  Measured at 256 -> 768 @16x16, B = 256:
     // one workgroup per CU with seven chunks in flight 60 us, two with two chunks each 42 us — a workgroup's own issue
     // chain (DMA issue + 16 MFMAs + epilogue per chunk), not load latency, sets the tile time, so occupancy wins over depth
-    case 1: return rw_launch<1, 3>(b, grid, st);
-    case 2: return rw_launch<2, 3>(b, grid, st);
-    case 3: return rw_launch<3, 3>(b, grid, st);
-    default: return rw_launch<4, 6>(b, grid, st);         // K = 512: 128 weight registers, one workgroup per CU, deeper ring
+    case 1: return rw_launch<1, 3>(p, st);
+    case 2: return rw_launch<2, 3>(p, st);
+    case 3: return rw_launch<3, 3>(p, st);
+    default: return rw_launch<4, 6>(p, st);         // K = 512: 128 weight registers, one workgroup per CU, deeper ring
     }
 }
 
@@ -332,10 +329,8 @@ static int gn_shortcut_nch(const dxmi_conv_desc* d, int groups) {
     if (d->IH != d->OH || d->IW != d->OW || (d->OH * d->OW) % 64 != 0) return 0;       // 64-pixel tiles inside one image
     if (CT != 1 && CT != 2 && CT != 4) return 0;                                          // the CT tiles split a chunk's 64 pixels
     if (groups <= 0 || groups > 32 || K % groups != 0 || (K / groups) % 2 != 0 || d->C1 % 8 != 0) return 0;
-    const int id = dxmi_conv2d_kernel_id(d);
-    const int nch = K / 128;
-    if (K % 128 != 0 || nch < 1 || nch > 4 || id != 500000 + nch * 1000 + (nch > 3 ? 6 : 3) * 10) return 0;
-    return nch;
+    ConvPlan p;
+    return conv_plan(d, &p) == DXMI_OK && p.kind == ConvKernel::rw ? p.t0 : 0;
 }
 
 extern "C" int dxmi_groupnorm_silu_shortcut_supported(const dxmi_conv_desc* d, int32_t groups) {

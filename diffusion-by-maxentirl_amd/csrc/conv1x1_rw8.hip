@@ -18,7 +18,6 @@
 //     fragments (a branch around them makes hipcc shuffle the accumulators between register files) and skip epilogue and stores;
 //   * bias through an LDS table, wave-private 4 KB output / residual slice, exact in-order vmcnt counts (conv1x1_rw_kernel's).
 #include "conv_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -187,54 +186,53 @@ __global__ __launch_bounds__(512, 1) void conv1x1_rw8_kernel(ConvArgs p) {
 }
 
 template <int NK>
-int r8_launch(const ConvArgs& b, int grid, hipStream_t st) {
+int r8_launch(const ConvPlan& p, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw8_kernel<NK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_rw8_kernel<NK, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    if (b.residual) hipLaunchKernelGGL((conv1x1_rw8_kernel<NK, true>), dim3(grid), dim3(512), (size_t)r8_lds(NK), st, b);
-    else hipLaunchKernelGGL((conv1x1_rw8_kernel<NK, false>), dim3(grid), dim3(512), (size_t)r8_lds(NK), st, b);
+    if (p.args.residual) hipLaunchKernelGGL((conv1x1_rw8_kernel<NK, true>), dim3(p.grid), dim3(512), p.lds, st, p.args);
+    else hipLaunchKernelGGL((conv1x1_rw8_kernel<NK, false>), dim3(p.grid), dim3(512), p.lds, st, p.args);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(1x1 rw8)");
     return DXMI_OK;
 }
 
 }  // namespace
 
-// Launches the eight-wave register-weights 1x1 kernel when the shape is in its scope; returns 1 otherwise (caller falls back).
-int conv1x1_rw8_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
-    static const int enabled = getenv("DXMI_CONV1X1_RW8") ? atoi(getenv("DXMI_CONV1X1_RW8")) : 1;   // 0: conv1x1_stream_kernel for these shapes
-    if (!enabled) return 1;
-    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return 1;
-    if (a.ksize != 1 || a.stride != 1 || a.pad != 0 || a.ups != 0 || a.mask_src || a.addvec || a.act == DXMI_ACT_SILU || a.gn_stats || a.gn_out) return 1;
+// The eight-wave register-weights 1x1 kernel's scope and tiling.
+bool conv1x1_rw8_select(const ConvArgs& a, ConvPlan* p) {
+    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return false;
+    if (a.ksize != 1 || a.stride != 1 || a.pad != 0 || a.ups != 0 || a.mask_src || a.addvec || a.act == DXMI_ACT_SILU) return false;
     const int K = a.C0 + a.C1;
-    const long px_ = (long)a.N * a.OH * a.OW;
     // K = 576: always (conv1x1_stream_kernel otherwise: 85 -> 70 us on 576 -> 1728 @16x16, 206 -> 124 us on 576 -> 192 @64x64, B = 100).
     // K = 384 / 512: where conv1x1_rw_kernel does not take the shape (Cout % 128 != 0: 384 -> 192 @64x64 151 -> 101 us) or, at K = 512,
     // Cout >= 1024 (512 -> 1536 @32x32: 283 -> 189 us); on conv1x1_rw_kernel's other shapes its two workgroups per CU win
     // (384 -> 1152 @32x32: 119 us there, 131 us here).  K = 768 spills 76-118 registers here (41 -> 76 us): conv1x1_stream_kernel.
-    const bool rw_takes = K % 128 == 0 && a.C0 % 128 == 0 && K <= 512 && a.Cout % 128 == 0 && px_ % 64 == 0 && px_ / 64 >= 512;
-    const bool kok = K == 576 || ((K == 384 || K == 512) && (!rw_takes || (K == 512 && a.Cout >= 1024)));
-    if (!kok || a.C0 % 8 != 0 || a.C1 % 8 != 0 || a.Cout % 32 != 0) return 1;
+    ConvPlan rw = *p;
+    const bool kok = K == 576 || ((K == 384 || K == 512) && (!conv1x1_rw_select(a, &rw) || (K == 512 && a.Cout >= 1024)));
+    if (!kok || a.C0 % 8 != 0 || a.C1 % 8 != 0 || a.Cout % 32 != 0) return false;
     const long px = (long)a.N * a.OH * a.OW;
-    if (px % 64 != 0) return 1;
-    ConvArgs b = a;
-    b.PT = (int)(px / 64);
-    b.CT = (a.Cout + 255) / 256;
-    b.tile_px = 64;
-    if (b.CT > 32) return 1;
-    const int grid = 8 * b.CT * (32 / b.CT);              // one workgroup per CU, whole XCD groups of CT cout tiles
-    const int nstreams = (grid >> 3) / b.CT * 8;
+    if (px % 64 != 0) return false;
+    const int PT = (int)(px / 64), CT = (a.Cout + 255) / 256;
+    if (CT > 32) return false;
+    const int grid = 8 * CT * (32 / CT);              // one workgroup per CU, whole XCD groups of CT cout tiles
+    const int nstreams = (grid >> 3) / CT * 8;
     // every pixel stream needs a few tiles to pay for its 256 x K weight load (small maps / batches stay on the per-tile kernel)
-    if (b.PT < 2 * nstreams) return 1;
-    if (kernel_id) {
-        *kernel_id = 550000 + (K / 64) * 10 + (a.residual ? 1 : 0);   // conv1x1_rw8_kernel<NK, RES>
-        return DXMI_OK;
-    }
-    switch (K / 64) {
-    case 6: return r8_launch<6>(b, grid, st);
-    case 8: return r8_launch<8>(b, grid, st);
-    default: return r8_launch<9>(b, grid, st);
+    if (PT < 2 * nstreams) return false;
+    p->args.PT = PT; p->args.CT = CT; p->args.tile_px = 64;
+    p->kind = ConvKernel::rw8; p->t0 = K / 64;
+    p->grid = grid;
+    p->lds = r8_lds(K / 64);
+    p->id = 550000 + (K / 64) * 10 + (a.residual ? 1 : 0);   // conv1x1_rw8_kernel<NK, RES>
+    return true;
+}
+
+int conv1x1_rw8_launch(const ConvPlan& p, hipStream_t st) {
+    switch (p.t0) {
+    case 6: return r8_launch<6>(p, st);
+    case 8: return r8_launch<8>(p, st);
+    default: return r8_launch<9>(p, st);
     }
 }

@@ -171,6 +171,47 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[M
     }
 }
 
-// conv_pipe.hip: software-pipelined kernel for stride-1 / upsampled convs with Cout % 128 == 0.
-// Returns DXMI_OK after launching, or 1 when the shape is not eligible (caller falls back).
-int conv_pipe_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id);
+// The forward kernel a conv descriptor runs: chosen once by conv_select (conv_igemm.hip), a host-only function of the
+// descriptor and the tuning knobs, then launched by conv_launch.  dxmi_conv2d_kernel_id and the GroupNorm queries read it.
+enum class ConvKernel { igemm, pipe, stream1x1, stem, ws, ws8, sm, rw, rw8, head };
+
+struct ConvPlan {
+    ConvKernel kind;
+    int t0, t1, t2;          // template arguments that pick the instance (see the family's *_launch)
+    ConvArgs args;           // tiling filled in
+    int grid;
+    size_t lds;              // dynamic LDS bytes
+    int id;                  // dxmi_conv2d_kernel_id
+    int stats_tile;          // output pixels per GroupNorm block-statistics partial (0: the kernel writes none)
+    bool gn_out;             // the kernel can write the fused GroupNorm output (dxmi_conv2d_gn_fuse_supported)
+};
+
+// Per family: *_select returns whether the shape is in the kernel's scope and fills the plan (no HIP calls, no state);
+// *_launch does what needs the runtime.
+bool conv_ws_select(const ConvArgs& a, ConvPlan* p);
+bool conv_ws8_select(const ConvArgs& a, ConvPlan* p);
+bool conv_sm_select(const ConvArgs& a, ConvPlan* p);
+bool conv1x1_rw_select(const ConvArgs& a, ConvPlan* p);
+bool conv1x1_rw8_select(const ConvArgs& a, ConvPlan* p);
+bool conv_head_select(const ConvArgs& a, ConvPlan* p);
+bool conv_stem_select(const ConvArgs& a, ConvPlan* p);
+bool conv_pipe_select(const ConvArgs& a, ConvPlan* p);     // conv_pipe_kernel and conv1x1_stream_kernel
+int conv_ws_launch(const ConvPlan& p, hipStream_t st);
+int conv_ws8_launch(const ConvPlan& p, hipStream_t st);
+int conv_sm_launch(const ConvPlan& p, hipStream_t st);
+int conv1x1_rw_launch(const ConvPlan& p, hipStream_t st);
+int conv1x1_rw8_launch(const ConvPlan& p, hipStream_t st);
+int conv_head_launch(const ConvPlan& p, hipStream_t st);
+int conv_stem_launch(const ConvPlan& p, hipStream_t st);
+int conv_pipe_launch(const ConvPlan& p, hipStream_t st);
+
+// Device address of a family's zero page (`symbol`), looked up once into `page`; false when the runtime has none.
+template <typename T>
+bool conv_zero_page(const void*& page, const T& symbol) {
+    void* zp = nullptr;
+    if (!page && hipGetSymbolAddress(&zp, symbol) == hipSuccess) page = zp;
+    return page != nullptr;
+}
+
+// Validates a descriptor and selects its kernel, refusing GroupNorm requests that kernel cannot serve (conv_igemm.hip)
+int conv_plan(const dxmi_conv_desc* d, ConvPlan* p);

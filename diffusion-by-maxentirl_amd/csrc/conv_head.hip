@@ -11,7 +11,6 @@
 // v_mfma_f32_16x16x32_bf16 over its 32 pixels (one tile row) with B fragments read by ds_read_b128 at a per-lane base plus
 // a compile-time offset.  Pixel rows are 256 B = 16 slots of 16 B; channel piece s of halo pixel hp sits in slot s ^ (hp & 15).
 #include "conv_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -97,24 +96,25 @@ __global__ __launch_bounds__(256, 2) void conv_head_kernel(ConvArgs p) {
 
 }  // namespace
 
-// Launches the narrow-head kernel when the shape is in its scope; returns 1 otherwise (caller falls back).
-int conv_head_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
-    static const int enabled = getenv("DXMI_CONV_HEAD") ? atoi(getenv("DXMI_CONV_HEAD")) : 1;   // 0: generic kernel
-    if (!enabled) return 1;
-    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NCHW_F32) return 1;
-    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups != 0 || a.mask_src || a.addvec || a.residual || a.act == DXMI_ACT_SILU) return 1;
-    if (a.C0 != 128 || a.C1 != 0 || a.Cout > 16 || a.OW % 32 != 0 || a.OH % HD_TH != 0) return 1;
-    if (kernel_id) {
-        *kernel_id = 600000;
-        return DXMI_OK;
-    }
+// The narrow-head kernel's scope and grid.
+bool conv_head_select(const ConvArgs& a, ConvPlan* p) {
+    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NCHW_F32) return false;
+    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups != 0 || a.mask_src || a.addvec || a.residual || a.act == DXMI_ACT_SILU) return false;
+    if (a.C0 != 128 || a.C1 != 0 || a.Cout > 16 || a.OW % 32 != 0 || a.OH % HD_TH != 0) return false;
+    p->kind = ConvKernel::head;
+    p->grid = a.N * (a.OH / HD_TH) * (a.OW / 32);
+    p->lds = (size_t)HD_BLOCKS * 1024;
+    p->id = 600000;
+    return true;
+}
+
+int conv_head_launch(const ConvPlan& p, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    const int grid = a.N * (a.OH / HD_TH) * (a.OW / 32);
-    hipLaunchKernelGGL(conv_head_kernel, dim3(grid), dim3(256), (size_t)HD_BLOCKS * 1024, st, a);
+    hipLaunchKernelGGL(conv_head_kernel, dim3(p.grid), dim3(256), p.lds, st, p.args);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(head)");
     return DXMI_OK;
 }

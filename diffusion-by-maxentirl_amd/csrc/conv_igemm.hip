@@ -440,50 +440,69 @@ extern "C" int dxmi_pack_conv_weights(const dxmi_pack_item* items, int32_t count
 
 namespace {
 
-int dispatch_conv(ConvArgs& a, int variant, hipStream_t st, int* kernel_id = nullptr) {
-    if (variant == 0) {
-        const int rc = conv_pipe_try_launch(a, st, kernel_id);
-        if (rc <= 0) return rc;  // launched (or failed loudly); rc == 1: not eligible
-    }
-    DXMI_CHECK_ARG(!a.gn_stats || kernel_id, "dxmi_conv2d_fwd: the kernel for this shape does not emit GroupNorm block statistics "
-                                             "(dxmi_conv2d_gn_stats_partials returns 0 for it)");
-    DXMI_CHECK_ARG(!a.gn_out || kernel_id, "dxmi_conv2d_fwd: the kernel for this shape cannot fuse the GroupNorm of its output "
-                                           "(dxmi_conv2d_gn_fuse_supported returns 0 for it)");
+// The generic implicit-GEMM kernel: every shape, cout tile 128 when Cout allows it, else 32 (conv_out, heads).
+void conv_igemm_select(const ConvArgs& a, int variant, ConvPlan* p) {
     constexpr int CK = 32;
-    a.tile_px = 256;
-    a.stagger = 0;
+    ConvArgs& b = p->args;
+    b.tile_px = 256;
+    b.stagger = 0;
     const bool flat = a.in_mode != DXMI_IN_NHWC_BF16;
     const int HP = flat ? 256 : a.SUBS * a.HH * a.HWd;
-    const size_t lds = (size_t)HP * (CK * 2 + 16);
-    a.lds_buf = (int)lds;
-    DXMI_CHECK_ARG(lds <= 160 * 1024, "dxmi_conv2d_fwd: LDS image %zu too large", lds);
+    p->lds = (size_t)HP * (CK * 2 + 16);
+    b.lds_buf = (int)p->lds;
     const int npieces = HP * (CK / 8);
     // staging pieces per thread cached in registers: 6 covers the 32x8 / 16x16 tiles, 9 the
     // multi-image 8x8 / 4x4 tiles; larger halos (stride 2) recompute their addresses per chunk.
     const int pmax = npieces <= 6 * 256 ? 6 : (npieces <= 9 * 256 ? 9 : 0);
-    // Tiling variants: cout tile BN = 128 when Cout allows it, else 32 (conv_out, heads).
-    if (kernel_id) {
-        // id = MB*1000 + NB*100 + (small_halo ? 6 : 0): names the template instantiation that runs
-        if (a.Cout % 128 == 0 && a.out_mode != DXMI_OUT_NCHW_F32) *kernel_id = (variant == 1 ? 2400 : 1800) + pmax;
-        else *kernel_id = 1200 + pmax;
-        return DXMI_OK;
+    const bool wide = a.Cout % 128 == 0 && a.out_mode != DXMI_OUT_NCHW_F32;
+    b.CT = wide ? a.Cout / 128 : a.CB;    // 32-cout tiles: one 32-co block per workgroup, 4 waves split the 256 pixels
+    p->kind = ConvKernel::igemm;
+    p->t0 = wide && variant == 1 ? 2 : 1;                     // MB
+    p->t1 = !wide ? 2 : (variant == 1 ? 4 : 8);               // NB
+    p->t2 = pmax;
+    p->grid = (a.PT + 7) / 8 * 8 * b.CT;
+    p->id = p->t0 * 1000 + p->t1 * 100 + pmax;      // conv_igemm_kernel<MB, NB, 32, PMAX>
+}
+
+template <int MB, int NB>
+int launch_igemm(const ConvPlan& p, hipStream_t st) {
+    return p.t2 == 6 ? launch_conv<MB, NB, 32, 6>(p.args, p.lds, st)
+                     : p.t2 == 9 ? launch_conv<MB, NB, 32, 9>(p.args, p.lds, st) : launch_conv<MB, NB, 32, 0>(p.args, p.lds, st);
+}
+
+// The forward kernel of a conv, in order of preference.  A fused GroupNorm output narrows the choice to the two kernels that
+// can write it; a GroupNorm statistics request does not change the choice (conv_plan checks it against the plan).
+void conv_select(const ConvArgs& a, int variant, ConvPlan* p) {
+    auto is = [&](bool (*select)(const ConvArgs&, ConvPlan*)) { *p = ConvPlan{}; p->args = a; return select(a, p); };
+    if (variant == 0 && (a.gn_out ? is(conv_sm_select) || is(conv_ws8_select)
+                                  : is(conv_ws_select) || is(conv1x1_rw8_select) || is(conv1x1_rw_select) || is(conv_head_select) ||
+                                        is(conv_sm_select) || is(conv_ws8_select) || is(conv_stem_select) || is(conv_pipe_select)))
+        return;
+    *p = ConvPlan{};
+    p->args = a;
+    conv_igemm_select(a, variant, p);
+}
+
+int conv_launch(const ConvPlan& p, hipStream_t st) {
+    switch (p.kind) {
+    case ConvKernel::ws: return conv_ws_launch(p, st);
+    case ConvKernel::ws8: return conv_ws8_launch(p, st);
+    case ConvKernel::sm: return conv_sm_launch(p, st);
+    case ConvKernel::rw: return conv1x1_rw_launch(p, st);
+    case ConvKernel::rw8: return conv1x1_rw8_launch(p, st);
+    case ConvKernel::head: return conv_head_launch(p, st);
+    case ConvKernel::stem: return conv_stem_launch(p, st);
+    case ConvKernel::pipe:
+    case ConvKernel::stream1x1: return conv_pipe_launch(p, st);
+    case ConvKernel::igemm: break;
     }
-    if (a.Cout % 128 == 0 && a.out_mode != DXMI_OUT_NCHW_F32) {
-        a.CT = a.Cout / 128;
-#define DXMI_CONV_PM(MB_, NB_)                                           \
-    (pmax == 6 ? launch_conv<MB_, NB_, CK, 6>(a, lds, st)                \
-               : pmax == 9 ? launch_conv<MB_, NB_, CK, 9>(a, lds, st) : launch_conv<MB_, NB_, CK, 0>(a, lds, st))
-        if (variant == 1) return DXMI_CONV_PM(2, 4);
-        return DXMI_CONV_PM(1, 8);
-    }
-    a.CT = a.CB;  // one 32-co block per workgroup, 4 waves split the 256 pixels
-    return DXMI_CONV_PM(1, 2);
-#undef DXMI_CONV_PM
+    if (p.t0 == 2) return launch_igemm<2, 4>(p, st);
+    return p.t1 == 8 ? launch_igemm<1, 8>(p, st) : launch_igemm<1, 2>(p, st);
 }
 
 }  // namespace
 
-static int conv2d_impl(const dxmi_conv_desc* d, void* stream, int* kernel_id) {
+int conv_plan(const dxmi_conv_desc* d, ConvPlan* p) {
     DXMI_CHECK_ARG(d && d->in0 && d->wpacked && d->out, "dxmi_conv2d_fwd: null pointer");
     const bool k27 = d->in_mode == DXMI_IN_NCHW_F32_K27;
     DXMI_CHECK_ARG(d->in_mode == DXMI_IN_NHWC_BF16 || k27, "dxmi_conv2d_fwd: in_mode %d unsupported", d->in_mode);
@@ -514,12 +533,11 @@ static int conv2d_impl(const dxmi_conv_desc* d, void* stream, int* kernel_id) {
     DXMI_CHECK_ARG(!d->residual || d->Cout % 4 == 0, "dxmi_conv2d_fwd: residual needs Cout%%4==0");
     DXMI_CHECK_ARG(!d->mask_src || (d->Cout % 4 == 0 && d->out_mode == DXMI_OUT_NHWC_BF16), "dxmi_conv2d_fwd: mask_src needs NHWC bf16 output, Cout%%4==0");
 
-    ConvArgs a;
+    ConvArgs a = {};
     a.in0 = (const bf16*)d->in0; a.in1 = (const bf16*)d->in1; a.w = (const bf16*)d->wpacked;
     a.bias = d->bias; a.addvec = d->addvec; a.residual = (const bf16*)d->residual; a.out = d->out;
     a.mask_src = (const bf16*)d->mask_src; a.mask_slope = d->mask_slope; a.gn_stats = d->gn_stats;
     a.gn_out = (bf16*)d->gn_out; a.gn_gamma = d->gn_gamma; a.gn_beta = d->gn_beta; a.gn_eps = d->gn_eps; a.gn_flags = d->gn_flags;
-    a.res_is_mask = 0;
     DXMI_CHECK_ARG(!d->gn_out || (d->gn_gamma && d->gn_beta && d->gn_groups > 0 && d->Cout == 8 * d->gn_groups && d->variant == 0 &&
                                   d->out_mode == DXMI_OUT_NHWC_BF16),
                    "dxmi_conv2d_fwd: gn_out needs gamma / beta, 8 channels per group, the default variant and NHWC bf16 output");
@@ -527,7 +545,7 @@ static int conv2d_impl(const dxmi_conv_desc* d, void* stream, int* kernel_id) {
                    "dxmi_conv2d_fwd: gn_stats needs the default variant, NHWC bf16 output and Cout%%4==0");
     a.N = d->N; a.IH = d->IH; a.IW = d->IW; a.C0 = d->C0; a.C1 = d->C1; a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout;
     a.ksize = d->ksize; a.stride = d->stride; a.pad = d->pad; a.ups = d->upsample; a.act = d->act;
-    a.addvec_ld = d->addvec_ld; a.in_mode = d->in_mode; a.out_mode = d->out_mode; a.P = 0; a.pre_act = 0;
+    a.addvec_ld = d->addvec_ld; a.in_mode = d->in_mode; a.out_mode = d->out_mode;
     const int TW = d->OW < 32 ? d->OW : 32;
     int TH = 256 / TW; if (TH > d->OH) TH = d->OH;
     a.TWl = ilog2(TW); a.THl = ilog2(TH); a.SUBS = 256 / (TW * TH);
@@ -537,53 +555,48 @@ static int conv2d_impl(const dxmi_conv_desc* d, void* stream, int* kernel_id) {
     a.PT = ngroups * (d->OH / TH) * (d->OW / TW);
     a.CB = (d->Cout + 31) / 32;
     a.KST = k27 ? 2 : Cin / 16;
-    return dispatch_conv(a, d->variant, (hipStream_t)stream, kernel_id);
+    conv_select(a, d->variant, p);
+    DXMI_CHECK_ARG(!a.gn_out || p->gn_out, "dxmi_conv2d_fwd: the kernel for this shape cannot fuse the GroupNorm of its output "
+                                          "(dxmi_conv2d_gn_fuse_supported returns 0 for it)");
+    DXMI_CHECK_ARG(!a.gn_stats || p->stats_tile, "dxmi_conv2d_fwd: the kernel for this shape does not emit GroupNorm block statistics "
+                                                "(dxmi_conv2d_gn_stats_partials returns 0 for it)");
+    DXMI_CHECK_ARG(p->lds <= 160 * 1024, "dxmi_conv2d_fwd: LDS image %zu too large", p->lds);
+    return DXMI_OK;
 }
 
-extern "C" int dxmi_conv2d_fwd(const dxmi_conv_desc* d, void* stream) { return conv2d_impl(d, stream, nullptr); }
+extern "C" int dxmi_conv2d_fwd(const dxmi_conv_desc* d, void* stream) {
+    ConvPlan p;
+    const int rc = conv_plan(d, &p);
+    return rc == DXMI_OK ? conv_launch(p, (hipStream_t)stream) : rc;
+}
 
 // Partials per image of the GroupNorm block statistics the selected kernel writes (0: it writes none).
-int conv_pipe_stats_tile(int id, int OH, int OW, int Cout);     // conv_pipe.hip
-
-static int gn_stats_partials_of(const dxmi_conv_desc* d, int id) {
-    if (id >= 400000 && id < 400100) {            // conv_ws_kernel<TW>: (pixel tile, pixel half) of the image
-        const int TW = id - 400000, TH = 256 / TW;
-        return (d->OH / TH) * (d->OW / TW) * 2;
-    }
-    const int tile = conv_pipe_stats_tile(id, d->OH, d->OW, d->Cout);     // stem / conv_pipe / 1x1 stream kernels: one partial per tile
-    return tile ? d->OH * d->OW / tile : 0;
-}
-
 extern "C" int dxmi_conv2d_gn_stats_partials(const dxmi_conv_desc* d) {
-    int id = 0;
-    if (!d) return 0;
+    if (!d || d->variant != 0 || d->out_mode != DXMI_OUT_NHWC_BF16) return 0;
     dxmi_conv_desc q = *d;
     q.gn_stats = nullptr;
-    if (q.variant != 0 || q.out_mode != DXMI_OUT_NHWC_BF16) return 0;
-    const int rc = conv2d_impl(&q, nullptr, &id);
-    return rc == DXMI_OK ? gn_stats_partials_of(d, id) : 0;
+    ConvPlan p;
+    return conv_plan(&q, &p) == DXMI_OK && p.stats_tile ? d->OH * d->OW / p.stats_tile : 0;
 }
 
+// Whether the selected kernel can write the fused GroupNorm(+SiLU) of its output: conv_sm_kernel<2, 8, 32> (eight whole 4x4
+// images x 32 couts per tile) and conv_ws8_kernel (a whole 8x8 image per wave, instead of the raw output).
 extern "C" int dxmi_conv2d_gn_fuse_supported(const dxmi_conv_desc* d) {
-    int id = 0;
-    if (!d) return 0;
+    if (!d || d->variant != 0 || d->out_mode != DXMI_OUT_NHWC_BF16 || d->gn_groups <= 0 || d->Cout != 8 * d->gn_groups) return 0;
     dxmi_conv_desc q = *d;
     q.gn_stats = nullptr;
     q.gn_out = nullptr;
-    if (q.variant != 0 || q.out_mode != DXMI_OUT_NHWC_BF16 || d->gn_groups <= 0 || d->Cout != 8 * d->gn_groups) return 0;
-    const int rc = conv2d_impl(&q, nullptr, &id);
-    if (rc != DXMI_OK) return 0;
-    if (id == 450432) return 1;                        // conv_sm_kernel<2, 8, 32>: eight whole 4x4 images x 32 couts per tile
-    return id == 400008 && (d->gn_flags & 2) ? 1 : 0;  // conv_ws8_kernel: a whole 8x8 image per wave, instead of the raw output
+    ConvPlan p;
+    return conv_plan(&q, &p) == DXMI_OK && p.gn_out ? 1 : 0;
 }
 
-// Which template instantiation dxmi_conv2d_fwd would launch for this descriptor (no launch):
-// MB*1000 + NB*100 + PMAX, e.g. 1806 = conv_igemm_kernel<1,8,32,6>.  Used by bench.py to attribute
-// HIP-event timings to the kernel named in the rocprof summary.
+// Which kernel dxmi_conv2d_fwd would launch for this descriptor (no launch), e.g. 1806 = conv_igemm_kernel<1,8,32,6>
+// (MB*1000 + NB*100 + PMAX), or the error it would return.  Used by bench.py to attribute HIP-event timings to the kernel
+// named in the rocprof summary.
 extern "C" int dxmi_conv2d_kernel_id(const dxmi_conv_desc* d) {
-    int id = 0;
-    const int rc = conv2d_impl(d, nullptr, &id);
-    return rc == DXMI_OK ? id : rc;
+    ConvPlan p;
+    const int rc = conv_plan(d, &p);
+    return rc == DXMI_OK ? p.id : rc;
 }
 
 // Small dense layers (timestep-embedding MLP, temb_proj / emb_layers: P = batch rows, K <= 2048): the conv kernel gives
@@ -676,7 +689,9 @@ extern "C" int dxmi_linear_fwd(const float* x, const void* wpacked, const float*
     a.in_mode = DXMI_IN_ROWS_F32; a.out_mode = DXMI_OUT_ROWS_F32; a.P = P; a.pre_act = pre_act;
     a.TWl = 5; a.THl = 3; a.SUBS = 1; a.HH = 8; a.HWd = 32;
     a.PT = (P + 255) / 256; a.CB = (M + 31) / 32; a.KST = K / 16;
-    return dispatch_conv(a, 0, (hipStream_t)stream);
+    ConvPlan p;
+    conv_select(a, 0, &p);
+    return conv_launch(p, (hipStream_t)stream);
 }
 
 // Split-K form for skinny products with a long K: partials[s][P][M] = pre(x[:, slice s]) @ W[:, slice s]^T, s < nsplit = dxmi_linear_splitk_slices(P, K, M)

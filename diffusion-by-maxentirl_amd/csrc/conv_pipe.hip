@@ -19,7 +19,6 @@
 //     bank-conflict free.
 // NB in {8,4,2} (pixels per tile = 32*NB) is chosen on the host; 2 workgroups per CU for NB <= 4.
 #include "conv_common.h"
-#include <stdlib.h>
 
 #ifdef DXMI_CONV_STAMPS
 // timing-only build (make STAMPS=1): per-workgroup cycle stamps of wave 0 (s_memtime), read back with
@@ -702,53 +701,27 @@ __global__ __launch_bounds__(256, OCC) void conv1x1_stream_kernel(ConvArgs p) {
 }
 
 template <int NB, int RC, int OCC>
-int launch_stream(const ConvArgs& a, int grid, hipStream_t st) {
+int launch_stream(const ConvPlan& p, hipStream_t st) {
     auto kern = conv1x1_stream_kernel<NB, RC, OCC>;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    size_t lds = (size_t)RC * 32 * NB * 80;
-    if (lds < (size_t)EPI_BYTES) lds = EPI_BYTES;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, st, p.args);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(1x1 stream)");
     return DXMI_OK;
 }
 
-int ilog2p(int v);
-
-int conv_stem_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
-    const int tile = 128;
-    const int TW = a.OW < 32 ? a.OW : 32;
-    int TH = tile / TW;
-    if (TH > a.OH) TH = a.OH;
-    const int SUBS = tile / (TW * TH);
-    if (TW * TH * SUBS != tile) return 1;
-    if (kernel_id) {
-        *kernel_id = 300000;
-        return DXMI_OK;
-    }
-    ConvArgs b = a;
-    b.TWl = ilog2p(TW); b.THl = ilog2p(TH); b.SUBS = SUBS;
-    const int ngroups = (a.N + SUBS - 1) / SUBS;
-    b.PT = ngroups * (a.OH / TH) * (a.OW / TW);
-    b.CT = (a.Cout + 127) / 128;
-    b.tile_px = tile;
-    hipLaunchKernelGGL(conv_stem_kernel, dim3(b.PT * b.CT), dim3(256), (size_t)128 * 80 + EPI_BYTES + 4096, st, b);     // + the 3-channel halo image
-    DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(stem)");
-    return DXMI_OK;
-}
-
 template <int NB, int PMAX, int KS, int DBG = 0, int AQ = 1, int SD = 1>
-int launch_pipe(const ConvArgs& a, int grid, hipStream_t st) {
+int launch_pipe(const ConvPlan& p, hipStream_t st) {
     auto kern = conv_pipe_kernel<NB, PMAX, KS, DBG, AQ, SD>;
     static bool attr_set = false;  // benign race: idempotent
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)2 * a.lds_buf + EPI_BYTES, st, a);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, st, p.args);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(pipe)");
     return DXMI_OK;
 }
@@ -759,137 +732,111 @@ int ilog2p(int v) {
     return l;
 }
 
-}  // namespace
-
-int conv_ws_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id);       // conv_ws.hip
-int conv1x1_rw_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id);   // conv1x1_rw.hip
-int conv1x1_rw8_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id);  // conv1x1_rw8.hip
-int conv_head_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id);    // conv_head.hip
-int conv_ws8_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id);     // conv_ws8.hip
-int conv_sm_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id);      // conv_sm.hip
-
-// Pixels per tile of the kernels whose epilogue (conv_epilogue_lds) can emit GroupNorm block statistics, 0 for the others:
-// conv_stem_kernel (300000), conv_pipe_kernel (k NB pmax = 10000 k + 100 NB + pmax) and conv1x1_stream_kernel (200000), for
-// tiles inside one image and full 128-cout tiles.
-int conv_pipe_stats_tile(int id, int OH, int OW, int Cout) {
-    int tile = 0;
-    if (id == 300000) tile = 128;
-    else if (id == 200000) tile = 64;
-    else if ((id >= 10000 && id < 20000) || (id >= 30000 && id < 40000)) tile = 32 * ((id % 10000) / 100);
-    if (tile == 0 || Cout % 128 != 0 || OH * OW < tile || (OH * OW) % tile != 0) return 0;
-    return tile;
+// Output pixels per GroupNorm statistics partial of the kernels whose epilogue (conv_epilogue_lds) can emit them: their pixel
+// tile, when it lies inside one image and the cout tiles are full; 0 otherwise
+int one_image_tile(const ConvArgs& a, int tile) {
+    return a.Cout % 128 == 0 && a.OH * a.OW >= tile && (a.OH * a.OW) % tile == 0 ? tile : 0;
 }
 
-int conv_pipe_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
-    if (a.gn_stats && !kernel_id) {
-        // the statistics request must not change which kernel runs: select without it, then check that kernel can
-        ConvArgs q = a;
-        q.gn_stats = nullptr;
-        int id = 0;
-        const int rc = conv_pipe_try_launch(q, st, &id);
-        if (rc < 0) return rc;
-        DXMI_CHECK_ARG(rc == 0 && ((id >= 400000 && id < 400100) || conv_pipe_stats_tile(id, a.OH, a.OW, a.Cout) > 0),
-                       "dxmi_conv2d_fwd: the kernel for this shape does not emit GroupNorm block statistics "
-                       "(dxmi_conv2d_gn_stats_partials returns 0 for it)");
-    }
-    {
-        int rc = 1;
-        if (a.gn_out) {          // conv_sm_kernel (4x4 maps) and conv_ws8_kernel (8x8, instead of the raw output) fuse the GroupNorm of their output
-            rc = conv_sm_try_launch(a, st, kernel_id);
-            if (rc <= 0) return rc;
-            rc = conv_ws8_try_launch(a, st, kernel_id);
-            if (rc <= 0) return rc;
-            DXMI_CHECK_ARG(false, "dxmi_conv2d_fwd: the kernel for this shape cannot fuse the GroupNorm of its output "
-                                  "(dxmi_conv2d_gn_fuse_supported returns 0 for it)");
-        }
-        rc = conv_ws_try_launch(a, st, kernel_id);
-        if (rc <= 0) return rc;
-        // besides conv_ws_kernel only the stem / conv_pipe kernels below emit GroupNorm block statistics, for one-image tiles
-        // (dxmi_conv2d_gn_stats_partials says which shapes); the other small-map kernels are skipped for such a request
-        rc = conv1x1_rw8_try_launch(a, st, kernel_id);      // K = 576 (256-cout tiles, one 512-thread workgroup per CU)
-        if (rc <= 0) return rc;
-        rc = conv1x1_rw_try_launch(a, st, kernel_id);
-        if (rc <= 0) return rc;
-        rc = conv_head_try_launch(a, st, kernel_id);
-        if (rc <= 0) return rc;
-        rc = conv_sm_try_launch(a, st, kernel_id);
-        if (rc <= 0) return rc;
-        rc = conv_ws8_try_launch(a, st, kernel_id);
-        if (rc <= 0) return rc;
-    }
-    if (a.in_mode == DXMI_IN_NCHW_F32_K27 && a.out_mode == DXMI_OUT_NHWC_BF16 && a.Cout % 64 == 0) return conv_stem_launch(a, st, kernel_id);
-    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return 1;
-    if (a.Cout % 64 != 0 || (a.C0 + a.C1) % 64 != 0 || a.C0 % 32 != 0) return 1;  // even chunk count
-    if (a.stride != 1 && !(a.stride == 2 && a.ups == 0 && a.ksize == 3)) return 1;   // stride 2: Downsample convs
+}  // namespace
+
+// The RGB stem kernel (K27 input): 128-pixel tiles.
+bool conv_stem_select(const ConvArgs& a, ConvPlan* p) {
+    if (a.in_mode != DXMI_IN_NCHW_F32_K27 || a.out_mode != DXMI_OUT_NHWC_BF16 || a.Cout % 64 != 0) return false;
+    const int tile = 128;
+    const int TW = a.OW < 32 ? a.OW : 32;
+    int TH = tile / TW;
+    if (TH > a.OH) TH = a.OH;
+    const int SUBS = tile / (TW * TH);
+    if (TW * TH * SUBS != tile) return false;
+    ConvArgs& b = p->args;
+    b.TWl = ilog2p(TW); b.THl = ilog2p(TH); b.SUBS = SUBS;
+    b.PT = (a.N + SUBS - 1) / SUBS * (a.OH / TH) * (a.OW / TW);
+    b.CT = (a.Cout + 127) / 128; b.tile_px = tile;
+    p->kind = ConvKernel::stem;
+    p->grid = b.PT * b.CT;
+    p->lds = (size_t)128 * 80 + EPI_BYTES + 4096;     // + the 3-channel halo image
+    p->id = 300000;
+    p->stats_tile = one_image_tile(a, tile);
+    return true;
+}
+
+int conv_stem_launch(const ConvPlan& p, hipStream_t st) {
+    hipLaunchKernelGGL(conv_stem_kernel, dim3(p.grid), dim3(256), p.lds, st, p.args);
+    DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(stem)");
+    return DXMI_OK;
+}
+
+// The software-pipelined kernel (stride-1 / upsampled / stride-2 3x3 convs, Cout % 64 == 0) and, for plain 1x1 convs,
+// conv1x1_stream_kernel.
+bool conv_pipe_select(const ConvArgs& a, ConvPlan* p) {
+    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return false;
+    if (a.Cout % 64 != 0 || (a.C0 + a.C1) % 64 != 0 || a.C0 % 32 != 0) return false;  // even chunk count
+    if (a.stride != 1 && !(a.stride == 2 && a.ups == 0 && a.ksize == 3)) return false;   // stride 2: Downsample convs
     const int CT = (a.Cout + 127) / 128;
-    // pixel-tile size: the largest of 256/128/64 that still gives every CU a workgroup
+    // pixel-tile size: 128 pixels (2 workgroups / CU: one's tile switch hides under the other's MFMAs; measured faster than
+    // 256-pixel tiles at 1 workgroup / CU) where that still gives every CU two workgroups, else 64
     const long px = (long)a.N * a.OH * a.OW;
-    int NB = 8;
-    while (NB > 2 && (px / (32 * NB)) * CT < 512) NB >>= 1;   // two workgroups per CU
-    // 128-pixel tiles (2 workgroups / CU: one's tile switch hides under the other's MFMAs) measured
-    // faster than 256-pixel tiles at 1 workgroup / CU: default cap 4.
-    static const int nb_env = getenv("DXMI_CONV_NB") ? atoi(getenv("DXMI_CONV_NB")) : 4;  // tuning override (2 or 4)
-    const int nb_cap = nb_env >= 4 ? 4 : 2;
-    while (NB > nb_cap && NB > 2) NB >>= 1;
+    int NB = (px / 128) * CT < 512 ? 2 : 4;
     if (a.stride == 2) NB = 2;   // the stride-2 halo of a 64-pixel tile is 17x17 pixels (23 KB)
-    if (a.ksize == 1 && a.ups == 0) NB = 2;   // 1x1: 64-pixel tiles, four workgroups per CU (conv1x1_stream_kernel)
+    const bool stream1x1 = a.ksize == 1 && a.ups == 0;
+    if (stream1x1) NB = 2;   // 1x1: 64-pixel tiles, four workgroups per CU (conv1x1_stream_kernel)
     const int tile = 32 * NB;
     const int TW = a.OW < 32 ? a.OW : 32;
     int TH = tile / TW;
     if (TH > a.OH) TH = a.OH;
     const int SUBS = tile / (TW * TH);
-    if (TW * TH * SUBS != tile) return 1;
-    ConvArgs b = a;
-    b.TWl = ilog2p(TW); b.THl = ilog2p(TH); b.SUBS = SUBS;
-    b.HH = (TH - 1) * a.stride + a.ksize; b.HWd = (TW - 1) * a.stride + a.ksize;
-    b.tile_px = tile;
-    const int ngroups = (a.N + SUBS - 1) / SUBS;
-    b.PT = ngroups * (a.OH / TH) * (a.OW / TW);
-    b.CT = CT;
-    const int HP = SUBS * b.HH * b.HWd;
+    if (TW * TH * SUBS != tile) return false;
+    const int HH = (TH - 1) * a.stride + a.ksize, HWd = (TW - 1) * a.stride + a.ksize;
     // LDS pitches: a 32-pixel MFMA block spans 32/TW halo rows; the ds_read_b128 lane groups stay
     // conflict-free when consecutive rows are offset by 0 / 128 / 64 bytes (mod 256) for TW = 16 / 8 / 4
     // (brute-forced over the b128 lane groups; TW = 32 is conflict-free at any pitch) and sub-images by
     // a multiple of 256.
-    {
-        const int want = TW == 16 ? 0 : (TW == 8 ? 128 : (TW == 4 ? 64 : -1));
-        int rp = b.HWd * 80;
-        if (want >= 0) while (rp % 256 != want) rp += 16;
-        int sp = b.HH * rp;
-        if (SUBS > 1) while (sp % 256 != 0) sp += 16;
-        b.RP = rp; b.SP = sp;
-    }
-    b.lds_buf = SUBS * b.SP;
-    if (2 * b.lds_buf + EPI_BYTES > 160 * 1024) return 1;
-    const int npieces = HP * 4;
-    if (npieces > 6 * 256) return 1;          // larger halos go to the generic kernel
-    // staging pieces per thread: the small counts get the two-set (SD = 2) kernels
-    const int pmax = (a.ksize == 3 && NB == 4 && npieces <= 4 * 256) ? 4 : 6;
-    const bool stream1x1 = a.ksize == 1 && a.ups == 0;
-    if (kernel_id) {
-        // kxxyy = conv_pipe_kernel<xx, yy, k> ; 200000 = conv1x1_stream_kernel<2, 4, 4>
-        *kernel_id = stream1x1 ? 200000 : 10000 * a.ksize + NB * 100 + pmax;
-        return DXMI_OK;
-    }
-    // persistent grid: as many workgroups as are co-resident (2 per CU for NB <= 4, else 1), a
-    // multiple of CT; each walks PT / nstreams pixel tiles.
-    static const int wg_per_cu = getenv("DXMI_CONV_WGS") ? atoi(getenv("DXMI_CONV_WGS")) : 0;
-    const int resident = 256 * (wg_per_cu > 0 ? wg_per_cu : (NB <= 4 ? 2 : 1));
-    int nstreams = resident / CT;
+    const int want = TW == 16 ? 0 : (TW == 8 ? 128 : (TW == 4 ? 64 : -1));
+    int rp = HWd * 80;
+    if (want >= 0) while (rp % 256 != want) rp += 16;
+    int sp = HH * rp;
+    if (SUBS > 1) while (sp % 256 != 0) sp += 16;
+    if (2 * SUBS * sp + EPI_BYTES > 160 * 1024) return false;
+    const int npieces = SUBS * HH * HWd * 4;
+    if (npieces > 6 * 256) return false;          // larger halos go to the generic kernel
+    ConvArgs& b = p->args;
+    b.TWl = ilog2p(TW); b.THl = ilog2p(TH); b.SUBS = SUBS; b.HH = HH; b.HWd = HWd; b.tile_px = tile;
+    b.PT = (a.N + SUBS - 1) / SUBS * (a.OH / TH) * (a.OW / TW);
+    b.CT = CT; b.RP = rp; b.SP = sp; b.lds_buf = SUBS * sp;
+    // persistent grid: as many workgroups as are co-resident (2 per CU), a multiple of CT; each walks PT / nstreams pixel tiles
+    int nstreams = 512 / CT;
     if (nstreams > b.PT) nstreams = b.PT;
     if (nstreams >= 8) nstreams &= ~7;   // whole XCD groups (see the kernel's block mapping)
     if (nstreams < 1) nstreams = 1;
     const int grid = nstreams * CT;
-    static const int stagger = getenv("DXMI_CONV_STAGGER") ? atoi(getenv("DXMI_CONV_STAGGER")) : 2;   // measured: 0 -> 2 = -2 % conv time
-    b.stagger = (grid > 256 && b.PT / nstreams >= 2) ? stagger : 0;
-    if (stream1x1) return launch_stream<2, 4, 4>(b, b.PT * CT, st);
+    b.stagger = (grid > 256 && b.PT / nstreams >= 2) ? 2 : 0;   // measured: 0 -> 2 = -2 % conv time
+    p->stats_tile = one_image_tile(a, tile);
+    if (stream1x1) {
+        p->kind = ConvKernel::stream1x1;    // conv1x1_stream_kernel<2, 4, 4>: one workgroup per tile
+        p->grid = b.PT * CT;
+        p->lds = 4 * 32 * 2 * 80 > EPI_BYTES ? 4 * 32 * 2 * 80 : EPI_BYTES;
+        p->id = 200000;
+        return true;
+    }
+    // staging pieces per thread: the small counts get the two-set (SD = 2) kernels
+    const int pmax = (a.ksize == 3 && NB == 4 && npieces <= 4 * 256) ? 4 : 6;
+    p->kind = ConvKernel::pipe; p->t0 = NB; p->t1 = pmax; p->t2 = a.ksize;
+    p->grid = grid;
+    p->lds = (size_t)2 * b.lds_buf + EPI_BYTES;
+    p->id = 10000 * a.ksize + NB * 100 + pmax;    // conv_pipe_kernel<NB, PMAX, KS>
+    return true;
+}
+
+int conv_pipe_launch(const ConvPlan& p, hipStream_t st) {
+    if (p.kind == ConvKernel::stream1x1) return launch_stream<2, 4, 4>(p, st);
     // queue depth by shape: 3x3 at NB=2 (4x4 / 8x8 maps, latency bound) 8 ahead, 3x3 at NB=4 3 ahead with the two staging sets (4 ahead spills
     // at two workgroups per CU: measured 4.74 -> 4.63 ms of conv time per forward going from 4 to 3), 1x1 (short K loops, measured no gain) 1 ahead
     // staging distance: with few enough halo pieces per thread two register sets fit, and the halo of the chunk AFTER
     // next is requested (17 steps of cover instead of 8): -5..10 % on the K <= 2304 layers
-    if (a.ksize == 3) {
-        if (NB == 4) return pmax == 4 ? launch_pipe<4, 4, 3, 0, 3, 2>(b, grid, st) : launch_pipe<4, 6, 3, 0, 4>(b, grid, st);
-        return launch_pipe<2, 6, 3, 0, 8>(b, grid, st);   // 64-pixel tiles: the second register set measured no gain
+    if (p.t2 == 3) {
+        if (p.t0 == 4) return p.t1 == 4 ? launch_pipe<4, 4, 3, 0, 3, 2>(p, st) : launch_pipe<4, 6, 3, 0, 4>(p, st);
+        return launch_pipe<2, 6, 3, 0, 8>(p, st);   // 64-pixel tiles: the second register set measured no gain
     }
-    return NB == 4 ? launch_pipe<4, 6, 1>(b, grid, st) : launch_pipe<2, 6, 1>(b, grid, st);   // 1x1 behind an upsample (unused by the nets)
+    return p.t0 == 4 ? launch_pipe<4, 6, 1>(p, st) : launch_pipe<2, 6, 1>(p, st);   // 1x1 behind an upsample (unused by the nets)
 }

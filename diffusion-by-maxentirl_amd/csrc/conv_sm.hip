@@ -348,8 +348,8 @@ __global__ __launch_bounds__(256 + 64 * NL) void conv_sm_kernel(ConvArgs p) {
 
 }  // namespace
 
-// Launches the small-map kernel when the shape is in its scope; returns 1 otherwise (caller falls back).
-int conv_sm_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
+// The small-map kernel's scope and tiling.
+bool conv_sm_select(const ConvArgs& a, ConvPlan* p) {
     // bit 0: 4x4 maps (32-cout tiles), bit 1: every 8x8 map, bit 3: see below, bit 2: 8x8 maps whose conv_ws8 grid (256-pixel x 128-cout tiles) would
     // leave more than half of the CUs idle (round 4: the EDM nets at the train batch of 16 - 24 tiles; 768 -> 768 measured 40.0 us
     // on conv_ws8_kernel, 18.6 us here with 192 workgroups; at 150 tiles conv_ws8_kernel is 5-9 % ahead); 0: conv_ws8 / conv_pipe
@@ -360,38 +360,22 @@ int conv_sm_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
     // >= 1024 channels in and out — the bottom of the LSUN-256 net, whose per-GPU batch of 16 is 32 conv_ws8 tiles; at batch 100
     // this kernel is ~5 % behind conv_ws8_kernel on such layers, at batch 16 it is 2x ahead
     const bool wide8 = a.OW == 8 && a.C0 + a.C1 >= 1024 && a.Cout >= 1024;
-    if (!((a.OW == 4 && (enabled & 1)) || (a.OW == 8 && ((enabled & 2) || ((enabled & 4) && small_grid8) || ((enabled & 8) && wide8))))) return 1;
-    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return 1;
-    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups != 0 || (a.mask_src && a.residual) || a.act == DXMI_ACT_SILU || a.gn_stats) return 1;   // a mask alone rides the residual path
-    if (a.OH != a.OW || (a.OW != 4 && a.OW != 8) || a.IH != a.OH || a.IW != a.OW) return 1;
+    if (!((a.OW == 4 && (enabled & 1)) || (a.OW == 8 && ((enabled & 2) || ((enabled & 4) && small_grid8) || ((enabled & 8) && wide8))))) return false;
+    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return false;
+    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups != 0 || (a.mask_src && a.residual) || a.act == DXMI_ACT_SILU) return false;   // a mask alone rides the residual path
+    if (a.OH != a.OW || (a.OW != 4 && a.OW != 8) || a.IH != a.OH || a.IW != a.OW) return false;
     // tile width: 64 couts where that still gives every CU a tile (8x8 maps at batch 256), else 32
     const int imgs = 128 / (a.OH * a.OW);
     const int PT = (a.N + imgs - 1) / imgs;
     const int MT = (a.Cout % 64 == 0 && (long)PT * (a.Cout / 64) >= 256) ? 64 : 32;
-    if (a.Cout % MT != 0 || a.C0 % 32 != 0 || a.C1 % 32 != 0) return 1;
-    if (a.gn_out && !(a.OW == 4 && MT == 32)) return 1;      // the fused GroupNorm needs whole images per DPP row
+    if (a.Cout % MT != 0 || a.C0 % 32 != 0 || a.C1 % 32 != 0) return false;
+    p->gn_out = a.OW == 4 && MT == 32;       // the fused GroupNorm needs whole images per DPP row
+    if (a.gn_out && !p->gn_out) return false;
     const int nchunks = (a.C0 + a.C1) / 32;
-    if (nchunks < 5) return 1;               // the residual / table buffers are refilled R - 1 chunks ahead of their tile's end
-    if ((long)a.N * a.OH * a.OW * (a.C0 > a.C1 ? a.C0 : a.C1) * 2 >= (1L << 31)) return 1;
-    if (kernel_id) {
-        *kernel_id = 450000 + a.OW * 100 + MT;      // conv_sm_kernel<log2 OW, 8, MT>
-        return DXMI_OK;
-    }
-    static const void* zero_page = nullptr;
-    if (!zero_page) {
-        void* zp = nullptr;
-        if (hipGetSymbolAddress(&zp, HIP_SYMBOL(sm_zero16)) != hipSuccess || !zp) {
-            dxmi_set_error("dxmi_conv2d_fwd(sm): hipGetSymbolAddress(sm_zero16) failed");
-            return DXMI_EINVAL;
-        }
-        zero_page = zp;
-    }
-    ConvArgs b = a;
-    if (a.mask_src) {
-        b.residual = a.mask_src;
-        b.res_is_mask = 1;
-    }
-    b.mask_src = reinterpret_cast<const bf16*>(zero_page);    // the field carries the zero page (a mask source travels in `residual`)
+    if (nchunks < 5) return false;               // the residual / table buffers are refilled R - 1 chunks ahead of their tile's end
+    if ((long)a.N * a.OH * a.OW * (a.C0 > a.C1 ? a.C0 : a.C1) * 2 >= (1L << 31)) return false;
+    ConvArgs& b = p->args;
+    if (a.mask_src) { b.residual = a.mask_src; b.res_is_mask = 1; }
     b.PT = PT;
     b.CT = a.Cout / MT;
     b.tile_px = 128;
@@ -400,14 +384,26 @@ int conv_sm_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
     // at 8 cout tiles, every XCD serves one slice of the weights)
     int grid = ntiles < 256 ? ntiles : (256 / b.CT) * b.CT;
     if (grid < 1) grid = ntiles < b.CT ? ntiles : b.CT;
+    p->kind = ConvKernel::sm; p->t0 = a.OW == 4 ? 2 : 3; p->t1 = MT;
+    p->grid = grid;
+    p->lds = MT == 32 ? SmCfg<32>::LDS : SmCfg<64>::LDS;
+    p->id = 450000 + a.OW * 100 + MT;      // conv_sm_kernel<log2 OW, 8, MT>
+    return true;
+}
+
+int conv_sm_launch(const ConvPlan& p, hipStream_t st) {
+    static const void* zero_page = nullptr;
+    DXMI_CHECK_ARG(conv_zero_page(zero_page, HIP_SYMBOL(sm_zero16)), "dxmi_conv2d_fwd(sm): hipGetSymbolAddress(sm_zero16) failed");
+    ConvArgs b = p.args;
+    b.mask_src = reinterpret_cast<const bf16*>(zero_page);    // the field carries the zero page (a mask source travels in `residual`)
 #define SM_LAUNCH(ML_, MT_)                                                                                                   \
     do {                                                                                                                      \
         static bool attr = false;                                                                                             \
         if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sm_kernel<ML_, 8, MT_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        hipLaunchKernelGGL((conv_sm_kernel<ML_, 8, MT_>), dim3(grid), dim3(256 + 64 * 8), SmCfg<MT_>::LDS, st, b);            \
+        hipLaunchKernelGGL((conv_sm_kernel<ML_, 8, MT_>), dim3(p.grid), dim3(256 + 64 * 8), p.lds, st, b);                    \
     } while (0)
-    if (a.OW == 4) { if (MT == 32) SM_LAUNCH(2, 32); else SM_LAUNCH(2, 64); }
-    else { if (MT == 32) SM_LAUNCH(3, 32); else SM_LAUNCH(3, 64); }
+    if (p.t0 == 2) { if (p.t1 == 32) SM_LAUNCH(2, 32); else SM_LAUNCH(2, 64); }
+    else { if (p.t1 == 32) SM_LAUNCH(3, 32); else SM_LAUNCH(3, 64); }
 #undef SM_LAUNCH
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(sm)");
     return DXMI_OK;

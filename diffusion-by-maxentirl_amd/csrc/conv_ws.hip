@@ -782,73 +782,61 @@ __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs p) {
 
 }  // namespace
 
-// Launches the wave-specialised kernel when the shape is in its scope; returns 1 otherwise (caller falls back).
-int conv_ws_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
-    static const int enabled = getenv("DXMI_CONV_WS") ? atoi(getenv("DXMI_CONV_WS")) : 1;   // DXMI_CONV_WS=0: conv_pipe_kernel for every shape
-    if (!enabled) return 1;
-    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return 1;
+// The wave-specialised kernel's scope and tiling.
+bool conv_ws_select(const ConvArgs& a, ConvPlan* p) {
+    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return false;
     // an activation mask (data gradient of the value net's convs: out *= mask_src > 0 ? 1 : slope) rides the residual tile's path
     // when there is no residual; both at once stay on conv_pipe_kernel
-    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups == 2 || (a.mask_src && a.residual) || a.act == DXMI_ACT_SILU) return 1;
-    if (a.gn_out) return 1;          // a fused GroupNorm of the output: conv_sm_kernel / conv_ws8_kernel only
-    if (a.Cout % 64 != 0 || (a.C0 + a.C1) % 32 != 0 || a.C0 % 32 != 0) return 1;   // Cout % 128 == 64: the last cout tile is half empty
+    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups == 2 || (a.mask_src && a.residual) || a.act == DXMI_ACT_SILU) return false;
+    if (a.Cout % 64 != 0 || (a.C0 + a.C1) % 32 != 0 || a.C0 % 32 != 0) return false;   // Cout % 128 == 64: the last cout tile is half empty
     const int TW = a.OW >= 32 ? 32 : a.OW;
-    if (TW != 32 && TW != 16) return 1;
+    if (TW != 32 && TW != 16) return false;
     const int TH = 256 / TW;
-    if (a.OH % TH != 0 || a.OW % TW != 0) return 1;
+    if (a.OH % TH != 0 || a.OW % TW != 0) return false;
     const int nchunks = (a.C0 + a.C1) / 32;
-    if ((9 * nchunks) % WS_RING != 0 || nchunks % 2 != 0) return 1;   // ring slot / halo image of a step must not depend on the tile
-    if (nchunks < 4) return 1;   // the tile switch is spread over nchunks-1 chunks at <= 12 pieces per chunk
+    if ((9 * nchunks) % WS_RING != 0 || nchunks % 2 != 0) return false;   // ring slot / halo image of a step must not depend on the tile
+    if (nchunks < 4) return false;   // the tile switch is spread over nchunks-1 chunks at <= 12 pieces per chunk
     // fewer (256-pixel, 128-cout) tiles than ~a third of the CUs (the EDM nets' 16x16 maps at the train batch of 16: 80 tiles):
     // conv_pipe_kernel's 64-pixel tiles fill the chip better (576 -> 576 @16x16, B = 16: 48.1 us here, 41.1 us there; at 192
     // tiles this kernel is 40 % ahead)
     // (knob "conv_ws_min_tiles" / DXMI_CONV_WS_MIN_TILES; the kernel's own edge-case tests set it to 0)
     const int min_tiles = dxmi_tuning("conv_ws_min_tiles");
-    if ((long)a.N * (a.OH / TH) * (a.OW / TW) * ((a.Cout + 127) / 128) < min_tiles) return 1;
+    if ((long)a.N * (a.OH / TH) * (a.OW / TW) * ((a.Cout + 127) / 128) < min_tiles) return false;
     // 32-bit byte offsets inside either input part (the movers' per-tile source tables)
-    if ((long)a.N * a.IH * a.IW * (a.C0 > a.C1 ? a.C0 : a.C1) * 2 >= (1L << 31)) return 1;
-    if (kernel_id) {
-        *kernel_id = 400000 + TW;    // conv_ws_kernel<TW>
-        return DXMI_OK;
-    }
-    static const void* zero_page = nullptr;
-    if (!zero_page) {
-        void* zp = nullptr;
-        if (hipGetSymbolAddress(&zp, HIP_SYMBOL(ws_zero16)) != hipSuccess || !zp) {
-            dxmi_set_error("dxmi_conv2d_fwd(ws): hipGetSymbolAddress(ws_zero16) failed");
-            return DXMI_EINVAL;
-        }
-        zero_page = zp;
-    }
-    ConvArgs b = a;
-    if (a.mask_src) {
-        b.residual = a.mask_src;
-        b.res_is_mask = 1;
-    }
-    b.mask_src = reinterpret_cast<const bf16*>(zero_page);    // the field carries the zero page (a mask source travels in `residual`)
+    if ((long)a.N * a.IH * a.IW * (a.C0 > a.C1 ? a.C0 : a.C1) * 2 >= (1L << 31)) return false;
+    ConvArgs& b = p->args;
+    if (a.mask_src) { b.residual = a.mask_src; b.res_is_mask = 1; }
     b.SUBS = 1;
     b.PT = a.N * (a.OH / TH) * (a.OW / TW);
     b.CT = (a.Cout + 127) / 128;
     b.tile_px = 256;
-    static const int xcd_env = getenv("DXMI_CONV_WS_XCD") ? atoi(getenv("DXMI_CONV_WS_XCD")) : 1;
-    b.xcd_order = xcd_env;
+    b.xcd_order = 1;
+    b.stagger = 0;
+    p->kind = ConvKernel::ws; p->t0 = TW;
+    p->grid = b.PT * b.CT < 256 ? b.PT * b.CT : 256;
+    p->lds = 2 * WS_HALO + WS_A_RING + WS_RO + WS_TB;
+    p->id = 400000 + TW;    // conv_ws_kernel<TW>
+    p->stats_tile = 128;    // one partial per (pixel tile, pixel half)
+    return true;
+}
+
+int conv_ws_launch(const ConvPlan& p, hipStream_t st) {
+    static const void* zero_page = nullptr;
+    DXMI_CHECK_ARG(conv_zero_page(zero_page, HIP_SYMBOL(ws_zero16)), "dxmi_conv2d_fwd(ws): hipGetSymbolAddress(ws_zero16) failed");
+    ConvArgs b = p.args;
+    b.mask_src = reinterpret_cast<const bf16*>(zero_page);    // the field carries the zero page (a mask source travels in `residual`)
 #ifdef DXMI_CONV_STAMPS
     static const int dbg = getenv("DXMI_CONV_WS_DBG") ? atoi(getenv("DXMI_CONV_WS_DBG")) : 0;
     b.stagger = dbg;
-#else
-    b.stagger = 0;
 #endif
-    const size_t lds = 2 * WS_HALO + WS_A_RING + WS_RO + WS_TB;
-    int grid = b.PT * b.CT;
-    if (grid > 256) grid = 256;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    if (TW == 32) hipLaunchKernelGGL(conv_ws_kernel<32>, dim3(grid), dim3(512), lds, st, b);
-    else hipLaunchKernelGGL(conv_ws_kernel<16>, dim3(grid), dim3(512), lds, st, b);
+    if (p.t0 == 32) hipLaunchKernelGGL(conv_ws_kernel<32>, dim3(p.grid), dim3(512), p.lds, st, b);
+    else hipLaunchKernelGGL(conv_ws_kernel<16>, dim3(p.grid), dim3(512), p.lds, st, b);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(ws)");
     return DXMI_OK;
 }

@@ -11,7 +11,6 @@
 // Scope: 3x3 / stride 1 / pad 1 on 8x8 maps, NHWC bf16 in (virtual concat) and out, any batch, Cout % 64 == 0,
 // an even number (>= 4) of 32-channel chunks.
 #include "conv_common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 
@@ -547,60 +546,47 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
 
 }  // namespace
 
-// Launches the 8x8-map wave-specialised kernel when the shape is in its scope; returns 1 otherwise (caller falls back).
-int conv_ws8_try_launch(ConvArgs& a, hipStream_t st, int* kernel_id) {
-    static const int enabled = getenv("DXMI_CONV_WS8") ? atoi(getenv("DXMI_CONV_WS8")) : 1;   // 0: conv_pipe_kernel for the 8x8 maps
-    if (!enabled) return 1;
-    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return 1;
-    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups == 2 || (a.mask_src && a.residual) || a.act == DXMI_ACT_SILU) return 1;   // a mask alone rides the residual path
-    if (a.OH != 8 || a.OW != 8) return 1;
-    if (a.ups ? (a.IH != 4 || a.IW != 4) : (a.IH != 8 || a.IW != 8)) return 1;     // ups: nearest x2 upsample of a 4x4 map in front
-    if (a.Cout % 64 != 0 || (a.C0 + a.C1) % 32 != 0 || a.C0 % 32 != 0) return 1;
+// The 8x8-map wave-specialised kernel's scope and tiling.
+bool conv_ws8_select(const ConvArgs& a, ConvPlan* p) {
+    if (a.in_mode != DXMI_IN_NHWC_BF16 || a.out_mode != DXMI_OUT_NHWC_BF16) return false;
+    if (a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.ups == 2 || (a.mask_src && a.residual) || a.act == DXMI_ACT_SILU) return false;   // a mask alone rides the residual path
+    if (a.OH != 8 || a.OW != 8) return false;
+    if (a.ups ? (a.IH != 4 || a.IW != 4) : (a.IH != 8 || a.IW != 8)) return false;     // ups: nearest x2 upsample of a 4x4 map in front
+    if (a.Cout % 64 != 0 || (a.C0 + a.C1) % 32 != 0 || a.C0 % 32 != 0) return false;
     const int nchunks = (a.C0 + a.C1) / 32;
-    if (nchunks < 4 || nchunks % 2 != 0 || (9 * nchunks) % W8_RING != 0) return 1;
+    if (nchunks < 4 || nchunks % 2 != 0 || (9 * nchunks) % W8_RING != 0) return false;
     // no batch-size condition: an image's result must not depend on the batch it rides in (the kernels differ in summation order)
-    if ((long)a.N * 64 * (a.C0 > a.C1 ? a.C0 : a.C1) * 2 >= (1L << 31)) return 1;   // 32-bit byte offsets inside either input part
-    if (a.gn_out && !(a.gn_flags & 2)) return 1;     // the fused GroupNorm replaces the raw output (one output tile in LDS)
-    if (kernel_id) {
-        *kernel_id = 400008;    // conv_ws8_kernel
-        return DXMI_OK;
-    }
-    static const void* zero_page = nullptr;
-    if (!zero_page) {
-        void* zp = nullptr;
-        if (hipGetSymbolAddress(&zp, HIP_SYMBOL(w8_zero16)) != hipSuccess || !zp) {
-            dxmi_set_error("dxmi_conv2d_fwd(ws8): hipGetSymbolAddress(w8_zero16) failed");
-            return DXMI_EINVAL;
-        }
-        zero_page = zp;
-    }
-    ConvArgs b = a;
-    if (a.mask_src) {
-        b.residual = a.mask_src;
-        b.res_is_mask = 1;
-    }
-    b.mask_src = reinterpret_cast<const bf16*>(zero_page);    // the field carries the zero page (a mask source travels in `residual`)
+    if ((long)a.N * 64 * (a.C0 > a.C1 ? a.C0 : a.C1) * 2 >= (1L << 31)) return false;   // 32-bit byte offsets inside either input part
+    p->gn_out = (a.gn_flags & 2) != 0;       // the fused GroupNorm replaces the raw output (one output tile in LDS)
+    if (a.gn_out && !p->gn_out) return false;
+    ConvArgs& b = p->args;
+    if (a.mask_src) { b.residual = a.mask_src; b.res_is_mask = 1; }
+    if (a.gn_out) b.out = a.gn_out;       // the movers drain the (normalised) tile to the fused output
     b.SUBS = 4;
     b.PT = (a.N + 3) / 4;      // the last tile may hold fewer than four images (masked)
     b.CT = a.Cout / 64;
     b.tile_px = 256;
-    static const int xcd_env = getenv("DXMI_CONV_WS_XCD") ? atoi(getenv("DXMI_CONV_WS_XCD")) : 1;
-    b.xcd_order = xcd_env;
-    const size_t lds = 2 * W8_HALO + W8_A_RING + W8_RO + W8_TB;
-    int grid = b.PT * b.CT;
-    if (grid > 256) grid = 256;
+    b.xcd_order = 1;
+    p->kind = ConvKernel::ws8; p->t0 = a.gn_out != nullptr;
+    p->grid = b.PT * b.CT < 256 ? b.PT * b.CT : 256;
+    p->lds = 2 * W8_HALO + W8_A_RING + W8_RO + W8_TB;
+    p->id = 400008;    // conv_ws8_kernel
+    return true;
+}
+
+int conv_ws8_launch(const ConvPlan& p, hipStream_t st) {
+    static const void* zero_page = nullptr;
+    DXMI_CHECK_ARG(conv_zero_page(zero_page, HIP_SYMBOL(w8_zero16)), "dxmi_conv2d_fwd(ws8): hipGetSymbolAddress(w8_zero16) failed");
+    ConvArgs b = p.args;
+    b.mask_src = reinterpret_cast<const bf16*>(zero_page);    // the field carries the zero page (a mask source travels in `residual`)
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws8_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws8_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    if (a.gn_out) {
-        b.out = a.gn_out;       // the movers drain the (normalised) tile to the fused output
-        hipLaunchKernelGGL(conv_ws8_kernel<true>, dim3(grid), dim3(512), lds, st, b);
-    } else {
-        hipLaunchKernelGGL(conv_ws8_kernel<false>, dim3(grid), dim3(512), lds, st, b);
-    }
+    if (p.t0) hipLaunchKernelGGL(conv_ws8_kernel<true>, dim3(p.grid), dim3(512), p.lds, st, b);
+    else hipLaunchKernelGGL(conv_ws8_kernel<false>, dim3(p.grid), dim3(512), p.lds, st, b);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(ws8)");
     return DXMI_OK;
 }

@@ -196,6 +196,12 @@ class FwdCensus(backward_census.Census):
 
 def conv_kernel_id(ops, r):
     """dxmi_conv2d_kernel_id of a conv2d census row under its recorded tuning: a host-side query (no launch, no device memory)."""
+    return conv_query(ops, r, "dxmi_conv2d_kernel_id")
+
+
+def conv_query(ops, r, fn, *args, **fields):
+    """lib.fn(descriptor of a conv2d census row, *args) under the row's recorded tuning, with `fields` set on the descriptor: a
+    host-side query (no launch, no device memory)."""
     (_, xs, c1, Cout, k, k27, stride, pad, pad_br, ups, has_bias, addvec, has_res, has_mask, act, nchw, want_stats, fuse, variant,
      P, tuning, kid) = r
     d = ops.ConvDesc()
@@ -216,9 +222,11 @@ def conv_kernel_id(ops, r):
     d.in_mode = ops.IN_NCHW_F32_K27 if k27 else ops.IN_NHWC_BF16
     d.out_mode = ops.OUT_NCHW_F32 if nchw else ops.OUT_NHWC_BF16
     d.variant = variant
+    for name, v in fields.items():
+        setattr(d, name, v)
     tune = ops.throughput_tuning() if tuning == "throughput" else backward_census._nullctx()
     with tune:
-        return int(ops.load().dxmi_conv2d_kernel_id(ctypes.byref(d)))
+        return int(getattr(ops.load(), fn)(ctypes.byref(d), *args))
 
 
 def cifar10_sample(device, B, T):

@@ -12,6 +12,8 @@ bench.kernel_name can name, both linear forms, every attention kernel and every 
 GroupNorm inputs carry one mean offset per group: the largest (image, group) |mean| / std of every image is COND_MULT times the
 largest the census measured on the programs' own activations (random-init nets, not trained weights), at least MIN_COND.
 """
+import json
+import os
 import zlib
 
 import pytest
@@ -1068,9 +1070,57 @@ def test_extra_conv_rows_select_their_kernel(ops):
         assert forward_census.conv_kernel_id(ops, r) == r[-1], r
 
 
+PLAN_QUERIES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan_queries.json")
+
+
+def conv_plan_queries(ops, r):
+    """The host-side queries that read the forward conv selection besides the kernel id: GroupNorm statistics partials per
+    image, the fused GroupNorm output (8 channels per group) in place of / next to the raw output, and the norm1 + 1x1
+    shortcut fusion with 32 groups."""
+    q = forward_census.conv_query
+    fuse = dict(gn_groups=r[3] // 8)
+    return [q(ops, r, "dxmi_conv2d_gn_stats_partials"),
+            q(ops, r, "dxmi_conv2d_gn_fuse_supported", gn_flags=2, **fuse),
+            q(ops, r, "dxmi_conv2d_gn_fuse_supported", gn_flags=0, **fuse),
+            q(ops, r, "dxmi_groupnorm_silu_shortcut_supported", 32)]
+
+
+def test_conv_rows_plan_queries(ops):
+    """Host-side queries (no launch): every CASES + EXTRA conv row answers conv_plan_queries as recorded in
+    golden/conv_plan_queries.json (rows not listed there answer all zeros)."""
+    with open(PLAN_QUERIES) as f:
+        want = json.load(f)
+    got = {}
+    for r in [r for r in EXTRA + CASES if r[0] == "conv2d"]:
+        v = conv_plan_queries(ops, r)
+        if any(v):
+            got[repr(r)] = v
+    assert got == want
+
+
+@pytest.mark.parametrize("Cout", [4224, 8192])
+def test_wide_1x1_reports_the_kernel_that_runs(ops, Cout):
+    """1x1, K = 256, Cout / 128 > 32: beyond conv1x1_rw_kernel's 32 cout tiles, so the query names conv1x1_stream_kernel, which
+    is what dxmi_conv2d_fwd launches."""
+    assert forward_census.conv_kernel_id(ops, _cx((32, 32, 32, 256), Cout, 1, 200000)) == 200000
+
+
+@pytest.mark.parametrize("hw", [4, 8])
+def test_stats_request_on_small_maps_is_refused(ops, hw):
+    """gn_stats on a 3x3 conv over 8x8 (conv_ws8_kernel) or 4x4 maps (conv_sm_kernel): neither kernel writes GroupNorm
+    statistics, so dxmi_conv2d_fwd refuses the request before any launch (host-side: no device memory)."""
+    C = 128 if hw == 8 else 256
+    r = _cx((2, hw, hw, C), C, 3, 400008 if hw == 8 else 450432)
+    assert forward_census.conv_kernel_id(ops, r) == r[-1]
+    assert forward_census.conv_query(ops, r, "dxmi_conv2d_gn_stats_partials") == 0
+    assert forward_census.conv_query(ops, r, "dxmi_conv2d_kernel_id", gn_stats=16) == -1      # DXMI_EINVAL: nothing to launch
+    assert forward_census.conv_query(ops, r, "dxmi_conv2d_fwd", None, gn_stats=16) == -1
+    assert "does not emit GroupNorm block statistics" in ops.load().dxmi_last_error().decode()
+
+
 def test_table_reaches_every_conv_kernel():
-    """CASES + EXTRA launch every conv kernel instance the forward dispatcher (dispatch_conv / conv_pipe_try_launch and the
-    launchers it tries) can select."""
+    """CASES + EXTRA launch every conv kernel instance the forward dispatcher (conv_select and the *_select functions it
+    tries) can select."""
     import bench
     assert conv_kernel_names(CASES + EXTRA) == {bench.kernel_name(k) for k in ALL_CONV_KERNEL_IDS}
 

@@ -1,6 +1,7 @@
 """GPU box: the 1x1 conv shapes of the ImageNet-64 ADM net with K = 576 / 768 (q|k|v, proj_out, skip_connection; B = 100),
-graph-captured time per launch on the kernel the library selects: DXMI_CONV1X1_RW8=0 / 1 switches conv1x1_rw8_kernel (round 5) off /
-on; SHAPES=small_k lists the K = 384 / 512 shapes (ImageNet-64 level 1, CIFAR-10, LSUN) — DESIGN 5.5."""
+graph-captured time per launch on the kernel the library selects; SHAPES=small_k lists the K = 384 / 512 shapes (ImageNet-64
+level 1, CIFAR-10, LSUN) — DESIGN 5.5.  The A/B against conv1x1_stream_kernel needs a variant library in which
+conv1x1_rw8_select declines (tools/build_variant.sh, timed through DXMI_LIB=<path>) next to the product one."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "diffusion-by-maxentirl_amd")]

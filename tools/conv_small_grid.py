@@ -1,5 +1,6 @@
 """GPU box: 3x3 conv shapes whose (pixel tile, cout tile) grid leaves most CUs idle (EDM nets at the train batch): time per launch
-with the wave-specialised kernels and with DXMI_CONV_WS=0 (conv_pipe_kernel: 64-pixel tiles).  B=16 python tools/conv_small_grid.py"""
+on the kernel the library selects, and with the knob conv_ws_min_tiles raised past every shape (conv_ws_kernel declines:
+conv_pipe_kernel, 64-pixel tiles, on the maps it would take).  B=16 python tools/conv_small_grid.py"""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,15 +14,20 @@ for (cin, cout, h) in SHAPES:
     pw = ops.pack_conv_weight(torch.randn(cout, cin, 3, 3, device=dev) * 0.05)
     bias = torch.randn(cout, device=dev)
     out = torch.empty(B, h, h, cout, device=dev, dtype=torch.bfloat16)
-    for _ in range(5):
-        ops.conv2d(x, pw, bias=bias, out=out)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    n = 50
-    e0.record()
-    for _ in range(n):
-        ops.conv2d(x, pw, bias=bias, out=out)
-    e1.record(); torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / n
     tiles = (B * h * h // 256) * ((cout + 127) // 128)
-    print(f"B={B} {cin:4d}->{cout:4d} @{h:2d}: {us:7.1f} us  {2.0 * B * h * h * cout * cin * 9 / us / 1e6:7.0f} TFLOP/s   ws tiles {tiles}")
+    for min_tiles in (None, 1 << 30):
+        old = ops.set_tuning("conv_ws_min_tiles", min_tiles) if min_tiles else None
+        for _ in range(5):
+            ops.conv2d(x, pw, bias=bias, out=out)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        n = 50
+        e0.record()
+        for _ in range(n):
+            ops.conv2d(x, pw, bias=bias, out=out)
+        e1.record(); torch.cuda.synchronize()
+        if min_tiles:
+            ops.set_tuning("conv_ws_min_tiles", old)
+        us = e0.elapsed_time(e1) * 1e3 / n
+        print(f"B={B} {cin:4d}->{cout:4d} @{h:2d} {'no conv_ws' if min_tiles else 'selected  '}: {us:7.1f} us  "
+              f"{2.0 * B * h * h * cout * cin * 9 / us / 1e6:7.0f} TFLOP/s   ws tiles {tiles}")
