@@ -1,6 +1,6 @@
 """bench.py — DxMI hot-path throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1 works both ways: launched once per rank by torchrun / torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment), or as a plain `python bench.py --gpus N` — the parent then spawns N fresh rank processes BEFORE it touches
@@ -12,7 +12,8 @@ bf16 MFMA operands / fp32 accumulate / fp32 sampler state, random-init weights. 
 data-path collective (each rank draws its own trajectories: reference generate_cifar10.py:193-204), so scaling is "weak"
 and `value` = all ranks' images / max-over-ranks time of exactly K steps between barrier + synchronize brackets.
 
-The JSON line also carries
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs if asked, and
+prints the JSON line.  With --full the line also carries (each leg can still be left out with its --no-* option)
   roofline           the dominant kernel (3x3 MFMA implicit-GEMM conv): algorithmic FLOPs per launch / average launch
                      duration from HIP events on the launch stream, against the dense bf16 MFMA peak (2.5 PFLOP/s);
   roofline_classes   the same per kernel class — conv3x3 / conv1x1 (MFMA-graded), GroupNorm / attention / sampler step
@@ -61,7 +62,7 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-eager-reference", action="store_true")
     ap.add_argument("--no-events", action="store_true", help="skip the per-launch HIP events (roofline legs)")
-    ap.add_argument("--train-steps", type=int, default=8, help="timed DxMI train steps (0 = skip the train leg)")
+    ap.add_argument("--train-steps", type=int, default=None, help="timed DxMI train steps with --full (default 8; 0 = skip the train leg)")
     ap.add_argument("--no-edm", action="store_true", help="skip the EDM legs (BASELINE configs[3], configs[4] at their per-GPU sizes)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch images per GPU whatever N (generation shards by images: generate_cifar10.py:193-204); strong: the "
@@ -70,9 +71,19 @@ def parse_args():
     ap.add_argument("--no-small-batch", action="store_true", help="skip the 1-GPU legs at the per-rank batches of an 8-GPU / 4-GPU reference run (32 @ T=10, 128 @ T=4)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the arrays the last timed step returned (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: per-launch events (roofline), the train leg, the EDM legs, the small-batch "
+                         "legs, the eager reference and the CPU baseline (the --no-* options take legs out of this mode)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.full:
+        args.train_steps = 8 if args.train_steps is None else args.train_steps
+    else:                   # a plain run: set up, warm up, the timed steps, --dump-outputs, the line
+        if args.train_steps:
+            ap.error("--train-steps times the train leg, which runs with --full only")
+        args.no_events = args.no_edm = args.no_small_batch = args.no_eager_reference = args.no_cpu_baseline = True
+        args.train_steps = 0
     return args
 
 

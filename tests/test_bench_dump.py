@@ -49,6 +49,29 @@ def test_dump_outputs_budget_and_rows(tmp_path, B):
     assert info["arrays"] == {n: list(v.shape) for n, v in a.items()}
 
 
+def test_plain_run_leaves_the_other_legs_to_full(monkeypatch):
+    """Without --full a run measures the headline alone (asking it for train steps is an error); with it every leg is on by
+    default and the --no-* options still take legs out."""
+    import bench
+    legs = ("no_events", "no_edm", "no_small_batch", "no_eager_reference", "no_cpu_baseline")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse_args()
+    assert not a.full and all(getattr(a, k) for k in legs) and a.train_steps == 0
+    assert (a.gpus, a.steps, a.warmup, a.batch, a.T) == (1, 4, 2, 256, 10)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "4", "--train-steps", "0", "--no-edm"])
+    a = bench.parse_args()
+    assert not a.full and all(getattr(a, k) for k in legs) and a.train_steps == 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "4", "--train-steps", "3"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2", "--full"])
+    a = bench.parse_args()
+    assert a.full and not any(getattr(a, k) for k in legs) and a.train_steps == 8
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-edm", "--train-steps", "0"])
+    a = bench.parse_args()
+    assert a.no_edm and not a.no_events and a.train_steps == 0
+
+
 @pytest.mark.gpu
 def test_bench_dump_outputs_repeat_identically(tmp_path):
     """Two runs with the same arguments: --steps timed steps, ms_per_step in the line, and bit-identical dumps of the last step

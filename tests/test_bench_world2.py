@@ -23,7 +23,7 @@ def test_bench_two_ranks_on_one_gpu(scaling, world):
     env = dict(os.environ, DXMI_DIST_BACKEND="gloo", DXMI_DIST_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "32",
-           "--train-steps", "2", "--scaling", scaling]
+           "--full", "--train-steps", "2", "--scaling", scaling]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

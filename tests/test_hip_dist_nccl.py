@@ -77,7 +77,7 @@ def test_bench_self_launch_over_visible_gpus():
     import torch
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     n = torch.cuda.device_count()
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--train-steps", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--full", "--train-steps", "1",
                         "--no-cpu-baseline", "--no-eager-reference", "--no-edm", "--no-events", "--no-small-batch"], cwd=root, capture_output=True, text=True,
                        timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
