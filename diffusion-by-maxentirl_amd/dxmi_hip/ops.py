@@ -948,6 +948,93 @@ def edm_step(x, model_out, z, sigma, sigma_down, sigma_up, sigma_data=0.5, outs=
     return sample, mean
 
 
+# dxmi_edm_dsm_* weight schedules (include/dxmi_hip.h), by the reference's names (karras_diffusion.py:18-31)
+DSM_WEIGHT_SCHEDULES = {"snr": 0, "snr+1": 1, "karras": 2, "truncated-snr": 3, "uniform": 4}
+
+
+def _dsm_operands(x_start, sigma, same=(), per_sample=()):
+    """fp32 contiguous 16-byte aligned device tensors; `same` must have x_start's shape, sigma and `per_sample` N elements (the
+    kernels read N x CHW elements of every image-sized operand and N of every per-sample one)."""
+    ts = (x_start, sigma) + tuple(same) + tuple(per_sample)
+    _need_cuda(*ts)
+    for t in ts:
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+            raise _lib.DxmiError("dxmi_edm_dsm_*: fp32 contiguous 16-byte aligned device tensors")
+    if x_start.dim() < 2 or x_start.numel() == 0:
+        raise _lib.DxmiError(f"dxmi_edm_dsm_*: x_start must be a non-empty batch [N, ...], got {tuple(x_start.shape)}")
+    N = x_start.shape[0]
+    for t in same:
+        if t is not None and t.shape != x_start.shape:
+            raise _lib.DxmiError(f"dxmi_edm_dsm_*: operand of shape {tuple(t.shape)} where x_start's {tuple(x_start.shape)} is needed")
+    for t in (sigma,) + tuple(per_sample):
+        if t is not None and t.numel() != N:
+            raise _lib.DxmiError(f"dxmi_edm_dsm_*: per-sample operand of {t.numel()} elements for a batch of {N}")
+
+
+def _dsm_schedule(weight_schedule):
+    if weight_schedule not in DSM_WEIGHT_SCHEDULES:
+        raise NotImplementedError(f"weight schedule {weight_schedule!r}")
+    return DSM_WEIGHT_SCHEDULES[weight_schedule]
+
+
+def edm_dsm_prep(x_start, noise, sigma, sigma_data=0.5, out=None):
+    """-> (x_in = c_in(sigma) (x_start + noise sigma), t = 250 ln(sigma + 1e-44)) of the DSM loss (dxmi_edm_dsm_prep)."""
+    _dsm_operands(x_start, sigma, same=(noise, out))
+    N = x_start.shape[0]
+    x_in = torch.empty_like(x_start) if out is None else out
+    t = torch.empty(N, dtype=torch.float32, device=x_start.device)
+    check(load().dxmi_edm_dsm_prep(_ptr(x_start), _ptr(noise), _ptr(sigma), _ptr(x_in), _ptr(t), N, x_start.numel() // N,
+                                   float(sigma_data), _stream()), "dxmi_edm_dsm_prep")
+    return x_in, t
+
+
+def edm_dsm_loss_fwd(model_out, x_start, noise, sigma, weight_schedule, sigma_data=0.5, sigma_min=0.002, distillation=False):
+    """-> per-sample (xs_mse, mse) of the DSM loss (dxmi_edm_dsm_loss_fwd)."""
+    _dsm_operands(x_start, sigma, same=(model_out, noise))
+    N = x_start.shape[0]
+    xs = torch.empty(N, dtype=torch.float32, device=x_start.device)
+    mse = torch.empty_like(xs)
+    check(load().dxmi_edm_dsm_loss_fwd(_ptr(model_out), _ptr(x_start), _ptr(noise), _ptr(sigma), _ptr(xs), _ptr(mse), N,
+                                       x_start.numel() // N, float(sigma_data), float(sigma_min), int(bool(distillation)),
+                                       _dsm_schedule(weight_schedule), _stream()), "dxmi_edm_dsm_loss_fwd")
+    return xs, mse
+
+
+def edm_dsm_loss_bwd(g_mse, g_xs, model_out, x_start, noise, sigma, weight_schedule, sigma_data=0.5, sigma_min=0.002,
+                     distillation=False, out=None):
+    """-> d(model_out) of the DSM terms for the device upstream gradients g_mse / g_xs [N] (either may be None)."""
+    _dsm_operands(x_start, sigma, same=(model_out, noise, out), per_sample=(g_mse, g_xs))
+    N = x_start.shape[0]
+    d = torch.empty_like(model_out) if out is None else out
+    check(load().dxmi_edm_dsm_loss_bwd(_ptr(g_mse), _ptr(g_xs), _ptr(model_out), _ptr(x_start), _ptr(noise), _ptr(sigma), _ptr(d), N,
+                                       x_start.numel() // N, float(sigma_data), float(sigma_min), int(bool(distillation)),
+                                       _dsm_schedule(weight_schedule), _stream()), "dxmi_edm_dsm_loss_bwd")
+    return d
+
+
+EMA_MAX_RATES = 4
+
+
+def ema_update(targets, sources, rates, found_inf=None):
+    """targets: one list of fp32 device tensors per rate (up to EMA_MAX_RATES), each parallel to `sources`;
+    targets[k][i] = rates[k] targets[k][i] + (1 - rates[k]) sources[i] in one launch series (dxmi_ema_update).
+    found_inf: device fp32 [1] flag: when it is non-zero the launches leave every target untouched."""
+    rates = [float(r) for r in rates]
+    K, n = len(rates), len(sources)
+    if not 1 <= K <= EMA_MAX_RATES or len(targets) != K or any(len(t) != n for t in targets):
+        raise _lib.DxmiError(f"ema_update: 1..{EMA_MAX_RATES} rates, one target list of {n} tensors per rate")
+    _need_f32_dense(sources, *targets)
+    for ts in targets:
+        for t, s in zip(ts, sources):
+            if t.numel() != s.numel():
+                raise _lib.DxmiError("ema_update: target and source sizes differ")
+    if found_inf is not None:
+        assert found_inf.is_cuda and found_inf.dtype == torch.float32
+    ema = _ptr_array([t for ts in targets for t in ts])
+    check(load().dxmi_ema_update(ema, _ptr_array(sources), _numel_array(sources), n, K, (ctypes.c_double * K)(*rates),
+                                 _ptr(found_inf), _stream()), "dxmi_ema_update")
+
+
 # dxmi_karras_stage modes and table columns (include/dxmi_hip.h)
 KARRAS_FIRST, KARRAS_PRED, KARRAS_HEUN_CORR, KARRAS_DPM_CORR, KARRAS_EULER, KARRAS_ANCESTRAL = range(6)
 KT_SIGMA, KT_CSKIP, KT_COUT, KT_DT, KT_SIGMA_UP, KT_CHURN, KT_SNOISE, KT_CIN, KT_T, KT_XSCALE, KT_CLIP = range(11)
@@ -1455,6 +1542,16 @@ def clip_grad_norm_(parameters, max_norm):
     if not grads:
         return None
     return gradnorm_clip(grads, max_norm)[0]
+
+
+def dropout_site_seed(base, n):
+    """32-bit seed of dropout site number `n` under the 64-bit `base` seed: a counter hash, so the nets' dropout draws nothing from
+    torch's generators (whose streams the trainers' parity tests depend on)."""
+    x = (int(base) * 0x9E3779B97F4A7C15 + int(n) * 0xD1B54A32D192ED03 + 0x8CB92BA72F3D8DD7) & 0xFFFFFFFFFFFFFFFF
+    x ^= x >> 32
+    x = (x * 0xD6E8FEB86659FD93) & 0xFFFFFFFFFFFFFFFF
+    x ^= x >> 32
+    return x & 0xFFFFFFFF
 
 
 def dropout(x, p, seed, out=None):

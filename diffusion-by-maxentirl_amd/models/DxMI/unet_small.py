@@ -163,12 +163,8 @@ class Model(nn.Module):
         """32-bit seed of the next dropout site: hash of (base seed, running call counter).  Deliberately NOT drawn from
         torch's CPU generator, whose stream the trainer's randperm parity depends on."""
         base = torch.initial_seed() if self.dropout_seed is None else self.dropout_seed
-        x = (base * 0x9E3779B97F4A7C15 + self._dropout_calls * 0xD1B54A32D192ED03 + 0x8CB92BA72F3D8DD7) & 0xFFFFFFFFFFFFFFFF
-        x ^= x >> 32
-        x = (x * 0xD6E8FEB86659FD93) & 0xFFFFFFFFFFFFFFFF
-        x ^= x >> 32
+        seed = ops.dropout_site_seed(base, self._dropout_calls)
         self._dropout_calls += 1
-        seed = x & 0xFFFFFFFF
         self.dropout_seeds_used.append(seed)
         return seed
 

@@ -4,7 +4,14 @@ Reference: models/cm/karras_diffusion.py — KarrasDenoiser.__init__/get_snr/get
 denoise (:337-351), karras_sample (:354-420), get_sigmas_karras (:423-429), get_ancestral_step (:437-444),
 sample_euler_ancestral / sample_heun / sample_euler / sample_dpm (:447-640), and the consistency-model samplers
 sample_onestep / stochastic_iterative_sampler (:644-683) with the zero-shot editing loops iterative_colorization /
-iterative_inpainting / iterative_superres (:722-951).  The consistency-distillation losses and progdist stay out of scope.
+iterative_inpainting / iterative_superres (:722-951), and the denoising score-matching loss training_losses with
+get_weightings (:18-31, :82-106) that models.cm.train_util.TrainLoop trains the U-Net with.  The consistency-distillation
+losses and progdist stay out of scope.
+
+training_losses on the HIP UNetModel (bare, or behind a wrapper that holds it as `.module`) is ONE autograd node: the network
+input of the batch in one launch (dxmi_edm_dsm_prep), the U-Net forward of models.cm.unet_train, the per-sample terms in one
+launch (dxmi_edm_dsm_loss_fwd); its backward forms d(model output) in one launch (dxmi_edm_dsm_loss_bwd) and runs the U-Net
+backward.  x_t is never stored.  Any other callable model gets the reference's expressions in torch.
 
 denoise() keeps the reference signature for any callable `model`; neither sampler calls it on the hot path.
 OpenAIDiffusion (the DxMI few-step sampler) uses the fused dxmi_edm_precond / dxmi_edm_step_fwd kernels.
@@ -23,7 +30,64 @@ import weakref
 import numpy as np
 import torch
 
-from .nn import append_dims, append_zero
+from .nn import append_dims, append_zero, mean_flat
+
+
+def get_weightings(weight_schedule, snrs, sigma_data):
+    if weight_schedule == "snr":
+        weightings = snrs
+    elif weight_schedule == "snr+1":
+        weightings = snrs + 1
+    elif weight_schedule == "karras":
+        weightings = snrs + 1.0 / sigma_data ** 2
+    elif weight_schedule == "truncated-snr":
+        weightings = torch.clamp(snrs, min=1.0)
+    elif weight_schedule == "uniform":
+        weightings = torch.ones_like(snrs)
+    else:
+        raise NotImplementedError()
+    return weightings
+
+
+def _hip_unet(model):
+    """The HIP UNetModel behind `model` (itself, or a wrapper's `.module`), else None."""
+    from .unet import UNetModel
+    net = model.module if hasattr(model, "module") else model
+    return net if isinstance(net, UNetModel) else None
+
+
+class _DSMLossFn(torch.autograd.Function):
+    """prep -> U-Net forward (models.cm.unet_train) -> per-sample terms, as one node; outputs (xs_mse, mse)."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, x_start, noise, sigmas, y, *params):
+        import types
+        from dxmi_hip import ops
+        from .unet_train import _EDMUNetFn
+        x_in, t = ops.edm_dsm_prep(x_start, noise, sigmas, diffusion.sigma_data)
+        sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
+        F = _EDMUNetFn.forward(sub, net, x_in, t, y, *params)
+        kw = dict(weight_schedule=diffusion.weight_schedule, sigma_data=diffusion.sigma_data, sigma_min=diffusion.sigma_min,
+                  distillation=diffusion.distillation)
+        xs, mse = ops.edm_dsm_loss_fwd(F, x_start, noise, sigmas, **kw)
+        ctx.sub, ctx.F, ctx.kw, ctx.ops = sub, F, kw, (x_start, noise, sigmas)
+        ctx.set_materialize_grads(False)
+        return xs, mse
+
+    @staticmethod
+    def backward(ctx, g_xs, g_mse):
+        from dxmi_hip import ops
+        from .unet_train import _EDMUNetFn
+        n_params = len(ctx.needs_input_grad) - 6
+        if g_xs is None and g_mse is None:
+            return (None,) * (6 + n_params)
+        x_start, noise, sigmas = ctx.ops
+        cont = lambda g: None if g is None else g.detach().float().contiguous()
+        dF = ops.edm_dsm_loss_bwd(cont(g_mse), cont(g_xs), ctx.F, x_start, noise, sigmas, **ctx.kw)
+        ctx.F = None
+        grads = _EDMUNetFn.backward(ctx.sub, dF)
+        ctx.sub = None
+        return (None,) * 6 + tuple(grads[4:])
 
 
 class KarrasDenoiser:
@@ -51,6 +115,61 @@ class KarrasDenoiser:
         c_out = (sigma - self.sigma_min) * self.sigma_data / (sigma ** 2 + self.sigma_data ** 2) ** 0.5
         c_in = 1 / (sigma ** 2 + self.sigma_data ** 2) ** 0.5
         return c_skip, c_out, c_in
+
+    def training_losses(self, model, x_start, sigmas, model_kwargs=None, noise=None):
+        """DSM terms per sample (reference :82-106): xs_mse = mean_flat((denoised - x_start)^2), mse = the same weighted by
+        get_weightings(weight_schedule, sigma^-2, sigma_data), loss = mse."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        net = _hip_unet(model)
+        if net is not None and x_start.is_cuda:
+            return self._training_losses_hip(net, x_start, sigmas, model_kwargs, noise)
+        terms = {}
+        dims = x_start.ndim
+        x_t = x_start + noise * append_dims(sigmas, dims)
+        model_output, denoised = self.denoise(model, x_t, sigmas, **model_kwargs)
+        snrs = self.get_snr(sigmas)
+        weights = append_dims(get_weightings(self.weight_schedule, snrs, self.sigma_data), dims)
+        terms["xs_mse"] = mean_flat((denoised - x_start) ** 2)
+        terms["mse"] = mean_flat(weights * (denoised - x_start) ** 2)
+        terms["loss"] = terms["mse"]
+        return terms
+
+    def _training_losses_hip(self, net, x_start, sigmas, model_kwargs, noise):
+        from dxmi_hip import graph as _graph
+        from dxmi_hip import ops
+        if x_start.requires_grad or sigmas.requires_grad or noise.requires_grad:
+            raise NotImplementedError("training_losses on the HIP U-Net differentiates the network parameters only: x_start, "
+                                      "noise and sigmas must not require grad")
+        if _graph.current() is not None:
+            raise NotImplementedError("training_losses: capturing the DSM step into a hipGraph is not supported")
+        extra = set(model_kwargs) - {"y"}
+        if extra:
+            raise NotImplementedError(f"training_losses on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
+        y = model_kwargs.get("y")
+        if (y is not None) != (net.num_classes is not None):
+            raise ValueError("must specify y if and only if the model is class-conditional")
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        x_start, noise, sigmas = f32(x_start), f32(noise), f32(sigmas).reshape(-1)
+        if noise.shape != x_start.shape or sigmas.numel() != x_start.shape[0]:
+            raise ValueError(f"training_losses: noise {tuple(noise.shape)} must match x_start {tuple(x_start.shape)} and sigmas "
+                             f"({sigmas.numel()}) hold one level per sample")
+        if torch.is_grad_enabled():
+            xs, mse = _DSMLossFn.apply(self, net, x_start, noise, sigmas, y, *ops.fast_parameters(net))
+        elif net.training and net.dropout > 0:      # dropout is part of the loss in train mode: the training forward applies it
+            import types
+            from .unet_train import _EDMUNetFn
+            sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
+            F = _EDMUNetFn.forward(sub, net, *ops.edm_dsm_prep(x_start, noise, sigmas, self.sigma_data), y, *ops.fast_parameters(net))
+            xs, mse = ops.edm_dsm_loss_fwd(F, x_start, noise, sigmas, self.weight_schedule, self.sigma_data, self.sigma_min,
+                                           self.distillation)
+        else:
+            F = net.forward_inference(*ops.edm_dsm_prep(x_start, noise, sigmas, self.sigma_data), y)
+            xs, mse = ops.edm_dsm_loss_fwd(F, x_start, noise, sigmas, self.weight_schedule, self.sigma_data, self.sigma_min,
+                                           self.distillation)
+        return {"xs_mse": xs, "mse": mse, "loss": mse}
 
     def denoise(self, model, x_t, sigmas, **model_kwargs):
         scal = self.get_scalings_for_boundary_condition(sigmas) if self.distillation else self.get_scalings(sigmas)

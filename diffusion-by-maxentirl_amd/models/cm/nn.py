@@ -49,9 +49,30 @@ def append_zero(x):
     return torch.cat([x, x.new_zeros([1])])
 
 
+def _ema_device_lists(targets, sources):
+    ts = [t for ts_ in targets for t in ts_]
+    return bool(sources) and all(len(t) == len(sources) for t in targets) and all(
+        t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts + sources)
+
+
 def update_ema(target_params, source_params, rate=0.99):
-    for targ, src in zip(target_params, source_params):
+    """Reference :57-67.  Lists of CUDA fp32 tensors take one dxmi_ema_update launch series; anything else the reference's loop."""
+    targets, sources = list(target_params), list(source_params)
+    if _ema_device_lists([targets], sources):
+        update_ema_rates([targets], sources, [rate])
+        return
+    for targ, src in zip(targets, sources):
         targ.detach().mul_(rate).add_(src, alpha=1 - rate)
+
+
+def update_ema_rates(targets_per_rate, source_params, rates, found_inf=None):
+    """update_ema for several rates over the same sources, the source read once for all of them (dxmi_ema_update, up to
+    ops.EMA_MAX_RATES rates per launch series).  found_inf: device fp32 flag; non-zero leaves every EMA untouched."""
+    sources = [s.detach() for s in source_params]
+    targets = [[t.detach() for t in ts] for ts in targets_per_rate]
+    for k in range(0, len(rates), ops.EMA_MAX_RATES):
+        ops.ema_update(targets[k:k + ops.EMA_MAX_RATES], sources, rates[k:k + ops.EMA_MAX_RATES], found_inf=found_inf)
+    torch.autograd.graph.increment_version([t for ts in targets for t in ts])      # written through raw pointers
 
 
 def timestep_embedding(timesteps, dim, max_period=10000):

@@ -1,0 +1,210 @@
+"""Denoising score-matching training of the EDM U-Net (`models.cm.train_util.TrainLoop`; reference: models/cm/train_util.py:29-264).
+
+Same keyword arguments and methods as the reference (run_loop, run_step, forward_backward with microbatches, _update_ema,
+_anneal_lr, save; checkpoints model%06d.pt, ema_{rate}_%06d.pt, opt%06d.pt next to each other, resumed from the model file's
+step).  What differs:
+  * the loss is KarrasDenoiser.training_losses on the HIP U-Net (one autograd node around the network, models/cm/karras_diffusion.py);
+  * the optimiser is dxmi_hip.optim.RAdam behind MixedPrecisionTrainer, and gradients are exchanged by the trainer's
+    dxmi_hip.dist.FlatGradSync in optimize() (the reference wraps the model in DDP);
+  * every EMA rate is updated by one dxmi_ema_update launch series that reads the master weights once (nn.update_ema_rates);
+  * `schedule_sampler` is required (the reference's default UniformSampler needs a num_timesteps KarrasDenoiser lacks: use
+    models.cm.resample.LogNormalSampler), and `log_dir` replaces blobfile's get_blob_logdir();
+  * the logged terms are summed on the device and read back once per `log_interval` steps (dumpkvs), as their means.
+The reference's bookkeeping is kept as it is: the step counter advances, and the EMA moves, only on steps the optimiser took
+(an fp16 overflow skips both); after a resume `step` starts at the resumed step and _anneal_lr / save add resume_step to it.
+"""
+import json
+import os
+
+import torch
+import torch.distributed as dist
+
+from dxmi_hip.dist import broadcast_parameters, is_distributed
+from dxmi_hip.optim import RAdam
+
+from .fp16_util import MixedPrecisionTrainer
+from .nn import update_ema, update_ema_rates
+
+INITIAL_LOG_LOSS_SCALE = 20.0
+
+
+def _rank():
+    return dist.get_rank() if is_distributed() else 0
+
+
+def _world():
+    return dist.get_world_size() if is_distributed() else 1
+
+
+class TrainLoop:
+    def __init__(self, *, model, diffusion, data, batch_size, microbatch, lr, ema_rate, log_interval, save_interval,
+                 resume_checkpoint, use_fp16=False, fp16_scale_growth=1e-3, schedule_sampler=None, weight_decay=0.0,
+                 lr_anneal_steps=0, log_dir=None):
+        if schedule_sampler is None:
+            raise ValueError("TrainLoop: schedule_sampler is required (e.g. models.cm.resample.LogNormalSampler())")
+        self.model, self.diffusion, self.data = model, diffusion, data
+        self.batch_size = batch_size
+        self.microbatch = microbatch if microbatch > 0 else batch_size
+        self.lr = lr
+        self.ema_rate = [ema_rate] if isinstance(ema_rate, float) else [float(x) for x in str(ema_rate).split(",")]
+        self.log_interval, self.save_interval = log_interval, save_interval
+        self.resume_checkpoint = resume_checkpoint
+        self.use_fp16, self.fp16_scale_growth = use_fp16, fp16_scale_growth
+        self.schedule_sampler = schedule_sampler
+        self.weight_decay, self.lr_anneal_steps = weight_decay, lr_anneal_steps
+        self.log_dir = log_dir or os.getcwd()
+        self.device = next(model.parameters()).device
+
+        self.step = 0
+        self.resume_step = 0
+        self.global_batch = self.batch_size * _world()
+
+        self._load_and_sync_parameters()
+        self.mp_trainer = MixedPrecisionTrainer(model=self.model, use_fp16=self.use_fp16, fp16_scale_growth=fp16_scale_growth)
+        self.opt = RAdam(self.mp_trainer.master_params, lr=self.lr, weight_decay=self.weight_decay)
+        if self.resume_step:
+            self._load_optimizer_state()
+            self.ema_params = [self._load_ema_parameters(rate) for rate in self.ema_rate]
+        else:
+            self.ema_params = [[p.detach().clone() for p in self.mp_trainer.master_params] for _ in self.ema_rate]
+        self.ddp_model = self.model
+        self.step = self.resume_step
+        self._log_sums, self._log_count, self.logged = {}, 0, []
+
+    # ------------------------------------------------------------------ checkpoints
+    def _load_and_sync_parameters(self):
+        if self.resume_checkpoint:
+            self.resume_step = parse_resume_step_from_filename(self.resume_checkpoint)
+            self.model.load_state_dict(torch.load(self.resume_checkpoint, map_location=self.device))
+        broadcast_parameters(self.model)
+
+    def _load_ema_parameters(self, rate):
+        ema_params = [p.detach().clone() for p in self.mp_trainer.master_params]
+        ema_checkpoint = find_ema_checkpoint(self.resume_checkpoint, self.resume_step, rate)
+        if ema_checkpoint:
+            state_dict = torch.load(ema_checkpoint, map_location=self.device)
+            ema_params = [p.detach().clone().contiguous() for p in self.mp_trainer.state_dict_to_master_params(state_dict)]
+        if is_distributed():
+            with torch.no_grad():
+                for p in ema_params:
+                    dist.broadcast(p, 0)
+        return ema_params
+
+    def _load_optimizer_state(self):
+        opt_checkpoint = os.path.join(os.path.dirname(self.resume_checkpoint), f"opt{self.resume_step:06}.pt")
+        if os.path.exists(opt_checkpoint):
+            self.opt.load_state_dict(torch.load(opt_checkpoint, map_location=self.device))
+
+    def save(self):
+        def save_checkpoint(rate, params):
+            state_dict = self.mp_trainer.master_params_to_state_dict(params)
+            if _rank() == 0:
+                name = f"model{(self.step + self.resume_step):06d}.pt" if not rate else f"ema_{rate}_{(self.step + self.resume_step):06d}.pt"
+                torch.save({k: v.detach().clone() for k, v in state_dict.items()}, os.path.join(self.log_dir, name))
+
+        os.makedirs(self.log_dir, exist_ok=True)
+        for rate, params in zip(self.ema_rate, self.ema_params):
+            save_checkpoint(rate, params)
+        if _rank() == 0:
+            torch.save(self.opt.state_dict(), os.path.join(self.log_dir, f"opt{(self.step + self.resume_step):06d}.pt"))
+        save_checkpoint(0, self.mp_trainer.master_params)     # last: a restart never finds a model without its opt / EMA files
+        if is_distributed():
+            dist.barrier()
+
+    # ------------------------------------------------------------------ loop
+    def run_loop(self):
+        while not self.lr_anneal_steps or self.step < self.lr_anneal_steps:
+            batch, cond = next(self.data)
+            self.run_step(batch, cond)
+            if self.step % self.log_interval == 0:
+                self.dumpkvs()
+            if self.step % self.save_interval == 0:
+                self.save()
+                if os.environ.get("DIFFUSION_TRAINING_TEST", "") and self.step > 0:
+                    return
+        if (self.step - 1) % self.save_interval != 0:
+            self.save()
+
+    def run_step(self, batch, cond):
+        self.forward_backward(batch, cond)
+        took_step = self.mp_trainer.optimize(self.opt)
+        if took_step:
+            self.step += 1
+            self._update_ema()
+        self._anneal_lr()
+        self.log_step()
+        return took_step
+
+    def forward_backward(self, batch, cond):
+        self.mp_trainer.zero_grad()
+        for i in range(0, batch.shape[0], self.microbatch):
+            micro = batch[i:i + self.microbatch].to(self.device)
+            micro_cond = {k: v[i:i + self.microbatch].to(self.device) for k, v in cond.items()}
+            sigmas, weights = self.schedule_sampler.sample(micro.shape[0], self.device)
+            losses = self.diffusion.training_losses(self.ddp_model, micro, sigmas, model_kwargs=micro_cond)
+            loss = (losses["loss"] * weights).mean()
+            self._log_loss_dict({k: v * weights for k, v in losses.items()})
+            self.mp_trainer.backward(loss)
+
+    def _update_ema(self):
+        masters = self.mp_trainer.master_params
+        if all(p.is_cuda for p in masters):
+            update_ema_rates(self.ema_params, masters, self.ema_rate)
+            return
+        for rate, params in zip(self.ema_rate, self.ema_params):
+            update_ema(params, masters, rate=rate)
+
+    def _anneal_lr(self):
+        if not self.lr_anneal_steps:
+            return
+        frac_done = (self.step + self.resume_step) / self.lr_anneal_steps
+        lr = self.lr * (1 - frac_done)
+        for param_group in self.opt.param_groups:
+            param_group["lr"] = lr
+
+    # ------------------------------------------------------------------ logging
+    def _log_loss_dict(self, losses):
+        """Device sums of every term's batch mean (no host sync); dumpkvs() reads them."""
+        for k, v in losses.items():
+            m = v.detach().float().mean()
+            self._log_sums[k] = self._log_sums[k] + m if k in self._log_sums else m
+        self._log_count += 1
+
+    def log_step(self):
+        self._kv = {"step": self.step + self.resume_step, "samples": (self.step + self.resume_step + 1) * self.global_batch}
+
+    def dumpkvs(self):
+        """Means of the logged terms since the last dump: ONE device-to-host read.  Appended to self.logged, and written as a
+        JSON line to log_dir/progress.jsonl on rank 0."""
+        row = dict(getattr(self, "_kv", {}))
+        if self._log_count:
+            keys = sorted(self._log_sums)
+            vals = torch.stack([self._log_sums[k] for k in keys]).tolist()
+            row.update({k: v / self._log_count for k, v in zip(keys, vals)})
+        row.update({k: v for k, v in self.mp_trainer.log.items()})
+        self._log_sums, self._log_count = {}, 0
+        self.logged.append(row)
+        if _rank() == 0:
+            os.makedirs(self.log_dir, exist_ok=True)
+            with open(os.path.join(self.log_dir, "progress.jsonl"), "a") as f:
+                f.write(json.dumps(row) + "\n")
+        return row
+
+
+def parse_resume_step_from_filename(filename):
+    """Parse filenames of the form path/to/modelNNNNNN.pt, where NNNNNN is the checkpoint's number of steps."""
+    split = os.path.basename(filename).split("model")
+    if len(split) < 2:
+        return 0
+    split1 = split[-1].split(".")[0]
+    try:
+        return int(split1)
+    except ValueError:
+        return 0
+
+
+def find_ema_checkpoint(main_checkpoint, step, rate):
+    if main_checkpoint is None:
+        return None
+    path = os.path.join(os.path.dirname(main_checkpoint), f"ema_{rate}_{step:06d}.pt")
+    return path if os.path.exists(path) else None

@@ -12,7 +12,10 @@ package) plus a tape of saved NHWC bf16 activations; backward() walks the tape i
   attention             = batched MFMA GEMMs + softmax backward (dxmi_bgemm_bf16), any head count;
   mean pool / nearest x2 = each other's transposes (dxmi_upsample2x, dxmi_pool_act);
   time_embed, label_emb, emb_layers = tiny dense layers, re-evaluated and differentiated with torch fp32 matmuls.
-Dropout must be 0 (every DxMI EDM config sets dropout: 0.0).  Parameter gradients come back in net.parameters() order.
+Dropout (ResBlock out_layers: norm, SiLU, Dropout, conv; models/cm/unet.py) runs in train mode as the counter-hash kernel
+dxmi_dropout_bf16 on the conv2 input: one seed per ResBlock per forward, kept on the tape with p, and the backward applies the same
+(seed, p) to the gradient (no mask is stored).  With dropout 0, or in eval mode, nothing of it runs.  Parameter gradients come back in
+net.parameters() order.
 """
 import math
 import os
@@ -90,12 +93,26 @@ def _pool_t(g):
     return out
 
 
+def _next_dropout_seed(net):
+    """32-bit seed of the next dropout site (ops.dropout_site_seed of the base seed and a running site counter).  The base is
+    `net.dropout_seed` if set, else torch.initial_seed().  The counter lives on the net and is not part of a checkpoint: a run
+    resumed with dropout > 0 draws the masks of a fresh net again, so it is not bit-exact with the run it continues."""
+    base = torch.initial_seed() if getattr(net, "dropout_seed", None) is None else int(net.dropout_seed)
+    n = net.__dict__.get("_dropout_calls", 0)
+    net.__dict__["_dropout_calls"] = n + 1
+    return ops.dropout_site_seed(base, n)
+
+
 class _EDMUNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, x, timesteps, y, *params):
         from .unet import AttentionBlock, Downsample, ResBlock, Upsample
-        if net.training and net.dropout:
-            raise NotImplementedError("UNetModel HIP training path: dropout > 0 is not implemented (DxMI configs use 0.0)")
+        p_drop = float(net.dropout) if net.training else 0.0
+        if p_drop > 0:
+            from dxmi_hip import graph as _graph
+            if _graph.current() is not None:
+                raise NotImplementedError("UNetModel HIP training path: dropout > 0 inside a captured step is not implemented")
+        net.dropout_seeds_used = []
         pk = net.packed()
         x = x.contiguous().float()
         sinus = ops.timestep_embedding(timesteps, net.model_channels, order=1)
@@ -135,10 +152,15 @@ class _EDMUNetFn(torch.autograd.Function):
             else:
                 h, sh = conv_s(a1p, pk[id(b), "conv1"], bias=conv1.bias, upsample=b.up, addvec=e)
                 a2, s2 = gn_fwd(gn2, h, sh, silu=True)
+            drop = None
+            if p_drop > 0:       # nn.Dropout of out_layers: the backward regenerates the mask from (seed, p)
+                drop = (_next_dropout_seed(net), p_drop)
+                net.dropout_seeds_used.append(drop[0])
+                a2 = ops.dropout(a2, p_drop, drop[0])
             if (id(b), "skip") in pk:
                 xs = ops.conv2d(x0, pk[id(b), "skip"], in1=x1, bias=b.skip_connection.bias)
             out, so = conv_s(a2, pk[id(b), "conv2"], bias=conv2.bias, residual=xs)
-            tape.append(("res", b, x0, x1, a1p, h, a2, s1, s2))
+            tape.append(("res", b, x0, x1, a1p, h, a2, s1, s2, drop))
             return out, (so if so is not None else stats_of(out))
 
         def attn(m, xa, sx):
@@ -233,10 +255,12 @@ class _EDMUNetFn(torch.autograd.Function):
         gskip = {}
 
         def res_bwd(entry, g):
-            _, b, x0, x1, a1p, h, a2, s1, s2 = entry
+            _, b, x0, x1, a1p, h, a2, s1, s2, drop = entry
             gn1, conv1, gn2, conv2 = b.in_layers[0], b.in_layers[2], b.out_layers[0], b.out_layers[3]
             conv_wb(conv2, a2, g, 3)
             d_a2 = ops.conv2d(g, pkt[id(b), "conv2"])
+            if drop is not None:
+                d_a2 = ops.dropout(d_a2, drop[1], drop[0], out=d_a2)
             off, eo = pk[id(b), "eoff"], b.emb_layers[1].out_features
             if b.use_scale_shift_norm:
                 d_h, _, d_ss = gn_bwd(gn2, h, d_a2, scale_shift=emb_all[:, off:off + eo], fwd_stats=s2)

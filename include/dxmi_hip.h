@@ -556,6 +556,38 @@ int dxmi_dropout_bf16(const void* x, void* y, int64_t n, float p, uint32_t seed,
  * before every replay). */
 int dxmi_dropout_bf16_dev(const void* x, void* y, int64_t n, float p, const uint32_t* seed, void* stream);
 
+/* Denoising score-matching loss of the EDM teacher (KarrasDenoiser.training_losses, models/cm/karras_diffusion.py:82-106, with
+ * get_weightings :18-31 and denoise :337-351), fp32 NCHW [N, CHW] tensors (CHW a multiple of 4, 16-byte aligned), sigma [N]:
+ * dxmi_edm_dsm_prep:     x_in = c_in(s) (x_start + noise s), t[n] = 250 ln(s + 1e-44) — the network input; x_t is not stored.
+ * dxmi_edm_dsm_loss_fwd: x_t recomputed, denoised = c_out F + c_skip x_t (boundary-condition scalings when distillation != 0),
+ *                        xs_mse[n] = mean((denoised - x_start)^2), mse[n] = mean(w(s) (denoised - x_start)^2), w = the weight
+ *                        schedule below; per-sample sums in a fixed order (bitwise reproducible).
+ * dxmi_edm_dsm_loss_bwd: d_model_out = (((g_mse/D) w) 2e + (g_xs/D) 2e) c_out, e = denoised - x_start: autograd's nodes in its
+ *                        order; g_mse / g_xs are DEVICE [N] upstream gradients, either may be NULL (that term not differentiated).
+ * Every fp32 operation in the reference's order, one rounding per torch op. */
+#define DXMI_DSM_W_SNR        0   /* snrs = sigma^-2 */
+#define DXMI_DSM_W_SNR_P1     1   /* snrs + 1 */
+#define DXMI_DSM_W_KARRAS     2   /* snrs + 1 / sigma_data^2 */
+#define DXMI_DSM_W_TRUNC_SNR  3   /* clamp(snrs, min=1) */
+#define DXMI_DSM_W_UNIFORM    4   /* 1 */
+int dxmi_edm_dsm_prep(const float* x_start, const float* noise, const float* sigma, float* x_in, float* t_out, int32_t N,
+                      int32_t CHW, float sigma_data, void* stream);
+int dxmi_edm_dsm_loss_fwd(const float* model_out, const float* x_start, const float* noise, const float* sigma, float* xs_mse,
+                          float* mse, int32_t N, int32_t CHW, float sigma_data, float sigma_min, int32_t distillation,
+                          int32_t weight_schedule, void* stream);
+int dxmi_edm_dsm_loss_bwd(const float* g_mse, const float* g_xs, const float* model_out, const float* x_start, const float* noise,
+                          const float* sigma, float* d_model_out, int32_t N, int32_t CHW, float sigma_data, float sigma_min,
+                          int32_t distillation, int32_t weight_schedule, void* stream);
+
+/* update_ema (models/cm/nn.py:57-67) for up to DXMI_EMA_MAX_RATES rates at once (TrainLoop._update_ema, train_util.py:190-193):
+ * ema[k * count + i] = rates[k] ema[k * count + i] + (1 - rates[k]) src[i] over fp32 DEVICE tensors of numel[i] elements, as
+ * torch's mul_(rate).add_(src, alpha=1-rate) (rate and 1-rate formed in double, rounded to fp32 once; the add is one fused
+ * multiply-add, as ATen's).  The source is read once for all rates.  found_inf: DEVICE fp32 flag or NULL; when it is non-zero the
+ * launch leaves every EMA tensor untouched (the step was skipped on overflow), with no host sync. */
+#define DXMI_EMA_MAX_RATES 4
+int dxmi_ema_update(void* const* ema, const void* const* src, const int64_t* numel, int32_t count, int32_t n_rates,
+                    const double* rates, const float* found_inf, void* stream);
+
 /* TD step of DxMI_Trainer.update_f_v on the replay ring, data side in one launch (reference trainer.py:271-300, :163-169): rows
  * `state_rows[b]` (and `next_rows[b]`, or the dense re-drawn next states of value_resample) of the ring's fp32 [n_src_rows, CHW]
  * trajectory block are gathered into out_state / out_next — the two halves of the batch [next_state | state] the value net
