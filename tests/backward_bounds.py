@@ -189,3 +189,151 @@ def groupnorm_bwd_ref(x, dy, gamma, beta, groups, eps, silu, scale_shift=None, a
             G1 = (dyy * yn.abs() * kappa.repeat_interleave(C // groups, 1).reshape(N, C, 1, 1)).sum((2, 3))
             A_ss = torch.cat([G1, G0], 1)
     return (dx, g.grad, b.grad, ss.grad if ss is not None else None), (A_dx, A_dg, A_db, A_ss)
+
+
+# ------------------------------------------------------------------------------------------ ops outside the original ten
+def silu_bwd_ref(pre, g):
+    """g * s (1 + x (1 - s)), s = sigmoid(x), in fp64, and the magnitude A of its fp32 bound |got - ref| <= 16 u32 A.
+    ops.silu_bwd evaluates the expression in fp32: s to <= 4 u32 (exp, add, divide), 1 - s to 5 u32 absolute, x (1 - s) to
+    6 u32 |x|, 1 + x (1 - s) to 7 u32 (1 + |x|), its product with s to 12 u32 (1 + |x|) (s <= 1, |1 + x (1 - s)| <= 1 + |x|),
+    and the product with g adds one rounding: 13 u32 |g| (1 + |x|), rounded up to c = 16 with A = |g| (1 + |x|)."""
+    x, gd = pre.double(), g.double()
+    s = torch.sigmoid(x)
+    return gd * s * (1 + x * (1 - s)), gd.abs() * (1 + x.abs())
+
+
+def dropout_keep(shape_nhwc, p, seed, device):
+    """The counter hash of dxmi_dropout_bf16 restated in torch int64 on `device`: keep(i) = (mix32(i ^ seed) >> 8) >= p 2^24
+    over the NHWC linear index i (oracle.unet_small.dropout_keep_mask states the same hash in numpy; the two are compared on
+    the host by test_backward_bounds.py).  -> bool tensor of shape_nhwc."""
+    n = math.prod(shape_nhwc)
+    m = 0xFFFFFFFF
+    h = torch.arange(n, dtype=torch.int64, device=device) ^ (int(seed) & m)
+    h = h ^ (h >> 16)
+    h = (h * 0x7feb352d) & m
+    h = h ^ (h >> 15)
+    h = (h * 0x846ca68b) & m
+    h = h ^ (h >> 16)
+    return ((h >> 8) >= int(float(p) * 16777216.0)).reshape(shape_nhwc)
+
+
+def dropout_ref(x, p, seed):
+    """bf16(x / (1 - p)) computed in fp64 where kept, 0 elsewhere.  The kernel multiplies by the fp32 scalar 1 / (1 - p); where
+    the fp64 quotient lies within 4 u32 of a bf16 rounding midpoint either neighbour is accepted (mask `tie`)."""
+    keep = dropout_keep(tuple(x.shape), p, seed, x.device)
+    q = x.double() / (1.0 - float(p))
+    b = q.to(torch.bfloat16)
+    e = torch.floor(torch.log2(b.double().abs().clamp_min(1e-38)))
+    tie = ((q - b.double()).abs() - 2.0 ** (e - 8)).abs() <= 4 * U32 * q.abs() + 1e-300
+    return keep, torch.where(keep, b, torch.zeros_like(b)), tie & keep
+
+
+def value_head_bwd_ref(feat, w, dy):
+    """fp64 autograd through y[n] = sum_c w[c] sum_hw relu(feat[n, hw, c]) (the expressions of
+    test_hip_backward.py::test_colsum_and_pool_bwd_and_head_bwd: F.relu, whose derivative at exactly 0 is 0 as the kernel's
+    `v > 0` is; clamp_min's is 1 there, and a randn draw that is exactly 0 does occur in these batches)
+    -> (dfeat, s = the relu-sum features, sum |relu| for s)."""
+    f = feat.double().clone().requires_grad_(True)
+    s = torch.relu(f).sum((1, 2))
+    ((s @ w.double()) * dy.double()).sum().backward()
+    return f.grad, s.detach(), feat.double().clamp_min(0).sum((1, 2))
+
+
+def value_head_pgrad_ref(s, w, b, dy, ow):
+    """fp64 autograd through y = (s . w + b) ow + ob -> [C + 3] = d w | d b | d ow | d ob (zeros for the last two without
+    out_scale), and the sums of absolute terms A of the same layout.  The kernel's sums over the N images have depth N, the
+    dot product s[n] . w depth C: c = N + C + 8 covers both and the scalar products."""
+    sd, dyd = s.double(), dy.double()
+    wd = w.double().clone().requires_grad_(True)
+    bd = b.double().clone().requires_grad_(True)
+    owd = (ow.double().reshape(()) if ow is not None else torch.ones((), dtype=torch.float64, device=s.device)).clone().requires_grad_(True)
+    obd = torch.zeros((), dtype=torch.float64, device=s.device, requires_grad=True)
+    y = (sd @ wd + bd) * owd + obd
+    (y * dyd).sum().backward()
+    z = torch.zeros(1, dtype=torch.float64, device=s.device)
+    ref = torch.cat([wd.grad, bd.grad.reshape(1), owd.grad.reshape(1) if ow is not None else z, obd.grad.reshape(1) if ow is not None else z])
+    sc = owd.detach().abs()
+    pre = sd.abs() @ wd.detach().abs() + bd.detach().abs()
+    A = torch.cat([(dyd.abs()[:, None] * sc * sd.abs()).sum(0), (dyd.abs() * sc).sum().reshape(1),
+                   (dyd.abs() * pre).sum().reshape(1) if ow is not None else z, dyd.abs().sum().reshape(1) if ow is not None else z])
+    return ref, A
+
+
+def td_loss_ref(v, cost, extra):
+    """mse(v[B:], v[:B] + extra) in fp64 under autograd -> (d loss / d v [2B], logs [3], A_grad, A_logs).  The kernel's three
+    means are sums of depth B (any order) of terms evaluated with <= 4 roundings: c = B + 8."""
+    B = cost.numel()
+    vd = v.double().clone().requires_grad_(True)
+    ex = extra.double() if extra is not None else 0.0
+    target = (vd[:B] + ex).detach()
+    d = vd[B:] - target
+    loss = (d * d).mean()
+    loss.backward()
+    logs = torch.stack([loss.detach(), vd[B:].detach().mean(), cost.double().mean()])
+    mag = vd[B:].detach().abs() + vd[:B].detach().abs() + (extra.double().abs() if extra is not None else 0.0)
+    A_grad = torch.cat([torch.zeros(B, dtype=torch.float64, device=v.device), 2 * mag / B])
+    A_logs = torch.stack([(mag * mag).mean(), vd[B:].detach().abs().mean(), cost.double().abs().mean()])
+    return vd.grad, logs, A_grad, A_logs
+
+
+def dsm_loss_bwd_ref(e, Me, c_out, gm, gx, w):
+    """d(model_out) = 2 e a c_out of the DSM terms, a = g_mse w / CHW + g_xs / CHW per sample (either gradient may be None), and
+    the product of the factors' absolute terms: fl(e) carries 16 u32 Me (forward_bounds.dsm_error_terms), a and c_out <= 8 u32
+    each, two products: |got - ref| <= 16 u32 A covers them only together with the factor 2 kept in A = 2 Me Ma |c_out|."""
+    CHW = e.shape[1]
+    z = torch.zeros(e.shape[0], 1, dtype=torch.float64, device=e.device)
+    a = (gm.double()[:, None] / CHW * w[:, None] if gm is not None else z) + (gx.double()[:, None] / CHW if gx is not None else z)
+    Ma = (gm.double().abs()[:, None] / CHW * w[:, None] if gm is not None else z) + (gx.double().abs()[:, None] / CHW if gx is not None else z)
+    return 2 * e * a * c_out, 2 * Me * Ma * c_out.abs()
+
+
+def var_step_bwd_ref(g_next, g_mean, g_control, g_logp, z, cm, sg):
+    """Gradients of the VAR transition w.r.t. eps and sigma by fp64 autograd through the expressions of
+    test_hip_round5_kernels.py::test_var_and_edm_step_backward_vs_torch_autograd (x' detached inside the log-prob), [N, CHW]
+    tensors and per-sample [N] scalars; any incoming gradient may be None.  -> (d_eps, d_sigma, A_eps, A_sigma).
+    d_eps = cm (g_x' + g_mean + g_control + g_logp z / (sg CHW)): four fp32 terms and a product, 8 u32 A_eps.
+    d_sigma = sum_CHW g_x' z + g_logp (mean z^2 - 1) / sg: two sums of depth CHW in any order, (CHW + 8) u32 A_sigma with
+    A_sigma = sum |g_x' z| + |g_logp| (mean z^2 + 1) / sg."""
+    import math
+    N, CHW = z.shape
+    e = lambda v: v[:, None]
+    zd, cmd = z.double(), cm.double()
+    eps = torch.zeros(N, CHW, dtype=torch.float64, device=z.device, requires_grad=True)      # linear in eps: any point serves
+    sgd = sg.double().clone().requires_grad_(True)
+    control = e(cmd) * eps
+    mean = control                                       # the xm x term has no gradient w.r.t. eps or sigma
+    xn = mean + e(sgd) * zd
+    lp = (-((xn.detach() - mean) ** 2) / (2 * e(sgd) ** 2) - torch.log(e(sgd)) - math.log(math.sqrt(2 * math.pi))).mean(1)
+    loss = 0
+    zero = torch.zeros(N, CHW, dtype=torch.float64, device=z.device)
+    for out, g in ((xn, g_next), (mean, g_mean), (control, g_control), (lp, g_logp)):
+        if g is not None:
+            loss = loss + (out * g.double()).sum()
+    loss.backward()
+    ab = lambda g: zero if g is None else g.double().abs()
+    gl = torch.zeros(N, dtype=torch.float64, device=z.device) if g_logp is None else g_logp.double().abs()
+    sd_ = sg.double()
+    A_eps = e(cmd.abs()) * (ab(g_next) + ab(g_mean) + ab(g_control) + e(gl / (sd_ * CHW)) * zd.abs())
+    A_sig = (ab(g_next) * zd.abs()).sum(1) + gl * ((zd ** 2).mean(1) + 1) / sd_
+    return eps.grad, sgd.grad, A_eps, A_sig
+
+
+def edm_step_bwd_ref(g_sample, g_mean, z, sigma, sdn, sd=0.5):
+    """Gradients of the EDM transition w.r.t. the network output F and sigma_up by fp64 autograd through
+    mu = x + (x - c_out F - c_skip x) / sigma (sigma_down - sigma), x' = mu + z sigma_up (x = 0: it has no part in either
+    gradient).  d_F = -(c_out (sigma_down - sigma) / sigma) (g_x' + g_mu): the coefficient carries <= 12 u32, one sum, one
+    product: 16 u32 A_F.  d_sigma_up = sum_CHW g_x' z: depth CHW, (CHW + 8) u32 sum |g_x' z|."""
+    N, CHW = z.shape
+    e = lambda v: v.double()[:, None]
+    s = sigma.double()
+    c_out = (s * sd / (s ** 2 + sd ** 2) ** 0.5)[:, None]
+    F = torch.zeros(N, CHW, dtype=torch.float64, device=z.device, requires_grad=True)
+    up = torch.ones(N, dtype=torch.float64, device=z.device, requires_grad=True)
+    mu = (0 - c_out * F) / e(sigma) * (e(sdn) - e(sigma))
+    smp = mu + z.double() * up[:, None]
+    zero = torch.zeros(N, CHW, dtype=torch.float64, device=z.device)
+    gs = zero if g_sample is None else g_sample.double()
+    gm = zero if g_mean is None else g_mean.double()
+    ((smp * gs).sum() + (mu * gm).sum()).backward()
+    coef = (c_out * (e(sdn) - e(sigma)) / e(sigma)).abs()
+    return F.grad, up.grad, coef * (gs.abs() + gm.abs()), (gs.abs() * z.double().abs()).sum(1)

@@ -198,8 +198,10 @@ def bf16_near_tie(v):
     return ((v - b).abs() - half).abs() <= 8 * U32 * v.abs() + 1e-300
 
 
-def linear_ref(x, W, bias, pre_act, post_act):
-    """fp64 reference of ops.linear and its element-wise bound: x fp32 [P, K], W fp32 [M, K] (bf16-rounded by the pack)."""
+def linear_ref(x, W, bias, pre_act, post_act, depth=None):
+    """fp64 reference of ops.linear and its element-wise bound: x fp32 [P, K], W fp32 [M, K] (bf16-rounded by the pack).
+    depth: the accumulation depth of the sum (default K + 2: the K products and the bias; a split-K launch adds its S partial
+    sums: K + 2 + S); the tie and store terms do not depend on it."""
     pre = act64(x.double(), pre_act)
     a = pre.to(torch.bfloat16).double()
     Wb = W.to(torch.bfloat16).double()
@@ -210,7 +212,8 @@ def linear_ref(x, W, bias, pre_act, post_act):
     tie = (bf16_near_tie(pre) * pre.abs() * U16) @ Wb.abs().T
     ref = act64(y, post_act)
     K = x.shape[1]
-    bound = ACT_L[post_act] * ((K + 2) * U32 * A + tie) + 4 * U32 * ref.abs()
+    depth = K + 2 if depth is None else depth
+    bound = ACT_L[post_act] * (depth * U32 * A + tie) + 4 * U32 * ref.abs()
     return ref, bound
 
 
@@ -243,3 +246,111 @@ def attn_blocks(t, heads, rb=128):
     N, T, C = t.shape
     rb = min(rb, T)
     return t.reshape(N, T // rb, rb, heads, C // heads).permute(0, 3, 1, 2, 4)
+
+
+# ------------------------------------------------------------------------------------------ non-network launches of a step
+def pool_act_ref(x, pool, act):
+    """2x2 mean pool (optional) + activation of a bf16 NHWC tensor in fp64, and its bound: four exact bf16 -> fp32 values are
+    added and scaled by 0.25 (<= 4 u32 of the mean of |x|), the activation is evaluated in fp32, one bf16 store."""
+    xd, xa = x.double(), x.double().abs()
+    if pool:
+        N, H, W, C = x.shape
+        xd = xd.reshape(N, H // 2, 2, W // 2, 2, C).mean((2, 4))
+        xa = xa.reshape(N, H // 2, 2, W // 2, 2, C).mean((2, 4))
+    ref = act64(xd, act)
+    return ref, store_bound(4 * U32 * xa, ref)
+
+
+def edm_scalings64(sigma, sd=0.5):
+    """(c_skip, c_out, c_in) of KarrasDenoiser.get_scalings in fp64."""
+    s = sigma.double()
+    return sd ** 2 / (s ** 2 + sd ** 2), s * sd / (s ** 2 + sd ** 2) ** 0.5, 1 / (s ** 2 + sd ** 2) ** 0.5
+
+
+def log_sigma_t(sigma):
+    """t = 250 ln(sigma) and its bound: logf to <= 4 ulp and two fp32 products (16 u32 |t| covers them generously), plus the
+    absolute error of ln near sigma = 1, where |t| is small: 250 * 4 u32."""
+    lt = 250 * torch.log(sigma.double())
+    return lt, 16 * U32 * lt.abs() + 250 * 4 * U32
+
+
+def scaled_input_ref(x, sigma, noise=None):
+    """x_in = c_in(sigma) (x [+ noise sigma]) per sample (edm_precond without noise, edm_dsm_prep with it), x [N, CHW] -> (ref, A).
+    c_in is an fp32 expression of four operations and a powf (<= 8 u32 relative), the sum and the product add two roundings:
+    |got - ref| <= 16 u32 A with A = c_in (|x| + |noise sigma|)."""
+    c_in = edm_scalings64(sigma)[2][:, None]
+    xt, M = x.double(), x.double().abs()
+    if noise is not None:
+        ns = noise.double() * sigma.double()[:, None]
+        xt, M = xt + ns, M + ns.abs()
+    return c_in * xt, c_in * M
+
+
+def dsm_error_terms(F, x0, noise, sigma, scalings):
+    """e = c_out F + c_skip (x0 + noise sigma) - x0 of the DSM loss and the sum Me of its absolute terms, fp64 [N, CHW].
+    In fp32 every factor (c_out, c_skip, x_t) carries <= 8 u32 and the three-term sum two more roundings: |fl(e) - e| <= 16 u32 Me."""
+    c_skip, c_out = scalings[0][:, None], scalings[1][:, None]
+    xt = x0.double() + noise.double() * sigma.double()[:, None]
+    e = c_out * F.double() + c_skip * xt - x0.double()
+    Me = (c_out * F.double()).abs() + (c_skip * xt).abs() + x0.double().abs()
+    return e, Me, c_out
+
+
+def dsm_loss_fwd_bound(e, Me, w=None):
+    """Bound of the per-sample DSM terms mean_CHW(e^2) (and w times it).  Each square is computed from fl(e) with
+    |fl(e) - e| <= 16 u32 Me: |fl(e)^2 - e^2| <= 2 * 16 u32 Me (|e| + 16 u32 Me), its mean the second term.  The sum of the CHW
+    squares, in whatever order, and the division by CHW: (CHW + 16) u32 mean(e^2), the first term (the depth-d bound; no measured
+    constant).  The weighted term multiplies by the fp32 weight w(sigma), an expression of <= 6 operations: 8 u32 relative on
+    the product, hence (1 + 8 u32) on the bound and 8 u32 w mean(e^2)."""
+    CHW = e.shape[1]
+    m = (e ** 2).mean(1)
+    b = (CHW + 16) * U32 * m + 2 * 16 * U32 * (Me * (e.abs() + 16 * U32 * Me)).mean(1)
+    if w is None:
+        return m, b
+    return w * m, w * b * (1 + 8 * U32) + 8 * U32 * w * m
+
+
+def td_gather_cost_ref(xn, x, beta):
+    """Running cost mean_CHW (x' - x)^2 / (2 beta) in fp64 and the sum of its absolute terms: the differences and squares are
+    fp32 (<= 3 roundings, covered by taking (|x'| + |x|)^2 as the term magnitude), the sum has depth CHW: c = CHW + 8."""
+    b2 = 2 * beta.double()
+    xn, x = xn.double(), x.double()
+    return ((xn - x) ** 2).mean(1) / b2, ((xn.abs() + x.abs()) ** 2).mean(1) / b2
+
+
+def var_step_ref(x, eps, z, xm, cm, sg):
+    """The VAR transition (models/DxMI/var_sampler.py:285 / :399) in fp64, x / eps / z [N, CHW], per-sample xm, cm, sg [N]:
+    control = cm eps, mean = xm x + control, x' = mean + sg z, logp = mean_CHW(-(x' - mean)^2 / (2 sg^2) - ln sg - ln sqrt(2 pi)).
+    -> {name: (ref, bound)}.  The three image outputs are sums of <= 3 fp32 products: 4 u32 A, A = |xm x| + |cm eps| + |sg z|
+    (either association of the sum).  The kernel forms d = x' - mean from the ROUNDED x': |fl(d) - sg z| <= 3 u32 A =: dd (the
+    rounding of x', of sg z and of the difference), so a log-prob term errs by (2 |sg z| dd + dd^2) / (2 sg^2) plus 4 u32 of its
+    own absolute terms T = z^2 / 2 + |ln sg| + ln sqrt(2 pi); the sum over CHW, in any order, adds (CHW + 8) u32 mean(T)."""
+    import math
+    e = lambda v: v.double()[:, None]
+    x, eps, z = x.double(), eps.double(), z.double()
+    control = e(cm) * eps
+    mean = x * e(xm) + control
+    xn = mean + e(sg) * z
+    A = (x * e(xm)).abs() + control.abs() + (e(sg) * z).abs()
+    c = math.log(math.sqrt(2 * math.pi))
+    logp = (-(z ** 2) / 2 - torch.log(e(sg)) - c).mean(1)
+    T = z ** 2 / 2 + torch.log(e(sg)).abs() + c
+    dd = 3 * U32 * A
+    CHW = x.shape[1]
+    lb = ((2 * (e(sg) * z).abs() * dd + dd ** 2) / (2 * e(sg) ** 2) + 4 * U32 * T).mean(1) + (CHW + 8) * U32 * T.mean(1)
+    return {"x_next": (xn, 4 * U32 * A), "mean": (mean, 4 * U32 * A), "control": (control, 4 * U32 * control.abs()), "logp": (logp, lb)}
+
+
+def edm_step_ref(x, F, z, sigma, sdn, sup, sd=0.5):
+    """The Euler-ancestral EDM transition (models/DxMI/openai_diffusion.py:71-94) in fp64, [N, CHW] and per-sample scalars:
+    den = c_out F + c_skip x, mu = x + (x - den) / sigma (sigma_down - sigma), x' = mu + z sigma_up -> (mu, x', A_mu, A_x'),
+    each within 16 u32 A: the scalings carry <= 8 u32, every further operation one rounding of its absolute terms
+    A_mu = |x| + (|x| + |c_out F| + |c_skip x|) |sigma_down - sigma| / sigma, A_x' = A_mu + |z sigma_up|."""
+    e = lambda v: v.double()[:, None]
+    c_skip, c_out, _ = [c[:, None] for c in edm_scalings64(sigma, sd)]
+    x, F, z = x.double(), F.double(), z.double()
+    den = c_out * F + c_skip * x
+    dt = e(sdn) - e(sigma)
+    mu = x + (x - den) / e(sigma) * dt
+    A = x.abs() + (x.abs() + (c_out * F).abs() + (c_skip * x).abs()) / e(sigma) * dt.abs()
+    return mu, mu + z * e(sup), A, A + (z * e(sup)).abs()

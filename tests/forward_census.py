@@ -1,8 +1,10 @@
 """Shape census of the forward launches of the sampling and training programs (used by test_hip_forward_shapes.py).
 
-`FwdCensus` wraps the forward `ops` entry points the models call and records a signature for every call made OUTSIDE the
-backward() methods of _EDMUNetFn, _UNetFn and _ValueNetFn: operand shapes plus every field that takes part in choosing a kernel
-or an epilogue, including the conv kernel id dxmi_conv2d_kernel_id reports for the launch (read through an ops.PROFILER, as
+`FwdCensus` intercepts every public function of `dxmi_hip.ops` (backward_census.Census: "record or refuse") and records a
+signature for every launch op (FWD_OPS, the network kernels, and STEP_OPS, the non-network forward launches of a step) called
+OUTSIDE the instrumented backward() methods (backward_census.Census.region_classes); a call that is neither a launch op nor on
+the allow-list backward_census.ALLOWED nor a backward launch op called from a backward lands in
+`FwdCensus.unknown`.  A row holds operand shapes plus every field that takes part in choosing a kernel or an epilogue, including the conv kernel id dxmi_conv2d_kernel_id reports for the launch (read through an ops.PROFILER, as
 tools/conv_shapes.py does) and the knobs in effect.  The programs (PROGRAMS) run eagerly with graphs off, each under the tuning
 it really uses.  For every GroupNorm row the census also keeps the largest |mean| / std over (image, group) of the activation
 it normalised (`cond`): these are random-init nets, not trained weights, so this measures the conditioning of the census's own
@@ -18,6 +20,11 @@ import backward_census
 FWD_OPS = ("conv2d", "linear", "groupnorm_silu", "groupnorm_apply", "groupnorm_generic", "block_stats", "fold_stats",
            "gn_blockstats_to_generic", "attention", "attention_proj", "attn_block", "timestep_embedding", "upsample2x", "pool_act",
            "value_head")
+# Non-network forward launches of a step: the DSM loss kernels, the TD kernels (td_loss also returns the gradient: it has a row
+# in both censuses), dropout, the input layout conversion, the sampler stages and transitions
+STEP_OPS = ("dropout", "nchw_f32_to_nhwc_bf16", "edm_dsm_prep", "edm_dsm_loss_fwd", "td_gather_cost", "td_loss", "karras_stage",
+            "cm_stage", "var_step", "edm_step", "groupnorm_silu_shortcut", "edm_precond", "var_gather_sched", "nhwc_bf16_to_nchw_f32",
+            "quantize_u8")
 THROUGHPUT_KNOBS = (96, 13)          # (conv_ws_min_tiles, conv_sm_mask) under ops.throughput_tuning()
 
 
@@ -50,7 +57,7 @@ class FwdCensus(backward_census.Census):
     def __init__(self, ops):
         super().__init__(ops)
         self.cond, self.kid, self.gn_frames = {}, None, []
-        self.sigs = {n: inspect.signature(getattr(ops, n)) for n in FWD_OPS}
+        self.sigs = {n: inspect.signature(getattr(ops, n)) for n in FWD_OPS + STEP_OPS}
 
     def tuning(self):
         knobs = (self.ops.get_tuning("conv_ws_min_tiles"), self.ops.get_tuning("conv_sm_mask"))
@@ -66,6 +73,15 @@ class FwdCensus(backward_census.Census):
         self.cond[row] = max(self.cond.get(row, 0.0), round(r, 3))
 
     def _wrap(self, name, fn):
+        if name not in self.sigs:
+            judged = name in backward_census.ALLOWED
+
+            def other(*a, **kw):
+                # inside a backward(): the backward census judges the call; outside, a backward launch op is as unknown as any
+                if not self.depth and not judged:
+                    self.unknown.add(name)
+                return fn(*a, **kw)
+            return other
         sig = self.sigs[name]
 
         def w(*a, **kw):
@@ -94,6 +110,8 @@ class FwdCensus(backward_census.Census):
                 return out
             out = fn(*a, **kw)
             row = self._row(name, p, out)
+            if row is None:                     # the op declined the shape and launched nothing (groupnorm_silu_shortcut)
+                return out
             self.rows.add(row)
             if row[0] == "gn":
                 if self.gn_frames:
@@ -122,12 +140,47 @@ class FwdCensus(backward_census.Census):
 
     def _row(self, name, p, out):
         ops = self.ops
-        if name == "linear":
-            x, pw = p["x"], p["pw"]
-            P, K = x.shape
-            S = int(ops.load().dxmi_linear_splitk_slices(P, K, pw.Cout)) if (p["splitk"] and p["post_act"] == ops.ACT_NONE) else 1
-            form = "small" if (P <= 4096 and pw.Cout % 4 == 0) else "tiled"      # mirrors dxmi_linear_fwd (csrc/conv_igemm.hip)
-            return ("linear", int(P), int(K), pw.Cout, int(p["pre_act"]), int(p["post_act"]), p["bias"] is not None, form, S)
+        if name in ("linear", "upsample2x", "pool_act"):
+            return backward_census.forward_style_row(ops, name, p)
+        has = lambda *names: tuple(n for n in names if p[n] is not None)
+        if name == "dropout":
+            return backward_census._NEW["dropout"](p)
+        if name == "td_loss":
+            return backward_census._NEW["td_loss"](p)
+        if name == "nchw_f32_to_nhwc_bf16":
+            return ("nchw_f32_to_nhwc_bf16", tuple(p["x"].shape))
+        if name == "edm_dsm_prep":
+            return ("edm_dsm_prep", tuple(p["x_start"].shape))
+        if name == "edm_dsm_loss_fwd":
+            return ("edm_dsm_loss_fwd", tuple(p["x_start"].shape), p["weight_schedule"], bool(p["distillation"]))
+        if name == "td_gather_cost":
+            return ("td_gather_cost", int(p["state_rows"].numel()), int(p["traj2d"].shape[1]), has("next_rows", "next_dense"))
+        if name == "karras_stage":
+            return ("karras_stage", int(p["mode"]), bool(p["last"]), tuple(p["x"].shape),
+                    has("x2", "d", "model_out", "noise", "x_in", "t", "out", "denoised"))
+        if name == "cm_stage":
+            return ("cm_stage", int(p["mode"]), int(p["edit"]), bool(p["last"]), tuple(p["x"].shape),
+                    has("Q", "model_out", "noise", "ref", "mask", "x_in", "t", "out", "denoised"))
+        if name == "var_step":
+            outs = p["outs"]
+            mean, control = (p["want_mean"], p["want_control"]) if outs is None else (outs[1] is not None, outs[2] is not None)
+            return ("var_step", tuple(p["x"].shape), bool(mean), bool(control), int(p["assoc"]))
+        if name == "edm_step":
+            return ("edm_step", tuple(p["x"].shape))
+        if name == "groupnorm_silu_shortcut":
+            if out is None:
+                return None
+            st = p["stats"]
+            return ("gn_shortcut", tuple(p["x"].shape), _c(p["in1"]), p["pw"].Cout, int(p["groups"]), float(p["eps"]), bool(p["silu"]),
+                    p["bias"] is not None, st[0].P, st[1].P if p["in1"] is not None else 0)
+        if name == "edm_precond":
+            return ("edm_precond", tuple(p["x"].shape))
+        if name == "var_gather_sched":
+            return ("var_gather_sched", int(p["t"].numel()), int(p["continuous_steps"].numel()))
+        if name == "nhwc_bf16_to_nchw_f32":
+            return ("nhwc_bf16_to_nchw_f32", tuple(p["x"].shape))
+        if name == "quantize_u8":
+            return ("quantize_u8", tuple(p["x"].shape), int(p["mode"]), bool(p["nhwc"]))
         if name in ("groupnorm_apply", "groupnorm_generic"):
             x, in1 = p["x"], p["in1"]
             if name == "groupnorm_apply":
@@ -156,10 +209,6 @@ class FwdCensus(backward_census.Census):
             return ("attn_block", tuple(p["x"].shape), p["stats"].P, bool(p["want_stats"]))
         if name == "timestep_embedding":
             return ("timestep_embedding", int(p["t"].numel()), int(p["dim"]), int(p["order"]), float(p["max_period"]))
-        if name == "upsample2x":
-            return ("upsample2x", tuple(p["x"].shape))
-        if name == "pool_act":
-            return ("pool_act", tuple(p["x"].shape), bool(p["pool"]), int(p["act"]))
         if name == "value_head":
             return ("value_head", tuple(p["x"].shape), p["out_w"] is not None)
         raise KeyError(name)
@@ -167,9 +216,6 @@ class FwdCensus(backward_census.Census):
     def __enter__(self):
         import os
         assert not [v for v in ATTN_ENV if v in os.environ], f"unset {ATTN_ENV}: attention_kernel() names the default dispatch"
-        from models.cm import unet_train
-        from models.DxMI import unet_small_train
-        from models import value_train
         ops, census = self.ops, self
 
         class _KernelIdProbe(ops.OpProfiler):
@@ -185,12 +231,7 @@ class FwdCensus(backward_census.Census):
 
         self.saved[(ops, "PROFILER")] = ops.PROFILER
         ops.PROFILER = _KernelIdProbe()
-        for n in FWD_OPS:
-            self.saved[(ops, n)] = getattr(ops, n)
-            setattr(ops, n, self._wrap(n, getattr(ops, n)))
-        for cls in (unet_train._EDMUNetFn, unet_small_train._UNetFn, value_train._ValueNetFn):
-            self.saved[(cls, "backward")] = cls.__dict__["backward"]
-            cls.backward = self._wrap_bwd(cls.__dict__["backward"].__func__)
+        self._instrument()
         return self
 
 
@@ -269,8 +310,80 @@ def edm_sample(device, name, B, class_cond):
     del s, net
 
 
+def edm_teacher(device):
+    """The class-conditional ImageNet-64 EDM net as generate_large.py --karras_sampler / --cm_sampler sets it up (imagenet64_T10's
+    diffusion block, fp16 conversion, eval mode), random init with the zero-initialised layers given weights."""
+    import configs_builtin
+    from models.cm.script_util import create_model_and_diffusion
+    cfg = configs_builtin.get("imagenet64_T10")
+    torch.manual_seed(0)
+    with torch.device(device):
+        net, diffusion = create_model_and_diffusion(**cfg.diffusion)
+    with torch.no_grad():
+        for p in net.parameters():
+            if float(p.abs().max()) == 0:
+                torch.nn.init.normal_(p, std=0.02)
+    net.to(device)
+    if cfg.diffusion.use_fp16:
+        net.convert_to_fp16()
+    net.eval()
+    return net, diffusion
+
+
+def _labels(device, B):
+    return torch.randint(0, 1000, (B,), device=device, generator=torch.Generator(device=device).manual_seed(1))
+
+
+def karras_heun(device, B, steps=3):
+    """karras_sample(..., sampler="heun") of generate_large.py --karras_sampler heun at batch B, graphs off.  `steps` = 3 gives
+    two Heun steps with the corrector and the final Euler step: the launch signatures of the documented 40 steps."""
+    from models.cm.karras_diffusion import karras_sample
+    net, diffusion = edm_teacher(device)
+    with torch.no_grad():
+        karras_sample(diffusion, net, (B, 3, 64, 64), steps, model_kwargs={"y": _labels(device, B)}, device=device,
+                      sigma_min=diffusion.sigma_min, sigma_max=diffusion.sigma_max, sampler="heun", use_graph=False)
+    torch.cuda.synchronize()
+    del net
+
+
+def cm_multistep(device, B):
+    """generate_large.py --cm_sampler multistep --ts 0,22,39 (steps 40, distillation=True) at batch B, graphs off."""
+    from models.cm.karras_diffusion import karras_sample
+    net, diffusion = edm_teacher(device)
+    diffusion.distillation = True
+    with torch.no_grad():
+        karras_sample(diffusion, net, (B, 3, 64, 64), 40, model_kwargs={"y": _labels(device, B)}, device=device,
+                      sigma_min=diffusion.sigma_min, sigma_max=diffusion.sigma_max, sampler="multistep", ts=(0, 22, 39),
+                      use_graph=False)
+    torch.cuda.synchronize()
+    del net
+
+
+def cm_inpainting(device, B=14):
+    """iterative_inpainting (zero-shot editing) on the full-size net at the batch tests/test_hip_cm_sample.py drives it with
+    (14 images, ts = (0, 10, 20), steps 40, a mask that keeps the first seven images)."""
+    from models.cm import karras_diffusion as kd
+    net, diffusion = edm_teacher(device)
+    diffusion.distillation = True
+    g = torch.Generator(device=device).manual_seed(5)
+    images = torch.rand(B, 3, 64, 64, device=device, generator=g) * 2 - 1
+    x = torch.randn(B, 3, 64, 64, device=device, generator=g) * 80.0
+    mask = torch.zeros_like(x)
+    mask[: B // 2] = 1.0
+    with torch.no_grad():
+        kd.iterative_inpainting(kd.KarrasDenoiserFn(diffusion, net, True, {"y": _labels(device, B)}), images, x, (0, 10, 20),
+                                steps=40, generator=None, mask=mask)
+    torch.cuda.synchronize()
+    del net
+
+
 # program -> (runner(device), tuning)
 PROGRAMS = {
+    "edm_dsm_train_b16": (lambda d: backward_census.edm_dsm_step(d, 16), "default"),
+    "edm_dsm_train_b32": (lambda d: backward_census.edm_dsm_step(d, 32), "default"),
+    "imagenet64_karras_heun_b100": (lambda d: karras_heun(d, 100), "default"),
+    "imagenet64_cm_multistep_b100": (lambda d: cm_multistep(d, 100), "default"),
+    "imagenet64_cm_inpainting_b14": (lambda d: cm_inpainting(d, 14), "default"),
     "cifar10_sample_T10_b256": (lambda d: cifar10_sample(d, 256, 10), "default"),
     "cifar10_sample_T10_b32": (lambda d: cifar10_sample(d, 32, 10), "default"),
     "cifar10_sample_T4_b128": (lambda d: cifar10_sample(d, 128, 4), "default"),
@@ -284,10 +397,9 @@ PROGRAMS = {
 
 
 def record(ops, program, device="cuda:0"):
-    """(rows, cond) of one program's forward launches, under the tuning the program uses."""
+    """(rows, cond, unknown) of one program's forward launches, under the tuning the program uses."""
     run, tuning = PROGRAMS[program]
-    tune = ops.throughput_tuning() if tuning == "throughput" else backward_census._nullctx()
-    with tune, FwdCensus(ops) as c:
+    with backward_census.tuned(ops, tuning), FwdCensus(ops) as c:
         run(device)
     torch.cuda.empty_cache()
-    return c.rows, c.cond
+    return c.rows, c.cond, sorted(c.unknown)

@@ -207,3 +207,31 @@ def test_attention_block_bound_rejects_the_neighbouring_heads_lse():
     bad = lse.clone()
     bad[1, 1, 128:256] = lse[1, 2, 128:256]
     must_reject(lambda: ck.blocks("attn", blocks(bwd(bad)), blocks(ref), tol, 4))
+
+
+def test_dropout_hash_restatement_matches_the_oracles():
+    """backward_bounds.dropout_keep (torch int64) and oracle.unet_small.dropout_keep_mask (numpy) state the same hash."""
+    import backward_bounds as bb
+    from oracle.unet_small import dropout_keep_mask
+    for shp, p, seed in (((3, 8, 8, 64), 0.1, 12345), ((2, 5, 7, 24), 0.5, 0xDEADBEEF), ((1, 4, 4, 8), 0.0, 7)):
+        a = bb.dropout_keep(shp, p, seed, "cpu")
+        b = dropout_keep_mask((shp[0], shp[3], shp[1], shp[2]), p, seed).permute(0, 2, 3, 1) != 0
+        assert torch.equal(a, b)
+
+
+def test_silu_bwd_bound_holds_for_fp32_torch_and_catches_a_bf16_ulp():
+    """The fp32 evaluation of the expression stays inside 16 u32 A on the host; one bf16 ulp on one element does not."""
+    import backward_bounds as bb
+    g = torch.Generator().manual_seed(0)
+    pre, gy = torch.randn(32, 768, generator=g) * 3, torch.randn(32, 768, generator=g)
+    ref, A = bb.silu_bwd_ref(pre, gy)
+    s = torch.sigmoid(pre)
+    got = gy * (s * (1 + pre * (1 - s)))
+    c = bb.Checker()
+    assert c.fp32("silu_bwd", got, ref, A, 16) < 1.0
+    assert float((16 * bb.U32 * A / ref.abs().clamp_min(1e-30)).median()) < 1e-4          # not vacuous
+    i = int(ref.abs().argmax())
+    bad = got.clone()
+    bad.view(-1)[i] *= 1 + 2.0 ** -8
+    with pytest.raises(bb.BoundError):
+        c.fp32("silu_bwd", bad, ref, A, 16)

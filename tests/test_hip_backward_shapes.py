@@ -1,12 +1,17 @@
-"""Every backward launch of the two training steps against an fp64 reference, at the shapes the training steps use.
+"""Every backward launch of the training programs against an fp64 reference, at the shapes the programs use.
 
-CASES below is the census of the backward launches of one eager iteration of each training program (tests/backward_census.py):
-the ImageNet-64 EDM step (imagenet64_T10, per-GPU batch 16, ops.throughput_tuning()) and the CIFAR-10 step (cifar10_T10 U-Net
-and value net, batch 128).  test_census_is_covered re-records the census and fails when a model change adds a launch shape the
-table does not hold.  Each row is then checked on seeded bf16 inputs against stock torch in float64 on the device (F.unfold +
-matmul for convolutions and weight gradients, softmax attention and F.group_norm under autograd), with the element-wise bounds
-of tests/backward_bounds.py; none of this project's kernels takes part in a reference.  test_report prints the largest
-|err| / bound seen per op.
+CASES below is the census of the backward launches of one eager iteration of each program of backward_census.PROGRAMS
+(tests/backward_census.py), each recorded under the tuning the program runs under:
+    imagenet64    DxMI step on imagenet64_T10, per-GPU batch 16                 ops.throughput_tuning()
+    cifar10       DxMI step on cifar10_T10 (U-Net and value net), batch 128     ops.throughput_tuning()
+    edm_dsm_b16   DSM microbatch of the full-size EDM U-Net (TrainLoop), 16     default knobs
+    edm_dsm_b32   the same at 32 images                                         default knobs
+test_census_is_covered re-records each program and fails when it launches a shape the table does not hold, or calls an `ops`
+function inside a backward that is neither a launch op nor on the census's allow-list (record or refuse).  Each row is then
+checked on seeded inputs against stock torch in float64 on the device (F.unfold + matmul for convolutions and weight
+gradients, softmax attention and F.group_norm under autograd, plain expressions for the element-wise ops), with the
+element-wise bounds of tests/backward_bounds.py; none of this project's kernels takes part in a reference.  test_report
+prints the largest |err| / bound seen per op; test_every_row_kind_has_a_test keeps the kinds of the table and of the tests equal.
 """
 import zlib
 
@@ -14,10 +19,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from backward_bounds import U16, U32, Checker, attention_bwd_ref, groupnorm_bwd_ref, unfold_nhwc, wgrad_depth, wgrad_ref
+from backward_bounds import (U16, U32, Checker, attention_bwd_ref, dropout_ref, dsm_loss_bwd_ref, edm_step_bwd_ref, groupnorm_bwd_ref,
+                             silu_bwd_ref, unfold_nhwc, value_head_bwd_ref, value_head_pgrad_ref, var_step_bwd_ref, wgrad_depth,
+                             wgrad_ref)
+from forward_bounds import FwdChecker, dsm_error_terms, linear_ref, pool_act_ref
 
 DEV = "cuda:0"
-CHECK = Checker()
+CHECK = FwdChecker()              # Checker plus `within` (an explicit element-wise bound) for the forward kernels' rows
 
 CASES = {
     'wgrad': [
@@ -129,16 +137,63 @@ CASES = {
         ('wgrad', (256, 4, 4, 256), 0, (256, 4, 4, 256), 3, 1, 1, 0, False, True),
         ('wgrad', (256, 8, 8, 256), 0, (256, 8, 8, 256), 1, 0, 1, 0, False, False),
         ('wgrad', (256, 8, 8, 256), 0, (256, 8, 8, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 1152), 0, (32, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 1344), 0, (32, 16, 16, 576), 3, 1, 1, 0, False, True),
         ('wgrad', (32, 16, 16, 256), 0, (32, 16, 16, 256), 1, 0, 1, 0, False, False),
         ('wgrad', (32, 16, 16, 256), 0, (32, 16, 16, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 384), 0, (32, 16, 16, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 384), 0, (32, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 384), 0, (32, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 576), 0, (32, 16, 16, 1728), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 576), 0, (32, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 576), 0, (32, 16, 16, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 576), 0, (32, 32, 32, 576), 3, 1, 1, 1, False, True),
+        ('wgrad', (32, 16, 16, 576), 384, (32, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 576), 576, (32, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 768), 0, (32, 16, 16, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 768), 576, (32, 16, 16, 576), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 16, 16, 960), 0, (32, 16, 16, 576), 3, 1, 1, 0, False, True),
         ('wgrad', (32, 32, 32, 128), 0, (32, 32, 32, 128), 3, 1, 1, 0, False, True),
         ('wgrad', (32, 32, 32, 128), 0, (32, 32, 32, 256), 1, 0, 1, 0, False, False),
         ('wgrad', (32, 32, 32, 128), 0, (32, 32, 32, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 192), 0, (32, 32, 32, 192), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 192), 0, (32, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 192), 0, (32, 32, 32, 384), 3, 1, 1, 0, False, True),
         ('wgrad', (32, 32, 32, 256), 0, (32, 32, 32, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 384), 0, (32, 32, 32, 1152), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 384), 0, (32, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 384), 0, (32, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 384), 0, (32, 64, 64, 384), 3, 1, 1, 1, False, True),
+        ('wgrad', (32, 32, 32, 384), 192, (32, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 384), 384, (32, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 576), 0, (32, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 576), 0, (32, 32, 32, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 576), 384, (32, 32, 32, 384), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 768), 0, (32, 32, 32, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 32, 32, 960), 0, (32, 32, 32, 384), 3, 1, 1, 0, False, True),
         ('wgrad', (32, 64, 64, 128), 0, (32, 64, 64, 128), 1, 0, 1, 0, False, False),
         ('wgrad', (32, 64, 64, 128), 0, (32, 64, 64, 128), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 192), 0, (32, 64, 64, 192), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 192), 0, (32, 64, 64, 64), 3, 1, 1, 0, False, False),
+        ('wgrad', (32, 64, 64, 192), 192, (32, 64, 64, 192), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 384), 0, (32, 64, 64, 192), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 384), 0, (32, 64, 64, 384), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 384), 192, (32, 64, 64, 192), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 64, 64, 576), 0, (32, 64, 64, 192), 3, 1, 1, 0, False, True),
         ('wgrad', (32, 64, 64, 64), 0, (32, 64, 64, 128), 1, 0, 1, 0, False, False),
+        ('wgrad', (32, 64, 64, 64), 0, (32, 64, 64, 192), 1, 0, 1, 0, False, False),
+        ('wgrad', (32, 8, 8, 1344), 0, (32, 8, 8, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 1536), 0, (32, 8, 8, 768), 3, 1, 1, 0, False, True),
         ('wgrad', (32, 8, 8, 256), 0, (32, 8, 8, 256), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 576), 0, (32, 8, 8, 576), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 576), 0, (32, 8, 8, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 576), 0, (32, 8, 8, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 768), 0, (32, 16, 16, 768), 3, 1, 1, 1, False, True),
+        ('wgrad', (32, 8, 8, 768), 0, (32, 8, 8, 2304), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 768), 0, (32, 8, 8, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 768), 0, (32, 8, 8, 768), 3, 1, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 768), 576, (32, 8, 8, 768), 1, 0, 1, 0, False, True),
+        ('wgrad', (32, 8, 8, 768), 768, (32, 8, 8, 768), 1, 0, 1, 0, False, True),
     ],
     'stem_wgrad': [
         # (op, x NCHW, dy NHWC)
@@ -147,6 +202,7 @@ CASES = {
         ('stem_wgrad', (16, 3, 64, 64), (16, 64, 64, 192)),
         ('stem_wgrad', (256, 3, 32, 32), (256, 32, 32, 128)),
         ('stem_wgrad', (32, 3, 64, 64), (32, 64, 64, 128)),
+        ('stem_wgrad', (32, 3, 64, 64), (32, 64, 64, 192)),
     ],
     'linear_bwd': [
         # (op, x [P, K], dy [P, M], need_dx)
@@ -156,6 +212,9 @@ CASES = {
         ('linear_bwd', (16, 192), (16, 768), False),
         ('linear_bwd', (16, 768), (16, 35712), True),
         ('linear_bwd', (16, 768), (16, 768), True),
+        ('linear_bwd', (32, 192), (32, 768), False),
+        ('linear_bwd', (32, 768), (32, 35712), True),
+        ('linear_bwd', (32, 768), (32, 768), True),
     ],
     'conv2d': [
         # (op, x NHWC, C1, Cout, k, transpose-flipped pack, stride, pad, pad_br, upsample, residual, mask_src, bias, act, out_nchw_f32)
@@ -266,19 +325,59 @@ CASES = {
         ('conv2d', (256, 8, 8, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
         ('conv2d', (256, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
         ('conv2d', (256, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 1728), 0, 576, 1, True, 1, 0, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 16, 16, 256), 0, 256, 1, True, 1, 0, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
         ('conv2d', (32, 16, 16, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 384), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 1152, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 1344, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 384, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 576, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 576, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 768, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 576), 0, 960, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 16, 16, 768), 0, 768, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 1152), 0, 384, 1, True, 1, 0, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
         ('conv2d', (32, 32, 32, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 192), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 32, 32, 256), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 32, 32, 256), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
         ('conv2d', (32, 32, 32, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 192, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 384, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 384, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 576, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 768, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 384), 0, 960, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 32, 32, 576), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 64, 64, 128), 0, 128, 1, True, 1, 0, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 64, 64, 128), 0, 128, 3, True, 1, 1, None, 0, False, True, False, 0, False),
         ('conv2d', (32, 64, 64, 128), 0, 128, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 192), 0, 192, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 192), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 192), 0, 384, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 192), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 192), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 384), 0, 384, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 64, 64, 64), 0, 192, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 2304), 0, 768, 1, True, 1, 0, None, 0, False, False, False, 0, False),
         ('conv2d', (32, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, False, True, False, 0, False),
         ('conv2d', (32, 8, 8, 256), 0, 256, 3, True, 1, 1, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 576), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 768), 0, 1344, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 768), 0, 1536, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 768), 0, 576, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 768), 0, 576, 3, True, 1, 1, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 768), 0, 768, 1, True, 1, 0, None, 0, False, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 768), 0, 768, 1, True, 1, 0, None, 0, True, False, False, 0, False),
+        ('conv2d', (32, 8, 8, 768), 0, 768, 3, True, 1, 1, None, 0, False, False, False, 0, False),
     ],
     'groupnorm_generic_bwd': [
         # (op, x NHWC, C1, add0, add1, groups, silu, scale_shift, fwd_stats)
@@ -315,6 +414,37 @@ CASES = {
         ('groupnorm_generic_bwd', (16, 8, 8, 768), 0, True, False, 32, True, False, False),
         ('groupnorm_generic_bwd', (16, 8, 8, 768), 576, False, False, 32, True, False, True),
         ('groupnorm_generic_bwd', (16, 8, 8, 768), 768, False, False, 32, True, False, False),
+        ('groupnorm_generic_bwd', (32, 16, 16, 384), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 384), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 576), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 576), 0, True, False, 32, False, False, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 576), 0, True, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 576), 384, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 576), 576, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 768), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 16, 16, 768), 576, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 192), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 192), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 384), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 384), 0, True, False, 32, False, False, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 384), 0, True, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 384), 192, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 384), 384, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 576), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 32, 32, 576), 384, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 64, 64, 192), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 64, 64, 192), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 64, 64, 192), 0, True, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 64, 64, 192), 192, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 64, 64, 384), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 64, 64, 384), 192, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 8, 8, 576), 0, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 8, 8, 576), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 8, 8, 768), 0, False, False, 32, True, True, True),
+        ('groupnorm_generic_bwd', (32, 8, 8, 768), 0, True, False, 32, False, False, False),
+        ('groupnorm_generic_bwd', (32, 8, 8, 768), 0, True, False, 32, True, False, False),
+        ('groupnorm_generic_bwd', (32, 8, 8, 768), 576, False, False, 32, True, False, True),
+        ('groupnorm_generic_bwd', (32, 8, 8, 768), 768, False, False, 32, True, False, False),
     ],
     'groupnorm_silu_bwd': [
         # (op, x NHWC, C1, add0, add1, groups, silu, scale_shift, fwd_stats)
@@ -343,6 +473,9 @@ CASES = {
         ('attention_bwd', (16, 1024, 1152), 6, True, True),
         ('attention_bwd', (16, 256, 1728), 9, True, True),
         ('attention_bwd', (16, 64, 2304), 12, True, True),
+        ('attention_bwd', (32, 1024, 1152), 6, True, True),
+        ('attention_bwd', (32, 256, 1728), 9, True, True),
+        ('attention_bwd', (32, 64, 2304), 12, True, True),
     ],
     'colsum': [
         # (op, x, accumulate)
@@ -351,6 +484,7 @@ CASES = {
         ('colsum', (16, 64, 64, 192), False),
         ('colsum', (256, 32, 32, 128), False),
         ('colsum', (32, 64, 64, 128), False),
+        ('colsum', (32, 64, 64, 192), False),
     ],
     'colsum_per_image': [
         # (op, x NHWC)
@@ -389,6 +523,106 @@ CASES = {
         ('pool_act_bwd', (32, 64, 64, 128), False),
         ('pool_act_bwd', (32, 8, 8, 256), False),
         ('pool_act_bwd', (32, 8, 8, 256), True),
+    ],
+    'upsample2x': [
+        # (op, x NHWC)
+        ('upsample2x', (16, 16, 16, 384)),
+        ('upsample2x', (16, 32, 32, 192)),
+        ('upsample2x', (16, 8, 8, 576)),
+        ('upsample2x', (32, 16, 16, 384)),
+        ('upsample2x', (32, 32, 32, 192)),
+        ('upsample2x', (32, 8, 8, 576)),
+    ],
+    'dropout': [
+        # (op, x NHWC, p, seed on the device)
+        ('dropout', (128, 16, 16, 256), 0.1, False),
+        ('dropout', (128, 32, 32, 128), 0.1, False),
+        ('dropout', (128, 4, 4, 256), 0.1, False),
+        ('dropout', (128, 8, 8, 256), 0.1, False),
+        ('dropout', (16, 16, 16, 384), 0.1, False),
+        ('dropout', (16, 16, 16, 576), 0.1, False),
+        ('dropout', (16, 16, 16, 768), 0.1, False),
+        ('dropout', (16, 32, 32, 192), 0.1, False),
+        ('dropout', (16, 32, 32, 384), 0.1, False),
+        ('dropout', (16, 32, 32, 576), 0.1, False),
+        ('dropout', (16, 64, 64, 192), 0.1, False),
+        ('dropout', (16, 64, 64, 384), 0.1, False),
+        ('dropout', (16, 8, 8, 576), 0.1, False),
+        ('dropout', (16, 8, 8, 768), 0.1, False),
+        ('dropout', (32, 16, 16, 384), 0.1, False),
+        ('dropout', (32, 16, 16, 576), 0.1, False),
+        ('dropout', (32, 16, 16, 768), 0.1, False),
+        ('dropout', (32, 32, 32, 192), 0.1, False),
+        ('dropout', (32, 32, 32, 384), 0.1, False),
+        ('dropout', (32, 32, 32, 576), 0.1, False),
+        ('dropout', (32, 64, 64, 192), 0.1, False),
+        ('dropout', (32, 64, 64, 384), 0.1, False),
+        ('dropout', (32, 8, 8, 576), 0.1, False),
+        ('dropout', (32, 8, 8, 768), 0.1, False),
+    ],
+    'value_head_bwd': [
+        # (op, feat NHWC)
+        ('value_head_bwd', (128, 4, 4, 256)),
+        ('value_head_bwd', (16, 8, 8, 256)),
+        ('value_head_bwd', (256, 4, 4, 256)),
+        ('value_head_bwd', (32, 8, 8, 256)),
+    ],
+    'edm_dsm_loss_bwd': [
+        # (op, x_start, weight schedule, distillation, g_mse, g_xs)
+        ('edm_dsm_loss_bwd', (16, 3, 64, 64), 'karras', False, True, False),
+        ('edm_dsm_loss_bwd', (32, 3, 64, 64), 'karras', False, True, False),
+    ],
+    'silu_bwd': [
+        # (op, pre shape, pre dtype, g dtype)
+        ('silu_bwd', (128, 512), 'float32', 'float32'),
+        ('silu_bwd', (16, 768), 'float32', 'float32'),
+        ('silu_bwd', (32, 768), 'float32', 'float32'),
+    ],
+    'var_step_bwd': [
+        # (op, z, g_next, g_mean, g_control, g_logp)
+        ('var_step_bwd', (128, 3, 32, 32), True, True, True, True),
+    ],
+    'linear': [
+        # (op, P, K, Cout, pre_act, post_act, bias, form, split-K slices): forward kernels launched by the backward() methods
+        ('linear', 128, 128, 512, 0, 0, True, 'small', 1),
+        ('linear', 128, 4992, 512, 0, 0, False, 'small', 9),
+        ('linear', 128, 512, 512, 0, 0, False, 'small', 1),
+        ('linear', 128, 512, 512, 0, 0, True, 'small', 1),
+        ('linear', 16, 192, 768, 0, 0, True, 'small', 1),
+        ('linear', 16, 35712, 768, 0, 0, False, 'small', 64),
+        ('linear', 16, 768, 768, 0, 0, False, 'small', 1),
+        ('linear', 16, 768, 768, 0, 0, True, 'small', 1),
+        ('linear', 32, 192, 768, 0, 0, True, 'small', 1),
+        ('linear', 32, 35712, 768, 0, 0, False, 'small', 64),
+        ('linear', 32, 768, 768, 0, 0, False, 'small', 1),
+        ('linear', 32, 768, 768, 0, 0, True, 'small', 1),
+    ],
+    'pool_act': [
+        # (op, x NHWC, pool, act)
+        ('pool_act', (128, 16, 16, 256), True, 0),
+        ('pool_act', (128, 32, 32, 256), True, 0),
+        ('pool_act', (128, 8, 8, 256), True, 0),
+        ('pool_act', (16, 16, 16, 768), True, 0),
+        ('pool_act', (16, 32, 32, 576), True, 0),
+        ('pool_act', (16, 64, 64, 384), True, 0),
+        ('pool_act', (32, 16, 16, 768), True, 0),
+        ('pool_act', (32, 32, 32, 576), True, 0),
+        ('pool_act', (32, 64, 64, 384), True, 0),
+    ],
+    'value_head_pgrad': [
+        # (op, s [N, C], learn_out_scale)
+        ('value_head_pgrad', (128, 256), True),
+        ('value_head_pgrad', (16, 256), True),
+        ('value_head_pgrad', (256, 256), True),
+        ('value_head_pgrad', (32, 256), True),
+    ],
+    'td_loss': [
+        # (op, B, extra)
+        ('td_loss', 128, True),
+    ],
+    'edm_step_bwd': [
+        # (op, z, g_sample, g_mean)
+        ('edm_step_bwd', (16, 3, 64, 64), True, True),
     ],
 }
 
@@ -435,17 +669,52 @@ def test_table_reaches_every_wgrad_family(ops):
     assert fam_all == ALL_FAMILIES, fam_all
 
 
+import backward_census  # noqa: E402
+
+# op kinds every recording must contain (a silently empty recording fails), and the kinds of each program beyond those
+MIN_KINDS = {"wgrad", "conv2d", "stem_wgrad", "linear_bwd", "colsum", "silu_bwd", "dropout", "linear", "pool_act"}
+PROGRAM_KINDS = {
+    "imagenet64": {"attention_bwd", "groupnorm_generic_bwd", "pool_act_bwd", "value_head_bwd", "value_head_pgrad", "edm_step_bwd",
+                   "upsample2x"},
+    "cifar10": {"attention_bwd", "groupnorm_silu_bwd", "pool_act_bwd", "value_head_bwd", "value_head_pgrad", "var_step_bwd", "td_loss"},
+    "edm_dsm_b16": {"attention_bwd", "groupnorm_generic_bwd", "edm_dsm_loss_bwd", "upsample2x"},
+    "edm_dsm_b32": {"attention_bwd", "groupnorm_generic_bwd", "edm_dsm_loss_bwd", "upsample2x"},
+}
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("which", ["imagenet64", "cifar10"])
+@pytest.mark.parametrize("which", sorted(backward_census.PROGRAMS))
 def test_census_is_covered(ops, which):
-    import backward_census
     ops.device_check()
-    rows = backward_census.record(ops, which)
+    rows, unknown = backward_census.record(ops, which)
+    assert not unknown, f"{which}: ops functions called inside a backward that are neither launch ops nor allowed: {unknown}"
     table = {r for v in CASES.values() for r in v if not isinstance(r, str)}
     missing = sorted(rows - table, key=repr)
     assert not missing, f"{which}: backward launches not in CASES (add them): {missing}"
-    assert {r[0] for r in rows} >= {"wgrad", "conv2d", "stem_wgrad", "linear_bwd", "attention_bwd", "colsum", "pool_act_bwd"}
+    need = (MIN_KINDS - ({"dropout"} if which == "imagenet64" else set())) | PROGRAM_KINDS[which]      # imagenet64_T10 has dropout 0
+    assert {r[0] for r in rows} >= need, need - {r[0] for r in rows}
     torch.cuda.empty_cache()
+
+
+def test_census_lists_are_consistent(ops):
+    """Host-side: the launch ops, the allow-list and the class list of the censuses name only things `ops` has, and an op is
+    recorded or allowed, not both.  (Functions on none of the lists are refused at run time, when a program calls them.)"""
+    import forward_census
+    fns = set(backward_census.public_functions(ops))
+    launch, allowed = set(backward_census.OPS), set(backward_census.ALLOWED)
+    fwd = set(forward_census.FWD_OPS + forward_census.STEP_OPS)
+    assert launch <= fns and allowed <= fns and fwd <= fns, sorted((launch | allowed | fwd) - fns)
+    assert not (launch & allowed) and not (fwd & allowed)
+    assert not backward_census.unknown_classes(ops)
+    assert set(backward_census._NEW) <= launch
+
+
+def test_every_row_kind_has_a_test():
+    """Host-side: the op kinds of CASES are exactly the kinds some test of this file parametrises over."""
+    import re
+    src = open(__file__).read()
+    tested = set(re.findall(r'CASES\["([a-z0-9_]+)"\]', src))
+    assert set(CASES) == tested, set(CASES) ^ tested
 
 
 # ------------------------------------------------------------------------------------------ weight gradients
@@ -709,6 +978,179 @@ def test_attention_bwd(ops, r):
     rb = 128 if T >= 128 else T
     blk = lambda d: d.reshape(N, T // rb, rb, 3, heads, D).permute(0, 3, 4, 1, 2, 5)
     CHECK.blocks(f"attention_bwd[T{T},h{heads}{',lse' if with_lse else ''}]", blk(got), blk(ref), 8 * U16, 4)
+
+
+# ------------------------------------------------------------------------------------------ the ops outside the first ten
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["silu_bwd"], ids=_id)
+def test_silu_bwd(ops, r):
+    """g * s (1 + x (1 - s)) in fp64 on the same fp32 inputs (pre-activations of the embedding MLP, a few units wide)."""
+    _, shape, dt_pre, dt_g = r
+    assert dt_pre == dt_g == "float32"
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    pre, gy = rnd(g, *shape, scale=3.0), rnd(g, *shape)
+    got = ops.silu_bwd(pre, gy)
+    assert got.dtype == torch.float32
+    ref, A = silu_bwd_ref(pre, gy)
+    CHECK.fp32("silu_bwd", got, ref, A, 16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["dropout"], ids=_id)
+def test_dropout_and_its_backward_replay(ops, r):
+    """The kept set is bit-equal to the hash restatement, kept values are bf16(x / (1 - p)) of the fp64 quotient, the same seed
+    on a second tensor (the gradient: the backward's replay, written in place as the nets do) keeps the same elements, and the
+    next site of the step (dropout_site_seed(base, 1)) draws another mask."""
+    _, shape, p, on_dev = r
+    assert not on_dev
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    x, gy = bf(rnd(g, *shape)), bf(rnd(g, *shape))
+    seed0, seed1 = ops.dropout_site_seed(1234, 0), ops.dropout_site_seed(1234, 1)
+    y = ops.dropout(x, p, seed0)
+    keep, ref, tie = dropout_ref(x, p, seed0)
+    assert torch.equal((y != 0) | (x == 0), keep | (x == 0)), "kept set differs from the hash"
+    bad = (y != ref) & ~tie
+    assert not bool(bad.any()), f"{int(bad.sum())} kept values differ from bf16(x / (1 - p))"
+    near = (y.double() - ref.double()).abs() <= 2 * U16 * ref.double().abs()
+    assert bool(near.all())
+    dgy = gy.clone()
+    ops.dropout(dgy, p, seed0, out=dgy)
+    _, gref, gtie = dropout_ref(gy, p, seed0)
+    assert not bool(((dgy != gref) & ~gtie).any()), "the backward replay of the seed keeps other elements / values"
+    y1 = ops.dropout(x, p, seed1)
+    same = float(((y1 != 0) == (y != 0)).double().mean())
+    assert seed0 != seed1 and same < 1 - p, f"two sites of one step share a mask (agreement {same})"
+    CHECK._note("dropout[mismatches]", 0.0)
+
+
+VALUE_HEAD_EXTRA = [("value_head_bwd", (64, 4, 4, 256)), ("value_head_bwd", (32, 4, 4, 256)), ("value_head_bwd", (512, 4, 4, 256))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["value_head_bwd"] + VALUE_HEAD_EXTRA, ids=_id)
+def test_value_head_bwd(ops, r):
+    """dfeat = relu'(feat) w dy: one fp32 product, one bf16 store; s = sum_hw relu(feat): fp32 depth HW.  The census holds the
+    pair batches of the recorded steps (2B and B); the extra rows are the pairs of the CIFAR-10 batches 256 and 32."""
+    _, fs = r
+    N, H, W, C = fs
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    feat = bf(rnd(g, *fs))
+    w, dy = rnd(g, C, scale=C ** -0.5), rnd(g, N)
+    dfeat, s = ops.value_head_bwd(feat, w, dy)
+    rdf, rs, As = value_head_bwd_ref(feat, w, dy)
+    CHECK.bf16("value_head_bwd_dfeat", dfeat, rdf, rdf.abs(), 2)
+    CHECK.fp32("value_head_bwd_s", s, rs, As, H * W + 2)
+
+
+PGRAD_EXTRA = [("value_head_pgrad", (n, 256), o) for n in (512, 256, 128, 64, 32) for o in (True, False)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", sorted(set(CASES["value_head_pgrad"]) | set(PGRAD_EXTRA), key=repr), ids=_id)
+def test_value_head_pgrad(ops, r):
+    """The four head-parameter gradients against fp64 autograd, with and without learn_out_scale, at the recorded batches and
+    the pair batches of CIFAR-10 at 256 / 128 / 32."""
+    _, (N, C), has_ow = r
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    s = rnd(g, N, C).abs() * 4
+    w, b, dy = rnd(g, C, scale=C ** -0.5), rnd(g, 1), rnd(g, N)
+    ow = rnd(g, 1, 1) if has_ow else None
+    got = ops.value_head_pgrad(s, w, b, dy, ow)
+    ref, A = value_head_pgrad_ref(s, w, b, dy, ow)
+    CHECK.fp32("value_head_pgrad", got, ref, A, N + C + 8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["td_loss"] + [("td_loss", 256, True), ("td_loss", 32, True), ("td_loss", 100, False)], ids=_id)
+def test_td_loss(ops, r):
+    from test_hip_forward_shapes import check_td_loss
+    check_td_loss(ops, CHECK, r)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["edm_dsm_loss_bwd"], ids=_id)
+def test_edm_dsm_loss_bwd(ops, r):
+    """d(model_out) of the DSM terms at the recorded batch: the fp64 expressions of
+    test_hip_edm_dsm.py::test_dsm_kernels_vs_fp64 (operands, scalings64, weights64 imported), bound derived in
+    backward_bounds.dsm_loss_bwd_ref."""
+    from test_hip_edm_dsm import operands, scalings64, weights64
+    _, shape, ws, distill, has_gm, has_gx = r
+    N, CHW = shape[0], shape[1] * shape[2] * shape[3]
+    x0, noise, F_, sig = [t.to(DEV) for t in operands(N, CHW, zlib.crc32(repr(r).encode()) % 1000)]
+    g = torch.Generator(device=DEV).manual_seed(3)
+    gm, gx = (rnd(g, N) if has_gm else None), (rnd(g, N) if has_gx else None)
+    v4 = lambda t: t.view(shape).contiguous()
+    dF = ops.edm_dsm_loss_bwd(gm, gx, v4(F_), v4(x0), v4(noise), sig, ws, distillation=distill)
+    e, Me, c_out = dsm_error_terms(F_, x0, noise, sig, scalings64(sig, distill=distill))
+    CHECK.fp32("edm_dsm_loss_bwd", dF.view(N, CHW), *dsm_loss_bwd_ref(e, Me, c_out, gm, gx, weights64(ws, sig)), 16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["var_step_bwd"], ids=_id)
+def test_var_step_bwd(ops, r):
+    """dxmi_var_step_bwd at the recorded batch, per-sample scalars all different, against fp64 autograd
+    (backward_bounds.var_step_bwd_ref)."""
+    _, shape, *has = r
+    N, CHW = shape[0], shape[1] * shape[2] * shape[3]
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    gs = [rnd(g, *shape) if h else None for h in has[:3]] + [rnd(g, N) if has[3] else None]
+    z, cm, sg = rnd(g, *shape), -rnd(g, N).abs() - 0.1, torch.exp(rnd(g, N) * 0.3 - 1.0)
+    d_eps, d_sigma = ops.var_step_bwd(*gs, z, cm, sg)
+    f = lambda t: None if t is None else t.view(N, CHW)
+    re_, rs, Ae, As = var_step_bwd_ref(f(gs[0]), f(gs[1]), f(gs[2]), gs[3], f(z), cm, sg)
+    CHECK.fp32("var_step_bwd_deps", f(d_eps), re_, Ae, 8)
+    CHECK.fp32("var_step_bwd_dsigma", d_sigma, rs, As, CHW + 8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["edm_step_bwd"], ids=_id)
+def test_edm_step_bwd(ops, r):
+    """dxmi_edm_step_bwd at the recorded batch, one sigma per sample over the whole ladder, against fp64 autograd
+    (backward_bounds.edm_step_bwd_ref)."""
+    _, shape, has_gs, has_gm = r
+    N, CHW = shape[0], shape[1] * shape[2] * shape[3]
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    gs, gm = (rnd(g, *shape) if has_gs else None), (rnd(g, *shape) if has_gm else None)
+    z = rnd(g, *shape)
+    sigma = torch.exp(torch.linspace(-6.2, 4.38, N, device=DEV))
+    sdn = sigma * (0.2 + 0.6 * torch.rand(N, generator=g, device=DEV))
+    d_out, d_up = ops.edm_step_bwd(gs, gm, z, sigma, sdn)
+    f = lambda t: None if t is None else t.view(N, CHW)
+    rF, rup, AF, Aup = edm_step_bwd_ref(f(gs), f(gm), f(z), sigma, sdn)
+    CHECK.fp32("edm_step_bwd_dF", f(d_out), rF, AF, 16)
+    CHECK.fp32("edm_step_bwd_dsigma_up", d_up, rup, Aup, CHW + 8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["linear"], ids=_id)
+def test_linear_in_backward(ops, r):
+    """The forward `linear` launches of the backward() methods: recomputed pre-activations, and the transposed-pack dx of
+    linear_bwd, which splits K (S slices: partial sums added in fp32, within the same depth-K bound)."""
+    _, P, K, M, pre, post, has_bias, form, S = r
+    g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
+    x = rnd(g, P, K)
+    W = rnd(g, M, K, scale=K ** -0.5)
+    bias = rnd(g, M, scale=0.1) if has_bias else None
+    if S > 1:
+        assert int(ops.load().dxmi_linear_splitk_slices(P, K, M)) == S
+    got = ops.linear(x, ops.pack_conv_weight(W), bias, pre_act=pre, post_act=post, splitk=S > 1)
+    ref, bound = linear_ref(x, W, bias, pre, post, depth=K + 2 + S if S > 1 else None)
+    CHECK.within(f"linear[{form},S{'>1' if S > 1 else '=1'}]", got, ref, bound)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["upsample2x"], ids=_id)
+def test_upsample2x_in_backward(ops, r):
+    x = bf(rnd(torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode())), *r[1]))
+    assert torch.equal(ops.upsample2x(x), x.repeat_interleave(2, 1).repeat_interleave(2, 2))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", CASES["pool_act"], ids=_id)
+def test_pool_act_in_backward(ops, r):
+    _, xs, pool, act = r
+    x = bf(rnd(torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode())), *xs))
+    CHECK.within("pool_act", ops.pool_act(x, pool, act), *pool_act_ref(x, pool, act))
 
 
 @pytest.mark.gpu

@@ -348,10 +348,7 @@ def test_trainloop_ema_anneal_overflow_resume(ops, tmp_path, use_fp16):
 def test_imagenet64_full_size_dsm_step(ops):
     from models.cm.karras_diffusion import KarrasDenoiser
     from models.cm.script_util import create_model_and_diffusion
-    kw = dict(image_size=64, class_cond=True, learn_sigma=False, num_channels=192, num_res_blocks=3, channel_mult="",
-              num_heads=4, num_head_channels=64, num_heads_upsample=-1, attention_resolutions="32,16,8", dropout=0.1,
-              use_checkpoint=False, use_scale_shift_norm=True, resblock_updown=True, use_fp16=True,
-              use_new_attention_order=False, weight_schedule="karras")
+    from backward_census import EDM_DSM_MODEL as kw              # the set-up the launch censuses record (dropout 0.1, fp16)
     torch.manual_seed(0)
     net, diffusion = create_model_and_diffusion(**kw)
     net = net.to(DEV).train()

@@ -1,9 +1,14 @@
 """Every forward launch of the sampling and training programs against an fp64 reference, at the shapes the programs use.
 
-CASES is the census of the forward launches (tests/forward_census.py) of the nine programs of forward_census.PROGRAMS:
+CASES is the census of the forward launches (tests/forward_census.py) of the fourteen programs of forward_census.PROGRAMS:
 CIFAR-10 generation at 256 / 32 (T=10) and 128 (T=4), CIFAR-10 training at 256 / 128 / 32 (throughput tuning), ImageNet-64
-class-conditional generation at 100, ImageNet-64 training at 16 (throughput tuning) and LSUN-256 generation at 16.
-test_census_is_covered re-records each program and fails on any launch the table lacks.  Every row is then run on seeded
+class-conditional generation at 100, ImageNet-64 training at 16 (throughput tuning), LSUN-256 generation at 16, and on the
+full-size ImageNet-64 EDM net under the default knobs: DSM training (models/cm/train_util.TrainLoop) at 16 and 32 images,
+the Karras Heun teacher sampler at 100, consistency multistep sampling (ts 0, 22, 39) at 100 and zero-shot inpainting at 14.
+The two samplers at 100 add no network row to the table: they launch what imagenet64_sample_b100 launches, and
+test_census_is_covered now guards that.  test_census_is_covered re-records each program and fails on any launch the table
+lacks and on any `ops` function called outside a backward that is neither a launch op nor on the census's allow-lists.
+test_every_row_kind_has_a_test keeps the row kinds of the table and the kinds the tests parametrise over equal.  Every row is then run on seeded
 inputs and checked element by element (attention: per 128-row block) against stock torch in float64 on the device, with the
 bounds derived in tests/forward_bounds.py; conv rows run under the tuning the census recorded and must select the kernel the
 census saw.  EXTRA rows reach the forward kernel instances no program launches, so that every conv kernel id
@@ -19,9 +24,10 @@ import zlib
 import pytest
 import torch
 
-from backward_bounds import U16, U32, groupnorm_bwd_ref
-from forward_bounds import (FwdChecker, act64, attention_ref, attn_blocks, conv_bound, conv_fwd_ref, gn_bound, gn_fused_bound,
-                            gn_ref, linear_ref, lse_bound, stats_depth, stats_ref, store_bound)
+from backward_bounds import U16, U32, dropout_ref, groupnorm_bwd_ref, td_loss_ref
+from forward_bounds import (FwdChecker, act64, attention_ref, attn_blocks, conv_bound, conv_fwd_ref, dsm_error_terms,
+                            dsm_loss_fwd_bound, edm_step_ref, gn_bound, gn_fused_bound, gn_ref, linear_ref, log_sigma_t, lse_bound,
+                            pool_act_ref, scaled_input_ref, stats_depth, stats_ref, store_bound, td_gather_cost_ref, var_step_ref)
 
 DEV = "cuda:0"
 CHECK = FwdChecker()
@@ -36,6 +42,9 @@ CASES = [
     ('attention', 100, 64, 768, 12, False, False, 'attention_kernel<64>'),
     ('attention', 128, 16, 256, 1, False, False, 'attention_kernel<256>'),
     ('attention', 128, 256, 256, 1, False, False, 'attention256<false>'),
+    ('attention', 14, 1024, 384, 6, False, False, 'attention64'),
+    ('attention', 14, 256, 576, 9, False, False, 'attention64'),
+    ('attention', 14, 64, 768, 12, False, False, 'attention_kernel<64>'),
     ('attention', 16, 1024, 384, 6, False, False, 'attention64'),
     ('attention', 16, 1024, 384, 6, True, True, 'attention64'),
     ('attention', 16, 1024, 512, 8, False, False, 'attention64'),
@@ -47,8 +56,11 @@ CASES = [
     ('attention', 16, 64, 768, 12, True, True, 'attention_kernel<64>'),
     ('attention', 256, 16, 256, 1, False, False, 'attention_kernel<256>'),
     ('attention', 256, 256, 256, 1, False, False, 'attention256<false>'),
+    ('attention', 32, 1024, 384, 6, True, True, 'attention64'),
     ('attention', 32, 16, 256, 1, False, False, 'attention_kernel<256>'),
     ('attention', 32, 256, 256, 1, False, False, 'attention256<false>'),
+    ('attention', 32, 256, 576, 9, True, True, 'attention64'),
+    ('attention', 32, 64, 768, 12, True, True, 'attention_kernel<64>'),
     ('attn_block', (128, 16, 16, 256), 2, True),
     ('attn_block', (256, 16, 16, 256), 2, True),
     ('attn_block', (32, 16, 16, 256), 2, True),
@@ -56,12 +68,24 @@ CASES = [
     ('block_stats', (100, 16, 16, 576), 1),
     ('block_stats', (100, 32, 32, 384), 4),
     ('block_stats', (100, 64, 64, 192), 16),
+    ('block_stats', (14, 16, 16, 576), 1),
+    ('block_stats', (14, 32, 32, 384), 4),
+    ('block_stats', (14, 64, 64, 192), 16),
     ('block_stats', (16, 16, 16, 1024), 1),
     ('block_stats', (16, 16, 16, 576), 1),
     ('block_stats', (16, 256, 256, 256), 256),
     ('block_stats', (16, 32, 32, 384), 4),
     ('block_stats', (16, 32, 32, 512), 4),
     ('block_stats', (16, 64, 64, 192), 16),
+    ('block_stats', (32, 16, 16, 576), 1),
+    ('block_stats', (32, 32, 32, 384), 4),
+    ('block_stats', (32, 64, 64, 192), 16),
+    ('cm_stage', 0, 0, False, (100, 3, 64, 64), ('x_in', 't')),
+    ('cm_stage', 0, 0, False, (14, 3, 64, 64), ('x_in', 't')),
+    ('cm_stage', 1, 0, False, (100, 3, 64, 64), ('model_out', 'noise', 'x_in', 't')),
+    ('cm_stage', 1, 0, True, (100, 3, 64, 64), ('model_out', 'noise', 'out')),
+    ('cm_stage', 1, 1, False, (14, 3, 64, 64), ('model_out', 'noise', 'ref', 'mask', 'x_in', 't')),
+    ('cm_stage', 1, 1, True, (14, 3, 64, 64), ('model_out', 'noise', 'ref', 'mask', 'out')),
     ('conv2d', (100, 16, 16, 1152), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (100, 16, 16, 1344), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (100, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
@@ -189,6 +213,60 @@ CASES = [
     ('conv2d', (128, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, (32, True, False, False), 0, 0, 'throughput', 450864),
     ('conv2d', (128, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, (32, True, False, True), 0, 0, 'default', 400008),
     ('conv2d', (128, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 450864),
+    ('conv2d', (14, 16, 16, 1152), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 1344), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 384), 0, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 16, 16, 384), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 576), 0, 1728, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 16, 16, 576), 0, 576, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 16, 16, 576), 384, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 16, 16, 576), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 16, 16, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 16, 16, 768), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 16, 16, 960), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 3, 64, 64), 0, 192, 3, True, 1, 1, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 300000),
+    ('conv2d', (14, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 192), 0, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 32, 32, 192), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 384), 0, 1152, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550060),
+    ('conv2d', (14, 32, 32, 384), 0, 384, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (14, 32, 32, 384), 192, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 32, 32, 384), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 32, 32, 576), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 576), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 32, 32, 768), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 32, 32, 960), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (14, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (14, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (14, 64, 64, 192), 0, 3, 3, False, 1, 1, None, 0, True, '-', False, False, 0, True, False, None, 0, 0, 'default', 1206),
+    ('conv2d', (14, 64, 64, 192), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550060),
+    ('conv2d', (14, 64, 64, 384), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (14, 64, 64, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (14, 64, 64, 384), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550090),
+    ('conv2d', (14, 64, 64, 576), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (14, 8, 8, 1344), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (14, 8, 8, 1536), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (14, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (14, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (14, 8, 8, 576), 0, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 8, 8, 576), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (14, 8, 8, 768), 0, 2304, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 8, 8, 768), 0, 768, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (14, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (14, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (14, 8, 8, 768), 576, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (14, 8, 8, 768), 768, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 128, 128, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 4, 'default', 400032),
     ('conv2d', (16, 128, 128, 256), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 4, 'default', 400032),
     ('conv2d', (16, 128, 128, 256), 0, 256, 3, False, 1, 1, None, 1, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
@@ -205,31 +283,47 @@ CASES = [
     ('conv2d', (16, 16, 16, 1024), 1024, 1024, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 1024), 512, 1024, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 1152), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 1152), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 1344), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 1344), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 1536), 0, 1024, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 2048), 0, 1024, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 256), 0, 256, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (16, 16, 16, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 30206),
     ('conv2d', (16, 16, 16, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 30206),
     ('conv2d', (16, 16, 16, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 1, False, False, None, 0, 0, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 4, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 4, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 384), 0, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 384), 0, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (16, 16, 16, 384), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 384), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 512), 0, 1024, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 512), 0, 1024, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 512), 0, 512, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 512), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (16, 16, 16, 576), 0, 1728, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550090),
     ('conv2d', (16, 16, 16, 576), 0, 1728, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 550090),
+    ('conv2d', (16, 16, 16, 576), 0, 576, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 576), 0, 576, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (16, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (16, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 16, 16, 576), 384, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 576), 384, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 16, 16, 576), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 576), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 16, 16, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 16, 16, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'throughput', 400016),
+    ('conv2d', (16, 16, 16, 768), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 16, 16, 768), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (16, 16, 16, 960), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 30206),
+    ('conv2d', (16, 16, 16, 960), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 256, 256, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 256, 256, 256), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 256, 256, 256), 0, 3, 3, False, 1, 1, None, 0, True, '-', False, False, 0, True, False, None, 0, 0, 'default', 1206),
@@ -237,6 +331,7 @@ CASES = [
     ('conv2d', (16, 256, 256, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 3, 256, 256), 0, 256, 3, True, 1, 1, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 300000),
     ('conv2d', (16, 3, 64, 64), 0, 128, 3, True, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 300000),
+    ('conv2d', (16, 3, 64, 64), 0, 192, 3, True, 1, 1, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 300000),
     ('conv2d', (16, 3, 64, 64), 0, 192, 3, True, 1, 1, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 300000),
     ('conv2d', (16, 32, 32, 1024), 0, 1024, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 1024), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 8, 'default', 400032),
@@ -246,17 +341,28 @@ CASES = [
     ('conv2d', (16, 32, 32, 128), 0, 256, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (16, 32, 32, 128), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (16, 32, 32, 1536), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (16, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 192), 0, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 32, 32, 192), 0, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 32, 32, 192), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 192), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'throughput', 400032),
     ('conv2d', (16, 32, 32, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 384), 0, 1152, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550060),
     ('conv2d', (16, 32, 32, 384), 0, 1152, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 550060),
+    ('conv2d', (16, 32, 32, 384), 0, 384, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 550061),
     ('conv2d', (16, 32, 32, 384), 0, 384, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 550061),
+    ('conv2d', (16, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 1, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 384), 192, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550090),
     ('conv2d', (16, 32, 32, 384), 192, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 550090),
+    ('conv2d', (16, 32, 32, 384), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 32, 32, 384), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (16, 32, 32, 512), 0, 1536, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550080),
     ('conv2d', (16, 32, 32, 512), 0, 512, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 550081),
@@ -264,31 +370,44 @@ CASES = [
     ('conv2d', (16, 32, 32, 512), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 512), 0, 512, 3, False, 1, 1, None, 1, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 32, 32, 512), 512, 512, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (16, 32, 32, 576), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 576), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 576), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 32, 32, 576), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 32, 32, 768), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 768), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'throughput', 400032),
+    ('conv2d', (16, 32, 32, 960), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (16, 32, 32, 960), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'throughput', 400032),
     ('conv2d', (16, 64, 64, 1024), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 128), 0, 128, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 501030),
     ('conv2d', (16, 64, 64, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (16, 64, 64, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 400032),
+    ('conv2d', (16, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'throughput', 400032),
+    ('conv2d', (16, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'throughput', 400032),
+    ('conv2d', (16, 64, 64, 192), 0, 3, 3, False, 1, 1, None, 0, True, '-', False, False, 0, True, False, None, 0, 0, 'default', 1206),
     ('conv2d', (16, 64, 64, 192), 0, 3, 3, False, 1, 1, None, 0, True, '-', False, False, 0, True, False, None, 0, 0, 'throughput', 1206),
+    ('conv2d', (16, 64, 64, 192), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550060),
     ('conv2d', (16, 64, 64, 192), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 550060),
     ('conv2d', (16, 64, 64, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 256), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 256), 0, 512, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 502030),
     ('conv2d', (16, 64, 64, 256), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (16, 64, 64, 384), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 384), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'throughput', 400032),
+    ('conv2d', (16, 64, 64, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'throughput', 400032),
+    ('conv2d', (16, 64, 64, 384), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550090),
     ('conv2d', (16, 64, 64, 384), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 550090),
     ('conv2d', (16, 64, 64, 512), 0, 512, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 512), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 512), 0, 512, 3, False, 1, 1, None, 1, True, 'image', False, False, 0, False, True, None, 0, 4, 'default', 400032),
     ('conv2d', (16, 64, 64, 512), 256, 512, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 64, 64, 512), 512, 512, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (16, 64, 64, 576), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 64, 64, 576), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'throughput', 400032),
     ('conv2d', (16, 64, 64, 768), 0, 512, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 1, 'default', 400032),
     ('conv2d', (16, 8, 8, 1024), 0, 1024, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
@@ -297,21 +416,34 @@ CASES = [
     ('conv2d', (16, 8, 8, 1024), 0, 1024, 3, False, 1, 1, None, 1, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 8, 8, 1024), 0, 3072, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 8, 8, 1024), 1024, 1024, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (16, 8, 8, 1344), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (16, 8, 8, 1344), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (16, 8, 8, 1536), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (16, 8, 8, 1536), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 450832),
     ('conv2d', (16, 8, 8, 2048), 0, 1024, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 0, 'default', 450832),
     ('conv2d', (16, 8, 8, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 450832),
     ('conv2d', (16, 8, 8, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 1, False, False, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (16, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (16, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (16, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (16, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (16, 8, 8, 576), 0, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 8, 8, 576), 0, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 8, 8, 576), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (16, 8, 8, 576), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (16, 8, 8, 768), 0, 2304, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 8, 8, 768), 0, 2304, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 8, 8, 768), 0, 768, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 8, 8, 768), 0, 768, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (16, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (16, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (16, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (16, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (16, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 2, 'throughput', 400016),
+    ('conv2d', (16, 8, 8, 768), 576, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 8, 8, 768), 576, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
+    ('conv2d', (16, 8, 8, 768), 768, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (16, 8, 8, 768), 768, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (256, 16, 16, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 400016),
     ('conv2d', (256, 16, 16, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', True, False, 1, False, False, None, 0, 0, 'throughput', 400016),
@@ -382,6 +514,7 @@ CASES = [
     ('conv2d', (256, 8, 8, 256), 256, 256, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (256, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, (32, True, False, True), 0, 0, 'default', 400008),
     ('conv2d', (256, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 400008),
+    ('conv2d', (32, 16, 16, 1152), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (32, 16, 16, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 30206),
     ('conv2d', (32, 16, 16, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', True, False, 1, False, False, None, 0, 0, 'throughput', 30206),
     ('conv2d', (32, 16, 16, 128), 0, 256, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
@@ -390,6 +523,7 @@ CASES = [
     ('conv2d', (32, 16, 16, 128), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 30206),
     ('conv2d', (32, 16, 16, 128), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (32, 16, 16, 128), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 4, 'throughput', 30206),
+    ('conv2d', (32, 16, 16, 1344), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (32, 16, 16, 256), 0, 256, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (32, 16, 16, 256), 0, 256, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (32, 16, 16, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 30206),
@@ -410,13 +544,28 @@ CASES = [
     ('conv2d', (32, 16, 16, 384), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 30206),
     ('conv2d', (32, 16, 16, 384), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (32, 16, 16, 384), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 4, 'throughput', 30206),
+    ('conv2d', (32, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (32, 16, 16, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (32, 16, 16, 384), 0, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 16, 16, 384), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (32, 16, 16, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 30206),
     ('conv2d', (32, 16, 16, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (32, 16, 16, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 4, 'throughput', 30206),
+    ('conv2d', (32, 16, 16, 576), 0, 1728, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550090),
+    ('conv2d', (32, 16, 16, 576), 0, 576, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (32, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (32, 16, 16, 576), 0, 576, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 16, 16, 576), 384, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 16, 16, 576), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 16, 16, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (32, 16, 16, 768), 576, 576, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 16, 16, 960), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
     ('conv2d', (32, 3, 32, 32), 0, 128, 3, True, 1, 1, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 300000),
     ('conv2d', (32, 3, 32, 32), 0, 128, 3, True, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 300000),
     ('conv2d', (32, 3, 32, 32), 0, 128, 3, True, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 300000),
     ('conv2d', (32, 3, 64, 64), 0, 128, 3, True, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 300000),
+    ('conv2d', (32, 3, 64, 64), 0, 192, 3, True, 1, 1, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 300000),
     ('conv2d', (32, 32, 32, 128), 0, 128, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 501030),
     ('conv2d', (32, 32, 32, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (32, 32, 32, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 400032),
@@ -430,12 +579,28 @@ CASES = [
     ('conv2d', (32, 32, 32, 128), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (32, 32, 32, 128), 0, 3, 3, False, 1, 1, None, 0, True, '-', False, False, 0, True, False, None, 0, 0, 'default', 600000),
     ('conv2d', (32, 32, 32, 128), 128, 128, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 502030),
+    ('conv2d', (32, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 192), 0, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 32, 32, 192), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (32, 32, 32, 256), 0, 128, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (32, 32, 32, 256), 0, 128, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (32, 32, 32, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (32, 32, 32, 256), 128, 128, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 503030),
+    ('conv2d', (32, 32, 32, 384), 0, 1152, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 503030),
     ('conv2d', (32, 32, 32, 384), 0, 128, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (32, 32, 32, 384), 0, 128, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 384), 0, 384, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 503031),
+    ('conv2d', (32, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 384), 0, 384, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (32, 32, 32, 384), 192, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550090),
+    ('conv2d', (32, 32, 32, 384), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 32, 32, 576), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 576), 384, 384, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 32, 32, 768), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
+    ('conv2d', (32, 32, 32, 960), 0, 384, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 8, 'default', 400032),
     ('conv2d', (32, 4, 4, 256), 0, 256, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (32, 4, 4, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 450432),
     ('conv2d', (32, 4, 4, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, (32, False, True, True), 0, 0, 'default', 450432),
@@ -453,6 +618,16 @@ CASES = [
     ('conv2d', (32, 64, 64, 128), 0, 128, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 501030),
     ('conv2d', (32, 64, 64, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 400032),
     ('conv2d', (32, 64, 64, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 400032),
+    ('conv2d', (32, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (32, 64, 64, 192), 0, 192, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (32, 64, 64, 192), 0, 3, 3, False, 1, 1, None, 0, True, '-', False, False, 0, True, False, None, 0, 0, 'default', 1206),
+    ('conv2d', (32, 64, 64, 192), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550060),
+    ('conv2d', (32, 64, 64, 384), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (32, 64, 64, 384), 0, 384, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (32, 64, 64, 384), 192, 192, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 550090),
+    ('conv2d', (32, 64, 64, 576), 0, 192, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 1, 'default', 400032),
+    ('conv2d', (32, 8, 8, 1344), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (32, 8, 8, 1536), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
     ('conv2d', (32, 8, 8, 256), 0, 256, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 200000),
     ('conv2d', (32, 8, 8, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 450832),
     ('conv2d', (32, 8, 8, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, (32, True, True, False), 0, 0, 'default', 400008),
@@ -472,6 +647,17 @@ CASES = [
     ('conv2d', (32, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, (32, True, False, False), 0, 0, 'throughput', 450832),
     ('conv2d', (32, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, (32, True, False, True), 0, 0, 'default', 400008),
     ('conv2d', (32, 8, 8, 512), 0, 256, 3, False, 1, 1, None, 0, True, 'image', False, False, 0, False, False, None, 0, 0, 'throughput', 450832),
+    ('conv2d', (32, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (32, 8, 8, 576), 0, 576, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (32, 8, 8, 576), 0, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 8, 8, 576), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (32, 8, 8, 768), 0, 2304, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 8, 8, 768), 0, 768, 1, False, 1, 0, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', False, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (32, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, True, None, 0, 0, 'default', 400008),
+    ('conv2d', (32, 8, 8, 768), 0, 768, 3, False, 1, 1, None, 1, True, '-', False, False, 0, False, True, None, 0, 2, 'default', 400016),
+    ('conv2d', (32, 8, 8, 768), 576, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
+    ('conv2d', (32, 8, 8, 768), 768, 768, 1, False, 1, 0, None, 0, True, '-', False, False, 0, False, False, None, 0, 0, 'default', 200000),
     ('conv2d', (512, 16, 16, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 400016),
     ('conv2d', (512, 16, 16, 128), 0, 128, 3, False, 1, 1, None, 0, True, '-', True, False, 1, False, False, None, 0, 0, 'throughput', 400016),
     ('conv2d', (512, 16, 16, 128), 0, 256, 1, False, 1, 0, None, 0, False, '-', False, False, 0, False, False, None, 0, 0, 'throughput', 501030),
@@ -502,9 +688,54 @@ CASES = [
     ('conv2d', (64, 8, 8, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', False, False, 1, False, False, None, 0, 0, 'throughput', 450832),
     ('conv2d', (64, 8, 8, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 0, False, False, None, 0, 0, 'throughput', 450832),
     ('conv2d', (64, 8, 8, 256), 0, 256, 3, False, 1, 1, None, 0, True, '-', True, False, 1, False, False, None, 0, 0, 'throughput', 450832),
+    ('dropout', (128, 16, 16, 256), 0.1, False),
+    ('dropout', (128, 32, 32, 128), 0.1, False),
+    ('dropout', (128, 4, 4, 256), 0.1, False),
+    ('dropout', (128, 8, 8, 256), 0.1, False),
+    ('dropout', (16, 16, 16, 384), 0.1, False),
+    ('dropout', (16, 16, 16, 576), 0.1, False),
+    ('dropout', (16, 16, 16, 768), 0.1, False),
+    ('dropout', (16, 32, 32, 192), 0.1, False),
+    ('dropout', (16, 32, 32, 384), 0.1, False),
+    ('dropout', (16, 32, 32, 576), 0.1, False),
+    ('dropout', (16, 64, 64, 192), 0.1, False),
+    ('dropout', (16, 64, 64, 384), 0.1, False),
+    ('dropout', (16, 8, 8, 576), 0.1, False),
+    ('dropout', (16, 8, 8, 768), 0.1, False),
+    ('dropout', (256, 16, 16, 256), 0.1, False),
+    ('dropout', (256, 32, 32, 128), 0.1, False),
+    ('dropout', (256, 4, 4, 256), 0.1, False),
+    ('dropout', (256, 8, 8, 256), 0.1, False),
+    ('dropout', (32, 16, 16, 256), 0.1, False),
+    ('dropout', (32, 16, 16, 384), 0.1, False),
+    ('dropout', (32, 16, 16, 576), 0.1, False),
+    ('dropout', (32, 16, 16, 768), 0.1, False),
+    ('dropout', (32, 32, 32, 128), 0.1, False),
+    ('dropout', (32, 32, 32, 192), 0.1, False),
+    ('dropout', (32, 32, 32, 384), 0.1, False),
+    ('dropout', (32, 32, 32, 576), 0.1, False),
+    ('dropout', (32, 4, 4, 256), 0.1, False),
+    ('dropout', (32, 64, 64, 192), 0.1, False),
+    ('dropout', (32, 64, 64, 384), 0.1, False),
+    ('dropout', (32, 8, 8, 256), 0.1, False),
+    ('dropout', (32, 8, 8, 576), 0.1, False),
+    ('dropout', (32, 8, 8, 768), 0.1, False),
+    ('edm_dsm_loss_fwd', (16, 3, 64, 64), 'karras', False),
+    ('edm_dsm_loss_fwd', (32, 3, 64, 64), 'karras', False),
+    ('edm_dsm_prep', (16, 3, 64, 64)),
+    ('edm_dsm_prep', (32, 3, 64, 64)),
+    ('edm_precond', (100, 3, 64, 64)),
+    ('edm_precond', (16, 3, 256, 256)),
+    ('edm_precond', (16, 3, 64, 64)),
+    ('edm_step', (100, 3, 64, 64)),
+    ('edm_step', (16, 3, 256, 256)),
+    ('edm_step', (16, 3, 64, 64)),
     ('fold_stats', 100, 16, 192, 32),
     ('fold_stats', 100, 32, 192, 32),
     ('fold_stats', 100, 32, 384, 32),
+    ('fold_stats', 14, 16, 192, 32),
+    ('fold_stats', 14, 32, 192, 32),
+    ('fold_stats', 14, 32, 384, 32),
     ('fold_stats', 16, 128, 256, 32),
     ('fold_stats', 16, 128, 512, 32),
     ('fold_stats', 16, 16, 192, 32),
@@ -514,6 +745,9 @@ CASES = [
     ('fold_stats', 16, 32, 384, 32),
     ('fold_stats', 16, 32, 512, 32),
     ('fold_stats', 16, 512, 256, 32),
+    ('fold_stats', 32, 16, 192, 32),
+    ('fold_stats', 32, 32, 192, 32),
+    ('fold_stats', 32, 32, 384, 32),
     ('gn', 'apply', (100, 16, 16, 384), 0, 32, 1e-05, True, False, False, 2, 0),
     ('gn', 'apply', (100, 16, 16, 384), 0, 32, 1e-05, True, True, False, 2, 0),
     ('gn', 'apply', (100, 16, 16, 576), 0, 32, 1e-05, False, False, False, 2, 0),
@@ -547,6 +781,29 @@ CASES = [
     ('gn', 'apply', (128, 32, 32, 128), 128, 32, 1e-06, True, False, False, 8, 8),
     ('gn', 'apply', (128, 32, 32, 256), 128, 32, 1e-06, True, False, False, 8, 8),
     ('gn', 'apply', (128, 8, 8, 256), 0, 32, 1e-06, True, False, False, 1, 0),
+    ('gn', 'apply', (14, 16, 16, 384), 0, 32, 1e-05, True, False, False, 2, 0),
+    ('gn', 'apply', (14, 16, 16, 384), 0, 32, 1e-05, True, True, False, 2, 0),
+    ('gn', 'apply', (14, 16, 16, 576), 0, 32, 1e-05, False, False, False, 2, 0),
+    ('gn', 'apply', (14, 16, 16, 576), 0, 32, 1e-05, True, False, False, 1, 0),
+    ('gn', 'apply', (14, 16, 16, 576), 0, 32, 1e-05, True, True, False, 2, 0),
+    ('gn', 'apply', (14, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 2),
+    ('gn', 'apply', (14, 16, 16, 576), 576, 32, 1e-05, True, False, False, 1, 1),
+    ('gn', 'apply', (14, 16, 16, 768), 0, 32, 1e-05, True, True, False, 2, 0),
+    ('gn', 'apply', (14, 16, 16, 768), 576, 32, 1e-05, True, False, False, 2, 1),
+    ('gn', 'apply', (14, 32, 32, 192), 0, 32, 1e-05, True, False, False, 8, 0),
+    ('gn', 'apply', (14, 32, 32, 192), 0, 32, 1e-05, True, True, False, 8, 0),
+    ('gn', 'apply', (14, 32, 32, 384), 0, 32, 1e-05, False, False, False, 8, 0),
+    ('gn', 'apply', (14, 32, 32, 384), 0, 32, 1e-05, True, False, False, 4, 0),
+    ('gn', 'apply', (14, 32, 32, 384), 0, 32, 1e-05, True, True, False, 8, 0),
+    ('gn', 'apply', (14, 32, 32, 384), 192, 32, 1e-05, True, False, False, 4, 8),
+    ('gn', 'apply', (14, 32, 32, 384), 384, 32, 1e-05, True, False, False, 4, 4),
+    ('gn', 'apply', (14, 32, 32, 576), 0, 32, 1e-05, True, True, False, 8, 0),
+    ('gn', 'apply', (14, 32, 32, 576), 384, 32, 1e-05, True, False, False, 8, 4),
+    ('gn', 'apply', (14, 64, 64, 192), 0, 32, 1e-05, True, False, False, 1, 0),
+    ('gn', 'apply', (14, 64, 64, 192), 0, 32, 1e-05, True, True, False, 1, 0),
+    ('gn', 'apply', (14, 64, 64, 192), 192, 32, 1e-05, True, False, False, 1, 1),
+    ('gn', 'apply', (14, 64, 64, 384), 0, 32, 1e-05, True, True, False, 1, 0),
+    ('gn', 'apply', (14, 64, 64, 384), 192, 32, 1e-05, True, False, False, 1, 1),
     ('gn', 'apply', (16, 128, 128, 256), 0, 32, 1e-05, True, False, False, 4, 0),
     ('gn', 'apply', (16, 128, 128, 256), 256, 32, 1e-05, True, False, False, 4, 4),
     ('gn', 'apply', (16, 128, 128, 512), 0, 32, 1e-05, True, False, False, 4, 0),
@@ -557,11 +814,16 @@ CASES = [
     ('gn', 'apply', (16, 16, 16, 1024), 1024, 32, 1e-05, True, False, False, 1, 1),
     ('gn', 'apply', (16, 16, 16, 1024), 1024, 32, 1e-05, True, False, False, 2, 1),
     ('gn', 'apply', (16, 16, 16, 1024), 512, 32, 1e-05, True, False, False, 1, 2),
+    ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, False, False, 2, 0),
     ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, False, False, 4, 0),
+    ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, True, False, 2, 0),
     ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, True, False, 4, 0),
     ('gn', 'apply', (16, 16, 16, 512), 0, 32, 1e-05, True, False, False, 2, 0),
     ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, False, False, False, 1, 0),
+    ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, False, False, False, 2, 0),
     ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, True, False, False, 1, 0),
+    ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, True, True, False, 2, 0),
+    ('gn', 'apply', (16, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 2),
     ('gn', 'apply', (16, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 4),
     ('gn', 'apply', (16, 16, 16, 576), 576, 32, 1e-05, True, False, False, 1, 1),
     ('gn', 'apply', (16, 16, 16, 768), 0, 32, 1e-05, True, True, False, 2, 0),
@@ -613,14 +875,41 @@ CASES = [
     ('gn', 'apply', (32, 16, 16, 256), 256, 32, 1e-06, True, False, False, 2, 8),
     ('gn', 'apply', (32, 16, 16, 256), 256, 32, 1e-06, True, False, False, 4, 8),
     ('gn', 'apply', (32, 16, 16, 256), 256, 32, 1e-06, True, False, False, 8, 8),
+    ('gn', 'apply', (32, 16, 16, 384), 0, 32, 1e-05, True, False, False, 2, 0),
+    ('gn', 'apply', (32, 16, 16, 384), 0, 32, 1e-05, True, True, False, 2, 0),
+    ('gn', 'apply', (32, 16, 16, 576), 0, 32, 1e-05, False, False, False, 2, 0),
+    ('gn', 'apply', (32, 16, 16, 576), 0, 32, 1e-05, True, False, False, 1, 0),
+    ('gn', 'apply', (32, 16, 16, 576), 0, 32, 1e-05, True, True, False, 2, 0),
+    ('gn', 'apply', (32, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 2),
+    ('gn', 'apply', (32, 16, 16, 576), 576, 32, 1e-05, True, False, False, 1, 1),
+    ('gn', 'apply', (32, 16, 16, 768), 0, 32, 1e-05, True, True, False, 2, 0),
+    ('gn', 'apply', (32, 16, 16, 768), 576, 32, 1e-05, True, False, False, 2, 1),
     ('gn', 'apply', (32, 32, 32, 128), 0, 32, 1e-06, True, False, False, 8, 0),
     ('gn', 'apply', (32, 32, 32, 128), 128, 32, 1e-06, True, False, False, 8, 8),
+    ('gn', 'apply', (32, 32, 32, 192), 0, 32, 1e-05, True, False, False, 8, 0),
+    ('gn', 'apply', (32, 32, 32, 192), 0, 32, 1e-05, True, True, False, 8, 0),
     ('gn', 'apply', (32, 32, 32, 256), 128, 32, 1e-06, True, False, False, 8, 8),
+    ('gn', 'apply', (32, 32, 32, 384), 0, 32, 1e-05, False, False, False, 8, 0),
+    ('gn', 'apply', (32, 32, 32, 384), 0, 32, 1e-05, True, False, False, 4, 0),
+    ('gn', 'apply', (32, 32, 32, 384), 0, 32, 1e-05, True, True, False, 8, 0),
+    ('gn', 'apply', (32, 32, 32, 384), 192, 32, 1e-05, True, False, False, 4, 8),
+    ('gn', 'apply', (32, 32, 32, 384), 384, 32, 1e-05, True, False, False, 4, 4),
+    ('gn', 'apply', (32, 32, 32, 576), 0, 32, 1e-05, True, True, False, 8, 0),
+    ('gn', 'apply', (32, 32, 32, 576), 384, 32, 1e-05, True, False, False, 8, 4),
+    ('gn', 'apply', (32, 64, 64, 192), 0, 32, 1e-05, True, False, False, 1, 0),
+    ('gn', 'apply', (32, 64, 64, 192), 0, 32, 1e-05, True, True, False, 1, 0),
+    ('gn', 'apply', (32, 64, 64, 192), 192, 32, 1e-05, True, False, False, 1, 1),
+    ('gn', 'apply', (32, 64, 64, 384), 0, 32, 1e-05, True, True, False, 1, 0),
+    ('gn', 'apply', (32, 64, 64, 384), 192, 32, 1e-05, True, False, False, 1, 1),
     ('gn', 'apply', (32, 8, 8, 256), 0, 32, 1e-06, True, False, False, 1, 0),
     ('gn', 'generic', (100, 8, 8, 576), 0, 32, 1e-05, True, False, False, 0, 0),
     ('gn', 'generic', (100, 8, 8, 576), 0, 32, 1e-05, True, True, False, 0, 0),
     ('gn', 'generic', (100, 8, 8, 768), 0, 32, 1e-05, True, True, False, 0, 0),
     ('gn', 'generic', (100, 8, 8, 768), 576, 32, 1e-05, True, False, False, 0, 0),
+    ('gn', 'generic', (14, 8, 8, 576), 0, 32, 1e-05, True, False, False, 0, 0),
+    ('gn', 'generic', (14, 8, 8, 576), 0, 32, 1e-05, True, True, False, 0, 0),
+    ('gn', 'generic', (14, 8, 8, 768), 0, 32, 1e-05, True, True, False, 0, 0),
+    ('gn', 'generic', (14, 8, 8, 768), 576, 32, 1e-05, True, False, False, 0, 0),
     ('gn', 'generic', (16, 16, 16, 576), 0, 32, 1e-05, True, True, False, 0, 0),
     ('gn', 'generic', (16, 16, 16, 576), 0, 32, 1e-05, True, True, True, 0, 0),
     ('gn', 'generic', (16, 8, 8, 576), 0, 32, 1e-05, True, False, False, 0, 0),
@@ -631,6 +920,10 @@ CASES = [
     ('gn', 'generic', (16, 8, 8, 768), 0, 32, 1e-05, True, True, True, 0, 0),
     ('gn', 'generic', (16, 8, 8, 768), 576, 32, 1e-05, True, False, False, 0, 0),
     ('gn', 'generic', (16, 8, 8, 768), 576, 32, 1e-05, True, False, True, 0, 0),
+    ('gn', 'generic', (32, 8, 8, 576), 0, 32, 1e-05, True, False, True, 0, 0),
+    ('gn', 'generic', (32, 8, 8, 576), 0, 32, 1e-05, True, True, True, 0, 0),
+    ('gn', 'generic', (32, 8, 8, 768), 0, 32, 1e-05, True, True, True, 0, 0),
+    ('gn', 'generic', (32, 8, 8, 768), 576, 32, 1e-05, True, False, True, 0, 0),
     ('gn', 'resident', (100, 8, 8, 768), 0, 32, 1e-05, False, False, False, 0, 0),
     ('gn', 'resident', (100, 8, 8, 768), 0, 32, 1e-05, True, False, False, 0, 0),
     ('gn', 'resident', (100, 8, 8, 768), 768, 32, 1e-05, True, False, False, 0, 0),
@@ -647,6 +940,9 @@ CASES = [
     ('gn', 'resident', (128, 4, 4, 256), 256, 32, 1e-06, True, False, False, 0, 0),
     ('gn', 'resident', (128, 8, 8, 256), 0, 32, 1e-06, True, False, False, 0, 0),
     ('gn', 'resident', (128, 8, 8, 256), 256, 32, 1e-06, True, False, False, 0, 0),
+    ('gn', 'resident', (14, 8, 8, 768), 0, 32, 1e-05, False, False, False, 0, 0),
+    ('gn', 'resident', (14, 8, 8, 768), 0, 32, 1e-05, True, False, False, 0, 0),
+    ('gn', 'resident', (14, 8, 8, 768), 768, 32, 1e-05, True, False, False, 0, 0),
     ('gn', 'resident', (16, 8, 8, 1024), 0, 32, 1e-05, False, False, False, 0, 0),
     ('gn', 'resident', (16, 8, 8, 1024), 0, 32, 1e-05, True, False, False, 0, 0),
     ('gn', 'resident', (16, 8, 8, 1024), 1024, 32, 1e-05, True, False, False, 0, 0),
@@ -679,6 +975,9 @@ CASES = [
     ('gn', 'resident', (32, 4, 4, 256), 256, 32, 1e-06, True, False, False, 0, 0),
     ('gn', 'resident', (32, 8, 8, 256), 0, 32, 1e-06, True, False, False, 0, 0),
     ('gn', 'resident', (32, 8, 8, 256), 256, 32, 1e-06, True, False, False, 0, 0),
+    ('gn', 'resident', (32, 8, 8, 768), 0, 32, 1e-05, False, False, False, 0, 0),
+    ('gn', 'resident', (32, 8, 8, 768), 0, 32, 1e-05, True, False, False, 0, 0),
+    ('gn', 'resident', (32, 8, 8, 768), 768, 32, 1e-05, True, False, False, 0, 0),
     ('gn_bs2gen', 16, 1024, 192, 0, 32, 8, 0),
     ('gn_bs2gen', 16, 1024, 384, 0, 32, 4, 0),
     ('gn_bs2gen', 16, 1024, 384, 0, 32, 8, 0),
@@ -686,8 +985,11 @@ CASES = [
     ('gn_bs2gen', 16, 1024, 384, 384, 32, 4, 4),
     ('gn_bs2gen', 16, 1024, 576, 0, 32, 8, 0),
     ('gn_bs2gen', 16, 1024, 576, 384, 32, 8, 4),
+    ('gn_bs2gen', 16, 256, 384, 0, 32, 2, 0),
     ('gn_bs2gen', 16, 256, 384, 0, 32, 4, 0),
     ('gn_bs2gen', 16, 256, 576, 0, 32, 1, 0),
+    ('gn_bs2gen', 16, 256, 576, 0, 32, 2, 0),
+    ('gn_bs2gen', 16, 256, 576, 384, 32, 1, 2),
     ('gn_bs2gen', 16, 256, 576, 384, 32, 1, 4),
     ('gn_bs2gen', 16, 256, 576, 576, 32, 1, 1),
     ('gn_bs2gen', 16, 256, 768, 0, 32, 2, 0),
@@ -696,6 +998,42 @@ CASES = [
     ('gn_bs2gen', 16, 4096, 192, 192, 32, 1, 1),
     ('gn_bs2gen', 16, 4096, 384, 0, 32, 1, 0),
     ('gn_bs2gen', 16, 4096, 384, 192, 32, 1, 1),
+    ('gn_bs2gen', 32, 1024, 192, 0, 32, 8, 0),
+    ('gn_bs2gen', 32, 1024, 384, 0, 32, 4, 0),
+    ('gn_bs2gen', 32, 1024, 384, 0, 32, 8, 0),
+    ('gn_bs2gen', 32, 1024, 384, 192, 32, 4, 8),
+    ('gn_bs2gen', 32, 1024, 384, 384, 32, 4, 4),
+    ('gn_bs2gen', 32, 1024, 576, 0, 32, 8, 0),
+    ('gn_bs2gen', 32, 1024, 576, 384, 32, 8, 4),
+    ('gn_bs2gen', 32, 256, 384, 0, 32, 2, 0),
+    ('gn_bs2gen', 32, 256, 576, 0, 32, 1, 0),
+    ('gn_bs2gen', 32, 256, 576, 0, 32, 2, 0),
+    ('gn_bs2gen', 32, 256, 576, 384, 32, 1, 2),
+    ('gn_bs2gen', 32, 256, 576, 576, 32, 1, 1),
+    ('gn_bs2gen', 32, 256, 768, 0, 32, 2, 0),
+    ('gn_bs2gen', 32, 256, 768, 576, 32, 2, 1),
+    ('gn_bs2gen', 32, 4096, 192, 0, 32, 1, 0),
+    ('gn_bs2gen', 32, 4096, 192, 192, 32, 1, 1),
+    ('gn_bs2gen', 32, 4096, 384, 0, 32, 1, 0),
+    ('gn_bs2gen', 32, 4096, 384, 192, 32, 1, 1),
+    ('gn_shortcut', (128, 16, 16, 128), 0, 256, 32, 1e-06, True, True, 4, 0),
+    ('gn_shortcut', (128, 16, 16, 256), 128, 256, 32, 1e-06, True, True, 8, 4),
+    ('gn_shortcut', (128, 16, 16, 256), 256, 256, 32, 1e-06, True, True, 2, 8),
+    ('gn_shortcut', (128, 16, 16, 256), 256, 256, 32, 1e-06, True, True, 8, 8),
+    ('gn_shortcut', (128, 32, 32, 128), 128, 128, 32, 1e-06, True, True, 8, 8),
+    ('gn_shortcut', (128, 32, 32, 256), 128, 128, 32, 1e-06, True, True, 8, 8),
+    ('gn_shortcut', (256, 16, 16, 128), 0, 256, 32, 1e-06, True, True, 4, 0),
+    ('gn_shortcut', (256, 16, 16, 256), 128, 256, 32, 1e-06, True, True, 8, 4),
+    ('gn_shortcut', (256, 16, 16, 256), 256, 256, 32, 1e-06, True, True, 2, 8),
+    ('gn_shortcut', (256, 16, 16, 256), 256, 256, 32, 1e-06, True, True, 8, 8),
+    ('gn_shortcut', (256, 32, 32, 128), 128, 128, 32, 1e-06, True, True, 8, 8),
+    ('gn_shortcut', (256, 32, 32, 256), 128, 128, 32, 1e-06, True, True, 8, 8),
+    ('gn_shortcut', (32, 32, 32, 128), 128, 128, 32, 1e-06, True, True, 8, 8),
+    ('gn_shortcut', (32, 32, 32, 256), 128, 128, 32, 1e-06, True, True, 8, 8),
+    ('karras_stage', 0, False, (100, 3, 64, 64), ('x2', 'd', 'x_in', 't')),
+    ('karras_stage', 1, False, (100, 3, 64, 64), ('x2', 'd', 'model_out', 'x_in', 't')),
+    ('karras_stage', 2, False, (100, 3, 64, 64), ('x2', 'd', 'model_out', 'x_in', 't')),
+    ('karras_stage', 4, True, (100, 3, 64, 64), ('x2', 'd', 'model_out', 'out')),
     ('linear', 10, 128, 512, 0, 3, True, 'small', 1),
     ('linear', 10, 512, 4992, 0, 0, True, 'small', 1),
     ('linear', 10, 512, 512, 0, 3, True, 'small', 1),
@@ -705,6 +1043,9 @@ CASES = [
     ('linear', 128, 128, 512, 0, 3, True, 'small', 1),
     ('linear', 128, 512, 4992, 0, 0, True, 'small', 1),
     ('linear', 128, 512, 512, 0, 3, True, 'small', 1),
+    ('linear', 14, 192, 768, 0, 3, True, 'small', 1),
+    ('linear', 14, 768, 35712, 3, 0, True, 'small', 1),
+    ('linear', 14, 768, 768, 0, 0, True, 'small', 1),
     ('linear', 16, 1024, 1024, 0, 0, True, 'small', 1),
     ('linear', 16, 1024, 25856, 3, 0, True, 'small', 1),
     ('linear', 16, 192, 768, 0, 3, True, 'small', 1),
@@ -715,8 +1056,11 @@ CASES = [
     ('linear', 256, 512, 4992, 0, 0, True, 'small', 1),
     ('linear', 256, 512, 512, 0, 3, True, 'small', 1),
     ('linear', 32, 128, 512, 0, 3, True, 'small', 1),
+    ('linear', 32, 192, 768, 0, 3, True, 'small', 1),
     ('linear', 32, 512, 4992, 0, 0, True, 'small', 1),
     ('linear', 32, 512, 512, 0, 3, True, 'small', 1),
+    ('linear', 32, 768, 35712, 3, 0, True, 'small', 1),
+    ('linear', 32, 768, 768, 0, 0, True, 'small', 1),
     ('linear', 4, 128, 512, 0, 3, True, 'small', 1),
     ('linear', 4, 512, 4992, 0, 0, True, 'small', 1),
     ('linear', 4, 512, 512, 0, 3, True, 'small', 1),
@@ -726,6 +1070,9 @@ CASES = [
     ('pool_act', (128, 16, 16, 256), True, 1),
     ('pool_act', (128, 32, 32, 128), True, 1),
     ('pool_act', (128, 8, 8, 256), True, 1),
+    ('pool_act', (14, 16, 16, 576), True, 0),
+    ('pool_act', (14, 32, 32, 384), True, 0),
+    ('pool_act', (14, 64, 64, 192), True, 0),
     ('pool_act', (16, 128, 128, 256), True, 0),
     ('pool_act', (16, 16, 16, 1024), True, 0),
     ('pool_act', (16, 16, 16, 256), True, 1),
@@ -741,9 +1088,12 @@ CASES = [
     ('pool_act', (256, 32, 32, 128), True, 1),
     ('pool_act', (256, 8, 8, 256), True, 1),
     ('pool_act', (32, 16, 16, 256), True, 1),
+    ('pool_act', (32, 16, 16, 576), True, 0),
     ('pool_act', (32, 32, 32, 128), True, 1),
     ('pool_act', (32, 32, 32, 256), True, 1),
+    ('pool_act', (32, 32, 32, 384), True, 0),
     ('pool_act', (32, 64, 64, 128), True, 1),
+    ('pool_act', (32, 64, 64, 192), True, 0),
     ('pool_act', (32, 8, 8, 256), True, 1),
     ('pool_act', (512, 16, 16, 256), True, 1),
     ('pool_act', (512, 32, 32, 128), True, 1),
@@ -751,17 +1101,28 @@ CASES = [
     ('pool_act', (64, 16, 16, 256), True, 1),
     ('pool_act', (64, 32, 32, 128), True, 1),
     ('pool_act', (64, 8, 8, 256), True, 1),
+    ('td_gather_cost', 128, 3072, ('next_rows',)),
+    ('td_gather_cost', 256, 3072, ('next_rows',)),
+    ('td_gather_cost', 32, 3072, ('next_rows',)),
+    ('td_loss', 128, True),
+    ('td_loss', 256, True),
+    ('td_loss', 32, True),
     ('timestep_embedding', 10, 128, 0, 10000.0),
     ('timestep_embedding', 100, 192, 1, 10000.0),
     ('timestep_embedding', 128, 128, 0, 10000.0),
+    ('timestep_embedding', 14, 192, 1, 10000.0),
     ('timestep_embedding', 16, 192, 1, 10000.0),
     ('timestep_embedding', 16, 256, 1, 10000.0),
     ('timestep_embedding', 256, 128, 0, 10000.0),
     ('timestep_embedding', 32, 128, 0, 10000.0),
+    ('timestep_embedding', 32, 192, 1, 10000.0),
     ('timestep_embedding', 4, 128, 0, 10000.0),
     ('upsample2x', (100, 16, 16, 576)),
     ('upsample2x', (100, 32, 32, 384)),
     ('upsample2x', (100, 8, 8, 768)),
+    ('upsample2x', (14, 16, 16, 576)),
+    ('upsample2x', (14, 32, 32, 384)),
+    ('upsample2x', (14, 8, 8, 768)),
     ('upsample2x', (16, 128, 128, 256)),
     ('upsample2x', (16, 16, 16, 1024)),
     ('upsample2x', (16, 16, 16, 576)),
@@ -770,6 +1131,9 @@ CASES = [
     ('upsample2x', (16, 64, 64, 512)),
     ('upsample2x', (16, 8, 8, 1024)),
     ('upsample2x', (16, 8, 8, 768)),
+    ('upsample2x', (32, 16, 16, 576)),
+    ('upsample2x', (32, 32, 32, 384)),
+    ('upsample2x', (32, 8, 8, 768)),
     ('value_head', (128, 4, 4, 256), True),
     ('value_head', (16, 8, 8, 256), True),
     ('value_head', (256, 4, 4, 256), True),
@@ -777,6 +1141,16 @@ CASES = [
     ('value_head', (32, 8, 8, 256), True),
     ('value_head', (512, 4, 4, 256), True),
     ('value_head', (64, 4, 4, 256), True),
+    ('var_gather_sched', 128, 10),
+    ('var_gather_sched', 128, 4),
+    ('var_gather_sched', 256, 10),
+    ('var_gather_sched', 32, 10),
+    ('var_step', (128, 3, 32, 32), True, True, 0),
+    ('var_step', (128, 3, 32, 32), True, True, 1),
+    ('var_step', (256, 3, 32, 32), True, True, 0),
+    ('var_step', (256, 3, 32, 32), True, True, 1),
+    ('var_step', (32, 3, 32, 32), True, True, 0),
+    ('var_step', (32, 3, 32, 32), True, True, 1),
 ]
 
 COND = {
@@ -813,6 +1187,29 @@ COND = {
     ('gn', 'apply', (128, 32, 32, 128), 128, 32, 1e-06, True, False, False, 8, 8): 0.499,
     ('gn', 'apply', (128, 32, 32, 256), 128, 32, 1e-06, True, False, False, 8, 8): 0.357,
     ('gn', 'apply', (128, 8, 8, 256), 0, 32, 1e-06, True, False, False, 1, 0): 0.626,
+    ('gn', 'apply', (14, 16, 16, 384), 0, 32, 1e-05, True, False, False, 2, 0): 0.727,
+    ('gn', 'apply', (14, 16, 16, 384), 0, 32, 1e-05, True, True, False, 2, 0): 1.077,
+    ('gn', 'apply', (14, 16, 16, 576), 0, 32, 1e-05, False, False, False, 2, 0): 0.702,
+    ('gn', 'apply', (14, 16, 16, 576), 0, 32, 1e-05, True, False, False, 1, 0): 0.707,
+    ('gn', 'apply', (14, 16, 16, 576), 0, 32, 1e-05, True, True, False, 2, 0): 0.817,
+    ('gn', 'apply', (14, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 2): 0.446,
+    ('gn', 'apply', (14, 16, 16, 576), 576, 32, 1e-05, True, False, False, 1, 1): 0.495,
+    ('gn', 'apply', (14, 16, 16, 768), 0, 32, 1e-05, True, True, False, 2, 0): 0.512,
+    ('gn', 'apply', (14, 16, 16, 768), 576, 32, 1e-05, True, False, False, 2, 1): 0.331,
+    ('gn', 'apply', (14, 32, 32, 192), 0, 32, 1e-05, True, False, False, 8, 0): 1.113,
+    ('gn', 'apply', (14, 32, 32, 192), 0, 32, 1e-05, True, True, False, 8, 0): 1.265,
+    ('gn', 'apply', (14, 32, 32, 384), 0, 32, 1e-05, False, False, False, 8, 0): 0.864,
+    ('gn', 'apply', (14, 32, 32, 384), 0, 32, 1e-05, True, False, False, 4, 0): 0.716,
+    ('gn', 'apply', (14, 32, 32, 384), 0, 32, 1e-05, True, True, False, 8, 0): 0.83,
+    ('gn', 'apply', (14, 32, 32, 384), 192, 32, 1e-05, True, False, False, 4, 8): 0.696,
+    ('gn', 'apply', (14, 32, 32, 384), 384, 32, 1e-05, True, False, False, 4, 4): 0.53,
+    ('gn', 'apply', (14, 32, 32, 576), 0, 32, 1e-05, True, True, False, 8, 0): 0.692,
+    ('gn', 'apply', (14, 32, 32, 576), 384, 32, 1e-05, True, False, False, 8, 4): 0.381,
+    ('gn', 'apply', (14, 64, 64, 192), 0, 32, 1e-05, True, False, False, 1, 0): 0.766,
+    ('gn', 'apply', (14, 64, 64, 192), 0, 32, 1e-05, True, True, False, 1, 0): 0.91,
+    ('gn', 'apply', (14, 64, 64, 192), 192, 32, 1e-05, True, False, False, 1, 1): 0.715,
+    ('gn', 'apply', (14, 64, 64, 384), 0, 32, 1e-05, True, True, False, 1, 0): 0.744,
+    ('gn', 'apply', (14, 64, 64, 384), 192, 32, 1e-05, True, False, False, 1, 1): 0.503,
     ('gn', 'apply', (16, 128, 128, 256), 0, 32, 1e-05, True, False, False, 4, 0): 1.083,
     ('gn', 'apply', (16, 128, 128, 256), 256, 32, 1e-05, True, False, False, 4, 4): 0.447,
     ('gn', 'apply', (16, 128, 128, 512), 0, 32, 1e-05, True, False, False, 4, 0): 0.492,
@@ -823,11 +1220,16 @@ COND = {
     ('gn', 'apply', (16, 16, 16, 1024), 1024, 32, 1e-05, True, False, False, 1, 1): 0.414,
     ('gn', 'apply', (16, 16, 16, 1024), 1024, 32, 1e-05, True, False, False, 2, 1): 0.284,
     ('gn', 'apply', (16, 16, 16, 1024), 512, 32, 1e-05, True, False, False, 1, 2): 0.425,
+    ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, False, False, 2, 0): 0.908,
     ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, False, False, 4, 0): 0.896,
+    ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, True, False, 2, 0): 0.665,
     ('gn', 'apply', (16, 16, 16, 384), 0, 32, 1e-05, True, True, False, 4, 0): 1.28,
     ('gn', 'apply', (16, 16, 16, 512), 0, 32, 1e-05, True, False, False, 2, 0): 0.94,
     ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, False, False, False, 1, 0): 0.809,
+    ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, False, False, False, 2, 0): 0.69,
     ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, True, False, False, 1, 0): 0.792,
+    ('gn', 'apply', (16, 16, 16, 576), 0, 32, 1e-05, True, True, False, 2, 0): 0.65,
+    ('gn', 'apply', (16, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 2): 0.438,
     ('gn', 'apply', (16, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 4): 0.468,
     ('gn', 'apply', (16, 16, 16, 576), 576, 32, 1e-05, True, False, False, 1, 1): 0.503,
     ('gn', 'apply', (16, 16, 16, 768), 0, 32, 1e-05, True, True, False, 2, 0): 0.583,
@@ -879,14 +1281,41 @@ COND = {
     ('gn', 'apply', (32, 16, 16, 256), 256, 32, 1e-06, True, False, False, 2, 8): 0.335,
     ('gn', 'apply', (32, 16, 16, 256), 256, 32, 1e-06, True, False, False, 4, 8): 0.335,
     ('gn', 'apply', (32, 16, 16, 256), 256, 32, 1e-06, True, False, False, 8, 8): 0.359,
+    ('gn', 'apply', (32, 16, 16, 384), 0, 32, 1e-05, True, False, False, 2, 0): 0.908,
+    ('gn', 'apply', (32, 16, 16, 384), 0, 32, 1e-05, True, True, False, 2, 0): 0.665,
+    ('gn', 'apply', (32, 16, 16, 576), 0, 32, 1e-05, False, False, False, 2, 0): 0.809,
+    ('gn', 'apply', (32, 16, 16, 576), 0, 32, 1e-05, True, False, False, 1, 0): 0.829,
+    ('gn', 'apply', (32, 16, 16, 576), 0, 32, 1e-05, True, True, False, 2, 0): 0.693,
+    ('gn', 'apply', (32, 16, 16, 576), 384, 32, 1e-05, True, False, False, 1, 2): 0.48,
+    ('gn', 'apply', (32, 16, 16, 576), 576, 32, 1e-05, True, False, False, 1, 1): 0.442,
+    ('gn', 'apply', (32, 16, 16, 768), 0, 32, 1e-05, True, True, False, 2, 0): 0.591,
+    ('gn', 'apply', (32, 16, 16, 768), 576, 32, 1e-05, True, False, False, 2, 1): 0.399,
     ('gn', 'apply', (32, 32, 32, 128), 0, 32, 1e-06, True, False, False, 8, 0): 0.84,
     ('gn', 'apply', (32, 32, 32, 128), 128, 32, 1e-06, True, False, False, 8, 8): 0.499,
+    ('gn', 'apply', (32, 32, 32, 192), 0, 32, 1e-05, True, False, False, 8, 0): 1.115,
+    ('gn', 'apply', (32, 32, 32, 192), 0, 32, 1e-05, True, True, False, 8, 0): 0.871,
     ('gn', 'apply', (32, 32, 32, 256), 128, 32, 1e-06, True, False, False, 8, 8): 0.343,
+    ('gn', 'apply', (32, 32, 32, 384), 0, 32, 1e-05, False, False, False, 8, 0): 0.774,
+    ('gn', 'apply', (32, 32, 32, 384), 0, 32, 1e-05, True, False, False, 4, 0): 0.709,
+    ('gn', 'apply', (32, 32, 32, 384), 0, 32, 1e-05, True, True, False, 8, 0): 0.876,
+    ('gn', 'apply', (32, 32, 32, 384), 192, 32, 1e-05, True, False, False, 4, 8): 0.463,
+    ('gn', 'apply', (32, 32, 32, 384), 384, 32, 1e-05, True, False, False, 4, 4): 0.505,
+    ('gn', 'apply', (32, 32, 32, 576), 0, 32, 1e-05, True, True, False, 8, 0): 0.589,
+    ('gn', 'apply', (32, 32, 32, 576), 384, 32, 1e-05, True, False, False, 8, 4): 0.507,
+    ('gn', 'apply', (32, 64, 64, 192), 0, 32, 1e-05, True, False, False, 1, 0): 0.724,
+    ('gn', 'apply', (32, 64, 64, 192), 0, 32, 1e-05, True, True, False, 1, 0): 0.75,
+    ('gn', 'apply', (32, 64, 64, 192), 192, 32, 1e-05, True, False, False, 1, 1): 0.595,
+    ('gn', 'apply', (32, 64, 64, 384), 0, 32, 1e-05, True, True, False, 1, 0): 0.562,
+    ('gn', 'apply', (32, 64, 64, 384), 192, 32, 1e-05, True, False, False, 1, 1): 0.484,
     ('gn', 'apply', (32, 8, 8, 256), 0, 32, 1e-06, True, False, False, 1, 0): 0.626,
     ('gn', 'generic', (100, 8, 8, 576), 0, 32, 1e-05, True, False, False, 0, 0): 0.87,
     ('gn', 'generic', (100, 8, 8, 576), 0, 32, 1e-05, True, True, False, 0, 0): 0.871,
     ('gn', 'generic', (100, 8, 8, 768), 0, 32, 1e-05, True, True, False, 0, 0): 0.707,
     ('gn', 'generic', (100, 8, 8, 768), 576, 32, 1e-05, True, False, False, 0, 0): 0.569,
+    ('gn', 'generic', (14, 8, 8, 576), 0, 32, 1e-05, True, False, False, 0, 0): 0.667,
+    ('gn', 'generic', (14, 8, 8, 576), 0, 32, 1e-05, True, True, False, 0, 0): 0.758,
+    ('gn', 'generic', (14, 8, 8, 768), 0, 32, 1e-05, True, True, False, 0, 0): 0.615,
+    ('gn', 'generic', (14, 8, 8, 768), 576, 32, 1e-05, True, False, False, 0, 0): 0.503,
     ('gn', 'generic', (16, 16, 16, 576), 0, 32, 1e-05, True, True, False, 0, 0): 0.783,
     ('gn', 'generic', (16, 16, 16, 576), 0, 32, 1e-05, True, True, True, 0, 0): 0.783,
     ('gn', 'generic', (16, 8, 8, 576), 0, 32, 1e-05, True, False, False, 0, 0): 0.76,
@@ -897,6 +1326,10 @@ COND = {
     ('gn', 'generic', (16, 8, 8, 768), 0, 32, 1e-05, True, True, True, 0, 0): 0.584,
     ('gn', 'generic', (16, 8, 8, 768), 576, 32, 1e-05, True, False, False, 0, 0): 0.438,
     ('gn', 'generic', (16, 8, 8, 768), 576, 32, 1e-05, True, False, True, 0, 0): 0.438,
+    ('gn', 'generic', (32, 8, 8, 576), 0, 32, 1e-05, True, False, True, 0, 0): 0.729,
+    ('gn', 'generic', (32, 8, 8, 576), 0, 32, 1e-05, True, True, True, 0, 0): 0.705,
+    ('gn', 'generic', (32, 8, 8, 768), 0, 32, 1e-05, True, True, True, 0, 0): 0.53,
+    ('gn', 'generic', (32, 8, 8, 768), 576, 32, 1e-05, True, False, True, 0, 0): 0.524,
     ('gn', 'resident', (100, 8, 8, 768), 0, 32, 1e-05, False, False, False, 0, 0): 0.776,
     ('gn', 'resident', (100, 8, 8, 768), 0, 32, 1e-05, True, False, False, 0, 0): 0.746,
     ('gn', 'resident', (100, 8, 8, 768), 768, 32, 1e-05, True, False, False, 0, 0): 0.491,
@@ -913,6 +1346,9 @@ COND = {
     ('gn', 'resident', (128, 4, 4, 256), 256, 32, 1e-06, True, False, False, 0, 0): 0.537,
     ('gn', 'resident', (128, 8, 8, 256), 0, 32, 1e-06, True, False, False, 0, 0): 0.615,
     ('gn', 'resident', (128, 8, 8, 256), 256, 32, 1e-06, True, False, False, 0, 0): 0.43,
+    ('gn', 'resident', (14, 8, 8, 768), 0, 32, 1e-05, False, False, False, 0, 0): 0.652,
+    ('gn', 'resident', (14, 8, 8, 768), 0, 32, 1e-05, True, False, False, 0, 0): 0.634,
+    ('gn', 'resident', (14, 8, 8, 768), 768, 32, 1e-05, True, False, False, 0, 0): 0.461,
     ('gn', 'resident', (16, 8, 8, 1024), 0, 32, 1e-05, False, False, False, 0, 0): 0.527,
     ('gn', 'resident', (16, 8, 8, 1024), 0, 32, 1e-05, True, False, False, 0, 0): 0.506,
     ('gn', 'resident', (16, 8, 8, 1024), 1024, 32, 1e-05, True, False, False, 0, 0): 0.311,
@@ -945,6 +1381,9 @@ COND = {
     ('gn', 'resident', (32, 4, 4, 256), 256, 32, 1e-06, True, False, False, 0, 0): 0.481,
     ('gn', 'resident', (32, 8, 8, 256), 0, 32, 1e-06, True, False, False, 0, 0): 0.605,
     ('gn', 'resident', (32, 8, 8, 256), 256, 32, 1e-06, True, False, False, 0, 0): 0.405,
+    ('gn', 'resident', (32, 8, 8, 768), 0, 32, 1e-05, False, False, False, 0, 0): 0.579,
+    ('gn', 'resident', (32, 8, 8, 768), 0, 32, 1e-05, True, False, False, 0, 0): 0.58,
+    ('gn', 'resident', (32, 8, 8, 768), 768, 32, 1e-05, True, False, False, 0, 0): 0.412,
 }
 
 CASE_SET = set(CASES)
@@ -987,6 +1426,9 @@ EXTRA = [
     ("attention", 4, 256, 256, 2, True, True, "attention_kernel<128>"),
     ("attention", 4, 128, 256, 4, True, True, "attention_kernel<64>"),      # T % 256 != 0: the generic 64-wide kernel
     ("attention_proj", 5, 256, 256, 1, True),                              # attention256_kernel<true>
+    ("nhwc_bf16_to_nchw_f32", (5, 16, 24, 40)),                            # layout copy and output stage: launched by the
+    ("quantize_u8", (100, 3, 64, 64), 1, False),                           # generation scripts after the recorded programs
+    ("quantize_u8", (7, 3, 32, 32), 0, True),
 ]
 ATTN_KERNELS = {"attention_kernel<64>", "attention_kernel<128>", "attention_kernel<256>", "attention64", "attention256<false>"}
 
@@ -1043,7 +1485,9 @@ class _tuned:
 def test_census_is_covered(ops, program):
     import forward_census
     ops.device_check()
-    rows, cond = forward_census.record(ops, program)
+    rows, cond, unknown = forward_census.record(ops, program)
+    assert not unknown, f"{program}: ops functions called outside a backward that are neither launch ops nor allowed: {unknown}"
+    assert rows, f"{program}: nothing recorded"
     missing = sorted((r for r in rows if not _covered(r)), key=repr)
     assert not missing, f"{program}: forward launches not in CASES (add them): {missing}"
     for r, c in cond.items():
@@ -1481,14 +1925,7 @@ def test_upsample2x(ops, r):
 def test_pool_act(ops, r):
     _, xs, pool, act = r
     x = bf(rnd(_seed(r), *xs))
-    got = ops.pool_act(x, pool, act)
-    xd, xa = x.double(), x.double().abs()
-    if pool:
-        N, H, W, C = xs
-        xd = xd.reshape(N, H // 2, 2, W // 2, 2, C).mean((2, 4))
-        xa = xa.reshape(N, H // 2, 2, W // 2, 2, C).mean((2, 4))
-    ref = act64(xd, act)
-    CHECK.within("pool_act", got, ref, store_bound(4 * U32 * xa, ref))
+    CHECK.within("pool_act", ops.pool_act(x, pool, act), *pool_act_ref(x, pool, act))
 
 
 @pytest.mark.gpu
@@ -1508,6 +1945,264 @@ def test_value_head(ops, r):
     if has_out:
         ref, A = ref * ow.double() + ob.double(), A * ow.double().abs() + ob.double().abs()
     CHECK.fp32("value_head", got.reshape(-1), ref, A, H * W + C + 4)
+
+
+# ------------------------------------------------------------------------------------------ non-network launches of a step
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("dropout"), ids=_id)
+def test_dropout_fwd(ops, r):
+    """Kept set bit-equal to the hash restatement; kept values bf16(x / (1 - p)) of the fp64 quotient (either neighbour where
+    the quotient is within 4 u32 of a rounding midpoint).  The backward replay is in test_hip_backward_shapes.py."""
+    _, shape, p, on_dev = r
+    assert not on_dev
+    x = bf(rnd(_seed(r), *shape))
+    seed = ops.dropout_site_seed(zlib.crc32(repr(r).encode()), 3)
+    y = ops.dropout(x, p, seed)
+    keep, ref, tie = dropout_ref(x, p, seed)
+    assert torch.equal((y != 0) | (x == 0), keep | (x == 0)), "kept set differs from the hash"
+    assert not bool(((y != ref) & ~tie).any()) and bool(((y.double() - ref.double()).abs() <= 2 * U16 * ref.double().abs()).all())
+    CHECK._note("dropout[mismatches]", 0.0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("edm_dsm_prep") + _rows("edm_dsm_loss_fwd"), ids=_id)
+def test_edm_dsm_fwd(ops, r):
+    """edm_dsm_prep and the per-sample DSM terms at the recorded batch against the fp64 expressions of
+    test_hip_edm_dsm.py::test_dsm_kernels_vs_fp64 (operands, scalings64, weights64 imported from there), with the bounds derived
+    in forward_bounds (scaled_input_ref, log_sigma_t, dsm_error_terms, dsm_loss_fwd_bound)."""
+    from test_hip_edm_dsm import operands, scalings64, weights64
+    shape = r[1]
+    N, CHW = shape[0], shape[1] * shape[2] * shape[3]
+    x0, noise, F_, sig = [t.to(DEV) for t in operands(N, CHW, zlib.crc32(repr(r).encode()) % 1000)]
+    v4 = lambda t: t.view(shape).contiguous()
+    if r[0] == "edm_dsm_prep":
+        x_in, t = ops.edm_dsm_prep(v4(x0), v4(noise), sig)
+        ref, A = scaled_input_ref(x0, sig, noise)
+        CHECK.fp32("edm_dsm_prep_x", x_in.view(N, CHW), ref, A, 16)
+        CHECK.within("edm_dsm_prep_t", t, *log_sigma_t(sig))
+        return
+    _, _, ws, distill = r
+    xs, mse = ops.edm_dsm_loss_fwd(v4(F_), v4(x0), v4(noise), sig, ws, distillation=distill)
+    e, Me, _ = dsm_error_terms(F_, x0, noise, sig, scalings64(sig, distill=distill))
+    CHECK.within("edm_dsm_loss_fwd_xs", xs, *dsm_loss_fwd_bound(e, Me))
+    CHECK.within("edm_dsm_loss_fwd_mse", mse, *dsm_loss_fwd_bound(e, Me, weights64(ws, sig)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("td_gather_cost"), ids=_id)
+def test_td_gather_cost(ops, r):
+    """[next_state | state] gathered bit for bit from the trajectory block; running cost mean_CHW (x' - x)^2 / (2 beta): a sum
+    of depth CHW of fp32 squares of fp32 differences."""
+    _, B, CHW, has = r
+    assert has == ("next_rows",)
+    g = _seed(r)
+    rows = 11 * B
+    traj = rnd(g, rows, CHW)
+    srows = torch.randperm(rows - B, generator=g, device=DEV)[:B].contiguous()
+    nrows = srows + B
+    beta = torch.full((1,), 0.37, device=DEV)
+    pair = torch.empty(2 * B, CHW, device=DEV)
+    cost = ops.td_gather_cost(traj, srows, beta, next_rows=nrows, out_pair=pair)
+    assert torch.equal(pair[:B], traj[nrows]) and torch.equal(pair[B:], traj[srows])
+    CHECK.fp32("td_gather_cost", cost, *td_gather_cost_ref(traj[nrows], traj[srows], beta), CHW + 8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("td_loss"), ids=_id)
+def test_td_loss_fwd(ops, r):
+    check_td_loss(ops, CHECK, r)
+
+
+def check_td_loss(ops, check, r):
+    """d loss / d v (zeros in the target half) and the three logged means of one td_loss row against fp64 autograd: depth-B
+    sums (shared with test_hip_backward_shapes.py, where td_loss is a row of the backward census too)."""
+    _, B, has_extra = r
+    g = _seed(r)
+    v, cost = rnd(g, 2 * B), rnd(g, B).abs()
+    extra = rnd(g, 1) if has_extra else None
+    grad, logs = ops.td_loss(v, cost, extra)
+    rg, rl, Ag, Al = td_loss_ref(v, cost, extra)
+    assert torch.equal(grad[:B], torch.zeros_like(grad[:B]))
+    check.fp32("td_loss_grad", grad, rg, Ag, 8)
+    check.fp32("td_loss_logs", logs, rl, Al, B + 8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("var_step"), ids=_id)
+def test_var_step(ops, r):
+    """The VAR transition at the recorded batches, both associations of x' (assoc 1: the sampling loop, 0: the training step),
+    per-sample schedule scalars all different: forward_bounds.var_step_ref."""
+    _, shape, want_mean, want_control, assoc = r
+    N, CHW = shape[0], shape[1] * shape[2] * shape[3]
+    g = _seed(r)
+    x, eps, z = rnd(g, *shape), rnd(g, *shape), rnd(g, *shape)
+    xm, cm, sg = rnd(g, N).abs() + 0.5, -rnd(g, N).abs() - 0.1, torch.exp(rnd(g, N) * 0.3 - 1.0)
+    got = dict(zip(("x_next", "mean", "control", "logp"),
+                   ops.var_step(x, eps, z, xm, cm, sg, want_mean=want_mean, want_control=want_control, assoc=assoc)))
+    assert (got["mean"] is not None) == want_mean and (got["control"] is not None) == want_control
+    f = lambda t: t.view(N, CHW)
+    for k, (ref, bound) in var_step_ref(f(x), f(eps), f(z), xm, cm, sg).items():
+        if got[k] is not None:
+            CHECK.within(f"var_step_{k}", got[k].view(ref.shape), ref, bound)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("edm_step") + _rows("edm_precond"), ids=_id)
+def test_edm_step_and_precond(ops, r):
+    """The EDM transition and its preconditioning at the recorded batches, one sigma per sample over the whole ladder."""
+    shape = r[1]
+    N, CHW = shape[0], shape[1] * shape[2] * shape[3]
+    g = _seed(r)
+    f = lambda t: t.view(N, CHW)
+    x = rnd(g, *shape)
+    sigma = torch.exp(torch.linspace(-6.2, 4.38, N, device=DEV))          # 0.002 .. 80
+    if r[0] == "edm_precond":
+        x_in, t = ops.edm_precond(x, sigma)
+        ref, A = scaled_input_ref(f(x), sigma)
+        CHECK.fp32("edm_precond_x", f(x_in), ref, A, 16)
+        CHECK.within("edm_precond_t", t, *log_sigma_t(sigma))
+        return
+    F_, z = rnd(g, *shape), rnd(g, *shape)
+    sdn, sup = sigma * (0.2 + 0.6 * torch.rand(N, generator=g, device=DEV)), sigma * 0.3
+    sample, mean = ops.edm_step(x, F_, z, sigma, sdn, sup)
+    mu, smp, Am, As = edm_step_ref(f(x), f(F_), f(z), sigma, sdn, sup)
+    CHECK.fp32("edm_step_mean", f(mean), mu, Am, 16)
+    CHECK.fp32("edm_step_sample", f(sample), smp, As, 16)
+
+
+def _stage_io(shape, g, names):
+    """Seeded state / operand tensors of a sampler stage on the host (the references of the sampler tests take host tensors)."""
+    t = {k: 1.5 * torch.randn(shape, generator=g) for k in ("x", "x2", "d")}
+    t["F"] = 3.0 * torch.randn(shape, generator=g)             # c_out F + c_skip x lands on both sides of the +-1 clamp
+    t["noise"] = torch.randn(shape, generator=g)
+    t["ref"] = torch.rand(shape, generator=g) * 2 - 1
+    t["mask"] = (torch.rand(shape, generator=g) > 0.5).float()
+    return t
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("karras_stage"), ids=_id)
+def test_karras_stage(ops, r):
+    """dxmi_karras_stage with exactly the operands the sampler passed, at the recorded batch, against the fp64 restatement of
+    test_hip_karras_sample.py (_row, _ref_stage, imported) with that test's bound: every output an fp32 expression of <= 8
+    operations on table scalars, 16 u32 times the sum M of its absolute terms; clip on and off."""
+    from test_hip_karras_sample import _ref_stage, _row
+    _, mode, last, shape, has = r
+    N = shape[0]
+    for clip in (1.0, 0.0):
+        g = torch.Generator().manual_seed(zlib.crc32(repr((r, clip)).encode()))
+        tab = _row(g, mode, clip)
+        h = _stage_io(shape, g, has)
+        dev = {k: v.to(DEV).contiguous() for k, v in h.items()}
+        outs = {k: torch.full(shape, float("nan"), device=DEV) for k in ("x_in", "out", "denoised") if k in has}
+        t = torch.full((N,), float("nan"), device=DEV) if "t" in has else None
+        ops.karras_stage(mode, last, tab.to(DEV), 1, dev["x"], x2=dev["x2"] if "x2" in has else None, d=dev["d"] if "d" in has else None,
+                         model_out=dev["F"] if "model_out" in has else None, noise=dev["noise"] if "noise" in has else None,
+                         x_in=outs.get("x_in"), t=t, out=outs.get("out"), denoised=outs.get("denoised"))
+        got = {"x": dev["x"], "x2": dev["x2"], "d": dev["d"], **outs}
+        want = _ref_stage(mode, last, tab[1], h["x"], h["x2"], h["d"], h["F"], h["noise"] if "noise" in has else None)
+        assert set(want) - {"denoised"} <= set(got)
+        for k, (w, M) in want.items():
+            if k in got:
+                CHECK.fp32(f"karras_stage[{mode}]_{k}", got[k], w.to(DEV), M.to(DEV), 16)
+        if t is not None:
+            assert torch.equal(t.cpu(), tab[1, ops.KT_T].expand(N))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("cm_stage"), ids=_id)
+def test_cm_stage(ops, r):
+    """dxmi_cm_stage with exactly the operands the sampler / editing loop passed, at the recorded batch, against the fp64
+    restatement of test_hip_cm_sample.py (_table, _ref_stage, imported) with that test's bound 16 u32 M (+ 136 u32 M_Q for the
+    basis changes, which no recorded row uses); clip / output clamp on and off."""
+    from models.cm.karras_diffusion import colour_basis, patch_basis
+    from test_hip_cm_sample import _ref_stage, _table
+    _, mode, edit, last, shape, has = r
+    N = shape[0]
+    Q = {ops.CM_EDIT_COLOUR: colour_basis(), ops.CM_EDIT_PATCH: patch_basis()}.get(edit)
+    assert (Q is not None) == ("Q" in has)
+    for clip, out_clamp in ((1.0, 1.0), (0.0, 0.0)):
+        g = torch.Generator().manual_seed(zlib.crc32(repr((r, clip)).encode()))
+        tab = _table(g, mode, last, clip, out_clamp)
+        h = _stage_io(shape, g, has)
+        dev = {k: v.to(DEV).contiguous() for k, v in h.items()}
+        outs = {k: torch.full(shape, float("nan"), device=DEV) for k in ("x_in", "out", "denoised") if k in has}
+        t = torch.full((N,), float("nan"), device=DEV) if "t" in has else None
+        opt = lambda name, key: dev[key] if name in has else None
+        ops.cm_stage(mode, last, tab.to(DEV), 1, dev["x"], edit=edit, Q=None if Q is None else Q.to(DEV), model_out=opt("model_out", "F"),
+                     noise=opt("noise", "noise"), ref=opt("ref", "ref"), mask=opt("mask", "mask"), x_in=outs.get("x_in"), t=t,
+                     out=outs.get("out"), denoised=outs.get("denoised"))
+        got = {"x": dev["x"], **outs}
+        want = _ref_stage(mode, edit, last, tab[1], Q, h["x"], h["F"], h["noise"] if "noise" in has else None, h["ref"], h["mask"])
+        assert set(want) - {"denoised"} <= set(got)
+        for k, (w, Me, Mq) in want.items():
+            if k in got:
+                CHECK.within(f"cm_stage[{mode},{edit}]_{k}", got[k], w.to(DEV), (16 * U32 * Me + 136 * U32 * Mq).to(DEV))
+        if t is not None:
+            assert torch.equal(t.cpu(), tab[1, ops.CT_T].expand(N))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("gn_shortcut"), ids=_id)
+def test_groupnorm_silu_shortcut(ops, r):
+    """The fused norm1 + 1x1 shortcut kernel at the recorded shapes: y against the fp64 GroupNorm of the streaming-apply path
+    (block statistics with the recorded partial counts), the shortcut against the fp64 1x1 conv of the same input."""
+    _, xs, c1, Cout, groups, eps, silu, has_bias, P0, P1 = r
+    N, H, W, C0 = xs
+    C = C0 + c1
+    g = _seed(r)
+    xc = _gn_input(g, N, H, W, C, MIN_COND, groups)
+    x0 = xc[..., :C0].contiguous()
+    x1 = xc[..., C0:].contiguous() if c1 else None
+    gamma, beta = 1 + 0.3 * rnd(g, C), 0.3 * rnd(g, C)
+    Wt = rnd(g, Cout, C, 1, 1, scale=C ** -0.5)
+    bias = rnd(g, Cout, scale=0.1) if has_bias else None
+    st0 = ops.BlockStats(_block_stats_tensor(x0, P0), P0)
+    st1 = ops.BlockStats(_block_stats_tensor(x1, P1), P1) if c1 else None
+    res = ops.groupnorm_silu_shortcut(x0, gamma, beta, ops.pack_conv_weight(Wt), in1=x1, bias=bias, groups=groups, eps=eps, silu=silu,
+                                      stats=(st0, st1))
+    assert res is not None, "the census saw this shape launch the fused kernel"
+    y, sc = res
+    yo, parts = gn_ref(xc, gamma, beta, groups, eps, silu, None)
+    CHECK.within("gn_shortcut_y", y, yo, gn_bound(yo, parts, gamma, beta, max(P0, P1) + C // groups // 2 + 2, silu))
+    ref, A = conv_fwd_ref(xc, bf(Wt).float(), bias=bias)
+    CHECK.within("gn_shortcut_conv", sc, ref, conv_bound(ref, A, C, 0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", _rows("var_gather_sched") + _rows("nhwc_bf16_to_nchw_f32") + _rows("quantize_u8"), ids=_id)
+def test_gathers_and_layout_copies(ops, r):
+    """The integer schedule gather, the layout copy and the output stage, bit-equal to stock torch (sigma = exp(log_betas): fp32
+    expf against the fp64 exponential within 4 u32)."""
+    g = _seed(r)
+    if r[0] == "var_gather_sched":
+        _, N, T = r
+        t = torch.randint(-T, T, (N,), generator=g, device=DEV)                     # negative steps wrap as torch indexing does
+        tabs = [rnd(g, T) for _ in range(4)]
+        tau, xm, cm, sg = ops.var_gather_sched(t, *tabs)
+        assert torch.equal(tau, tabs[0][t]) and torch.equal(xm, tabs[1][t]) and torch.equal(cm, tabs[2][t])
+        ref = torch.exp(tabs[3][t].double())
+        CHECK.fp32("var_gather_sched_sigma", sg, ref, ref, 4)
+    elif r[0] == "nhwc_bf16_to_nchw_f32":
+        x = bf(rnd(g, *r[1]))
+        assert torch.equal(ops.nhwc_bf16_to_nchw_f32(x), x.float().permute(0, 3, 1, 2).contiguous())
+    else:
+        _, shape, mode, nhwc = r
+        x = rnd(g, *shape) * 0.8
+        if mode == 1:
+            ref = ((x + 1) * 127.5).clamp(0, 255).to(torch.uint8)
+        else:
+            ref = (((x + 1) / 2).clamp(0, 1) * 255 + 0.5).clamp(0, 255).to(torch.uint8)
+        got = ops.quantize_u8(x, mode=mode, nhwc=nhwc)
+        assert torch.equal(got, ref.permute(0, 2, 3, 1).contiguous() if nhwc else ref)
+
+
+def test_every_row_kind_has_a_test():
+    """Host-side: the op kinds of CASES + EXTRA are exactly the kinds some test of this file parametrises over."""
+    import re
+    src = open(os.path.abspath(__file__)).read()
+    tested = set(re.findall(r'_rows\("([a-z0-9_]+)"\)', src))
+    assert {r[0] for r in CASES + EXTRA} == tested, {r[0] for r in CASES + EXTRA} ^ tested
 
 
 @pytest.mark.gpu
