@@ -1633,6 +1633,7 @@ def pool3x3(x, stride, pad, avg_exclude_pad=False, out=None, coff=0):
     OH, OW = (IH + 2 * pad - 3) // stride + 1, (IW + 2 * pad - 3) // stride + 1
     if out is None:
         out = torch.empty((N, OH, OW, C), dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape[:3]) == (N, OH, OW)
     check(load().dxmi_pool3x3(_ptr(x), _ptr(out), N, IH, IW, C, stride, pad, int(avg_exclude_pad), out.shape[3], coff, _stream()), "dxmi_pool3x3")
     return out
 

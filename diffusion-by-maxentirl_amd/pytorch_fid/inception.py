@@ -159,8 +159,8 @@ class InceptionV3(nn.Module):
             run(m.branch3x3dbl_3, run(m.branch3x3dbl_2, run(m.branch3x3dbl_1, x)), out, 128)
             run(m.branch_pool, ops.pool3x3(x, 1, 1, avg_exclude_pad=True), out, 224)
         elif k == "B":
-            OH = (H - 3) // 2 + 1
-            out = new(OH, OH, 480 + x.shape[3])
+            OH, OW = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+            out = new(OH, OW, 480 + x.shape[3])
             run(m.branch3x3, x, out, 0)
             run(m.branch3x3dbl_3, run(m.branch3x3dbl_2, run(m.branch3x3dbl_1, x)), out, 384)
             ops.pool3x3(x, 2, 0, out=out, coff=480)
@@ -172,8 +172,8 @@ class InceptionV3(nn.Module):
             run(m.branch7x7dbl_5, run(m.branch7x7dbl_4, run(m.branch7x7dbl_3, t)), out, 384)
             run(m.branch_pool, ops.pool3x3(x, 1, 1, avg_exclude_pad=True), out, 576)
         elif k == "D":
-            OH = (H - 3) // 2 + 1
-            out = new(OH, OH, 512 + x.shape[3])
+            OH, OW = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+            out = new(OH, OW, 512 + x.shape[3])
             run(m.branch3x3_2, run(m.branch3x3_1, x), out, 0)
             run(m.branch7x7x3_4, run(m.branch7x7x3_3, run(m.branch7x7x3_2, run(m.branch7x7x3_1, x))), out, 320)
             ops.pool3x3(x, 2, 0, out=out, coff=512)

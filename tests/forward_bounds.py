@@ -47,6 +47,30 @@ Attention.  P is rounded to bf16 before the P V product (an MFMA operand), so th
 lse2 = log2 sum_j 2^(s_ij log2 e), s = scale q.k.  A score is an fp32 sum of D exact products (error D u32 scale sum|q||k|),
 2^x is evaluated to ~2 ulp and summed over T keys, so element-wise
     |got - lse2| <= log2(e) (D + 2) u32 scale max_j sum_d |q_id k_jd| + (T + 8) u32 log2(e) + 4 u32 |lse2|
+
+InceptionV3 extractor (csrc/inception_ops.hip).  Bounds of the extractor's launches (tests/test_hip_inception_launches.py).
+
+gconv: the conv bound above with L = 1 (none / ReLU): K = CinP * KH * KW products (the zero-padded channels included: they add
+exact zeros), + bias; the weight operand of the reference is the UNPACKED PACKED BUFFER, bit for bit the kernel's operand
+(gconv_unpack, written from the layout the kernel's header documents: [CoutP][KH * KW][CinP], CoutP = ceil32(Cout),
+CinP = ceil16(Cin)); gconv_pack_ref ties that buffer to the checkpoint's tensors.
+
+gconv_pack: scale = gamma / sqrt(var + eps) is three fp32 operations (add, correctly rounded sqrt and divide), the product
+w * scale a fourth, the fp32 value of eps a relative 2^-24 of a small term: <= 8 u32 in all, then one bf16 rounding:
+    |wp - fold64| <= (u16 + 8 u32) |fold64|,   |bias - (beta - mean scale)| <= 8 u32 (|beta| + |mean scale|).
+
+Average pool over the cnt in-bounds pixels of a 3x3 window: cnt exact bf16 -> fp32 values are added ((cnt - 1) u32 sum|x|) and
+divided by cnt (one rounding): (cnt + 1) u32 mean|x|, then one bf16 store.  Max pool: exact.
+
+Global average pool (fp32 out): HW values added in fp32, one division: (HW + 1) u32 mean|x| + 4 u32 |ref|.
+
+Bilinear resize (+ 2 x - 1).  The kernel evaluates the source coordinate src = (dst + 0.5) * (in / out) - 0.5 in fp32: the quotient,
+the sum, the product and the difference round once each, relative to magnitudes <= max(IH, IW) + 1, so
+|src32 - src| <= d = 4 u32 (max(IH, IW) + 1).  The interpolant is continuous and piecewise linear in each source coordinate with
+slope at most D = the largest absolute difference of vertically or horizontally adjacent input pixels (image-wide), so an error of
+d per axis moves it by at most 2 d D, also when the floor lands on the other side of an integer.  The weights 1 - l, l and the
+four products and three sums are fp32: 8 u32 max|x| covers them.  With s = 2 when normalising (v -> 2 v - 1), else 1:
+    |got - ref64| <= s (2 d D + 8 u32 max|x|) (1 + u16) + (u16 + 4 u32) |ref64|
 """
 import math
 
@@ -354,3 +378,123 @@ def edm_step_ref(x, F, z, sigma, sdn, sup, sd=0.5):
     mu = x + (x - den) / e(sigma) * dt
     A = x.abs() + (x.abs() + (c_out * F).abs() + (c_skip * x).abs()) / e(sigma) * dt.abs()
     return mu, mu + z * e(sup), A, A + (z * e(sup)).abs()
+
+
+# ------------------------------------------------------------------------------------------ InceptionV3 extractor (csrc/inception_ops.hip)
+def gconv_unpack(wp, Cout, Cin, KH, KW):
+    """Packed buffer [CoutP][KH * KW][CinP] (flat bf16) -> [CoutP, CinP, KH, KW] in the OIHW order of the checkpoint."""
+    CoutP, CinP = -(-Cout // 32) * 32, -(-Cin // 16) * 16
+    assert wp.numel() == CoutP * KH * KW * CinP, (wp.numel(), CoutP, KH, KW, CinP)
+    return wp.reshape(CoutP, KH * KW, CinP).permute(0, 2, 1).reshape(CoutP, CinP, KH, KW)
+
+
+def gconv_pack_ref(weight, bn, eps):
+    """fp64 fold of BatchNorm into the conv: (w scale [Cout, Cin, KH, KW], bias [Cout], bias magnitude |beta| + |mean scale|)."""
+    w = weight.double()
+    if bn is None:
+        z = torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
+        return w, z, z
+    gamma, beta, mean, var = (t.double() for t in bn)
+    scale = gamma / torch.sqrt(var + eps)
+    return w * scale[:, None, None, None], beta - mean * scale, beta.abs() + (mean * scale).abs()
+
+
+def gconv_pack_bounds(fold, bias_mag):
+    return (U16 + 8 * U32) * fold.abs(), 8 * U32 * bias_mag
+
+
+def gconv_ref(x, w4, bias, stride, pad, chunk_bytes=1 << 29):
+    """fp64 pre-activation conv with a rectangular kernel and A = sum |w||x| + |bias|: x NHWC [N, IH, IW, C] (any dtype),
+    w4 [Cout, C, KH, KW], bias [Cout], stride / pad pairs (h, w).  A few images at a time, as conv_fwd_ref."""
+    N, IH, IW, C = x.shape
+    Co, Cw, KH, KW = w4.shape
+    assert Cw == C, (Cw, C)
+    OH, OW = (IH + 2 * pad[0] - KH) // stride[0] + 1, (IW + 2 * pad[1] - KW) // stride[1] + 1
+    Wm = w4.double().reshape(Co, -1)
+    Wa = Wm.abs()
+    out = torch.empty(N, OH, OW, Co, dtype=torch.float64, device=x.device)
+    A = torch.empty_like(out)
+    per = max(1, chunk_bytes // (C * KH * KW * OH * OW * 8 * 2))
+    for n0 in range(0, N, per):
+        cols = F.unfold(x[n0:n0 + per].double().permute(0, 3, 1, 2), (KH, KW), padding=tuple(pad), stride=tuple(stride))   # [n, C*KH*KW, OH*OW]
+        out[n0:n0 + per] = torch.einsum("ok,nkp->npo", Wm, cols).reshape(-1, OH, OW, Co)
+        A[n0:n0 + per] = torch.einsum("ok,nkp->npo", Wa, cols.abs_()).reshape(-1, OH, OW, Co)
+        del cols
+    b = bias.double()
+    out += b
+    A += b.abs()
+    return out, A
+
+
+def avgpool3x3_ref(x, stride, pad):
+    """Average over the in-bounds pixels of each 3x3 window of an NHWC tensor in fp64 (F.avg_pool2d, count_include_pad=False)
+    and its bound."""
+    xd = x.double().permute(0, 3, 1, 2)
+    ref = F.avg_pool2d(xd, 3, stride, pad, count_include_pad=False).permute(0, 2, 3, 1)
+    mabs = F.avg_pool2d(xd.abs(), 3, stride, pad, count_include_pad=False).permute(0, 2, 3, 1)
+    cnt = 9 * F.avg_pool2d(torch.ones_like(xd[:, :1]), 3, stride, pad, count_include_pad=True).permute(0, 2, 3, 1)
+    return ref, store_bound((cnt + 1) * U32 * mabs, ref), cnt
+
+
+def maxpool3x3_ref(x, stride, pad):
+    return F.max_pool2d(x.double().permute(0, 3, 1, 2), 3, stride, pad).permute(0, 2, 3, 1)
+
+
+def global_avgpool_ref(x):
+    """[N, H, W, C] -> fp64 mean over the pixels [N, C] and its bound (fp32 output)."""
+    xd = x.double()
+    HW = x.shape[1] * x.shape[2]
+    ref = xd.mean((1, 2))
+    return ref, store_bound((HW + 1) * U32 * xd.abs().mean((1, 2)), ref, bf16_out=False)
+
+
+def _src_index(O, I, device):
+    """Source coordinate of F.interpolate(mode='bilinear', align_corners=False) in fp64: (i0, i1, l)."""
+    s = ((torch.arange(O, dtype=torch.float64, device=device) + 0.5) * (I / O) - 0.5).clamp_min(0)
+    i0 = s.floor().clamp_max(I - 1)
+    i1 = (i0 + 1).clamp_max(I - 1)
+    return i0.long(), i1.long(), s - i0
+
+
+def resize_ref(x, OH, OW, normalize):
+    """Closed-form bilinear resize (+ 2 x - 1) of NCHW [N, 3, IH, IW] in fp64 -> (ref NHWC [N, OH, OW, 3], bound)."""
+    xd = x.double()
+    N, C, IH, IW = xd.shape
+    y0, y1, ly = _src_index(OH, IH, x.device)
+    x0, x1, lx = _src_index(OW, IW, x.device)
+    ly, lx = ly[:, None], lx[None, :]
+    top = xd[:, :, y0][:, :, :, x0] * (1 - lx) + xd[:, :, y0][:, :, :, x1] * lx
+    bot = xd[:, :, y1][:, :, :, x0] * (1 - lx) + xd[:, :, y1][:, :, :, x1] * lx
+    ref = top * (1 - ly) + bot * ly
+    s = 1.0
+    if normalize:
+        ref, s = 2 * ref - 1, 2.0
+    ref = ref.permute(0, 2, 3, 1)
+    d = 4 * U32 * (max(IH, IW) + 1)
+    D = max(float((xd[:, :, 1:] - xd[:, :, :-1]).abs().max()) if IH > 1 else 0.0,
+            float((xd[:, :, :, 1:] - xd[:, :, :, :-1]).abs().max()) if IW > 1 else 0.0)
+    core = s * (2 * d * D + 8 * U32 * float(xd.abs().max()))
+    return ref, store_bound(torch.full_like(ref, core), ref)
+
+
+def resize_emulate_f32(x, OH, OW, normalize):
+    """The expressions of resize_norm_kernel evaluated by torch in fp32, operation by operation, before the bf16 store: what
+    the bound's pre-store part is checked against without a device (NHWC [N, OH, OW, 3] fp32)."""
+    N, C, IH, IW = x.shape
+    f = torch.float32
+
+    def idx(O, I):
+        sc = torch.tensor(I, dtype=f) / torch.tensor(O, dtype=f)
+        s = ((torch.arange(O, dtype=f) + 0.5) * sc - 0.5).clamp_min(0)
+        i0 = s.to(torch.int64)
+        i1 = i0 + (i0 < I - 1).long()
+        return i0, i1, s - i0.to(f)
+    y0, y1, ly = idx(OH, IH)
+    x0, x1, lx = idx(OW, IW)
+    ly, lx = ly[:, None], lx[None, :]
+    xf = x.to(f)
+    g = lambda yi, xi: xf[:, :, yi][:, :, :, xi]
+    v = (1 - ly) * ((1 - lx) * g(y0, x0) + lx * g(y0, x1)) + ly * ((1 - lx) * g(y1, x0) + lx * g(y1, x1))
+    if normalize:
+        v = 2 * v - 1
+    return v.permute(0, 2, 3, 1)
