@@ -1,0 +1,108 @@
+"""Train a consistency model on the HIP U-Net: distillation from an EDM teacher, or consistency training without one
+(models.cm.train_util.CMTrainLoop over KarrasDenoiser.consistency_losses; reference: the consistency_models training entry point
+over models/cm/script_util.py cm_train_defaults + model_and_diffusion_defaults).
+
+    torchrun --nproc_per_node=8 cm_train.py --training_mode consistency_distillation --teacher_model_path edm_imagenet64.pt \\
+        --synthetic_data True --batch_size 16 --log_dir results/cd
+    python cm_train.py --training_mode consistency_training --synthetic_data True --max_iters 2
+
+Every key of cm_train_defaults() and model_and_diffusion_defaults() is a flag, next to --synthetic_data, --batch_size, --microbatch,
+--lr, --ema_rate, --log_dir, --max_iters, --use_fp16 and the loop's intervals.  For distillation the student and the target start
+from the teacher's weights, the teacher's diffusion has distillation=False and the student's distillation=True.  The target_model
+checkpoints it writes are what `generate_large.py --cm_sampler onestep --pretrained ...` reads.  Real-data loaders are not part of
+this package: --synthetic_data True draws uniform images and labels.  CMTrainLoop.run_loop keeps the reference's condition, which
+ends only when both lr_anneal_steps and total_training_steps are reached: --max_iters N (smoke runs) sets both to N, so the
+learning rate anneals to zero over those N steps.
+"""
+import argparse
+import os
+
+import torch
+
+from dxmi_hip import dist as _dist
+from models.cm.script_util import (add_dict_to_argparser, args_to_dict, cm_train_defaults, create_ema_and_scales_fn,
+                                   create_model_and_diffusion, model_and_diffusion_defaults)
+from models.cm.train_util import CMTrainLoop
+
+
+def print0(*a):
+    if int(os.environ.get("RANK", "0")) == 0:
+        print(*a, flush=True)
+
+
+def synthetic_batches(batch_size, image_size, class_cond, device, seed):
+    gen = torch.Generator(device=device).manual_seed(seed)
+    while True:
+        x = torch.rand(batch_size, 3, image_size, image_size, device=device, generator=gen) * 2 - 1
+        cond = {"y": torch.randint(0, 1000, (batch_size,), device=device, generator=gen)} if class_cond else {}
+        yield x, cond
+
+
+def main():
+    defaults = dict(model_and_diffusion_defaults())
+    defaults.update(cm_train_defaults())
+    defaults.update(synthetic_data=False, batch_size=16, microbatch=-1, lr=1e-4, ema_rate="0.9999", log_dir="results/cm_train",
+                    max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
+                    fp16_scale_growth=1e-3, seed=42, batch_invariant=False)
+    ap = argparse.ArgumentParser()
+    add_dict_to_argparser(ap, defaults)
+    args = ap.parse_args()
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    device = _dist.rank_device(local_rank)
+    torch.cuda.set_device(device)
+    if not args.batch_invariant:
+        from dxmi_hip import ops as _ops
+        _ops.tune_for_throughput()
+    torch.manual_seed(args.seed + local_rank)
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")   # RCCL
+    if not args.synthetic_data:
+        raise NotImplementedError("cm_train.py: real-data loaders are not part of this package; run with --synthetic_data True")
+    distill = args.training_mode == "consistency_distillation"
+    if args.training_mode not in ("consistency_distillation", "consistency_training"):
+        raise NotImplementedError(f"training_mode {args.training_mode!r}: consistency_distillation or consistency_training")
+
+    model_kw = args_to_dict(args, model_and_diffusion_defaults().keys())
+    model, diffusion = create_model_and_diffusion(distillation=True, **model_kw)
+    diffusion.loss_norm = args.loss_norm
+    if args.loss_norm == "lpips":
+        raise NotImplementedError("loss_norm='lpips': no LPIPS weights are available to this package; use l1, l2 or l2-32")
+    target_model, _ = create_model_and_diffusion(distillation=True, **model_kw)
+    teacher_model = teacher_diffusion = None
+    if distill:
+        teacher_model, teacher_diffusion = create_model_and_diffusion(distillation=False, **dict(model_kw, dropout=args.teacher_dropout))
+        if args.teacher_model_path:
+            teacher_model.load_state_dict(torch.load(args.teacher_model_path, map_location="cpu"))
+            print0(f"teacher loaded from {args.teacher_model_path}")
+        else:
+            print0("no --teacher_model_path: the teacher keeps its random initialisation (smoke runs)")
+        model.load_state_dict(teacher_model.state_dict())      # student and target start from the teacher
+        teacher_model.to(device).eval()
+    target_model.load_state_dict(model.state_dict())
+    model.to(device).train()
+    target_model.to(device).train()
+
+    ema_scale_fn = create_ema_and_scales_fn(target_ema_mode=args.target_ema_mode, start_ema=args.start_ema, scale_mode=args.scale_mode,
+                                            start_scales=args.start_scales, end_scales=args.end_scales,
+                                            total_steps=args.total_training_steps, distill_steps_per_iter=args.distill_steps_per_iter)
+    total = args.max_iters if args.max_iters else args.total_training_steps
+    loop = CMTrainLoop(model=model, target_model=target_model, teacher_model=teacher_model, teacher_diffusion=teacher_diffusion,
+                       training_mode=args.training_mode, ema_scale_fn=ema_scale_fn, total_training_steps=total, diffusion=diffusion,
+                       data=synthetic_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + local_rank),
+                       batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr, ema_rate=args.ema_rate,
+                       log_interval=args.log_interval, save_interval=args.save_interval, resume_checkpoint=args.resume_checkpoint,
+                       use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth, weight_decay=args.weight_decay,
+                       lr_anneal_steps=args.lr_anneal_steps if not args.max_iters else args.max_iters, log_dir=args.log_dir)
+    print0(f"{args.training_mode}: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
+           f"{total} steps, loss_norm {args.loss_norm}")
+    loop.run_loop()
+    if loop.logged:
+        print0("last log row:", loop.logged[-1])
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()

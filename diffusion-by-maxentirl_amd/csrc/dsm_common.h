@@ -1,0 +1,41 @@
+// Scalings and loss weights shared by the DSM loss (edm_dsm.hip) and the consistency losses (cm_train.hip).
+#pragma once
+#include "common.h"
+
+// the reference's fp32 operation order, one rounding per torch op: no fused multiply-add between them.  The pragma is at file
+// scope: it holds for the rest of every file that includes this header (both includers set it themselves, before the include).
+#pragma clang fp contract(off)
+
+namespace {
+
+struct DsmScal {
+    float c_skip, c_out, c_in, w;
+};
+
+// KarrasDenoiser.get_scalings / get_scalings_for_boundary_condition (:64-80) and get_weightings (:18-31) on the fp32 sigma, in
+// torch's forms: x**2 = x*x, x**0.5 = sqrt, python scalar / tensor = reciprocal(tensor) * scalar, x**-2 = 1 / (x*x).
+__device__ __forceinline__ DsmScal dsm_scalings(float s, float sd, float sd2, float sigma_min, int distill, int sched, float inv_sd2) {
+    DsmScal r;
+    const float den = s * s + sd2;
+    const float root = __builtin_sqrtf(den);
+    r.c_in = 1.f / root;
+    if (distill) {
+        const float sm = s - sigma_min;
+        r.c_skip = (1.f / (sm * sm + sd2)) * sd2;
+        r.c_out = (sm * sd) / root;
+    } else {
+        r.c_skip = (1.f / den) * sd2;
+        r.c_out = (s * sd) / root;
+    }
+    const float snr = 1.f / (s * s);
+    switch (sched) {
+        case DXMI_DSM_W_SNR:       r.w = snr; break;
+        case DXMI_DSM_W_SNR_P1:    r.w = snr + 1.f; break;
+        case DXMI_DSM_W_KARRAS:    r.w = snr + inv_sd2; break;
+        case DXMI_DSM_W_TRUNC_SNR: r.w = snr < 1.f ? 1.f : snr; break;    // th.clamp(snrs, min=1.0): NaN passes
+        default:                   r.w = 1.f; break;
+    }
+    return r;
+}
+
+}  // namespace

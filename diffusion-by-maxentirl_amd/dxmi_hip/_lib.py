@@ -122,6 +122,10 @@ SIGNATURES = {
     "dxmi_edm_dsm_loss_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_edm_dsm_loss_bwd": (c_int, [c_void_p] * 7 + [c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_ema_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_void_p, c_void_p]),
+    "dxmi_cd_prep": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 4 + [c_int, c_int, c_float, c_float, c_void_p]),
+    "dxmi_cd_solver": (c_int, [c_int] + [c_void_p] * 7 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_int, c_float, c_void_p]),
+    "dxmi_cd_loss_fwd": (c_int, [c_void_p] * 6 + [c_int, c_void_p] + [c_int] * 5 + [c_float, c_float, c_int, c_int, c_void_p]),
+    "dxmi_cd_loss_bwd": (c_int, [c_void_p] * 7 + [c_int, c_void_p] + [c_int] * 5 + [c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_karras_stage": (c_int, [c_int, c_int, c_void_p, c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
     "dxmi_cm_stage": (c_int, [c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 10 + [c_int] * 4 + [c_void_p]),
     "dxmi_quantize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1012,6 +1012,111 @@ def edm_dsm_loss_bwd(g_mse, g_xs, model_out, x_start, noise, sigma, weight_sched
     return d
 
 
+# dxmi_cd_solver modes and dxmi_cd_loss_* norms (include/dxmi_hip.h), by the reference's names (karras_diffusion.py:206-220)
+CD_EULER_X0, CD_HEUN_PRED, CD_HEUN_CORR = range(3)
+CD_LOSS_NORMS = {"l1": 0, "l2": 1, "l2-32": 2}
+
+
+def _cd_operands(what, x_start, indices, t_table, same=(), per_sample=()):
+    """The checks of _dsm_operands for the consistency launches: image-sized operands fp32 contiguous 16-byte aligned of one
+    shape, `indices` int64 [N] and `t_table` fp32 [num_scales >= 2] on the same device, per-sample operands of N elements."""
+    ts = (x_start,) + tuple(same) + tuple(per_sample)
+    _need_cuda(indices, t_table, *ts)
+    for t in ts + (t_table,):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+            raise _lib.DxmiError(f"{what}: fp32 contiguous 16-byte aligned device tensors")
+    if x_start.dim() < 2 or x_start.numel() == 0:
+        raise _lib.DxmiError(f"{what}: a non-empty batch [N, ...] is needed, got {tuple(x_start.shape)}")
+    N = x_start.shape[0]
+    for t in same:
+        if t is not None and t.shape != x_start.shape:
+            raise _lib.DxmiError(f"{what}: operand of shape {tuple(t.shape)} where {tuple(x_start.shape)} is needed")
+    for t in per_sample:
+        if t is not None and t.numel() != N:
+            raise _lib.DxmiError(f"{what}: per-sample operand of {t.numel()} elements for a batch of {N}")
+    if indices.dtype != torch.int64 or not indices.is_contiguous() or indices.numel() != N:
+        raise _lib.DxmiError(f"{what}: indices must be {N} contiguous int64 values")
+    if t_table.dim() != 1 or t_table.numel() < 2:
+        raise _lib.DxmiError(f"{what}: t_table must hold num_scales >= 2 levels, got {tuple(t_table.shape)}")
+    if any(t is not None and t.device != x_start.device for t in ts + (indices, t_table)):
+        raise _lib.DxmiError(f"{what}: operands on different devices")
+    return N, x_start.numel() // N, t_table.numel()
+
+
+def cd_prep(x_start, noise, indices, t_table, sigma_data=0.5, teacher_sigma_data=None):
+    """-> (x_t = x_start + noise t, x_in = c_in(t) x_t, time = 250 ln(t + 1e-44), x_in_teacher | None) with t = t_table[indices]
+    (dxmi_cd_prep).  x_in_teacher is written only where teacher_sigma_data is given and differs from sigma_data."""
+    N, CHW, S = _cd_operands("dxmi_cd_prep", x_start, indices, t_table, same=(noise,))
+    x_t, x_in = torch.empty_like(x_start), torch.empty_like(x_start)
+    t = torch.empty(N, dtype=torch.float32, device=x_start.device)
+    own = teacher_sigma_data is not None and float(teacher_sigma_data) != float(sigma_data)
+    x_te = torch.empty_like(x_start) if own else None
+    check(load().dxmi_cd_prep(_ptr(x_start), _ptr(noise), _ptr(indices), _ptr(t_table), S, _ptr(x_t), _ptr(x_in), _ptr(t), _ptr(x_te),
+                              N, CHW, float(sigma_data), float(teacher_sigma_data if own else sigma_data), _stream()), "dxmi_cd_prep")
+    return x_t, x_in, t, x_te
+
+
+def cd_solver(mode, x_t, indices, t_table, x_start=None, model_out=None, d=None, samples=None, sigma_data=0.5, sigma_min=0.002,
+              distillation=False, next_sigma_data=0.5):
+    """One stage of euler_solver / heun_solver (dxmi_cd_solver).  sigma_data / sigma_min / distillation: the diffusion whose
+    denoise() forms the denoiser (the teacher's); next_sigma_data: the diffusion of the network that reads the returned input.
+      CD_EULER_X0  (x_start)                 -> (x_t2, target input, target time)
+      CD_HEUN_PRED (model_out)               -> (d, samples, teacher's second input, its time)
+      CD_HEUN_CORR (model_out, d, samples)   -> (x_t2, target input, target time)"""
+    need = {CD_EULER_X0: (x_start,), CD_HEUN_PRED: (model_out,), CD_HEUN_CORR: (model_out, d, samples)}.get(mode)
+    if need is None:
+        raise _lib.DxmiError(f"dxmi_cd_solver: unknown mode {mode!r}")
+    if any(v is None for v in need):
+        raise _lib.DxmiError("dxmi_cd_solver: EULER_X0 needs x_start, HEUN_PRED model_out, HEUN_CORR model_out, d and samples")
+    N, CHW, S = _cd_operands("dxmi_cd_solver", x_t, indices, t_table, same=need)
+    x_next, t_next = torch.empty_like(x_t), torch.empty(N, dtype=torch.float32, device=x_t.device)
+    x_t2 = None
+    if mode == CD_HEUN_PRED:
+        d, samples = torch.empty_like(x_t), torch.empty_like(x_t)
+    else:
+        x_t2 = torch.empty_like(x_t)
+    check(load().dxmi_cd_solver(int(mode), _ptr(x_start), _ptr(x_t), _ptr(model_out), _ptr(d), _ptr(samples), _ptr(indices),
+                                _ptr(t_table), S, _ptr(x_t2), _ptr(x_next), _ptr(t_next), N, CHW, float(sigma_data), float(sigma_min),
+                                int(bool(distillation)), float(next_sigma_data), _stream()), "dxmi_cd_solver")
+    return (d, samples, x_next, t_next) if mode == CD_HEUN_PRED else (x_t2, x_next, t_next)
+
+
+def _cd_loss_args(what, f_online, loss_norm, weight_schedule):
+    if loss_norm not in CD_LOSS_NORMS:
+        raise _lib.DxmiError(f"{what}: loss norm {loss_norm!r} is not one of {sorted(CD_LOSS_NORMS)}")
+    if f_online.dim() != 4:
+        raise _lib.DxmiError(f"{what}: [N, C, H, W] tensors are needed, got {tuple(f_online.shape)}")
+    return CD_LOSS_NORMS[loss_norm], _dsm_schedule(weight_schedule)
+
+
+def cd_loss_fwd(f_online, f_target, x_t, x_t2, indices, t_table, loss_norm, weight_schedule, sigma_data=0.5, sigma_min=0.002,
+                distillation=False):
+    """-> per-sample consistency loss mean_flat(norm(distiller - target)) * get_weightings(snr(t)) (dxmi_cd_loss_fwd)."""
+    norm, sched = _cd_loss_args("dxmi_cd_loss_fwd", f_online, loss_norm, weight_schedule)
+    N, _, S = _cd_operands("dxmi_cd_loss_fwd", f_online, indices, t_table, same=(f_target, x_t, x_t2))
+    _, C, H, W = f_online.shape
+    loss = torch.empty(N, dtype=torch.float32, device=f_online.device)
+    check(load().dxmi_cd_loss_fwd(_ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices), _ptr(t_table), S, _ptr(loss),
+                                  N, C, H, W, norm, float(sigma_data), float(sigma_min), int(bool(distillation)), sched, _stream()),
+          "dxmi_cd_loss_fwd")
+    return loss
+
+
+def cd_loss_bwd(g_loss, f_online, f_target, x_t, x_t2, indices, t_table, loss_norm, weight_schedule, sigma_data=0.5,
+                sigma_min=0.002, distillation=False):
+    """-> d(f_online) of the consistency loss for the device upstream gradient g_loss [N] (dxmi_cd_loss_bwd)."""
+    norm, sched = _cd_loss_args("dxmi_cd_loss_bwd", f_online, loss_norm, weight_schedule)
+    if g_loss is None:
+        raise _lib.DxmiError("dxmi_cd_loss_bwd: no upstream gradient")
+    N, _, S = _cd_operands("dxmi_cd_loss_bwd", f_online, indices, t_table, same=(f_target, x_t, x_t2), per_sample=(g_loss,))
+    _, C, H, W = f_online.shape
+    d = torch.empty_like(f_online)
+    check(load().dxmi_cd_loss_bwd(_ptr(g_loss), _ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices), _ptr(t_table), S,
+                                  _ptr(d), N, C, H, W, norm, float(sigma_data), float(sigma_min), int(bool(distillation)), sched,
+                                  _stream()), "dxmi_cd_loss_bwd")
+    return d
+
+
 EMA_MAX_RATES = 4
 
 

@@ -5,13 +5,22 @@ denoise (:337-351), karras_sample (:354-420), get_sigmas_karras (:423-429), get_
 sample_euler_ancestral / sample_heun / sample_euler / sample_dpm (:447-640), and the consistency-model samplers
 sample_onestep / stochastic_iterative_sampler (:644-683) with the zero-shot editing loops iterative_colorization /
 iterative_inpainting / iterative_superres (:722-951), and the denoising score-matching loss training_losses with
-get_weightings (:18-31, :82-106) that models.cm.train_util.TrainLoop trains the U-Net with.  The consistency-distillation
-losses and progdist stay out of scope.
+get_weightings (:18-31, :82-106) that models.cm.train_util.TrainLoop trains the U-Net with, and the consistency distillation /
+consistency training loss consistency_losses (:108-241) of models.cm.train_util.CMTrainLoop.  progdist (losses and sampler) and
+the LPIPS norm stay out of scope.
 
 training_losses on the HIP UNetModel (bare, or behind a wrapper that holds it as `.module`) is ONE autograd node: the network
 input of the batch in one launch (dxmi_edm_dsm_prep), the U-Net forward of models.cm.unet_train, the per-sample terms in one
 launch (dxmi_edm_dsm_loss_fwd); its backward forms d(model output) in one launch (dxmi_edm_dsm_loss_bwd) and runs the U-Net
 backward.  x_t is never stored.  Any other callable model gets the reference's expressions in torch.
+
+consistency_losses on HIP UNetModels (online, target and, for distillation, teacher: all three, else the torch expressions run) is
+ONE autograd node around the online network: dxmi_cd_prep, the online training forward, per teacher evaluation (forward_inference,
+eval, no grad) one dxmi_cd_solver launch, the target evaluation (no grad), dxmi_cd_loss_fwd; its backward is dxmi_cd_loss_bwd and the
+U-Net backward.  The time ladder of a call is a host table (CDLevels: fp32 torch, the reference's expression, cached per (num_scales,
+sigma_min, sigma_max, rho)), uploaded once per device; the kernels gather t and t2 by index.  The target runs in the mode it is in:
+train mode with dropout > 0 takes the training forward with the dropout seeds the online forward just consumed (the reference restores
+the RNG state between the two so that they share masks, :192,200); otherwise forward_inference.
 
 denoise() keeps the reference signature for any callable `model`; neither sampler calls it on the hot path.
 OpenAIDiffusion (the DxMI few-step sampler) uses the fused dxmi_edm_precond / dxmi_edm_step_fwd kernels.
@@ -90,13 +99,120 @@ class _DSMLossFn(torch.autograd.Function):
         return (None,) * 6 + tuple(grads[4:])
 
 
+class CDLevels:
+    """The num_scales time levels of consistency_losses (reference :180-188), on the host in fp32 torch with the reference's own
+    expression: `indices / (num_scales - 1)` is an int64 tensor over a python int, then `** rho`.  Bit-identical to the reference
+    on the same CPU (1 ulp of pow across CPUs, as the sigma tables of the samplers).  table[i] = t of index i, table[i + 1] = t2."""
+
+    def __init__(self, num_scales, sigma_min, sigma_max, rho):
+        if int(num_scales) < 2:
+            raise ValueError(f"consistency_losses: num_scales must be at least 2, got {num_scales}")
+        indices = torch.arange(int(num_scales), dtype=torch.int64)
+        t = sigma_max ** (1 / rho) + indices / (num_scales - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))
+        self.table = (t ** rho).to(torch.float32)
+        self.num_scales = int(num_scales)
+        self._dev = {}
+
+    def device_table(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self.table.to(device)
+        return self._dev[key]
+
+
+_CD_LEVELS = {}
+_NO_LPIPS = "loss_norm='lpips': no LPIPS weights are available to this package; the consistency losses run with l1, l2 and l2-32"
+
+
+def cd_levels(num_scales, sigma_min, sigma_max, rho):
+    key = (int(num_scales), float(sigma_min), float(sigma_max), float(rho))
+    lv = _CD_LEVELS.get(key)
+    if lv is None:
+        if len(_CD_LEVELS) > 256:
+            _CD_LEVELS.clear()
+        lv = _CD_LEVELS[key] = CDLevels(num_scales, sigma_min, sigma_max, rho)
+    return lv
+
+
+def _train_forward_no_grad(net, x_in, t, y, seeds=None):
+    """The training forward of `net` without a tape kept (dropout applied).  seeds: the dropout seeds to use, site by site, and
+    they must be consumed exactly (a net with more or fewer dropout sites is an error); None: the net draws its own."""
+    import types
+    from dxmi_hip import ops
+    from .unet_train import _EDMUNetFn
+    sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
+    if seeds is not None:
+        net.__dict__["_dropout_seed_feed"] = list(seeds)
+    try:
+        with torch.no_grad():
+            out = _EDMUNetFn.forward(sub, net, x_in, t, y, *ops.fast_parameters(net))
+        left = net.__dict__.get("_dropout_seed_feed")
+        if left:
+            raise RuntimeError(f"dropout seed hand-over: {len(left)} of {len(seeds)} seeds were not consumed (the two nets differ in "
+                               "their dropout sites)")
+        return out
+    finally:
+        net.__dict__.pop("_dropout_seed_feed", None)
+
+
+class _CDLossFn(torch.autograd.Function):
+    """prep -> online U-Net forward -> solver stages around the teacher evaluations -> target evaluation -> per-sample loss, as
+    one node around the online network."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, target, teacher, teacher_diffusion, x_start, noise, indices, tab, y, *params):
+        import types
+        from dxmi_hip import ops
+        from .unet_train import _EDMUNetFn
+        sd = diffusion.sigma_data
+        x_t, x_in, t, x_te = ops.cd_prep(x_start, noise, indices, tab, sd, None if teacher is None else teacher_diffusion.sigma_data)
+        sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
+        F = _EDMUNetFn.forward(sub, net, x_in, t, y, *params)
+        seeds = list(net.dropout_seeds_used)
+        if teacher is None:
+            x_t2, tg_in, tg_t = ops.cd_solver(ops.CD_EULER_X0, x_t, indices, tab, x_start=x_start, next_sigma_data=sd)
+        else:
+            tk = dict(sigma_data=teacher_diffusion.sigma_data, sigma_min=teacher_diffusion.sigma_min,
+                      distillation=teacher_diffusion.distillation)
+            F1 = teacher.forward_inference(x_in if x_te is None else x_te, t, y)
+            d, samples, te_in, te_t = ops.cd_solver(ops.CD_HEUN_PRED, x_t, indices, tab, model_out=F1,
+                                                    next_sigma_data=teacher_diffusion.sigma_data, **tk)
+            F2 = teacher.forward_inference(te_in, te_t, y)
+            x_t2, tg_in, tg_t = ops.cd_solver(ops.CD_HEUN_CORR, x_t, indices, tab, model_out=F2, d=d, samples=samples,
+                                              next_sigma_data=sd, **tk)
+        if target.training and target.dropout > 0:
+            # an online forward that dropped nothing (eval mode, or dropout 0) has no masks to share: the target draws its own
+            F_tg = _train_forward_no_grad(target, tg_in, tg_t, y, seeds if seeds else None)
+        else:
+            F_tg = target.forward_inference(tg_in, tg_t, y)
+        kw = dict(loss_norm=diffusion.loss_norm, weight_schedule=diffusion.weight_schedule, sigma_data=sd,
+                  sigma_min=diffusion.sigma_min, distillation=diffusion.distillation)
+        loss = ops.cd_loss_fwd(F, F_tg, x_t, x_t2, indices, tab, **kw)
+        ctx.sub, ctx.kw, ctx.ops = sub, kw, (F, F_tg, x_t, x_t2, indices, tab)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from dxmi_hip import ops
+        from .unet_train import _EDMUNetFn
+        n_in = len(ctx.needs_input_grad)
+        if g is None:
+            return (None,) * n_in
+        dF = ops.cd_loss_bwd(g.detach().float().contiguous(), *ctx.ops, **ctx.kw)
+        ctx.ops = None
+        grads = _EDMUNetFn.backward(ctx.sub, dF)
+        ctx.sub = None
+        return (None,) * 10 + tuple(grads[4:])
+
+
 class KarrasDenoiser:
     def __init__(self, sigma_data: float = 0.5, sigma_max=80.0, sigma_min=0.002, rho=7.0, weight_schedule="karras",
                  distillation=False, loss_norm="l2"):
         self.sigma_data, self.sigma_max, self.sigma_min = sigma_data, sigma_max, sigma_min
         self.weight_schedule, self.distillation, self.loss_norm, self.rho = weight_schedule, distillation, loss_norm, rho
         if loss_norm == "lpips":
-            raise NotImplementedError("LPIPS loss belongs to consistency distillation, not to the DxMI path")
+            raise NotImplementedError(_NO_LPIPS)
 
     def get_snr(self, sigmas):
         return sigmas ** -2
@@ -170,6 +286,106 @@ class KarrasDenoiser:
             xs, mse = ops.edm_dsm_loss_fwd(F, x_start, noise, sigmas, self.weight_schedule, self.sigma_data, self.sigma_min,
                                            self.distillation)
         return {"xs_mse": xs, "mse": mse, "loss": mse}
+
+    def consistency_losses(self, model, x_start, num_scales, model_kwargs=None, target_model=None, teacher_model=None,
+                           teacher_diffusion=None, noise=None, indices=None, generator=None):
+        """Consistency distillation (teacher_model given: the Heun step through teacher_diffusion) or consistency training
+        (teacher_model None: the Euler step with denoiser = x_start) loss per sample (reference :108-241) -> {"loss": [N]}.
+        indices: the ladder index of every sample (the reference draws th.randint(0, num_scales - 1, (N,)) inside; drawn here,
+        from `generator` if given, when None)."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        if target_model is None:
+            raise NotImplementedError("Must have a target model")
+        if self.loss_norm == "lpips":        # set on the object after construction, as the reference's callers set it
+            raise NotImplementedError(_NO_LPIPS)
+        if self.loss_norm not in ("l1", "l2", "l2-32"):
+            raise ValueError(f"Unknown loss norm {self.loss_norm}")
+        if teacher_model is not None and teacher_diffusion is None:
+            raise ValueError("consistency_losses: a teacher_model needs its teacher_diffusion")
+        N = x_start.shape[0]
+        if indices is None:
+            if generator is not None:
+                indices = torch.randint(0, num_scales - 1, (N,), generator=generator, device=generator.device).to(x_start.device)
+            else:
+                indices = torch.randint(0, num_scales - 1, (N,), device=x_start.device)
+        nets = [_hip_unet(m) for m in (model, target_model) + ((teacher_model,) if teacher_model is not None else ())]
+        if all(n is not None for n in nets) and x_start.is_cuda:
+            return self._consistency_losses_hip(nets, x_start, num_scales, model_kwargs, teacher_diffusion, noise, indices)
+
+        dims = x_start.ndim
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(x_start.device)
+        indices = indices.to(x_start.device)
+        t, t2 = levels[indices], levels[indices + 1]
+
+        @torch.no_grad()
+        def teacher_denoise_fn(x, s):
+            return teacher_diffusion.denoise(teacher_model, x, s, **model_kwargs)[1]
+
+        x_t = x_start + noise * append_dims(t, dims)
+        dropout_state = torch.get_rng_state()
+        distiller = self.denoise(model, x_t, t, **model_kwargs)[1]
+        with torch.no_grad():
+            x = x_t
+            denoiser = x_start if teacher_model is None else teacher_denoise_fn(x, t)
+            d = (x - denoiser) / append_dims(t, dims)
+            samples = x + d * append_dims(t2 - t, dims)
+            if teacher_model is not None:                   # heun_solver (:144-162); euler_solver (:164-174) ends above
+                denoiser = teacher_denoise_fn(samples, t2)
+                next_d = (samples - denoiser) / append_dims(t2, dims)
+                samples = x + (d + next_d) * append_dims((t2 - t) / 2, dims)
+            x_t2 = samples.detach()
+            torch.set_rng_state(dropout_state)
+            distiller_target = self.denoise(target_model, x_t2, t2, **model_kwargs)[1].detach()
+
+        weights = get_weightings(self.weight_schedule, self.get_snr(t), self.sigma_data)
+        if self.loss_norm == "l1":
+            diffs = torch.abs(distiller - distiller_target)
+        elif self.loss_norm == "l2":
+            diffs = (distiller - distiller_target) ** 2
+        else:
+            import torch.nn.functional as F
+            distiller = F.interpolate(distiller, size=32, mode="bilinear")
+            distiller_target = F.interpolate(distiller_target, size=32, mode="bilinear")
+            diffs = (distiller - distiller_target) ** 2
+        return {"loss": mean_flat(diffs) * weights}
+
+    def progdist_losses(self, *args, **kwargs):
+        raise NotImplementedError("progressive distillation (progdist_losses, reference :243-335) is not implemented")
+
+    def _consistency_losses_hip(self, nets, x_start, num_scales, model_kwargs, teacher_diffusion, noise, indices):
+        from dxmi_hip import graph as _graph
+        from dxmi_hip import ops
+        net, target = nets[0], nets[1]
+        teacher = nets[2] if len(nets) > 2 else None
+        if x_start.requires_grad or noise.requires_grad:
+            raise NotImplementedError("consistency_losses on the HIP U-Net differentiates the online network's parameters only: "
+                                      "x_start and noise must not require grad")
+        if _graph.current() is not None:
+            raise NotImplementedError("consistency_losses: capturing the consistency step into a hipGraph is not supported")
+        extra = set(model_kwargs) - {"y"}
+        if extra:
+            raise NotImplementedError(f"consistency_losses on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
+        y = model_kwargs.get("y")
+        for n in nets:
+            if (y is not None) != (n.num_classes is not None):
+                raise ValueError("must specify y if and only if the model is class-conditional")
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        x_start, noise = f32(x_start), f32(noise)
+        indices = indices.detach().to(device=x_start.device, dtype=torch.int64).reshape(-1).contiguous()
+        if noise.shape != x_start.shape or indices.numel() != x_start.shape[0] or x_start.dim() != 4:
+            raise ValueError(f"consistency_losses: noise {tuple(noise.shape)} must match x_start {tuple(x_start.shape)} [N, C, H, W] "
+                             f"and indices ({indices.numel()}) hold one level per sample")
+        tab = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).device_table(x_start.device)
+        args = (self, net, target, teacher, teacher_diffusion, x_start, noise, indices, tab, y)
+        if torch.is_grad_enabled():
+            loss = _CDLossFn.apply(*args, *ops.fast_parameters(net))
+        else:
+            import types
+            loss = _CDLossFn.forward(types.SimpleNamespace(set_materialize_grads=lambda v: None), *args, *ops.fast_parameters(net))
+        return {"loss": loss}
 
     def denoise(self, model, x_t, sigmas, **model_kwargs):
         scal = self.get_scalings_for_boundary_condition(sigmas) if self.distillation else self.get_scalings(sigmas)

@@ -1,13 +1,23 @@
 """`models.cm.script_util` — model/diffusion factory with the reference keyword surface
-(reference: models/cm/script_util.py:22-157).  YAML `diffusion:` blocks written for the reference
-instantiate unchanged: create_model_and_diffusion(**cfg.diffusion).
+(reference: models/cm/script_util.py:10-219).  YAML `diffusion:` blocks written for the reference
+instantiate unchanged: create_model_and_diffusion(**cfg.diffusion).  cm_train_defaults and create_ema_and_scales_fn are the
+consistency-training side (models.cm.train_util.CMTrainLoop); `loss_norm` is set on the diffusion object by the caller.
 """
 import argparse
+
+import numpy as np
 
 from .karras_diffusion import KarrasDenoiser
 from .unet import UNetModel
 
 NUM_CLASSES = 1000
+
+
+def cm_train_defaults():
+    """The reference's keys and values (:10-23), but loss_norm "l2": there are no LPIPS weights here."""
+    return dict(teacher_model_path="", teacher_dropout=0.1, training_mode="consistency_distillation", target_ema_mode="fixed",
+                scale_mode="fixed", total_training_steps=600000, start_ema=0.0, start_scales=40, end_scales=40,
+                distill_steps_per_iter=50000, loss_norm="l2")
 
 
 def model_and_diffusion_defaults():
@@ -49,6 +59,39 @@ def create_model(image_size, num_channels, num_res_blocks, channel_mult="", lear
                      num_heads=num_heads, num_head_channels=num_head_channels, num_heads_upsample=num_heads_upsample,
                      use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown,
                      use_new_attention_order=use_new_attention_order)
+
+
+def create_ema_and_scales_fn(target_ema_mode, start_ema, scale_mode, start_scales, end_scales, total_steps, distill_steps_per_iter):
+    """step -> (target EMA rate: float, num_scales: int) for the reference's four (target_ema_mode, scale_mode) pairs (:161-219)."""
+    pair = (target_ema_mode, scale_mode)
+    if pair not in (("fixed", "fixed"), ("fixed", "progressive"), ("adaptive", "progressive"), ("fixed", "progdist")):
+        raise NotImplementedError(f"target_ema_mode={target_ema_mode!r} with scale_mode={scale_mode!r}")
+
+    def progressive_scales(step):
+        scales = np.ceil(np.sqrt((step / total_steps) * ((end_scales + 1) ** 2 - start_scales ** 2) + start_scales ** 2) - 1).astype(np.int32)
+        return np.maximum(scales, 1)
+
+    def ema_and_scales_fn(step):
+        if pair == ("fixed", "fixed"):
+            target_ema, scales = start_ema, start_scales
+        elif pair == ("fixed", "progressive"):
+            target_ema, scales = start_ema, progressive_scales(step) + 1
+        elif pair == ("adaptive", "progressive"):
+            scales = progressive_scales(step)
+            c = -np.log(start_ema) * start_scales
+            target_ema = np.exp(-c / scales)
+            scales = scales + 1
+        else:
+            distill_stage = step // distill_steps_per_iter
+            scales = np.maximum(start_scales // (2 ** distill_stage), 2)
+            sub_stage = np.maximum(step - distill_steps_per_iter * (np.log2(start_scales) - 1), 0)
+            sub_stage = sub_stage // (distill_steps_per_iter * 2)
+            sub_scales = np.maximum(2 // (2 ** sub_stage), 1)
+            scales = np.where(scales == 2, sub_scales, scales)
+            target_ema = 1.0
+        return float(target_ema), int(scales)
+
+    return ema_and_scales_fn
 
 
 def add_dict_to_argparser(parser, default_dict):

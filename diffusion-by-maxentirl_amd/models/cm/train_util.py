@@ -12,6 +12,16 @@ step).  What differs:
   * the logged terms are summed on the device and read back once per `log_interval` steps (dumpkvs), as their means.
 The reference's bookkeeping is kept as it is: the step counter advances, and the EMA moves, only on steps the optimiser took
 (an fp16 overflow skips both); after a resume `step` starts at the resumed step and _anneal_lr / save add resume_step to it.
+
+CMTrainLoop (reference :267-566) trains a consistency model by distillation from an EDM teacher or by consistency training, with
+KarrasDenoiser.consistency_losses.  It keeps the reference's own bookkeeping, which differs from TrainLoop's: `step` and
+`global_step` advance AFTER the EMA updates of a step the optimiser took, the target network follows the masters by an EMA whose
+rate comes from ema_scale_fn(global_step) (one dxmi_ema_update launch series on the device), checkpoints are named by
+global_step, and target_model%06d.pt (plus, with the first save, teacher_model%06d.pt) is written next to TrainLoop's files and
+read back on resume (a checkpoint later than the first finds the teacher under the first save's name in the same directory;
+where there is none, the teacher the caller passed is kept).  An fp16 overflow step skips the target EMA on the host, from the
+flag optimize() has already read back, so its launch passes no found_inf as the other EMA launches can.  progdist is not
+implemented.
 """
 import json
 import os
@@ -22,7 +32,7 @@ import torch.distributed as dist
 from dxmi_hip.dist import broadcast_parameters, is_distributed
 from dxmi_hip.optim import RAdam
 
-from .fp16_util import MixedPrecisionTrainer
+from .fp16_util import MixedPrecisionTrainer, get_param_groups_and_shapes, make_master_params, master_params_to_model_params
 from .nn import update_ema, update_ema_rates
 
 INITIAL_LOG_LOSS_SCALE = 20.0
@@ -189,6 +199,163 @@ class TrainLoop:
             with open(os.path.join(self.log_dir, "progress.jsonl"), "a") as f:
                 f.write(json.dumps(row) + "\n")
         return row
+
+
+class CMTrainLoop(TrainLoop):
+    def __init__(self, *, target_model, teacher_model, teacher_diffusion, training_mode, ema_scale_fn, total_training_steps, **kwargs):
+        if training_mode == "progdist":
+            raise NotImplementedError("CMTrainLoop: progressive distillation (progdist) is not implemented")
+        if training_mode not in ("consistency_distillation", "consistency_training"):
+            raise ValueError(f"Unknown training mode {training_mode}")
+        if target_model is None:
+            raise NotImplementedError("Must have a target model")
+        if training_mode == "consistency_distillation" and (teacher_model is None or teacher_diffusion is None):
+            raise ValueError("CMTrainLoop: consistency_distillation needs teacher_model and teacher_diffusion")
+        if kwargs.get("schedule_sampler") is None:      # consistency_losses draws its own levels: only `weights` is used
+            kwargs["schedule_sampler"] = _UnitWeights()
+        super().__init__(**kwargs)
+        self.training_mode, self.ema_scale_fn = training_mode, ema_scale_fn
+        self.target_model, self.teacher_model, self.teacher_diffusion = target_model, teacher_model, teacher_diffusion
+        self.total_training_steps = total_training_steps
+        self._teacher_saved = False
+
+        self._load_and_sync_side_model(self.target_model, "target_model")
+        self.target_model.requires_grad_(False)
+        self.target_model.train()
+        if self.use_fp16:       # flat fp32 masters in the trainer's groups, the target parameters views of them on the device
+            self.target_model_param_groups_and_shapes = get_param_groups_and_shapes(self.target_model.named_parameters())
+            self.target_model_master_params = [p.detach().requires_grad_(False) for p in
+                                               make_master_params(self.target_model_param_groups_and_shapes)]
+            _alias_params_into_masters(self.target_model_param_groups_and_shapes, self.target_model_master_params)
+        else:                   # the trainer's masters are the model parameters themselves: so are the target's
+            self.target_model_param_groups_and_shapes = None
+            self.target_model_master_params = [p.detach() for p in self.target_model.parameters()]
+        if self.teacher_model is not None:
+            self._load_and_sync_side_model(self.teacher_model, "teacher_model")
+            self.teacher_model.requires_grad_(False)
+            self.teacher_model.eval()
+        self.global_step = self.step
+
+    def _load_and_sync_side_model(self, net, prefix):
+        if self.resume_checkpoint:
+            path, name = os.path.split(self.resume_checkpoint)
+            ckpt = os.path.join(path, name.replace("model", prefix))
+            if not os.path.exists(ckpt) and prefix == "teacher_model":
+                # the teacher never changes and is written with the first save only: a later checkpoint resumes from that file
+                found = sorted(f for f in os.listdir(path or ".") if f.startswith("teacher_model") and f.endswith(".pt"))
+                if found:
+                    ckpt = os.path.join(path, found[0])
+            if os.path.exists(ckpt):
+                net.load_state_dict(torch.load(ckpt, map_location=self.device))
+        broadcast_parameters(net)
+        if is_distributed():
+            with torch.no_grad():
+                for b in net.buffers():
+                    dist.broadcast(b, 0)
+
+    def run_loop(self):
+        saved = False
+        while not self.lr_anneal_steps or self.step < self.lr_anneal_steps or self.global_step < self.total_training_steps:
+            batch, cond = next(self.data)
+            self.run_step(batch, cond)
+            saved = False
+            if self.global_step and self.save_interval != -1 and self.global_step % self.save_interval == 0:
+                self.save()
+                saved = True
+                if os.environ.get("DIFFUSION_TRAINING_TEST", "") and self.step > 0:
+                    return
+            if self.global_step % self.log_interval == 0:
+                self.dumpkvs()
+        if not saved:
+            self.save()
+
+    def run_step(self, batch, cond):
+        self.forward_backward(batch, cond)
+        took_step = self.mp_trainer.optimize(self.opt)
+        if took_step:           # an fp16 overflow step moves neither EMA: optimize() has read the flag back already
+            self._update_ema()
+            self._update_target_ema()
+            self.step += 1
+            self.global_step += 1
+        self._anneal_lr()
+        self.log_step()
+        return took_step
+
+    def _update_target_ema(self):
+        target_ema, _ = self.ema_scale_fn(self.global_step)
+        with torch.no_grad():
+            update_ema(self.target_model_master_params, [p.detach() for p in self.mp_trainer.master_params], rate=target_ema)
+            if self.target_model_param_groups_and_shapes is not None:
+                master_params_to_model_params(self.target_model_param_groups_and_shapes, self.target_model_master_params)
+            else:
+                torch.autograd.graph.increment_version(list(self.target_model.parameters()))
+        net = self.target_model.module if hasattr(self.target_model, "module") else self.target_model
+        if hasattr(net, "refresh_packs") and next(net.parameters()).is_cuda:
+            net.refresh_packs()
+
+    def forward_backward(self, batch, cond):
+        self.mp_trainer.zero_grad()
+        for i in range(0, batch.shape[0], self.microbatch):
+            micro = batch[i:i + self.microbatch].to(self.device)
+            micro_cond = {k: v[i:i + self.microbatch].to(self.device) for k, v in cond.items()}
+            _, weights = self.schedule_sampler.sample(micro.shape[0], self.device)
+            _, num_scales = self.ema_scale_fn(self.global_step)
+            distill = self.training_mode == "consistency_distillation"
+            losses = self.diffusion.consistency_losses(self.ddp_model, micro, num_scales, target_model=self.target_model,
+                                                       teacher_model=self.teacher_model if distill else None,
+                                                       teacher_diffusion=self.teacher_diffusion if distill else None,
+                                                       model_kwargs=micro_cond)
+            loss = (losses["loss"] * weights).mean()
+            self._log_loss_dict({k: v * weights for k, v in losses.items()})
+            self.mp_trainer.backward(loss)
+
+    def save(self):
+        step = self.global_step
+
+        def save_checkpoint(rate, params):
+            state_dict = self.mp_trainer.master_params_to_state_dict(params)
+            if _rank() == 0:
+                name = f"model{step:06d}.pt" if not rate else f"ema_{rate}_{step:06d}.pt"
+                torch.save({k: v.detach().clone() for k, v in state_dict.items()}, os.path.join(self.log_dir, name))
+
+        os.makedirs(self.log_dir, exist_ok=True)
+        for rate, params in zip(self.ema_rate, self.ema_params):
+            save_checkpoint(rate, params)
+        if _rank() == 0:
+            torch.save(self.opt.state_dict(), os.path.join(self.log_dir, f"opt{step:06d}.pt"))
+            torch.save({k: v.detach().clone() for k, v in self.target_model.state_dict().items()},
+                       os.path.join(self.log_dir, f"target_model{step:06d}.pt"))
+            if self.teacher_model is not None and not self._teacher_saved:      # the teacher never changes: written once
+                torch.save({k: v.detach().clone() for k, v in self.teacher_model.state_dict().items()},
+                           os.path.join(self.log_dir, f"teacher_model{step:06d}.pt"))
+        self._teacher_saved = True
+        save_checkpoint(0, self.mp_trainer.master_params)
+        if is_distributed():
+            dist.barrier()
+
+    def log_step(self):
+        self._kv = {"step": self.global_step, "samples": (self.global_step + 1) * self.global_batch}
+
+
+class _UnitWeights:
+    """schedule_sampler of CMTrainLoop when none is given: unit loss weights (consistency_losses draws the levels itself)."""
+
+    def sample(self, batch_size, device):
+        return None, torch.ones(batch_size, dtype=torch.float32, device=device)
+
+
+def _alias_params_into_masters(param_groups_and_shapes, master_params):
+    """Device fp32 parameters become views of their slices of the flat masters (as MixedPrecisionTrainer does for the model it
+    trains): the EMA of the masters then IS the update of the network, with nothing to copy."""
+    params = [p for group, _ in param_groups_and_shapes for _, p in group]
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        return
+    for master, (group, _) in zip(master_params, param_groups_and_shapes):
+        flat, off = master.detach().view(-1), 0
+        for _, p in group:
+            p.data = flat[off:off + p.numel()].view_as(p)
+            off += p.numel()
+    torch.autograd.graph.increment_version(params)
 
 
 def parse_resume_step_from_filename(filename):

@@ -97,6 +97,11 @@ def _next_dropout_seed(net):
     """32-bit seed of the next dropout site (ops.dropout_site_seed of the base seed and a running site counter).  The base is
     `net.dropout_seed` if set, else torch.initial_seed().  The counter lives on the net and is not part of a checkpoint: a run
     resumed with dropout > 0 draws the masks of a fresh net again, so it is not bit-exact with the run it continues."""
+    feed = net.__dict__.get("_dropout_seed_feed")
+    if feed is not None:    # seeds handed over by the caller (the target net of consistency_losses takes the online net's)
+        if not feed:
+            raise RuntimeError("dropout seed hand-over: the net has more dropout sites than seeds were handed to it")
+        return feed.pop(0)
     base = torch.initial_seed() if getattr(net, "dropout_seed", None) is None else int(net.dropout_seed)
     n = net.__dict__.get("_dropout_calls", 0)
     net.__dict__["_dropout_calls"] = n + 1

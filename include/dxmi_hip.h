@@ -588,6 +588,49 @@ int dxmi_edm_dsm_loss_bwd(const float* g_mse, const float* g_xs, const float* mo
 int dxmi_ema_update(void* const* ema, const void* const* src, const int64_t* numel, int32_t count, int32_t n_rates,
                     const double* rates, const float* found_inf, void* stream);
 
+/* Consistency distillation / consistency training losses (KarrasDenoiser.consistency_losses, models/cm/karras_diffusion.py:108-241),
+ * one launch between two network evaluations.  fp32 NCHW [N, CHW] tensors (CHW a multiple of 4, 16-byte aligned); indices: int64
+ * [N] on the DEVICE; t_table: fp32 [num_scales] on the DEVICE, the time ladder of :180-188 built on the host: t = t_table[index],
+ * t2 = t_table[index + 1].  An index outside [0, num_scales - 2] gives NaN levels; nothing outside the table is read.  Every fp32
+ * operation in the reference's order, one rounding per torch op (true division by t; (d + next_d) * ((t2 - t) / 2)).
+ * dxmi_cd_prep (:190, denoise :345-349): x_t = x_start + noise t (kept), x_in = c_in(t) x_t, t_out = 250 ln(t + 1e-44) — the online
+ *   net's input; x_in_teacher (NULL: not written) = c_in(t) x_t under teacher_sigma_data, for a teacher diffusion whose sigma_data
+ *   differs (its time is t_out: the time does not depend on sigma_data).
+ * dxmi_cd_solver (euler_solver :164-174, heun_solver :144-162), the denoiser formed with the SOLVER diffusion's scalings (the
+ *   teacher's sigma_data / sigma_min / distillation flag; denoise() does not clamp) and x_in_next scaled by c_in(t2) under
+ *   next_sigma_data, t_next = 250 ln(t2 + 1e-44):
+ *     EULER_X0   x_t2 = x_t + ((x_t - x_start) / t) (t2 - t); x_in_next = the TARGET net's input (no network between).
+ *     HEUN_PRED  model_out = the teacher at (x_t, t): d = (x_t - denoiser) / t and samples = x_t + d (t2 - t) are written;
+ *                x_in_next = the teacher's second input c_in(t2) samples.
+ *     HEUN_CORR  model_out = the teacher at (samples, t2): next_d = (samples - denoiser) / t2,
+ *                x_t2 = x_t + (d + next_d) ((t2 - t) / 2); x_in_next = the TARGET net's input.
+ * dxmi_cd_loss_fwd (:193-220): distiller = c_out(t) f_online + c_skip(t) x_t, target = c_out(t2) f_target + c_skip(t2) x_t2
+ *   (boundary-condition scalings when distillation != 0), diffs = |.| (L1), (.)^2 (L2), or (.)^2 after both were resized to
+ *   32 x 32 by F.interpolate(size=32, mode="bilinear") (L2_32: align_corners False, no antialias, two taps per axis);
+ *   loss[n] = mean_flat(diffs) * get_weightings(weight_schedule, t^-2) (DXMI_DSM_W_*).  Sums in a fixed order (bitwise reproducible).
+ * dxmi_cd_loss_bwd: d_f_online of loss for the DEVICE [N] upstream gradient g_loss: autograd's nodes in its order; L1 uses
+ *   sign with sign(0) = 0 (th.abs), L2_32 the transpose of the resize. */
+#define DXMI_CD_EULER_X0   0
+#define DXMI_CD_HEUN_PRED  1
+#define DXMI_CD_HEUN_CORR  2
+#define DXMI_CD_NORM_L1    0
+#define DXMI_CD_NORM_L2    1
+#define DXMI_CD_NORM_L2_32 2
+int dxmi_cd_prep(const float* x_start, const float* noise, const int64_t* indices, const float* t_table, int32_t num_scales,
+                 float* x_t, float* x_in, float* t_out, float* x_in_teacher, int32_t N, int32_t CHW, float sigma_data,
+                 float teacher_sigma_data, void* stream);
+int dxmi_cd_solver(int32_t mode, const float* x_start, const float* x_t, const float* model_out, float* d, float* samples,
+                   const int64_t* indices, const float* t_table, int32_t num_scales, float* x_t2, float* x_in_next, float* t_next,
+                   int32_t N, int32_t CHW, float solver_sigma_data, float solver_sigma_min, int32_t solver_distillation,
+                   float next_sigma_data, void* stream);
+int dxmi_cd_loss_fwd(const float* f_online, const float* f_target, const float* x_t, const float* x_t2, const int64_t* indices,
+                     const float* t_table, int32_t num_scales, float* loss, int32_t N, int32_t C, int32_t H, int32_t W,
+                     int32_t loss_norm, float sigma_data, float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream);
+int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, const float* f_target, const float* x_t, const float* x_t2,
+                     const int64_t* indices, const float* t_table, int32_t num_scales, float* d_f_online, int32_t N, int32_t C,
+                     int32_t H, int32_t W, int32_t loss_norm, float sigma_data, float sigma_min, int32_t distillation,
+                     int32_t weight_schedule, void* stream);
+
 /* TD step of DxMI_Trainer.update_f_v on the replay ring, data side in one launch (reference trainer.py:271-300, :163-169): rows
  * `state_rows[b]` (and `next_rows[b]`, or the dense re-drawn next states of value_resample) of the ring's fp32 [n_src_rows, CHW]
  * trajectory block are gathered into out_state / out_next — the two halves of the batch [next_state | state] the value net

@@ -1,0 +1,554 @@
+"""Consistency distillation / consistency training on the GPU: the kernels of csrc/cm_train.hip against float64 on the same fp32
+operands, run-to-run bits, malformed arguments, consistency_losses on the shrunken U-Nets against the reference
+(tests/golden/cm_train.npz, cm_train_plain.npz), the shared dropout seeds, and CMTrainLoop (target EMA, overflow, resume, the
+saved target under the one-step sampler).
+
+Bounds: elementwise kernel results within 16 u M of float64 (u = 2^-24, M = the magnitude of the operands that meet in the
+result); per-sample sums within 64 u of their magnitude; parameter gradients cosine >= 0.995 and norm within 5 %
+(test_edm_trainer.py).  Per-sample loss of the shrunken nets against the reference: LOSS_REL_BOUND, twice the worst value
+measured on an MI355X (4.085e-3: unet, ct, l2-32; printed by the test); it may not exceed 0.12 = 2 operands x 2 x
+1.5e-2 (the bound the shrunken net's forward is held to) / 0.5 (the fixture's separation ratio).
+"""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as Fn
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+U = 2.0 ** -24
+NORMS = ("l1", "l2", "l2-32")
+LOSS_REL_BOUND = 8.2e-3
+assert LOSS_REL_BOUND <= 0.12
+SMIN = float(np.float32(0.002))      # sigma_min as the fp32 scalar the kernels subtract
+TINY_KW = dict(image_size=16, class_cond=True, learn_sigma=False, num_channels=64, num_res_blocks=1, channel_mult="1,2",
+               num_heads=4, num_head_channels=64, num_heads_upsample=-1, attention_resolutions="8", dropout=0.0,
+               use_checkpoint=False, use_scale_shift_norm=True, resblock_updown=True, use_fp16=False,
+               use_new_attention_order=False, weight_schedule="karras")
+PLAIN = dict(class_cond=False, use_scale_shift_norm=False, resblock_updown=False)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from dxmi_hip import ops as o
+    o.device_check()
+    return o
+
+
+@pytest.fixture(scope="module")
+def g(golden_dir):
+    a = dict(np.load(os.path.join(golden_dir, "cm_train.npz"), allow_pickle=False))
+    a.update(np.load(os.path.join(golden_dir, "cm_train_plain.npz"), allow_pickle=False))
+    return a
+
+
+def build(over=None, salt="", out_scale=1.0, **kw2):
+    from models.cm.script_util import create_model_and_diffusion
+    from oracle.weights import formula_tensor
+    kw = dict(TINY_KW)
+    kw.update(over or {})
+    kw.update(kw2)
+    net, _ = create_model_and_diffusion(**kw)
+    sd = {k: formula_tensor(salt + k, v.shape) for k, v in net.state_dict().items()}
+    for k in ("out.2.weight", "out.2.bias"):
+        sd[k] = sd[k] * out_scale
+    net.load_state_dict(sd)
+    return net.to(DEV).eval()
+
+
+def scal64(s, distill, sd=0.5):
+    s = s.double()
+    if distill:
+        c_skip = sd ** 2 / ((s - SMIN) ** 2 + sd ** 2)
+        c_out = (s - SMIN) * sd / (s ** 2 + sd ** 2) ** 0.5
+    else:
+        c_skip = sd ** 2 / (s ** 2 + sd ** 2)
+        c_out = s * sd / (s ** 2 + sd ** 2) ** 0.5
+    e = lambda v: v[:, None, None, None]
+    return e(c_skip), e(c_out), e(1 / (s ** 2 + sd ** 2) ** 0.5)
+
+
+def operands(N, shape, seed, S=18):
+    from models.cm.karras_diffusion import cd_levels
+    gen = torch.Generator().manual_seed(seed)
+    x0 = torch.rand(N, *shape, generator=gen) * 2 - 1
+    noise = torch.randn(N, *shape, generator=gen)
+    F1, F2, Fs, Ft = (torch.randn(N, *shape, generator=gen) for _ in range(4))
+    idx = torch.randint(0, S - 1, (N,), generator=gen)
+    idx[0] = S - 2                       # the boundary level
+    if N > 1:
+        idx[1] = 0
+    tab = cd_levels(S, 0.002, 80.0, 7.0).table
+    return x0, noise, F1, F2, Fs, Ft, idx, tab
+
+
+def close(got, ref, M, k=16, floor=1e-30):
+    return ((got.cpu().double() - ref).abs() <= k * U * M + floor).all()
+
+
+# ------------------------------------------------------------------------------------------ kernels
+@pytest.mark.parametrize("shape", [(3, 16, 16), (3, 64, 64), (3, 12, 11)])
+@pytest.mark.parametrize("N", [1, 7])
+@pytest.mark.parametrize("distill", [False, True])
+def test_prep_and_solver_vs_fp64(ops, shape, N, distill):
+    x0, noise, F1, F2, _, _, idx, tab = operands(N, shape, 11 + N + shape[1])
+    d = lambda t: t.to(DEV).contiguous()
+    t, t2 = tab[idx], tab[idx + 1]
+    e = lambda v: v.double()[:, None, None, None]
+    x_t, x_in, tm, x_te = ops.cd_prep(d(x0), d(noise), d(idx), d(tab), 0.5, 0.5)
+    assert x_te is None                                             # shared sigma_data: written once
+    _, _, c_in = scal64(t, False)
+    Mx = x0.double().abs() + (noise.double() * e(t)).abs()
+    assert close(x_t, x0.double() + noise.double() * e(t), Mx)
+    assert close(x_in, c_in * x_t.cpu().double(), c_in * x_t.cpu().double().abs(), k=8)
+    assert ((tm.cpu().double() - 250 * torch.log(t.double())).abs() <= 16 * U * 250 * torch.log(t.double()).abs() + 1e-4).all()
+    _, _, _, x_te = ops.cd_prep(d(x0), d(noise), d(idx), d(tab), 0.5, 0.25)
+    _, _, c_in_te = scal64(t, False, sd=0.25)
+    assert close(x_te, c_in_te * x_t.cpu().double(), c_in_te * x_t.cpu().double().abs(), k=8)
+
+    xt = x_t.cpu().double()
+    dt = e(t2) - e(t)
+    _, _, c_in2 = scal64(t2, False)
+    # EULER_X0
+    x_t2, nx, nt = ops.cd_solver(ops.CD_EULER_X0, x_t, d(idx), d(tab), x_start=d(x0))
+    Md = (xt.abs() + x0.double().abs()) / e(t)
+    assert close(x_t2, xt + (xt - x0.double()) / e(t) * dt, xt.abs() + Md * dt.abs())
+    assert close(nx, c_in2 * x_t2.cpu().double(), c_in2 * x_t2.cpu().double().abs(), k=8)
+    assert ((nt.cpu().double() - 250 * torch.log(t2.double())).abs() <= 16 * U * 250 * torch.log(t2.double()).abs() + 1e-4).all()
+    # HEUN_PRED with the solver diffusion's scalings
+    kw = dict(sigma_data=0.5, sigma_min=0.002, distillation=distill, next_sigma_data=0.5)
+    c_skip, c_out, _ = scal64(t, distill)
+    dd, smp, nx, nt = ops.cd_solver(ops.CD_HEUN_PRED, x_t, d(idx), d(tab), model_out=d(F1), **kw)
+    den = c_out * F1.double() + c_skip * xt
+    Md = (xt.abs() + (c_out * F1.double()).abs() + (c_skip * xt).abs()) / e(t)
+    assert close(dd, (xt - den) / e(t), Md)
+    assert close(smp, xt + (xt - den) / e(t) * dt, xt.abs() + Md * dt.abs())
+    assert close(nx, c_in2 * smp.cpu().double(), c_in2 * smp.cpu().double().abs(), k=8)
+    # HEUN_CORR on the fp32 d and samples the kernel wrote
+    c_skip2, c_out2, _ = scal64(t2, distill)
+    s64, d64 = smp.cpu().double(), dd.cpu().double()
+    x_t2, nx, nt = ops.cd_solver(ops.CD_HEUN_CORR, x_t, d(idx), d(tab), model_out=d(F2), d=dd, samples=smp, **kw)
+    den2 = c_out2 * F2.double() + c_skip2 * s64
+    nd = (s64 - den2) / e(t2)
+    Mn = (s64.abs() + (c_out2 * F2.double()).abs() + (c_skip2 * s64).abs()) / e(t2)
+    assert close(x_t2, xt + (d64 + nd) * (dt / 2), xt.abs() + (d64.abs() + Mn) * dt.abs() / 2)
+    assert close(nx, c_in2 * x_t2.cpu().double(), c_in2 * x_t2.cpu().double().abs(), k=8)
+
+
+def _loss_operands(N, shape, seed):
+    x0, noise, F1, F2, Fs, Ft, idx, tab = operands(N, shape, seed)
+    x_t = x0 + noise * tab[idx][:, None, None, None]
+    x_t2 = x0 + F1 * tab[idx + 1][:, None, None, None]
+    return Fs, Ft, x_t, x_t2, idx, tab
+
+
+def _w64(ws, t, sd=0.5):
+    snr = t.double() ** -2
+    return {"karras": snr + 1 / sd ** 2, "uniform": torch.ones_like(snr), "snr": snr}[ws]
+
+
+@pytest.mark.parametrize("shape", [(3, 16, 16), (3, 64, 64), (3, 12, 11), (3, 32, 32)])
+@pytest.mark.parametrize("N", [1, 7])
+@pytest.mark.parametrize("distill", [False, True])
+def test_loss_kernels_vs_fp64(ops, shape, N, distill):
+    Fs, Ft, x_t, x_t2, idx, tab = _loss_operands(N, shape, 23 + N + shape[1])
+    d = lambda t: t.to(DEV).contiguous()
+    dev = [d(v) for v in (Fs, Ft, x_t, x_t2, idx, tab)]
+    t, t2 = tab[idx], tab[idx + 1]
+    cs_s, cs_o, _ = scal64(t, distill)
+    ct_s, ct_o, _ = scal64(t2, distill)
+    gl = torch.randn(N, generator=torch.Generator().manual_seed(N))
+    worst = 0.0
+    for ws in ("karras", "uniform"):
+        w = _w64(ws, t)
+        for norm in NORMS:
+            if norm == "l2-32" and shape[1] == 12:
+                continue                                   # the resize cases are 16 -> 32, 32 -> 32 and 64 -> 32
+            kw = dict(sigma_data=0.5, sigma_min=0.002, distillation=distill)
+            loss = ops.cd_loss_fwd(*dev, norm, ws, **kw)
+            dF = ops.cd_loss_bwd(d(gl), *dev, norm, ws, **kw)
+            F64 = Fs.double().requires_grad_(True)
+            ds = cs_o * F64 + cs_s * x_t.double()
+            dt_ = ct_o * Ft.double() + ct_s * x_t2.double()
+            Me = (cs_o * Fs.double()).abs() + (cs_s * x_t.double()).abs() + (ct_o * Ft.double()).abs() + (ct_s * x_t2.double()).abs()
+            if norm == "l2-32":                            # torch's own resize in float64
+                ds, dt_ = Fn.interpolate(ds, size=32, mode="bilinear"), Fn.interpolate(dt_, size=32, mode="bilinear")
+                Me_o = Fn.interpolate(Me, size=32, mode="bilinear")
+            else:
+                Me_o = Me
+            e = ds - dt_
+            diffs = e.abs() if norm == "l1" else e ** 2
+            ref = diffs.mean((1, 2, 3)) * w
+            (ref * gl.double()).sum().backward()
+            ed = e.detach()
+            if norm == "l1":
+                bound = 64 * U * Me_o.mean((1, 2, 3)) * w + 1e-30
+            else:
+                bound = 64 * U * (Me_o * (ed.abs() + 16 * U * Me_o)).mean((1, 2, 3)) * 2 * w + 1e-30
+            err = (loss.cpu().double() - ref.detach()).abs()
+            assert (err <= bound).all(), (ws, norm, err / bound)
+            worst = max(worst, (err / bound).max().item())
+            D = diffs[0].numel()
+            gs = (gl.double().abs() * w / D)[:, None, None, None]
+            if norm == "l1":
+                ok = ed.abs() > 32 * U * Me                # sign() of a difference inside its rounding error is not determined
+                assert ok.float().mean() > 0.99
+                assert (((dF.cpu().double() - F64.grad).abs() <= 16 * U * gs * cs_o.abs() + 1e-38) | ~ok).all(), (ws, norm)
+            elif norm == "l2":
+                assert close(dF, F64.grad, gs * 2 * Me * cs_o.abs(), floor=1e-38), (ws, norm)
+            else:                                          # magnitude through the transpose of the resize (its weights are >= 0)
+                A = torch.zeros_like(Me, requires_grad=True)
+                (Fn.interpolate(A, size=32, mode="bilinear") * (gs * 2 * Me_o)).sum().backward()
+                assert close(dF, F64.grad, A.grad * cs_o.abs(), floor=1e-38), (ws, norm)
+    print(f"cd loss_fwd worst |err| / bound = {worst:.3e} (shape {shape}, N {N}, distill {distill})")
+
+
+def test_l1_sign_of_zero_is_zero(ops):
+    z = torch.zeros(2, 3, 16, 16, device=DEV)
+    idx, tab = torch.tensor([0, 3], device=DEV), torch.tensor([80.0, 20.0, 5.0, 1.0, 0.002], device=DEV)
+    dF = ops.cd_loss_bwd(torch.ones(2, device=DEV), z, z, z, z, idx, tab, "l1", "uniform")
+    assert torch.equal(dF, z)
+
+
+def test_kernels_reproducible_and_index_guard(ops):
+    Fs, Ft, x_t, x_t2, idx, tab = [v.to(DEV) for v in _loss_operands(16, (3, 64, 64), 3)]
+    gl = torch.rand(16, device=DEV)
+    for norm in NORMS:
+        a, b = (ops.cd_loss_fwd(Fs, Ft, x_t, x_t2, idx, tab, norm, "karras", distillation=True) for _ in range(2))
+        assert torch.equal(a, b)
+        a, b = (ops.cd_loss_bwd(gl, Fs, Ft, x_t, x_t2, idx, tab, norm, "karras", distillation=True) for _ in range(2))
+        assert torch.equal(a, b)
+    x0, noise, F1, F2 = [v.to(DEV) for v in operands(16, (3, 64, 64), 3)[:4]]
+    same = lambda a, b: all(torch.equal(u, v) for u, v in zip(a, b) if u is not None)
+    assert same(ops.cd_prep(x0, noise, idx, tab, 0.5, 0.25), ops.cd_prep(x0, noise, idx, tab, 0.5, 0.25))
+    assert same(ops.cd_solver(ops.CD_EULER_X0, x_t, idx, tab, x_start=x0), ops.cd_solver(ops.CD_EULER_X0, x_t, idx, tab, x_start=x0))
+    p1, p2 = (ops.cd_solver(ops.CD_HEUN_PRED, x_t, idx, tab, model_out=F1, distillation=True) for _ in range(2))
+    assert same(p1, p2)
+    assert same(*(ops.cd_solver(ops.CD_HEUN_CORR, x_t, idx, tab, model_out=F2, d=p1[0], samples=p1[1]) for _ in range(2)))
+    bad = idx.clone()
+    bad[3], bad[5] = tab.numel() - 1, -1                    # t2 / t outside the table: NaN for those samples only, nothing read
+    loss = ops.cd_loss_fwd(Fs, Ft, x_t, x_t2, bad, tab, "l2", "karras")
+    assert torch.isnan(loss[[3, 5]]).all() and torch.isfinite(loss[[0, 1, 2, 4]]).all()
+
+
+def test_wrappers_refuse_malformed_arguments(ops):
+    from dxmi_hip import DxmiError
+    Fs, Ft, x_t, x_t2, idx, tab = [v.to(DEV) for v in _loss_operands(4, (3, 16, 16), 9)]
+    g1 = torch.ones(4, device=DEV)
+    bad_calls = [
+        lambda: ops.cd_prep(x_t, x_t2[:2], idx, tab),
+        lambda: ops.cd_prep(x_t, x_t2, idx[:3], tab),
+        lambda: ops.cd_prep(x_t, x_t2, idx.int(), tab),
+        lambda: ops.cd_prep(x_t, x_t2, idx, tab[:1]),
+        lambda: ops.cd_prep(x_t, x_t2, idx, tab.double()),
+        lambda: ops.cd_prep(x_t.cpu(), x_t2, idx, tab),
+        lambda: ops.cd_prep(x_t.view(-1)[1:1 + 4 * 764].view(4, 764), x_t2.view(4, 768)[:, :764].contiguous(), idx, tab),   # misaligned
+        lambda: ops.cd_solver(ops.CD_EULER_X0, x_t, idx, tab),
+        lambda: ops.cd_solver(ops.CD_HEUN_PRED, x_t, idx, tab),
+        lambda: ops.cd_solver(ops.CD_HEUN_CORR, x_t, idx, tab, model_out=Fs),
+        lambda: ops.cd_solver(7, x_t, idx, tab, x_start=x_t),
+        lambda: ops.cd_solver(ops.CD_HEUN_PRED, x_t, idx, tab, model_out=Fs[:2]),
+        lambda: ops.cd_loss_fwd(Fs, Ft, x_t, x_t2, idx, tab, "lpips", "karras"),
+        lambda: ops.cd_loss_fwd(Fs.view(4, -1), Ft.view(4, -1), x_t.view(4, -1), x_t2.view(4, -1), idx, tab, "l2", "karras"),
+        lambda: ops.cd_loss_fwd(Fs, Ft[:, :, :8], x_t, x_t2, idx, tab, "l2", "karras"),
+        lambda: ops.cd_loss_bwd(g1[:3], Fs, Ft, x_t, x_t2, idx, tab, "l2", "karras"),
+        lambda: ops.cd_loss_bwd(None, Fs, Ft, x_t, x_t2, idx, tab, "l2", "karras"),
+    ]
+    for i, call in enumerate(bad_calls):
+        with pytest.raises(DxmiError):
+            call()
+            pytest.fail(f"malformed call {i} was accepted")
+    with pytest.raises(NotImplementedError):
+        ops.cd_loss_fwd(Fs, Ft, x_t, x_t2, idx, tab, "l2", "no-such-schedule")
+    # the C entry points themselves: a status and a message, no launch
+    lib = ops.load()
+    p = lambda t: t.data_ptr()
+    assert lib.dxmi_cd_prep(p(x_t), p(x_t2), p(idx), p(tab), 1, p(Fs), p(Ft), p(g1), None, 4, 768, 0.5, 0.5, None) != 0
+    assert b"num_scales" in lib.dxmi_last_error()
+    assert lib.dxmi_cd_solver(3, None, p(x_t), None, None, None, p(idx), p(tab), 5, None, p(Fs), p(g1), 4, 768, 0.5, 0.002, 0, 0.5, None) != 0
+    assert lib.dxmi_cd_loss_fwd(p(Fs), p(Ft), p(x_t), p(x_t2), p(idx), p(tab), 18, p(g1), 4, 3, 16, 16, 5, 0.5, 0.002, 0, 2, None) != 0
+    assert b"loss norm" in lib.dxmi_last_error()
+    assert lib.dxmi_cd_loss_bwd(None, p(Fs), p(Ft), p(x_t), p(x_t2), p(idx), p(tab), 18, p(Fs), 4, 3, 16, 16, 1, 0.5, 0.002, 0, 2, None) != 0
+    torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------ consistency_losses on the U-Nets
+def _cos(a, b):
+    a, b = a.double().reshape(-1), b.double().reshape(-1)
+    return float(a @ b / (a.norm() * b.norm() + 1e-300))
+
+
+def _diffusions(norm, ws="karras"):
+    from models.cm.karras_diffusion import KarrasDenoiser
+    return (KarrasDenoiser(sigma_data=0.5, weight_schedule=ws, distillation=True, loss_norm=norm),
+            KarrasDenoiser(sigma_data=0.5, weight_schedule=ws, distillation=False))
+
+
+@pytest.mark.parametrize("tag", ["unet", "unet_plain"])
+def test_consistency_losses_vs_reference(ops, g, tag):
+    over = PLAIN if tag == "unet_plain" else None
+    scale = float(g[f"{tag}.target_out_scale"])
+    online, target, teacher = build(over), build(over, "target:", scale), build(over, "teacher:")
+    for p in online.parameters():
+        p.requires_grad_(True)
+    kw = {"y": torch.from_numpy(g["y"]).to(DEV)} if tag == "unet" else {}
+    x0, noise, idx = (torch.from_numpy(g[k]).to(DEV) for k in ("x_start", "noise", "indices.6"))
+    loss_w = torch.from_numpy(g["loss_w"]).to(DEV)
+    P = dict(online.named_parameters())
+    worst, wc, wn = 0.0, ("", 1.0), ("", 0.0)
+    for mode in ("cd", "ct"):
+        for norm in NORMS:
+            student, teacher_diffusion = _diffusions(norm)
+            online.zero_grad()
+            t = student.consistency_losses(online, x0, 6, model_kwargs=kw, target_model=target,
+                                           teacher_model=teacher if mode == "cd" else None,
+                                           teacher_diffusion=teacher_diffusion if mode == "cd" else None, noise=noise, indices=idx)
+            assert set(t) == {"loss"} and t["loss"].requires_grad
+            (t["loss"] * loss_w).mean().backward()
+            ref = torch.from_numpy(g[f"{tag}.{mode}.{norm}.loss"]).double()
+            rel = ((t["loss"].detach().cpu().double() - ref).abs() / ref.abs()).max().item()
+            print(f"{tag} {mode} {norm}: per-sample loss worst relative error {rel:.3e}")
+            worst = max(worst, rel)
+            for n in g[f"{tag}.grad_names"]:
+                rg = torch.from_numpy(g[f"{tag}.{mode}.{norm}.grad.{n}"]).float()
+                got = P[str(n)].grad.cpu()
+                assert got.shape == rg.shape
+                if rg.norm() < 1e-6 * max(1.0, got.norm().item()):
+                    continue
+                c, nr = _cos(got, rg), (got.norm() / rg.norm()).item()
+                wc = min(wc, (f"{mode}.{norm}.{n}", c), key=lambda v: v[1])
+                wn = max(wn, (f"{mode}.{norm}.{n}", abs(nr - 1)), key=lambda v: v[1])
+                assert c >= 0.995 and abs(nr - 1) <= 0.05, (mode, norm, n, c, nr)
+    print(f"{tag}: per-sample loss worst relative error {worst:.3e} (bound {LOSS_REL_BOUND}); gradient worst cosine {wc[1]:.5f} "
+          f"({wc[0]}), worst norm ratio deviation {wn[1]:.4f} ({wn[0]})")
+    assert worst <= LOSS_REL_BOUND
+
+
+def test_no_grad_path_and_refusals(ops, g):
+    online, target, teacher = build(PLAIN), build(PLAIN, "target:"), build(PLAIN, "teacher:")
+    student, td = _diffusions("l2")
+    x0, noise, idx = (torch.from_numpy(g[k]).to(DEV) for k in ("x_start", "noise", "indices.6"))
+    a = student.consistency_losses(online, x0, 6, target_model=target, teacher_model=teacher, teacher_diffusion=td, noise=noise, indices=idx)
+    with torch.no_grad():
+        b = student.consistency_losses(online, x0, 6, target_model=target, teacher_model=teacher, teacher_diffusion=td, noise=noise,
+                                       indices=idx)
+    assert torch.equal(a["loss"].detach(), b["loss"]) and not b["loss"].requires_grad
+    with pytest.raises(NotImplementedError):
+        student.consistency_losses(online, x0.clone().requires_grad_(True), 6, target_model=target, noise=noise, indices=idx)
+    with pytest.raises(NotImplementedError):
+        student.consistency_losses(online, x0, 6, target_model=target, noise=noise, indices=idx, model_kwargs={"z": 1})
+    with pytest.raises(NotImplementedError, match="Must have a target model"):
+        student.consistency_losses(online, x0, 6, noise=noise, indices=idx)
+    # a mix of HIP and non-HIP models takes the torch path
+    fn = lambda x_in, t, **kw: torch.tanh(x_in)
+    c = student.consistency_losses(online, x0, 6, target_model=fn, noise=noise, indices=idx)["loss"]
+    assert c.shape == (6,) and torch.isfinite(c).all()
+
+
+def test_dropout_online_and_target_share_seeds(ops, g):
+    online, target = build(PLAIN, dropout=0.1), build(PLAIN, "target:", dropout=0.1)
+    online.train()
+    target.train()
+    online.dropout_seed, target.dropout_seed = 5, 77
+    student, _ = _diffusions("l2")
+    x0, noise, idx = (torch.from_numpy(g[k]).to(DEV) for k in ("x_start", "noise", "indices.6"))
+    for p in online.parameters():
+        p.requires_grad_(True)
+    calls = target.__dict__.get("_dropout_calls", 0)
+    t = student.consistency_losses(online, x0, 6, target_model=target, noise=noise, indices=idx)
+    assert len(online.dropout_seeds_used) > 0 and target.dropout_seeds_used == online.dropout_seeds_used
+    assert target.__dict__.get("_dropout_calls", 0) == calls and "_dropout_seed_feed" not in target.__dict__
+    t["loss"].mean().backward()
+    target.eval()                                          # eval: forward_inference, no dropout on the target
+    online.dropout_seed, online._dropout_calls = 5, 0
+    e = student.consistency_losses(online, x0, 6, target_model=target, noise=noise, indices=idx)
+    assert target.dropout_seeds_used == online.dropout_seeds_used          # untouched by the inference forward
+    assert not torch.equal(e["loss"], t["loss"])
+
+
+# ------------------------------------------------------------------------------------------ CMTrainLoop
+class _FixedDraws:
+    def __init__(self, noises, indices, start=0):
+        from models.cm.karras_diffusion import KarrasDenoiser
+        self.d = KarrasDenoiser(sigma_data=0.5, weight_schedule="uniform", distillation=True, loss_norm="l2")
+        self.noises, self.indices, self.i = noises, indices, start
+
+    def consistency_losses(self, model, x_start, num_scales, **kw):
+        n, idx = self.noises[self.i % 8].to(x_start.device), self.indices[self.i % 8].to(x_start.device)
+        self.i += 1
+        return self.d.consistency_losses(model, x_start, num_scales, noise=n, indices=idx, **kw)
+
+
+def _data():
+    gen = torch.Generator().manual_seed(99)
+    x = [torch.rand(4, 3, 16, 16, generator=gen) * 2 - 1 for _ in range(4)]
+    noise = [torch.randn(2, 3, 16, 16, generator=gen) for _ in range(8)]
+    idx = [torch.randint(0, 5, (2,), generator=gen) for _ in range(8)]
+    return x, noise, idx
+
+
+RATES = [0.9, 0.5, 0.95, 0.7, 0.8]
+
+
+def _loop(tmp, mode, resume="", start=0, use_fp16=True):
+    from models.cm.karras_diffusion import KarrasDenoiser
+    from models.cm.train_util import CMTrainLoop
+    _, noise, idx = _data()
+    cd = mode == "consistency_distillation"
+    online = build(PLAIN)
+    online.train()
+    return CMTrainLoop(model=online, target_model=build(PLAIN, "target:"), teacher_model=build(PLAIN, "teacher:") if cd else None,
+                       teacher_diffusion=KarrasDenoiser(weight_schedule="uniform") if cd else None, training_mode=mode,
+                       ema_scale_fn=lambda step: (RATES[step], 6), total_training_steps=4,
+                       diffusion=_FixedDraws(noise, idx, 2 * start), data=None, batch_size=4, microbatch=2, lr=1e-4, ema_rate="0.999,0.9",
+                       log_interval=2, save_interval=100, resume_checkpoint=resume, use_fp16=use_fp16, log_dir=str(tmp))
+
+
+def _run3(tmp, mode, save_at=None):
+    x, _, _ = _data()
+    tl = _loop(tmp, mode)
+    t0 = [p.detach().clone() for p in tl.target_model_master_params]
+    masters, targets = [], []
+    for k in range(3):
+        assert tl.run_step(x[k], {})
+        assert tl.step == k + 1 and tl.global_step == k + 1
+        masters.append([p.detach().clone() for p in tl.mp_trainer.master_params])
+        targets.append([p.detach().clone() for p in tl.target_model_master_params])
+        if save_at == k:
+            tl.save()
+            tl.lg_saved = tl.mp_trainer.lg_loss_scale
+    return tl, t0, masters, targets
+
+
+@pytest.mark.parametrize("mode", ["consistency_distillation", "consistency_training"])
+def test_cmtrainloop_on_the_device(ops, tmp_path, mode):
+    from models.cm.karras_diffusion import KarrasDenoiser, karras_sample
+    x, _, _ = _data()
+    tl, t0, masters, targets = _run3(tmp_path / "a", mode, save_at=1)
+    _, _, masters_b, targets_b = _run3(tmp_path / "b", mode)
+    for a, b in zip(masters + targets, masters_b + targets_b):              # two runs, bit for bit
+        assert all(torch.equal(u, v) for u, v in zip(a, b))
+    # The float64 EMA recursion of the recorded masters.  The target and the masters are different weight sets, so the two terms
+    # may cancel: the bound is on their magnitudes M_k = r M_(k-1) + (1 - r) |master| (4 u M per update, the bound of
+    # test_ema_update_vs_fp64; the errors of earlier steps shrink by r and M_k >= r M_(k-1), so three steps stay within 12 u M_k).
+    rec, mag = [t.double() for t in t0], [t.double().abs() for t in t0]
+    for k in range(3):
+        r, q = np.float32(RATES[k]).astype(np.float64), np.float32(1 - RATES[k]).astype(np.float64)
+        rec = [r * a + q * m.double() for a, m in zip(rec, masters[k])]
+        mag = [r * a + q * m.double().abs() for a, m in zip(mag, masters[k])]
+        for a, b, M in zip(targets[k], rec, mag):
+            assert ((a.double() - b).abs() <= 12 * U * M + 1e-30).all()
+    # the target NETWORK follows its masters, and its packed weights follow the network
+    flat = torch.cat([p.detach().reshape(-1) for grp, _ in tl.target_model_param_groups_and_shapes for _, p in grp])
+    assert torch.equal(flat, torch.cat([m.reshape(-1) for m in tl.target_model_master_params]))
+    net = tl.target_model
+    assert net._packed_key == net._param_key()
+    row = tl.dumpkvs()
+    assert row["step"] == 3 and math.isfinite(row["loss"])
+    files = set(os.listdir(tmp_path / "a"))
+    want = {"ema_0.999_000002.pt", "ema_0.9_000002.pt", "model000002.pt", "opt000002.pt", "target_model000002.pt"}
+    assert want | ({"teacher_model000002.pt"} if mode == "consistency_distillation" else set()) <= files
+
+    # an fp16 overflow step: no optimiser step, no EMA, no target move, no counters
+    before = [p.clone() for p in tl.target_model_master_params + [q for ps in tl.ema_params for q in ps] + list(tl.mp_trainer.master_params)]
+    tl.mp_trainer.lg_loss_scale = 400.0
+    assert not tl.run_step(x[3], {})
+    assert tl.step == 3 and tl.global_step == 3 and tl.mp_trainer.lg_loss_scale == 399.0
+    after = tl.target_model_master_params + [q for ps in tl.ema_params for q in ps] + list(tl.mp_trainer.master_params)
+    assert all(torch.equal(a.detach(), b) for a, b in zip(after, before))
+
+    # resume from the save after step 2: the target / teacher files come back, and step 3 is the uninterrupted run's
+    tr = _loop(tmp_path / "a", mode, resume=str(tmp_path / "a" / "model000002.pt"), start=2)
+    assert tr.global_step == 2 and tr.step == 2
+    assert all(torch.equal(a, b) for a, b in zip(tr.target_model_master_params, targets[1]))
+    tr.mp_trainer.lg_loss_scale = tl.lg_saved       # the reference does not checkpoint the loss scale
+    assert tr.run_step(x[2], {})
+    assert tr.global_step == 3
+    assert all(torch.equal(a.detach(), b) for a, b in zip(tr.mp_trainer.master_params, masters[2]))
+    assert all(torch.equal(a, b) for a, b in zip(tr.target_model_master_params, targets[2]))
+
+    # the saved target loads into a fresh UNetModel and samples in one step
+    fresh = build(PLAIN, "other:")
+    fresh.load_state_dict(torch.load(tmp_path / "a" / "target_model000002.pt", map_location=DEV))
+    out = karras_sample(KarrasDenoiser(sigma_data=0.5, distillation=True), fresh, (2, 3, 16, 16), steps=6, device=DEV, sampler="onestep",
+                        generator=None)
+    assert out.shape == (2, 3, 16, 16) and torch.isfinite(out).all() and out.min() >= -1 and out.max() <= 1
+
+
+def test_target_with_other_dropout_sites_is_an_error(ops, g):
+    """The hand-over of the dropout seeds is exact: a target with more, or fewer, dropout sites than the online net raises."""
+    online = build(PLAIN, dropout=0.1)
+    student, _ = _diffusions("l2")
+    x0, noise, idx = (torch.from_numpy(g[k]).to(DEV) for k in ("x_start", "noise", "indices.6"))
+    online.train()
+    for blocks in (2, 1):
+        online2 = build(PLAIN, dropout=0.1, num_res_blocks=blocks).train() if blocks == 2 else online
+        target = build(PLAIN, "target:", dropout=0.1, num_res_blocks=3 - blocks).train()
+        with pytest.raises(RuntimeError, match="dropout seed hand-over"):
+            student.consistency_losses(online2, x0, 6, target_model=target, noise=noise, indices=idx)
+        assert "_dropout_seed_feed" not in target.__dict__
+
+
+@pytest.mark.parametrize("mode", ["consistency_distillation", "consistency_training"])
+def test_cli_cm_train_then_onestep_sample(ops, tmp_path, mode):
+    """cm_train.py, 2 synthetic iterations on a shrunken config (distillation: from a saved teacher state dict); the
+    target_model file it writes loads into a fresh UNetModel and samples in one step."""
+    import subprocess
+    import sys
+    from models.cm.karras_diffusion import KarrasDenoiser, karras_sample
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "diffusion-by-maxentirl_amd")
+    shrunk = dict(image_size=16, num_channels=64, num_res_blocks=1, channel_mult="1,2", attention_resolutions="8", num_head_channels=64,
+                  class_cond=True, resblock_updown=True)
+    args = [a for k, v in shrunk.items() for a in (f"--{k}", str(v))]
+    over = dict(TINY_KW, **{k: v for k, v in shrunk.items()})
+    teacher = build(over, "teacher:")
+    if mode == "consistency_distillation":
+        torch.save(teacher.state_dict(), tmp_path / "teacher.pt")
+        args += ["--teacher_model_path", str(tmp_path / "teacher.pt")]
+    env = dict(os.environ, LOCAL_RANK="0", WORLD_SIZE="1", RANK="0")
+    r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, "cm_train.py", "--training_mode", mode, "--synthetic_data", "True",
+                        "--max_iters", "2", "--batch_size", "4", "--microbatch", "2", "--use_fp16", "True", "--start_scales", "6",
+                        "--end_scales", "6", "--save_interval", "2", "--log_interval", "1", "--ema_rate", "0.999,0.9",
+                        "--lr", "0.0" if mode == "consistency_distillation" else "1e-4",
+                        "--log_dir", str(tmp_path / "run")] + args, cwd=pkg, env=env, capture_output=True, text=True, timeout=700)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    files = set(os.listdir(tmp_path / "run"))
+    want = {"model000002.pt", "target_model000002.pt", "opt000002.pt", "ema_0.999_000002.pt", "ema_0.9_000002.pt", "progress.jsonl"}
+    assert want | ({"teacher_model000002.pt"} if mode == "consistency_distillation" else set()) <= files, files
+    sd = torch.load(tmp_path / "run" / "target_model000002.pt", map_location=DEV)
+    fresh = build(over, "other:")
+    fresh.load_state_dict(sd)
+    assert all(torch.isfinite(v).all() for v in sd.values())
+    if mode == "consistency_distillation":      # student and target start from the teacher: at lr 0 they are still its weights
+        te = teacher.state_dict()
+        saved_te = torch.load(tmp_path / "run" / "teacher_model000002.pt", map_location=DEV)
+        student = torch.load(tmp_path / "run" / "model000002.pt", map_location=DEV)
+        for k, v in te.items():
+            assert torch.equal(saved_te[k], v) and torch.equal(sd[k], v) and torch.equal(student[k], v), k
+    out = karras_sample(KarrasDenoiser(sigma_data=0.5, distillation=True), fresh, (2, 3, 16, 16), steps=6, device=DEV, sampler="onestep",
+                        model_kwargs={"y": torch.tensor([1, 2], device=DEV)})
+    assert torch.isfinite(out).all() and out.min() >= -1 and out.max() <= 1
+
+
+def test_imagenet64_full_size_cd_step(ops):
+    from backward_census import EDM_DSM_MODEL as kw                       # the full-size set-up of the DSM step (dropout 0.1, fp16)
+    from models.cm.karras_diffusion import KarrasDenoiser
+    from models.cm.script_util import create_model_and_diffusion
+    torch.manual_seed(0)
+    online, student = create_model_and_diffusion(**dict(kw, distillation=True))
+    target, _ = create_model_and_diffusion(**kw)
+    teacher, teacher_diffusion = create_model_and_diffusion(**kw)
+    online, target, teacher = online.to(DEV).train(), target.to(DEV).train().requires_grad_(False), teacher.to(DEV).eval().requires_grad_(False)
+    assert isinstance(student, KarrasDenoiser) and student.distillation
+    x0 = torch.rand(2, 3, 64, 64, device=DEV) * 2 - 1
+    t = student.consistency_losses(online, x0, 40, model_kwargs={"y": torch.arange(2, device=DEV)}, target_model=target,
+                                   teacher_model=teacher, teacher_diffusion=teacher_diffusion)
+    t["loss"].mean().backward()
+    assert torch.isfinite(t["loss"]).all() and t["loss"].shape == (2,)
+    assert target.dropout_seeds_used == online.dropout_seeds_used and len(online.dropout_seeds_used) > 0
+    for p in online.parameters():
+        assert p.grad is not None and p.grad.shape == p.shape and torch.isfinite(p.grad).all()
+    print(f"imagenet64 CD step at 2 images: loss {t['loss'].tolist()}")
