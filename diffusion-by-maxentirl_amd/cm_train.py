@@ -12,7 +12,8 @@ from the teacher's weights, the teacher's diffusion has distillation=False and t
 checkpoints it writes are what `generate_large.py --cm_sampler onestep --pretrained ...` reads.  Real-data loaders are not part of
 this package: --synthetic_data True draws uniform images and labels.  CMTrainLoop.run_loop keeps the reference's condition, which
 ends only when both lr_anneal_steps and total_training_steps are reached: --max_iters N (smoke runs) sets both to N, so the
-learning rate anneals to zero over those N steps.
+learning rate anneals to zero over those N steps.  --loss_norm lpips needs the VGG16 and LPIPS linear weight files:
+--lpips_vgg16 PATH --lpips_lin PATH, or DXMI_LPIPS_VGG16 / DXMI_LPIPS_LIN in the environment; without them it is refused.
 """
 import argparse
 import os
@@ -43,7 +44,7 @@ def main():
     defaults.update(cm_train_defaults())
     defaults.update(synthetic_data=False, batch_size=16, microbatch=-1, lr=1e-4, ema_rate="0.9999", log_dir="results/cm_train",
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
-                    fp16_scale_growth=1e-3, seed=42, batch_invariant=False)
+                    fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="")
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
     args = ap.parse_args()
@@ -67,8 +68,13 @@ def main():
     model_kw = args_to_dict(args, model_and_diffusion_defaults().keys())
     model, diffusion = create_model_and_diffusion(distillation=True, **model_kw)
     diffusion.loss_norm = args.loss_norm
-    if args.loss_norm == "lpips":
-        raise NotImplementedError("loss_norm='lpips': no LPIPS weights are available to this package; use l1, l2 or l2-32")
+    if args.loss_norm == "lpips":      # refused here, before the target and the teacher are built, when no weights were named
+        from models.cm.karras_diffusion import _NO_LPIPS
+        from models.cm.lpips import ENV_LIN, ENV_VGG16, LPIPS
+        vgg, lin = args.lpips_vgg16 or os.environ.get(ENV_VGG16), args.lpips_lin or os.environ.get(ENV_LIN)      # a flag wins
+        if not vgg or not lin:
+            raise NotImplementedError(_NO_LPIPS)
+        diffusion.lpips_loss = LPIPS.from_files(vgg, lin)
     target_model, _ = create_model_and_diffusion(distillation=True, **model_kw)
     teacher_model = teacher_diffusion = None
     if distill:

@@ -357,6 +357,51 @@ __global__ __launch_bounds__(EW_BLOCK) void cd_loss32_bwd_kernel(const float* __
     }
 }
 
+// loss_norm lpips: the two images the LPIPS network reads, (distiller + 1) / 2 in rows [0, N) and (target + 1) / 2 in rows [N, 2 N) of one
+// stacked batch (reference :232-233), and get_weightings(snr(t)) per sample
+__global__ __launch_bounds__(EW_BLOCK) void cd_lpips_images_kernel(const float* __restrict__ Fs, const float* __restrict__ Ft,
+                                                                   const float* __restrict__ x_t, const float* __restrict__ x_t2,
+                                                                   const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
+                                                                   float* __restrict__ x01, float* __restrict__ wout, int N, int CHW,
+                                                                   float sd, float sd2, float sigma_min, int distill, int sched,
+                                                                   float inv_sd2) {
+    const int b = blockIdx.y;
+    const LossScal c = loss_scalings(cd_levels(idx, tab, S, b), sd, sd2, sigma_min, distill, sched, inv_sd2);
+    if (blockIdx.x == 0 && threadIdx.x == 0) wout[b] = c.w;
+    const size_t base = (size_t)b * CHW, base_t = (size_t)(N + b) * CHW;
+    const int n4 = CHW / 4;
+    for (int i = blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += gridDim.x * EW_BLOCK) {
+        const f32x4 fs = ld4(Fs, base, i), xa = ld4(x_t, base, i), ft = ld4(Ft, base, i), xb = ld4(x_t2, base, i);
+        f32x4 o, ot;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o[e] = ((c.cs_o * fs[e] + c.cs_s * xa[e]) + 1.f) / 2.f;
+            ot[e] = ((c.ct_o * ft[e] + c.ct_s * xb[e]) + 1.f) / 2.f;
+        }
+        st4(x01, base, i, o);
+        st4(x01, base_t, i, ot);
+    }
+}
+
+// dF_s = ((g w) d_x01 / 2) c_out(t): autograd's nodes in its order, for d_x01 of the LPIPS value at unit upstream
+__global__ __launch_bounds__(EW_BLOCK) void cd_lpips_bwd_kernel(const float* __restrict__ g, const float* __restrict__ dx01,
+                                                                const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
+                                                                float* __restrict__ dFs, int CHW, float sd, float sd2, float sigma_min,
+                                                                int distill, int sched, float inv_sd2) {
+    const int b = blockIdx.y;
+    const LossScal c = loss_scalings(cd_levels(idx, tab, S, b), sd, sd2, sigma_min, distill, sched, inv_sd2);
+    const float gs = g[b] * c.w;
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    for (int i = blockIdx.x * EW_BLOCK + threadIdx.x; i < n4; i += gridDim.x * EW_BLOCK) {
+        const f32x4 d = ld4(dx01, base, i);
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = ((gs * d[e]) / 2.f) * c.cs_o;
+        st4(dFs, base, i, o);
+    }
+}
+
 bool cd_aligned(const void* a, const void* b, const void* c, const void* d, const void* e = nullptr, const void* f = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15) == 0;
 }
@@ -470,5 +515,38 @@ extern "C" int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, cons
                            x_t, x_t2, indices, t_table, num_scales, d_f_online, CHW, sigma_data, sd2, sigma_min, dist, weight_schedule,
                            inv_sd2, (float)(1.0 / (double)CHW));
     DXMI_CHECK_LAUNCH("dxmi_cd_loss_bwd");
+    return DXMI_OK;
+}
+
+#define CD_CHECK_LPIPS(fn)                                                                                                       \
+    CD_CHECK_SHAPE(fn);                                                                                                          \
+    DXMI_CHECK_ARG(CHW < (1 << 30), fn ": CHW (%d) must be below 2^30", CHW);                                                    \
+    DXMI_CHECK_ARG(weight_schedule >= DXMI_DSM_W_SNR && weight_schedule <= DXMI_DSM_W_UNIFORM, fn ": unknown weight schedule %d", \
+                   weight_schedule)
+
+extern "C" int dxmi_cd_lpips_images(const float* f_online, const float* f_target, const float* x_t, const float* x_t2,
+                                    const int64_t* indices, const float* t_table, int32_t num_scales, float* x01, float* weights,
+                                    int32_t N, int32_t CHW, float sigma_data, float sigma_min, int32_t distillation,
+                                    int32_t weight_schedule, void* stream) {
+    DXMI_CHECK_ARG(f_online && f_target && x_t && x_t2 && indices && t_table && x01 && weights, "dxmi_cd_lpips_images: null pointer");
+    CD_CHECK_LPIPS("dxmi_cd_lpips_images");
+    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2, x01), "dxmi_cd_lpips_images: tensors must be 16-byte aligned");
+    const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
+    hipLaunchKernelGGL(cd_lpips_images_kernel, cd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_online, f_target, x_t, x_t2, indices,
+                       t_table, num_scales, x01, weights, N, CHW, sigma_data, sd2, sigma_min, (int)(distillation != 0), weight_schedule, inv_sd2);
+    DXMI_CHECK_LAUNCH("dxmi_cd_lpips_images");
+    return DXMI_OK;
+}
+
+extern "C" int dxmi_cd_lpips_bwd(const float* g_loss, const float* d_x01, const int64_t* indices, const float* t_table, int32_t num_scales,
+                                 float* d_f_online, int32_t N, int32_t CHW, float sigma_data, float sigma_min, int32_t distillation,
+                                 int32_t weight_schedule, void* stream) {
+    DXMI_CHECK_ARG(g_loss && d_x01 && indices && t_table && d_f_online, "dxmi_cd_lpips_bwd: null pointer");
+    CD_CHECK_LPIPS("dxmi_cd_lpips_bwd");
+    DXMI_CHECK_ARG(cd_aligned(d_x01, d_f_online, nullptr, nullptr), "dxmi_cd_lpips_bwd: tensors must be 16-byte aligned");
+    const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
+    hipLaunchKernelGGL(cd_lpips_bwd_kernel, cd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, d_x01, indices, t_table, num_scales,
+                       d_f_online, CHW, sigma_data, sd2, sigma_min, (int)(distillation != 0), weight_schedule, inv_sd2);
+    DXMI_CHECK_LAUNCH("dxmi_cd_lpips_bwd");
     return DXMI_OK;
 }

@@ -149,6 +149,16 @@ SIGNATURES = {
     "dxmi_pool3x3": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "dxmi_global_avgpool": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dxmi_resize_bilinear_nhwc16": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "dxmi_lpips_front_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "dxmi_lpips_front_bwd": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "dxmi_avgpool2x2_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "dxmi_avgpool2x2_bwd": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "dxmi_lpips_tap_partials": (c_int64, [c_int, c_int]),
+    "dxmi_lpips_tap_fwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
+    "dxmi_lpips_tap_bwd": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+    "dxmi_relu_mask_acc": (c_int, [c_void_p] * 4 + [c_int64, c_void_p]),
+    "dxmi_cd_lpips_images": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
+    "dxmi_cd_lpips_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
 }
 

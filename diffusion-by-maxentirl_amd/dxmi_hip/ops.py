@@ -1699,18 +1699,22 @@ class PackedGConv:
         self.w, self.bias, self.Cout, self.Cin, self.CinP, self.KH, self.KW = w, bias, Cout, Cin, CinP, KH, KW
 
 
-def gconv_pack(weight, bn=None, eps=1e-3):
-    """weight fp32 [Cout, Cin, KH, KW]; bn = (gamma, beta, running_mean, running_var) or None."""
+def gconv_pack(weight, bn=None, eps=1e-3, bias=None):
+    """weight fp32 [Cout, Cin, KH, KW]; bn = (gamma, beta, running_mean, running_var) or None; bias fp32 [Cout] of a convolution
+    without BatchNorm (None: zero)."""
     _need_cuda(weight)
     w = weight.detach().float().contiguous()
     Cout, Cin, KH, KW = w.shape
-    lib = load()
+    conv_bias, lib = bias, load()
     wp = torch.empty(int(lib.dxmi_gconv_packed_elems(Cout, Cin, KH, KW)), dtype=torch.bfloat16, device=w.device)
     CoutP, CinP = (Cout + 31) // 32 * 32, (Cin + 15) // 16 * 16
     bias = torch.empty(CoutP, dtype=torch.float32, device=w.device)
     bnp = [t.detach().float().contiguous() for t in bn] if bn is not None else [None] * 4
     check(lib.dxmi_gconv_pack(_ptr(w), _ptr(bnp[0]), _ptr(bnp[1]), _ptr(bnp[2]), _ptr(bnp[3]), float(eps), _ptr(wp), _ptr(bias), Cout, Cin, KH, KW,
                               _stream()), "dxmi_gconv_pack")
+    if conv_bias is not None:
+        assert bn is None and conv_bias.numel() == Cout, "gconv_pack: bias is [Cout] and excludes bn"
+        bias[:Cout].copy_(conv_bias.detach().float().reshape(Cout))
     return PackedGConv(wp, bias, Cout, Cin, CinP, KH, KW)
 
 

@@ -6,8 +6,8 @@ sample_euler_ancestral / sample_heun / sample_euler / sample_dpm (:447-640), and
 sample_onestep / stochastic_iterative_sampler (:644-683) with the zero-shot editing loops iterative_colorization /
 iterative_inpainting / iterative_superres (:722-951), and the denoising score-matching loss training_losses with
 get_weightings (:18-31, :82-106) that models.cm.train_util.TrainLoop trains the U-Net with, and the consistency distillation /
-consistency training loss consistency_losses (:108-241) of models.cm.train_util.CMTrainLoop.  progdist (losses and sampler) and
-the LPIPS norm stay out of scope.
+consistency training loss consistency_losses (:108-241) of models.cm.train_util.CMTrainLoop, its lpips norm (:221-234) through
+models.cm.lpips once the caller supplies the weights.  progdist (losses and sampler) stays out of scope.
 
 training_losses on the HIP UNetModel (bare, or behind a wrapper that holds it as `.module`) is ONE autograd node: the network
 input of the batch in one launch (dxmi_edm_dsm_prep), the U-Net forward of models.cm.unet_train, the per-sample terms in one
@@ -121,7 +121,9 @@ class CDLevels:
 
 
 _CD_LEVELS = {}
-_NO_LPIPS = "loss_norm='lpips': no LPIPS weights are available to this package; the consistency losses run with l1, l2 and l2-32"
+_NO_LPIPS = ("loss_norm='lpips': no LPIPS weights are available to this package; the consistency losses run with l1, l2 and l2-32 "
+             "unless DXMI_LPIPS_VGG16 and DXMI_LPIPS_LIN name the VGG16 and linear weight files (or lpips_loss= is given)")
+LPIPS_RESIZE_BELOW, LPIPS_SIZE = 256, 224      # reference :222-230: images narrower than 256 go through F.interpolate(size=224)
 
 
 def cd_levels(num_scales, sigma_min, sigma_max, rho):
@@ -187,8 +189,18 @@ class _CDLossFn(torch.autograd.Function):
             F_tg = target.forward_inference(tg_in, tg_t, y)
         kw = dict(loss_norm=diffusion.loss_norm, weight_schedule=diffusion.weight_schedule, sigma_data=sd,
                   sigma_min=diffusion.sigma_min, distillation=diffusion.distillation)
-        loss = ops.cd_loss_fwd(F, F_tg, x_t, x_t2, indices, tab, **kw)
-        ctx.sub, ctx.kw, ctx.ops = sub, kw, (F, F_tg, x_t, x_t2, indices, tab)
+        if diffusion.loss_norm == "lpips":
+            from dxmi_hip import lpips_ops
+            from .lpips import _lpips_forward
+            del kw["loss_norm"]
+            lp = diffusion._lpips()
+            x01, w = lpips_ops.cd_lpips_images(F, F_tg, x_t, x_t2, indices, tab, **kw)
+            loss, acts = _lpips_forward(lp, x01, LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None, scale=w,
+                                        keep=not getattr(ctx, "no_backward", False))
+            ctx.sub, ctx.kw, ctx.ops, ctx.lpips = sub, kw, (indices, tab), (lp, acts, tuple(x_start.shape[2:]))
+        else:
+            loss = ops.cd_loss_fwd(F, F_tg, x_t, x_t2, indices, tab, **kw)
+            ctx.sub, ctx.kw, ctx.ops, ctx.lpips = sub, kw, (F, F_tg, x_t, x_t2, indices, tab), None
         ctx.set_materialize_grads(False)
         return loss
 
@@ -199,8 +211,13 @@ class _CDLossFn(torch.autograd.Function):
         n_in = len(ctx.needs_input_grad)
         if g is None:
             return (None,) * n_in
-        dF = ops.cd_loss_bwd(g.detach().float().contiguous(), *ctx.ops, **ctx.kw)
-        ctx.ops = None
+        if ctx.lpips is not None:
+            from dxmi_hip import lpips_ops
+            from .lpips import _lpips_backward
+            dF = lpips_ops.cd_lpips_bwd(g.detach().float().contiguous(), _lpips_backward(*ctx.lpips, None), *ctx.ops, **ctx.kw)
+        else:
+            dF = ops.cd_loss_bwd(g.detach().float().contiguous(), *ctx.ops, **ctx.kw)
+        ctx.ops = ctx.lpips = None
         grads = _EDMUNetFn.backward(ctx.sub, dF)
         ctx.sub = None
         return (None,) * 10 + tuple(grads[4:])
@@ -208,11 +225,21 @@ class _CDLossFn(torch.autograd.Function):
 
 class KarrasDenoiser:
     def __init__(self, sigma_data: float = 0.5, sigma_max=80.0, sigma_min=0.002, rho=7.0, weight_schedule="karras",
-                 distillation=False, loss_norm="l2"):
+                 distillation=False, loss_norm="l2", lpips_loss=None):
         self.sigma_data, self.sigma_max, self.sigma_min = sigma_data, sigma_max, sigma_min
         self.weight_schedule, self.distillation, self.loss_norm, self.rho = weight_schedule, distillation, loss_norm, rho
+        self.lpips_loss = lpips_loss
         if loss_norm == "lpips":
+            self._lpips()
+
+    def _lpips(self):
+        """The LPIPS object of loss_norm='lpips': `lpips_loss` if set, else the one the two environment variables name (built once)."""
+        if self.lpips_loss is None:
+            from .lpips import LPIPS
+            self.lpips_loss = LPIPS.from_env()
+        if self.lpips_loss is None:
             raise NotImplementedError(_NO_LPIPS)
+        return self.lpips_loss
 
     def get_snr(self, sigmas):
         return sigmas ** -2
@@ -300,8 +327,8 @@ class KarrasDenoiser:
         if target_model is None:
             raise NotImplementedError("Must have a target model")
         if self.loss_norm == "lpips":        # set on the object after construction, as the reference's callers set it
-            raise NotImplementedError(_NO_LPIPS)
-        if self.loss_norm not in ("l1", "l2", "l2-32"):
+            self._lpips()
+        if self.loss_norm not in ("l1", "l2", "l2-32", "lpips"):
             raise ValueError(f"Unknown loss norm {self.loss_norm}")
         if teacher_model is not None and teacher_diffusion is None:
             raise ValueError("consistency_losses: a teacher_model needs its teacher_diffusion")
@@ -345,6 +372,9 @@ class KarrasDenoiser:
             diffs = torch.abs(distiller - distiller_target)
         elif self.loss_norm == "l2":
             diffs = (distiller - distiller_target) ** 2
+        elif self.loss_norm == "lpips":
+            resize = LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None
+            return {"loss": self._lpips()((distiller + 1) / 2.0, (distiller_target + 1) / 2.0, resize=resize) * weights}
         else:
             import torch.nn.functional as F
             distiller = F.interpolate(distiller, size=32, mode="bilinear")
@@ -384,7 +414,7 @@ class KarrasDenoiser:
             loss = _CDLossFn.apply(*args, *ops.fast_parameters(net))
         else:
             import types
-            loss = _CDLossFn.forward(types.SimpleNamespace(set_materialize_grads=lambda v: None), *args, *ops.fast_parameters(net))
+            loss = _CDLossFn.forward(types.SimpleNamespace(set_materialize_grads=lambda v: None, no_backward=True), *args, *ops.fast_parameters(net))
         return {"loss": loss}
 
     def denoise(self, model, x_t, sigmas, **model_kwargs):

@@ -14,7 +14,8 @@ NUM_CLASSES = 1000
 
 
 def cm_train_defaults():
-    """The reference's keys and values (:10-23), but loss_norm "l2": there are no LPIPS weights here."""
+    """The reference's keys and values (:10-23), but loss_norm "l2": no LPIPS weights ship with this package, and the
+    defaults must run without any.  "lpips" (the reference's default) is available once the caller supplies them (models.cm.lpips)."""
     return dict(teacher_model_path="", teacher_dropout=0.1, training_mode="consistency_distillation", target_ema_mode="fixed",
                 scale_mode="fixed", total_training_steps=600000, start_ema=0.0, start_scales=40, end_scales=40,
                 distill_steps_per_iter=50000, loss_norm="l2")

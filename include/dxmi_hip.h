@@ -825,6 +825,41 @@ int dxmi_cm_stage(int32_t mode, int32_t edit, int32_t last, const float* tab, in
                   const float* model_out, const float* noise, const float* ref, const float* mask, float* x_in, float* t_out,
                   float* out, float* denoised, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 
+/* LPIPS (piq's LPIPS(replace_pooling=True, reduction="none") on torchvision's VGG16 features) as a device loss: the launches around
+ * the 13 convolutions, which go through dxmi_gconv_fwd forward and, with transposed-and-flipped packed weights, backward.
+ * Activations and gradients are NHWC bf16; every sum is fp32 and taken in a fixed order (bitwise reproducible, no atomics).
+ * dxmi_lpips_front_fwd: x fp32 [N, 3, IH, IW] in [0, 1] -> F.interpolate(size=(OH, OW), mode="bilinear") (align_corners False; the
+ *   identity when the sizes agree) -> (v - mean) / std -> out bf16 [N, OH, OW, 16], channels 3..15 zero.
+ * dxmi_lpips_front_bwd: its transpose from g_out bf16 [N, OH, OW, 16] (channels 0..2 read) to d_x fp32 [N, 3, IH, IW], 1 / std included.
+ * dxmi_avgpool2x2_fwd: AvgPool2d(2, 2, 0), x [N, IH, IW, C] -> out [N, IH / 2, IW / 2, C] (floor).  dxmi_avgpool2x2_bwd: g_out of that shape
+ *   -> g_in [N, IH, IW, C]; a dropped last row / column gets zero.  C % 8 == 0.
+ * dxmi_lpips_tap_fwd: fx, fy bf16 [N, HW, C], w fp32 [C]: per pixel f^ = f / (sqrt(sum_c f^2) + 1e-10) of both,
+ *   v[n] = (1 / HW) sum_pixels sum_c w_c (fx^ - fy^)^2; out[n] = (accumulate ? out[n] : 0) + v[n], then times scale[n] if scale is not
+ *   NULL.  partials: fp32 workspace of N * dxmi_lpips_tap_partials(HW, C) elements.  C % 16 == 0, 16 <= C <= 512.
+ * dxmi_lpips_tap_bwd: d_fx bf16 [N, HW, C] of v[n] for the upstream g[n] (NULL: 1), through the normalisation; zero-norm pixels take
+ *   the subgradient 0 of the norm.  fy is a constant.
+ * dxmi_relu_mask_acc: out = (g_a + g_b) * (act > 0) over numel bf16 values (g_b NULL: g_a alone); numel % 8 == 0. */
+int dxmi_lpips_front_fwd(const float* x, void* out, int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW, void* stream);
+int dxmi_lpips_front_bwd(const void* g_out, float* d_x, int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW, void* stream);
+int dxmi_avgpool2x2_fwd(const void* x, void* out, int32_t N, int32_t IH, int32_t IW, int32_t C, void* stream);
+int dxmi_avgpool2x2_bwd(const void* g_out, void* g_in, int32_t N, int32_t IH, int32_t IW, int32_t C, void* stream);
+int64_t dxmi_lpips_tap_partials(int32_t HW, int32_t C);
+int dxmi_lpips_tap_fwd(const void* fx, const void* fy, const float* w, const float* scale, float* partials, float* out, int32_t N,
+                       int32_t HW, int32_t C, int32_t accumulate, void* stream);
+int dxmi_lpips_tap_bwd(const float* g, const void* fx, const void* fy, const float* w, void* d_fx, int32_t N, int32_t HW, int32_t C,
+                       void* stream);
+int dxmi_relu_mask_acc(const void* g_a, const void* g_b, const void* act, void* out, int64_t numel, void* stream);
+/* The lpips norm of the consistency losses (reference :221-234) around that network.  dxmi_cd_lpips_images: with the scalings of
+ * dxmi_cd_loss_fwd, x01 fp32 [2 N, CHW] = (distiller + 1) / 2 in rows [0, N) and (target + 1) / 2 in rows [N, 2 N), and
+ * weights[n] = get_weightings(weight_schedule, t^-2).  dxmi_cd_lpips_bwd: d_f_online = ((g_loss w) d_x01 / 2) c_out(t) for d_x01
+ * fp32 [N, CHW], the gradient of the LPIPS value into the online image at unit upstream. */
+int dxmi_cd_lpips_images(const float* f_online, const float* f_target, const float* x_t, const float* x_t2, const int64_t* indices,
+                         const float* t_table, int32_t num_scales, float* x01, float* weights, int32_t N, int32_t CHW, float sigma_data,
+                         float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream);
+int dxmi_cd_lpips_bwd(const float* g_loss, const float* d_x01, const int64_t* indices, const float* t_table, int32_t num_scales,
+                      float* d_f_online, int32_t N, int32_t CHW, float sigma_data, float sigma_min, int32_t distillation,
+                      int32_t weight_schedule, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
