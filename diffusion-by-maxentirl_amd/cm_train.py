@@ -9,8 +9,10 @@ over models/cm/script_util.py cm_train_defaults + model_and_diffusion_defaults).
 Every key of cm_train_defaults() and model_and_diffusion_defaults() is a flag, next to --synthetic_data, --batch_size, --microbatch,
 --lr, --ema_rate, --log_dir, --max_iters, --use_fp16 and the loop's intervals.  For distillation the student and the target start
 from the teacher's weights, the teacher's diffusion has distillation=False and the student's distillation=True.  The target_model
-checkpoints it writes are what `generate_large.py --cm_sampler onestep --pretrained ...` reads.  Real-data loaders are not part of
-this package: --synthetic_data True draws uniform images and labels.  CMTrainLoop.run_loop keeps the reference's condition, which
+checkpoints it writes are what `generate_large.py --cm_sampler onestep --pretrained ...` reads.  Image folders are not read by
+this package: --data_npz PATH trains on a uint8 image array file (dxmi_hip/data.py ImageStore, normalised as the reference's
+image_datasets.py does; --data_resident auto|device|host), --synthetic_data True draws uniform images and labels; the two exclude
+each other and one of them is required.  CMTrainLoop.run_loop keeps the reference's condition, which
 ends only when both lr_anneal_steps and total_training_steps are reached: --max_iters N (smoke runs) sets both to N, so the
 learning rate anneals to zero over those N steps.  --loss_norm lpips needs the VGG16 and LPIPS linear weight files:
 --lpips_vgg16 PATH --lpips_lin PATH, or DXMI_LPIPS_VGG16 / DXMI_LPIPS_LIN in the environment; without them it is refused.
@@ -39,15 +41,38 @@ def synthetic_batches(batch_size, image_size, class_cond, device, seed):
         yield x, cond
 
 
-def main():
+def make_loader(args, device, rank, world):
+    """The `data=` iterator of CMTrainLoop for the parsed flags, and the ImageStore behind it (None for synthetic data)."""
+    if args.data_npz:
+        from dxmi_hip.data import NORM_ADM, ImageStore
+        store = ImageStore(args.data_npz, device, NORM_ADM, batch_size=args.batch_size, rank=rank, world=world, seed=args.seed,
+                           class_cond=args.class_cond, resident=args.data_resident)
+        return store.batches(), store
+    if not args.synthetic_data:
+        raise NotImplementedError("cm_train.py: image folders are not read by this package; run with --data_npz PATH (an uint8 array "
+                                  "file, see make_npz.py) or --synthetic_data True")
+    return synthetic_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + rank), None
+
+
+def parse_args(argv=None):
     defaults = dict(model_and_diffusion_defaults())
     defaults.update(cm_train_defaults())
-    defaults.update(synthetic_data=False, batch_size=16, microbatch=-1, lr=1e-4, ema_rate="0.9999", log_dir="results/cm_train",
+    defaults.update(synthetic_data=False, data_npz="", data_resident="auto", batch_size=16, microbatch=-1, lr=1e-4, ema_rate="0.9999",
+                    log_dir="results/cm_train",
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
                     fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="")
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.synthetic_data and args.data_npz:
+        ap.error("--synthetic_data and --data_npz exclude each other")
+    if args.data_resident not in ("auto", "device", "host"):
+        ap.error(f"--data_resident {args.data_resident!r}: auto, device or host")
+    return args
+
+
+def main():
+    args = parse_args()
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = _dist.rank_device(local_rank)
@@ -59,8 +84,9 @@ def main():
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")   # RCCL
-    if not args.synthetic_data:
-        raise NotImplementedError("cm_train.py: real-data loaders are not part of this package; run with --synthetic_data True")
+    data, store = make_loader(args, device, local_rank, world)
+    if store is not None:
+        print0(store.describe())
     distill = args.training_mode == "consistency_distillation"
     if args.training_mode not in ("consistency_distillation", "consistency_training"):
         raise NotImplementedError(f"training_mode {args.training_mode!r}: consistency_distillation or consistency_training")
@@ -96,7 +122,7 @@ def main():
     total = args.max_iters if args.max_iters else args.total_training_steps
     loop = CMTrainLoop(model=model, target_model=target_model, teacher_model=teacher_model, teacher_diffusion=teacher_diffusion,
                        training_mode=args.training_mode, ema_scale_fn=ema_scale_fn, total_training_steps=total, diffusion=diffusion,
-                       data=synthetic_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + local_rank),
+                       data=data,
                        batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr, ema_rate=args.ema_rate,
                        log_interval=args.log_interval, save_interval=args.save_interval, resume_checkpoint=args.resume_checkpoint,
                        use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth, weight_decay=args.weight_decay,
@@ -106,6 +132,8 @@ def main():
     loop.run_loop()
     if loop.logged:
         print0("last log row:", loop.logged[-1])
+    if store is not None:
+        store.close()
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -160,6 +160,7 @@ SIGNATURES = {
     "dxmi_cd_lpips_images": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_cd_lpips_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "dxmi_image_batch": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
 }
 
 _lib = None

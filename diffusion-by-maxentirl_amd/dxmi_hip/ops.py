@@ -1689,6 +1689,36 @@ def gather_rows(src, idx, out=None):
     return out
 
 
+IMG_NORM_ADM, IMG_NORM_TOTENSOR = 0, 1
+
+
+def image_batch(store, idx, flip, norm, out=None):
+    """One training batch from a uint8 image array (see dxmi_image_batch): store uint8 [M, H, W, C] (C = 3 or 1), idx int64 [B] (None:
+    rows 0 .. B-1, with B from flip or out), flip uint8 [B] (None: no flips) -> fp32 [B, C, H, W], normalised by IMG_NORM_ADM
+    (v / 127.5 - 1) or IMG_NORM_TOTENSOR (2 (v / 255) - 1).  An index outside [0, M) gives a NaN image."""
+    _need_cuda(store, idx, flip, out)
+    assert store.dtype == torch.uint8 and store.dim() == 4 and store.is_contiguous(), "image_batch: store is a contiguous uint8 [M, H, W, C]"
+    M, H, W, C = store.shape
+    assert M >= 1 and C in (1, 3), f"image_batch: store {tuple(store.shape)} needs rows and 3 or 1 channels"
+    assert norm in (IMG_NORM_ADM, IMG_NORM_TOTENSOR), f"image_batch: norm {norm!r}"
+    if idx is not None:
+        assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous(), "image_batch: idx is a contiguous int64 [B]"
+    if flip is not None:
+        assert flip.dtype == torch.uint8 and flip.dim() == 1 and flip.is_contiguous(), "image_batch: flip is a contiguous uint8 [B]"
+    sized = [t.shape[0] for t in (idx, flip, out) if t is not None]
+    assert sized, "image_batch: the batch size comes from idx, flip or out"
+    B = sized[0]
+    assert B >= 1 and all(n == B for n in sized), f"image_batch: idx / flip / out disagree on the batch size {sized}"
+    assert idx is not None or B <= M, f"image_batch: without idx the batch ({B}) is rows 0 .. B-1 of {M}"
+    if out is None:
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=store.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, C, H, W), \
+        f"image_batch: out must be a contiguous fp32 {(B, C, H, W)}"
+    _prof("data", f"image_batch{H}x{W}x{C}", 0.0, 5.0 * out.numel(), lambda: check(
+        load().dxmi_image_batch(_ptr(store), M, _ptr(idx), _ptr(flip), _ptr(out), B, H, W, C, int(norm), _stream()), "dxmi_image_batch"))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)
 class PackedGConv:
     """BatchNorm-folded bf16 weights [ceil32(Cout)][KH * KW][ceil16(Cin)] + fp32 bias of one BasicConv2d (dxmi_gconv_pack)."""

@@ -11,7 +11,8 @@ per-rank batch = batchsize // world, epoch loop of `train_one_epoch` (:141-205),
 reference's file names and state-dict keys (:58-78, :459-462).  Differences, all outside the
 accelerated path: gradients are exchanged by one flat RCCL all-reduce per backward instead of DDP
 buckets (dxmi_hip/dist.py); FID / wandb / tensorboard are skipped unless their packages and the dataset
-PNG folder exist; `--synthetic_data` feeds uniform images (benchmarks, smoke runs).
+PNG folder exist; `--data_npz PATH` trains on a uint8 image array file (dxmi_hip/data.py ImageStore: ToTensor's scaling, random
+horizontal flips, `--data_resident auto|device|host`); `--synthetic_data` feeds uniform images (benchmarks, smoke runs).
 """
 import argparse
 import os
@@ -45,13 +46,39 @@ def synthetic_loader(batchsize, n_batches, device, seed):
         yield torch.rand(batchsize, 3, 32, 32, device=device, generator=g), None
 
 
-def train_one_epoch(trainer, sampler, dataloader, n_critic, n_generator, device, log_every, state):
-    """reference train_one_epoch (:141-205) without the FID / logging side paths."""
+def make_store(args, cfg, device, rank, world):
+    """The ImageStore of --data_npz (None without the flag): ToTensor's normalisation with the `2 * images - 1` of train_one_epoch
+    applied in the same launch, the per-rank batch, and the seed and rank the synthetic loader gets."""
+    if not args.data_npz:
+        return None
+    from dxmi_hip.data import NORM_TOTENSOR, ImageStore
+    return ImageStore(args.data_npz, device, NORM_TOTENSOR, batch_size=cfg.training.batchsize // world, rank=rank, world=world,
+                      seed=cfg.training.seed, resident=args.data_resident)
+
+
+def make_loader(args, cfg, device, rank, world, epoch, store=None):
+    """One epoch's (images, labels) iterable: the ImageStore's epoch, the synthetic loader, or the reference's pipeline."""
+    batchsize = cfg.training.batchsize // world
+    if store is not None:
+        return store.epoch(epoch)
+    if args.synthetic_data:
+        return synthetic_loader(batchsize, args.max_iters or 100, device, cfg.training.seed + rank + epoch)
+    import loader as ref_loader  # the reference's torchvision CIFAR-10 pipeline (out of scope here)
+    from torch.utils.data import DataLoader
+    from torch.utils.data.distributed import DistributedSampler
+    train_set = ref_loader.get_dataset(cfg.data.name, cfg.data.data_dir)
+    ds = DistributedSampler(train_set) if world > 1 else None
+    return DataLoader(train_set, batch_size=batchsize, shuffle=ds is None, sampler=ds, num_workers=4, pin_memory=True, drop_last=True)
+
+
+def train_one_epoch(trainer, sampler, dataloader, n_critic, n_generator, device, log_every, state, normalised=False, max_iters=None):
+    """reference train_one_epoch (:141-205) without the FID / logging side paths.  normalised: the loader's images are already in
+    [-1, 1] (ImageStore); max_iters: stop inside the epoch once state['i_iter'] reaches it."""
     # device-resident replay ring: n_critic trajectories of T transitions each, generated in place by the sampler
     buf = TransitionRing(n_critic, trainer.n_timesteps, trainer.batchsize, sampler.sample_shape, device)
     for step, (images, _) in enumerate(dataloader):
         sampler.eval()
-        images = (2 * images - 1).to(device)
+        images = images.to(device) if normalised else (2 * images - 1).to(device)
         in_ring = len(images) == trainer.batchsize
         d_sample = sampler.sample(len(images), device=device, out=buf.next_slot() if in_ring else None)
         append_buffer(buf, d_sample)
@@ -63,6 +90,8 @@ def train_one_epoch(trainer, sampler, dataloader, n_critic, n_generator, device,
                 print0(f"iter {state['i_iter']}: d_loss {d_energy['ebm/d_loss_']:.4f} v_loss {d_energy['ebm/v_loss_']:.4f} "
                        f"sampler_loss {d_sampler['sampler/sampler_loss_']:.4f}")
         state["i_iter"] += 1
+        if max_iters is not None and state["i_iter"] >= max_iters:
+            break
 
 
 def load_config(config, dataset, overrides=None):
@@ -87,12 +116,15 @@ def build_optimizers(cfg, net, sampler, v):
     return optimizer, Adam(v.parameters(), lr=cfg.training.v_lr)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--dataset", type=str, required=True)
     ap.add_argument("--run", type=str, default="run")
     ap.add_argument("--synthetic_data", action="store_true")
+    ap.add_argument("--data_npz", type=str, default="", help="uint8 image array file: .npz with arr_0 [M, 32, 32, 3], or .npy")
+    ap.add_argument("--data_resident", choices=("auto", "device", "host"), default="auto",
+                    help="keep the array in device memory, or on the host behind a prefetch thread (auto: by its size)")
     ap.add_argument("--max_iters", type=int, default=None, help="stop after this many iterations (smoke runs)")
     ap.add_argument("--batch_invariant", action="store_true",
                     help="keep one conv kernel per layer shape whatever the batch size (bitwise batch-independent results) instead of "
@@ -100,7 +132,14 @@ def main():
     ap.add_argument("--no_graph", action="store_true",
                     help="issue every kernel launch from python instead of replaying the generation call and the two updates as hipGraphs "
                          "(dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
-    args, unknown = ap.parse_known_args()
+    args, unknown = ap.parse_known_args(argv)
+    if args.synthetic_data and args.data_npz:
+        ap.error("--synthetic_data and --data_npz exclude each other")
+    return args, unknown
+
+
+def main():
+    args, unknown = parse_args()
     d_cmd_cfg = cmd.parse_nested_args(cmd.parse_unknown_args(unknown))
     print0("Overriding", d_cmd_cfg)
 
@@ -151,23 +190,19 @@ def main():
         mkdir_p(logdir)
         dxmi_config.save(cfg, os.path.join(logdir, "config.yaml"))
 
+    store = make_store(args, cfg, device, local_rank, world)
+    if store is not None:
+        print0(store.describe())
     state = {"i_iter": 0}
     for epoch in range(cfg.training.n_epochs):
-        if args.synthetic_data:
-            n_batches = args.max_iters or 100
-            loader = synthetic_loader(batchsize, n_batches, device, seed + local_rank + epoch)
-        else:
-            import loader as ref_loader  # the reference's torchvision CIFAR-10 pipeline (out of scope here)
-            from torch.utils.data import DataLoader
-            from torch.utils.data.distributed import DistributedSampler
-            train_set = ref_loader.get_dataset(cfg.data.name, cfg.data.data_dir)
-            ds = DistributedSampler(train_set) if world > 1 else None
-            loader = DataLoader(train_set, batch_size=batchsize, shuffle=ds is None, sampler=ds, num_workers=4,
-                                pin_memory=True, drop_last=True)
+        loader = make_loader(args, cfg, device, local_rank, world, epoch, store)
         train_one_epoch(trainer, sampler, loader, cfg.training.n_critic, cfg.training.n_generator, device,
-                        cfg.training.log_every, state)
+                        cfg.training.log_every, state, normalised=store is not None,
+                        max_iters=args.max_iters if store is not None else None)
         if args.max_iters is not None and state["i_iter"] >= args.max_iters:
             break
+    if store is not None:
+        store.close()
     if local_rank == 0:
         save_model(trainer, logdir, "last", d_other_info={"epoch": epoch, "iter": state["i_iter"], "fid": None})
         print0(f"saved {logdir}/sampler_last.pth and value_last.pth after {state['i_iter']} iterations")

@@ -11,7 +11,9 @@ pretrained EDM weights when the file exists, OpenAIDiffusion, value net from `_t
 batchsize // world, and per iteration sample -> append_buffer -> update_f_v -> update_sampler_mixed_precision ->
 reset_buffer (:301-321).  Differences, all outside the accelerated path: gradients are exchanged by one flat RCCL
 all-reduce per backward (dxmi_hip/dist.py) instead of DDP buckets; FID / wandb / tensorboard are skipped unless their
-packages and statistics files exist; `--synthetic_data` feeds uniform images and random labels.
+packages and statistics files exist; `--data_npz PATH` trains on a uint8 image array file (dxmi_hip/data.py ImageStore: the
+normalisation and flips of image_datasets.py, labels from `arr_1`, `--data_resident auto|device|host`); `--synthetic_data` feeds
+uniform images and random labels.
 Checkpoints: `sampler.pth` ({'state_dict', 'fid', 'i_iter'}) and `value.pth`, the names generate_large.py reads.
 """
 import argparse
@@ -39,6 +41,28 @@ def synthetic_batches(batchsize, image_size, class_cond, n_class, device, seed):
         data = torch.rand(batchsize, 3, image_size, image_size, device=device, generator=g) * 2 - 1
         cond = {"y": torch.randint(0, n_class, (batchsize,), device=device, generator=g)} if class_cond else {}
         yield data, cond
+
+
+def make_loader(args, cfg, device, rank, world):
+    """The infinite (images, cond) iterator for the parsed flags, and the ImageStore behind it (None unless --data_npz)."""
+    batchsize = cfg.training.batchsize // world
+    class_cond = bool(cfg.data.get("class_cond", cfg.sampler.get("class_cond", False)))
+    seed = cfg.training.seed
+    if args.data_npz:
+        from dxmi_hip.data import NORM_ADM, ImageStore
+        store = ImageStore(args.data_npz, device, NORM_ADM, batch_size=batchsize, rank=rank, world=world, seed=seed,
+                           class_cond=class_cond, resident=args.data_resident)
+        return store.batches(), store
+    if args.synthetic_data:
+        return synthetic_batches(batchsize, cfg.diffusion.image_size, class_cond, cfg.data.get("n_class", 1000), device, seed + rank), None
+    from models.cm.dxmi_util import infinite_loader, load_data   # the reference's image-folder pipeline (out of scope here)
+    from torch.utils.data import DataLoader
+    from torch.utils.data.distributed import DistributedSampler
+    ds = load_data(data_dir=cfg.data.data_dir, cachefile=cfg.data.cachefile, batch_size=cfg.training.batchsize,
+                   image_size=cfg.data.image_size, class_cond=cfg.data.class_cond, deterministic=cfg.data.deterministic,
+                   random_crop=False, random_flip=True)
+    dsamp = DistributedSampler(ds) if world > 1 else None
+    return infinite_loader(DataLoader(ds, batch_size=batchsize, shuffle=dsamp is None, sampler=dsamp, num_workers=4, drop_last=True)), None
 
 
 def load_config(config, dataset, overrides=None):
@@ -70,12 +94,15 @@ def build_optimizers(cfg, unet, v):
     return mp_trainer, opt, Adam(v.parameters(), lr=cfg.training.v_lr)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--dataset", type=str, required=True)
     ap.add_argument("--run", type=str, required=True)
     ap.add_argument("--synthetic_data", action="store_true")
+    ap.add_argument("--data_npz", type=str, default="", help="uint8 image array file: .npz with arr_0 [M, H, W, 3] (and arr_1 labels), or .npy")
+    ap.add_argument("--data_resident", choices=("auto", "device", "host"), default="auto",
+                    help="keep the array in device memory, or on the host behind a prefetch thread (auto: by its size)")
     ap.add_argument("--max_iters", type=int, default=None, help="stop after this many iterations (smoke runs)")
     ap.add_argument("--batch_invariant", action="store_true",
                     help="keep one conv kernel per layer shape whatever the batch size (bitwise batch-independent results) instead of "
@@ -88,7 +115,14 @@ def main():
     ap.add_argument("--no_graph", action="store_true",
                     help="issue every kernel launch from python instead of replaying the three phases of an iteration as hipGraphs "
                          "(dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
-    args, unknown = ap.parse_known_args()
+    args, unknown = ap.parse_known_args(argv)
+    if args.synthetic_data and args.data_npz:
+        ap.error("--synthetic_data and --data_npz exclude each other")
+    return args, unknown
+
+
+def main():
+    args, unknown = parse_args()
     d_cmd_cfg = cmd.parse_nested_args(cmd.parse_unknown_args(unknown))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -133,17 +167,9 @@ def main():
 
     batchsize = cfg.training.batchsize // world
     class_cond = bool(cfg.data.get("class_cond", cfg.sampler.get("class_cond", False)))
-    if args.synthetic_data:
-        loader = synthetic_batches(batchsize, cfg.diffusion.image_size, class_cond, cfg.data.get("n_class", 1000), device, seed + local_rank)
-    else:
-        from models.cm.dxmi_util import infinite_loader, load_data   # the reference's image-folder pipeline (out of scope here)
-        from torch.utils.data import DataLoader
-        from torch.utils.data.distributed import DistributedSampler
-        ds = load_data(data_dir=cfg.data.data_dir, cachefile=cfg.data.cachefile, batch_size=cfg.training.batchsize,
-                       image_size=cfg.data.image_size, class_cond=cfg.data.class_cond, deterministic=cfg.data.deterministic,
-                       random_crop=False, random_flip=True)
-        dsamp = DistributedSampler(ds) if world > 1 else None
-        loader = infinite_loader(DataLoader(ds, batch_size=batchsize, shuffle=dsamp is None, sampler=dsamp, num_workers=4, drop_last=True))
+    loader, store = make_loader(args, cfg, device, local_rank, world)
+    if store is not None:
+        print0(store.describe())
 
     model_cfg_name = os.path.basename(args.config).split(".")[0].replace("builtin:", "")
     logdir = os.path.join(f"results/{cfg.data.name}/{model_cfg_name}", args.run)
@@ -214,6 +240,8 @@ def main():
         torch.save({"state_dict": unet.state_dict(), "fid": None, "i_iter": i_iter}, os.path.join(logdir, "sampler.pth"))
         torch.save({"state_dict": v.state_dict()}, os.path.join(logdir, "value.pth"))
         print0(f"saved {logdir}/sampler.pth and value.pth after {i_iter + 1} iterations")
+    if store is not None:
+        store.close()
 
 
 if __name__ == "__main__":

@@ -860,6 +860,22 @@ int dxmi_cd_lpips_bwd(const float* g_loss, const float* d_x01, const int64_t* in
                       float* d_f_online, int32_t N, int32_t CHW, float sigma_data, float sigma_min, int32_t distillation,
                       int32_t weight_schedule, void* stream);
 
+/* Training batches from a uint8 image array (csrc/image_batch.hip): what the reference's loaders do per image on the
+ * host (models/cm/image_datasets.py:115-119 `arr[:, ::-1]`, `arr.astype(np.float32) / 127.5 - 1`, `np.transpose(arr, [2, 0, 1])`;
+ * loader/__init__.py:14-15 RandomHorizontalFlip + ToTensor, then train_cifar10.py:170 `2 * images - 1`) as ONE launch per batch.
+ * store: uint8 [n_rows, H, W, C] on the device (`arr_0` of the evaluator's .npz batches and of make_npz.py), C = 3 or 1.
+ * idx: int64 [B] on the device, the source row of each output image; NULL = rows 0 .. B-1 (B <= n_rows).  An index outside
+ * [0, n_rows) fills that image with NaN and reads nothing outside the store (no wrap-around).  flip: uint8 [B] on the device,
+ * nonzero mirrors the image along W; NULL = no flips.  out: fp32 [B, C, H, W].  norm, one rounding per operation:
+ *   DXMI_IMG_NORM_ADM       v / 127.5f - 1.0f
+ *   DXMI_IMG_NORM_TOTENSOR  2.0f * (v / 255.0f) - 1.0f
+ * W % 16 == 0 with 16-byte aligned store and out: 16-byte loads of interleaved pixels, f32x4 stores per channel plane, the flip in
+ * the store index.  Anything else: one element per lane.  No workspace; bitwise reproducible. */
+#define DXMI_IMG_NORM_ADM       0
+#define DXMI_IMG_NORM_TOTENSOR  1
+int dxmi_image_batch(const void* store, int64_t n_rows, const int64_t* idx, const uint8_t* flip, float* out, int32_t B, int32_t H,
+                     int32_t W, int32_t C, int32_t norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
