@@ -52,6 +52,26 @@ def default_enabled():
     return os.environ.get("DXMI_GRAPH", "1") != "0"
 
 
+def pack_modules(net):
+    """Sub-modules of `net` that keep packed bf16 weight sets (objects with refresh_packs / prepare_capture): the `modules=` of a
+    StepGraph around a step that reads or updates `net`."""
+    mods = net.modules() if hasattr(net, "modules") else [net]
+    out = [m for m in mods if hasattr(m, "refresh_packs") and hasattr(m, "prepare_capture")]
+    inner = getattr(net, "net", None)          # OpenAIDiffusion: a plain object holding the U-Net
+    if not out and inner is not None and hasattr(inner, "modules"):
+        out = [m for m in inner.modules() if hasattr(m, "refresh_packs") and hasattr(m, "prepare_capture")]
+    return out
+
+
+def indexed_device(device):
+    """torch.device(device) with the index a graph key and a StepGraph need: a bare "cuda" is the current device.  Other device
+    types pass through."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 class StepGraph:
     def __init__(self, fn, device, warmup=1, modules=(), stage_bytes=1 << 20, name="step"):
         """fn(*tensors) -> tensor | tuple | list | dict | None.  modules: the networks whose packed bf16 weights the step reads or

@@ -132,15 +132,13 @@ class OpenAIDiffusion:
                 and device.type == "cuda" and not _graph.capturing():
             # hipGraph replay (dxmi_hip/graph.py): one graph per (batch, destination, labels given or drawn); the first call of a key
             # runs eagerly, the second is captured.  Without `out=` the returned tensors are static (overwritten by the next call).
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
+            device = _graph.indexed_device(device)
             key = (n_sample, device.index, None if out is None else (id(out["ring"]), out["slot"]), i_class is not None)
             g = self._graphs.get(key)
             if g is None:
-                from .trainer import _pack_modules
                 fn = (lambda y: self._sample(n_sample, device, y, False, None, None, out)) if i_class is not None else \
                      (lambda: self._sample(n_sample, device, None, False, None, None, out))
-                g = self._graphs[key] = _graph.StepGraph(fn, device, modules=_pack_modules(self), name=f"OpenAIDiffusion.sample{key}")
+                g = self._graphs[key] = _graph.StepGraph(fn, device, modules=_graph.pack_modules(self), name=f"OpenAIDiffusion.sample{key}")
             return g(i_class) if i_class is not None else g()
         return self._sample(n_sample, device, i_class, enable_grad, x0, noise, out)
 

@@ -57,16 +57,6 @@ def _children_disagree(module, training, last):
     return False
 
 
-def _pack_modules(net):
-    """Sub-modules of `net` that keep packed bf16 weight sets (objects with refresh_packs / prepare_capture)."""
-    mods = net.modules() if hasattr(net, "modules") else [net]
-    out = [m for m in mods if hasattr(m, "refresh_packs") and hasattr(m, "prepare_capture")]
-    inner = getattr(net, "net", None)          # OpenAIDiffusion: a plain object holding the U-Net
-    if not out and inner is not None and hasattr(inner, "modules"):
-        out = [m for m in inner.modules() if hasattr(m, "refresh_packs") and hasattr(m, "prepare_capture")]
-    return out
-
-
 def reset_buffer(device, ring=None):
     """Empty transition buffer (reference :58-70).  ring: a TransitionRing to recycle (its rows are dropped)."""
     if ring is not None:
@@ -137,7 +127,7 @@ class DxMI_Trainer:
             device = state_dict.device
             if torch.is_tensor(getattr(self, "betas_for_q", None)) and self.betas_for_q.device != device:
                 self.betas_for_q = self.betas_for_q.to(device)       # q-betas are indexed on the device inside the step
-            mods = [m for net in nets if net is not None for m in _pack_modules(net)]
+            mods = [m for net in nets if net is not None for m in _graph.pack_modules(net)]
             g = graphs[key] = _graph.StepGraph(fn, device, modules=mods, name=f"{type(self).__name__}.{name}")
         return g
 

@@ -269,8 +269,7 @@ class VARSampler(nn.Module):
         if self.use_graph and noise is None and not _graph.capturing():
             # hipGraph replay (dxmi_hip/graph.py): one graph per (batch, destination); the first call of a key runs eagerly, the
             # second is captured.  Without `out=` the returned tensors are static: the next call with the same key overwrites them.
-            if device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
+            device = _graph.indexed_device(device)
             key = (n_sample, device.index, None if out is None else (id(out["ring"]), out["slot"]))
             g = self._graphs.get(key)
             if g is None:

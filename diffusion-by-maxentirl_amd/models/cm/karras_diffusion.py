@@ -30,6 +30,15 @@ between two network evaluations (denoised, clamp, d, the Heun / DPM-2 / Euler / 
 churn and the next preconditioned input; the clamped sample after the last evaluation).  The consistency-model samplers
 and editing loops follow the same pattern with their own table (CMSchedule) and stage kernel (dxmi_cm_stage).
 
+Host structure.  Both families run through ONE launch loop, _run_stages: a schedule (KarrasSchedule, CMSchedule) is a host table
+(_HostTable: `table`, device_table) plus `launches`, one record per stage launch (last; the generator's draw there and whether it
+is used; the callback's step index), the scratch buffers it needs, stage(), which launches its kernel, and callback_info().  The
+loop itself knows no sampler.  karras_sample settles the sampler, builds denoiser and schedule, and ends for both families in
+_sample_on_device: device, eager or hipGraph replay, the per-model graph cache _GRAPHS.  Schedules and CD levels are memoised by
+_memo in plain dicts.  The two loss nodes run the U-Net through unet_train.train_forward / train_backward, which own the rule for
+running its training program without an autograd ctx; _cd_loss is the consistency loss as a plain function, shared by the node
+and the no-grad call.
+
 Pairing (a deliberate restriction of the device path; the reference allows any combination): onestep and multistep run
 only for a diffusion with distillation=True (boundary-condition scalings), and the EDM samplers only with distillation=False.
 """
@@ -39,7 +48,11 @@ import weakref
 import numpy as np
 import torch
 
+from dxmi_hip import graph as _graph
+from dxmi_hip import ops
+from dxmi_hip._lib import DxmiError
 from .nn import append_dims, append_zero, mean_flat
+from .unet_train import train_backward, train_forward
 
 
 def get_weightings(weight_schedule, snrs, sigma_data):
@@ -70,23 +83,16 @@ class _DSMLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, diffusion, net, x_start, noise, sigmas, y, *params):
-        import types
-        from dxmi_hip import ops
-        from .unet_train import _EDMUNetFn
-        x_in, t = ops.edm_dsm_prep(x_start, noise, sigmas, diffusion.sigma_data)
-        sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
-        F = _EDMUNetFn.forward(sub, net, x_in, t, y, *params)
+        F, tape = train_forward(net, *ops.edm_dsm_prep(x_start, noise, sigmas, diffusion.sigma_data), y)
         kw = dict(weight_schedule=diffusion.weight_schedule, sigma_data=diffusion.sigma_data, sigma_min=diffusion.sigma_min,
                   distillation=diffusion.distillation)
         xs, mse = ops.edm_dsm_loss_fwd(F, x_start, noise, sigmas, **kw)
-        ctx.sub, ctx.F, ctx.kw, ctx.ops = sub, F, kw, (x_start, noise, sigmas)
+        ctx.tape, ctx.F, ctx.kw, ctx.ops = tape, F, kw, (x_start, noise, sigmas)
         ctx.set_materialize_grads(False)
         return xs, mse
 
     @staticmethod
     def backward(ctx, g_xs, g_mse):
-        from dxmi_hip import ops
-        from .unet_train import _EDMUNetFn
         n_params = len(ctx.needs_input_grad) - 6
         if g_xs is None and g_mse is None:
             return (None,) * (6 + n_params)
@@ -94,12 +100,35 @@ class _DSMLossFn(torch.autograd.Function):
         cont = lambda g: None if g is None else g.detach().float().contiguous()
         dF = ops.edm_dsm_loss_bwd(cont(g_mse), cont(g_xs), ctx.F, x_start, noise, sigmas, **ctx.kw)
         ctx.F = None
-        grads = _EDMUNetFn.backward(ctx.sub, dF)
-        ctx.sub = None
-        return (None,) * 6 + tuple(grads[4:])
+        grads = train_backward(ctx.tape, dF)
+        ctx.tape = None
+        return (None,) * 6 + grads
 
 
-class CDLevels:
+class _HostTable:
+    """A small fp32 table built once on the host (`table`) and uploaded once per device."""
+
+    def __init__(self, table):
+        self.table, self._dev = table, {}
+
+    def device_table(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self.table.to(device)
+        return self._dev[key]
+
+
+def _memo(cache, key, cap, build):
+    """cache[key], built on first use; a cache that has grown past `cap` entries is emptied first."""
+    v = cache.get(key)
+    if v is None:
+        if len(cache) > cap:
+            cache.clear()
+        v = cache[key] = build()
+    return v
+
+
+class CDLevels(_HostTable):
     """The num_scales time levels of consistency_losses (reference :180-188), on the host in fp32 torch with the reference's own
     expression: `indices / (num_scales - 1)` is an int64 tensor over a python int, then `** rho`.  Bit-identical to the reference
     on the same CPU (1 ulp of pow across CPUs, as the sigma tables of the samplers).  table[i] = t of index i, table[i + 1] = t2."""
@@ -109,15 +138,8 @@ class CDLevels:
             raise ValueError(f"consistency_losses: num_scales must be at least 2, got {num_scales}")
         indices = torch.arange(int(num_scales), dtype=torch.int64)
         t = sigma_max ** (1 / rho) + indices / (num_scales - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))
-        self.table = (t ** rho).to(torch.float32)
+        super().__init__((t ** rho).to(torch.float32))
         self.num_scales = int(num_scales)
-        self._dev = {}
-
-    def device_table(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = self.table.to(device)
-        return self._dev[key]
 
 
 _CD_LEVELS = {}
@@ -128,26 +150,17 @@ LPIPS_RESIZE_BELOW, LPIPS_SIZE = 256, 224      # reference :222-230: images narr
 
 def cd_levels(num_scales, sigma_min, sigma_max, rho):
     key = (int(num_scales), float(sigma_min), float(sigma_max), float(rho))
-    lv = _CD_LEVELS.get(key)
-    if lv is None:
-        if len(_CD_LEVELS) > 256:
-            _CD_LEVELS.clear()
-        lv = _CD_LEVELS[key] = CDLevels(num_scales, sigma_min, sigma_max, rho)
-    return lv
+    return _memo(_CD_LEVELS, key, 256, lambda: CDLevels(num_scales, sigma_min, sigma_max, rho))
 
 
 def _train_forward_no_grad(net, x_in, t, y, seeds=None):
     """The training forward of `net` without a tape kept (dropout applied).  seeds: the dropout seeds to use, site by site, and
     they must be consumed exactly (a net with more or fewer dropout sites is an error); None: the net draws its own."""
-    import types
-    from dxmi_hip import ops
-    from .unet_train import _EDMUNetFn
-    sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
     if seeds is not None:
         net.__dict__["_dropout_seed_feed"] = list(seeds)
     try:
         with torch.no_grad():
-            out = _EDMUNetFn.forward(sub, net, x_in, t, y, *ops.fast_parameters(net))
+            out, _ = train_forward(net, x_in, t, y)
         left = net.__dict__.get("_dropout_seed_feed")
         if left:
             raise RuntimeError(f"dropout seed hand-over: {len(left)} of {len(seeds)} seeds were not consumed (the two nets differ in "
@@ -157,60 +170,57 @@ def _train_forward_no_grad(net, x_in, t, y, seeds=None):
         net.__dict__.pop("_dropout_seed_feed", None)
 
 
+def _cd_loss(diffusion, net, target, teacher, teacher_diffusion, x_start, noise, indices, tab, y, keep):
+    """prep -> online U-Net forward -> solver stages around the teacher evaluations -> target evaluation -> per-sample loss.
+    -> (loss, (tape, kw, operands, lpips)), the second being what _CDLossFn.backward reads.  keep=False: no backward follows, so
+    LPIPS keeps no activations."""
+    sd = diffusion.sigma_data
+    x_t, x_in, t, x_te = ops.cd_prep(x_start, noise, indices, tab, sd, None if teacher is None else teacher_diffusion.sigma_data)
+    F, tape = train_forward(net, x_in, t, y)
+    seeds = list(net.dropout_seeds_used)
+    if teacher is None:
+        x_t2, tg_in, tg_t = ops.cd_solver(ops.CD_EULER_X0, x_t, indices, tab, x_start=x_start, next_sigma_data=sd)
+    else:
+        tk = dict(sigma_data=teacher_diffusion.sigma_data, sigma_min=teacher_diffusion.sigma_min,
+                  distillation=teacher_diffusion.distillation)
+        F1 = teacher.forward_inference(x_in if x_te is None else x_te, t, y)
+        d, samples, te_in, te_t = ops.cd_solver(ops.CD_HEUN_PRED, x_t, indices, tab, model_out=F1,
+                                                next_sigma_data=teacher_diffusion.sigma_data, **tk)
+        F2 = teacher.forward_inference(te_in, te_t, y)
+        x_t2, tg_in, tg_t = ops.cd_solver(ops.CD_HEUN_CORR, x_t, indices, tab, model_out=F2, d=d, samples=samples,
+                                          next_sigma_data=sd, **tk)
+    if target.training and target.dropout > 0:
+        # an online forward that dropped nothing (eval mode, or dropout 0) has no masks to share: the target draws its own
+        F_tg = _train_forward_no_grad(target, tg_in, tg_t, y, seeds if seeds else None)
+    else:
+        F_tg = target.forward_inference(tg_in, tg_t, y)
+    kw = dict(loss_norm=diffusion.loss_norm, weight_schedule=diffusion.weight_schedule, sigma_data=sd,
+              sigma_min=diffusion.sigma_min, distillation=diffusion.distillation)
+    if diffusion.loss_norm == "lpips":
+        from dxmi_hip import lpips_ops
+        from .lpips import _lpips_forward
+        del kw["loss_norm"]
+        lp = diffusion._lpips()
+        x01, w = lpips_ops.cd_lpips_images(F, F_tg, x_t, x_t2, indices, tab, **kw)
+        loss, acts = _lpips_forward(lp, x01, LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None, scale=w, keep=keep)
+        return loss, (tape, kw, (indices, tab), (lp, acts, tuple(x_start.shape[2:])))
+    return ops.cd_loss_fwd(F, F_tg, x_t, x_t2, indices, tab, **kw), (tape, kw, (F, F_tg, x_t, x_t2, indices, tab), None)
+
+
 class _CDLossFn(torch.autograd.Function):
-    """prep -> online U-Net forward -> solver stages around the teacher evaluations -> target evaluation -> per-sample loss, as
-    one node around the online network."""
+    """_cd_loss as one node around the online network."""
 
     @staticmethod
     def forward(ctx, diffusion, net, target, teacher, teacher_diffusion, x_start, noise, indices, tab, y, *params):
-        import types
-        from dxmi_hip import ops
-        from .unet_train import _EDMUNetFn
-        sd = diffusion.sigma_data
-        x_t, x_in, t, x_te = ops.cd_prep(x_start, noise, indices, tab, sd, None if teacher is None else teacher_diffusion.sigma_data)
-        sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
-        F = _EDMUNetFn.forward(sub, net, x_in, t, y, *params)
-        seeds = list(net.dropout_seeds_used)
-        if teacher is None:
-            x_t2, tg_in, tg_t = ops.cd_solver(ops.CD_EULER_X0, x_t, indices, tab, x_start=x_start, next_sigma_data=sd)
-        else:
-            tk = dict(sigma_data=teacher_diffusion.sigma_data, sigma_min=teacher_diffusion.sigma_min,
-                      distillation=teacher_diffusion.distillation)
-            F1 = teacher.forward_inference(x_in if x_te is None else x_te, t, y)
-            d, samples, te_in, te_t = ops.cd_solver(ops.CD_HEUN_PRED, x_t, indices, tab, model_out=F1,
-                                                    next_sigma_data=teacher_diffusion.sigma_data, **tk)
-            F2 = teacher.forward_inference(te_in, te_t, y)
-            x_t2, tg_in, tg_t = ops.cd_solver(ops.CD_HEUN_CORR, x_t, indices, tab, model_out=F2, d=d, samples=samples,
-                                              next_sigma_data=sd, **tk)
-        if target.training and target.dropout > 0:
-            # an online forward that dropped nothing (eval mode, or dropout 0) has no masks to share: the target draws its own
-            F_tg = _train_forward_no_grad(target, tg_in, tg_t, y, seeds if seeds else None)
-        else:
-            F_tg = target.forward_inference(tg_in, tg_t, y)
-        kw = dict(loss_norm=diffusion.loss_norm, weight_schedule=diffusion.weight_schedule, sigma_data=sd,
-                  sigma_min=diffusion.sigma_min, distillation=diffusion.distillation)
-        if diffusion.loss_norm == "lpips":
-            from dxmi_hip import lpips_ops
-            from .lpips import _lpips_forward
-            del kw["loss_norm"]
-            lp = diffusion._lpips()
-            x01, w = lpips_ops.cd_lpips_images(F, F_tg, x_t, x_t2, indices, tab, **kw)
-            loss, acts = _lpips_forward(lp, x01, LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None, scale=w,
-                                        keep=not getattr(ctx, "no_backward", False))
-            ctx.sub, ctx.kw, ctx.ops, ctx.lpips = sub, kw, (indices, tab), (lp, acts, tuple(x_start.shape[2:]))
-        else:
-            loss = ops.cd_loss_fwd(F, F_tg, x_t, x_t2, indices, tab, **kw)
-            ctx.sub, ctx.kw, ctx.ops, ctx.lpips = sub, kw, (F, F_tg, x_t, x_t2, indices, tab), None
+        loss, (ctx.tape, ctx.kw, ctx.ops, ctx.lpips) = _cd_loss(diffusion, net, target, teacher, teacher_diffusion, x_start, noise,
+                                                                indices, tab, y, keep=True)
         ctx.set_materialize_grads(False)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        from dxmi_hip import ops
-        from .unet_train import _EDMUNetFn
-        n_in = len(ctx.needs_input_grad)
         if g is None:
-            return (None,) * n_in
+            return (None,) * len(ctx.needs_input_grad)
         if ctx.lpips is not None:
             from dxmi_hip import lpips_ops
             from .lpips import _lpips_backward
@@ -218,9 +228,9 @@ class _CDLossFn(torch.autograd.Function):
         else:
             dF = ops.cd_loss_bwd(g.detach().float().contiguous(), *ctx.ops, **ctx.kw)
         ctx.ops = ctx.lpips = None
-        grads = _EDMUNetFn.backward(ctx.sub, dF)
-        ctx.sub = None
-        return (None,) * 10 + tuple(grads[4:])
+        grads = train_backward(ctx.tape, dF)
+        ctx.tape = None
+        return (None,) * 10 + grads
 
 
 class KarrasDenoiser:
@@ -281,8 +291,6 @@ class KarrasDenoiser:
         return terms
 
     def _training_losses_hip(self, net, x_start, sigmas, model_kwargs, noise):
-        from dxmi_hip import graph as _graph
-        from dxmi_hip import ops
         if x_start.requires_grad or sigmas.requires_grad or noise.requires_grad:
             raise NotImplementedError("training_losses on the HIP U-Net differentiates the network parameters only: x_start, "
                                       "noise and sigmas must not require grad")
@@ -301,15 +309,10 @@ class KarrasDenoiser:
                              f"({sigmas.numel()}) hold one level per sample")
         if torch.is_grad_enabled():
             xs, mse = _DSMLossFn.apply(self, net, x_start, noise, sigmas, y, *ops.fast_parameters(net))
-        elif net.training and net.dropout > 0:      # dropout is part of the loss in train mode: the training forward applies it
-            import types
-            from .unet_train import _EDMUNetFn
-            sub = types.SimpleNamespace(needs_input_grad=(False, False, False, False))
-            F = _EDMUNetFn.forward(sub, net, *ops.edm_dsm_prep(x_start, noise, sigmas, self.sigma_data), y, *ops.fast_parameters(net))
-            xs, mse = ops.edm_dsm_loss_fwd(F, x_start, noise, sigmas, self.weight_schedule, self.sigma_data, self.sigma_min,
-                                           self.distillation)
         else:
-            F = net.forward_inference(*ops.edm_dsm_prep(x_start, noise, sigmas, self.sigma_data), y)
+            x_in, t = ops.edm_dsm_prep(x_start, noise, sigmas, self.sigma_data)
+            # dropout is part of the loss in train mode: the training forward applies it
+            F = train_forward(net, x_in, t, y)[0] if net.training and net.dropout > 0 else net.forward_inference(x_in, t, y)
             xs, mse = ops.edm_dsm_loss_fwd(F, x_start, noise, sigmas, self.weight_schedule, self.sigma_data, self.sigma_min,
                                            self.distillation)
         return {"xs_mse": xs, "mse": mse, "loss": mse}
@@ -386,8 +389,6 @@ class KarrasDenoiser:
         raise NotImplementedError("progressive distillation (progdist_losses, reference :243-335) is not implemented")
 
     def _consistency_losses_hip(self, nets, x_start, num_scales, model_kwargs, teacher_diffusion, noise, indices):
-        from dxmi_hip import graph as _graph
-        from dxmi_hip import ops
         net, target = nets[0], nets[1]
         teacher = nets[2] if len(nets) > 2 else None
         if x_start.requires_grad or noise.requires_grad:
@@ -413,8 +414,7 @@ class KarrasDenoiser:
         if torch.is_grad_enabled():
             loss = _CDLossFn.apply(*args, *ops.fast_parameters(net))
         else:
-            import types
-            loss = _CDLossFn.forward(types.SimpleNamespace(set_materialize_grads=lambda v: None, no_backward=True), *args, *ops.fast_parameters(net))
+            loss, _ = _cd_loss(*args, keep=False)
         return {"loss": loss}
 
     def denoise(self, model, x_t, sigmas, **model_kwargs):
@@ -467,17 +467,17 @@ def _refuse_distillation(diffusion):
                                   "scalings belong to consistency-distilled models, which sample with onestep / multistep")
 
 
-class KarrasSchedule:
+class KarrasSchedule(_HostTable):
     """Host schedule of one sampler over a sigma ladder, in fp32 torch with the reference's expressions (:447-640).
 
     Per step i: gamma (python float, as the reference), sigma_hat, churn = (sigma_hat^2 - sigma^2)^0.5, and per sampler the
     step sizes (dt; dpm: sigma_mid, dt_1, dt_2; ancestral: sigma_down, sigma_up).  `launches` is the launch sequence of
     dxmi_karras_stage: launch 0 (FIRST) precedes evaluation 1 and launch k follows evaluation k; `table` holds one row per launch
-    (include/dxmi_hip.h, DXMI_KT_*)."""
+    (include/dxmi_hip.h, DXMI_KT_*).  What _run_stages reads of a launch: `last`; `draw`, the draw a generator makes there (None:
+    none) and `used`, whether its result reaches the kernel; `cb`, the callback's step index (None: no callback)."""
 
     def __init__(self, sigmas, sampler, diffusion, clip_denoised=True, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0,
                  x_scale=1.0):
-        from dxmi_hip import ops
         if sampler not in KARRAS_SAMPLERS:
             raise ValueError(f"unknown Karras sampler {sampler!r}; the device path runs {KARRAS_SAMPLERS}")
         sigmas = sigmas.detach().to("cpu", torch.float32)
@@ -531,7 +531,11 @@ class KarrasSchedule:
             else:   # euler, and heun's last step (sigma_{i+1} = 0: Euler, :537-539)
                 L.append(dict(mode=ops.KARRAS_EULER, last=i == n - 1, sig=sh[i], dt=dt[i], up=z,
                               nxt=None if i == n - 1 else sigmas[i + 1], churn_step=None, draw=None, cb=i))
+        for l in L:     # eps at gamma = 0 and a z at sigma_up = 0 (the last ancestral step) are drawn for the generator's sake alone
+            kind, i = l["draw"] or (None, None)
+            l["used"] = kind is not None and (self.gamma[i] > 0 if kind == "eps" else float(up[i]) != 0.0)
         self.launches = L
+        self.scratch = ("x2", "d") if churned else ()       # state buffers next to x / x_in / t / out
         self.nfe = len(L) - 1
         self.eval_sigmas = torch.stack([l["nxt"] for l in L if l["nxt"] is not None])      # noise level of every evaluation
 
@@ -550,26 +554,28 @@ class KarrasSchedule:
                 tab[k, ops.KT_T] = (1000 * 0.25 * torch.log(s + 1e-44))[0]      # denoise() (:348)
             tab[k, ops.KT_XSCALE] = x_scale
             tab[k, ops.KT_CLIP] = 1.0 if clip_denoised else 0.0
-        self.table = tab
-        self._dev = {}
+        super().__init__(tab)
 
-    def device_table(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = self.table.to(device)
-        return self._dev[key]
+    def stage(self, k, bufs, F, noise, den):
+        l = self.launches[k]
+        last = l["last"]
+        ops.karras_stage(l["mode"], last, bufs["tab"], k, bufs["x"], x2=bufs.get("x2"), d=bufs.get("d"), model_out=F, noise=noise,
+                         x_in=None if last else bufs["x_in"], t=None if last else bufs["t"], out=bufs["out"] if last else None,
+                         denoised=den)
+
+    def callback_info(self, k, x, den):
+        i = self.launches[k]["cb"]
+        info = {"x": x, "i": i, "sigma": self.sigmas[i], "sigma_hat": self.sigma_hat[i], "denoised": den}
+        if self.sampler == "euler":
+            del info["sigma_hat"]          # the reference's euler callback has none (:566-574)
+        return info
 
 
 def _schedule(sigmas, sampler, denoiser, x_scale, s_churn, s_tmin, s_tmax, s_noise):
     key = (sampler, tuple(sigmas.detach().cpu().float().tolist()), float(denoiser.diffusion.sigma_data), denoiser.clip_denoised,
            float(s_churn), float(s_tmin), float(s_tmax), float(s_noise), float(x_scale))
-    sch = _SCHEDULES.get(key)
-    if sch is None:
-        if len(_SCHEDULES) > 64:
-            _SCHEDULES.clear()
-        sch = _SCHEDULES[key] = KarrasSchedule(sigmas, sampler, denoiser.diffusion, denoiser.clip_denoised, s_churn, s_tmin,
-                                               s_tmax, s_noise, x_scale)
-    return sch
+    return _memo(_SCHEDULES, key, 64, lambda: KarrasSchedule(sigmas, sampler, denoiser.diffusion, denoiser.clip_denoised, s_churn,
+                                                             s_tmin, s_tmax, s_noise, x_scale))
 
 
 def _as_f32(v, device):
@@ -577,23 +583,22 @@ def _as_f32(v, device):
     return v if v.is_contiguous() else v.contiguous()
 
 
-def _run(sch, denoiser, x0, shape, device, generator, callback=None, progress=False):
-    """The launch sequence of `sch`: FIRST, then per network evaluation one dxmi_karras_stage launch.  x0: the initial state
-    (scaled by the table's XSCALE), or None to draw it (generator.randn, else on the device).  -> the clamped sample (a new
-    tensor, static under graph capture)."""
-    from dxmi_hip import ops
+def _run_stages(sch, denoiser, x0, shape, device, generator, callback=None, progress=False, **edit):
+    """The launch sequence of `sch` (a KarrasSchedule or a CMSchedule): FIRST, then per network evaluation one stage launch.  x0: the
+    initial state (scaled by the table's XSCALE), or None to draw it (generator.randn, else on the device).  edit: what the editing
+    loops hand to every dxmi_cm_stage launch after FIRST (edit, Q, ref, mask).  -> the output (a new tensor, static under graph
+    capture)."""
     f32 = dict(dtype=torch.float32, device=device)
-    tab = sch.device_table(device)
-    x = torch.empty(shape, **f32)
+    bufs = dict(tab=sch.device_table(device), x=torch.empty(shape, **f32))
+    x = bufs["x"]
     if x0 is not None:
         x.copy_(x0)
     elif generator is not None:
         x.copy_(generator.randn(*shape, device=device))
     else:
         x.normal_()
-    two = sch.sampler in ("heun", "dpm")
-    x2, d = (torch.empty(shape, **f32), torch.empty(shape, **f32)) if two else (None, None)
-    x_in, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
+    bufs.update({k: torch.empty(shape, **f32) for k in sch.scratch + ("x_in",)}, t=torch.empty(shape[0], **f32),
+                out=torch.empty(shape, **f32))
     noise_buf = None
     model, kw = denoiser.model, denoiser.model_kwargs
     launches = range(len(sch.launches))
@@ -607,33 +612,26 @@ def _run(sch, denoiser, x0, shape, device, generator, callback=None, progress=Fa
     for k in launches:
         l = sch.launches[k]
         if k > 0:
-            F = model(x_in, t, **kw)
+            F = model(bufs["x_in"], bufs["t"], **kw)
             if F.dtype != torch.float32 or not F.is_contiguous() or F.device != x.device:
                 F = _as_f32(F, device)
             assert F.shape == x.shape, f"model output {tuple(F.shape)} != sample shape {tuple(x.shape)}"
         noise = None
         if l["draw"] is not None:
-            kind, i = l["draw"]
-            used = sch.gamma[i] > 0 if kind == "eps" else float(sch.sigma_up[i]) != 0.0
-            if generator is not None:     # the reference's draws, in its order and number (:522, :603, :477)
+            if generator is not None:     # the reference's draws, in its order and number (:522, :603, :477, :681)
                 draw = generator.randn_like(x)
-                noise = _as_f32(draw, device) if used else None
-            elif used:
+                noise = _as_f32(draw, device) if l["used"] else None
+            elif l["used"]:
                 if noise_buf is None:
                     noise_buf = torch.empty(shape, **f32)
                 noise = noise_buf.normal_()
         den, cb_x = None, None
         if callback is not None and l["cb"] is not None:
             den, cb_x = torch.empty(shape, **f32), x.clone()
-        ops.karras_stage(l["mode"], l["last"], tab, k, x, x2=x2, d=d, model_out=F, noise=noise, x_in=None if l["last"] else x_in,
-                         t=None if l["last"] else t, out=out if l["last"] else None, denoised=den)
+        sch.stage(k, bufs, F, noise, den, **edit)
         if den is not None:
-            i = l["cb"]
-            info = {"x": cb_x, "i": i, "sigma": sch.sigmas[i], "sigma_hat": sch.sigma_hat[i], "denoised": den}
-            if sch.sampler == "euler":
-                del info["sigma_hat"]          # the reference's euler callback has none (:566-574)
-            callback(info)
-    return out
+            callback(sch.callback_info(k, cb_x, den))
+    return bufs["out"]
 
 
 def _check_sampler_args(denoiser, x, edm=True):
@@ -650,7 +648,6 @@ def _check_sampler_args(denoiser, x, edm=True):
 
 def _check_device(x):
     if not x.is_cuda:
-        from dxmi_hip._lib import DxmiError
         raise DxmiError("the Karras samplers run only on the HIP device path (no CPU fallback)")
 
 
@@ -659,7 +656,7 @@ def sample_euler_ancestral(model, x, sigmas, generator, progress=False, callback
     """Ancestral sampling with Euler steps (reference :447-478).  model: a KarrasDenoiserFn; x: the initial state."""
     _check_sampler_args(model, x)
     sch = _schedule(sigmas, "ancestral", model, 1.0, 0.0, 0.0, float("inf"), 1.0)
-    return _run(sch, model, x, tuple(x.shape), x.device, generator, callback, progress)
+    return _run_stages(sch, model, x, tuple(x.shape), x.device, generator, callback, progress)
 
 
 @torch.no_grad()
@@ -668,7 +665,7 @@ def sample_heun(denoiser, x, sigmas, generator, progress=False, callback=None, s
     """Algorithm 2 (Heun steps) of Karras et al. (2022) (reference :499-547).  NFE = 2 * steps - 1 (the last step is Euler)."""
     _check_sampler_args(denoiser, x)
     sch = _schedule(sigmas, "heun", denoiser, 1.0, s_churn, s_tmin, s_tmax, s_noise)
-    return _run(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
+    return _run_stages(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
 
 
 @torch.no_grad()
@@ -676,7 +673,7 @@ def sample_euler(denoiser, x, sigmas, generator, progress=False, callback=None):
     """Euler steps (reference :550-578).  NFE = steps."""
     _check_sampler_args(denoiser, x)
     sch = _schedule(sigmas, "euler", denoiser, 1.0, 0.0, 0.0, float("inf"), 1.0)
-    return _run(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
+    return _run_stages(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
 
 
 @torch.no_grad()
@@ -685,7 +682,7 @@ def sample_dpm(denoiser, x, sigmas, generator, progress=False, callback=None, s_
     """DPM-Solver-2-like midpoint steps, midpoint on a rho=3 Karras ladder (reference :581-621).  NFE = 2 * steps."""
     _check_sampler_args(denoiser, x)
     sch = _schedule(sigmas, "dpm", denoiser, 1.0, s_churn, s_tmin, s_tmax, s_noise)
-    return _run(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
+    return _run_stages(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
 
 
 def karras_nfe(sampler, steps):
@@ -708,49 +705,61 @@ def karras_sample(diffusion, model, shape, steps, clip_denoised=True, progress=F
     of the same key overwrites it.  Off with callback, progress or a generator, and for model_kwargs other than `y`.
     sampler onestep / multistep (ts: the multistep step indices in [0, steps - 1]): consistency-model sampling, only for a
     diffusion with distillation=True (see the module docstring); multistep uses diffusion.rho, as the reference does (:400)."""
+    denoiser = KarrasDenoiserFn(diffusion, model, clip_denoised, model_kwargs)
     if sampler in CM_SAMPLERS and getattr(diffusion, "distillation", False):
-        return _karras_sample_cm(diffusion, model, shape, steps, clip_denoised, progress, callback, model_kwargs, device,
-                                 sigma_min, sigma_max, rho, sampler, generator, ts, use_graph)
+        # x_T = randn * sigma_max, clamp(x_0, -1, 1); the schedule (and so ts) is settled before the device is looked at
+        if sampler == "onestep":
+            sigma0 = float(get_sigmas_karras(steps, sigma_min, sigma_max, rho)[0])
+            sch = _cm_schedule("onestep", diffusion, None, steps, sigma_min, sigma_max, rho, clip_denoised, sigma_max, True, sigma0)
+        else:
+            ts = _check_ts(ts, steps)
+            sch = _cm_schedule("multistep", diffusion, ts, steps, sigma_min, sigma_max, diffusion.rho, clip_denoised, sigma_max,
+                               True)
+        key = (sampler, steps, ts, float(sigma_min), float(sigma_max), float(rho), float(diffusion.rho),
+               bool(diffusion.distillation), bool(clip_denoised), float(diffusion.sigma_data))
+        return _sample_on_device(lambda: sch, denoiser, shape, device, "cm_sample", key, use_graph, generator, callback, progress)
     if sampler in _DISTILLED_SAMPLERS:
         raise NotImplementedError(f"sampler {sampler!r} needs a consistency-distilled model (`ts`, boundary-condition scalings), "
                                   "which no config here builds; the device path runs heun, dpm, euler and ancestral")
     if sampler not in KARRAS_SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}")
     _refuse_distillation(diffusion)
-    denoiser = KarrasDenoiserFn(diffusion, model, clip_denoised, model_kwargs)
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type != "cuda":
-        from dxmi_hip._lib import DxmiError
-        raise DxmiError("karras_sample runs only on the HIP device path (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    shape = tuple(int(s) for s in shape)
-    sigmas = get_sigmas_karras(steps, sigma_min, sigma_max, rho, device="cpu")
     churned = sampler in ("heun", "dpm")
-    sch = _schedule(sigmas, sampler, denoiser, sigma_max, s_churn if churned else 0.0, s_tmin if churned else 0.0,
-                    s_tmax if churned else float("inf"), s_noise if churned else 1.0)
-    from dxmi_hip import graph as _graph
-    kw = denoiser.model_kwargs
-    if use_graph and callback is None and not progress and generator is None and set(kw) <= {"y"} \
-            and not _graph.capturing():
-        key = (sampler, steps, float(sigma_min), float(sigma_max), float(rho), float(s_churn), float(s_tmin), float(s_tmax),
-               float(s_noise), bool(clip_denoised), float(diffusion.sigma_data), shape, device.index, "y" in kw)
+    schedule = lambda: _schedule(get_sigmas_karras(steps, sigma_min, sigma_max, rho, device="cpu"), sampler, denoiser, sigma_max,
+                                 s_churn if churned else 0.0, s_tmin if churned else 0.0, s_tmax if churned else float("inf"),
+                                 s_noise if churned else 1.0)
+    key = (sampler, steps, float(sigma_min), float(sigma_max), float(rho), float(s_churn), float(s_tmin), float(s_tmax),
+           float(s_noise), bool(clip_denoised), float(diffusion.sigma_data))
+    return _sample_on_device(schedule, denoiser, shape, device, "karras_sample", key, use_graph, generator, callback, progress)
+
+
+def _sample_on_device(schedule, denoiser, shape, device, name, key, use_graph, generator, callback, progress):
+    """karras_sample once the sampler is settled: resolve the device, build the schedule (schedule()), then run its launch
+    sequence, eagerly or as the hipGraph of (key, shape, device, labels given) in the model's graphs."""
+    device = _graph.indexed_device(torch.device("cuda") if device is None else device)
+    if device.type != "cuda":
+        raise DxmiError("karras_sample runs only on the HIP device path (no CPU fallback)")
+    shape = tuple(int(s) for s in shape)
+    sch = schedule()
+    model, kw = denoiser.model, denoiser.model_kwargs
+    with torch.no_grad():
+        if not (use_graph and callback is None and not progress and generator is None and set(kw) <= {"y"}
+                and not _graph.capturing()):
+            return _run_stages(sch, denoiser, None, shape, device, generator, callback, progress)
+        key = key + (shape, device.index, "y" in kw)
         try:
             graphs = _GRAPHS.setdefault(model, {})
         except TypeError:        # not weak-referenceable: no cache, so no replay
             graphs = {}
         g = graphs.get(key)
         if g is None:
-            from models.DxMI.trainer import _pack_modules
             if "y" in kw:
-                fn = lambda y: _run(sch, KarrasDenoiserFn(diffusion, model, clip_denoised, {"y": y}), None, shape, device, None)
+                fn = lambda y: _run_stages(sch, KarrasDenoiserFn(denoiser.diffusion, model, denoiser.clip_denoised, {"y": y}), None,
+                                           shape, device, None)
             else:
-                fn = lambda: _run(sch, denoiser, None, shape, device, None)
-            g = graphs[key] = _graph.StepGraph(fn, device, modules=_pack_modules(model), name=f"karras_sample{key}")
-        with torch.no_grad():
-            return g(kw["y"]) if "y" in kw else g()
-    with torch.no_grad():
-        return _run(sch, denoiser, None, shape, device, generator, callback, progress)
+                fn = lambda: _run_stages(sch, denoiser, None, shape, device, None)
+            g = graphs[key] = _graph.StepGraph(fn, device, modules=_graph.pack_modules(model), name=f"{name}{key}")
+        return g(kw["y"]) if "y" in kw else g()
 
 
 # ------------------------------------------------------------------------------------------------- consistency-model samplers
@@ -772,7 +781,7 @@ def _check_ts(ts, steps):
     return tuple(ts)
 
 
-class CMSchedule:
+class CMSchedule(_HostTable):
     """Host table of the consistency-model samplers (reference :644-683) and editing loops (:722-951).
 
     onestep evaluates once at sigma0 (karras_sample: sigmas[0] = sigma_max of the fp32 Karras ladder).  multistep evaluates at
@@ -781,11 +790,13 @@ class CMSchedule:
     [t_min, t_max] (np.clip / np.sqrt, float64; nonzero after the last evaluation unless ts[-1] = steps - 1).  The network sees
     fp32(t) (t * s_in); the scalings are the diffusion's boundary-condition ones when distillation is set, else the plain ones,
     evaluated on that fp32 sigma as denoise() does.  Row 0 is the FIRST launch, row k the launch after evaluation k
-    (include/dxmi_hip.h, DXMI_CT_*)."""
+    (include/dxmi_hip.h, DXMI_CT_*); `launches` describes them to _run_stages as KarrasSchedule's do: one z per multistep
+    evaluation, the last included, used unless its factor is 0; none for onestep; the callback fires after every evaluation."""
+
+    scratch = ()
 
     def __init__(self, sampler, diffusion, ts=None, steps=40, t_min=0.002, t_max=80.0, rho=7.0, clip_denoised=True,
                  x_scale=1.0, out_clamp=False, sigma0=None):
-        from dxmi_hip import ops
         if sampler == "onestep":
             self.t = [float(sigma0)]
             self.noise = [0.0]
@@ -802,6 +813,10 @@ class CMSchedule:
         else:
             raise ValueError(f"unknown consistency sampler {sampler!r}; the device path runs onestep and multistep")
         self.sampler, self.nfe = sampler, len(self.t)
+        self.launches = [dict(mode=ops.CM_FIRST, last=False, draw=None, used=False, cb=None)]
+        for k in range(1, self.nfe + 1):
+            self.launches.append(dict(mode=ops.CM_STEP, last=k == self.nfe, draw=("z", k - 1) if sampler == "multistep" else None,
+                                      used=sampler == "multistep" and float(self.noise[k - 1]) != 0.0, cb=k - 1))
         self.eval_sigmas = torch.stack([torch.tensor([t], dtype=torch.float32)[0] for t in self.t])   # fp32(t): t * s_in
         scal = diffusion.get_scalings_for_boundary_condition if diffusion.distillation else diffusion.get_scalings
         tab = torch.zeros((self.nfe + 1, ops.CT_COLS), dtype=torch.float32)
@@ -817,26 +832,24 @@ class CMSchedule:
             tab[k, ops.CT_XSCALE] = x_scale
             tab[k, ops.CT_CLIP] = 1.0 if clip_denoised else 0.0
             tab[k, ops.CT_OUTCLAMP] = 1.0 if out_clamp else 0.0
-        self.table = tab
-        self._dev = {}
+        super().__init__(tab)
 
-    def device_table(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = self.table.to(device)
-        return self._dev[key]
+    def stage(self, k, bufs, F, noise, den, **edit):
+        l = self.launches[k]
+        last = l["last"]
+        ops.cm_stage(l["mode"], last, bufs["tab"], k, bufs["x"], model_out=F, noise=noise, x_in=None if last else bufs["x_in"],
+                     t=None if last else bufs["t"], out=bufs["out"] if last else None, denoised=den, **(edit if k > 0 else {}))
+
+    def callback_info(self, k, x, den):
+        return {"x": x, "i": k - 1, "sigma": self.eval_sigmas[k - 1], "denoised": den}
 
 
 def _cm_schedule(sampler, diffusion, ts, steps, t_min, t_max, rho, clip, x_scale, out_clamp, sigma0=None):
     key = (sampler, None if ts is None else tuple(float(v) for v in ts), int(steps), float(t_min), float(t_max), float(rho),
            float(diffusion.sigma_data), float(diffusion.sigma_min), bool(diffusion.distillation), bool(clip), float(x_scale),
            bool(out_clamp), None if sigma0 is None else float(sigma0))
-    sch = _CM_SCHEDULES.get(key)
-    if sch is None:
-        if len(_CM_SCHEDULES) > 64:
-            _CM_SCHEDULES.clear()
-        sch = _CM_SCHEDULES[key] = CMSchedule(sampler, diffusion, ts, steps, t_min, t_max, rho, clip, x_scale, out_clamp, sigma0)
-    return sch
+    return _memo(_CM_SCHEDULES, key, 64, lambda: CMSchedule(sampler, diffusion, ts, steps, t_min, t_max, rho, clip, x_scale, out_clamp,
+                                                            sigma0))
 
 
 def _orthogonal(vector):
@@ -866,57 +879,6 @@ def patch_basis():
     return _Q_CACHE["patch"]
 
 
-def _run_cm(sch, denoiser, x0, shape, device, generator, edit=None, Q=None, ref=None, mask=None, callback=None,
-            progress=False):
-    """FIRST, then per network evaluation one dxmi_cm_stage launch.  x0: the initial state (scaled by XSCALE), or None to draw
-    it (generator.randn, else on the device).  -> the output (a new tensor, static under graph capture)."""
-    from dxmi_hip import ops
-    edit = ops.CM_EDIT_NONE if edit is None else edit
-    f32 = dict(dtype=torch.float32, device=device)
-    tab = sch.device_table(device)
-    x = torch.empty(shape, **f32)
-    if x0 is not None:
-        x.copy_(x0)
-    elif generator is not None:
-        x.copy_(generator.randn(*shape, device=device))
-    else:
-        x.normal_()
-    x_in, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
-    ops.cm_stage(ops.CM_FIRST, False, tab, 0, x, x_in=x_in, t=t)
-    noise_buf = None
-    model, kw = denoiser.model, denoiser.model_kwargs
-    evals = range(1, sch.nfe + 1)
-    if progress:
-        try:
-            from tqdm.auto import tqdm
-            evals = tqdm(evals)
-        except ImportError:
-            pass
-    for k in evals:
-        last = k == sch.nfe
-        F = model(x_in, t, **kw)
-        if F.dtype != torch.float32 or not F.is_contiguous() or F.device != x.device:
-            F = _as_f32(F, device)
-        assert F.shape == x.shape, f"model output {tuple(F.shape)} != sample shape {tuple(x.shape)}"
-        noise = None
-        used = float(sch.noise[k - 1]) != 0.0
-        if sch.sampler == "multistep" and generator is not None:     # one randn_like per step, the last included (:681)
-            draw = generator.randn_like(x)
-            noise = _as_f32(draw, device) if used else None
-        elif sch.sampler == "multistep" and used:
-            if noise_buf is None:
-                noise_buf = torch.empty(shape, **f32)
-            noise = noise_buf.normal_()
-        den, cb_x = None, None
-        if callback is not None:
-            den, cb_x = torch.empty(shape, **f32), x.clone()
-        ops.cm_stage(ops.CM_STEP, last, tab, k, x, edit=edit, Q=Q, model_out=F, noise=noise, ref=ref, mask=mask,
-                     x_in=None if last else x_in, t=None if last else t, out=out if last else None, denoised=den)
-        if den is not None:
-            callback({"x": cb_x, "i": k - 1, "sigma": sch.eval_sigmas[k - 1], "denoised": den})
-    return out
-
-
 def _check_cm_args(distiller, x):
     _check_sampler_args(distiller, x, edm=False)
 
@@ -929,7 +891,7 @@ def sample_onestep(distiller, x, sigmas, generator=None, progress=False, callbac
     _check_cm_args(distiller, x)
     sch = _cm_schedule("onestep", distiller.diffusion, None, 1, 0.002, 80.0, 7.0, distiller.clip_denoised, 1.0, False,
                        sigma0=float(torch.as_tensor(sigmas[0], dtype=torch.float32)))
-    return _run_cm(sch, distiller, x, tuple(x.shape), x.device, generator, callback=callback, progress=progress)
+    return _run_stages(sch, distiller, x, tuple(x.shape), x.device, generator, callback, progress)
 
 
 @torch.no_grad()
@@ -940,50 +902,7 @@ def stochastic_iterative_sampler(distiller, x, sigmas, generator, ts, progress=F
     _check_ts(ts, steps)
     _check_cm_args(distiller, x)
     sch = _cm_schedule("multistep", distiller.diffusion, ts, steps, t_min, t_max, rho, distiller.clip_denoised, 1.0, False)
-    return _run_cm(sch, distiller, x, tuple(x.shape), x.device, generator, callback=callback, progress=progress)
-
-
-def _karras_sample_cm(diffusion, model, shape, steps, clip_denoised, progress, callback, model_kwargs, device, sigma_min,
-                      sigma_max, rho, sampler, generator, ts, use_graph):
-    """karras_sample's onestep / multistep branch (distillation=True): x_T = randn * sigma_max, clamp(x_0, -1, 1)."""
-    if sampler == "multistep":
-        ts = _check_ts(ts, steps)
-    denoiser = KarrasDenoiserFn(diffusion, model, clip_denoised, model_kwargs)
-    if sampler == "onestep":
-        sigma0 = float(get_sigmas_karras(steps, sigma_min, sigma_max, rho)[0])
-        sch = _cm_schedule("onestep", diffusion, None, steps, sigma_min, sigma_max, rho, clip_denoised, sigma_max, True, sigma0)
-    else:
-        sch = _cm_schedule("multistep", diffusion, ts, steps, sigma_min, sigma_max, diffusion.rho, clip_denoised, sigma_max,
-                           True)
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type != "cuda":
-        from dxmi_hip._lib import DxmiError
-        raise DxmiError("karras_sample runs only on the HIP device path (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    shape = tuple(int(s) for s in shape)
-    from dxmi_hip import graph as _graph
-    kw = denoiser.model_kwargs
-    if use_graph and callback is None and not progress and generator is None and set(kw) <= {"y"} \
-            and not _graph.capturing():
-        key = (sampler, steps, ts, float(sigma_min), float(sigma_max), float(rho), float(diffusion.rho),
-               bool(diffusion.distillation), bool(clip_denoised), float(diffusion.sigma_data), shape, device.index, "y" in kw)
-        try:
-            graphs = _GRAPHS.setdefault(model, {})
-        except TypeError:        # not weak-referenceable: no cache, so no replay
-            graphs = {}
-        g = graphs.get(key)
-        if g is None:
-            from models.DxMI.trainer import _pack_modules
-            if "y" in kw:
-                fn = lambda y: _run_cm(sch, KarrasDenoiserFn(diffusion, model, clip_denoised, {"y": y}), None, shape, device, None)
-            else:
-                fn = lambda: _run_cm(sch, denoiser, None, shape, device, None)
-            g = graphs[key] = _graph.StepGraph(fn, device, modules=_pack_modules(model), name=f"cm_sample{key}")
-        with torch.no_grad():
-            return g(kw["y"]) if "y" in kw else g()
-    with torch.no_grad():
-        return _run_cm(sch, denoiser, None, shape, device, generator, callback=callback, progress=progress)
+    return _run_stages(sch, distiller, x, tuple(x.shape), x.device, generator, callback, progress)
 
 
 # ------------------------------------------------------------------------------------------------------ zero-shot editing
@@ -1030,14 +949,13 @@ def _edit_args(distiller, images, x, ts, steps, generator):
 def _edit(distiller, x, ts, t_min, t_max, rho, steps, generator, edit, Q, ref, mask=None):
     # the editing loops clamp x0 themselves (:758, :819, :938): CLIP is on whatever clip_denoised says
     sch = _cm_schedule("multistep", distiller.diffusion, ts, steps, t_min, t_max, rho, True, 1.0, False)
-    return _run_cm(sch, distiller, x, tuple(x.shape), x.device, generator, edit=edit, Q=Q, ref=ref, mask=mask)
+    return _run_stages(sch, distiller, x, tuple(x.shape), x.device, generator, edit=edit, Q=Q, ref=ref, mask=mask)
 
 
 @torch.no_grad()
 def iterative_colorization(distiller, images, x, ts, t_min=0.002, t_max=80.0, rho=7.0, steps=40, generator=None):
     """Zero-shot colourisation (reference :722-771): keep the luma coefficient of `images`, let the model fill the two chroma
     coefficients.  -> (x, the greyscale view of images), unclamped.  generator=None draws on the device."""
-    from dxmi_hip import ops
     if x.shape[1] != 3:
         raise ValueError("iterative_colorization needs 3 channels")
     _check_cm_args(distiller, x)
@@ -1055,7 +973,6 @@ def iterative_inpainting(distiller, images, x, ts, t_min=0.002, t_max=80.0, rho=
     """Zero-shot inpainting (reference :774-832): where mask = 1 keep `images`, elsewhere let the model fill.  mask: fp32
     [N, C, H, W]; without it the reference's letter mask (inpainting_mask, needs font_path and N % 7 == 0).
     -> (x, images with the masked-out part set to -1), unclamped."""
-    from dxmi_hip import ops
     ts = _check_ts(ts, steps)
     if mask is None:
         if x.shape[-1] != x.shape[-2] or x.shape[1] != 3:
@@ -1074,7 +991,6 @@ def iterative_inpainting(distiller, images, x, ts, t_min=0.002, t_max=80.0, rho=
 def iterative_superres(distiller, images, x, ts, t_min=0.002, t_max=80.0, rho=7.0, steps=40, generator=None):
     """Zero-shot 8x super-resolution (reference :835-951): keep each 8x8 patch's mean of `images`, let the model fill the other
     63 coefficients of the patch basis.  H and W must be multiples of 8.  -> (x, the patch-averaged images), unclamped."""
-    from dxmi_hip import ops
     if x.dim() != 4 or x.shape[-1] % 8 or x.shape[-2] % 8:
         raise ValueError(f"iterative_superres needs H and W multiples of 8 (got {tuple(x.shape)})")
     _check_cm_args(distiller, x)

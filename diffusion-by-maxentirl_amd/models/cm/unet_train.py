@@ -396,3 +396,22 @@ class _EDMUNetFn(torch.autograd.Function):
 
 def forward_with_grad(net, x, timesteps, y=None):
     return _EDMUNetFn.apply(net, x, timesteps, y, *ops.fast_parameters(net))
+
+
+class _Tape:
+    """What _EDMUNetFn.forward keeps for its backward, held outside autograd: it takes the place of the ctx for a caller that is an
+    autograd node of its own around the network (the loss nodes of models.cm.karras_diffusion), or that keeps no graph at all.
+    No input gradient is formed: such a caller differentiates the parameters only."""
+    needs_input_grad = (False, False, False, False)
+
+
+def train_forward(net, x, timesteps, y=None):
+    """The training forward of `net` (dropout applied in train mode; net.dropout_seeds_used lists its seeds) outside autograd
+    -> (model output, tape).  Drop the tape where no backward follows."""
+    tape = _Tape()
+    return _EDMUNetFn.forward(tape, net, x, timesteps, y), tape
+
+
+def train_backward(tape, d_out):
+    """The backward of train_forward -> the gradients of net.parameters(), in that order."""
+    return tuple(_EDMUNetFn.backward(tape, d_out)[4:])

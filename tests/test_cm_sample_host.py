@@ -136,7 +136,7 @@ def test_draw_order_with_generator(monkeypatch):
         gen = CountingGenerator()
         den = kd.KarrasDenoiserFn(diffusion(), lambda x, t: x)
         monkeypatch.setattr(sch, "device_table", lambda device: sch.table)
-        kd._run_cm(sch, den, None, (2, 3, 8, 8), torch.device("cpu"), gen)
+        kd._run_stages(sch, den, None, (2, 3, 8, 8), torch.device("cpu"), gen)
         assert gen.calls == [("randn", (2, 3, 8, 8))] + [("randn_like", (2, 3, 8, 8))] * (sch.nfe if sch.sampler == "multistep" else 0)
         assert [(m, l, r) for m, l, r, _ in stages] == [(ops.CM_FIRST, False, 0)] + \
             [(ops.CM_STEP, k == sch.nfe, k) for k in range(1, sch.nfe + 1)]

@@ -91,6 +91,61 @@ def test_nfe_and_draw_sequence(gold, case):
     assert draws == ([(kinds[sampler], i) for i in range(steps)] if sampler in kinds else [])
 
 
+LOOP_CASES = [("heun", 4, 0.0), ("heun", 4, 40.0), ("dpm", 3, 0.0), ("euler", 3, 0.0), ("ancestral", 4, 0.0)]
+
+
+@pytest.mark.parametrize("with_callback", [False, True])
+@pytest.mark.parametrize("with_generator", [True, False])
+@pytest.mark.parametrize("sampler,steps,s_churn", LOOP_CASES)
+def test_launch_loop_draws_stages_and_callbacks(monkeypatch, sampler, steps, s_churn, with_generator, with_callback):
+    """The launch loop on the host alone (the stage kernel is replaced by a recorder, so no device is needed): a generator is
+    called in the reference's order and number (randn for x_T, one randn_like per heun / dpm step even at gamma = 0, one per
+    ancestral step, the last included, none for euler); the launches are the schedule's, row by row; a launch gets noise exactly
+    when its draw is used, and without a generator all of them share one buffer; `denoised` is asked for exactly on the launches
+    that fire the callback, whose dict has the reference's keys (no sigma_hat for euler, :566-574)."""
+    from dxmi_hip import ops
+    import models.cm.karras_diffusion as kd
+    from test_cm_sample_host import CountingGenerator
+    shape = (2, 3, 8, 8)
+    sch = kd.KarrasSchedule(kd.get_sigmas_karras(steps, 0.002, 80.0, 7.0), sampler, kd.KarrasDenoiser(sigma_data=0.5), x_scale=80.0,
+                            s_churn=s_churn)
+    stages, infos = [], []
+    monkeypatch.setattr(ops, "karras_stage", lambda mode, last, tab, row, x, **k: stages.append((mode, last, row, k.get("noise"),
+                                                                                                  k.get("denoised"))))
+    monkeypatch.setattr(sch, "device_table", lambda device: sch.table)
+    gen = CountingGenerator() if with_generator else None
+    kd._run_stages(sch, kd.KarrasDenoiserFn(kd.KarrasDenoiser(sigma_data=0.5), lambda x, t: x), None, shape, torch.device("cpu"), gen,
+                   callback=infos.append if with_callback else None)
+
+    draws = {"heun": steps, "dpm": steps, "euler": 0, "ancestral": steps}[sampler]
+    if with_generator:
+        assert gen.calls == [("randn", shape)] + [("randn_like", shape)] * draws
+    assert len([l for l in sch.launches if l["draw"] is not None]) == draws
+    assert [(m, l, r) for m, l, r, _, _ in stages] == [(l["mode"], l["last"], k) for k, l in enumerate(sch.launches)]
+
+    def used(l):
+        if l["draw"] is None:
+            return False
+        kind, i = l["draw"]
+        return sch.gamma[i] > 0 if kind == "eps" else float(sch.sigma_up[i]) != 0.0
+    assert [n is not None for _, _, _, n, _ in stages] == [used(l) for l in sch.launches]
+    n_used = sum(used(l) for l in sch.launches)
+    assert n_used == {("heun", 0.0): 0, ("heun", 40.0): steps, ("dpm", 0.0): 0, ("euler", 0.0): 0,
+                      ("ancestral", 0.0): steps - 1}[sampler, s_churn]      # the last ancestral z has sigma_up = 0
+    if not with_generator:
+        assert len({id(n) for _, _, _, n, _ in stages if n is not None}) == min(n_used, 1)
+
+    fired = [l["cb"] is not None for l in sch.launches]
+    assert [d is not None for *_, d in stages] == ([False] * len(fired) if not with_callback else fired)
+    if with_callback:
+        keys = {"x", "i", "sigma", "denoised"} | (set() if sampler == "euler" else {"sigma_hat"})
+        assert [set(i) for i in infos] == [keys] * steps and [i["i"] for i in infos] == list(range(steps))
+        assert all(tuple(i["x"].shape) == shape and tuple(i["denoised"].shape) == shape for i in infos)
+        assert all(torch.equal(i["sigma"], sch.sigmas[i["i"]]) for i in infos)
+    else:
+        assert infos == []
+
+
 def test_churn_window_turns_gamma_off():
     sch = schedule("heun6_churn")
     sig = sch.sigmas[:-1]
