@@ -16,6 +16,8 @@ each other and one of them is required.  CMTrainLoop.run_loop keeps the referenc
 ends only when both lr_anneal_steps and total_training_steps are reached: --max_iters N (smoke runs) sets both to N, so the
 learning rate anneals to zero over those N steps.  --loss_norm lpips needs the VGG16 and LPIPS linear weight files:
 --lpips_vgg16 PATH --lpips_lin PATH, or DXMI_LPIPS_VGG16 / DXMI_LPIPS_LIN in the environment; without them it is refused.
+--use_graph True replays the train step from hipGraphs (CMTrainLoop(use_graph=True): needs --use_fp16 True and a loss norm other than
+lpips); DXMI_GRAPH=0 in the environment forces it off.
 """
 import argparse
 import os
@@ -23,6 +25,7 @@ import os
 import torch
 
 from dxmi_hip import dist as _dist
+from dxmi_hip import graph as _graph
 from models.cm.script_util import (add_dict_to_argparser, args_to_dict, cm_train_defaults, create_ema_and_scales_fn,
                                    create_model_and_diffusion, model_and_diffusion_defaults)
 from models.cm.train_util import CMTrainLoop
@@ -60,7 +63,7 @@ def parse_args(argv=None):
     defaults.update(synthetic_data=False, data_npz="", data_resident="auto", batch_size=16, microbatch=-1, lr=1e-4, ema_rate="0.9999",
                     log_dir="results/cm_train",
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
-                    fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="")
+                    fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False)
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
     args = ap.parse_args(argv)
@@ -126,7 +129,8 @@ def main():
                        batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr, ema_rate=args.ema_rate,
                        log_interval=args.log_interval, save_interval=args.save_interval, resume_checkpoint=args.resume_checkpoint,
                        use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth, weight_decay=args.weight_decay,
-                       lr_anneal_steps=args.lr_anneal_steps if not args.max_iters else args.max_iters, log_dir=args.log_dir)
+                       lr_anneal_steps=args.lr_anneal_steps if not args.max_iters else args.max_iters, log_dir=args.log_dir,
+                       use_graph=args.use_graph and _graph.default_enabled())
     print0(f"{args.training_mode}: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
            f"{total} steps, loss_norm {args.loss_norm}")
     loop.run_loop()

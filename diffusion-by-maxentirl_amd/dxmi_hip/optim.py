@@ -46,6 +46,17 @@ def _ptr_key(params, ms, vs):
     return tuple(t.data_ptr() for ts in (params, ms, vs) for t in ts)
 
 
+def _host_step_counters(opt):
+    """The `step` counters live on the host, where _gather() / step_sliced() create them.  torch's load_state_dict leaves a
+    loaded counter on whatever device the checkpoint was mapped to (torch.load(..., map_location="cuda")): every float(step)
+    would then be a device read — a sync per launch series eagerly, and an illegal one inside a StepGraph capture, whose host
+    producers read the counters."""
+    for st in opt.state.values():
+        step = st.get("step")
+        if torch.is_tensor(step) and step.device.type != "cpu":
+            st["step"] = step.cpu()
+
+
 def _bump_versions(params):
     """The kernels write parameters through raw pointers, which autograd's version counters do not see, while every
     packed bf16 weight cache (Model._param_key, modules._pack_t ...) is keyed on (data_ptr, _version): without the bump the
@@ -147,6 +158,7 @@ class Adam(_FusedBase, torch.optim.Adam):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        _host_step_counters(self)
         self.__dict__.pop("_dxmi_cache", None)
 
 
@@ -172,6 +184,7 @@ class RAdam(_FusedBase, torch.optim.RAdam):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        _host_step_counters(self)
         self.__dict__.pop("_dxmi_cache", None)
         self.__dict__.pop("_dxmi_slices", None)
 

@@ -206,6 +206,7 @@ class MixedPrecisionTrainer:
         found = gstat[2:3]
         opt.step_sliced_captured(st["cap"], self._slices, row[2:5], row[1:2], found)
         st["stats"][st["i"]] = torch.stack([gstat[0], pstat[0], gstat[2]])
+        st["found"] = found
         st["ovf"] += (found != 0).to(torch.int64)
         zero_grad(self.model_params)
         st["i"] += 1
@@ -217,8 +218,14 @@ class MixedPrecisionTrainer:
         st = self.__dict__["_cap_state"]
         return st["stats"][:st["i"]]
 
+    def captured_found_inf(self):
+        """Device fp32 [1] overflow flag of the last captured iteration: what a launch that must skip with the optimiser takes as
+        its found_inf (the EMA updates of a replayed training step)."""
+        return self.__dict__["_cap_state"]["found"]
+
     def finish_replay(self, opt, stats):
-        """stats: captured_stats() read back ([K][3] python floats).  The eager bookkeeping of optimize(), iteration by iteration."""
+        """stats: captured_stats() read back ([K][3] python floats).  The eager bookkeeping of optimize(), iteration by iteration.
+        -> the number of iterations that took their step."""
         ok = 0
         for gn, pn, flag in stats:
             self.log["lg_loss_scale"] = self.lg_loss_scale
@@ -230,6 +237,7 @@ class MixedPrecisionTrainer:
                 self.lg_loss_scale += self.fp16_scale_growth
                 ok += 1
         opt.advance_steps(ok)
+        return ok
 
     def _optimize_fp16_sliced(self, opt):
         """`_optimize_fp16` without its five passes over the 1.2 GB of parameters (flatten the gradients, two norm passes with a

@@ -39,6 +39,13 @@ _memo in plain dicts.  The two loss nodes run the U-Net through unet_train.train
 running its training program without an autograd ctx; _cd_loss is the consistency loss as a plain function, shared by the node
 and the no-grad call.
 
+Both loss nodes run inside a StepGraph capture (models.cm.train_util's use_graph): they read nothing back, allocate from the graph's
+pool only, and their draws (randn_like, the index randint) are torch device RNG, which is graph-aware.  What a capture freezes is
+what reaches the kernels by value: num_scales, the randint bound and the table pointer, so the loop keys its graph on them, and the
+level table must be on the device before the capture (an upload cannot be captured: refused otherwise).  Dropout seeds are host
+inputs of the graph (models/cm/unet_train.py); the target reads the online forward's device words.  loss_norm='lpips' keeps its
+refusal under capture (models/cm/lpips.py).
+
 Pairing (a deliberate restriction of the device path; the reference allows any combination): onestep and multistep run
 only for a diffusion with distillation=True (boundary-condition scalings), and the EDM samplers only with distillation=False.
 """
@@ -116,6 +123,9 @@ class _HostTable:
         if key not in self._dev:
             self._dev[key] = self.table.to(device)
         return self._dev[key]
+
+    def on_device(self, device):
+        return str(device) in self._dev
 
 
 def _memo(cache, key, cap, build):
@@ -294,8 +304,6 @@ class KarrasDenoiser:
         if x_start.requires_grad or sigmas.requires_grad or noise.requires_grad:
             raise NotImplementedError("training_losses on the HIP U-Net differentiates the network parameters only: x_start, "
                                       "noise and sigmas must not require grad")
-        if _graph.current() is not None:
-            raise NotImplementedError("training_losses: capturing the DSM step into a hipGraph is not supported")
         extra = set(model_kwargs) - {"y"}
         if extra:
             raise NotImplementedError(f"training_losses on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
@@ -394,8 +402,6 @@ class KarrasDenoiser:
         if x_start.requires_grad or noise.requires_grad:
             raise NotImplementedError("consistency_losses on the HIP U-Net differentiates the online network's parameters only: "
                                       "x_start and noise must not require grad")
-        if _graph.current() is not None:
-            raise NotImplementedError("consistency_losses: capturing the consistency step into a hipGraph is not supported")
         extra = set(model_kwargs) - {"y"}
         if extra:
             raise NotImplementedError(f"consistency_losses on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
@@ -409,7 +415,11 @@ class KarrasDenoiser:
         if noise.shape != x_start.shape or indices.numel() != x_start.shape[0] or x_start.dim() != 4:
             raise ValueError(f"consistency_losses: noise {tuple(noise.shape)} must match x_start {tuple(x_start.shape)} [N, C, H, W] "
                              f"and indices ({indices.numel()}) hold one level per sample")
-        tab = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).device_table(x_start.device)
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho)
+        if _graph.capturing() and not levels.on_device(x_start.device):
+            raise DxmiError(f"consistency_losses inside a StepGraph capture: the {int(num_scales)}-level table is not on {x_start.device} "
+                            "yet (cd_levels(...).device_table(device) before the capture: an upload cannot be captured)")
+        tab = levels.device_table(x_start.device)
         args = (self, net, target, teacher, teacher_diffusion, x_start, noise, indices, tab, y)
         if torch.is_grad_enabled():
             loss = _CDLossFn.apply(*args, *ops.fast_parameters(net))

@@ -55,12 +55,15 @@ def _ema_device_lists(targets, sources):
         t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts + sources)
 
 
-def update_ema(target_params, source_params, rate=0.99):
-    """Reference :57-67.  Lists of CUDA fp32 tensors take one dxmi_ema_update launch series; anything else the reference's loop."""
+def update_ema(target_params, source_params, rate=0.99, found_inf=None):
+    """Reference :57-67.  Lists of CUDA fp32 tensors take one dxmi_ema_update launch series; anything else the reference's loop.
+    found_inf: device fp32 flag of the launch series (non-zero leaves the targets untouched); the loop has no such gate."""
     targets, sources = list(target_params), list(source_params)
     if _ema_device_lists([targets], sources):
-        update_ema_rates([targets], sources, [rate])
+        update_ema_rates([targets], sources, [rate], found_inf=found_inf)
         return
+    if found_inf is not None:
+        raise ValueError("update_ema: found_inf needs lists of contiguous CUDA fp32 tensors (the dxmi_ema_update launch series)")
     for targ, src in zip(targets, sources):
         targ.detach().mul_(rate).add_(src, alpha=1 - rate)
 

@@ -20,15 +20,30 @@ rate comes from ema_scale_fn(global_step) (one dxmi_ema_update launch series on 
 global_step, and target_model%06d.pt (plus, with the first save, teacher_model%06d.pt) is written next to TrainLoop's files and
 read back on resume (a checkpoint later than the first finds the teacher under the first save's name in the same directory;
 where there is none, the teacher the caller passed is kept).  An fp16 overflow step skips the target EMA on the host, from the
-flag optimize() has already read back, so its launch passes no found_inf as the other EMA launches can.  progdist is not
-implemented.
+flag optimize() has already read back, so its eager launch passes no found_inf.  progdist is not implemented.
+
+use_graph=True (both loops; off by default) replays a whole step from hipGraphs (dxmi_hip/graph.py StepGraph): the first run_step
+runs eagerly (weight packs, workspaces, optimiser state), the second is captured, later ones are host producers + one upload + the
+graph launches.  Captured is everything run_step does on the device: zero_grad, every microbatch of forward_backward (sigma, index
+and noise draws are torch device RNG), the gradient exchange (a cut: the collectives run eagerly between two graph launches), the
+norm + RAdam launches (loss scale, RAdam scalars and lr are host inputs), every EMA launch series and, for CMTrainLoop, the target's
+EMA and the refresh of its packed weights.  The batch and cond["y"] are the graph's tensor arguments.  Nothing on the host decides
+per step: both EMA series take the device overflow flag of the iteration as found_inf; after the launches ONE read-back (norms, flag,
+the logged terms of every microbatch) feeds MixedPrecisionTrainer.finish_replay, and the same flag advances or holds the counters.
+What a capture freezes by value is the pair ema_scale_fn(global_step) = (target EMA rate, num_scales): the graph is keyed on it
+(_KeyedStepGraph), a changed pair drops the graph (and its pool) and captures a new one at once, so only one graph is alive.  The
+logged terms are summed in fp32 on the host in the order the eager loop sums them on the device, so the rows are the same.
+Refused at construction: use_fp16 off or masters that are not device-aliased (the trainer's captured path), loss_norm="lpips", a
+schedule_sampler that draws on the host; a CPU model runs eagerly.
 """
 import json
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
+from dxmi_hip import graph as _graph
 from dxmi_hip.dist import broadcast_parameters, is_distributed
 from dxmi_hip.optim import RAdam
 
@@ -46,12 +61,52 @@ def _world():
     return dist.get_world_size() if is_distributed() else 1
 
 
+class _KeyedStepGraph:
+    """At most ONE StepGraph, the one of the current key: graph(key) is built by build(key) on first use and whenever the key
+    differs from the one held; the graph held before is dropped first (drop(): on_drop(), then its references, so that its pool is
+    free before the next capture).  captures / replays count over every graph this object has held."""
+
+    def __init__(self, build, on_drop=None):
+        self.build, self.on_drop = build, on_drop
+        self.key, self.graph = None, None
+        self.captures = self.replays = self.builds = 0
+
+    def drop(self):
+        if self.graph is not None and self.on_drop is not None:
+            self.on_drop()
+        self.key, self.graph = None, None
+
+    def __call__(self, key, *args):
+        if self.graph is None or key != self.key:
+            self.drop()
+            self.graph, self.key = self.build(key), key
+            self.builds += 1
+        g = self.graph
+        c0, r0 = g.captures, g.replays
+        try:
+            return g(*args)
+        finally:
+            self.captures += g.captures - c0
+            self.replays += g.replays - r0
+
+
 class TrainLoop:
     def __init__(self, *, model, diffusion, data, batch_size, microbatch, lr, ema_rate, log_interval, save_interval,
                  resume_checkpoint, use_fp16=False, fp16_scale_growth=1e-3, schedule_sampler=None, weight_decay=0.0,
-                 lr_anneal_steps=0, log_dir=None):
+                 lr_anneal_steps=0, log_dir=None, use_graph=False):
         if schedule_sampler is None:
             raise ValueError("TrainLoop: schedule_sampler is required (e.g. models.cm.resample.LogNormalSampler())")
+        if use_graph:
+            if not use_fp16:
+                raise NotImplementedError("use_graph=True needs use_fp16=True: a captured step keeps the loss scale, the overflow flag and "
+                                          "the RAdam scalars on the device, which only MixedPrecisionTrainer's fp16 path (flat masters "
+                                          "aliased by the model parameters) does")
+            if getattr(diffusion, "loss_norm", None) == "lpips":
+                raise NotImplementedError("use_graph=True with loss_norm='lpips': LPIPS refuses a StepGraph capture (models/cm/lpips.py); "
+                                          "train eagerly, or with l1 / l2 / l2-32")
+            if getattr(schedule_sampler, "generator", None) is not None:
+                raise NotImplementedError("use_graph=True needs a schedule_sampler that draws on the device (generator=None): with a "
+                                          "generator the sampler draws on the host, which cannot be captured")
         self.model, self.diffusion, self.data = model, diffusion, data
         self.batch_size = batch_size
         self.microbatch = microbatch if microbatch > 0 else batch_size
@@ -80,6 +135,13 @@ class TrainLoop:
         self.ddp_model = self.model
         self.step = self.resume_step
         self._log_sums, self._log_count, self.logged = {}, 0, []
+        self.use_graph = bool(use_graph) and self.device.type == "cuda"      # a CPU model runs eagerly
+        if self.use_graph and not self.mp_trainer._aliased:
+            raise NotImplementedError("use_graph=True needs masters that the model parameters alias on the device (contiguous fp32 "
+                                      "CUDA parameters): MixedPrecisionTrainer captures no other layout")
+        self._graph = _KeyedStepGraph(self._build_graph, self._on_graph_drop) if self.use_graph else None
+        self._graph_warm = False
+        self._cap_log = self._cap_keys = None
 
     # ------------------------------------------------------------------ checkpoints
     def _load_and_sync_parameters(self):
@@ -136,14 +198,27 @@ class TrainLoop:
             self.save()
 
     def run_step(self, batch, cond):
-        self.forward_backward(batch, cond)
-        took_step = self.mp_trainer.optimize(self.opt)
+        took_step = self._step_replayed(batch, cond) if self.use_graph and self._graph_warm else self._step_on_device(batch, cond)
+        self._graph_warm = True
         if took_step:
-            self.step += 1
-            self._update_ema()
+            self._count_step()
         self._anneal_lr()
         self.log_step()
         return took_step
+
+    def _step_on_device(self, batch, cond):
+        """The device work of an eager step -> took_step (read back by optimize()); the EMAs move only on a step that was taken."""
+        self.forward_backward(batch, cond)
+        took_step = self.mp_trainer.optimize(self.opt)
+        if took_step:
+            self._update_emas()
+        return took_step
+
+    def _count_step(self):
+        self.step += 1
+
+    def _update_emas(self, found_inf=None):
+        self._update_ema(found_inf)
 
     def forward_backward(self, batch, cond):
         self.mp_trainer.zero_grad()
@@ -156,13 +231,67 @@ class TrainLoop:
             self._log_loss_dict({k: v * weights for k, v in losses.items()})
             self.mp_trainer.backward(loss)
 
-    def _update_ema(self):
+    def _update_ema(self, found_inf=None):
+        """found_inf: device fp32 flag (a captured step: the launches skip on it, as the optimiser's do)."""
         masters = self.mp_trainer.master_params
         if all(p.is_cuda for p in masters):
-            update_ema_rates(self.ema_params, masters, self.ema_rate)
+            update_ema_rates(self.ema_params, masters, self.ema_rate, found_inf=found_inf)
             return
         for rate, params in zip(self.ema_rate, self.ema_params):
-            update_ema(params, masters, rate=rate)
+            update_ema(params, masters, rate=rate, found_inf=found_inf)
+
+    # ------------------------------------------------------------------ hipGraph replay of the step (use_graph=True)
+    def _graph_key(self):
+        """What the captured step freezes by value, beyond the shapes of its arguments."""
+        return ()
+
+    def _graph_modules(self):
+        return _graph.pack_modules(self.model)
+
+    def _before_capture(self, key):
+        """Host work a capture cannot hold (uploads), for the graph of `key`."""
+
+    def _build_graph(self, key):
+        self._before_capture(key)
+        return _graph.StepGraph(self._captured_step, self.device, warmup=0, modules=self._graph_modules(),
+                                name=f"{type(self).__name__}.run_step{key}")
+
+    def _on_graph_drop(self):
+        self.mp_trainer.__dict__.pop("_cap_state", None)      # tensors of the dropped graph's pool
+        self._cap_log = self._cap_keys = None
+
+    def _captured_step(self, batch, *y):
+        """The body of the StepGraph: the device work of run_step, with the device overflow flag where the eager step branches on
+        the host -> fp32 [3 + terms]: (scaled gradient norm, parameter norm, overflow flag), then every logged term of every
+        microbatch in the order _log_loss_dict met them."""
+        self.mp_trainer.begin_captured(self.opt)
+        self._cap_log = log = []
+        try:
+            self.forward_backward(batch, {"y": y[0]} if y else {})
+        finally:
+            self._cap_log = None                 # _log_loss_dict sums on the device again (a capture that failed included)
+        self.mp_trainer.optimize(self.opt)
+        self._update_emas(self.mp_trainer.captured_found_inf())
+        self._cap_keys = [k for k, _ in log]
+        return torch.cat([self.mp_trainer.captured_stats().reshape(-1)] + [m.reshape(1) for _, m in log])
+
+    def _step_replayed(self, batch, cond):
+        """run_step's device work from the graph of the current key (captured by this call if there is none) -> took_step."""
+        extra = set(cond) - {"y"}
+        if extra:
+            raise NotImplementedError(f"use_graph=True: cond entries {sorted(extra)} are not inputs of the captured step (only 'y' is)")
+        if any(torch.is_tensor(v) for v in self._log_sums.values()):      # sums an eager step left on the device: to the host
+            keys = list(self._log_sums)
+            vals = torch.stack([torch.as_tensor(self._log_sums[k], dtype=torch.float32, device=self.device) for k in keys]).tolist()
+            self._log_sums = {k: np.float32(v) for k, v in zip(keys, vals)}
+        args = [batch.to(self.device)] + ([cond["y"].to(self.device)] if "y" in cond else [])
+        out = self._graph(self._graph_key(), *args).tolist()               # the step's ONE read-back
+        took_step = self.mp_trainer.finish_replay(self.opt, [out[:3]]) == 1
+        with np.errstate(over="ignore", invalid="ignore"):
+            for k, v in zip(self._cap_keys, out[3:]):                        # fp32 sums in the eager loop's order
+                self._log_sums[k] = self._log_sums[k] + np.float32(v) if k in self._log_sums else np.float32(v)
+        self._log_count += len(self._cap_keys) // max(1, len(set(self._cap_keys)))
+        return took_step
 
     def _anneal_lr(self):
         if not self.lr_anneal_steps:
@@ -175,6 +304,9 @@ class TrainLoop:
     # ------------------------------------------------------------------ logging
     def _log_loss_dict(self, losses):
         """Device sums of every term's batch mean (no host sync); dumpkvs() reads them."""
+        if self._cap_log is not None:        # a step being captured: the means are outputs of the graph (_step_replayed sums them)
+            self._cap_log += [(k, v.detach().float().mean()) for k, v in losses.items()]
+            return
         for k, v in losses.items():
             m = v.detach().float().mean()
             self._log_sums[k] = self._log_sums[k] + m if k in self._log_sums else m
@@ -189,7 +321,8 @@ class TrainLoop:
         row = dict(getattr(self, "_kv", {}))
         if self._log_count:
             keys = sorted(self._log_sums)
-            vals = torch.stack([self._log_sums[k] for k in keys]).tolist()
+            sums = [self._log_sums[k] for k in keys]           # device tensors (eager steps) or fp32 host sums (replayed steps)
+            vals = torch.stack(sums).tolist() if all(torch.is_tensor(v) for v in sums) else [float(v) for v in sums]
             row.update({k: v / self._log_count for k, v in zip(keys, vals)})
         row.update({k: v for k, v in self.mp_trainer.log.items()})
         self._log_sums, self._log_count = {}, 0
@@ -203,6 +336,7 @@ class TrainLoop:
 
 class CMTrainLoop(TrainLoop):
     def __init__(self, *, target_model, teacher_model, teacher_diffusion, training_mode, ema_scale_fn, total_training_steps, **kwargs):
+        """kwargs: TrainLoop's, use_graph among them."""
         if training_mode == "progdist":
             raise NotImplementedError("CMTrainLoop: progressive distillation (progdist) is not implemented")
         if training_mode not in ("consistency_distillation", "consistency_training"):
@@ -269,22 +403,39 @@ class CMTrainLoop(TrainLoop):
         if not saved:
             self.save()
 
-    def run_step(self, batch, cond):
-        self.forward_backward(batch, cond)
-        took_step = self.mp_trainer.optimize(self.opt)
-        if took_step:           # an fp16 overflow step moves neither EMA: optimize() has read the flag back already
-            self._update_ema()
-            self._update_target_ema()
-            self.step += 1
-            self.global_step += 1
-        self._anneal_lr()
-        self.log_step()
-        return took_step
+    def _count_step(self):      # after the EMA updates of the step: _update_target_ema reads global_step before it moves
+        self.step += 1
+        self.global_step += 1
 
-    def _update_target_ema(self):
+    def _update_emas(self, found_inf=None):
+        """Eagerly only on a step the optimiser took (an fp16 overflow step moves neither EMA: optimize() has read the flag back
+        already); in a captured step always, with the device flag."""
+        self._update_ema(found_inf)
+        self._update_target_ema(found_inf)
+
+    def _graph_key(self):
+        return self.ema_scale_fn(self.global_step)
+
+    def _graph_modules(self):
+        nets = [self.model, self.target_model] + ([self.teacher_model] if self.teacher_model is not None else [])
+        return [m for net in nets for m in _graph.pack_modules(net)]
+
+    def _before_capture(self, key):
+        d = self.diffusion
+        if all(hasattr(d, a) for a in ("sigma_min", "sigma_max", "rho")):       # the level table of this key: uploaded, not captured
+            from .karras_diffusion import cd_levels
+            # held for as long as the graph lives: the graph has the table's address, the cache of level sets may be emptied
+            self._cap_table = cd_levels(key[1], d.sigma_min, d.sigma_max, d.rho).device_table(self.device)
+
+    def _on_graph_drop(self):
+        super()._on_graph_drop()
+        self._cap_table = None
+
+    def _update_target_ema(self, found_inf=None):
         target_ema, _ = self.ema_scale_fn(self.global_step)
         with torch.no_grad():
-            update_ema(self.target_model_master_params, [p.detach() for p in self.mp_trainer.master_params], rate=target_ema)
+            update_ema(self.target_model_master_params, [p.detach() for p in self.mp_trainer.master_params], rate=target_ema,
+                       found_inf=found_inf)
             if self.target_model_param_groups_and_shapes is not None:
                 master_params_to_model_params(self.target_model_param_groups_and_shapes, self.target_model_master_params)
             else:

@@ -14,8 +14,9 @@ package) plus a tape of saved NHWC bf16 activations; backward() walks the tape i
   time_embed, label_emb, emb_layers = tiny dense layers, re-evaluated and differentiated with torch fp32 matmuls.
 Dropout (ResBlock out_layers: norm, SiLU, Dropout, conv; models/cm/unet.py) runs in train mode as the counter-hash kernel
 dxmi_dropout_bf16 on the conv2 input: one seed per ResBlock per forward, kept on the tape with p, and the backward applies the same
-(seed, p) to the gradient (no mask is stored).  With dropout 0, or in eval mode, nothing of it runs.  Parameter gradients come back in
-net.parameters() order.
+(seed, p) to the gradient (no mask is stored).  With dropout 0, or in eval mode, nothing of it runs.  Inside a StepGraph capture
+(dxmi_hip/graph.py) every site's seed is a host input of the graph, so a replayed step draws the seeds an eager step would draw.
+Parameter gradients come back in net.parameters() order.
 """
 import math
 import os
@@ -24,6 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from dxmi_hip import graph as _graph
 from dxmi_hip import ops
 
 
@@ -113,10 +115,7 @@ class _EDMUNetFn(torch.autograd.Function):
     def forward(ctx, net, x, timesteps, y, *params):
         from .unet import AttentionBlock, Downsample, ResBlock, Upsample
         p_drop = float(net.dropout) if net.training else 0.0
-        if p_drop > 0:
-            from dxmi_hip import graph as _graph
-            if _graph.current() is not None:
-                raise NotImplementedError("UNetModel HIP training path: dropout > 0 inside a captured step is not implemented")
+        cap = _graph.current() if p_drop > 0 else None
         net.dropout_seeds_used = []
         pk = net.packed()
         x = x.contiguous().float()
@@ -159,7 +158,12 @@ class _EDMUNetFn(torch.autograd.Function):
                 a2, s2 = gn_fwd(gn2, h, sh, silu=True)
             drop = None
             if p_drop > 0:       # nn.Dropout of out_layers: the backward regenerates the mask from (seed, p)
-                drop = (_next_dropout_seed(net), p_drop)
+                if cap is not None and net.__dict__.get("_dropout_seed_feed") is None:
+                    # captured step: the seed is a host input of the graph (a device word, dxmi_dropout_bf16_dev), declared in site
+                    # order; its producer advances the counter an eager forward advances
+                    drop = (cap.host_input(torch.int32, 1, lambda: [_next_dropout_seed(net)]), p_drop)
+                else:       # eager: a python int; seeds handed over by the caller are taken as they are (device words under capture)
+                    drop = (_next_dropout_seed(net), p_drop)
                 net.dropout_seeds_used.append(drop[0])
                 a2 = ops.dropout(a2, p_drop, drop[0])
             if (id(b), "skip") in pk:
