@@ -161,6 +161,8 @@ SIGNATURES = {
     "dxmi_cd_lpips_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "dxmi_image_batch": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "dxmi_randn_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "dxmi_randint_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
 }
 
 _lib = None

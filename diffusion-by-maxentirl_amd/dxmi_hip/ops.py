@@ -1719,6 +1719,47 @@ def image_batch(store, idx, flip, norm, out=None):
     return out
 
 
+def _indexed_operands(what, sample_index, shape_tail, dtype, out):
+    """The checks of the indexed draws: sample_index a contiguous int64 [N >= 1] device tensor, shape_tail non-negative sizes with
+    at least one element per row, out (if given) a contiguous `dtype` [N, *shape_tail] on the same device.  -> (N, per_sample, out)."""
+    _need_cuda(sample_index, out)
+    if sample_index.dtype != torch.int64 or sample_index.dim() != 1 or not sample_index.is_contiguous() or sample_index.numel() < 1:
+        raise _lib.DxmiError(f"{what}: sample_index must be a non-empty contiguous int64 [N] device tensor")
+    N, tail = sample_index.numel(), tuple(int(s) for s in shape_tail)
+    per = 1
+    for s in tail:
+        per *= s
+    if per < 1 or any(s < 0 for s in tail):
+        raise _lib.DxmiError(f"{what}: every row needs at least one element, got the shape tail {tail}")
+    if out is None:
+        out = torch.empty((N,) + tail, dtype=dtype, device=sample_index.device)
+    elif not (out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == (N,) + tail and out.device == sample_index.device):
+        raise _lib.DxmiError(f"{what}: out must be a contiguous {dtype} {(N,) + tail} on the device of sample_index")
+    return N, per, out
+
+
+_U64 = (1 << 64) - 1
+
+
+def randn_indexed(sample_index, shape_tail, seed, draw, out=None):
+    """Standard normals fp32 [N, *shape_tail] whose row n is a function of (seed, sample_index[n], draw) alone: the same row whatever
+    batch it is drawn in (dxmi_randn_indexed; Philox-4x32-10 + Box-Muller, include/dxmi_hip.h).  sample_index: int64 [N] on the
+    device; seed: any integer, taken modulo 2^64; draw: the draw number, modulo 2^32."""
+    N, per, out = _indexed_operands("dxmi_randn_indexed", sample_index, shape_tail, torch.float32, out)
+    check(load().dxmi_randn_indexed(_ptr(out), _ptr(sample_index), N, per, int(seed) & _U64, int(draw) & 0xFFFFFFFF, _stream()),
+          "dxmi_randn_indexed")
+    return out
+
+
+def randint_indexed(sample_index, shape_tail, low, high, seed, draw, out=None):
+    """Integers in [low, high), int64 [N, *shape_tail], from the words of the same generator (dxmi_randint_indexed): row n is a
+    function of (seed, sample_index[n], draw) alone.  1 <= high - low <= 2^31."""
+    N, per, out = _indexed_operands("dxmi_randint_indexed", sample_index, shape_tail, torch.int64, out)
+    check(load().dxmi_randint_indexed(_ptr(out), _ptr(sample_index), N, per, int(low), int(high), int(seed) & _U64,
+                                      int(draw) & 0xFFFFFFFF, _stream()), "dxmi_randint_indexed")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)
 class PackedGConv:
     """BatchNorm-folded bf16 weights [ceil32(Cout)][KH * KW][ceil16(Cin)] + fp32 bias of one BasicConv2d (dxmi_gconv_pack)."""

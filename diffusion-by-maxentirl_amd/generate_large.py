@@ -19,6 +19,12 @@ otherwise `sampler.pth` from --log_dir without its `log_betas` entry.  Class-con
 `--cm_sampler {onestep,multistep}` samples a consistency-distilled model the same way (karras_sample's onestep /
 multistep branch, reference :644-683): the diffusion is built with distillation=True; `--ts 0,22,39` (required for
 multistep), `--cm_steps` (40); `--pretrained [PATH]` as above.  It excludes --karras_sampler and --guidance_scale.
+
+`--generator {dummy,determ,determ-indiv}` (with --karras_sampler / --cm_sampler; reference models/cm/random_util.py): `dummy`, the
+default, draws on the device as before.  `determ` / `determ-indiv` make image i of the run see the same noise and label whatever
+--batchsize and the number of ranks are (models.cm.random_util): image i is row k of batch b on rank r with
+i = b * batchsize * world + r + k * world, and samples_N.npz is written in that order.  `--seed` is the generator's seed (default:
+the config's training.seed).
 """
 import argparse
 import os
@@ -69,6 +75,10 @@ def build_parser():
                     help="sample a consistency-distilled model (distillation=True) with this sampler")
     ap.add_argument("--ts", type=str, default=None, help="multistep: comma-separated step indices, e.g. 0,22,39")
     ap.add_argument("--cm_steps", type=int, default=None, help="consistency sampler steps: the ts index range (default 40)")
+    ap.add_argument("--generator", type=str, default="dummy", choices=("dummy", "determ", "determ-indiv"),
+                    help="with --karras_sampler / --cm_sampler: determ / determ-indiv give image i of the run the same noise "
+                         "whatever the batch size and the number of ranks (models/cm/random_util.py)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of --generator determ / determ-indiv (default: the config's training.seed)")
     return ap
 
 
@@ -77,6 +87,10 @@ def parse_args(argv=None):
     consistency flags: they need --cm_sampler, which excludes --karras_sampler and --guidance_scale."""
     ap = build_parser()
     args, unknown = ap.parse_known_args(argv)
+    if args.generator == "dummy" and args.seed is not None:
+        ap.error("--seed only applies with --generator determ / determ-indiv")
+    if args.generator != "dummy" and args.cm_sampler is None and args.karras_sampler is None:
+        ap.error("--generator determ / determ-indiv only applies with --karras_sampler or --cm_sampler")
     if args.cm_sampler is not None:
         return parse_cm_args(ap, args), unknown
     given = [f"--{k}" for k in CM_FLAGS if getattr(args, k) is not None]
@@ -220,13 +234,22 @@ def main():
     finish(args, l_sample, device, local_rank, world)
 
 
+def index_order(gathered, batchsize):
+    """The ranks' samples (each [n_batches * batchsize, ...], batch after batch) in the order of the deterministic generators'
+    global index b * batchsize * world + r + k * world: batch, then row, then rank."""
+    s = torch.stack(gathered)
+    world, tail = s.shape[0], tuple(s.shape[2:])
+    s = s.reshape((world, -1, batchsize) + tail)
+    return s.permute(1, 2, 0, *range(3, s.dim())).reshape((-1,) + tail)
+
+
 def finish(args, l_sample, device, local_rank, world):
     """All-gather of the uint8 batches, samples_N.npz on rank 0 and FID."""
     samples = torch.cat(l_sample)
     if world > 1:
         gathered = [torch.zeros_like(samples) for _ in range(world)]
         torch.distributed.all_gather(gathered, samples)
-        samples = torch.cat(gathered)
+        samples = torch.cat(gathered) if args.generator == "dummy" else index_order(gathered, args.batchsize)
     if local_rank == 0:
         np.savez(os.path.join(args.log_dir, f"samples_{len(samples)}.npz"), samples.permute(0, 2, 3, 1).cpu().numpy())
     if args.fid_extractor is None or args.fid_stats is None:
@@ -275,16 +298,24 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         sampler, steps, nfe = args.karras_sampler, args.karras_steps, karras_nfe(args.karras_sampler, args.karras_steps)
         extra = dict(rho=args.rho, s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax, s_noise=args.s_noise)
     n_batches = int(args.n_sample / args.batchsize / world)
+    generator = None                            # dummy: every draw on the device, hipGraph replay allowed
+    if args.generator != "dummy":
+        from models.cm.random_util import get_generator
+        generator = get_generator(args.generator, n_batches * args.batchsize * world,
+                                  cfg.training.seed if args.seed is None else args.seed)
     l_sample, i_img = [], 0
     writer = ImageWriter()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(n_batches):
+    for i_batch in range(n_batches):
         kw = {}
+        if generator is not None:               # the images all ranks have finished; the batch's draws count from 0 again
+            generator.set_done_samples(i_batch * args.batchsize * world)
         if unet.num_classes is not None:        # one uniform label per image, as OpenAIDiffusion._sample draws them
-            kw["y"] = torch.randint(0, unet.num_classes, (args.batchsize,), device=device)
+            kw["y"] = (torch.randint(0, unet.num_classes, (args.batchsize,), device=device) if generator is None else
+                       generator.randint(0, unet.num_classes, (args.batchsize,), device=device))
         sample = karras_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
-                               sigma_max=diffusion.sigma_max, sampler=sampler, use_graph=use_graph, **extra)
+                               sigma_max=diffusion.sigma_max, sampler=sampler, use_graph=use_graph, generator=generator, **extra)
         if args.skip_fid:
             writer.submit(sample, [os.path.join(output_path, f"{local_rank}_{i_img + k}.png") for k in range(len(sample))])
             i_img += len(sample)

@@ -876,6 +876,32 @@ int dxmi_cd_lpips_bwd(const float* g_loss, const float* d_x01, const int64_t* in
 int dxmi_image_batch(const void* store, int64_t n_rows, const int64_t* idx, const uint8_t* flip, float* out, int32_t B, int32_t H,
                      int32_t W, int32_t C, int32_t norm, void* stream);
 
+/* Batch- and rank-invariant sampling noise (csrc/randn_indexed.hip): the device form of the reference's
+ * DeterministicGenerator / DeterministicIndividualGenerator (models/cm/random_util.py:28-182), whose one property is that image i of
+ * a run sees the same noise whatever the batch size and however many ranks share the run.  A counter-based generator: every value is
+ * a pure function of (seed, sample_index[n], draw, element), and one launch produces a draw for the whole batch.  The stream is this
+ * library's own; it matches neither torch's CPU nor torch's device generator.
+ * out: [N, per_sample] contiguous, 16-byte aligned.  sample_index: int64 [N] on the device, the global index of row n (any int64; its
+ * 64 bits go into the counter, so indices above 2^32 stay distinct).  A row depends on its own index only: not on n, N or the launch.
+ * Generator: Philox-4x32-10 (Salmon et al., SC'11; Random123) with the published constants (multipliers 0xD2511F53, 0xCD9E8D57, key
+ *   increments 0x9E3779B9, 0xBB67AE85).  key = (seed & 0xffffffff, seed >> 32); counter = (block, draw, index & 0xffffffff,
+ *   index >> 32) with block = e / 4 for element e of the row: the four output words x0..x3 of one call are elements 4 block .. 4 block + 3.
+ * dxmi_randn_indexed: uniforms u(x) = ((x >> 9) + 0.5f) * 2^-23, exact in fp32 and inside [2^-24, 1 - 2^-24] (23 bits: with 24 the
+ *   half would not fit the significand for x >> 8 >= 2^23, and the sum would round to 1.0 at the top).  Box-Muller on the pairs
+ *   (x0, x1) and (x2, x3): r = sqrtf(-2.f * logf(u(x_a))), t = 6.2831855f * u(x_b), z_a = r * cosf(t), z_b = r * sinf(t); so
+ *   |z| <= sqrt(48 ln 2) = 5.77.  fp32 throughout, one rounding per operation (no fused multiply-add); logf, sinf and cosf are the device
+ *   library's (ROCm OCML, ~1 ulp), sqrtf is correctly rounded: the bits of a normal depend on them, so they may change with the
+ *   ROCm release, while the raw words never do.
+ * dxmi_randint_indexed: out int64, element e = low + (x_(e % 4) mod (high - low)) from the same words, one 32-bit word per element;
+ *   1 <= high - low <= 2^31 (wider ranges: DXMI_EINVAL).  The usual modulo bias, below (high - low) / 2^32.  low = 0, high = 2^31
+ *   exposes the low 31 bits of every word.
+ * N in [1, 65535], per_sample in [1, 2^31 - 1].  f32x4 stores per lane where the rows are 16-byte aligned (per_sample % 4 == 0), 4-byte
+ * aligned vector stores otherwise, the last per_sample % 4 elements one by one.  No workspace, no LDS, no atomics. */
+int dxmi_randn_indexed(float* out, const int64_t* sample_index, int32_t N, int64_t per_sample, uint64_t seed, uint32_t draw,
+                       void* stream);
+int dxmi_randint_indexed(int64_t* out, const int64_t* sample_index, int32_t N, int64_t per_sample, int64_t low, int64_t high,
+                         uint64_t seed, uint32_t draw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
