@@ -8,7 +8,9 @@ import torch
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-# odd sizes on purpose: scalar tail, unaligned views, > one chunk, > DXMI_MT_MAX tensors
+# odd sizes on purpose: scalar tail, > one chunk, > DXMI_MT_MAX tensors.  _params allocates every tensor separately, so every base is
+# 16-byte aligned here: misaligned views (full chunks on the dword loops), per-tensor scalars across launches and the norm's partial
+# offsets are in test_hip_train_tail_edges.py
 SHAPES = [(3,), (10,), (128, 3, 3, 3), (256, 128, 3, 3), (4097,), (1, 1), (513, 7)] + [(17 + i,) for i in range(70)]
 
 
