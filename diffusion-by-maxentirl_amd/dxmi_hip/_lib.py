@@ -121,6 +121,9 @@ SIGNATURES = {
     "dxmi_edm_dsm_prep": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p]),
     "dxmi_edm_dsm_loss_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_edm_dsm_loss_bwd": (c_int, [c_void_p] * 7 + [c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
+    "dxmi_ddpm_prep": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "dxmi_ddpm_loss_fwd": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p]),
+    "dxmi_ddpm_loss_bwd": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
     "dxmi_ema_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_void_p, c_void_p]),
     "dxmi_cd_prep": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 4 + [c_int, c_int, c_float, c_float, c_void_p]),
     "dxmi_cd_solver": (c_int, [c_int] + [c_void_p] * 7 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_int, c_float, c_void_p]),

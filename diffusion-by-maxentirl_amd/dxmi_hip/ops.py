@@ -1012,6 +1012,63 @@ def edm_dsm_loss_bwd(g_mse, g_xs, model_out, x_start, noise, sigma, weight_sched
     return d
 
 
+def _ddpm_operands(name, ref, same=(), per_sample=()):
+    """fp32 contiguous 16-byte aligned device tensors of ref's shape [N, ...]; `per_sample` hold N elements."""
+    ts = (ref,) + tuple(same) + tuple(per_sample)
+    _need_cuda(*ts)
+    for t in (ref,) + tuple(same):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+            raise _lib.DxmiError(f"{name}: fp32 contiguous 16-byte aligned device tensors")
+    if ref.dim() < 2 or ref.numel() == 0:
+        raise _lib.DxmiError(f"{name}: a non-empty batch [N, ...] is needed, got {tuple(ref.shape)}")
+    N = ref.shape[0]
+    if (ref.numel() // N) % 4:
+        raise _lib.DxmiError(f"{name}: {ref.numel() // N} elements per sample are not a multiple of 4")
+    for t in same:
+        if t is not None and t.shape != ref.shape:
+            raise _lib.DxmiError(f"{name}: operand of shape {tuple(t.shape)} where {tuple(ref.shape)} is needed")
+    for t in per_sample:
+        if not (t.is_contiguous() and t.numel() == N):
+            raise _lib.DxmiError(f"{name}: per-sample operand of {t.numel()} elements (contiguous) for a batch of {N}")
+    return N, ref.numel() // N
+
+
+def ddpm_prep(x_start, noise, t_idx, table, out=None):
+    """-> (x_t = table[0][t] x_start + table[1][t] noise, float(t)): the DDPM forward process q(x_t | x_0) and the network's time
+    input (dxmi_ddpm_prep).  table: fp32 [2, T] on the device; t_idx: int64 [N] on the device."""
+    name = "dxmi_ddpm_prep"
+    _need_cuda(table)
+    N, chw = _ddpm_operands(name, x_start, same=(noise, out), per_sample=(t_idx,))
+    if t_idx.dtype != torch.int64:
+        raise _lib.DxmiError(f"{name}: t_idx must be int64, got {t_idx.dtype}")
+    if not (table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[0] == 2 and table.shape[1] >= 1):
+        raise _lib.DxmiError(f"{name}: table must be a contiguous fp32 [2, T], got {table.dtype} {tuple(table.shape)}")
+    x_t = torch.empty_like(x_start) if out is None else out
+    t = torch.empty(N, dtype=torch.float32, device=x_start.device)
+    check(load().dxmi_ddpm_prep(_ptr(x_start), _ptr(noise), _ptr(t_idx), _ptr(table), int(table.shape[1]), _ptr(x_t), _ptr(t), N, chw,
+                                _stream()), name)
+    return x_t, t
+
+
+def ddpm_loss_fwd(eps_pred, noise):
+    """-> per-sample mean_flat((eps_pred - noise)^2) of the noise-prediction loss (dxmi_ddpm_loss_fwd)."""
+    N, chw = _ddpm_operands("dxmi_ddpm_loss_fwd", eps_pred, same=(noise,))
+    loss = torch.empty(N, dtype=torch.float32, device=eps_pred.device)
+    check(load().dxmi_ddpm_loss_fwd(_ptr(eps_pred), _ptr(noise), _ptr(loss), N, chw, _stream()), "dxmi_ddpm_loss_fwd")
+    return loss
+
+
+def ddpm_loss_bwd(g_loss, eps_pred, noise, out=None):
+    """-> d(eps_pred) of the noise-prediction loss for the device upstream gradient g_loss [N] (dxmi_ddpm_loss_bwd)."""
+    name = "dxmi_ddpm_loss_bwd"
+    N, chw = _ddpm_operands(name, eps_pred, same=(noise, out), per_sample=(g_loss,))
+    if g_loss.dtype != torch.float32:
+        raise _lib.DxmiError(f"{name}: g_loss must be fp32, got {g_loss.dtype}")
+    d = torch.empty_like(eps_pred) if out is None else out
+    check(load().dxmi_ddpm_loss_bwd(_ptr(g_loss), _ptr(eps_pred), _ptr(noise), _ptr(d), N, chw, _stream()), name)
+    return d
+
+
 # dxmi_cd_solver modes and dxmi_cd_loss_* norms (include/dxmi_hip.h), by the reference's names (karras_diffusion.py:206-220)
 CD_EULER_X0, CD_HEUN_PRED, CD_HEUN_CORR = range(3)
 CD_LOSS_NORMS = {"l1": 0, "l2": 1, "l2-32": 2}

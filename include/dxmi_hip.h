@@ -579,6 +579,21 @@ int dxmi_edm_dsm_loss_bwd(const float* g_mse, const float* g_xs, const float* mo
                           const float* sigma, float* d_model_out, int32_t N, int32_t CHW, float sigma_data, float sigma_min,
                           int32_t distillation, int32_t weight_schedule, void* stream);
 
+/* Noise-prediction training of the DDPM U-Net (Ho et al. 2020, "Denoising Diffusion Probabilistic Models"), fp32 NCHW [N, CHW]
+ * tensors (CHW a multiple of 4, 16-byte aligned).  table: fp32 [2][T] on the DEVICE, row 0 = sqrt(alpha_bar), row 1 =
+ * sqrt(1 - alpha_bar) of calc_diffusion_hyperparams (models/DxMI/var_sampler.py); t_idx: int64 [N] on the DEVICE.
+ * dxmi_ddpm_prep (eq. 4, q(x_t | x_0)): x_t[n] = table[0][t] x_start[n] + table[1][t] noise[n] (two products, one sum),
+ *   t_out[n] = (float)t — the network's input.  An index outside [0, T) gives NaN coefficients for that sample; nothing outside
+ *   the table is read.
+ * dxmi_ddpm_loss_fwd (eq. 14, L_simple): loss[n] = mean_flat((eps_pred - noise)^2); the sum in a fixed order (bitwise reproducible).
+ * dxmi_ddpm_loss_bwd: d_eps[n] = (g_loss[n] / CHW) * (2 (eps_pred[n] - noise[n])): torch autograd's nodes of
+ *   ((a - b) ** 2).mean(dim) in its order; g_loss is the DEVICE [N] upstream gradient. */
+int dxmi_ddpm_prep(const float* x_start, const float* noise, const int64_t* t_idx, const float* table, int32_t T, float* x_t,
+                   float* t_out, int32_t N, int32_t CHW, void* stream);
+int dxmi_ddpm_loss_fwd(const float* eps_pred, const float* noise, float* loss, int32_t N, int32_t CHW, void* stream);
+int dxmi_ddpm_loss_bwd(const float* g_loss, const float* eps_pred, const float* noise, float* d_eps, int32_t N, int32_t CHW,
+                       void* stream);
+
 /* update_ema (models/cm/nn.py:57-67) for up to DXMI_EMA_MAX_RATES rates at once (TrainLoop._update_ema, train_util.py:190-193):
  * ema[k * count + i] = rates[k] ema[k * count + i] + (1 - rates[k]) src[i] over fp32 DEVICE tensors of numel[i] elements, as
  * torch's mul_(rate).add_(src, alpha=1-rate) (rate and 1-rate formed in double, rounded to fp32 once; the add is one fused
