@@ -9,6 +9,7 @@
 // of the row.  One workgroup row per image (grid.y), one Philox call per lane per trip; ALU-bound (ten rounds of two 32 x 32 -> 64
 // multiplies, then two logf / sqrtf / sinf / cosf per four floats).  Stores only: no loads besides the row's index, no LDS, no atomics.
 #include "common.h"
+#include "philox_normal.h"
 
 // one rounding per operation: the bits of a normal are part of the interface
 #pragma clang fp contract(off)
@@ -17,48 +18,11 @@ namespace {
 
 constexpr int RN_BLOCK = 256;
 constexpr int RN_MAX_CHUNKS = 64;
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;      // multipliers
-constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // Weyl key increments (golden ratio, sqrt(3) - 1)
-
 // rows whose base is not 16-byte aligned (per_sample % 4 != 0, or odd for int64) store through these: the compiler picks the widest
 // store the target allows at the stated alignment
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
 typedef int64_t i64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
-
-__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += PHILOX_W0;      // the key is bumped between rounds (the bump after the tenth is unused)
-        k1 += PHILOX_W1;
-    }
-    u32x4 o;
-    o[0] = c0, o[1] = c1, o[2] = c2, o[3] = c3;
-    return o;
-}
-
-// ((x >> 9) + 0.5) 2^-23: 23 bits and the half fit fp32's 24-bit significand, so the value is exact and lies in [2^-24, 1 - 2^-24]
-__device__ __forceinline__ float uniform23(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-7f; }
-
-// Box-Muller on the pairs (x0, x1) and (x2, x3): r = sqrtf(-2 logf(u_a)), z0 = r cosf(2 pi u_b), z1 = r sinf(2 pi u_b); |z| <= sqrt(48 ln 2)
-__device__ __forceinline__ f32x4 normals(u32x4 w) {
-    f32x4 z;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const float ua = uniform23(w[2 * p]), ub = uniform23(w[2 * p + 1]);
-        const float r = __builtin_sqrtf(-2.f * logf(ua));
-        const float th = 6.2831855f * ub;
-        z[2 * p] = r * cosf(th);
-        z[2 * p + 1] = r * sinf(th);
-    }
-    return z;
-}
 
 // A row is a function of its own index only: the counter holds the element block and the row's global index, never n, N or the grid.
 __global__ __launch_bounds__(RN_BLOCK) void randn_indexed_kernel(float* __restrict__ out, const int64_t* __restrict__ sample_index,

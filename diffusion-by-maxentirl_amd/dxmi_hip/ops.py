@@ -1817,6 +1817,47 @@ def randint_indexed(sample_index, shape_tail, low, high, seed, draw, out=None):
     return out
 
 
+# dxmi_ddpm_stage modes, table columns and flags (include/dxmi_hip.h)
+DDPM_FIRST, DDPM_STEP = range(2)
+DT_T, DT_T_NEXT, DT_XM, DT_C, DT_S, DT_A, DT_B, DT_Q, DT_R, DT_C0, DT_C1, DT_FLAGS = range(12)
+DT_COLS = 16
+DT_FLAG_CLIP, DT_FLAG_LAST = 1, 2
+
+
+def ddpm_stage(mode, tab, t_out, row=0, x=None, eps=None, z=None, sample_index=None, seed=0, draw=0, ctl=None, out=None,
+               pred_xstart=None):
+    """One transition of the DDPM teacher's ancestral / DDIM samplers between two network evaluations (dxmi_ddpm_stage): x is
+    updated in place, t_out [N] takes the next evaluation's time, out the clamped sample on the row flagged last.  tab: fp32
+    [rows, DT_COLS] on the device.  Noise: z [N, ...] given, or sample_index (int64 [N]) with seed / draw: made in the launch, the
+    values of randn_indexed.  ctl: an int32 [4] device block (row, draw, seed low, seed high) that replaces row / draw / seed: a
+    captured launch then serves every row.  DDPM_FIRST writes t_out of `row` only."""
+    name = "dxmi_ddpm_stage"
+    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, out, pred_xstart)
+    if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == DT_COLS and tab.shape[0] >= 1):
+        raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {DT_COLS}], got {tab.dtype} {tuple(tab.shape)}")
+    if not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
+        raise _lib.DxmiError(f"{name}: t_out must be a contiguous fp32 [N]")
+    N = t_out.numel()
+    chw = 1
+    if mode != DDPM_FIRST:
+        if x is None or eps is None or out is None:
+            raise _lib.DxmiError(f"{name}: a transition needs x, eps and out")
+        for v in (x, eps, z, out, pred_xstart):
+            if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
+                raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
+        if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
+            raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} samples, got {tuple(x.shape)}")
+        chw = x.numel() // N
+        if sample_index is not None and not (sample_index.dtype == torch.int64 and sample_index.is_contiguous()
+                                             and sample_index.shape == (N,)):
+            raise _lib.DxmiError(f"{name}: sample_index must be a contiguous int64 [{N}]")
+    if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
+        raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
+    check(load().dxmi_ddpm_stage(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF, int(seed) & _U64,
+                                 _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), _ptr(t_out), _ptr(out), _ptr(pred_xstart), N, chw,
+                                 _stream()), name)
+
+
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)
 class PackedGConv:
     """BatchNorm-folded bf16 weights [ceil32(Cout)][KH * KW][ceil16(Cin)] + fp32 bias of one BasicConv2d (dxmi_gconv_pack)."""

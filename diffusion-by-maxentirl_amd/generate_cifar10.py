@@ -9,6 +9,16 @@ images over ranks with seed+rank (reference :103-110, :193-204), runs the HIP sa
 is outside the accelerated path: it runs only when pytorch_fid and the dataset folder are present,
 otherwise it is skipped with a message (`--skip_fid` forces that).  `--synthetic` builds the net from
 the built-in config with random weights (benchmark / smoke use, no checkpoint needed).
+
+    python generate_cifar10.py --log_dir out/ddim50 --config builtin:cifar10_T10 --teacher_ckpt .../ema_0.9999_800000.pt \\
+        --ddpm_steps 50 --eta 0 -n 50000 --batchsize 500
+
+`--teacher_ckpt PATH` samples the DDPM teacher itself (models/DxMI/ddpm_sample.py ddpm_sample: ancestral, DDIM and strided
+schedules): PATH is a plain state dict of the bare network, train_ddpm.py's ema_*.pt / model*.pt.  With it: `--ddpm_steps S`
+(1000), `--eta E` (1: ancestral, 0: DDIM), `--variance {small,large}`, `--skip_type {uniform,quad}`, `--no_clip`,
+`--generator {dummy,determ,determ-indiv}` (the deterministic ones make a run's images independent of batch size and rank count;
+`--seed` is their seed) and `--config builtin:NAME | PATH` for a --log_dir that holds no config.yaml.  The images go to
+<log_dir>/generated and through the same FID flow.  It excludes --guidance_scale.
 """
 import argparse
 import os
@@ -33,7 +43,10 @@ def save_png(img_chw, path):
     write_png_batch(to_uint8_nhwc(img_chw[None]), [path], workers=1)
 
 
-def main():
+TEACHER_FLAGS = ("ddpm_steps", "eta", "variance", "skip_type", "generator", "config")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--log_dir", type=str, required=True)
     ap.add_argument("--batchsize", type=int, default=100)
@@ -51,7 +64,39 @@ def main():
     ap.add_argument("--synthetic", type=str, default=None, help="builtin config name, e.g. cifar10_T10 (random weights)")
     ap.add_argument("--no_graph", action="store_true", help="issue every launch from python instead of replaying the T-step loop of a "
                                                            "batch as one hipGraph (dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
-    args, unknown = ap.parse_known_args()
+    ap.add_argument("--teacher_ckpt", type=str, default=None,
+                    help="sample the DDPM teacher itself: a plain state dict of the bare network (train_ddpm.py's ema_*.pt / model*.pt)")
+    ap.add_argument("--ddpm_steps", type=int, default=None, help="with --teacher_ckpt: transitions per image (default 1000)")
+    ap.add_argument("--eta", type=float, default=None, help="with --teacher_ckpt: 1 ancestral (default), 0 DDIM")
+    ap.add_argument("--variance", type=str, default=None, choices=("small", "large"),
+                    help="with --teacher_ckpt: the posterior variance (default) or Ho et al.'s fixedlarge (needs --eta 1)")
+    ap.add_argument("--skip_type", type=str, default=None, choices=("uniform", "quad"), help="with --teacher_ckpt: spacing of the steps")
+    ap.add_argument("--no_clip", action="store_true", help="with --teacher_ckpt: do not clip the predicted x_0 to [-1, 1]")
+    ap.add_argument("--generator", type=str, default=None, choices=("dummy", "determ", "determ-indiv"),
+                    help="with --teacher_ckpt: dummy (default) draws on the device; determ / determ-indiv make image i independent "
+                         "of batch size and rank count (models/cm/random_util.py)")
+    ap.add_argument("--config", type=str, default=None,
+                    help="with --teacher_ckpt: builtin:NAME or a yaml path, for a --log_dir that holds no config.yaml")
+    args, unknown = ap.parse_known_args(argv)
+    given = [f"--{k}" for k in TEACHER_FLAGS if getattr(args, k) is not None] + (["--no_clip"] if args.no_clip else [])
+    if args.teacher_ckpt is None and given:
+        ap.error(f"{', '.join(given)} only apply with --teacher_ckpt")
+    if args.teacher_ckpt is not None and args.guidance_scale is not None:
+        ap.error("--teacher_ckpt and --guidance_scale exclude each other")
+    if args.teacher_ckpt is not None:
+        args.ddpm_steps = 1000 if args.ddpm_steps is None else args.ddpm_steps
+        args.eta = 1.0 if args.eta is None else args.eta
+        args.variance, args.skip_type = args.variance or "small", args.skip_type or "uniform"
+        args.generator = args.generator or "dummy"
+        if args.variance == "large" and args.eta != 1.0:
+            ap.error("--variance large is the ancestral sampler's: it needs --eta 1")
+        if not 0.0 <= args.eta <= 1.0 or args.ddpm_steps < 1:
+            ap.error("--eta must lie in [0, 1] and --ddpm_steps be at least 1")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -64,7 +109,13 @@ def main():
     random.seed(seed + local_rank)
     assert args.n_generate % args.batchsize == 0, "n_generate must be a multiple of batchsize"
 
-    if args.synthetic:
+    if args.config is not None:
+        if args.config.startswith("builtin:"):
+            import configs_builtin
+            run_config = configs_builtin.get(args.config.split(":", 1)[1])
+        else:
+            run_config = dxmi_config.load(args.config)
+    elif args.synthetic:
         import configs_builtin
         run_config = configs_builtin.get(args.synthetic)
     else:
@@ -76,6 +127,8 @@ def main():
     mkdir_p(output_path)
 
     net = dxmi_config.instantiate(run_config.sampler_net)
+    if args.teacher_ckpt is not None:
+        return generate_teacher(args, run_config, net, device, local_rank, world, output_path)
     sampler = dxmi_config.instantiate(run_config.sampler, net=net).to(device)
     if not args.synthetic:
         sampler_path = os.path.join(args.log_dir, f"sampler_{args.epoch}.pth")
@@ -108,23 +161,60 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")  # RCCL; only the final barrier uses it
 
+    def batch(_):
+        with torch.no_grad():
+            if trainer is not None:
+                return trainer.sample_guidance(n_sample=args.batchsize, device=device, guidance_scale=args.guidance_scale)["sample"]
+            return sampler.sample(args.batchsize, device=device)["sample"]
+
+    generate_and_score(args, run_config, batch, device, local_rank, world, output_path)
+
+
+def generate_teacher(args, run_config, net, device, local_rank, world, output_path):
+    """--teacher_ckpt: the DDPM teacher under ddpm_sample, through the output stage and the FID flow of the sampler path."""
+    from dxmi_hip import graph as hip_graph
+    from models.DxMI.ddpm_sample import ddpm_sample
+    from utils import fix_legacy_dict
+    net = net.to(device)
+    net.load_state_dict(fix_legacy_dict(torch.load(args.teacher_ckpt, map_location=device)))
+    net.eval()
+    print0(f"Loaded the DDPM teacher from {args.teacher_ckpt}: {args.ddpm_steps} {args.skip_type} steps, eta {args.eta}, "
+           f"variance {args.variance}, clip_denoised {not args.no_clip}, generator {args.generator}")
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")
+    n_batches = int(args.n_generate / args.batchsize / world)
+    generator = None
+    if args.generator != "dummy":       # after the process group is up: the generator reads its rank and world size
+        from models.cm.random_util import get_generator
+        generator = get_generator(args.generator, n_batches * args.batchsize * world, args.seed)
+    use_graph = hip_graph.default_enabled() and not args.no_graph
+    shape = (args.batchsize,) + tuple(run_config.sampler.sample_shape)
+
+    def batch(i_batch):
+        if generator is not None:       # the images all ranks have finished; the batch's draws count from 0 again
+            generator.set_done_samples(i_batch * args.batchsize * world)
+        return ddpm_sample(net, shape, steps=args.ddpm_steps, eta=args.eta, variance=args.variance, skip_type=args.skip_type,
+                           clip_denoised=not args.no_clip, device=device, generator=generator, use_graph=use_graph)
+
+    generate_and_score(args, run_config, batch, device, local_rank, world, output_path)
+
+
+def generate_and_score(args, run_config, batch, device, local_rank, world, output_path):
+    """batch(i) -> [batchsize, 3, H, W] in [-1, 1], n_batches times: PNGs under output_path, then the FID on rank 0."""
     n_batches = int(args.n_generate / args.batchsize / world)
     i_img = 0
     from utils import ImageWriter
     writer = ImageWriter()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(n_batches):
-        with torch.no_grad():
-            if trainer is not None:
-                d_sample = trainer.sample_guidance(n_sample=args.batchsize, device=device, guidance_scale=args.guidance_scale)
-            else:
-                d_sample = sampler.sample(args.batchsize, device=device)
+    for i_batch in range(n_batches):
+        sample = batch(i_batch)
         if args.save_images:
             # rescale -> clamp -> save_image rounding on the device (dxmi_quantize_u8), pinned double-buffered copy on a side
             # stream, PNGs from a thread pool: the sampler never waits for the files
-            n = d_sample["sample"].shape[0]
-            writer.submit(d_sample["sample"], [os.path.join(output_path, f"{local_rank}_{i_img + k}.png") for k in range(n)])
+            n = sample.shape[0]
+            writer.submit(sample, [os.path.join(output_path, f"{local_rank}_{i_img + k}.png") for k in range(n)])
             i_img += n
     writer.close()
     torch.cuda.synchronize()

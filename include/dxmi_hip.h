@@ -917,6 +917,51 @@ int dxmi_randn_indexed(float* out, const int64_t* sample_index, int32_t N, int64
 int dxmi_randint_indexed(int64_t* out, const int64_t* sample_index, int32_t N, int64_t per_sample, int64_t low, int64_t high,
                          uint64_t seed, uint32_t draw, void* stream);
 
+/* Ancestral / DDIM sampling of the DDPM teacher (csrc/ddpm_sample.hip; models/DxMI/ddpm_sample.py): Ho et al. 2020,
+ * "Denoising Diffusion Probabilistic Models", Algorithm 2; Song et al. 2021, "Denoising Diffusion Implicit Models", eq. 12 and 16.
+ * dxmi_ddpm_stage is the ONE launch between two network evaluations.  With eps the output of the evaluation just done at the state
+ * x and K = tab[row], per element in fp32, one rounding per operation (no fused multiply-add but the linear form's one):
+ *     x0 = K[A] x - K[B] eps                                  (the predicted x_0; A = 1 / sqrt(a_t), B = sqrt(1 / a_t - 1))
+ *   FLAG_CLIP set (clip_denoised):
+ *     x0c = clamp(x0, -1, 1);  eps_hat = (x - K[Q] x0c) K[R]    (Q = sqrt(a_t), R = 1 / sqrt(1 - a_t))
+ *     x'  = (K[C0] x0c + K[C1] eps_hat) + K[S] z                (C0 = sqrt(a_p), C1 = sqrt(1 - a_p - sigma^2))
+ *     pred_xstart = x0c
+ *   FLAG_CLIP clear (the linear form, the association of dxmi_var_step_fwd with assoc = 1):
+ *     x'  = K[XM] x + fma(K[S], z, K[C] eps);  pred_xstart = x0    (that launch's one fused multiply-add, so the two agree bit for bit)
+ *   a row with K[S] == 0 adds no noise: it reads neither z nor the generator (x' = K[C0] x0c + K[C1] eps_hat, K[XM] x + K[C] eps).
+ * then x = x' in place, t_out[n] = K[T_NEXT] (the next evaluation's time) and, on a row with FLAG_LAST, out = clamp(x', -1, 1).
+ * pred_xstart is written when not NULL.  A NaN in eps reaches x' (the clamps pass it); images do not mix.
+ * DXMI_DDPM_FIRST writes t_out[n] = K[T] only (the first evaluation's time); x, eps, out may be NULL.
+ * Control: ctl NULL: row, draw and seed are the by-value arguments, and row outside [0, rows) is DXMI_EINVAL.  ctl not NULL: an
+ *   int32[4] block on the DEVICE = (row, draw, seed low word, seed high word) read by the kernel (the by-value three are ignored),
+ *   so a captured launch serves every row; a row outside [0, rows) read there gives NaN in x, out and t_out, and nothing outside
+ *   the table is read.
+ * Noise: z (fp32 [N, CHW]) is given, or z == NULL and sample_index (int64 [N], DEVICE) is: the kernel then makes
+ *   z[n][e] = the value dxmi_randn_indexed gives for (seed, sample_index[n], draw, e) (same counter layout, same functions: the
+ *   same bits).  Both NULL: no noise is added.  Both given: DXMI_EINVAL.
+ * tab: fp32 [rows][DXMI_DT_COLS] on the device.  x, eps, z, out, pred_xstart: fp32 [N, CHW], 16-byte aligned; CHW % 4 != 0 takes
+ * 4-byte aligned vector accesses and a scalar tail.  N in [1, 65535].  No workspace, no LDS, no atomics. */
+#define DXMI_DDPM_FIRST   0
+#define DXMI_DDPM_STEP    1
+#define DXMI_DT_T         0   /* time of the evaluation the launch follows: (float)tau_k */
+#define DXMI_DT_T_NEXT    1   /* time of the next evaluation (0 on the last row) */
+#define DXMI_DT_XM        2   /* linear form: sqrt(a_p / a_t) */
+#define DXMI_DT_C         3   /* linear form: sqrt(1 - a_p - sigma^2) - sqrt(1 - a_t) sqrt(a_p / a_t) */
+#define DXMI_DT_S         4   /* noise scale s (0 on the last row, and everywhere for eta = 0) */
+#define DXMI_DT_A         5   /* 1 / sqrt(a_t) */
+#define DXMI_DT_B         6   /* sqrt(1 / a_t - 1) */
+#define DXMI_DT_Q         7   /* sqrt(a_t) */
+#define DXMI_DT_R         8   /* 1 / sqrt(1 - a_t) */
+#define DXMI_DT_C0        9   /* sqrt(a_p) */
+#define DXMI_DT_C1       10   /* sqrt(1 - a_p - sigma^2) */
+#define DXMI_DT_FLAGS    11   /* DXMI_DT_FLAG_* summed, stored as a float */
+#define DXMI_DT_COLS     16
+#define DXMI_DT_FLAG_CLIP 1
+#define DXMI_DT_FLAG_LAST 2
+int dxmi_ddpm_stage(int32_t mode, const float* tab, int32_t rows, const int32_t* ctl, int32_t row, uint32_t draw, uint64_t seed,
+                    float* x, const float* eps, const float* z, const int64_t* sample_index, float* t_out, float* out,
+                    float* pred_xstart, int32_t N, int32_t CHW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

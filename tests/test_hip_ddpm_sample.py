@@ -1,0 +1,384 @@
+"""The DDPM teacher's samplers on the device: dxmi_ddpm_stage against float64 on the same fp32 operands, its fused noise against
+dxmi_randn_indexed, NaN and out-of-range handling, malformed calls, the loop against a float64 loop with an analytic network, replay
+against eager on the shrunken HIP Model, batch invariance with the deterministic generators, and generate_cifar10.py --teacher_ckpt.
+
+Bounds (u = 2^-24), per element, on the fp32 table values K widened to float64:
+  clip form    8 u [ (c0 + c1 r q)(a |x| + b |eps|) + c1 r (|x| + q |x0c|) + |c0 x0c| + |c1 eps_hat| + |s z| ]: every term is rounded at
+               most three times at half an ulp, and the clamp is continuous;
+  linear form  8 u (|xm x| + |c eps| + |s z|).
+The loop with the analytic network: 8 times the largest difference between this file's own fp32 numpy restatement of the loop and
+its float64 loop (the loop's conditioning, taken from the oracle and not from the code under test)."""
+import os
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+U = 2.0 ** -24
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.join(os.path.dirname(HERE), "diffusion-by-maxentirl_amd")
+STEPS, MID = 10, 4
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from dxmi_hip import ops as o
+    o.device_check()
+    return o
+
+
+def schedule(clip, variance):
+    from models.DxMI.ddpm_sample import DDPMSampleSchedule
+    return DDPMSampleSchedule(STEPS, 1.0 if variance == "large" else 0.7, variance, clip_denoised=clip)
+
+
+def operands(ops, row, N, CHW, seed):
+    """x, eps, z with about half of the predicted x_0 outside [-1, 1]: x = q x0 + sqrt(1 - a_t) e, eps = e, x0 uniform in [-2, 2]."""
+    gen = torch.Generator().manual_seed(seed)
+    x0 = torch.rand(N, CHW, generator=gen) * 4 - 2
+    e = torch.randn(N, CHW, generator=gen)
+    z = torch.randn(N, CHW, generator=gen)
+    q, r = float(row[ops.DT_Q]), float(row[ops.DT_R])
+    return (q * x0 + e / r).float(), e, z
+
+
+def oracle(ops, row, x, eps, z):
+    """float64 on the fp32 operands -> (x', pred_xstart, bound)."""
+    K = row.double().numpy()
+    x, eps, z = (v.double().numpy() for v in (x, eps, z))
+    xm, c, s, a, b, q, r, c0, c1 = (K[i] for i in (ops.DT_XM, ops.DT_C, ops.DT_S, ops.DT_A, ops.DT_B, ops.DT_Q, ops.DT_R, ops.DT_C0,
+                                                   ops.DT_C1))
+    x0 = a * x - b * eps
+    if int(K[ops.DT_FLAGS]) & ops.DT_FLAG_CLIP:
+        x0c = np.clip(x0, -1, 1)
+        eh = (x - q * x0c) * r
+        xn = c0 * x0c + c1 * eh + s * z
+        bound = 8 * U * ((c0 + c1 * r * q) * (a * np.abs(x) + b * np.abs(eps)) + c1 * r * (np.abs(x) + q * np.abs(x0c))
+                         + np.abs(c0 * x0c) + np.abs(c1 * eh) + np.abs(s * z))
+        return xn, x0c, bound
+    xn = xm * x + (c * eps + s * z)
+    return xn, x0, 8 * U * (np.abs(xm * x) + np.abs(c * eps) + np.abs(s * z))
+
+
+def launch(ops, tab, row, x, eps, z=None, pred=True, **kw):
+    """One by-value launch on copies -> (x', t_out, out, pred_xstart); out is pre-filled with 7."""
+    xd, t = x.to(DEV).clone(), torch.full((x.shape[0],), -5.0, device=DEV)
+    out = torch.full_like(xd, 7.0)
+    p = torch.empty_like(xd) if pred else None
+    ops.ddpm_stage(ops.DDPM_STEP, tab, t, row=row, x=xd, eps=eps.to(DEV), z=None if z is None else z.to(DEV), out=out, pred_xstart=p,
+                   **kw)
+    torch.cuda.synchronize()
+    return xd, t, out, p
+
+
+# ------------------------------------------------------------------------------------------ the launch against float64
+@pytest.mark.parametrize("variance", ["small", "large"])
+@pytest.mark.parametrize("clip", [True, False])
+@pytest.mark.parametrize("N,CHW", [(3, 75), (2, 192), (5, 3072), (1, 5000)])
+def test_stage_vs_fp64(ops, N, CHW, clip, variance):
+    sch = schedule(clip, variance)
+    tab = sch.device_table(DEV)
+    for row, neighbour in ((MID, MID + 1), (STEPS - 1, STEPS - 2)):
+        K = sch.table[row]
+        x, eps, z = operands(ops, K, N, CHW, 100 * row + CHW)
+        got, t_out, out, pred = launch(ops, tab, row, x, eps, z)
+        want, want_pred, bound = oracle(ops, K, x, eps, z)
+        clipped = (np.abs(want_pred) >= 1).mean() if clip else (np.abs(want_pred) > 1).mean()
+        assert 0.3 < clipped < 0.7, clipped
+        err = np.abs(got.cpu().double().numpy() - want)
+        perr = np.abs(pred.cpu().double().numpy() - want_pred)
+        pbound = 8 * U * (np.abs(float(K[ops.DT_A]) * x.double().numpy()) + np.abs(float(K[ops.DT_B]) * eps.double().numpy()))
+        print(f"({N}, {CHW}) clip {clip} {variance} row {row}: worst |err| / bound = {(err / bound).max():.3e}, pred_xstart "
+              f"{(perr / pbound).max():.3e}")
+        assert (err <= bound).all() and (perr <= pbound).all()
+        # negative control, on the CPU: the neighbouring row's coefficients must not pass
+        other, _, _ = oracle(ops, sch.table[neighbour], x, eps, z)
+        assert (np.abs(other - want) > bound).any()
+        last = row == STEPS - 1
+        assert torch.equal(t_out.cpu(), torch.full((N,), float(K[ops.DT_T_NEXT])))
+        assert t_out[0].item() == (0.0 if last else float(sch.tau[STEPS - 2 - row]))
+        assert torch.equal(out, got.clamp(-1, 1) if last else torch.full_like(out, 7.0))
+        if not clip and CHW % 4 == 0:      # the association of the VAR sampler's transition
+            full = lambda col: torch.full((N,), float(K[col]), device=DEV)
+            ref = ops.var_step(x.to(DEV), eps.to(DEV), z.to(DEV), full(ops.DT_XM), full(ops.DT_C), full(ops.DT_S), assoc=1)[0]
+            assert torch.equal(got, ref)
+
+
+def test_first_mode_writes_the_first_time(ops):
+    sch = schedule(True, "small")
+    t = torch.full((6,), -1.0, device=DEV)
+    ops.ddpm_stage(ops.DDPM_FIRST, sch.device_table(DEV), t, row=0)
+    assert t.tolist() == [float(sch.tau[-1])] * 6
+    ops.ddpm_stage(ops.DDPM_FIRST, sch.device_table(DEV), t, row=3)
+    assert t.tolist() == [float(sch.tau[-4])] * 6
+
+
+# ------------------------------------------------------------------------------------------ fused noise
+SEED = (1 << 40) + 12345
+INDEX = [5, (1 << 33) + 7, 123456, 0, 99]
+
+
+def control(row, draw, seed):
+    return torch.from_numpy(np.array([row, draw, seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32).view(np.int32)).to(DEV)
+
+
+@pytest.mark.parametrize("clip", [True, False])
+@pytest.mark.parametrize("N,CHW", [(3, 75), (5, 3072)])
+def test_fused_noise_is_randn_indexed(ops, N, CHW, clip):
+    sch = schedule(clip, "small")
+    tab = sch.device_table(DEV)
+    x, eps, _ = operands(ops, sch.table[MID], N, CHW, 9)
+    idx = torch.tensor(INDEX[:N], dtype=torch.int64, device=DEV)
+    z = ops.randn_indexed(idx, (CHW,), SEED, 3)
+    explicit = launch(ops, tab, MID, x, eps, z)
+    fused = launch(ops, tab, MID, x, eps, None, sample_index=idx, seed=SEED, draw=3)
+    assert torch.equal(explicit[0], fused[0]) and torch.equal(explicit[3], fused[3])
+    assert not torch.equal(fused[0], launch(ops, tab, MID, x, eps, None, sample_index=idx, seed=SEED, draw=4)[0])
+    # the same through the device control block, whose by-value twins are then ignored
+    xd, t, out = x.to(DEV).clone(), torch.empty(N, device=DEV), torch.empty(N, CHW, device=DEV)
+    ops.ddpm_stage(ops.DDPM_STEP, tab, t, row=0, seed=1, draw=9, ctl=control(MID, 3, SEED), x=xd, eps=eps.to(DEV), sample_index=idx, out=out)
+    assert torch.equal(xd, fused[0]) and torch.equal(t, fused[1])
+    # a row with s == 0 touches no noise: the last row gives the same with and without a source
+    a = launch(ops, tab, STEPS - 1, x, eps, None, sample_index=idx, seed=SEED, draw=3)
+    b = launch(ops, tab, STEPS - 1, x, eps, None)
+    c = launch(ops, tab, STEPS - 1, x, eps, torch.full_like(x, float("nan")))
+    assert torch.equal(a[0], b[0]) and torch.equal(a[2], b[2]) and torch.equal(c[0], b[0]) and torch.isfinite(b[0]).all()
+
+
+def test_run_to_run_bits(ops):
+    sch = schedule(True, "small")
+    tab = sch.device_table(DEV)
+    x, eps, z = operands(ops, sch.table[MID], 5, 3072, 21)
+    idx = torch.tensor(INDEX, dtype=torch.int64, device=DEV)
+    for kw in (dict(z=z), dict(sample_index=idx, seed=SEED, draw=1)):
+        a, b = launch(ops, tab, MID, x, eps, **kw), launch(ops, tab, MID, x, eps, **kw)
+        assert all(torch.equal(u, v) for u, v in zip(a, b))
+
+
+@pytest.mark.parametrize("clip", [True, False])
+def test_nan_stays_in_its_image(ops, clip):
+    sch = schedule(clip, "small")
+    tab = sch.device_table(DEV)
+    for row in (MID, STEPS - 1):
+        x, eps, z = operands(ops, sch.table[row], 4, 771, 33)
+        clean = launch(ops, tab, row, x, eps, z)
+        bad = eps.clone()
+        bad[2] = float("nan")
+        got = launch(ops, tab, row, x, bad, z)
+        last = row == STEPS - 1
+        for k in (0, 2, 3) if last else (0, 3):             # x', out (written on the last row only), pred_xstart
+            assert torch.isnan(got[k][2]).all()             # the clamps do not swallow it
+            for n in (0, 1, 3):
+                assert torch.equal(got[k][n], clean[k][n]) and torch.isfinite(got[k][n]).all()
+        assert torch.equal(got[1], clean[1])
+
+
+def test_out_of_range_row_in_the_control_block(ops):
+    sch = schedule(True, "small")
+    tab = sch.device_table(DEV)
+    x, eps, z = operands(ops, sch.table[MID], 3, 192, 41)
+    for row in (STEPS, -1 & 0xFFFFFFFF, 1 << 20):
+        xd, t, out = x.to(DEV).clone(), torch.zeros(3, device=DEV), torch.zeros(3, 192, device=DEV)
+        ops.ddpm_stage(ops.DDPM_STEP, tab, t, ctl=control(row, 0, 0), x=xd, eps=eps.to(DEV), z=z.to(DEV), out=out)
+        torch.cuda.synchronize()
+        assert torch.isnan(xd).all() and torch.isnan(out).all() and torch.isnan(t).all()
+
+
+def test_malformed_calls(ops):
+    from dxmi_hip import DxmiError
+    sch = schedule(True, "small")
+    tab = sch.device_table(DEV)
+    x, eps, z = (v.to(DEV) for v in operands(ops, sch.table[MID], 4, 768, 2))
+    t, out = torch.empty(4, device=DEV), torch.empty(4, 768, device=DEV)
+    idx = torch.arange(4, device=DEV)
+    step = lambda **kw: ops.ddpm_stage(ops.DDPM_STEP, **dict(dict(tab=tab, t_out=t, row=MID, x=x, eps=eps, z=z, out=out), **kw))
+    bad = [lambda: step(row=STEPS), lambda: step(row=-1), lambda: step(sample_index=idx), lambda: step(eps=eps[:3]),
+           lambda: step(eps=eps.double()), lambda: step(x=x.cpu()), lambda: step(out=None), lambda: step(tab=tab[:, :8]),
+           lambda: step(t_out=t[:3]), lambda: step(z=None, sample_index=idx.int()), lambda: step(ctl=torch.zeros(3, dtype=torch.int32, device=DEV)),
+           lambda: step(x=x[:, 1:], eps=eps[:, 1:], z=z[:, 1:], out=out[:, 1:])]
+    for i, call in enumerate(bad):
+        with pytest.raises(DxmiError):
+            call()
+            pytest.fail(f"malformed call {i} was accepted")
+    # the C entry point itself: a status and a message, no launch
+    lib = ops.load()
+    p = lambda v: v.data_ptr()
+    raw = lambda mode=1, tb=p(tab), rows=STEPS, ctl=None, row=MID, xx=p(x), ee=p(eps), zz=p(z), si=None, tt=p(t), oo=p(out), N=4, CHW=768: \
+        lib.dxmi_ddpm_stage(mode, tb, rows, ctl, row, 0, 0, xx, ee, zz, si, tt, oo, None, N, CHW, None)
+    for kw, msg in ((dict(tb=None), b"null pointer"), (dict(tt=None), b"null pointer"), (dict(xx=None), b"null pointer"),
+                    (dict(ee=None), b"null pointer"), (dict(oo=None), b"null pointer"), (dict(N=0), b"N (0)"),
+                    (dict(N=65536), b"N (65536)"), (dict(CHW=0), b"CHW (0)"), (dict(CHW=-4), b"CHW (-4)"), (dict(rows=0), b"at least one row"),
+                    (dict(row=STEPS), b"row (10)"), (dict(row=-1), b"row (-1)"), (dict(mode=2), b"unknown mode"),
+                    (dict(si=p(idx)), b"not both"), (dict(xx=p(x) + 4), b"16-byte aligned"), (dict(zz=p(z) + 8), b"16-byte aligned"),
+                    (dict(zz=None, si=p(idx) + 4), b"16-byte aligned"), (dict(ctl=p(idx) + 2), b"4-byte aligned")):
+        assert raw(**kw) != 0 and msg in lib.dxmi_last_error(), (kw, lib.dxmi_last_error())
+    assert raw(mode=0, row=STEPS) != 0
+    assert raw() == 0 and raw(mode=0, xx=None, ee=None, oo=None, zz=None) == 0
+    torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------ the loop, analytic network
+def analytic_net(x, t):
+    return 0.8 * torch.tanh(0.9 * x + 1e-3 * t[:, None, None, None])
+
+
+def numpy_loop(ops, tab, noise, dtype):
+    """The loop restated in numpy at `dtype` on the fp32 table -> the state after every transition."""
+    f = dtype
+    K = tab.numpy().astype(f)
+    x = noise[0].numpy().astype(f)
+    states = []
+    for k in range(len(K)):
+        xm, c, s, a, b, q, r, c0, c1 = (K[k][i] for i in (ops.DT_XM, ops.DT_C, ops.DT_S, ops.DT_A, ops.DT_B, ops.DT_Q, ops.DT_R,
+                                                         ops.DT_C0, ops.DT_C1))
+        eps = (f(0.8) * np.tanh(f(0.9) * x + f(1e-3) * K[k][ops.DT_T])).astype(f)
+        z = noise[k + 1].numpy().astype(f)
+        if int(K[k][ops.DT_FLAGS]) & ops.DT_FLAG_CLIP:
+            x0c = np.clip(a * x - b * eps, f(-1), f(1))
+            x = c0 * x0c + c1 * ((x - q * x0c) * r)
+            x = x + s * z if s != 0 else x
+        else:
+            x = xm * x + (c * eps + s * z) if s != 0 else xm * x + c * eps
+        assert x.dtype == f
+        states.append(x)
+    return np.stack(states)
+
+
+@pytest.mark.parametrize("clip,eta", [(True, 1.0), (False, 1.0), (True, 0.0), (False, 0.5)])
+def test_loop_with_analytic_network(ops, clip, eta):
+    from models.DxMI.ddpm_sample import ddpm_sample, ddpm_sample_schedule
+    S, shape = 6, (4, 3, 8, 8)
+    gen = torch.Generator().manual_seed(77)
+    noise = [torch.randn(shape, generator=gen) for _ in range(S + 1)]
+    tab = ddpm_sample_schedule(S, eta, clip_denoised=clip).table
+    want, low = numpy_loop(ops, tab, noise, np.float64), numpy_loop(ops, tab, noise, np.float32)
+    bound = 8 * np.abs(low.astype(np.float64) - want).max()
+    seen = []
+    out = ddpm_sample(analytic_net, shape, steps=S, eta=eta, clip_denoised=clip, device=DEV, noise=noise,
+                      callback=lambda d: seen.append(d))
+    torch.cuda.synchronize()
+    got = torch.stack([d["x"] for d in seen]).cpu().double().numpy()
+    err = np.abs(got - want).max()
+    print(f"clip {clip} eta {eta}: loop vs float64 {err:.3e}, bound {bound:.3e} (8 x the fp32 restatement's {bound / 8:.3e})")
+    assert bound > 0 and err <= bound
+    assert [d["i"] for d in seen] == list(range(S)) and [d["t"] for d in seen] == [833, 666, 500, 333, 166, 0]
+    assert torch.equal(out, seen[-1]["x"].clamp(-1, 1)) and out.abs().max() <= 1
+    if clip:
+        assert all(d["pred_xstart"].abs().max() <= 1 for d in seen)
+    # the torch path on the CPU states the same expressions
+    cpu = ddpm_sample(analytic_net, shape, steps=S, eta=eta, clip_denoised=clip, device="cpu", noise=noise)
+    assert (cpu - out.cpu()).abs().max() <= 2 * bound          # each within `bound` of the float64 loop
+
+
+# ------------------------------------------------------------------------------------------ the loop on the HIP Model
+NET_KW = dict(ch=64, out_ch=3, ch_mult=(1, 2), num_res_blocks=1, attn_resolutions=[8], dropout=0.1, in_channels=3, resolution=16)
+SHAPE = (4, 3, 16, 16)
+
+
+@pytest.fixture(scope="module")
+def net(ops):
+    """The shrunken Model of tests/test_hip_ddpm_train.py, in eval mode."""
+    from models.DxMI.unet_small import Model
+    from oracle.weights import formula_tensor
+    m = Model(**NET_KW)
+    m.load_state_dict({k: formula_tensor(k, v.shape) for k, v in m.state_dict().items()})
+    return m.to(DEV).eval()
+
+
+def test_replay_equals_eager_with_torch_draws(net):
+    from models.DxMI.ddpm_sample import ddpm_sample, replay_graphs
+    torch.manual_seed(5)
+    eager = ddpm_sample(net, SHAPE, steps=5, device=DEV).clone()
+    torch.manual_seed(5)
+    replayed = ddpm_sample(net, SHAPE, steps=5, device=DEV, use_graph=True).clone()
+    assert torch.isfinite(eager).all() and eager.abs().max() <= 1 and eager.std() > 0
+    assert torch.equal(eager, replayed)
+    graphs = replay_graphs(net)
+    assert len(graphs) == 1 and graphs[0].captures == 1 and graphs[0].replays >= 3
+    again = ddpm_sample(net, SHAPE, steps=5, device=DEV, use_graph=True).clone()      # no seed in between: other draws
+    assert not torch.equal(again, replayed) and graphs[0].captures == 1 and graphs[0].replays >= 8
+    torch.manual_seed(5)
+    from models.cm.random_util import get_generator
+    assert torch.equal(ddpm_sample(net, SHAPE, steps=5, device=DEV, generator=get_generator("dummy")), eager)
+
+
+@pytest.mark.parametrize("eta", [1.0, 0.0])
+def test_replay_equals_eager_with_the_deterministic_generator(net, eta):
+    from models.cm.random_util import get_generator
+    from models.DxMI.ddpm_sample import ddpm_sample, replay_graphs
+    gen = get_generator("determ", 64, seed=(1 << 35) + 3)
+    kw = dict(steps=5, eta=eta, device=DEV, generator=gen)
+    draws = 5 if eta else 1
+    gen.set_done_samples(8)
+    eager = ddpm_sample(net, SHAPE, **kw).clone()
+    assert gen.draw == draws
+    before = {id(g): (g.captures, g.replays) for g in replay_graphs(net)}
+    gen.set_done_samples(8)
+    first = ddpm_sample(net, SHAPE, use_graph=True, **kw).clone()
+    assert gen.draw == draws and torch.equal(first, eager)
+    new = [g for g in replay_graphs(net) if id(g) not in before]
+    assert len(new) == 1 and new[0].captures == 1 and new[0].replays >= 3
+    gen.set_done_samples(8)
+    second = ddpm_sample(net, SHAPE, use_graph=True, **kw).clone()
+    assert torch.equal(second, first) and new[0].captures == 1 and new[0].replays >= 8
+    gen.set_done_samples(12)
+    assert not torch.equal(ddpm_sample(net, SHAPE, use_graph=True, **kw), first)
+    # bit for bit what explicit generator draws fed through noise= give
+    gen.set_done_samples(8)
+    noise = [gen.randn(*SHAPE, device=DEV)]
+    noise += [gen.randn_like(noise[0]) for _ in range(draws - 1)] + [None] * (6 - draws)
+    assert torch.equal(ddpm_sample(net, SHAPE, steps=5, eta=eta, device=DEV, noise=noise), eager)
+
+
+def test_batch_invariance(net):
+    from models.cm.random_util import get_generator
+    from models.DxMI.ddpm_sample import ddpm_sample
+    gen = get_generator("determ-indiv", 6, seed=9)
+    gen.set_done_samples(0)
+    whole = ddpm_sample(net, (6, 3, 16, 16), steps=4, device=DEV, generator=gen).clone()
+    parts = []
+    for b in range(3):
+        gen.set_done_samples(2 * b)
+        parts.append(ddpm_sample(net, (2, 3, 16, 16), steps=4, device=DEV, generator=gen, use_graph=True).clone())
+    parts = torch.cat(parts)
+    for i in range(6):
+        assert torch.equal(parts[i], whole[i]), i
+    assert not torch.equal(whole[0], whole[1])
+
+
+# ------------------------------------------------------------------------------------------ command line
+def png_size(path):
+    with open(path, "rb") as f:
+        head = f.read(24)
+    assert head[:8] == b"\x89PNG\r\n\x1a\n"
+    return struct.unpack(">II", head[16:24])
+
+
+def test_generate_cifar10_teacher_cli(tmp_path):
+    """train_ddpm.py for two steps, then its EMA file through generate_cifar10.py --teacher_ckpt twice with --generator determ.  Each
+    child runs under its own time limit (the full-size net: its first pack and one capture); a child starts only if the one before
+    exited 0."""
+    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(PKG, "train_ddpm.py"), "--config", "builtin:cifar10_T10",
+                        "--synthetic_data", "--max_iters", "2", "--batch_size", "8", "--run", "t0"], cwd=tmp_path, capture_output=True,
+                       text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    ema = tmp_path / "results" / "cifar10" / "cifar10_T10_ddpm" / "t0" / "ema_0.9999_000002.pt"
+    assert ema.exists()
+    files = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(PKG, "generate_cifar10.py"), "--log_dir", str(out),
+                            "--teacher_ckpt", str(ema), "--config", "builtin:cifar10_T10", "--ddpm_steps", "4", "-n", "8", "--batchsize", "4",
+                            "--skip_fid", "--generator", "determ"], cwd=tmp_path, capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        names = sorted(os.listdir(out / "generated"))
+        assert names == [f"0_{i}.png" for i in range(8)]
+        assert all(png_size(out / "generated" / n) == (32, 32) for n in names)
+        files.append([(out / "generated" / n).read_bytes() for n in names])
+    assert files[0] == files[1]
+    assert len(set(files[0])) > 1
