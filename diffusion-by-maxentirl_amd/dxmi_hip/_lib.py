@@ -167,6 +167,7 @@ SIGNATURES = {
     "dxmi_randn_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
     "dxmi_randint_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
     "dxmi_ddpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 7 + [c_int, c_int, c_void_p]),
+    "dxmi_dpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 8 + [c_int, c_int, c_void_p]),
 }
 
 _lib = None

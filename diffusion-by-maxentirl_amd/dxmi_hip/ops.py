@@ -1858,6 +1858,50 @@ def ddpm_stage(mode, tab, t_out, row=0, x=None, eps=None, z=None, sample_index=N
                                  _stream()), name)
 
 
+# dxmi_dpm_stage modes, table columns and flags (include/dxmi_hip.h)
+DPM_FIRST, DPM_STEP = range(2)
+MT_T, MT_T_NEXT, MT_CX, MT_W0, MT_W1, MT_W2, MT_S, MT_A, MT_B, MT_FLAGS, MT_ORDER = range(11)
+MT_COLS = 16
+MT_FLAG_CLIP, MT_FLAG_LAST = 1, 2
+
+
+def dpm_stage(mode, tab, t_out, row=0, x=None, eps=None, z=None, sample_index=None, seed=0, draw=0, ctl=None, hist=None, out=None,
+              pred_xstart=None):
+    """One multistep DPM-Solver++ transition between two network evaluations (dxmi_dpm_stage): x is updated in place, this
+    evaluation's data prediction goes to hist[row % 3] (hist: fp32 [3, *x.shape]; the two before it are read from the other slots
+    where the row's weights are not 0), t_out [N] takes the next evaluation's time, out the clamped sample on the row flagged last.
+    tab: fp32 [rows, MT_COLS] on the device.  Noise: z [N, ...] given, or sample_index (int64 [N]) with seed / draw: made in the
+    launch, the values of randn_indexed.  ctl: an int32 [4] device block (row, draw, seed low, seed high) that replaces row / draw /
+    seed: a captured launch then serves every row.  DPM_FIRST writes t_out of `row` only."""
+    name = "dxmi_dpm_stage"
+    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, hist, out, pred_xstart)
+    if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == MT_COLS and tab.shape[0] >= 1):
+        raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {MT_COLS}], got {tab.dtype} {tuple(tab.shape)}")
+    if not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
+        raise _lib.DxmiError(f"{name}: t_out must be a contiguous fp32 [N]")
+    N = t_out.numel()
+    chw = 1
+    if mode != DPM_FIRST:
+        if x is None or eps is None or out is None or hist is None:
+            raise _lib.DxmiError(f"{name}: a transition needs x, eps, hist and out")
+        for v in (x, eps, z, out, pred_xstart):
+            if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
+                raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
+        if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
+            raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} samples, got {tuple(x.shape)}")
+        if not (hist.dtype == torch.float32 and hist.is_contiguous() and tuple(hist.shape) == (3,) + tuple(x.shape)):
+            raise _lib.DxmiError(f"{name}: hist must be a contiguous fp32 {(3,) + tuple(x.shape)}, got {hist.dtype} {tuple(hist.shape)}")
+        chw = x.numel() // N
+        if sample_index is not None and not (sample_index.dtype == torch.int64 and sample_index.is_contiguous()
+                                             and sample_index.shape == (N,)):
+            raise _lib.DxmiError(f"{name}: sample_index must be a contiguous int64 [{N}]")
+    if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
+        raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
+    check(load().dxmi_dpm_stage(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF, int(seed) & _U64,
+                                _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), _ptr(hist), _ptr(t_out), _ptr(out), _ptr(pred_xstart),
+                                N, chw, _stream()), name)
+
+
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)
 class PackedGConv:
     """BatchNorm-folded bf16 weights [ceil32(Cout)][KH * KW][ceil16(Cin)] + fp32 bias of one BasicConv2d (dxmi_gconv_pack)."""

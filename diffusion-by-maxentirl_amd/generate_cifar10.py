@@ -19,6 +19,14 @@ schedules): PATH is a plain state dict of the bare network, train_ddpm.py's ema_
 `--generator {dummy,determ,determ-indiv}` (the deterministic ones make a run's images independent of batch size and rank count;
 `--seed` is their seed) and `--config builtin:NAME | PATH` for a --log_dir that holds no config.yaml.  The images go to
 <log_dir>/generated and through the same FID flow.  It excludes --guidance_scale.
+
+    python generate_cifar10.py --log_dir out/dpmpp10 --config builtin:cifar10_T10 --teacher_ckpt .../ema_0.9999_800000.pt \\
+        --solver dpmpp --ddpm_steps 10 -n 50000 --batchsize 500
+
+`--solver {ancestral,dpmpp,sde-dpmpp}` (with --teacher_ckpt; default ancestral, the path above) samples the teacher with multistep
+DPM-Solver++ (models/DxMI/dpm_sample.py dpm_sample), the ODE solver or its SDE variant: `--ddpm_steps S` network evaluations (10),
+`--solver_order {1,2,3}` (2; the SDE variant 1 or 2), `--solver_type {midpoint,exact}`, `--no_lower_order_final`, `--skip_type
+{logsnr,uniform,quad}` (logsnr).  --eta and --variance belong to the ancestral path and are refused with these solvers.
 """
 import argparse
 import os
@@ -44,6 +52,8 @@ def save_png(img_chw, path):
 
 
 TEACHER_FLAGS = ("ddpm_steps", "eta", "variance", "skip_type", "generator", "config")
+SOLVER_FLAGS = ("solver", "solver_order", "solver_type")         # DPM-Solver++; with --no_lower_order_final
+SOLVERS = {"dpmpp": "dpmsolver++", "sde-dpmpp": "sde-dpmsolver++"}
 
 
 def parse_args(argv=None):
@@ -70,20 +80,50 @@ def parse_args(argv=None):
     ap.add_argument("--eta", type=float, default=None, help="with --teacher_ckpt: 1 ancestral (default), 0 DDIM")
     ap.add_argument("--variance", type=str, default=None, choices=("small", "large"),
                     help="with --teacher_ckpt: the posterior variance (default) or Ho et al.'s fixedlarge (needs --eta 1)")
-    ap.add_argument("--skip_type", type=str, default=None, choices=("uniform", "quad"), help="with --teacher_ckpt: spacing of the steps")
+    ap.add_argument("--skip_type", type=str, default=None, choices=("uniform", "quad", "logsnr"),
+                    help="with --teacher_ckpt: spacing of the steps (logsnr: with --solver dpmpp / sde-dpmpp only, their default)")
     ap.add_argument("--no_clip", action="store_true", help="with --teacher_ckpt: do not clip the predicted x_0 to [-1, 1]")
     ap.add_argument("--generator", type=str, default=None, choices=("dummy", "determ", "determ-indiv"),
                     help="with --teacher_ckpt: dummy (default) draws on the device; determ / determ-indiv make image i independent "
                          "of batch size and rank count (models/cm/random_util.py)")
     ap.add_argument("--config", type=str, default=None,
                     help="with --teacher_ckpt: builtin:NAME or a yaml path, for a --log_dir that holds no config.yaml")
+    ap.add_argument("--solver", type=str, default=None, choices=("ancestral", "dpmpp", "sde-dpmpp"),
+                    help="with --teacher_ckpt: ancestral (default: ddpm_sample, with --eta / --variance), or multistep DPM-Solver++ as "
+                         "the ODE solver (dpmpp) or its SDE variant (sde-dpmpp); --ddpm_steps then defaults to 10")
+    ap.add_argument("--solver_order", type=int, default=None, choices=(1, 2, 3), help="with --solver dpmpp (1-3) / sde-dpmpp (1-2): default 2")
+    ap.add_argument("--solver_type", type=str, default=None, choices=("midpoint", "exact"),
+                    help="with --solver dpmpp / sde-dpmpp: the second-order rows' weights (default midpoint)")
+    ap.add_argument("--no_lower_order_final", action="store_true",
+                    help="with --solver dpmpp / sde-dpmpp: keep the order up to the last transition")
     args, unknown = ap.parse_known_args(argv)
     given = [f"--{k}" for k in TEACHER_FLAGS if getattr(args, k) is not None] + (["--no_clip"] if args.no_clip else [])
+    given += [f"--{k}" for k in SOLVER_FLAGS if getattr(args, k) is not None] + (["--no_lower_order_final"] if args.no_lower_order_final else [])
     if args.teacher_ckpt is None and given:
         ap.error(f"{', '.join(given)} only apply with --teacher_ckpt")
     if args.teacher_ckpt is not None and args.guidance_scale is not None:
         ap.error("--teacher_ckpt and --guidance_scale exclude each other")
-    if args.teacher_ckpt is not None:
+    if args.teacher_ckpt is not None and args.solver in SOLVERS:
+        refused = [f"--{k}" for k in ("eta", "variance") if getattr(args, k) is not None]
+        if refused:
+            ap.error(f"{', '.join(refused)} belong to --solver ancestral, not to --solver {args.solver}")
+        args.ddpm_steps = 10 if args.ddpm_steps is None else args.ddpm_steps
+        args.solver_order = 2 if args.solver_order is None else args.solver_order
+        args.solver_type, args.skip_type = args.solver_type or "midpoint", args.skip_type or "logsnr"
+        args.generator = args.generator or "dummy"
+        if args.solver == "sde-dpmpp" and args.solver_order == 3:
+            ap.error("--solver sde-dpmpp is defined for --solver_order 1 and 2")
+        from models.DxMI.dpm_sample import dpm_timesteps
+        try:
+            dpm_timesteps(args.ddpm_steps, skip_type=args.skip_type)
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.teacher_ckpt is not None:
+        only = [f"--{k}" for k in SOLVER_FLAGS[1:] if getattr(args, k) is not None] + (["--no_lower_order_final"] if args.no_lower_order_final else [])
+        only += ["--skip_type logsnr"] if args.skip_type == "logsnr" else []
+        if only:
+            ap.error(f"{', '.join(only)} only apply with --solver dpmpp or --solver sde-dpmpp")
+        args.solver = "ancestral"
         args.ddpm_steps = 1000 if args.ddpm_steps is None else args.ddpm_steps
         args.eta = 1.0 if args.eta is None else args.eta
         args.variance, args.skip_type = args.variance or "small", args.skip_type or "uniform"
@@ -174,12 +214,18 @@ def generate_teacher(args, run_config, net, device, local_rank, world, output_pa
     """--teacher_ckpt: the DDPM teacher under ddpm_sample, through the output stage and the FID flow of the sampler path."""
     from dxmi_hip import graph as hip_graph
     from models.DxMI.ddpm_sample import ddpm_sample
+    from models.DxMI.dpm_sample import dpm_sample
     from utils import fix_legacy_dict
     net = net.to(device)
     net.load_state_dict(fix_legacy_dict(torch.load(args.teacher_ckpt, map_location=device)))
     net.eval()
-    print0(f"Loaded the DDPM teacher from {args.teacher_ckpt}: {args.ddpm_steps} {args.skip_type} steps, eta {args.eta}, "
-           f"variance {args.variance}, clip_denoised {not args.no_clip}, generator {args.generator}")
+    if args.solver in SOLVERS:
+        print0(f"Loaded the DDPM teacher from {args.teacher_ckpt}: DPM-Solver++ ({SOLVERS[args.solver]}), {args.ddpm_steps} "
+               f"{args.skip_type} steps, order {args.solver_order}, {args.solver_type}, lower_order_final "
+               f"{not args.no_lower_order_final}, clip_denoised {not args.no_clip}, generator {args.generator}")
+    else:
+        print0(f"Loaded the DDPM teacher from {args.teacher_ckpt}: {args.ddpm_steps} {args.skip_type} steps, eta {args.eta}, "
+               f"variance {args.variance}, clip_denoised {not args.no_clip}, generator {args.generator}")
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")
@@ -194,6 +240,10 @@ def generate_teacher(args, run_config, net, device, local_rank, world, output_pa
     def batch(i_batch):
         if generator is not None:       # the images all ranks have finished; the batch's draws count from 0 again
             generator.set_done_samples(i_batch * args.batchsize * world)
+        if args.solver in SOLVERS:
+            return dpm_sample(net, shape, steps=args.ddpm_steps, order=args.solver_order, algorithm=SOLVERS[args.solver],
+                              solver_type=args.solver_type, skip_type=args.skip_type, lower_order_final=not args.no_lower_order_final,
+                              clip_denoised=not args.no_clip, device=device, generator=generator, use_graph=use_graph)
         return ddpm_sample(net, shape, steps=args.ddpm_steps, eta=args.eta, variance=args.variance, skip_type=args.skip_type,
                            clip_denoised=not args.no_clip, device=device, generator=generator, use_graph=use_graph)
 

@@ -1,0 +1,403 @@
+"""Sample the CIFAR-10 DDPM teacher with DPM-Solver++ (Lu et al. 2022, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion
+Probabilistic Models", arXiv:2211.01095): the multistep data-prediction solver (Algorithm 2) at orders 1-3 and its SDE variant at
+orders 1-2, the training-free baseline a 10-step or 4-step DxMI sampler is measured against.  The same network and the same
+`Alpha_bar` table as models/DxMI/ddpm_sample.py (calc_diffusion_hyperparams; no second formula for the table).
+
+  dpm_timesteps        the integer steps tau_0 = 0 < ... < tau_{S-1} a run visits: linear in the log-SNR, uniform or quadratic
+  dpm_coefficients     every per-transition scalar in float64 (the host tests' statement of the formulas)
+  DPMSampleSchedule    one fp32 row per transition, noisiest first (columns ops.MT_*, include/dxmi_hip.h), built once on the host
+  dpm_transition       one transition as torch expressions on a row, in the operation order of dxmi_dpm_stage
+  dpm_sample           the loop: per transition one network evaluation and one dxmi_dpm_stage launch
+
+ab = Alpha_bar (the fp32 table read into float64), alpha = sqrt(ab), sigma = sqrt(1 - ab), lambda = log alpha - log sigma.  A run
+makes S evaluations and has S rows.  Row k < S - 1 goes from t = tau_{S-1-k} to p = tau_{S-2-k}, h = lambda_p - lambda_t > 0; row
+S - 1 goes from tau_0 to alpha_p = 1, sigma_p = 0.  Evaluation k gives the data prediction D_k = x / alpha_t - (sigma_t / alpha_t)
+eps, clamped to [-1, 1] with clip_denoised.  With o_k = min(order, k + 1), with lower_order_final also min(o_k, S - k), and L_j the
+Lagrange basis polynomial on the o_k nodes lambda of evaluations k, k - 1, ...:
+    ODE  "dpmsolver++"      x' = (sigma_p / sigma_t) x + sum_j w_j D_{k-j}
+         exact     w_j = sigma_p int_{lambda_t}^{lambda_p} e^lambda L_j dlambda       (order 1: alpha_p (1 - e^-h))
+         midpoint  order-2 rows: w_0 = alpha_p (1 - e^-h)(1 + 1 / (2r)), w_1 = -alpha_p (1 - e^-h) / (2r), r = (lambda_t - lambda_prev) / h
+    SDE  "sde-dpmsolver++"  x' = (sigma_p / sigma_t) e^-h x + sum_j w_j D_{k-j} + sigma_p sqrt(1 - e^-2h) z         (orders 1-2)
+         exact     w_j = 2 alpha_p int_{lambda_t}^{lambda_p} e^{-2 (lambda_p - lambda)} L_j dlambda
+         midpoint  order-2 rows: the ODE's with 1 - e^-2h in place of 1 - e^-h
+    the last row: x' = D (cx = 0, w_0 = 1, no noise); the run returns clamp(x', -1, 1).
+With v = lambda_p - lambda both integrals are alpha_p times sums of the moments M_n(h) = int_0^h e^-v v^n dv (the SDE's of 2h),
+evaluated by their series below h = 1 (no cancellation for the h ~ 5e-3 of adjacent steps) and by the recurrence above it.
+"""
+import math
+import weakref
+
+import numpy as np
+import torch
+
+from dxmi_hip import graph as _graph
+from dxmi_hip import ops
+from dxmi_hip._lib import DxmiError
+
+from ..cm.karras_diffusion import _HostTable, _as_f32, _memo
+from ..cm.random_util import DeterministicGenerator, DummyGenerator
+from .ddpm_sample import _evaluate, _initial_state, _progress, ddpm_timesteps
+from .ddpm_train import _hip_model
+from .var_sampler import calc_diffusion_hyperparams
+
+ALGORITHMS = ("dpmsolver++", "sde-dpmsolver++")
+SOLVER_TYPES = ("midpoint", "exact")
+SKIP_TYPES = ("logsnr", "uniform", "quad")
+
+
+# ------------------------------------------------------------------------------------------------- host schedule
+def _log_snr(alpha_bar):
+    """lambda = log alpha - log sigma of a float64 Alpha_bar."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    return 0.5 * (np.log(ab) - np.log1p(-ab))
+
+
+def _logsnr_sequence(lam, S):
+    """S values linear in lambda from lam[0] to lam[-1], each mapped to the step with the nearest lambda (a tie: the lowest index).
+    lam is strictly decreasing."""
+    target = np.linspace(lam[0], lam[-1], S)
+    pos = np.clip(np.searchsorted(-lam, -target, side="left"), 1, len(lam) - 1)      # lam[pos - 1] >= target >= lam[pos]
+    low = np.abs(lam[pos - 1] - target) <= np.abs(lam[pos] - target)
+    return [int(v) for v in np.where(low, pos - 1, pos)]
+
+
+def _logsnr_ok(lam, S):
+    if S < 2 or S > len(lam):
+        return False
+    tau = _logsnr_sequence(lam, S)
+    return tau[0] == 0 and tau[-1] == len(lam) - 1 and all(b > a for a, b in zip(tau, tau[1:]))
+
+
+def dpm_timesteps(S, T=1000, skip_type="logsnr", beta_0=1e-4, beta_T=0.02):
+    """The S steps of a run, increasing, tau_0 == 0.  uniform / quad: ddpm_timesteps.  logsnr (the DPM-Solver papers' spacing):
+    S values linear in lambda from lambda[0] to lambda[T - 1], each mapped to the step with the nearest lambda (a tie: the lowest
+    index), so tau_{S-1} == T - 1.  ValueError unless 2 <= S and the steps are strictly increasing (too many steps map two values to
+    one integer step at the crowded low-noise end); the message names the largest S that works."""
+    S, T = int(S), int(T)
+    if skip_type not in SKIP_TYPES:
+        raise ValueError(f"dpm_timesteps: skip_type must be one of {SKIP_TYPES}, got {skip_type!r}")
+    if skip_type != "logsnr":
+        return ddpm_timesteps(S, T, skip_type)
+    if T < 2:
+        raise ValueError(f"dpm_timesteps: logsnr spacing needs T >= 2, got {T}")
+    lam = _log_snr(calc_diffusion_hyperparams(T, beta_0, beta_T)["Alpha_bar"].to(torch.float32).numpy())
+    if not (np.diff(lam) < 0).all():
+        raise ValueError("dpm_timesteps: the schedule's log-SNR is not strictly decreasing")
+    if not _logsnr_ok(lam, S):
+        largest = max((n for n in range(T, 1, -1) if _logsnr_ok(lam, n)), default=None)
+        raise ValueError(f"dpm_timesteps: {S} logsnr steps do not give 2 <= S strictly increasing steps from 0 to T - 1 = {T - 1}; "
+                         f"the largest S that works is {largest}")
+    return _logsnr_sequence(lam, S)
+
+
+def _check_mode(algorithm, order, solver_type):
+    if algorithm not in ALGORITHMS:
+        raise ValueError(f"algorithm must be one of {ALGORITHMS}, got {algorithm!r}")
+    if solver_type not in SOLVER_TYPES:
+        raise ValueError(f"solver_type must be one of {SOLVER_TYPES}, got {solver_type!r}")
+    if isinstance(order, bool) or int(order) != order or not 1 <= int(order) <= 3:
+        raise ValueError(f"order must be 1, 2 or 3, got {order!r}")
+    if algorithm == "sde-dpmsolver++" and int(order) == 3:
+        raise ValueError("sde-dpmsolver++ is defined for orders 1 and 2, got order 3")
+
+
+def _moments(h, count):
+    """M_n = int_0^h e^-v v^n dv for n < count, float64.  Below h = 1 the series h^(n+1) sum_k (-h)^k / (k! (n + k + 1)), whose
+    terms fall at once (M_n ~ h^(n+1) / (n + 1): the recurrence would take it as the difference of two numbers 1 / h times as
+    large); from h = 1 on the recurrence M_0 = -expm1(-h), M_n = n M_{n-1} - h^n e^-h."""
+    if h < 1.0:
+        out = []
+        for n in range(count):
+            term, total = 1.0, 0.0
+            for k in range(40):
+                total += term / (n + k + 1)
+                term *= -h / (k + 1)
+            out.append(h ** (n + 1) * total)
+        return out
+    out = [-math.expm1(-h)]
+    for n in range(1, count):
+        out.append(n * out[-1] - h ** n * math.exp(-h))
+    return out
+
+
+def _lagrange_weights(nodes, moments):
+    """sum_n c_{j,n} moments[n] for every Lagrange basis polynomial L_j(v) = sum_n c_{j,n} v^n on `nodes`."""
+    out = []
+    for j, vj in enumerate(nodes):
+        poly = np.poly1d([1.0])
+        for i, vi in enumerate(nodes):
+            if i != j:
+                poly = poly * np.poly1d([1.0, -vi]) / (vj - vi)
+        out.append(float(sum(c * moments[n] for n, c in enumerate(poly.coeffs[::-1]))))
+    return out
+
+
+def dpm_orders(S, order, lower_order_final=True):
+    """The order of every row: min(order, k + 1), with lower_order_final also min(., S - k); the last (denoise) row has order 1."""
+    o = [min(int(order), k + 1) for k in range(S)]
+    if lower_order_final:
+        o = [min(v, S - k) for k, v in enumerate(o)]
+    o[-1] = 1
+    return o
+
+
+def dpm_coefficients(alpha_bar, tau, algorithm="dpmsolver++", order=2, solver_type="midpoint", lower_order_final=True):
+    """The scalars of every transition in float64, noisiest first, from `alpha_bar` as given (any float array): a dict of arrays
+    cx, w0, w1, w2, s, a, b and order (int64).  A weight beyond a row's order is exactly 0."""
+    _check_mode(algorithm, order, solver_type)
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    t = np.asarray(list(tau)[::-1], dtype=np.int64)
+    S = len(t)
+    alpha, sigma, lam = np.sqrt(ab[t]), np.sqrt(1.0 - ab[t]), _log_snr(ab[t])
+    sde = algorithm == "sde-dpmsolver++"
+    rate = 2.0 if sde else 1.0
+    orders = dpm_orders(S, order, lower_order_final)
+    co = {k: np.zeros(S) for k in ("cx", "w0", "w1", "w2", "s")}
+    co["a"], co["b"], co["order"] = 1.0 / alpha, sigma / alpha, np.asarray(orders, dtype=np.int64)
+    for k in range(S - 1):
+        o, h = orders[k], lam[k + 1] - lam[k]
+        if not h > 0:
+            raise ValueError(f"dpm_coefficients: the log-SNR must rise from step {t[k]} to step {t[k + 1]}")
+        alpha_p, sigma_p = alpha[k + 1], sigma[k + 1]
+        gain = -math.expm1(-rate * h)                                  # 1 - e^-h (ODE), 1 - e^-2h (SDE)
+        co["cx"][k] = sigma_p / sigma[k] * (math.exp(-h) if sde else 1.0)
+        co["s"][k] = sigma_p * math.sqrt(-math.expm1(-2.0 * h)) if sde else 0.0
+        if o == 2 and solver_type == "midpoint":
+            r = (lam[k] - lam[k - 1]) / h
+            w = [alpha_p * gain * (1.0 + 0.5 / r), -alpha_p * gain * 0.5 / r]
+        else:
+            # v = lambda_p - lambda: the nodes are h, h + (lambda_k - lambda_{k-1}), ...; the SDE's integrand e^-2v is the ODE's in 2v
+            nodes = [rate * (lam[k + 1] - lam[k - j]) for j in range(o)]
+            w = [alpha_p * v for v in _lagrange_weights(nodes, _moments(rate * h, o))]
+        for j, v in enumerate(w):
+            co[f"w{j}"][k] = v
+    co["w0"][-1] = 1.0                                                 # the denoise row: x' = D, alpha_p = 1, sigma_p = 0
+    return co
+
+
+class DPMSampleSchedule(_HostTable):
+    """table: fp32 [S, ops.MT_COLS], row k = the transition tau_{S-1-k} -> tau_{S-2-k}: dpm_coefficients on the fp32 Alpha_bar in
+    float64, rounded once.  draws[k]: whether transition k adds noise (S != 0); coef: the float64 coefficients."""
+
+    def __init__(self, steps=10, order=2, algorithm="dpmsolver++", solver_type="midpoint", skip_type="logsnr", lower_order_final=True,
+                 clip_denoised=True, T=1000, beta_0=1e-4, beta_T=0.02):
+        _check_mode(algorithm, order, solver_type)
+        hp = calc_diffusion_hyperparams(int(T), beta_0, beta_T)
+        alpha_bar = hp["Alpha_bar"].to(torch.float32).numpy()
+        self.tau = dpm_timesteps(steps, T, skip_type, beta_0, beta_T)
+        self.steps, self.T = len(self.tau), int(T)
+        self.order, self.algorithm, self.solver_type, self.skip_type = int(order), algorithm, solver_type, skip_type
+        self.lower_order_final, self.clip_denoised = bool(lower_order_final), bool(clip_denoised)
+        self.coef = co = dpm_coefficients(alpha_bar, self.tau, algorithm, order, solver_type, lower_order_final)
+        S = self.steps
+        tab = np.zeros((S, ops.MT_COLS), dtype=np.float32)
+        times = np.asarray(self.tau[::-1], dtype=np.float32)
+        tab[:, ops.MT_T] = times
+        tab[:-1, ops.MT_T_NEXT] = times[1:]
+        for col, k in ((ops.MT_CX, "cx"), (ops.MT_W0, "w0"), (ops.MT_W1, "w1"), (ops.MT_W2, "w2"), (ops.MT_S, "s"), (ops.MT_A, "a"),
+                       (ops.MT_B, "b"), (ops.MT_ORDER, "order")):
+            tab[:, col] = co[k].astype(np.float32)
+        tab[:, ops.MT_FLAGS] = ops.MT_FLAG_CLIP if self.clip_denoised else 0
+        tab[-1, ops.MT_FLAGS] += ops.MT_FLAG_LAST
+        assert tab[-1, ops.MT_S] == 0 and tab[-1, ops.MT_CX] == 0 and tab[-1, ops.MT_W0] == 1
+        # a row reads exactly the history its order names: rows 0 and 1 and the lowered rows never touch an unwritten slot
+        for k in range(S):
+            assert (tab[k, ops.MT_W1] != 0) == (co["order"][k] >= 2) and (tab[k, ops.MT_W2] != 0) == (co["order"][k] >= 3), k
+        super().__init__(torch.from_numpy(tab))
+        self.draws = [bool(v != 0) for v in tab[:, ops.MT_S]]
+        self.n_draws = sum(self.draws)
+
+
+_SCHEDULES = {}
+
+
+def dpm_sample_schedule(steps=10, order=2, algorithm="dpmsolver++", solver_type="midpoint", skip_type="logsnr", lower_order_final=True,
+                        clip_denoised=True, T=1000, beta_0=1e-4, beta_T=0.02):
+    """The (cached) DPMSampleSchedule of these settings: one object per setting, so that a replay graph keyed on the table's
+    identity is found again by the next call."""
+    _check_mode(algorithm, order, solver_type)
+    key = (int(steps), int(order), algorithm, solver_type, skip_type, bool(lower_order_final), bool(clip_denoised), int(T),
+           float(beta_0), float(beta_T))
+    return _memo(_SCHEDULES, key, 32, lambda: DPMSampleSchedule(steps, order, algorithm, solver_type, skip_type, lower_order_final,
+                                                                clip_denoised, T, beta_0, beta_T))
+
+
+def dpm_transition(x, eps, z, row, hist=()):
+    """One transition on `row` (a table row, or 16 coefficients of another dtype in its layout) as torch expressions in the
+    operation order of dxmi_dpm_stage -> (x', D0).  hist: (D_{k-1}, D_{k-2}), the data predictions of the evaluations before, as
+    far as the row's weights are not 0 (a zero weight reads nothing).  z None or row[MT_S] == 0: no noise is added."""
+    d0 = row[ops.MT_A] * x - row[ops.MT_B] * eps
+    if int(row[ops.MT_FLAGS]) & ops.MT_FLAG_CLIP:
+        d0 = d0.clamp(-1, 1)
+    acc = row[ops.MT_CX] * x + row[ops.MT_W0] * d0
+    for j, col in enumerate((ops.MT_W1, ops.MT_W2)):
+        if float(row[col]) != 0.0:
+            acc = acc + row[col] * hist[j]
+    if z is not None and float(row[ops.MT_S]) != 0.0:
+        acc = acc + row[ops.MT_S] * z
+    return acc, d0
+
+
+# ------------------------------------------------------------------------------------------------- the loop
+def _sample_torch(sch, net, shape, device, generator, noise, callback, progress):
+    """The transitions as torch expressions: the CPU path of the host tests.  The state takes the dtype of noise[0] when that is
+    float64 (a float64 network then runs in float64 on the widened fp32 table); it is fp32 otherwise."""
+    dtype = torch.float64 if noise is not None and noise[0].dtype == torch.float64 else torch.float32
+    tab = sch.table.to(device=device, dtype=dtype)
+    if noise is not None:
+        x = noise[0].to(device=device, dtype=dtype).clone()
+    elif generator is not None:
+        x = generator.randn(*shape, device=device)
+    else:
+        x = torch.randn(shape, device=device)
+    hist = []
+    for k in _progress(range(sch.steps), progress):
+        eps = net(x, torch.full((shape[0],), float(tab[k, ops.MT_T]), device=device, dtype=dtype))
+        z = None
+        if sch.draws[k]:
+            if noise is not None:
+                z = noise[k + 1].to(device=device, dtype=dtype)
+            else:
+                z = generator.randn_like(x) if generator is not None else torch.randn_like(x)
+        x, d0 = dpm_transition(x, eps, z, tab[k], hist)
+        hist = [d0] + hist[:1]
+        if callback is not None:
+            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x, "pred_xstart": d0})
+    return x.clamp(-1, 1)
+
+
+def _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress):
+    f32 = dict(dtype=torch.float32, device=device)
+    tab = sch.device_table(device)
+    x, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
+    hist = torch.empty((3,) + shape, **f32)
+    _initial_state(x, shape, device, generator, noise)
+    fused = isinstance(generator, DeterministicGenerator)
+    idx = generator.get_indices(shape[0], device) if fused and sch.n_draws else None
+    zbuf = None
+    ops.dpm_stage(ops.DPM_FIRST, tab, t, row=0)
+    for k in _progress(range(sch.steps), progress):
+        eps = _evaluate(hip, net, x, t)
+        kw = {}
+        if sch.draws[k]:
+            if noise is not None:
+                kw["z"] = _as_f32(noise[k + 1], device)
+            elif fused:       # the draw generator.randn_like(x) would make, made inside the launch
+                kw.update(sample_index=idx, seed=generator.seed, draw=generator._next_draw())
+            elif generator is not None:
+                kw["z"] = _as_f32(generator.randn_like(x), device)
+            else:
+                zbuf = torch.empty(shape, **f32) if zbuf is None else zbuf
+                kw["z"] = zbuf.normal_()
+        pred = torch.empty(shape, **f32) if callback is not None else None
+        ops.dpm_stage(ops.DPM_STEP, tab, t, row=k, x=x, eps=eps, hist=hist, out=out, pred_xstart=pred, **kw)
+        if callback is not None:
+            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x.clone(), "pred_xstart": pred})
+    return out
+
+
+class _Replay:
+    """ONE transition (network evaluation + dxmi_dpm_stage) as a StepGraph, and the static buffers it runs on: x, t, out and the
+    three history slots.  The row, the draw number and the seed reach the captured launch through a host input, and the launch
+    derives its history slots from the row, so the one captured step serves every row.  Holds the schedule: the captured launch
+    reads its device table for as long as the graph lives."""
+
+    def __init__(self, sch, hip, net, shape, device, mode):
+        f32 = dict(dtype=torch.float32, device=device)
+        self.sch, self.hip, self.net, self.mode = sch, hip, net, mode
+        self.tab = sch.device_table(device)
+        self.x, self.t, self.out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
+        self.hist = torch.empty((3,) + shape, **f32)
+        self.z = torch.empty(shape, **f32) if mode == "torch" else None
+        self.idx = torch.zeros(shape[0], dtype=torch.int64, device=device) if mode == "fused" else None
+        self.row = self.draw = self.seed = 0
+        self.graph = _graph.StepGraph(self._step, device, modules=_graph.pack_modules(hip if hip is not None else net),
+                                      name=f"dpm_sample{(sch.steps, sch.order, sch.algorithm, tuple(shape), mode)}")
+
+    def _control(self):
+        return [self.row, self.draw & 0xFFFFFFFF, self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF]
+
+    def _step(self):
+        eps = _evaluate(self.hip, self.net, self.x, self.t)
+        kw = {}
+        if self.mode == "torch":      # drawn in every transition: the captured step is the same for all rows (the last row's is unused)
+            kw["z"] = self.z.normal_()
+        elif self.mode == "fused":
+            kw["sample_index"] = self.idx
+        g = _graph.current()
+        if g is not None:
+            kw["ctl"] = g.host_input(torch.int32, 4, self._control)
+        else:
+            kw.update(row=self.row, draw=self.draw, seed=self.seed)
+        ops.dpm_stage(ops.DPM_STEP, self.tab, self.t, x=self.x, eps=eps, hist=self.hist, out=self.out, **kw)
+
+    def run(self, shape, device, generator):
+        sch = self.sch
+        _initial_state(self.x, shape, device, generator, None)       # None, or a deterministic generator (also when no row draws)
+        if self.mode == "fused":
+            self.idx.copy_(generator.get_indices(shape[0], device))
+            self.seed = int(generator.seed)
+        ops.dpm_stage(ops.DPM_FIRST, self.tab, self.t, row=0)
+        for k in range(sch.steps):
+            self.row = k
+            if self.mode == "fused" and sch.draws[k]:
+                self.draw = generator._next_draw()
+            self.graph()
+        return self.out
+
+
+_GRAPHS = weakref.WeakKeyDictionary()       # network -> {graph key: _Replay}
+
+
+def replay_graphs(net):
+    """The StepGraphs dpm_sample holds for `net` (their .captures / .replays count what ran)."""
+    try:
+        return [r.graph for r in _GRAPHS.get(net, {}).values()]
+    except TypeError:
+        return []
+
+
+def dpm_sample(net, shape, steps=10, order=2, algorithm="dpmsolver++", solver_type="midpoint", skip_type="logsnr",
+               lower_order_final=True, clip_denoised=True, device=None, generator=None, noise=None, callback=None, progress=False,
+               use_graph=False, T=1000, beta_0=1e-4, beta_T=0.02):
+    """Sample the DDPM teacher with multistep DPM-Solver++: `steps` network evaluations on dpm_timesteps(steps, T, skip_type) ->
+    clamp(x_0, -1, 1), [B, C, H, W].  algorithm "dpmsolver++" (the ODE solver, orders 1-3) or "sde-dpmsolver++" (orders 1-2);
+    solver_type "midpoint" (Algorithm 2 of the paper) or "exact" (the Lagrange weights) for the second-order rows;
+    lower_order_final lowers the order of the last rows so that the last transition is first order.
+
+    The contract of ddpm_sample.  net: the HIP Model (bare or under .module), or any callable net(x, t_float [B]) -> eps.  On the
+    device every transition is one network evaluation and one dxmi_dpm_stage launch; a CPU `device` with a callable runs the same
+    expressions in torch.  noise: S + 1 recorded draws (x_T, then one per transition; those of transitions that add no noise are not
+    read); nothing is drawn then.  callback({"i", "t", "x", "pred_xstart"}) after every transition (x: the new state, before the
+    final clamp).  generator: a models.cm.random_util generator.  None / dummy: torch's device generator.  determ / determ-indiv:
+    x_T is generator.randn and every transition's z is made inside the stage launch: bit for bit what generator.randn_like draws
+    fed through noise= give, and generator.draw ends advanced by the draws made.  The ODE solver draws x_T alone.
+    use_graph: capture ONE transition as a StepGraph and replay it for every later transition of every call with the same network,
+    shape, device, table and noise source; the data predictions a later row reads live in static buffers the captured launch
+    addresses from the row number.  Off with callback, progress or noise=.  The returned tensor is then STATIC: the next call of the
+    same key overwrites it."""
+    sch = dpm_sample_schedule(steps, order, algorithm, solver_type, skip_type, lower_order_final, clip_denoised, T, beta_0, beta_T)
+    shape = tuple(int(s) for s in shape)
+    if noise is not None and len(noise) != sch.steps + 1:
+        raise ValueError(f"dpm_sample: noise must hold {sch.steps + 1} draws (x_T and one per transition), got {len(noise)}")
+    hip = _hip_model(net)
+    if isinstance(generator, DummyGenerator):       # it forwards to torch: the same draws as no generator
+        generator = None
+    device = _graph.indexed_device(torch.device("cuda") if device is None else device)
+    with torch.no_grad():
+        if device.type != "cuda":
+            if hip is not None:
+                raise DxmiError("dpm_sample: the HIP Model runs only on the device (a CPU device takes a torch callable)")
+            return _sample_torch(sch, net, shape, device, generator, noise, callback, progress)
+        replayable = generator is None or isinstance(generator, DeterministicGenerator)
+        if not (use_graph and callback is None and not progress and noise is None and replayable and not _graph.capturing()):
+            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
+        mode = "none" if not sch.n_draws else ("fused" if isinstance(generator, DeterministicGenerator) else "torch")
+        try:
+            graphs = _GRAPHS.setdefault(hip if hip is not None else net, {})
+        except TypeError:        # not weak-referenceable: no cache, so no replay
+            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
+        # what a capture freezes: the network (the dictionary's key), the shape and the device, the table and where z comes from
+        key = (id(sch), shape, device.index, mode)
+        rp = _memo(graphs, key, 8, lambda: _Replay(sch, hip, net, shape, device, mode))
+        return rp.run(shape, device, generator)

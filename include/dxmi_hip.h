@@ -962,6 +962,52 @@ int dxmi_ddpm_stage(int32_t mode, const float* tab, int32_t rows, const int32_t*
                     float* x, const float* eps, const float* z, const int64_t* sample_index, float* t_out, float* out,
                     float* pred_xstart, int32_t N, int32_t CHW, void* stream);
 
+/* DPM-Solver++ sampling of the DDPM teacher (csrc/dpm_sample.hip; models/DxMI/dpm_sample.py): Lu, Zhou, Bao, Chen,
+ * Li and Zhu 2022, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models" (arXiv:2211.01095), the
+ * multistep data-prediction solver of Algorithm 2 at orders 1-3 and its SDE variant at orders 1-2 (the reference tree has no such
+ * sampler).  dxmi_dpm_stage is the ONE launch between two network evaluations.  With eps the output of evaluation k = row at the
+ * state x and K = tab[row], per element in fp32, one rounding per operation (no fused multiply-add), in this order:
+ *     D0  = K[A] x - K[B] eps;  FLAG_CLIP: D0 = clamp(D0, -1, 1)        (the data prediction; A = 1 / alpha_t, B = sigma_t / alpha_t)
+ *     acc = K[CX] x + K[W0] D0
+ *     acc += K[W1] D1     if K[W1] != 0       (D1 = D_{k-1}, the data prediction of the evaluation before)
+ *     acc += K[W2] D2     if K[W2] != 0       (D2 = D_{k-2})
+ *     acc += K[S] z       if K[S] != 0
+ * then x = acc in place, hist[row % 3] = D0, t_out[n] = K[T_NEXT] (the next evaluation's time) and, on a row with FLAG_LAST,
+ * out = clamp(acc, -1, 1).  pred_xstart = D0 is written when not NULL.  A NaN in eps reaches x' (the clamps pass it); images do not
+ * mix.
+ * History: hist is fp32 [3][N][CHW].  D1 and D2 are read from slots (row + 2) % 3 and (row + 1) % 3; the three slots are derived
+ *   in the kernel from the row number, so one captured launch serves every row.  A weight that is exactly 0 means its slot is NOT
+ *   read: rows 0 and 1 of a run and the rows whose order is lowered never touch history that was never written.
+ * DXMI_DPM_FIRST writes t_out[n] = K[T] only (the first evaluation's time); x, eps, hist, out may be NULL.
+ * Control: ctl NULL: row, draw and seed are the by-value arguments, and row outside [0, rows) is DXMI_EINVAL.  ctl not NULL: an
+ *   int32[4] block on the DEVICE = (row, draw, seed low word, seed high word) read by the kernel (the by-value three are ignored);
+ *   a row outside [0, rows) read there gives NaN in x, out, t_out and slot 0 of the history; nothing outside the table and no
+ *   history slot is read.
+ * Noise: z (fp32 [N, CHW]) is given, or z == NULL and sample_index (int64 [N], DEVICE) is: the kernel then makes
+ *   z[n][e] = the value dxmi_randn_indexed gives for (seed, sample_index[n], draw, e) (the same bits).  Both NULL: no noise is
+ *   added.  Both given: DXMI_EINVAL.  A row with K[S] == 0 reads neither z nor the generator.
+ * tab: fp32 [rows][DXMI_MT_COLS] on the device.  x, eps, z, hist, out, pred_xstart: 16-byte aligned; CHW % 4 != 0 takes 4-byte
+ * aligned vector accesses and a scalar tail.  N in [1, 65535].  No workspace, no LDS, no atomics. */
+#define DXMI_DPM_FIRST    0
+#define DXMI_DPM_STEP     1
+#define DXMI_MT_T         0   /* time of the evaluation the launch follows: (float)tau */
+#define DXMI_MT_T_NEXT    1   /* time of the next evaluation (0 on the last row) */
+#define DXMI_MT_CX        2   /* ODE sigma_p / sigma_t; SDE (sigma_p / sigma_t) exp(-h); 0 on the last row */
+#define DXMI_MT_W0        3   /* weight of D_k (1 on the last row) */
+#define DXMI_MT_W1        4   /* weight of D_{k-1}; exactly 0: the slot is not read */
+#define DXMI_MT_W2        5   /* weight of D_{k-2}; exactly 0: the slot is not read */
+#define DXMI_MT_S         6   /* noise scale: SDE sigma_p sqrt(1 - exp(-2h)); 0 for the ODE and on the last row */
+#define DXMI_MT_A         7   /* 1 / alpha_t */
+#define DXMI_MT_B         8   /* sigma_t / alpha_t */
+#define DXMI_MT_FLAGS     9   /* DXMI_MT_FLAG_* summed, stored as a float */
+#define DXMI_MT_ORDER    10   /* the order the row was built with (1-3); not read by the kernel */
+#define DXMI_MT_COLS     16
+#define DXMI_MT_FLAG_CLIP 1
+#define DXMI_MT_FLAG_LAST 2
+int dxmi_dpm_stage(int32_t mode, const float* tab, int32_t rows, const int32_t* ctl, int32_t row, uint32_t draw, uint64_t seed,
+                   float* x, const float* eps, const float* z, const int64_t* sample_index, float* hist, float* t_out, float* out,
+                   float* pred_xstart, int32_t N, int32_t CHW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
