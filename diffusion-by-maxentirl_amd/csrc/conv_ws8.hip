@@ -4,21 +4,27 @@
 //   * 256 images x 256 couts = 256 tiles: one per CU, same 512-thread workgroup (waves 0-3 MFMA, 4-5 weights, 6-7 the rest);
 //   * MFMA wave w owns image w of the tile: 64 couts x 64 pixels (4 x 4 accumulator blocks of 16 x 16), operands by
 //     ds_read_b128 at a per-lane base + compile-time offset; a step (one tap of one 32-channel chunk) is 16 MFMAs;
-//   * halo image: 4 x (10 x 10) pixels x 64 B = 25 KB per chunk, channel piece j of halo column hx in slot j ^ (hx & 2)
-//     (bank-conflict free for every tap at row pitch 10, brute-forced); weight ring 6 x 4 KB; output / residual tile 32 KB;
-//     bias + one temb row per image;
+//   * halo image: per image 10 rows x 8 pixels x 64 B (5 KB; 20 KB per chunk), channel piece j of column x in slot
+//     j ^ ((x & 4) >> 1) (bank-conflict free for every tap at row pitch 8, brute-forced: tools/ws8_swizzle.py).  Only the 64
+//     interior pixels are ever fetched: four 1-KiB DMAs per image and chunk.  The zero rows above and below (rows 0 and 9 of
+//     the image's block) are written once per launch; a lane whose tap column falls left or right of the map reads a 5 KB zero
+//     strip instead (its per-lane base points there: no padding column is stored, none is fetched);
+//   * weight ring 6 x 4 KB; output / residual tile 32 KB; bias + one temb row per image;
 //   * everything else as in conv_ws.hip: one barrier per step, movers issue a few DMAs per step, exact in-order vmcnt counts.
 // Scope: 3x3 / stride 1 / pad 1 on 8x8 maps, NHWC bf16 in (virtual concat) and out, any batch, Cout % 64 == 0,
 // an even number (>= 4) of 32-channel chunks.
 #include "conv_common.h"
+#include <stdlib.h>
 #include <type_traits>
 
 
 namespace {
 
-constexpr int W8_HP = 10, W8_HS = 100;              // halo row pitch / pixels per image halo
-constexpr int W8_HALO_BLOCKS = 25;                  // 4 x 100 pixels x 64 B = 25 KiB exactly
-constexpr int W8_HALO = W8_HALO_BLOCKS * 1024;
+constexpr int W8_ROW = 8 * 64;                      // halo row pitch: the 8 interior pixels x 64 B (no padding columns)
+constexpr int W8_IMG = 10 * W8_ROW;                 // an image's block: zero row, 8 interior rows (4 KiB contiguous), zero row
+constexpr int W8_HALO_BLOCKS = 16;                  // 1-KiB DMAs per chunk: 4 images x 4 row pairs
+constexpr int W8_HALO = 4 * W8_IMG;                 // 20 KiB per buffer
+constexpr int W8_STRIP = W8_IMG;                    // zero strip behind the two buffers: what a tap column outside 0..7 reads
 constexpr int W8_A_SLOT = 4096;                     // one (chunk, tap): 2 k-steps x 2 cout blocks x 1 KiB fragments
 #ifndef W8_RING_SLOTS
 #define W8_RING_SLOTS 6
@@ -29,6 +35,14 @@ constexpr int W8_RO = 256 * 128;                    // 256 px x 64 co bf16
 constexpr int W8_TB = 2048;                         // bias[64] | temb[4][64] fp32
 
 __device__ uint4 w8_zero16 = {0u, 0u, 0u, 0u};
+
+// timing-only ablations of the diagnostic build (make STAMPS=1; DXMI_CONV_WS8_DBG bits: 1 no weight stream, 2 no halo stream,
+// 4 no step barriers — wrong results); compiled out of the product library (tools/conv_ws8_ab.py)
+#ifdef DXMI_CONV_STAMPS
+#define W8_DBG(bit) (p.stagger & (bit))
+#else
+#define W8_DBG(bit) 0
+#endif
 
 #define W8_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define W8_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -76,7 +90,7 @@ template <bool GN>
 __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     char* const halo0 = smem;
-    char* const aring = smem + 2 * W8_HALO;
+    char* const aring = smem + 2 * W8_HALO + W8_STRIP;
     char* const ro = aring + W8_A_RING;
     float* const tb = reinterpret_cast<float*>(ro + W8_RO);
 
@@ -98,11 +112,17 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
     if (wave < 4) {
         // ================================================================ MFMA waves: image `wave` of the tile, 64 couts
         const int px = lane & 15, kg = lane >> 4;      // B: pixel / channel piece; A: cout / 8-channel group; D: pixel / 4-cout group
-        int bbase[3];
+        // per halo buffer and kx: a column outside the map points into the zero strip, at the low address bits (banks) of the
+        // slot it replaces; the strip is zero at every row offset read_b adds
+        int bbase[2][3];
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
-            const int hx = (px & 7) + kx;
-            bbase[kx] = ((wave * W8_HS + (px >> 3) * W8_HP + hx) * 64) + ((kg ^ (hx & 2)) << 4);
+            const int col = (px & 7) + kx - 1;
+            const int low = (px >> 3) * W8_ROW + ((kg ^ ((col & 4) >> 1)) << 4);
+            const bool inside = col >= 0 && col < 8;
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                bbase[b][kx] = inside ? b * W8_HALO + wave * W8_IMG + col * 64 + low : 2 * W8_HALO + (col & 3) * 64 + low;
         }
         const char* const abase = aring + ((kg >> 1) * 2048) + ((px + 32 * (kg & 1)) << 4);   // + slot*4096 + (cb16>>1)*1024 + (cb16&1)*256
         f32x4 acc[4][4];
@@ -121,9 +141,9 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
         };
         auto read_b = [&](int u, int half, bf16x8 (&B)[2]) {      // 16-pixel blocks 2 half, 2 half + 1: image rows 2 nb, 2 nb + 1
             const int t = u % 9, ky = t / 3, kx = t % 3;
-            const char* hb = halo0 + ((u / 9) & 1) * W8_HALO + bbase[kx];
+            const char* hb = halo0 + bbase[(u / 9) & 1][kx];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) B[i] = *reinterpret_cast<const bf16x8*>(hb + ((2 * (half * 2 + i) + ky) * W8_HP) * 64);
+            for (int i = 0; i < 2; ++i) B[i] = *reinterpret_cast<const bf16x8*>(hb + (2 * (half * 2 + i) + ky) * W8_ROW);
         };
         auto mfma8 = [&](const bf16x8 (&A)[4], const bf16x8 (&B)[2], int half) {
 #pragma unroll
@@ -135,7 +155,15 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
         const float slope = dxmi_act_slope(p.act);
         const bool has_res = p.residual != nullptr;
 
-        w8_barrier();                                   // P0: tap 0 and the first halo chunk have landed
+        // the padding no DMA ever touches, once per launch: this wave's image's rows 0 and 9 in both buffers, and the strip
+        {
+            const uint4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                *reinterpret_cast<uint4*>(halo0 + b * W8_HALO + wave * W8_IMG + (lane >> 5) * 9 * W8_ROW + (lane & 31) * 16) = z;
+            for (int i = wave; i < W8_STRIP / 1024; i += 4) *reinterpret_cast<uint4*>(halo0 + 2 * W8_HALO + i * 1024 + lane * 16) = z;
+        }
+        w8_barrier();                                   // P0: tap 0 and the first halo chunk have landed, the padding is written
         read_a(0, A0);
         read_b(0, 0, Bx);
         for (;;) {
@@ -155,7 +183,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                     read_b(u, 1, By);
                     if (u & 1) mfma8(A1, Bx, 0); else mfma8(A0, Bx, 0);
                     W8_INTERLEAVE_2();
-                    if (u % 3 == 2) w8_barrier();       // end of a group of three steps: the next group's weights (at a chunk end: the next halo image) landed
+                    if (u % 3 == 2 && !(W8_DBG(4))) w8_barrier();       // end of a group of three steps: the next group's weights (at a chunk end: the next halo image) landed
                     if (u & 1) read_a(u + 1, A0); else read_a(u + 1, A1);
                     read_b(u + 1, 0, Bx);
                     if (u & 1) mfma8(A1, By, 1); else mfma8(A0, By, 1);
@@ -290,6 +318,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
         static_assert(W8_RING == 6, "group hand-over needs the six-slot ring");
         u32x4 fq[2][3][2];
         auto load_tap = [&](int cot, int g, u32x4 (&f)[2]) {
+            if (W8_DBG(1)) return;
             const int c = g / 9, t = g - c * 9;
             const char* src = wb + ((size_t)(t * p.KST + c * 2 + lw) * p.CB + cot * 2) * 1024;
 #pragma unroll
@@ -359,7 +388,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                         }
                     }
                     load_group(G + 3, cur.cot, more ? nxt.cot : cur.cot, fq[(j + 1) & 1]);
-                    w8_barrier();                                           // end of group step G
+                    if (!(W8_DBG(4))) w8_barrier();                         // end of group step G
                 }
             }
             w8_barrier();                                        // E1
@@ -376,27 +405,27 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
     {
         const int bw = wave - 6;
         const int t2 = bw * 64 + lane;                     // 0..127 over the two waves
-        constexpr int HB2 = (W8_HALO_BLOCKS + 1) / 2;      // halo blocks per wave (block bw + 2k)
-        // per tile each lane keeps the BYTE offset of its source piece inside either concat part (-1: zero padding): a DMA
-        // address per chunk is then one 64-bit add and a select (no 64-bit multiply, no GOT load of the zero page per DMA)
+        constexpr int HB2 = W8_HALO_BLOCKS / 2;            // halo blocks per wave (block bw + 2k): row pair blk & 3 of image blk >> 2
+        // per tile each lane keeps the BYTE offset of its source piece inside either concat part (-1: an image past the end of
+        // the batch): a DMA address per chunk is then one 64-bit add and a select (no 64-bit multiply, no GOT load of the zero
+        // page per DMA).  Every block is interior pixels only.
         const char* const zero_page = reinterpret_cast<const char*>(p.mask_src);    // 16 zero bytes (host: &w8_zero16)
         int hoff0[HB2], hoff1[HB2];
         auto halo_plan = [&](const W8Tile& t) {
 #pragma unroll
             for (int k = 0; k < HB2; ++k) {
-                const int hp = (bw + 2 * k) * 16 + (lane >> 2);
-                const int sub = hp / W8_HS, r = hp - sub * W8_HS;
-                const int hy = r / W8_HP, hx = r - hy * W8_HP;
-                const int iy = hy - 1, ix = hx - 1;
-                const bool ok = sub < 4 && t.n0 + sub < p.N && iy >= 0 && ix >= 0 && iy < 8 && ix < 8;
+                const int blk = bw + 2 * k;
+                const int sub = blk >> 2, iy = (blk & 3) * 2 + (lane >> 5), ix = (lane >> 2) & 7;
+                const bool ok = t.n0 + sub < p.N;
                 // nearest x2 upsample in front of the conv (Upsample 4x4 -> 8x8): virtual pixel (iy, ix) is source pixel (iy / 2, ix / 2)
                 const int pix = p.ups ? ((t.n0 + sub) * 4 + (iy >> 1)) * 4 + (ix >> 1) : ((t.n0 + sub) * 8 + iy) * 8 + ix;
-                const int j8 = ((lane & 3) ^ (hx & 2)) * 8;
+                const int j8 = ((lane & 3) ^ ((ix & 4) >> 1)) * 8;
                 hoff0[k] = ok ? (pix * p.C0 + j8) * 2 : -1;
                 hoff1[k] = ok ? (pix * p.C1 + j8) * 2 : -1;
             }
         };
         auto halo_issue = [&](int c, char* buf, int ka, int kb) {     // blocks ka .. kb-1 of this wave's share (compile-time range)
+            if (W8_DBG(2)) return;
             const int cbase = c * 32;
             const bool first = cbase < p.C0;
             const char* base = reinterpret_cast<const char*>(first ? p.in0 : p.in1) + (first ? cbase : cbase - p.C0) * 2;
@@ -406,8 +435,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                 const int blk = bw + 2 * k;
                 const int off = first ? hoff0[k] : hoff1[k];
                 const char* g = off >= 0 ? base + off : zero_page;
-                if (blk < W8_HALO_BLOCKS)
-                    __builtin_amdgcn_global_load_lds(W8_GPTR(g), W8_LPTR(buf + blk * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(W8_GPTR(g), W8_LPTR(buf + (blk >> 2) * W8_IMG + W8_ROW + (blk & 3) * 1024), 16, 0, 0);
             }
         };
         // output-tile pieces of this thread: L = k*128 + t2 (k = 0..15): pixel lp = k*16 + (t2 >> 3), cout piece (t2 & 7) ^ (lp & 7)
@@ -505,12 +533,12 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                 int young = 0;
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
-                    if (t < 7 && do_halo) halo_issue(hc, hbuf, 2 * t, 2 * t + 2);
+                    if (t < 6 && do_halo) halo_issue(hc, hbuf, t < 2 ? 2 * t : t + 2, t < 2 ? 2 * t + 2 : t + 3);    // 2, 2, 1, 1, 1, 1
                     if (t < 8) {
                         const int ka = k0 + t * pps < k1 ? k0 + t * pps : k1, kb = ka + pps < k1 ? ka + pps : k1;
                         if (ka < kb) {
                             const int n = tile_switch(prev, cur, ka, kb);
-                            if (t >= 6) young += n;              // issued after the last halo block of this chunk
+                            if (t >= 5) young += n;              // issued after the last halo block of this chunk
                         }
                     }
                     if (t == 8) {
@@ -518,7 +546,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                         if (wrap) w8_wait_vm(0);
                         else w8_wait_vm(young);
                     }
-                    if (t % 3 == 2) w8_barrier();                // end of a group step
+                    if (t % 3 == 2 && !(W8_DBG(4))) w8_barrier();                // end of a group step
                 }
             }
             w8_barrier();                                        // E1
@@ -569,7 +597,7 @@ bool conv_ws8_select(const ConvArgs& a, ConvPlan* p) {
     b.xcd_order = 1;
     p->kind = ConvKernel::ws8; p->t0 = a.gn_out != nullptr;
     p->grid = b.PT * b.CT < 256 ? b.PT * b.CT : 256;
-    p->lds = 2 * W8_HALO + W8_A_RING + W8_RO + W8_TB;
+    p->lds = 2 * W8_HALO + W8_STRIP + W8_A_RING + W8_RO + W8_TB;
     p->id = 400008;    // conv_ws8_kernel
     return true;
 }
@@ -579,6 +607,10 @@ int conv_ws8_launch(const ConvPlan& p, hipStream_t st) {
     DXMI_CHECK_ARG(conv_zero_page(zero_page, HIP_SYMBOL(w8_zero16)), "dxmi_conv2d_fwd(ws8): hipGetSymbolAddress(w8_zero16) failed");
     ConvArgs b = p.args;
     b.mask_src = reinterpret_cast<const bf16*>(zero_page);    // the field carries the zero page (a mask source travels in `residual`)
+#ifdef DXMI_CONV_STAMPS
+    static const int dbg = getenv("DXMI_CONV_WS8_DBG") ? atoi(getenv("DXMI_CONV_WS8_DBG")) : 0;
+    b.stagger = dbg;
+#endif
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws8_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
