@@ -14,7 +14,9 @@ truncating store errs by up to 2 u16, and by more than u16 for about half of all
 
     |got - act(ref64)| <= L c u32 A (1 + u16) + (u16 + 4 u32) |act(ref64)|
 
-An fp32-output conv (conv_out, NCHW fp32) drops the bf16 term.
+An fp32-output conv (conv_out, NCHW fp32) drops the bf16 term.  conv_call_ref forms reference and bound from the operands of one
+ops.conv2d call (activation mask, zero-stuffed upsampling and the stem's fp32 image included); the program-shape suite
+(test_hip_forward_shapes.py) and the edge-case suites (conv_checked / linear_checked, worst ratio per kernel family in EDGE) share it.
 
 Block statistics (sum, sum of squares per channel pair).  The kernels sum the STORED bf16 outputs; a bf16 square is exact
 in fp32.  One partial adds 2 * pixels-per-partial terms; a fold pass adds `group` partials; summing the remaining partials
@@ -73,6 +75,7 @@ four products and three sums are fp32: 8 u32 max|x| covers them.  With s = 2 whe
     |got - ref64| <= s (2 d D + 8 u32 max|x|) (1 + u16) + (u16 + 4 u32) |ref64|
 """
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -112,7 +115,8 @@ def store_bound(core, ref, bf16_out=True):
 # ------------------------------------------------------------------------------------------ conv
 def conv_fwd_ref(x, W, bias=None, addvec=None, residual=None, stride=1, pad=None, pad_br=None, upsample=0, chunk_bytes=1 << 29):
     """fp64 pre-activation conv and A = sum |w||x| + |fused adds|: x NHWC (concat applied, any dtype), W [Cout, Cin, k, k],
-    bias [Cout], addvec [N, Cout] (a shared row expanded by the caller), residual NHWC.  Computed a few images at a time."""
+    bias [Cout], addvec [N, Cout] (a shared row expanded by the caller), residual NHWC.  upsample 1: nearest x2 in front,
+    2: zero-stuffed x2 (dxmi_conv_desc.upsample).  Computed a few images at a time."""
     k = W.shape[2]
     pad = k // 2 if pad is None else pad
     pb = pad if pad_br is None else pad_br
@@ -127,7 +131,11 @@ def conv_fwd_ref(x, W, bias=None, addvec=None, residual=None, stride=1, pad=None
     per = max(1, chunk_bytes // (Cin * k * k * OH * OW * 8 * 2))
     for n0 in range(0, N, per):
         xd = x[n0:n0 + per].double()
-        if upsample:
+        if upsample == 2:
+            z = xd.new_zeros(xd.shape[0], VH, VW, Cin)
+            z[:, ::2, ::2] = xd
+            xd = z
+        elif upsample:
             xd = xd.repeat_interleave(2, 1).repeat_interleave(2, 2)
         cols = unfold_nhwc(xd, k, stride, pad, pb)                          # [n, Cin*k*k, OH*OW]
         out[n0:n0 + per] = torch.einsum("ok,nkp->npo", Wm, cols).reshape(-1, OH, OW, Co)
@@ -148,6 +156,62 @@ def conv_bound(ref_post, A, K, act, bf16_out=True):
     return store_bound(ACT_L[act] * (K + 3) * U32 * A, ref_post, bf16_out)
 
 
+class ConvRef(NamedTuple):
+    """conv_call_ref's result.  ref / bound: fp64, in the layout of the launch's output (NHWC, or NCHW for out_nchw_f32);
+    pre / A: the pre-activation value and its absolute sum, NHWC; K: the accumulation depth Cin * k * k (27 for the stem)."""
+    ref: torch.Tensor
+    bound: torch.Tensor
+    pre: torch.Tensor
+    A: torch.Tensor
+    K: int
+
+    def dh(self):
+        """Error of every stored bf16 element of an NHWC output, as gn_fused_bound takes it for a fused GroupNorm."""
+        return (self.K + 3) * U32 * self.A + U16 * self.ref.abs()
+
+
+def conv_call_ref(x0, W, x1=None, bias=None, addvec=None, residual=None, mask_src=None, mask_slope=0.0, act=0, stride=1, pad=None,
+                  pad_br=None, upsample=0, out_nchw_f32=False):
+    """fp64 reference and element-wise bound of one ops.conv2d launch, from the operands as the caller holds them (on whatever
+    device they are; the GPU suites pass device tensors, so the reference never goes through an fp32 library conv).
+
+    x0: NHWC bf16 (or the stem's NCHW fp32 image [N, 3, H, W], which the kernel stages as bf16: K = 27), x1 the optional concat
+    source; W [Cout, Cin, k, k] fp32, rounded to bf16 here exactly as ops.pack_conv_weight rounds it (idempotent for weights
+    that already are); bias [Cout]; addvec [N, Cout] or one shared row [Cout]; residual / mask_src NHWC bf16 shaped like the
+    output; stride, pad (top / left), pad_br (bottom / right, default pad), upsample 0 / 1 (nearest) / 2 (zero-stuffed).
+
+    Depth: the K = Cin k k products (zero padding and stuffed zeros add exact zeros) and the three fused adds, conv_bound's
+    K + 3, for every kernel family: each adds the K products of an output element and the fused terms once, in fp32, in
+    whatever order or grouping (no forward conv kernel keeps split-K partials in memory, so nothing is added twice or rounded
+    to another format on the way).  The activation mask multiplies the fp32 value by 1 or by the fp32 mask_slope before the
+    activation (conv_common.h epilogue; `res_is_mask` in conv_ws.hip / conv_ws8.hip / conv_sm.hip): the reference scales
+    value and magnitude by that factor, and the product's rounding is one more term of depth, K + 4.  The depth comes from
+    the kernels' code, never from a measured error: a launch beyond the bound is a finding about the kernel."""
+    if x0.dtype == torch.float32:
+        assert x1 is None and x0.shape[1] == 3, "an fp32 input is the stem's NCHW image"
+        xc = x0.to(torch.bfloat16).permute(0, 2, 3, 1)
+    else:
+        xc = torch.cat([x0, x1], 3) if x1 is not None else x0
+    N = xc.shape[0]
+    Wb = W.to(torch.bfloat16)
+    Cout, Cin, k, _ = Wb.shape
+    assert Cin == xc.shape[3], (Cin, xc.shape)
+    if addvec is not None and addvec.dim() == 1:
+        addvec = addvec[None].expand(N, Cout)
+    pre, A = conv_fwd_ref(xc, Wb, bias, addvec, residual, stride, pad, pad_br, upsample)
+    K = Cin * k * k
+    depth = K
+    if mask_src is not None:
+        slope = float(torch.tensor(mask_slope, dtype=torch.float32))
+        f = torch.where(mask_src.double() > 0, 1.0, slope)
+        pre, A, depth = pre * f, A * f, K + 1
+    ref = act64(pre, act)
+    bound = conv_bound(ref, A, depth, act, bf16_out=not out_nchw_f32)
+    if out_nchw_f32:
+        ref, bound = ref.permute(0, 3, 1, 2), bound.permute(0, 3, 1, 2)
+    return ConvRef(ref, bound, pre, A, K)
+
+
 def stats_ref(o, pairs=True):
     """Per image and channel pair of a stored NHWC tensor: (sum, sum of squares) and their absolute sums, fp64."""
     od = o.double()
@@ -160,6 +224,14 @@ def stats_ref(o, pairs=True):
 
 def stats_depth(HW, P0, folds):
     return 2 * -(-HW // P0) + 32 * folds + 2
+
+
+def fold_passes(P, group=32):
+    """Passes ops.fold_stats makes over P partials (each adds `group` consecutive partials)."""
+    n = 0
+    while P > 8:
+        P, n = -(-P // group), n + 1
+    return n
 
 
 # ------------------------------------------------------------------------------------------ GroupNorm
@@ -239,6 +311,109 @@ def linear_ref(x, W, bias, pre_act, post_act, depth=None):
     depth = K + 2 if depth is None else depth
     bound = ACT_L[post_act] * (depth * U32 * A + tie) + 4 * U32 * ref.abs()
     return ref, bound
+
+
+# ------------------------------------------------------------------------------------------ launches of the edge-case suites
+EDGE = FwdChecker()      # shared by the conv / linear edge-case modules: report() gives one worst |err| / bound per kernel family
+
+
+def conv_family(kid):
+    """Kernel family of a dxmi_conv2d_kernel_id value (the names bench.kernel_name groups them by)."""
+    if kid >= 600000:
+        return "head"
+    if kid >= 550000:
+        return "rw8"
+    if kid >= 500000:
+        return "rw"
+    if kid >= 450000:
+        return "sm"
+    if kid >= 400000:
+        return "ws8" if kid in (400008, 400009) else "ws"
+    if kid >= 300000:
+        return "stem"
+    if kid >= 200000:
+        return "stream1x1"
+    return "pipe" if kid >= 10000 else "igemm"
+
+
+def launch_conv(ops, x0, pw, **kw):
+    """ops.conv2d(x0, pw, **kw) -> (its result, the kernel id dxmi_conv2d_kernel_id names for the descriptor it launched)."""
+    import ctypes
+    kids = []
+
+    class Probe(ops.OpProfiler):
+        def launch_conv(self, d):
+            kids.append(int(ops.load().dxmi_conv2d_kernel_id(ctypes.byref(d))))
+            ops.check(ops.load().dxmi_conv2d_fwd(ctypes.byref(d), ops._stream()), "dxmi_conv2d_fwd")
+
+    old, ops.PROFILER = ops.PROFILER, Probe()
+    try:
+        res = ops.conv2d(x0, pw, **kw)
+    finally:
+        ops.PROFILER = old
+    assert len(kids) == 1, kids
+    return res, kids[0]
+
+
+def conv_checked(ops, x0, pw, W, check=None, **kw):
+    """ops.conv2d(x0, pw, **kw) with everything it writes judged element by element against fp64 (conv_call_ref of the same
+    operands; W: the fp32 weight pw was packed from, on any device), tagged conv[<family>] in `check` (default EDGE):
+    the raw output; with fuse_gn the fused GroupNorm output (around the stored raw tensor when it is kept, else with the raw
+    tensor's error propagated: gn_fused_bound; statistics depth = the group size, valid for any order); with want_stats the
+    block statistics of the stored output (stats_depth of the partial count the conv wrote, one fold pass where ops folded).
+    -> (the result of ops.conv2d, kernel id)."""
+    check = EDGE if check is None else check
+    seen, orig_fold = [], ops.fold_stats
+
+    def fold(st, group=32):
+        seen.append(st.P)
+        return orig_fold(st, group)
+
+    ops.fold_stats = fold
+    try:
+        res, kid = launch_conv(ops, x0, pw, **kw)
+    finally:
+        ops.fold_stats = orig_fold
+    fam = conv_family(kid)
+    fuse, want_stats = kw.get("fuse_gn"), kw.get("want_stats", False)
+    c = conv_call_ref(x0, W.to(x0.device), kw.get("in1"), kw.get("bias"), kw.get("addvec"), kw.get("residual"), kw.get("mask_src"),
+                      kw.get("mask_slope", 0.0), kw.get("act", 0), kw.get("stride", 1), kw.get("pad"), kw.get("pad_br"),
+                      int(kw.get("upsample", 0)), kw.get("out_nchw_f32", False))
+    out, st, y = res, None, None
+    if fuse is not None:
+        out, y = res
+    elif want_stats:
+        out, st = res
+    if out is not None:
+        check.within(f"conv[{fam}]", out, c.ref, c.bound)
+    if st is not None:
+        HW = out.shape[1] * out.shape[2]
+        P0 = seen[0] if seen else st.P
+        S, Sa = stats_ref(out)
+        check.fp32(f"block_stats[{fam}]", st.buf.double().sum(1), S, Sa, stats_depth(HW, P0, fold_passes(P0)))
+    if y is not None:
+        gamma, beta, groups, eps, silu, keep_raw = fuse
+        d = c.ref.shape[1] * c.ref.shape[2] * c.ref.shape[3] // groups
+        if out is not None:
+            yo, parts = gn_ref(out, gamma, beta, groups, eps, silu)
+            bnd = gn_bound(yo, parts, gamma, beta, d, silu)
+        else:
+            yo, parts = gn_ref(c.ref, gamma, beta, groups, eps, silu)
+            bnd = gn_fused_bound(yo, parts, gamma, beta, d, silu, c.dh())
+        check.within(f"conv_fused_gn[{fam}]", y, yo, bnd)
+    return res, kid
+
+
+def linear_checked(ops, x, pw, W, bias=None, pre_act=0, post_act=0, splitk=False, check=None):
+    """ops.linear under linear_ref's bound, tagged `linear` (`linear[splitk]` when the split-K form ran: its S partial sums
+    are added after the K products, depth K + 2 + S)."""
+    check = EDGE if check is None else check
+    got = ops.linear(x, pw, bias, pre_act=pre_act, post_act=post_act, splitk=splitk)
+    P, K = x.shape
+    S = int(ops.load().dxmi_linear_splitk_slices(P, K, pw.Cout)) if (splitk and post_act == 0) else 1
+    ref, bound = linear_ref(x, W.to(x.device), bias, pre_act, post_act, depth=K + 2 + (S if S > 1 else 0))
+    check.within("linear[splitk]" if S > 1 else "linear", got, ref, bound)
+    return got
 
 
 # ------------------------------------------------------------------------------------------ attention

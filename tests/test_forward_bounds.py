@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from backward_bounds import BoundError
-from forward_bounds import (LOG2E, FwdChecker, act64, attention_ref, attn_blocks, conv_bound, conv_fwd_ref, gn_bound, gn_ref,
+from forward_bounds import (LOG2E, FwdChecker, act64, attention_ref, attn_blocks, conv_bound, conv_call_ref, conv_fwd_ref, gn_bound, gn_ref,
                             linear_ref, lse_bound, stats_depth, stats_ref)
 from backward_bounds import U16
 
@@ -121,6 +121,72 @@ def test_conv_bound_rejects_the_wrong_source_and_stride2_padding_side():
     bound = conv_bound(ref, A, 256 * 9, 0)
     assert ck.within("conv_s2", conv_fp32(xs, Ws, bs, stride=2, pad=0, pad_br=1), ref, bound) <= 1.0
     must_reject(lambda: ck.within("conv_s2", conv_fwd_ref(xs, Ws, bs, stride=2, pad=1, pad_br=0)[0], ref, bound))
+
+
+def rel_l2(a, b):
+    return float((a.double() - b.double()).norm() / b.double().norm())
+
+
+def test_whole_tensor_rel_l2_passes_local_faults_the_bound_rejects():
+    """The criterion the conv edge tests used alone (rel-L2 < 4e-3 of the whole tensor against an fp32 conv of the same bf16
+    operands) against the element-wise bound of conv_call_ref, on 96 images of 32x32, 256 -> 64, 3x3 with bias, a per-image
+    vector and a residual.  The honest result (fp32 accumulation, one bf16 store) spends 1.7e-3 of the 4e-3; a stale pixel (one
+    pixel of the last image holding its left neighbour's values in every cout) and a missing K chunk (32 input channels left
+    out of 4 couts over 7 rows of the last image) fit into the rest, and are hundreds of bounds away element by element."""
+    g = torch.Generator().manual_seed(20)
+    N, H, Cin, Co = 96, 32, 256, 64
+    x = torch.randn(N, H, H, Cin, generator=g).to(torch.bfloat16)
+    W = torch.randn(Co, Cin, 3, 3, generator=g) * (Cin * 9) ** -0.5
+    bias, av = torch.randn(Co, generator=g), torch.randn(N, Co, generator=g)
+    res = torch.randn(N, H, H, Co, generator=g).to(torch.bfloat16)
+    Wb = W.to(torch.bfloat16).float()
+    conv32 = lambda xx, ww: F.conv2d(xx.float().permute(0, 3, 1, 2), ww, padding=1).permute(0, 2, 3, 1)
+    full = conv32(x, Wb) + bias + av[:, None, None, :] + res.float()              # the old reference
+    honest = full.to(torch.bfloat16)
+    stale = honest.clone()
+    stale[N - 1, 16, 16] = honest[N - 1, 16, 15]
+    part = conv32(x[N - 1:, 2:11, :, 32:64], Wb[8:12, 32:64])[0, 1:8]              # rows 3..9 from input rows 2..10
+    miss = full.clone()
+    miss[N - 1, 3:10, :, 8:12] -= part
+    miss = miss.to(torch.bfloat16)
+    c = conv_call_ref(x, W, None, bias, av, res)
+    ck = FwdChecker()
+    assert ck.within("conv", honest, c.ref, c.bound) <= 1.0
+    for bad in (stale, miss):
+        assert rel_l2(honest, full) < rel_l2(bad, full) < 4e-3
+        must_reject(lambda: ck.within("conv", bad, c.ref, c.bound))
+
+
+def test_conv_call_ref_terms():
+    """conv_call_ref against direct fp64 restatements: the shared addvec row, the activation mask (and that a dropped mask is
+    rejected), zero-stuffed and nearest upsampling, the stem's fp32 image, NCHW fp32 output, unrounded weights."""
+    g = torch.Generator().manual_seed(21)
+    N, H, C, Co = 2, 8, 32, 16
+    x = torch.randn(N, H, H, C, generator=g).to(torch.bfloat16)
+    W = torch.randn(Co, C, 3, 3, generator=g) * (C * 9) ** -0.5
+    row = torch.randn(Co, generator=g)
+    m = torch.randn(N, H, H, Co, generator=g).to(torch.bfloat16)
+    Wd = W.to(torch.bfloat16).double()
+    conv64 = lambda xx, **kw: F.conv2d(xx.double().permute(0, 3, 1, 2), Wd, **kw).permute(0, 2, 3, 1)
+    c = conv_call_ref(x, W, addvec=row, mask_src=m, mask_slope=0.2, act=1)
+    slope = float(torch.tensor(0.2, dtype=torch.float32))
+    pre = (conv64(x, padding=1) + row.double()) * torch.where(m.double() > 0, 1.0, slope)
+    assert torch.allclose(c.ref, act64(pre, 1), rtol=1e-12, atol=1e-12) and c.K == C * 9
+    ck = FwdChecker()
+    assert ck.within("mask", bf(c.ref.float()), c.ref, c.bound) <= 1.0
+    must_reject(lambda: ck.within("mask", bf(act64(conv64(x, padding=1) + row.double(), 1).float()), c.ref, c.bound))
+    z = torch.zeros(N, 2 * H, 2 * H, C, dtype=torch.float64)
+    z[:, ::2, ::2] = x.double()
+    assert torch.allclose(conv_call_ref(x, W, upsample=2, pad=2, pad_br=0).ref, conv64(F.pad(z, (0, 0, 2, 0, 2, 0))), rtol=1e-12, atol=1e-12)
+    up = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    assert torch.allclose(conv_call_ref(x, W, upsample=1).ref, conv64(up, padding=1), rtol=1e-12, atol=1e-12)
+    c = conv_call_ref(x, W, out_nchw_f32=True)
+    assert c.ref.shape == (N, Co, H, H) and torch.equal(c.ref, c.pre.permute(0, 3, 1, 2))
+    assert torch.equal(c.bound, conv_bound(c.pre, c.A, c.K, 0, bf16_out=False).permute(0, 3, 1, 2))
+    img = torch.randn(N, 3, H, H, generator=g)
+    W3 = torch.randn(Co, 3, 3, 3, generator=g) * 27 ** -0.5
+    c = conv_call_ref(img, W3)
+    assert c.K == 27 and torch.allclose(c.ref, F.conv2d(bf(img), bf(W3), padding=1).permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
 
 
 def test_stats_bound_rejects_a_dropped_partial():

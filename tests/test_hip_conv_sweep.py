@@ -1,12 +1,15 @@
 """Seeded sweep over conv / linear shapes on the GPU (edge cases of the tile dispatch: ragged batches, cout tiles that are
 half empty, every kernel family — pipelined 3x3, stride 2, upsampled, streaming 1x1, stem, small GEMM) against torch fp32
-on the same bf16-rounded operands.  Tolerance: one bf16 rounding of the output (rel-L2 <= 4e-3)."""
+on the same bf16-rounded operands.  Tolerance: one bf16 rounding of the output (rel-L2 <= 4e-3), and every launch element by
+element against fp64 within the derived bound (forward_bounds.conv_checked / linear_checked, one tag per kernel family)."""
 import math
 import random
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+from forward_bounds import conv_checked, linear_checked
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -80,8 +83,8 @@ def test_conv_sweep(ops, N, C0, C1, Cout, H, k, stride, ups, fuse):
     if "act" in fuse:
         ref = F.leaky_relu(ref, 0.2)
         kw["act"] = ops.ACT_LEAKY02
-    y = ops.conv2d(nhwc(x[:, :C0]), ops.pack_conv_weight(w.to(DEV)), in1=nhwc(x[:, C0:]) if C1 else None,
-                   bias=b.to(DEV) if "bias" in fuse else None, stride=stride, pad=k // 2, upsample=ups, **kw)
+    y, _ = conv_checked(ops, nhwc(x[:, :C0]), ops.pack_conv_weight(w.to(DEV)), w, in1=nhwc(x[:, C0:]) if C1 else None,
+                        bias=b.to(DEV) if "bias" in fuse else None, stride=stride, pad=k // 2, upsample=ups, **kw)
     torch.cuda.synchronize()
     assert nchw(y).shape == ref.shape
     assert rel_l2(nchw(y), ref) < 4e-3
@@ -96,7 +99,8 @@ def test_stem_conv_sweep(ops, N, Cout, H, act):
     ref = F.conv2d(bf(x), w, b, padding=1)
     if act:
         ref = F.leaky_relu(ref, 0.2)
-    y = ops.conv2d(x.to(DEV), ops.pack_conv_weight(w.to(DEV), k27=True), bias=b.to(DEV), act=ops.ACT_LEAKY02 if act else ops.ACT_NONE)
+    y, _ = conv_checked(ops, x.to(DEV), ops.pack_conv_weight(w.to(DEV), k27=True), w, bias=b.to(DEV),
+                        act=ops.ACT_LEAKY02 if act else ops.ACT_NONE)
     assert rel_l2(nchw(y), ref) < 4e-3
 
 
@@ -107,5 +111,5 @@ def test_linear_sweep(ops, P, K, M):
     w = bf(torch.randn(M, K, generator=g) / math.sqrt(K))
     b = torch.randn(M, generator=g)
     ref = F.linear(bf(F.silu(x)), w, b)
-    got = ops.linear(x.to(DEV), ops.pack_conv_weight(w.to(DEV)), b.to(DEV), pre_act=ops.ACT_SILU).cpu()
+    got = linear_checked(ops, x.to(DEV), ops.pack_conv_weight(w.to(DEV)), w, b.to(DEV), pre_act=ops.ACT_SILU).cpu()
     assert rel_l2(got, ref) < 2e-3

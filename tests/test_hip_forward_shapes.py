@@ -25,8 +25,8 @@ import pytest
 import torch
 
 from backward_bounds import U16, U32, dropout_ref, groupnorm_bwd_ref, td_loss_ref
-from forward_bounds import (FwdChecker, act64, attention_ref, attn_blocks, conv_bound, conv_fwd_ref, dsm_error_terms,
-                            dsm_loss_fwd_bound, edm_step_ref, gn_bound, gn_fused_bound, gn_ref, linear_ref, log_sigma_t, lse_bound,
+from forward_bounds import (FwdChecker, attention_ref, attn_blocks, conv_call_ref, dsm_error_terms,
+                            dsm_loss_fwd_bound, edm_step_ref, fold_passes, gn_bound, gn_fused_bound, gn_ref, linear_ref, log_sigma_t, lse_bound,
                             pool_act_ref, scaled_input_ref, stats_depth, stats_ref, store_bound, td_gather_cost_ref, var_step_ref)
 
 DEV = "cuda:0"
@@ -1433,14 +1433,6 @@ EXTRA = [
 ATTN_KERNELS = {"attention_kernel<64>", "attention_kernel<128>", "attention_kernel<256>", "attention64", "attention256<false>"}
 
 
-def fold_passes(P, group=32):
-    """Passes ops.fold_stats makes over P partials (each adds `group` consecutive partials)."""
-    n = 0
-    while P > 8:
-        P, n = -(-P // group), n + 1
-    return n
-
-
 def _rows(op):
     return sorted({r for r in CASES if r[0] == op} | {r for r in EXTRA if r[0] == op}, key=repr)
 
@@ -1657,13 +1649,11 @@ def test_conv_fwd(ops, r):
         out, y = res_
     elif want_stats:
         out, st = res_
-    pre, A = conv_fwd_ref(xc, bf(W).float(), bias, avx, res, stride, pad, pad_br, ups)
-    ref = act64(pre, act)
-    K = 27 if k27 else Cin * k * k
+    cr = conv_call_ref(x0, W, x1, bias, av, res, act=act, stride=stride, pad=pad, pad_br=pad_br, upsample=ups, out_nchw_f32=nchw)
+    assert cr.K == (27 if k27 else Cin * k * k)
     name = f"conv2d[{r[-1]}]"
     if out is not None:
-        got = out.permute(0, 2, 3, 1) if nchw else out
-        CHECK.within(name, got, ref, conv_bound(ref, A, K, act, bf16_out=not nchw))
+        CHECK.within(name, out, cr.ref, cr.bound)
     if st is not None:
         assert st.P == P
         S, Sa = stats_ref(out)
@@ -1677,9 +1667,8 @@ def test_conv_fwd(ops, r):
             yo, parts = gn_ref(out, gamma, beta, groups, 1e-6, silu)
             bnd = gn_bound(yo, parts, gamma, beta, out.shape[1] * out.shape[2] * Cout // groups, silu)
         else:
-            yo, parts = gn_ref(ref, gamma, beta, groups, 1e-6, silu)
-            dh = (K + 3) * U32 * A + U16 * ref.abs()
-            bnd = gn_fused_bound(yo, parts, gamma, beta, ref.shape[1] * ref.shape[2] * Cout // groups, silu, dh)
+            yo, parts = gn_ref(cr.ref, gamma, beta, groups, 1e-6, silu)
+            bnd = gn_fused_bound(yo, parts, gamma, beta, cr.ref.shape[1] * cr.ref.shape[2] * Cout // groups, silu, cr.dh())
         CHECK.within("conv2d_fused_gn", y, yo, bnd)
 
 
@@ -2165,8 +2154,9 @@ def test_groupnorm_silu_shortcut(ops, r):
     y, sc = res
     yo, parts = gn_ref(xc, gamma, beta, groups, eps, silu, None)
     CHECK.within("gn_shortcut_y", y, yo, gn_bound(yo, parts, gamma, beta, max(P0, P1) + C // groups // 2 + 2, silu))
-    ref, A = conv_fwd_ref(xc, bf(Wt).float(), bias=bias)
-    CHECK.within("gn_shortcut_conv", sc, ref, conv_bound(ref, A, C, 0))
+    c = conv_call_ref(x0, Wt, x1, bias)
+    assert c.K == C
+    CHECK.within("gn_shortcut_conv", sc, c.ref, c.bound)
 
 
 @pytest.mark.gpu

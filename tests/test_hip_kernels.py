@@ -1,13 +1,16 @@
 """Per-kernel numerics of the HIP library against fp32 torch-CPU restatements of the same op.
 
 Inputs are rounded to bf16 first, so the only differences are accumulation order and the final
-bf16 rounding of the output: tolerances are stated per test.
+bf16 rounding of the output: tolerances are stated per test.  Every conv and linear launch is also judged element by element
+against fp64 within the derived bound (forward_bounds.conv_checked / linear_checked, one tag per kernel family).
 """
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+from forward_bounds import conv_checked, linear_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -69,7 +72,7 @@ def test_conv2d(ops, N, Cin, Cout, H, k, stride, ups, variant):
         ref = F.conv2d(xi, w, b, padding=k // 2)
         pad, pad_br = k // 2, k // 2
     pw = ops.pack_conv_weight(w.to(DEV))
-    y = ops.conv2d(nhwc(x), pw, bias=b.to(DEV), stride=stride, pad=pad, pad_br=pad_br, upsample=ups, variant=variant)
+    y, _ = conv_checked(ops, nhwc(x), pw, w, bias=b.to(DEV), stride=stride, pad=pad, pad_br=pad_br, upsample=ups, variant=variant)
     torch.cuda.synchronize()
     got = nchw(y)
     assert got.shape == ref.shape
@@ -91,8 +94,8 @@ def test_conv2d_epilogue_fusions(ops):
     ref = F.leaky_relu(ref, 0.2)
     pw = ops.pack_conv_weight(w.to(DEV))
     tvd = tv.to(DEV)
-    y = ops.conv2d(nhwc(x0), pw, in1=nhwc(x1), bias=b.to(DEV), addvec=tvd[:, Cout:2 * Cout], residual=nhwc(res),
-                   act=ops.ACT_LEAKY02)
+    y, _ = conv_checked(ops, nhwc(x0), pw, w, in1=nhwc(x1), bias=b.to(DEV), addvec=tvd[:, Cout:2 * Cout], residual=nhwc(res),
+                        act=ops.ACT_LEAKY02)
     got = nchw(y)
     assert rel_l2(got, ref) < 4e-3
 
@@ -106,7 +109,7 @@ def test_conv2d_k27_image_conv(ops):
     b = torch.randn(Cout, generator=g)
     ref = F.conv2d(bf(x), w, b, padding=1)
     pw = ops.pack_conv_weight(w.to(DEV), k27=True)
-    y = ops.conv2d(x.to(DEV), pw, bias=b.to(DEV))
+    y, _ = conv_checked(ops, x.to(DEV), pw, w, bias=b.to(DEV))
     assert rel_l2(nchw(y), ref) < 4e-3
 
 
@@ -118,7 +121,7 @@ def test_conv2d_nchw_f32_out(ops):
     b = torch.randn(3, generator=g)
     ref = F.conv2d(x, w, b, padding=1)
     pw = ops.pack_conv_weight(w.to(DEV))
-    y = ops.conv2d(nhwc(x), pw, bias=b.to(DEV), out_nchw_f32=True)
+    y, _ = conv_checked(ops, nhwc(x), pw, w, bias=b.to(DEV), out_nchw_f32=True)
     assert y.shape == (N, 3, H, H) and y.dtype == torch.float32
     # fp32 output: only accumulation-order noise
     assert rel_l2(y.cpu(), ref) < 1e-5
@@ -133,7 +136,7 @@ def test_conv2d_dgrad_packing(ops):
     x = torch.zeros(N, Cin, H, H, requires_grad=True)
     F.conv2d(x, w, padding=1).backward(gy)
     pw = ops.pack_conv_weight(w.to(DEV), transpose_flip=True)
-    gx = ops.conv2d(nhwc(gy), pw)
+    gx, _ = conv_checked(ops, nhwc(gy), pw, w.transpose(0, 1).flip(2, 3).contiguous())      # the operator the packing forms
     assert rel_l2(nchw(gx), x.grad) < 4e-3
 
 
@@ -213,7 +216,7 @@ def test_linear(ops, P, K, M):
     b = torch.randn(M, generator=g)
     ref = F.silu(F.linear(bf(F.silu(x)), w, b))
     pw = ops.pack_conv_weight(w.to(DEV))
-    got = ops.linear(x.to(DEV), pw, b.to(DEV), pre_act=ops.ACT_SILU, post_act=ops.ACT_SILU).cpu()
+    got = linear_checked(ops, x.to(DEV), pw, w, b.to(DEV), pre_act=ops.ACT_SILU, post_act=ops.ACT_SILU).cpu()
     assert rel_l2(got, ref) < 2e-3, rel_l2(got, ref)
 
 
@@ -231,9 +234,12 @@ def test_linear_long_k_split(ops, P, K, M, bias):
     b = torch.randn(M, generator=g) if bias else None
     ref = F.linear(bf(x), w, b)
     pw = ops.pack_conv_weight(w.to(DEV))
-    got = ops.linear(x.to(DEV), pw, b.to(DEV) if bias else None)
+    got = linear_checked(ops, x.to(DEV), pw, w, b.to(DEV) if bias else None)
     assert rel_l2(got.cpu(), ref) < 2e-3, rel_l2(got.cpu(), ref)
     assert torch.equal(got, ops.linear(x.to(DEV), pw, b.to(DEV) if bias else None))
+    # the split-K form itself (ops.linear takes it only when asked: the training backward does): S partial sums more in the depth
+    sk = linear_checked(ops, x.to(DEV), pw, w, b.to(DEV) if bias else None, splitk=True)
+    assert rel_l2(sk.cpu(), ref) < 2e-3 and torch.equal(sk, ops.linear(x.to(DEV), pw, b.to(DEV) if bias else None, splitk=True))
 
 
 def test_var_step_and_gather(ops):

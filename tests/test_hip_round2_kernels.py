@@ -1,12 +1,15 @@
 """Round-2 kernels at the shapes that select them (conv_ws_kernel, conv1x1_rw_kernel, attention256_kernel), against torch fp32
 on the same bf16-rounded operands: persistent loops with uneven tile counts per workgroup, single-tile launches, channel
 concat, upsample, every fused epilogue term, plus run-to-run determinism and batch independence.  The kernel each case runs is
-asserted through dxmi_conv2d_kernel_id.  Tolerance: one bf16 rounding of the output (rel-L2 <= 4e-3)."""
+asserted through dxmi_conv2d_kernel_id.  Tolerance: one bf16 rounding of the output (rel-L2 <= 4e-3), and every conv launch
+element by element against fp64 within the derived bound (forward_bounds.conv_checked, one tag per kernel family)."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+from forward_bounds import conv_checked, launch_conv
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -46,11 +49,13 @@ def rel_l2(a, b):
     return ((a - b).norm() / (b.norm() + 1e-30)).item()
 
 
-def run_conv(ops, N, C0, C1, Cout, H, k, ups, fuse, seed=0):
-    """-> (output NHWC bf16 on the device, fp32 reference NCHW, kernel id)"""
-    g = torch.Generator().manual_seed(seed + N * 1000003 + C0 * 131 + C1 * 17 + Cout * 7 + H + k)
+def run_conv(ops, N, C0, C1, Cout, H, k, ups, fuse, seed=0, W=None, judge=True):
+    """-> (output NHWC bf16 on the device, fp32 reference NCHW, kernel id); H x W input map (W defaults to H).  judge: the
+    launch is also judged element by element against fp64 (conv_checked; off for the repeat of a launch already judged)."""
+    W = H if W is None else W
+    g = torch.Generator().manual_seed(seed + N * 1000003 + C0 * 131 + C1 * 17 + Cout * 7 + H + k + (0 if W == H else 31 * W))
     Cin = C0 + C1
-    x = bf(torch.randn(N, Cin, H, H, generator=g))
+    x = bf(torch.randn(N, Cin, H, W, generator=g))
     w = bf(torch.randn(Cout, Cin, k, k, generator=g) / math.sqrt(Cin * k * k))
     b = torch.randn(Cout, generator=g)
     xd = x.to(DEV)
@@ -68,15 +73,11 @@ def run_conv(ops, N, C0, C1, Cout, H, k, ups, fuse, seed=0):
     if "act" in fuse:
         ref = F.leaky_relu(ref, 0.2)
         kw["act"] = ops.ACT_LEAKY02
-    prof = ops.OpProfiler()
-    ops.PROFILER = prof
-    try:
-        y = ops.conv2d(nhwc(x[:, :C0]), ops.pack_conv_weight(w.to(DEV)), in1=nhwc(x[:, C0:]) if C1 else None,
-                       bias=b.to(DEV) if "bias" in fuse else None, pad=k // 2, upsample=ups, **kw)
-    finally:
-        ops.PROFILER = None
+    run = conv_checked if judge else (lambda ops, x0, pw, w, **kw: launch_conv(ops, x0, pw, **kw))
+    y, kid = run(ops, nhwc(x[:, :C0]), ops.pack_conv_weight(w.to(DEV)), w, in1=nhwc(x[:, C0:]) if C1 else None,
+                 bias=b.to(DEV) if "bias" in fuse else None, pad=k // 2, upsample=ups, **kw)
     torch.cuda.synchronize()
-    return y, ref.cpu(), prof.records[-1][1]
+    return y, ref.cpu(), kid
 
 
 # (N, C0, C1, Cout, H, ups, fuse): 3x3 shapes in conv_ws_kernel's scope
@@ -122,7 +123,7 @@ def test_conv_ws8(ops, N, C0, C1, Cout, fuse):
     y, ref, kid = run_conv(ops, N, C0, C1, Cout, 8, 3, False, fuse)
     assert kid == 400008, f"expected conv_ws8_kernel, got kernel id {kid}"
     assert rel_l2(nchw(y), ref) < 4e-3
-    y2, _, _ = run_conv(ops, N, C0, C1, Cout, 8, 3, False, fuse)
+    y2, _, _ = run_conv(ops, N, C0, C1, Cout, 8, 3, False, fuse, judge=False)
     assert torch.equal(y, y2)
 
 
@@ -144,7 +145,43 @@ def test_conv_ws8_upsample(ops, N):
     y, ref, kid = run_conv(ops, N, 256, 0, 256, 4, 3, True, "bias")
     assert kid == 400008, f"expected conv_ws8_kernel, got kernel id {kid}"
     assert rel_l2(nchw(y), ref) < 4e-3
-    y2, _, _ = run_conv(ops, N, 256, 0, 256, 4, 3, True, "bias")
+    y2, _, _ = run_conv(ops, N, 256, 0, 256, 4, 3, True, "bias", judge=False)
+    assert torch.equal(y, y2)
+
+
+def test_conv_ws_upsample_with_concat(ops):
+    """Nearest x2 upsample in front TOGETHER with a concat input on conv_ws_kernel<32> (16x16 -> 32x32, 128 + 128 -> 128): the
+    halo mover halves the tile origin and the halo offsets inside either source part."""
+    y, ref, kid = run_conv(ops, 3, 128, 128, 128, 16, 3, True, "bias+res+vec")
+    assert kid == 400032, f"expected conv_ws_kernel<32>, got kernel id {kid}"
+    assert rel_l2(nchw(y), ref) < 4e-3
+    y2, _, _ = run_conv(ops, 3, 128, 128, 128, 16, 3, True, "bias+res+vec", judge=False)
+    assert torch.equal(y, y2)
+
+
+def test_conv_ws8_upsample_with_concat_and_ragged_tile(ops):
+    """Upsample 4x4 -> 8x8 with a concat input on conv_ws8_kernel, six images (the second tile holds two), one 64-cout tile."""
+    y, ref, kid = run_conv(ops, 6, 128, 128, 64, 4, 3, True, "bias+res+vec")
+    assert kid == 400008, f"expected conv_ws8_kernel, got kernel id {kid}"
+    assert rel_l2(nchw(y), ref) < 4e-3
+    y2, _, _ = run_conv(ops, 6, 128, 128, 64, 4, 3, True, "bias+res+vec", judge=False)
+    assert torch.equal(y, y2)
+
+
+# OH != OW (conv_plan takes any power-of-two OH, OW >= 4; every kernel below forms its tile grid from OH / TH and OW / TW and
+# indexes rows by OW / IW, images by OH * OW / IH * IW, with the halo's zero sides decided per axis): 3 images, 128 -> 128.
+# 3x3: 32x16 is two 16x16 tiles of conv_ws_kernel<16> one above the other, 16x32 two 8x32 tiles of conv_ws_kernel<32>; 8x4 and
+# 4x8 are 64-pixel tiles of two images on conv_pipe_kernel (the second tile holds one image).  1x1: conv1x1_stream_kernel.
+NONSQUARE = [(32, 16, 3, 400016), (16, 32, 3, 400032), (8, 4, 3, 30206), (4, 8, 3, 30206),
+             (32, 16, 1, 200000), (16, 32, 1, 200000), (8, 4, 1, 200000), (4, 8, 1, 200000)]
+
+
+@pytest.mark.parametrize("H,W,k,want", NONSQUARE)
+def test_conv_nonsquare_maps(ops, H, W, k, want):
+    y, ref, kid = run_conv(ops, 3, 128, 0, 128, H, k, False, "bias+res+vec", W=W)
+    assert kid == want, f"{H}x{W} k{k}: expected kernel id {want}, got {kid}"
+    assert tuple(y.shape) == (3, H, W, 128) and rel_l2(nchw(y), ref) < 4e-3
+    y2, _, _ = run_conv(ops, 3, 128, 0, 128, H, k, False, "bias+res+vec", W=W, judge=False)
     assert torch.equal(y, y2)
 
 
@@ -190,8 +227,9 @@ def test_wide_8x8_layers_take_the_feed_tiled_kernel(ops):
             assert rel_l2(nchw(y), ref) < 4e-3
         g = torch.Generator().manual_seed(77)
         x = torch.randn(16, 8, 8, 1024, generator=g).to(torch.bfloat16).to(DEV)
-        pw = ops.pack_conv_weight((torch.randn(1024, 1024, 3, 3, generator=g) * 0.01).to(DEV))
-        full = ops.conv2d(x, pw)
+        w = torch.randn(1024, 1024, 3, 3, generator=g) * 0.01
+        pw = ops.pack_conv_weight(w.to(DEV))
+        full, _ = conv_checked(ops, x, pw, w)
         assert torch.equal(ops.conv2d(x[5:8].contiguous(), pw), full[5:8])
     finally:
         ops.set_tuning("conv_ws_min_tiles", old[0])
@@ -216,18 +254,19 @@ def test_round2_convs_deterministic_and_batch_independent(ops, N, C0, C1, Cout, 
     """bitwise: the same launch twice; and image i of a batch does not depend on the rest of the batch (persistent loops, DMA
     rings and LDS tiles carry no state across tiles)"""
     y1, _, _ = run_conv(ops, N, C0, C1, Cout, H, k, False, fuse)
-    y2, _, _ = run_conv(ops, N, C0, C1, Cout, H, k, False, fuse)
+    y2, _, _ = run_conv(ops, N, C0, C1, Cout, H, k, False, fuse, judge=False)
     assert torch.equal(y1, y2)
     # same operands, batch cut to the first M images (run_conv seeds by N, so rebuild the operands by hand)
     g = torch.Generator().manual_seed(7)
     Cin = C0 + C1
     x = bf(torch.randn(N, Cin, H, H, generator=g))
-    pw = ops.pack_conv_weight(bf(torch.randn(Cout, Cin, k, k, generator=g) / math.sqrt(Cin * k * k)).to(DEV))
+    w = bf(torch.randn(Cout, Cin, k, k, generator=g) / math.sqrt(Cin * k * k))
+    pw = ops.pack_conv_weight(w.to(DEV))
     b = torch.randn(Cout, generator=g).to(DEV)
     res = nhwc(bf(torch.randn(N, Cout, H, H, generator=g)))
     x0, x1 = nhwc(x[:, :C0]), (nhwc(x[:, C0:]) if C1 else None)
     M = N // 2 + (1 if k == 3 else 0)      # the cut batch stays in the same kernel's scope
-    full = ops.conv2d(x0, pw, in1=x1, bias=b, residual=res, pad=k // 2)
+    full, _ = conv_checked(ops, x0, pw, w, in1=x1, bias=b, residual=res, pad=k // 2)
     part = ops.conv2d(x0[:M].contiguous(), pw, in1=x1[:M].contiguous() if C1 else None, bias=b, residual=res[:M].contiguous(), pad=k // 2)
     torch.cuda.synchronize()
     assert torch.equal(full[:M], part)
@@ -260,15 +299,10 @@ def test_conv_head(ops, N, H, Cout):
     w = bf(torch.randn(Cout, 128, 3, 3, generator=g) / math.sqrt(128 * 9))
     b = torch.randn(Cout, generator=g)
     ref = F.conv2d(x, w, b, padding=1)
-    prof = ops.OpProfiler()
-    ops.PROFILER = prof
-    try:
-        y = ops.conv2d(nhwc(x), ops.pack_conv_weight(w.to(DEV)), bias=b.to(DEV), out_nchw_f32=True)
-        y2 = ops.conv2d(nhwc(x), ops.pack_conv_weight(w.to(DEV)), bias=b.to(DEV), out_nchw_f32=True)
-    finally:
-        ops.PROFILER = None
+    y, kid = conv_checked(ops, nhwc(x), ops.pack_conv_weight(w.to(DEV)), w, bias=b.to(DEV), out_nchw_f32=True)
+    y2 = ops.conv2d(nhwc(x), ops.pack_conv_weight(w.to(DEV)), bias=b.to(DEV), out_nchw_f32=True)
     torch.cuda.synchronize()
-    assert prof.records[-1][1] == 600000, prof.records[-1][1]
+    assert kid == 600000, kid
     assert y.dtype == torch.float32 and tuple(y.shape) == tuple(ref.shape)
     assert torch.equal(y, y2)
     assert rel_l2(y.cpu(), ref) < 2e-3      # fp32 output: only the bf16 operands' products, fp32 accumulation

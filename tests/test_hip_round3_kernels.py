@@ -1,8 +1,12 @@
 """Round-3 kernels through the C-ABI: GroupNorm block statistics from the conv epilogue (dxmi_conv_desc.gn_stats) and from
-the statistics kernel, the streaming GroupNorm apply pass, and the U-Net forward on that path against the one-pass path."""
+the statistics kernel, the streaming GroupNorm apply pass, and the U-Net forward on that path against the one-pass path.
+Every conv launch is also judged element by element against fp64 within the derived bound (forward_bounds.conv_checked: the raw
+output, the block statistics, the fused GroupNorm output), one tag per kernel family."""
 import pytest
 import torch
 import torch.nn.functional as F
+
+from forward_bounds import conv_checked
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -66,12 +70,14 @@ def test_conv_epilogue_block_stats(ops, N, C0, C1, Cout, H, ups, res):
     IH = H // 2 if ups else H
     x0 = torch.randn(N, IH, IH, C0, generator=g).to(torch.bfloat16).to(DEV)
     x1 = torch.randn(N, IH, IH, C1, generator=g).to(torch.bfloat16).to(DEV) if C1 else None
-    pw = ops.pack_conv_weight((torch.randn(Cout, C0 + C1, 3, 3, generator=g) * 0.03).to(DEV))
+    w = torch.randn(Cout, C0 + C1, 3, 3, generator=g) * 0.03
+    pw = ops.pack_conv_weight(w.to(DEV))
     bias = torch.randn(Cout, generator=g).to(DEV)
     temb = torch.randn(N, Cout, generator=g).to(DEV)
     r = torch.randn(N, H, H, Cout, generator=g).to(torch.bfloat16).to(DEV) if res else None
     kw = dict(in1=x1, bias=bias, addvec=temb, residual=r, upsample=ups)
-    y, st = ops.conv2d(x0, pw, want_stats=True, **kw)
+    (y, st), kid = conv_checked(ops, x0, pw, w, want_stats=True, **kw)
+    assert kid == (400016 if H == 16 else 400032), kid
     assert st is not None and st.P == (2 if H == 16 else 8) and tuple(st.buf.shape) == (N, st.P, Cout // 2, 2)
     y_plain = ops.conv2d(x0, pw, **kw)
     assert torch.equal(y, y_plain)
@@ -219,7 +225,7 @@ def test_conv_sm_4x4(ops, N, C0, C1, Cout, res, temb, bias, act):
     tv = torch.randn(N, Cout, generator=g).to(DEV) if temb else None
     r = torch.randn(N, 4, 4, Cout, generator=g).to(torch.bfloat16).to(DEV) if res else None
     kw = dict(in1=x1, bias=bv, addvec=tv, residual=r, act=act)
-    y = ops.conv2d(x0, pw, **kw)
+    y, _ = conv_checked(ops, x0, pw, w, **kw)
     ref = _conv_ref(x0, x1, w, bv, tv, r, act)
     rel = ((y.float().cpu() - ref).norm() / ref.norm()).item()
     assert rel < 4e-3, rel
@@ -290,9 +296,10 @@ def test_conv_sm_fused_groupnorm(ops, N, C0, C1, res, silu):
     beta = (0.3 * torch.randn(Cout, generator=g)).to(DEV)
     kw = dict(in1=x1, bias=bv, addvec=tv, residual=r)
     raw = ops.conv2d(x0, pw, **kw)
-    out, y = ops.conv2d(x0, pw, fuse_gn=(gamma, beta, 32, 1e-6, silu, True), **kw)
+    (out, y), kid = conv_checked(ops, x0, pw, w, fuse_gn=(gamma, beta, 32, 1e-6, silu, True), **kw)
+    assert kid == 450432, kid
     assert y is not None and torch.equal(out, raw)                  # the raw tensor is unchanged by the fusion
-    none, y2 = ops.conv2d(x0, pw, fuse_gn=(gamma, beta, 32, 1e-6, silu, False), **kw)
+    (none, y2), _ = conv_checked(ops, x0, pw, w, fuse_gn=(gamma, beta, 32, 1e-6, silu, False), **kw)
     assert none is None and torch.equal(y, y2)
     # against the separate launch on the same stored tensor: same formula, statistics summed in another order -> bf16 ulps
     sep = ops.groupnorm_silu(raw, gamma, beta, groups=32, eps=1e-6, silu=silu)
@@ -355,7 +362,7 @@ def test_attention_proj_fused(ops, N):
     y = ops.attention_proj(qkv, ops.pack_attn_proj_weight(w), b, x, heads=1, scale=scale)
     # the unfused pair
     a = ops.attention(qkv, heads=1, scale=scale)
-    sep = ops.conv2d(a.view(N, 16, 16, C), ops.pack_conv_weight(w), bias=b, residual=x.view(N, 16, 16, C)).view(N, T, C)
+    sep = conv_checked(ops, a.view(N, 16, 16, C), ops.pack_conv_weight(w), w, bias=b, residual=x.view(N, 16, 16, C))[0].view(N, T, C)
     d = (y.float() - sep.float()).abs()
     assert d.max().item() <= 2 ** -6 * max(1.0, sep.float().abs().max().item()), d.max().item()
     assert (d > 0).float().mean().item() < 0.02          # same operands; only the order inside a 16-channel MFMA step differs
@@ -395,8 +402,9 @@ def test_conv_ws8_fused_groupnorm(ops, N, C0, C1, res, silu):
     gamma = (1 + 0.3 * torch.randn(Cout, generator=g)).to(DEV)
     beta = (0.3 * torch.randn(Cout, generator=g)).to(DEV)
     kw = dict(in1=x1, bias=bv, addvec=tv, residual=r)
-    raw = ops.conv2d(x0, pw, **kw)
-    none, y = ops.conv2d(x0, pw, fuse_gn=(gamma, beta, 32, 1e-6, silu, False), **kw)
+    raw, kid = conv_checked(ops, x0, pw, w, **kw)
+    assert kid == 400008, kid
+    (none, y), _ = conv_checked(ops, x0, pw, w, fuse_gn=(gamma, beta, 32, 1e-6, silu, False), **kw)
     assert none is None and y is not None
     sep = ops.groupnorm_silu(raw, gamma, beta, groups=32, eps=1e-6, silu=silu)
     d = (y.float() - sep.float()).abs()
@@ -419,9 +427,11 @@ def test_stem_and_stride2_conv_block_stats(ops):
     N = 5
     # stem: NCHW fp32 image -> NHWC bf16 [N,32,32,128]
     x = torch.randn(N, 3, 32, 32, generator=g).to(DEV)
-    pw = ops.pack_conv_weight((torch.randn(128, 3, 3, 3, generator=g) * 0.2).to(DEV), k27=True)
+    w = torch.randn(128, 3, 3, 3, generator=g) * 0.2
+    pw = ops.pack_conv_weight(w.to(DEV), k27=True)
     b = torch.randn(128, generator=g).to(DEV)
-    y, st = ops.conv2d(x, pw, bias=b, want_stats=True)
+    (y, st), kid = conv_checked(ops, x, pw, w, bias=b, want_stats=True)
+    assert kid == 300000, kid
     assert st is not None and st.P == 8 and torch.equal(y, ops.conv2d(x, pw, bias=b))
     ref = _torch_block_stats(y)
     assert (st.buf.double().sum(1) - ref).abs().max().item() <= 2e-6 * ref.abs().max().item()
@@ -432,9 +442,11 @@ def test_stem_and_stride2_conv_block_stats(ops):
     assert torch.equal(st1.buf[0], st.buf[2]) and torch.equal(y1[0], y[2])
     # Downsample: k3 s2, pad (0, 1): 32x32 -> 16x16, 128 channels
     x2 = torch.randn(N, 32, 32, 128, generator=g).to(torch.bfloat16).to(DEV)
-    pw2 = ops.pack_conv_weight((torch.randn(128, 128, 3, 3, generator=g) * 0.03).to(DEV))
+    w2 = torch.randn(128, 128, 3, 3, generator=g) * 0.03
+    pw2 = ops.pack_conv_weight(w2.to(DEV))
     kw = dict(bias=b, stride=2, pad=0, pad_br=1)
-    y2, st2 = ops.conv2d(x2, pw2, want_stats=True, **kw)
+    (y2, st2), kid2 = conv_checked(ops, x2, pw2, w2, want_stats=True, **kw)
+    assert 30000 <= kid2 < 40000, kid2                                   # conv_pipe_kernel, 3x3
     assert st2 is not None and st2.P == 4 and tuple(y2.shape) == (N, 16, 16, 128) and torch.equal(y2, ops.conv2d(x2, pw2, **kw))
     ref2 = _torch_block_stats(y2)
     assert (st2.buf.double().sum(1) - ref2).abs().max().item() <= 2e-6 * ref2.abs().max().item()
@@ -442,7 +454,7 @@ def test_stem_and_stride2_conv_block_stats(ops):
     assert torch.equal(st3.buf[0], st2.buf[4])
     # 8x8 output (a 64-pixel tile would hold one image, the kernel picked packs several): no statistics, None
     x4 = torch.randn(N, 16, 16, 128, generator=g).to(torch.bfloat16).to(DEV)
-    y4, st4 = ops.conv2d(x4, pw2, want_stats=True, **kw)
+    (y4, st4), _ = conv_checked(ops, x4, pw2, w2, want_stats=True, **kw)
     assert st4 is None or (st4.buf.double().sum(1) - _torch_block_stats(y4)).abs().max().item() <= 1e-3
 
 
@@ -475,23 +487,20 @@ def test_colsum_f32(ops):
     assert (ops.colsum_f32(x2).double() - x2.double().sum(0)).abs().max().item() <= 1e-4
 
 
-@pytest.mark.parametrize("N,C,Cout,H", [(5, 128, 128, 32), (3, 256, 128, 16), (260, 128, 128, 16), (37, 256, 256, 8), (19, 256, 256, 4)])
+@pytest.mark.parametrize("N,C,Cout,H", [(5, 128, 128, 32), (3, 256, 128, 16), (260, 128, 128, 16), (37, 256, 256, 8), (19, 256, 256, 4),
+                                        (5, 256, 256, 8), (11, 256, 256, 4)])
 def test_conv_ws_activation_mask(ops, N, C, Cout, H):
     """Data gradient through a LeakyReLU on conv_ws_kernel: the mask source rides the residual tile's path
-    (out = conv(x) * (mask > 0 ? 1 : slope); value net backward, models/modules.py:96-101)."""
+    (out = conv(x) * (mask > 0 ? 1 : slope); value net backward, models/modules.py:96-101).  8x8 maps: conv_ws8_kernel (5 images:
+    the second tile holds one), 4x4 maps: conv_sm_kernel (11 images: the second tile holds three)."""
     g = torch.Generator().manual_seed(41 + N)
     x = torch.randn(N, H, H, C, generator=g).to(torch.bfloat16).to(DEV)
     w = (torch.randn(Cout, C, 3, 3, generator=g) * 0.03).to(DEV)
     pw = ops.pack_conv_weight(w)
     m = torch.randn(N, H, H, Cout, generator=g).to(torch.bfloat16).to(DEV)
-    prof = ops.OpProfiler()
-    ops.PROFILER = prof
-    try:
-        y = ops.conv2d(x, pw, mask_src=m, mask_slope=0.2)
-    finally:
-        ops.PROFILER = None
+    y, kid = conv_checked(ops, x, pw, w, mask_src=m, mask_slope=0.2)
     torch.cuda.synchronize()
-    assert [k[1] for k in prof.summary()] == [{32: 400032, 16: 400016, 8: 400008, 4: 450432}[H]]      # conv_ws / conv_ws8 / conv_sm
+    assert kid == {32: 400032, 16: 400016, 8: 400008, 4: 450432}[H]      # conv_ws / conv_ws8 / conv_sm
     ref = F.conv2d(x.float().permute(0, 3, 1, 2), w.to(torch.bfloat16).float(), padding=1)
     ref = (ref * torch.where(m.float().permute(0, 3, 1, 2) > 0, 1.0, 0.2)).permute(0, 2, 3, 1)
     assert ((y.float() - ref).norm() / ref.norm()).item() < 4e-3
@@ -500,7 +509,37 @@ def test_conv_ws_activation_mask(ops, N, C, Cout, H):
     assert torch.equal(ops.conv2d(x[i:i + 1].contiguous(), pw, mask_src=m[i:i + 1].contiguous(), mask_slope=0.2)[0], y[i])
     # mask AND residual together stay on the pipelined kernel
     r = torch.randn(N, H, H, Cout, generator=g).to(torch.bfloat16).to(DEV)
-    y2 = ops.conv2d(x, pw, mask_src=m, mask_slope=0.2, residual=r)
+    y2, kid2 = conv_checked(ops, x, pw, w, mask_src=m, mask_slope=0.2, residual=r)
+    assert kid2 < 400000, kid2
     ref2 = F.conv2d(x.float().permute(0, 3, 1, 2), w.to(torch.bfloat16).float(), padding=1) + r.float().permute(0, 3, 1, 2)
     ref2 = (ref2 * torch.where(m.float().permute(0, 3, 1, 2) > 0, 1.0, 0.2)).permute(0, 2, 3, 1)
     assert ((y2.float() - ref2).norm() / ref2.norm()).item() < 4e-3
+
+
+@pytest.mark.parametrize("N,Cout,want", [(3, 96, 450832), (31, 1024, 450864)])
+def test_conv_sm_8x8_both_cout_tile_widths_odd_batch(ops, N, Cout, want):
+    """conv_sm_kernel on 8x8 maps (two images per 128-pixel tile), an odd image count: the last tile holds one image.
+    conv_sm_select takes 64-cout tiles only where ceil(N / 2) * Cout / 64 >= 256 tiles: 31 images x 1024 couts is the smallest
+    odd batch at that width (29 images give 240 tiles); 3 images x 96 couts runs three 32-cout tiles.  Five chunks (K = 1440)."""
+    C = 160
+    g = torch.Generator().manual_seed(61 + N)
+    x = torch.randn(N, 8, 8, C, generator=g).to(torch.bfloat16).to(DEV)
+    w = torch.randn(Cout, C, 3, 3, generator=g) * 0.03
+    pw = ops.pack_conv_weight(w.to(DEV))
+    bv, tv = torch.randn(Cout, generator=g).to(DEV), torch.randn(N, Cout, generator=g).to(DEV)
+    r = torch.randn(N, 8, 8, Cout, generator=g).to(torch.bfloat16).to(DEV)
+    kw = dict(bias=bv, addvec=tv, residual=r)
+    old = ops.set_tuning("conv_sm_mask", 3)                             # bit 1: every 8x8 map
+    try:
+        y, kid = conv_checked(ops, x, pw, w, **kw)
+        assert kid == want, kid
+        ref = _conv_ref(x, None, w, bv, tv, r, 0)
+        assert ((y.float().cpu() - ref).norm() / ref.norm()).item() < 4e-3
+        assert torch.equal(y, ops.conv2d(x, pw, **kw))
+        i = N - 1                                                       # the image alone in its tile
+        xn = x.clone()
+        xn[i, 3, 4, 7] = float("nan")
+        bad = torch.isnan(ops.conv2d(xn, pw, **kw).float())
+        assert bad[i, 2:5, 3:6].all() and not bad[i, :2].any() and not bad[i, 5:].any() and not bad[i, :, :3].any() and not bad[:i].any()
+    finally:
+        ops.set_tuning("conv_sm_mask", old)

@@ -1,9 +1,12 @@
 """Round-5 kernels through the C-ABI: the 16x16 AttnBlock as one launch (dxmi_attn_block_fwd: GroupNorm on load, folded
 Wk^T Wq / Wproj Wv, the raw input tile as K, V and residual) against the reference block in torch fp32
-(reference models/DxMI/unet_small.py:167-191) and against the three launches it replaces."""
+(reference models/DxMI/unet_small.py:167-191) and against the three launches it replaces.  The 1x1 convs on conv1x1_rw8_kernel
+are also judged element by element against fp64 within the derived bound (forward_bounds.conv_checked)."""
 import pytest
 import torch
 import torch.nn.functional as F
+
+from forward_bounds import conv_checked
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -206,14 +209,14 @@ def test_conv1x1_rw8(ops, N, H, C0, C1, Cout, res, rw8):
     b = torch.randn(Cout, generator=g).to(DEV)
     r = torch.randn(N, H, H, Cout, generator=g).to(torch.bfloat16).to(DEV) if res else None
     pw = ops.pack_conv_weight(w)
-    y = ops.conv2d(x0, pw, in1=x1, bias=b, residual=r)
+    y, kid_run = conv_checked(ops, x0, pw, w, in1=x1, bias=b, residual=r)      # element by element against fp64 as well
     d = _lib.ConvDesc()
     d.in0, d.in1, d.wpacked, d.bias, d.out = x0.data_ptr(), (x1.data_ptr() if C1 else None), pw.buf.data_ptr(), b.data_ptr(), y.data_ptr()
     d.residual = r.data_ptr() if res else None
     d.N, d.IH, d.IW, d.C0, d.C1, d.OH, d.OW, d.Cout = N, H, H, C0, C1, H, H, Cout
     d.ksize, d.stride, d.pad = 1, 1, 0
     kid = _lib.load().dxmi_conv2d_kernel_id(ctypes.byref(d))
-    assert (550000 <= kid < 600000) == rw8, kid
+    assert (550000 <= kid < 600000) == rw8 and kid_run == kid, (kid, kid_run)
     xin = torch.cat([x0, x1], 3) if C1 else x0
     ref = xin.float().reshape(-1, C0 + C1) @ w.view(Cout, -1).to(torch.bfloat16).float().t() + b
     if res:
