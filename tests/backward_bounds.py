@@ -96,6 +96,25 @@ class Checker:
                              f"({int((r > 1).sum())} of {nb} blocks out of bound)")
         return worst
 
+    def row_blocks(self, name, got, ref, tol, rows):
+        """rel-L2 per block with the row blocks given as slices: got / ref are [..., T, D]; every leading index and every
+        slice of `rows` (over T) is one block.  The form for a ragged last block, which a reshape by T // rb cannot express."""
+        got, ref = got.double(), ref.double()
+        if got.shape != ref.shape:
+            raise BoundError(f"{name}: shape {tuple(got.shape)} != {tuple(ref.shape)}")
+        if not torch.isfinite(got).all():
+            raise BoundError(f"{name}: non-finite output")
+        d = torch.stack([(got - ref)[..., s, :].flatten(-2).norm(dim=-1) for s in rows], -1)
+        n = torch.stack([ref[..., s, :].flatten(-2).norm(dim=-1) for s in rows], -1) + 1e-300
+        r = d / n / tol
+        worst = float(r.max())
+        self._note(name, worst)
+        if worst > 1.0:
+            idx = tuple(int(v) for v in torch.unravel_index(r.argmax(), r.shape))
+            raise BoundError(f"{name}: block {idx} (rows {rows[idx[-1]]}) rel-L2 {worst * tol:.3g} > {tol:.3g} "
+                             f"({int((r > 1).sum())} of {r.numel()} blocks out of bound)")
+        return worst
+
     def report(self):
         return {k: round(v[0], 4) for k, v in sorted(self.worst.items())}
 
@@ -172,8 +191,12 @@ def groupnorm_bwd_ref(x, dy, gamma, beta, groups, eps, silu, scale_shift=None, a
         else:
             y2 = yn
         sg = torch.sigmoid(y2)
-        dsil = sg * (1 + y2 * (1 - sg)) if silu else torch.ones_like(y2)
-        dyy = (dyd * dsil).abs()                                         # |d loss / d y2|
+        # magnitude of SiLU's derivative s (1 + y (1 - s)) as the fp32 evaluation sees it: the sum of its absolute terms
+        # s (1 + |y| (1 - s)), as silu_bwd_ref takes it.  The derivative crosses zero at y = -1.278, and the evaluation's error
+        # there is a few u32 of s (1 + |y| (1 - s)), not of the cancelled result; with |s (1 + y (1 - s))| in its place a sum of
+        # ONE term (a 1x1 map's per-image FiLM gradient) has no room for it.  The two agree for y >= 0.
+        dsil = sg * (1 + y2.abs() * (1 - sg)) if silu else torch.ones_like(y2)
+        dyy = dyd.abs() * dsil                                           # |d loss / d y2|
         film = (1 + ss.detach()[:, :C, None, None]).abs() if ss is not None else 1.0
         gx = (dyy * film * g.detach().abs()[None, :, None, None]).reshape(N, groups, -1)
         xh = xhat.abs().reshape(N, groups, -1)
@@ -186,7 +209,10 @@ def groupnorm_bwd_ref(x, dy, gamma, beta, groups, eps, silu, scale_shift=None, a
         A_ss = None
         if ss is not None:
             G0 = dyy.sum((2, 3))
-            G1 = (dyy * yn.abs() * kappa.repeat_interleave(C // groups, 1).reshape(N, C, 1, 1)).sum((2, 3))
+            # d scale = sum dyy (xhat gamma + beta): the terms' magnitudes |xhat gamma| + |beta|, not |xhat gamma + beta| (the two
+            # can cancel, and a 1x1 map sums one such term)
+            ynm = xhat.abs() * g.detach().abs()[None, :, None, None] + b.detach().abs()[None, :, None, None]
+            G1 = (dyy * ynm * kappa.repeat_interleave(C // groups, 1).reshape(N, C, 1, 1)).sum((2, 3))
             A_ss = torch.cat([G1, G0], 1)
     return (dx, g.grad, b.grad, ss.grad if ss is not None else None), (A_dx, A_dg, A_db, A_ss)
 
@@ -337,3 +363,150 @@ def edm_step_bwd_ref(g_sample, g_mean, z, sigma, sdn, sd=0.5):
     ((smp * gs).sum() + (mu * gm).sum()).backward()
     coef = (c_out * (e(sdn) - e(sigma)) / e(sigma)).abs()
     return F.grad, up.grad, coef * (gs.abs() + gm.abs()), (gs.abs() * z.double().abs()).sum(1)
+
+
+# ------------------------------------------------------------------------------------------ judged launches
+# One definition of each judged launch: test_hip_backward_shapes.py (the program shapes) and the off-program edge tests call
+# these, so a launch is judged the same way wherever it is made.  EDGE collects the edge tests' worst |err| / bound.
+EDGE = Checker()
+
+
+def wgrad_checked(ops, x0, dy, k, check=None, *, in1=None, pad=None, stride=1, upsample=False, with_bias=False, old=None, tag=None):
+    """ops._conv2d_wgrad(x0, dy, k, ...) judged element by element: dW within wgrad_depth(plan) * u32 * sum|dy||x| of
+    wgrad_ref on the same operands (db, with_bias, against the column sums of dy at the same depth), tagged
+    wgrad[family/reduce] unless `tag` is given.  accumulate=True into a copy of the result must give bitwise twice it.
+    old: an fp32 tensor of dW's shape; accumulate=True into a copy of it is judged against old + dW with A + |old| at the same
+    depth (the + 2 of wgrad_depth counts that add).  -> (dw, db | None, plan)."""
+    check = EDGE if check is None else check
+    N, IH, IW, C0 = x0.shape
+    C1 = in1.shape[3] if in1 is not None else 0
+    _, OH, OW, Co = dy.shape
+    if pad is None:
+        pad = k // 2
+    plan = ops.conv2d_wgrad_plan(N, IH, IW, OH, OW, C0, C1, Co, k, stride, pad, upsample)
+    c = wgrad_depth(plan)
+    xc = torch.cat([x0, in1], 3) if C1 else x0
+    ref, A = wgrad_ref(xc, dy, k, stride, pad, int(bool(upsample)))
+    tag = tag or f"wgrad[{plan['family']}/{plan['reduce']}]"
+    kw = dict(in1=in1, pad=pad, stride=stride, upsample=bool(upsample))
+    db = None
+    if with_bias:
+        dw, db = ops._conv2d_wgrad(x0, dy, k, with_bias=True, **kw)
+        d = dy.double().reshape(-1, Co)
+        check.fp32("wgrad_db", db, d.sum(0), d.abs().sum(0), c)
+    else:
+        dw = ops._conv2d_wgrad(x0, dy, k, **kw)
+    check.fp32(tag, dw, ref, A, c)
+    acc = dw.clone()
+    ops._conv2d_wgrad(x0, dy, k, out=acc, accumulate=True, **kw)
+    torch.cuda.synchronize()
+    assert torch.equal(acc, dw * 2), "accumulate=True is not bitwise 2x the first result"
+    if old is not None:
+        acc = old.clone()
+        ops._conv2d_wgrad(x0, dy, k, out=acc, accumulate=True, **kw)
+        check.fp32(tag + "+old", acc, old.double() + ref, A + old.double().abs(), c)
+    return dw, db, plan
+
+
+def gn_bwd_checked(ops, op, form, x0, dy, gamma, beta, check=None, *, in1=None, add0=None, add1=None, groups=32, eps, silu=True,
+                   scale_shift=None, fwd_stats=None):
+    """ops.groupnorm_generic_bwd / ops.groupnorm_silu_bwd (op) judged against groupnorm_bwd_ref: dx (both concat sources,
+    fused adds) with Checker.bf16 at c = H W cpg + 16, dgamma / dbeta at N H W + 16, the FiLM gradient at H W + 16; tagged
+    <op>[<form>]_dx ... (form: resident, two-launch, one-launch).  -> (dx0, dx1, dgamma, dbeta, d_scale_shift | None)."""
+    check = EDGE if check is None else check
+    N, H, W, C0 = x0.shape
+    c1 = in1.shape[3] if in1 is not None else 0
+    C = C0 + c1
+    kw = dict(in1=in1, add0=add0, add1=add1, groups=groups, eps=eps, silu=silu)
+    if op == "groupnorm_generic_bwd":
+        dx0, dx1, dg, db, dss = ops.groupnorm_generic_bwd(x0, dy, gamma, beta, scale_shift=scale_shift, fwd_stats=fwd_stats, **kw)
+    else:
+        assert op == "groupnorm_silu_bwd" and scale_shift is None and fwd_stats is None
+        dx0, dx1, dg, db = ops.groupnorm_silu_bwd(x0, dy, gamma, beta, **kw)
+        dss = None
+    xc = torch.cat([x0, in1], 3) if c1 else x0
+    addc = None
+    if add0 is not None or add1 is not None:
+        addc = torch.cat([add0 if add0 is not None else torch.zeros_like(x0), add1 if add1 is not None else torch.zeros_like(in1)], 3) \
+            if c1 else add0
+    (rdx, rdg, rdb, rdss), (Adx, Adg, Adb, Ass) = groupnorm_bwd_ref(xc, dy, gamma, beta, groups, eps, silu, scale_shift=scale_shift, add=addc)
+    cpg = C // groups
+    tag = f"{op}[{form}]"
+    dx = torch.cat([dx0, dx1], 3) if c1 else dx0
+    check.bf16(tag + "_dx", dx, rdx, Adx, H * W * cpg + 16)
+    check.fp32(tag + "_dgamma", dg, rdg, Adg, N * H * W + 16)
+    check.fp32(tag + "_dbeta", db, rdb, Adb, N * H * W + 16)
+    if scale_shift is not None:
+        check.fp32(tag + "_dscale_shift", dss, rdss, Ass, H * W + 16)
+    return dx0, dx1, dg, db, dss
+
+
+ATTN_TOL = 8 * U16
+
+
+def attn_row_slices(T, rb=128):
+    return [slice(r, min(r + rb, T)) for r in range(0, T, rb)]
+
+
+def attention_blocks_judge(check, name, got, ref, heads, tol=ATTN_TOL):
+    """dqkv [N, T, 3C] per (image, q|k|v, head, 128-row block) within rel-L2 `tol`; the last block is ragged when T % 128 != 0."""
+    N, T, C3 = got.shape
+    D = C3 // 3 // heads
+    rb = 128 if T >= 128 else T
+    if T % rb == 0:
+        blk = lambda d: d.reshape(N, T // rb, rb, 3, heads, D).permute(0, 3, 4, 1, 2, 5)
+        return check.blocks(name, blk(got), blk(ref), tol, 4)
+    blk = lambda d: d.reshape(N, T, 3, heads, D).permute(0, 2, 3, 1, 4)
+    return check.row_blocks(name, blk(got), blk(ref), tol, attn_row_slices(T, rb))
+
+
+def attention_bwd_checked(ops, qkv, do, heads, scale, check=None, *, o=None, lse=None, ref=None, tag=None):
+    """ops.attention_bwd(qkv, do, heads, scale, o=o, lse=lse) judged per (image, q|k|v, head, 128-row block) within rel-L2
+    8 u16 of attention_bwd_ref (P and dS are bf16 MFMA operands in the kernels, so the bound is per block at the kernel's tile
+    size rather than per element).  ref: attention_bwd_ref's result when the caller already has it.  -> (dqkv, ref)."""
+    check = EDGE if check is None else check
+    N, T, C3 = qkv.shape
+    if ref is None:
+        ref = attention_bwd_ref(qkv, do, heads, scale)
+    got = ops.attention_bwd(qkv, do, heads, scale, o=o, lse=lse)
+    tag = tag or f"attention_bwd[T{T},h{heads}{',lse' if lse is not None else ''}]"
+    attention_blocks_judge(check, tag, got, ref[0], heads)
+    return got, ref
+
+
+def softmax_bwd_ref(S, dP):
+    """P = softmax(S), dS = P (dP - sum_k dP_k P_k) per row in fp64, and each row's largest term: max_j P_j for P, and
+    max_j P_j (|dP_j| + sum_k |dP_k| P_k) for dS (the magnitude the fp32 evaluation's absolute error scales with)."""
+    s, g = S.double(), dP.double()
+    P = torch.softmax(s, -1)
+    dot = (g * P).sum(-1, keepdim=True)
+    dS = P * (g - dot)
+    mP = P.amax(-1, keepdim=True)
+    mS = (P * (g.abs() + (g.abs() * P).sum(-1, keepdim=True))).amax(-1, keepdim=True)
+    return P, dS, mP, mS
+
+
+def gn_resident_plan(C0, C1, HW, groups):
+    """The slicing walk of the register-resident GroupNorm backward (gn_plan in csrc/groupnorm.hip with its limits of 8 / 16
+    pieces per thread) restated, so a test can say which of its paths a shape takes -> dict(VEC, slices, threads, pieces, ppp)
+    or None where the walk fails; whether the kernel serves the shape is asked of dxmi_groupnorm_silu_bwd_supported."""
+    C = C0 + C1
+    cpg = C // groups
+    VEC = 8 if (cpg % 8 == 0 and C0 % 8 == 0) else 4
+    max_pieces = 8 if VEC == 8 else 16
+    slices = 1
+    while True:
+        if groups % slices:
+            return None
+        ppp = C // slices // VEC
+        unit = ppp // math.gcd(ppp, 64) * 64
+        if unit > 512:
+            return None
+        total = HW * ppp
+        threads = (512 // unit) * unit
+        if total < threads:
+            threads = -(-total // unit) * unit
+        pieces = -(-total // threads)
+        if pieces <= max_pieces or slices == groups:
+            return dict(VEC=VEC, slices=slices, threads=threads, pieces=pieces, ppp=ppp)
+        slices *= 2

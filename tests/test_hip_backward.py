@@ -3,7 +3,9 @@ data-gradient epilogues, pooling / head backward, and the whole value-network ba
 gradients the REFERENCE produced (tests/golden/value_forward.npz).
 
 Tolerance: operands and stored gradients are bf16 (fp32 accumulate) -> rel-L2 <= 1e-2 vs the fp32
-reference gradients; single kernels vs fp32 torch on bf16-rounded inputs <= 4e-3 (wgrad: fp32 out, 1e-4)."""
+reference gradients; single kernels vs fp32 torch on bf16-rounded inputs <= 4e-3 (wgrad: fp32 out, 1e-4).
+Every single-kernel launch is also judged element by element (attention: block by block) against fp64 within the derived
+bounds of tests/backward_bounds.py / forward_bounds.py, through the helpers the program-shape tests use."""
 import math
 import os
 
@@ -11,6 +13,9 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from backward_bounds import EDGE, attention_bwd_checked, gn_bwd_checked, value_head_bwd_ref, wgrad_checked
+from forward_bounds import conv_checked
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -72,6 +77,8 @@ def test_conv_wgrad(ops, N, cin, Cout, H, k):
     acc = got.clone()
     ops.conv2d_wgrad(x0, nhwc(dy), k, in1=x1, out=acc, accumulate=True)
     assert torch.equal(acc, got + got)
+    dw, _, _ = wgrad_checked(ops, x0, nhwc(dy), k, in1=x1)
+    assert torch.equal(dw, got)
 
 
 @pytest.mark.parametrize("N,C,Cout,H,k,bias", [(16, 256, 256, 16, 1, True), (16, 256, 256, 16, 1, False), (24, 128, 128, 16, 1, True),
@@ -95,6 +102,8 @@ def test_conv_wgrad_stays_inside_an_exactly_sized_workspace(ops, monkeypatch, N,
         assert rel_l2(db.cpu(), dy.sum((0, 2, 3))) < 1e-5
     torch.cuda.synchronize()
     assert rel_l2(got.cpu(), ref) < 1e-4
+    dw, db2, _ = wgrad_checked(ops, nhwc(x), nhwc(dy), k, with_bias=bias)
+    assert torch.equal(dw, got) and (not bias or torch.equal(db2, db))
     assert bool((buf[:guard] == 0x5A).all()) and bool((buf[guard + need:] == 0x5A).all()), "wgrad wrote outside its workspace"
 
 
@@ -103,18 +112,29 @@ def test_colsum_and_pool_bwd_and_head_bwd(ops):
     N, C, H = 5, 256, 8
     dy = bf(torch.randn(N, C, H, H, generator=g))
     assert rel_l2(ops.colsum(nhwc(dy)).cpu(), dy.sum((0, 2, 3))) < 1e-5
+    cs = lambda t: EDGE.fp32("colsum", ops.colsum(nhwc(t)), nhwc(t).double().sum((0, 1, 2)), nhwc(t).double().abs().sum((0, 1, 2)),
+                             t.shape[0] * t.shape[2] * t.shape[3] + 2)
+    cs(dy)
     for Cw, Hw in ((2304, 8), (768, 16), (192, 32)):   # EDM widths: q|k|v of 768 channels goes through 2 column blocks
         dw = bf(torch.randn(3, Cw, Hw, Hw, generator=g))
         assert rel_l2(ops.colsum(nhwc(dw)).cpu(), dw.sum((0, 2, 3))) < 1e-5, Cw
+        cs(dw)
     a = bf(torch.randn(N, C, H, H, generator=g))
     ref = dy * torch.where(a > 0, 1.0, 0.2)
     assert rel_l2(nchw(ops.pool_act_bwd(nhwc(dy), nhwc(a), False, 0.2)), ref) < 4e-3
     refp = F.interpolate(ref, scale_factor=2.0, mode="nearest") * 0.25
     assert rel_l2(nchw(ops.pool_act_bwd(nhwc(dy), nhwc(a), True, 0.2)), refp) < 4e-3
+    r64 = nhwc(dy).double() * torch.where(nhwc(a) > 0, 1.0, 0.2).double()          # one fp32 product, one bf16 rounding
+    EDGE.bf16("pool_act_bwd", ops.pool_act_bwd(nhwc(dy), nhwc(a), False, 0.2), r64, r64.abs(), 2)
+    r64p = 0.25 * r64.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    EDGE.bf16("pool_act_bwd", ops.pool_act_bwd(nhwc(dy), nhwc(a), True, 0.2), r64p, r64p.abs(), 2)
     w, gy = torch.randn(C, generator=g), torch.randn(N, generator=g)
     dfeat, s = ops.value_head_bwd(nhwc(a), w.to(DEV), gy.to(DEV))
     assert rel_l2(s.cpu(), F.relu(a).flatten(2).sum(2)) < 1e-5
     assert rel_l2(nchw(dfeat), (gy[:, None, None, None] * w[None, :, None, None]) * (a > 0)) < 4e-3
+    rdf, rs, As = value_head_bwd_ref(nhwc(a), w.to(DEV), gy.to(DEV))
+    EDGE.bf16("value_head_bwd_dfeat", dfeat, rdf, rdf.abs(), 2)
+    EDGE.fp32("value_head_bwd_s", s, rs, As, H * H + 2)
 
 
 def test_dgrad_with_fused_mask_and_skip(ops):
@@ -128,7 +148,8 @@ def test_dgrad_with_fused_mask_and_skip(ops):
     F.conv2d(x, w, padding=1).backward(gy)
     ref = (x.grad + skip) * torch.where(act > 0, 1.0, 0.2)
     pw = ops.pack_conv_weight(w.to(DEV), transpose_flip=True)
-    got = ops.conv2d(nhwc(gy), pw, residual=nhwc(skip), mask_src=nhwc(act), mask_slope=0.2)
+    got, _ = conv_checked(ops, nhwc(gy), pw, w.transpose(0, 1).flip(2, 3).contiguous(), residual=nhwc(skip), mask_src=nhwc(act),
+                          mask_slope=0.2)
     assert rel_l2(nchw(got), ref) < 4e-3
 
 
@@ -188,9 +209,10 @@ def test_groupnorm_silu_bwd(ops, N, C0, C1, H, silu):
         y = F.silu(y)
     y.backward(dy)
     xd = x.detach()
-    dx0, dx1, dg, db = ops.groupnorm_silu_bwd(nhwc(xd[:, :C0]), nhwc(dy), gamma.detach().to(DEV), beta.detach().to(DEV),
-                                              in1=nhwc(xd[:, C0:]) if C1 else None, add0=nhwc(add[:, :C0]),
-                                              add1=nhwc(add[:, C0:]) if C1 else None, silu=silu)
+    kw = dict(in1=nhwc(xd[:, C0:]) if C1 else None, add0=nhwc(add[:, :C0]), add1=nhwc(add[:, C0:]) if C1 else None, silu=silu)
+    sup = ops.load().dxmi_groupnorm_silu_bwd_supported(C0, C1, H * H, 32) and not (C // 32 == 12 and H * H >= 256)
+    dx0, dx1, dg, db, _ = gn_bwd_checked(ops, "groupnorm_silu_bwd", "resident" if sup else "routed-generic", nhwc(xd[:, :C0]), nhwc(dy),
+                                         gamma.detach().to(DEV), beta.detach().to(DEV), eps=1e-6, **kw)
     got = torch.cat([nchw(dx0)] + ([nchw(dx1)] if C1 else []), 1)
     assert rel_l2(got, x.grad + add) < 4e-3
     assert rel_l2(dg.cpu(), gamma.grad) < 1e-4 and rel_l2(db.cpu(), beta.grad) < 1e-4
@@ -216,10 +238,12 @@ def test_attention_bwd_fused_heads64(ops, N, T, C, heads):
     qd, dd = qkv.detach().to(torch.bfloat16).to(DEV), do.to(torch.bfloat16).to(DEV)
     od = ops.attention(qd, heads, scale)                              # the forward output the training graph keeps
     assert rel_l2(od.float().cpu(), o.detach()) < 1e-2
-    got = ops.attention_bwd(qd, dd, heads, scale, o=od)
+    got, ref64 = attention_bwd_checked(ops, qd, dd, heads, scale, o=od, tag=f"attention_bwd[fused,T{T}]")
     for name, sl in (("dq", slice(0, C)), ("dk", slice(C, 2 * C)), ("dv", slice(2 * C, 3 * C))):
         e = rel_l2(got[:, :, sl].float().cpu(), qkv.grad[:, :, sl])
         assert e < 1e-2, (name, e)
+    if T % 8 == 0:
+        old, _ = attention_bwd_checked(ops, qd, dd, heads, scale, ref=ref64, tag=f"attention_bwd[five-gemm,D64,T{T}]")
     old = ops.attention_bwd(qd, dd, heads, scale)                     # no o: the five-GEMM path
     assert rel_l2(got.float().cpu(), old.float().cpu()) < 1e-2
     assert torch.equal(got, ops.attention_bwd(qd, dd, heads, scale, o=od))
@@ -241,7 +265,8 @@ def test_attention_bwd(ops, N, T, C, heads):
     v = v.view(N, T, heads, D).transpose(1, 2)
     o = (torch.softmax(q @ k.transpose(-1, -2) * scale, dim=-1) @ v).transpose(1, 2).reshape(N, T, C)
     o.backward(do)
-    got = ops.attention_bwd(qkv.detach().to(torch.bfloat16).to(DEV), do.to(torch.bfloat16).to(DEV), heads, scale)
+    got, _ = attention_bwd_checked(ops, qkv.detach().to(torch.bfloat16).to(DEV), do.to(torch.bfloat16).to(DEV), heads, scale,
+                                   tag=f"attention_bwd[five-gemm,D{D}]")
     assert rel_l2(got.float().cpu(), qkv.grad) < 1e-2, rel_l2(got.float().cpu(), qkv.grad)
 
 
@@ -255,9 +280,11 @@ def test_stride2_conv_backward(ops):
     dy = bf(torch.randn(N, C, H // 2, H // 2, generator=g))
     F.conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2).backward(dy)
     pw_t = ops.pack_conv_weight(w.detach().to(DEV), transpose_flip=True)
-    dx = ops.conv2d(nhwc(dy), pw_t, pad=2, pad_br=0, upsample=2)
+    wt = w.detach().transpose(0, 1).flip(2, 3).contiguous()
+    dx, _ = conv_checked(ops, nhwc(dy), pw_t, wt, pad=2, pad_br=0, upsample=2)
     assert dx.shape == (N, H, H, C) and rel_l2(nchw(dx), x.grad) < 4e-3
     dw = ops.conv2d_wgrad(nhwc(x.detach()), nhwc(dy), 3, stride=2, pad=0)
+    assert torch.equal(dw, wgrad_checked(ops, nhwc(x.detach()), nhwc(dy), 3, stride=2, pad=0)[0])
     assert rel_l2(dw.cpu(), w.grad) < 1e-4
 
 
@@ -270,8 +297,9 @@ def test_upsample_conv_backward(ops):
     F.conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), w, padding=1).backward(dy)
     dw = ops.conv2d_wgrad(nhwc(x.detach()), nhwc(dy), 3, upsample=True)
     assert rel_l2(dw.cpu(), w.grad) < 1e-4
+    assert torch.equal(dw, wgrad_checked(ops, nhwc(x.detach()), nhwc(dy), 3, upsample=True)[0])
     pw_t = ops.pack_conv_weight(w.detach().to(DEV), transpose_flip=True)
-    dx_hi = ops.conv2d(nhwc(dy), pw_t)                       # gradient w.r.t. the upsampled image
+    dx_hi, _ = conv_checked(ops, nhwc(dy), pw_t, w.detach().transpose(0, 1).flip(2, 3).contiguous())     # gradient w.r.t. the upsampled image
     dx = ops.pool_act(dx_hi, True, ops.ACT_NONE)             # 2x2 mean; x4 = sum over the replicated pixels
     assert rel_l2(nchw(dx) * 4, x.grad) < 6e-3
 

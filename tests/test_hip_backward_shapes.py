@@ -19,9 +19,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from backward_bounds import (U16, U32, Checker, attention_bwd_ref, dropout_ref, dsm_loss_bwd_ref, edm_step_bwd_ref, groupnorm_bwd_ref,
-                             silu_bwd_ref, unfold_nhwc, value_head_bwd_ref, value_head_pgrad_ref, var_step_bwd_ref, wgrad_depth,
-                             wgrad_ref)
+from backward_bounds import (U16, U32, Checker, attention_bwd_checked, attention_bwd_ref, dropout_ref, dsm_loss_bwd_ref,
+                             edm_step_bwd_ref, gn_bwd_checked, silu_bwd_ref, unfold_nhwc, value_head_bwd_ref, value_head_pgrad_ref,
+                             var_step_bwd_ref, wgrad_checked, wgrad_depth, wgrad_ref)
 from forward_bounds import FwdChecker, dsm_error_terms, linear_ref, pool_act_ref
 
 DEV = "cuda:0"
@@ -729,21 +729,8 @@ def test_wgrad(ops, r):
     x1 = bf(rnd(g, *xs[:3], c1, scale=2.0)) if c1 else None
     dy = bf(rnd(g, *dys))
     plan = _plan(ops, r)
-    c = wgrad_depth(plan)
-    xc = torch.cat([x0, x1], 3) if c1 else x0
-    ref, A = wgrad_ref(xc, dy, k, stride, pad, ups)
-    tag = f"wgrad[{plan['family']}]"
-    if with_bias:
-        dw, db = ops._conv2d_wgrad(x0, dy, k, in1=x1, pad=pad, stride=stride, upsample=bool(ups), with_bias=True)
-        d = dy.double().reshape(-1, dy.shape[3])
-        CHECK.fp32("wgrad_db", db, d.sum(0), d.abs().sum(0), c)
-    else:
-        dw = ops._conv2d_wgrad(x0, dy, k, in1=x1, pad=pad, stride=stride, upsample=bool(ups))
-    CHECK.fp32(tag, dw, ref, A, c)
-    acc = dw.clone()
-    ops._conv2d_wgrad(x0, dy, k, in1=x1, pad=pad, stride=stride, upsample=bool(ups), out=acc, accumulate=True)
-    torch.cuda.synchronize()
-    assert torch.equal(acc, dw * 2), "accumulate=True is not bitwise 2x the first result"
+    wgrad_checked(ops, x0, dy, k, CHECK, in1=x1, pad=pad, stride=stride, upsample=bool(ups), with_bias=with_bias,
+                  tag=f"wgrad[{plan['family']}]")
 
 
 @pytest.mark.gpu
@@ -899,29 +886,11 @@ def _gn_case(ops, r, form):
     add1 = bf(rnd(g, N, H, W, c1)) if has_add1 else None
     ss = (0.3 * rnd(g, N, 3 * C))[:, C // 2: C // 2 + 2 * C] if has_ss else None     # a row-strided slice, as emb_all's
     eps = 1e-5 if op == "groupnorm_generic_bwd" else 1e-6
-    kw = dict(in1=x1, add0=add0, add1=add1, groups=groups, eps=eps, silu=silu)
-    if op == "groupnorm_generic_bwd":
-        saved = []
-        if has_saved:
-            ops.groupnorm_generic(x0, gamma, beta, in1=x1, groups=groups, eps=eps, silu=silu, scale_shift=ss, saved=saved)
-        dx0, dx1, dg, db, dss = ops.groupnorm_generic_bwd(x0, dy, gamma, beta, scale_shift=ss, fwd_stats=saved[0] if saved else None, **kw)
-    else:
-        dx0, dx1, dg, db = ops.groupnorm_silu_bwd(x0, dy, gamma, beta, **kw)
-        dss = None
-    xc = torch.cat([x0, x1], 3) if c1 else x0
-    addc = None
-    if has_add0 or has_add1:
-        addc = torch.cat([add0 if add0 is not None else torch.zeros_like(x0), add1 if add1 is not None else torch.zeros_like(x1)], 3) \
-            if c1 else add0
-    (rdx, rdg, rdb, rdss), (Adx, Adg, Adb, Ass) = groupnorm_bwd_ref(xc, dy, gamma, beta, groups, eps, silu, scale_shift=ss, add=addc)
-    cpg = C // groups
-    tag = f"{op}[{form}]"
-    dx = torch.cat([dx0, dx1], 3) if c1 else dx0
-    CHECK.bf16(tag + "_dx", dx, rdx, Adx, H * W * cpg + 16)
-    CHECK.fp32(tag + "_dgamma", dg, rdg, Adg, N * H * W + 16)
-    CHECK.fp32(tag + "_dbeta", db, rdb, Adb, N * H * W + 16)
-    if has_ss:
-        CHECK.fp32(tag + "_dscale_shift", dss, rdss, Ass, H * W + 16)
+    saved = []
+    if op == "groupnorm_generic_bwd" and has_saved:
+        ops.groupnorm_generic(x0, gamma, beta, in1=x1, groups=groups, eps=eps, silu=silu, scale_shift=ss, saved=saved)
+    gn_bwd_checked(ops, op, form, x0, dy, gamma, beta, CHECK, in1=x1, add0=add0, add1=add1, groups=groups, eps=eps, silu=silu,
+                   scale_shift=ss, fwd_stats=saved[0] if saved else None)
 
 
 @pytest.mark.gpu
@@ -967,17 +936,14 @@ def test_attention_bwd(ops, r):
     g = torch.Generator(device=DEV).manual_seed(zlib.crc32(repr(r).encode()))
     qkv = bf(rnd(g, N, T, C3))
     do = bf(rnd(g, N, T, C))
-    ref, o64 = attention_bwd_ref(qkv, do, heads, scale)
+    ref = attention_bwd_ref(qkv, do, heads, scale)
+    o = lse = None
     if with_lse:
         o, lse = ops.attention(qkv, heads, scale, want_lse=True)
-        got = ops.attention_bwd(qkv, do, heads, scale, o=o, lse=lse)
     elif with_o:
-        got = ops.attention_bwd(qkv, do, heads, scale, o=bf(o64))
-    else:
-        got = ops.attention_bwd(qkv, do, heads, scale)
-    rb = 128 if T >= 128 else T
-    blk = lambda d: d.reshape(N, T // rb, rb, 3, heads, D).permute(0, 3, 4, 1, 2, 5)
-    CHECK.blocks(f"attention_bwd[T{T},h{heads}{',lse' if with_lse else ''}]", blk(got), blk(ref), 8 * U16, 4)
+        o = bf(ref[1])
+    attention_bwd_checked(ops, qkv, do, heads, scale, CHECK, o=o, lse=lse, ref=ref,
+                          tag=f"attention_bwd[T{T},h{heads}{',lse' if with_lse else ''}]")
 
 
 # ------------------------------------------------------------------------------------------ the ops outside the first ten

@@ -434,8 +434,10 @@ def test_groupnorm_generic_bwd(ops, N, C0, C1, H, silu, ss):
     xd = x.detach()
     x0, x1 = nhwc(xd[:, :C0]), (nhwc(xd[:, C0:]) if C1 else None)
     a0, a1 = nhwc(add[:, :C0]), (nhwc(add[:, C0:]) if C1 else None)
-    dx0, dx1, dg, db, dss = ops.groupnorm_generic_bwd(x0, nhwc(dy), gamma.detach().to(DEV), beta.detach().to(DEV), in1=x1, add0=a0,
-                                                      add1=a1, eps=1e-5, silu=silu, scale_shift=sst.detach().to(DEV) if ss else None)
+    from backward_bounds import gn_bwd_checked
+    form = "one-launch" if ops.groupnorm_generic_bwd_plan(N, H * H, C) else "two-launch"
+    dx0, dx1, dg, db, dss = gn_bwd_checked(ops, "groupnorm_generic_bwd", form, x0, nhwc(dy), gamma.detach().to(DEV), beta.detach().to(DEV),
+                                           in1=x1, add0=a0, add1=a1, eps=1e-5, silu=silu, scale_shift=sst.detach().to(DEV) if ss else None)
     ref_dx = x.grad + add
     got = torch.cat([nchw(dx0)] + ([nchw(dx1)] if C1 else []), 1)
     assert rel_l2(got, ref_dx) < 6e-3

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from backward_bounds import EDGE
 from forward_bounds import conv_checked
 
 pytestmark = pytest.mark.gpu
@@ -482,9 +483,11 @@ def test_colsum_f32(ops):
         got = ops.colsum_f32(x)
         assert tuple(got.shape) == (B, C)
         assert (got.double() - x.double().sum(1)).abs().max().item() <= 1e-5 * N ** 0.5 * 4
+        EDGE.fp32("colsum_f32", got, x.double().sum(1), x.double().abs().sum(1), N + 2)
         assert torch.equal(got, ops.colsum_f32(x))
     x2 = torch.randn(33, 64, generator=g).to(DEV)
     assert (ops.colsum_f32(x2).double() - x2.double().sum(0)).abs().max().item() <= 1e-4
+    EDGE.fp32("colsum_f32", ops.colsum_f32(x2), x2.double().sum(0), x2.double().abs().sum(0), 33 + 2)
 
 
 @pytest.mark.parametrize("N,C,Cout,H", [(5, 128, 128, 32), (3, 256, 128, 16), (260, 128, 128, 16), (37, 256, 256, 8), (19, 256, 256, 4),

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from backward_bounds import EDGE, attention_bwd_checked, gn_bwd_checked
 from forward_bounds import conv_checked
 
 pytestmark = pytest.mark.gpu
@@ -280,8 +281,10 @@ def test_blockstats_to_generic_feeds_the_generic_backward():
         assert float(b[:, 1:].abs().max()) == 0.0                       # the whole image in chunk 0
         torch.testing.assert_close(b[:, 0], a, rtol=2e-5, atol=1e-2)
         torch.testing.assert_close(y_str.float(), y_gen.float(), rtol=2e-2, atol=2e-2)
-        ref = ops.groupnorm_generic_bwd(x0, dy, ga, be, in1=x1, eps=1e-5, silu=True, scale_shift=sst)
-        got = ops.groupnorm_generic_bwd(x0, dy, ga, be, in1=x1, eps=1e-5, silu=True, scale_shift=sst, fwd_stats=sv_str[0])
+        form = "one-launch" if ops.groupnorm_generic_bwd_plan(N, H * H, C) else "two-launch"
+        ref = gn_bwd_checked(ops, "groupnorm_generic_bwd", form, x0, dy, ga, be, in1=x1, eps=1e-5, silu=True, scale_shift=sst)
+        got = gn_bwd_checked(ops, "groupnorm_generic_bwd", form, x0, dy, ga, be, in1=x1, eps=1e-5, silu=True, scale_shift=sst,
+                             fwd_stats=sv_str[0])
         for r, t in zip(ref, got):
             assert (r is None) == (t is None)
             if r is not None:
@@ -314,11 +317,15 @@ def test_generic_groupnorm_backward_one_launch_vs_two():
         sv = []
         ops.groupnorm_generic(x0, ga, be, in1=x1, eps=1e-5, silu=True, scale_shift=sst, saved=sv)
         run = lambda st: ops.groupnorm_generic_bwd(x0, dy, ga, be, in1=x1, add0=a0, add1=a1, eps=1e-5, silu=True, scale_shift=sst, fwd_stats=st)
+        judged = lambda form, st: gn_bwd_checked(ops, "groupnorm_generic_bwd", form, x0, dy, ga, be, in1=x1, add0=a0, add1=a1, eps=1e-5,
+                                                 silu=True, scale_shift=sst, fwd_stats=st)
         old = ops.set_tuning("gn_bwd_fused", 0)
         try:
-            ref = run(sv[0])
+            assert ops.groupnorm_generic_bwd_plan(N, H * H, C) == 0
+            ref = judged("two-launch", sv[0])
             ops.set_tuning("gn_bwd_fused", 2)        # 2: on every shape the plan fits (1, the default: maps of <= 256 pixels)
-            got, again, fresh = run(sv[0]), run(sv[0]), run(None)
+            form = "one-launch" if ops.groupnorm_generic_bwd_plan(N, H * H, C) else "two-launch"
+            got, again, fresh = judged(form, sv[0]), run(sv[0]), judged(form, None)
         finally:
             ops.set_tuning("gn_bwd_fused", old)
         for i, (r, t, t2, t3) in enumerate(zip(ref, got, again, fresh)):
@@ -356,6 +363,11 @@ def test_gn_ss_grads_vs_torch():
         torch.testing.assert_close(d_ss, torch.cat([g[1] * ga + g[0] * be, g[0]], 1), rtol=1e-6, atol=1e-6)
         torch.testing.assert_close(dgb[0], (g[1] * one_s).sum(0), rtol=1e-5, atol=1e-5)
         torch.testing.assert_close(dgb[1], (g[0] * one_s).sum(0), rtol=1e-5, atol=1e-5)
+        gd, s64 = g.double(), 1.0 + ss[:, :C].double()
+        EDGE.fp32("gn_ss_grads_dss", d_ss, torch.cat([gd[1] * ga.double() + gd[0] * be.double(), gd[0]], 1),
+                  torch.cat([(gd[1] * ga.double()).abs() + (gd[0] * be.double()).abs(), gd[0].abs()], 1), 4)
+        EDGE.fp32("gn_ss_grads_dgamma", dgb[0], (gd[1] * s64).sum(0), (gd[1] * s64).abs().sum(0), N + 4)
+        EDGE.fp32("gn_ss_grads_dbeta", dgb[1], (gd[0] * s64).sum(0), (gd[0] * s64).abs().sum(0), N + 4)
 
 
 def test_attention_backward_with_the_forwards_log_sum_exp():
@@ -379,8 +391,8 @@ def test_attention_backward_with_the_forwards_log_sum_exp():
         s = torch.einsum("nthd,nshd->nhts", q, k) * scale
         ref = torch.logsumexp(s, dim=-1) / math.log(2.0)
         torch.testing.assert_close(lse, ref, rtol=1e-4, atol=2e-3)
-        a = ops.attention_bwd(qkv, do, heads, scale, o=o)
-        b = ops.attention_bwd(qkv, do, heads, scale, o=o, lse=lse)
+        a, ref64 = attention_bwd_checked(ops, qkv, do, heads, scale, o=o, tag=f"attention_bwd[fused,T{T}]")
+        b, _ = attention_bwd_checked(ops, qkv, do, heads, scale, o=o, lse=lse, ref=ref64, tag=f"attention_bwd[fused,lse,T{T}]")
         rel = float((a.float() - b.float()).norm() / a.float().norm())
         assert rel < 2e-3, (N, T, heads, rel)
     assert ops.attention(torch.zeros(1, 256, 768, dtype=torch.bfloat16, device=dev), 1, 1.0, want_lse=True)[1] is None     # attention256_kernel: no lse
