@@ -1,5 +1,5 @@
-// The counter-based generator behind the indexed draws (csrc/randn_indexed.hip) and the fused noise of dxmi_ddpm_stage
-// (csrc/ddpm_sample.hip): Philox-4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the
+// The counter-based generator behind the indexed draws (csrc/randn_indexed.hip) and the fused noise of dxmi_ddpm_stage and
+// dxmi_dpm_stage (csrc/stage_common.h): Philox-4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the
 // Random123 constants), the 23-bit uniform and Box-Muller.  ONE definition: the bits of a normal are part of the interface
 // (include/dxmi_hip.h), so every launch that makes one goes through these three functions, contraction off.
 #pragma once

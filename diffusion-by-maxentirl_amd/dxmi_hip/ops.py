@@ -1817,6 +1817,38 @@ def randint_indexed(sample_index, shape_tail, low, high, seed, draw, out=None):
     return out
 
 
+def _sampler_stage(name, cols, mode, first, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out, pred_xstart, hist=()):
+    """The checks and the call of the stage launches of the DDPM teacher's samplers (csrc/stage_common.h).  cols: the table's row
+    length; first: the sampler's FIRST mode; hist: () for a sampler without a history, else (the tensor or None,)."""
+    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, *hist, out, pred_xstart)
+    if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == cols and tab.shape[0] >= 1):
+        raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {cols}], got {tab.dtype} {tuple(tab.shape)}")
+    if not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
+        raise _lib.DxmiError(f"{name}: t_out must be a contiguous fp32 [N]")
+    N = t_out.numel()
+    chw = 1
+    if mode != first:
+        if x is None or eps is None or out is None or any(h is None for h in hist):
+            raise _lib.DxmiError(f"{name}: a transition needs x, eps{', hist' if hist else ''} and out")
+        for v in (x, eps, z, out, pred_xstart):
+            if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
+                raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
+        if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
+            raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} samples, got {tuple(x.shape)}")
+        for h in hist:
+            if not (h.dtype == torch.float32 and h.is_contiguous() and tuple(h.shape) == (3,) + tuple(x.shape)):
+                raise _lib.DxmiError(f"{name}: hist must be a contiguous fp32 {(3,) + tuple(x.shape)}, got {h.dtype} {tuple(h.shape)}")
+        chw = x.numel() // N
+        if sample_index is not None and not (sample_index.dtype == torch.int64 and sample_index.is_contiguous()
+                                             and sample_index.shape == (N,)):
+            raise _lib.DxmiError(f"{name}: sample_index must be a contiguous int64 [{N}]")
+    if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
+        raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
+    check(getattr(load(), name)(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF,
+                                int(seed) & _U64, _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), *(_ptr(h) for h in hist), _ptr(t_out),
+                                _ptr(out), _ptr(pred_xstart), N, chw, _stream()), name)
+
+
 # dxmi_ddpm_stage modes, table columns and flags (include/dxmi_hip.h)
 DDPM_FIRST, DDPM_STEP = range(2)
 DT_T, DT_T_NEXT, DT_XM, DT_C, DT_S, DT_A, DT_B, DT_Q, DT_R, DT_C0, DT_C1, DT_FLAGS = range(12)
@@ -1831,31 +1863,8 @@ def ddpm_stage(mode, tab, t_out, row=0, x=None, eps=None, z=None, sample_index=N
     [rows, DT_COLS] on the device.  Noise: z [N, ...] given, or sample_index (int64 [N]) with seed / draw: made in the launch, the
     values of randn_indexed.  ctl: an int32 [4] device block (row, draw, seed low, seed high) that replaces row / draw / seed: a
     captured launch then serves every row.  DDPM_FIRST writes t_out of `row` only."""
-    name = "dxmi_ddpm_stage"
-    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, out, pred_xstart)
-    if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == DT_COLS and tab.shape[0] >= 1):
-        raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {DT_COLS}], got {tab.dtype} {tuple(tab.shape)}")
-    if not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
-        raise _lib.DxmiError(f"{name}: t_out must be a contiguous fp32 [N]")
-    N = t_out.numel()
-    chw = 1
-    if mode != DDPM_FIRST:
-        if x is None or eps is None or out is None:
-            raise _lib.DxmiError(f"{name}: a transition needs x, eps and out")
-        for v in (x, eps, z, out, pred_xstart):
-            if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
-                raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
-        if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
-            raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} samples, got {tuple(x.shape)}")
-        chw = x.numel() // N
-        if sample_index is not None and not (sample_index.dtype == torch.int64 and sample_index.is_contiguous()
-                                             and sample_index.shape == (N,)):
-            raise _lib.DxmiError(f"{name}: sample_index must be a contiguous int64 [{N}]")
-    if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
-        raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
-    check(load().dxmi_ddpm_stage(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF, int(seed) & _U64,
-                                 _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), _ptr(t_out), _ptr(out), _ptr(pred_xstart), N, chw,
-                                 _stream()), name)
+    _sampler_stage("dxmi_ddpm_stage", DT_COLS, mode, DDPM_FIRST, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out,
+                   pred_xstart)
 
 
 # dxmi_dpm_stage modes, table columns and flags (include/dxmi_hip.h)
@@ -1873,33 +1882,8 @@ def dpm_stage(mode, tab, t_out, row=0, x=None, eps=None, z=None, sample_index=No
     tab: fp32 [rows, MT_COLS] on the device.  Noise: z [N, ...] given, or sample_index (int64 [N]) with seed / draw: made in the
     launch, the values of randn_indexed.  ctl: an int32 [4] device block (row, draw, seed low, seed high) that replaces row / draw /
     seed: a captured launch then serves every row.  DPM_FIRST writes t_out of `row` only."""
-    name = "dxmi_dpm_stage"
-    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, hist, out, pred_xstart)
-    if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == MT_COLS and tab.shape[0] >= 1):
-        raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {MT_COLS}], got {tab.dtype} {tuple(tab.shape)}")
-    if not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
-        raise _lib.DxmiError(f"{name}: t_out must be a contiguous fp32 [N]")
-    N = t_out.numel()
-    chw = 1
-    if mode != DPM_FIRST:
-        if x is None or eps is None or out is None or hist is None:
-            raise _lib.DxmiError(f"{name}: a transition needs x, eps, hist and out")
-        for v in (x, eps, z, out, pred_xstart):
-            if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
-                raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
-        if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
-            raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} samples, got {tuple(x.shape)}")
-        if not (hist.dtype == torch.float32 and hist.is_contiguous() and tuple(hist.shape) == (3,) + tuple(x.shape)):
-            raise _lib.DxmiError(f"{name}: hist must be a contiguous fp32 {(3,) + tuple(x.shape)}, got {hist.dtype} {tuple(hist.shape)}")
-        chw = x.numel() // N
-        if sample_index is not None and not (sample_index.dtype == torch.int64 and sample_index.is_contiguous()
-                                             and sample_index.shape == (N,)):
-            raise _lib.DxmiError(f"{name}: sample_index must be a contiguous int64 [{N}]")
-    if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
-        raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
-    check(load().dxmi_dpm_stage(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF, int(seed) & _U64,
-                                _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), _ptr(hist), _ptr(t_out), _ptr(out), _ptr(pred_xstart),
-                                N, chw, _stream()), name)
+    _sampler_stage("dxmi_dpm_stage", MT_COLS, mode, DPM_FIRST, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out,
+                   pred_xstart, hist=(hist,))
 
 
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)

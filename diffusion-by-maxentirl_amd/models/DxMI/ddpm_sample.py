@@ -9,7 +9,7 @@ on the noise-prediction network train_ddpm.py trains and the `Alpha_bar` table V
                        uploaded once per device.  Everything that differs from one transition to the next lives in the row, the
                        last-step behaviour included, so ONE captured step serves all of them.
   ddpm_transition      one transition as torch expressions on a row (the CPU path and the tests' float64 path)
-  ddpm_sample          the loop: per transition one network evaluation and one dxmi_ddpm_stage launch
+  ddpm_sample          the loop (models/DxMI/stage_loop.py): per transition one network evaluation and one dxmi_ddpm_stage launch
 
 One transition goes from t = tau_k to p = tau_{k-1}; a_t = Alpha_bar[t], a_p = Alpha_bar[p], a_p = 1 for the last one.
     sigma = eta sqrt((1 - a_p) / (1 - a_t)) sqrt(1 - a_t / a_p)                       eta in [0, 1]: 0 DDIM, 1 ancestral
@@ -22,18 +22,14 @@ One transition goes from t = tau_k to p = tau_{k-1}; a_t = Alpha_bar[t], a_p = A
 The run starts from x_T ~ N(0, I) and returns clamp(x_0, -1, 1).
 """
 import math
-import weakref
 
 import numpy as np
 import torch
 
-from dxmi_hip import graph as _graph
 from dxmi_hip import ops
-from dxmi_hip._lib import DxmiError
 
-from ..cm.karras_diffusion import _HostTable, _as_f32, _memo
-from ..cm.random_util import DeterministicGenerator, DummyGenerator
-from .ddpm_train import _hip_model
+from . import stage_loop as _loop
+from ..cm.karras_diffusion import _HostTable, _memo
 from .var_sampler import _step_tables, calc_diffusion_hyperparams
 
 SKIP_TYPES = ("uniform", "quad")
@@ -109,7 +105,10 @@ def ddpm_coefficients(alpha_bar, tau, eta=1.0, variance="small", beta=None):
 class DDPMSampleSchedule(_HostTable):
     """table: fp32 [S, ops.DT_COLS], row k = the transition tau_{S-1-k} -> tau_{S-2-k}.  The linear-form columns (XM, C, and S for
     variance 'small' without clipping) are _step_tables' scalar fp32 values; the clip-form columns, and S otherwise, are computed
-    in float64 from the fp32 Alpha_bar and rounded once.  draws[k]: whether transition k adds noise (S != 0)."""
+    in float64 from the fp32 Alpha_bar and rounded once.  draws[k]: whether transition k adds noise (S != 0).  The class
+    attributes are what stage_loop asks of a schedule."""
+    sampler, hist_slots = "ddpm_sample", 0
+    stage, FIRST, STEP, T_COL = staticmethod(ops.ddpm_stage), ops.DDPM_FIRST, ops.DDPM_STEP, ops.DT_T
 
     def __init__(self, steps=1000, eta=1.0, variance="small", skip_type="uniform", clip_denoised=True, T=1000, beta_0=1e-4,
                  beta_T=0.02):
@@ -136,6 +135,12 @@ class DDPMSampleSchedule(_HostTable):
         super().__init__(torch.from_numpy(tab))
         self.draws = [bool(v != 0) for v in tab[:, ops.DT_S]]
         self.n_draws = sum(self.draws)
+
+    def transition(self, x, eps, z, row, hist):
+        return ddpm_transition(x, eps, z, row)
+
+    def graph_name(self, shape, mode):
+        return f"ddpm_sample{(self.steps, tuple(shape), mode)}"
 
 
 _SCHEDULES = {}
@@ -165,145 +170,9 @@ def ddpm_transition(x, eps, z, row):
     return (xs + (control + s * z) if noisy else xs + control), x0
 
 
-# ------------------------------------------------------------------------------------------------- the loop
-def _progress(it, progress):
-    if progress:
-        try:
-            from tqdm.auto import tqdm
-            return tqdm(it)
-        except ImportError:
-            pass
-    return it
-
-
-def _evaluate(hip, net, x, t):
-    if hip is not None:
-        return hip.forward_inference(x, t)
-    eps = net(x, t)
-    assert eps.shape == x.shape, f"network output {tuple(eps.shape)} != sample shape {tuple(x.shape)}"
-    if eps.dtype != torch.float32 or not eps.is_contiguous() or eps.device != x.device:
-        eps = _as_f32(eps, x.device)
-    return eps
-
-
-def _sample_torch(sch, net, shape, device, generator, noise, callback, progress):
-    """The transitions as torch expressions: the CPU path of the host tests, and what the GPU tests compare the launches with."""
-    tab = sch.table.to(device)
-    if noise is not None:
-        x = noise[0].to(device=device, dtype=torch.float32).clone()
-    elif generator is not None:
-        x = generator.randn(*shape, device=device)
-    else:
-        x = torch.randn(shape, device=device)
-    for k in _progress(range(sch.steps), progress):
-        eps = net(x, torch.full((shape[0],), float(tab[k, ops.DT_T]), device=device))
-        z = None
-        if sch.draws[k]:
-            if noise is not None:
-                z = noise[k + 1].to(device=device, dtype=torch.float32)
-            else:
-                z = generator.randn_like(x) if generator is not None else torch.randn_like(x)
-        x, pred = ddpm_transition(x, eps, z, tab[k])
-        if callback is not None:
-            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x, "pred_xstart": pred})
-    return x.clamp(-1, 1)
-
-
-def _initial_state(x, shape, device, generator, noise):
-    if noise is not None:
-        x.copy_(noise[0])
-    elif generator is not None:
-        x.copy_(generator.randn(*shape, device=device))
-    else:
-        x.normal_()
-
-
-def _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress):
-    f32 = dict(dtype=torch.float32, device=device)
-    tab = sch.device_table(device)
-    x, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
-    _initial_state(x, shape, device, generator, noise)
-    fused = isinstance(generator, DeterministicGenerator)
-    idx = generator.get_indices(shape[0], device) if fused and sch.n_draws else None
-    zbuf = None
-    ops.ddpm_stage(ops.DDPM_FIRST, tab, t, row=0)
-    for k in _progress(range(sch.steps), progress):
-        eps = _evaluate(hip, net, x, t)
-        kw = {}
-        if sch.draws[k]:
-            if noise is not None:
-                kw["z"] = _as_f32(noise[k + 1], device)
-            elif fused:       # the draw generator.randn_like(x) would make, made inside the launch
-                kw.update(sample_index=idx, seed=generator.seed, draw=generator._next_draw())
-            elif generator is not None:
-                kw["z"] = _as_f32(generator.randn_like(x), device)
-            else:
-                zbuf = torch.empty(shape, **f32) if zbuf is None else zbuf
-                kw["z"] = zbuf.normal_()
-        pred = torch.empty(shape, **f32) if callback is not None else None
-        ops.ddpm_stage(ops.DDPM_STEP, tab, t, row=k, x=x, eps=eps, out=out, pred_xstart=pred, **kw)
-        if callback is not None:
-            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x.clone(), "pred_xstart": pred})
-    return out
-
-
-class _Replay:
-    """ONE transition (network evaluation + dxmi_ddpm_stage) as a StepGraph, and the static buffers it runs on.  The row, the draw
-    number and the seed reach the captured launch through a host input; the table, x, t, out and the index vector are static.
-    Holds the schedule: the captured launch reads its device table for as long as the graph lives."""
-
-    def __init__(self, sch, hip, net, shape, device, mode):
-        f32 = dict(dtype=torch.float32, device=device)
-        self.sch, self.hip, self.net, self.mode = sch, hip, net, mode
-        self.tab = sch.device_table(device)
-        self.x, self.t, self.out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
-        self.z = torch.empty(shape, **f32) if mode == "torch" else None
-        self.idx = torch.zeros(shape[0], dtype=torch.int64, device=device) if mode == "fused" else None
-        self.row = self.draw = self.seed = 0
-        self.graph = _graph.StepGraph(self._step, device, modules=_graph.pack_modules(hip if hip is not None else net),
-                                      name=f"ddpm_sample{(sch.steps, tuple(shape), mode)}")
-
-    def _control(self):
-        return [self.row, self.draw & 0xFFFFFFFF, self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF]
-
-    def _step(self):
-        eps = _evaluate(self.hip, self.net, self.x, self.t)
-        kw = {}
-        if self.mode == "torch":      # drawn in every transition: the captured step is the same for all rows (the last row's is unused)
-            kw["z"] = self.z.normal_()
-        elif self.mode == "fused":
-            kw["sample_index"] = self.idx
-        g = _graph.current()
-        if g is not None:
-            kw["ctl"] = g.host_input(torch.int32, 4, self._control)
-        else:
-            kw.update(row=self.row, draw=self.draw, seed=self.seed)
-        ops.ddpm_stage(ops.DDPM_STEP, self.tab, self.t, x=self.x, eps=eps, out=self.out, **kw)
-
-    def run(self, shape, device, generator):
-        sch = self.sch
-        _initial_state(self.x, shape, device, generator, None)       # None, or a deterministic generator (also when no row draws)
-        if self.mode == "fused":
-            self.idx.copy_(generator.get_indices(shape[0], device))
-            self.seed = int(generator.seed)
-        ops.ddpm_stage(ops.DDPM_FIRST, self.tab, self.t, row=0)
-        for k in range(sch.steps):
-            self.row = k
-            if self.mode == "fused" and sch.draws[k]:
-                self.draw = generator._next_draw()
-            self.graph()
-        return self.out
-
-
-_GRAPHS = weakref.WeakKeyDictionary()       # network -> {graph key: _Replay}
-
-
 def replay_graphs(net):
     """The StepGraphs ddpm_sample holds for `net` (their .captures / .replays count what ran)."""
-    try:
-        return [r.graph for r in _GRAPHS.get(net, {}).values()]
-    except TypeError:
-        return []
+    return _loop.replay_graphs(net, DDPMSampleSchedule.sampler)
 
 
 def ddpm_sample(net, shape, steps=1000, eta=1.0, variance="small", skip_type="uniform", clip_denoised=True, device=None,
@@ -324,28 +193,4 @@ def ddpm_sample(net, shape, steps=1000, eta=1.0, variance="small", skip_type="un
     captured step draws z in every transition, the last one's unused.  The returned tensor is then STATIC: the next call of the same
     key overwrites it."""
     sch = ddpm_sample_schedule(steps, eta, variance, skip_type, clip_denoised, T, beta_0, beta_T)
-    shape = tuple(int(s) for s in shape)
-    if noise is not None and len(noise) != sch.steps + 1:
-        raise ValueError(f"ddpm_sample: noise must hold {sch.steps + 1} draws (x_T and one per transition), got {len(noise)}")
-    hip = _hip_model(net)
-    if isinstance(generator, DummyGenerator):       # it forwards to torch: the same draws as no generator
-        generator = None
-    device = _graph.indexed_device(torch.device("cuda") if device is None else device)
-    with torch.no_grad():
-        if device.type != "cuda":
-            if hip is not None:
-                raise DxmiError("ddpm_sample: the HIP Model runs only on the device (a CPU device takes a torch callable)")
-            return _sample_torch(sch, net, shape, device, generator, noise, callback, progress)
-        replayable = generator is None or isinstance(generator, DeterministicGenerator)
-        if not (use_graph and callback is None and not progress and noise is None and replayable and not _graph.capturing()):
-            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
-        mode = "none" if not sch.n_draws else ("fused" if isinstance(generator, DeterministicGenerator) else "torch")
-        try:
-            graphs = _GRAPHS.setdefault(hip if hip is not None else net, {})
-        except TypeError:        # not weak-referenceable: no cache, so no replay
-            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
-        # what a capture freezes: the network (the dictionary's key), the shape and the device, the table, where z comes from, and
-        # whether pred_xstart is written (never under replay: it is the callback's)
-        key = (id(sch), shape, device.index, mode, False)
-        rp = _memo(graphs, key, 8, lambda: _Replay(sch, hip, net, shape, device, mode))
-        return rp.run(shape, device, generator)
+    return _loop.sample(sch, net, shape, device, generator, noise, callback, progress, use_graph, float64_state=False)

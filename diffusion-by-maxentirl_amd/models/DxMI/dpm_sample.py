@@ -7,7 +7,7 @@ orders 1-2, the training-free baseline a 10-step or 4-step DxMI sampler is measu
   dpm_coefficients     every per-transition scalar in float64 (the host tests' statement of the formulas)
   DPMSampleSchedule    one fp32 row per transition, noisiest first (columns ops.MT_*, include/dxmi_hip.h), built once on the host
   dpm_transition       one transition as torch expressions on a row, in the operation order of dxmi_dpm_stage
-  dpm_sample           the loop: per transition one network evaluation and one dxmi_dpm_stage launch
+  dpm_sample           the loop (models/DxMI/stage_loop.py): per transition one network evaluation and one dxmi_dpm_stage launch
 
 ab = Alpha_bar (the fp32 table read into float64), alpha = sqrt(ab), sigma = sqrt(1 - ab), lambda = log alpha - log sigma.  A run
 makes S evaluations and has S rows.  Row k < S - 1 goes from t = tau_{S-1-k} to p = tau_{S-2-k}, h = lambda_p - lambda_t > 0; row
@@ -25,19 +25,15 @@ With v = lambda_p - lambda both integrals are alpha_p times sums of the moments 
 evaluated by their series below h = 1 (no cancellation for the h ~ 5e-3 of adjacent steps) and by the recurrence above it.
 """
 import math
-import weakref
 
 import numpy as np
 import torch
 
-from dxmi_hip import graph as _graph
 from dxmi_hip import ops
-from dxmi_hip._lib import DxmiError
 
-from ..cm.karras_diffusion import _HostTable, _as_f32, _memo
-from ..cm.random_util import DeterministicGenerator, DummyGenerator
-from .ddpm_sample import _evaluate, _initial_state, _progress, ddpm_timesteps
-from .ddpm_train import _hip_model
+from . import stage_loop as _loop
+from ..cm.karras_diffusion import _HostTable, _memo
+from .ddpm_sample import ddpm_timesteps
 from .var_sampler import calc_diffusion_hyperparams
 
 ALGORITHMS = ("dpmsolver++", "sde-dpmsolver++")
@@ -177,7 +173,11 @@ def dpm_coefficients(alpha_bar, tau, algorithm="dpmsolver++", order=2, solver_ty
 
 class DPMSampleSchedule(_HostTable):
     """table: fp32 [S, ops.MT_COLS], row k = the transition tau_{S-1-k} -> tau_{S-2-k}: dpm_coefficients on the fp32 Alpha_bar in
-    float64, rounded once.  draws[k]: whether transition k adds noise (S != 0); coef: the float64 coefficients."""
+    float64, rounded once.  draws[k]: whether transition k adds noise (S != 0); coef: the float64 coefficients.  The class
+    attributes are what stage_loop asks of a schedule; the torch loop's state is float64 when noise[0] is (a float64 network then
+    runs in float64 on the widened fp32 table)."""
+    sampler, hist_slots = "dpm_sample", 3
+    stage, FIRST, STEP, T_COL = staticmethod(ops.dpm_stage), ops.DPM_FIRST, ops.DPM_STEP, ops.MT_T
 
     def __init__(self, steps=10, order=2, algorithm="dpmsolver++", solver_type="midpoint", skip_type="logsnr", lower_order_final=True,
                  clip_denoised=True, T=1000, beta_0=1e-4, beta_T=0.02):
@@ -206,6 +206,12 @@ class DPMSampleSchedule(_HostTable):
         super().__init__(torch.from_numpy(tab))
         self.draws = [bool(v != 0) for v in tab[:, ops.MT_S]]
         self.n_draws = sum(self.draws)
+
+    def transition(self, x, eps, z, row, hist):
+        return dpm_transition(x, eps, z, row, hist)
+
+    def graph_name(self, shape, mode):
+        return f"dpm_sample{(self.steps, self.order, self.algorithm, tuple(shape), mode)}"
 
 
 _SCHEDULES = {}
@@ -238,123 +244,9 @@ def dpm_transition(x, eps, z, row, hist=()):
     return acc, d0
 
 
-# ------------------------------------------------------------------------------------------------- the loop
-def _sample_torch(sch, net, shape, device, generator, noise, callback, progress):
-    """The transitions as torch expressions: the CPU path of the host tests.  The state takes the dtype of noise[0] when that is
-    float64 (a float64 network then runs in float64 on the widened fp32 table); it is fp32 otherwise."""
-    dtype = torch.float64 if noise is not None and noise[0].dtype == torch.float64 else torch.float32
-    tab = sch.table.to(device=device, dtype=dtype)
-    if noise is not None:
-        x = noise[0].to(device=device, dtype=dtype).clone()
-    elif generator is not None:
-        x = generator.randn(*shape, device=device)
-    else:
-        x = torch.randn(shape, device=device)
-    hist = []
-    for k in _progress(range(sch.steps), progress):
-        eps = net(x, torch.full((shape[0],), float(tab[k, ops.MT_T]), device=device, dtype=dtype))
-        z = None
-        if sch.draws[k]:
-            if noise is not None:
-                z = noise[k + 1].to(device=device, dtype=dtype)
-            else:
-                z = generator.randn_like(x) if generator is not None else torch.randn_like(x)
-        x, d0 = dpm_transition(x, eps, z, tab[k], hist)
-        hist = [d0] + hist[:1]
-        if callback is not None:
-            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x, "pred_xstart": d0})
-    return x.clamp(-1, 1)
-
-
-def _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress):
-    f32 = dict(dtype=torch.float32, device=device)
-    tab = sch.device_table(device)
-    x, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
-    hist = torch.empty((3,) + shape, **f32)
-    _initial_state(x, shape, device, generator, noise)
-    fused = isinstance(generator, DeterministicGenerator)
-    idx = generator.get_indices(shape[0], device) if fused and sch.n_draws else None
-    zbuf = None
-    ops.dpm_stage(ops.DPM_FIRST, tab, t, row=0)
-    for k in _progress(range(sch.steps), progress):
-        eps = _evaluate(hip, net, x, t)
-        kw = {}
-        if sch.draws[k]:
-            if noise is not None:
-                kw["z"] = _as_f32(noise[k + 1], device)
-            elif fused:       # the draw generator.randn_like(x) would make, made inside the launch
-                kw.update(sample_index=idx, seed=generator.seed, draw=generator._next_draw())
-            elif generator is not None:
-                kw["z"] = _as_f32(generator.randn_like(x), device)
-            else:
-                zbuf = torch.empty(shape, **f32) if zbuf is None else zbuf
-                kw["z"] = zbuf.normal_()
-        pred = torch.empty(shape, **f32) if callback is not None else None
-        ops.dpm_stage(ops.DPM_STEP, tab, t, row=k, x=x, eps=eps, hist=hist, out=out, pred_xstart=pred, **kw)
-        if callback is not None:
-            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x.clone(), "pred_xstart": pred})
-    return out
-
-
-class _Replay:
-    """ONE transition (network evaluation + dxmi_dpm_stage) as a StepGraph, and the static buffers it runs on: x, t, out and the
-    three history slots.  The row, the draw number and the seed reach the captured launch through a host input, and the launch
-    derives its history slots from the row, so the one captured step serves every row.  Holds the schedule: the captured launch
-    reads its device table for as long as the graph lives."""
-
-    def __init__(self, sch, hip, net, shape, device, mode):
-        f32 = dict(dtype=torch.float32, device=device)
-        self.sch, self.hip, self.net, self.mode = sch, hip, net, mode
-        self.tab = sch.device_table(device)
-        self.x, self.t, self.out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
-        self.hist = torch.empty((3,) + shape, **f32)
-        self.z = torch.empty(shape, **f32) if mode == "torch" else None
-        self.idx = torch.zeros(shape[0], dtype=torch.int64, device=device) if mode == "fused" else None
-        self.row = self.draw = self.seed = 0
-        self.graph = _graph.StepGraph(self._step, device, modules=_graph.pack_modules(hip if hip is not None else net),
-                                      name=f"dpm_sample{(sch.steps, sch.order, sch.algorithm, tuple(shape), mode)}")
-
-    def _control(self):
-        return [self.row, self.draw & 0xFFFFFFFF, self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF]
-
-    def _step(self):
-        eps = _evaluate(self.hip, self.net, self.x, self.t)
-        kw = {}
-        if self.mode == "torch":      # drawn in every transition: the captured step is the same for all rows (the last row's is unused)
-            kw["z"] = self.z.normal_()
-        elif self.mode == "fused":
-            kw["sample_index"] = self.idx
-        g = _graph.current()
-        if g is not None:
-            kw["ctl"] = g.host_input(torch.int32, 4, self._control)
-        else:
-            kw.update(row=self.row, draw=self.draw, seed=self.seed)
-        ops.dpm_stage(ops.DPM_STEP, self.tab, self.t, x=self.x, eps=eps, hist=self.hist, out=self.out, **kw)
-
-    def run(self, shape, device, generator):
-        sch = self.sch
-        _initial_state(self.x, shape, device, generator, None)       # None, or a deterministic generator (also when no row draws)
-        if self.mode == "fused":
-            self.idx.copy_(generator.get_indices(shape[0], device))
-            self.seed = int(generator.seed)
-        ops.dpm_stage(ops.DPM_FIRST, self.tab, self.t, row=0)
-        for k in range(sch.steps):
-            self.row = k
-            if self.mode == "fused" and sch.draws[k]:
-                self.draw = generator._next_draw()
-            self.graph()
-        return self.out
-
-
-_GRAPHS = weakref.WeakKeyDictionary()       # network -> {graph key: _Replay}
-
-
 def replay_graphs(net):
     """The StepGraphs dpm_sample holds for `net` (their .captures / .replays count what ran)."""
-    try:
-        return [r.graph for r in _GRAPHS.get(net, {}).values()]
-    except TypeError:
-        return []
+    return _loop.replay_graphs(net, DPMSampleSchedule.sampler)
 
 
 def dpm_sample(net, shape, steps=10, order=2, algorithm="dpmsolver++", solver_type="midpoint", skip_type="logsnr",
@@ -377,27 +269,4 @@ def dpm_sample(net, shape, steps=10, order=2, algorithm="dpmsolver++", solver_ty
     addresses from the row number.  Off with callback, progress or noise=.  The returned tensor is then STATIC: the next call of the
     same key overwrites it."""
     sch = dpm_sample_schedule(steps, order, algorithm, solver_type, skip_type, lower_order_final, clip_denoised, T, beta_0, beta_T)
-    shape = tuple(int(s) for s in shape)
-    if noise is not None and len(noise) != sch.steps + 1:
-        raise ValueError(f"dpm_sample: noise must hold {sch.steps + 1} draws (x_T and one per transition), got {len(noise)}")
-    hip = _hip_model(net)
-    if isinstance(generator, DummyGenerator):       # it forwards to torch: the same draws as no generator
-        generator = None
-    device = _graph.indexed_device(torch.device("cuda") if device is None else device)
-    with torch.no_grad():
-        if device.type != "cuda":
-            if hip is not None:
-                raise DxmiError("dpm_sample: the HIP Model runs only on the device (a CPU device takes a torch callable)")
-            return _sample_torch(sch, net, shape, device, generator, noise, callback, progress)
-        replayable = generator is None or isinstance(generator, DeterministicGenerator)
-        if not (use_graph and callback is None and not progress and noise is None and replayable and not _graph.capturing()):
-            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
-        mode = "none" if not sch.n_draws else ("fused" if isinstance(generator, DeterministicGenerator) else "torch")
-        try:
-            graphs = _GRAPHS.setdefault(hip if hip is not None else net, {})
-        except TypeError:        # not weak-referenceable: no cache, so no replay
-            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
-        # what a capture freezes: the network (the dictionary's key), the shape and the device, the table and where z comes from
-        key = (id(sch), shape, device.index, mode)
-        rp = _memo(graphs, key, 8, lambda: _Replay(sch, hip, net, shape, device, mode))
-        return rp.run(shape, device, generator)
+    return _loop.sample(sch, net, shape, device, generator, noise, callback, progress, use_graph, float64_state=True)

@@ -79,7 +79,7 @@ def launch(ops, tab, row, x, eps, z=None, pred=True, **kw):
 # ------------------------------------------------------------------------------------------ the launch against float64
 @pytest.mark.parametrize("variance", ["small", "large"])
 @pytest.mark.parametrize("clip", [True, False])
-@pytest.mark.parametrize("N,CHW", [(3, 75), (2, 192), (5, 3072), (1, 5000)])
+@pytest.mark.parametrize("N,CHW", [(3, 75), (2, 192), (5, 3072), (1, 5000), (1, 263347)])
 def test_stage_vs_fp64(ops, N, CHW, clip, variance):
     sch = schedule(clip, variance)
     tab = sch.device_table(DEV)

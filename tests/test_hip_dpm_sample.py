@@ -32,7 +32,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "diffusion-by-maxentirl_amd")
 STEPS = 10
 ODE, SDE = "dpmsolver++", "sde-dpmsolver++"
-SHAPES = [(3, 75), (2, 192), (5, 3072), (1, 5000)]
+SHAPES = [(3, 75), (2, 192), (5, 3072), (1, 5000), (1, 263347)]
 SENTINEL = 123.0
 
 
