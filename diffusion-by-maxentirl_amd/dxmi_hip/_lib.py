@@ -63,6 +63,11 @@ SIGNATURES = {
     "dxmi_gn_ss_grads": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dxmi_fid_stats_workspace_bytes": (c_int64, [c_int64, c_int]),
     "dxmi_fid_stats": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dxmi_frechet_workspace_bytes": (c_int64, [c_int]),
+    "dxmi_gemm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
+    "dxmi_frob_norm_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "dxmi_scale_f64": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p]),
+    "dxmi_symmetrize_f64": (c_int, [c_void_p, c_int, c_void_p]),
     "dxmi_knn_radii_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
     "dxmi_knn_radii": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dxmi_pr_membership_workspace_bytes": (c_int64, [c_int64, c_int64]),

@@ -1527,6 +1527,109 @@ def fid_stats(act):
     return mu, sigma
 
 
+# ------------------------------------------------------------------------------------------ Frechet distance in fp64 (csrc/frechet.hip)
+def _square_f64(x, what):
+    _need_cuda(x)
+    if not (x.dim() == 2 and x.shape[0] == x.shape[1] and x.dtype == torch.float64 and x.is_contiguous()):
+        raise ValueError(f"{what}: need a contiguous float64 [n, n] device tensor, got {tuple(x.shape)} {x.dtype}")
+    return x.shape[0]
+
+
+def gemm_f64(a, b, alpha=1.0, diag=0.0, out=None, trace=None):
+    """C = alpha * A @ B + diag * I for fp64 [n, n] device tensors (n % 16 == 0, 16 <= n <= 4096) on the f64 MFMA.  `trace`: a
+    one-element fp64 device tensor that receives trace(C).  `out` must not share memory with `a` or `b`."""
+    n = _square_f64(a, "gemm_f64(a)")
+    if _square_f64(b, "gemm_f64(b)") != n:
+        raise ValueError(f"gemm_f64: a is {n} x {n}, b is {b.shape[0]} x {b.shape[0]}")
+    if out is None:
+        out = torch.empty_like(a)
+    elif _square_f64(out, "gemm_f64(out)") != n:
+        raise ValueError("gemm_f64: out has another size")
+    if trace is not None:
+        _need_cuda(trace)
+        assert trace.dtype == torch.float64 and trace.numel() == 1
+    _prof("frechet", f"gemm_f64_n{n}", 2.0 * n * n * n, 24.0 * n * n, lambda: check(
+        load().dxmi_gemm_f64(_ptr(a), _ptr(b), _ptr(out), n, float(alpha), float(diag), _ptr(trace), _stream()), "dxmi_gemm_f64"))
+    return out
+
+
+def frob_norm_f64(x, out=None):
+    """||x||_F of an fp64 [n, n] device tensor -> one-element fp64 device tensor (fixed summation order)."""
+    n = _square_f64(x, "frob_norm_f64")
+    lib = load()
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=x.device)
+    ws = _workspace(max(256, lib.dxmi_frechet_workspace_bytes(n)), x.device)
+    _prof("frechet", f"frob_n{n}", 2.0 * n * n, 8.0 * n * n, lambda: check(
+        lib.dxmi_frob_norm_f64(_ptr(x), n, _ptr(out), _ptr(ws), _stream()), "dxmi_frob_norm_f64"))
+    return out
+
+
+def scale_f64(x, alpha, out=None):
+    """alpha * x for an fp64 [n, n] device tensor (`out` may be `x`)."""
+    n = _square_f64(x, "scale_f64")
+    if out is None:
+        out = torch.empty_like(x)
+    elif _square_f64(out, "scale_f64(out)") != n:
+        raise ValueError("scale_f64: out has another size")
+    _prof("frechet", f"scale_n{n}", 1.0 * n * n, 16.0 * n * n, lambda: check(
+        load().dxmi_scale_f64(_ptr(x), _ptr(out), n, float(alpha), _stream()), "dxmi_scale_f64"))
+    return out
+
+
+def symmetrize_f64(x):
+    """x <- (x + x^T) / 2 in place (fp64 [n, n] device tensor)."""
+    n = _square_f64(x, "symmetrize_f64")
+    _prof("frechet", f"symmetrize_n{n}", 1.0 * n * n, 16.0 * n * n, lambda: check(
+        load().dxmi_symmetrize_f64(_ptr(x), n, _stream()), "dxmi_symmetrize_f64"))
+    return x
+
+
+def _newton_schulz_sqrt(m, tol, max_iters, eye, want_matrix):
+    """Coupled Newton-Schulz iteration on a symmetric PSD fp64 device matrix: Y -> (m / c)^(1/2), Z -> its inverse, c = ||m||_F.
+    -> (m^(1/2) or None, trace of it, iterations, converged).  Per iteration three GEMMs and one 8-byte readback (the trace)."""
+    c = float(frob_norm_f64(m).item())
+    y = scale_f64(m, 1.0 / c if c != 0.0 else float("inf"))
+    z = eye.clone()
+    t, y2, z2 = torch.empty_like(m), torch.empty_like(m), torch.empty_like(m)
+    tr_dev = torch.empty(1, dtype=torch.float64, device=m.device)
+    rc = c ** 0.5 if c >= 0.0 else float("nan")
+    prev, tr, k, ok = None, float("nan"), 0, False
+    while k < max_iters:
+        gemm_f64(z, y, -0.5, 1.5, out=t)
+        gemm_f64(y, t, out=y2, trace=tr_dev)
+        gemm_f64(t, z, out=z2)
+        y, y2, z, z2 = y2, y, z2, z
+        k += 1
+        tr = float(tr_dev.item()) * rc
+        if tr != tr or tr in (float("inf"), float("-inf")):
+            break
+        if prev is not None and abs(tr - prev) <= tol * abs(tr):
+            ok = True
+            break
+        prev = tr
+    return (scale_f64(y, rc, out=y) if want_matrix and ok else None), tr, k, ok
+
+
+def frechet_trace_sqrt(sigma1, sigma2, tol=1e-8, max_iters=100):
+    """tr sqrt(sigma1 sigma2) of two symmetric PSD fp64 [n, n] device matrices -> (trace, (k1, k2), converged), by the two-stage
+    Newton-Schulz iteration on symmetric matrices: R = sigma1^(1/2), then the trace of (R sigma2 R)^(1/2).  A stage
+    ends not converged when its trace is not finite or after max_iters iterations; k2 = 0 when stage 1 did not converge.
+    Everything stays on the device but the norm of each stage and one trace per iteration."""
+    n = _square_f64(sigma1, "frechet_trace_sqrt(sigma1)")
+    if _square_f64(sigma2, "frechet_trace_sqrt(sigma2)") != n:
+        raise ValueError("frechet_trace_sqrt: sigma1 and sigma2 differ in size")
+    eye = torch.eye(n, dtype=torch.float64, device=sigma1.device)
+    r, _, k1, ok = _newton_schulz_sqrt(sigma1, tol, max_iters, eye, True)
+    if not ok:
+        return float("nan"), (k1, 0), False
+    symmetrize_f64(r)
+    m = gemm_f64(gemm_f64(r, sigma2), r)
+    symmetrize_f64(m)
+    _, tr, k2, ok = _newton_schulz_sqrt(m, tol, max_iters, eye, False)
+    return tr, (k1, k2), ok
+
+
 # ------------------------------------------------------------------------------------------ evaluator metrics
 KNN_KMAX = 7
 

@@ -5,6 +5,7 @@
     act = gather_activations(act)                                                      # all_gather over ranks (RCCL)
     m1, s1 = activation_statistics(act)                                                # np.mean / np.cov -> HIP (f32 MFMA)
     fid = calculate_frechet_distance(m1, s1, m2, s2)                                   # float64 host algorithm, as the reference
+    fid = calculate_frechet_distance_device(m1, s1, m2, s2)                            # or: fp64 MFMA Newton-Schulz on the device
 
 The feature extractor is an argument — any callable `extractor(batch) -> [features [B, dims, h, w]]` with the reference
 extractor's call convention (`model(batch)[0]`, fid_score.py:208); `load_extractor("module:attr")` resolves one from the command
@@ -79,14 +80,17 @@ def gather_activations(act):
     return torch.cat(parts)
 
 
-def activation_statistics(act):
+def activation_statistics(act, keep_on_device=False):
     """(mu, sigma) = (np.mean(act, axis=0), np.cov(act, rowvar=False)) of fp32 activations [N, dims] (reference
     train_image_large.py:68, fid_score.py:300-302), computed on the device by `dxmi_fid_stats` (f32-input MFMA Gram matrix, fp64
-    fold); returned as float64 numpy arrays, which is what `calculate_frechet_distance` takes.  Device tensors only: there is
-    no CPU path in this package."""
+    fold); returned as float64 numpy arrays, which is what `calculate_frechet_distance` takes -- or, with keep_on_device, as the
+    fp64 device tensors themselves, which `calculate_frechet_distance_device` takes without a round trip of the covariance
+    through the host.  Device tensors only: there is no CPU path in this package."""
     if not (torch.is_tensor(act) and act.is_cuda):
         raise DxmiError("pytorch_fid.activation_statistics needs a device tensor (the HIP path is the only one)")
     mu, sigma = ops.fid_stats(act.float().contiguous())
+    if keep_on_device:
+        return mu, sigma
     return mu.cpu().numpy(), sigma.cpu().numpy()
 
 
@@ -112,6 +116,45 @@ def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
             raise ValueError("Imaginary component {}".format(np.max(np.abs(covmean.imag))))
         covmean = covmean.real
     return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
+
+
+# which path the last calculate_frechet_distance_device call took: "device" (the kernels' value was returned) or "host" (the
+# iteration did not converge and calculate_frechet_distance was called); iterations = (stage 1, stage 2) of the device iteration
+last_distance_info = {"path": None, "iterations": (0, 0)}
+
+
+def _host_f64(x):
+    return x.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(x) else np.asarray(x, dtype=np.float64)
+
+
+def calculate_frechet_distance_device(mu1, sigma1, mu2, sigma2, eps=1e-6, device=None):
+    """The same distance with Tr sqrt(C1 C2) from `ops.frechet_trace_sqrt`: the two-stage Newton-Schulz iteration on symmetric
+    matrices in fp64 on the device (csrc/frechet.hip).  Inputs as the host function's (numpy arrays or tensors; covariances that
+    are already fp64 device tensors are used where they lie).  The mean term and the two traces are formed in float64 on the host
+    from the means and the diagonals.  If the iteration does not converge (rank-deficient or non-finite input), one line says so
+    and the value of the host `calculate_frechet_distance(..., eps)` is returned; `last_distance_info` tells which path ran."""
+    if not torch.cuda.is_available():
+        raise DxmiError("pytorch_fid.calculate_frechet_distance_device needs a GPU (calculate_frechet_distance is the host algorithm)")
+    if device is None:
+        device = next((t.device for t in (sigma1, sigma2) if torch.is_tensor(t) and t.is_cuda), torch.device("cuda"))
+    mu1, mu2 = np.atleast_1d(_host_f64(mu1)), np.atleast_1d(_host_f64(mu2))
+    if mu1.shape != mu2.shape:
+        raise AssertionError("Training and test mean vectors have different lengths")
+    dev = []
+    for s in (sigma1, sigma2):
+        t = s if torch.is_tensor(s) else torch.from_numpy(np.atleast_2d(np.asarray(s, dtype=np.float64)))
+        dev.append(t.to(device=device, dtype=torch.float64).contiguous())
+    if dev[0].shape != dev[1].shape:
+        raise AssertionError("Training and test covariances have different dimensions")
+    tr_sqrt, iterations, converged = ops.frechet_trace_sqrt(dev[0], dev[1])
+    if not converged:
+        print(f"fid calculation on the device did not converge after {iterations} iterations; using the host algorithm")
+        last_distance_info.update(path="host", iterations=iterations)
+        return calculate_frechet_distance(mu1, _host_f64(sigma1), mu2, _host_f64(sigma2), eps)
+    last_distance_info.update(path="device", iterations=iterations)
+    diff = mu1 - mu2
+    tr1, tr2 = (d.diagonal().cpu().numpy().sum() for d in dev)
+    return diff.dot(diff) + tr1 + tr2 - 2 * tr_sqrt
 
 
 IMAGE_EXTENSIONS = {"bmp", "jpg", "jpeg", "pgm", "png", "ppm", "tif", "tiff", "webp"}
@@ -157,10 +200,16 @@ def calculate_fid_given_paths(paths, batch_size, device, dims, resize=0, extract
     return calculate_frechet_distance(m1, s1, m2, s2)
 
 
-def fid_from_images(images_u8, extractor, m2, s2, batch_size=50, dims=2048, device="cuda"):
+def fid_from_images(images_u8, extractor, m2, s2, batch_size=50, dims=2048, device="cuda", distance="host"):
     """The body of the reference's fid() (train_image_large.py:56-70) for this rank's uint8 images [n, 3, H, W]: scale to
-    [0, 1], extract, gather over ranks, statistics on the device, distance on rank 0's host.  Every rank returns the value."""
+    [0, 1], extract, gather over ranks, statistics on the device, then the distance: distance="host" on the host as the reference,
+    distance="device" on the fp64 kernels with the statistics left where they are.  Every rank returns the value."""
+    if distance not in ("host", "device"):
+        raise ValueError(f"fid_from_images: distance is 'host' or 'device', got {distance!r}")
     x = (images_u8.to(device) / 255.0).float()
     act = gather_activations(get_activations_from_tensor(x, extractor, batch_size=batch_size, dims=dims, device=device))
+    if distance == "device":
+        m1, s1 = activation_statistics(act, keep_on_device=True)
+        return float(calculate_frechet_distance_device(m1, s1, m2, s2))
     m1, s1 = activation_statistics(act)
     return float(calculate_frechet_distance(m1, s1, np.asarray(m2), np.asarray(s2)))

@@ -10,9 +10,10 @@ net / sampler / value from `_target_`, Adam with the log_betas / rest split (ref
 per-rank batch = batchsize // world, epoch loop of `train_one_epoch` (:141-205), checkpoints with the
 reference's file names and state-dict keys (:58-78, :459-462).  Differences, all outside the
 accelerated path: gradients are exchanged by one flat RCCL all-reduce per backward instead of DDP
-buckets (dxmi_hip/dist.py); FID / wandb / tensorboard are skipped unless their packages and the dataset
-PNG folder exist; `--data_npz PATH` trains on a uint8 image array file (dxmi_hip/data.py ImageStore: ToTensor's scaling, random
-horizontal flips, `--data_resident auto|device|host`); `--synthetic_data` feeds uniform images (benchmarks, smoke runs).
+buckets (dxmi_hip/dist.py); wandb / tensorboard logging is skipped; the in-training FID (training.fid_epoch / training.fid_every,
+best sampler kept as sampler.pth / value.pth) runs on the device from `--fid_extractor module:attr --fid_stats stats.npz`
+(FidEvaluator; without the two flags no FID is computed) instead of from PNG folders; `--data_npz PATH` trains on a uint8 image
+array file (dxmi_hip/data.py ImageStore: ToTensor's scaling, random horizontal flips, `--data_resident auto|device|host`); `--synthetic_data` feeds uniform images (benchmarks, smoke runs).
 """
 import argparse
 import os
@@ -71,12 +72,66 @@ def make_loader(args, cfg, device, rank, world, epoch, store=None):
     return DataLoader(train_set, batch_size=batchsize, shuffle=ds is None, sampler=ds, num_workers=4, pin_memory=True, drop_last=True)
 
 
-def train_one_epoch(trainer, sampler, dataloader, n_critic, n_generator, device, log_every, state, normalised=False, max_iters=None):
-    """reference train_one_epoch (:141-205) without the FID / logging side paths.  normalised: the loader's images are already in
-    [-1, 1] (ImageStore); max_iters: stop inside the epoch once state['i_iter'] reaches it."""
+class FidEvaluator:
+    """The reference's in-training FID (train_cifar10.py:81-139, :384-442) on the device: int(n_fid_samples / sampling_batchsize /
+    world) batches per rank from the sampler in eval(), each quantised to uint8 as save_image would store it before the next
+    sample() call (with use_graph the returned tensors are the graph's static outputs), activations gathered over RCCL, statistics
+    by dxmi_fid_stats, the distance by `distance` ("device": fp64 MFMA Newton-Schulz, "host": scipy's sqrtm).  Every rank computes
+    the same value; rank 0 keeps the best-scoring sampler as sampler.pth / value.pth, which is what generate_cifar10.py loads.
+    The samples go to no replay ring, and the sampler's train() / eval() flag is put back."""
+
+    def __init__(self, args, cfg, trainer, sampler, logdir, device, rank, world):
+        from pytorch_fid.fid_score import load_extractor, load_statistics
+        extractor = load_extractor(args.fid_extractor)
+        self.extractor = extractor.to(device) if hasattr(extractor, "to") else extractor
+        self.m2, self.s2 = load_statistics(args.fid_stats)
+        self.dims, self.distance = args.fid_dims, args.fid_distance
+        self.n_batches = int(cfg.training.n_fid_samples / cfg.training.sampling_batchsize / world)
+        self.sampling_batchsize = cfg.training.sampling_batchsize
+        self.trainer, self.sampler, self.logdir, self.device, self.rank = trainer, sampler, logdir, device, rank
+        self.best_fid = float("inf")
+
+    def __call__(self, epoch, i_iter):
+        from dxmi_hip import ops
+        from pytorch_fid.fid_score import fid_from_images
+        was_training = self.sampler.training
+        print0("generating images for FID evaluation")
+        self.sampler.eval()
+        images = torch.cat([ops.quantize_u8(self.sampler.sample(self.sampling_batchsize, device=self.device)["sample"], mode=0, nhwc=False)
+                            for _ in range(self.n_batches)])
+        print0("calculating FID score")
+        fid = fid_from_images(images, self.extractor, self.m2, self.s2, batch_size=50, dims=self.dims, device=self.device,
+                              distance=self.distance)
+        if self.rank == 0 and fid < self.best_fid:
+            self.best_fid = fid
+            path = os.path.join(self.logdir, "sampler.pth")
+            torch.save({"state_dict": self.trainer.sampler.net.state_dict(), "fid": fid, "epoch": epoch, "iter": i_iter}, path)
+            if self.trainer.v is not None:
+                torch.save({"state_dict": self.trainer.v.state_dict()}, os.path.join(self.logdir, "value.pth"))
+            print0(f"best FID: sampler saved at {path}")
+        print0(f"FID score: {fid}")
+        self.sampler.train(was_training)
+        return fid
+
+
+def check_fid_schedule(cfg):
+    """(fid_every, fid_epoch) of cfg.training; setting both is refused as the reference refuses it (:251-253)."""
+    fid_every, fid_epoch = cfg.training.get("fid_every"), cfg.training.get("fid_epoch")
+    if fid_every is not None and fid_epoch is not None:
+        raise ValueError("cannot set both fid_epoch and fid_every")
+    return fid_every, fid_epoch
+
+
+def train_one_epoch(trainer, sampler, dataloader, n_critic, n_generator, device, log_every, state, normalised=False, max_iters=None,
+                    fid_every=None, evaluate=None):
+    """reference train_one_epoch (:141-205) without the logging side paths.  normalised: the loader's images are already in
+    [-1, 1] (ImageStore); max_iters: stop inside the epoch once state['i_iter'] reaches it; evaluate(i_iter): called at the top of
+    every iteration with i_iter % fid_every == 0, iteration 0 included (reference :165-167)."""
     # device-resident replay ring: n_critic trajectories of T transitions each, generated in place by the sampler
     buf = TransitionRing(n_critic, trainer.n_timesteps, trainer.batchsize, sampler.sample_shape, device)
     for step, (images, _) in enumerate(dataloader):
+        if evaluate is not None and fid_every is not None and state["i_iter"] % fid_every == 0:
+            evaluate(state["i_iter"])
         sampler.eval()
         images = images.to(device) if normalised else (2 * images - 1).to(device)
         in_ring = len(images) == trainer.batchsize
@@ -132,6 +187,13 @@ def parse_args(argv=None):
     ap.add_argument("--no_graph", action="store_true",
                     help="issue every kernel launch from python instead of replaying the generation call and the two updates as hipGraphs "
                          "(dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
+    ap.add_argument("--fid_extractor", type=str, default=None,
+                    help="'module:attribute' of the FID feature extractor (the reference builds pytorch_fid's InceptionV3, whose weights "
+                         "this image cannot download); with --fid_stats it enables the FID of training.fid_epoch / training.fid_every")
+    ap.add_argument("--fid_stats", type=str, default=None, help="dataset statistics npz (`mu`, `sigma`)")
+    ap.add_argument("--fid_dims", type=int, default=2048)
+    ap.add_argument("--fid_distance", choices=("device", "host"), default="device",
+                    help="the Frechet distance of an evaluation: fp64 MFMA Newton-Schulz on the device, or scipy's sqrtm on the host")
     args, unknown = ap.parse_known_args(argv)
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")
@@ -193,12 +255,20 @@ def main():
     store = make_store(args, cfg, device, local_rank, world)
     if store is not None:
         print0(store.describe())
+    # in-training FID (reference :81-139, :384-442): on with --fid_extractor and --fid_stats, scheduled by the config
+    fid_every = fid_epoch = evaluator = None
+    if args.fid_extractor is not None and args.fid_stats is not None:
+        fid_every, fid_epoch = check_fid_schedule(cfg)
+        evaluator = FidEvaluator(args, cfg, trainer, sampler, logdir, device, local_rank, world)
     state = {"i_iter": 0}
     for epoch in range(cfg.training.n_epochs):
         loader = make_loader(args, cfg, device, local_rank, world, epoch, store)
         train_one_epoch(trainer, sampler, loader, cfg.training.n_critic, cfg.training.n_generator, device,
                         cfg.training.log_every, state, normalised=store is not None,
-                        max_iters=args.max_iters if store is not None else None)
+                        max_iters=args.max_iters if store is not None else None,
+                        fid_every=fid_every, evaluate=None if evaluator is None else (lambda it, e=epoch: evaluator(e, it)))
+        if evaluator is not None and fid_epoch is not None and epoch % fid_epoch == 0:
+            evaluator(epoch, state["i_iter"])           # the sampler as it stands after this epoch
         if args.max_iters is not None and state["i_iter"] >= args.max_iters:
             break
     if store is not None:

@@ -112,6 +112,8 @@ def parse_args(argv=None):
                          "this image cannot download); with --fid_stats it enables the periodic fid() of training.fid_every")
     ap.add_argument("--fid_stats", type=str, default=None, help="dataset statistics npz (`mu`, `sigma`; reference: datasets/VIRTUAL_*.npz)")
     ap.add_argument("--fid_dims", type=int, default=2048)
+    ap.add_argument("--fid_distance", choices=("device", "host"), default="host",
+                    help="the Frechet distance of an evaluation: scipy's sqrtm on the host, or fp64 MFMA Newton-Schulz on the device")
     ap.add_argument("--no_graph", action="store_true",
                     help="issue every kernel launch from python instead of replaying the three phases of an iteration as hipGraphs "
                          "(dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
@@ -210,7 +212,8 @@ def main():
             parts = [torch.zeros_like(samples) for _ in range(world)]
             torch.distributed.all_gather(parts, samples)
             samples = torch.cat(parts)
-        value = fid_from_images(samples[local_rank::world], extractor, m2, s2, batch_size=50, dims=args.fid_dims, device=device)
+        value = fid_from_images(samples[local_rank::world], extractor, m2, s2, batch_size=50, dims=args.fid_dims, device=device,
+                                distance=args.fid_distance)
         print0(f"FID: {value}")
         if local_rank == 0 and value < best_fid:
             best_fid = value

@@ -717,11 +717,29 @@ int dxmi_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t n_r
  * 768 / 2048) -> mu fp64 [D], sigma fp64 [D, D] (unbiased, N - 1, as np.cov).  Column means in fp64; the centred Gram matrix on
  * the f32-input MFMA (exact fp32 products, fp32 accumulation inside a row split), splits folded in fp64 in a fixed order
  * (bitwise reproducible).  workspace: dxmi_fid_stats_workspace_bytes(N, D) bytes.
- * The Frechet distance itself (a 2048 x 2048 matrix square root, fid_score.py:224-281) stays the reference's float64 host
- * algorithm (scipy.linalg.sqrtm) in pytorch_fid/fid_score.py of this package.
+ * The Frechet distance itself (a 2048 x 2048 matrix square root, fid_score.py:224-281) has two forms in pytorch_fid/fid_score.py of
+ * this package: calculate_frechet_distance, the reference's float64 host algorithm (scipy.linalg.sqrtm), and its device sibling
+ * calculate_frechet_distance_device on the fp64 kernels below.
  * ---------------------------------------------------------------------------------------- */
 int64_t dxmi_fid_stats_workspace_bytes(int64_t N, int32_t D);
 int dxmi_fid_stats(const float* act, int64_t N, int32_t D, double* mu, double* sigma, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * fp64 matrix kernels of the Frechet distance (csrc/frechet.hip): tr sqrt(S1 S2) of symmetric PSD S1, S2 by the
+ * coupled Newton-Schulz iteration on symmetric matrices (dxmi_hip/ops.py frechet_trace_sqrt holds the loop).  All matrices are
+ * fp64 row-major n x n on the device, n % 16 == 0, 16 <= n <= 4096.  Every reduction runs in a fixed order without atomics: two
+ * calls give bitwise the same result.  Inf and NaN flow through as arithmetic.
+ *
+ * dxmi_gemm_f64: C = alpha * A * B + diag * I on v_mfma_f64_16x16x4_f64.  A, B, C 16-byte aligned; C must not overlap A or B
+ * (A may be B).  trace, if not NULL, receives trace(C) as a device double (a second, one-workgroup launch over C's diagonal).
+ * dxmi_frob_norm_f64: *out = ||X||_F (device double); workspace: dxmi_frechet_workspace_bytes(n) bytes.
+ * dxmi_scale_f64: Y = alpha * X (Y may be X itself).   dxmi_symmetrize_f64: X <- (X + X^T) / 2 in place.
+ * ---------------------------------------------------------------------------------------- */
+int64_t dxmi_frechet_workspace_bytes(int32_t n);
+int dxmi_gemm_f64(const double* A, const double* B, double* C, int32_t n, double alpha, double diag, double* trace, void* stream);
+int dxmi_frob_norm_f64(const double* X, int32_t n, double* out, void* workspace, void* stream);
+int dxmi_scale_f64(const double* X, double* Y, int32_t n, double alpha, void* stream);
+int dxmi_symmetrize_f64(double* X, int32_t n, void* stream);
 
 /* ----------------------------------------------------------------------------------------
  * Sample-quality metrics of the ADM evaluator (reference evaluations/evaluator.py), csrc/eval_metrics.hip.
