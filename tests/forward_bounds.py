@@ -45,10 +45,29 @@ of a bf16 rounding midpoint the kernel's fp32 value may round the other way: suc
 Depth K plus the bias add; post_act as for the conv; fp32 output:  |got - ref| <= L (K + 2) u32 A + 4 u32 |ref| + tie term.
 
 Attention.  P is rounded to bf16 before the P V product (an MFMA operand), so the output is judged by rel-L2 per (image, head,
-128-row block) within 8 u16, as the backward is.  The row log-sum-exp the kernels keep is in the LOG2 domain:
+128-row block) within 8 u16, as the backward is (and element by element: next paragraph).  The row log-sum-exp the kernels keep is in the LOG2 domain:
 lse2 = log2 sum_j 2^(s_ij log2 e), s = scale q.k.  A score is an fp32 sum of D exact products (error D u32 scale sum|q||k|),
 2^x is evaluated to ~2 ulp and summed over T keys, so element-wise
     |got - lse2| <= log2(e) (D + 2) u32 scale max_j sum_d |q_id k_jd| + (T + 8) u32 log2(e) + 4 u32 |lse2|
+
+Attention, element by element (attn_elem_bound; ops.attention alone: a fused projection or GroupNorm-on-load sits outside it).
+The per-block rel-L2 averages over 128 rows x D columns: one query row that is 10 % wrong moves it by 0.1 / sqrt(128) = 0.9 %,
+under 8 u16 = 3.1 %, and it cannot take a ragged T at all.  What the kernels compute (attention_kernel<D>, attention64_kernel,
+attention256_kernel<false>), with P = softmax(s) in fp64, o = P v and a_id = sum_j P_ij |v_jd|:
+  * a score is an fp32 sum of D exact bf16 products, scaled once by scale * log2(e) (one rounded constant, one product):
+    |s32_ij - s_ij| <= delta_i = (D + 2) u32 smag_i in natural-log units, smag_i = scale max_j sum_d |q_id k_jd| (attention_ref's).
+  * p_ij = exp2(t_ij - m_i) in fp32, m_i a running maximum.  The quotient p_ij / sum_j p_ij does not depend on m_i, so only the
+    score errors matter: the numerator moves by a factor within e^(+-delta_i) and so does the denominator, 2 delta_i on the
+    quotient (first order).  The subtraction and exp2 round to a few ulps of fp32: part of the (T + 8) u32 below.
+  * l_i SUMS THE UNROUNDED p (fp32), the P V operand is p rounded to bf16, round to nearest: each term of the numerator carries a
+    relative error <= 2^-9 <= u16 that the denominator does not share, u16 a_id in all.
+  * O accumulates in fp32 over the T keys and l over the same T terms, with one rescale of both per key block when the maximum
+    moved (skipped when no lane's did): recursive sums of depth <= T, the rescales and exp2's ulps in the + 8: (T + 8) u32 a_id.
+  * O / l is one reciprocal and one product in fp32, then one bf16 store: (u16 + 4 u32) |o_id|, and (1 + u16) on what came before.
+    |got_id - o_id| <= (u16 + 2 delta_i + (T + 8) u32) a_id (1 + u16) + (u16 + 4 u32) |o_id|
+The u16 terms carry the bound (T u32 is 1e-5 at T = 200); a wrong key set does not fit: with every true score near -9
+(below_zero of attn_inputs) one zero-filled key left unmasked holds nearly all of a row's weight and misses the bound ~100 times
+over, where under Gaussian q, k it moves the denominator T e^0.5 by 0.3 %, below u16 (test_forward_bounds.py measures both).
 
 InceptionV3 extractor (csrc/inception_ops.hip).  Bounds of the extractor's launches (tests/test_hip_inception_launches.py).
 
@@ -285,6 +304,107 @@ def gn_fused_bound(yo, parts, gamma, beta, d, silu, dh):
     return gn_bound(yo, parts, gamma, beta, d, silu) + L * gamma.double().abs() * p["film"].abs() * lin * (1 + U16)
 
 
+MIN_COND = 8.0           # the smallest (image, group) |mean| / std a GroupNorm input of the suites is conditioned to
+
+
+def gn_input(g, N, H, W, C, cond, groups=32):
+    """bf16 activation (on g's device) whose (image, group) |mean| / std spread up to `cond`: one offset per group, uniform in
+    [-cond, cond] (unit-variance noise inside), the largest |offset| of every image set to cond; image 0's first group zero-mean
+    with a tiny variance, where eps matters."""
+    dev = g.device
+    off = (torch.rand(N, groups, generator=g, device=dev) * 2 - 1) * cond
+    off[torch.arange(N, device=dev), off.abs().argmax(1)] = cond
+    x = torch.randn(N, H, W, C, generator=g, device=dev) + off.repeat_interleave(C // groups, 1)[:, None, None, :]
+    x[0, :, :, :C // groups] = 0.003 * torch.randn(H, W, C // groups, generator=g, device=dev)
+    return x.to(torch.bfloat16)
+
+
+def block_stats_tensor(x, P):
+    """fp32 BlockStats buffer [N, P, C/2, 2] of x: P contiguous chunks of ceil(HW / P) pixels (the last ones short or empty when
+    P does not divide HW), sums in fp64 then rounded once."""
+    N, H, W, C = x.shape
+    HW = H * W
+    per = -(-HW // P)
+    xd = x.double().reshape(N, HW, C // 2, 2)
+    xd = torch.cat([xd, xd.new_zeros(N, P * per - HW, C // 2, 2)], 1).reshape(N, P, per, C // 2, 2)
+    return torch.stack([xd.sum((2, 4)), xd.square().sum((2, 4))], -1).float().contiguous()
+
+
+def gn_fwd_plan(C0, C1, HW, groups=32):
+    """The slicing walk of dxmi_groupnorm_silu_fwd (csrc/groupnorm.hip) restated -> the plan of gn_silu_kernel<VEC, PIECES>, or
+    None where dxmi_groupnorm_silu_supported refuses: VEC channels per piece, `slices` channel slices (whole groups each), ppp
+    pieces per pixel of a slice, `threads` a multiple of lcm(ppp, 64), `pieces` per thread (<= 16 at VEC 8, <= 32 at VEC 4 before
+    another halving is tried; <= 32 at the last), `ragged` when the last piece of some thread lies past the map, ppt pieces per
+    group and pixel, `fast`: the xor-shuffle group reduce (else a masked wave sum per group)."""
+    C = C0 + C1
+    if groups <= 0 or groups > 32 or C % groups:
+        return None
+    cpg = C // groups
+    if cpg % 4 or C0 % 4:
+        return None
+    VEC = 8 if (cpg % 8 == 0 and C0 % 8 == 0) else 4
+    max_pieces = 16 if VEC == 8 else 32
+    slices = 1
+    while True:
+        if groups % slices:
+            return None
+        ppp = C // slices // VEC
+        unit = ppp // math.gcd(ppp, 64) * 64
+        if unit > 512:
+            return None
+        total = HW * ppp
+        threads = (512 // unit) * unit
+        if total < threads:
+            threads = -(-total // unit) * unit
+        pieces = -(-total // threads)
+        if pieces <= max_pieces or slices == groups:
+            break
+        slices *= 2
+    if pieces > 32:
+        return None
+    ppt = cpg // VEC
+    fast = ppp <= 64 and ppp & (ppp - 1) == 0 and ppt & (ppt - 1) == 0
+    return dict(VEC=VEC, slices=slices, ppp=ppp, threads=threads, pieces=pieces, ragged=total % threads != 0, fast=fast, ppt=ppt)
+
+
+def gn_apply_chunks(HW, C):
+    """gn_apply_impl's chunking under the default knobs: two trips of four rows by 256 // (C / 8) row lanes per workgroup
+    -> (rows per chunk, chunks per image)."""
+    rpc = min(2 * 4 * (256 // (C // 8)), HW)
+    return rpc, -(-HW // rpc)
+
+
+def gn_fwd_checked(ops, path, x0, gamma, beta, in1=None, groups=32, eps=1e-6, silu=True, scale_shift=None, saved=None, st0=None,
+                   st1=None, cond=None, tag=None, check=None):
+    """One GroupNorm(+FiLM)(+SiLU) forward launch on `path` under gn_bound, tagged groupnorm[<tag or path>] in `check` (default
+    EDGE): "resident" (ops.groupnorm_silu without statistics; dxmi_groupnorm_silu_supported is asserted), "generic"
+    (ops.groupnorm_generic, `saved` as given) or "apply" (ops.groupnorm_apply with the BlockStats st0 / st1).  Depth of the
+    statistics: the group size + 2 (any order of the partial sums) for the first two, max(P0, P1) + cpg / 2 + 2 for the apply
+    (a pair adds its P partials, then a group its cpg / 2 pairs, + the rounding of the given partials).  cond: the largest
+    (image, group) |mean| / std of the input must exceed 0.9 cond.  -> the kernel's output."""
+    check = EDGE if check is None else check
+    N, H, W, C0 = x0.shape
+    C1 = in1.shape[3] if in1 is not None else 0
+    C = C0 + C1
+    if path == "apply":
+        got = ops.groupnorm_apply(x0, st0, gamma, beta, in1=in1, st1=st1, groups=groups, eps=eps, silu=silu, scale_shift=scale_shift)
+        d = max(st0.P, st1.P if st1 is not None else 0) + C // groups // 2 + 2
+    elif path == "generic":
+        got = ops.groupnorm_generic(x0, gamma, beta, in1=in1, groups=groups, eps=eps, silu=silu, scale_shift=scale_shift, saved=saved)
+        d = H * W * C // groups + 2
+    else:
+        assert path == "resident" and scale_shift is None
+        assert ops.load().dxmi_groupnorm_silu_supported(C0, C1, H * W, groups) == 1
+        got = ops.groupnorm_silu(x0, gamma, beta, in1=in1, groups=groups, eps=eps, silu=silu)
+        d = H * W * C // groups + 2
+    xc = torch.cat([x0, in1], 3) if in1 is not None else x0
+    yo, parts = gn_ref(xc, gamma, beta, groups, eps, silu, scale_shift)
+    if cond is not None:
+        assert float((parts["m"].abs() / parts["var"].sqrt()).max()) > 0.9 * cond          # the stated conditioning is reached
+    check.within(f"groupnorm[{tag or path}]", got, yo, gn_bound(yo, parts, gamma, beta, d, silu))
+    return got
+
+
 # ------------------------------------------------------------------------------------------ linear
 def bf16_near_tie(v):
     """Mask of fp64 values within 8 u32 |v| of a bf16 rounding midpoint (an fp32 evaluation may round them either way)."""
@@ -431,7 +551,7 @@ def attention_ref(qkv, heads, scale, chunk=4):
         q, k, v = (x[:, :, i * C:(i + 1) * C].reshape(-1, T, heads, D).transpose(1, 2) for i in range(3))
         s = scale * q @ k.transpose(-1, -2)
         lse[n0:n0 + chunk] = torch.logsumexp(s, -1) * LOG2E
-        smag[n0:n0 + chunk] = (scale * q.abs() @ k.abs().transpose(-1, -2)).amax(-1)
+        smag[n0:n0 + chunk] = (abs(scale) * q.abs() @ k.abs().transpose(-1, -2)).amax(-1)      # a magnitude: scale may be negative
         o[n0:n0 + chunk] = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(-1, T, C)
     return o, lse, smag
 
@@ -445,6 +565,96 @@ def attn_blocks(t, heads, rb=128):
     N, T, C = t.shape
     rb = min(rb, T)
     return t.reshape(N, T // rb, rb, heads, C // heads).permute(0, 3, 1, 2, 4)
+
+
+def attn_elem_bound(qkv, heads, scale, chunk=4):
+    """attention_ref's (o, lse2, smag) and the element-wise bound of o [N, T, C] derived in the module docstring, a few images
+    at a time."""
+    N, T, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    o, lse2, smag = attention_ref(qkv, heads, scale, chunk)
+    bound = torch.empty_like(o)
+    for n0 in range(0, N, chunk):
+        x = qkv[n0:n0 + chunk].double()
+        n = x.shape[0]
+        q, k, v = (x[:, :, i * C:(i + 1) * C].reshape(n, T, heads, D).transpose(1, 2) for i in range(3))
+        a = (torch.softmax(scale * q @ k.transpose(-1, -2), -1) @ v.abs()).transpose(1, 2).reshape(n, T, C)
+        delta = (D + 2) * U32 * smag[n0:n0 + chunk].transpose(1, 2)[..., None].expand(n, T, heads, D).reshape(n, T, C)
+        oc = o[n0:n0 + chunk]
+        bound[n0:n0 + chunk] = (U16 + 2 * delta + (T + 8) * U32) * a * (1 + U16) + (U16 + 4 * U32) * oc.abs()
+    return o, lse2, smag, bound
+
+
+def attn_inputs(g, N, T, heads, D, kind):
+    """bf16 qkv [N, T, 3 heads D] on g's device.  kind "gauss": unit Gaussians.  "below_zero": the component of every q and k
+    head vector along one unit vector u is replaced by -3 D^(1/4) (q) and +3 D^(1/4) (k), so that D^-1/2 q.k = -9 + N(0, 1): every
+    true score is far below the exp(0) of a zero-filled key.  "peaked": q and k times 3, scores of +-30 and more, so that the
+    running maximum moves in most key blocks."""
+    C = heads * D
+    x = torch.randn(N, T, 3 * C, generator=g, device=g.device)
+    if kind == "below_zero":
+        u = torch.randn(D, generator=g, device=g.device)
+        u /= u.norm()
+        qq, kk = x[:, :, :C].view(N, T, heads, D), x[:, :, C:2 * C].view(N, T, heads, D)
+        qq -= (qq @ u)[..., None] * u
+        kk -= (kk @ u)[..., None] * u
+        qq -= 3.0 * D ** 0.25 * u
+        kk += 3.0 * D ** 0.25 * u
+    elif kind == "peaked":
+        x[:, :, :2 * C] *= 3
+    else:
+        assert kind == "gauss", kind
+    return x.to(torch.bfloat16)
+
+
+def attn_max_score(qkv, heads, scale):
+    """Largest fp64 score scale q.k of the whole batch."""
+    N, T, C3 = qkv.shape
+    C = C3 // 3
+    x = qkv.double()
+    q, k = (x[:, :, i * C:(i + 1) * C].reshape(N, T, heads, C // heads).transpose(1, 2) for i in range(2))
+    return float((scale * q @ k.transpose(-1, -2)).max())
+
+
+def attn_xcd_logical(b, G):
+    """attn_xcd_logical of csrc/attention.hip restated: hardware block b of a grid of G -> logical block (XCD b % 8 owns
+    G // 8 + (b % 8 < G % 8) consecutive logical ids)."""
+    x, k = b & 7, b >> 3
+    q, r = G >> 3, G & 7
+    return x * q + min(x, r) + k
+
+
+def attention_checked(ops, qkv, heads, scale, tag, want_lse=False, check=None):
+    """ops.attention under attn_elem_bound (tagged attention[<tag>] in `check`, default EDGE), the lse, where one is returned,
+    under lse_bound; a second identical launch must be bitwise the first.  -> what ops.attention returned."""
+    check = EDGE if check is None else check
+    N, T, C3 = qkv.shape
+    res = ops.attention(qkv, heads, scale, want_lse=want_lse)
+    got, lse = res if want_lse else (res, None)
+    o, lse2, smag, bound = attn_elem_bound(qkv, heads, scale)
+    check.within(f"attention[{tag}]", got, o, bound)
+    if lse is not None:
+        check.within(f"attention_lse2[{tag}]", lse, lse2, lse_bound(lse2, smag, C3 // 3 // heads, T))
+    again = ops.attention(qkv, heads, scale, want_lse=want_lse)
+    again, lse_b = again if want_lse else (again, None)
+    assert torch.equal(got, again) and (lse is None or torch.equal(lse, lse_b)), f"attention[{tag}]: two launches differ"
+    return res
+
+
+def attention_case(ops, N, T, heads, D, kind, tag, scale=None, want_lse=False, check=None, device="cuda:0"):
+    """One edge case of ops.attention on attn_inputs seeded by the case itself: attention_checked, every true score below -3
+    for the below-zero kind, and image N - 1 run alone bitwise its rows of the batch.  -> (qkv, what ops.attention returned)."""
+    import zlib
+    g = torch.Generator(device=device).manual_seed(zlib.crc32(repr((N, T, heads, D, kind)).encode()))
+    scale = D ** -0.5 if scale is None else scale
+    qkv = attn_inputs(g, N, T, heads, D, kind)
+    if kind == "below_zero":
+        assert scale > 0 and attn_max_score(qkv, heads, scale) < -3
+    res = attention_checked(ops, qkv, heads, scale, tag, want_lse=want_lse, check=check)
+    out = res[0] if want_lse else res
+    assert torch.equal(ops.attention(qkv[N - 1:].contiguous(), heads, scale)[0], out[N - 1]), f"attention[{tag}]: batch dependence"
+    return qkv, res
 
 
 # ------------------------------------------------------------------------------------------ non-network launches of a step

@@ -11,8 +11,9 @@ import torch
 import torch.nn.functional as F
 
 from backward_bounds import BoundError
-from forward_bounds import (LOG2E, FwdChecker, act64, attention_ref, attn_blocks, conv_bound, conv_call_ref, conv_fwd_ref, gn_bound, gn_ref,
-                            linear_ref, lse_bound, stats_depth, stats_ref)
+from forward_bounds import (LOG2E, FwdChecker, act64, attention_ref, attn_blocks, attn_elem_bound, attn_inputs, attn_max_score,
+                            attn_xcd_logical, conv_bound, conv_call_ref, conv_fwd_ref, gn_bound, gn_fwd_plan, gn_ref, linear_ref, lse_bound,
+                            stats_depth, stats_ref)
 from backward_bounds import U16
 
 
@@ -325,6 +326,182 @@ def test_attention_bounds_reject_head_and_lse_bugs():
     lb_bad[1, 2, 128:] = lse[1, 3, 128:]
     must_reject(lambda: ck.within("lse2", lb_bad, lse2, lb))
     must_reject(lambda: ck.within("lse2", lse / LOG2E, lse2, lb))      # natural log instead of log2
+
+
+def attention_fp32_online(qkv, heads, scale, fault=None, fault_kb=1):
+    """attention_kernel<D>'s arithmetic in torch fp32 for any T: key blocks of 64 with a ragged last one, scores scaled into the
+    log2 domain, a running maximum with the rescale of l and O per block, l summing the UNROUNDED p, p rounded to bf16 for P V,
+    O / l stored as bf16 -> (o [N, T, C], lse2 [N, heads, T]).  fault plants one kernel bug:
+      "unmasked"     the first zero-filled key past T of the ragged last block takes part (score 0, value 0)
+      "masked_last"  key T - 1 is masked as well
+      "l_half"       query 0 of every (image, head): l misses the first 32 keys of the last block (a lost half-wave exchange)
+      "skip_rescale" O is not rescaled in key block fault_kb although the maximum moved there (l is)"""
+    N, T, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    q, k, v = (qkv[:, :, i * C:(i + 1) * C].float().reshape(N, T, heads, D).transpose(1, 2) for i in range(3))
+    sc2 = torch.tensor(scale, dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32)
+    m = torch.full((N, heads, T, 1), -math.inf)
+    l = torch.zeros(N, heads, T, 1)
+    o = torch.zeros(N, heads, T, D)
+    nkb = -(-T // 64)
+    for kb in range(nkb):
+        kk, vv = k[:, :, kb * 64:(kb + 1) * 64], v[:, :, kb * 64:(kb + 1) * 64]
+        last = kb == nkb - 1
+        if last and fault == "unmasked":
+            assert kk.shape[2] < 64
+            kk, vv = (torch.cat([t, torch.zeros(N, heads, 1, D)], 2) for t in (kk, vv))
+        if last and fault == "masked_last":
+            kk, vv = kk[:, :, :-1], vv[:, :, :-1]
+            if kk.shape[2] == 0:
+                break
+        s = (q @ kk.transpose(-1, -2)) * sc2
+        m_new = torch.maximum(m, s.amax(-1, keepdim=True))
+        p = torch.exp2(s - m_new)
+        psum = p.sum(-1, keepdim=True)
+        if last and fault == "l_half":
+            psum[:, :, 0] -= p[:, :, 0, :32].sum(-1, keepdim=True)
+        alpha = torch.exp2(m - m_new)
+        l = l * alpha + psum
+        if fault == "skip_rescale" and kb == fault_kb:
+            assert bool((alpha < 0.5).any())             # the maximum did move in this block
+        else:
+            o = o * alpha
+        o = o + p.to(torch.bfloat16).float() @ vv
+        m = m_new
+    return bf((o / l).transpose(1, 2).reshape(N, T, C)), (m + torch.log2(l)).squeeze(-1).double()
+
+
+# (N, T, heads, D, kind): the five shapes the element-wise attention bound was checked on
+ATTN_SHAPES = [(2, 200, 2, 64, "gauss"), (2, 200, 2, 64, "below_zero"), (1, 130, 1, 128, "peaked"), (2, 40, 1, 256, "below_zero"),
+               (1, 321, 1, 64, "peaked")]
+
+
+def _attn_case(i):
+    N, T, heads, D, kind = ATTN_SHAPES[i]
+    qkv = attn_inputs(torch.Generator().manual_seed(30 + i), N, T, heads, D, kind)
+    scale = D ** -0.5
+    return qkv, heads, scale, attn_elem_bound(qkv, heads, scale)
+
+
+def _ratio(got, o, bound):
+    return float(((got.double() - o).abs() / bound).max())
+
+
+def test_attention_elem_bound_accepts_the_kernel_arithmetic():
+    """The emulation of the kernels' arithmetic stays inside attn_elem_bound on every shape (with margin: worst 0.7 or so), lse
+    included; the below-zero inputs keep every true score under -3."""
+    ck = FwdChecker()
+    for i, (N, T, heads, D, kind) in enumerate(ATTN_SHAPES):
+        qkv, heads, scale, (o, lse2, smag, bound) = _attn_case(i)
+        got, lse = attention_fp32_online(qkv, heads, scale)
+        assert ck.within(f"attn{i}", got, o, bound) <= 1.0
+        assert ck.within(f"lse{i}", lse, lse2, lse_bound(lse2, smag, D, T)) <= 1.0
+        got1, _ = attention_fp32(qkv, heads, scale)                         # the one-block form (global maximum) as well
+        assert ck.within(f"attn{i}_global", got1, o, bound) <= 1.0
+        if kind == "below_zero":
+            assert attn_max_score(qkv, heads, scale) < -3
+    print(ck.report())
+
+
+def test_attention_elem_bound_rejects_mask_sum_and_rescale_bugs():
+    ck = FwdChecker()
+    for i in (1, 3):                                                        # below-zero inputs, ragged last block
+        qkv, heads, scale, (o, _, _, bound) = _attn_case(i)
+        for fault in ("unmasked", "masked_last", "l_half"):
+            bad, _ = attention_fp32_online(qkv, heads, scale, fault=fault)
+            must_reject(lambda: ck.within(f"attn{i}_{fault}", bad, o, bound))
+        assert _ratio(attention_fp32_online(qkv, heads, scale, fault="unmasked")[0], o, bound) > 50
+    for i in (2, 4):                                                        # peaked inputs, several key blocks
+        qkv, heads, scale, (o, _, _, bound) = _attn_case(i)
+        bad, _ = attention_fp32_online(qkv, heads, scale, fault="skip_rescale", fault_kb=1)
+        must_reject(lambda: ck.within(f"attn{i}_skip_rescale", bad, o, bound))
+    # one query row of a 128-row block scaled by 1.1
+    qkv, heads, scale, (o, _, _, bound) = _attn_case(0)
+    got, _ = attention_fp32_online(qkv, heads, scale)
+    bad = got.clone()
+    bad[1, 150] *= 1.1
+    must_reject(lambda: ck.within("attn_row", bad, o, bound))
+
+
+def test_old_attention_measures_pass_faults_the_elem_bound_rejects():
+    """What the attention edge tests used alone (whole-tensor rel-L2 < 8e-3) and the program-shape suite's rel-L2 per (image,
+    head, 128-row block) within 8 u16, against attn_elem_bound.  (The whole-tensor measure is taken against the fp64 output here;
+    the tests took it against torch fp32, which differs from fp64 by 1e-6 of the tolerance.)
+      * one query row of 256 scaled by 1.1: both old measures pass it, the bound rejects it;
+      * one zero key past T unmasked under Gaussian q, k (T = 200): the whole-tensor measure passes it (about 3e-3) AND SO DOES THE
+        BOUND (the denominator moves by 0.3 %, under u16), which is why the ragged cases take below-zero inputs;
+      * the same key under below-zero inputs at T = 40, where one block exists: the per-block measure REJECTS it as well (the
+        stray key holds nearly all the weight, the block's rel-L2 is close to 1), so no assertion that it passes is made; at
+        T = 200 the per-block measure cannot be formed at all (attn_blocks needs T % 128 == 0 or T < 128)."""
+    g = torch.Generator().manual_seed(40)
+    N, T, heads, D = 2, 256, 4, 64
+    qkv = attn_inputs(g, N, T, heads, D, "gauss")
+    o, _, _, bound = attn_elem_bound(qkv, heads, D ** -0.5)
+    got, _ = attention_fp32_online(qkv, heads, D ** -0.5)
+    bad = got.clone()
+    bad[1, 77] *= 1.1
+    ck = FwdChecker()
+    assert ck.within("attn", got, o, bound) <= 1.0
+    assert rel_l2(got, o) < rel_l2(bad, o) < 8e-3
+    assert ck.blocks("attn_blocks", attn_blocks(bad, heads), attn_blocks(o, heads), 8 * U16, 3) <= 1.0
+    must_reject(lambda: ck.within("attn", bad, o, bound))
+    # the unmasked key under Gaussian inputs
+    qkv, heads, scale, (o, _, _, bound) = _attn_case(0)
+    bad, _ = attention_fp32_online(qkv, heads, scale, fault="unmasked")
+    assert rel_l2(attention_fp32_online(qkv, heads, scale)[0], o) < rel_l2(bad, o) < 8e-3
+    assert _ratio(bad, o, bound) <= 1.0
+    # ... and under below-zero inputs: far outside the bound; the per-block measure sees it too where it can be formed
+    qkv, heads, scale, (o, _, _, bound) = _attn_case(3)
+    bad, _ = attention_fp32_online(qkv, heads, scale, fault="unmasked")
+    assert _ratio(bad, o, bound) > 50
+    must_reject(lambda: ck.blocks("attn_blocks", attn_blocks(bad, heads), attn_blocks(o, heads), 8 * U16, 3))
+    with pytest.raises(RuntimeError):
+        attn_blocks(_attn_case(1)[3][0], 2)
+
+
+def test_attn_xcd_logical_is_a_bijection():
+    """The XCD block permutation of csrc/attention.hip (restated in forward_bounds.attn_xcd_logical) maps 0..G-1 onto itself for
+    every grid size, and gives the blocks of one XCD (b % 8) consecutive logical ids."""
+    for G in range(1, 201):
+        ids = [attn_xcd_logical(b, G) for b in range(G)]
+        assert sorted(ids) == list(range(G)), G
+        for x in range(min(8, G)):
+            mine = [attn_xcd_logical(b, G) for b in range(x, G, 8)]
+            assert mine == list(range(mine[0], mine[0] + len(mine))), (G, x)
+
+
+# The plans of the resident GroupNorm forward rows of tests/test_hip_forward_edges.py: (C0, C1, HW, groups) ->
+# (VEC, slices, ppp, threads, pieces, ragged, fast, ppt) of dxmi_groupnorm_silu_fwd's slicing walk (the library is not loaded here)
+GN_FWD_PLANS = {
+    "vec4_cpg4": ((128, 0, 64, 32), (4, 1, 32, 512, 4, False, True, 1)),
+    "vec4_c0_132": ((132, 124, 64, 32), (4, 1, 64, 512, 8, False, True, 2)),
+    "cpg12_notfast": ((384, 0, 64, 32), (4, 1, 96, 384, 16, False, False, 3)),
+    "cpg12_cat_ragged": ((256, 128, 49, 32), (4, 1, 96, 384, 13, True, False, 3)),
+    "cpg24_notfast": ((768, 0, 16, 32), (8, 1, 96, 384, 4, False, False, 3)),
+    "wide_ppp128_4x4": ((1024, 0, 16, 32), (8, 1, 128, 512, 4, False, False, 4)),
+    "wide_ppp128_8x8": ((1024, 0, 64, 32), (8, 1, 128, 512, 16, False, False, 4)),
+    "c2048": ((2048, 0, 4, 32), (8, 1, 256, 512, 2, False, False, 8)),
+    "map_1x1": ((256, 0, 1, 32), (8, 1, 32, 64, 1, True, True, 1)),
+    "map_2x2_cat": ((128, 128, 4, 32), (8, 1, 32, 128, 1, False, True, 1)),
+    "map_3x3": ((128, 0, 9, 32), (4, 1, 32, 320, 1, True, True, 1)),
+    "ragged_piece": ((256, 0, 35, 32), (8, 1, 32, 512, 3, True, True, 1)),
+    "one_group": ((64, 0, 12, 1), (8, 1, 8, 128, 1, True, True, 8)),
+    "sliced_vec4_32": ((128, 0, 1024, 32), (4, 2, 16, 512, 32, False, True, 1)),
+    "sliced_ragged": ((128, 0, 5000, 32), (4, 16, 2, 512, 20, True, True, 1)),
+}
+
+
+def test_gn_fwd_plan_table_and_refusals():
+    keys = ("VEC", "slices", "ppp", "threads", "pieces", "ragged", "fast", "ppt")
+    for name, (shape, want) in GN_FWD_PLANS.items():
+        plan = gn_fwd_plan(*shape)
+        assert plan is not None and tuple(plan[k] for k in keys) == want, (name, plan)
+    # 3 and 6 channels per group; a slice whose unit is 576 threads; more than 32 pieces after the last slicing (32 slices of one
+    # piece per pixel at 512 threads hold 32 * 512 pixels: 16385 is the smallest map that does not fit, for any channel count)
+    for shape in ((96, 0, 100, 32), (192, 0, 64, 32), (288, 0, 16, 8), (128, 0, 16385, 32), (4, 0, 16385, 1)):
+        assert gn_fwd_plan(*shape) is None, shape
+    assert gn_fwd_plan(128, 0, 16384, 32)["pieces"] == 32 and gn_fwd_plan(4, 0, 16384, 1)["pieces"] == 32
 
 
 # ------------------------------------------------------------------------------------------ linear

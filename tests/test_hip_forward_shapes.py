@@ -9,7 +9,7 @@ The two samplers at 100 add no network row to the table: they launch what imagen
 test_census_is_covered now guards that.  test_census_is_covered re-records each program and fails on any launch the table
 lacks and on any `ops` function called outside a backward that is neither a launch op nor on the census's allow-lists.
 test_every_row_kind_has_a_test keeps the row kinds of the table and the kinds the tests parametrise over equal.  Every row is then run on seeded
-inputs and checked element by element (attention: per 128-row block) against stock torch in float64 on the device, with the
+inputs and checked element by element (attention: also per 128-row block) against stock torch in float64 on the device, with the
 bounds derived in tests/forward_bounds.py; conv rows run under the tuning the census recorded and must select the kernel the
 census saw.  EXTRA rows reach the forward kernel instances no program launches, so that every conv kernel id
 bench.kernel_name can name, both linear forms, every attention kernel and every GroupNorm path is launched here.
@@ -25,13 +25,14 @@ import pytest
 import torch
 
 from backward_bounds import U16, U32, dropout_ref, groupnorm_bwd_ref, td_loss_ref
-from forward_bounds import (FwdChecker, attention_ref, attn_blocks, conv_call_ref, dsm_error_terms,
-                            dsm_loss_fwd_bound, edm_step_ref, fold_passes, gn_bound, gn_fused_bound, gn_ref, linear_ref, log_sigma_t, lse_bound,
+from forward_bounds import (MIN_COND, FwdChecker, attention_ref, attn_blocks, attn_elem_bound, block_stats_tensor, conv_call_ref, dsm_error_terms,
+                            dsm_loss_fwd_bound, edm_step_ref, fold_passes, gn_bound, gn_fused_bound, gn_fwd_checked, gn_input, gn_ref,
+                            linear_ref, log_sigma_t, lse_bound,
                             pool_act_ref, scaled_input_ref, stats_depth, stats_ref, store_bound, td_gather_cost_ref, var_step_ref)
 
 DEV = "cuda:0"
 CHECK = FwdChecker()
-COND_MULT, MIN_COND = 4.0, 8.0
+COND_MULT = 4.0
 
 import forward_census  # noqa: E402
 from forward_census import PROGRAMS  # noqa: E402
@@ -1673,22 +1674,8 @@ def test_conv_fwd(ops, r):
 
 
 # ------------------------------------------------------------------------------------------ GroupNorm
-def _gn_input(g, N, H, W, C, cond, groups=32):
-    """bf16 activation whose (image, group) |mean| / std spread up to `cond`: one offset per group, uniform in [-cond, cond]
-    (unit-variance noise inside), the largest |offset| of every image set to cond; image 0's first group zero-mean with a
-    tiny variance, where eps matters."""
-    off = (torch.rand(N, groups, generator=g, device=DEV) * 2 - 1) * cond
-    off[torch.arange(N, device=DEV), off.abs().argmax(1)] = cond
-    x = rnd(g, N, H, W, C) + off.repeat_interleave(C // groups, 1)[:, None, None, :]
-    x[0, :, :, :C // groups] = 0.003 * rnd(g, H, W, C // groups)
-    return bf(x)
-
-
-def _block_stats_tensor(x, P):
-    """fp32 BlockStats buffer [N, P, C/2, 2] of x: P contiguous pixel chunks, sums in fp64 then rounded once."""
-    N, H, W, C = x.shape
-    xd = x.double().reshape(N, P, H * W // P, C // 2, 2)
-    return torch.stack([xd.sum((2, 4)), xd.square().sum((2, 4))], -1).float().contiguous()
+_gn_input = gn_input                    # moved to forward_bounds.py (the edge-case suite builds its inputs the same way)
+_block_stats_tensor = block_stats_tensor
 
 
 @pytest.mark.gpu
@@ -1706,22 +1693,14 @@ def test_groupnorm_fwd(ops, r):
     x1 = xc[..., C0:].contiguous() if c1 else None
     gamma, beta = 1 + 0.3 * rnd(g, C), 0.3 * rnd(g, C)
     ss = (0.3 * rnd(g, N, 3 * C))[:, C // 2: C // 2 + 2 * C] if has_ss else None
+    st0 = st1 = None
     if path == "apply":
         st0 = ops.BlockStats(_block_stats_tensor(x0, P0), P0)
         st1 = ops.BlockStats(_block_stats_tensor(x1, P1), P1) if c1 else None
-        got = ops.groupnorm_apply(x0, st0, gamma, beta, in1=x1, st1=st1, groups=groups, eps=eps, silu=silu, scale_shift=ss)
-        d = max(P0, P1) + C // groups // 2 + 2     # a pair adds its P partials, then a group its cpg / 2 pairs (+ our rounding)
-    elif path == "generic":
-        got = ops.groupnorm_generic(x0, gamma, beta, in1=x1, groups=groups, eps=eps, silu=silu, scale_shift=ss,
-                                    saved=[] if saved else None)
-        d = H * W * C // groups + 2
     else:
-        assert ops.load().dxmi_groupnorm_silu_supported(C0, c1, H * W, groups) and not has_ss
-        got = ops.groupnorm_silu(x0, gamma, beta, in1=x1, groups=groups, eps=eps, silu=silu)
-        d = H * W * C // groups + 2
-    yo, parts = gn_ref(xc, gamma, beta, groups, eps, silu, ss)
-    assert float((parts["m"].abs() / parts["var"].sqrt()).max()) > 0.9 * cond          # the stated conditioning is reached
-    CHECK.within(f"groupnorm[{path}]", got, yo, gn_bound(yo, parts, gamma, beta, d, silu))
+        assert path in ("generic", "resident")
+    gn_fwd_checked(ops, path, x0, gamma, beta, in1=x1, groups=groups, eps=eps, silu=silu, scale_shift=ss, saved=[] if saved else None,
+                   st0=st0, st1=st1, cond=cond, check=CHECK)
 
 
 @pytest.mark.gpu
@@ -1804,8 +1783,9 @@ def test_linear_fwd(ops, r):
 # ------------------------------------------------------------------------------------------ attention
 def _attn_check(name, got, lse, qkv, heads, scale):
     N, T, C3 = qkv.shape
-    o, lse2, smag = attention_ref(qkv, heads, scale)
+    o, lse2, smag, bound = attn_elem_bound(qkv, heads, scale)
     CHECK.blocks(name, attn_blocks(got, heads), attn_blocks(o, heads), 8 * U16, 3)
+    CHECK.within(name + "_elem", got, o, bound)
     if lse is not None:
         CHECK.within(name + "_lse2", lse, lse2, lse_bound(lse2, smag, C3 // 3 // heads, T))
     return o

@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from forward_bounds import conv_checked, linear_checked
+from forward_bounds import attention_checked, conv_checked, gn_fwd_checked, linear_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -169,6 +169,9 @@ def test_groupnorm_silu(ops, N, C0, C1, H, silu, eps):
     got = nchw(y)
     assert (got - ref).abs().max().item() <= 2e-2 * max(1.0, ref.abs().max().item())
     assert rel_l2(got, ref) < 4e-3
+    # element by element against fp64, on the kernel the dispatcher picked for the shape (bitwise the dispatcher's result)
+    path = "resident" if ops.load().dxmi_groupnorm_silu_supported(C0, C1, H * H, 32) else "generic"
+    assert torch.equal(y, gn_fwd_checked(ops, path, x0, gamma.to(DEV), beta.to(DEV), in1=x1, eps=eps, silu=silu))
 
 
 @pytest.mark.parametrize("N,T,C,heads", [(2, 256, 256, 1), (3, 16, 256, 1), (2, 64, 128, 2), (1, 1024, 128, 2), (2, 200, 64, 1)])
@@ -183,7 +186,7 @@ def test_attention(ops, N, T, C, heads):
     v = v.view(N, T, heads, D).transpose(1, 2)
     w = torch.softmax(q @ k.transpose(-1, -2) * scale, dim=-1)
     ref = (w @ v).transpose(1, 2).reshape(N, T, C)
-    y = ops.attention(qkv.to(torch.bfloat16).to(DEV), heads, scale)
+    y = attention_checked(ops, qkv.to(torch.bfloat16).to(DEV), heads, scale, f"test_attention T{T} D{D}")     # fp64, element by element
     got = y.float().cpu()
     # P is rounded to bf16 before PV: ~2^-9 relative per term
     assert rel_l2(got, ref) < 8e-3, rel_l2(got, ref)

@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from forward_bounds import conv_checked, launch_conv
+from forward_bounds import attention_checked, conv_checked, launch_conv
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -280,7 +280,7 @@ def test_attention256(ops, N):
     scale = 1.0 / math.sqrt(C)
     q, k, v = qkv.to(DEV).split(C, dim=2)
     ref = (torch.softmax(q @ k.transpose(-1, -2) * scale, dim=-1) @ v).cpu()
-    y1 = ops.attention(qkv.to(torch.bfloat16).to(DEV), 1, scale)
+    y1 = attention_checked(ops, qkv.to(torch.bfloat16).to(DEV), 1, scale, "attention256<false>")      # fp64, element by element
     y2 = ops.attention(qkv.to(torch.bfloat16).to(DEV), 1, scale)
     torch.cuda.synchronize()
     assert torch.equal(y1, y2)

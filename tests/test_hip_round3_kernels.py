@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from backward_bounds import EDGE
-from forward_bounds import conv_checked
+from forward_bounds import block_stats_tensor, conv_checked, gn_fwd_checked
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -158,6 +158,10 @@ def test_groupnorm_apply_vs_torch_and_resident(ops, N, C0, C1, H, silu):
         assert (y == yr).float().mean().item() > 0.999
     y2 = ops.groupnorm_silu(x0, ga, be, in1=x1, eps=1e-6, silu=silu, stats=(s0, s1))
     assert torch.equal(y, y2)                                   # bitwise reproducible
+    # element by element against fp64, from partials of the same count formed in fp64 (gn_bound's depth is for given partials)
+    f0 = ops.BlockStats(block_stats_tensor(x0, s0.P), s0.P)
+    f1 = ops.BlockStats(block_stats_tensor(x1, s1.P), s1.P) if C1 else None
+    gn_fwd_checked(ops, "apply", x0, ga, be, in1=x1, st0=f0, st1=f1, eps=1e-6, silu=silu)
     # batch independence
     s00 = ops.BlockStats(s0.buf[:1].contiguous(), s0.P)
     s10 = ops.BlockStats(s1.buf[:1].contiguous(), s1.P) if C1 else None
@@ -270,6 +274,9 @@ def test_groupnorm_apply_scale_shift_and_fold(ops):
     y = ops.groupnorm_silu(x0, gamma.to(DEV), beta.to(DEV), eps=1e-5, silu=True, scale_shift=ss.to(DEV), stats=(st, None))
     got = nchw(y)
     assert ((got - ref).norm() / ref.norm()).item() < 4e-3
+    # element by element against fp64, from one partial formed in fp64 (gn_bound's depth is for given partials)
+    gn_fwd_checked(ops, "apply", x0, gamma.to(DEV), beta.to(DEV), st0=ops.BlockStats(block_stats_tensor(x0, 1), 1), eps=1e-5, silu=True,
+                   scale_shift=ss.to(DEV))
     yg = ops.groupnorm_silu(x0, gamma.to(DEV), beta.to(DEV), eps=1e-5, silu=True, scale_shift=ss.to(DEV))     # generic path
     assert (y == yg).float().mean().item() > 0.999
     # fold of a conv's many partials equals their plain sum
