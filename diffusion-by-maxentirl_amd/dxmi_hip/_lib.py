@@ -157,6 +157,14 @@ SIGNATURES = {
     "dxmi_pool3x3": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "dxmi_global_avgpool": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dxmi_resize_bilinear_nhwc16": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    # the extractor in fp32 (csrc/inception_f32.hip; the reference's pytorch_fid/inception.py:129-163 runs torch fp32)
+    "dxmi_gconv_f32_packed_elems": (c_int64, [c_int] * 4),
+    "dxmi_gconv_f32_pack": (c_int, [c_void_p] * 5 + [c_float] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "dxmi_gconv_f32_fwd": (c_int, [c_void_p] * 5 + [c_int] * 14 + [c_void_p]),
+    "dxmi_pool3x3_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "dxmi_global_avgpool_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dxmi_resize_bilinear_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "dxmi_nhwc_f32_to_nchw_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dxmi_lpips_front_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "dxmi_lpips_front_bwd": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "dxmi_avgpool2x2_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),

@@ -8,6 +8,9 @@ so the FID weight file (pt_inception-2015-12-05-6726825d.pth: inception.py:13) l
 state dict has the reference class's keys (`blocks.0.0.conv.weight` ...).  forward() runs the HIP program: bilinear resize + 2x-1
 into NHWC bf16, every BasicConv2d as one generic implicit-GEMM MFMA launch with its BatchNorm folded into the weights and ReLU in
 the epilogue, the blocks' concatenations written in place (channel windows of one tensor), the FID pools, the global average pool.
+`precision="fp32"` runs the same program on the fp32 op set (dxmi_hip/inception_f32_ops.py): NHWC fp32 activations, the checkpoint's
+fp32 weights re-laid-out without arithmetic on the exact f32-input MFMA, BatchNorm + ReLU in the epilogue — the reference's
+arithmetic, which the default bf16 mode departs from by about one bf16 rounding per layer.
 PARITY IS UNPINNED: neither torchvision nor the weight file exists in this image, so the tests check the program against a
 torch-CPU restatement of the same architecture on formula weights (oracle/inception.py), not against the reference's outputs.
 No CPU path: non-device tensors raise.
@@ -17,8 +20,13 @@ import os
 import torch
 import torch.nn as nn
 
-from dxmi_hip import ops
+from dxmi_hip import inception_f32_ops, ops
 from dxmi_hip._lib import DxmiError
+
+# precision -> (op module, activation dtype, name of its resize op, name of its NHWC -> NCHW fp32 op).  Both modules have gconv_pack,
+# gconv, pool3x3 and global_avgpool with one calling convention; the ops are looked up on the module at every call.
+_PRECISIONS = {"bf16": (ops, torch.bfloat16, "resize_bilinear_nhwc16", "nhwc_bf16_to_nchw_f32"),
+               "fp32": (inception_f32_ops, torch.float32, "resize_bilinear_nhwc", "nhwc_to_nchw")}
 
 
 class BasicConv2d(nn.Module):
@@ -82,11 +90,15 @@ class InceptionV3(nn.Module):
     BLOCK_INDEX_BY_DIM = {64: 0, 192: 1, 768: 2, 2048: 3}
 
     def __init__(self, output_blocks=(DEFAULT_BLOCK_INDEX,), resize_input=True, normalize_input=True, requires_grad=False,
-                 use_fid_inception=True, weights=None):
+                 use_fid_inception=True, weights=None, precision="bf16"):
         """Constructor of the reference class (inception.py:31-36) + `weights`: path of the FID weight file (or a state dict with
         torchvision's names); None leaves the torch default initialisation — the reference downloads the file, which this image
-        cannot."""
+        cannot.  `precision`: "bf16" (activations and BatchNorm-folded weights in bf16, csrc/inception_ops.hip) or "fp32" (the
+        reference's arithmetic: fp32 activations and weights, BatchNorm in the conv epilogue, csrc/inception_f32.hip); the
+        attribute may be set again later, each precision keeps its own packed weights."""
         super().__init__()
+        self._cache = {}
+        self.precision = precision
         if not use_fid_inception:
             raise NotImplementedError("use_fid_inception=False (torchvision's own weights and pools) is not built: the DxMI scripts score FID")
         if requires_grad:
@@ -111,7 +123,6 @@ class InceptionV3(nn.Module):
             self.blocks.append(nn.Sequential(*(mods + ([tails[b]] if tails[b] is not None else []))))
         for prm in self.parameters():
             prm.requires_grad = False
-        self._packed, self._packed_key = None, None
         if weights is not None:
             self.load_fid_weights(torch.load(weights, map_location="cpu") if isinstance(weights, (str, os.PathLike)) else weights)
 
@@ -123,7 +134,27 @@ class InceptionV3(nn.Module):
             mod.load_state_dict(sub, strict=True)
         self._packed = None
 
-    # ------------------------------------------------------------------ packed weights
+    # ------------------------------------------------------------------ precision and packed weights
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        if value not in _PRECISIONS:
+            raise ValueError(f"InceptionV3: precision must be one of {sorted(_PRECISIONS)}, got {value!r}")
+        self._precision = value
+
+    @property
+    def _packed(self):
+        """The packed weights of the current precision, {id(BasicConv2d): packed}; None before the first forward."""
+        return self._cache.get(self._precision, (None, None))[1]
+
+    @_packed.setter
+    def _packed(self, value):
+        assert value is None, "the packed weights are made by packed()"
+        self._cache.clear()
+
     def _convs(self):
         for name, mod in self._by_name.items():
             if isinstance(mod, BasicConv2d):
@@ -135,21 +166,21 @@ class InceptionV3(nn.Module):
 
     def packed(self):
         key = tuple((t.data_ptr(), t._version) for _, c in self._convs() for t in (c.conv.weight, c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var))
-        if self._packed is None or key != self._packed_key:
-            self._packed = {id(c): ops.gconv_pack(c.conv.weight, (c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var), c.bn.eps)
-                            for _, c in self._convs()}
-            self._packed_key = key
-        return self._packed
+        if self._cache.get(self._precision, (None, None))[0] != key:
+            o = _PRECISIONS[self._precision][0]
+            self._cache[self._precision] = (key, {id(c): o.gconv_pack(c.conv.weight, (c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var), c.bn.eps)
+                                                  for _, c in self._convs()})
+        return self._cache[self._precision][1]
 
     # ------------------------------------------------------------------ program
-    @staticmethod
-    def _run(pk, c, x, out=None, coff=0):
-        return ops.gconv(x, pk[id(c)], stride=c.s, pad=c.p, relu=True, out=out, coff=coff)
+    def _run(self, pk, c, x, out=None, coff=0):
+        return _PRECISIONS[self._precision][0].gconv(x, pk[id(c)], stride=c.s, pad=c.p, relu=True, out=out, coff=coff)
 
     def _mixed(self, pk, m, x):
         run = lambda c, t, out=None, coff=0: self._run(pk, c, t, out, coff)
         N, H, W, _ = x.shape
-        new = lambda h, w, c: torch.empty((N, h, w, c), dtype=torch.bfloat16, device=x.device)
+        o, dtype = _PRECISIONS[self._precision][:2]
+        new = lambda h, w, c: torch.empty((N, h, w, c), dtype=dtype, device=x.device)
         k = m.kind
         if k == "A":
             pf = m.branch_pool.conv.out_channels
@@ -157,26 +188,26 @@ class InceptionV3(nn.Module):
             run(m.branch1x1, x, out, 0)
             run(m.branch5x5_2, run(m.branch5x5_1, x), out, 64)
             run(m.branch3x3dbl_3, run(m.branch3x3dbl_2, run(m.branch3x3dbl_1, x)), out, 128)
-            run(m.branch_pool, ops.pool3x3(x, 1, 1, avg_exclude_pad=True), out, 224)
+            run(m.branch_pool, o.pool3x3(x, 1, 1, avg_exclude_pad=True), out, 224)
         elif k == "B":
             OH, OW = (H - 3) // 2 + 1, (W - 3) // 2 + 1
             out = new(OH, OW, 480 + x.shape[3])
             run(m.branch3x3, x, out, 0)
             run(m.branch3x3dbl_3, run(m.branch3x3dbl_2, run(m.branch3x3dbl_1, x)), out, 384)
-            ops.pool3x3(x, 2, 0, out=out, coff=480)
+            o.pool3x3(x, 2, 0, out=out, coff=480)
         elif k == "C":
             out = new(H, W, 768)
             run(m.branch1x1, x, out, 0)
             run(m.branch7x7_3, run(m.branch7x7_2, run(m.branch7x7_1, x)), out, 192)
             t = run(m.branch7x7dbl_2, run(m.branch7x7dbl_1, x))
             run(m.branch7x7dbl_5, run(m.branch7x7dbl_4, run(m.branch7x7dbl_3, t)), out, 384)
-            run(m.branch_pool, ops.pool3x3(x, 1, 1, avg_exclude_pad=True), out, 576)
+            run(m.branch_pool, o.pool3x3(x, 1, 1, avg_exclude_pad=True), out, 576)
         elif k == "D":
             OH, OW = (H - 3) // 2 + 1, (W - 3) // 2 + 1
             out = new(OH, OW, 512 + x.shape[3])
             run(m.branch3x3_2, run(m.branch3x3_1, x), out, 0)
             run(m.branch7x7x3_4, run(m.branch7x7x3_3, run(m.branch7x7x3_2, run(m.branch7x7x3_1, x))), out, 320)
-            ops.pool3x3(x, 2, 0, out=out, coff=512)
+            o.pool3x3(x, 2, 0, out=out, coff=512)
         else:           # E1 / E2
             out = new(H, W, 2048)
             run(m.branch1x1, x, out, 0)
@@ -187,7 +218,7 @@ class InceptionV3(nn.Module):
             run(m.branch3x3dbl_3a, t, out, 1088)
             run(m.branch3x3dbl_3b, t, out, 1472)
             # Mixed_7b: average over the in-bounds pixels; Mixed_7c: MAX pool (the FID model's own quirk, inception.py:303-308)
-            pooled = ops.pool3x3(x, 1, 1, avg_exclude_pad=(k == "E1"))
+            pooled = o.pool3x3(x, 1, 1, avg_exclude_pad=(k == "E1"))
             run(m.branch_pool, pooled, out, 1856)
         return out
 
@@ -200,34 +231,45 @@ class InceptionV3(nn.Module):
         x = inp.contiguous().float()
         N, _, H, W = x.shape
         OH, OW = (299, 299) if self.resize_input else (H, W)
-        h = ops.resize_bilinear_nhwc16(x, OH, OW, normalize=self.normalize_input)
+        o, _, resize, to_nchw = _PRECISIONS[self._precision]
+        h = getattr(o, resize)(x, OH, OW, normalize=self.normalize_input)
         outp = []
         for idx in range(self.last_needed_block + 1):
             for name in _LAYOUT[idx]:
                 m = self._by_name[name]
                 h = self._run(pk, m, h) if isinstance(m, BasicConv2d) else self._mixed(pk, m, h)
             if idx in (0, 1):
-                h = ops.pool3x3(h, 2, 0)
+                h = o.pool3x3(h, 2, 0)
             if idx == 3:
-                feat = ops.global_avgpool(h)
+                feat = o.global_avgpool(h)
                 if idx in self.output_blocks:
                     outp.append(feat.view(N, -1, 1, 1))
             elif idx in self.output_blocks:
-                outp.append(ops.nhwc_bf16_to_nchw_f32(h))
+                outp.append(getattr(o, to_nchw)(h))
         return outp
 
 
 class FIDInceptionV3(InceptionV3):
     """The extractor `--fid_extractor pytorch_fid.inception:FIDInceptionV3` resolves to (the scripts instantiate a class): InceptionV3
     pool3 features with the FID weights named by DXMI_FID_WEIGHTS (pt_inception-2015-12-05-6726825d.pth).  Without the file this
-    raises — scoring FID on an untrained extractor is never what the caller wants."""
+    raises — scoring FID on an untrained extractor is never what the caller wants.  This class computes in bf16 (PRECISION);
+    FIDInceptionV3FP32 is the same extractor in the reference's fp32."""
+
+    PRECISION = "bf16"
 
     def __init__(self, dims=2048):
         path = os.environ.get("DXMI_FID_WEIGHTS")
         if not path or not os.path.exists(path):
             raise DxmiError("DXMI_FID_WEIGHTS must name the FID Inception weight file (pt_inception-2015-12-05-6726825d.pth); "
                             "it cannot be downloaded into this image")
-        super().__init__([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], weights=path)
+        super().__init__([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], weights=path, precision=self.PRECISION)
+
+
+class FIDInceptionV3FP32(FIDInceptionV3):
+    """`--fid_extractor pytorch_fid.inception:FIDInceptionV3FP32`: FIDInceptionV3 with every activation, weight and sum in fp32, the
+    arithmetic of the reference's extractor (csrc/inception_f32.hip).  Same contract, same DXMI_FID_WEIGHTS."""
+
+    PRECISION = "fp32"
 
 
 class EvalInceptionV3(InceptionV3):
@@ -245,9 +287,11 @@ class EvalInceptionV3(InceptionV3):
     17 x 17 block, and its `conv` is the un-prefixed first branch, the 1x1 conv + BN + ReLU that torchvision calls
     `Mixed_6d.branch1x1` (192 channels, written first into the block's concatenation).  2023 = 17 * 17 * 7 is the sFID feature
     size of the reference, which only a 17 x 17 tap gives.  softmax_weight is `fc.weight`^T (`softmax/logits/MatMul`'s
-    operand; the reference drops the bias, evaluator.py:603-616)."""
+    operand; the reference drops the bias, evaluator.py:603-616).  This class computes in bf16 (PRECISION); EvalInceptionV3FP32
+    is the same extractor in fp32."""
 
     SPATIAL_CHANNELS = 7
+    PRECISION = "bf16"
 
     def __init__(self, weights=None):
         path = weights or os.environ.get("DXMI_FID_WEIGHTS")
@@ -257,8 +301,9 @@ class EvalInceptionV3(InceptionV3):
         sd = torch.load(path, map_location="cpu")
         if "fc.weight" not in sd:
             raise DxmiError(f"{path}: no fc.weight (the Inception Score needs the classifier weight)")
-        super().__init__([InceptionV3.DEFAULT_BLOCK_INDEX], weights=sd)
+        super().__init__([InceptionV3.DEFAULT_BLOCK_INDEX], weights=sd, precision=self.PRECISION)
         self.softmax_weight = sd["fc.weight"].float().t().contiguous().cuda()
+        self.to(self.softmax_weight.device)          # evaluator.py calls the instance as it is built: the weights go where the images are
         self._tap = None
 
     def _mixed(self, pk, m, x):
@@ -275,3 +320,10 @@ class EvalInceptionV3(InceptionV3):
         pool = self.forward(x)[0].reshape(x.shape[0], -1)
         spatial, self._tap = self._tap, None
         return pool, spatial
+
+
+class EvalInceptionV3FP32(EvalInceptionV3):
+    """`evaluator.py --extractor pytorch_fid.inception:EvalInceptionV3FP32`: EvalInceptionV3 in fp32 (csrc/inception_f32.hip); `spatial`
+    is Mixed_6d.branch1x1[..., :7] of the fp32 tensor.  Same contract, same weight file."""
+
+    PRECISION = "fp32"

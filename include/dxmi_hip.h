@@ -702,6 +702,44 @@ int dxmi_global_avgpool(const void* x, float* out, int32_t N, int32_t HW, int32_
 int dxmi_resize_bilinear_nhwc16(const float* x, void* out, int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW,
                                 int32_t normalize, void* stream);
 
+/* The same extractor in fp32 end to end (csrc/inception_f32.hip), as the reference runs it (pytorch_fid/inception.py:129-163 is
+ * torch fp32; evaluations/evaluator.py:584-616): NHWC fp32 activations whose channel count is a multiple of 8, weights that are a
+ * re-layout of the checkpoint's conv.weight with no arithmetic on them, BatchNorm in the conv epilogue.  Every entry validates its
+ * arguments before it touches the device (DXMI_EINVAL + dxmi_last_error). */
+
+/* fp32 elements of a packed weight: [ceil32(Cout)][KH * KW][ceil8(Cin)] (0 for a non-positive size). */
+int64_t dxmi_gconv_f32_packed_elems(int32_t Cout, int32_t Cin, int32_t KH, int32_t KW);
+
+/* BasicConv2d's operands for dxmi_gconv_f32_fwd (inception.py:193-310 over torchvision's BasicConv2d): w fp32 [Cout, Cin, KH, KW]
+ * -> w_packed[co][ky * KW + kx][ci], copied bit for bit, padded couts / channels zero; scale[ceil32(Cout)] = gamma / sqrt(var + eps),
+ * shift = beta - mean * scale (padding zero).  bn_gamma NULL: scale 1, shift = conv_bias (NULL: 0); conv_bias excludes BatchNorm. */
+int dxmi_gconv_f32_pack(const float* w, const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
+                        float bn_eps, const float* conv_bias, float* w_packed, float* scale, float* shift, int32_t Cout,
+                        int32_t Cin, int32_t KH, int32_t KW, void* stream);
+
+/* out[n, oy, ox, out_coff + co] = relu?(scale[co] * (sum x[n, oy*SH - PH + ky, ox*SW - PW + kx, ci] * w[co][ky, kx][ci]) + shift[co]):
+ * dxmi_gconv_fwd's argument shape on the exact f32-input MFMA, fp32 accumulation over K = Cin * KH * KW in one fixed order per
+ * layer shape (a pixel's result does not depend on N); Cin % 8 == 0 (the packed weight's padded count); one fp32 store. */
+int dxmi_gconv_f32_fwd(const float* x, const float* w_packed, const float* scale, const float* shift, float* out, int32_t N,
+                       int32_t IH, int32_t IW, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t SH, int32_t SW,
+                       int32_t PH, int32_t PW, int32_t out_cstride, int32_t out_coff, int32_t relu, void* stream);
+
+/* dxmi_pool3x3 on NHWC fp32 (inception.py:209-212, :299-308): C % 8 == 0, out_cstride and out_coff multiples of 4; the maximum is
+ * bitwise, the average is the in-order fp32 sum of the in-bounds pixels divided by their count. */
+int dxmi_pool3x3_f32(const float* x, float* out, int32_t N, int32_t IH, int32_t IW, int32_t C, int32_t stride, int32_t pad,
+                     int32_t avg_exclude_pad, int32_t out_cstride, int32_t out_coff, void* stream);
+
+/* adaptive_avg_pool2d(x, 1) (inception.py:124): [N, HW, C] fp32 -> [N, C] fp32, pixels summed in index order; C % 8 == 0. */
+int dxmi_global_avgpool_f32(const float* x, float* out, int32_t N, int32_t HW, int32_t C, void* stream);
+
+/* dxmi_resize_bilinear_nhwc16's expressions (inception.py:146-153) with fp32 stores: NCHW fp32 [N, 3, IH, IW] -> NHWC fp32
+ * [N, OH, OW, 8] (channels 3..7 zero). */
+int dxmi_resize_bilinear_nhwc_f32(const float* x, float* out, int32_t N, int32_t IH, int32_t IW, int32_t OH, int32_t OW,
+                                  int32_t normalize, void* stream);
+
+/* NHWC fp32 [N, HW, C] -> NCHW fp32 [N, C, HW] (the feature maps forward() returns, inception.py:155-163). */
+int dxmi_nhwc_f32_to_nchw_f32(const float* in, float* out, int32_t N, int32_t C, int32_t HW, void* stream);
+
 /* Replay-buffer row gather (INT path; trainer.py:278-289 `state_dict[key][indices][train_indices]`, :357-359):
  * dst[r] = src[idx[r]], rows of row_bytes (multiple of 4), idx int64 on the device, negative indices wrap; an index
  * outside [-n_src_rows, n_src_rows) fills the row with 0xFF bytes instead of reading out of bounds. */
