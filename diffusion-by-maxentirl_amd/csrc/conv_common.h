@@ -189,6 +189,7 @@ struct ConvPlan {
 // Per family: *_select returns whether the shape is in the kernel's scope and fills the plan (no HIP calls, no state);
 // *_launch does what needs the runtime.
 bool conv_ws_select(const ConvArgs& a, ConvPlan* p);
+bool conv_ws_up_select(const ConvArgs& a, ConvPlan* p);    // conv_ws_up.hip: second kernel function of ConvKernel::ws (plan.t1 = 1)
 bool conv_ws8_select(const ConvArgs& a, ConvPlan* p);
 bool conv_sm_select(const ConvArgs& a, ConvPlan* p);
 bool conv1x1_rw_select(const ConvArgs& a, ConvPlan* p);
@@ -197,6 +198,7 @@ bool conv_head_select(const ConvArgs& a, ConvPlan* p);
 bool conv_stem_select(const ConvArgs& a, ConvPlan* p);
 bool conv_pipe_select(const ConvArgs& a, ConvPlan* p);     // conv_pipe_kernel and conv1x1_stream_kernel
 int conv_ws_launch(const ConvPlan& p, hipStream_t st);
+int conv_ws_up_launch(const ConvPlan& p, hipStream_t st);
 int conv_ws8_launch(const ConvPlan& p, hipStream_t st);
 int conv_sm_launch(const ConvPlan& p, hipStream_t st);
 int conv1x1_rw_launch(const ConvPlan& p, hipStream_t st);

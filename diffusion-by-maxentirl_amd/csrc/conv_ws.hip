@@ -31,7 +31,8 @@
 //
 // Scope: 3x3 / stride 1 / pad 1 (optionally behind a nearest x2 upsample), NHWC bf16 in (virtual concat) and out,
 // Cout % 64 == 0 (half-empty last cout tile masked), an even number (>= 4) of 32-channel chunks, maps >= 16x16 (one image per 256-pixel tile); 8x8 maps: conv_ws8.hip.
-// Everything else stays on conv_pipe.hip.
+// Everything else stays on conv_pipe.hip.  Full-width nearest-x2 upsample convs (OW = 2 IW in {16, 32}) run the family's second
+// kernel function, conv_ws_up_kernel (conv_ws_up.hip): same plan kind, id and statistics layout.
 #include "conv_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -817,10 +818,13 @@ bool conv_ws_select(const ConvArgs& a, ConvPlan* p) {
     p->lds = 2 * WS_HALO + WS_A_RING + WS_RO + WS_TB;
     p->id = 400000 + TW;    // conv_ws_kernel<TW>
     p->stats_tile = 128;    // one partial per (pixel tile, pixel half)
+    // the id names a family of two kernel functions: full-width nearest-x2 upsample convs run conv_ws_up_kernel<TW> (t1 = 1)
+    conv_ws_up_select(a, p);
     return true;
 }
 
 int conv_ws_launch(const ConvPlan& p, hipStream_t st) {
+    if (p.t1 == 1) return conv_ws_up_launch(p, st);
     static const void* zero_page = nullptr;
     DXMI_CHECK_ARG(conv_zero_page(zero_page, HIP_SYMBOL(ws_zero16)), "dxmi_conv2d_fwd(ws): hipGetSymbolAddress(ws_zero16) failed");
     ConvArgs b = p.args;
