@@ -179,6 +179,8 @@ SIGNATURES = {
     "dxmi_image_batch": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "dxmi_randn_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
     "dxmi_randint_indexed": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "dxmi_var_step_fwd_indexed": (c_int, [c_void_p] * 4 + [ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 7 + [c_int, c_int, c_int, c_void_p]),
+    "dxmi_edm_step_fwd_indexed": (c_int, [c_void_p] * 4 + [ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p]),
     "dxmi_ddpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 7 + [c_int, c_int, c_void_p]),
     "dxmi_dpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 8 + [c_int, c_int, c_void_p]),
 }

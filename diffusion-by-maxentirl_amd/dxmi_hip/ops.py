@@ -1920,6 +1920,72 @@ def randint_indexed(sample_index, shape_tail, low, high, seed, draw, out=None):
     return out
 
 
+def _step_indexed_operands(what, x, net_out, sample_index, ctl, per_sample, same, logp=None):
+    """The checks of the transitions that make their own noise: the checks of the indexed draws (_indexed_operands) on sample_index and
+    the state's shape tail, then x and net_out fp32 contiguous [N, ...] with a multiple of 4 elements per row, `same` (outputs, None
+    allowed) of that shape, `per_sample` fp32 contiguous with N elements, ctl (if given) a contiguous int32 [4].  The shapes are
+    judged before the devices, so a malformed call is named as such on a host without a device too.  -> (N, CHW)."""
+    if x.dim() < 2 or x.numel() == 0 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.DxmiError(f"{what}: the state must be a non-empty fp32 contiguous batch [N, ...], got {x.dtype} {tuple(x.shape)}")
+    N = x.shape[0]
+    chw = x.numel() // N
+    if chw % 4:
+        raise _lib.DxmiError(f"{what}: a row must hold a multiple of 4 elements, got {chw}")
+    if not torch.is_tensor(sample_index) or sample_index.shape != (N,):
+        raise _lib.DxmiError(f"{what}: sample_index must hold the state's {N} rows")
+    for v in (net_out,) + tuple(same):
+        if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape and v.device == x.device):
+            raise _lib.DxmiError(f"{what}: fp32 contiguous tensors of the state's shape {tuple(x.shape)} on its device")
+    for v in tuple(per_sample) + (logp,):
+        if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == N and v.device == x.device):
+            raise _lib.DxmiError(f"{what}: the per-sample vectors must be fp32 contiguous with {N} elements on the state's device")
+    if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4 and ctl.device == x.device):
+        raise _lib.DxmiError(f"{what}: ctl must be a contiguous int32 [4] on the state's device")
+    _need_cuda(x, net_out, ctl, logp, *per_sample, *same)
+    _indexed_operands(what, sample_index, tuple(x.shape[1:]), torch.float32, x)
+    return N, chw
+
+
+def var_step_indexed(x, eps, sample_index, xmul, cmul, sigma, seed=0, draw=0, ctl=None, want_mean=True, want_control=True, outs=None,
+                     assoc=0):
+    """var_step with its noise made in the launch (dxmi_var_step_fwd_indexed): bit for bit var_step(x, eps, z, ...) on z =
+    randn_indexed(sample_index, x.shape[1:], seed, draw).  ctl: an int32 [4] device block (unused, draw, seed low, seed high) that
+    replaces draw / seed, so a captured launch is fed per replay.  outs = (x_next, mean, control, logp), the last three None or not."""
+    what = "dxmi_var_step_fwd_indexed"
+    if assoc not in (0, 1):
+        raise _lib.DxmiError(f"{what}: assoc must be 0 or 1, got {assoc}")
+    if outs is None:
+        x_next = torch.empty_like(x)
+        mean = torch.empty_like(x) if want_mean else None
+        control = torch.empty_like(x) if want_control else None
+        logp = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    else:
+        x_next, mean, control, logp = outs
+        if x_next is None:
+            raise _lib.DxmiError(f"{what}: outs needs x_next")
+    N, CHW = _step_indexed_operands(what, x, eps, sample_index, ctl, (xmul, cmul, sigma), (x_next, mean, control), logp)
+    nb = 4.0 * N * CHW * (2 + 1 + (mean is not None) + (control is not None))
+    _prof("sampler_step", "var_step_indexed", 0.0, nb, lambda: check(
+        load().dxmi_var_step_fwd_indexed(_ptr(x), _ptr(eps), _ptr(sample_index), _ptr(ctl), int(draw) & 0xFFFFFFFF, int(seed) & _U64,
+                                         _ptr(xmul), _ptr(cmul), _ptr(sigma), _ptr(x_next), _ptr(mean), _ptr(control), _ptr(logp), N,
+                                         CHW, int(assoc), _stream()), what))
+    return x_next, mean, control, logp
+
+
+def edm_step_indexed(x, model_out, sample_index, sigma, sigma_down, sigma_up, sigma_data=0.5, seed=0, draw=0, ctl=None, outs=None):
+    """edm_step with its noise made in the launch (dxmi_edm_step_fwd_indexed): bit for bit edm_step(x, model_out, z, ...) on z =
+    randn_indexed(sample_index, x.shape[1:], seed, draw).  ctl as in var_step_indexed.  outs = (sample, mean)."""
+    what = "dxmi_edm_step_fwd_indexed"
+    sample, mean = (torch.empty_like(x), torch.empty_like(x)) if outs is None else outs
+    if sample is None or mean is None:
+        raise _lib.DxmiError(f"{what}: outs needs sample and mean")
+    N, CHW = _step_indexed_operands(what, x, model_out, sample_index, ctl, (sigma, sigma_down, sigma_up), (sample, mean))
+    check(load().dxmi_edm_step_fwd_indexed(_ptr(x), _ptr(model_out), _ptr(sample_index), _ptr(ctl), int(draw) & 0xFFFFFFFF,
+                                           int(seed) & _U64, _ptr(sigma), _ptr(sigma_down), _ptr(sigma_up), _ptr(sample), _ptr(mean), N,
+                                           CHW, float(sigma_data), _stream()), what)
+    return sample, mean
+
+
 def _sampler_stage(name, cols, mode, first, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out, pred_xstart, hist=()):
     """The checks and the call of the stage launches of the DDPM teacher's samplers (csrc/stage_common.h).  cols: the table's row
     length; first: the sampler's FIRST mode; hist: () for a sampler without a history, else (the tensor or None,)."""

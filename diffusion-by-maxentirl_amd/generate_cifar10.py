@@ -27,6 +27,11 @@ schedules): PATH is a plain state dict of the bare network, train_ddpm.py's ema_
 DPM-Solver++ (models/DxMI/dpm_sample.py dpm_sample), the ODE solver or its SDE variant: `--ddpm_steps S` network evaluations (10),
 `--solver_order {1,2,3}` (2; the SDE variant 1 or 2), `--solver_type {midpoint,exact}`, `--no_lower_order_final`, `--skip_type
 {logsnr,uniform,quad}` (logsnr).  --eta and --variance belong to the ancestral path and are refused with these solvers.
+
+`--sampler_generator {dummy,determ,determ-indiv}` is the DxMI sampler's own (--guidance_scale included; refused with --teacher_ckpt,
+which has --generator): with determ / determ-indiv image i of the run sees the same noise whatever --batchsize and the number of
+ranks are (models.cm.random_util with `--seed` as its seed), and the PNGs are named by that global index, `{i}.png` with
+i = b * batchsize * world + rank + k * world for row k of batch b, so the folders of two runs compare file by file.
 """
 import argparse
 import os
@@ -86,6 +91,9 @@ def parse_args(argv=None):
     ap.add_argument("--generator", type=str, default=None, choices=("dummy", "determ", "determ-indiv"),
                     help="with --teacher_ckpt: dummy (default) draws on the device; determ / determ-indiv make image i independent "
                          "of batch size and rank count (models/cm/random_util.py)")
+    ap.add_argument("--sampler_generator", type=str, default="dummy", choices=("dummy", "determ", "determ-indiv"),
+                    help="the DxMI sampler's draws (without --teacher_ckpt): dummy draws on the device; determ / determ-indiv make "
+                         "image i independent of batch size and rank count and name the PNGs by global index (--seed is their seed)")
     ap.add_argument("--config", type=str, default=None,
                     help="with --teacher_ckpt: builtin:NAME or a yaml path, for a --log_dir that holds no config.yaml")
     ap.add_argument("--solver", type=str, default=None, choices=("ancestral", "dpmpp", "sde-dpmpp"),
@@ -103,6 +111,8 @@ def parse_args(argv=None):
         ap.error(f"{', '.join(given)} only apply with --teacher_ckpt")
     if args.teacher_ckpt is not None and args.guidance_scale is not None:
         ap.error("--teacher_ckpt and --guidance_scale exclude each other")
+    if args.teacher_ckpt is not None and args.sampler_generator != "dummy":
+        ap.error("--sampler_generator is the DxMI sampler's: with --teacher_ckpt use --generator")
     if args.teacher_ckpt is not None and args.solver in SOLVERS:
         refused = [f"--{k}" for k in ("eta", "variance") if getattr(args, k) is not None]
         if refused:
@@ -201,13 +211,21 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")  # RCCL; only the final barrier uses it
 
-    def batch(_):
+    generator = None
+    if args.sampler_generator != "dummy":       # after the process group is up: the generator reads its rank and world size
+        from models.cm.random_util import get_generator
+        generator = get_generator(args.sampler_generator, int(args.n_generate / args.batchsize / world) * args.batchsize * world, args.seed)
+
+    def batch(i_batch):
+        if generator is not None:       # the images all ranks have finished; the batch's draws count from 0 again
+            generator.set_done_samples(i_batch * args.batchsize * world)
         with torch.no_grad():
             if trainer is not None:
-                return trainer.sample_guidance(n_sample=args.batchsize, device=device, guidance_scale=args.guidance_scale)["sample"]
-            return sampler.sample(args.batchsize, device=device)["sample"]
+                return trainer.sample_guidance(n_sample=args.batchsize, device=device, guidance_scale=args.guidance_scale,
+                                               generator=generator)["sample"]
+            return sampler.sample(args.batchsize, device=device, generator=generator)["sample"]
 
-    generate_and_score(args, run_config, batch, device, local_rank, world, output_path)
+    generate_and_score(args, run_config, batch, device, local_rank, world, output_path, by_global_index=generator is not None)
 
 
 def generate_teacher(args, run_config, net, device, local_rank, world, output_path):
@@ -250,8 +268,9 @@ def generate_teacher(args, run_config, net, device, local_rank, world, output_pa
     generate_and_score(args, run_config, batch, device, local_rank, world, output_path)
 
 
-def generate_and_score(args, run_config, batch, device, local_rank, world, output_path):
-    """batch(i) -> [batchsize, 3, H, W] in [-1, 1], n_batches times: PNGs under output_path, then the FID on rank 0."""
+def generate_and_score(args, run_config, batch, device, local_rank, world, output_path, by_global_index=False):
+    """batch(i) -> [batchsize, 3, H, W] in [-1, 1], n_batches times: PNGs under output_path, then the FID on rank 0.  The PNGs are
+    `{rank}_{count}.png`, or with by_global_index `{i}.png` by the deterministic generators' global index of the row."""
     n_batches = int(args.n_generate / args.batchsize / world)
     i_img = 0
     from utils import ImageWriter
@@ -264,7 +283,8 @@ def generate_and_score(args, run_config, batch, device, local_rank, world, outpu
             # rescale -> clamp -> save_image rounding on the device (dxmi_quantize_u8), pinned double-buffered copy on a side
             # stream, PNGs from a thread pool: the sampler never waits for the files
             n = sample.shape[0]
-            writer.submit(sample, [os.path.join(output_path, f"{local_rank}_{i_img + k}.png") for k in range(n)])
+            names = [f"{i_batch * n * world + local_rank + k * world}.png" if by_global_index else f"{local_rank}_{i_img + k}.png" for k in range(n)]
+            writer.submit(sample, [os.path.join(output_path, name) for name in names])
             i_img += n
     writer.close()
     torch.cuda.synchronize()

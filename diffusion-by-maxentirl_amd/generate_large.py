@@ -25,6 +25,11 @@ default, draws on the device as before.  `determ` / `determ-indiv` make image i 
 --batchsize and the number of ranks are (models.cm.random_util): image i is row k of batch b on rank r with
 i = b * batchsize * world + r + k * world, and samples_N.npz is written in that order.  `--seed` is the generator's seed (default:
 the config's training.seed).
+
+`--sampler_generator {dummy,determ,determ-indiv}` is the same choice for the DxMI sampler's own path (--guidance_scale included;
+refused with --karras_sampler / --cm_sampler, which have --generator): labels and noise of image i then do not depend on --batchsize
+or the number of ranks, every transition makes its draw inside its launch (dxmi_edm_step_fwd_indexed), `--seed` is accepted with it
+and samples_N.npz is written in global-index order.
 """
 import argparse
 import os
@@ -78,7 +83,11 @@ def build_parser():
     ap.add_argument("--generator", type=str, default="dummy", choices=("dummy", "determ", "determ-indiv"),
                     help="with --karras_sampler / --cm_sampler: determ / determ-indiv give image i of the run the same noise "
                          "whatever the batch size and the number of ranks (models/cm/random_util.py)")
-    ap.add_argument("--seed", type=int, default=None, help="seed of --generator determ / determ-indiv (default: the config's training.seed)")
+    ap.add_argument("--sampler_generator", type=str, default="dummy", choices=("dummy", "determ", "determ-indiv"),
+                    help="the DxMI sampler's draws (without --karras_sampler / --cm_sampler): determ / determ-indiv give image i of "
+                         "the run the same labels and noise whatever the batch size and the number of ranks")
+    ap.add_argument("--seed", type=int, default=None, help="seed of --generator / --sampler_generator determ / determ-indiv (default: the "
+                                                           "config's training.seed)")
     return ap
 
 
@@ -87,8 +96,10 @@ def parse_args(argv=None):
     consistency flags: they need --cm_sampler, which excludes --karras_sampler and --guidance_scale."""
     ap = build_parser()
     args, unknown = ap.parse_known_args(argv)
-    if args.generator == "dummy" and args.seed is not None:
-        ap.error("--seed only applies with --generator determ / determ-indiv")
+    if args.generator == "dummy" and args.sampler_generator == "dummy" and args.seed is not None:
+        ap.error("--seed only applies with --generator / --sampler_generator determ / determ-indiv")
+    if args.sampler_generator != "dummy" and (args.cm_sampler is not None or args.karras_sampler is not None):
+        ap.error("--sampler_generator is the DxMI sampler's: with --karras_sampler / --cm_sampler use --generator")
     if args.generator != "dummy" and args.cm_sampler is None and args.karras_sampler is None:
         ap.error("--generator determ / determ-indiv only applies with --karras_sampler or --cm_sampler")
     if args.cm_sampler is not None:
@@ -206,17 +217,25 @@ def main():
     from dxmi_hip import graph as hip_graph
     sampler.use_graph = hip_graph.default_enabled() and not args.no_graph        # second batch onwards: one hipGraphLaunch per batch
     n_batches = int(args.n_sample / args.batchsize / world)
+    generator = None                            # dummy: every draw on the device with torch
+    if args.sampler_generator != "dummy":       # after the process group is up: the generator reads its rank and world size
+        from models.cm.random_util import get_generator
+        generator = get_generator(args.sampler_generator, n_batches * args.batchsize * world,
+                                  cfg.training.seed if args.seed is None else args.seed)
     l_sample, i_img = [], 0
     from dxmi_hip import ops
     from utils import ImageWriter
     writer = ImageWriter()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(n_batches):
+    for i_batch in range(n_batches):
+        if generator is not None:               # the images all ranks have finished; the batch's draws count from 0 again
+            generator.set_done_samples(i_batch * args.batchsize * world)
         if trainer is not None:
-            d_sample = trainer.sample_guidance(n_sample=args.batchsize, device=device, guidance_scale=args.guidance_scale)
+            d_sample = trainer.sample_guidance(n_sample=args.batchsize, device=device, guidance_scale=args.guidance_scale,
+                                               generator=generator)
         else:
-            d_sample = sampler.sample(args.batchsize, device=device, i_class=None, enable_grad=False)
+            d_sample = sampler.sample(args.batchsize, device=device, i_class=None, enable_grad=False, generator=generator)
         sample = d_sample["sample"]
         if args.skip_fid:
             # ((sample + 1) / 2).clamp(0, 1) -> save_image (:36-41) on the device, pinned copy on a side stream, PNG thread pool
@@ -249,7 +268,8 @@ def finish(args, l_sample, device, local_rank, world):
     if world > 1:
         gathered = [torch.zeros_like(samples) for _ in range(world)]
         torch.distributed.all_gather(gathered, samples)
-        samples = torch.cat(gathered) if args.generator == "dummy" else index_order(gathered, args.batchsize)
+        indexed = args.generator != "dummy" or args.sampler_generator != "dummy"
+        samples = index_order(gathered, args.batchsize) if indexed else torch.cat(gathered)
     if local_rank == 0:
         np.savez(os.path.join(args.log_dir, f"samples_{len(samples)}.npz"), samples.permute(0, 2, 3, 1).cpu().numpy())
     if args.fid_extractor is None or args.fid_stats is None:

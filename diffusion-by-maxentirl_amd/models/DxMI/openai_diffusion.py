@@ -10,6 +10,9 @@ Device side, per step: ONE preconditioning kernel (c_in * x and the 250 ln(sigma
 U-Net, then ONE fused transition kernel (denoised, d, mean, x' = mean + sigma_up z) instead of the
 ~12 eager elementwise ops of :71-94.
 Extension: `noise=` injects the Gaussian draws (x_T and z_1..z_T) so CPU and GPU runs share "seeds".
+Extension: `generator=` (models.cm.random_util) draws the labels and the noise instead; with a DeterministicGenerator
+image i of a run gets the same labels and noise whatever the batch and however many ranks share the run, and every
+transition makes its draw inside its launch (dxmi_edm_step_fwd_indexed).
 """
 import torch
 import torch.nn as nn
@@ -18,6 +21,7 @@ from dxmi_hip import graph as _graph
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
 from models.cm.karras_diffusion import get_sigmas_karras
+from models.cm.random_util import DeterministicGenerator, draw_controls, sampling_generator
 
 
 class _EdmStepFn(torch.autograd.Function):
@@ -60,6 +64,7 @@ class OpenAIDiffusion:
         self._dev_tabs = {}
         self.use_graph = False      # sample(): replay the T-step loop of a fixed (batch, destination) as one hipGraph
         self._graphs = {}
+        self._generator = None      # the DeterministicGenerator of the sample() call in flight: what a replay's host inputs read
 
     def get_ancestral_step(self, sigmas):
         sigma_from, sigma_to = sigmas[:-1], sigmas[1:]
@@ -86,7 +91,10 @@ class OpenAIDiffusion:
         net = self.net.module if hasattr(self.net, "module") else self.net
         return net.log_betas
 
-    def sample_step(self, x, indices, noise=None, _outs=None, **model_kwargs):
+    def sample_step(self, x, indices, noise=None, _outs=None, generator=None, _indexed=None, **model_kwargs):
+        """generator: the draw comes from it instead of torch; a DeterministicGenerator's next draw is made inside the launch (row k
+        of x is row k of the generator's batch).  _indexed: sample()'s own sample_index and seed / draw or ctl of that launch."""
+        generator = sampling_generator("OpenAIDiffusion.sample_step", generator, noise)
         if not x.is_cuda:
             raise DxmiError("OpenAIDiffusion.sample_step runs only on the HIP device path (no CPU fallback)")
         sig_t, down_t, up_t = self._tabs(x.device)
@@ -102,13 +110,26 @@ class OpenAIDiffusion:
                 s = s * non_terminal + sigma_up * (~non_terminal)
             sigma_up = s
         x = x.contiguous().float()
-        z = torch.randn_like(x) if noise is None else noise
-        if torch.is_grad_enabled() and any(p.requires_grad for p in ops.fast_parameters(self.net)):
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in ops.fast_parameters(self.net))
+        if _indexed is None and isinstance(generator, DeterministicGenerator) and not grad:
+            _indexed = dict(sample_index=generator.get_indices(len(x), x.device), seed=generator.seed, draw=generator._next_draw())
+        if _indexed is not None:
+            z = None
+        elif generator is not None:
+            z = generator.randn_like(x).float()
+        else:
+            z = torch.randn_like(x) if noise is None else noise
+        if grad:
             return self._sample_step_grad(x, z, sigma, sigma_down, sigma_up, model_kwargs)
         x_in, rescaled_t = ops.edm_precond(x, sigma.contiguous(), self.diffusion.sigma_data)
         model_output = self.net(x_in, rescaled_t, **model_kwargs)
-        samples, mu = ops.edm_step(x, model_output, z.contiguous(), sigma.contiguous(), sigma_down.contiguous(),
-                                   sigma_up.detach().float().contiguous(), self.diffusion.sigma_data, outs=_outs)
+        if _indexed is not None:
+            samples, mu = ops.edm_step_indexed(x, model_output, sigma=sigma.contiguous(), sigma_down=sigma_down.contiguous(),
+                                               sigma_up=sigma_up.detach().float().contiguous(), sigma_data=self.diffusion.sigma_data,
+                                               outs=_outs, **_indexed)
+        else:
+            samples, mu = ops.edm_step(x, model_output, z.contiguous(), sigma.contiguous(), sigma_down.contiguous(),
+                                       sigma_up.detach().float().contiguous(), self.diffusion.sigma_data, outs=_outs)
         return {"sample": samples, "mean": mu, "sigma": sigma_up.clamp(1e-4, None)}
 
     def _sample_step_grad(self, x, z, sigma, sigma_down, sigma_up, model_kwargs):
@@ -123,28 +144,54 @@ class OpenAIDiffusion:
         samples, mu = _EdmStepFn.apply(x, model_output, z, sigma, sigma_down, sigma_up, self.diffusion.sigma_data)
         return {"sample": samples, "mean": mu, "sigma": sigma_up.clamp(1e-4, None)}
 
-    def sample(self, n_sample, device, i_class=None, enable_grad=False, x0=None, noise=None, out=None):
+    def sample(self, n_sample, device, i_class=None, enable_grad=False, x0=None, noise=None, out=None, generator=None):
         """noise: optional [T+1, n, C, H, W]; noise[0] * sigma_max is x_T, noise[1 + i] the draw of step i.
         The trajectory is ONE block [T+1, B, C, H, W] (+ [T, B, ...] mean, [T, B] sigma) written by the fused transition
-        kernel; out: a slot of a models.DxMI.replay.TransitionRing to generate in place in the replay buffer."""
+        kernel; out: a slot of a models.DxMI.replay.TransitionRing to generate in place in the replay buffer.
+        generator (models.cm.random_util; excludes noise=): None or a DummyGenerator: torch's draws.  Otherwise the labels come
+        first (class_cond and i_class None: generator.randint), and the result is, bit for bit, that of noise=[g.randn(size) for
+        T + 1 draws] of an identical generator after that label draw: x_T (unless x0 is given), then one draw per transition.  A
+        DeterministicGenerator makes each transition's draw inside its launch (dxmi_edm_step_fwd_indexed); any other generator
+        feeds generator.randn_like to the launches that take z."""
+        generator = sampling_generator("OpenAIDiffusion.sample", generator, noise)
         device = torch.device(device)
+        fused = isinstance(generator, DeterministicGenerator) and not enable_grad
         if self.use_graph and not enable_grad and x0 is None and noise is None and not isinstance(i_class, int) \
-                and device.type == "cuda" and not _graph.capturing():
-            # hipGraph replay (dxmi_hip/graph.py): one graph per (batch, destination, labels given or drawn); the first call of a key
-            # runs eagerly, the second is captured.  Without `out=` the returned tensors are static (overwritten by the next call).
+                and (generator is None or fused) and device.type == "cuda" and not _graph.capturing():
+            # hipGraph replay (dxmi_hip/graph.py): one graph per (batch, destination, labels given or drawn, torch or indexed noise);
+            # the first call of a key runs eagerly, the second is captured.  Without `out=` the returned tensors are static
+            # (overwritten by the next call).
             device = _graph.indexed_device(device)
             key = (n_sample, device.index, None if out is None else (id(out["ring"]), out["slot"]), i_class is not None)
+            if fused:
+                # the labels and x_T are drawn here and handed over as the graph's tensor arguments; the rows' indices and the
+                # transitions' draw numbers and seed are host inputs read from self._generator at every replay, so
+                # set_done_samples, a continued draw counter or another generator of the run replay the same capture
+                self._generator = generator
+                if self.class_cond and i_class is None:
+                    i_class = generator.randint(0, self.num_classes, (n_sample,), device=device)
+                key = key[:3] + (i_class is not None, "indexed")
+                x_T = generator.randn((n_sample,) + self.sample_shape, device=device).mul_(self.sigma_max)
+                g = self._graphs.get(key)
+                if g is None:
+                    fn = (lambda y, x: self._sample(n_sample, device, y, False, x, None, out, self._generator)) if i_class is not None \
+                        else (lambda x: self._sample(n_sample, device, None, False, x, None, out, self._generator))
+                    g = self._graphs[key] = _graph.StepGraph(fn, device, modules=_graph.pack_modules(self),
+                                                             name=f"OpenAIDiffusion.sample{key}")
+                return g(i_class, x_T) if i_class is not None else g(x_T)
             g = self._graphs.get(key)
             if g is None:
                 fn = (lambda y: self._sample(n_sample, device, y, False, None, None, out)) if i_class is not None else \
                      (lambda: self._sample(n_sample, device, None, False, None, None, out))
                 g = self._graphs[key] = _graph.StepGraph(fn, device, modules=_graph.pack_modules(self), name=f"OpenAIDiffusion.sample{key}")
             return g(i_class) if i_class is not None else g()
-        return self._sample(n_sample, device, i_class, enable_grad, x0, noise, out)
+        return self._sample(n_sample, device, i_class, enable_grad, x0, noise, out, generator)
 
-    def _sample(self, n_sample, device, i_class, enable_grad, x0, noise, out):
+    def _sample(self, n_sample, device, i_class, enable_grad, x0, noise, out, generator=None):
         if self.class_cond:
-            if i_class is None:
+            if i_class is None and generator is not None:
+                i_class = generator.randint(0, self.num_classes, (n_sample,), device=device)
+            elif i_class is None:
                 i_class = torch.randint(0, self.num_classes, (n_sample,), device=device)
             elif isinstance(i_class, int):
                 i_class = torch.tensor([i_class] * n_sample, device=device, dtype=torch.long)
@@ -168,15 +215,32 @@ class OpenAIDiffusion:
         elif noise is not None:
             traj[0].copy_(noise[0])
             traj[0].mul_(self.sigma_max)
+        elif generator is not None:
+            traj[0].copy_(generator.randn_like(traj[0]))
+            traj[0].mul_(self.sigma_max)
         else:
             traj[0].normal_().mul_(self.sigma_max)
         x = traj[0]
         l_x, l_mean, l_sigma = [x], [], []
+        fused, idx, ctl = isinstance(generator, DeterministicGenerator) and not enable_grad, None, None
+        if fused:
+            cur = _graph.current()
+            if cur is not None:
+                idx = cur.host_input(torch.int64, n_sample, lambda: self._generator.get_indices(n_sample, "cpu"))
+                ctl = cur.host_input(torch.int32, 4 * T, lambda: draw_controls(self._generator, T)).view(T, 4)
+            else:
+                idx = generator.get_indices(n_sample, device)
         for i in range(T):
+            kw = dict(model_kwargs)
+            if fused:
+                kw["_indexed"] = dict(sample_index=idx)
+                kw["_indexed"].update({"ctl": ctl[i]} if ctl is not None else {"seed": generator.seed, "draw": generator._next_draw()})
+            elif generator is not None:
+                kw["generator"] = generator
             with torch.set_grad_enabled(enable_grad):
                 d_step = self.sample_step(x, torch.full((len(x),), i, dtype=torch.long, device=device),
                                           noise=None if noise is None else noise[1 + i].to(device),
-                                          _outs=(traj[i + 1], mean_b[i]) if in_place else None, **model_kwargs)
+                                          _outs=(traj[i + 1], mean_b[i]) if in_place else None, **kw)
             x = d_step["sample"]
             l_x.append(x)
             l_mean.append(d_step["mean"])

@@ -397,20 +397,33 @@ class DxMI_Trainer:
         return self._stack_logs(logs)
 
     # ------------------------------------------------------------------ value-guided sampling
-    def sample_guidance(self, n_sample, device, x0=None, guidance_scale=None, t_select=None, noise=None):
+    def sample_guidance(self, n_sample, device, x0=None, guidance_scale=None, t_select=None, noise=None, generator=None):
         """reference :171-216: after every sampler transition, move the sample along the gradient of the value net at
         the next step, scaled by guidance_scale * sigma.  The transition is the fused HIP step; the input gradient of the
-        value net is its HIP backward (models/value_train.py).  noise: optional per-step draws (extension, as in sample)."""
+        value net is its HIP backward (models/value_train.py).  noise: optional per-step draws (extension, as in sample).
+        generator (models.cm.random_util; excludes noise=): None or a DummyGenerator: torch's draws, in today's order.  Otherwise
+        the labels (the class-conditional trainer) are drawn first, then x_T (unless x0 is given), then one draw per transition,
+        which a DeterministicGenerator makes inside the transition's launch: image i of a run then takes the same guided path
+        whatever the batch and however many ranks share the run."""
         from torch.distributions import Normal
         from ..modules import process_single_t
+        from ..cm.random_util import sampling_generator
         assert guidance_scale is not None, "guidance_scale must be given"
+        generator = sampling_generator("sample_guidance", generator, noise)
         _set_mode(self.v, False)
-        if x0 is None:
+        kw = None
+        if generator is not None:
+            kw = self._guidance_model_kwargs(n_sample, device, generator)
+            if x0 is None:
+                x0 = self._guidance_x0_scale(generator.randn(n_sample, *self.sampler.sample_shape, device=device))
+            kw["generator"] = generator
+        elif x0 is None:
             x0 = self._guidance_x0_scale(torch.randn(n_sample, *self.sampler.sample_shape, device=device))
         x0 = x0.to(device)
         l_x, l_guidance, l_logp, l_logp_orig = [x0.detach().clone()], [], [], []
         x = x0
-        kw = self._guidance_model_kwargs(n_sample, device)
+        if kw is None:
+            kw = self._guidance_model_kwargs(n_sample, device)
         for t in range(self.n_timesteps):
             tt = process_single_t(x, t)
             with torch.no_grad():
@@ -436,7 +449,7 @@ class DxMI_Trainer:
     def _guidance_x0_scale(self, x0):
         return x0
 
-    def _guidance_model_kwargs(self, n_sample, device):
+    def _guidance_model_kwargs(self, n_sample, device, generator=None):
         return {}
 
     class _frozen:
@@ -652,10 +665,11 @@ class DxMI_Trainer_Cond(DxMI_Trainer):
     def _guidance_x0_scale(self, x0):          # reference :818-820: EDM trajectories start at sigma_max * N(0, I)
         return x0 * self.sampler.sigma_max
 
-    def _guidance_model_kwargs(self, n_sample, device):   # reference :829-831 ("hard coding": random ImageNet labels)
+    def _guidance_model_kwargs(self, n_sample, device, generator=None):   # reference :829-831 ("hard coding": random ImageNet labels)
         if not self.sampler.class_cond:
             return {}
-        return {"y": torch.randint(0, self.sampler.num_classes or 1000, (n_sample,), device=device)}
+        draw = torch if generator is None else generator
+        return {"y": draw.randint(0, self.sampler.num_classes or 1000, (n_sample,), device=device)}
 
     def update_sampler_mixed_precision(self, state_dict, mp_trainer, d_sample=None):
         """reference :693-746: one optimiser step per `batchsize` slice of ALL buffered transitions."""

@@ -13,6 +13,9 @@ x' = mean + sigma z, Gaussian log-prob reduced over CHW) instead of ~10 eager op
 (reference :262-295); per-sample schedule scalars come from an integer-index gather kernel.
 Extension: `noise=` injects the Gaussian draws (x_T, z_1..z_T) — the only way to define
 "identical seeds" across CPU and GPU generators.
+Extension: `generator=` (models.cm.random_util) draws them instead; with a DeterministicGenerator image i
+of a run gets the same noise whatever the batch and however many ranks share the run, and every
+transition makes its draw inside its launch (dxmi_var_step_fwd_indexed).
 """
 import math
 
@@ -23,6 +26,7 @@ import torch.nn as nn
 from dxmi_hip import graph as _graph
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
+from ..cm.random_util import DeterministicGenerator, draw_controls, sampling_generator
 from ..modules import process_single_t
 
 diffusion_config = {"beta_0": 0.0001, "beta_T": 0.02, "T": 1000}
@@ -175,6 +179,7 @@ class VARSampler(nn.Module):
         self._tcache = {}
         self.use_graph = False      # sample(): replay the T-step loop of a fixed (batch, device, destination) as one hipGraph
         self._graphs = {}
+        self._generator = None      # the DeterministicGenerator of the sample() call in flight: what a replay's host inputs read
 
     def init_schedule(self):
         """reference :326-355."""
@@ -225,10 +230,11 @@ class VARSampler(nn.Module):
         if hi >= self.n_timesteps or lo < -self.n_timesteps:
             raise IndexError(f"timestep out of range for a {self.n_timesteps}-step sampler: [{lo}, {hi}]")
 
-    def _transition(self, x, t, z, assoc, outs=None, sigma_out=None, temb_rows=None, log_betas=None):
+    def _transition(self, x, t, z, assoc, outs=None, sigma_out=None, temb_rows=None, log_betas=None, indexed=None):
         """One fused transition for integer timesteps t [B] (device int64).  outs = (x_next, mean, control, logp) and
         sigma_out: preallocated destinations (rows of the trajectory block / replay ring).  temb_rows: this step's row of the
-        U-Net's timestep-branch table when the whole batch shares t (sample())."""
+        U-Net's timestep-branch table when the whole batch shares t (sample()).  indexed (with z None): sample_index and seed / draw
+        or ctl of ops.var_step_indexed, which makes the draw in the launch."""
         if log_betas is None:
             log_betas = self._log_betas_all().detach().float().contiguous()
         tau, xm, cm, sg = ops.var_gather_sched(t, self.continuous_steps, self.x_prev_multiplier, self.theta_multiplier,
@@ -236,49 +242,75 @@ class VARSampler(nn.Module):
         eps = self.net(x, tau) if temb_rows is None else self.net(x, tau, temb_rows=temb_rows)
         if self.adhoc_scale1 != 1.0:
             cm = cm * self.adhoc_scale1
-        x_next, mean, control, logp = ops.var_step(x, eps, z, xm, cm, sg, assoc=assoc, outs=outs)
+        if indexed is not None:
+            x_next, mean, control, logp = ops.var_step_indexed(x, eps, xmul=xm, cmul=cm, sigma=sg, assoc=assoc, outs=outs, **indexed)
+        else:
+            x_next, mean, control, logp = ops.var_step(x, eps, z, xm, cm, sg, assoc=assoc, outs=outs)
         return x_next, mean, control, logp, sg
 
     # ---- plugin API
-    def sample_step(self, x, t, y=None, noise=None):
-        """One transition with per-sample integer t (reference :357-408)."""
+    def sample_step(self, x, t, y=None, noise=None, generator=None):
+        """One transition with per-sample integer t (reference :357-408).  generator: the draw comes from it instead of torch; a
+        DeterministicGenerator's next draw is made inside the launch (row k of x is row k of the generator's batch)."""
+        generator = sampling_generator("VARSampler.sample_step", generator, noise)
         if not x.is_cuda:
             raise DxmiError("VARSampler.sample_step runs only on the HIP device path")
         self._check_t(t)
         t = process_single_t(x, t)
         if torch.is_grad_enabled() and any(p.requires_grad for p in ops.fast_parameters(self.net)):
             from .var_sampler_train import sample_step_with_grad
-            return sample_step_with_grad(self, x, t, noise)
-        z = torch.randn_like(x) if noise is None else noise
+            return sample_step_with_grad(self, x, t, noise if generator is None else generator.randn_like(x))
+        z = indexed = None
+        if isinstance(generator, DeterministicGenerator):
+            indexed = dict(sample_index=generator.get_indices(len(x), x.device), seed=generator.seed, draw=generator._next_draw())
+        elif generator is not None:
+            z = generator.randn_like(x).float().contiguous()
+        else:
+            z = (torch.randn_like(x) if noise is None else noise).contiguous()
         with torch.no_grad():
-            xn, mean, control, logp, sg = self._transition(x.contiguous().float(), t, z.contiguous(), assoc=0)
+            xn, mean, control, logp, sg = self._transition(x.contiguous().float(), t, z, assoc=0, indexed=indexed)
         sigma = sg.view(-1, 1, 1, 1)
         return {"sample": xn, "logp": logp, "logp_terminal": torch.zeros(len(x), device=x.device), "mean": mean,
                 "sigma": sigma, "entropy": torch.log(sigma), "control": control}
 
-    def sample(self, n_sample, device="cpu", enable_grad=False, noise=None, out=None):
+    def sample(self, n_sample, device="cpu", enable_grad=False, noise=None, out=None, generator=None):
         """T-step generation (reference :411-428 -> VAR_sampling :204-297).  The whole trajectory lives in ONE block
         [T+1, B, C, H, W] (+ [T, B, ...] mean / control, [T, B] logp / sigma) that the fused transition kernel writes
         directly; the returned lists are views of it.  out: a slot of a models.DxMI.replay.TransitionRing — the
-        trajectory is then generated in place in the replay buffer."""
+        trajectory is then generated in place in the replay buffer.
+        generator (models.cm.random_util; excludes noise=): None or a DummyGenerator: torch's draws.  Otherwise the result is, bit for
+        bit, that of noise=[g.randn(size) for T + 1 draws] of an identical generator: x_T first, then one draw per transition.  A
+        DeterministicGenerator makes each transition's draw inside its launch (dxmi_var_step_fwd_indexed); any other generator
+        feeds generator.randn_like to the launches that take z."""
+        generator = sampling_generator("VARSampler.sample", generator, noise)
         device = torch.device(device)
         if device.type != "cuda":
             raise DxmiError("VARSampler.sample runs only on the HIP device path (device must be cuda:N)")
         if enable_grad:
             raise NotImplementedError("enable_grad=True (fresh_sample_grad) is not used by the DxMI configs")
-        if self.use_graph and noise is None and not _graph.capturing():
-            # hipGraph replay (dxmi_hip/graph.py): one graph per (batch, destination); the first call of a key runs eagerly, the
-            # second is captured.  Without `out=` the returned tensors are static: the next call with the same key overwrites them.
+        fused = isinstance(generator, DeterministicGenerator)
+        if self.use_graph and noise is None and (generator is None or fused) and not _graph.capturing():
+            # hipGraph replay (dxmi_hip/graph.py): one graph per (batch, destination, torch or indexed noise); the first call of a key
+            # runs eagerly, the second is captured.  Without `out=` the returned tensors are static: the next call with the same key
+            # overwrites them.
             device = _graph.indexed_device(device)
             key = (n_sample, device.index, None if out is None else (id(out["ring"]), out["slot"]))
+            if fused:
+                # x_T is drawn here and handed over as the graph's one tensor argument; the rows' indices and the transitions' draw
+                # numbers and seed are host inputs read from self._generator at every replay, so set_done_samples, a continued draw
+                # counter or another generator of the run replay the same capture
+                key += ("indexed",)
+                self._generator = generator
+                x_T = generator.randn((n_sample,) + tuple(self.sample_shape), device=device)
             g = self._graphs.get(key)
             if g is None:
-                g = self._graphs[key] = _graph.StepGraph(lambda: self._sample(n_sample, device, None, out), device,
-                                                         modules=[self._bare_net()], name=f"VARSampler.sample{key}")
-            return g()
-        return self._sample(n_sample, device, noise, out)
+                fn = (lambda x0: self._sample(n_sample, device, None, out, self._generator, x0)) if fused else \
+                     (lambda: self._sample(n_sample, device, None, out))
+                g = self._graphs[key] = _graph.StepGraph(fn, device, modules=[self._bare_net()], name=f"VARSampler.sample{key}")
+            return g(x_T) if fused else g()
+        return self._sample(n_sample, device, noise, out, generator)
 
-    def _sample(self, n_sample, device, noise, out):
+    def _sample(self, n_sample, device, noise, out, generator=None, x_T=None):
         shape = tuple(self.sample_shape)
         size = (n_sample,) + shape
         T = self.n_timesteps
@@ -290,10 +322,22 @@ class VARSampler(nn.Module):
         else:
             traj, mean_b, control_b, logp_b, sigma_b = (out[k] for k in ("traj", "mean", "control", "logp", "sigma"))
             assert traj.shape == (T + 1,) + size and traj.device == device, "ring slot does not match this sampler / batch"
-        if noise is None:
+        fused, idx, ctl = isinstance(generator, DeterministicGenerator), None, None
+        if x_T is not None:
+            traj[0].copy_(x_T)
+        elif generator is not None:
+            traj[0].copy_(generator.randn_like(traj[0]))
+        elif noise is None:
             traj[0].normal_()
         else:
             traj[0].copy_(noise[0])
+        if fused:
+            cur = _graph.current()
+            if cur is not None:
+                idx = cur.host_input(torch.int64, n_sample, lambda: self._generator.get_indices(n_sample, "cpu"))
+                ctl = cur.host_input(torch.int32, 4 * T, lambda: draw_controls(self._generator, T)).view(T, 4)
+            else:
+                idx = generator.get_indices(n_sample, device)
         with torch.no_grad():
             # every image of a generation step shares its timestep: the U-Net's timestep branch (embedding, two dense layers,
             # all temb_proj) is evaluated once per sample() call on the T distinct timesteps instead of on T x B identical rows
@@ -302,10 +346,17 @@ class VARSampler(nn.Module):
                 table = self._bare_net().temb_table(self.continuous_steps[:T].to(device).float().contiguous())
             lb = self._log_betas_all().detach().float().contiguous()     # the sigma table does not change inside a sample() call
             for i in range(T):
-                z = torch.randn(size, device=device) if noise is None else noise[i + 1].to(device).float().contiguous()
+                z = indexed = None
+                if fused:
+                    indexed = dict(sample_index=idx)
+                    indexed.update({"ctl": ctl[i]} if ctl is not None else {"seed": generator.seed, "draw": generator._next_draw()})
+                elif generator is not None:
+                    z = generator.randn_like(traj[i]).float().contiguous()
+                else:
+                    z = torch.randn(size, device=device) if noise is None else noise[i + 1].to(device).float().contiguous()
                 self._transition(traj[i], self._t_const(n_sample, i, device), z, assoc=1,
                                  outs=(traj[i + 1], mean_b[i], control_b[i], logp_b[i]), sigma_out=sigma_b[i],
-                                 temb_rows=None if table is None else table[i:i + 1], log_betas=lb)
+                                 temb_rows=None if table is None else table[i:i + 1], log_betas=lb, indexed=indexed)
         d = {"sample": traj[T], "l_sample": list(traj.unbind(0)), "logp": list(logp_b.unbind(0)),
              "logp_terminal": torch.zeros(n_sample, device=device), "mean": list(mean_b.unbind(0)),
              "sigma": [s_.view(-1, 1, 1, 1) for s_ in sigma_b.unbind(0)], "control": list(control_b.unbind(0))}

@@ -35,6 +35,24 @@ def get_generator(generator, num_samples=0, seed=0):
         raise NotImplementedError
 
 
+def sampling_generator(what, generator, noise=None):
+    """What a DxMI sampler (VARSampler, OpenAIDiffusion, sample_guidance) draws with: None for no generator or a DummyGenerator (the
+    sampler's own torch draws), else the generator.  Noise is injected or generated, not both."""
+    if generator is not None and noise is not None:
+        raise ValueError(f"{what}: noise= and generator= exclude each other")
+    return None if isinstance(generator, DummyGenerator) else generator
+
+
+def draw_controls(generator, n):
+    """The next n draw numbers of a DeterministicGenerator as n control blocks (unused, draw, seed low word, seed high word): the
+    host input of n captured launches that make their own noise (dxmi_var_step_fwd_indexed, dxmi_edm_step_fwd_indexed)."""
+    seed = int(generator.seed) & ((1 << 64) - 1)
+    out = []
+    for _ in range(n):
+        out += [0, generator._next_draw() & 0xFFFFFFFF, seed & 0xFFFFFFFF, seed >> 32]
+    return out
+
+
 class DummyGenerator:
     def randn(self, *args, **kwargs):
         return torch.randn(*args, **kwargs)

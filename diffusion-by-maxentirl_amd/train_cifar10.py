@@ -78,7 +78,9 @@ class FidEvaluator:
     sample() call (with use_graph the returned tensors are the graph's static outputs), activations gathered over RCCL, statistics
     by dxmi_fid_stats, the distance by `distance` ("device": fp64 MFMA Newton-Schulz, "host": scipy's sqrtm).  Every rank computes
     the same value; rank 0 keeps the best-scoring sampler as sampler.pth / value.pth, which is what generate_cifar10.py loads.
-    The samples go to no replay ring, and the sampler's train() / eval() flag is put back."""
+    The samples go to no replay ring, and the sampler's train() / eval() flag is put back.
+    --fid_generator determ: every evaluation samples the same n_fid_samples noise streams (a DeterministicGenerator seeded with
+    training.seed, set_done_samples before each batch), so the FID of two checkpoints differs by the weights alone."""
 
     def __init__(self, args, cfg, trainer, sampler, logdir, device, rank, world):
         from pytorch_fid.fid_score import load_extractor, load_statistics
@@ -90,6 +92,16 @@ class FidEvaluator:
         self.sampling_batchsize = cfg.training.sampling_batchsize
         self.trainer, self.sampler, self.logdir, self.device, self.rank = trainer, sampler, logdir, device, rank
         self.best_fid = float("inf")
+        self.world, self.generator = world, None
+        if getattr(args, "fid_generator", "dummy") != "dummy":      # built after the process group: it reads its rank and world size
+            from models.cm.random_util import get_generator
+            self.generator = get_generator(args.fid_generator, self.n_batches * self.sampling_batchsize * world, cfg.training.seed)
+
+    def _batch(self, i_batch):
+        if self.generator is not None:
+            self.generator.set_done_samples(i_batch * self.sampling_batchsize * self.world)
+            return self.sampler.sample(self.sampling_batchsize, device=self.device, generator=self.generator)["sample"]
+        return self.sampler.sample(self.sampling_batchsize, device=self.device)["sample"]
 
     def __call__(self, epoch, i_iter):
         from dxmi_hip import ops
@@ -97,8 +109,7 @@ class FidEvaluator:
         was_training = self.sampler.training
         print0("generating images for FID evaluation")
         self.sampler.eval()
-        images = torch.cat([ops.quantize_u8(self.sampler.sample(self.sampling_batchsize, device=self.device)["sample"], mode=0, nhwc=False)
-                            for _ in range(self.n_batches)])
+        images = torch.cat([ops.quantize_u8(self._batch(i), mode=0, nhwc=False) for i in range(self.n_batches)])
         print0("calculating FID score")
         fid = fid_from_images(images, self.extractor, self.m2, self.s2, batch_size=50, dims=self.dims, device=self.device,
                               distance=self.distance)
@@ -194,6 +205,9 @@ def parse_args(argv=None):
     ap.add_argument("--fid_dims", type=int, default=2048)
     ap.add_argument("--fid_distance", choices=("device", "host"), default="device",
                     help="the Frechet distance of an evaluation: fp64 MFMA Newton-Schulz on the device, or scipy's sqrtm on the host")
+    ap.add_argument("--fid_generator", choices=("dummy", "determ"), default="dummy",
+                    help="the noise of the in-training FID: dummy draws afresh at every evaluation; determ gives every evaluation the "
+                         "same n_fid_samples noise streams (models/cm/random_util.py, seeded with training.seed)")
     args, unknown = ap.parse_known_args(argv)
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")

@@ -117,6 +117,9 @@ def parse_args(argv=None):
     ap.add_argument("--no_graph", action="store_true",
                     help="issue every kernel launch from python instead of replaying the three phases of an iteration as hipGraphs "
                          "(dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
+    ap.add_argument("--fid_generator", choices=("dummy", "determ"), default="dummy",
+                    help="the labels and noise of the periodic fid(): dummy draws afresh at every evaluation; determ gives every "
+                         "evaluation the same n_fid_samples streams (models/cm/random_util.py, seeded with training.seed)")
     args, unknown = ap.parse_known_args(argv)
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")
@@ -200,13 +203,23 @@ def main():
         extractor = load_extractor(args.fid_extractor)
         extractor = extractor.to(device) if hasattr(extractor, "to") else extractor
         m2, s2 = load_statistics(args.fid_stats)
+    fid_generator = None
+    if fid_on and args.fid_generator != "dummy":        # after the process group is up: the generator reads its rank and world size
+        from models.cm.random_util import get_generator
+        sb = cfg.training.sampling_batchsize
+        fid_generator = get_generator(args.fid_generator, int(cfg.training.n_fid_samples / sb / world) * sb * world, seed)
+
+    def fid_batch(i_batch, sb):
+        if fid_generator is not None:                   # every evaluation: the same labels and noise for image i
+            fid_generator.set_done_samples(i_batch * sb * world)
+        return sampler.sample(sb, device=device, i_class=None, enable_grad=False, generator=fid_generator)["sample"]
 
     def fid(it):
         nonlocal best_fid
         sb = cfg.training.sampling_batchsize
         sampler.eval()
-        mine = [ops.quantize_u8(sampler.sample(sb, device=device, i_class=None, enable_grad=False)["sample"].contiguous().float(),
-                                mode=1, nhwc=False) for _ in range(int(cfg.training.n_fid_samples / sb / world))]
+        mine = [ops.quantize_u8(fid_batch(i, sb).contiguous().float(), mode=1, nhwc=False)
+                for i in range(int(cfg.training.n_fid_samples / sb / world))]
         samples = torch.cat(mine)
         if world > 1:                                   # reference :50-53, :59: gather the images, take this rank's strided share
             parts = [torch.zeros_like(samples) for _ in range(world)]

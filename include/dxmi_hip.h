@@ -973,6 +973,34 @@ int dxmi_randn_indexed(float* out, const int64_t* sample_index, int32_t N, int64
 int dxmi_randint_indexed(int64_t* out, const int64_t* sample_index, int32_t N, int64_t per_sample, int64_t low, int64_t high,
                          uint64_t seed, uint32_t draw, void* stream);
 
+/* The DxMI samplers' transitions with the noise made in the launch (csrc/step_indexed.hip): dxmi_var_step_fwd and
+ * dxmi_edm_step_fwd without their z operand.  The kernel makes
+ *   z[n][e] = the value dxmi_randn_indexed gives for (seed, sample_index[n], draw, e)
+ * (key = the two halves of the seed, counter = (e / 4, draw, index low word, index high word), the same Philox / Box-Muller
+ * functions: the same bits) and then forms what the launch it is named after forms from x, the network output and z.  Every output
+ * is BIT FOR BIT that of dxmi_randn_indexed followed by dxmi_var_step_fwd / dxmi_edm_step_fwd on the z it wrote: the fused
+ * multiply-adds those two kernels are compiled to are written out here (VAR: mean = fma(xmul, x, control), assoc 1: x' = xmul x +
+ * fma(sigma, z, control), assoc 0: x' = fma(sigma, z, mean); EDM: denoised = fma(c_out, F, c_skip x), mean = fma(sigma_down - sigma,
+ * d, x), sample = fma(sigma_up, z, mean); everything else one rounding per operation), and logp is reduced in the same order.  The
+ * launch saves the pair one launch and one write plus read of z per transition.
+ * dxmi_var_step_fwd_indexed: x_next, mean, control ([N, CHW]) and logp ([N]) as dxmi_var_step_fwd writes them, assoc 0 or 1 with its
+ *   meaning there; mean, control and logp may be NULL.
+ * dxmi_edm_step_fwd_indexed: sample and mean ([N, CHW]) as dxmi_edm_step_fwd writes them; N <= 65535.
+ * sample_index: int64 [N] on the device, the global index of row n; a row's noise depends on its own index only.
+ * Control: ctl NULL: draw and seed are the by-value arguments.  ctl not NULL: an int32[4] block on the DEVICE laid out as that of
+ *   dxmi_ddpm_stage = (unused, draw, seed low word, seed high word), read by the kernel (the by-value two are ignored), so a
+ *   captured launch is fed per replay.
+ * DXMI_EINVAL with a message and no launch: a null pointer (but the optional ones), N <= 0, CHW not a multiple of 4 in [4, 2^30],
+ *   assoc outside {0, 1}, or a misaligned tensor (x, the network output and the [N, CHW] outputs 16-byte; sample_index 8-byte; ctl, the
+ *   per-sample vectors and logp 4-byte).  One workgroup per image (VAR) or per 1024 elements up to 64 per image (EDM), f32x4 per
+ *   lane; with the generator the launch is VALU-bound.  No workspace, no atomics; LDS: VAR's four partial sums. */
+int dxmi_var_step_fwd_indexed(const float* x, const float* eps, const int64_t* sample_index, const int32_t* ctl, uint32_t draw,
+                              uint64_t seed, const float* xmul, const float* cmul, const float* sigma, float* x_next, float* mean,
+                              float* control, float* logp, int32_t N, int32_t CHW, int32_t assoc, void* stream);
+int dxmi_edm_step_fwd_indexed(const float* x, const float* model_out, const int64_t* sample_index, const int32_t* ctl, uint32_t draw,
+                              uint64_t seed, const float* sigma, const float* sigma_down, const float* sigma_up, float* sample,
+                              float* mean, int32_t N, int32_t CHW, float sigma_data, void* stream);
+
 /* Ancestral / DDIM sampling of the DDPM teacher (csrc/ddpm_sample.hip; models/DxMI/ddpm_sample.py): Ho et al. 2020,
  * "Denoising Diffusion Probabilistic Models", Algorithm 2; Song et al. 2021, "Denoising Diffusion Implicit Models", eq. 12 and 16.
  * dxmi_ddpm_stage is the ONE launch between two network evaluations.  With eps the output of the evaluation just done at the state
