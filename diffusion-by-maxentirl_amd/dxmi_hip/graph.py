@@ -9,7 +9,7 @@ then stream-captured ONCE into hipGraphs, and every later call is: host producer
 What makes a python step replayable:
   * static addresses     tensor arguments are copied into static input buffers; everything the step allocates while it is being
                          captured comes from the graph's private pool (torch's caching allocator) and keeps its address;
-                         packed weights are refreshed IN PLACE (ops.pack_batch(reuse=...)) and a re-allocation anywhere bumps
+                         packed weights are refreshed IN PLACE (packs.WeightPacks replays its plan) and a full build anywhere bumps
                          ops.PACK_GENERATION, which makes every StepGraph re-capture itself;
   * host inputs          values the host computes per step — Adam's bias-corrected step sizes, dropout seeds, `torch.randperm`
                          rows (CPU generator: reference trainer.py:271, :352) — are DECLARED while capturing

@@ -163,54 +163,25 @@ class PackedConvWeight:
 
 
 _PACK_BATCH = None
-_PACK_REC = None            # the outermost active pack_batch: hands out (and records) the destination buffers of the block
-PACK_GENERATION = 0         # bumped whenever a recorded packed-weight buffer is freshly allocated (dxmi_hip/graph.py re-captures)
+PACK_GENERATION = 0         # bumped by every full build of a packed-weight set (dxmi_hip/packs.py); dxmi_hip/graph.py re-captures
 
 
 class pack_batch:
     """`with ops.pack_batch():` — every pack_conv_weight() inside allocates its destination and is DEFERRED; on exit all of
-    them run as a few multi-tensor launches (dxmi_pack_conv_weights).  The nets' `_pack` / `_pack_t` use it: after an
-    optimiser step ~60 (CIFAR U-Net) to ~330 (ImageNet-64 EDM net) weights are refreshed.
-    Every destination the block asks for (packed fragments, and the derived tensors of `pack_tensor`) is recorded in call order
-    in `.buffers`; `pack_batch(reuse=previous.buffers)` hands the SAME buffers out again in the same order: a re-pack after an
-    optimiser step (parameters updated in place) then rewrites the fragments where they are — the addresses a captured hipGraph
-    holds stay valid (dxmi_hip/graph.py).  A block that allocates anything fresh bumps PACK_GENERATION."""
-
-    def __init__(self, reuse=None):
-        self.reuse = list(reuse) if reuse is not None else None
+    them run as a few multi-tensor launches (dxmi_pack_conv_weights), and `.plan` is the PackPlan that ran them (None when nothing
+    was deferred).  The nets' packed-weight sets are built in one (dxmi_hip/packs.py): after an optimiser step ~60 (CIFAR U-Net)
+    to ~330 (ImageNet-64 EDM net) weights are refreshed."""
 
     def __enter__(self):
-        global _PACK_BATCH, _PACK_REC
+        global _PACK_BATCH
         self.plan = None
-        self.nested = _PACK_REC is not None
         self.outer = _PACK_BATCH is not None or os.environ.get("DXMI_PACK_BATCH", "1") == "0"     # (=0: one launch per weight, A/B timing)
         if not self.outer:
             _PACK_BATCH = []
-        if not self.nested:
-            _PACK_REC = self
-            self.buffers, self.cursor, self.fresh = [], 0, False
         return self
 
-    def alloc(self, shape, dtype, device):
-        """Next destination of the block: the matching buffer of `reuse`, or a new one."""
-        shape = (shape,) if isinstance(shape, int) else tuple(shape)
-        if self.reuse is not None and self.cursor < len(self.reuse):
-            t = self.reuse[self.cursor]
-            if tuple(t.shape) != shape or t.dtype != dtype or t.device != torch.device(device):
-                raise _lib.DxmiError("pack_batch(reuse=...): the block asks for different buffers than the pack it replays")
-        else:
-            t = torch.empty(shape, dtype=dtype, device=device)
-            self.fresh = True
-        self.cursor += 1
-        self.buffers.append(t)
-        return t
-
     def __exit__(self, *exc):
-        global _PACK_BATCH, _PACK_REC, PACK_GENERATION
-        if not self.nested:
-            _PACK_REC = None
-            if self.fresh:
-                PACK_GENERATION += 1
+        global _PACK_BATCH
         if self.outer:
             return False
         items, _PACK_BATCH = _PACK_BATCH, None
@@ -225,10 +196,7 @@ class pack_batch:
 
 
 def pack_tensor(shape, dtype, device):
-    """Destination for a DERIVED tensor of a weight pack (concatenated biases, zero-padded sources): recorded / reused by the
-    enclosing pack_batch like the packed fragments; a plain allocation outside one."""
-    if _PACK_REC is not None:
-        return _PACK_REC.alloc(shape, dtype, device)
+    """The destination buffer of a pack (a plain allocation; no launch)."""
     return torch.empty(shape, dtype=dtype, device=device)
 
 
@@ -1270,12 +1238,13 @@ def attention_proj_supported(T, C, heads):
     return bool(load().dxmi_attention_proj_supported(T, C, heads))
 
 
-def pack_attn_proj_weight(w):
-    """proj_out weight [256, 256(, 1, 1)] fp32 -> the 128 KiB bf16 fragment image dxmi_attention_proj_fwd reads."""
+def pack_attn_proj_weight(w, out=None):
+    """proj_out weight [256, 256(, 1, 1)] fp32 -> the 128 KiB bf16 fragment image dxmi_attention_proj_fwd reads (out: rewrite that
+    image in place)."""
     _need_cuda(w)
     w2 = w.detach().float().reshape(w.shape[0], -1).contiguous()
     assert tuple(w2.shape) == (256, 256)
-    dst = pack_tensor(256 * 256, torch.bfloat16, w.device)
+    dst = pack_tensor(256 * 256, torch.bfloat16, w.device) if out is None else out
     check(load().dxmi_pack_attn_proj_weight(_ptr(w2), _ptr(dst), _stream()), "dxmi_pack_attn_proj_weight")
     return dst
 
@@ -1302,14 +1271,14 @@ def attn_block_supported(T, C, heads, groups=32):
     return bool(load().dxmi_attn_block_supported(T, C, heads, groups))
 
 
-def attn_block_pack(wq, bq, wk, wv, bv, wproj, bproj, scale):
+def attn_block_pack(wq, bq, wk, wv, bv, wproj, bproj, scale, out=None):
     """Folded + packed weights of a whole AttnBlock (include/dxmi_hip.h: dxmi_attn_block_pack): G = scale Wk^T Wq, W' = Wproj Wv,
     g = scale Wk^T bq, b' = bproj + Wproj bv.  The k bias has no effect on the block (constant along the key axis of the softmax)."""
     ws = [t.detach().float().reshape(t.shape[0], -1).contiguous() for t in (wq, wk, wv, wproj)]
     bs = [t.detach().float().contiguous() for t in (bq, bv, bproj)]
     _need_cuda(*ws, *bs)
     assert all(tuple(w.shape) == (256, 256) for w in ws) and all(b.numel() == 256 for b in bs)
-    dst = pack_tensor(int(load().dxmi_attn_block_packed_bytes()), torch.uint8, ws[0].device)
+    dst = pack_tensor(int(load().dxmi_attn_block_packed_bytes()), torch.uint8, ws[0].device) if out is None else out
     check(load().dxmi_attn_block_pack(_ptr(ws[0]), _ptr(bs[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(bs[1]), _ptr(ws[3]), _ptr(bs[2]),
                                       float(scale), _ptr(dst), _stream()), "dxmi_attn_block_pack")
     return dst

@@ -59,7 +59,7 @@ def _host_step_counters(opt):
 
 def _bump_versions(params):
     """The kernels write parameters through raw pointers, which autograd's version counters do not see, while every
-    packed bf16 weight cache (Model._param_key, modules._pack_t ...) is keyed on (data_ptr, _version): without the bump the
+    packed bf16 weight cache (dxmi_hip/packs.py) is keyed on (data_ptr, _version): without the bump the
     nets would keep running on the weights of the first pack.  No kernel is launched."""
     torch.autograd.graph.increment_version(params)
 

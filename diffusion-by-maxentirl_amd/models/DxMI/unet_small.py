@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
+from dxmi_hip.packs import PackedWeights, WeightPacks
 
 
 def Normalize(in_channels):
@@ -91,7 +92,7 @@ class _Normed:
         self.y, self.norm = y, norm
 
 
-class Model(nn.Module):
+class Model(PackedWeights, nn.Module):
     def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0,
                  resamp_with_conv=True, in_channels, resolution):
         super().__init__()
@@ -152,9 +153,7 @@ class Model(nn.Module):
 
         self.norm_out = Normalize(block_in)
         self.conv_out = _conv(block_in, out_ch, 3, 1, 1)
-        self._packed = None
-        self._packed_key = None
-        self._pack_bufs = None
+        self._packs = WeightPacks(self, Model._build_packs)
         self.dropout_seed = None          # base seed of the dropout hash (None: torch.initial_seed() at first use)
         self.dropout_seeds_used = []      # seeds of the most recent training forward, in _resblocks() call order
         self._dropout_calls = 0
@@ -177,79 +176,39 @@ class Model(nn.Module):
         for lvl in reversed(self.up):
             yield from lvl.block
 
-    def _param_key(self):
-        # torch bumps _version on every in-place update (optimizer.step, load_state_dict, .to())
-        return tuple((p.data_ptr(), p._version) for p in ops.fast_parameters(self))
-
-    def _pack(self, reuse=None):
-        """(Re)build the bf16 MFMA weight fragments from the fp32 master parameters.  reuse: the buffers of the previous pack
-        (parameters updated in place): the fragments are rewritten where they are (ops.pack_batch)."""
-        with ops.pack_batch(reuse=reuse) as pb:            # every pack below runs in a few multi-tensor launches
-            pk = {}
-            dev = self.conv_in.weight.device
-            f32 = torch.float32
-            pk["dense0"] = ops.pack_conv_weight(self.temb.dense[0].weight)
-            pk["dense1"] = ops.pack_conv_weight(self.temb.dense[1].weight)
-            blocks = list(self._resblocks())
-            # every temb_proj of the net in ONE [sum(Cout), temb_ch] operator (reference :123)
-            pk["tproj"] = ops.pack_conv_weight(torch.cat([b.temb_proj.weight for b in blocks], 0))
-            pk["tproj_bias"] = torch.cat([b.temb_proj.bias.detach() for b in blocks], 0,
-                                         out=ops.pack_tensor(sum(b.out_channels for b in blocks), f32, dev))
-            off = 0
-            for b in blocks:
-                pk[id(b), "toff"] = off
-                off += b.out_channels
-                pk[id(b), "conv1"] = ops.pack_conv_weight(b.conv1.weight)
-                pk[id(b), "conv2"] = ops.pack_conv_weight(b.conv2.weight)
-                if b.in_channels != b.out_channels:
-                    sc = b.conv_shortcut if b.use_conv_shortcut else b.nin_shortcut
-                    pk[id(b), "short"] = ops.pack_conv_weight(sc.weight)
-            for m in self.modules():
-                if isinstance(m, AttnBlock):
-                    pk[id(m), "qkv"] = ops.pack_conv_weight(torch.cat([m.q.weight, m.k.weight, m.v.weight], 0))
-                    pk[id(m), "qkv_bias"] = torch.cat([m.q.bias.detach(), m.k.bias.detach(), m.v.bias.detach()], 0,
-                                                      out=ops.pack_tensor(3 * m.in_channels, f32, dev))
-                    pk[id(m), "proj"] = ops.pack_conv_weight(m.proj_out.weight)
-                    if m.in_channels == 256:      # the 16x16 blocks: proj_out fused behind the attention (ops.attention_proj)
-                        pk[id(m), "proj_attn"] = ops.pack_attn_proj_weight(m.proj_out.weight)
-                        # ... and the whole block as one launch (round 5: ops.attn_block, folded Wk^T Wq / Wproj Wv)
-                        pk[id(m), "block"] = ops.attn_block_pack(m.q.weight, m.q.bias, m.k.weight, m.v.weight, m.v.bias,
-                                                                 m.proj_out.weight, m.proj_out.bias, float(int(m.in_channels) ** (-0.5)))
-                elif isinstance(m, (Upsample, Downsample)):
-                    pk[id(m), "conv"] = ops.pack_conv_weight(m.conv.weight)
-            pk["conv_in"] = ops.pack_conv_weight(self.conv_in.weight, k27=(self.in_channels == 3))
-            pk["conv_out"] = ops.pack_conv_weight(self.conv_out.weight)
-        assert dev.type == "cuda"
-        self._pack_bufs = pb.buffers
-        return pk
-
-    @staticmethod
-    def _same_storage(key, old_key):
-        return old_key is not None and len(key) == len(old_key) and all(a[0] == b[0] for a, b in zip(key, old_key))
-
-    def packed(self):
-        key = self._param_key()
-        if self._packed is None or key != self._packed_key:
-            # parameters updated in place (an optimiser step): the same buffers are rewritten, so every address a captured
-            # hipGraph holds stays valid (dxmi_hip/graph.py); moved parameters (.to(), a new tensor): fresh buffers
-            reuse = self._pack_bufs if (self._packed is not None and self._same_storage(key, self._packed_key)) else None
-            self._packed, self._packed_key = self._pack(reuse=reuse), key
-        return self._packed
-
-    def refresh_packs(self):
-        """Bring every packed-weight set of the net that exists up to date with the parameters (no-op when they are)."""
-        self.packed()
-        if getattr(self, "_packed_t", None) is not None:
-            from .unet_small_train import _pack_t
-            _pack_t(self)
-
-    def prepare_capture(self):
-        """Before a StepGraph capture: on-demand entries of the transposed set (packed by a backward when first needed) are
-        dropped so that the captured step packs them itself, then everything else is refreshed eagerly."""
-        if getattr(self, "_packed_t", None) is not None:
-            for k in [k for k in self._packed_t if k not in self._packed_t_planned]:
-                del self._packed_t[k]
-        self.refresh_packs()
+    def _build_packs(self, ps):
+        """The bf16 MFMA weight fragments of the fp32 master parameters (dxmi_hip.packs.WeightPacks)."""
+        pk = ps.entries
+        ps.pack("dense0", self.temb.dense[0].weight)
+        ps.pack("dense1", self.temb.dense[1].weight)
+        blocks = list(self._resblocks())
+        # every temb_proj of the net in ONE [sum(Cout), temb_ch] operator (reference :123)
+        ps.pack("tproj", ps.stage_cat([b.temb_proj.weight for b in blocks]))
+        pk["tproj_bias"] = ps.stage_cat([b.temb_proj.bias for b in blocks])
+        off = 0
+        for b in blocks:
+            pk[id(b), "toff"] = off
+            off += b.out_channels
+            ps.pack((id(b), "conv1"), b.conv1.weight)
+            ps.pack((id(b), "conv2"), b.conv2.weight)
+            if b.in_channels != b.out_channels:
+                sc = b.conv_shortcut if b.use_conv_shortcut else b.nin_shortcut
+                ps.pack((id(b), "short"), sc.weight)
+        for m in self.modules():
+            if isinstance(m, AttnBlock):
+                ps.pack((id(m), "qkv"), ps.stage_cat([m.q.weight, m.k.weight, m.v.weight]))
+                pk[id(m), "qkv_bias"] = ps.stage_cat([m.q.bias, m.k.bias, m.v.bias])
+                ps.pack((id(m), "proj"), m.proj_out.weight)
+                if m.in_channels == 256:      # the 16x16 blocks: proj_out fused behind the attention (ops.attention_proj)
+                    ps.derived((id(m), "proj_attn"), lambda out, m=m: ops.pack_attn_proj_weight(m.proj_out.weight, out=out))
+                    # ... and the whole block as one launch (round 5: ops.attn_block, folded Wk^T Wq / Wproj Wv)
+                    ps.derived((id(m), "block"), lambda out, m=m: ops.attn_block_pack(
+                        m.q.weight, m.q.bias, m.k.weight, m.v.weight, m.v.bias, m.proj_out.weight, m.proj_out.bias,
+                        float(int(m.in_channels) ** (-0.5)), out=out))
+            elif isinstance(m, (Upsample, Downsample)):
+                ps.pack((id(m), "conv"), m.conv.weight)
+        ps.pack("conv_in", self.conv_in.weight, k27=(self.in_channels == 3))
+        ps.pack("conv_out", self.conv_out.weight)
 
     # ------------------------------------------------------------------ fused blocks
     # Activations on maps of >= STREAM_GN_MIN_HW pixels travel as (tensor, BlockStats): the producing conv's epilogue writes the

@@ -20,38 +20,33 @@ import torch.nn.functional as F
 
 from dxmi_hip import graph as _graph
 from dxmi_hip import ops
+from dxmi_hip.packs import WeightPacks
+
+
+def _build_packs_t(net, ps):
+    """Transpose-flipped fragments of every conv."""
+    from .unet_small import AttnBlock, Downsample, Upsample
+    for b in net._resblocks():
+        ps.pack((id(b), "conv1"), b.conv1.weight, transpose_flip=True)
+        ps.pack((id(b), "conv2"), b.conv2.weight, transpose_flip=True)
+        if b.in_channels != b.out_channels:
+            sc = b.conv_shortcut if b.use_conv_shortcut else b.nin_shortcut
+            ps.entries[id(b), "short"] = sc.weight  # split per concat source at use time
+    for m in net.modules():
+        if isinstance(m, AttnBlock):
+            ps.pack((id(m), "qkv"), ps.stage_cat([m.q.weight, m.k.weight, m.v.weight]), transpose_flip=True)
+            ps.pack((id(m), "proj"), m.proj_out.weight, transpose_flip=True)
+        elif isinstance(m, (Upsample, Downsample)):
+            ps.pack((id(m), "conv"), m.conv.weight, transpose_flip=True)
+    w = net.conv_out.weight
+    ps.pack("conv_out", ps.stage((64,) + tuple(w.shape[1:]), lambda out: out[: w.shape[0]].copy_(w.detach()), zero=True), transpose_flip=True)
 
 
 def _pack_t(net):
-    """Transpose-flipped fragments of every conv (cached on the net, refreshed with the parameters)."""
-    key = net._param_key()
-    if getattr(net, "_packed_t", None) is not None and net._packed_t_key == key:
-        return net._packed_t
-    from .unet_small import AttnBlock, Downsample, Upsample
-    pk = {}
-    # parameters updated in place: the previous set's buffers are rewritten (addresses held by a captured hipGraph stay valid)
-    reuse = net._pack_t_bufs if (getattr(net, "_packed_t", None) is not None and net._same_storage(key, net._packed_t_key)) else None
-    with ops.pack_batch(reuse=reuse) as pb:            # a few multi-tensor launches instead of one per layer
-        for b in net._resblocks():
-            pk[id(b), "conv1"] = ops.pack_conv_weight(b.conv1.weight, transpose_flip=True)
-            pk[id(b), "conv2"] = ops.pack_conv_weight(b.conv2.weight, transpose_flip=True)
-            if b.in_channels != b.out_channels:
-                sc = b.conv_shortcut if b.use_conv_shortcut else b.nin_shortcut
-                pk[id(b), "short"] = sc.weight  # split per concat source at use time
-        for m in net.modules():
-            if isinstance(m, AttnBlock):
-                pk[id(m), "qkv"] = ops.pack_conv_weight(torch.cat([m.q.weight, m.k.weight, m.v.weight], 0), transpose_flip=True)
-                pk[id(m), "proj"] = ops.pack_conv_weight(m.proj_out.weight, transpose_flip=True)
-            elif isinstance(m, (Upsample, Downsample)):
-                pk[id(m), "conv"] = ops.pack_conv_weight(m.conv.weight, transpose_flip=True)
-        w = net.conv_out.weight
-        wpad = torch.zeros((64,) + tuple(w.shape[1:]), dtype=torch.float32, device=w.device)
-        wpad[: w.shape[0]] = w.detach()
-        pk["conv_out"] = ops.pack_conv_weight(wpad, transpose_flip=True)
-    net._pack_t_bufs = pb.buffers
-    net._packed_t_planned = set(pk.keys())       # everything else is packed on demand by a backward and dropped at the next re-pack
-    net._packed_t, net._packed_t_key = pk, key
-    return pk
+    """The transposed set of the net (dxmi_hip.packs.WeightPacks: cached on the net, refreshed with the parameters)."""
+    if net._packs_t is None:
+        net._packs_t = WeightPacks(net, _build_packs_t)
+    return net._packs_t.get()
 
 
 class _UNetFn(torch.autograd.Function):
@@ -185,10 +180,9 @@ class _UNetFn(torch.autograd.Function):
                 C0 = x0.shape[3]
                 w = pkt[id(b), "short"]
                 # transposed fragments of the shortcut, split per concat source; cached with the other packs
-                if (id(b), "short_t", C0) not in pkt:
-                    pkt[id(b), "short_t", C0] = (ops.pack_conv_weight(w[:, :C0].contiguous(), transpose_flip=True),
-                                                 ops.pack_conv_weight(w[:, C0:].contiguous(), transpose_flip=True) if x1 is not None else None)
-                w0t, w1t = pkt[id(b), "short_t", C0]
+                w0t, w1t = net._packs_t.on_demand((id(b), "short_t", C0), lambda: (
+                    ops.pack_conv_weight(w[:, :C0].contiguous(), transpose_flip=True),
+                    ops.pack_conv_weight(w[:, C0:].contiguous(), transpose_flip=True) if x1 is not None else None))
                 d_x0 = ops.conv2d(g, w0t, residual=dxg0)
                 d_x1 = None
                 if x1 is not None:
@@ -259,9 +253,8 @@ class _UNetFn(torch.autograd.Function):
         grads[net.conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
         dx = None
         if ctx.needs_input_grad[1]:
-            if "conv_in_t" not in pkt:
-                pkt["conv_in_t"] = ops.pack_conv_weight(net.conv_in.weight, transpose_flip=True)
-            dx = ops.conv2d(g, pkt["conv_in_t"], out_nchw_f32=True)
+            conv_in_t = net._packs_t.on_demand("conv_in_t", lambda: ops.pack_conv_weight(net.conv_in.weight, transpose_flip=True))
+            dx = ops.conv2d(g, conv_in_t, out_nchw_f32=True)
 
         # ---- temb MLP + all temb_proj layers (reference unet_small.py:296-299, :123): dense backward on the HIP kernels
         # (ops.linear_bwd: transposed-pack linear for dx, the 1x1 weight-gradient kernel for dW), pre-activations recomputed
@@ -271,17 +264,17 @@ class _UNetFn(torch.autograd.Function):
         a0 = F.silu(e0)
         e1 = ops.linear(a0, pk["dense1"], d1.bias)
         s_t = F.silu(e1)
-        if "tproj_t" not in pkt:
-            pkt["tproj_t"] = ops.pack_conv_weight(torch.cat([b.temb_proj.weight for b in blocks], 0), transpose_flip=True)
-            pkt["dense1_t"] = ops.pack_conv_weight(d1.weight, transpose_flip=True)
-        ds, dw_cat, db_cat = ops.linear_bwd(s_t, d_tp, pkt["tproj_t"])
+        tproj_t = net._packs_t.on_demand("tproj_t", lambda: ops.pack_conv_weight(torch.cat([b.temb_proj.weight for b in blocks], 0),
+                                                                                 transpose_flip=True))
+        dense1_t = net._packs_t.on_demand("dense1_t", lambda: ops.pack_conv_weight(d1.weight, transpose_flip=True))
+        ds, dw_cat, db_cat = ops.linear_bwd(s_t, d_tp, tproj_t)
         off = 0
         for b in blocks:
             grads[b.temb_proj.weight] = dw_cat[off:off + b.out_channels]
             grads[b.temb_proj.bias] = db_cat[off:off + b.out_channels]
             off += b.out_channels
         de1 = ops.silu_bwd(e1, ds)
-        da0, grads[d1.weight], grads[d1.bias] = ops.linear_bwd(a0, de1, pkt["dense1_t"])
+        da0, grads[d1.weight], grads[d1.bias] = ops.linear_bwd(a0, de1, dense1_t)
         de0 = ops.silu_bwd(e0, da0)
         _, grads[d0.weight], grads[d0.bias] = ops.linear_bwd(ctx.emb, de0, None, need_dx=False)
 

@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
+from dxmi_hip.packs import PackedWeights, WeightPacks
 from .nn import conv_nd, linear, normalization, zero_module
 
 
@@ -98,7 +99,7 @@ class AttentionBlock(nn.Module):
         self.proj_out = zero_module(conv_nd(dims, channels, channels, 1))
 
 
-class UNetModel(nn.Module):
+class UNetModel(PackedWeights, nn.Module):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None, use_checkpoint=False,
                  use_fp16=False, num_heads=1, num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=False,
@@ -158,8 +159,7 @@ class UNetModel(nn.Module):
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(normalization(ch), nn.SiLU(), zero_module(conv_nd(dims, input_ch, out_channels, 3, padding=1)))
-        self._packed, self._packed_key = None, None
-        self._pack_plan, self._fp32_params = None, False
+        self._packs = WeightPacks(self, UNetModel._build_packs)
 
     def convert_to_fp16(self):
         """Accepted for script compatibility (generate_large.py:129-130): activations are bf16 in the HIP
@@ -169,75 +169,32 @@ class UNetModel(nn.Module):
         pass
 
     # ------------------------------------------------------------------ weight fragments
-    def _param_key(self):
-        return tuple((p.data_ptr(), p._version) for p in ops.fast_parameters(self))
-
-    def _pack(self):
-        with ops.pack_batch() as pb:      # every pack below runs in a few multi-tensor launches
-            pk = {"te0": ops.pack_conv_weight(self.time_embed[0].weight), "te2": ops.pack_conv_weight(self.time_embed[2].weight)}
-            blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
-            # the concatenated emb_layers operands live in buffers of their own, refreshed in place by _repack()
-            self._emb_w_cat = torch.cat([b.emb_layers[1].weight.detach() for b in blocks], 0).float().contiguous()
-            pk["emb_w"] = ops.pack_conv_weight(self._emb_w_cat)
-            pk["emb_b"] = torch.cat([b.emb_layers[1].bias.detach() for b in blocks], 0).float().contiguous()
-            self._emb_blocks = blocks
-            off = 0
-            for b in blocks:
-                pk[id(b), "eoff"] = off
-                off += b.emb_layers[1].out_features
-                pk[id(b), "conv1"] = ops.pack_conv_weight(b.in_layers[2].weight)
-                pk[id(b), "conv2"] = ops.pack_conv_weight(b.out_layers[3].weight)
-                if not isinstance(b.skip_connection, nn.Identity):
-                    pk[id(b), "skip"] = ops.pack_conv_weight(b.skip_connection.weight)
-            for m in self.modules():
-                if isinstance(m, AttentionBlock):
-                    pk[id(m), "qkv"] = ops.pack_conv_weight(m.qkv.weight.reshape(3 * m.channels, m.channels, 1, 1))
-                    pk[id(m), "proj"] = ops.pack_conv_weight(m.proj_out.weight.reshape(m.channels, m.channels, 1, 1))
-                elif isinstance(m, Upsample) and m.use_conv:
-                    pk[id(m), "conv"] = ops.pack_conv_weight(m.conv.weight)
-                elif isinstance(m, Downsample) and m.use_conv:
-                    pk[id(m), "conv"] = ops.pack_conv_weight(m.op.weight)
-            conv_in = self.input_blocks[0][0]
-            pk["conv_in"] = ops.pack_conv_weight(conv_in.weight, k27=(self.in_channels == 3))
-            pk["conv_out"] = ops.pack_conv_weight(self.out[2].weight)
-        self._pack_plan = pb.plan
-        return pk
-
-    def _repack(self):
-        """Parameters updated in place (an optimiser step: same addresses, new versions): the same sources into the same fragment
-        buffers, one call (ops.PackPlan)."""
-        torch.cat([b.emb_layers[1].weight.detach() for b in self._emb_blocks], 0, out=self._emb_w_cat)
-        torch.cat([b.emb_layers[1].bias.detach() for b in self._emb_blocks], 0, out=self._packed["emb_b"])
-        self._pack_plan.replay()
-
-    def packed(self):
-        key = self._param_key()
-        if self._packed is None or key != self._packed_key:
-            moved = self._packed is None or getattr(self, "_pack_plan", None) is None or \
-                len(key) != len(self._packed_key) or any(a[0] != b[0] for a, b in zip(key, self._packed_key))
-            if moved or not self._fp32_params or not ops.PACK_PLAN_REPLAY:
-                self._packed = self._pack()
-                self._fp32_params = all(p.dtype == torch.float32 and p.is_contiguous() for p in ops.fast_parameters(self))
-            else:
-                self._repack()
-            self._packed_key = key
-        return self._packed
-
-    def refresh_packs(self):
-        """Bring every packed-weight set of the net that exists up to date with the parameters (no-op when they are)."""
-        self.packed()
-        if getattr(self, "_packed_t", None) is not None:
-            from .unet_train import _pack_t
-            _pack_t(self)
-
-    def prepare_capture(self):
-        """Before a StepGraph capture (dxmi_hip/graph.py): entries of the transposed set that a backward packs on demand are dropped
-        so that the captured step packs them itself; the planned sets are refreshed eagerly (in place: ops.PackPlan)."""
-        pkt = getattr(self, "_packed_t", None)
-        if pkt is not None:
-            for k in [k for k in pkt if k not in self._pack_t_planned]:
-                del pkt[k]
-        self.refresh_packs()
+    def _build_packs(self, ps):
+        """The bf16 MFMA weight fragments of the fp32 master parameters (dxmi_hip.packs.WeightPacks)."""
+        pk = ps.entries
+        ps.pack("te0", self.time_embed[0].weight)
+        ps.pack("te2", self.time_embed[2].weight)
+        blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
+        ps.pack("emb_w", ps.stage_cat([b.emb_layers[1].weight for b in blocks]))       # every emb_layers Linear as one operator
+        pk["emb_b"] = ps.stage_cat([b.emb_layers[1].bias for b in blocks])
+        off = 0
+        for b in blocks:
+            pk[id(b), "eoff"] = off
+            off += b.emb_layers[1].out_features
+            ps.pack((id(b), "conv1"), b.in_layers[2].weight)
+            ps.pack((id(b), "conv2"), b.out_layers[3].weight)
+            if not isinstance(b.skip_connection, nn.Identity):
+                ps.pack((id(b), "skip"), b.skip_connection.weight)
+        for m in self.modules():
+            if isinstance(m, AttentionBlock):
+                ps.pack((id(m), "qkv"), m.qkv.weight.reshape(3 * m.channels, m.channels, 1, 1))
+                ps.pack((id(m), "proj"), m.proj_out.weight.reshape(m.channels, m.channels, 1, 1))
+            elif isinstance(m, Upsample) and m.use_conv:
+                ps.pack((id(m), "conv"), m.conv.weight)
+            elif isinstance(m, Downsample) and m.use_conv:
+                ps.pack((id(m), "conv"), m.op.weight)
+        ps.pack("conv_in", self.input_blocks[0][0].weight, k27=(self.in_channels == 3))
+        ps.pack("conv_out", self.out[2].weight)
 
     # ------------------------------------------------------------------ fused blocks
     # Activations on maps of >= STREAM_GN_MIN_HW pixels travel as (tensor, BlockStats): the conv that produces a tensor writes

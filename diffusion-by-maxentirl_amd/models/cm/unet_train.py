@@ -27,51 +27,35 @@ import torch.nn.functional as F
 
 from dxmi_hip import graph as _graph
 from dxmi_hip import ops
+from dxmi_hip.packs import WeightPacks
+
+
+def _build_packs_t(net, ps):
+    """Transpose-flipped fragments of every conv, and of the two dense operators the embedding backward differentiates through."""
+    from .unet import AttentionBlock, Downsample, ResBlock, Upsample
+    for m in net.modules():
+        if isinstance(m, ResBlock):
+            ps.pack((id(m), "conv1"), m.in_layers[2].weight, transpose_flip=True)
+            ps.pack((id(m), "conv2"), m.out_layers[3].weight, transpose_flip=True)
+        elif isinstance(m, AttentionBlock):
+            C = m.channels
+            ps.pack((id(m), "qkv"), m.qkv.weight.reshape(3 * C, C, 1, 1), transpose_flip=True)
+            ps.pack((id(m), "proj"), m.proj_out.weight.reshape(C, C, 1, 1), transpose_flip=True)
+        elif isinstance(m, Upsample) and m.use_conv:
+            ps.pack((id(m), "conv"), m.conv.weight, transpose_flip=True)
+        elif isinstance(m, Downsample) and m.use_conv:
+            ps.pack((id(m), "conv"), m.op.weight, transpose_flip=True)
+    w = net.out[2].weight
+    ps.pack("conv_out", ps.stage((64,) + tuple(w.shape[1:]), lambda out: out[: w.shape[0]].copy_(w.detach()), zero=True), transpose_flip=True)
+    ps.pack("emb_t", ps.stage_cat([m.emb_layers[1].weight for m in net.modules() if isinstance(m, ResBlock)]), transpose_flip=True)
+    ps.pack("te2_t", net.time_embed[2].weight, transpose_flip=True)
 
 
 def _pack_t(net):
-    key = net._param_key()
-    if getattr(net, "_packed_t", None) is not None and net._packed_t_key == key:
-        return net._packed_t
-    from .unet import AttentionBlock, Downsample, ResBlock, Upsample
-    old = getattr(net, "_packed_t", None)
-    if ops.PACK_PLAN_REPLAY and old is not None and getattr(net, "_pack_t_plan", None) is not None and net._fp32_params and len(key) == len(net._packed_t_key) \
-            and all(a[0] == b[0] for a, b in zip(key, net._packed_t_key)):
-        # parameters updated in place: the same sources into the same buffers (ops.PackPlan); the padded conv_out source and the
-        # concatenated emb_layers operand are refreshed in place first
-        w = net.out[2].weight
-        net._wpad_t[: w.shape[0]] = w.detach()
-        if "emb_t" in old:
-            torch.cat([b.emb_layers[1].weight.detach() for b in net._emb_blocks], 0, out=net._emb_w_cat_t)
-            net._pack_t_plan2.replay()
-        net._pack_t_plan.replay()
-        for k in [k for k in old if k not in net._pack_t_planned]:
-            del old[k]                      # packed on demand by the backward (conv_in_t, the per-source skip_t pairs): stale now
-        net._packed_t_key = key
-        return old
-    pk = {}
-    with ops.pack_batch() as pb:      # a few multi-tensor launches instead of one per layer
-        for m in net.modules():
-            if isinstance(m, ResBlock):
-                pk[id(m), "conv1"] = ops.pack_conv_weight(m.in_layers[2].weight, transpose_flip=True)
-                pk[id(m), "conv2"] = ops.pack_conv_weight(m.out_layers[3].weight, transpose_flip=True)
-            elif isinstance(m, AttentionBlock):
-                C = m.channels
-                pk[id(m), "qkv"] = ops.pack_conv_weight(m.qkv.weight.reshape(3 * C, C, 1, 1), transpose_flip=True)
-                pk[id(m), "proj"] = ops.pack_conv_weight(m.proj_out.weight.reshape(C, C, 1, 1), transpose_flip=True)
-            elif isinstance(m, Upsample) and m.use_conv:
-                pk[id(m), "conv"] = ops.pack_conv_weight(m.conv.weight, transpose_flip=True)
-            elif isinstance(m, Downsample) and m.use_conv:
-                pk[id(m), "conv"] = ops.pack_conv_weight(m.op.weight, transpose_flip=True)
-        w = net.out[2].weight
-        wpad = torch.zeros((64,) + tuple(w.shape[1:]), dtype=torch.float32, device=w.device)
-        wpad[: w.shape[0]] = w.detach()
-        net._wpad_t = wpad
-        pk["conv_out"] = ops.pack_conv_weight(wpad, transpose_flip=True)
-    net._pack_t_plan, net._pack_t_plan2 = pb.plan, None
-    net._pack_t_planned = set(pk.keys()) | {"emb_t", "te2_t"}      # what the two plans refresh
-    net._packed_t, net._packed_t_key = pk, key
-    return pk
+    """The transposed set of the net (dxmi_hip.packs.WeightPacks: cached on the net, refreshed with the parameters)."""
+    if net._packs_t is None:
+        net._packs_t = WeightPacks(net, _build_packs_t)
+    return net._packs_t.get()
 
 
 # Training forward: GroupNorm on the producers' block statistics (streaming apply) where the inference path uses them; 0 = the generic
@@ -290,10 +274,9 @@ class _EDMUNetFn(torch.autograd.Function):
                 dxg0, dxg1, _ = gn_bwd(gn1, x0, d_a1, in1=x1, fwd_stats=s1)
                 C0 = x0.shape[3]
                 w = sk.weight
-                if (id(b), "skip_t", C0) not in pkt:     # transposed fragments per concat source, cached with the other packs
-                    pkt[id(b), "skip_t", C0] = (ops.pack_conv_weight(w[:, :C0].contiguous(), transpose_flip=True),
-                                                ops.pack_conv_weight(w[:, C0:].contiguous(), transpose_flip=True) if x1 is not None else None)
-                w0t, w1t = pkt[id(b), "skip_t", C0]
+                w0t, w1t = net._packs_t.on_demand((id(b), "skip_t", C0), lambda: (      # transposed fragments per concat source
+                    ops.pack_conv_weight(w[:, :C0].contiguous(), transpose_flip=True),
+                    ops.pack_conv_weight(w[:, C0:].contiguous(), transpose_flip=True) if x1 is not None else None))
                 d_x0 = ops.conv2d(g, w0t, residual=dxg0)
                 d_x1 = None
                 if x1 is not None:
@@ -357,9 +340,8 @@ class _EDMUNetFn(torch.autograd.Function):
         grads[conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
         dx = None
         if ctx.needs_input_grad[1]:
-            if "conv_in_t" not in pkt:
-                pkt["conv_in_t"] = ops.pack_conv_weight(conv_in.weight, transpose_flip=True)
-            dx = ops.conv2d(g, pkt["conv_in_t"], out_nchw_f32=True)
+            conv_in_t = net._packs_t.on_demand("conv_in_t", lambda: ops.pack_conv_weight(conv_in.weight, transpose_flip=True))
+            dx = ops.conv2d(g, conv_in_t, out_nchw_f32=True)
 
         # ---- embedding graph (models/cm/unet.py:775-779, :249): time_embed MLP, label embedding, every emb_layers Linear as one
         # operator — dense backward on the HIP kernels (ops.linear_bwd), pre-activations recomputed
@@ -371,12 +353,6 @@ class _EDMUNetFn(torch.autograd.Function):
         if net.num_classes is not None:
             emb = emb + net.label_emb.weight.detach()[ctx.y]
         s_e = F.silu(emb)
-        if "emb_t" not in pkt:
-            with ops.pack_batch() as pb2:
-                net._emb_w_cat_t = torch.cat([b.emb_layers[1].weight.detach() for b in blocks], 0).float().contiguous()
-                pkt["emb_t"] = ops.pack_conv_weight(net._emb_w_cat_t, transpose_flip=True)
-                pkt["te2_t"] = ops.pack_conv_weight(l2.weight, transpose_flip=True)
-            net._pack_t_plan2 = pb2.plan
         ds, dw_cat, db_cat = ops.linear_bwd(s_e, d_emb_all, pkt["emb_t"])
         off = 0
         for b in blocks:

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
+from dxmi_hip.packs import PackedWeights, WeightPacks
 
 
 def process_single_t(x, t):
@@ -52,7 +53,22 @@ class ResBlockV2(nn.Module):
         self.downsample = downsample
 
 
-class IGEBMEncoderV2(nn.Module):
+def _build_packs(net, ps, **kw):
+    """bf16 weight fragments of the convs (kw transpose_flip=True: of their data-gradient operators)."""
+    if not kw:
+        ps.pack("conv1", net.conv1.weight, k27=(net.in_chan == 3))
+    for i, b in enumerate(net.blocks):
+        ps.pack((i, "conv1"), b.conv1.weight, **kw)
+        ps.pack((i, "conv2"), b.conv2.weight, **kw)
+        if b.skip is not None:
+            ps.pack((i, "skip"), b.skip[0].weight, **kw)
+
+
+def _build_packs_t(net, ps):
+    _build_packs(net, ps, transpose_flip=True)
+
+
+class IGEBMEncoderV2(PackedWeights, nn.Module):
     def __init__(self, in_chan=3, out_chan=1, n_class=None, use_spectral_norm=False, keepdim=True,
                  out_activation="linear", avg_pool_dim=1, learn_out_scale=False, nh=128):
         super().__init__()
@@ -76,53 +92,11 @@ class IGEBMEncoderV2(nn.Module):
         self.learn_out_scale = learn_out_scale
         if learn_out_scale:
             self.out_scale = nn.Linear(1, 1, bias=True)
-        self._packed, self._packed_key, self._pack_bufs = None, None, None
-        self._packed_t, self._packed_t_key, self._pack_t_bufs = None, None, None
-
-    # ---- bf16 weight fragments, rebuilt when a parameter's version changes
-    def packed(self):
-        key = tuple((p.data_ptr(), p._version) for p in ops.fast_parameters(self))
-        if self._packed is None or key != self._packed_key:
-            # parameters updated in place: the same buffers are rewritten (addresses held by a captured hipGraph stay valid)
-            reuse = self._pack_bufs if (self._packed is not None and self._same_storage(key, self._packed_key)) else None
-            with ops.pack_batch(reuse=reuse) as pb:             # one multi-tensor launch for the net's weights
-                pk = {"conv1": ops.pack_conv_weight(self.conv1.weight, k27=(self.in_chan == 3))}
-                for i, b in enumerate(self.blocks):
-                    pk[i, "conv1"] = ops.pack_conv_weight(b.conv1.weight)
-                    pk[i, "conv2"] = ops.pack_conv_weight(b.conv2.weight)
-                    if b.skip is not None:
-                        pk[i, "skip"] = ops.pack_conv_weight(b.skip[0].weight)
-            self._packed, self._packed_key, self._pack_bufs = pk, key, pb.buffers
-        return self._packed
-
-    @staticmethod
-    def _same_storage(key, old_key):
-        return old_key is not None and len(key) == len(old_key) and all(a[0] == b[0] for a, b in zip(key, old_key))
-
-    def refresh_packs(self):
-        """Bring the packed-weight sets that exist up to date with the parameters (no-op when they are)."""
-        self.packed()
-        if self._packed_t is not None:
-            self.packed_transposed()
-
-    def prepare_capture(self):
-        """Before a StepGraph capture (dxmi_hip/graph.py)."""
-        self.refresh_packs()
+        self._packs, self._packs_t = WeightPacks(self, _build_packs), WeightPacks(self, _build_packs_t)
 
     def packed_transposed(self):
         """Transpose-flipped fragments: the data-gradient operators of the block convs."""
-        key = tuple((p.data_ptr(), p._version) for p in ops.fast_parameters(self))
-        if self._packed_t is None or key != self._packed_t_key:
-            pk = {}
-            reuse = self._pack_t_bufs if (self._packed_t is not None and self._same_storage(key, self._packed_t_key)) else None
-            with ops.pack_batch(reuse=reuse) as pb:
-                for i, b in enumerate(self.blocks):
-                    pk[i, "conv1"] = ops.pack_conv_weight(b.conv1.weight, transpose_flip=True)
-                    pk[i, "conv2"] = ops.pack_conv_weight(b.conv2.weight, transpose_flip=True)
-                    if b.skip is not None:
-                        pk[i, "skip"] = ops.pack_conv_weight(b.skip[0].weight, transpose_flip=True)
-            self._packed_t, self._packed_t_key, self._pack_t_bufs = pk, key, pb.buffers
-        return self._packed_t
+        return self._packs_t.get()
 
     def train(self, mode=True):
         """The trainers switch the value net between eval() and train() around every TD target (reference trainer.py:288-295), 24

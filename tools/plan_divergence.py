@@ -149,9 +149,9 @@ def compare_packs():
     for p in unet.parameters():
         p.data.add_(0)
     a = snap()
-    print("replayed:", unet._pack_plan is not None, "fp32_params", unet._fp32_params)
-    unet._pack_plan = unet._pack_t_plan = None
-    unet._packed = unet._packed_t = None
+    print("replayable:", [ps.plan is not None and ps.direct for ps in (unet._packs, unet._packs_t)])
+    unet._packs.forget()
+    unet._packs_t.forget()
     b = snap()
     bad = [k for k in b if not torch.equal(a[k], b[k])]
     print("pack entries", len(b), "differing", len(bad), bad[:10])
