@@ -1,4 +1,5 @@
-"""Train a consistency model on the HIP U-Net: distillation from an EDM teacher, or consistency training without one
+"""Train a consistency model on the HIP U-Net: distillation from an EDM teacher, consistency training without one, or progressive
+distillation of the teacher
 (models.cm.train_util.CMTrainLoop over KarrasDenoiser.consistency_losses; reference: the consistency_models training entry point
 over models/cm/script_util.py cm_train_defaults + model_and_diffusion_defaults).
 
@@ -12,7 +13,12 @@ from the teacher's weights, the teacher's diffusion has distillation=False and t
 checkpoints it writes are what `generate_large.py --cm_sampler onestep --pretrained ...` reads.  Image folders are not read by
 this package: --data_npz PATH trains on a uint8 image array file (dxmi_hip/data.py ImageStore, normalised as the reference's
 image_datasets.py does; --data_resident auto|device|host), --synthetic_data True draws uniform images and labels; the two exclude
-each other and one of them is required.  CMTrainLoop.run_loop keeps the reference's condition, which
+each other and one of them is required.  --training_mode progdist is progressive distillation (KarrasDenoiser.progdist_losses):
+the student keeps distillation=False and starts from the teacher (--teacher_model_path), there is no target network, the schedule is
+the reference's ("fixed", "progdist") pair (--start_scales halved every --distill_steps_per_iter steps; --scale_mode is set to progdist
+unless given otherwise), a phase anneals the learning rate over --lr_anneal_steps (default: --distill_steps_per_iter) steps, and
+--max_iters only bounds total_training_steps; its model%06d.pt is what `generate_large.py --karras_sampler progdist --pretrained ...`
+reads.  CMTrainLoop.run_loop keeps the reference's condition, which
 ends only when both lr_anneal_steps and total_training_steps are reached: --max_iters N (smoke runs) sets both to N, so the
 learning rate anneals to zero over those N steps.  --loss_norm lpips needs the VGG16 and LPIPS linear weight files:
 --lpips_vgg16 PATH --lpips_lin PATH, or DXMI_LPIPS_VGG16 / DXMI_LPIPS_LIN in the environment; without them it is refused.
@@ -69,6 +75,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")
+    if args.training_mode == "progdist" and args.scale_mode == "fixed":
+        args.scale_mode = "progdist"       # the reference's pair for this mode: target_ema_mode fixed, scale_mode progdist
     if args.data_resident not in ("auto", "device", "host"):
         ap.error(f"--data_resident {args.data_resident!r}: auto, device or host")
     return args
@@ -90,12 +98,13 @@ def main():
     data, store = make_loader(args, device, local_rank, world)
     if store is not None:
         print0(store.describe())
-    distill = args.training_mode == "consistency_distillation"
-    if args.training_mode not in ("consistency_distillation", "consistency_training"):
-        raise NotImplementedError(f"training_mode {args.training_mode!r}: consistency_distillation or consistency_training")
+    progdist = args.training_mode == "progdist"
+    distill = args.training_mode == "consistency_distillation" or progdist      # the modes with a teacher
+    if args.training_mode not in ("consistency_distillation", "consistency_training", "progdist"):
+        raise NotImplementedError(f"training_mode {args.training_mode!r}: consistency_distillation, consistency_training or progdist")
 
     model_kw = args_to_dict(args, model_and_diffusion_defaults().keys())
-    model, diffusion = create_model_and_diffusion(distillation=True, **model_kw)
+    model, diffusion = create_model_and_diffusion(distillation=not progdist, **model_kw)     # a progdist student keeps EDM scalings
     diffusion.loss_norm = args.loss_norm
     if args.loss_norm == "lpips":      # refused here, before the target and the teacher are built, when no weights were named
         from models.cm.karras_diffusion import _NO_LPIPS
@@ -104,7 +113,7 @@ def main():
         if not vgg or not lin:
             raise NotImplementedError(_NO_LPIPS)
         diffusion.lpips_loss = LPIPS.from_files(vgg, lin)
-    target_model, _ = create_model_and_diffusion(distillation=True, **model_kw)
+    target_model = None if progdist else create_model_and_diffusion(distillation=True, **model_kw)[0]
     teacher_model = teacher_diffusion = None
     if distill:
         teacher_model, teacher_diffusion = create_model_and_diffusion(distillation=False, **dict(model_kw, dropout=args.teacher_dropout))
@@ -115,21 +124,25 @@ def main():
             print0("no --teacher_model_path: the teacher keeps its random initialisation (smoke runs)")
         model.load_state_dict(teacher_model.state_dict())      # student and target start from the teacher
         teacher_model.to(device).eval()
-    target_model.load_state_dict(model.state_dict())
     model.to(device).train()
-    target_model.to(device).train()
+    if target_model is not None:
+        target_model.load_state_dict(model.state_dict())
+        target_model.to(device).train()
 
     ema_scale_fn = create_ema_and_scales_fn(target_ema_mode=args.target_ema_mode, start_ema=args.start_ema, scale_mode=args.scale_mode,
                                             start_scales=args.start_scales, end_scales=args.end_scales,
                                             total_steps=args.total_training_steps, distill_steps_per_iter=args.distill_steps_per_iter)
     total = args.max_iters if args.max_iters else args.total_training_steps
+    lr_anneal_steps = args.lr_anneal_steps if not args.max_iters else args.max_iters
+    if progdist:       # the loop's phase arithmetic takes lr_anneal_steps for the length of a phase (doubled for num_scales 2 and 1)
+        lr_anneal_steps = args.lr_anneal_steps or args.distill_steps_per_iter
     loop = CMTrainLoop(model=model, target_model=target_model, teacher_model=teacher_model, teacher_diffusion=teacher_diffusion,
                        training_mode=args.training_mode, ema_scale_fn=ema_scale_fn, total_training_steps=total, diffusion=diffusion,
                        data=data,
                        batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr, ema_rate=args.ema_rate,
                        log_interval=args.log_interval, save_interval=args.save_interval, resume_checkpoint=args.resume_checkpoint,
                        use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth, weight_decay=args.weight_decay,
-                       lr_anneal_steps=args.lr_anneal_steps if not args.max_iters else args.max_iters, log_dir=args.log_dir,
+                       lr_anneal_steps=lr_anneal_steps, log_dir=args.log_dir,
                        use_graph=args.use_graph and _graph.default_enabled())
     print0(f"{args.training_mode}: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
            f"{total} steps, loss_norm {args.loss_norm}")

@@ -134,6 +134,10 @@ SIGNATURES = {
     "dxmi_cd_solver": (c_int, [c_int] + [c_void_p] * 7 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_int, c_float, c_void_p]),
     "dxmi_cd_loss_fwd": (c_int, [c_void_p] * 6 + [c_int, c_void_p] + [c_int] * 5 + [c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_cd_loss_bwd": (c_int, [c_void_p] * 7 + [c_int, c_void_p] + [c_int] * 5 + [c_float, c_float, c_int, c_int, c_void_p]),
+    "dxmi_pd_solver": (c_int, [c_int] + [c_void_p] * 5 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_int, c_float, c_void_p]),
+    "dxmi_pd_loss_fwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p] + [c_int] * 3 + [c_float, c_float, c_int, c_int, c_void_p]),
+    "dxmi_pd_loss_bwd": (c_int, [c_void_p] * 6 + [c_int, c_void_p] + [c_int] * 3 + [c_float, c_float, c_int, c_int, c_void_p]),
+    "dxmi_pd_lpips_images": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_karras_stage": (c_int, [c_int, c_int, c_void_p, c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
     "dxmi_cm_stage": (c_int, [c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 10 + [c_int] * 4 + [c_void_p]),
     "dxmi_quantize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -181,3 +181,19 @@ def cd_lpips_bwd(g_loss, d_x01, indices, t_table, weight_schedule, sigma_data=0.
     check(load().dxmi_cd_lpips_bwd(_ptr(g_loss), _ptr(d_x01), _ptr(indices), _ptr(t_table), S, _ptr(d), N, CHW, float(sigma_data),
                                    float(sigma_min), int(bool(distillation)), sched, _stream()), "dxmi_cd_lpips_bwd")
     return d
+
+
+def pd_lpips_images(f_online, x_t, target_x, indices, t_table, weight_schedule, sigma_data=0.5, sigma_min=0.002, distillation=False):
+    """-> (x01 fp32 [2 N, C, H, W]: (denoised + 1) / 2 then (target_x + 1) / 2, weights fp32 [N]) of progdist_losses
+    (dxmi_pd_lpips_images).  t_table: the 2 S + 1 levels of ops.pd_solver."""
+    from .ops import _pd_operands
+    sched = _dsm_schedule(weight_schedule)
+    if f_online is None or f_online.dim() != 4:
+        _err("dxmi_pd_lpips_images: [N, C, H, W] tensors are needed")
+    N, CHW, S = _pd_operands("dxmi_pd_lpips_images", f_online, indices, t_table, same=(x_t, target_x))
+    x01 = torch.empty((2 * N,) + tuple(f_online.shape[1:]), dtype=torch.float32, device=f_online.device)
+    w = torch.empty(N, dtype=torch.float32, device=f_online.device)
+    check(load().dxmi_pd_lpips_images(_ptr(f_online), _ptr(x_t), _ptr(target_x), _ptr(indices), _ptr(t_table), S, _ptr(x01), _ptr(w), N,
+                                      CHW, float(sigma_data), float(sigma_min), int(bool(distillation)), sched, _stream()),
+          "dxmi_pd_lpips_images")
+    return x01, w

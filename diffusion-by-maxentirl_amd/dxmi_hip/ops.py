@@ -1142,6 +1142,75 @@ def cd_loss_bwd(g_loss, f_online, f_target, x_t, x_t2, indices, t_table, loss_no
     return d
 
 
+# dxmi_pd_solver modes (include/dxmi_hip.h); the progdist norms are the consistency ones without l2-32 (karras_diffusion.py:311-329)
+PD_MID, PD_END = range(2)
+PD_LOSS_NORMS = {"l1": 0, "l2": 1}
+
+
+def _pd_operands(what, first, indices, t_table, same=(), per_sample=()):
+    """_cd_operands for the progressive-distillation launches: t_table holds 2 S + 1 levels (S + 1 coarse, then S half steps).
+    -> (N, CHW, S)."""
+    if t_table is None or t_table.dim() != 1 or t_table.numel() < 3 or t_table.numel() % 2 == 0:
+        raise _lib.DxmiError(f"{what}: t_table must hold 2 num_scales + 1 levels (num_scales >= 1), got "
+                             f"{None if t_table is None else tuple(t_table.shape)}")
+    N, CHW, L = _cd_operands(what, first, indices, t_table, same=same, per_sample=per_sample)
+    if CHW % 4:
+        raise _lib.DxmiError(f"{what}: the elements per sample ({CHW}) must be a multiple of 4")
+    return N, CHW, (L - 1) // 2
+
+
+def pd_solver(mode, x_t, model_out, indices, t_table, x_t2=None, sigma_data=0.5, sigma_min=0.002, distillation=False,
+              next_sigma_data=0.5):
+    """One Euler stage of progdist_losses (dxmi_pd_solver).  sigma_data / sigma_min / distillation: the diffusion whose denoise()
+    forms the denoiser (the teacher's); next_sigma_data: the diffusion of the network that reads the returned input.
+      PD_MID (model_out at (x_t, t))          -> (x_t2, the teacher's second input, its time)
+      PD_END (model_out at (x_t2, t2), x_t2)  -> target_x"""
+    if mode not in (PD_MID, PD_END):
+        raise _lib.DxmiError(f"dxmi_pd_solver: unknown mode {mode!r}")
+    if model_out is None or (mode == PD_END and x_t2 is None):
+        raise _lib.DxmiError("dxmi_pd_solver: MID needs model_out, END model_out and x_t2")
+    N, CHW, S = _pd_operands("dxmi_pd_solver", x_t, indices, t_table, same=(model_out, x_t2))
+    out = torch.empty_like(x_t)
+    x_next = t_next = None
+    if mode == PD_MID:
+        x_next, t_next = torch.empty_like(x_t), torch.empty(N, dtype=torch.float32, device=x_t.device)
+    check(load().dxmi_pd_solver(int(mode), _ptr(x_t), _ptr(x_t2), _ptr(model_out), _ptr(indices), _ptr(t_table), S, _ptr(out),
+                                _ptr(x_next), _ptr(t_next), N, CHW, float(sigma_data), float(sigma_min), int(bool(distillation)),
+                                float(next_sigma_data), _stream()), "dxmi_pd_solver")
+    return (out, x_next, t_next) if mode == PD_MID else out
+
+
+def _pd_loss_args(what, loss_norm, weight_schedule):
+    if loss_norm not in PD_LOSS_NORMS:
+        raise _lib.DxmiError(f"{what}: loss norm {loss_norm!r} is not one of {sorted(PD_LOSS_NORMS)}")
+    return PD_LOSS_NORMS[loss_norm], _dsm_schedule(weight_schedule)
+
+
+def pd_loss_fwd(f_online, x_t, target_x, indices, t_table, loss_norm, weight_schedule, sigma_data=0.5, sigma_min=0.002,
+                distillation=False):
+    """-> per-sample progdist loss mean_flat(norm(denoised - target_x)) * get_weightings(snr(t)) (dxmi_pd_loss_fwd)."""
+    norm, sched = _pd_loss_args("dxmi_pd_loss_fwd", loss_norm, weight_schedule)
+    N, CHW, S = _pd_operands("dxmi_pd_loss_fwd", f_online, indices, t_table, same=(x_t, target_x))
+    loss = torch.empty(N, dtype=torch.float32, device=f_online.device)
+    check(load().dxmi_pd_loss_fwd(_ptr(f_online), _ptr(x_t), _ptr(target_x), _ptr(indices), _ptr(t_table), S, _ptr(loss), N, CHW, norm,
+                                  float(sigma_data), float(sigma_min), int(bool(distillation)), sched, _stream()), "dxmi_pd_loss_fwd")
+    return loss
+
+
+def pd_loss_bwd(g_loss, f_online, x_t, target_x, indices, t_table, loss_norm, weight_schedule, sigma_data=0.5, sigma_min=0.002,
+                distillation=False):
+    """-> d(f_online) of the progdist loss for the device upstream gradient g_loss [N] (dxmi_pd_loss_bwd)."""
+    norm, sched = _pd_loss_args("dxmi_pd_loss_bwd", loss_norm, weight_schedule)
+    if g_loss is None:
+        raise _lib.DxmiError("dxmi_pd_loss_bwd: no upstream gradient")
+    N, CHW, S = _pd_operands("dxmi_pd_loss_bwd", f_online, indices, t_table, same=(x_t, target_x), per_sample=(g_loss,))
+    d = torch.empty_like(f_online)
+    check(load().dxmi_pd_loss_bwd(_ptr(g_loss), _ptr(f_online), _ptr(x_t), _ptr(target_x), _ptr(indices), _ptr(t_table), S, _ptr(d), N,
+                                  CHW, norm, float(sigma_data), float(sigma_min), int(bool(distillation)), sched, _stream()),
+          "dxmi_pd_loss_bwd")
+    return d
+
+
 EMA_MAX_RATES = 4
 
 

@@ -11,7 +11,8 @@ gather of uint8 images for the FID npz.  FID itself (pytorch_fid + Inception wei
 outside the accelerated path and runs only when those are present; --skip_fid writes PNGs as images are produced.
 `--synthetic NAME` builds the net of a built-in config with random weights (benchmark / smoke use).
 
-`--karras_sampler {heun,dpm,euler,ancestral}` samples the EDM teacher instead (models.cm.karras_diffusion.karras_sample,
+`--karras_sampler {heun,dpm,euler,ancestral,progdist}` samples the EDM teacher instead (progdist: a progressively distilled
+student of it, `--pretrained` a model%06d.pt of `cm_train.py --training_mode progdist`, NFE = `--karras_steps`) (models.cm.karras_diffusion.karras_sample,
 reference models/cm/karras_diffusion.py:354-420): `--karras_steps` (40), `--rho`, `--s_churn`, `--s_tmin`, `--s_tmax`,
 `--s_noise`.  Weights: `--pretrained [PATH]` loads a plain U-Net state dict (PATH, or the config's training.pretrained_path),
 otherwise `sampler.pth` from --log_dir without its `log_betas` entry.  Class-conditional nets draw one label per image.
@@ -65,7 +66,7 @@ def build_parser():
     ap.add_argument("--synthetic", type=str, default=None, help="builtin config name, e.g. imagenet64_T10 (random weights)")
     ap.add_argument("--no_graph", action="store_true", help="issue every launch from python instead of replaying the T-step loop of a "
                                                            "batch as one hipGraph (dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
-    ap.add_argument("--karras_sampler", type=str, default=None, choices=("heun", "dpm", "euler", "ancestral"),
+    ap.add_argument("--karras_sampler", type=str, default=None, choices=("heun", "dpm", "euler", "ancestral", "progdist"),
                     help="sample the EDM teacher with this Karras sampler instead of the DxMI sampler")
     ap.add_argument("--karras_steps", type=int, default=None, help="Karras sampler steps (default 40)")
     ap.add_argument("--rho", type=float, default=None, help="Karras schedule rho (default 7.0)")
@@ -292,7 +293,7 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
     consistency-distilled model through the same path, with distillation=True."""
     from dxmi_hip import graph as hip_graph
     from dxmi_hip import ops
-    from models.cm.karras_diffusion import cm_nfe, karras_nfe, karras_sample
+    from models.cm.karras_diffusion import cm_nfe, karras_nfe, karras_sample, progdist_sample
     from utils import ImageWriter
     path, kind = resolve_weights(args, cfg)
     if path is not None:
@@ -334,8 +335,12 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         if unet.num_classes is not None:        # one uniform label per image, as OpenAIDiffusion._sample draws them
             kw["y"] = (torch.randint(0, unet.num_classes, (args.batchsize,), device=device) if generator is None else
                        generator.randint(0, unet.num_classes, (args.batchsize,), device=device))
-        sample = karras_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
-                               sigma_max=diffusion.sigma_max, sampler=sampler, use_graph=use_graph, generator=generator, **extra)
+        if sampler == "progdist":               # its own entry point: karras_sample keeps refusing this sampler
+            sample = progdist_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
+                                     sigma_max=diffusion.sigma_max, rho=args.rho, use_graph=use_graph, generator=generator)
+        else:
+            sample = karras_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
+                                   sigma_max=diffusion.sigma_max, sampler=sampler, use_graph=use_graph, generator=generator, **extra)
         if args.skip_fid:
             writer.submit(sample, [os.path.join(output_path, f"{local_rank}_{i_img + k}.png") for k in range(len(sample))])
             i_img += len(sample)

@@ -7,7 +7,8 @@ sample_onestep / stochastic_iterative_sampler (:644-683) with the zero-shot edit
 iterative_inpainting / iterative_superres (:722-951), and the denoising score-matching loss training_losses with
 get_weightings (:18-31, :82-106) that models.cm.train_util.TrainLoop trains the U-Net with, and the consistency distillation /
 consistency training loss consistency_losses (:108-241) of models.cm.train_util.CMTrainLoop, its lpips norm (:221-234) through
-models.cm.lpips once the caller supplies the weights.  progdist (losses and sampler) stays out of scope.
+models.cm.lpips once the caller supplies the weights, and progressive distillation: progdist_losses (:243-335) and its sampler
+sample_progdist / progdist_sample (:378-379, :685-719).
 
 training_losses on the HIP UNetModel (bare, or behind a wrapper that holds it as `.module`) is ONE autograd node: the network
 input of the batch in one launch (dxmi_edm_dsm_prep), the U-Net forward of models.cm.unet_train, the per-sample terms in one
@@ -39,7 +40,13 @@ _memo in plain dicts.  The two loss nodes run the U-Net through unet_train.train
 running its training program without an autograd ctx; _cd_loss is the consistency loss as a plain function, shared by the node
 and the no-grad call.
 
-Both loss nodes run inside a StepGraph capture (models.cm.train_util's use_graph): they read nothing back, allocate from the graph's
+progdist_losses on HIP UNetModels (online and teacher) is ONE autograd node around the online network in the same way (_pd_loss,
+_PDLossFn): dxmi_cd_prep on the coarse ladder, the online training forward, teacher evaluation 1, dxmi_pd_solver MID, teacher
+evaluation 2, dxmi_pd_solver END (target_x; x_t3 is never stored), dxmi_pd_loss_fwd; its backward is dxmi_pd_loss_bwd and the U-Net
+backward.  Its levels are a host table of 2 S + 1 entries (PDLevels: the coarse ladder, then the half steps); num_scales = 1 is legal.
+lpips goes through dxmi_pd_lpips_images and, backwards, dxmi_cd_lpips_bwd.  The reference has no l2-32 here: refused.
+
+The training_losses and consistency_losses nodes run inside a StepGraph capture (models.cm.train_util's use_graph): they read nothing back, allocate from the graph's
 pool only, and their draws (randn_like, the index randint) are torch device RNG, which is graph-aware.  What a capture freezes is
 what reaches the kernels by value: num_scales, the randint bound and the table pointer, so the loop keys its graph on them, and the
 level table must be on the device before the capture (an upload cannot be captured: refused otherwise).  Dropout seeds are host
@@ -243,6 +250,90 @@ class _CDLossFn(torch.autograd.Function):
         return (None,) * 10 + grads
 
 
+class PDLevels(_HostTable):
+    """The levels of progdist_losses (reference :285-298) for num_scales = S >= 1, on the host in fp32 torch with the reference's
+    own expressions: `indices / num_scales` is an int64 tensor over a python int, `indices + 0.5` a float tensor, then `** rho`.
+    One table of 2 S + 1 entries: the coarse ladder arange(S + 1) / S first (t of index i = table[i], t3 = table[i + 1]: the
+    reference's `(indices + 1) / num_scales` is the next coarse entry), then the half steps (arange(S) + 0.5) / S
+    (t2 = table[S + 1 + i]).  Bit-identical to the reference's per-sample t, t2, t3 on the same CPU."""
+
+    def __init__(self, num_scales, sigma_min, sigma_max, rho):
+        S = int(num_scales)
+        if S < 1:
+            raise ValueError(f"progdist_losses: num_scales must be at least 1, got {num_scales}")
+        coarse, half = torch.arange(S + 1, dtype=torch.int64), torch.arange(S, dtype=torch.int64)
+        delta = sigma_min ** (1 / rho) - sigma_max ** (1 / rho)
+        t = (sigma_max ** (1 / rho) + coarse / S * delta) ** rho
+        t2 = (sigma_max ** (1 / rho) + (half + 0.5) / S * delta) ** rho
+        super().__init__(torch.cat([t, t2]).to(torch.float32))
+        self.num_scales = S
+
+    def levels(self, indices):
+        """-> (t, t2, t3) of every index, gathered on the host table's device."""
+        tab, S = self.table.to(indices.device), self.num_scales
+        return tab[indices], tab[S + 1 + indices], tab[indices + 1]
+
+
+_PD_LEVELS = {}
+
+
+def pd_levels(num_scales, sigma_min, sigma_max, rho):
+    key = (int(num_scales), float(sigma_min), float(sigma_max), float(rho))
+    return _memo(_PD_LEVELS, key, 256, lambda: PDLevels(num_scales, sigma_min, sigma_max, rho))
+
+
+def _pd_loss(diffusion, net, teacher, teacher_diffusion, x_start, noise, indices, tab, y, keep):
+    """prep -> online U-Net forward -> the two Euler stages around the teacher evaluations -> per-sample loss (reference :300-327).
+    -> (loss, (tape, kw, operands, lpips)), the second being what _PDLossFn.backward reads.  tab: the 2 S + 1 levels of PDLevels;
+    its first S + 1 entries are a ladder dxmi_cd_prep / dxmi_cd_lpips_bwd read as they read CDLevels."""
+    sd, td = diffusion.sigma_data, teacher_diffusion
+    coarse = tab[:(tab.numel() + 1) // 2]
+    x_t, x_in, t, x_te = ops.cd_prep(x_start, noise, indices, coarse, sd, td.sigma_data)
+    F, tape = train_forward(net, x_in, t, y)
+    tk = dict(sigma_data=td.sigma_data, sigma_min=td.sigma_min, distillation=td.distillation)
+    F1 = teacher.forward_inference(x_in if x_te is None else x_te, t, y)
+    x_t2, te_in, te_t = ops.pd_solver(ops.PD_MID, x_t, F1, indices, tab, next_sigma_data=td.sigma_data, **tk)
+    F2 = teacher.forward_inference(te_in, te_t, y)
+    target_x = ops.pd_solver(ops.PD_END, x_t, F2, indices, tab, x_t2=x_t2, **tk)
+    kw = dict(loss_norm=diffusion.loss_norm, weight_schedule=diffusion.weight_schedule, sigma_data=sd,
+              sigma_min=diffusion.sigma_min, distillation=diffusion.distillation)
+    if diffusion.loss_norm == "lpips":
+        from dxmi_hip import lpips_ops
+        from .lpips import _lpips_forward
+        del kw["loss_norm"]
+        lp = diffusion._lpips()
+        x01, w = lpips_ops.pd_lpips_images(F, x_t, target_x, indices, tab, **kw)
+        loss, acts = _lpips_forward(lp, x01, LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None, scale=w, keep=keep)
+        return loss, (tape, kw, (indices, coarse), (lp, acts, tuple(x_start.shape[2:])))
+    return ops.pd_loss_fwd(F, x_t, target_x, indices, tab, **kw), (tape, kw, (F, x_t, target_x, indices, tab), None)
+
+
+class _PDLossFn(torch.autograd.Function):
+    """_pd_loss as one node around the online network."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, teacher, teacher_diffusion, x_start, noise, indices, tab, y, *params):
+        loss, (ctx.tape, ctx.kw, ctx.ops, ctx.lpips) = _pd_loss(diffusion, net, teacher, teacher_diffusion, x_start, noise, indices,
+                                                                tab, y, keep=True)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * len(ctx.needs_input_grad)
+        if ctx.lpips is not None:
+            from dxmi_hip import lpips_ops
+            from .lpips import _lpips_backward
+            dF = lpips_ops.cd_lpips_bwd(g.detach().float().contiguous(), _lpips_backward(*ctx.lpips, None), *ctx.ops, **ctx.kw)
+        else:
+            dF = ops.pd_loss_bwd(g.detach().float().contiguous(), *ctx.ops, **ctx.kw)
+        ctx.ops = ctx.lpips = None
+        grads = train_backward(ctx.tape, dF)
+        ctx.tape = None
+        return (None,) * 9 + grads
+
+
 class KarrasDenoiser:
     def __init__(self, sigma_data: float = 0.5, sigma_max=80.0, sigma_min=0.002, rho=7.0, weight_schedule="karras",
                  distillation=False, loss_norm="l2", lpips_loss=None):
@@ -393,8 +484,86 @@ class KarrasDenoiser:
             diffs = (distiller - distiller_target) ** 2
         return {"loss": mean_flat(diffs) * weights}
 
-    def progdist_losses(self, *args, **kwargs):
-        raise NotImplementedError("progressive distillation (progdist_losses, reference :243-335) is not implemented")
+    def progdist_losses(self, model, x_start, num_scales, model_kwargs=None, teacher_model=None, teacher_diffusion=None, noise=None,
+                        indices=None, generator=None):
+        """Progressive distillation loss per sample (reference :243-335) -> {"loss": [N]}: the student's denoised x at t against
+        the denoiser that one Euler step from t to t3 would need to land where the teacher's two Euler steps t -> t2 -> t3 land.
+        indices: the ladder index of every sample in [0, num_scales - 1] (the reference draws th.randint(0, num_scales, (N,))
+        inside; drawn here, from `generator` if given, when None).  num_scales = 1 is legal (the schedule's last phase)."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        if teacher_model is None or teacher_diffusion is None:
+            raise NotImplementedError("progdist_losses: Must have a teacher model and its teacher_diffusion")
+        if self.loss_norm == "lpips":        # set on the object after construction, as the reference's callers set it
+            self._lpips()
+        if self.loss_norm not in ("l1", "l2", "lpips"):      # no l2-32 here: the reference's else branch (:328-329)
+            raise ValueError(f"Unknown loss norm {self.loss_norm}")
+        N = x_start.shape[0]
+        if indices is None:
+            if generator is not None:
+                indices = torch.randint(0, num_scales, (N,), generator=generator, device=generator.device).to(x_start.device)
+            else:
+                indices = torch.randint(0, num_scales, (N,), device=x_start.device)
+        nets = [_hip_unet(m) for m in (model, teacher_model)]
+        if all(n is not None for n in nets) and x_start.is_cuda:
+            return self._progdist_losses_hip(nets, x_start, num_scales, model_kwargs, teacher_diffusion, noise, indices)
+
+        dims = x_start.ndim
+        t, t2, t3 = pd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).levels(indices.to(x_start.device))
+
+        @torch.no_grad()
+        def euler_solver(x, s, next_s):
+            denoiser = teacher_diffusion.denoise(teacher_model, x, s, **model_kwargs)[1]
+            d = (x - denoiser) / append_dims(s, dims)
+            return x + d * append_dims(next_s - s, dims)
+
+        x_t = x_start + noise * append_dims(t, dims)
+        denoised_x = self.denoise(model, x_t, t, **model_kwargs)[1]
+        with torch.no_grad():
+            x_t2 = euler_solver(x_t, t, t2).detach()
+            x_t3 = euler_solver(x_t2, t2, t3).detach()
+            target_x = (x_t - append_dims(t, dims) * (x_t3 - x_t) / append_dims(t3 - t, dims)).detach()     # euler_to_denoiser
+        weights = get_weightings(self.weight_schedule, self.get_snr(t), self.sigma_data)
+        if self.loss_norm == "l1":
+            diffs = torch.abs(denoised_x - target_x)
+        elif self.loss_norm == "l2":
+            diffs = (denoised_x - target_x) ** 2
+        else:
+            resize = LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None
+            return {"loss": self._lpips()((denoised_x + 1) / 2.0, (target_x + 1) / 2.0, resize=resize) * weights}
+        return {"loss": mean_flat(diffs) * weights}
+
+    def _progdist_losses_hip(self, nets, x_start, num_scales, model_kwargs, teacher_diffusion, noise, indices):
+        net, teacher = nets
+        if x_start.requires_grad or noise.requires_grad:
+            raise NotImplementedError("progdist_losses on the HIP U-Net differentiates the online network's parameters only: "
+                                      "x_start and noise must not require grad")
+        extra = set(model_kwargs) - {"y"}
+        if extra:
+            raise NotImplementedError(f"progdist_losses on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
+        y = model_kwargs.get("y")
+        for n in nets:
+            if (y is not None) != (n.num_classes is not None):
+                raise ValueError("must specify y if and only if the model is class-conditional")
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        x_start, noise = f32(x_start), f32(noise)
+        indices = indices.detach().to(device=x_start.device, dtype=torch.int64).reshape(-1).contiguous()
+        if noise.shape != x_start.shape or indices.numel() != x_start.shape[0] or x_start.dim() != 4:
+            raise ValueError(f"progdist_losses: noise {tuple(noise.shape)} must match x_start {tuple(x_start.shape)} [N, C, H, W] "
+                             f"and indices ({indices.numel()}) hold one level per sample")
+        levels = pd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho)
+        if _graph.capturing() and not levels.on_device(x_start.device):
+            raise DxmiError(f"progdist_losses inside a StepGraph capture: the level table of num_scales {int(num_scales)} is not on "
+                            f"{x_start.device} yet (pd_levels(...).device_table(device) before the capture: an upload cannot be captured)")
+        tab = levels.device_table(x_start.device)
+        args = (self, net, teacher, teacher_diffusion, x_start, noise, indices, tab, y)
+        if torch.is_grad_enabled():
+            loss = _PDLossFn.apply(*args, *ops.fast_parameters(net))
+        else:
+            loss, _ = _pd_loss(*args, keep=False)
+        return {"loss": loss}
 
     def _consistency_losses_hip(self, nets, x_start, num_scales, model_kwargs, teacher_diffusion, noise, indices):
         net, target = nets[0], nets[1]
@@ -451,7 +620,6 @@ def get_ancestral_step(sigma_from, sigma_to):
 
 # ------------------------------------------------------------------------------------------------------------- Karras samplers
 KARRAS_SAMPLERS = ("heun", "dpm", "euler", "ancestral")
-_DISTILLED_SAMPLERS = ("onestep", "multistep", "progdist")
 CM_SAMPLERS = ("onestep", "multistep")
 _GRAPHS = weakref.WeakKeyDictionary()       # model -> {graph key: StepGraph}
 _SCHEDULES = {}
@@ -695,9 +863,21 @@ def sample_dpm(denoiser, x, sigmas, generator, progress=False, callback=None, s_
     return _run_stages(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
 
 
+@torch.no_grad()
+def sample_progdist(denoiser, x, sigmas, generator=None, progress=False, callback=None):
+    """The sampler of a progressively distilled student (reference :685-719): the trailing zero of `sigmas` is dropped and every
+    remaining interval is one Euler step, so it ends at the last non-zero sigma (sigma_min), not at 0.  NFE = len(sigmas) - 2.
+    The launches are sample_euler's (DXMI_KARRAS_EULER rows) on the shortened ladder."""
+    if len(sigmas) < 3:
+        raise ValueError(f"sample_progdist needs at least one step: three sigmas with the trailing zero, got {len(sigmas)}")
+    _check_sampler_args(denoiser, x)
+    sch = _schedule(sigmas[:-1], "euler", denoiser, 1.0, 0.0, 0.0, float("inf"), 1.0)
+    return _run_stages(sch, denoiser, x, tuple(x.shape), x.device, generator, callback, progress)
+
+
 def karras_nfe(sampler, steps):
-    """Network evaluations per image: heun 2 steps - 1, dpm 2 steps, euler / ancestral steps."""
-    return {"heun": 2 * steps - 1, "dpm": 2 * steps, "euler": steps, "ancestral": steps}[sampler]
+    """Network evaluations per image: heun 2 steps - 1, dpm 2 steps, euler / ancestral / progdist steps."""
+    return {"heun": 2 * steps - 1, "dpm": 2 * steps, "euler": steps, "ancestral": steps, "progdist": steps}[sampler]
 
 
 def karras_sample(diffusion, model, shape, steps, clip_denoised=True, progress=False, callback=None, model_kwargs=None,
@@ -714,7 +894,10 @@ def karras_sample(diffusion, model, shape, steps, clip_denoised=True, progress=F
     hipGraph: the first call of a key runs eagerly, the second is captured.  The returned tensor is then STATIC: the next call
     of the same key overwrites it.  Off with callback, progress or a generator, and for model_kwargs other than `y`.
     sampler onestep / multistep (ts: the multistep step indices in [0, steps - 1]): consistency-model sampling, only for a
-    diffusion with distillation=True (see the module docstring); multistep uses diffusion.rho, as the reference does (:400)."""
+    diffusion with distillation=True (see the module docstring); multistep uses diffusion.rho, as the reference does (:400).
+    sampler progdist is not served here: this entry point keeps refusing it together with the consistency samplers on a plain
+    diffusion (tests/test_karras_sample_host.py and tests/test_cm_sample_host.py pin that refusal); progdist_sample below is the
+    entry point of that sampler."""
     denoiser = KarrasDenoiserFn(diffusion, model, clip_denoised, model_kwargs)
     if sampler in CM_SAMPLERS and getattr(diffusion, "distillation", False):
         # x_T = randn * sigma_max, clamp(x_0, -1, 1); the schedule (and so ts) is settled before the device is looked at
@@ -728,9 +911,13 @@ def karras_sample(diffusion, model, shape, steps, clip_denoised=True, progress=F
         key = (sampler, steps, ts, float(sigma_min), float(sigma_max), float(rho), float(diffusion.rho),
                bool(diffusion.distillation), bool(clip_denoised), float(diffusion.sigma_data))
         return _sample_on_device(lambda: sch, denoiser, shape, device, "cm_sample", key, use_graph, generator, callback, progress)
-    if sampler in _DISTILLED_SAMPLERS:
-        raise NotImplementedError(f"sampler {sampler!r} needs a consistency-distilled model (`ts`, boundary-condition scalings), "
-                                  "which no config here builds; the device path runs heun, dpm, euler and ancestral")
+    if sampler == "progdist":
+        raise NotImplementedError("karras_sample refuses sampler 'progdist' as it refuses the samplers of a consistency-distilled "
+                                  "model on a plain diffusion: a progressively distilled student, which keeps the EDM scalings "
+                                  "(distillation=False), samples through progdist_sample(diffusion, model, shape, steps, ...)")
+    if sampler in CM_SAMPLERS:
+        raise NotImplementedError(f"sampler {sampler!r} needs a consistency-distilled model (`ts`, boundary-condition scalings): a "
+                                  "diffusion with distillation=True; a plain one samples with heun, dpm, euler and ancestral")
     if sampler not in KARRAS_SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}")
     _refuse_distillation(diffusion)
@@ -741,6 +928,25 @@ def karras_sample(diffusion, model, shape, steps, clip_denoised=True, progress=F
     key = (sampler, steps, float(sigma_min), float(sigma_max), float(rho), float(s_churn), float(s_tmin), float(s_tmax),
            float(s_noise), bool(clip_denoised), float(diffusion.sigma_data))
     return _sample_on_device(schedule, denoiser, shape, device, "karras_sample", key, use_graph, generator, callback, progress)
+
+
+def progdist_sample(diffusion, model, shape, steps, clip_denoised=True, progress=False, callback=None, model_kwargs=None, device=None,
+                    sigma_min=0.002, sigma_max=80, rho=7.0, generator=None, use_graph=False):
+    """Sample a progressively distilled student on the device: what the reference's karras_sample(sampler="progdist") does
+    (:378-379, sample_progdist :685-719); returns clamp(x, -1, 1).  The ladder is get_sigmas_karras(steps + 1) with the trailing zero
+    dropped: `steps` Euler steps (NFE = steps) that end at sigma_min, not at 0.  distillation=False only: the student keeps the EDM
+    scalings.  model, generator, callback (no sigma_hat in its dict, as the reference's), progress and use_graph as for
+    karras_sample's euler; the launches are DXMI_KARRAS_EULER rows."""
+    if getattr(diffusion, "distillation", False):
+        raise NotImplementedError("progdist_sample runs a progressively distilled student, which keeps the EDM scalings "
+                                  "(distillation=False); a consistency-distilled model samples with onestep / multistep")
+    if steps < 1:
+        raise ValueError(f"progdist_sample needs at least one step, got {steps}")
+    denoiser = KarrasDenoiserFn(diffusion, model, clip_denoised, model_kwargs)
+    schedule = lambda: _schedule(get_sigmas_karras(steps + 1, sigma_min, sigma_max, rho, device="cpu")[:-1], "euler", denoiser,
+                                 sigma_max, 0.0, 0.0, float("inf"), 1.0)
+    key = ("progdist", steps, float(sigma_min), float(sigma_max), float(rho), bool(clip_denoised), float(diffusion.sigma_data))
+    return _sample_on_device(schedule, denoiser, shape, device, "progdist_sample", key, use_graph, generator, callback, progress)
 
 
 def _sample_on_device(schedule, denoiser, shape, device, name, key, use_graph, generator, callback, progress):

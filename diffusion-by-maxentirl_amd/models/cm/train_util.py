@@ -20,7 +20,16 @@ rate comes from ema_scale_fn(global_step) (one dxmi_ema_update launch series on 
 global_step, and target_model%06d.pt (plus, with the first save, teacher_model%06d.pt) is written next to TrainLoop's files and
 read back on resume (a checkpoint later than the first finds the teacher under the first save's name in the same directory;
 where there is none, the teacher the caller passed is kept).  An fp16 overflow step skips the target EMA on the host, from the
-flag optimize() has already read back, so its eager launch passes no found_inf.  progdist is not implemented.
+flag optimize() has already read back, so its eager launch passes no found_inf.
+
+training_mode="progdist" (reference :305-318, :388-442, :456-476, :551-555) is progressive distillation with
+KarrasDenoiser.progdist_losses: ema_scale_fn's ("fixed", "progdist") schedule halves num_scales; the first phase distils
+teacher_model under teacher_diffusion, and after the step at which num_scales changes reset_training_for_progdist copies the student
+into teacher_model (fresh RAdam, EMA series restarted from the masters, lr_anneal_steps doubled at num_scales 2, step = 0), so every
+later phase distils the previous phase's student under the student's own diffusion.  teacher_model%06d.pt is written with EVERY
+save and a resume reads the file of the resumed step.  target_model may be None; one that is given stays in eval mode, is saved,
+and neither enters the loss nor is moved by an EMA.  `step` is the phase's own counter (the learning rate anneals on it alone).
+use_graph=True is refused in this mode.  Where this differs from the reference's call site, which cannot run: DESIGN 5.28.
 
 use_graph=True (both loops; off by default) replays a whole step from hipGraphs (dxmi_hip/graph.py StepGraph): the first run_step
 runs eagerly (weight packs, workspaces, optimiser state), the second is captured, later ones are host producers + one upload + the
@@ -337,15 +346,21 @@ class TrainLoop:
 class CMTrainLoop(TrainLoop):
     def __init__(self, *, target_model, teacher_model, teacher_diffusion, training_mode, ema_scale_fn, total_training_steps, **kwargs):
         """kwargs: TrainLoop's, use_graph among them."""
-        if training_mode == "progdist":
-            raise NotImplementedError("CMTrainLoop: progressive distillation (progdist) is not implemented")
-        if training_mode not in ("consistency_distillation", "consistency_training"):
+        progdist = training_mode == "progdist"
+        if training_mode not in ("consistency_distillation", "consistency_training", "progdist"):
             raise ValueError(f"Unknown training mode {training_mode}")
-        if target_model is None:
+        if progdist:
+            if teacher_model is None or teacher_diffusion is None:
+                raise NotImplementedError("CMTrainLoop: progdist must have a teacher_model and its teacher_diffusion")
+            if kwargs.get("use_graph"):
+                raise NotImplementedError("CMTrainLoop: use_graph=True with training_mode='progdist' is not supported: a phase change "
+                                          "replaces the optimiser and the EMA buffers and rewrites the teacher under a live capture; "
+                                          "train this mode eagerly")
+        elif target_model is None:
             raise NotImplementedError("Must have a target model")
         if training_mode == "consistency_distillation" and (teacher_model is None or teacher_diffusion is None):
             raise ValueError("CMTrainLoop: consistency_distillation needs teacher_model and teacher_diffusion")
-        if kwargs.get("schedule_sampler") is None:      # consistency_losses draws its own levels: only `weights` is used
+        if kwargs.get("schedule_sampler") is None:      # the losses draw their own levels: only `weights` is used
             kwargs["schedule_sampler"] = _UnitWeights()
         super().__init__(**kwargs)
         self.training_mode, self.ema_scale_fn = training_mode, ema_scale_fn
@@ -353,27 +368,47 @@ class CMTrainLoop(TrainLoop):
         self.total_training_steps = total_training_steps
         self._teacher_saved = False
 
-        self._load_and_sync_side_model(self.target_model, "target_model")
-        self.target_model.requires_grad_(False)
-        self.target_model.train()
-        if self.use_fp16:       # flat fp32 masters in the trainer's groups, the target parameters views of them on the device
-            self.target_model_param_groups_and_shapes = get_param_groups_and_shapes(self.target_model.named_parameters())
-            self.target_model_master_params = [p.detach().requires_grad_(False) for p in
-                                               make_master_params(self.target_model_param_groups_and_shapes)]
-            _alias_params_into_masters(self.target_model_param_groups_and_shapes, self.target_model_master_params)
-        else:                   # the trainer's masters are the model parameters themselves: so are the target's
-            self.target_model_param_groups_and_shapes = None
-            self.target_model_master_params = [p.detach() for p in self.target_model.parameters()]
+        if self.target_model is not None:
+            self._load_and_sync_side_model(self.target_model, "target_model")
+            self.target_model.requires_grad_(False)
+            self.target_model.train()
+            if self.use_fp16:   # flat fp32 masters in the trainer's groups, the target parameters views of them on the device
+                self.target_model_param_groups_and_shapes = get_param_groups_and_shapes(self.target_model.named_parameters())
+                self.target_model_master_params = [p.detach().requires_grad_(False) for p in
+                                                   make_master_params(self.target_model_param_groups_and_shapes)]
+                _alias_params_into_masters(self.target_model_param_groups_and_shapes, self.target_model_master_params)
+            else:               # the trainer's masters are the model parameters themselves: so are the target's
+                self.target_model_param_groups_and_shapes = None
+                self.target_model_master_params = [p.detach() for p in self.target_model.parameters()]
         if self.teacher_model is not None:
             self._load_and_sync_side_model(self.teacher_model, "teacher_model")
             self.teacher_model.requires_grad_(False)
             self.teacher_model.eval()
         self.global_step = self.step
+        if progdist:        # reference :305-318: `step` counts within the phase of the resumed global_step
+            if self.target_model is not None:
+                self.target_model.eval()
+            if self.lr_anneal_steps:
+                _, scale = ema_scale_fn(self.global_step)
+                if scale == 1 or scale == 2:
+                    _, start_scale = ema_scale_fn(0)
+                    n_normal_steps = int(np.log2(start_scale // 2)) * self.lr_anneal_steps
+                    step = self.global_step - n_normal_steps
+                    if step != 0:
+                        self.lr_anneal_steps *= 2
+                        self.step = step % self.lr_anneal_steps
+                    else:
+                        self.step = 0
+                else:
+                    self.step = self.global_step % self.lr_anneal_steps
 
     def _load_and_sync_side_model(self, net, prefix):
         if self.resume_checkpoint:
             path, name = os.path.split(self.resume_checkpoint)
             ckpt = os.path.join(path, name.replace("model", prefix))
+            if not os.path.exists(ckpt) and prefix == "teacher_model" and self.training_mode == "progdist":
+                # the teacher changes at every phase: only the file of the resumed step holds the one this step distils from
+                raise FileNotFoundError(f"CMTrainLoop: resuming progdist needs {ckpt} (the teacher is written at every save)")
             if not os.path.exists(ckpt) and prefix == "teacher_model":
                 # the teacher never changes and is written with the first save only: a later checkpoint resumes from that file
                 found = sorted(f for f in os.listdir(path or ".") if f.startswith("teacher_model") and f.endswith(".pt"))
@@ -411,13 +446,51 @@ class CMTrainLoop(TrainLoop):
         """Eagerly only on a step the optimiser took (an fp16 overflow step moves neither EMA: optimize() has read the flag back
         already); in a captured step always, with the device flag."""
         self._update_ema(found_inf)
-        self._update_target_ema(found_inf)
+        if self.training_mode == "progdist":     # the target, if any, takes no part (rate 1.0: its EMA launch series is skipped)
+            self.reset_training_for_progdist()
+        else:
+            self._update_target_ema(found_inf)
+
+    def reset_training_for_progdist(self):
+        """Reference :416-442, in its place: after the EMA updates of a step the optimiser took, before the counters advance.  When
+        that step was the first of a new num_scales, the student becomes the teacher of the phase that has begun: its weights are
+        copied into teacher_model (and the teacher's packed weights refreshed: forward_inference reads those), the optimiser is a
+        fresh RAdam over the masters, every EMA series restarts from the masters, lr_anneal_steps doubles for num_scales 2, and
+        `step` restarts."""
+        assert self.training_mode == "progdist", "Training mode must be progdist"
+        if self.global_step <= 0:
+            return
+        scales, scales2 = self.ema_scale_fn(self.global_step)[1], self.ema_scale_fn(self.global_step - 1)[1]
+        if scales == scales2:
+            return
+        with torch.no_grad():
+            for pt, ps in zip(self.teacher_model.parameters(), self.model.parameters()):
+                pt.copy_(ps.detach())
+        net = self.teacher_model.module if hasattr(self.teacher_model, "module") else self.teacher_model
+        if hasattr(net, "refresh_packs") and next(net.parameters()).is_cuda:
+            net.refresh_packs()
+        # a fresh optimiser of the loop's own kind (RAdam; a host test stands torch's in for it), with no state
+        self.opt = type(self.opt)(self.mp_trainer.master_params, lr=self.lr, weight_decay=self.weight_decay)
+        self.ema_params = [[p.detach().clone() for p in self.mp_trainer.master_params] for _ in self.ema_rate]
+        if scales == 2:
+            self.lr_anneal_steps *= 2
+        self.teacher_model.eval()
+        self.step = 0
+
+    def _anneal_lr(self):
+        if self.training_mode != "progdist":
+            return super()._anneal_lr()
+        if not self.lr_anneal_steps:
+            return
+        lr = self.lr * (1 - self.step / self.lr_anneal_steps)      # `step` is the phase's own count here, after a resume too (:305-318)
+        for param_group in self.opt.param_groups:
+            param_group["lr"] = lr
 
     def _graph_key(self):
         return self.ema_scale_fn(self.global_step)
 
     def _graph_modules(self):
-        nets = [self.model, self.target_model] + ([self.teacher_model] if self.teacher_model is not None else [])
+        nets = [n for n in (self.model, self.target_model, self.teacher_model) if n is not None]
         return [m for net in nets for m in _graph.pack_modules(net)]
 
     def _before_capture(self, key):
@@ -451,6 +524,18 @@ class CMTrainLoop(TrainLoop):
             micro_cond = {k: v[i:i + self.microbatch].to(self.device) for k, v in cond.items()}
             _, weights = self.schedule_sampler.sample(micro.shape[0], self.device)
             _, num_scales = self.ema_scale_fn(self.global_step)
+            if self.training_mode == "progdist":
+                # the first phase distils the given teacher under its own diffusion; every later one the previous phase's student,
+                # which reset_training_for_progdist copied into teacher_model, under the student's diffusion (reference :456-476,
+                # whose keyword names progdist_losses does not take: DESIGN 5.28)
+                first = num_scales == self.ema_scale_fn(0)[1]
+                losses = self.diffusion.progdist_losses(self.ddp_model, micro, num_scales, teacher_model=self.teacher_model,
+                                                        teacher_diffusion=self.teacher_diffusion if first else self.diffusion,
+                                                        model_kwargs=micro_cond)
+                loss = (losses["loss"] * weights).mean()
+                self._log_loss_dict({k: v * weights for k, v in losses.items()})
+                self.mp_trainer.backward(loss)
+                continue
             distill = self.training_mode == "consistency_distillation"
             losses = self.diffusion.consistency_losses(self.ddp_model, micro, num_scales, target_model=self.target_model,
                                                        teacher_model=self.teacher_model if distill else None,
@@ -474,9 +559,11 @@ class CMTrainLoop(TrainLoop):
             save_checkpoint(rate, params)
         if _rank() == 0:
             torch.save(self.opt.state_dict(), os.path.join(self.log_dir, f"opt{step:06d}.pt"))
-            torch.save({k: v.detach().clone() for k, v in self.target_model.state_dict().items()},
-                       os.path.join(self.log_dir, f"target_model{step:06d}.pt"))
-            if self.teacher_model is not None and not self._teacher_saved:      # the teacher never changes: written once
+            if self.target_model is not None:
+                torch.save({k: v.detach().clone() for k, v in self.target_model.state_dict().items()},
+                           os.path.join(self.log_dir, f"target_model{step:06d}.pt"))
+            # the teacher of CD never changes: written once; the teacher of progdist changes at every phase: written with every save
+            if self.teacher_model is not None and (not self._teacher_saved or self.training_mode == "progdist"):
                 torch.save({k: v.detach().clone() for k, v in self.teacher_model.state_dict().items()},
                            os.path.join(self.log_dir, f"teacher_model{step:06d}.pt"))
         self._teacher_saved = True

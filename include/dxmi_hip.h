@@ -646,6 +646,41 @@ int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, const float* f_
                      int32_t H, int32_t W, int32_t loss_norm, float sigma_data, float sigma_min, int32_t distillation,
                      int32_t weight_schedule, void* stream);
 
+/* Progressive distillation loss (KarrasDenoiser.progdist_losses, models/cm/karras_diffusion.py:243-335), the launches between its
+ * network evaluations; the first, x_t and the inputs at t (:300, denoise :345-349), is dxmi_cd_prep on the first num_scales + 1
+ * entries of the table.  Tensors as for dxmi_cd_*.  t_table: fp32 [2 num_scales + 1] on the DEVICE, built on the host with the
+ * reference's expressions (:285-298): entries [0, num_scales] the coarse ladder (t = t_table[index], t3 = t_table[index + 1]),
+ * entries [num_scales + 1, 2 num_scales] the half steps (t2 = t_table[num_scales + 1 + index]).  num_scales >= 1.  An index outside
+ * [0, num_scales - 1] gives NaN levels; nothing outside the table is read.  Every fp32 operation in the reference's order, one
+ * rounding per torch op.
+ * dxmi_pd_solver (euler_solver :267-274, euler_to_denoiser :276-281), the denoiser formed with the SOLVER diffusion's scalings
+ *   (the teacher's sigma_data / sigma_min / distillation flag; denoise() does not clamp):
+ *     MID  model_out = the teacher at (x_t, t): out = x_t2 = x_t + ((x_t - denoiser) / t) (t2 - t); x_in_next = c_in(t2) x_t2
+ *          under next_sigma_data and t_next = 250 ln(t2 + 1e-44), the teacher's second input.  x_t2_in is not read.
+ *     END  model_out = the teacher at (x_t2_in, t2): x_t3 = x_t2 + ((x_t2 - denoiser) / t2) (t3 - t2) (never stored) and
+ *          out = target_x = x_t - (t (x_t3 - x_t)) / (t3 - t) (:278-280).  x_in_next / t_next are not written (may be NULL).
+ * dxmi_pd_loss_fwd (:302, :309-316): denoised = c_out(t) f_online + c_skip(t) x_t (boundary-condition scalings when
+ *   distillation != 0), diffs = |denoised - target_x| (DXMI_CD_NORM_L1) or (.)^2 (DXMI_CD_NORM_L2; progdist has no l2-32),
+ *   loss[n] = mean_flat(diffs) * get_weightings(weight_schedule, t^-2) (DXMI_DSM_W_*).  Sums in a fixed order.
+ * dxmi_pd_loss_bwd: d_f_online of that loss for the DEVICE [N] upstream gradient g_loss; L1 uses sign with sign(0) = 0 (th.abs).
+ * dxmi_pd_lpips_images (:317-327): x01 fp32 [2 N, CHW] = (denoised + 1) / 2 in rows [0, N) and (target_x + 1) / 2 in rows
+ *   [N, 2 N), weights[n] = get_weightings(weight_schedule, t^-2); the backward of the lpips norm is dxmi_cd_lpips_bwd on the coarse
+ *   ladder, which needs only c_out(t). */
+#define DXMI_PD_MID 0
+#define DXMI_PD_END 1
+int dxmi_pd_solver(int32_t mode, const float* x_t, const float* x_t2_in, const float* model_out, const int64_t* indices,
+                   const float* t_table, int32_t num_scales, float* out, float* x_in_next, float* t_next, int32_t N, int32_t CHW,
+                   float solver_sigma_data, float solver_sigma_min, int32_t solver_distillation, float next_sigma_data, void* stream);
+int dxmi_pd_loss_fwd(const float* f_online, const float* x_t, const float* target_x, const int64_t* indices, const float* t_table,
+                     int32_t num_scales, float* loss, int32_t N, int32_t CHW, int32_t loss_norm, float sigma_data, float sigma_min,
+                     int32_t distillation, int32_t weight_schedule, void* stream);
+int dxmi_pd_loss_bwd(const float* g_loss, const float* f_online, const float* x_t, const float* target_x, const int64_t* indices,
+                     const float* t_table, int32_t num_scales, float* d_f_online, int32_t N, int32_t CHW, int32_t loss_norm,
+                     float sigma_data, float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream);
+int dxmi_pd_lpips_images(const float* f_online, const float* x_t, const float* target_x, const int64_t* indices,
+                         const float* t_table, int32_t num_scales, float* x01, float* weights, int32_t N, int32_t CHW,
+                         float sigma_data, float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream);
+
 /* TD step of DxMI_Trainer.update_f_v on the replay ring, data side in one launch (reference trainer.py:271-300, :163-169): rows
  * `state_rows[b]` (and `next_rows[b]`, or the dense re-drawn next states of value_resample) of the ring's fp32 [n_src_rows, CHW]
  * trajectory block are gathered into out_state / out_next — the two halves of the batch [next_state | state] the value net
