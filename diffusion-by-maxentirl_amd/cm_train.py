@@ -24,9 +24,16 @@ learning rate anneals to zero over those N steps.  --loss_norm lpips needs the V
 --lpips_vgg16 PATH --lpips_lin PATH, or DXMI_LPIPS_VGG16 / DXMI_LPIPS_LIN in the environment; without them it is refused.
 --use_graph True replays the train step from hipGraphs (CMTrainLoop(use_graph=True): needs --use_fp16 True and a loss norm other than
 lpips); DXMI_GRAPH=0 in the environment forces it off.
+Improved consistency training (Song and Dhariwal 2023) needs neither LPIPS weights nor a teacher: --loss_norm pseudo-huber (--huber_c C,
+0 = 0.00054 sqrt(C H W)), --weight_schedule ict (1 / (t - t2); with pseudo-huber only), --index_sampler lognormal (--p_mean, --p_std: the
+discretised lognormal over the levels; uniform = the reference's randint), --scale_mode ict (num_scales doubles from --start_scales to
+--end_scales over --total_training_steps) and --start_ema 0 (the target is the student of the step before).  --ict True sets all of these
+at once (loss_norm, weight_schedule, scale_mode, target_ema_mode fixed, start_ema 0, start_scales 10, end_scales 1280, index_sampler
+lognormal) and takes --training_mode consistency_training, which it also selects where no --training_mode is given; any other is an error.
 """
 import argparse
 import os
+import sys
 
 import torch
 
@@ -63,18 +70,40 @@ def make_loader(args, device, rank, world):
     return synthetic_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + rank), None
 
 
+# what --ict True sets: improved consistency training as its paper runs it
+ICT_SETTINGS = dict(training_mode="consistency_training", loss_norm="pseudo-huber", weight_schedule="ict", scale_mode="ict",
+                    target_ema_mode="fixed", start_ema=0.0, start_scales=10, end_scales=1280, index_sampler="lognormal")
+
+
 def parse_args(argv=None):
     defaults = dict(model_and_diffusion_defaults())
     defaults.update(cm_train_defaults())
     defaults.update(synthetic_data=False, data_npz="", data_resident="auto", batch_size=16, microbatch=-1, lr=1e-4, ema_rate="0.9999",
                     log_dir="results/cm_train",
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
-                    fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False)
+                    fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False,
+                    huber_c=0.0, index_sampler="uniform", p_mean=-1.1, p_std=2.0, ict=False)
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
     args = ap.parse_args(argv)
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")
+    if args.ict:
+        given = any(a == "--training_mode" or a.startswith("--training_mode=") for a in (sys.argv[1:] if argv is None else argv))
+        if given and args.training_mode != "consistency_training":
+            ap.error(f"--ict True is improved consistency TRAINING: --training_mode {args.training_mode} does not go with it")
+        for k, v in ICT_SETTINGS.items():
+            setattr(args, k, v)
+    if args.index_sampler not in ("uniform", "lognormal"):
+        ap.error(f"--index_sampler {args.index_sampler!r}: uniform or lognormal")
+    if args.huber_c < 0:
+        ap.error(f"--huber_c {args.huber_c}: a positive constant, or 0 for 0.00054 sqrt(C H W)")
+    if args.weight_schedule == "ict" and args.loss_norm != "pseudo-huber":
+        ap.error(f"--weight_schedule ict goes with --loss_norm pseudo-huber only, not {args.loss_norm}")
+    if args.loss_norm == "pseudo-huber" and args.training_mode == "progdist":
+        ap.error("--loss_norm pseudo-huber belongs to the consistency losses, not to progdist")
+    if args.index_sampler == "lognormal" and args.training_mode == "progdist":
+        ap.error("--index_sampler lognormal belongs to the consistency losses, not to progdist")
     if args.training_mode == "progdist" and args.scale_mode == "fixed":
         args.scale_mode = "progdist"       # the reference's pair for this mode: target_ema_mode fixed, scale_mode progdist
     if args.data_resident not in ("auto", "device", "host"):
@@ -106,6 +135,7 @@ def main():
     model_kw = args_to_dict(args, model_and_diffusion_defaults().keys())
     model, diffusion = create_model_and_diffusion(distillation=not progdist, **model_kw)     # a progdist student keeps EDM scalings
     diffusion.loss_norm = args.loss_norm
+    diffusion.huber_c = args.huber_c or None       # 0: the paper's constant for the image size of a call
     if args.loss_norm == "lpips":      # refused here, before the target and the teacher are built, when no weights were named
         from models.cm.karras_diffusion import _NO_LPIPS
         from models.cm.lpips import ENV_LIN, ENV_VGG16, LPIPS
@@ -136,13 +166,17 @@ def main():
     lr_anneal_steps = args.lr_anneal_steps if not args.max_iters else args.max_iters
     if progdist:       # the loop's phase arithmetic takes lr_anneal_steps for the length of a phase (doubled for num_scales 2 and 1)
         lr_anneal_steps = args.lr_anneal_steps or args.distill_steps_per_iter
+    index_sampler = None
+    if args.index_sampler == "lognormal":
+        from models.cm.resample import DiscreteLogNormalSampler
+        index_sampler = DiscreteLogNormalSampler(diffusion.sigma_min, diffusion.sigma_max, diffusion.rho, args.p_mean, args.p_std)
     loop = CMTrainLoop(model=model, target_model=target_model, teacher_model=teacher_model, teacher_diffusion=teacher_diffusion,
                        training_mode=args.training_mode, ema_scale_fn=ema_scale_fn, total_training_steps=total, diffusion=diffusion,
                        data=data,
                        batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr, ema_rate=args.ema_rate,
                        log_interval=args.log_interval, save_interval=args.save_interval, resume_checkpoint=args.resume_checkpoint,
                        use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth, weight_decay=args.weight_decay,
-                       lr_anneal_steps=lr_anneal_steps, log_dir=args.log_dir,
+                       lr_anneal_steps=lr_anneal_steps, log_dir=args.log_dir, index_sampler=index_sampler,
                        use_graph=args.use_graph and _graph.default_enabled())
     print0(f"{args.training_mode}: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
            f"{total} steps, loss_norm {args.loss_norm}")

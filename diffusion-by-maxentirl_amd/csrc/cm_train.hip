@@ -9,6 +9,9 @@
 //   dxmi_cd_loss_fwd  distiller = c_out(t) F_s + c_skip(t) x_t, target = c_out(t2) F_tg + c_skip(t2) x_t2, the norm (l1, l2,
 //                     l2 after the two-tap bilinear resize to 32 x 32) and mean_flat(.) * get_weightings(snr(t))
 //   dxmi_cd_loss_bwd  dF_s of that loss for a per-sample upstream gradient
+//   dxmi_cd_huber_fwd / _bwd  the pseudo-Huber metric of improved consistency training (Song and Dhariwal 2023) on the same
+//                     difference: ssq = sum(df^2) (kept for the backward), loss = w ssq / (sqrt(ssq + c^2) + c); the weight schedules
+//                     above and DXMI_DSM_W_ICT, w = 1 / (t - t2)
 // Elementwise streams: one workgroup row per image, 16 bytes per lane, several loads in flight; per-sample sums in a fixed order
 // (bitwise reproducible).  The time levels are gathered from one small device table by index; an index outside [0, S - 2] gives
 // NaN levels (nothing is read outside the table).
@@ -167,7 +170,8 @@ struct LossScal {
 __device__ __forceinline__ LossScal loss_scalings(Levels L, float sd, float sd2, float sigma_min, int distill, int sched, float inv_sd2) {
     const DsmScal a = dsm_scalings(L.t, sd, sd2, sigma_min, distill, sched, inv_sd2);
     const DsmScal b = dsm_scalings(L.t2, sd, sd2, sigma_min, distill, sched, inv_sd2);
-    return LossScal{a.c_out, a.c_skip, b.c_out, b.c_skip, a.w};
+    // DXMI_DSM_W_ICT needs both levels (the ladder descends: t > t2); only the pseudo-Huber entry points let it through
+    return LossScal{a.c_out, a.c_skip, b.c_out, b.c_skip, sched == DXMI_DSM_W_ICT ? 1.f / (L.t - L.t2) : a.w};
 }
 
 // l1 / l2 on the full-resolution difference; one workgroup per image
@@ -250,6 +254,92 @@ __global__ __launch_bounds__(EW_BLOCK) void cd_loss_bwd_kernel(const float* __re
                 if (NORM == DXMI_CD_NORM_L1) gd = gs * (df > 0.f ? 1.f : (df < 0.f ? -1.f : (df == 0.f ? 0.f : df)));   // sign, sign(0) = 0
                 else gd = gs * (2.f * df);
                 o[e] = gd * c.cs_o;
+            }
+            st4(dFs, base, i, o);
+        }
+    }
+}
+
+// Pseudo-Huber metric on the full-resolution difference: the l2 stream and sum order of cd_loss_fwd_kernel, the sum kept.
+// w * ssq / (sqrt(ssq + c^2) + c) is sqrt(ssq + c^2) - c without the cancellation at ssq << c^2 (a converged model).
+__global__ __launch_bounds__(EW_BLOCK) void cd_huber_fwd_kernel(const float* __restrict__ Fs, const float* __restrict__ Ft,
+                                                                const float* __restrict__ x_t, const float* __restrict__ x_t2,
+                                                                const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
+                                                                float* __restrict__ loss, float* __restrict__ ssq, int CHW, float hc,
+                                                                float sd, float sd2, float sigma_min, int distill, int sched,
+                                                                float inv_sd2) {
+    __shared__ float red[EW_BLOCK / 64];
+    const int b = blockIdx.x;
+    const LossScal c = loss_scalings(cd_levels(idx, tab, S, b), sd, sd2, sigma_min, distill, sched, inv_sd2);
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    float acc = 0.f;
+    for (int i0 = threadIdx.x; i0 < n4; i0 += EW_BLOCK * EW_UNROLL) {
+        f32x4 fs[EW_UNROLL], ft[EW_UNROLL], xa[EW_UNROLL], xb[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i < n4) {
+                fs[u] = ld4(Fs, base, i);
+                xa[u] = ld4(x_t, base, i);
+                ft[u] = ld4(Ft, base, i);
+                xb[u] = ld4(x_t2, base, i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i >= n4) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float ds = c.cs_o * fs[u][e] + c.cs_s * xa[u][e];
+                const float dt = c.ct_o * ft[u][e] + c.ct_s * xb[u][e];
+                const float df = ds - dt;
+                acc += df * df;
+            }
+        }
+    }
+    const float tot = block_sum(acc, red);
+    if (threadIdx.x == 0) {
+        ssq[b] = tot;
+        loss[b] = c.w * (tot / (__builtin_sqrtf(tot + hc * hc) + hc));
+    }
+}
+
+// dF_s = ((g w) / sqrt(ssq + c^2)) df c_out(t), ssq as the forward wrote it
+__global__ __launch_bounds__(EW_BLOCK) void cd_huber_bwd_kernel(const float* __restrict__ g, const float* __restrict__ ssq,
+                                                                const float* __restrict__ Fs, const float* __restrict__ Ft,
+                                                                const float* __restrict__ x_t, const float* __restrict__ x_t2,
+                                                                const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
+                                                                float* __restrict__ dFs, int CHW, float hc, float sd, float sd2,
+                                                                float sigma_min, int distill, int sched, float inv_sd2) {
+    const int b = blockIdx.y;
+    const LossScal c = loss_scalings(cd_levels(idx, tab, S, b), sd, sd2, sigma_min, distill, sched, inv_sd2);
+    const float gs = (g[b] * c.w) / __builtin_sqrtf(ssq[b] + hc * hc);
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
+        f32x4 fs[EW_UNROLL], ft[EW_UNROLL], xa[EW_UNROLL], xb[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i < n4) {
+                fs[u] = ld4(Fs, base, i);
+                xa[u] = ld4(x_t, base, i);
+                ft[u] = ld4(Ft, base, i);
+                xb[u] = ld4(x_t2, base, i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i >= n4) continue;
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float ds = c.cs_o * fs[u][e] + c.cs_s * xa[u][e];
+                const float dt = c.ct_o * ft[u][e] + c.ct_s * xb[u][e];
+                o[e] = (gs * (ds - dt)) * c.cs_o;
             }
             st4(dFs, base, i, o);
         }
@@ -515,6 +605,44 @@ extern "C" int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, cons
                            x_t, x_t2, indices, t_table, num_scales, d_f_online, CHW, sigma_data, sd2, sigma_min, dist, weight_schedule,
                            inv_sd2, (float)(1.0 / (double)CHW));
     DXMI_CHECK_LAUNCH("dxmi_cd_loss_bwd");
+    return DXMI_OK;
+}
+
+#define CD_CHECK_HUBER(fn)                                                                                                       \
+    CD_CHECK_SHAPE(fn);                                                                                                          \
+    DXMI_CHECK_ARG(CHW < (1 << 30), fn ": CHW (%d) must be below 2^30", CHW);                                                    \
+    DXMI_CHECK_ARG(huber_c > 0.f && huber_c <= 3.4028234663852886e38f, fn ": huber_c (%g) must be finite and positive",          \
+                   (double)huber_c);                                                                                             \
+    DXMI_CHECK_ARG(weight_schedule >= DXMI_DSM_W_SNR && weight_schedule <= DXMI_DSM_W_ICT, fn ": unknown weight schedule %d",    \
+                   weight_schedule)
+
+extern "C" int dxmi_cd_huber_fwd(const float* f_online, const float* f_target, const float* x_t, const float* x_t2,
+                                 const int64_t* indices, const float* t_table, int32_t num_scales, float* loss, float* ssq, int32_t N,
+                                 int32_t CHW, float huber_c, float sigma_data, float sigma_min, int32_t distillation,
+                                 int32_t weight_schedule, void* stream) {
+    DXMI_CHECK_ARG(f_online && f_target && x_t && x_t2 && indices && t_table && loss && ssq, "dxmi_cd_huber_fwd: null pointer");
+    CD_CHECK_HUBER("dxmi_cd_huber_fwd");
+    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2), "dxmi_cd_huber_fwd: tensors must be 16-byte aligned");
+    const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
+    hipLaunchKernelGGL(cd_huber_fwd_kernel, dim3(N), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_online, f_target, x_t, x_t2, indices, t_table,
+                       num_scales, loss, ssq, CHW, huber_c, sigma_data, sd2, sigma_min, (int)(distillation != 0), weight_schedule, inv_sd2);
+    DXMI_CHECK_LAUNCH("dxmi_cd_huber_fwd");
+    return DXMI_OK;
+}
+
+extern "C" int dxmi_cd_huber_bwd(const float* g_loss, const float* ssq, const float* f_online, const float* f_target, const float* x_t,
+                                 const float* x_t2, const int64_t* indices, const float* t_table, int32_t num_scales, float* d_f_online,
+                                 int32_t N, int32_t CHW, float huber_c, float sigma_data, float sigma_min, int32_t distillation,
+                                 int32_t weight_schedule, void* stream) {
+    DXMI_CHECK_ARG(g_loss && ssq && f_online && f_target && x_t && x_t2 && indices && t_table && d_f_online,
+                   "dxmi_cd_huber_bwd: null pointer");
+    CD_CHECK_HUBER("dxmi_cd_huber_bwd");
+    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2, d_f_online), "dxmi_cd_huber_bwd: tensors must be 16-byte aligned");
+    const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
+    hipLaunchKernelGGL(cd_huber_bwd_kernel, cd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, ssq, f_online, f_target, x_t,
+                       x_t2, indices, t_table, num_scales, d_f_online, CHW, huber_c, sigma_data, sd2, sigma_min, (int)(distillation != 0),
+                       weight_schedule, inv_sd2);
+    DXMI_CHECK_LAUNCH("dxmi_cd_huber_bwd");
     return DXMI_OK;
 }
 

@@ -33,7 +33,7 @@ __device__ __forceinline__ DsmScal dsm_scalings(float s, float sd, float sd2, fl
         case DXMI_DSM_W_SNR_P1:    r.w = snr + 1.f; break;
         case DXMI_DSM_W_KARRAS:    r.w = snr + inv_sd2; break;
         case DXMI_DSM_W_TRUNC_SNR: r.w = snr < 1.f ? 1.f : snr; break;    // th.clamp(snrs, min=1.0): NaN passes
-        default:                   r.w = 1.f; break;
+        default:                   r.w = 1.f; break;                      // UNIFORM; DXMI_DSM_W_ICT needs two levels: loss_scalings (cm_train.hip)
     }
     return r;
 }

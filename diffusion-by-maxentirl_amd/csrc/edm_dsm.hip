@@ -170,6 +170,12 @@ struct EmaRates {
     float rate[DXMI_EMA_MAX_RATES], alpha[DXMI_EMA_MAX_RATES];
 };
 
+// rate 0 (the target of improved consistency training: the stop-gradient student) is a copy, bit for bit: 0 * ema + src turns a
+// source of -0 into +0 and a non-finite ema into NaN
+__device__ __forceinline__ float ema_one(float rate, float alpha, float src, float ema) {
+    return rate == 0.f ? src : __builtin_fmaf(alpha, src, ema * rate);
+}
+
 template <int K>
 __global__ __launch_bounds__(EMA_BLOCK) void ema_kernel(EmaTable t, EmaRates r, const float* __restrict__ found_inf) {
     if (found_inf && *found_inf != 0.f) return;     // the EMA follows the optimiser: an overflow step leaves it (train_util.py:190-193)
@@ -197,7 +203,7 @@ __global__ __launch_bounds__(EMA_BLOCK) void ema_kernel(EmaTable t, EmaRates r, 
             for (int q = 0; q < R; ++q) {
                 f32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(r.alpha[k], sv[q][e], ev[k][q][e] * r.rate[k]);
+                for (int e = 0; e < 4; ++e) o[e] = ema_one(r.rate[k], r.alpha[k], sv[q][e], ev[k][q][e]);
                 *(f32x4*)(t.ema[k][ti] + base + (int64_t)(q * EMA_BLOCK + threadIdx.x) * 4) = o;
             }
         return;
@@ -206,7 +212,7 @@ __global__ __launch_bounds__(EMA_BLOCK) void ema_kernel(EmaTable t, EmaRates r, 
     for (int64_t i = base + threadIdx.x; i < end; i += EMA_BLOCK) {
         const float sv = S[i];
 #pragma unroll
-        for (int k = 0; k < K; ++k) t.ema[k][ti][i] = __builtin_fmaf(r.alpha[k], sv, t.ema[k][ti][i] * r.rate[k]);
+        for (int k = 0; k < K; ++k) t.ema[k][ti][i] = ema_one(r.rate[k], r.alpha[k], sv, t.ema[k][ti][i]);
     }
 }
 

@@ -177,6 +177,8 @@ SIGNATURES = {
     "dxmi_lpips_tap_fwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "dxmi_lpips_tap_bwd": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "dxmi_relu_mask_acc": (c_int, [c_void_p] * 4 + [c_int64, c_void_p]),
+    "dxmi_cd_huber_fwd": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int] + [c_float] * 3 + [c_int, c_int, c_void_p]),
+    "dxmi_cd_huber_bwd": (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int] + [c_float] * 3 + [c_int, c_int, c_void_p]),
     "dxmi_cd_lpips_images": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_cd_lpips_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),

@@ -5,6 +5,7 @@ Every function launches asynchronously on torch's current stream and allocates i
 torch.empty unless `out=` is given (pass `out=` inside hipGraph capture to keep addresses fixed).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -1139,6 +1140,52 @@ def cd_loss_bwd(g_loss, f_online, f_target, x_t, x_t2, indices, t_table, loss_no
     check(load().dxmi_cd_loss_bwd(_ptr(g_loss), _ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices), _ptr(t_table), S,
                                   _ptr(d), N, C, H, W, norm, float(sigma_data), float(sigma_min), int(bool(distillation)), sched,
                                   _stream()), "dxmi_cd_loss_bwd")
+    return d
+
+
+# the schedules of dxmi_cd_huber_fwd / _bwd: the DSM ones and DXMI_DSM_W_ICT (1 / (t - t2)), which only these two have the levels for
+HUBER_WEIGHT_SCHEDULES = dict(DSM_WEIGHT_SCHEDULES, ict=5)
+
+
+def _cd_huber_args(what, huber_c, weight_schedule):
+    if weight_schedule not in HUBER_WEIGHT_SCHEDULES:
+        raise NotImplementedError(f"weight schedule {weight_schedule!r}")
+    c = float(huber_c)
+    if not (math.isfinite(c) and c > 0):
+        raise _lib.DxmiError(f"{what}: huber_c must be finite and positive, got {huber_c!r}")
+    return c, HUBER_WEIGHT_SCHEDULES[weight_schedule]
+
+
+def cd_huber_fwd(f_online, f_target, x_t, x_t2, indices, t_table, huber_c, weight_schedule, sigma_data=0.5, sigma_min=0.002,
+                 distillation=False):
+    """-> (loss, ssq): ssq = sum((distiller - target)^2) per sample and the pseudo-Huber consistency loss
+    w ssq / (sqrt(ssq + huber_c^2) + huber_c), w the weight schedule ("ict": 1 / (t - t2)) (dxmi_cd_huber_fwd)."""
+    c, sched = _cd_huber_args("dxmi_cd_huber_fwd", huber_c, weight_schedule)
+    N, CHW, S = _cd_operands("dxmi_cd_huber_fwd", f_online, indices, t_table, same=(f_target, x_t, x_t2))
+    if CHW % 4:
+        raise _lib.DxmiError(f"dxmi_cd_huber_fwd: the elements per sample ({CHW}) must be a multiple of 4")
+    loss = torch.empty(N, dtype=torch.float32, device=f_online.device)
+    ssq = torch.empty_like(loss)
+    check(load().dxmi_cd_huber_fwd(_ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices), _ptr(t_table), S, _ptr(loss),
+                                   _ptr(ssq), N, CHW, c, float(sigma_data), float(sigma_min), int(bool(distillation)), sched, _stream()),
+          "dxmi_cd_huber_fwd")
+    return loss, ssq
+
+
+def cd_huber_bwd(g_loss, ssq, f_online, f_target, x_t, x_t2, indices, t_table, huber_c, weight_schedule, sigma_data=0.5,
+                 sigma_min=0.002, distillation=False):
+    """-> d(f_online) of the pseudo-Huber consistency loss for the device upstream gradient g_loss [N], with the forward's ssq
+    (dxmi_cd_huber_bwd)."""
+    c, sched = _cd_huber_args("dxmi_cd_huber_bwd", huber_c, weight_schedule)
+    if g_loss is None or ssq is None:
+        raise _lib.DxmiError("dxmi_cd_huber_bwd: no upstream gradient / no ssq of the forward")
+    N, CHW, S = _cd_operands("dxmi_cd_huber_bwd", f_online, indices, t_table, same=(f_target, x_t, x_t2), per_sample=(g_loss, ssq))
+    if CHW % 4:
+        raise _lib.DxmiError(f"dxmi_cd_huber_bwd: the elements per sample ({CHW}) must be a multiple of 4")
+    d = torch.empty_like(f_online)
+    check(load().dxmi_cd_huber_bwd(_ptr(g_loss), _ptr(ssq), _ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices),
+                                   _ptr(t_table), S, _ptr(d), N, CHW, c, float(sigma_data), float(sigma_min), int(bool(distillation)),
+                                   sched, _stream()), "dxmi_cd_huber_bwd")
     return d
 
 

@@ -23,6 +23,10 @@ sigma_min, sigma_max, rho)), uploaded once per device; the kernels gather t and 
 train mode with dropout > 0 takes the training forward with the dropout seeds the online forward just consumed (the reference restores
 the RNG state between the two so that they share masks, :192,200); otherwise forward_inference.
 
+loss_norm="pseudo-huber" with weight_schedule="ict" and an index_sampler (models.cm.resample.DiscreteLogNormalSampler) is improved
+consistency training (Song and Dhariwal 2023; not in the reference): the same node, ending in dxmi_cd_huber_fwd (loss and the summed
+squared difference, which the node keeps) and, backwards, dxmi_cd_huber_bwd.
+
 denoise() keeps the reference signature for any callable `model`; neither sampler calls it on the hot path.
 OpenAIDiffusion (the DxMI few-step sampler) uses the fused dxmi_edm_precond / dxmi_edm_step_fwd kernels.
 karras_sample builds its schedule ONCE on the host, in fp32 torch with the reference's expressions (tables
@@ -80,9 +84,16 @@ def get_weightings(weight_schedule, snrs, sigma_data):
         weightings = torch.clamp(snrs, min=1.0)
     elif weight_schedule == "uniform":
         weightings = torch.ones_like(snrs)
+    elif weight_schedule == "ict":
+        raise NotImplementedError(_ICT_PAIRING)
     else:
         raise NotImplementedError()
     return weightings
+
+
+_ICT_PAIRING = ("weight_schedule='ict' (1 / (t - t2)) needs both levels of a consistency pair: it is valid only in consistency_losses "
+                "with loss_norm='pseudo-huber'")
+HUBER_C_PER_SQRT_DIM = 0.00054      # Song and Dhariwal 2023: c = 0.00054 sqrt(d), d the dimension of an image
 
 
 def _hip_unet(model):
@@ -221,6 +232,11 @@ def _cd_loss(diffusion, net, target, teacher, teacher_diffusion, x_start, noise,
         x01, w = lpips_ops.cd_lpips_images(F, F_tg, x_t, x_t2, indices, tab, **kw)
         loss, acts = _lpips_forward(lp, x01, LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None, scale=w, keep=keep)
         return loss, (tape, kw, (indices, tab), (lp, acts, tuple(x_start.shape[2:])))
+    if diffusion.loss_norm == "pseudo-huber":      # the norm travels as huber_c; ssq goes first among the saved operands
+        del kw["loss_norm"]
+        kw["huber_c"] = diffusion._huber_c(x_start)
+        loss, ssq = ops.cd_huber_fwd(F, F_tg, x_t, x_t2, indices, tab, **kw)
+        return loss, (tape, kw, (ssq, F, F_tg, x_t, x_t2, indices, tab), None)
     return ops.cd_loss_fwd(F, F_tg, x_t, x_t2, indices, tab, **kw), (tape, kw, (F, F_tg, x_t, x_t2, indices, tab), None)
 
 
@@ -242,6 +258,8 @@ class _CDLossFn(torch.autograd.Function):
             from dxmi_hip import lpips_ops
             from .lpips import _lpips_backward
             dF = lpips_ops.cd_lpips_bwd(g.detach().float().contiguous(), _lpips_backward(*ctx.lpips, None), *ctx.ops, **ctx.kw)
+        elif "huber_c" in ctx.kw:
+            dF = ops.cd_huber_bwd(g.detach().float().contiguous(), *ctx.ops, **ctx.kw)
         else:
             dF = ops.cd_loss_bwd(g.detach().float().contiguous(), *ctx.ops, **ctx.kw)
         ctx.ops = ctx.lpips = None
@@ -336,12 +354,30 @@ class _PDLossFn(torch.autograd.Function):
 
 class KarrasDenoiser:
     def __init__(self, sigma_data: float = 0.5, sigma_max=80.0, sigma_min=0.002, rho=7.0, weight_schedule="karras",
-                 distillation=False, loss_norm="l2", lpips_loss=None):
+                 distillation=False, loss_norm="l2", lpips_loss=None, huber_c=None):
+        """huber_c: the constant of loss_norm="pseudo-huber"; None: 0.00054 sqrt(C H W) of the x_start of a call."""
         self.sigma_data, self.sigma_max, self.sigma_min = sigma_data, sigma_max, sigma_min
         self.weight_schedule, self.distillation, self.loss_norm, self.rho = weight_schedule, distillation, loss_norm, rho
         self.lpips_loss = lpips_loss
+        self.huber_c = huber_c
+        if huber_c is not None:
+            self._huber_c(None)
         if loss_norm == "lpips":
             self._lpips()
+
+    def _huber_c(self, x_start):
+        """The pseudo-Huber constant of a call on x_start (set on the object after construction too, so checked at every use)."""
+        c = self.huber_c
+        if c is None:
+            return HUBER_C_PER_SQRT_DIM * math.sqrt(x_start[0].numel())
+        c = float(c)
+        if not (math.isfinite(c) and c > 0):
+            raise ValueError(f"huber_c must be finite and > 0 (None: {HUBER_C_PER_SQRT_DIM} sqrt(C H W)), got {self.huber_c!r}")
+        return c
+
+    def _refuse_ict(self, where):
+        if self.weight_schedule == "ict":
+            raise NotImplementedError(f"{where}: {_ICT_PAIRING}")
 
     def _lpips(self):
         """The LPIPS object of loss_norm='lpips': `lpips_loss` if set, else the one the two environment variables name (built once)."""
@@ -377,6 +413,7 @@ class KarrasDenoiser:
             model_kwargs = {}
         if noise is None:
             noise = torch.randn_like(x_start)
+        self._refuse_ict("training_losses")
         net = _hip_unet(model)
         if net is not None and x_start.is_cuda:
             return self._training_losses_hip(net, x_start, sigmas, model_kwargs, noise)
@@ -417,11 +454,14 @@ class KarrasDenoiser:
         return {"xs_mse": xs, "mse": mse, "loss": mse}
 
     def consistency_losses(self, model, x_start, num_scales, model_kwargs=None, target_model=None, teacher_model=None,
-                           teacher_diffusion=None, noise=None, indices=None, generator=None):
+                           teacher_diffusion=None, noise=None, indices=None, generator=None, index_sampler=None):
         """Consistency distillation (teacher_model given: the Heun step through teacher_diffusion) or consistency training
         (teacher_model None: the Euler step with denoiser = x_start) loss per sample (reference :108-241) -> {"loss": [N]}.
         indices: the ladder index of every sample (the reference draws th.randint(0, num_scales - 1, (N,)) inside; drawn here,
-        from `generator` if given, when None)."""
+        from `generator` if given, when None; by index_sampler.sample_indices(num_scales, N, device, generator) where a sampler is
+        given, e.g. models.cm.resample.DiscreteLogNormalSampler).
+        loss_norm="pseudo-huber" (not in the reference: Song and Dhariwal 2023) is w s / (sqrt(s + c^2) + c) with s the SUM of the
+        squared difference over the image and c = huber_c; weight_schedule="ict", w = 1 / (t - t2), goes with this norm only."""
         if model_kwargs is None:
             model_kwargs = {}
         if noise is None:
@@ -430,11 +470,17 @@ class KarrasDenoiser:
             raise NotImplementedError("Must have a target model")
         if self.loss_norm == "lpips":        # set on the object after construction, as the reference's callers set it
             self._lpips()
-        if self.loss_norm not in ("l1", "l2", "l2-32", "lpips"):
+        if self.loss_norm not in ("l1", "l2", "l2-32", "lpips", "pseudo-huber"):
             raise ValueError(f"Unknown loss norm {self.loss_norm}")
+        if self.loss_norm == "pseudo-huber":
+            huber_c = self._huber_c(x_start)
+        else:
+            self._refuse_ict(f"consistency_losses with loss_norm={self.loss_norm!r}")
         if teacher_model is not None and teacher_diffusion is None:
             raise ValueError("consistency_losses: a teacher_model needs its teacher_diffusion")
         N = x_start.shape[0]
+        if indices is None and index_sampler is not None:
+            indices = index_sampler.sample_indices(num_scales, N, x_start.device, generator)
         if indices is None:
             if generator is not None:
                 indices = torch.randint(0, num_scales - 1, (N,), generator=generator, device=generator.device).to(x_start.device)
@@ -469,11 +515,15 @@ class KarrasDenoiser:
             torch.set_rng_state(dropout_state)
             distiller_target = self.denoise(target_model, x_t2, t2, **model_kwargs)[1].detach()
 
-        weights = get_weightings(self.weight_schedule, self.get_snr(t), self.sigma_data)
+        weights = 1 / (t - t2) if self.weight_schedule == "ict" else get_weightings(self.weight_schedule, self.get_snr(t), self.sigma_data)
         if self.loss_norm == "l1":
             diffs = torch.abs(distiller - distiller_target)
         elif self.loss_norm == "l2":
             diffs = (distiller - distiller_target) ** 2
+        elif self.loss_norm == "pseudo-huber":     # s / (sqrt(s + c^2) + c) = sqrt(s + c^2) - c, without its cancellation at s << c^2
+            diffs = (distiller - distiller_target) ** 2
+            s = diffs.flatten(1).sum(1)
+            return {"loss": s / (torch.sqrt(s + huber_c ** 2) + huber_c) * weights}
         elif self.loss_norm == "lpips":
             resize = LPIPS_SIZE if x_start.shape[-1] < LPIPS_RESIZE_BELOW else None
             return {"loss": self._lpips()((distiller + 1) / 2.0, (distiller_target + 1) / 2.0, resize=resize) * weights}
@@ -498,8 +548,9 @@ class KarrasDenoiser:
             raise NotImplementedError("progdist_losses: Must have a teacher model and its teacher_diffusion")
         if self.loss_norm == "lpips":        # set on the object after construction, as the reference's callers set it
             self._lpips()
-        if self.loss_norm not in ("l1", "l2", "lpips"):      # no l2-32 here: the reference's else branch (:328-329)
+        if self.loss_norm not in ("l1", "l2", "lpips"):      # no l2-32 here: the reference's else branch (:328-329); no pseudo-huber
             raise ValueError(f"Unknown loss norm {self.loss_norm}")
+        self._refuse_ict("progdist_losses")
         N = x_start.shape[0]
         if indices is None:
             if generator is not None:

@@ -65,7 +65,10 @@ def update_ema(target_params, source_params, rate=0.99, found_inf=None):
     if found_inf is not None:
         raise ValueError("update_ema: found_inf needs lists of contiguous CUDA fp32 tensors (the dxmi_ema_update launch series)")
     for targ, src in zip(targets, sources):
-        targ.detach().mul_(rate).add_(src, alpha=1 - rate)
+        if rate == 0:       # a copy, bit for bit: 0 * targ + src turns a source of -0 into +0 and a non-finite targ into NaN
+            targ.detach().copy_(src)
+        else:
+            targ.detach().mul_(rate).add_(src, alpha=1 - rate)
 
 
 def update_ema_rates(targets_per_rate, source_params, rates, found_inf=None):

@@ -63,10 +63,18 @@ def create_model(image_size, num_channels, num_res_blocks, channel_mult="", lear
 
 
 def create_ema_and_scales_fn(target_ema_mode, start_ema, scale_mode, start_scales, end_scales, total_steps, distill_steps_per_iter):
-    """step -> (target EMA rate: float, num_scales: int) for the reference's four (target_ema_mode, scale_mode) pairs (:161-219)."""
+    """step -> (target EMA rate: float, num_scales: int) for the reference's four (target_ema_mode, scale_mode) pairs (:161-219),
+    and ("fixed", "ict"): the doubling curriculum of improved consistency training (Song and Dhariwal 2023, section 3.4),
+    N(k) = min(start_scales 2^(k // K'), end_scales) + 1 levels with K' = total_steps // (floor(log2(end_scales // start_scales)) + 1),
+    at the fixed rate start_ema (0 there: the target is the stop-gradient student)."""
     pair = (target_ema_mode, scale_mode)
-    if pair not in (("fixed", "fixed"), ("fixed", "progressive"), ("adaptive", "progressive"), ("fixed", "progdist")):
+    if pair not in (("fixed", "fixed"), ("fixed", "progressive"), ("adaptive", "progressive"), ("fixed", "progdist"), ("fixed", "ict")):
         raise NotImplementedError(f"target_ema_mode={target_ema_mode!r} with scale_mode={scale_mode!r}")
+    if pair == ("fixed", "ict"):
+        if not (int(start_scales) >= 1 and int(end_scales) >= int(start_scales)):
+            raise ValueError(f"scale_mode='ict': 1 <= start_scales <= end_scales is needed, got {start_scales}, {end_scales}")
+        doublings = int(np.floor(np.log2(int(end_scales) // int(start_scales))))
+        k_prime = max(1, int(total_steps) // (doublings + 1))
 
     def progressive_scales(step):
         scales = np.ceil(np.sqrt((step / total_steps) * ((end_scales + 1) ** 2 - start_scales ** 2) + start_scales ** 2) - 1).astype(np.int32)
@@ -77,6 +85,9 @@ def create_ema_and_scales_fn(target_ema_mode, start_ema, scale_mode, start_scale
             target_ema, scales = start_ema, start_scales
         elif pair == ("fixed", "progressive"):
             target_ema, scales = start_ema, progressive_scales(step) + 1
+        elif pair == ("fixed", "ict"):      # python ints: 2 ** (step // K') has no upper bound in a long run
+            target_ema = start_ema
+            scales = (int(end_scales) if int(step) // k_prime > doublings else min(int(start_scales) << (int(step) // k_prime), int(end_scales))) + 1
         elif pair == ("adaptive", "progressive"):
             scales = progressive_scales(step)
             c = -np.log(start_ema) * start_scales

@@ -16,7 +16,8 @@ The reference's bookkeeping is kept as it is: the step counter advances, and the
 CMTrainLoop (reference :267-566) trains a consistency model by distillation from an EDM teacher or by consistency training, with
 KarrasDenoiser.consistency_losses.  It keeps the reference's own bookkeeping, which differs from TrainLoop's: `step` and
 `global_step` advance AFTER the EMA updates of a step the optimiser took, the target network follows the masters by an EMA whose
-rate comes from ema_scale_fn(global_step) (one dxmi_ema_update launch series on the device), checkpoints are named by
+rate comes from ema_scale_fn(global_step) (one dxmi_ema_update launch series on the device; rate 0, the stop-gradient student of
+improved consistency training, is a copy bit for bit), checkpoints are named by
 global_step, and target_model%06d.pt (plus, with the first save, teacher_model%06d.pt) is written next to TrainLoop's files and
 read back on resume (a checkpoint later than the first finds the teacher under the first save's name in the same directory;
 where there is none, the teacher the caller passed is kept).  An fp16 overflow step skips the target EMA on the host, from the
@@ -344,8 +345,10 @@ class TrainLoop:
 
 
 class CMTrainLoop(TrainLoop):
-    def __init__(self, *, target_model, teacher_model, teacher_diffusion, training_mode, ema_scale_fn, total_training_steps, **kwargs):
-        """kwargs: TrainLoop's, use_graph among them."""
+    def __init__(self, *, target_model, teacher_model, teacher_diffusion, training_mode, ema_scale_fn, total_training_steps,
+                 index_sampler=None, **kwargs):
+        """kwargs: TrainLoop's, use_graph among them.  index_sampler: what draws the ladder index of every sample in
+        consistency_losses (models.cm.resample.DiscreteLogNormalSampler); None: the loss's own uniform randint."""
         progdist = training_mode == "progdist"
         if training_mode not in ("consistency_distillation", "consistency_training", "progdist"):
             raise ValueError(f"Unknown training mode {training_mode}")
@@ -360,8 +363,11 @@ class CMTrainLoop(TrainLoop):
             raise NotImplementedError("Must have a target model")
         if training_mode == "consistency_distillation" and (teacher_model is None or teacher_diffusion is None):
             raise ValueError("CMTrainLoop: consistency_distillation needs teacher_model and teacher_diffusion")
+        if index_sampler is not None and progdist:
+            raise NotImplementedError("CMTrainLoop: index_sampler belongs to consistency_losses; progdist_losses draws its own indices")
         if kwargs.get("schedule_sampler") is None:      # the losses draw their own levels: only `weights` is used
             kwargs["schedule_sampler"] = _UnitWeights()
+        self.index_sampler = index_sampler
         super().__init__(**kwargs)
         self.training_mode, self.ema_scale_fn = training_mode, ema_scale_fn
         self.target_model, self.teacher_model, self.teacher_diffusion = target_model, teacher_model, teacher_diffusion
@@ -499,10 +505,12 @@ class CMTrainLoop(TrainLoop):
             from .karras_diffusion import cd_levels
             # held for as long as the graph lives: the graph has the table's address, the cache of level sets may be emptied
             self._cap_table = cd_levels(key[1], d.sigma_min, d.sigma_max, d.rho).device_table(self.device)
+        if self.index_sampler is not None and hasattr(self.index_sampler, "cdf"):      # its CDF over the levels of this key, likewise
+            self._cap_cdf = self.index_sampler.cdf(key[1]).device_table(self.device)
 
     def _on_graph_drop(self):
         super()._on_graph_drop()
-        self._cap_table = None
+        self._cap_table = self._cap_cdf = None
 
     def _update_target_ema(self, found_inf=None):
         target_ema, _ = self.ema_scale_fn(self.global_step)
@@ -540,7 +548,8 @@ class CMTrainLoop(TrainLoop):
             losses = self.diffusion.consistency_losses(self.ddp_model, micro, num_scales, target_model=self.target_model,
                                                        teacher_model=self.teacher_model if distill else None,
                                                        teacher_diffusion=self.teacher_diffusion if distill else None,
-                                                       model_kwargs=micro_cond)
+                                                       model_kwargs=micro_cond,
+                                                       **({} if self.index_sampler is None else {"index_sampler": self.index_sampler}))
             loss = (losses["loss"] * weights).mean()
             self._log_loss_dict({k: v * weights for k, v in losses.items()})
             self.mp_trainer.backward(loss)

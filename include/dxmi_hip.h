@@ -570,6 +570,9 @@ int dxmi_dropout_bf16_dev(const void* x, void* y, int64_t n, float p, const uint
 #define DXMI_DSM_W_KARRAS     2   /* snrs + 1 / sigma_data^2 */
 #define DXMI_DSM_W_TRUNC_SNR  3   /* clamp(snrs, min=1) */
 #define DXMI_DSM_W_UNIFORM    4   /* 1 */
+#define DXMI_DSM_W_ICT        5   /* 1 / (t - t2), t = t_table[index], t2 = t_table[index + 1] (Song and Dhariwal 2023, "Improved
+                                   * Techniques for Training Consistency Models"): dxmi_cd_huber_fwd / _bwd ONLY, which have both
+                                   * levels; every other entry point refuses it */
 int dxmi_edm_dsm_prep(const float* x_start, const float* noise, const float* sigma, float* x_in, float* t_out, int32_t N,
                       int32_t CHW, float sigma_data, void* stream);
 int dxmi_edm_dsm_loss_fwd(const float* model_out, const float* x_start, const float* noise, const float* sigma, float* xs_mse,
@@ -597,7 +600,8 @@ int dxmi_ddpm_loss_bwd(const float* g_loss, const float* eps_pred, const float* 
 /* update_ema (models/cm/nn.py:57-67) for up to DXMI_EMA_MAX_RATES rates at once (TrainLoop._update_ema, train_util.py:190-193):
  * ema[k * count + i] = rates[k] ema[k * count + i] + (1 - rates[k]) src[i] over fp32 DEVICE tensors of numel[i] elements, as
  * torch's mul_(rate).add_(src, alpha=1-rate) (rate and 1-rate formed in double, rounded to fp32 once; the add is one fused
- * multiply-add, as ATen's).  The source is read once for all rates.  found_inf: DEVICE fp32 flag or NULL; when it is non-zero the
+ * multiply-add, as ATen's).  A rate of exactly 0 (the target network of improved consistency training) is a copy of src, bit for
+ * bit (0 * ema + src would turn a src of -0 into +0 and a non-finite ema into NaN).  The source is read once for all rates.  found_inf: DEVICE fp32 flag or NULL; when it is non-zero the
  * launch leaves every EMA tensor untouched (the step was skipped on overflow), with no host sync. */
 #define DXMI_EMA_MAX_RATES 4
 int dxmi_ema_update(void* const* ema, const void* const* src, const int64_t* numel, int32_t count, int32_t n_rates,
@@ -624,7 +628,13 @@ int dxmi_ema_update(void* const* ema, const void* const* src, const int64_t* num
  *   32 x 32 by F.interpolate(size=32, mode="bilinear") (L2_32: align_corners False, no antialias, two taps per axis);
  *   loss[n] = mean_flat(diffs) * get_weightings(weight_schedule, t^-2) (DXMI_DSM_W_*).  Sums in a fixed order (bitwise reproducible).
  * dxmi_cd_loss_bwd: d_f_online of loss for the DEVICE [N] upstream gradient g_loss: autograd's nodes in its order; L1 uses
- *   sign with sign(0) = 0 (th.abs), L2_32 the transpose of the resize. */
+ *   sign with sign(0) = 0 (th.abs), L2_32 the transpose of the resize.
+ * dxmi_cd_huber_fwd: the pseudo-Huber metric of improved consistency training on the same difference df = distiller - target
+ *   (the scalings of dxmi_cd_loss_fwd): ssq[n] = sum(df^2) over the image (a sum, not mean_flat; the fixed order of the L2 norm,
+ *   bitwise reproducible) and loss[n] = w ssq / (sqrt(ssq + c^2) + c), c = huber_c > 0.  That form equals sqrt(ssq + c^2) - c and
+ *   keeps its digits at ssq << c^2, where the subtraction loses them.  w: DXMI_DSM_W_* including DXMI_DSM_W_ICT.
+ * dxmi_cd_huber_bwd: d_f_online = (g_loss[n] w / sqrt(ssq[n] + c^2)) df c_out(t) for the DEVICE [N] upstream gradient g_loss; ssq
+ *   is the forward's (read, not recomputed).  Neither reads anything back. */
 #define DXMI_CD_EULER_X0   0
 #define DXMI_CD_HEUN_PRED  1
 #define DXMI_CD_HEUN_CORR  2
@@ -645,6 +655,13 @@ int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, const float* f_
                      const int64_t* indices, const float* t_table, int32_t num_scales, float* d_f_online, int32_t N, int32_t C,
                      int32_t H, int32_t W, int32_t loss_norm, float sigma_data, float sigma_min, int32_t distillation,
                      int32_t weight_schedule, void* stream);
+int dxmi_cd_huber_fwd(const float* f_online, const float* f_target, const float* x_t, const float* x_t2, const int64_t* indices,
+                      const float* t_table, int32_t num_scales, float* loss, float* ssq, int32_t N, int32_t CHW, float huber_c,
+                      float sigma_data, float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream);
+int dxmi_cd_huber_bwd(const float* g_loss, const float* ssq, const float* f_online, const float* f_target, const float* x_t,
+                      const float* x_t2, const int64_t* indices, const float* t_table, int32_t num_scales, float* d_f_online,
+                      int32_t N, int32_t CHW, float huber_c, float sigma_data, float sigma_min, int32_t distillation,
+                      int32_t weight_schedule, void* stream);
 
 /* Progressive distillation loss (KarrasDenoiser.progdist_losses, models/cm/karras_diffusion.py:243-335), the launches between its
  * network evaluations; the first, x_t and the inputs at t (:300, denoise :345-349), is dxmi_cd_prep on the first num_scales + 1

@@ -1,7 +1,7 @@
 """Time a consistency-distillation (CD) and a consistency-training (CT) step of the full-size ImageNet-64 U-Net (295.9 M
 parameters, synthetic weights) against the sum of their parts, on one GPU, in one process.
 
-    python tools/cm_train_time.py [--batch 16] [--reps 3] [--warmup 2] [--leg_timeout 120]
+    python tools/cm_train_time.py [--batch 16] [--reps 3] [--warmup 2] [--leg_timeout 120] [--launches_only]
 
 Legs, alternating, median of --reps after --warmup rounds (device events around each leg, a synchronise at its end):
   cd    one CMTrainLoop.run_step, consistency_distillation: online forward + backward, two teacher and one target evaluation
@@ -73,6 +73,11 @@ def launch_times(ops, B, dev, limit):
     for norm in ("l1", "l2", "l2-32"):
         cases[f"loss_fwd_{norm}"] = (16, lambda norm=norm: ops.cd_loss_fwd(Fs, Ft, x_t, x_t2, idx, tab, norm, "uniform", distillation=True))
         cases[f"loss_bwd_{norm}"] = (20, lambda norm=norm: ops.cd_loss_bwd(g, Fs, Ft, x_t, x_t2, idx, tab, norm, "uniform", distillation=True))
+    # the pseudo-Huber pair of improved consistency training: the l2 stream plus one [B] vector (ssq) written / read
+    hc = 0.00054 * (3 * 64 * 64) ** 0.5
+    _, ssq = ops.cd_huber_fwd(Fs, Ft, x_t, x_t2, idx, tab, hc, "ict", distillation=True)
+    cases["huber_fwd"] = (16, lambda: ops.cd_huber_fwd(Fs, Ft, x_t, x_t2, idx, tab, hc, "ict", distillation=True))
+    cases["huber_bwd"] = (20, lambda: ops.cd_huber_bwd(g, ssq, Fs, Ft, x_t, x_t2, idx, tab, hc, "ict", distillation=True))
     out = {}
     for k, (bytes_per, fn) in cases.items():
         timed(fn, limit, 20)
@@ -86,8 +91,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--leg_timeout", type=int, default=120)
+    ap.add_argument("--launches_only", action="store_true", help="skip the step legs: only the per-launch times")
     args = ap.parse_args()
     from dxmi_hip import ops
+    if args.launches_only:
+        ops.device_check()
+        print(json.dumps({"launches_us": launch_times(ops, args.batch, "cuda:0", args.leg_timeout)}), flush=True)
+        return
     from models.cm.resample import LogNormalSampler
     from models.cm.script_util import create_ema_and_scales_fn, create_model_and_diffusion
     from models.cm.train_util import CMTrainLoop, TrainLoop
