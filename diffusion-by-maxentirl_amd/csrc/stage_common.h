@@ -1,4 +1,5 @@
-// The stage launch of the DDPM teacher's samplers (csrc/ddpm_sample.hip, csrc/dpm_sample.hip), written once: ONE launch between two
+// The stage launch of the DDPM teacher's samplers (csrc/ddpm_sample.hip, csrc/dpm_sample.hip) and of DPM-Solver++ on the EDM nets
+// (csrc/edm_dpm_sample.hip), written once: ONE launch between two
 // network evaluations finishes a transition in place (x'), writes the next evaluation's time and, on the row flagged last, the
 // clamped sample.  Every per-transition scalar is read from one fp32 table row built on the host, the last-step behaviour
 // included, and the row number, the draw number and the seed can be read from a small device block: one captured launch serves
@@ -11,6 +12,10 @@
 //   HIST                                how many earlier predictions an element reads (0 or 2), kept in a ring of HIST + 1 slots
 //                                       fp32 [HIST + 1][N][CHW]: this row's goes to slot row % (HIST + 1), the one j + 1 rows back
 //                                       comes from slot (row - 1 - j) % (HIST + 1).  HIST == 0: no pointer, load or register
+//   XIN                                 whether the launch has a second output stream: the next evaluation's preconditioned input
+//                                       x_in = K[CIN_NEXT] x', written on every row that is not last (and, NaN, on a poisoned one); the
+//                                       policy then names the columns CIN, CIN_NEXT and XSCALE too, and FIRST scales x in place by
+//                                       K[XSCALE] and writes x_in = K[CIN] x next to t_out.  false: no pointer, product or store
 //   StageCoef                           the row's scalars; members s (the noise scale) and noisy, and with HIST rd[HIST]: whether
 //                                       slot j is read (a slot never written holds anything, and 0 * NaN would be NaN)
 //   fill(r, ok, flags)                  StageCoef from the row r; !ok: the row is poisoned, what must be NaN and what must be 0
@@ -46,13 +51,39 @@ __device__ __forceinline__ void store4(float* p, f32x4 v) {
     else *reinterpret_cast<f32x4_a4*>(p) = v;
 }
 
-// the body of <sampler>_stage_kernel<ALIGNED>; hist and N are used with P::HIST alone
+// FIRST of a policy with XIN: x *= K[XSCALE] in place (x_T = randn * sigma_max), x_in = K[CIN] x; a poisoned row gives NaN in both
+template <class P, bool ALIGNED>
+__device__ __forceinline__ void stage_first_xin(const float* __restrict__ r, bool ok, float* x, float* __restrict__ x_in, size_t base,
+                                                int CHW) {
+    const float nan = __builtin_nanf("");
+    const float scale = ok ? r[P::XSCALE] : nan, c_in = ok ? r[P::CIN] : nan;
+    const int n4 = CHW / 4, rem = CHW % 4;
+    for (int i = blockIdx.x * STAGE_BLOCK + threadIdx.x; i < n4; i += gridDim.x * STAGE_BLOCK) {
+        const size_t o = base + (size_t)i * 4;
+        f32x4 v = load4<ALIGNED>(x + o), w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = v[e] * scale, w[e] = c_in * v[e];
+        store4<ALIGNED>(x + o, v);
+        store4<ALIGNED>(x_in + o, w);
+    }
+    if (rem && blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int e = 0; e < rem; ++e) {
+            const size_t o = base + (size_t)n4 * 4 + e;
+            const float v = x[o] * scale;
+            x[o] = v;
+            x_in[o] = c_in * v;
+        }
+    }
+}
+
+// the body of <sampler>_stage_kernel<ALIGNED>; hist and N are used with P::HIST alone, x_in with P::XIN alone
 template <class P, bool ALIGNED>
 __device__ __forceinline__ void stage_body(int first, const float* __restrict__ tab, int rows, const int32_t* __restrict__ ctl,
                                            int row_v, uint32_t draw_v, uint32_t k0_v, uint32_t k1_v, float* x,
                                            const float* __restrict__ eps, const float* __restrict__ z,
                                            const int64_t* __restrict__ sample_index, float* hist, float* __restrict__ t_out,
-                                           float* __restrict__ out, float* __restrict__ pred, int N, int CHW) {
+                                           float* __restrict__ out, float* __restrict__ pred, int N, int CHW,
+                                           float* __restrict__ x_in = nullptr) {
     constexpr int H = P::HIST, HD = H ? H : 1;
     const int n = blockIdx.y;
     const int row = ctl ? ctl[0] : row_v;
@@ -63,6 +94,7 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
     const float nan = __builtin_nanf("");
     if (first) {
         if (blockIdx.x == 0 && threadIdx.x == 0) t_out[n] = ok ? r[P::T] : nan;
+        if constexpr (P::XIN) stage_first_xin<P, ALIGNED>(r, ok, x, x_in, (size_t)n * CHW, CHW);
         return;
     }
     const int flags = ok ? (int)r[P::FLAGS] : 0;
@@ -77,6 +109,9 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
         i_lo = (uint32_t)index, i_hi = (uint32_t)(index >> 32);
     }
     const size_t base = (size_t)n * CHW;
+    float c_next = 0.f;
+    bool feed = false;                                       // whether x_in is written: not on the last row, where nothing follows
+    if constexpr (P::XIN) c_next = ok ? r[P::CIN_NEXT] : nan, feed = x_in && (!last || !ok);
     float* h0 = nullptr;
     const float* hp[HD] = {};
     if constexpr (H > 0) {
@@ -124,6 +159,14 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
             store4<ALIGNED>(x + o, xn);
             if constexpr (H > 0) store4<ALIGNED>(h0 + o, pv);
             if (pred) store4<ALIGNED>(pred + o, pv);
+            if constexpr (P::XIN) {
+                if (feed) {
+                    f32x4 xi;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xi[e] = c_next * xn[e];
+                    store4<ALIGNED>(x_in + o, xi);
+                }
+            }
             if (last) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xn[e] = clamp1(xn[e]);
@@ -147,6 +190,9 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
             x[o] = xn;
             if constexpr (H > 0) h0[o] = p;
             if (pred) pred[o] = p;
+            if constexpr (P::XIN) {
+                if (feed) x_in[o] = c_next * xn;
+            }
             if (last) out[o] = clamp1(xn);
         }
     }

@@ -2071,20 +2071,34 @@ def edm_step_indexed(x, model_out, sample_index, sigma, sigma_down, sigma_up, si
     return sample, mean
 
 
-def _sampler_stage(name, cols, mode, first, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out, pred_xstart, hist=()):
-    """The checks and the call of the stage launches of the DDPM teacher's samplers (csrc/stage_common.h).  cols: the table's row
-    length; first: the sampler's FIRST mode; hist: () for a sampler without a history, else (the tensor or None,)."""
-    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, *hist, out, pred_xstart)
+def _sampler_stage(name, cols, mode, first, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out, pred_xstart, hist=(),
+                   x_in=()):
+    """The checks and the call of the stage launches of csrc/stage_common.h.  cols: the table's row length; first: the sampler's
+    FIRST mode; hist: () for a sampler without a history, else (the tensor or None,); x_in: () for a sampler without the second
+    output stream, else (the tensor or None,): FIRST then takes x and x_in, and a transition's x_in may be None on the table's last
+    row given by value."""
+    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, *hist, *x_in, out, pred_xstart)
     if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == cols and tab.shape[0] >= 1):
         raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {cols}], got {tab.dtype} {tuple(tab.shape)}")
     if not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
         raise _lib.DxmiError(f"{name}: t_out must be a contiguous fp32 [N]")
     N = t_out.numel()
     chw = 1
+    if mode == first and x_in:
+        if x is None or x_in[0] is None:
+            raise _lib.DxmiError(f"{name}: FIRST scales x and writes x_in: both are needed")
+        for v in (x, x_in[0]):
+            if not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
+                raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
+        if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
+            raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} samples, got {tuple(x.shape)}")
+        chw = x.numel() // N
     if mode != first:
         if x is None or eps is None or out is None or any(h is None for h in hist):
             raise _lib.DxmiError(f"{name}: a transition needs x, eps{', hist' if hist else ''} and out")
-        for v in (x, eps, z, out, pred_xstart):
+        if x_in and x_in[0] is None and (ctl is not None or int(row) != tab.shape[0] - 1):
+            raise _lib.DxmiError(f"{name}: x_in is needed on every row but the table's last, given by value")
+        for v in (x, eps, z, out, pred_xstart, *x_in):
             if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
                 raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
         if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
@@ -2099,8 +2113,8 @@ def _sampler_stage(name, cols, mode, first, tab, t_out, row, x, eps, z, sample_i
     if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
         raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
     check(getattr(load(), name)(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF,
-                                int(seed) & _U64, _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), *(_ptr(h) for h in hist), _ptr(t_out),
-                                _ptr(out), _ptr(pred_xstart), N, chw, _stream()), name)
+                                int(seed) & _U64, _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), *(_ptr(h) for h in hist),
+                                *(_ptr(v) for v in x_in), _ptr(t_out), _ptr(out), _ptr(pred_xstart), N, chw, _stream()), name)
 
 
 # dxmi_ddpm_stage modes, table columns and flags (include/dxmi_hip.h)
@@ -2138,6 +2152,25 @@ def dpm_stage(mode, tab, t_out, row=0, x=None, eps=None, z=None, sample_index=No
     seed: a captured launch then serves every row.  DPM_FIRST writes t_out of `row` only."""
     _sampler_stage("dxmi_dpm_stage", MT_COLS, mode, DPM_FIRST, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out,
                    pred_xstart, hist=(hist,))
+
+
+# dxmi_edm_dpm_stage modes, table columns and flags (include/dxmi_hip.h): columns 0-10 are MT_*'s with c_skip, c_out for A, B
+EDM_DPM_FIRST, EDM_DPM_STEP = range(2)
+(ET_T, ET_T_NEXT, ET_CX, ET_W0, ET_W1, ET_W2, ET_S, ET_CSKIP, ET_COUT, ET_FLAGS, ET_ORDER, ET_CIN, ET_CIN_NEXT, ET_XSCALE,
+ ET_SIGMA) = range(15)
+ET_COLS = 16
+ET_FLAG_CLIP, ET_FLAG_LAST = 1, 2
+
+
+def edm_dpm_stage(mode, tab, t_out, row=0, x=None, model_out=None, z=None, sample_index=None, seed=0, draw=0, ctl=None, hist=None,
+                  x_in=None, out=None, pred_xstart=None):
+    """One multistep DPM-Solver++ transition of the EDM nets between two network evaluations (dxmi_edm_dpm_stage): model_out is
+    turned into the data prediction by the Karras preconditioning and filed in hist[row % 3] (hist: fp32 [3, *x.shape]), x is
+    updated in place, x_in takes the next evaluation's input c_in x' on every row that is not last, t_out [N] its time, out the
+    clamped sample on the row flagged last.  tab: fp32 [rows, ET_COLS] on the device.  Noise and ctl as dpm_stage.
+    EDM_DPM_FIRST scales x by the row's XSCALE in place and writes x_in = c_in x and t_out of `row`."""
+    _sampler_stage("dxmi_edm_dpm_stage", ET_COLS, mode, EDM_DPM_FIRST, tab, t_out, row, x, model_out, z, sample_index, seed, draw, ctl,
+                   out, pred_xstart, hist=(hist,), x_in=(x_in,))
 
 
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)

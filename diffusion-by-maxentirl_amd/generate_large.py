@@ -17,6 +17,11 @@ reference models/cm/karras_diffusion.py:354-420): `--karras_steps` (40), `--rho`
 `--s_noise`.  Weights: `--pretrained [PATH]` loads a plain U-Net state dict (PATH, or the config's training.pretrained_path),
 otherwise `sampler.pth` from --log_dir without its `log_betas` entry.  Class-conditional nets draw one label per image.
 
+`--karras_sampler {dpmpp,sde-dpmpp}` samples the EDM teacher with multistep DPM-Solver++ (models.cm.dpm_sample.edm_dpm_sample; the
+ODE solver and its SDE variant): NFE = `--karras_steps` (default 10), `--solver_order` (2; 3 with dpmpp only), `--solver_type
+midpoint|exact`, `--skip_type karras|logsnr` (`--rho` with the karras ladder only), `--no_lower_order_final`; `--pretrained`,
+`--generator`, `--seed` and `--no_graph` as above.  The churn flags do not apply.
+
 `--cm_sampler {onestep,multistep}` samples a consistency-distilled model the same way (karras_sample's onestep /
 multistep branch, reference :644-683): the diffusion is built with distillation=True; `--ts 0,22,39` (required for
 multistep), `--cm_steps` (40); `--pretrained [PATH]` as above.  It excludes --karras_sampler and --guidance_scale.
@@ -49,6 +54,9 @@ from utils import mkdir_p, print0, to_uint8_nhwc, write_png_batch
 
 KARRAS_FLAGS = ("karras_steps", "rho", "s_churn", "s_tmin", "s_tmax", "s_noise", "pretrained")
 CM_FLAGS = ("ts", "cm_steps")
+DPM_SAMPLERS = {"dpmpp": "dpmsolver++", "sde-dpmpp": "sde-dpmsolver++"}
+DPM_FLAGS = ("solver_order", "solver_type", "skip_type", "no_lower_order_final")
+CHURN_FLAGS = ("s_churn", "s_tmin", "s_tmax", "s_noise")
 
 
 def build_parser():
@@ -66,9 +74,19 @@ def build_parser():
     ap.add_argument("--synthetic", type=str, default=None, help="builtin config name, e.g. imagenet64_T10 (random weights)")
     ap.add_argument("--no_graph", action="store_true", help="issue every launch from python instead of replaying the T-step loop of a "
                                                            "batch as one hipGraph (dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
-    ap.add_argument("--karras_sampler", type=str, default=None, choices=("heun", "dpm", "euler", "ancestral", "progdist"),
-                    help="sample the EDM teacher with this Karras sampler instead of the DxMI sampler")
-    ap.add_argument("--karras_steps", type=int, default=None, help="Karras sampler steps (default 40)")
+    ap.add_argument("--karras_sampler", type=str, default=None, choices=("heun", "dpm", "euler", "ancestral", "progdist", "dpmpp", "sde-dpmpp"),
+                    help="sample the EDM teacher with this Karras sampler, or with DPM-Solver++ (dpmpp: the ODE solver, sde-dpmpp: "
+                         "its SDE variant), instead of the DxMI sampler")
+    ap.add_argument("--karras_steps", type=int, default=None, help="Karras sampler steps (default 40; dpmpp / sde-dpmpp: the number "
+                                                                   "of network evaluations, default 10)")
+    ap.add_argument("--solver_order", type=int, default=None, choices=(1, 2, 3), help="dpmpp / sde-dpmpp: the solver's order (default 2; "
+                                                                                      "3 with dpmpp only)")
+    ap.add_argument("--solver_type", type=str, default=None, choices=("midpoint", "exact"), help="dpmpp / sde-dpmpp: the second-order rows "
+                                                                                                "(default midpoint)")
+    ap.add_argument("--skip_type", type=str, default=None, choices=("karras", "logsnr"), help="dpmpp / sde-dpmpp: the sigma ladder "
+                                                                                             "(default karras)")
+    ap.add_argument("--no_lower_order_final", action="store_const", const=True, default=None,
+                    help="dpmpp / sde-dpmpp: keep the full order on the last rows")
     ap.add_argument("--rho", type=float, default=None, help="Karras schedule rho (default 7.0)")
     ap.add_argument("--s_churn", type=float, default=None, help="Karras churn (default 0)")
     ap.add_argument("--s_tmin", type=float, default=None, help="churn window lower end (default 0)")
@@ -103,6 +121,10 @@ def parse_args(argv=None):
         ap.error("--sampler_generator is the DxMI sampler's: with --karras_sampler / --cm_sampler use --generator")
     if args.generator != "dummy" and args.cm_sampler is None and args.karras_sampler is None:
         ap.error("--generator determ / determ-indiv only applies with --karras_sampler or --cm_sampler")
+    if args.karras_sampler not in DPM_SAMPLERS:
+        given = [f"--{k}" for k in DPM_FLAGS if getattr(args, k) is not None]
+        if given:
+            ap.error(f"{', '.join(given)} only apply with --karras_sampler dpmpp / sde-dpmpp")
     if args.cm_sampler is not None:
         return parse_cm_args(ap, args), unknown
     given = [f"--{k}" for k in CM_FLAGS if getattr(args, k) is not None]
@@ -115,6 +137,8 @@ def parse_args(argv=None):
     else:
         if args.guidance_scale is not None:
             ap.error("--karras_sampler samples the EDM teacher: it cannot be combined with --guidance_scale")
+        if args.karras_sampler in DPM_SAMPLERS:
+            return parse_dpm_args(ap, args), unknown
         for k, v in (("karras_steps", 40), ("rho", 7.0), ("s_churn", 0.0), ("s_tmin", 0.0), ("s_tmax", float("inf")),
                      ("s_noise", 1.0)):
             if getattr(args, k) is None:
@@ -122,6 +146,26 @@ def parse_args(argv=None):
         if args.karras_steps < 1:
             ap.error("--karras_steps must be >= 1")
     return args, unknown
+
+
+def parse_dpm_args(ap, args):
+    """--karras_sampler dpmpp / sde-dpmpp: the defaults of the solver's flags and what they exclude."""
+    given = [f"--{k}" for k in CHURN_FLAGS if getattr(args, k) is not None]
+    if given:
+        ap.error(f"{', '.join(given)}: --karras_sampler {args.karras_sampler} has no churn")
+    for k, v in (("karras_steps", 10), ("solver_order", 2), ("solver_type", "midpoint"), ("skip_type", "karras")):
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+    args.no_lower_order_final = bool(args.no_lower_order_final)
+    if args.karras_steps < 2:
+        ap.error(f"--karras_steps must be >= 2 with --karras_sampler {args.karras_sampler}")
+    if args.karras_sampler == "sde-dpmpp" and args.solver_order == 3:
+        ap.error("--karras_sampler sde-dpmpp is defined for --solver_order 1 and 2")
+    if args.rho is not None and args.skip_type == "logsnr":
+        ap.error("--rho shapes the karras ladder: it does not apply with --skip_type logsnr")
+    if args.rho is None:
+        args.rho = 7.0
+    return args
 
 
 def parse_cm_args(ap, args):
@@ -293,6 +337,7 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
     consistency-distilled model through the same path, with distillation=True."""
     from dxmi_hip import graph as hip_graph
     from dxmi_hip import ops
+    from models.cm.dpm_sample import edm_dpm_sample
     from models.cm.karras_diffusion import cm_nfe, karras_nfe, karras_sample, progdist_sample
     from utils import ImageWriter
     path, kind = resolve_weights(args, cfg)
@@ -315,6 +360,10 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         diffusion.distillation = True          # boundary-condition scalings (the diffusion block's distillation: True)
         sampler, steps, nfe = args.cm_sampler, args.cm_steps, cm_nfe(args.cm_sampler, args.ts)
         extra = dict(ts=args.ts)
+    elif args.karras_sampler in DPM_SAMPLERS:      # one evaluation per step
+        sampler, steps, nfe = args.karras_sampler, args.karras_steps, args.karras_steps
+        extra = dict(algorithm=DPM_SAMPLERS[sampler], order=args.solver_order, solver_type=args.solver_type, skip_type=args.skip_type,
+                     lower_order_final=not args.no_lower_order_final, rho=args.rho)
     else:
         sampler, steps, nfe = args.karras_sampler, args.karras_steps, karras_nfe(args.karras_sampler, args.karras_steps)
         extra = dict(rho=args.rho, s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax, s_noise=args.s_noise)
@@ -335,7 +384,10 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         if unet.num_classes is not None:        # one uniform label per image, as OpenAIDiffusion._sample draws them
             kw["y"] = (torch.randint(0, unet.num_classes, (args.batchsize,), device=device) if generator is None else
                        generator.randint(0, unet.num_classes, (args.batchsize,), device=device))
-        if sampler == "progdist":               # its own entry point: karras_sample keeps refusing this sampler
+        if sampler in DPM_SAMPLERS:
+            sample = edm_dpm_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
+                                    sigma_max=diffusion.sigma_max, use_graph=use_graph, generator=generator, **extra)
+        elif sampler == "progdist":             # its own entry point: karras_sample keeps refusing this sampler
             sample = progdist_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
                                      sigma_max=diffusion.sigma_max, rho=args.rho, use_graph=use_graph, generator=generator)
         else:
@@ -351,7 +403,8 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
     dt = time.perf_counter() - t0
     print0(f"generated {n_batches * args.batchsize} images/rank x {world} ranks, "
            f"{n_batches * args.batchsize / max(dt, 1e-9):.1f} images/s/rank, {nfe} NFE/image "
-           f"({sampler}, {steps} steps{'' if args.cm_sampler is None or args.ts is None else ', ts ' + str(list(args.ts))})")
+           f"({sampler}, {steps} steps{', order ' + str(args.solver_order) + ', ' + args.skip_type if sampler in DPM_SAMPLERS else ''}"
+           f"{'' if args.cm_sampler is None or args.ts is None else ', ts ' + str(list(args.ts))})")
     if not args.skip_fid:
         finish(args, l_sample, device, local_rank, world)
 

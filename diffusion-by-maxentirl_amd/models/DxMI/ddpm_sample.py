@@ -29,7 +29,7 @@ import torch
 from dxmi_hip import ops
 
 from . import stage_loop as _loop
-from ..cm.karras_diffusion import _HostTable, _memo
+from ..cm.karras_diffusion import _memo
 from .var_sampler import _step_tables, calc_diffusion_hyperparams
 
 SKIP_TYPES = ("uniform", "quad")
@@ -102,7 +102,7 @@ def ddpm_coefficients(alpha_bar, tau, eta=1.0, variance="small", beta=None):
             "r": 1.0 / np.sqrt(1.0 - a_t), "c0": c0, "c1": c1, "xm": xm, "c": c1 - np.sqrt(1.0 - a_t) * xm}
 
 
-class DDPMSampleSchedule(_HostTable):
+class DDPMSampleSchedule(_loop.StageSchedule):
     """table: fp32 [S, ops.DT_COLS], row k = the transition tau_{S-1-k} -> tau_{S-2-k}.  The linear-form columns (XM, C, and S for
     variance 'small' without clipping) are _step_tables' scalar fp32 values; the clip-form columns, and S otherwise, are computed
     in float64 from the fp32 Alpha_bar and rounded once.  draws[k]: whether transition k adds noise (S != 0).  The class

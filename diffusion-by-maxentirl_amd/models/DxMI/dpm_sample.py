@@ -32,7 +32,7 @@ import torch
 from dxmi_hip import ops
 
 from . import stage_loop as _loop
-from ..cm.karras_diffusion import _HostTable, _memo
+from ..cm.karras_diffusion import _memo
 from .ddpm_sample import ddpm_timesteps
 from .var_sampler import calc_diffusion_hyperparams
 
@@ -143,17 +143,27 @@ def dpm_coefficients(alpha_bar, tau, algorithm="dpmsolver++", order=2, solver_ty
     _check_mode(algorithm, order, solver_type)
     ab = np.asarray(alpha_bar, dtype=np.float64)
     t = np.asarray(list(tau)[::-1], dtype=np.int64)
-    S = len(t)
     alpha, sigma, lam = np.sqrt(ab[t]), np.sqrt(1.0 - ab[t]), _log_snr(ab[t])
+    co = multistep_coefficients(alpha, sigma, lam, algorithm, order, solver_type, lower_order_final,
+                                lambda k: f"dpm_coefficients: the log-SNR must rise from step {t[k]} to step {t[k + 1]}")
+    co["a"], co["b"] = 1.0 / alpha, sigma / alpha
+    return co
+
+
+def multistep_coefficients(alpha, sigma, lam, algorithm, order, solver_type, lower_order_final, not_rising):
+    """The solver in its (alpha, sigma, lambda) form, stated once for every parametrisation (the DDPM teacher's here, the EDM nets'
+    in models/cm/dpm_sample.py): float64 arrays of the S evaluations, noisiest first -> cx, w0, w1, w2, s and order (int64) of the
+    S rows; the last row goes to alpha_p = 1, sigma_p = 0.  not_rising(k): the message when lambda does not rise over row k."""
+    S = len(lam)
     sde = algorithm == "sde-dpmsolver++"
     rate = 2.0 if sde else 1.0
     orders = dpm_orders(S, order, lower_order_final)
     co = {k: np.zeros(S) for k in ("cx", "w0", "w1", "w2", "s")}
-    co["a"], co["b"], co["order"] = 1.0 / alpha, sigma / alpha, np.asarray(orders, dtype=np.int64)
+    co["order"] = np.asarray(orders, dtype=np.int64)
     for k in range(S - 1):
         o, h = orders[k], lam[k + 1] - lam[k]
         if not h > 0:
-            raise ValueError(f"dpm_coefficients: the log-SNR must rise from step {t[k]} to step {t[k + 1]}")
+            raise ValueError(not_rising(k))
         alpha_p, sigma_p = alpha[k + 1], sigma[k + 1]
         gain = -math.expm1(-rate * h)                                  # 1 - e^-h (ODE), 1 - e^-2h (SDE)
         co["cx"][k] = sigma_p / sigma[k] * (math.exp(-h) if sde else 1.0)
@@ -171,7 +181,7 @@ def dpm_coefficients(alpha_bar, tau, algorithm="dpmsolver++", order=2, solver_ty
     return co
 
 
-class DPMSampleSchedule(_HostTable):
+class DPMSampleSchedule(_loop.StageSchedule):
     """table: fp32 [S, ops.MT_COLS], row k = the transition tau_{S-1-k} -> tau_{S-2-k}: dpm_coefficients on the fp32 Alpha_bar in
     float64, rounded once.  draws[k]: whether transition k adds noise (S != 0); coef: the float64 coefficients.  The class
     attributes are what stage_loop asks of a schedule; the torch loop's state is float64 when noise[0] is (a float64 network then

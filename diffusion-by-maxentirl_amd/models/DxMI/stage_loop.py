@@ -1,19 +1,26 @@
-"""The loop of the DDPM teacher's samplers (models/DxMI/ddpm_sample.py, models/DxMI/dpm_sample.py), written once: per transition
-one network evaluation and one stage launch (csrc/stage_common.h), as torch expressions on the CPU, eagerly on the device, or as
-ONE captured transition replayed for every row.
+"""The loop of the DDPM teacher's samplers (models/DxMI/ddpm_sample.py, models/DxMI/dpm_sample.py) and of DPM-Solver++ on the EDM
+nets (models/cm/dpm_sample.py), written once: per transition one network evaluation and one stage launch (csrc/stage_common.h),
+as torch expressions on the CPU, eagerly on the device, or as ONE captured transition replayed for every row.
 
-  sample          the dispatcher behind ddpm_sample / dpm_sample: checks, device resolution, eager or replay, the graph cache
+  sample          the dispatcher behind ddpm_sample / dpm_sample / edm_dpm_sample: checks, device resolution, eager or replay,
+                  the graph cache
   replay_graphs   the StepGraphs a sampler holds for a network
 
-The loop never asks which sampler it serves.  What differs lives on the schedule object (a _HostTable with tau, steps, draws and
+The loop never asks which sampler it serves.  What differs lives on the schedule object (a _HostTable with steps, draws and
 n_draws, one table row per transition):
   sampler                        the public function's name, for messages and the graph cache's key
-  stage, FIRST, STEP             the launch (ops.ddpm_stage / ops.dpm_stage) and its two modes
+  stage, FIRST, STEP             the launch (ops.ddpm_stage / ops.dpm_stage / ops.edm_dpm_stage) and its two modes
   T_COL                          the table column of the evaluation's time
   hist_slots                     the ring of earlier predictions the launch keeps: 0, or 3 (fp32 [3, *shape], passed as hist=)
   transition(x, eps, z, row, hist)   one transition as torch expressions -> (x', pred_xstart); hist: the hist_slots - 1 predictions
                                  before this one, newest first, as far as the run has made them
   graph_name(shape, mode)        the StepGraph's name
+  x_in                           whether the network is evaluated on a second tensor the launch writes (the preconditioned input
+                                 x_in, passed as x_in=) instead of on the state; FIRST then takes the state and x_in too
+  initial(x, row), net_input(x, row)   the torch loop's share of that: the state FIRST leaves, and what the network is evaluated on
+  net_keywords                   the model_kwargs the network takes (static buffers under replay); any other name is refused
+  step_info(k)                   what the callback's dict says of row k besides i, x and pred_xstart
+StageSchedule holds the DDPM teacher's answers to the last five.
 """
 import weakref
 
@@ -22,9 +29,23 @@ import torch
 from dxmi_hip import graph as _graph
 from dxmi_hip._lib import DxmiError
 
-from ..cm.karras_diffusion import _as_f32, _memo
+from ..cm.karras_diffusion import _as_f32, _HostTable, _memo
 from ..cm.random_util import DeterministicGenerator, DummyGenerator
 from .ddpm_train import _hip_model
+
+
+class StageSchedule(_HostTable):
+    """A schedule of the loop with the answers of a sampler whose network reads the state itself and takes no keywords."""
+    x_in, net_keywords = False, ()
+
+    def initial(self, x, row):
+        return x
+
+    def net_input(self, x, row):
+        return x
+
+    def step_info(self, k):
+        return {"t": self.tau[self.steps - 1 - k]}
 
 
 def _progress(it, progress):
@@ -37,17 +58,17 @@ def _progress(it, progress):
     return it
 
 
-def _evaluate(hip, net, x, t):
+def _evaluate(hip, net, x, t, kw):
     if hip is not None:
         return hip.forward_inference(x, t)
-    eps = net(x, t)
+    eps = net(x, t, **kw)
     assert eps.shape == x.shape, f"network output {tuple(eps.shape)} != sample shape {tuple(x.shape)}"
     if eps.dtype != torch.float32 or not eps.is_contiguous() or eps.device != x.device:
         eps = _as_f32(eps, x.device)
     return eps
 
 
-def _sample_torch(sch, net, shape, device, generator, noise, callback, progress, dtype):
+def _sample_torch(sch, net, shape, device, generator, noise, callback, progress, dtype, kw):
     """The transitions as torch expressions in `dtype`: the CPU path of the host tests, and what the GPU tests compare the launches
     with (a float64 network runs in float64 on the widened fp32 table)."""
     tab = sch.table.to(device=device, dtype=dtype)
@@ -57,9 +78,10 @@ def _sample_torch(sch, net, shape, device, generator, noise, callback, progress,
         x = generator.randn(*shape, device=device)
     else:
         x = torch.randn(shape, device=device)
+    x = sch.initial(x, tab[0])
     hist = []
     for k in _progress(range(sch.steps), progress):
-        eps = net(x, torch.full((shape[0],), float(tab[k, sch.T_COL]), device=device, dtype=dtype))
+        eps = net(sch.net_input(x, tab[k]), torch.full((shape[0],), float(tab[k, sch.T_COL]), device=device, dtype=dtype), **kw)
         z = None
         if sch.draws[k]:
             if noise is not None:
@@ -69,7 +91,7 @@ def _sample_torch(sch, net, shape, device, generator, noise, callback, progress,
         x, pred = sch.transition(x, eps, z, tab[k], hist)
         hist = ([pred] + hist)[:max(sch.hist_slots - 1, 0)]
         if callback is not None:
-            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x, "pred_xstart": pred})
+            callback({"i": k, **sch.step_info(k), "x": x, "pred_xstart": pred})
     return x.clamp(-1, 1)
 
 
@@ -83,16 +105,28 @@ def _initial_state(x, shape, device, generator, noise):
 
 
 def _buffers(sch, shape, device):
-    """x, t, out and the keywords every transition's launch takes: out, and hist where the sampler keeps one."""
+    """x, t, out and the keywords every transition's launch takes: out, hist where the sampler keeps one, and x_in where the
+    network is evaluated on it."""
     f32 = dict(dtype=torch.float32, device=device)
     x, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
     kw = {"out": out}
     if sch.hist_slots:
         kw["hist"] = torch.empty((sch.hist_slots,) + shape, **f32)
+    if sch.x_in:
+        kw["x_in"] = torch.empty(shape, **f32)
     return x, t, out, kw
 
 
-def _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress):
+def _first(sch, tab, x, t, static):
+    """The FIRST launch, and the tensor the network is evaluated on."""
+    if sch.x_in:
+        sch.stage(sch.FIRST, tab, t, row=0, x=x, x_in=static["x_in"])
+        return static["x_in"]
+    sch.stage(sch.FIRST, tab, t, row=0)
+    return x
+
+
+def _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress, net_kw):
     f32 = dict(dtype=torch.float32, device=device)
     tab = sch.device_table(device)
     x, t, out, static = _buffers(sch, shape, device)
@@ -100,9 +134,9 @@ def _sample_eager(sch, hip, net, shape, device, generator, noise, callback, prog
     fused = isinstance(generator, DeterministicGenerator)
     idx = generator.get_indices(shape[0], device) if fused and sch.n_draws else None
     zbuf = None
-    sch.stage(sch.FIRST, tab, t, row=0)
+    x_net = _first(sch, tab, x, t, static)
     for k in _progress(range(sch.steps), progress):
-        eps = _evaluate(hip, net, x, t)
+        eps = _evaluate(hip, net, x_net, t, net_kw)
         kw = {}
         if sch.draws[k]:
             if noise is not None:
@@ -117,7 +151,7 @@ def _sample_eager(sch, hip, net, shape, device, generator, noise, callback, prog
         pred = torch.empty(shape, **f32) if callback is not None else None
         sch.stage(sch.STEP, tab, t, row=k, x=x, eps=eps, pred_xstart=pred, **static, **kw)
         if callback is not None:
-            callback({"i": k, "t": sch.tau[sch.steps - 1 - k], "x": x.clone(), "pred_xstart": pred})
+            callback({"i": k, **sch.step_info(k), "x": x.clone(), "pred_xstart": pred})
     return out
 
 
@@ -127,10 +161,12 @@ class _Replay:
     through a host input, and the launch derives its history slots from the row, so the one captured step serves every row.  Holds
     the schedule: the captured launch reads its device table for as long as the graph lives."""
 
-    def __init__(self, sch, hip, net, shape, device, mode):
+    def __init__(self, sch, hip, net, shape, device, mode, net_kw):
         self.sch, self.hip, self.net, self.mode = sch, hip, net, mode
         self.tab = sch.device_table(device)
         self.x, self.t, self.out, self.static = _buffers(sch, shape, device)
+        self.x_net = self.static["x_in"] if sch.x_in else self.x
+        self.net_kw = {k: torch.empty_like(v, device=device) for k, v in net_kw.items()}      # the labels: static buffers
         self.z = torch.empty(shape, dtype=torch.float32, device=device) if mode == "torch" else None
         self.idx = torch.zeros(shape[0], dtype=torch.int64, device=device) if mode == "fused" else None
         self.row = self.draw = self.seed = 0
@@ -141,7 +177,7 @@ class _Replay:
         return [self.row, self.draw & 0xFFFFFFFF, self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF]
 
     def _step(self):
-        eps = _evaluate(self.hip, self.net, self.x, self.t)
+        eps = _evaluate(self.hip, self.net, self.x_net, self.t, self.net_kw)
         kw = {}
         if self.mode == "torch":      # drawn in every transition: the captured step is the same for all rows (the last row's is unused)
             kw["z"] = self.z.normal_()
@@ -154,13 +190,15 @@ class _Replay:
             kw.update(row=self.row, draw=self.draw, seed=self.seed)
         self.sch.stage(self.sch.STEP, self.tab, self.t, x=self.x, eps=eps, **self.static, **kw)
 
-    def run(self, shape, device, generator):
+    def run(self, shape, device, generator, net_kw):
         sch = self.sch
         _initial_state(self.x, shape, device, generator, None)       # None, or a deterministic generator (also when no row draws)
+        for k, v in net_kw.items():
+            self.net_kw[k].copy_(v)
         if self.mode == "fused":
             self.idx.copy_(generator.get_indices(shape[0], device))
             self.seed = int(generator.seed)
-        sch.stage(sch.FIRST, self.tab, self.t, row=0)
+        _first(sch, self.tab, self.x, self.t, self.static)
         for k in range(sch.steps):
             self.row = k
             if self.mode == "fused" and sch.draws[k]:
@@ -180,10 +218,15 @@ def replay_graphs(net, sampler):
         return []
 
 
-def sample(sch, net, shape, device, generator, noise, callback, progress, use_graph, float64_state):
-    """The body of ddpm_sample / dpm_sample on the schedule `sch` (their docstrings are the contract).  float64_state: whether the
-    torch loop's state takes float64 from a float64 noise[0]; it is fp32 otherwise."""
+def sample(sch, net, shape, device, generator, noise, callback, progress, use_graph, float64_state, model_kwargs=None):
+    """The body of ddpm_sample / dpm_sample / edm_dpm_sample on the schedule `sch` (their docstrings are the contract).
+    float64_state: whether the torch loop's state takes float64 from a float64 noise[0]; it is fp32 otherwise.  model_kwargs: the
+    keywords of the network, of sch.net_keywords; under replay they are tensors, copied into static buffers."""
     shape = tuple(int(s) for s in shape)
+    net_kw = dict(model_kwargs or {})
+    extra = set(net_kw) - set(sch.net_keywords)
+    if extra:
+        raise ValueError(f"{sch.sampler}: model_kwargs {sorted(extra)} are not inputs of its network (it takes {sch.net_keywords})")
     if noise is not None and len(noise) != sch.steps + 1:
         raise ValueError(f"{sch.sampler}: noise must hold {sch.steps + 1} draws (x_T and one per transition), got {len(noise)}")
     hip = _hip_model(net)
@@ -196,17 +239,19 @@ def sample(sch, net, shape, device, generator, noise, callback, progress, use_gr
                 raise DxmiError(f"{sch.sampler}: the HIP Model runs only on the device (a CPU device takes a torch callable)")
             wide = float64_state and noise is not None and noise[0].dtype == torch.float64
             dtype = torch.float64 if wide else torch.float32
-            return _sample_torch(sch, net, shape, device, generator, noise, callback, progress, dtype)
+            return _sample_torch(sch, net, shape, device, generator, noise, callback, progress, dtype, net_kw)
         replayable = generator is None or isinstance(generator, DeterministicGenerator)
-        if not (use_graph and callback is None and not progress and noise is None and replayable and not _graph.capturing()):
-            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
+        static_kw = all(torch.is_tensor(v) for v in net_kw.values())
+        if not (use_graph and callback is None and not progress and noise is None and replayable and static_kw
+                and not _graph.capturing()):
+            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress, net_kw)
         mode = "none" if not sch.n_draws else ("fused" if isinstance(generator, DeterministicGenerator) else "torch")
         try:
             graphs = _GRAPHS.setdefault(hip if hip is not None else net, {})
         except TypeError:        # not weak-referenceable: no cache, so no replay
-            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress)
+            return _sample_eager(sch, hip, net, shape, device, generator, noise, callback, progress, net_kw)
         # what a capture freezes: the sampler and the network (the dictionary's key), the shape and the device, the table and where
         # z comes from.  pred_xstart is never written under replay: it is the callback's
-        key = (sch.sampler, id(sch), shape, device.index, mode)
-        rp = _memo(graphs, key, 8, lambda: _Replay(sch, hip, net, shape, device, mode))
-        return rp.run(shape, device, generator)
+        key = (sch.sampler, id(sch), shape, device.index, mode) + tuple((k, v.dtype, tuple(v.shape)) for k, v in sorted(net_kw.items()))
+        rp = _memo(graphs, key, 8, lambda: _Replay(sch, hip, net, shape, device, mode, net_kw))
+        return rp.run(shape, device, generator, net_kw)

@@ -1144,6 +1144,59 @@ int dxmi_dpm_stage(int32_t mode, const float* tab, int32_t rows, const int32_t* 
                    float* x, const float* eps, const float* z, const int64_t* sample_index, float* hist, float* t_out, float* out,
                    float* pred_xstart, int32_t N, int32_t CHW, void* stream);
 
+/* DPM-Solver++ sampling of the EDM nets (csrc/edm_dpm_sample.hip; models/cm/dpm_sample.py): the multistep solver of
+ * dxmi_dpm_stage in the EDM parametrisation x = x_0 + sigma e (alpha = 1, lambda = -ln sigma) on a sigma ladder, with the Karras
+ * preconditioning inside the launch (the reference tree has no such sampler).  dxmi_edm_dpm_stage is the ONE launch between two
+ * network evaluations.  With F = model_out the output of evaluation k = row at c_in(sigma_k) x and K = tab[row], per element in fp32,
+ * one rounding per operation (no fused multiply-add), in this order:
+ *     D0  = K[COUT] F + K[CSKIP] x;  FLAG_CLIP: D0 = clamp(D0, -1, 1)    (the data prediction; dxmi_karras_stage's order)
+ *     acc = K[CX] x + K[W0] D0
+ *     acc += K[W1] D1     if K[W1] != 0       (D1 = D_{k-1}, the data prediction of the evaluation before)
+ *     acc += K[W2] D2     if K[W2] != 0       (D2 = D_{k-2})
+ *     acc += K[S] z       if K[S] != 0
+ * then x = acc in place, hist[row % 3] = D0, t_out[n] = K[T_NEXT] (the next evaluation's time 250 ln(sigma_{k+1} + 1e-44)),
+ * on a row without FLAG_LAST x_in = K[CIN_NEXT] acc (the next evaluation's input; x_in is not touched on the last row) and, on the
+ * row with FLAG_LAST, out = clamp(acc, -1, 1).  pred_xstart = D0 is written when not NULL.  A NaN in F reaches x' (the clamps pass
+ * it); images do not mix.
+ * History: hist is fp32 [3][N][CHW], addressed from the row number exactly as dxmi_dpm_stage addresses it; a weight that is exactly
+ *   0 means its slot is NOT read.
+ * DXMI_EDM_DPM_FIRST: x = x K[XSCALE] in place (x_T = randn sigma_max), x_in = K[CIN] x, t_out[n] = K[T]; model_out, hist and out
+ *   may be NULL.
+ * Control: ctl NULL: row, draw and seed are the by-value arguments, and row outside [0, rows) is DXMI_EINVAL.  ctl not NULL: an
+ *   int32[4] block on the DEVICE = (row, draw, seed low word, seed high word) read by the kernel (the by-value three are ignored);
+ *   a row outside [0, rows) read there gives NaN in x, x_in, out, t_out and slot 0 of the history; nothing outside the table and no
+ *   history slot is read.
+ * Noise: as dxmi_dpm_stage: z given, or z == NULL and sample_index (int64 [N], DEVICE): the bits of dxmi_randn_indexed for
+ *   (seed, sample_index[n], draw, e).  Both NULL: no noise.  Both given: DXMI_EINVAL.  A row with K[S] == 0 reads neither.
+ * x_in may be NULL only on the table's last row (rows - 1, the one the host flags last) given by value: with a control block the
+ *   row is not known to the host, so x_in is required.
+ * tab: fp32 [rows][DXMI_ET_COLS] on the device.  x, model_out, z, hist, x_in, out, pred_xstart: 16-byte aligned; CHW % 4 != 0
+ * takes 4-byte aligned vector accesses and a scalar tail.  N in [1, 65535].  No workspace, no LDS, no atomics.
+ * The table: columns 0-10 are those of DXMI_MT_* with the preconditioning's two scalars in the place of A and B. */
+#define DXMI_EDM_DPM_FIRST 0
+#define DXMI_EDM_DPM_STEP  1
+#define DXMI_ET_T         0   /* time of the evaluation the launch follows: 250 ln(sigma_k + 1e-44) */
+#define DXMI_ET_T_NEXT    1   /* time of the next evaluation (0 on the last row) */
+#define DXMI_ET_CX        2   /* ODE sigma_p / sigma_t; SDE (sigma_p / sigma_t) exp(-h); 0 on the last row */
+#define DXMI_ET_W0        3   /* weight of D_k (1 on the last row) */
+#define DXMI_ET_W1        4   /* weight of D_{k-1}; exactly 0: the slot is not read */
+#define DXMI_ET_W2        5   /* weight of D_{k-2}; exactly 0: the slot is not read */
+#define DXMI_ET_S         6   /* noise scale: SDE sigma_p sqrt(1 - exp(-2h)); 0 for the ODE and on the last row */
+#define DXMI_ET_CSKIP     7   /* c_skip(sigma_k) */
+#define DXMI_ET_COUT      8   /* c_out(sigma_k) */
+#define DXMI_ET_FLAGS     9   /* DXMI_ET_FLAG_* summed, stored as a float */
+#define DXMI_ET_ORDER    10   /* the order the row was built with (1-3); not read by the kernel */
+#define DXMI_ET_CIN      11   /* c_in(sigma_k): FIRST's factor of x_in */
+#define DXMI_ET_CIN_NEXT 12   /* c_in(sigma_{k+1}) (0 on the last row, where x_in is not written) */
+#define DXMI_ET_XSCALE   13   /* FIRST's factor of x: sigma_max */
+#define DXMI_ET_SIGMA    14   /* sigma_k; not read by the kernel */
+#define DXMI_ET_COLS     16
+#define DXMI_ET_FLAG_CLIP 1
+#define DXMI_ET_FLAG_LAST 2
+int dxmi_edm_dpm_stage(int32_t mode, const float* tab, int32_t rows, const int32_t* ctl, int32_t row, uint32_t draw, uint64_t seed,
+                       float* x, const float* model_out, const float* z, const int64_t* sample_index, float* hist, float* x_in,
+                       float* t_out, float* out, float* pred_xstart, int32_t N, int32_t CHW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
