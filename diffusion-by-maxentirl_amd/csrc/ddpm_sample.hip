@@ -14,7 +14,7 @@ namespace {
 struct DdpmStage {
     static constexpr int COLS = DXMI_DT_COLS, T = DXMI_DT_T, T_NEXT = DXMI_DT_T_NEXT, FLAGS = DXMI_DT_FLAGS;
     static constexpr int FLAG_LAST = DXMI_DT_FLAG_LAST, HIST = 0;
-    static constexpr bool XIN = false;
+    static constexpr bool XIN = false, CORR = false;
 
     struct StageCoef {
         float xm, c, s, a, b, q, r, c0, c1;

@@ -20,7 +20,7 @@ namespace {
 struct DpmStage {
     static constexpr int COLS = DXMI_MT_COLS, T = DXMI_MT_T, T_NEXT = DXMI_MT_T_NEXT, FLAGS = DXMI_MT_FLAGS;
     static constexpr int FLAG_LAST = DXMI_MT_FLAG_LAST, HIST = 2;
-    static constexpr bool XIN = false;
+    static constexpr bool XIN = false, CORR = false;
 
     struct StageCoef {
         float cx, w0, w1, w2, s, a, b;

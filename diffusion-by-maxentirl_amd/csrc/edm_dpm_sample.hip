@@ -22,7 +22,7 @@ namespace {
 struct EdmDpmStage {
     static constexpr int COLS = DXMI_ET_COLS, T = DXMI_ET_T, T_NEXT = DXMI_ET_T_NEXT, FLAGS = DXMI_ET_FLAGS;
     static constexpr int FLAG_LAST = DXMI_ET_FLAG_LAST, HIST = 2;
-    static constexpr bool XIN = true;
+    static constexpr bool XIN = true, CORR = false;
     static constexpr int CIN = DXMI_ET_CIN, CIN_NEXT = DXMI_ET_CIN_NEXT, XSCALE = DXMI_ET_XSCALE;
 
     struct StageCoef {

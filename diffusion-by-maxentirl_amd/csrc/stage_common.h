@@ -1,5 +1,5 @@
-// The stage launch of the DDPM teacher's samplers (csrc/ddpm_sample.hip, csrc/dpm_sample.hip) and of DPM-Solver++ on the EDM nets
-// (csrc/edm_dpm_sample.hip), written once: ONE launch between two
+// The stage launch of the DDPM teacher's samplers (csrc/ddpm_sample.hip, csrc/dpm_sample.hip, csrc/unipc_sample.hip) and of the EDM
+// nets' multistep solvers (csrc/edm_dpm_sample.hip, csrc/edm_unipc_sample.hip), written once: ONE launch between two
 // network evaluations finishes a transition in place (x'), writes the next evaluation's time and, on the row flagged last, the
 // clamped sample.  Every per-transition scalar is read from one fp32 table row built on the host, the last-step behaviour
 // included, and the row number, the draw number and the seed can be read from a small device block: one captured launch serves
@@ -9,13 +9,18 @@
 //
 // A sampler supplies a policy P, resolved at compile time (nothing here asks which sampler it serves):
 //   COLS, T, T_NEXT, FLAGS, FLAG_LAST   the table's row length, the shared columns and the last-row flag
-//   HIST                                how many earlier predictions an element reads (0 or 2), kept in a ring of HIST + 1 slots
+//   HIST                                how many earlier predictions an element reads (0, 2 or 3), kept in a ring of HIST + 1 slots
 //                                       fp32 [HIST + 1][N][CHW]: this row's goes to slot row % (HIST + 1), the one j + 1 rows back
 //                                       comes from slot (row - 1 - j) % (HIST + 1).  HIST == 0: no pointer, load or register
 //   XIN                                 whether the launch has a second output stream: the next evaluation's preconditioned input
 //                                       x_in = K[CIN_NEXT] x', written on every row that is not last (and, NaN, on a poisoned one); the
 //                                       policy then names the columns CIN, CIN_NEXT and XSCALE too, and FIRST scales x in place by
 //                                       K[XSCALE] and writes x_in = K[CIN] x next to t_out.  false: no pointer, product or store
+//   CORR                                whether the launch carries a second in-place state stream xc (UniPC's corrected state): on a
+//                                       row the policy marks corrected (k.corr) xc is read, on every row b, the state the step
+//                                       starts from, is written to it (NaN on a poisoned row).  xc == NULL: P::uncorrect(k) clears
+//                                       k.corr and the reads only the corrector asked for; xc is then neither read nor written.  The
+//                                       element is then stage_elem(k, x, e, d, xc, &pred, &b).  false: no pointer, load or register
 //   StageCoef                           the row's scalars; members s (the noise scale) and noisy, and with HIST rd[HIST]: whether
 //                                       slot j is read (a slot never written holds anything, and 0 * NaN would be NaN)
 //   fill(r, ok, flags)                  StageCoef from the row r; !ok: the row is poisoned, what must be NaN and what must be 0
@@ -76,14 +81,14 @@ __device__ __forceinline__ void stage_first_xin(const float* __restrict__ r, boo
     }
 }
 
-// the body of <sampler>_stage_kernel<ALIGNED>; hist and N are used with P::HIST alone, x_in with P::XIN alone
+// the body of <sampler>_stage_kernel<ALIGNED>; hist and N are used with P::HIST alone, x_in with P::XIN alone, xc with P::CORR alone
 template <class P, bool ALIGNED>
 __device__ __forceinline__ void stage_body(int first, const float* __restrict__ tab, int rows, const int32_t* __restrict__ ctl,
                                            int row_v, uint32_t draw_v, uint32_t k0_v, uint32_t k1_v, float* x,
                                            const float* __restrict__ eps, const float* __restrict__ z,
                                            const int64_t* __restrict__ sample_index, float* hist, float* __restrict__ t_out,
                                            float* __restrict__ out, float* __restrict__ pred, int N, int CHW,
-                                           float* __restrict__ x_in = nullptr) {
+                                           float* __restrict__ x_in = nullptr, float* xc = nullptr) {
     constexpr int H = P::HIST, HD = H ? H : 1;
     const int n = blockIdx.y;
     const int row = ctl ? ctl[0] : row_v;
@@ -101,6 +106,9 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
     typename P::StageCoef k = P::fill(r, ok, flags);
     const bool fused = !z && sample_index;
     k.noisy = k.s != 0.f && (z || fused);                    // rows with s == 0 touch neither z nor the generator
+    if constexpr (P::CORR) {
+        if (!xc) P::uncorrect(k);
+    }
     const bool last = !ok || (flags & P::FLAG_LAST) != 0;              // a poisoned launch poisons the sample too
     if (blockIdx.x == 0 && threadIdx.x == 0) t_out[n] = ok ? r[P::T_NEXT] : nan;
     uint32_t i_lo = 0, i_hi = 0;
@@ -123,7 +131,7 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
     }
     const int n4 = CHW / 4, rem = CHW % 4;
     for (int i0 = blockIdx.x * STAGE_BLOCK * STAGE_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * STAGE_BLOCK * STAGE_UNROLL) {
-        f32x4 xv[STAGE_UNROLL], ev[STAGE_UNROLL], hv[HD][STAGE_UNROLL], zv[STAGE_UNROLL];
+        f32x4 xv[STAGE_UNROLL], ev[STAGE_UNROLL], hv[HD][STAGE_UNROLL], zv[STAGE_UNROLL], cv[P::CORR ? STAGE_UNROLL : 1];
 #pragma unroll
         for (int u = 0; u < STAGE_UNROLL; ++u) {
             const int i = i0 + u * STAGE_BLOCK;
@@ -137,6 +145,9 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
                         if (k.rd[j]) hv[j][u] = load4<ALIGNED>(hp[j] + o);
                 }
                 if (k.noisy && !fused) zv[u] = load4<ALIGNED>(z + o);
+                if constexpr (P::CORR) {
+                    if (k.corr) cv[u] = load4<ALIGNED>(xc + o);
+                }
             }
         }
 #pragma unroll
@@ -145,7 +156,7 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
             if (i >= n4) continue;
             const size_t o = base + (size_t)i * 4;
             if (k.noisy && fused) zv[u] = normals(philox4x32_10((uint32_t)i, draw, i_lo, i_hi, k0, k1));
-            f32x4 xn, pv;
+            f32x4 xn, pv, bv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float d[HD] = {}, p;
@@ -153,10 +164,19 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
 #pragma unroll
                     for (int j = 0; j < H; ++j) d[j] = k.rd[j] ? hv[j][u][e] : 0.f;
                 }
-                xn[e] = P::stage_elem(k, xv[u][e], ev[u][e], d, k.noisy ? zv[u][e] : 0.f, &p);
+                if constexpr (P::CORR) {
+                    float b;
+                    xn[e] = P::stage_elem(k, xv[u][e], ev[u][e], d, k.corr ? cv[u][e] : 0.f, &p, &b);
+                    bv[e] = ok ? b : nan;
+                } else {
+                    xn[e] = P::stage_elem(k, xv[u][e], ev[u][e], d, k.noisy ? zv[u][e] : 0.f, &p);
+                }
                 pv[e] = p;
             }
             store4<ALIGNED>(x + o, xn);
+            if constexpr (P::CORR) {
+                if (xc) store4<ALIGNED>(xc + o, bv);
+            }
             if constexpr (H > 0) store4<ALIGNED>(h0 + o, pv);
             if (pred) store4<ALIGNED>(pred + o, pv);
             if constexpr (P::XIN) {
@@ -186,7 +206,14 @@ __device__ __forceinline__ void stage_body(int first, const float* __restrict__ 
 #pragma unroll
                 for (int j = 0; j < H; ++j) d[j] = k.rd[j] ? hp[j][o] : 0.f;
             }
-            const float xn = P::stage_elem(k, x[o], eps[o], d, zt[e], &p);
+            float xn;
+            if constexpr (P::CORR) {
+                float b;
+                xn = P::stage_elem(k, x[o], eps[o], d, k.corr ? xc[o] : 0.f, &p, &b);
+                if (xc) xc[o] = ok ? b : nan;
+            } else {
+                xn = P::stage_elem(k, x[o], eps[o], d, zt[e], &p);
+            }
             x[o] = xn;
             if constexpr (H > 0) h0[o] = p;
             if (pred) pred[o] = p;

@@ -190,6 +190,8 @@ SIGNATURES = {
     "dxmi_ddpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 7 + [c_int, c_int, c_void_p]),
     "dxmi_dpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 8 + [c_int, c_int, c_void_p]),
     "dxmi_edm_dpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
+    "dxmi_unipc_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_void_p]),
+    "dxmi_edm_unipc_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -2072,12 +2072,13 @@ def edm_step_indexed(x, model_out, sample_index, sigma, sigma_down, sigma_up, si
 
 
 def _sampler_stage(name, cols, mode, first, tab, t_out, row, x, eps, z, sample_index, seed, draw, ctl, out, pred_xstart, hist=(),
-                   x_in=()):
+                   x_in=(), xc=(), slots=3):
     """The checks and the call of the stage launches of csrc/stage_common.h.  cols: the table's row length; first: the sampler's
-    FIRST mode; hist: () for a sampler without a history, else (the tensor or None,); x_in: () for a sampler without the second
-    output stream, else (the tensor or None,): FIRST then takes x and x_in, and a transition's x_in may be None on the table's last
-    row given by value."""
-    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, *hist, *x_in, out, pred_xstart)
+    FIRST mode; hist: () for a sampler without a history, else (the tensor or None,), of `slots` slots; x_in: () for a sampler
+    without the second output stream, else (the tensor or None,): FIRST then takes x and x_in, and a transition's x_in may be None on
+    the table's last row given by value.  xc: () for a sampler with one state, else (the second state or None,): such an entry adds
+    no noise and takes no draw, seed, z or sample_index."""
+    _need_cuda(tab, t_out, x, eps, z, sample_index, ctl, *hist, *x_in, *xc, out, pred_xstart)
     if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == cols and tab.shape[0] >= 1):
         raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {cols}], got {tab.dtype} {tuple(tab.shape)}")
     if not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
@@ -2098,20 +2099,29 @@ def _sampler_stage(name, cols, mode, first, tab, t_out, row, x, eps, z, sample_i
             raise _lib.DxmiError(f"{name}: a transition needs x, eps{', hist' if hist else ''} and out")
         if x_in and x_in[0] is None and (ctl is not None or int(row) != tab.shape[0] - 1):
             raise _lib.DxmiError(f"{name}: x_in is needed on every row but the table's last, given by value")
-        for v in (x, eps, z, out, pred_xstart, *x_in):
+        for v in (x, eps, z, out, pred_xstart, *x_in, *xc):
             if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
                 raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
         if x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
             raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} samples, got {tuple(x.shape)}")
         for h in hist:
-            if not (h.dtype == torch.float32 and h.is_contiguous() and tuple(h.shape) == (3,) + tuple(x.shape)):
-                raise _lib.DxmiError(f"{name}: hist must be a contiguous fp32 {(3,) + tuple(x.shape)}, got {h.dtype} {tuple(h.shape)}")
+            if not (h.dtype == torch.float32 and h.is_contiguous() and tuple(h.shape) == (slots,) + tuple(x.shape)):
+                raise _lib.DxmiError(f"{name}: hist must be a contiguous fp32 {(slots,) + tuple(x.shape)}, got {h.dtype} {tuple(h.shape)}")
         chw = x.numel() // N
         if sample_index is not None and not (sample_index.dtype == torch.int64 and sample_index.is_contiguous()
                                              and sample_index.shape == (N,)):
             raise _lib.DxmiError(f"{name}: sample_index must be a contiguous int64 [{N}]")
     if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
         raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
+    if xc:
+        if z is not None or sample_index is not None:
+            raise _lib.DxmiError(f"{name}: the solver adds no noise: neither z nor sample_index")
+        if xc[0] is not None and x is not None and xc[0].data_ptr() == x.data_ptr():
+            raise _lib.DxmiError(f"{name}: xc and x are two states: they may not be one tensor")
+        check(getattr(load(), name)(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), _ptr(x), _ptr(xc[0]), _ptr(eps),
+                                    *(_ptr(h) for h in hist), *(_ptr(v) for v in x_in), _ptr(t_out), _ptr(out), _ptr(pred_xstart), N,
+                                    chw, _stream()), name)
+        return
     check(getattr(load(), name)(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF,
                                 int(seed) & _U64, _ptr(x), _ptr(eps), _ptr(z), _ptr(sample_index), *(_ptr(h) for h in hist),
                                 *(_ptr(v) for v in x_in), _ptr(t_out), _ptr(out), _ptr(pred_xstart), N, chw, _stream()), name)
@@ -2171,6 +2181,42 @@ def edm_dpm_stage(mode, tab, t_out, row=0, x=None, model_out=None, z=None, sampl
     EDM_DPM_FIRST scales x by the row's XSCALE in place and writes x_in = c_in x and t_out of `row`."""
     _sampler_stage("dxmi_edm_dpm_stage", ET_COLS, mode, EDM_DPM_FIRST, tab, t_out, row, x, model_out, z, sample_index, seed, draw, ctl,
                    out, pred_xstart, hist=(hist,), x_in=(x_in,))
+
+
+# dxmi_unipc_stage modes, table columns and flags (include/dxmi_hip.h): MT_*'s columns (the solver has no noise: S's place holds the
+# corrector's order) and the corrector's five
+UNIPC_FIRST, UNIPC_STEP = range(2)
+(UT_T, UT_T_NEXT, UT_CX, UT_W0, UT_W1, UT_W2, UT_CORDER, UT_A, UT_B, UT_FLAGS, UT_ORDER, UT_CCX, UT_CV0, UT_CV1, UT_CV2,
+ UT_CV3) = range(16)
+UT_COLS = 16
+UT_FLAG_CLIP, UT_FLAG_LAST, UT_FLAG_CORR = 1, 2, 4
+
+
+def unipc_stage(mode, tab, t_out, row=0, x=None, xc=None, eps=None, ctl=None, hist=None, out=None, pred_xstart=None):
+    """One UniPC transition of the DDPM teacher between two network evaluations (dxmi_unipc_stage): this evaluation's data
+    prediction goes to hist[row % 4] (hist: fp32 [4, *x.shape]), on a row flagged CORR the corrected state xc is re-done with it,
+    x (the predicted state the network sees) and xc are updated in place, t_out [N] takes the next evaluation's time, out the
+    clamped sample on the row flagged last.  xc None: no corrected state, every row runs uncorrected.  tab: fp32 [rows, UT_COLS] on
+    the device.  ctl: an int32 [4] device block whose first word replaces row.  UNIPC_FIRST writes t_out of `row` only."""
+    _sampler_stage("dxmi_unipc_stage", UT_COLS, mode, UNIPC_FIRST, tab, t_out, row, x, eps, None, None, 0, 0, ctl, out, pred_xstart,
+                   hist=(hist,), xc=(xc,), slots=4)
+
+
+# dxmi_edm_unipc_stage: ET_*'s columns (S's place holds the corrector's order) and the corrector's five
+EDM_UNIPC_FIRST, EDM_UNIPC_STEP = range(2)
+(EUT_T, EUT_T_NEXT, EUT_CX, EUT_W0, EUT_W1, EUT_W2, EUT_CORDER, EUT_CSKIP, EUT_COUT, EUT_FLAGS, EUT_ORDER, EUT_CIN, EUT_CIN_NEXT,
+ EUT_XSCALE, EUT_SIGMA, EUT_CCX, EUT_CV0, EUT_CV1, EUT_CV2, EUT_CV3) = range(20)
+EUT_COLS = 20
+EUT_FLAG_CLIP, EUT_FLAG_LAST, EUT_FLAG_CORR = 1, 2, 4
+
+
+def edm_unipc_stage(mode, tab, t_out, row=0, x=None, xc=None, model_out=None, ctl=None, hist=None, x_in=None, out=None,
+                    pred_xstart=None):
+    """One UniPC transition of the EDM nets between two network evaluations (dxmi_edm_unipc_stage): unipc_stage with the Karras
+    preconditioning of edm_dpm_stage; x_in takes the next evaluation's input c_in x' on every row that is not last.  tab: fp32
+    [rows, EUT_COLS] on the device.  EDM_UNIPC_FIRST scales x by the row's XSCALE in place and writes x_in = c_in x and t_out."""
+    _sampler_stage("dxmi_edm_unipc_stage", EUT_COLS, mode, EDM_UNIPC_FIRST, tab, t_out, row, x, model_out, None, None, 0, 0, ctl, out,
+                   pred_xstart, hist=(hist,), x_in=(x_in,), xc=(xc,), slots=4)
 
 
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)

@@ -181,6 +181,76 @@ def multistep_coefficients(alpha, sigma, lam, algorithm, order, solver_type, low
     return co
 
 
+UNIPC_VARIANTS = ("bh1", "bh2")
+
+
+def unipc_coefficients(alpha, sigma, lam, order, variant, corrector, lower_order_final, not_rising):
+    """UniPC (Zhao et al. 2023, arXiv:2302.04867; multistep, data prediction, ODE) in the (alpha, sigma, lambda) form of
+    multistep_coefficients: float64 arrays of the S evaluations, noisiest first -> the predictor's cx, w0, w1, w2 and order, and
+    the corrector's ccx, cv0..cv3 and corr_order (0: the row is not corrected) of the S rows.  With B(h) = h (bh1) or 1 - e^-h
+    (bh2) and g = 1 - e^-h, row k < S - 1 after evaluation k:
+        corrector, k >= 1, order q = order[k - 1], h = lambda_k - lambda_{k-1}:
+            x_k = (sigma_k / sigma_{k-1}) x_{k-1} + sum_{j <= q} cv_j D_{k-j}
+            q = 1 (rho = 1/2): cv_0 = alpha_k B / 2, cv_1 = alpha_k (g - B / 2)
+            q >= 2: cv_j = alpha_k int_0^h e^-v L_j(v) dv, L_j the Lagrange basis on the q + 1 nodes v_j = lambda_k - lambda_{k-j}
+                    (UniPC's system R rho = b solved in closed form: B cancels)
+        predictor, order p = order[k], h = lambda_{k+1} - lambda_k:
+            xt_{k+1} = (sigma_{k+1} / sigma_k) x_k + sum_{j < p} w_j D_{k-j}
+            p = 1: w_0 = alpha_{k+1} g;  p = 3: multistep_coefficients' "exact" rows (B cancels)
+            p = 2 (rho = 1/2), r = (lambda_k - lambda_{k-1}) / h: w_0 = alpha_{k+1} (g + B / (2r)), w_1 = -alpha_{k+1} B / (2r);
+                  with bh2 multistep_coefficients' "midpoint" row
+    The last row is the denoise row and is never corrected.  A weight beyond a row's order is exactly 0."""
+    if variant not in UNIPC_VARIANTS:
+        raise ValueError(f"variant must be one of {UNIPC_VARIANTS}, got {variant!r}")
+    if isinstance(order, bool) or int(order) != order or not 1 <= int(order) <= 3:
+        raise ValueError(f"order must be 1, 2 or 3, got {order!r}")
+    S = len(lam)
+    co = multistep_coefficients(alpha, sigma, lam, "dpmsolver++", order, "exact", lower_order_final, not_rising)
+    mid = multistep_coefficients(alpha, sigma, lam, "dpmsolver++", order, "midpoint", lower_order_final, not_rising)
+    del co["s"]
+    orders = [int(o) for o in co["order"]]
+    for k in ("ccx", "cv0", "cv1", "cv2", "cv3"):
+        co[k] = np.zeros(S)
+    co["corr_order"] = np.zeros(S, dtype=np.int64)
+
+    def bh(h):
+        return h if variant == "bh1" else -math.expm1(-h)
+
+    for k in range(S - 1):
+        if orders[k] == 2:
+            if variant == "bh2":
+                co["w0"][k], co["w1"][k] = mid["w0"][k], mid["w1"][k]
+            else:
+                h = lam[k + 1] - lam[k]
+                r = (lam[k] - lam[k - 1]) / h
+                co["w0"][k] = alpha[k + 1] * (-math.expm1(-h) + bh(h) * 0.5 / r)
+                co["w1"][k] = -alpha[k + 1] * bh(h) * 0.5 / r
+        if corrector and k >= 1:
+            q, h = orders[k - 1], lam[k] - lam[k - 1]
+            co["corr_order"][k], co["ccx"][k] = q, sigma[k] / sigma[k - 1]
+            if q == 1:
+                half = bh(h) * 0.5
+                cv = [alpha[k] * half, alpha[k] * (-math.expm1(-h) - half)]
+            else:
+                nodes = [lam[k] - lam[k - j] for j in range(q + 1)]
+                cv = [alpha[k] * v for v in _lagrange_weights(nodes, _moments(h, q + 1))]
+            for j, v in enumerate(cv):
+                co[f"cv{j}"][k] = v
+    return co
+
+
+def unipc_dpm_coefficients(alpha_bar, tau, order=3, variant="bh1", corrector=True, lower_order_final=True):
+    """unipc_coefficients of the DDPM teacher, from `alpha_bar` as given (any float array) on the steps tau, with a = 1 / alpha and
+    b = sigma / alpha of every evaluation (dpm_coefficients' two)."""
+    ab = np.asarray(alpha_bar, dtype=np.float64)
+    t = np.asarray(list(tau)[::-1], dtype=np.int64)
+    alpha, sigma, lam = np.sqrt(ab[t]), np.sqrt(1.0 - ab[t]), _log_snr(ab[t])
+    co = unipc_coefficients(alpha, sigma, lam, order, variant, corrector, lower_order_final,
+                            lambda k: f"unipc_coefficients: the log-SNR must rise from step {t[k]} to step {t[k + 1]}")
+    co["a"], co["b"] = 1.0 / alpha, sigma / alpha
+    return co
+
+
 class DPMSampleSchedule(_loop.StageSchedule):
     """table: fp32 [S, ops.MT_COLS], row k = the transition tau_{S-1-k} -> tau_{S-2-k}: dpm_coefficients on the fp32 Alpha_bar in
     float64, rounded once.  draws[k]: whether transition k adds noise (S != 0); coef: the float64 coefficients.  The class

@@ -1,5 +1,5 @@
-"""The loop of the DDPM teacher's samplers (models/DxMI/ddpm_sample.py, models/DxMI/dpm_sample.py) and of DPM-Solver++ on the EDM
-nets (models/cm/dpm_sample.py), written once: per transition one network evaluation and one stage launch (csrc/stage_common.h),
+"""The loop of the DDPM teacher's samplers (models/DxMI/ddpm_sample.py, models/DxMI/dpm_sample.py, models/DxMI/unipc_sample.py) and
+of the EDM nets' multistep solvers (models/cm/dpm_sample.py, models/cm/unipc_sample.py), written once: per transition one network evaluation and one stage launch (csrc/stage_common.h),
 as torch expressions on the CPU, eagerly on the device, or as ONE captured transition replayed for every row.
 
   sample          the dispatcher behind ddpm_sample / dpm_sample / edm_dpm_sample: checks, device resolution, eager or replay,
@@ -11,16 +11,20 @@ n_draws, one table row per transition):
   sampler                        the public function's name, for messages and the graph cache's key
   stage, FIRST, STEP             the launch (ops.ddpm_stage / ops.dpm_stage / ops.edm_dpm_stage) and its two modes
   T_COL                          the table column of the evaluation's time
-  hist_slots                     the ring of earlier predictions the launch keeps: 0, or 3 (fp32 [3, *shape], passed as hist=)
+  hist_slots                     the ring of earlier predictions the launch keeps: 0, 3 or 4 (fp32 [hist_slots, *shape], passed as
+                                 hist=)
   transition(x, eps, z, row, hist)   one transition as torch expressions -> (x', pred_xstart); hist: the hist_slots - 1 predictions
                                  before this one, newest first, as far as the run has made them
+  carry                          whether a second state is carried from transition to transition next to x: the launch then takes a
+                                 static buffer of the state's shape as xc= (it writes it before it reads it), and the torch
+                                 transition takes the carried value as a sixth argument (None on row 0) and returns it third
   graph_name(shape, mode)        the StepGraph's name
   x_in                           whether the network is evaluated on a second tensor the launch writes (the preconditioned input
                                  x_in, passed as x_in=) instead of on the state; FIRST then takes the state and x_in too
   initial(x, row), net_input(x, row)   the torch loop's share of that: the state FIRST leaves, and what the network is evaluated on
   net_keywords                   the model_kwargs the network takes (static buffers under replay); any other name is refused
   step_info(k)                   what the callback's dict says of row k besides i, x and pred_xstart
-StageSchedule holds the DDPM teacher's answers to the last five.
+StageSchedule holds the DDPM teacher's answers to the last five, and carry = False.
 """
 import weakref
 
@@ -36,7 +40,7 @@ from .ddpm_train import _hip_model
 
 class StageSchedule(_HostTable):
     """A schedule of the loop with the answers of a sampler whose network reads the state itself and takes no keywords."""
-    x_in, net_keywords = False, ()
+    x_in, net_keywords, carry = False, (), False
 
     def initial(self, x, row):
         return x
@@ -79,7 +83,7 @@ def _sample_torch(sch, net, shape, device, generator, noise, callback, progress,
     else:
         x = torch.randn(shape, device=device)
     x = sch.initial(x, tab[0])
-    hist = []
+    hist, carried = [], None
     for k in _progress(range(sch.steps), progress):
         eps = net(sch.net_input(x, tab[k]), torch.full((shape[0],), float(tab[k, sch.T_COL]), device=device, dtype=dtype), **kw)
         z = None
@@ -88,7 +92,10 @@ def _sample_torch(sch, net, shape, device, generator, noise, callback, progress,
                 z = noise[k + 1].to(device=device, dtype=dtype)
             else:
                 z = generator.randn_like(x) if generator is not None else torch.randn_like(x)
-        x, pred = sch.transition(x, eps, z, tab[k], hist)
+        if sch.carry:
+            x, pred, carried = sch.transition(x, eps, z, tab[k], hist, carried)
+        else:
+            x, pred = sch.transition(x, eps, z, tab[k], hist)
         hist = ([pred] + hist)[:max(sch.hist_slots - 1, 0)]
         if callback is not None:
             callback({"i": k, **sch.step_info(k), "x": x, "pred_xstart": pred})
@@ -105,8 +112,8 @@ def _initial_state(x, shape, device, generator, noise):
 
 
 def _buffers(sch, shape, device):
-    """x, t, out and the keywords every transition's launch takes: out, hist where the sampler keeps one, and x_in where the
-    network is evaluated on it."""
+    """x, t, out and the keywords every transition's launch takes: out, hist where the sampler keeps one, x_in where the
+    network is evaluated on it, and xc where a second state is carried."""
     f32 = dict(dtype=torch.float32, device=device)
     x, t, out = torch.empty(shape, **f32), torch.empty(shape[0], **f32), torch.empty(shape, **f32)
     kw = {"out": out}
@@ -114,6 +121,8 @@ def _buffers(sch, shape, device):
         kw["hist"] = torch.empty((sch.hist_slots,) + shape, **f32)
     if sch.x_in:
         kw["x_in"] = torch.empty(shape, **f32)
+    if sch.carry:
+        kw["xc"] = torch.empty(shape, **f32)
     return x, t, out, kw
 
 

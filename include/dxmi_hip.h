@@ -1197,6 +1197,98 @@ int dxmi_edm_dpm_stage(int32_t mode, const float* tab, int32_t rows, const int32
                        float* x, const float* model_out, const float* z, const int64_t* sample_index, float* hist, float* x_in,
                        float* t_out, float* out, float* pred_xstart, int32_t N, int32_t CHW, void* stream);
 
+/* UniPC sampling of the DDPM teacher (csrc/unipc_sample.hip; models/DxMI/unipc_sample.py): Zhao, Bai, Rao, Zhou and Lu
+ * 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models" (arXiv:2302.04867), the multistep
+ * data-prediction predictor UniP with the corrector UniC at orders 1-3, ODE only (UniPC has no reference call site: the reference
+ * tree has no such sampler).  dxmi_unipc_stage is the ONE launch between two network evaluations.  x is the predicted state the
+ * network was evaluated on, xc the corrected state of the evaluation before.  With eps the output of evaluation k = row at x and
+ * K = tab[row], per element in fp32, one rounding per operation (no fused multiply-add), in this order:
+ *     D0  = K[A] x - K[B] eps;  FLAG_CLIP: D0 = clamp(D0, -1, 1)        (the data prediction)
+ *     a row with FLAG_CORR, xc given (the corrector: the step that led here, re-done with D0 as a node at its end):
+ *       b = K[CCX] xc;  b += K[CV0] D0;  b += K[CV1] D1;  b += K[CV2] D2 if K[CV2] != 0;  b += K[CV3] D3 if K[CV3] != 0
+ *     otherwise b = x
+ *     acc = K[CX] b + K[W0] D0;  acc += K[W1] D1 if K[W1] != 0;  acc += K[W2] D2 if K[W2] != 0      (the predictor)
+ * then x = acc and xc = b in place (xc when given), hist[row % 4] = D0, t_out[n] = K[T_NEXT] and, on a row with FLAG_LAST,
+ * out = clamp(acc, -1, 1).  pred_xstart = D0 is written when not NULL.  A NaN in eps reaches x' (the clamps pass it); images do not
+ * mix.  The solver adds no noise: there is no z, no sample_index, no draw and no seed.
+ * History: hist is fp32 [4][N][CHW].  D1, D2 and D3 are read from slots (row + 3) % 4, (row + 2) % 4 and (row + 1) % 4, derived in
+ *   the kernel from the row number.  Slot j is read only if one of its two weights (K[Wj]; K[CVj] on a corrected row) is not 0.
+ * xc: fp32 [N, CHW], read only on a row with FLAG_CORR, written on every row.  xc == NULL means "no corrected state": every row
+ *   runs uncorrected, whatever its flags, and reads what its predictor alone reads.  xc == x is DXMI_EINVAL.
+ * DXMI_UNIPC_FIRST writes t_out[n] = K[T] only (the first evaluation's time); x, xc, eps, hist, out may be NULL.
+ * Control: ctl NULL: row is the by-value argument, and row outside [0, rows) is DXMI_EINVAL.  ctl not NULL: an int32[4] block on
+ *   the DEVICE whose first word is the row (the layout of dxmi_dpm_stage's block; the other three words are not read); a row outside
+ *   [0, rows) read there gives NaN in x, xc, out, t_out and slot 0 of the history; nothing outside the table, no history slot and
+ *   no xc is read.
+ * tab: fp32 [rows][DXMI_UT_COLS] on the device.  x, xc, eps, hist, out, pred_xstart: 16-byte aligned; CHW % 4 != 0 takes 4-byte
+ * aligned vector accesses and a scalar tail.  N in [1, 65535].  No workspace, no LDS, no atomics.
+ * The table: the columns of DXMI_MT_* (the solver has no noise: S's place holds the corrector's order) and the corrector's five. */
+#define DXMI_UNIPC_FIRST   0
+#define DXMI_UNIPC_STEP    1
+#define DXMI_UT_T          0   /* time of the evaluation the launch follows: (float)tau */
+#define DXMI_UT_T_NEXT     1   /* time of the next evaluation (0 on the last row) */
+#define DXMI_UT_CX         2   /* sigma_{k+1} / sigma_k; 0 on the last row */
+#define DXMI_UT_W0         3   /* predictor weight of D_k (1 on the last row) */
+#define DXMI_UT_W1         4   /* predictor weight of D_{k-1} */
+#define DXMI_UT_W2         5   /* predictor weight of D_{k-2} */
+#define DXMI_UT_CORDER     6   /* the corrector's order q (0: the row is not corrected); not read by the kernel */
+#define DXMI_UT_A          7   /* 1 / alpha_k */
+#define DXMI_UT_B          8   /* sigma_k / alpha_k */
+#define DXMI_UT_FLAGS      9   /* DXMI_UT_FLAG_* summed, stored as a float */
+#define DXMI_UT_ORDER     10   /* the predictor's order p (1-3); not read by the kernel */
+#define DXMI_UT_CCX       11   /* sigma_k / sigma_{k-1}: the corrector's factor of xc */
+#define DXMI_UT_CV0       12   /* corrector weight of D_k */
+#define DXMI_UT_CV1       13   /* corrector weight of D_{k-1} */
+#define DXMI_UT_CV2       14   /* corrector weight of D_{k-2}; 0 below q = 2 */
+#define DXMI_UT_CV3       15   /* corrector weight of D_{k-3}; 0 below q = 3 */
+#define DXMI_UT_COLS      16
+#define DXMI_UT_FLAG_CLIP  1
+#define DXMI_UT_FLAG_LAST  2
+#define DXMI_UT_FLAG_CORR  4
+int dxmi_unipc_stage(int32_t mode, const float* tab, int32_t rows, const int32_t* ctl, int32_t row, float* x, float* xc,
+                     const float* eps, float* hist, float* t_out, float* out, float* pred_xstart, int32_t N, int32_t CHW,
+                     void* stream);
+
+/* UniPC sampling of the EDM nets (csrc/edm_unipc_sample.hip; models/cm/unipc_sample.py): dxmi_unipc_stage's solver in
+ * the EDM parametrisation x = x_0 + sigma e (alpha = 1, lambda = -ln sigma) with the Karras preconditioning inside the launch, as
+ * dxmi_edm_dpm_stage has it (UniPC has no reference call site: the reference tree has no such sampler).  With F = model_out the
+ * output of evaluation k = row at c_in(sigma_k) x and K = tab[row]:
+ *     D0  = K[COUT] F + K[CSKIP] x;  FLAG_CLIP: D0 = clamp(D0, -1, 1)
+ *     b and acc as dxmi_unipc_stage forms them
+ * then x = acc and xc = b in place, hist[row % 4] = D0, t_out[n] = K[T_NEXT], on a row without FLAG_LAST x_in = K[CIN_NEXT] acc and,
+ * on the row with FLAG_LAST, out = clamp(acc, -1, 1).  History, xc and the control block as dxmi_unipc_stage (a poisoned row gives
+ * NaN in x_in too); DXMI_EDM_UNIPC_FIRST and the x_in == NULL rule as dxmi_edm_dpm_stage.
+ * tab: fp32 [rows][DXMI_EUT_COLS]: the columns of DXMI_ET_* (S's place holds the corrector's order) and the corrector's five. */
+#define DXMI_EDM_UNIPC_FIRST 0
+#define DXMI_EDM_UNIPC_STEP  1
+#define DXMI_EUT_T         0   /* time of the evaluation the launch follows: 250 ln(sigma_k + 1e-44) */
+#define DXMI_EUT_T_NEXT    1   /* time of the next evaluation (0 on the last row) */
+#define DXMI_EUT_CX        2   /* sigma_{k+1} / sigma_k; 0 on the last row */
+#define DXMI_EUT_W0        3   /* predictor weight of D_k (1 on the last row) */
+#define DXMI_EUT_W1        4   /* predictor weight of D_{k-1} */
+#define DXMI_EUT_W2        5   /* predictor weight of D_{k-2} */
+#define DXMI_EUT_CORDER    6   /* the corrector's order q (0: the row is not corrected); not read by the kernel */
+#define DXMI_EUT_CSKIP     7   /* c_skip(sigma_k) */
+#define DXMI_EUT_COUT      8   /* c_out(sigma_k) */
+#define DXMI_EUT_FLAGS     9   /* DXMI_EUT_FLAG_* summed, stored as a float */
+#define DXMI_EUT_ORDER    10   /* the predictor's order p (1-3); not read by the kernel */
+#define DXMI_EUT_CIN      11   /* c_in(sigma_k): FIRST's factor of x_in */
+#define DXMI_EUT_CIN_NEXT 12   /* c_in(sigma_{k+1}) (0 on the last row, where x_in is not written) */
+#define DXMI_EUT_XSCALE   13   /* FIRST's factor of x: sigma_max */
+#define DXMI_EUT_SIGMA    14   /* sigma_k; not read by the kernel */
+#define DXMI_EUT_CCX      15   /* sigma_k / sigma_{k-1}: the corrector's factor of xc */
+#define DXMI_EUT_CV0      16   /* corrector weight of D_k */
+#define DXMI_EUT_CV1      17   /* corrector weight of D_{k-1} */
+#define DXMI_EUT_CV2      18   /* corrector weight of D_{k-2}; 0 below q = 2 */
+#define DXMI_EUT_CV3      19   /* corrector weight of D_{k-3}; 0 below q = 3 */
+#define DXMI_EUT_COLS     20
+#define DXMI_EUT_FLAG_CLIP 1
+#define DXMI_EUT_FLAG_LAST 2
+#define DXMI_EUT_FLAG_CORR 4
+int dxmi_edm_unipc_stage(int32_t mode, const float* tab, int32_t rows, const int32_t* ctl, int32_t row, float* x, float* xc,
+                         const float* model_out, float* hist, float* x_in, float* t_out, float* out, float* pred_xstart, int32_t N,
+                         int32_t CHW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
