@@ -30,6 +30,12 @@ discretised lognormal over the levels; uniform = the reference's randint), --sca
 --end_scales over --total_training_steps) and --start_ema 0 (the target is the student of the step before).  --ict True sets all of these
 at once (loss_norm, weight_schedule, scale_mode, target_ema_mode fixed, start_ema 0, start_scales 10, end_scales 1280, index_sampler
 lognormal) and takes --training_mode consistency_training, which it also selects where no --training_mode is given; any other is an error.
+--training_mode dm is distribution matching distillation of the teacher into a ONE-step generator (models.cm.train_util.DMTrainLoop over
+KarrasDenoiser.dm_generator_losses; Diff-Instruct / DMD / DMD2 without its GAN term): generator and fake denoiser start from
+--teacher_model_path, the data are latents and uniform labels from a device generator seeded seed + rank, so neither --data_npz (refused)
+nor --synthetic_data is needed; --gen_update_every (5), --fake_lr (0 = --lr), --dm_weighting dmd|none, --dm_num_scales (1000).  The sigma
+levels of the fake denoiser's loss are EDM's (LogNormalSampler's defaults, as train_edm.py draws them).  --ict, a --loss_norm other than the default and
+--index_sampler lognormal are errors with it.  Its model%06d.pt is what `generate_large.py --karras_sampler dm --pretrained ...` reads.
 """
 import argparse
 import os
@@ -41,7 +47,7 @@ from dxmi_hip import dist as _dist
 from dxmi_hip import graph as _graph
 from models.cm.script_util import (add_dict_to_argparser, args_to_dict, cm_train_defaults, create_ema_and_scales_fn,
                                    create_model_and_diffusion, model_and_diffusion_defaults)
-from models.cm.train_util import CMTrainLoop
+from models.cm.train_util import CMTrainLoop, DMTrainLoop
 
 
 def print0(*a):
@@ -55,6 +61,15 @@ def synthetic_batches(batch_size, image_size, class_cond, device, seed):
         x = torch.rand(batch_size, 3, image_size, image_size, device=device, generator=gen) * 2 - 1
         cond = {"y": torch.randint(0, 1000, (batch_size,), device=device, generator=gen)} if class_cond else {}
         yield x, cond
+
+
+def latent_batches(batch_size, image_size, class_cond, device, seed, num_classes=1000):
+    """The `data=` iterator of DMTrainLoop: standard-normal latents of the image shape and uniform labels, from a device generator."""
+    gen = torch.Generator(device=device).manual_seed(seed)
+    while True:
+        z = torch.randn(batch_size, 3, image_size, image_size, device=device, generator=gen)
+        cond = {"y": torch.randint(0, num_classes, (batch_size,), device=device, generator=gen)} if class_cond else {}
+        yield z, cond
 
 
 def make_loader(args, device, rank, world):
@@ -82,12 +97,28 @@ def parse_args(argv=None):
                     log_dir="results/cm_train",
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
                     fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False,
-                    huber_c=0.0, index_sampler="uniform", p_mean=-1.1, p_std=2.0, ict=False)
+                    huber_c=0.0, index_sampler="uniform", p_mean=-1.1, p_std=2.0, ict=False, gen_update_every=5, fake_lr=0.0,
+                    dm_weighting="dmd", dm_num_scales=1000)
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
     args = ap.parse_args(argv)
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")
+    if args.training_mode == "dm":
+        if args.data_npz:
+            ap.error("--data_npz does not go with --training_mode dm: distribution matching trains on latents alone, it reads no images")
+        if args.ict:
+            ap.error("--ict True is improved consistency TRAINING: --training_mode dm does not go with it")
+        if args.loss_norm != cm_train_defaults()["loss_norm"]:
+            ap.error(f"--loss_norm {args.loss_norm} belongs to the consistency and progdist losses, not to --training_mode dm")
+        if args.index_sampler == "lognormal":
+            ap.error("--index_sampler lognormal belongs to the consistency losses, not to --training_mode dm")
+        if args.dm_weighting not in ("dmd", "none"):
+            ap.error(f"--dm_weighting {args.dm_weighting!r}: dmd or none")
+        if args.gen_update_every < 1 or args.dm_num_scales < 2 or args.fake_lr < 0:
+            ap.error("--gen_update_every must be >= 1, --dm_num_scales >= 2 and --fake_lr >= 0 (0: --lr)")
+        if args.use_graph:
+            ap.error("--use_graph True does not go with --training_mode dm (two update clocks; DMTrainLoop refuses it)")
     if args.ict:
         given = any(a == "--training_mode" or a.startswith("--training_mode=") for a in (sys.argv[1:] if argv is None else argv))
         if given and args.training_mode != "consistency_training":
@@ -124,6 +155,8 @@ def main():
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.distributed.init_process_group(backend=_dist.dist_backend(), init_method="env://")   # RCCL
+    if args.training_mode == "dm":
+        return main_dm(args, device, local_rank, world)
     data, store = make_loader(args, device, local_rank, world)
     if store is not None:
         print0(store.describe())
@@ -185,6 +218,40 @@ def main():
         print0("last log row:", loop.logged[-1])
     if store is not None:
         store.close()
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def main_dm(args, device, local_rank, world):
+    """--training_mode dm: generator and fake denoiser start from the teacher, which stays frozen as the real denoiser."""
+    from models.cm.resample import LogNormalSampler
+    model_kw = args_to_dict(args, model_and_diffusion_defaults().keys())
+    model, diffusion = create_model_and_diffusion(distillation=False, **model_kw)
+    fake_model = create_model_and_diffusion(distillation=False, **model_kw)[0]
+    real_model, real_diffusion = create_model_and_diffusion(distillation=False, **dict(model_kw, dropout=args.teacher_dropout))
+    if args.teacher_model_path:
+        real_model.load_state_dict(torch.load(args.teacher_model_path, map_location="cpu"))
+        print0(f"teacher loaded from {args.teacher_model_path}")
+    else:
+        print0("no --teacher_model_path: the teacher keeps its random initialisation (smoke runs)")
+    model.load_state_dict(real_model.state_dict())
+    fake_model.load_state_dict(real_model.state_dict())
+    real_model.to(device).eval()
+    model.to(device).train()
+    fake_model.to(device).train()
+    data = latent_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + local_rank)
+    loop = DMTrainLoop(model=model, diffusion=diffusion, real_model=real_model, real_diffusion=real_diffusion, fake_model=fake_model,
+                       num_scales=args.dm_num_scales, gen_update_every=args.gen_update_every, fake_lr=args.fake_lr or None,
+                       weighting=args.dm_weighting, data=data, batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr,
+                       ema_rate=args.ema_rate, log_interval=args.log_interval, save_interval=args.save_interval,
+                       resume_checkpoint=args.resume_checkpoint, use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth,
+                       schedule_sampler=LogNormalSampler(), weight_decay=args.weight_decay,
+                       lr_anneal_steps=args.max_iters if args.max_iters else args.lr_anneal_steps, log_dir=args.log_dir)
+    print0(f"dm: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), weighting {args.dm_weighting}, "
+           f"generator update every {args.gen_update_every} iterations")
+    loop.run_loop()
+    if loop.logged:
+        print0("last log row:", loop.logged[-1])
     if world > 1:
         torch.distributed.destroy_process_group()
 

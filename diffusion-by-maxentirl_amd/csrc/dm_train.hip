@@ -1,0 +1,412 @@
+// Distribution matching distillation of the EDM teacher into a one-step generator G(z) = D_theta(sigma_G z, sigma_G): Diff-Instruct
+// (Luo et al. 2023, eq. 8 / Algorithm 1), DMD (Yin et al. 2023, eq. 7-8) and DMD2 (Yin et al. 2024, eq. 2-3) without its GAN term.
+// The launches between the three network evaluations of one generator step (KarrasDenoiser.dm_generator_losses):
+//   dxmi_dm_gen_in     latents -> generator: x_in = c_in(sigma_G) (sigma_G z), time = 250 ln(sigma_G + 1e-44)
+//   dxmi_dm_gen_out    generator -> images (sampling): x = c_skip(sigma_G) (sigma_G z) + c_out(sigma_G) F_g, clamped when asked
+//   dxmi_dm_gen_prep   generator -> the real and the fake denoiser (training): the same x, t = tab[idx], x_t = x + noise t, the
+//                      inputs of both nets and their time, in one launch (F_g, z and noise are read once)
+//   dxmi_dm_grad_fwd   after both denoisers: D_r, D_f, s = mean|x - D_r|, g = (D_f - D_r) / s (DMD eq. 8) or D_f - D_r (Diff-Instruct),
+//                      loss = 0.5 mean(g^2); one workgroup per image
+//   dxmi_dm_gen_bwd    dF_g = upstream c_out(sigma_G) g / CHW: the gradient reaches the generator through x only (DMD eq. 7)
+// Conventions of cm_train.hip / pd_train.hip: fp32, one rounding per written operation, 16 bytes per lane, several loads in flight,
+// per-sample sums in a fixed order (bitwise reproducible), no atomics.  The level is gathered from the device table of S entries
+// (cd_levels) by an int64 index; these launches need only t, so the index S - 1 is legal.  An index outside [0, S - 1] gives a NaN
+// level (nothing is read outside the table).
+#include "common.h"
+
+// one rounding per written operation: no fused multiply-add between them
+#pragma clang fp contract(off)
+#include "dsm_common.h"
+
+namespace {
+
+constexpr int EW_BLOCK = 256;
+constexpr int EW_UNROLL = 4;      // f32x4 per stream per lane in flight
+// dm_grad_fwd keeps D_f - D_r of a whole image in registers between its two sums: at most DM_REG_V4 f32x4 (48 fp32 VGPRs) per lane,
+// i.e. CHW <= 256 * 4 * DM_REG_V4 = 12288 = 3x64x64, the largest image of the programs here.  A larger image takes the two-pass
+// kernel.  (The compiler issues all 48 loads of a lane before the first use: 244 VGPRs + 16 AGPRs, no scratch, one wave per SIMD,
+// which one workgroup per image does not feel.)
+constexpr int DM_REG_V4 = 12;
+constexpr int DM_REG_CHW = EW_BLOCK * 4 * DM_REG_V4;
+
+__device__ __forceinline__ float dm_level(const int64_t* __restrict__ idx, const float* __restrict__ tab, int S, int b) {
+    const int64_t i = idx[b];
+    return (i >= 0 && i < (int64_t)S) ? tab[i] : __builtin_nanf("");
+}
+
+__device__ __forceinline__ float dm_c_in(float s, float sd2) { return 1.f / __builtin_sqrtf(s * s + sd2); }
+__device__ __forceinline__ float dm_time(float s) { return 250.f * logf(s + 1e-44f); }      // 1000 * 0.25 * th.log(sigmas + 1e-44)
+
+__device__ __forceinline__ f32x4 ld4(const float* p, size_t base, int i) { return *reinterpret_cast<const f32x4*>(p + base + (size_t)i * 4); }
+__device__ __forceinline__ void st4(float* p, size_t base, int i, f32x4 v) { *reinterpret_cast<f32x4*>(p + base + (size_t)i * 4) = v; }
+
+// EDM scalings of the generator's diffusion at sigma_G (distillation=False)
+__device__ __forceinline__ DsmScal dm_gen_scalings(float sg, float sd, float sd2) {
+    return dsm_scalings(sg, sd, sd2, 0.f, 0, DXMI_DSM_W_UNIFORM, 0.f);
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void dm_gen_in_kernel(const float* __restrict__ z, float* __restrict__ x_in, float* __restrict__ t_out,
+                                                             int CHW, float sg, float sd2) {
+    const int b = blockIdx.y;
+    const float c_in = dm_c_in(sg, sd2);
+    if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dm_time(sg);
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
+        f32x4 zv[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u)
+            if (i0 + u * EW_BLOCK < n4) zv[u] = ld4(z, base, i0 + u * EW_BLOCK);
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i >= n4) continue;
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = c_in * (zv[u][e] * sg);
+            st4(x_in, base, i, o);
+        }
+    }
+}
+
+// PREP = 0: dxmi_dm_gen_out (x, clamped when asked).  PREP = 1: dxmi_dm_gen_prep (x, x_t and the inputs of the two denoisers).
+template <int PREP>
+__global__ __launch_bounds__(EW_BLOCK) void dm_gen_x_kernel(const float* __restrict__ Fg, const float* __restrict__ z,
+                                                            const float* __restrict__ noise, const int64_t* __restrict__ idx,
+                                                            const float* __restrict__ tab, int S, float* __restrict__ x,
+                                                            float* __restrict__ x_t, float* __restrict__ x_in_real,
+                                                            float* __restrict__ t_out, float* __restrict__ x_in_fake, int CHW, float sg,
+                                                            float sd, float sd2, float sd2_real, float sd2_fake, int clip) {
+    const int b = blockIdx.y;
+    const DsmScal c = dm_gen_scalings(sg, sd, sd2);
+    float t = 0.f, cr = 0.f, cf = 0.f;
+    if (PREP) {
+        t = dm_level(idx, tab, S, b);
+        cr = dm_c_in(t, sd2_real);
+        cf = dm_c_in(t, sd2_fake);
+        if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dm_time(t);
+    }
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
+        f32x4 fv[EW_UNROLL], zv[EW_UNROLL], nv[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i < n4) {
+                fv[u] = ld4(Fg, base, i);
+                zv[u] = ld4(z, base, i);
+                if (PREP) nv[u] = ld4(noise, base, i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i >= n4) continue;
+            f32x4 xo, xt, ir, jf;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = c.c_out * fv[u][e] + c.c_skip * (zv[u][e] * sg);          // denoise() at sigma_G
+                if (!PREP && clip) v = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);      // th.clamp(-1, 1): NaN passes
+                xo[e] = v;
+                if (PREP) {
+                    xt[e] = v + nv[u][e] * t;
+                    ir[e] = cr * xt[e];
+                    jf[e] = cf * xt[e];
+                }
+            }
+            st4(x, base, i, xo);
+            if (PREP) {
+                st4(x_t, base, i, xt);
+                st4(x_in_real, base, i, ir);
+                if (x_in_fake) st4(x_in_fake, base, i, jf);
+            }
+        }
+    }
+}
+
+// fixed order: a lane's running sum in index order, the xor-shuffle tree of a wave, a fixed pairing of the four wave partials
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// s == 0: the sample sits on the teacher's denoised image already, and the normalised direction does not exist: g = 0
+__device__ __forceinline__ float dm_g(float df, float s, int weighting) {
+    if (s == 0.f) return 0.f;
+    return weighting == DXMI_DM_W_DMD ? df / s : df;
+}
+
+// One workgroup per image, the image's D_f - D_r in registers (NV f32x4 per lane): every input is read from memory once.
+template <int NV>
+__global__ __launch_bounds__(EW_BLOCK) void dm_grad_fwd_reg_kernel(const float* __restrict__ Fr, const float* __restrict__ Ff,
+                                                                   const float* __restrict__ x, const float* __restrict__ x_t,
+                                                                   const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
+                                                                   float* __restrict__ g, float* __restrict__ loss, float* __restrict__ s_out,
+                                                                   int CHW, int weighting, float sdr, float sdr2,
+                                                                   float smin_r, int dist_r, float sdf, float sdf2, float smin_f, int dist_f) {
+    __shared__ float red[2][EW_BLOCK / 64];
+    const int b = blockIdx.x;
+    const float t = dm_level(idx, tab, S, b);
+    const DsmScal cr = dsm_scalings(t, sdr, sdr2, smin_r, dist_r, DXMI_DSM_W_UNIFORM, 0.f);
+    const DsmScal cf = dsm_scalings(t, sdf, sdf2, smin_f, dist_f, DXMI_DSM_W_UNIFORM, 0.f);
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    f32x4 df[NV];
+    float acc = 0.f;
+#pragma unroll
+    for (int k0 = 0; k0 < NV; k0 += EW_UNROLL) {
+        f32x4 fr[EW_UNROLL], ff[EW_UNROLL], xv[EW_UNROLL], xt[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = threadIdx.x + (k0 + u) * EW_BLOCK;
+            if (i < n4) {
+                fr[u] = ld4(Fr, base, i);
+                ff[u] = ld4(Ff, base, i);
+                xv[u] = ld4(x, base, i);
+                xt[u] = ld4(x_t, base, i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = threadIdx.x + (k0 + u) * EW_BLOCK;
+            if (i >= n4) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float dr = cr.c_out * fr[u][e] + cr.c_skip * xt[u][e];
+                const float dfk = cf.c_out * ff[u][e] + cf.c_skip * xt[u][e];
+                df[k0 + u][e] = dfk - dr;
+                acc += __builtin_fabsf(xv[u][e] - dr);
+            }
+        }
+    }
+    const float s = block_sum(acc, red[0]) / (float)CHW;
+    float acc2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int i = threadIdx.x + k * EW_BLOCK;
+        if (i >= n4) continue;
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o[e] = dm_g(df[k][e], s, weighting);
+            acc2 += o[e] * o[e];
+        }
+        st4(g, base, i, o);
+    }
+    const float tot2 = block_sum(acc2, red[1]);
+    if (threadIdx.x == 0) {
+        s_out[b] = s;
+        loss[b] = 0.5f * (tot2 / (float)CHW);
+    }
+}
+
+// The same for an image above the register budget: a second pass over the inputs forms D_f - D_r again (the same operations on
+// the same operands: the same bits).
+__global__ __launch_bounds__(EW_BLOCK) void dm_grad_fwd_2pass_kernel(const float* __restrict__ Fr, const float* __restrict__ Ff,
+                                                                     const float* __restrict__ x, const float* __restrict__ x_t,
+                                                                     const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
+                                                                     float* __restrict__ g, float* __restrict__ loss, float* __restrict__ s_out,
+                                                                     int CHW, int weighting, float sdr, float sdr2, float smin_r, int dist_r,
+                                                                     float sdf, float sdf2, float smin_f, int dist_f) {
+    __shared__ float red[2][EW_BLOCK / 64];
+    const int b = blockIdx.x;
+    const float t = dm_level(idx, tab, S, b);
+    const DsmScal cr = dsm_scalings(t, sdr, sdr2, smin_r, dist_r, DXMI_DSM_W_UNIFORM, 0.f);
+    const DsmScal cf = dsm_scalings(t, sdf, sdf2, smin_f, dist_f, DXMI_DSM_W_UNIFORM, 0.f);
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    float acc = 0.f;
+    for (int i0 = threadIdx.x; i0 < n4; i0 += EW_BLOCK * EW_UNROLL) {
+        f32x4 fr[EW_UNROLL], xv[EW_UNROLL], xt[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i < n4) {
+                fr[u] = ld4(Fr, base, i);
+                xv[u] = ld4(x, base, i);
+                xt[u] = ld4(x_t, base, i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            if (i0 + u * EW_BLOCK >= n4) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc += __builtin_fabsf(xv[u][e] - (cr.c_out * fr[u][e] + cr.c_skip * xt[u][e]));
+        }
+    }
+    const float s = block_sum(acc, red[0]) / (float)CHW;
+    float acc2 = 0.f;
+    for (int i0 = threadIdx.x; i0 < n4; i0 += EW_BLOCK * EW_UNROLL) {
+        f32x4 fr[EW_UNROLL], ff[EW_UNROLL], xt[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i < n4) {
+                fr[u] = ld4(Fr, base, i);
+                ff[u] = ld4(Ff, base, i);
+                xt[u] = ld4(x_t, base, i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i >= n4) continue;
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float dr = cr.c_out * fr[u][e] + cr.c_skip * xt[u][e];
+                const float dfk = cf.c_out * ff[u][e] + cf.c_skip * xt[u][e];
+                o[e] = dm_g(dfk - dr, s, weighting);
+                acc2 += o[e] * o[e];
+            }
+            st4(g, base, i, o);
+        }
+    }
+    const float tot2 = block_sum(acc2, red[1]);
+    if (threadIdx.x == 0) {
+        s_out[b] = s;
+        loss[b] = 0.5f * (tot2 / (float)CHW);
+    }
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void dm_gen_bwd_kernel(const float* __restrict__ up, const float* __restrict__ g,
+                                                              float* __restrict__ dF, int CHW, float c_out, float invD) {
+    const int b = blockIdx.y;
+    const float gs = up[b] * invD;              // mean -> / CHW
+    const size_t base = (size_t)b * CHW;
+    const int n4 = CHW / 4;
+    for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
+        f32x4 gv[EW_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u)
+            if (i0 + u * EW_BLOCK < n4) gv[u] = ld4(g, base, i0 + u * EW_BLOCK);
+#pragma unroll
+        for (int u = 0; u < EW_UNROLL; ++u) {
+            const int i = i0 + u * EW_BLOCK;
+            if (i >= n4) continue;
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (gs * gv[u][e]) * c_out;
+            st4(dF, base, i, o);
+        }
+    }
+}
+
+bool dm_aligned(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr,
+                const void* f = nullptr, const void* g = nullptr) {
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f) | ((uintptr_t)g)) & 15) == 0;
+}
+
+dim3 dm_grid(int N, int CHW) {
+    const int chunks = (CHW / 4 + EW_BLOCK * EW_UNROLL - 1) / (EW_BLOCK * EW_UNROLL);
+    return dim3(chunks < 64 ? chunks : 64, N);
+}
+
+// c_out(sigma_G) with the device's operations, for the backward's scalar
+float dm_host_c_out(float sg, float sd) {
+    const float den = sg * sg + sd * sd;
+    return (sg * sd) / __builtin_sqrtf(den);
+}
+
+}  // namespace
+
+#define DM_CHECK_SHAPE(fn)                                                                                                       \
+    DXMI_CHECK_ARG(N > 0 && N <= 65535 && CHW > 0 && CHW % 4 == 0 && CHW < (1 << 30), fn ": N (%d) must be in [1, 65535] and "   \
+                   "CHW (%d) a positive multiple of 4 below 2^30", N, CHW)
+#define DM_CHECK_SCALES(fn)                                                                                                      \
+    DXMI_CHECK_ARG(num_scales >= 1 && num_scales < (1 << 30), fn ": num_scales (%d) must be in [1, 2^30)", num_scales)
+#define DM_CHECK_POS(fn, v, what)                                                                                                \
+    DXMI_CHECK_ARG((v) > 0.f && (v) <= 3.0e38f, fn ": " what " (%g) must be positive and finite", (double)(v))
+
+extern "C" int dxmi_dm_gen_in(const float* z, float* x_in, float* t_out, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
+                              void* stream) {
+    DXMI_CHECK_ARG(z && x_in && t_out, "dxmi_dm_gen_in: null pointer");
+    DM_CHECK_SHAPE("dxmi_dm_gen_in");
+    DM_CHECK_POS("dxmi_dm_gen_in", gen_sigma, "gen_sigma");
+    DM_CHECK_POS("dxmi_dm_gen_in", sigma_data, "sigma_data");
+    DXMI_CHECK_ARG(dm_aligned(z, x_in), "dxmi_dm_gen_in: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL(dm_gen_in_kernel, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, z, x_in, t_out, CHW, gen_sigma,
+                       sigma_data * sigma_data);
+    DXMI_CHECK_LAUNCH("dxmi_dm_gen_in");
+    return DXMI_OK;
+}
+
+extern "C" int dxmi_dm_gen_out(const float* f_gen, const float* z, float* x, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
+                               int32_t clip, void* stream) {
+    DXMI_CHECK_ARG(f_gen && z && x, "dxmi_dm_gen_out: null pointer");
+    DM_CHECK_SHAPE("dxmi_dm_gen_out");
+    DM_CHECK_POS("dxmi_dm_gen_out", gen_sigma, "gen_sigma");
+    DM_CHECK_POS("dxmi_dm_gen_out", sigma_data, "sigma_data");
+    DXMI_CHECK_ARG(dm_aligned(f_gen, z, x), "dxmi_dm_gen_out: tensors must be 16-byte aligned");
+    const float sd2 = sigma_data * sigma_data;
+    hipLaunchKernelGGL(dm_gen_x_kernel<0>, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_gen, z, (const float*)nullptr,
+                       (const int64_t*)nullptr, (const float*)nullptr, 0, x, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, CHW, gen_sigma, sigma_data, sd2, 0.f, 0.f, (int)(clip != 0));
+    DXMI_CHECK_LAUNCH("dxmi_dm_gen_out");
+    return DXMI_OK;
+}
+
+extern "C" int dxmi_dm_gen_prep(const float* f_gen, const float* z, const float* noise, const int64_t* indices, const float* t_table,
+                                int32_t num_scales, float* x, float* x_t, float* x_in_real, float* t_out, float* x_in_fake, int32_t N,
+                                int32_t CHW, float gen_sigma, float gen_sigma_data, float real_sigma_data, float fake_sigma_data,
+                                void* stream) {
+    DXMI_CHECK_ARG(f_gen && z && noise && indices && t_table && x && x_t && x_in_real && t_out, "dxmi_dm_gen_prep: null pointer");
+    DM_CHECK_SHAPE("dxmi_dm_gen_prep");
+    DM_CHECK_SCALES("dxmi_dm_gen_prep");
+    DM_CHECK_POS("dxmi_dm_gen_prep", gen_sigma, "gen_sigma");
+    DM_CHECK_POS("dxmi_dm_gen_prep", gen_sigma_data, "sigma_data");
+    DM_CHECK_POS("dxmi_dm_gen_prep", real_sigma_data, "sigma_data");
+    DM_CHECK_POS("dxmi_dm_gen_prep", fake_sigma_data, "sigma_data");
+    DXMI_CHECK_ARG(dm_aligned(f_gen, z, noise, x, x_t, x_in_real, x_in_fake), "dxmi_dm_gen_prep: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL(dm_gen_x_kernel<1>, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_gen, z, noise, indices, t_table,
+                       num_scales, x, x_t, x_in_real, t_out, x_in_fake, CHW, gen_sigma, gen_sigma_data, gen_sigma_data * gen_sigma_data,
+                       real_sigma_data * real_sigma_data, fake_sigma_data * fake_sigma_data, 0);
+    DXMI_CHECK_LAUNCH("dxmi_dm_gen_prep");
+    return DXMI_OK;
+}
+
+extern "C" int dxmi_dm_grad_fwd(const float* f_real, const float* f_fake, const float* x, const float* x_t, const int64_t* indices,
+                                const float* t_table, int32_t num_scales, float* g, float* loss, float* s, int32_t N, int32_t CHW,
+                                int32_t weighting, float real_sigma_data, float real_sigma_min, int32_t real_distillation,
+                                float fake_sigma_data, float fake_sigma_min, int32_t fake_distillation, void* stream) {
+    DXMI_CHECK_ARG(f_real && f_fake && x && x_t && indices && t_table && g && loss && s, "dxmi_dm_grad_fwd: null pointer");
+    DM_CHECK_SHAPE("dxmi_dm_grad_fwd");
+    DM_CHECK_SCALES("dxmi_dm_grad_fwd");
+    DXMI_CHECK_ARG(weighting == DXMI_DM_W_DMD || weighting == DXMI_DM_W_NONE, "dxmi_dm_grad_fwd: unknown weighting %d", weighting);
+    DM_CHECK_POS("dxmi_dm_grad_fwd", real_sigma_data, "sigma_data");
+    DM_CHECK_POS("dxmi_dm_grad_fwd", fake_sigma_data, "sigma_data");
+    DXMI_CHECK_ARG(dm_aligned(f_real, f_fake, x, x_t, g), "dxmi_dm_grad_fwd: tensors must be 16-byte aligned");
+    const dim3 grid(N), block(EW_BLOCK);
+    const float sdr2 = real_sigma_data * real_sigma_data, sdf2 = fake_sigma_data * fake_sigma_data;
+    const int dr = (int)(real_distillation != 0), df = (int)(fake_distillation != 0);
+    if (CHW <= EW_BLOCK * 4 * 4)
+        hipLaunchKernelGGL(dm_grad_fwd_reg_kernel<4>, grid, block, 0, (hipStream_t)stream, f_real, f_fake, x, x_t, indices, t_table,
+                           num_scales, g, loss, s, CHW, weighting, real_sigma_data, sdr2, real_sigma_min, dr, fake_sigma_data, sdf2,
+                           fake_sigma_min, df);
+    else if (CHW <= DM_REG_CHW)
+        hipLaunchKernelGGL(dm_grad_fwd_reg_kernel<DM_REG_V4>, grid, block, 0, (hipStream_t)stream, f_real, f_fake, x, x_t, indices, t_table,
+                           num_scales, g, loss, s, CHW, weighting, real_sigma_data, sdr2, real_sigma_min, dr, fake_sigma_data, sdf2,
+                           fake_sigma_min, df);
+    else
+        hipLaunchKernelGGL(dm_grad_fwd_2pass_kernel, grid, block, 0, (hipStream_t)stream, f_real, f_fake, x, x_t, indices, t_table,
+                           num_scales, g, loss, s, CHW, weighting, real_sigma_data, sdr2, real_sigma_min, dr, fake_sigma_data, sdf2,
+                           fake_sigma_min, df);
+    DXMI_CHECK_LAUNCH("dxmi_dm_grad_fwd");
+    return DXMI_OK;
+}
+
+extern "C" int dxmi_dm_gen_bwd(const float* upstream, const float* g, float* d_f_gen, int32_t N, int32_t CHW, float gen_sigma,
+                               float sigma_data, void* stream) {
+    DXMI_CHECK_ARG(upstream && g && d_f_gen, "dxmi_dm_gen_bwd: null pointer");
+    DM_CHECK_SHAPE("dxmi_dm_gen_bwd");
+    DM_CHECK_POS("dxmi_dm_gen_bwd", gen_sigma, "gen_sigma");
+    DM_CHECK_POS("dxmi_dm_gen_bwd", sigma_data, "sigma_data");
+    DXMI_CHECK_ARG(dm_aligned(g, d_f_gen), "dxmi_dm_gen_bwd: tensors must be 16-byte aligned");
+    hipLaunchKernelGGL(dm_gen_bwd_kernel, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, upstream, g, d_f_gen, CHW,
+                       dm_host_c_out(gen_sigma, sigma_data), (float)(1.0 / (double)CHW));
+    DXMI_CHECK_LAUNCH("dxmi_dm_gen_bwd");
+    return DXMI_OK;
+}

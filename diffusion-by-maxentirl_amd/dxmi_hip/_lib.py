@@ -138,6 +138,12 @@ SIGNATURES = {
     "dxmi_pd_loss_fwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p] + [c_int] * 3 + [c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_pd_loss_bwd": (c_int, [c_void_p] * 6 + [c_int, c_void_p] + [c_int] * 3 + [c_float, c_float, c_int, c_int, c_void_p]),
     "dxmi_pd_lpips_images": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
+    "dxmi_dm_gen_in": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_void_p]),
+    "dxmi_dm_gen_out": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_int, c_void_p]),
+    "dxmi_dm_gen_prep": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 5 + [c_int, c_int] + [c_float] * 4 + [c_void_p]),
+    "dxmi_dm_grad_fwd": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_float,
+                                                                             c_int, c_void_p]),
+    "dxmi_dm_gen_bwd": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_void_p]),
     "dxmi_karras_stage": (c_int, [c_int, c_int, c_void_p, c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
     "dxmi_cm_stage": (c_int, [c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 10 + [c_int] * 4 + [c_void_p]),
     "dxmi_quantize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1258,6 +1258,126 @@ def pd_loss_bwd(g_loss, f_online, x_t, target_x, indices, t_table, loss_norm, we
     return d
 
 
+# dxmi_dm_grad_fwd weightings (include/dxmi_hip.h): DMD's normaliser mean|x - D_real|, or Diff-Instruct's plain score difference
+DM_WEIGHTINGS = {"dmd": 0, "none": 1}
+DM_REG_CHW = 12288      # dxmi_dm_grad_fwd keeps an image's D_fake - D_real in registers up to this many elements (csrc/dm_train.hip)
+
+
+def _dm_scalar(what, name, v):
+    v = float(v)
+    if not (math.isfinite(v) and v > 0):
+        raise _lib.DxmiError(f"{what}: {name} must be positive and finite, got {v!r}")
+    return v
+
+
+def _dm_images(what, first, same=(), per_sample=()):
+    """The operand checks of _cd_operands for the launches of csrc/dm_train.hip that read no level table.  -> (N, CHW)."""
+    ts = (first,) + tuple(same) + tuple(per_sample)
+    _need_cuda(*ts)
+    for t in ts:
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
+            raise _lib.DxmiError(f"{what}: fp32 contiguous 16-byte aligned device tensors")
+    if first.dim() < 2 or first.numel() == 0:
+        raise _lib.DxmiError(f"{what}: a non-empty batch [N, ...] is needed, got {tuple(first.shape)}")
+    N = first.shape[0]
+    for t in same:
+        if t is not None and t.shape != first.shape:
+            raise _lib.DxmiError(f"{what}: operand of shape {tuple(t.shape)} where {tuple(first.shape)} is needed")
+    for t in per_sample:
+        if t is not None and t.numel() != N:
+            raise _lib.DxmiError(f"{what}: per-sample operand of {t.numel()} elements for a batch of {N}")
+    if any(t is not None and t.device != first.device for t in ts):
+        raise _lib.DxmiError(f"{what}: operands on different devices")
+    CHW = first.numel() // N
+    if CHW % 4:
+        raise _lib.DxmiError(f"{what}: the elements per sample ({CHW}) must be a multiple of 4")
+    return N, CHW
+
+
+def _dm_operands(what, first, indices, t_table, same=(), per_sample=()):
+    """_cd_operands for the launches of csrc/dm_train.hip that gather t = t_table[indices] (the table of cd_levels: >= 2 levels)."""
+    if any(v is None for v in (first, indices, t_table) + tuple(same)):
+        raise _lib.DxmiError(f"{what}: a needed operand is None")
+    N, CHW, S = _cd_operands(what, first, indices, t_table, same=same, per_sample=per_sample)
+    if CHW % 4:
+        raise _lib.DxmiError(f"{what}: the elements per sample ({CHW}) must be a multiple of 4")
+    return N, CHW, S
+
+
+def dm_gen_in(z, gen_sigma, sigma_data=0.5):
+    """-> (x_in = c_in(sigma_G) (sigma_G z), time [N] = 250 ln(sigma_G + 1e-44)): the one-step generator's input (dxmi_dm_gen_in)."""
+    if z is None:
+        raise _lib.DxmiError("dxmi_dm_gen_in: no latents")
+    N, CHW = _dm_images("dxmi_dm_gen_in", z)
+    sg, sd = _dm_scalar("dxmi_dm_gen_in", "gen_sigma", gen_sigma), _dm_scalar("dxmi_dm_gen_in", "sigma_data", sigma_data)
+    x_in, t = torch.empty_like(z), torch.empty(N, dtype=torch.float32, device=z.device)
+    check(load().dxmi_dm_gen_in(_ptr(z), _ptr(x_in), _ptr(t), N, CHW, sg, sd, _stream()), "dxmi_dm_gen_in")
+    return x_in, t
+
+
+def dm_gen_out(f_gen, z, gen_sigma, sigma_data=0.5, clip=True, out=None):
+    """-> x = c_skip(sigma_G) (sigma_G z) + c_out(sigma_G) f_gen, clamped to [-1, 1] when `clip` (dxmi_dm_gen_out)."""
+    if f_gen is None or z is None:
+        raise _lib.DxmiError("dxmi_dm_gen_out: f_gen and z are needed")
+    N, CHW = _dm_images("dxmi_dm_gen_out", f_gen, same=(z, out))
+    sg, sd = _dm_scalar("dxmi_dm_gen_out", "gen_sigma", gen_sigma), _dm_scalar("dxmi_dm_gen_out", "sigma_data", sigma_data)
+    x = torch.empty_like(f_gen) if out is None else out
+    check(load().dxmi_dm_gen_out(_ptr(f_gen), _ptr(z), _ptr(x), N, CHW, sg, sd, int(bool(clip)), _stream()), "dxmi_dm_gen_out")
+    return x
+
+
+def dm_gen_prep(f_gen, z, noise, indices, t_table, gen_sigma, sigma_data=0.5, real_sigma_data=0.5, fake_sigma_data=None):
+    """-> (x, x_t = x + noise t, x_in_real = c_in_real(t) x_t, time = 250 ln(t + 1e-44), x_in_fake | None) with x the generator's
+    unclamped image and t = t_table[indices] (dxmi_dm_gen_prep).  x_in_fake is written only where fake_sigma_data is given and
+    differs from real_sigma_data."""
+    N, CHW, S = _dm_operands("dxmi_dm_gen_prep", f_gen, indices, t_table, same=(z, noise))
+    what = "dxmi_dm_gen_prep"
+    sg, sd, sdr = _dm_scalar(what, "gen_sigma", gen_sigma), _dm_scalar(what, "sigma_data", sigma_data), _dm_scalar(what, "sigma_data", real_sigma_data)
+    own = fake_sigma_data is not None and float(fake_sigma_data) != float(real_sigma_data)
+    sdf = _dm_scalar(what, "sigma_data", fake_sigma_data) if own else sdr
+    x, x_t, x_in = torch.empty_like(f_gen), torch.empty_like(f_gen), torch.empty_like(f_gen)
+    t = torch.empty(N, dtype=torch.float32, device=f_gen.device)
+    x_fk = torch.empty_like(f_gen) if own else None
+    check(load().dxmi_dm_gen_prep(_ptr(f_gen), _ptr(z), _ptr(noise), _ptr(indices), _ptr(t_table), S, _ptr(x), _ptr(x_t), _ptr(x_in),
+                                  _ptr(t), _ptr(x_fk), N, CHW, sg, sd, sdr, sdf, _stream()), what)
+    return x, x_t, x_in, t, x_fk
+
+
+def _dm_diffusion(d, sigma_data=0.5, sigma_min=0.002, distillation=False):
+    return (sigma_data, sigma_min, distillation) if d is None else (d["sigma_data"], d["sigma_min"], d["distillation"])
+
+
+def dm_grad_fwd(f_real, f_fake, x, x_t, indices, t_table, weighting="dmd", real=None, fake=None):
+    """-> (g [N, ...], loss [N], s [N]): D_r = c_out_r(t) f_real + c_skip_r(t) x_t, D_f likewise, s = mean|x - D_r|,
+    g = (D_f - D_r) / s ("dmd") or D_f - D_r ("none"), loss = 0.5 mean(g^2); s == 0 gives g = 0 (dxmi_dm_grad_fwd).
+    real / fake: dict(sigma_data, sigma_min, distillation) of the denoiser's diffusion (None: 0.5, 0.002, False; fake None: real's)."""
+    what = "dxmi_dm_grad_fwd"
+    if weighting not in DM_WEIGHTINGS:
+        raise _lib.DxmiError(f"{what}: weighting {weighting!r} is not one of {sorted(DM_WEIGHTINGS)}")
+    N, CHW, S = _dm_operands(what, f_real, indices, t_table, same=(f_fake, x, x_t))
+    sdr, smr, dr = _dm_diffusion(real)
+    sdf, smf, df = _dm_diffusion(fake if fake is not None else real)
+    sdr, sdf = _dm_scalar(what, "sigma_data", sdr), _dm_scalar(what, "sigma_data", sdf)
+    g = torch.empty_like(f_real)
+    loss = torch.empty(N, dtype=torch.float32, device=f_real.device)
+    s = torch.empty_like(loss)
+    check(load().dxmi_dm_grad_fwd(_ptr(f_real), _ptr(f_fake), _ptr(x), _ptr(x_t), _ptr(indices), _ptr(t_table), S, _ptr(g), _ptr(loss),
+                                  _ptr(s), N, CHW, DM_WEIGHTINGS[weighting], sdr, float(smr), int(bool(dr)), sdf, float(smf),
+                                  int(bool(df)), _stream()), what)
+    return g, loss, s
+
+
+def dm_gen_bwd(upstream, g, gen_sigma, sigma_data=0.5):
+    """-> d(f_gen) = ((upstream[n] / CHW) g[n]) c_out(sigma_G) for the device upstream gradient [N] (dxmi_dm_gen_bwd)."""
+    if upstream is None or g is None:
+        raise _lib.DxmiError("dxmi_dm_gen_bwd: no upstream gradient / no g of the forward")
+    N, CHW = _dm_images("dxmi_dm_gen_bwd", g, per_sample=(upstream,))
+    sg, sd = _dm_scalar("dxmi_dm_gen_bwd", "gen_sigma", gen_sigma), _dm_scalar("dxmi_dm_gen_bwd", "sigma_data", sigma_data)
+    d = torch.empty_like(g)
+    check(load().dxmi_dm_gen_bwd(_ptr(upstream), _ptr(g), _ptr(d), N, CHW, sg, sd, _stream()), "dxmi_dm_gen_bwd")
+    return d
+
+
 EMA_MAX_RATES = 4
 
 

@@ -12,7 +12,9 @@ outside the accelerated path and runs only when those are present; --skip_fid wr
 `--synthetic NAME` builds the net of a built-in config with random weights (benchmark / smoke use).
 
 `--karras_sampler {heun,dpm,euler,ancestral,progdist}` samples the EDM teacher instead (progdist: a progressively distilled
-student of it, `--pretrained` a model%06d.pt of `cm_train.py --training_mode progdist`, NFE = `--karras_steps`) (models.cm.karras_diffusion.karras_sample,
+student of it, `--pretrained` a model%06d.pt of `cm_train.py --training_mode progdist`, NFE = `--karras_steps`; `--karras_sampler dm`: a
+one-step distribution-matching generator, `--pretrained` a model%06d.pt of `cm_train.py --training_mode dm`, NFE = 1, and
+`--karras_steps`, `--rho` and the churn and solver flags are refused with it) (models.cm.karras_diffusion.karras_sample,
 reference models/cm/karras_diffusion.py:354-420): `--karras_steps` (40), `--rho`, `--s_churn`, `--s_tmin`, `--s_tmax`,
 `--s_noise`.  Weights: `--pretrained [PATH]` loads a plain U-Net state dict (PATH, or the config's training.pretrained_path),
 otherwise `sampler.pth` from --log_dir without its `log_betas` entry.  Class-conditional nets draw one label per image.
@@ -74,9 +76,10 @@ def build_parser():
     ap.add_argument("--synthetic", type=str, default=None, help="builtin config name, e.g. imagenet64_T10 (random weights)")
     ap.add_argument("--no_graph", action="store_true", help="issue every launch from python instead of replaying the T-step loop of a "
                                                            "batch as one hipGraph (dxmi_hip/graph.py; DXMI_GRAPH=0 does the same)")
-    ap.add_argument("--karras_sampler", type=str, default=None, choices=("heun", "dpm", "euler", "ancestral", "progdist", "dpmpp", "sde-dpmpp"),
+    ap.add_argument("--karras_sampler", type=str, default=None, choices=("heun", "dpm", "euler", "ancestral", "progdist", "dpmpp", "sde-dpmpp", "dm"),
                     help="sample the EDM teacher with this Karras sampler, or with DPM-Solver++ (dpmpp: the ODE solver, sde-dpmpp: "
-                         "its SDE variant), instead of the DxMI sampler")
+                         "its SDE variant), or a one-step distribution-matching generator distilled from it (dm), instead of the "
+                         "DxMI sampler")
     ap.add_argument("--karras_steps", type=int, default=None, help="Karras sampler steps (default 40; dpmpp / sde-dpmpp: the number "
                                                                    "of network evaluations, default 10)")
     ap.add_argument("--solver_order", type=int, default=None, choices=(1, 2, 3), help="dpmpp / sde-dpmpp: the solver's order (default 2; "
@@ -139,6 +142,11 @@ def parse_args(argv=None):
             ap.error("--karras_sampler samples the EDM teacher: it cannot be combined with --guidance_scale")
         if args.karras_sampler in DPM_SAMPLERS:
             return parse_dpm_args(ap, args), unknown
+        if args.karras_sampler == "dm":       # one evaluation at sigma_max: no ladder, no churn, no solver
+            given = [f"--{k}" for k in ("karras_steps", "rho") + CHURN_FLAGS if getattr(args, k) is not None]
+            if given:
+                ap.error(f"{', '.join(given)}: --karras_sampler dm is one network evaluation at sigma_max, it has no steps, ladder or churn")
+            return args, unknown
         for k, v in (("karras_steps", 40), ("rho", 7.0), ("s_churn", 0.0), ("s_tmin", 0.0), ("s_tmax", float("inf")),
                      ("s_noise", 1.0)):
             if getattr(args, k) is None:
@@ -338,7 +346,7 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
     from dxmi_hip import graph as hip_graph
     from dxmi_hip import ops
     from models.cm.dpm_sample import edm_dpm_sample
-    from models.cm.karras_diffusion import cm_nfe, karras_nfe, karras_sample, progdist_sample
+    from models.cm.karras_diffusion import cm_nfe, dm_sample, karras_nfe, karras_sample, progdist_sample
     from utils import ImageWriter
     path, kind = resolve_weights(args, cfg)
     if path is not None:
@@ -364,6 +372,8 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         sampler, steps, nfe = args.karras_sampler, args.karras_steps, args.karras_steps
         extra = dict(algorithm=DPM_SAMPLERS[sampler], order=args.solver_order, solver_type=args.solver_type, skip_type=args.skip_type,
                      lower_order_final=not args.no_lower_order_final, rho=args.rho)
+    elif args.karras_sampler == "dm":              # a distribution-matching generator: one evaluation at sigma_max
+        sampler, steps, nfe, extra = "dm", 1, 1, {}
     else:
         sampler, steps, nfe = args.karras_sampler, args.karras_steps, karras_nfe(args.karras_sampler, args.karras_steps)
         extra = dict(rho=args.rho, s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax, s_noise=args.s_noise)
@@ -387,6 +397,8 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         if sampler in DPM_SAMPLERS:
             sample = edm_dpm_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
                                     sigma_max=diffusion.sigma_max, use_graph=use_graph, generator=generator, **extra)
+        elif sampler == "dm":
+            sample = dm_sample(diffusion, unet, shape, model_kwargs=kw, device=device, generator=generator)
         elif sampler == "progdist":             # its own entry point: karras_sample keeps refusing this sampler
             sample = progdist_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
                                      sigma_max=diffusion.sigma_max, rho=args.rho, use_graph=use_graph, generator=generator)

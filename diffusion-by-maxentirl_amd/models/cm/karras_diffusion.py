@@ -49,6 +49,11 @@ _PDLossFn): dxmi_cd_prep on the coarse ladder, the online training forward, teac
 evaluation 2, dxmi_pd_solver END (target_x; x_t3 is never stored), dxmi_pd_loss_fwd; its backward is dxmi_pd_loss_bwd and the U-Net
 backward.  Its levels are a host table of 2 S + 1 entries (PDLevels: the coarse ladder, then the half steps); num_scales = 1 is legal.
 lpips goes through dxmi_pd_lpips_images and, backwards, dxmi_cd_lpips_bwd.  The reference has no l2-32 here: refused.
+dm_generator_losses (not in the reference: Diff-Instruct / DMD / DMD2 without its GAN term) trains a ONE-step generator
+G(z) = D_theta(sigma_max z, sigma_max) against a frozen real and an online-trained fake denoiser; on HIP UNetModels it is ONE autograd
+node around the generator (_dm_loss, _DMLossFn): dxmi_dm_gen_in, the generator's training forward, dxmi_dm_gen_prep, the two
+denoisers' forward_inference, dxmi_dm_grad_fwd; its backward is dxmi_dm_gen_bwd and the U-Net backward.  dm_sample is its sampler
+(dxmi_dm_gen_in, one evaluation, dxmi_dm_gen_out).  DESIGN 5.32.
 
 The training_losses and consistency_losses nodes run inside a StepGraph capture (models.cm.train_util's use_graph): they read nothing back, allocate from the graph's
 pool only, and their draws (randn_like, the index randint) are torch device RNG, which is graph-aware.  What a capture freezes is
@@ -352,6 +357,82 @@ class _PDLossFn(torch.autograd.Function):
         return (None,) * 9 + grads
 
 
+# ------------------------------------------------------------------------------------------------- distribution matching
+DM_WEIGHTINGS = ("dmd", "none")
+
+
+def dm_index_range(num_scales, min_step_frac=0.02, max_step_frac=0.98):
+    """-> (lo, hi), both inclusive: the ladder indices dm_generator_losses draws from, [ceil(min (S - 1)), floor(max (S - 1))]
+    (DMD's EDM runs: the middle 96 % of a 1000-level Karras ladder)."""
+    S = int(num_scales)
+    if not (0.0 <= min_step_frac <= max_step_frac <= 1.0):
+        raise ValueError(f"dm_generator_losses: need 0 <= min_step_frac <= max_step_frac <= 1, got {min_step_frac}, {max_step_frac}")
+    lo, hi = math.ceil(min_step_frac * (S - 1)), math.floor(max_step_frac * (S - 1))
+    if lo > hi:
+        raise ValueError(f"dm_generator_losses: no ladder index of {S} levels lies in [{min_step_frac}, {max_step_frac}] (S - 1)")
+    return lo, hi
+
+
+class _DMSurrogate(torch.autograd.Function):
+    """The distribution-matching term of x for the stop-gradient direction g (DMD eq. 7): the value is 0.5 mean_flat(g^2), the
+    gradient d loss_n / d x = g_n / CHW, that of the surrogate 0.5 mean_flat((x - sg(x - g))^2) without its rounding of x - (x - g)."""
+
+    @staticmethod
+    def forward(ctx, x, g):
+        ctx.save_for_backward(g)
+        return 0.5 * mean_flat(g ** 2)
+
+    @staticmethod
+    def backward(ctx, up):
+        g, = ctx.saved_tensors
+        return append_dims(up, g.ndim) * g / g[0].numel(), None
+
+
+def _scal_kw(d):
+    return dict(sigma_data=d.sigma_data, sigma_min=d.sigma_min, distillation=d.distillation)
+
+
+def _dm_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting, keep):
+    """dm_gen_in -> generator forward -> dm_gen_prep -> the real and the fake denoiser -> dm_grad_fwd.
+    -> (loss, x, s, (tape, g)), the last being what _DMLossFn.backward reads.  keep=False: no backward follows, so the generator
+    runs forward_inference (the training forward where its dropout is live) and no tape is kept."""
+    sd = diffusion.sigma_data
+    x_in, t_g = ops.dm_gen_in(z, gen_sigma, sd)
+    if keep:
+        F, tape = train_forward(net, x_in, t_g, y)
+    else:
+        F, tape = (_train_forward_no_grad(net, x_in, t_g, y) if net.training and net.dropout > 0 else net.forward_inference(x_in, t_g, y)), None
+    x, x_t, xr_in, t, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, sd, real_diffusion.sigma_data,
+                                              fake_diffusion.sigma_data)
+    F_r = real.forward_inference(xr_in, t, y)
+    F_f = fake.forward_inference(xr_in if xf_in is None else xf_in, t, y)
+    g, loss, s = ops.dm_grad_fwd(F_r, F_f, x, x_t, indices, tab, weighting, real=_scal_kw(real_diffusion), fake=_scal_kw(fake_diffusion))
+    return loss, x, s, (tape, g)
+
+
+class _DMLossFn(torch.autograd.Function):
+    """_dm_loss as one node around the generator; outputs (loss, x, dm_norm), of which only loss is differentiable."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting, *params):
+        loss, x, s, (ctx.tape, ctx.g) = _dm_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y,
+                                                 gen_sigma, weighting, keep=True)
+        ctx.gen = (gen_sigma, diffusion.sigma_data)
+        ctx.mark_non_differentiable(x, s)
+        ctx.set_materialize_grads(False)
+        return loss, x, s
+
+    @staticmethod
+    def backward(ctx, g_loss, g_x, g_s):
+        if g_loss is None:
+            return (None,) * len(ctx.needs_input_grad)
+        dF = ops.dm_gen_bwd(g_loss.detach().float().contiguous(), ctx.g, *ctx.gen)
+        ctx.g = None
+        grads = train_backward(ctx.tape, dF)
+        ctx.tape = None
+        return (None,) * 13 + grads
+
+
 class KarrasDenoiser:
     def __init__(self, sigma_data: float = 0.5, sigma_max=80.0, sigma_min=0.002, rho=7.0, weight_schedule="karras",
                  distillation=False, loss_norm="l2", lpips_loss=None, huber_c=None):
@@ -646,6 +727,99 @@ class KarrasDenoiser:
         else:
             loss, _ = _cd_loss(*args, keep=False)
         return {"loss": loss}
+
+    def dm_generator_losses(self, model, z, num_scales=1000, real_model=None, real_diffusion=None, fake_model=None, fake_diffusion=None,
+                            model_kwargs=None, noise=None, indices=None, generator=None, gen_sigma=None, weighting="dmd",
+                            min_step_frac=0.02, max_step_frac=0.98):
+        """Distribution-matching loss of the one-step generator G(z) = D_theta(sigma_G z, sigma_G) (Diff-Instruct, Luo et al. 2023;
+        DMD, Yin et al. 2023, eq. 7-8; DMD2, Yin et al. 2024, without its GAN term) -> {"loss": [N], "x": [N, C, H, W] detached fp32,
+        "dm_norm": [N]}.  x = G(z) is diffused to x_t = x + noise t, t = cd_levels(num_scales)[index]; with D_r / D_f the denoised
+        images of real_model under real_diffusion (the teacher) and fake_model under fake_diffusion (None: real_diffusion; trained
+        online on x by training_losses), s = mean|x - D_r| ("dm_norm") and g = (D_f - D_r) / s (weighting "dmd") or D_f - D_r
+        ("none"); a sample with s == 0 gets g = 0.  loss = 0.5 mean(g^2) per sample, and its gradient is DEFINED as
+        d loss_n / d x = g_n / CHW: both denoisers are under stop-gradient, neither net receives a gradient, the generator receives
+        it through x alone.  `self` is the generator's diffusion (distillation=False).  gen_sigma: None = sigma_max.
+        indices: drawn uniformly from [ceil(min_step_frac (S - 1)), floor(max_step_frac (S - 1))] when None, then noise, both from
+        `generator` where given."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        if self.distillation:
+            raise NotImplementedError("dm_generator_losses: the one-step generator keeps the EDM scalings (distillation=False); a "
+                                      "diffusion with boundary-condition scalings belongs to the consistency losses")
+        if real_model is None or real_diffusion is None or fake_model is None:
+            raise NotImplementedError("dm_generator_losses: Must have a real_model with its real_diffusion and a fake_model")
+        if fake_diffusion is None:
+            fake_diffusion = real_diffusion
+        if weighting not in DM_WEIGHTINGS:
+            raise ValueError(f"dm_generator_losses: weighting {weighting!r} is not one of {DM_WEIGHTINGS}")
+        gen_sigma = float(self.sigma_max if gen_sigma is None else gen_sigma)
+        if not (math.isfinite(gen_sigma) and gen_sigma > 0):
+            raise ValueError(f"dm_generator_losses: gen_sigma must be positive and finite, got {gen_sigma!r}")
+        N = z.shape[0]
+        if indices is None:
+            lo, hi = dm_index_range(num_scales, min_step_frac, max_step_frac)
+            if generator is not None:
+                indices = torch.randint(lo, hi + 1, (N,), generator=generator, device=generator.device).to(z.device)
+            else:
+                indices = torch.randint(lo, hi + 1, (N,), device=z.device)
+        if noise is None:
+            if generator is not None:
+                noise = torch.randn(z.shape, generator=generator, device=generator.device, dtype=z.dtype).to(z.device)
+            else:
+                noise = torch.randn_like(z)
+        nets = [_hip_unet(m) for m in (model, real_model, fake_model)]
+        if all(n is not None for n in nets) and z.is_cuda:
+            return self._dm_generator_losses_hip(nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices,
+                                                 gen_sigma, weighting)
+        if z.requires_grad or noise.requires_grad:
+            raise NotImplementedError("dm_generator_losses differentiates the generator's parameters only: z and noise must not "
+                                      "require grad")
+        dims = z.ndim
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(z.device)
+        t = levels[indices.to(z.device)]
+        sigma_g = torch.full((N,), gen_sigma, dtype=torch.float32, device=z.device)
+        x = self.denoise(model, z * gen_sigma, sigma_g, **model_kwargs)[1]
+        with torch.no_grad():
+            x_t = x + noise * append_dims(t, dims)
+            d_real = real_diffusion.denoise(real_model, x_t, t, **model_kwargs)[1]
+            d_fake = fake_diffusion.denoise(fake_model, x_t, t, **model_kwargs)[1]
+            s = mean_flat(torch.abs(x - d_real))
+            g = d_fake - d_real
+            if weighting == "dmd":
+                g = g / append_dims(s, dims)
+            g = torch.where(append_dims(s, dims) == 0, torch.zeros_like(g), g)
+        return {"loss": _DMSurrogate.apply(x, g), "x": x.detach().float(), "dm_norm": s}
+
+    def _dm_generator_losses_hip(self, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma,
+                                 weighting):
+        net, real, fake = nets
+        if z.requires_grad or noise.requires_grad:
+            raise NotImplementedError("dm_generator_losses on the HIP U-Net differentiates the generator's parameters only: "
+                                      "z and noise must not require grad")
+        extra = set(model_kwargs) - {"y"}
+        if extra:
+            raise NotImplementedError(f"dm_generator_losses on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
+        y = model_kwargs.get("y")
+        for n in nets:
+            if (y is not None) != (n.num_classes is not None):
+                raise ValueError("must specify y if and only if the model is class-conditional")
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        z, noise = f32(z), f32(noise)
+        indices = indices.detach().to(device=z.device, dtype=torch.int64).reshape(-1).contiguous()
+        if noise.shape != z.shape or indices.numel() != z.shape[0] or z.dim() != 4:
+            raise ValueError(f"dm_generator_losses: noise {tuple(noise.shape)} must match z {tuple(z.shape)} [N, C, H, W] "
+                             f"and indices ({indices.numel()}) hold one level per sample")
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho)
+        if _graph.capturing() and not levels.on_device(z.device):
+            raise DxmiError(f"dm_generator_losses inside a StepGraph capture: the {int(num_scales)}-level table is not on {z.device} "
+                            "yet (cd_levels(...).device_table(device) before the capture: an upload cannot be captured)")
+        tab = levels.device_table(z.device)
+        args = (self, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting)
+        if torch.is_grad_enabled():
+            loss, x, s = _DMLossFn.apply(*args, *ops.fast_parameters(net))
+        else:
+            loss, x, s, _ = _dm_loss(*args, keep=False)
+        return {"loss": loss, "x": x, "dm_norm": s}
 
     def denoise(self, model, x_t, sigmas, **model_kwargs):
         scal = self.get_scalings_for_boundary_condition(sigmas) if self.distillation else self.get_scalings(sigmas)
@@ -998,6 +1172,32 @@ def progdist_sample(diffusion, model, shape, steps, clip_denoised=True, progress
                                  sigma_max, 0.0, 0.0, float("inf"), 1.0)
     key = ("progdist", steps, float(sigma_min), float(sigma_max), float(rho), bool(clip_denoised), float(diffusion.sigma_data))
     return _sample_on_device(schedule, denoiser, shape, device, "progdist_sample", key, use_graph, generator, callback, progress)
+
+
+def dm_sample(diffusion, model, shape, gen_sigma=None, clip_denoised=True, model_kwargs=None, generator=None, device=None):
+    """Sample the one-step generator that dm_generator_losses trains: x = D_theta(sigma_G z, sigma_G) with the EDM scalings, NFE = 1
+    (dxmi_dm_gen_in -> forward_inference -> dxmi_dm_gen_out); clamped to [-1, 1] when clip_denoised.  gen_sigma: None = sigma_max,
+    and it must be the one the generator was trained at.  generator: as for karras_sample (its randn draws z: with a
+    DeterministicGenerator image i gets the same latent whatever the batch size); None: drawn on the device."""
+    if getattr(diffusion, "distillation", False):
+        raise NotImplementedError("dm_sample runs a distribution-matching generator, which keeps the EDM scalings (distillation=False); "
+                                  "a consistency-distilled model samples in one step with --cm_sampler onestep")
+    device = _graph.indexed_device(torch.device("cuda") if device is None else device)
+    if device.type != "cuda":
+        raise DxmiError("dm_sample runs only on the HIP device path (no CPU fallback)")
+    kw = {} if model_kwargs is None else model_kwargs
+    shape = tuple(int(v) for v in shape)
+    gen_sigma = float(diffusion.sigma_max if gen_sigma is None else gen_sigma)
+    with torch.no_grad():
+        if generator is not None:
+            z = _as_f32(generator.randn(*shape, device=device), device)
+        else:
+            z = torch.randn(shape, dtype=torch.float32, device=device)
+        x_in, t = ops.dm_gen_in(z, gen_sigma, diffusion.sigma_data)
+        F = model(x_in, t, **kw)          # under no_grad the HIP UNetModel's forward is forward_inference
+        if F.dtype != torch.float32 or not F.is_contiguous() or F.device != z.device:
+            F = _as_f32(F, device)
+        return ops.dm_gen_out(F, z, gen_sigma, diffusion.sigma_data, clip=clip_denoised)
 
 
 def _sample_on_device(schedule, denoiser, shape, device, name, key, use_graph, generator, callback, progress):

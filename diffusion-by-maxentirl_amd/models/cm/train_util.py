@@ -32,7 +32,11 @@ save and a resume reads the file of the resumed step.  target_model may be None;
 and neither enters the loss nor is moved by an EMA.  `step` is the phase's own counter (the learning rate anneals on it alone).
 use_graph=True is refused in this mode.  Where this differs from the reference's call site, which cannot run: DESIGN 5.28.
 
-use_graph=True (both loops; off by default) replays a whole step from hipGraphs (dxmi_hip/graph.py StepGraph): the first run_step
+DMTrainLoop (not in the reference) distils the EDM teacher into a one-step generator by distribution matching
+(KarrasDenoiser.dm_generator_losses): the generator and an online-trained fake denoiser have a trainer and an optimiser each and are
+updated on two clocks; the data are latents.  It refuses use_graph=True.
+
+use_graph=True (the first two loops; off by default) replays a whole step from hipGraphs (dxmi_hip/graph.py StepGraph): the first run_step
 runs eagerly (weight packs, workspaces, optimiser state), the second is captured, later ones are host producers + one upload + the
 graph launches.  Captured is everything run_step does on the device: zero_grad, every microbatch of forward_backward (sigma, index
 and noise draws are torch device RNG), the gradient exchange (a cut: the collectives run eagerly between two graph launches), the
@@ -582,6 +586,124 @@ class CMTrainLoop(TrainLoop):
 
     def log_step(self):
         self._kv = {"step": self.global_step, "samples": (self.global_step + 1) * self.global_batch}
+
+
+class DMTrainLoop(TrainLoop):
+    """Distribution matching distillation of an EDM teacher (`real_model` under `real_diffusion`, frozen) into the one-step
+    generator `model` (KarrasDenoiser.dm_generator_losses; DMD2's two time-scale rule without its GAN term).  Two trainers on two
+    clocks: the generator has TrainLoop's own mp_trainer / opt / EMA series and is updated when step % gen_update_every == 0; the
+    fake denoiser `fake_model` has a MixedPrecisionTrainer and RAdam of its own (fake_lr, None = lr; its own loss scale and
+    gradient exchange) and is updated at EVERY iteration by denoising score matching on that iteration's generated images, which
+    were made before the generator moved.  data yields (z, cond): standard-normal latents of the image shape and {"y": labels}
+    for a class-conditional net.  `step` counts iterations and names the checkpoints (no resume_step is added to it); an overflow
+    in one trainer skips that trainer's update alone.  save() adds fake_model%06d.pt and fake_opt%06d.pt to TrainLoop's files; a
+    resume reads all of them, and a missing fake_model file is an error.  use_graph=True is refused."""
+
+    def __init__(self, *, real_model, real_diffusion, fake_model, fake_diffusion=None, num_scales=1000, gen_update_every=5,
+                 fake_lr=None, weighting="dmd", gen_sigma=None, min_step_frac=0.02, max_step_frac=0.98, generator=None, **kwargs):
+        if kwargs.get("use_graph"):
+            raise NotImplementedError("DMTrainLoop: use_graph=True is not supported: the generator and the fake denoiser are updated "
+                                      "on two clocks, which needs two captured steps and a graph key per clock; train this mode eagerly")
+        if real_model is None or real_diffusion is None or fake_model is None:
+            raise NotImplementedError("DMTrainLoop: must have a real_model with its real_diffusion and a fake_model")
+        if int(gen_update_every) < 1:
+            raise ValueError(f"DMTrainLoop: gen_update_every must be at least 1, got {gen_update_every}")
+        super().__init__(**kwargs)
+        self.real_model, self.real_diffusion, self.fake_model = real_model, real_diffusion, fake_model
+        self.fake_diffusion = real_diffusion if fake_diffusion is None else fake_diffusion
+        self.num_scales, self.gen_update_every = int(num_scales), int(gen_update_every)
+        self.fake_lr = self.lr if fake_lr is None else fake_lr
+        self.weighting, self.gen_sigma, self.generator = weighting, gen_sigma, generator
+        self.min_step_frac, self.max_step_frac = min_step_frac, max_step_frac
+        self.real_model.requires_grad_(False)
+        self.real_model.eval()
+        if self.resume_checkpoint:      # never restart the fake denoiser from the teacher silently
+            ckpt = self._side_file("fake_model")
+            if not os.path.exists(ckpt):
+                raise FileNotFoundError(f"DMTrainLoop: resuming needs {ckpt} (the fake denoiser is written at every save)")
+            self.fake_model.load_state_dict(torch.load(ckpt, map_location=self.device))
+        broadcast_parameters(self.fake_model)
+        self.fake_trainer = MixedPrecisionTrainer(model=self.fake_model, use_fp16=self.use_fp16, fp16_scale_growth=self.fp16_scale_growth)
+        self.fake_opt = RAdam(self.fake_trainer.master_params, lr=self.fake_lr, weight_decay=self.weight_decay)
+        if self.resume_checkpoint and os.path.exists(self._side_file("fake_opt")):
+            self.fake_opt.load_state_dict(torch.load(self._side_file("fake_opt"), map_location=self.device))
+        self.resume_step = 0            # `step` already stands at the resumed step: nothing is added to it again
+
+    def _side_file(self, prefix):
+        path, name = os.path.split(self.resume_checkpoint)
+        return os.path.join(path, f"{prefix}{parse_resume_step_from_filename(name):06d}.pt")
+
+    def run_loop(self):
+        while not self.lr_anneal_steps or self.step < self.lr_anneal_steps:
+            batch, cond = next(self.data)
+            self.run_step(batch, cond)
+            if self.step % self.log_interval == 0:
+                self.dumpkvs()
+            if self.step % self.save_interval == 0:
+                self.save()
+                if os.environ.get("DIFFUSION_TRAINING_TEST", "") and self.step > 0:
+                    return
+        if self.step % self.save_interval != 0:
+            self.save()
+
+    def run_step(self, batch, cond):
+        """One iteration -> (generator step taken, fake step taken)."""
+        gen_turn = self.step % self.gen_update_every == 0
+        self.forward_backward(batch, cond, gen_turn)
+        took_gen = False
+        if gen_turn:
+            took_gen = bool(self.mp_trainer.optimize(self.opt))
+            if took_gen:
+                self._update_emas()
+        took_fake = bool(self.fake_trainer.optimize(self.fake_opt))
+        self.step += 1
+        self._anneal_lr()
+        self.log_step()
+        return took_gen, took_fake
+
+    def forward_backward(self, batch, cond, gen_turn=True):
+        """Both losses of every microbatch, accumulated before either optimize(): the generator's (with grad on its turn, else under
+        no_grad) and, on the images it returned, the fake denoiser's DSM loss as TrainLoop.forward_backward forms it."""
+        if gen_turn:
+            self.mp_trainer.zero_grad()
+        self.fake_trainer.zero_grad()
+        for i in range(0, batch.shape[0], self.microbatch):
+            z = batch[i:i + self.microbatch].to(self.device)
+            micro_cond = {k: v[i:i + self.microbatch].to(self.device) for k, v in cond.items()}
+            with torch.enable_grad() if gen_turn else torch.no_grad():
+                terms = self.diffusion.dm_generator_losses(
+                    self.ddp_model, z, self.num_scales, real_model=self.real_model, real_diffusion=self.real_diffusion,
+                    fake_model=self.fake_model, fake_diffusion=self.fake_diffusion, model_kwargs=micro_cond, generator=self.generator,
+                    gen_sigma=self.gen_sigma, weighting=self.weighting, min_step_frac=self.min_step_frac,
+                    max_step_frac=self.max_step_frac)
+            if gen_turn:
+                self.mp_trainer.backward(terms["loss"].mean())
+            x = terms["x"]
+            sigmas, weights = self.schedule_sampler.sample(x.shape[0], self.device)
+            losses = self.fake_diffusion.training_losses(self.fake_model, x, sigmas, model_kwargs=micro_cond)
+            self._log_loss_dict({"loss": terms["loss"], "dm_norm": terms["dm_norm"], "fake_mse": losses["mse"] * weights,
+                                 "fake_xs_mse": losses["xs_mse"] * weights})
+            self.fake_trainer.backward((losses["loss"] * weights).mean())
+
+    def _anneal_lr(self):
+        if not self.lr_anneal_steps:
+            return
+        frac = 1 - self.step / self.lr_anneal_steps
+        for opt, lr in ((self.opt, self.lr), (self.fake_opt, self.fake_lr)):
+            for param_group in opt.param_groups:
+                param_group["lr"] = lr * frac
+
+    def log_step(self):
+        self._kv = {"step": self.step, "samples": (self.step + 1) * self.global_batch}
+        self._kv.update({f"fake_{k}": v for k, v in self.fake_trainer.log.items()})
+
+    def save(self):
+        os.makedirs(self.log_dir, exist_ok=True)
+        if _rank() == 0:
+            torch.save({k: v.detach().clone() for k, v in self.fake_model.state_dict().items()},
+                       os.path.join(self.log_dir, f"fake_model{self.step:06d}.pt"))
+            torch.save(self.fake_opt.state_dict(), os.path.join(self.log_dir, f"fake_opt{self.step:06d}.pt"))
+        super().save()                  # ema, opt, then the model file last
 
 
 class _UnitWeights:

@@ -698,6 +698,42 @@ int dxmi_pd_lpips_images(const float* f_online, const float* x_t, const float* t
                          const float* t_table, int32_t num_scales, float* x01, float* weights, int32_t N, int32_t CHW,
                          float sigma_data, float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream);
 
+/* Distribution matching distillation of an EDM teacher into a ONE-step generator G(z) = D_theta(sigma_G z, sigma_G)
+ * (KarrasDenoiser.dm_generator_losses; Diff-Instruct, Luo et al. 2023, eq. 8 and Algorithm 1; DMD, Yin et al. 2023, eq. 7-8; DMD2,
+ * Yin et al. 2024, eq. 2-3, without its GAN term): the launches between the generator and the "real" (teacher) and "fake" (trained
+ * online on the generator's samples) denoisers.  Tensors as for dxmi_cd_*: fp32 [N, CHW] contiguous, 16-byte aligned, CHW % 4 == 0.
+ * t_table: fp32 [num_scales] on the DEVICE (the ladder of dxmi_cd_*); t = t_table[index], and since no t2 is needed every index
+ * in [0, num_scales - 1] is legal.  An index outside gives a NaN level; nothing outside the table is read.  One rounding per written
+ * operation, sums in a fixed order (bitwise reproducible), no atomics.  gen_sigma and every sigma_data must be positive and finite.
+ * dxmi_dm_gen_in   (the generator's input, EDM preconditioning, Karras et al. 2022 eq. 7): x_in = c_in(sigma_G) (sigma_G z) and
+ *   t_out[n] = 250 ln(sigma_G + 1e-44).
+ * dxmi_dm_gen_out  (sampling; DMD eq. 1 with the EDM scalings, distillation = False): x = c_skip(sigma_G) (sigma_G z) +
+ *   c_out(sigma_G) f_gen, clamped to [-1, 1] when clip != 0.
+ * dxmi_dm_gen_prep (training; DMD2 Algorithm 1, the forward diffusion of the generated image): the same unclamped x (kept),
+ *   x_t = x + noise t (kept), x_in_real = c_in_real(t) x_t, t_out[n] = 250 ln(t + 1e-44) (the time of both denoisers), and
+ *   x_in_fake = c_in_fake(t) x_t where x_in_fake is not NULL (pass it only where fake_sigma_data differs).
+ * dxmi_dm_grad_fwd (DMD eq. 7-8): D_r = c_out_r(t) f_real + c_skip_r(t) x_t, D_f likewise with the fake net's scalings
+ *   (boundary-condition scalings where that diffusion's distillation != 0), s[n] = mean|x - D_r| (DMD eq. 8's normaliser),
+ *   g = (D_f - D_r) / s (DXMI_DM_W_DMD) or D_f - D_r (DXMI_DM_W_NONE, Diff-Instruct eq. 8 with w = 1), loss[n] = 0.5 mean(g^2).
+ *   A sample with s == 0 gets g = 0 and loss = 0 under either weighting.  One workgroup per image; D_f - D_r stays in registers up
+ *   to CHW = 12288 (3 x 64 x 64), above that the inputs are read a second time.
+ * dxmi_dm_gen_bwd  (DMD eq. 7: the gradient reaches the generator through x alone, d loss_n / d x = g_n / CHW):
+ *   d_f_gen[n] = ((upstream[n] / CHW) g[n]) c_out(sigma_G) for the DEVICE [N] upstream gradient. */
+#define DXMI_DM_W_DMD  0
+#define DXMI_DM_W_NONE 1
+int dxmi_dm_gen_in(const float* z, float* x_in, float* t_out, int32_t N, int32_t CHW, float gen_sigma, float sigma_data, void* stream);
+int dxmi_dm_gen_out(const float* f_gen, const float* z, float* x, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
+                    int32_t clip, void* stream);
+int dxmi_dm_gen_prep(const float* f_gen, const float* z, const float* noise, const int64_t* indices, const float* t_table,
+                     int32_t num_scales, float* x, float* x_t, float* x_in_real, float* t_out, float* x_in_fake, int32_t N,
+                     int32_t CHW, float gen_sigma, float gen_sigma_data, float real_sigma_data, float fake_sigma_data, void* stream);
+int dxmi_dm_grad_fwd(const float* f_real, const float* f_fake, const float* x, const float* x_t, const int64_t* indices,
+                     const float* t_table, int32_t num_scales, float* g, float* loss, float* s, int32_t N, int32_t CHW,
+                     int32_t weighting, float real_sigma_data, float real_sigma_min, int32_t real_distillation,
+                     float fake_sigma_data, float fake_sigma_min, int32_t fake_distillation, void* stream);
+int dxmi_dm_gen_bwd(const float* upstream, const float* g, float* d_f_gen, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
+                    void* stream);
+
 /* TD step of DxMI_Trainer.update_f_v on the replay ring, data side in one launch (reference trainer.py:271-300, :163-169): rows
  * `state_rows[b]` (and `next_rows[b]`, or the dense re-drawn next states of value_resample) of the ring's fp32 [n_src_rows, CHW]
  * trajectory block are gathered into out_state / out_next — the two halves of the batch [next_state | state] the value net
