@@ -198,6 +198,7 @@ SIGNATURES = {
     "dxmi_edm_dpm_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
     "dxmi_unipc_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_void_p]),
     "dxmi_edm_unipc_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_int, c_void_p]),
+    "dxmi_pf_ll_stage": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 14 + [c_int, c_int, c_void_p]),
 }
 
 _lib = None

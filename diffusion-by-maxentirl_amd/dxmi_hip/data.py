@@ -228,6 +228,20 @@ class ImageStore:
             flips = (torch.rand(self.per_rank, generator=g) < 0.5).to(torch.uint8)
         return rows, flips
 
+    def raw(self, rows):
+        """(uint8 [B, C, H, W], labels int64 [B] or None) of the file's rows `rows` (int64, any order) on the store's device: the
+        stored bytes, neither flipped nor normalised (eval_bpd.py dequantises them itself)."""
+        rows = torch.as_tensor(rows, dtype=torch.int64).cpu()
+        if rows.numel() and not (0 <= int(rows.min()) and int(rows.max()) < self.M):
+            raise ValueError(f"ImageStore.raw: rows must lie in [0, {self.M})")
+        if self.resident == "device" and self.device.type == "cuda":
+            r = rows.to(self.device)
+            u8, y = self.store_dev[r], (self.labels_dev[r] if self.with_labels else None)
+        else:
+            u8 = torch.from_numpy(np.ascontiguousarray(self.arr[rows.numpy()])).to(self.device)
+            y = torch.from_numpy(self.labels[rows.numpy()]).to(self.device) if self.with_labels else None
+        return u8.permute(0, 3, 1, 2).contiguous(), y
+
     def epoch_flips(self, epoch, flips):
         """The epoch's flip bits where the batch is formed, uploaded once per epoch."""
         if flips is None or self.device.type != "cuda":

@@ -2339,6 +2339,63 @@ def edm_unipc_stage(mode, tab, t_out, row=0, x=None, xc=None, model_out=None, ct
                    pred_xstart, hist=(hist,), x_in=(x_in,), xc=(xc,), slots=4)
 
 
+# dxmi_pf_ll_stage modes, table columns and flags (include/dxmi_hip.h)
+PF_LL_FIRST, PF_LL_PREDICT, PF_LL_CORRECT = range(3)
+(PL_T, PL_T_NEXT, PL_CIN, PL_CIN_NEXT, PL_XSCALE, PL_LOGDET0, PL_KA, PL_KB, PL_DB, PL_KA2, PL_KB2, PL_DB2, PL_H, PL_HH, PL_FLAGS,
+ PL_PRIOR_Q, PL_PRIOR_C, PL_BPD_SCALE, PL_SIGMA, PL_SIGMA_NEXT) = range(20)
+PL_COLS = 20
+PL_FLAG_LAST = 2
+
+
+def pf_ll_stage(mode, tab, t_out, row=0, x=None, model_out=None, vjp=None, eps=None, sample_index=None, seed=0, draw=0, ctl=None,
+                k1=None, xt=None, x_in=None, div1=None, ell=None, prior=None, logp=None, bpd=None):
+    """The launch after each evaluation of the probability-flow likelihood (dxmi_pf_ll_stage): Heun on (x, ell) over the rows of
+    tab (fp32 [rows, PL_COLS] on the device).  PF_LL_FIRST scales x by the row's XSCALE in place, writes x_in = c_in x, t_out and
+    ell = logdet0.  PF_LL_PREDICT (model_out = F, vjp = g of the evaluation at x): writes k1, xt (if given), x_in = c_in_next xt,
+    t_out and the per-image div1; x is read only.  PF_LL_CORRECT (F, g of the evaluation at xt): x in place, x_in, t_out,
+    ell += (h / 2)(div1 + div2) and, on the row flagged last, prior, logp and bpd.  The probe: eps [N, ...] given, or sample_index
+    (int64 [N]) with seed / draw: Rademacher signs made in the launch, the signs of randn_indexed's normals.  ctl: an int32 [4]
+    device block (row, draw, seed low, seed high) that replaces row / draw / seed.  t_out, div1, ell, prior, logp, bpd: fp32 [N]."""
+    name = "dxmi_pf_ll_stage"
+    same, per = (x, model_out, vjp, eps, k1, xt, x_in), (t_out, div1, ell, prior, logp, bpd)
+    _need_cuda(tab, ctl, sample_index, *same, *per)
+    if mode not in (PF_LL_FIRST, PF_LL_PREDICT, PF_LL_CORRECT):
+        raise _lib.DxmiError(f"{name}: unknown mode {mode}")
+    if not (tab.dtype == torch.float32 and tab.is_contiguous() and tab.dim() == 2 and tab.shape[1] == PL_COLS and tab.shape[0] >= 1):
+        raise _lib.DxmiError(f"{name}: tab must be a contiguous fp32 [rows, {PL_COLS}], got {tab.dtype} {tuple(tab.shape)}")
+    if t_out is None or not (t_out.dtype == torch.float32 and t_out.is_contiguous() and t_out.dim() == 1):
+        raise _lib.DxmiError(f"{name}: t_out must be a contiguous fp32 [N]")
+    N = t_out.numel()
+    if x is None or x.dim() < 2 or x.shape[0] != N or x.numel() == 0:
+        raise _lib.DxmiError(f"{name}: the state [N, ...] must hold t_out's {N} images")
+    need = {PF_LL_FIRST: dict(x_in=x_in, ell=ell),
+            PF_LL_PREDICT: dict(model_out=model_out, vjp=vjp, k1=k1, x_in=x_in, div1=div1),
+            PF_LL_CORRECT: dict(model_out=model_out, vjp=vjp, k1=k1, div1=div1, ell=ell, prior=prior, logp=logp, bpd=bpd)}[mode]
+    missing = [k for k, v in need.items() if v is None]
+    if missing:
+        raise _lib.DxmiError(f"{name}: mode {mode} needs {', '.join(missing)}")
+    if mode != PF_LL_FIRST and (eps is None) == (sample_index is None):
+        raise _lib.DxmiError(f"{name}: the probe is either given (eps) or made in the launch (sample_index): exactly one")
+    if x_in is None and (ctl is not None or int(row) != tab.shape[0] - 1):
+        raise _lib.DxmiError(f"{name}: x_in is needed on every row but the table's last, given by value")
+    for v in same:
+        if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape):
+            raise _lib.DxmiError(f"{name}: fp32 contiguous tensors of the state's shape {tuple(x.shape)}")
+    for v in per:
+        if v is not None and not (v.dtype == torch.float32 and v.is_contiguous() and v.shape == (N,)):
+            raise _lib.DxmiError(f"{name}: the per-image vectors must be contiguous fp32 [{N}]")
+    if sample_index is not None and not (sample_index.dtype == torch.int64 and sample_index.is_contiguous()
+                                         and sample_index.shape == (N,)):
+        raise _lib.DxmiError(f"{name}: sample_index must be a contiguous int64 [{N}]")
+    if ctl is not None and not (ctl.dtype == torch.int32 and ctl.is_contiguous() and ctl.numel() == 4):
+        raise _lib.DxmiError(f"{name}: ctl must be a contiguous int32 [4]")
+    first = mode == PF_LL_FIRST
+    check(load().dxmi_pf_ll_stage(int(mode), _ptr(tab), int(tab.shape[0]), _ptr(ctl), int(row), int(draw) & 0xFFFFFFFF,
+                                  int(seed) & _U64, _ptr(x), _ptr(model_out), _ptr(vjp), None if first else _ptr(eps),
+                                  None if first else _ptr(sample_index), _ptr(k1), _ptr(xt), _ptr(x_in), _ptr(t_out), _ptr(div1),
+                                  _ptr(ell), _ptr(prior), _ptr(logp), _ptr(bpd), N, x.numel() // N, _stream()), name)
+
+
 # ------------------------------------------------------------------------------------------ InceptionV3 of the FID (f4)
 class PackedGConv:
     """BatchNorm-folded bf16 weights [ceil32(Cout)][KH * KW][ceil16(Cin)] + fp32 bias of one BasicConv2d (dxmi_gconv_pack)."""

@@ -140,19 +140,24 @@ class _UNetFn(torch.autograd.Function):
         grads = {}
         N = d_eps.shape[0]
         dev = d_eps.device
-        d_tp = torch.zeros((N, pk["tproj_bias"].numel()), dtype=torch.float32, device=dev)
+        # input_only (input_vjp): the walk forms the data gradients alone: no weight, bias or embedding gradient is launched
+        params = not getattr(ctx, "input_only", False)
+        d_tp = torch.zeros((N, pk["tproj_bias"].numel()), dtype=torch.float32, device=dev) if params else None
 
         def conv_wb(conv, x0, gy, k, x1=None, **kw):
+            if not params:
+                return
             grads[conv.weight], grads[conv.bias] = ops.conv2d_wgrad(x0, gy, k, in1=x1, with_bias=True, **kw)
 
         # ---- head: eps = conv_out(silu(gn(h_last)))
         H = d_eps.shape[2]
         d_pad = torch.zeros((N, H, H, 64), dtype=torch.bfloat16, device=dev)
         d_pad[..., : d_eps.shape[1]] = d_eps.permute(0, 2, 3, 1).to(torch.bfloat16)
-        with ops.wgrad_branch((ctx.a_out, d_pad)):       # (captured step: a parallel branch, joined at the end of this backward)
-            wg = ops._conv2d_wgrad(ctx.a_out, d_pad, 3)
-            grads[net.conv_out.weight] = wg[: net.out_ch].contiguous()
-        grads[net.conv_out.bias] = d_eps.float().sum((0, 2, 3))
+        if params:
+            with ops.wgrad_branch((ctx.a_out, d_pad)):       # (captured step: a parallel branch, joined at the end of this backward)
+                wg = ops._conv2d_wgrad(ctx.a_out, d_pad, 3)
+                grads[net.conv_out.weight] = wg[: net.out_ch].contiguous()
+            grads[net.conv_out.bias] = d_eps.float().sum((0, 2, 3))
         d_a = ops.conv2d(d_pad, pkt["conv_out"])
         g, _, dg, db = ops.groupnorm_silu_bwd(ctx.h_last, d_a, net.norm_out.weight, net.norm_out.bias, silu=True)
         grads[net.norm_out.weight], grads[net.norm_out.bias] = dg, db
@@ -168,7 +173,8 @@ class _UNetFn(torch.autograd.Function):
             d_h, _, dg2, db2 = ops.groupnorm_silu_bwd(h, d_a2, b.norm2.weight, b.norm2.bias, silu=True)
             grads[b.norm2.weight], grads[b.norm2.bias] = dg2, db2
             off = pk[id(b), "toff"]
-            d_tp[:, off:off + b.out_channels] = ops.colsum_per_image(d_h)
+            if params:
+                d_tp[:, off:off + b.out_channels] = ops.colsum_per_image(d_h)
             conv_wb(b.conv1, a1, d_h, 3)
             d_a1 = ops.conv2d(d_h, pkt[id(b), "conv1"])
             if b.in_channels != b.out_channels:
@@ -201,11 +207,12 @@ class _UNetFn(torch.autograd.Function):
             d_a = ops.conv2d(g, pkt[id(m), "proj"])
             d_qkv = ops.attention_bwd(qkv.view(Nn, Hh * Ww, 3 * C), d_a.view(Nn, Hh * Ww, C), 1, float(int(C) ** (-0.5)))
             d_qkv = d_qkv.view(Nn, Hh, Ww, 3 * C)
-            with ops.wgrad_branch((hn, d_qkv)):
-                wq, bq = ops._conv2d_wgrad(hn, d_qkv, 1, with_bias=True)   # the bias gradient from the dY tiles the kernel stages anyway
-                for j, conv in enumerate((m.q, m.k, m.v)):
-                    grads[conv.weight] = wq[j * C:(j + 1) * C].contiguous()
-                    grads[conv.bias] = bq[j * C:(j + 1) * C].contiguous()
+            if params:
+                with ops.wgrad_branch((hn, d_qkv)):
+                    wq, bq = ops._conv2d_wgrad(hn, d_qkv, 1, with_bias=True)   # the bias gradient from the dY tiles the kernel stages anyway
+                    for j, conv in enumerate((m.q, m.k, m.v)):
+                        grads[conv.weight] = wq[j * C:(j + 1) * C].contiguous()
+                        grads[conv.bias] = bq[j * C:(j + 1) * C].contiguous()
             d_hn = ops.conv2d(d_qkv, pkt[id(m), "qkv"])
             d_x, _, dgn, dbn = ops.groupnorm_silu_bwd(xa, d_hn, m.norm.weight, m.norm.bias, add0=g, silu=False)
             grads[m.norm.weight], grads[m.norm.bias] = dgn, dbn
@@ -249,12 +256,15 @@ class _UNetFn(torch.autograd.Function):
         # hs[0] = conv_in output: add its skip gradient, then the stem conv
         if 0 in gskip:
             g = g + gskip.pop(0)
-        grads[net.conv_in.bias] = ops.colsum(g)
-        grads[net.conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
+        if params:
+            grads[net.conv_in.bias] = ops.colsum(g)
+            grads[net.conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
         dx = None
         if ctx.needs_input_grad[1]:
             conv_in_t = net._packs_t.on_demand("conv_in_t", lambda: ops.pack_conv_weight(net.conv_in.weight, transpose_flip=True))
             dx = ops.conv2d(g, conv_in_t, out_nchw_f32=True)
+        if not params:
+            return (None, dx, None)
 
         # ---- temb MLP + all temb_proj layers (reference unet_small.py:296-299, :123): dense backward on the HIP kernels
         # (ops.linear_bwd: transposed-pack linear for dx, the 1x1 weight-gradient kernel for dW), pre-activations recomputed
@@ -287,3 +297,28 @@ class _UNetFn(torch.autograd.Function):
 
 def forward_with_grad(net, x, t):
     return _UNetFn.apply(net, x, t, *ops.fast_parameters(net))
+
+
+class _InputTape:
+    """What _UNetFn.forward keeps for its backward, held outside autograd in the place of the ctx (models.cm.unet_train._Tape's
+    role; this net's loss node keeps its tape on its own ctx, so there is no other tape class here).  input_only is read by the
+    backward with getattr: an autograd ctx has no such attribute, which means False."""
+    needs_input_grad = (False, True, False)
+    input_only = True
+
+
+def input_vjp(net, x, t, v):
+    """The network output F at (x, t) and g = d(v . F)/dx, the vector-Jacobian product of the network at v, with dropout off and no
+    parameter gradient formed (the probability-flow likelihood, models/DxMI/likelihood.py): the training forward with its tape,
+    then the backward walk with its weight, bias and embedding launches switched off.  g is the dx the full backward of
+    forward_with_grad returns, bit for bit.  The net's train / eval mode is left as it was."""
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            tape = _InputTape()
+            out = _UNetFn.forward(tape, net, x, t)
+            g = _UNetFn.backward(tape, v.contiguous().float())[1]
+    finally:
+        net.train(was_training)
+    return out, g

@@ -221,10 +221,14 @@ class _EDMUNetFn(torch.autograd.Function):
         grads = {}
         N = d_out.shape[0]
         dev = d_out.device
-        d_emb_all = torch.zeros(ctx.emb_all_shape, dtype=torch.float32, device=dev)
+        # input_only (input_vjp): the walk forms the data gradients alone: no weight, bias or embedding gradient is launched
+        params = not getattr(ctx, "input_only", False)
+        d_emb_all = torch.zeros(ctx.emb_all_shape, dtype=torch.float32, device=dev) if params else None
         emb_all = ctx.emb_all
 
         def conv_wb(conv, x0, gy, k, x1=None, **kw):
+            if not params:
+                return
             dw, grads[conv.bias] = ops.conv2d_wgrad(x0, gy, k, in1=x1, with_bias=True, **kw)
             grads[conv.weight] = dw.reshape(conv.weight.shape)
 
@@ -238,10 +242,11 @@ class _EDMUNetFn(torch.autograd.Function):
         H, W = d_out.shape[2], d_out.shape[3]
         d_pad = torch.zeros((N, H, W, 64), dtype=torch.bfloat16, device=dev)
         d_pad[..., : d_out.shape[1]] = d_out.permute(0, 2, 3, 1).to(torch.bfloat16)
-        with ops.wgrad_branch((ctx.a_out, d_pad)):       # (captured step: a parallel branch, joined at the end of this backward)
-            wg = ops._conv2d_wgrad(ctx.a_out, d_pad, 3)
-            grads[net.out[2].weight] = wg[: net.out_channels].contiguous()
-        grads[net.out[2].bias] = d_out.float().sum((0, 2, 3))
+        if params:
+            with ops.wgrad_branch((ctx.a_out, d_pad)):       # (captured step: a parallel branch, joined at the end of this backward)
+                wg = ops._conv2d_wgrad(ctx.a_out, d_pad, 3)
+                grads[net.out[2].weight] = wg[: net.out_channels].contiguous()
+            grads[net.out[2].bias] = d_out.float().sum((0, 2, 3))
         d_a = ops.conv2d(d_pad, pkt["conv_out"])
         g, _, _ = gn_bwd(net.out[0], ctx.h_last, d_a, fwd_stats=ctx.s_out)
 
@@ -257,10 +262,12 @@ class _EDMUNetFn(torch.autograd.Function):
             off, eo = pk[id(b), "eoff"], b.emb_layers[1].out_features
             if b.use_scale_shift_norm:
                 d_h, _, d_ss = gn_bwd(gn2, h, d_a2, scale_shift=emb_all[:, off:off + eo], fwd_stats=s2)
-                d_emb_all[:, off:off + eo] = d_ss
+                if params:
+                    d_emb_all[:, off:off + eo] = d_ss
             else:
                 d_h, _, _ = gn_bwd(gn2, h, d_a2, fwd_stats=s2)
-                d_emb_all[:, off:off + eo] = ops.colsum_per_image(d_h)
+                if params:
+                    d_emb_all[:, off:off + eo] = ops.colsum_per_image(d_h)
             conv_wb(conv1, a1p, d_h, 3, upsample=b.up)
             d_a1 = ops.conv2d(d_h, pkt[id(b), "conv1"])
             if b.up:
@@ -336,12 +343,15 @@ class _EDMUNetFn(torch.autograd.Function):
         if 0 in gskip:
             g = g + gskip.pop(0)
         conv_in = net.input_blocks[0][0]
-        grads[conv_in.bias] = ops.colsum(g)
-        grads[conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
+        if params:
+            grads[conv_in.bias] = ops.colsum(g)
+            grads[conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
         dx = None
         if ctx.needs_input_grad[1]:
             conv_in_t = net._packs_t.on_demand("conv_in_t", lambda: ops.pack_conv_weight(conv_in.weight, transpose_flip=True))
             dx = ops.conv2d(g, conv_in_t, out_nchw_f32=True)
+        if not params:
+            return (None, dx, None, None)
 
         # ---- embedding graph (models/cm/unet.py:775-779, :249): time_embed MLP, label embedding, every emb_layers Linear as one
         # operator — dense backward on the HIP kernels (ops.linear_bwd), pre-activations recomputed
@@ -381,8 +391,10 @@ def forward_with_grad(net, x, timesteps, y=None):
 class _Tape:
     """What _EDMUNetFn.forward keeps for its backward, held outside autograd: it takes the place of the ctx for a caller that is an
     autograd node of its own around the network (the loss nodes of models.cm.karras_diffusion), or that keeps no graph at all.
-    No input gradient is formed: such a caller differentiates the parameters only."""
+    No input gradient is formed: such a caller differentiates the parameters only.  input_only (read by the backward with
+    getattr, so an autograd ctx, which has no such attribute, means False): the walk forms the data gradients alone."""
     needs_input_grad = (False, False, False, False)
+    input_only = False
 
 
 def train_forward(net, x, timesteps, y=None):
@@ -395,3 +407,26 @@ def train_forward(net, x, timesteps, y=None):
 def train_backward(tape, d_out):
     """The backward of train_forward -> the gradients of net.parameters(), in that order."""
     return tuple(_EDMUNetFn.backward(tape, d_out)[4:])
+
+
+class _InputTape(_Tape):
+    """The tape of input_vjp: the backward walks it for the input gradient alone."""
+    needs_input_grad = (False, True, False, False)
+    input_only = True
+
+
+def input_vjp(net, x, timesteps, v, y=None):
+    """The network output F at (x, timesteps[, y]) and g = d(v . F)/dx, the vector-Jacobian product of the network at v, with
+    dropout off and no parameter gradient formed (the probability-flow likelihood, models/cm/likelihood.py): the training forward
+    with its tape, then the backward walk with its weight, bias and embedding launches switched off.  g is the dx the full
+    backward of forward_with_grad returns, bit for bit.  The net's train / eval mode is left as it was."""
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            tape = _InputTape()
+            out = _EDMUNetFn.forward(tape, net, x, timesteps, y)
+            g = _EDMUNetFn.backward(tape, v.contiguous().float())[1]
+    finally:
+        net.train(was_training)
+    return out, g

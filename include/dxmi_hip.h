@@ -1325,6 +1325,64 @@ int dxmi_edm_unipc_stage(int32_t mode, const float* tab, int32_t rows, const int
                          const float* model_out, float* hist, float* x_in, float* t_out, float* out, float* pred_xstart, int32_t N,
                          int32_t CHW, void* stream);
 
+/* Likelihood (bits/dim) of the EDM nets and the DDPM teacher by the probability-flow ODE (csrc/pf_likelihood.hip;
+ * models/cm/likelihood.py, models/DxMI/likelihood.py; the reference tree computes no likelihood, so there is no reference call
+ * site).  In the EDM variable dx/dsigma = k = (x - D(x; sigma)) / sigma, d log p / dsigma = -div k; Heun on (x, l) over the nodes
+ * sigma_0 < ... < sigma_S.  Each evaluation is a forward F = net(x_in, time) and the input-only backward g = d(e . F)/d(x_in) at the
+ * probe e (input_vjp); dxmi_pf_ll_stage is the ONE launch after it.  Row i of the table describes the step sigma_i -> sigma_{i+1}.
+ * With K = tab[row], per element in fp32, one rounding per operation (no fused multiply-add), in this order:
+ *   DXMI_PF_LL_FIRST    x = x K[XSCALE] in place, x_in = K[CIN] x, t_out[n] = K[T], ell[n] = K[LOGDET0]
+ *   DXMI_PF_LL_PREDICT  (after the evaluation at (x_i, sigma_i); x is read only)
+ *       k1 = K[KA] x + K[KB] F;  xt = x + K[H] k1;  x_in = K[CIN_NEXT] xt;  t_out[n] = K[T_NEXT]
+ *       div1[n] = sum_i ( K[KA] (e_i e_i) + K[DB] (e_i g_i) )              k1 is written to its buffer, xt when not NULL
+ *   DXMI_PF_LL_CORRECT  (after the evaluation at (xt, sigma_{i+1}))
+ *       xt = x + K[H] k1 (the bits PREDICT formed);  k2 = K[KA2] xt + K[KB2] F;  x = x + K[HH] (k1 + k2) in place
+ *       x_in = K[CIN_NEXT] x (not on the row flagged last);  t_out[n] = K[T_NEXT]
+ *       div2 = sum_i ( K[KA2] (e_i e_i) + K[DB2] (e_i g_i) );  ell[n] = ell[n] + K[HH] (div1[n] + div2)
+ *       on the row with FLAG_LAST: prior[n] = K[PRIOR_Q] sum_i x_i^2 + K[PRIOR_C], logp[n] = ell[n] + prior[n],
+ *       bpd[n] = logp[n] K[BPD_SCALE] + 7
+ * Sums: one workgroup per image; a lane's running sum in index order, the xor-shuffle tree of a wave, a fixed pairing of the four
+ *   wave partials: bitwise equal run to run, and an image's result does not depend on the batch it rides in.
+ * Probe: eps given (any fp32 tensor: Gaussian probes, tests), or eps == NULL and sample_index (int64 [N], DEVICE): Rademacher signs
+ *   made here, e = +1 where the normal dxmi_randn_indexed gives for (seed, sample_index[n], draw, element) is >= 0, else -1.  Exactly
+ *   one of the two (PREDICT, CORRECT); PREDICT and CORRECT of a trajectory pass the same draw.
+ * Control: as dxmi_edm_dpm_stage: ctl NULL: row, draw and seed by value, a row outside [0, rows) is DXMI_EINVAL; ctl an int32[4]
+ *   DEVICE block (row, draw, seed low, seed high): a row outside [0, rows) read there gives NaN in every output of the mode (CORRECT:
+ *   prior, logp and bpd too); nothing outside the table is read.
+ * x_in may be NULL only in CORRECT on the table's last row given by value.  x, k1, xt and x_in are distinct tensors.
+ * tab: fp32 [rows][DXMI_PL_COLS] on the device, every entry formed in float64 on the host and rounded once.  x, model_out, vjp, eps,
+ * k1, xt, x_in: 16-byte aligned; CHW % 4 != 0 takes 4-byte aligned vector accesses and a scalar tail.  N in [1, 65535], CHW < 2^30.
+ * t_out, div1, ell, prior, logp, bpd: fp32 [N].  No workspace, no atomics. */
+#define DXMI_PF_LL_FIRST   0
+#define DXMI_PF_LL_PREDICT 1
+#define DXMI_PF_LL_CORRECT 2
+#define DXMI_PL_T          0   /* time of the evaluation at sigma_i (EDM: 250 ln(sigma_i + 1e-44); DDPM: the integer step) */
+#define DXMI_PL_T_NEXT     1   /* time of the evaluation at sigma_{i+1} */
+#define DXMI_PL_CIN        2   /* c_in(sigma_i): FIRST's factor of x_in */
+#define DXMI_PL_CIN_NEXT   3   /* c_in(sigma_{i+1}) */
+#define DXMI_PL_XSCALE     4   /* FIRST's factor of x (EDM 1; DDPM 1 / sqrt(alpha_bar of the first step)) */
+#define DXMI_PL_LOGDET0    5   /* FIRST's ell (EDM 0; DDPM -(d / 2) ln alpha_bar of the first step) */
+#define DXMI_PL_KA         6   /* (1 - c_skip(sigma_i)) / sigma_i: weight of x in k1 and of e e in div1 */
+#define DXMI_PL_KB         7   /* -c_out(sigma_i) / sigma_i: weight of F in k1 */
+#define DXMI_PL_DB         8   /* -c_out(sigma_i) c_in(sigma_i) / sigma_i: weight of e g in div1 */
+#define DXMI_PL_KA2        9   /* the same three at sigma_{i+1} */
+#define DXMI_PL_KB2       10
+#define DXMI_PL_DB2       11
+#define DXMI_PL_H         12   /* sigma_{i+1} - sigma_i */
+#define DXMI_PL_HH        13   /* (sigma_{i+1} - sigma_i) / 2 */
+#define DXMI_PL_FLAGS     14   /* DXMI_PL_FLAG_* summed, stored as a float */
+#define DXMI_PL_PRIOR_Q   15   /* -1 / (2 prior_var) */
+#define DXMI_PL_PRIOR_C   16   /* -(d / 2) ln(2 pi prior_var) */
+#define DXMI_PL_BPD_SCALE 17   /* -1 / (d ln 2) */
+#define DXMI_PL_SIGMA     18   /* sigma_i; not read by the kernel */
+#define DXMI_PL_SIGMA_NEXT 19  /* sigma_{i+1}; not read by the kernel */
+#define DXMI_PL_COLS      20
+#define DXMI_PL_FLAG_LAST  2
+int dxmi_pf_ll_stage(int32_t mode, const float* tab, int32_t rows, const int32_t* ctl, int32_t row, uint32_t draw, uint64_t seed,
+                     float* x, const float* model_out, const float* vjp, const float* eps, const int64_t* sample_index, float* k1,
+                     float* xt, float* x_in, float* t_out, float* div1, float* ell, float* prior, float* logp, float* bpd, int32_t N,
+                     int32_t CHW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
