@@ -36,8 +36,13 @@ KarrasDenoiser.dm_generator_losses; Diff-Instruct / DMD / DMD2 without its GAN t
 nor --synthetic_data is needed; --gen_update_every (5), --fake_lr (0 = --lr), --dm_weighting dmd|none, --dm_num_scales (1000).  The sigma
 levels of the fake denoiser's loss are EDM's (LogNormalSampler's defaults, as train_edm.py draws them).  --ict, a --loss_norm other than the default and
 --index_sampler lognormal are errors with it.  Its model%06d.pt is what `generate_large.py --karras_sampler dm --pretrained ...` reads.
+--dm_objective sid trains the same generator by score identity distillation instead (KarrasDenoiser.sid_generator_losses; SiD, Zhou et
+al. 2024: the loss is differentiated through both denoisers' inputs): --sid_alpha (1.2), and --gen_sigma, the generator's input level
+(0 = sigma_max; SiD's runs use 2.5, and generate_large.py must then be given the same --gen_sigma).  --dm_weighting none does not go
+with it, and the three flags are errors outside --training_mode dm.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -98,10 +103,12 @@ def parse_args(argv=None):
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
                     fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False,
                     huber_c=0.0, index_sampler="uniform", p_mean=-1.1, p_std=2.0, ict=False, gen_update_every=5, fake_lr=0.0,
-                    dm_weighting="dmd", dm_num_scales=1000)
+                    dm_weighting="dmd", dm_num_scales=1000, dm_objective="dmd", sid_alpha=1.2, gen_sigma=0.0)
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
     args = ap.parse_args(argv)
+    words = sys.argv[1:] if argv is None else argv
+    given = lambda flag: any(a == flag or a.startswith(flag + "=") for a in words)
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")
     if args.training_mode == "dm":
@@ -119,9 +126,20 @@ def parse_args(argv=None):
             ap.error("--gen_update_every must be >= 1, --dm_num_scales >= 2 and --fake_lr >= 0 (0: --lr)")
         if args.use_graph:
             ap.error("--use_graph True does not go with --training_mode dm (two update clocks; DMTrainLoop refuses it)")
+        if args.dm_objective not in ("dmd", "sid"):
+            ap.error(f"--dm_objective {args.dm_objective!r}: dmd or sid")
+        if args.dm_objective == "sid" and args.dm_weighting == "none":
+            ap.error("--dm_weighting none belongs to --dm_objective dmd: score identity distillation has its normaliser in the loss")
+        if not math.isfinite(args.sid_alpha):
+            ap.error(f"--sid_alpha {args.sid_alpha}: a finite number (SiD: 1.2; 1 is its base form)")
+        if not (math.isfinite(args.gen_sigma) and args.gen_sigma >= 0):
+            ap.error(f"--gen_sigma {args.gen_sigma}: a positive level, or 0 for sigma_max")
+    else:
+        for flag in ("--dm_objective", "--sid_alpha", "--gen_sigma"):
+            if given(flag):
+                ap.error(f"{flag} belongs to --training_mode dm, not to --training_mode {args.training_mode}")
     if args.ict:
-        given = any(a == "--training_mode" or a.startswith("--training_mode=") for a in (sys.argv[1:] if argv is None else argv))
-        if given and args.training_mode != "consistency_training":
+        if given("--training_mode") and args.training_mode != "consistency_training":
             ap.error(f"--ict True is improved consistency TRAINING: --training_mode {args.training_mode} does not go with it")
         for k, v in ICT_SETTINGS.items():
             setattr(args, k, v)
@@ -242,12 +260,15 @@ def main_dm(args, device, local_rank, world):
     data = latent_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + local_rank)
     loop = DMTrainLoop(model=model, diffusion=diffusion, real_model=real_model, real_diffusion=real_diffusion, fake_model=fake_model,
                        num_scales=args.dm_num_scales, gen_update_every=args.gen_update_every, fake_lr=args.fake_lr or None,
-                       weighting=args.dm_weighting, data=data, batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr,
+                       weighting=args.dm_weighting, objective=args.dm_objective, sid_alpha=args.sid_alpha,
+                       gen_sigma=args.gen_sigma or None, data=data, batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr,
                        ema_rate=args.ema_rate, log_interval=args.log_interval, save_interval=args.save_interval,
                        resume_checkpoint=args.resume_checkpoint, use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth,
                        schedule_sampler=LogNormalSampler(), weight_decay=args.weight_decay,
                        lr_anneal_steps=args.max_iters if args.max_iters else args.lr_anneal_steps, log_dir=args.log_dir)
-    print0(f"dm: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), weighting {args.dm_weighting}, "
+    print0(f"dm: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
+           + (f"objective sid (alpha {args.sid_alpha}), " if args.dm_objective == "sid" else f"weighting {args.dm_weighting}, ")
+           + f"gen_sigma {args.gen_sigma or diffusion.sigma_max}, "
            f"generator update every {args.gen_update_every} iterations")
     loop.run_loop()
     if loop.logged:

@@ -17,28 +17,16 @@
 // one rounding per written operation: no fused multiply-add between them
 #pragma clang fp contract(off)
 #include "dsm_common.h"
+#include "dm_common.h"
 
 namespace {
 
-constexpr int EW_BLOCK = 256;
-constexpr int EW_UNROLL = 4;      // f32x4 per stream per lane in flight
 // dm_grad_fwd keeps D_f - D_r of a whole image in registers between its two sums: at most DM_REG_V4 f32x4 (48 fp32 VGPRs) per lane,
 // i.e. CHW <= 256 * 4 * DM_REG_V4 = 12288 = 3x64x64, the largest image of the programs here.  A larger image takes the two-pass
 // kernel.  (The compiler issues all 48 loads of a lane before the first use: 244 VGPRs + 16 AGPRs, no scratch, one wave per SIMD,
 // which one workgroup per image does not feel.)
 constexpr int DM_REG_V4 = 12;
 constexpr int DM_REG_CHW = EW_BLOCK * 4 * DM_REG_V4;
-
-__device__ __forceinline__ float dm_level(const int64_t* __restrict__ idx, const float* __restrict__ tab, int S, int b) {
-    const int64_t i = idx[b];
-    return (i >= 0 && i < (int64_t)S) ? tab[i] : __builtin_nanf("");
-}
-
-__device__ __forceinline__ float dm_c_in(float s, float sd2) { return 1.f / __builtin_sqrtf(s * s + sd2); }
-__device__ __forceinline__ float dm_time(float s) { return 250.f * logf(s + 1e-44f); }      // 1000 * 0.25 * th.log(sigmas + 1e-44)
-
-__device__ __forceinline__ f32x4 ld4(const float* p, size_t base, int i) { return *reinterpret_cast<const f32x4*>(p + base + (size_t)i * 4); }
-__device__ __forceinline__ void st4(float* p, size_t base, int i, f32x4 v) { *reinterpret_cast<f32x4*>(p + base + (size_t)i * 4) = v; }
 
 // EDM scalings of the generator's diffusion at sigma_G (distillation=False)
 __device__ __forceinline__ DsmScal dm_gen_scalings(float sg, float sd, float sd2) {
@@ -123,14 +111,6 @@ __global__ __launch_bounds__(EW_BLOCK) void dm_gen_x_kernel(const float* __restr
             }
         }
     }
-}
-
-// fixed order: a lane's running sum in index order, the xor-shuffle tree of a wave, a fixed pairing of the four wave partials
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // s == 0: the sample sits on the teacher's denoised image already, and the normalised direction does not exist: g = 0
@@ -295,16 +275,6 @@ __global__ __launch_bounds__(EW_BLOCK) void dm_gen_bwd_kernel(const float* __res
     }
 }
 
-bool dm_aligned(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr,
-                const void* f = nullptr, const void* g = nullptr) {
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f) | ((uintptr_t)g)) & 15) == 0;
-}
-
-dim3 dm_grid(int N, int CHW) {
-    const int chunks = (CHW / 4 + EW_BLOCK * EW_UNROLL - 1) / (EW_BLOCK * EW_UNROLL);
-    return dim3(chunks < 64 ? chunks : 64, N);
-}
-
 // c_out(sigma_G) with the device's operations, for the backward's scalar
 float dm_host_c_out(float sg, float sd) {
     const float den = sg * sg + sd * sd;
@@ -312,14 +282,6 @@ float dm_host_c_out(float sg, float sd) {
 }
 
 }  // namespace
-
-#define DM_CHECK_SHAPE(fn)                                                                                                       \
-    DXMI_CHECK_ARG(N > 0 && N <= 65535 && CHW > 0 && CHW % 4 == 0 && CHW < (1 << 30), fn ": N (%d) must be in [1, 65535] and "   \
-                   "CHW (%d) a positive multiple of 4 below 2^30", N, CHW)
-#define DM_CHECK_SCALES(fn)                                                                                                      \
-    DXMI_CHECK_ARG(num_scales >= 1 && num_scales < (1 << 30), fn ": num_scales (%d) must be in [1, 2^30)", num_scales)
-#define DM_CHECK_POS(fn, v, what)                                                                                                \
-    DXMI_CHECK_ARG((v) > 0.f && (v) <= 3.0e38f, fn ": " what " (%g) must be positive and finite", (double)(v))
 
 extern "C" int dxmi_dm_gen_in(const float* z, float* x_in, float* t_out, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
                               void* stream) {

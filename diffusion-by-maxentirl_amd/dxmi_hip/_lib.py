@@ -144,6 +144,9 @@ SIGNATURES = {
     "dxmi_dm_grad_fwd": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_float,
                                                                              c_int, c_void_p]),
     "dxmi_dm_gen_bwd": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_void_p]),
+    "dxmi_sid_grad_fwd": (c_int, [c_void_p] * 6 + [c_int, c_float] + [c_void_p] * 5 + [c_int, c_int, c_float, c_float, c_int, c_float,
+                                                                                        c_float, c_int, c_void_p]),
+    "dxmi_sid_join": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
     "dxmi_karras_stage": (c_int, [c_int, c_int, c_void_p, c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
     "dxmi_cm_stage": (c_int, [c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 10 + [c_int] * 4 + [c_void_p]),
     "dxmi_quantize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

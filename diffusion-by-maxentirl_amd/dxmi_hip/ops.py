@@ -1378,6 +1378,55 @@ def dm_gen_bwd(upstream, g, gen_sigma, sigma_data=0.5):
     return d
 
 
+def sid_grad_fwd(f_real, f_fake, x, x_t, indices, t_table, alpha=1.2, real=None, fake=None, outs=None):
+    """-> (v_real, v_fake, d_dir [N, ...], loss [N], s [N]) of score identity distillation (dxmi_sid_grad_fwd): with D_r, D_f as in
+    dm_grad_fwd, delta = D_r - D_f, e = D_f - x, s = mean|x - D_r|: loss = ((1 - alpha) sum(delta^2) + sum(delta e)) / (CHW s);
+    v_real = c_out_r (2 (1 - alpha) delta + e) and v_fake = c_out_f ((2 alpha - 1) delta - e), the cotangents on f_real and f_fake,
+    and d_dir, the paths to x through no network; all three without the 1 / s (sid_join applies it).  real / fake as in dm_grad_fwd.
+    outs: (v_real, v_fake, d_dir, loss, s) to write into."""
+    what = "dxmi_sid_grad_fwd"
+    alpha = float(alpha)
+    if not math.isfinite(alpha):
+        raise _lib.DxmiError(f"{what}: alpha must be finite, got {alpha!r}")
+    N, CHW, S = _dm_operands(what, f_real, indices, t_table, same=(f_fake, x, x_t))
+    sdr, smr, dr = _dm_diffusion(real)
+    sdf, smf, df = _dm_diffusion(fake if fake is not None else real)
+    sdr, sdf = _dm_scalar(what, "sigma_data", sdr), _dm_scalar(what, "sigma_data", sdf)
+    if outs is None:
+        v_r, v_f, d_dir = torch.empty_like(f_real), torch.empty_like(f_real), torch.empty_like(f_real)
+        loss = torch.empty(N, dtype=torch.float32, device=f_real.device)
+        s = torch.empty_like(loss)
+    else:
+        v_r, v_f, d_dir, loss, s = outs
+        _dm_images(what, f_real, same=(v_r, v_f, d_dir), per_sample=(loss, s))
+        if any(v is None for v in outs):
+            raise _lib.DxmiError(f"{what}: outs holds five tensors")
+    check(load().dxmi_sid_grad_fwd(_ptr(f_real), _ptr(f_fake), _ptr(x), _ptr(x_t), _ptr(indices), _ptr(t_table), S, alpha, _ptr(v_r),
+                                   _ptr(v_f), _ptr(d_dir), _ptr(loss), _ptr(s), N, CHW, sdr, float(smr), int(bool(dr)), sdf, float(smf),
+                                   int(bool(df)), _stream()), what)
+    return v_r, v_f, d_dir, loss, s
+
+
+def sid_join(d_dir, g_real, g_fake, s, indices, t_table, real_sigma_data=0.5, fake_sigma_data=None, out=None):
+    """-> g = ((d_dir + c_in_r g_real) + c_in_f g_fake) / s, 0 where s == 0 (dxmi_sid_join): the operand of dm_gen_bwd.  g_real /
+    g_fake: the input gradients of the two denoisers at sid_grad_fwd's cotangents.  out: d_dir itself (in place) or a fresh tensor."""
+    what = "dxmi_sid_join"
+    if s is None:
+        raise _lib.DxmiError(f"{what}: a needed operand is None")
+    N, CHW, S = _dm_operands(what, d_dir, indices, t_table, same=(g_real, g_fake), per_sample=(s,))
+    sdr = _dm_scalar(what, "sigma_data", real_sigma_data)
+    sdf = sdr if fake_sigma_data is None else _dm_scalar(what, "sigma_data", fake_sigma_data)
+    if out is None:
+        out = torch.empty_like(d_dir)
+    elif out is not d_dir:
+        _dm_images(what, d_dir, same=(out,))
+        if any(out.data_ptr() == v.data_ptr() for v in (d_dir, g_real, g_fake)):
+            raise _lib.DxmiError(f"{what}: out may be d_dir itself or a tensor of its own")
+    check(load().dxmi_sid_join(_ptr(d_dir), _ptr(g_real), _ptr(g_fake), _ptr(s), _ptr(indices), _ptr(t_table), S, _ptr(out), N, CHW,
+                               sdr, sdf, _stream()), what)
+    return out
+
+
 EMA_MAX_RATES = 4
 
 

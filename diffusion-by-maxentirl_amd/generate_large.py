@@ -13,7 +13,8 @@ outside the accelerated path and runs only when those are present; --skip_fid wr
 
 `--karras_sampler {heun,dpm,euler,ancestral,progdist}` samples the EDM teacher instead (progdist: a progressively distilled
 student of it, `--pretrained` a model%06d.pt of `cm_train.py --training_mode progdist`, NFE = `--karras_steps`; `--karras_sampler dm`: a
-one-step distribution-matching generator, `--pretrained` a model%06d.pt of `cm_train.py --training_mode dm`, NFE = 1, and
+one-step distribution-matching generator, `--pretrained` a model%06d.pt of `cm_train.py --training_mode dm`, NFE = 1,
+`--gen_sigma` its input level (0 = sigma_max; the level it was trained at, 2.5 for score identity distillation as SiD runs it), and
 `--karras_steps`, `--rho` and the churn and solver flags are refused with it) (models.cm.karras_diffusion.karras_sample,
 reference models/cm/karras_diffusion.py:354-420): `--karras_steps` (40), `--rho`, `--s_churn`, `--s_tmin`, `--s_tmax`,
 `--s_noise`.  Weights: `--pretrained [PATH]` loads a plain U-Net state dict (PATH, or the config's training.pretrained_path),
@@ -40,6 +41,7 @@ or the number of ranks, every transition makes its draw inside its launch (dxmi_
 and samples_N.npz is written in global-index order.
 """
 import argparse
+import math
 import os
 import random
 import time
@@ -91,6 +93,8 @@ def build_parser():
     ap.add_argument("--no_lower_order_final", action="store_const", const=True, default=None,
                     help="dpmpp / sde-dpmpp: keep the full order on the last rows")
     ap.add_argument("--rho", type=float, default=None, help="Karras schedule rho (default 7.0)")
+    ap.add_argument("--gen_sigma", type=float, default=None, help="--karras_sampler dm: the generator's input level, the one it was "
+                                                                  "trained at (cm_train.py --gen_sigma; default 0 = sigma_max)")
     ap.add_argument("--s_churn", type=float, default=None, help="Karras churn (default 0)")
     ap.add_argument("--s_tmin", type=float, default=None, help="churn window lower end (default 0)")
     ap.add_argument("--s_tmax", type=float, default=None, help="churn window upper end (default inf)")
@@ -128,6 +132,8 @@ def parse_args(argv=None):
         given = [f"--{k}" for k in DPM_FLAGS if getattr(args, k) is not None]
         if given:
             ap.error(f"{', '.join(given)} only apply with --karras_sampler dpmpp / sde-dpmpp")
+    if args.gen_sigma is not None and args.karras_sampler != "dm":
+        ap.error("--gen_sigma only applies with --karras_sampler dm")
     if args.cm_sampler is not None:
         return parse_cm_args(ap, args), unknown
     given = [f"--{k}" for k in CM_FLAGS if getattr(args, k) is not None]
@@ -146,6 +152,9 @@ def parse_args(argv=None):
             given = [f"--{k}" for k in ("karras_steps", "rho") + CHURN_FLAGS if getattr(args, k) is not None]
             if given:
                 ap.error(f"{', '.join(given)}: --karras_sampler dm is one network evaluation at sigma_max, it has no steps, ladder or churn")
+            args.gen_sigma = 0.0 if args.gen_sigma is None else args.gen_sigma
+            if not (math.isfinite(args.gen_sigma) and args.gen_sigma >= 0):
+                ap.error(f"--gen_sigma {args.gen_sigma}: a positive level, or 0 for sigma_max")
             return args, unknown
         for k, v in (("karras_steps", 40), ("rho", 7.0), ("s_churn", 0.0), ("s_tmin", 0.0), ("s_tmax", float("inf")),
                      ("s_noise", 1.0)):
@@ -398,7 +407,8 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
             sample = edm_dpm_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
                                     sigma_max=diffusion.sigma_max, use_graph=use_graph, generator=generator, **extra)
         elif sampler == "dm":
-            sample = dm_sample(diffusion, unet, shape, model_kwargs=kw, device=device, generator=generator)
+            sample = dm_sample(diffusion, unet, shape, gen_sigma=args.gen_sigma or None, model_kwargs=kw, device=device,
+                               generator=generator)
         elif sampler == "progdist":             # its own entry point: karras_sample keeps refusing this sampler
             sample = progdist_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
                                      sigma_max=diffusion.sigma_max, rho=args.rho, use_graph=use_graph, generator=generator)

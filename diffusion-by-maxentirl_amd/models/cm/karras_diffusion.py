@@ -54,6 +54,11 @@ G(z) = D_theta(sigma_max z, sigma_max) against a frozen real and an online-train
 node around the generator (_dm_loss, _DMLossFn): dxmi_dm_gen_in, the generator's training forward, dxmi_dm_gen_prep, the two
 denoisers' forward_inference, dxmi_dm_grad_fwd; its backward is dxmi_dm_gen_bwd and the U-Net backward.  dm_sample is its sampler
 (dxmi_dm_gen_in, one evaluation, dxmi_dm_gen_out).  DESIGN 5.32.
+sid_generator_losses (not in the reference: Score identity Distillation, Zhou et al., ICML 2024) trains the same generator with the
+loss differentiated THROUGH both denoisers with respect to their input x_t (no parameter of either receives a gradient).  On HIP
+UNetModels it is ONE node around the generator (_sid_loss, _SiDLossFn) whose forward already forms d loss / d x: dxmi_dm_gen_in, the
+generator's training forward, dxmi_dm_gen_prep (the denoisers' time by _denoiser_time), input_forward on both denoisers, dxmi_sid_grad_fwd, input_backward on both,
+dxmi_sid_join; its backward is dxmi_dm_gen_bwd and the U-Net backward, as _DMLossFn's.  DESIGN 5.34.
 
 The training_losses and consistency_losses nodes run inside a StepGraph capture (models.cm.train_util's use_graph): they read nothing back, allocate from the graph's
 pool only, and their draws (randn_like, the index randint) are torch device RNG, which is graph-aware.  What a capture freezes is
@@ -75,7 +80,7 @@ from dxmi_hip import graph as _graph
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
 from .nn import append_dims, append_zero, mean_flat
-from .unet_train import train_backward, train_forward
+from .unet_train import input_backward, input_forward, train_backward, train_forward
 
 
 def get_weightings(weight_schedule, snrs, sigma_data):
@@ -388,21 +393,38 @@ class _DMSurrogate(torch.autograd.Function):
         return append_dims(up, g.ndim) * g / g[0].numel(), None
 
 
+class _SiDSurrogate(torch.autograd.Function):
+    """The value `loss` of sid_generator_losses' torch path with the gradient already taken: d loss_n / d x = g_n / CHW."""
+
+    @staticmethod
+    def forward(ctx, x, g, loss):
+        ctx.save_for_backward(g)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, up):
+        g, = ctx.saved_tensors
+        return append_dims(up, g.ndim) * g / g[0].numel(), None, None
+
+
 def _scal_kw(d):
     return dict(sigma_data=d.sigma_data, sigma_min=d.sigma_min, distillation=d.distillation)
+
+
+def _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep):
+    """dm_gen_in -> the generator's forward -> (F, tape); keep=False as in _dm_loss."""
+    x_in, t_g = ops.dm_gen_in(z, gen_sigma, diffusion.sigma_data)
+    if keep:
+        return train_forward(net, x_in, t_g, y)
+    return (_train_forward_no_grad(net, x_in, t_g, y) if net.training and net.dropout > 0 else net.forward_inference(x_in, t_g, y)), None
 
 
 def _dm_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting, keep):
     """dm_gen_in -> generator forward -> dm_gen_prep -> the real and the fake denoiser -> dm_grad_fwd.
     -> (loss, x, s, (tape, g)), the last being what _DMLossFn.backward reads.  keep=False: no backward follows, so the generator
     runs forward_inference (the training forward where its dropout is live) and no tape is kept."""
-    sd = diffusion.sigma_data
-    x_in, t_g = ops.dm_gen_in(z, gen_sigma, sd)
-    if keep:
-        F, tape = train_forward(net, x_in, t_g, y)
-    else:
-        F, tape = (_train_forward_no_grad(net, x_in, t_g, y) if net.training and net.dropout > 0 else net.forward_inference(x_in, t_g, y)), None
-    x, x_t, xr_in, t, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, sd, real_diffusion.sigma_data,
+    F, tape = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
+    x, x_t, xr_in, t, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, diffusion.sigma_data, real_diffusion.sigma_data,
                                               fake_diffusion.sigma_data)
     F_r = real.forward_inference(xr_in, t, y)
     F_f = fake.forward_inference(xr_in if xf_in is None else xf_in, t, y)
@@ -431,6 +453,58 @@ class _DMLossFn(torch.autograd.Function):
         grads = train_backward(ctx.tape, dF)
         ctx.tape = None
         return (None,) * 13 + grads
+
+
+def _denoiser_time(tab, indices):
+    """The time input 250 ln(t + 1e-44) of both denoisers at t = tab[indices], by denoise()'s own torch expression on the device.
+    dxmi_dm_gen_prep's logf and torch.log differ in the last bit at some levels (neither is the correctly rounded one throughout),
+    and the bf16 nets turn one ulp of time into output differences of 1e-3 relative; with this the node and the torch path on
+    the same device evaluate the denoisers at bitwise the same point.  An index outside the table is clamped here: its x_t is NaN
+    already."""
+    return 1000 * 0.25 * torch.log(tab[indices.clamp(0, tab.numel() - 1)] + 1e-44)
+
+
+def _sid_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, alpha, keep):
+    """Score identity distillation around the generator -> (loss, x, s, (tape, g)).  keep=True: both denoisers run input_forward,
+    dxmi_sid_grad_fwd forms their cotangents, input_backward walks each tape (dropped at once), dxmi_sid_join forms g = CHW
+    d loss / d x, which _SiDLossFn.backward hands to dxmi_dm_gen_bwd.  keep=False: no backward follows: the generator as in
+    _dm_loss(keep=False), the denoisers' forward_inference, and only loss, x and s are formed."""
+    F, tape = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
+    sdr, sdf = real_diffusion.sigma_data, fake_diffusion.sigma_data
+    x, x_t, xr_in, _, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, diffusion.sigma_data, sdr, sdf)
+    xf_in = xr_in if xf_in is None else xf_in
+    t = _denoiser_time(tab, indices)
+    if keep:
+        F_r, tape_r = input_forward(real, xr_in, t, y)
+        F_f, tape_f = input_forward(fake, xf_in, t, y)
+    else:
+        F_r, F_f = real.forward_inference(xr_in, t, y), fake.forward_inference(xf_in, t, y)
+    v_r, v_f, d_dir, loss, s = ops.sid_grad_fwd(F_r, F_f, x, x_t, indices, tab, alpha, real=_scal_kw(real_diffusion),
+                                                fake=_scal_kw(fake_diffusion))
+    if not keep:
+        return loss, x, s, (None, None)
+    g_r = input_backward(tape_r, v_r)
+    del tape_r, v_r
+    g_f = input_backward(tape_f, v_f)
+    del tape_f, v_f
+    g = ops.sid_join(d_dir, g_r, g_f, s, indices, tab, sdr, sdf, out=d_dir)
+    return loss, x, s, (tape, g)
+
+
+class _SiDLossFn(torch.autograd.Function):
+    """_sid_loss as one node around the generator; outputs (loss, x, dm_norm), of which only loss is differentiable.  The forward
+    has walked both denoisers backward already; the backward is _DMLossFn's."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, alpha, *params):
+        loss, x, s, (ctx.tape, ctx.g) = _sid_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y,
+                                                  gen_sigma, alpha, keep=True)
+        ctx.gen = (gen_sigma, diffusion.sigma_data)
+        ctx.mark_non_differentiable(x, s)
+        ctx.set_materialize_grads(False)
+        return loss, x, s
+
+    backward = staticmethod(_DMLossFn.backward)
 
 
 class KarrasDenoiser:
@@ -741,40 +815,23 @@ class KarrasDenoiser:
         it through x alone.  `self` is the generator's diffusion (distillation=False).  gen_sigma: None = sigma_max.
         indices: drawn uniformly from [ceil(min_step_frac (S - 1)), floor(max_step_frac (S - 1))] when None, then noise, both from
         `generator` where given."""
-        if model_kwargs is None:
-            model_kwargs = {}
-        if self.distillation:
-            raise NotImplementedError("dm_generator_losses: the one-step generator keeps the EDM scalings (distillation=False); a "
-                                      "diffusion with boundary-condition scalings belongs to the consistency losses")
-        if real_model is None or real_diffusion is None or fake_model is None:
-            raise NotImplementedError("dm_generator_losses: Must have a real_model with its real_diffusion and a fake_model")
-        if fake_diffusion is None:
-            fake_diffusion = real_diffusion
+        what = "dm_generator_losses"
+        model_kwargs, fake_diffusion = self._dm_refusals(what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs)
         if weighting not in DM_WEIGHTINGS:
             raise ValueError(f"dm_generator_losses: weighting {weighting!r} is not one of {DM_WEIGHTINGS}")
-        gen_sigma = float(self.sigma_max if gen_sigma is None else gen_sigma)
-        if not (math.isfinite(gen_sigma) and gen_sigma > 0):
-            raise ValueError(f"dm_generator_losses: gen_sigma must be positive and finite, got {gen_sigma!r}")
-        N = z.shape[0]
-        if indices is None:
-            lo, hi = dm_index_range(num_scales, min_step_frac, max_step_frac)
-            if generator is not None:
-                indices = torch.randint(lo, hi + 1, (N,), generator=generator, device=generator.device).to(z.device)
-            else:
-                indices = torch.randint(lo, hi + 1, (N,), device=z.device)
-        if noise is None:
-            if generator is not None:
-                noise = torch.randn(z.shape, generator=generator, device=generator.device, dtype=z.dtype).to(z.device)
-            else:
-                noise = torch.randn_like(z)
+        gen_sigma, indices, noise = self._dm_draws(what, z, num_scales, noise, indices, generator, gen_sigma, min_step_frac, max_step_frac)
         nets = [_hip_unet(m) for m in (model, real_model, fake_model)]
         if all(n is not None for n in nets) and z.is_cuda:
-            return self._dm_generator_losses_hip(nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices,
-                                                 gen_sigma, weighting)
+            args = self._dm_hip_operands(what, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma)
+            if torch.is_grad_enabled():
+                loss, x, s = _DMLossFn.apply(*args, weighting, *ops.fast_parameters(nets[0]))
+            else:
+                loss, x, s, _ = _dm_loss(*args, weighting, keep=False)
+            return {"loss": loss, "x": x, "dm_norm": s}
         if z.requires_grad or noise.requires_grad:
             raise NotImplementedError("dm_generator_losses differentiates the generator's parameters only: z and noise must not "
                                       "require grad")
-        dims = z.ndim
+        N, dims = z.shape[0], z.ndim
         levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(z.device)
         t = levels[indices.to(z.device)]
         sigma_g = torch.full((N,), gen_sigma, dtype=torch.float32, device=z.device)
@@ -790,15 +847,43 @@ class KarrasDenoiser:
             g = torch.where(append_dims(s, dims) == 0, torch.zeros_like(g), g)
         return {"loss": _DMSurrogate.apply(x, g), "x": x.detach().float(), "dm_norm": s}
 
-    def _dm_generator_losses_hip(self, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma,
-                                 weighting):
+    def _dm_refusals(self, what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs):
+        """The refusals dm_generator_losses and sid_generator_losses share -> (model_kwargs, fake_diffusion)."""
+        if self.distillation:
+            raise NotImplementedError(f"{what}: the one-step generator keeps the EDM scalings (distillation=False); a "
+                                      "diffusion with boundary-condition scalings belongs to the consistency losses")
+        if real_model is None or real_diffusion is None or fake_model is None:
+            raise NotImplementedError(f"{what}: Must have a real_model with its real_diffusion and a fake_model")
+        return ({} if model_kwargs is None else model_kwargs), (real_diffusion if fake_diffusion is None else fake_diffusion)
+
+    def _dm_draws(self, what, z, num_scales, noise, indices, generator, gen_sigma, min_step_frac, max_step_frac):
+        """-> (gen_sigma, indices, noise): sigma_G checked, then the draws of one generator step, indices before noise."""
+        gen_sigma = float(self.sigma_max if gen_sigma is None else gen_sigma)
+        if not (math.isfinite(gen_sigma) and gen_sigma > 0):
+            raise ValueError(f"{what}: gen_sigma must be positive and finite, got {gen_sigma!r}")
+        N = z.shape[0]
+        if indices is None:
+            lo, hi = dm_index_range(num_scales, min_step_frac, max_step_frac)
+            if generator is not None:
+                indices = torch.randint(lo, hi + 1, (N,), generator=generator, device=generator.device).to(z.device)
+            else:
+                indices = torch.randint(lo, hi + 1, (N,), device=z.device)
+        if noise is None:
+            if generator is not None:
+                noise = torch.randn(z.shape, generator=generator, device=generator.device, dtype=z.dtype).to(z.device)
+            else:
+                noise = torch.randn_like(z)
+        return gen_sigma, indices, noise
+
+    def _dm_hip_operands(self, what, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma):
+        """The checks of the device path -> the leading arguments of _dm_loss / _sid_loss, up to gen_sigma."""
         net, real, fake = nets
         if z.requires_grad or noise.requires_grad:
-            raise NotImplementedError("dm_generator_losses on the HIP U-Net differentiates the generator's parameters only: "
+            raise NotImplementedError(f"{what} on the HIP U-Net differentiates the generator's parameters only: "
                                       "z and noise must not require grad")
         extra = set(model_kwargs) - {"y"}
         if extra:
-            raise NotImplementedError(f"dm_generator_losses on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
+            raise NotImplementedError(f"{what} on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
         y = model_kwargs.get("y")
         for n in nets:
             if (y is not None) != (n.num_classes is not None):
@@ -807,19 +892,65 @@ class KarrasDenoiser:
         z, noise = f32(z), f32(noise)
         indices = indices.detach().to(device=z.device, dtype=torch.int64).reshape(-1).contiguous()
         if noise.shape != z.shape or indices.numel() != z.shape[0] or z.dim() != 4:
-            raise ValueError(f"dm_generator_losses: noise {tuple(noise.shape)} must match z {tuple(z.shape)} [N, C, H, W] "
+            raise ValueError(f"{what}: noise {tuple(noise.shape)} must match z {tuple(z.shape)} [N, C, H, W] "
                              f"and indices ({indices.numel()}) hold one level per sample")
         levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho)
         if _graph.capturing() and not levels.on_device(z.device):
-            raise DxmiError(f"dm_generator_losses inside a StepGraph capture: the {int(num_scales)}-level table is not on {z.device} "
+            raise DxmiError(f"{what} inside a StepGraph capture: the {int(num_scales)}-level table is not on {z.device} "
                             "yet (cd_levels(...).device_table(device) before the capture: an upload cannot be captured)")
         tab = levels.device_table(z.device)
-        args = (self, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting)
-        if torch.is_grad_enabled():
-            loss, x, s = _DMLossFn.apply(*args, *ops.fast_parameters(net))
-        else:
-            loss, x, s, _ = _dm_loss(*args, keep=False)
-        return {"loss": loss, "x": x, "dm_norm": s}
+        return (self, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma)
+
+    def sid_generator_losses(self, model, z, num_scales=1000, real_model=None, real_diffusion=None, fake_model=None, fake_diffusion=None,
+                             model_kwargs=None, noise=None, indices=None, generator=None, gen_sigma=None, alpha=1.2,
+                             min_step_frac=0.02, max_step_frac=0.98):
+        """Score identity Distillation loss of the one-step generator of dm_generator_losses (SiD, Zhou et al., ICML 2024: the fused
+        loss L~^(alpha) up to the constant 1 / CHW; its released code's (y_real - y_fake) * ((y_real - y) - alpha (y_real - y_fake))
+        / weight_factor) -> {"loss": [N], "x": [N, C, H, W] detached fp32, "dm_norm": [N]}.  With x, x_t, D_r, D_f as there,
+        delta = D_r - D_f and s = mean|x - D_r| ("dm_norm") under stop-gradient:
+            loss_n = ((1 - alpha) sum(delta^2) + sum(delta (D_f - x))) / (CHW s_n)
+        differentiated through x AND through both denoisers with respect to their input x_t; no parameter of the real or the fake
+        net receives a gradient (theirs stay None).  A sample with s == 0 gets loss = 0 and no gradient (SiD's code clips the
+        normaliser at 1e-5 instead), and the mean over CHW stands where SiD sums.  alpha: finite, SiD's default 1.2, 1 its base
+        form; alpha = 0.5 is NOT dm_generator_losses (that one has no Jacobian paths).  Checks, refusals and draws (indices, then
+        noise) are dm_generator_losses's.  DESIGN 5.34."""
+        what = "sid_generator_losses"
+        model_kwargs, fake_diffusion = self._dm_refusals(what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs)
+        alpha = float(alpha)
+        if not math.isfinite(alpha):
+            raise ValueError(f"sid_generator_losses: alpha must be finite, got {alpha!r}")
+        gen_sigma, indices, noise = self._dm_draws(what, z, num_scales, noise, indices, generator, gen_sigma, min_step_frac, max_step_frac)
+        nets = [_hip_unet(m) for m in (model, real_model, fake_model)]
+        if all(n is not None for n in nets) and z.is_cuda:
+            args = self._dm_hip_operands(what, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma)
+            if torch.is_grad_enabled():
+                loss, x, s = _SiDLossFn.apply(*args, alpha, *ops.fast_parameters(nets[0]))
+            else:
+                loss, x, s, _ = _sid_loss(*args, alpha, keep=False)
+            return {"loss": loss, "x": x, "dm_norm": s}
+        if z.requires_grad or noise.requires_grad:
+            raise NotImplementedError("sid_generator_losses differentiates the generator's parameters only: z and noise must not "
+                                      "require grad")
+        N, dims = z.shape[0], z.ndim
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(z.device)
+        t = levels[indices.to(z.device)]
+        sigma_g = torch.full((N,), gen_sigma, dtype=torch.float32, device=z.device)
+        x = self.denoise(model, z * gen_sigma, sigma_g, **model_kwargs)[1]
+        keep = torch.is_grad_enabled()
+        # d loss / d x is taken here, by autograd.grad with respect to x alone: the denoisers' parameters see no backward at all
+        with torch.enable_grad() if keep else torch.no_grad():
+            xd = x.detach().requires_grad_(keep)
+            x_t = xd + noise * append_dims(t, dims)
+            d_real = real_diffusion.denoise(real_model, x_t, t, **model_kwargs)[1]
+            d_fake = fake_diffusion.denoise(fake_model, x_t, t, **model_kwargs)[1]
+            s = mean_flat(torch.abs(xd - d_real)).detach()
+            delta = d_real - d_fake
+            total = ((1 - alpha) * delta ** 2 + delta * (d_fake - xd)).flatten(1).sum(dim=1)
+            live = s != 0
+            loss = torch.where(live, total / (xd[0].numel() * torch.where(live, s, torch.ones_like(s))), torch.zeros_like(s))
+            g = torch.autograd.grad(loss.sum(), xd)[0] * xd[0].numel() if keep else None
+        loss = loss.detach()
+        return {"loss": _SiDSurrogate.apply(x, g, loss) if keep else loss, "x": x.detach().float(), "dm_norm": s}
 
     def denoise(self, model, x_t, sigmas, **model_kwargs):
         scal = self.get_scalings_for_boundary_condition(sigmas) if self.distillation else self.get_scalings(sigmas)

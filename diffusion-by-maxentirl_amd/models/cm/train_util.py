@@ -51,6 +51,7 @@ Refused at construction: use_fp16 off or masters that are not device-aliased (th
 schedule_sampler that draws on the host; a CPU model runs eagerly.
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -597,10 +598,13 @@ class DMTrainLoop(TrainLoop):
     were made before the generator moved.  data yields (z, cond): standard-normal latents of the image shape and {"y": labels}
     for a class-conditional net.  `step` counts iterations and names the checkpoints (no resume_step is added to it); an overflow
     in one trainer skips that trainer's update alone.  save() adds fake_model%06d.pt and fake_opt%06d.pt to TrainLoop's files; a
-    resume reads all of them, and a missing fake_model file is an error.  use_graph=True is refused."""
+    resume reads all of them, and a missing fake_model file is an error.  use_graph=True is refused.
+    objective: "dmd" (dm_generator_losses under `weighting`) or "sid" (sid_generator_losses at sid_alpha: score identity distillation,
+    DESIGN 5.34); only the generator's loss differs, everything else of the loop is the same."""
 
     def __init__(self, *, real_model, real_diffusion, fake_model, fake_diffusion=None, num_scales=1000, gen_update_every=5,
-                 fake_lr=None, weighting="dmd", gen_sigma=None, min_step_frac=0.02, max_step_frac=0.98, generator=None, **kwargs):
+                 fake_lr=None, weighting="dmd", gen_sigma=None, min_step_frac=0.02, max_step_frac=0.98, generator=None, objective="dmd",
+                 sid_alpha=1.2, **kwargs):
         if kwargs.get("use_graph"):
             raise NotImplementedError("DMTrainLoop: use_graph=True is not supported: the generator and the fake denoiser are updated "
                                       "on two clocks, which needs two captured steps and a graph key per clock; train this mode eagerly")
@@ -608,6 +612,10 @@ class DMTrainLoop(TrainLoop):
             raise NotImplementedError("DMTrainLoop: must have a real_model with its real_diffusion and a fake_model")
         if int(gen_update_every) < 1:
             raise ValueError(f"DMTrainLoop: gen_update_every must be at least 1, got {gen_update_every}")
+        if objective not in ("dmd", "sid"):
+            raise ValueError(f"DMTrainLoop: objective {objective!r} is not one of ('dmd', 'sid')")
+        if objective == "sid" and not math.isfinite(float(sid_alpha)):
+            raise ValueError(f"DMTrainLoop: sid_alpha must be finite, got {sid_alpha!r}")
         super().__init__(**kwargs)
         self.real_model, self.real_diffusion, self.fake_model = real_model, real_diffusion, fake_model
         self.fake_diffusion = real_diffusion if fake_diffusion is None else fake_diffusion
@@ -615,6 +623,7 @@ class DMTrainLoop(TrainLoop):
         self.fake_lr = self.lr if fake_lr is None else fake_lr
         self.weighting, self.gen_sigma, self.generator = weighting, gen_sigma, generator
         self.min_step_frac, self.max_step_frac = min_step_frac, max_step_frac
+        self.objective, self.sid_alpha = objective, float(sid_alpha)
         self.real_model.requires_grad_(False)
         self.real_model.eval()
         if self.resume_checkpoint:      # never restart the fake denoiser from the teacher silently
@@ -670,12 +679,15 @@ class DMTrainLoop(TrainLoop):
         for i in range(0, batch.shape[0], self.microbatch):
             z = batch[i:i + self.microbatch].to(self.device)
             micro_cond = {k: v[i:i + self.microbatch].to(self.device) for k, v in cond.items()}
+            if self.objective == "sid":
+                gen_loss, how = self.diffusion.sid_generator_losses, dict(alpha=self.sid_alpha)
+            else:
+                gen_loss, how = self.diffusion.dm_generator_losses, dict(weighting=self.weighting)
             with torch.enable_grad() if gen_turn else torch.no_grad():
-                terms = self.diffusion.dm_generator_losses(
+                terms = gen_loss(
                     self.ddp_model, z, self.num_scales, real_model=self.real_model, real_diffusion=self.real_diffusion,
                     fake_model=self.fake_model, fake_diffusion=self.fake_diffusion, model_kwargs=micro_cond, generator=self.generator,
-                    gen_sigma=self.gen_sigma, weighting=self.weighting, min_step_frac=self.min_step_frac,
-                    max_step_frac=self.max_step_frac)
+                    gen_sigma=self.gen_sigma, min_step_frac=self.min_step_frac, max_step_frac=self.max_step_frac, **how)
             if gen_turn:
                 self.mp_trainer.backward(terms["loss"].mean())
             x = terms["x"]

@@ -415,18 +415,33 @@ class _InputTape(_Tape):
     input_only = True
 
 
-def input_vjp(net, x, timesteps, v, y=None):
-    """The network output F at (x, timesteps[, y]) and g = d(v . F)/dx, the vector-Jacobian product of the network at v, with
-    dropout off and no parameter gradient formed (the probability-flow likelihood, models/cm/likelihood.py): the training forward
-    with its tape, then the backward walk with its weight, bias and embedding launches switched off.  g is the dx the full
-    backward of forward_with_grad returns, bit for bit.  The net's train / eval mode is left as it was."""
+def input_forward(net, x, timesteps, y=None):
+    """The first half of input_vjp -> (F, tape): the training forward with dropout off (eval mode, the net's own mode restored),
+    its tape kept for input_backward.  For a caller whose cotangent is known only after this forward (score identity distillation,
+    KarrasDenoiser.sid_generator_losses, needs both denoisers' outputs first)."""
     was_training = net.training
     net.eval()
     try:
         with torch.no_grad():
             tape = _InputTape()
             out = _EDMUNetFn.forward(tape, net, x, timesteps, y)
-            g = _EDMUNetFn.backward(tape, v.contiguous().float())[1]
     finally:
         net.train(was_training)
-    return out, g
+    return out, tape
+
+
+def input_backward(tape, v):
+    """The second half of input_vjp -> g = d(v . F)/dx for the tape of input_forward: the backward walk with its weight, bias and
+    embedding launches switched off.  A tape is walked once; drop it afterwards."""
+    with torch.no_grad():
+        return _EDMUNetFn.backward(tape, v.contiguous().float())[1]
+
+
+def input_vjp(net, x, timesteps, v, y=None):
+    """The network output F at (x, timesteps[, y]) and g = d(v . F)/dx, the vector-Jacobian product of the network at v, with
+    dropout off and no parameter gradient formed (the probability-flow likelihood, models/cm/likelihood.py): the training forward
+    with its tape, then the backward walk with its weight, bias and embedding launches switched off (input_forward, then
+    input_backward).  g is the dx the full backward of forward_with_grad returns, bit for bit.  The net's train / eval mode is left
+    as it was."""
+    out, tape = input_forward(net, x, timesteps, y)
+    return out, input_backward(tape, v)

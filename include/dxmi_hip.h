@@ -734,6 +734,26 @@ int dxmi_dm_grad_fwd(const float* f_real, const float* f_fake, const float* x, c
 int dxmi_dm_gen_bwd(const float* upstream, const float* g, float* d_f_gen, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
                     void* stream);
 
+/* Score identity Distillation of the same one-step generator (KarrasDenoiser.sid_generator_losses; SiD, Zhou et al., ICML 2024, the
+ * fused loss L~^(alpha); csrc/sid_train.hip): the loss is differentiated through both denoisers with respect to their
+ * input x_t, and these are the two launches around the two input-only backward walks.  Tensors, table, index rule, rounding and
+ * sum order as for dxmi_dm_*.  With D_r, D_f as dxmi_dm_grad_fwd forms them, delta = D_r - D_f and e = D_f - x:
+ * dxmi_sid_grad_fwd: s[n] = mean|x - D_r|, loss[n] = ((1 - alpha) sum(delta^2) + sum(delta e)) / (CHW s[n]) (0 where s == 0);
+ *   a_r = 2 (1 - alpha) delta + e, a_f = (2 alpha - 1) delta - e; v_real = c_out_r a_r and v_fake = c_out_f a_f, the cotangents
+ *   on f_real and f_fake, and d_dir = (c_skip_r a_r + c_skip_f a_f) - delta, all three WITHOUT the factor 1 / s.  One workgroup
+ *   per image and one pass over the operands at every CHW.  alpha must be finite.
+ * dxmi_sid_join: with g_real = J_real^T v_real and g_fake = J_fake^T v_fake, each with respect to its net's own input c_in x_t:
+ *   g = ((d_dir + c_in_r g_real) + c_in_f g_fake) / s, 0 where s == 0: d loss_n / d x = g_n / CHW, the operand of dxmi_dm_gen_bwd.
+ *   c_in is the same under the EDM and the boundary-condition scalings, so only the two sigma_data are taken.  g may alias d_dir
+ *   (and nothing else). */
+int dxmi_sid_grad_fwd(const float* f_real, const float* f_fake, const float* x, const float* x_t, const int64_t* indices,
+                      const float* t_table, int32_t num_scales, float alpha, float* v_real, float* v_fake, float* d_dir, float* loss,
+                      float* s, int32_t N, int32_t CHW, float real_sigma_data, float real_sigma_min, int32_t real_distillation,
+                      float fake_sigma_data, float fake_sigma_min, int32_t fake_distillation, void* stream);
+int dxmi_sid_join(const float* d_dir, const float* g_real, const float* g_fake, const float* s, const int64_t* indices,
+                  const float* t_table, int32_t num_scales, float* g, int32_t N, int32_t CHW, float real_sigma_data,
+                  float fake_sigma_data, void* stream);
+
 /* TD step of DxMI_Trainer.update_f_v on the replay ring, data side in one launch (reference trainer.py:271-300, :163-169): rows
  * `state_rows[b]` (and `next_rows[b]`, or the dense re-drawn next states of value_resample) of the ring's fp32 [n_src_rows, CHW]
  * trajectory block are gathered into out_state / out_next — the two halves of the batch [next_state | state] the value net
