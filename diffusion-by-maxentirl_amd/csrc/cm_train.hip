@@ -15,16 +15,11 @@
 // Elementwise streams: one workgroup row per image, 16 bytes per lane, several loads in flight; per-sample sums in a fixed order
 // (bitwise reproducible).  The time levels are gathered from one small device table by index; an index outside [0, S - 2] gives
 // NaN levels (nothing is read outside the table).
-#include "common.h"
-
-// the reference's fp32 operation order, one rounding per torch op: no fused multiply-add between them
-#pragma clang fp contract(off)
 #include "dsm_common.h"
+#include "ew_common.h"
 
 namespace {
 
-constexpr int EW_BLOCK = 256;
-constexpr int EW_UNROLL = 4;      // f32x4 per stream per lane in flight
 constexpr int RS = 32;            // F.interpolate(size=32)
 
 struct Levels {
@@ -40,12 +35,6 @@ __device__ __forceinline__ Levels cd_levels(const int64_t* __restrict__ idx, con
     return r;
 }
 
-__device__ __forceinline__ float cd_c_in(float s, float sd2) { return 1.f / __builtin_sqrtf(s * s + sd2); }
-__device__ __forceinline__ float cd_time(float s) { return 250.f * logf(s + 1e-44f); }      // 1000 * 0.25 * th.log(sigmas + 1e-44)
-
-__device__ __forceinline__ f32x4 ld4(const float* p, size_t base, int i) { return *reinterpret_cast<const f32x4*>(p + base + (size_t)i * 4); }
-__device__ __forceinline__ void st4(float* p, size_t base, int i, f32x4 v) { *reinterpret_cast<f32x4*>(p + base + (size_t)i * 4) = v; }
-
 __global__ __launch_bounds__(EW_BLOCK) void cd_prep_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
                                                            const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
                                                            float* __restrict__ x_t, float* __restrict__ x_in,
@@ -53,8 +42,8 @@ __global__ __launch_bounds__(EW_BLOCK) void cd_prep_kernel(const float* __restri
                                                            float sd2, float sd2_te) {
     const int b = blockIdx.y;
     const float t = cd_levels(idx, tab, S, b).t;
-    const float c_in = cd_c_in(t, sd2), c_in_te = cd_c_in(t, sd2_te);
-    if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = cd_time(t);
+    const float c_in = dsm_c_in(t, sd2), c_in_te = dsm_c_in(t, sd2_te);
+    if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dsm_time(t);
     const size_t base = (size_t)b * CHW;
     const int n4 = CHW / 4;
     for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
@@ -101,8 +90,8 @@ __global__ __launch_bounds__(EW_BLOCK) void cd_solver_kernel(const float* __rest
     // EULER_X0 forms no denoiser: it has no scalings, and the solver_* arguments of the entry point mean nothing to it
     const DsmScal c = MODE == DXMI_CD_EULER_X0 ? DsmScal{0.f, 0.f, 0.f, 0.f}
                                                : dsm_scalings(MODE == DXMI_CD_HEUN_CORR ? t2 : t, sd, sd2, sigma_min, distill, DXMI_DSM_W_UNIFORM, 0.f);
-    const float c_in_next = cd_c_in(t2, sd2_next);
-    if (blockIdx.x == 0 && threadIdx.x == 0) t_next[b] = cd_time(t2);
+    const float c_in_next = dsm_c_in(t2, sd2_next);
+    if (blockIdx.x == 0 && threadIdx.x == 0) t_next[b] = dsm_time(t2);
     const size_t base = (size_t)b * CHW;
     const int n4 = CHW / 4;
     for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
@@ -153,14 +142,6 @@ __global__ __launch_bounds__(EW_BLOCK) void cd_solver_kernel(const float* __rest
             st4(x_in_next, base, i, on);
         }
     }
-}
-
-// fixed order: a lane's running sum in index order, the xor-shuffle tree of a wave, a fixed pairing of the four wave partials
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 struct LossScal {
@@ -492,20 +473,10 @@ __global__ __launch_bounds__(EW_BLOCK) void cd_lpips_bwd_kernel(const float* __r
     }
 }
 
-bool cd_aligned(const void* a, const void* b, const void* c, const void* d, const void* e = nullptr, const void* f = nullptr) {
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15) == 0;
-}
-
-dim3 cd_grid(int N, int CHW) {
-    const int chunks = (CHW / 4 + EW_BLOCK * EW_UNROLL - 1) / (EW_BLOCK * EW_UNROLL);
-    return dim3(chunks < 64 ? chunks : 64, N);
-}
-
 }  // namespace
 
 #define CD_CHECK_SHAPE(fn)                                                                                                       \
-    DXMI_CHECK_ARG(N > 0 && N <= 65535 && CHW > 0 && CHW % 4 == 0, fn ": N (%d) must be in [1, 65535] and CHW (%d) a positive "  \
-                   "multiple of 4", N, CHW);                                                                                     \
+    EW_CHECK_SHAPE(fn);                                                                                                          \
     DXMI_CHECK_ARG(num_scales >= 2, fn ": num_scales (%d) must be at least 2", num_scales)
 
 extern "C" int dxmi_cd_prep(const float* x_start, const float* noise, const int64_t* indices, const float* t_table, int32_t num_scales,
@@ -513,8 +484,8 @@ extern "C" int dxmi_cd_prep(const float* x_start, const float* noise, const int6
                             float teacher_sigma_data, void* stream) {
     DXMI_CHECK_ARG(x_start && noise && indices && t_table && x_t && x_in && t_out, "dxmi_cd_prep: null pointer");
     CD_CHECK_SHAPE("dxmi_cd_prep");
-    DXMI_CHECK_ARG(cd_aligned(x_start, noise, x_t, x_in, x_in_teacher), "dxmi_cd_prep: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(cd_prep_kernel, cd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, x_start, noise, indices, t_table,
+    EW_CHECK_ALIGNED("dxmi_cd_prep", x_start, noise, x_t, x_in, x_in_teacher);
+    hipLaunchKernelGGL(cd_prep_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, x_start, noise, indices, t_table,
                        num_scales, x_t, x_in, t_out, x_in_teacher, CHW, sigma_data * sigma_data, teacher_sigma_data * teacher_sigma_data);
     DXMI_CHECK_LAUNCH("dxmi_cd_prep");
     return DXMI_OK;
@@ -531,9 +502,8 @@ extern "C" int dxmi_cd_solver(int32_t mode, const float* x_start, const float* x
     if (mode == DXMI_CD_HEUN_CORR)
         DXMI_CHECK_ARG(model_out && d && samples && x_t2, "dxmi_cd_solver: HEUN_CORR needs model_out, d, samples and x_t2");
     CD_CHECK_SHAPE("dxmi_cd_solver");
-    DXMI_CHECK_ARG(cd_aligned(x_start, x_t, model_out, d, samples, x_t2) && cd_aligned(x_in_next, nullptr, nullptr, nullptr),
-                   "dxmi_cd_solver: tensors must be 16-byte aligned");
-    const dim3 grid = cd_grid(N, CHW), block(EW_BLOCK);
+    EW_CHECK_ALIGNED("dxmi_cd_solver", x_start, x_t, model_out, d, samples, x_t2, x_in_next);
+    const dim3 grid = ew_grid(N, CHW), block(EW_BLOCK);
     const float sd = solver_sigma_data, sd2 = sd * sd, sd2n = next_sigma_data * next_sigma_data;
     const int dist = (int)(solver_distillation != 0);
 #define CD_SOLVER_LAUNCH(M)                                                                                                        \
@@ -564,7 +534,7 @@ extern "C" int dxmi_cd_loss_fwd(const float* f_online, const float* f_target, co
                                 int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(f_online && f_target && x_t && x_t2 && indices && t_table && loss, "dxmi_cd_loss_fwd: null pointer");
     CD_CHECK_LOSS("dxmi_cd_loss_fwd");
-    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2), "dxmi_cd_loss_fwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_cd_loss_fwd", f_online, f_target, x_t, x_t2);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
     const int dist = (int)(distillation != 0);
     const dim3 grid(N), block(EW_BLOCK);
@@ -588,7 +558,7 @@ extern "C" int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, cons
     DXMI_CHECK_ARG(g_loss && f_online && f_target && x_t && x_t2 && indices && t_table && d_f_online, "dxmi_cd_loss_bwd: null pointer");
     CD_CHECK_LOSS("dxmi_cd_loss_bwd");
     DXMI_CHECK_ARG(C <= 65535, "dxmi_cd_loss_bwd: C (%d) must be at most 65535", C);
-    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2, d_f_online), "dxmi_cd_loss_bwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_cd_loss_bwd", f_online, f_target, x_t, x_t2, d_f_online);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
     const int dist = (int)(distillation != 0);
     const dim3 block(EW_BLOCK);
@@ -597,11 +567,11 @@ extern "C" int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, cons
                            t_table, num_scales, d_f_online, C, H, W, sigma_data, sd2, sigma_min, dist, weight_schedule, inv_sd2,
                            (float)(1.0 / (double)(C * RS * RS)));
     else if (loss_norm == DXMI_CD_NORM_L1)
-        hipLaunchKernelGGL(cd_loss_bwd_kernel<DXMI_CD_NORM_L1>, cd_grid(N, CHW), block, 0, (hipStream_t)stream, g_loss, f_online, f_target,
+        hipLaunchKernelGGL(cd_loss_bwd_kernel<DXMI_CD_NORM_L1>, ew_grid(N, CHW), block, 0, (hipStream_t)stream, g_loss, f_online, f_target,
                            x_t, x_t2, indices, t_table, num_scales, d_f_online, CHW, sigma_data, sd2, sigma_min, dist, weight_schedule,
                            inv_sd2, (float)(1.0 / (double)CHW));
     else
-        hipLaunchKernelGGL(cd_loss_bwd_kernel<DXMI_CD_NORM_L2>, cd_grid(N, CHW), block, 0, (hipStream_t)stream, g_loss, f_online, f_target,
+        hipLaunchKernelGGL(cd_loss_bwd_kernel<DXMI_CD_NORM_L2>, ew_grid(N, CHW), block, 0, (hipStream_t)stream, g_loss, f_online, f_target,
                            x_t, x_t2, indices, t_table, num_scales, d_f_online, CHW, sigma_data, sd2, sigma_min, dist, weight_schedule,
                            inv_sd2, (float)(1.0 / (double)CHW));
     DXMI_CHECK_LAUNCH("dxmi_cd_loss_bwd");
@@ -610,7 +580,6 @@ extern "C" int dxmi_cd_loss_bwd(const float* g_loss, const float* f_online, cons
 
 #define CD_CHECK_HUBER(fn)                                                                                                       \
     CD_CHECK_SHAPE(fn);                                                                                                          \
-    DXMI_CHECK_ARG(CHW < (1 << 30), fn ": CHW (%d) must be below 2^30", CHW);                                                    \
     DXMI_CHECK_ARG(huber_c > 0.f && huber_c <= 3.4028234663852886e38f, fn ": huber_c (%g) must be finite and positive",          \
                    (double)huber_c);                                                                                             \
     DXMI_CHECK_ARG(weight_schedule >= DXMI_DSM_W_SNR && weight_schedule <= DXMI_DSM_W_ICT, fn ": unknown weight schedule %d",    \
@@ -622,7 +591,7 @@ extern "C" int dxmi_cd_huber_fwd(const float* f_online, const float* f_target, c
                                  int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(f_online && f_target && x_t && x_t2 && indices && t_table && loss && ssq, "dxmi_cd_huber_fwd: null pointer");
     CD_CHECK_HUBER("dxmi_cd_huber_fwd");
-    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2), "dxmi_cd_huber_fwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_cd_huber_fwd", f_online, f_target, x_t, x_t2);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
     hipLaunchKernelGGL(cd_huber_fwd_kernel, dim3(N), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_online, f_target, x_t, x_t2, indices, t_table,
                        num_scales, loss, ssq, CHW, huber_c, sigma_data, sd2, sigma_min, (int)(distillation != 0), weight_schedule, inv_sd2);
@@ -637,9 +606,9 @@ extern "C" int dxmi_cd_huber_bwd(const float* g_loss, const float* ssq, const fl
     DXMI_CHECK_ARG(g_loss && ssq && f_online && f_target && x_t && x_t2 && indices && t_table && d_f_online,
                    "dxmi_cd_huber_bwd: null pointer");
     CD_CHECK_HUBER("dxmi_cd_huber_bwd");
-    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2, d_f_online), "dxmi_cd_huber_bwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_cd_huber_bwd", f_online, f_target, x_t, x_t2, d_f_online);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
-    hipLaunchKernelGGL(cd_huber_bwd_kernel, cd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, ssq, f_online, f_target, x_t,
+    hipLaunchKernelGGL(cd_huber_bwd_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, ssq, f_online, f_target, x_t,
                        x_t2, indices, t_table, num_scales, d_f_online, CHW, huber_c, sigma_data, sd2, sigma_min, (int)(distillation != 0),
                        weight_schedule, inv_sd2);
     DXMI_CHECK_LAUNCH("dxmi_cd_huber_bwd");
@@ -648,7 +617,6 @@ extern "C" int dxmi_cd_huber_bwd(const float* g_loss, const float* ssq, const fl
 
 #define CD_CHECK_LPIPS(fn)                                                                                                       \
     CD_CHECK_SHAPE(fn);                                                                                                          \
-    DXMI_CHECK_ARG(CHW < (1 << 30), fn ": CHW (%d) must be below 2^30", CHW);                                                    \
     DXMI_CHECK_ARG(weight_schedule >= DXMI_DSM_W_SNR && weight_schedule <= DXMI_DSM_W_UNIFORM, fn ": unknown weight schedule %d", \
                    weight_schedule)
 
@@ -658,9 +626,9 @@ extern "C" int dxmi_cd_lpips_images(const float* f_online, const float* f_target
                                     int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(f_online && f_target && x_t && x_t2 && indices && t_table && x01 && weights, "dxmi_cd_lpips_images: null pointer");
     CD_CHECK_LPIPS("dxmi_cd_lpips_images");
-    DXMI_CHECK_ARG(cd_aligned(f_online, f_target, x_t, x_t2, x01), "dxmi_cd_lpips_images: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_cd_lpips_images", f_online, f_target, x_t, x_t2, x01);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
-    hipLaunchKernelGGL(cd_lpips_images_kernel, cd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_online, f_target, x_t, x_t2, indices,
+    hipLaunchKernelGGL(cd_lpips_images_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_online, f_target, x_t, x_t2, indices,
                        t_table, num_scales, x01, weights, N, CHW, sigma_data, sd2, sigma_min, (int)(distillation != 0), weight_schedule, inv_sd2);
     DXMI_CHECK_LAUNCH("dxmi_cd_lpips_images");
     return DXMI_OK;
@@ -671,9 +639,9 @@ extern "C" int dxmi_cd_lpips_bwd(const float* g_loss, const float* d_x01, const 
                                  int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(g_loss && d_x01 && indices && t_table && d_f_online, "dxmi_cd_lpips_bwd: null pointer");
     CD_CHECK_LPIPS("dxmi_cd_lpips_bwd");
-    DXMI_CHECK_ARG(cd_aligned(d_x01, d_f_online, nullptr, nullptr), "dxmi_cd_lpips_bwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_cd_lpips_bwd", d_x01, d_f_online);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
-    hipLaunchKernelGGL(cd_lpips_bwd_kernel, cd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, d_x01, indices, t_table, num_scales,
+    hipLaunchKernelGGL(cd_lpips_bwd_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, d_x01, indices, t_table, num_scales,
                        d_f_online, CHW, sigma_data, sd2, sigma_min, (int)(distillation != 0), weight_schedule, inv_sd2);
     DXMI_CHECK_LAUNCH("dxmi_cd_lpips_bwd");
     return DXMI_OK;

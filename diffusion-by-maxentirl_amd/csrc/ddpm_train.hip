@@ -7,15 +7,9 @@
 // All three are HBM-bound: one workgroup row per image, 16 bytes per lane, several loads in flight per wave; the per-sample sum is
 // reduced in a fixed order (bitwise reproducible).  The two coefficients are gathered from one small device table by index; an
 // index outside [0, T) gives NaN coefficients (nothing is read outside the table).
-#include "common.h"
-
-// torch's fp32 operation order, one rounding per torch op: no fused multiply-add between them
-#pragma clang fp contract(off)
+#include "ew_common.h"
 
 namespace {
-
-constexpr int EW_BLOCK = 256;
-constexpr int EW_UNROLL = 4;      // f32x4 per stream per lane in flight
 
 __global__ __launch_bounds__(EW_BLOCK) void ddpm_prep_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
                                                              const int64_t* __restrict__ t_idx, const float* __restrict__ table,
@@ -35,8 +29,8 @@ __global__ __launch_bounds__(EW_BLOCK) void ddpm_prep_kernel(const float* __rest
         for (int u = 0; u < EW_UNROLL; ++u) {
             const int i = i0 + u * EW_BLOCK;
             if (i < n4) {
-                xv[u] = *reinterpret_cast<const f32x4*>(x0 + base + (size_t)i * 4);
-                nv[u] = *reinterpret_cast<const f32x4*>(noise + base + (size_t)i * 4);
+                xv[u] = ld4(x0, base, i);
+                nv[u] = ld4(noise, base, i);
             }
         }
 #pragma unroll
@@ -49,13 +43,12 @@ __global__ __launch_bounds__(EW_BLOCK) void ddpm_prep_kernel(const float* __rest
                 const float px = ca * xv[u][e], pn = cb * nv[u][e];     // two products, one sum
                 o[e] = px + pn;
             }
-            *reinterpret_cast<f32x4*>(x_t + base + (size_t)i * 4) = o;
+            st4(x_t, base, i, o);
         }
     }
 }
 
-// One workgroup per sample: each lane sums its elements in index order, then a fixed xor-shuffle tree per wave and a fixed
-// pairing of the four wave partials.
+// One workgroup per sample: each lane sums its elements in index order, then block_sum.
 __global__ __launch_bounds__(EW_BLOCK) void ddpm_loss_fwd_kernel(const float* __restrict__ eps, const float* __restrict__ noise,
                                                                  float* __restrict__ loss, int CHW) {
     __shared__ float red[EW_BLOCK / 64];
@@ -69,8 +62,8 @@ __global__ __launch_bounds__(EW_BLOCK) void ddpm_loss_fwd_kernel(const float* __
         for (int u = 0; u < EW_UNROLL; ++u) {
             const int i = i0 + u * EW_BLOCK;
             if (i < n4) {
-                ev[u] = *reinterpret_cast<const f32x4*>(eps + base + (size_t)i * 4);
-                nv[u] = *reinterpret_cast<const f32x4*>(noise + base + (size_t)i * 4);
+                ev[u] = ld4(eps, base, i);
+                nv[u] = ld4(noise, base, i);
             }
         }
 #pragma unroll
@@ -84,10 +77,8 @@ __global__ __launch_bounds__(EW_BLOCK) void ddpm_loss_fwd_kernel(const float* __
             }
         }
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[b] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)CHW;       // mean_flat
+    const float tot = block_sum(acc, red);
+    if (threadIdx.x == 0) loss[b] = tot / (float)CHW;       // mean_flat
 }
 
 // autograd of ((a - b) ** 2).mean(dim), node by node: mean -> g / D; pow(., 2) -> . * (2 e).
@@ -103,8 +94,8 @@ __global__ __launch_bounds__(EW_BLOCK) void ddpm_loss_bwd_kernel(const float* __
         for (int u = 0; u < EW_UNROLL; ++u) {
             const int i = i0 + u * EW_BLOCK;
             if (i < n4) {
-                ev[u] = *reinterpret_cast<const f32x4*>(eps + base + (size_t)i * 4);
-                nv[u] = *reinterpret_cast<const f32x4*>(noise + base + (size_t)i * 4);
+                ev[u] = ld4(eps, base, i);
+                nv[u] = ld4(noise, base, i);
             }
         }
 #pragma unroll
@@ -114,33 +105,20 @@ __global__ __launch_bounds__(EW_BLOCK) void ddpm_loss_bwd_kernel(const float* __
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = g * (2.f * (ev[u][e] - nv[u][e]));
-            *reinterpret_cast<f32x4*>(d_eps + base + (size_t)i * 4) = o;
+            st4(d_eps, base, i, o);
         }
     }
 }
 
-bool ddpm_aligned(const void* a, const void* b, const void* c) {
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
-}
-
-dim3 ddpm_grid(int N, int CHW) {
-    const int chunks = (CHW / 4 + EW_BLOCK * EW_UNROLL - 1) / (EW_BLOCK * EW_UNROLL);
-    return dim3(chunks < 64 ? chunks : 64, N);
-}
-
 }  // namespace
-
-#define DDPM_CHECK_SHAPE(fn)                                                                                                     \
-    DXMI_CHECK_ARG(N > 0 && N <= 65535 && CHW > 0 && CHW % 4 == 0, fn ": N (%d) must be in [1, 65535] and CHW (%d) a positive "  \
-                   "multiple of 4", N, CHW)
 
 extern "C" int dxmi_ddpm_prep(const float* x_start, const float* noise, const int64_t* t_idx, const float* table, int32_t T,
                               float* x_t, float* t_out, int32_t N, int32_t CHW, void* stream) {
     DXMI_CHECK_ARG(x_start && noise && t_idx && table && x_t && t_out, "dxmi_ddpm_prep: null pointer");
-    DDPM_CHECK_SHAPE("dxmi_ddpm_prep");
+    EW_CHECK_SHAPE("dxmi_ddpm_prep");
     DXMI_CHECK_ARG(T >= 1, "dxmi_ddpm_prep: T (%d) must be at least 1", T);
-    DXMI_CHECK_ARG(ddpm_aligned(x_start, noise, x_t), "dxmi_ddpm_prep: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(ddpm_prep_kernel, ddpm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, x_start, noise, t_idx, table,
+    EW_CHECK_ALIGNED("dxmi_ddpm_prep", x_start, noise, x_t);
+    hipLaunchKernelGGL(ddpm_prep_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, x_start, noise, t_idx, table,
                        (int)T, x_t, t_out, CHW);
     DXMI_CHECK_LAUNCH("dxmi_ddpm_prep");
     return DXMI_OK;
@@ -148,8 +126,8 @@ extern "C" int dxmi_ddpm_prep(const float* x_start, const float* noise, const in
 
 extern "C" int dxmi_ddpm_loss_fwd(const float* eps_pred, const float* noise, float* loss, int32_t N, int32_t CHW, void* stream) {
     DXMI_CHECK_ARG(eps_pred && noise && loss, "dxmi_ddpm_loss_fwd: null pointer");
-    DDPM_CHECK_SHAPE("dxmi_ddpm_loss_fwd");
-    DXMI_CHECK_ARG(ddpm_aligned(eps_pred, noise, nullptr), "dxmi_ddpm_loss_fwd: tensors must be 16-byte aligned");
+    EW_CHECK_SHAPE("dxmi_ddpm_loss_fwd");
+    EW_CHECK_ALIGNED("dxmi_ddpm_loss_fwd", eps_pred, noise);
     hipLaunchKernelGGL(ddpm_loss_fwd_kernel, dim3(N), dim3(EW_BLOCK), 0, (hipStream_t)stream, eps_pred, noise, loss, CHW);
     DXMI_CHECK_LAUNCH("dxmi_ddpm_loss_fwd");
     return DXMI_OK;
@@ -158,9 +136,9 @@ extern "C" int dxmi_ddpm_loss_fwd(const float* eps_pred, const float* noise, flo
 extern "C" int dxmi_ddpm_loss_bwd(const float* g_loss, const float* eps_pred, const float* noise, float* d_eps, int32_t N,
                                   int32_t CHW, void* stream) {
     DXMI_CHECK_ARG(g_loss && eps_pred && noise && d_eps, "dxmi_ddpm_loss_bwd: null pointer");
-    DDPM_CHECK_SHAPE("dxmi_ddpm_loss_bwd");
-    DXMI_CHECK_ARG(ddpm_aligned(eps_pred, noise, d_eps), "dxmi_ddpm_loss_bwd: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(ddpm_loss_bwd_kernel, ddpm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, eps_pred, noise, d_eps,
+    EW_CHECK_SHAPE("dxmi_ddpm_loss_bwd");
+    EW_CHECK_ALIGNED("dxmi_ddpm_loss_bwd", eps_pred, noise, d_eps);
+    hipLaunchKernelGGL(ddpm_loss_bwd_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_loss, eps_pred, noise, d_eps,
                        CHW);
     DXMI_CHECK_LAUNCH("dxmi_ddpm_loss_bwd");
     return DXMI_OK;

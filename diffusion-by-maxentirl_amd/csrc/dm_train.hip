@@ -12,12 +12,8 @@
 // per-sample sums in a fixed order (bitwise reproducible), no atomics.  The level is gathered from the device table of S entries
 // (cd_levels) by an int64 index; these launches need only t, so the index S - 1 is legal.  An index outside [0, S - 1] gives a NaN
 // level (nothing is read outside the table).
-#include "common.h"
-
-// one rounding per written operation: no fused multiply-add between them
-#pragma clang fp contract(off)
 #include "dsm_common.h"
-#include "dm_common.h"
+#include "ew_common.h"
 
 namespace {
 
@@ -36,8 +32,8 @@ __device__ __forceinline__ DsmScal dm_gen_scalings(float sg, float sd, float sd2
 __global__ __launch_bounds__(EW_BLOCK) void dm_gen_in_kernel(const float* __restrict__ z, float* __restrict__ x_in, float* __restrict__ t_out,
                                                              int CHW, float sg, float sd2) {
     const int b = blockIdx.y;
-    const float c_in = dm_c_in(sg, sd2);
-    if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dm_time(sg);
+    const float c_in = dsm_c_in(sg, sd2);
+    if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dsm_time(sg);
     const size_t base = (size_t)b * CHW;
     const int n4 = CHW / 4;
     for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
@@ -69,10 +65,10 @@ __global__ __launch_bounds__(EW_BLOCK) void dm_gen_x_kernel(const float* __restr
     const DsmScal c = dm_gen_scalings(sg, sd, sd2);
     float t = 0.f, cr = 0.f, cf = 0.f;
     if (PREP) {
-        t = dm_level(idx, tab, S, b);
-        cr = dm_c_in(t, sd2_real);
-        cf = dm_c_in(t, sd2_fake);
-        if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dm_time(t);
+        t = ew_level(idx, tab, S, b);
+        cr = dsm_c_in(t, sd2_real);
+        cf = dsm_c_in(t, sd2_fake);
+        if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dsm_time(t);
     }
     const size_t base = (size_t)b * CHW;
     const int n4 = CHW / 4;
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(EW_BLOCK) void dm_grad_fwd_reg_kernel(const float* 
                                                                    float smin_r, int dist_r, float sdf, float sdf2, float smin_f, int dist_f) {
     __shared__ float red[2][EW_BLOCK / 64];
     const int b = blockIdx.x;
-    const float t = dm_level(idx, tab, S, b);
+    const float t = ew_level(idx, tab, S, b);
     const DsmScal cr = dsm_scalings(t, sdr, sdr2, smin_r, dist_r, DXMI_DSM_W_UNIFORM, 0.f);
     const DsmScal cf = dsm_scalings(t, sdf, sdf2, smin_f, dist_f, DXMI_DSM_W_UNIFORM, 0.f);
     const size_t base = (size_t)b * CHW;
@@ -193,7 +189,7 @@ __global__ __launch_bounds__(EW_BLOCK) void dm_grad_fwd_2pass_kernel(const float
                                                                      float sdf, float sdf2, float smin_f, int dist_f) {
     __shared__ float red[2][EW_BLOCK / 64];
     const int b = blockIdx.x;
-    const float t = dm_level(idx, tab, S, b);
+    const float t = ew_level(idx, tab, S, b);
     const DsmScal cr = dsm_scalings(t, sdr, sdr2, smin_r, dist_r, DXMI_DSM_W_UNIFORM, 0.f);
     const DsmScal cf = dsm_scalings(t, sdf, sdf2, smin_f, dist_f, DXMI_DSM_W_UNIFORM, 0.f);
     const size_t base = (size_t)b * CHW;
@@ -286,11 +282,11 @@ float dm_host_c_out(float sg, float sd) {
 extern "C" int dxmi_dm_gen_in(const float* z, float* x_in, float* t_out, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
                               void* stream) {
     DXMI_CHECK_ARG(z && x_in && t_out, "dxmi_dm_gen_in: null pointer");
-    DM_CHECK_SHAPE("dxmi_dm_gen_in");
-    DM_CHECK_POS("dxmi_dm_gen_in", gen_sigma, "gen_sigma");
-    DM_CHECK_POS("dxmi_dm_gen_in", sigma_data, "sigma_data");
-    DXMI_CHECK_ARG(dm_aligned(z, x_in), "dxmi_dm_gen_in: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(dm_gen_in_kernel, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, z, x_in, t_out, CHW, gen_sigma,
+    EW_CHECK_SHAPE("dxmi_dm_gen_in");
+    EW_CHECK_POS("dxmi_dm_gen_in", gen_sigma, "gen_sigma");
+    EW_CHECK_POS("dxmi_dm_gen_in", sigma_data, "sigma_data");
+    EW_CHECK_ALIGNED("dxmi_dm_gen_in", z, x_in);
+    hipLaunchKernelGGL(dm_gen_in_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, z, x_in, t_out, CHW, gen_sigma,
                        sigma_data * sigma_data);
     DXMI_CHECK_LAUNCH("dxmi_dm_gen_in");
     return DXMI_OK;
@@ -299,12 +295,12 @@ extern "C" int dxmi_dm_gen_in(const float* z, float* x_in, float* t_out, int32_t
 extern "C" int dxmi_dm_gen_out(const float* f_gen, const float* z, float* x, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
                                int32_t clip, void* stream) {
     DXMI_CHECK_ARG(f_gen && z && x, "dxmi_dm_gen_out: null pointer");
-    DM_CHECK_SHAPE("dxmi_dm_gen_out");
-    DM_CHECK_POS("dxmi_dm_gen_out", gen_sigma, "gen_sigma");
-    DM_CHECK_POS("dxmi_dm_gen_out", sigma_data, "sigma_data");
-    DXMI_CHECK_ARG(dm_aligned(f_gen, z, x), "dxmi_dm_gen_out: tensors must be 16-byte aligned");
+    EW_CHECK_SHAPE("dxmi_dm_gen_out");
+    EW_CHECK_POS("dxmi_dm_gen_out", gen_sigma, "gen_sigma");
+    EW_CHECK_POS("dxmi_dm_gen_out", sigma_data, "sigma_data");
+    EW_CHECK_ALIGNED("dxmi_dm_gen_out", f_gen, z, x);
     const float sd2 = sigma_data * sigma_data;
-    hipLaunchKernelGGL(dm_gen_x_kernel<0>, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_gen, z, (const float*)nullptr,
+    hipLaunchKernelGGL(dm_gen_x_kernel<0>, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_gen, z, (const float*)nullptr,
                        (const int64_t*)nullptr, (const float*)nullptr, 0, x, (float*)nullptr, (float*)nullptr, (float*)nullptr,
                        (float*)nullptr, CHW, gen_sigma, sigma_data, sd2, 0.f, 0.f, (int)(clip != 0));
     DXMI_CHECK_LAUNCH("dxmi_dm_gen_out");
@@ -316,14 +312,14 @@ extern "C" int dxmi_dm_gen_prep(const float* f_gen, const float* z, const float*
                                 int32_t CHW, float gen_sigma, float gen_sigma_data, float real_sigma_data, float fake_sigma_data,
                                 void* stream) {
     DXMI_CHECK_ARG(f_gen && z && noise && indices && t_table && x && x_t && x_in_real && t_out, "dxmi_dm_gen_prep: null pointer");
-    DM_CHECK_SHAPE("dxmi_dm_gen_prep");
-    DM_CHECK_SCALES("dxmi_dm_gen_prep");
-    DM_CHECK_POS("dxmi_dm_gen_prep", gen_sigma, "gen_sigma");
-    DM_CHECK_POS("dxmi_dm_gen_prep", gen_sigma_data, "sigma_data");
-    DM_CHECK_POS("dxmi_dm_gen_prep", real_sigma_data, "sigma_data");
-    DM_CHECK_POS("dxmi_dm_gen_prep", fake_sigma_data, "sigma_data");
-    DXMI_CHECK_ARG(dm_aligned(f_gen, z, noise, x, x_t, x_in_real, x_in_fake), "dxmi_dm_gen_prep: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(dm_gen_x_kernel<1>, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_gen, z, noise, indices, t_table,
+    EW_CHECK_SHAPE("dxmi_dm_gen_prep");
+    EW_CHECK_SCALES("dxmi_dm_gen_prep");
+    EW_CHECK_POS("dxmi_dm_gen_prep", gen_sigma, "gen_sigma");
+    EW_CHECK_POS("dxmi_dm_gen_prep", gen_sigma_data, "sigma_data");
+    EW_CHECK_POS("dxmi_dm_gen_prep", real_sigma_data, "sigma_data");
+    EW_CHECK_POS("dxmi_dm_gen_prep", fake_sigma_data, "sigma_data");
+    EW_CHECK_ALIGNED("dxmi_dm_gen_prep", f_gen, z, noise, x, x_t, x_in_real, x_in_fake);
+    hipLaunchKernelGGL(dm_gen_x_kernel<1>, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_gen, z, noise, indices, t_table,
                        num_scales, x, x_t, x_in_real, t_out, x_in_fake, CHW, gen_sigma, gen_sigma_data, gen_sigma_data * gen_sigma_data,
                        real_sigma_data * real_sigma_data, fake_sigma_data * fake_sigma_data, 0);
     DXMI_CHECK_LAUNCH("dxmi_dm_gen_prep");
@@ -335,12 +331,12 @@ extern "C" int dxmi_dm_grad_fwd(const float* f_real, const float* f_fake, const 
                                 int32_t weighting, float real_sigma_data, float real_sigma_min, int32_t real_distillation,
                                 float fake_sigma_data, float fake_sigma_min, int32_t fake_distillation, void* stream) {
     DXMI_CHECK_ARG(f_real && f_fake && x && x_t && indices && t_table && g && loss && s, "dxmi_dm_grad_fwd: null pointer");
-    DM_CHECK_SHAPE("dxmi_dm_grad_fwd");
-    DM_CHECK_SCALES("dxmi_dm_grad_fwd");
+    EW_CHECK_SHAPE("dxmi_dm_grad_fwd");
+    EW_CHECK_SCALES("dxmi_dm_grad_fwd");
     DXMI_CHECK_ARG(weighting == DXMI_DM_W_DMD || weighting == DXMI_DM_W_NONE, "dxmi_dm_grad_fwd: unknown weighting %d", weighting);
-    DM_CHECK_POS("dxmi_dm_grad_fwd", real_sigma_data, "sigma_data");
-    DM_CHECK_POS("dxmi_dm_grad_fwd", fake_sigma_data, "sigma_data");
-    DXMI_CHECK_ARG(dm_aligned(f_real, f_fake, x, x_t, g), "dxmi_dm_grad_fwd: tensors must be 16-byte aligned");
+    EW_CHECK_POS("dxmi_dm_grad_fwd", real_sigma_data, "sigma_data");
+    EW_CHECK_POS("dxmi_dm_grad_fwd", fake_sigma_data, "sigma_data");
+    EW_CHECK_ALIGNED("dxmi_dm_grad_fwd", f_real, f_fake, x, x_t, g);
     const dim3 grid(N), block(EW_BLOCK);
     const float sdr2 = real_sigma_data * real_sigma_data, sdf2 = fake_sigma_data * fake_sigma_data;
     const int dr = (int)(real_distillation != 0), df = (int)(fake_distillation != 0);
@@ -363,11 +359,11 @@ extern "C" int dxmi_dm_grad_fwd(const float* f_real, const float* f_fake, const 
 extern "C" int dxmi_dm_gen_bwd(const float* upstream, const float* g, float* d_f_gen, int32_t N, int32_t CHW, float gen_sigma,
                                float sigma_data, void* stream) {
     DXMI_CHECK_ARG(upstream && g && d_f_gen, "dxmi_dm_gen_bwd: null pointer");
-    DM_CHECK_SHAPE("dxmi_dm_gen_bwd");
-    DM_CHECK_POS("dxmi_dm_gen_bwd", gen_sigma, "gen_sigma");
-    DM_CHECK_POS("dxmi_dm_gen_bwd", sigma_data, "sigma_data");
-    DXMI_CHECK_ARG(dm_aligned(g, d_f_gen), "dxmi_dm_gen_bwd: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(dm_gen_bwd_kernel, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, upstream, g, d_f_gen, CHW,
+    EW_CHECK_SHAPE("dxmi_dm_gen_bwd");
+    EW_CHECK_POS("dxmi_dm_gen_bwd", gen_sigma, "gen_sigma");
+    EW_CHECK_POS("dxmi_dm_gen_bwd", sigma_data, "sigma_data");
+    EW_CHECK_ALIGNED("dxmi_dm_gen_bwd", g, d_f_gen);
+    hipLaunchKernelGGL(dm_gen_bwd_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, upstream, g, d_f_gen, CHW,
                        dm_host_c_out(gen_sigma, sigma_data), (float)(1.0 / (double)CHW));
     DXMI_CHECK_LAUNCH("dxmi_dm_gen_bwd");
     return DXMI_OK;

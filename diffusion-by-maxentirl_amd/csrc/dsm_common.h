@@ -1,9 +1,10 @@
-// Scalings and loss weights shared by the DSM loss (edm_dsm.hip) and the consistency losses (cm_train.hip).
+// Karras scalings, loss weights, input scaling and time shared by the DSM loss (edm_dsm.hip) and the consistency, progressive and
+// distribution-matching launches (cm_train.hip, pd_train.hip, dm_train.hip, sid_train.hip).
 #pragma once
 #include "common.h"
 
 // the reference's fp32 operation order, one rounding per torch op: no fused multiply-add between them.  The pragma is at file
-// scope: it holds for the rest of every file that includes this header (both includers set it themselves, before the include).
+// scope: it holds for the rest of every file that includes this header.
 #pragma clang fp contract(off)
 
 namespace {
@@ -37,5 +38,9 @@ __device__ __forceinline__ DsmScal dsm_scalings(float s, float sd, float sd2, fl
     }
     return r;
 }
+
+// the network's input scaling and time at level s (denoise(), :348-349): c_in alone, and 1000 * 0.25 * th.log(sigmas + 1e-44)
+__device__ __forceinline__ float dsm_c_in(float s, float sd2) { return 1.f / __builtin_sqrtf(s * s + sd2); }
+__device__ __forceinline__ float dsm_time(float s) { return 250.f * logf(s + 1e-44f); }
 
 }  // namespace

@@ -6,24 +6,18 @@
 //   dxmi_ema_update        ema_k = rate_k ema_k + (1 - rate_k) src over many tensors and up to DXMI_EMA_MAX_RATES rates
 // x_t is never stored: the loss kernels recompute it with the prep kernel's operations.  All four are HBM-bound: 16 bytes per
 // lane, several loads in flight per wave; the per-sample sums are reduced in a fixed order (bitwise reproducible).
-#include "common.h"
-
-// the reference's fp32 operation order, one rounding per torch op: no fused multiply-add between them
-#pragma clang fp contract(off)
 #include "dsm_common.h"
+#include "ew_common.h"
 
 namespace {
-
-constexpr int EW_BLOCK = 256;
-constexpr int EW_UNROLL = 4;      // f32x4 per stream per lane in flight
 
 __global__ __launch_bounds__(EW_BLOCK) void dsm_prep_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
                                                             const float* __restrict__ sigma, float* __restrict__ x_in,
                                                             float* __restrict__ t_out, int CHW, float sd2) {
     const int b = blockIdx.y;
     const float s = sigma[b];
-    const float c_in = 1.f / __builtin_sqrtf(s * s + sd2);
-    if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = 250.f * logf(s + 1e-44f);      // 1000 * 0.25 * th.log(sigmas + 1e-44)
+    const float c_in = dsm_c_in(s, sd2);
+    if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = dsm_time(s);
     const size_t base = (size_t)b * CHW;
     const int n4 = CHW / 4;
     for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
@@ -32,8 +26,8 @@ __global__ __launch_bounds__(EW_BLOCK) void dsm_prep_kernel(const float* __restr
         for (int u = 0; u < EW_UNROLL; ++u) {
             const int i = i0 + u * EW_BLOCK;
             if (i < n4) {
-                xv[u] = *reinterpret_cast<const f32x4*>(x0 + base + (size_t)i * 4);
-                nv[u] = *reinterpret_cast<const f32x4*>(noise + base + (size_t)i * 4);
+                xv[u] = ld4(x0, base, i);
+                nv[u] = ld4(noise, base, i);
             }
         }
 #pragma unroll
@@ -46,13 +40,12 @@ __global__ __launch_bounds__(EW_BLOCK) void dsm_prep_kernel(const float* __restr
                 const float xt = xv[u][e] + nv[u][e] * s;     // x_t = x_start + noise * sigma (:91)
                 o[e] = c_in * xt;                             // c_in * x_t (:348-349)
             }
-            *reinterpret_cast<f32x4*>(x_in + base + (size_t)i * 4) = o;
+            st4(x_in, base, i, o);
         }
     }
 }
 
-// One workgroup per sample: each lane sums its elements in index order, then a fixed xor-shuffle tree per wave and a fixed
-// pairing of the four wave partials.
+// One workgroup per sample: each lane sums its elements in index order, then block_sum.
 __global__ __launch_bounds__(EW_BLOCK) void dsm_loss_fwd_kernel(const float* __restrict__ F, const float* __restrict__ x0,
                                                                 const float* __restrict__ noise, const float* __restrict__ sigma,
                                                                 float* __restrict__ xs_mse, float* __restrict__ mse, int CHW,
@@ -71,9 +64,9 @@ __global__ __launch_bounds__(EW_BLOCK) void dsm_loss_fwd_kernel(const float* __r
         for (int u = 0; u < EW_UNROLL; ++u) {
             const int i = i0 + u * EW_BLOCK;
             if (i < n4) {
-                fv[u] = *reinterpret_cast<const f32x4*>(F + base + (size_t)i * 4);
-                xv[u] = *reinterpret_cast<const f32x4*>(x0 + base + (size_t)i * 4);
-                nv[u] = *reinterpret_cast<const f32x4*>(noise + base + (size_t)i * 4);
+                fv[u] = ld4(F, base, i);
+                xv[u] = ld4(x0, base, i);
+                nv[u] = ld4(noise, base, i);
             }
         }
 #pragma unroll
@@ -91,17 +84,11 @@ __global__ __launch_bounds__(EW_BLOCK) void dsm_loss_fwd_kernel(const float* __r
             }
         }
     }
-    acc_xs = wave_sum(acc_xs);
-    acc_w = wave_sum(acc_w);
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = acc_xs;
-        red[1][threadIdx.x >> 6] = acc_w;
-    }
-    __syncthreads();
+    const float tot_xs = block_sum(acc_xs, red[0]), tot_w = block_sum(acc_w, red[1]);
     if (threadIdx.x == 0) {
         const float fD = (float)CHW;
-        xs_mse[b] = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / fD;       // mean_flat
-        mse[b] = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / fD;
+        xs_mse[b] = tot_xs / fD;       // mean_flat
+        mse[b] = tot_w / fD;
     }
 }
 
@@ -126,9 +113,9 @@ __global__ __launch_bounds__(EW_BLOCK) void dsm_loss_bwd_kernel(const float* __r
         for (int u = 0; u < EW_UNROLL; ++u) {
             const int i = i0 + u * EW_BLOCK;
             if (i < n4) {
-                fv[u] = *reinterpret_cast<const f32x4*>(F + base + (size_t)i * 4);
-                xv[u] = *reinterpret_cast<const f32x4*>(x0 + base + (size_t)i * 4);
-                nv[u] = *reinterpret_cast<const f32x4*>(noise + base + (size_t)i * 4);
+                fv[u] = ld4(F, base, i);
+                xv[u] = ld4(x0, base, i);
+                nv[u] = ld4(noise, base, i);
             }
         }
 #pragma unroll
@@ -146,7 +133,7 @@ __global__ __launch_bounds__(EW_BLOCK) void dsm_loss_bwd_kernel(const float* __r
                 else g = has_m ? ga * d2 : gb * d2;
                 o[e] = g * c.c_out;
             }
-            *reinterpret_cast<f32x4*>(dF + base + (size_t)i * 4) = o;
+            st4(dF, base, i, o);
         }
     }
 }
@@ -216,27 +203,14 @@ __global__ __launch_bounds__(EMA_BLOCK) void ema_kernel(EmaTable t, EmaRates r, 
     }
 }
 
-bool dsm_args_ok(const void* a, const void* b, const void* c, const void* d) {
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
-}
-
-dim3 dsm_grid(int N, int CHW) {
-    const int chunks = (CHW / 4 + EW_BLOCK * EW_UNROLL - 1) / (EW_BLOCK * EW_UNROLL);
-    return dim3(chunks < 64 ? chunks : 64, N);
-}
-
 }  // namespace
-
-#define DSM_CHECK_SHAPE(fn)                                                                                                      \
-    DXMI_CHECK_ARG(N > 0 && N <= 65535 && CHW > 0 && CHW % 4 == 0, fn ": N (%d) must be in [1, 65535] and CHW (%d) a positive "  \
-                   "multiple of 4", N, CHW)
 
 extern "C" int dxmi_edm_dsm_prep(const float* x_start, const float* noise, const float* sigma, float* x_in, float* t_out, int32_t N,
                                  int32_t CHW, float sigma_data, void* stream) {
     DXMI_CHECK_ARG(x_start && noise && sigma && x_in && t_out, "dxmi_edm_dsm_prep: null pointer");
-    DSM_CHECK_SHAPE("dxmi_edm_dsm_prep");
-    DXMI_CHECK_ARG(dsm_args_ok(x_start, noise, x_in, nullptr), "dxmi_edm_dsm_prep: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(dsm_prep_kernel, dsm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, x_start, noise, sigma, x_in, t_out,
+    EW_CHECK_SHAPE("dxmi_edm_dsm_prep");
+    EW_CHECK_ALIGNED("dxmi_edm_dsm_prep", x_start, noise, x_in);
+    hipLaunchKernelGGL(dsm_prep_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, x_start, noise, sigma, x_in, t_out,
                        CHW, sigma_data * sigma_data);
     DXMI_CHECK_LAUNCH("dxmi_edm_dsm_prep");
     return DXMI_OK;
@@ -246,10 +220,10 @@ extern "C" int dxmi_edm_dsm_loss_fwd(const float* model_out, const float* x_star
                                      float* xs_mse, float* mse, int32_t N, int32_t CHW, float sigma_data, float sigma_min,
                                      int32_t distillation, int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(model_out && x_start && noise && sigma && xs_mse && mse, "dxmi_edm_dsm_loss_fwd: null pointer");
-    DSM_CHECK_SHAPE("dxmi_edm_dsm_loss_fwd");
+    EW_CHECK_SHAPE("dxmi_edm_dsm_loss_fwd");
     DXMI_CHECK_ARG(weight_schedule >= DXMI_DSM_W_SNR && weight_schedule <= DXMI_DSM_W_UNIFORM,
                    "dxmi_edm_dsm_loss_fwd: unknown weight schedule %d", weight_schedule);
-    DXMI_CHECK_ARG(dsm_args_ok(model_out, x_start, noise, nullptr), "dxmi_edm_dsm_loss_fwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_edm_dsm_loss_fwd", model_out, x_start, noise);
     hipLaunchKernelGGL(dsm_loss_fwd_kernel, dim3(N), dim3(EW_BLOCK), 0, (hipStream_t)stream, model_out, x_start, noise, sigma, xs_mse,
                        mse, CHW, sigma_data, sigma_data * sigma_data, sigma_min, (int)(distillation != 0), weight_schedule,
                        (float)(1.0 / ((double)sigma_data * (double)sigma_data)));
@@ -262,11 +236,11 @@ extern "C" int dxmi_edm_dsm_loss_bwd(const float* g_mse, const float* g_xs, cons
                                      float sigma_data, float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(model_out && x_start && noise && sigma && d_model_out, "dxmi_edm_dsm_loss_bwd: null pointer");
     DXMI_CHECK_ARG(g_mse || g_xs, "dxmi_edm_dsm_loss_bwd: no upstream gradient (g_mse and g_xs both null)");
-    DSM_CHECK_SHAPE("dxmi_edm_dsm_loss_bwd");
+    EW_CHECK_SHAPE("dxmi_edm_dsm_loss_bwd");
     DXMI_CHECK_ARG(weight_schedule >= DXMI_DSM_W_SNR && weight_schedule <= DXMI_DSM_W_UNIFORM,
                    "dxmi_edm_dsm_loss_bwd: unknown weight schedule %d", weight_schedule);
-    DXMI_CHECK_ARG(dsm_args_ok(model_out, x_start, noise, d_model_out), "dxmi_edm_dsm_loss_bwd: tensors must be 16-byte aligned");
-    hipLaunchKernelGGL(dsm_loss_bwd_kernel, dsm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_mse, g_xs, model_out, x_start,
+    EW_CHECK_ALIGNED("dxmi_edm_dsm_loss_bwd", model_out, x_start, noise, d_model_out);
+    hipLaunchKernelGGL(dsm_loss_bwd_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, g_mse, g_xs, model_out, x_start,
                        noise, sigma, d_model_out, CHW, sigma_data, sigma_data * sigma_data, sigma_min, (int)(distillation != 0),
                        weight_schedule, (float)(1.0 / ((double)sigma_data * (double)sigma_data)), (float)(1.0 / (double)CHW));
     DXMI_CHECK_LAUNCH("dxmi_edm_dsm_loss_bwd");

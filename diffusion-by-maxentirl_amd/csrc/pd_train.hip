@@ -12,16 +12,10 @@
 // order (bitwise reproducible).  The levels are gathered from one device table of 2 S + 1 entries by index: t = tab[i], t3 = tab[i + 1]
 // (the coarse ladder, S + 1 levels) and t2 = tab[S + 1 + i] (the half steps, S levels).  An index outside [0, S - 1] gives NaN levels
 // (nothing is read outside the table).
-#include "common.h"
-
-// the reference's fp32 operation order, one rounding per torch op: no fused multiply-add between them
-#pragma clang fp contract(off)
 #include "dsm_common.h"
+#include "ew_common.h"
 
 namespace {
-
-constexpr int EW_BLOCK = 256;
-constexpr int EW_UNROLL = 4;      // f32x4 per stream per lane in flight
 
 struct Levels {
     float t, t2, t3;
@@ -36,12 +30,6 @@ __device__ __forceinline__ Levels pd_levels(const int64_t* __restrict__ idx, con
     r.t2 = ok ? tab[(int64_t)S + 1 + i] : __builtin_nanf("");
     return r;
 }
-
-__device__ __forceinline__ float pd_c_in(float s, float sd2) { return 1.f / __builtin_sqrtf(s * s + sd2); }
-__device__ __forceinline__ float pd_time(float s) { return 250.f * logf(s + 1e-44f); }      // 1000 * 0.25 * th.log(sigmas + 1e-44)
-
-__device__ __forceinline__ f32x4 ld4(const float* p, size_t base, int i) { return *reinterpret_cast<const f32x4*>(p + base + (size_t)i * 4); }
-__device__ __forceinline__ void st4(float* p, size_t base, int i, f32x4 v) { *reinterpret_cast<f32x4*>(p + base + (size_t)i * 4) = v; }
 
 // euler_solver (:267-274) twice and euler_to_denoiser (:276-281).  `sd`, `sigma_min`, `distill`: the scalings of the diffusion
 // whose denoise() forms the denoiser (the teacher's); sd2_next: sigma_data^2 of the diffusion whose network reads x_in_next.
@@ -58,8 +46,8 @@ __global__ __launch_bounds__(EW_BLOCK) void pd_solver_kernel(const float* __rest
     const float dt = MODE == DXMI_PD_MID ? t2 - t : t3 - t2;                       // next_t - t (:272)
     const float dt3 = t3 - t;                                                      // next_t - t of euler_to_denoiser (:279)
     const DsmScal c = dsm_scalings(s_eval, sd, sd2, sigma_min, distill, DXMI_DSM_W_UNIFORM, 0.f);
-    const float c_in_next = pd_c_in(t2, sd2_next);
-    if (MODE == DXMI_PD_MID && blockIdx.x == 0 && threadIdx.x == 0) t_next[b] = pd_time(t2);
+    const float c_in_next = dsm_c_in(t2, sd2_next);
+    if (MODE == DXMI_PD_MID && blockIdx.x == 0 && threadIdx.x == 0) t_next[b] = dsm_time(t2);
     const size_t base = (size_t)b * CHW;
     const int n4 = CHW / 4;
     for (int i0 = blockIdx.x * EW_BLOCK * EW_UNROLL + threadIdx.x; i0 < n4; i0 += gridDim.x * EW_BLOCK * EW_UNROLL) {
@@ -96,14 +84,6 @@ __global__ __launch_bounds__(EW_BLOCK) void pd_solver_kernel(const float* __rest
             if (MODE == DXMI_PD_MID) st4(x_in_next, base, i, on);
         }
     }
-}
-
-// fixed order: a lane's running sum in index order, the xor-shuffle tree of a wave, a fixed pairing of the four wave partials
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // l1 / l2 against the stored target; one workgroup per image
@@ -212,21 +192,11 @@ __global__ __launch_bounds__(EW_BLOCK) void pd_lpips_images_kernel(const float* 
     }
 }
 
-bool pd_aligned(const void* a, const void* b, const void* c, const void* d, const void* e = nullptr) {
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e)) & 15) == 0;
-}
-
-dim3 pd_grid(int N, int CHW) {
-    const int chunks = (CHW / 4 + EW_BLOCK * EW_UNROLL - 1) / (EW_BLOCK * EW_UNROLL);
-    return dim3(chunks < 64 ? chunks : 64, N);
-}
-
 }  // namespace
 
-#define PD_CHECK_SHAPE(fn)                                                                                                       \
-    DXMI_CHECK_ARG(N > 0 && N <= 65535 && CHW > 0 && CHW % 4 == 0 && CHW < (1 << 30), fn ": N (%d) must be in [1, 65535] and "   \
-                   "CHW (%d) a positive multiple of 4 below 2^30", N, CHW);                                                      \
-    DXMI_CHECK_ARG(num_scales >= 1 && num_scales < (1 << 30), fn ": num_scales (%d) must be in [1, 2^30)", num_scales)
+#define PD_CHECK_SHAPE(fn) \
+    EW_CHECK_SHAPE(fn);    \
+    EW_CHECK_SCALES(fn)
 
 #define PD_CHECK_LOSS(fn)                                                                                                        \
     PD_CHECK_SHAPE(fn);                                                                                                          \
@@ -244,8 +214,8 @@ extern "C" int dxmi_pd_solver(int32_t mode, const float* x_t, const float* x_t2_
     if (mode == DXMI_PD_MID) DXMI_CHECK_ARG(x_in_next && t_next, "dxmi_pd_solver: MID needs x_in_next and t_next");
     if (mode == DXMI_PD_END) DXMI_CHECK_ARG(x_t2_in, "dxmi_pd_solver: END needs x_t2");
     PD_CHECK_SHAPE("dxmi_pd_solver");
-    DXMI_CHECK_ARG(pd_aligned(x_t, x_t2_in, model_out, out, x_in_next), "dxmi_pd_solver: tensors must be 16-byte aligned");
-    const dim3 grid = pd_grid(N, CHW), block(EW_BLOCK);
+    EW_CHECK_ALIGNED("dxmi_pd_solver", x_t, x_t2_in, model_out, out, x_in_next);
+    const dim3 grid = ew_grid(N, CHW), block(EW_BLOCK);
     const float sd = solver_sigma_data, sd2 = sd * sd, sd2n = next_sigma_data * next_sigma_data;
     const int dist = (int)(solver_distillation != 0);
     if (mode == DXMI_PD_MID)
@@ -263,7 +233,7 @@ extern "C" int dxmi_pd_loss_fwd(const float* f_online, const float* x_t, const f
                                 float sigma_data, float sigma_min, int32_t distillation, int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(f_online && x_t && target_x && indices && t_table && loss, "dxmi_pd_loss_fwd: null pointer");
     PD_CHECK_LOSS("dxmi_pd_loss_fwd");
-    DXMI_CHECK_ARG(pd_aligned(f_online, x_t, target_x, nullptr), "dxmi_pd_loss_fwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_pd_loss_fwd", f_online, x_t, target_x);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
     const int dist = (int)(distillation != 0);
     const dim3 grid(N), block(EW_BLOCK);
@@ -283,10 +253,10 @@ extern "C" int dxmi_pd_loss_bwd(const float* g_loss, const float* f_online, cons
                                 int32_t weight_schedule, void* stream) {
     DXMI_CHECK_ARG(g_loss && f_online && x_t && target_x && indices && t_table && d_f_online, "dxmi_pd_loss_bwd: null pointer");
     PD_CHECK_LOSS("dxmi_pd_loss_bwd");
-    DXMI_CHECK_ARG(pd_aligned(f_online, x_t, target_x, d_f_online), "dxmi_pd_loss_bwd: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_pd_loss_bwd", f_online, x_t, target_x, d_f_online);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
     const int dist = (int)(distillation != 0);
-    const dim3 grid = pd_grid(N, CHW), block(EW_BLOCK);
+    const dim3 grid = ew_grid(N, CHW), block(EW_BLOCK);
     if (loss_norm == DXMI_CD_NORM_L1)
         hipLaunchKernelGGL(pd_loss_bwd_kernel<DXMI_CD_NORM_L1>, grid, block, 0, (hipStream_t)stream, g_loss, f_online, x_t, target_x, indices,
                            t_table, num_scales, d_f_online, CHW, sigma_data, sd2, sigma_min, dist, weight_schedule, inv_sd2,
@@ -306,9 +276,9 @@ extern "C" int dxmi_pd_lpips_images(const float* f_online, const float* x_t, con
     PD_CHECK_SHAPE("dxmi_pd_lpips_images");
     DXMI_CHECK_ARG(weight_schedule >= DXMI_DSM_W_SNR && weight_schedule <= DXMI_DSM_W_UNIFORM,
                    "dxmi_pd_lpips_images: unknown weight schedule %d", weight_schedule);
-    DXMI_CHECK_ARG(pd_aligned(f_online, x_t, target_x, x01), "dxmi_pd_lpips_images: tensors must be 16-byte aligned");
+    EW_CHECK_ALIGNED("dxmi_pd_lpips_images", f_online, x_t, target_x, x01);
     const float sd2 = sigma_data * sigma_data, inv_sd2 = (float)(1.0 / ((double)sigma_data * (double)sigma_data));
-    hipLaunchKernelGGL(pd_lpips_images_kernel, pd_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_online, x_t, target_x, indices,
+    hipLaunchKernelGGL(pd_lpips_images_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_online, x_t, target_x, indices,
                        t_table, num_scales, x01, weights, N, CHW, sigma_data, sd2, sigma_min, (int)(distillation != 0), weight_schedule,
                        inv_sd2);
     DXMI_CHECK_LAUNCH("dxmi_pd_lpips_images");

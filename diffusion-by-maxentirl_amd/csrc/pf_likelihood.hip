@@ -21,6 +21,7 @@
 //             bpd = logp K[BPD_SCALE] + 7.
 // CORRECT moves 32 bytes per element with a given probe (reads x, k1, F, g, e; writes x, x_in), 28 with the probe made here.
 #include "stage_common.h"
+#include "ew_common.h"
 
 namespace {
 
@@ -29,13 +30,6 @@ constexpr int PL_UNROLL = 2;      // f32x4 per stream per lane in flight: five s
 struct PlCoef {
     float ka, kb, db, h, hh, c_next;
 };
-
-__device__ __forceinline__ float pl_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __device__ __forceinline__ float pl_sign(float z) { return z >= 0.f ? 1.f : -1.f; }
 
@@ -192,12 +186,12 @@ __global__ __launch_bounds__(STAGE_BLOCK) void pf_ll_stage_kernel(const float* _
             if (feed) x_in[o] = k.c_next * xn;
         }
     }
-    const float d = pl_block_sum(acc, red[0]);
+    const float d = block_sum(acc, red[0]);
     if (!CORRECT) {
         if (threadIdx.x == 0) div1[n] = d;
         return;
     }
-    const float q = pl_block_sum(acc2, red[1]);      // every lane takes part (last is uniform; acc2 is 0 where it is not set)
+    const float q = block_sum(acc2, red[1]);      // every lane takes part (last is uniform; acc2 is 0 where it is not set)
     if (threadIdx.x == 0) {
         const float ds = div1[n] + d;
         const float dl = k.hh * ds;

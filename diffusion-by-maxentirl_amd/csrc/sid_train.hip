@@ -19,12 +19,8 @@
 // per image in dxmi_sid_grad_fwd, per-sample sums in a fixed order (bitwise reproducible), no atomics.  An index outside
 // [0, S - 1] gives a NaN level (nothing is read outside the table).  s == 0 gives loss = 0 and g = 0 (SiD's code clips the
 // normaliser at 1e-5 instead).
-#include "common.h"
-
-// one rounding per written operation: no fused multiply-add between them
-#pragma clang fp contract(off)
 #include "dsm_common.h"
-#include "dm_common.h"
+#include "ew_common.h"
 
 namespace {
 
@@ -38,7 +34,7 @@ __global__ __launch_bounds__(EW_BLOCK) void sid_grad_fwd_kernel(const float* __r
                                                                 float smin_f, int dist_f) {
     __shared__ float red[3][EW_BLOCK / 64];
     const int b = blockIdx.x;
-    const float t = dm_level(idx, tab, S, b);
+    const float t = ew_level(idx, tab, S, b);
     const DsmScal cr = dsm_scalings(t, sdr, sdr2, smin_r, dist_r, DXMI_DSM_W_UNIFORM, 0.f);
     const DsmScal cf = dsm_scalings(t, sdf, sdf2, smin_f, dist_f, DXMI_DSM_W_UNIFORM, 0.f);
     const size_t base = (size_t)b * CHW;
@@ -96,8 +92,8 @@ __global__ __launch_bounds__(EW_BLOCK) void sid_join_kernel(const float* d_dir, 
                                                             const int64_t* __restrict__ idx, const float* __restrict__ tab, int S,
                                                             float* g, int CHW, float sdr2, float sdf2) {
     const int b = blockIdx.y;
-    const float t = dm_level(idx, tab, S, b);
-    const float ci_r = dm_c_in(t, sdr2), ci_f = dm_c_in(t, sdf2);
+    const float t = ew_level(idx, tab, S, b);
+    const float ci_r = dsm_c_in(t, sdr2), ci_f = dsm_c_in(t, sdf2);
     const float s = s_in[b];
     const size_t base = (size_t)b * CHW;
     const int n4 = CHW / 4;
@@ -133,12 +129,12 @@ extern "C" int dxmi_sid_grad_fwd(const float* f_real, const float* f_fake, const
                                  void* stream) {
     DXMI_CHECK_ARG(f_real && f_fake && x && x_t && indices && t_table && v_real && v_fake && d_dir && loss && s,
                    "dxmi_sid_grad_fwd: null pointer");
-    DM_CHECK_SHAPE("dxmi_sid_grad_fwd");
-    DM_CHECK_SCALES("dxmi_sid_grad_fwd");
+    EW_CHECK_SHAPE("dxmi_sid_grad_fwd");
+    EW_CHECK_SCALES("dxmi_sid_grad_fwd");
     DXMI_CHECK_ARG(alpha >= -3.0e38f && alpha <= 3.0e38f, "dxmi_sid_grad_fwd: alpha (%g) must be finite", (double)alpha);
-    DM_CHECK_POS("dxmi_sid_grad_fwd", real_sigma_data, "sigma_data");
-    DM_CHECK_POS("dxmi_sid_grad_fwd", fake_sigma_data, "sigma_data");
-    DXMI_CHECK_ARG(dm_aligned(f_real, f_fake, x, x_t, v_real, v_fake, d_dir), "dxmi_sid_grad_fwd: tensors must be 16-byte aligned");
+    EW_CHECK_POS("dxmi_sid_grad_fwd", real_sigma_data, "sigma_data");
+    EW_CHECK_POS("dxmi_sid_grad_fwd", fake_sigma_data, "sigma_data");
+    EW_CHECK_ALIGNED("dxmi_sid_grad_fwd", f_real, f_fake, x, x_t, v_real, v_fake, d_dir);
     const float oma = 1.f - alpha;
     hipLaunchKernelGGL(sid_grad_fwd_kernel, dim3(N), dim3(EW_BLOCK), 0, (hipStream_t)stream, f_real, f_fake, x, x_t, indices, t_table,
                        num_scales, v_real, v_fake, d_dir, loss, s, CHW, oma, 2.f * oma, 2.f * alpha - 1.f, real_sigma_data,
@@ -152,13 +148,13 @@ extern "C" int dxmi_sid_join(const float* d_dir, const float* g_real, const floa
                              const float* t_table, int32_t num_scales, float* g, int32_t N, int32_t CHW, float real_sigma_data,
                              float fake_sigma_data, void* stream) {
     DXMI_CHECK_ARG(d_dir && g_real && g_fake && s && indices && t_table && g, "dxmi_sid_join: null pointer");
-    DM_CHECK_SHAPE("dxmi_sid_join");
-    DM_CHECK_SCALES("dxmi_sid_join");
-    DM_CHECK_POS("dxmi_sid_join", real_sigma_data, "sigma_data");
-    DM_CHECK_POS("dxmi_sid_join", fake_sigma_data, "sigma_data");
-    DXMI_CHECK_ARG(dm_aligned(d_dir, g_real, g_fake, g), "dxmi_sid_join: tensors must be 16-byte aligned");
+    EW_CHECK_SHAPE("dxmi_sid_join");
+    EW_CHECK_SCALES("dxmi_sid_join");
+    EW_CHECK_POS("dxmi_sid_join", real_sigma_data, "sigma_data");
+    EW_CHECK_POS("dxmi_sid_join", fake_sigma_data, "sigma_data");
+    EW_CHECK_ALIGNED("dxmi_sid_join", d_dir, g_real, g_fake, g);
     DXMI_CHECK_ARG(g != g_real && g != g_fake, "dxmi_sid_join: g may alias d_dir only");
-    hipLaunchKernelGGL(sid_join_kernel, dm_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, d_dir, g_real, g_fake, s, indices,
+    hipLaunchKernelGGL(sid_join_kernel, ew_grid(N, CHW), dim3(EW_BLOCK), 0, (hipStream_t)stream, d_dir, g_real, g_fake, s, indices,
                        t_table, num_scales, g, CHW, real_sigma_data * real_sigma_data, fake_sigma_data * fake_sigma_data);
     DXMI_CHECK_LAUNCH("dxmi_sid_join");
     return DXMI_OK;

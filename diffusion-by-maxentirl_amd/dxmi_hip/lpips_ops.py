@@ -149,10 +149,10 @@ def relu_mask_acc(ga, gb, act):
 
 
 def _cd_lpips_operands(what, first, indices, t_table, same, per_sample=()):
-    from .ops import _cd_operands
+    from .ops import _batch_operands
     if first is None or first.dim() != 4:
         _err(f"{what}: [N, C, H, W] tensors are needed")
-    N, CHW, S = _cd_operands(what, first, indices, t_table, same=same, per_sample=per_sample)
+    N, CHW, S = _batch_operands(what, first, same, per_sample, indices=indices, t_table=t_table)
     if CHW % 4:
         _err(f"{what}: C H W ({CHW}) must be a multiple of 4")
     return N, CHW, S

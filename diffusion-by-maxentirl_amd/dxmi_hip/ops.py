@@ -921,23 +921,41 @@ def edm_step(x, model_out, z, sigma, sigma_down, sigma_up, sigma_data=0.5, outs=
 DSM_WEIGHT_SCHEDULES = {"snr": 0, "snr+1": 1, "karras": 2, "truncated-snr": 3, "uniform": 4}
 
 
-def _dsm_operands(x_start, sigma, same=(), per_sample=()):
-    """fp32 contiguous 16-byte aligned device tensors; `same` must have x_start's shape, sigma and `per_sample` N elements (the
-    kernels read N x CHW elements of every image-sized operand and N of every per-sample one)."""
-    ts = (x_start, sigma) + tuple(same) + tuple(per_sample)
-    _need_cuda(*ts)
-    for t in ts:
+_NO_LEVELS = object()
+
+
+def _batch_operands(what, first, same=(), per_sample=(), *, indices=_NO_LEVELS, t_table=_NO_LEVELS, chw4=False):
+    """The operand check of the elementwise training launches (csrc/ew_common.h).  `first` and `same`: fp32 contiguous 16-byte
+    aligned device tensors of one shape [N, ...] (the kernels read N x CHW elements of each); `per_sample`: the same with N
+    elements; a None among `same` / `per_sample` is an absent optional operand.  A launch that gathers levels names `indices`
+    (int64 [N]) and `t_table` (fp32 [L >= 2]).  chw4: refuse here, not in the library, a CHW that is no multiple of 4.
+    -> (N, CHW, L), L = 0 without a table."""
+    levels = t_table is not _NO_LEVELS
+    ts = (first,) + tuple(same) + tuple(per_sample)
+    _need_cuda(*((indices, t_table) if levels else ()), *ts)
+    for t in ts + ((t_table,) if levels else ()):
         if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
-            raise _lib.DxmiError("dxmi_edm_dsm_*: fp32 contiguous 16-byte aligned device tensors")
-    if x_start.dim() < 2 or x_start.numel() == 0:
-        raise _lib.DxmiError(f"dxmi_edm_dsm_*: x_start must be a non-empty batch [N, ...], got {tuple(x_start.shape)}")
-    N = x_start.shape[0]
+            raise _lib.DxmiError(f"{what}: fp32 contiguous 16-byte aligned device tensors")
+    if first.dim() < 2 or first.numel() == 0:
+        raise _lib.DxmiError(f"{what}: a non-empty batch [N, ...] is needed, got {tuple(first.shape)}")
+    N = first.shape[0]
     for t in same:
-        if t is not None and t.shape != x_start.shape:
-            raise _lib.DxmiError(f"dxmi_edm_dsm_*: operand of shape {tuple(t.shape)} where x_start's {tuple(x_start.shape)} is needed")
-    for t in (sigma,) + tuple(per_sample):
+        if t is not None and t.shape != first.shape:
+            raise _lib.DxmiError(f"{what}: operand of shape {tuple(t.shape)} where {tuple(first.shape)} is needed")
+    for t in per_sample:
         if t is not None and t.numel() != N:
-            raise _lib.DxmiError(f"dxmi_edm_dsm_*: per-sample operand of {t.numel()} elements for a batch of {N}")
+            raise _lib.DxmiError(f"{what}: per-sample operand of {t.numel()} elements for a batch of {N}")
+    if levels:
+        if indices.dtype != torch.int64 or not indices.is_contiguous() or indices.numel() != N:
+            raise _lib.DxmiError(f"{what}: indices must be {N} contiguous int64 values")
+        if t_table.dim() != 1 or t_table.numel() < 2:
+            raise _lib.DxmiError(f"{what}: t_table must hold num_scales >= 2 levels, got {tuple(t_table.shape)}")
+    if any(t is not None and t.device != first.device for t in ts + ((indices, t_table) if levels else ())):
+        raise _lib.DxmiError(f"{what}: operands on different devices")
+    CHW = first.numel() // N
+    if chw4 and CHW % 4:
+        raise _lib.DxmiError(f"{what}: the elements per sample ({CHW}) must be a multiple of 4")
+    return N, CHW, t_table.numel() if levels else 0
 
 
 def _dsm_schedule(weight_schedule):
@@ -948,23 +966,21 @@ def _dsm_schedule(weight_schedule):
 
 def edm_dsm_prep(x_start, noise, sigma, sigma_data=0.5, out=None):
     """-> (x_in = c_in(sigma) (x_start + noise sigma), t = 250 ln(sigma + 1e-44)) of the DSM loss (dxmi_edm_dsm_prep)."""
-    _dsm_operands(x_start, sigma, same=(noise, out))
-    N = x_start.shape[0]
+    N, CHW, _ = _batch_operands("dxmi_edm_dsm_prep", x_start, same=(noise, out), per_sample=(sigma,))
     x_in = torch.empty_like(x_start) if out is None else out
     t = torch.empty(N, dtype=torch.float32, device=x_start.device)
-    check(load().dxmi_edm_dsm_prep(_ptr(x_start), _ptr(noise), _ptr(sigma), _ptr(x_in), _ptr(t), N, x_start.numel() // N,
+    check(load().dxmi_edm_dsm_prep(_ptr(x_start), _ptr(noise), _ptr(sigma), _ptr(x_in), _ptr(t), N, CHW,
                                    float(sigma_data), _stream()), "dxmi_edm_dsm_prep")
     return x_in, t
 
 
 def edm_dsm_loss_fwd(model_out, x_start, noise, sigma, weight_schedule, sigma_data=0.5, sigma_min=0.002, distillation=False):
     """-> per-sample (xs_mse, mse) of the DSM loss (dxmi_edm_dsm_loss_fwd)."""
-    _dsm_operands(x_start, sigma, same=(model_out, noise))
-    N = x_start.shape[0]
+    N, CHW, _ = _batch_operands("dxmi_edm_dsm_loss_fwd", x_start, same=(model_out, noise), per_sample=(sigma,))
     xs = torch.empty(N, dtype=torch.float32, device=x_start.device)
     mse = torch.empty_like(xs)
     check(load().dxmi_edm_dsm_loss_fwd(_ptr(model_out), _ptr(x_start), _ptr(noise), _ptr(sigma), _ptr(xs), _ptr(mse), N,
-                                       x_start.numel() // N, float(sigma_data), float(sigma_min), int(bool(distillation)),
+                                       CHW, float(sigma_data), float(sigma_min), int(bool(distillation)),
                                        _dsm_schedule(weight_schedule), _stream()), "dxmi_edm_dsm_loss_fwd")
     return xs, mse
 
@@ -972,34 +988,19 @@ def edm_dsm_loss_fwd(model_out, x_start, noise, sigma, weight_schedule, sigma_da
 def edm_dsm_loss_bwd(g_mse, g_xs, model_out, x_start, noise, sigma, weight_schedule, sigma_data=0.5, sigma_min=0.002,
                      distillation=False, out=None):
     """-> d(model_out) of the DSM terms for the device upstream gradients g_mse / g_xs [N] (either may be None)."""
-    _dsm_operands(x_start, sigma, same=(model_out, noise, out), per_sample=(g_mse, g_xs))
-    N = x_start.shape[0]
+    N, CHW, _ = _batch_operands("dxmi_edm_dsm_loss_bwd", x_start, same=(model_out, noise, out), per_sample=(sigma, g_mse, g_xs))
     d = torch.empty_like(model_out) if out is None else out
     check(load().dxmi_edm_dsm_loss_bwd(_ptr(g_mse), _ptr(g_xs), _ptr(model_out), _ptr(x_start), _ptr(noise), _ptr(sigma), _ptr(d), N,
-                                       x_start.numel() // N, float(sigma_data), float(sigma_min), int(bool(distillation)),
+                                       CHW, float(sigma_data), float(sigma_min), int(bool(distillation)),
                                        _dsm_schedule(weight_schedule), _stream()), "dxmi_edm_dsm_loss_bwd")
     return d
 
 
-def _ddpm_operands(name, ref, same=(), per_sample=()):
-    """fp32 contiguous 16-byte aligned device tensors of ref's shape [N, ...]; `per_sample` hold N elements."""
-    ts = (ref,) + tuple(same) + tuple(per_sample)
-    _need_cuda(*ts)
-    for t in (ref,) + tuple(same):
-        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
-            raise _lib.DxmiError(f"{name}: fp32 contiguous 16-byte aligned device tensors")
-    if ref.dim() < 2 or ref.numel() == 0:
-        raise _lib.DxmiError(f"{name}: a non-empty batch [N, ...] is needed, got {tuple(ref.shape)}")
-    N = ref.shape[0]
-    if (ref.numel() // N) % 4:
-        raise _lib.DxmiError(f"{name}: {ref.numel() // N} elements per sample are not a multiple of 4")
-    for t in same:
-        if t is not None and t.shape != ref.shape:
-            raise _lib.DxmiError(f"{name}: operand of shape {tuple(t.shape)} where {tuple(ref.shape)} is needed")
-    for t in per_sample:
-        if not (t.is_contiguous() and t.numel() == N):
-            raise _lib.DxmiError(f"{name}: per-sample operand of {t.numel()} elements (contiguous) for a batch of {N}")
-    return N, ref.numel() // N
+def _ddpm_per_sample(name, t, N):
+    """t_idx (int64) and g_loss of the DDPM launches: a device tensor of N contiguous elements, its dtype the caller's to check."""
+    _need_cuda(t)
+    if not (t.is_contiguous() and t.numel() == N):
+        raise _lib.DxmiError(f"{name}: per-sample operand of {t.numel()} elements (contiguous) for a batch of {N}")
 
 
 def ddpm_prep(x_start, noise, t_idx, table, out=None):
@@ -1007,7 +1008,8 @@ def ddpm_prep(x_start, noise, t_idx, table, out=None):
     input (dxmi_ddpm_prep).  table: fp32 [2, T] on the device; t_idx: int64 [N] on the device."""
     name = "dxmi_ddpm_prep"
     _need_cuda(table)
-    N, chw = _ddpm_operands(name, x_start, same=(noise, out), per_sample=(t_idx,))
+    N, chw, _ = _batch_operands(name, x_start, same=(noise, out), chw4=True)
+    _ddpm_per_sample(name, t_idx, N)
     if t_idx.dtype != torch.int64:
         raise _lib.DxmiError(f"{name}: t_idx must be int64, got {t_idx.dtype}")
     if not (table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[0] == 2 and table.shape[1] >= 1):
@@ -1021,7 +1023,7 @@ def ddpm_prep(x_start, noise, t_idx, table, out=None):
 
 def ddpm_loss_fwd(eps_pred, noise):
     """-> per-sample mean_flat((eps_pred - noise)^2) of the noise-prediction loss (dxmi_ddpm_loss_fwd)."""
-    N, chw = _ddpm_operands("dxmi_ddpm_loss_fwd", eps_pred, same=(noise,))
+    N, chw, _ = _batch_operands("dxmi_ddpm_loss_fwd", eps_pred, same=(noise,), chw4=True)
     loss = torch.empty(N, dtype=torch.float32, device=eps_pred.device)
     check(load().dxmi_ddpm_loss_fwd(_ptr(eps_pred), _ptr(noise), _ptr(loss), N, chw, _stream()), "dxmi_ddpm_loss_fwd")
     return loss
@@ -1030,7 +1032,8 @@ def ddpm_loss_fwd(eps_pred, noise):
 def ddpm_loss_bwd(g_loss, eps_pred, noise, out=None):
     """-> d(eps_pred) of the noise-prediction loss for the device upstream gradient g_loss [N] (dxmi_ddpm_loss_bwd)."""
     name = "dxmi_ddpm_loss_bwd"
-    N, chw = _ddpm_operands(name, eps_pred, same=(noise, out), per_sample=(g_loss,))
+    N, chw, _ = _batch_operands(name, eps_pred, same=(noise, out), chw4=True)
+    _ddpm_per_sample(name, g_loss, N)
     if g_loss.dtype != torch.float32:
         raise _lib.DxmiError(f"{name}: g_loss must be fp32, got {g_loss.dtype}")
     d = torch.empty_like(eps_pred) if out is None else out
@@ -1043,36 +1046,10 @@ CD_EULER_X0, CD_HEUN_PRED, CD_HEUN_CORR = range(3)
 CD_LOSS_NORMS = {"l1": 0, "l2": 1, "l2-32": 2}
 
 
-def _cd_operands(what, x_start, indices, t_table, same=(), per_sample=()):
-    """The checks of _dsm_operands for the consistency launches: image-sized operands fp32 contiguous 16-byte aligned of one
-    shape, `indices` int64 [N] and `t_table` fp32 [num_scales >= 2] on the same device, per-sample operands of N elements."""
-    ts = (x_start,) + tuple(same) + tuple(per_sample)
-    _need_cuda(indices, t_table, *ts)
-    for t in ts + (t_table,):
-        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
-            raise _lib.DxmiError(f"{what}: fp32 contiguous 16-byte aligned device tensors")
-    if x_start.dim() < 2 or x_start.numel() == 0:
-        raise _lib.DxmiError(f"{what}: a non-empty batch [N, ...] is needed, got {tuple(x_start.shape)}")
-    N = x_start.shape[0]
-    for t in same:
-        if t is not None and t.shape != x_start.shape:
-            raise _lib.DxmiError(f"{what}: operand of shape {tuple(t.shape)} where {tuple(x_start.shape)} is needed")
-    for t in per_sample:
-        if t is not None and t.numel() != N:
-            raise _lib.DxmiError(f"{what}: per-sample operand of {t.numel()} elements for a batch of {N}")
-    if indices.dtype != torch.int64 or not indices.is_contiguous() or indices.numel() != N:
-        raise _lib.DxmiError(f"{what}: indices must be {N} contiguous int64 values")
-    if t_table.dim() != 1 or t_table.numel() < 2:
-        raise _lib.DxmiError(f"{what}: t_table must hold num_scales >= 2 levels, got {tuple(t_table.shape)}")
-    if any(t is not None and t.device != x_start.device for t in ts + (indices, t_table)):
-        raise _lib.DxmiError(f"{what}: operands on different devices")
-    return N, x_start.numel() // N, t_table.numel()
-
-
 def cd_prep(x_start, noise, indices, t_table, sigma_data=0.5, teacher_sigma_data=None):
     """-> (x_t = x_start + noise t, x_in = c_in(t) x_t, time = 250 ln(t + 1e-44), x_in_teacher | None) with t = t_table[indices]
     (dxmi_cd_prep).  x_in_teacher is written only where teacher_sigma_data is given and differs from sigma_data."""
-    N, CHW, S = _cd_operands("dxmi_cd_prep", x_start, indices, t_table, same=(noise,))
+    N, CHW, S = _batch_operands("dxmi_cd_prep", x_start, indices=indices, t_table=t_table, same=(noise,))
     x_t, x_in = torch.empty_like(x_start), torch.empty_like(x_start)
     t = torch.empty(N, dtype=torch.float32, device=x_start.device)
     own = teacher_sigma_data is not None and float(teacher_sigma_data) != float(sigma_data)
@@ -1094,7 +1071,7 @@ def cd_solver(mode, x_t, indices, t_table, x_start=None, model_out=None, d=None,
         raise _lib.DxmiError(f"dxmi_cd_solver: unknown mode {mode!r}")
     if any(v is None for v in need):
         raise _lib.DxmiError("dxmi_cd_solver: EULER_X0 needs x_start, HEUN_PRED model_out, HEUN_CORR model_out, d and samples")
-    N, CHW, S = _cd_operands("dxmi_cd_solver", x_t, indices, t_table, same=need)
+    N, CHW, S = _batch_operands("dxmi_cd_solver", x_t, indices=indices, t_table=t_table, same=need)
     x_next, t_next = torch.empty_like(x_t), torch.empty(N, dtype=torch.float32, device=x_t.device)
     x_t2 = None
     if mode == CD_HEUN_PRED:
@@ -1119,7 +1096,7 @@ def cd_loss_fwd(f_online, f_target, x_t, x_t2, indices, t_table, loss_norm, weig
                 distillation=False):
     """-> per-sample consistency loss mean_flat(norm(distiller - target)) * get_weightings(snr(t)) (dxmi_cd_loss_fwd)."""
     norm, sched = _cd_loss_args("dxmi_cd_loss_fwd", f_online, loss_norm, weight_schedule)
-    N, _, S = _cd_operands("dxmi_cd_loss_fwd", f_online, indices, t_table, same=(f_target, x_t, x_t2))
+    N, _, S = _batch_operands("dxmi_cd_loss_fwd", f_online, indices=indices, t_table=t_table, same=(f_target, x_t, x_t2))
     _, C, H, W = f_online.shape
     loss = torch.empty(N, dtype=torch.float32, device=f_online.device)
     check(load().dxmi_cd_loss_fwd(_ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices), _ptr(t_table), S, _ptr(loss),
@@ -1134,7 +1111,7 @@ def cd_loss_bwd(g_loss, f_online, f_target, x_t, x_t2, indices, t_table, loss_no
     norm, sched = _cd_loss_args("dxmi_cd_loss_bwd", f_online, loss_norm, weight_schedule)
     if g_loss is None:
         raise _lib.DxmiError("dxmi_cd_loss_bwd: no upstream gradient")
-    N, _, S = _cd_operands("dxmi_cd_loss_bwd", f_online, indices, t_table, same=(f_target, x_t, x_t2), per_sample=(g_loss,))
+    N, _, S = _batch_operands("dxmi_cd_loss_bwd", f_online, indices=indices, t_table=t_table, same=(f_target, x_t, x_t2), per_sample=(g_loss,))
     _, C, H, W = f_online.shape
     d = torch.empty_like(f_online)
     check(load().dxmi_cd_loss_bwd(_ptr(g_loss), _ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices), _ptr(t_table), S,
@@ -1161,9 +1138,7 @@ def cd_huber_fwd(f_online, f_target, x_t, x_t2, indices, t_table, huber_c, weigh
     """-> (loss, ssq): ssq = sum((distiller - target)^2) per sample and the pseudo-Huber consistency loss
     w ssq / (sqrt(ssq + huber_c^2) + huber_c), w the weight schedule ("ict": 1 / (t - t2)) (dxmi_cd_huber_fwd)."""
     c, sched = _cd_huber_args("dxmi_cd_huber_fwd", huber_c, weight_schedule)
-    N, CHW, S = _cd_operands("dxmi_cd_huber_fwd", f_online, indices, t_table, same=(f_target, x_t, x_t2))
-    if CHW % 4:
-        raise _lib.DxmiError(f"dxmi_cd_huber_fwd: the elements per sample ({CHW}) must be a multiple of 4")
+    N, CHW, S = _batch_operands("dxmi_cd_huber_fwd", f_online, indices=indices, t_table=t_table, same=(f_target, x_t, x_t2), chw4=True)
     loss = torch.empty(N, dtype=torch.float32, device=f_online.device)
     ssq = torch.empty_like(loss)
     check(load().dxmi_cd_huber_fwd(_ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices), _ptr(t_table), S, _ptr(loss),
@@ -1179,9 +1154,8 @@ def cd_huber_bwd(g_loss, ssq, f_online, f_target, x_t, x_t2, indices, t_table, h
     c, sched = _cd_huber_args("dxmi_cd_huber_bwd", huber_c, weight_schedule)
     if g_loss is None or ssq is None:
         raise _lib.DxmiError("dxmi_cd_huber_bwd: no upstream gradient / no ssq of the forward")
-    N, CHW, S = _cd_operands("dxmi_cd_huber_bwd", f_online, indices, t_table, same=(f_target, x_t, x_t2), per_sample=(g_loss, ssq))
-    if CHW % 4:
-        raise _lib.DxmiError(f"dxmi_cd_huber_bwd: the elements per sample ({CHW}) must be a multiple of 4")
+    N, CHW, S = _batch_operands("dxmi_cd_huber_bwd", f_online, indices=indices, t_table=t_table, same=(f_target, x_t, x_t2), per_sample=(g_loss, ssq),
+                                chw4=True)
     d = torch.empty_like(f_online)
     check(load().dxmi_cd_huber_bwd(_ptr(g_loss), _ptr(ssq), _ptr(f_online), _ptr(f_target), _ptr(x_t), _ptr(x_t2), _ptr(indices),
                                    _ptr(t_table), S, _ptr(d), N, CHW, c, float(sigma_data), float(sigma_min), int(bool(distillation)),
@@ -1195,14 +1169,12 @@ PD_LOSS_NORMS = {"l1": 0, "l2": 1}
 
 
 def _pd_operands(what, first, indices, t_table, same=(), per_sample=()):
-    """_cd_operands for the progressive-distillation launches: t_table holds 2 S + 1 levels (S + 1 coarse, then S half steps).
+    """_batch_operands for the progressive-distillation launches: t_table holds 2 S + 1 levels (S + 1 coarse, then S half steps).
     -> (N, CHW, S)."""
     if t_table is None or t_table.dim() != 1 or t_table.numel() < 3 or t_table.numel() % 2 == 0:
         raise _lib.DxmiError(f"{what}: t_table must hold 2 num_scales + 1 levels (num_scales >= 1), got "
                              f"{None if t_table is None else tuple(t_table.shape)}")
-    N, CHW, L = _cd_operands(what, first, indices, t_table, same=same, per_sample=per_sample)
-    if CHW % 4:
-        raise _lib.DxmiError(f"{what}: the elements per sample ({CHW}) must be a multiple of 4")
+    N, CHW, L = _batch_operands(what, first, same, per_sample, indices=indices, t_table=t_table, chw4=True)
     return N, CHW, (L - 1) // 2
 
 
@@ -1270,45 +1242,19 @@ def _dm_scalar(what, name, v):
     return v
 
 
-def _dm_images(what, first, same=(), per_sample=()):
-    """The operand checks of _cd_operands for the launches of csrc/dm_train.hip that read no level table.  -> (N, CHW)."""
-    ts = (first,) + tuple(same) + tuple(per_sample)
-    _need_cuda(*ts)
-    for t in ts:
-        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0):
-            raise _lib.DxmiError(f"{what}: fp32 contiguous 16-byte aligned device tensors")
-    if first.dim() < 2 or first.numel() == 0:
-        raise _lib.DxmiError(f"{what}: a non-empty batch [N, ...] is needed, got {tuple(first.shape)}")
-    N = first.shape[0]
-    for t in same:
-        if t is not None and t.shape != first.shape:
-            raise _lib.DxmiError(f"{what}: operand of shape {tuple(t.shape)} where {tuple(first.shape)} is needed")
-    for t in per_sample:
-        if t is not None and t.numel() != N:
-            raise _lib.DxmiError(f"{what}: per-sample operand of {t.numel()} elements for a batch of {N}")
-    if any(t is not None and t.device != first.device for t in ts):
-        raise _lib.DxmiError(f"{what}: operands on different devices")
-    CHW = first.numel() // N
-    if CHW % 4:
-        raise _lib.DxmiError(f"{what}: the elements per sample ({CHW}) must be a multiple of 4")
-    return N, CHW
-
-
 def _dm_operands(what, first, indices, t_table, same=(), per_sample=()):
-    """_cd_operands for the launches of csrc/dm_train.hip that gather t = t_table[indices] (the table of cd_levels: >= 2 levels)."""
+    """_batch_operands for the launches of csrc/dm_train.hip and sid_train.hip that gather t = t_table[indices] (the table of
+    cd_levels: >= 2 levels); none of their operands is optional."""
     if any(v is None for v in (first, indices, t_table) + tuple(same)):
         raise _lib.DxmiError(f"{what}: a needed operand is None")
-    N, CHW, S = _cd_operands(what, first, indices, t_table, same=same, per_sample=per_sample)
-    if CHW % 4:
-        raise _lib.DxmiError(f"{what}: the elements per sample ({CHW}) must be a multiple of 4")
-    return N, CHW, S
+    return _batch_operands(what, first, same, per_sample, indices=indices, t_table=t_table, chw4=True)
 
 
 def dm_gen_in(z, gen_sigma, sigma_data=0.5):
     """-> (x_in = c_in(sigma_G) (sigma_G z), time [N] = 250 ln(sigma_G + 1e-44)): the one-step generator's input (dxmi_dm_gen_in)."""
     if z is None:
         raise _lib.DxmiError("dxmi_dm_gen_in: no latents")
-    N, CHW = _dm_images("dxmi_dm_gen_in", z)
+    N, CHW, _ = _batch_operands("dxmi_dm_gen_in", z, chw4=True)
     sg, sd = _dm_scalar("dxmi_dm_gen_in", "gen_sigma", gen_sigma), _dm_scalar("dxmi_dm_gen_in", "sigma_data", sigma_data)
     x_in, t = torch.empty_like(z), torch.empty(N, dtype=torch.float32, device=z.device)
     check(load().dxmi_dm_gen_in(_ptr(z), _ptr(x_in), _ptr(t), N, CHW, sg, sd, _stream()), "dxmi_dm_gen_in")
@@ -1319,7 +1265,7 @@ def dm_gen_out(f_gen, z, gen_sigma, sigma_data=0.5, clip=True, out=None):
     """-> x = c_skip(sigma_G) (sigma_G z) + c_out(sigma_G) f_gen, clamped to [-1, 1] when `clip` (dxmi_dm_gen_out)."""
     if f_gen is None or z is None:
         raise _lib.DxmiError("dxmi_dm_gen_out: f_gen and z are needed")
-    N, CHW = _dm_images("dxmi_dm_gen_out", f_gen, same=(z, out))
+    N, CHW, _ = _batch_operands("dxmi_dm_gen_out", f_gen, same=(z, out), chw4=True)
     sg, sd = _dm_scalar("dxmi_dm_gen_out", "gen_sigma", gen_sigma), _dm_scalar("dxmi_dm_gen_out", "sigma_data", sigma_data)
     x = torch.empty_like(f_gen) if out is None else out
     check(load().dxmi_dm_gen_out(_ptr(f_gen), _ptr(z), _ptr(x), N, CHW, sg, sd, int(bool(clip)), _stream()), "dxmi_dm_gen_out")
@@ -1371,7 +1317,7 @@ def dm_gen_bwd(upstream, g, gen_sigma, sigma_data=0.5):
     """-> d(f_gen) = ((upstream[n] / CHW) g[n]) c_out(sigma_G) for the device upstream gradient [N] (dxmi_dm_gen_bwd)."""
     if upstream is None or g is None:
         raise _lib.DxmiError("dxmi_dm_gen_bwd: no upstream gradient / no g of the forward")
-    N, CHW = _dm_images("dxmi_dm_gen_bwd", g, per_sample=(upstream,))
+    N, CHW, _ = _batch_operands("dxmi_dm_gen_bwd", g, per_sample=(upstream,), chw4=True)
     sg, sd = _dm_scalar("dxmi_dm_gen_bwd", "gen_sigma", gen_sigma), _dm_scalar("dxmi_dm_gen_bwd", "sigma_data", sigma_data)
     d = torch.empty_like(g)
     check(load().dxmi_dm_gen_bwd(_ptr(upstream), _ptr(g), _ptr(d), N, CHW, sg, sd, _stream()), "dxmi_dm_gen_bwd")
@@ -1398,7 +1344,7 @@ def sid_grad_fwd(f_real, f_fake, x, x_t, indices, t_table, alpha=1.2, real=None,
         s = torch.empty_like(loss)
     else:
         v_r, v_f, d_dir, loss, s = outs
-        _dm_images(what, f_real, same=(v_r, v_f, d_dir), per_sample=(loss, s))
+        _batch_operands(what, f_real, same=(v_r, v_f, d_dir), per_sample=(loss, s), chw4=True)
         if any(v is None for v in outs):
             raise _lib.DxmiError(f"{what}: outs holds five tensors")
     check(load().dxmi_sid_grad_fwd(_ptr(f_real), _ptr(f_fake), _ptr(x), _ptr(x_t), _ptr(indices), _ptr(t_table), S, alpha, _ptr(v_r),
@@ -1419,7 +1365,7 @@ def sid_join(d_dir, g_real, g_fake, s, indices, t_table, real_sigma_data=0.5, fa
     if out is None:
         out = torch.empty_like(d_dir)
     elif out is not d_dir:
-        _dm_images(what, d_dir, same=(out,))
+        _batch_operands(what, d_dir, same=(out,), chw4=True)
         if any(out.data_ptr() == v.data_ptr() for v in (d_dir, g_real, g_fake)):
             raise _lib.DxmiError(f"{what}: out may be d_dir itself or a tensor of its own")
     check(load().dxmi_sid_join(_ptr(d_dir), _ptr(g_real), _ptr(g_fake), _ptr(s), _ptr(indices), _ptr(t_table), S, _ptr(out), N, CHW,

@@ -557,7 +557,7 @@ int dxmi_dropout_bf16(const void* x, void* y, int64_t n, float p, uint32_t seed,
 int dxmi_dropout_bf16_dev(const void* x, void* y, int64_t n, float p, const uint32_t* seed, void* stream);
 
 /* Denoising score-matching loss of the EDM teacher (KarrasDenoiser.training_losses, models/cm/karras_diffusion.py:82-106, with
- * get_weightings :18-31 and denoise :337-351), fp32 NCHW [N, CHW] tensors (CHW a multiple of 4, 16-byte aligned), sigma [N]:
+ * get_weightings :18-31 and denoise :337-351), fp32 NCHW [N, CHW] tensors (CHW a multiple of 4 below 2^30, 16-byte aligned), sigma [N]:
  * dxmi_edm_dsm_prep:     x_in = c_in(s) (x_start + noise s), t[n] = 250 ln(s + 1e-44) — the network input; x_t is not stored.
  * dxmi_edm_dsm_loss_fwd: x_t recomputed, denoised = c_out F + c_skip x_t (boundary-condition scalings when distillation != 0),
  *                        xs_mse[n] = mean((denoised - x_start)^2), mse[n] = mean(w(s) (denoised - x_start)^2), w = the weight
@@ -583,7 +583,7 @@ int dxmi_edm_dsm_loss_bwd(const float* g_mse, const float* g_xs, const float* mo
                           int32_t distillation, int32_t weight_schedule, void* stream);
 
 /* Noise-prediction training of the DDPM U-Net (Ho et al. 2020, "Denoising Diffusion Probabilistic Models"), fp32 NCHW [N, CHW]
- * tensors (CHW a multiple of 4, 16-byte aligned).  table: fp32 [2][T] on the DEVICE, row 0 = sqrt(alpha_bar), row 1 =
+ * tensors (CHW a multiple of 4 below 2^30, 16-byte aligned).  table: fp32 [2][T] on the DEVICE, row 0 = sqrt(alpha_bar), row 1 =
  * sqrt(1 - alpha_bar) of calc_diffusion_hyperparams (models/DxMI/var_sampler.py); t_idx: int64 [N] on the DEVICE.
  * dxmi_ddpm_prep (eq. 4, q(x_t | x_0)): x_t[n] = table[0][t] x_start[n] + table[1][t] noise[n] (two products, one sum),
  *   t_out[n] = (float)t — the network's input.  An index outside [0, T) gives NaN coefficients for that sample; nothing outside
@@ -608,7 +608,7 @@ int dxmi_ema_update(void* const* ema, const void* const* src, const int64_t* num
                     const double* rates, const float* found_inf, void* stream);
 
 /* Consistency distillation / consistency training losses (KarrasDenoiser.consistency_losses, models/cm/karras_diffusion.py:108-241),
- * one launch between two network evaluations.  fp32 NCHW [N, CHW] tensors (CHW a multiple of 4, 16-byte aligned); indices: int64
+ * one launch between two network evaluations.  fp32 NCHW [N, CHW] tensors (CHW a multiple of 4 below 2^30, 16-byte aligned); indices: int64
  * [N] on the DEVICE; t_table: fp32 [num_scales] on the DEVICE, the time ladder of :180-188 built on the host: t = t_table[index],
  * t2 = t_table[index + 1].  An index outside [0, num_scales - 2] gives NaN levels; nothing outside the table is read.  Every fp32
  * operation in the reference's order, one rounding per torch op (true division by t; (d + next_d) * ((t2 - t) / 2)).

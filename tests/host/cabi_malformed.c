@@ -129,6 +129,15 @@ int main(void) {
     expect_einval("dropout_bf16(p = 1.5)", dxmi_dropout_bf16(FAKE(1), FAKE(2), 1024, 1.5f, 7u, NULL));
     expect_einval("colsum_f32(B = 0)", dxmi_colsum_f32((const float*)FAKE(1), (float*)FAKE(2), 0, 4, 128, NULL));
     expect_einval("edm_step_fwd(NULL sigma)", dxmi_edm_step_fwd((const float*)FAKE(1), (const float*)FAKE(2), (const float*)FAKE(3), NULL, (const float*)FAKE(4), (const float*)FAKE(5), (float*)FAKE(6), (float*)FAKE(7), 4, 12288, 0.5f, NULL));
+    /* the elementwise training launches index an image's vectors in int: CHW < 2^30 (csrc/ew_common.h EW_CHECK_SHAPE) */
+    expect_einval("ddpm_prep(CHW = 2^30)", dxmi_ddpm_prep((const float*)FAKE(1), (const float*)FAKE(2), (const int64_t*)FAKE(3), (const float*)FAKE(4), 1000, (float*)FAKE(5), (float*)FAKE(6), 4, 1 << 30, NULL));
+    expect_einval("ddpm_loss_fwd(CHW = 2^30)", dxmi_ddpm_loss_fwd((const float*)FAKE(1), (const float*)FAKE(2), (float*)FAKE(3), 4, 1 << 30, NULL));
+    expect_einval("ddpm_loss_bwd(CHW = 2^30)", dxmi_ddpm_loss_bwd((const float*)FAKE(1), (const float*)FAKE(2), (const float*)FAKE(3), (float*)FAKE(4), 4, 1 << 30, NULL));
+    expect_einval("edm_dsm_prep(CHW = 2^30)", dxmi_edm_dsm_prep((const float*)FAKE(1), (const float*)FAKE(2), (const float*)FAKE(3), (float*)FAKE(4), (float*)FAKE(5), 4, 1 << 30, 0.5f, NULL));
+    expect_einval("edm_dsm_loss_fwd(CHW = 2^30)", dxmi_edm_dsm_loss_fwd((const float*)FAKE(1), (const float*)FAKE(2), (const float*)FAKE(3), (const float*)FAKE(4), (float*)FAKE(5), (float*)FAKE(6), 4, 1 << 30, 0.5f, 0.002f, 0, DXMI_DSM_W_KARRAS, NULL));
+    expect_einval("edm_dsm_loss_bwd(CHW = 2^30)", dxmi_edm_dsm_loss_bwd((const float*)FAKE(1), NULL, (const float*)FAKE(2), (const float*)FAKE(3), (const float*)FAKE(4), (const float*)FAKE(5), (float*)FAKE(6), 4, 1 << 30, 0.5f, 0.002f, 0, DXMI_DSM_W_KARRAS, NULL));
+    expect_einval("cd_prep(CHW = 2^30)", dxmi_cd_prep((const float*)FAKE(1), (const float*)FAKE(2), (const int64_t*)FAKE(3), (const float*)FAKE(4), 18, (float*)FAKE(5), (float*)FAKE(6), (float*)FAKE(7), NULL, 4, 1 << 30, 0.5f, 0.5f, NULL));
+    expect_einval("cd_solver(CHW = 2^30)", dxmi_cd_solver(DXMI_CD_EULER_X0, (const float*)FAKE(1), (const float*)FAKE(2), NULL, NULL, NULL, (const int64_t*)FAKE(3), (const float*)FAKE(4), 18, (float*)FAKE(5), (float*)FAKE(6), (float*)FAKE(7), 4, 1 << 30, 0.5f, 0.002f, 0, 0.5f, NULL));
 
     expect_einval("attention_bwd(NULL o)", dxmi_attention_bwd(FAKE(1), NULL, FAKE(2), FAKE(3), FAKE(4), 2, 256, 128, 2, 0.125f, NULL));
     expect_einval("attention_bwd(head dim 32)", dxmi_attention_bwd(FAKE(1), FAKE(5), FAKE(2), FAKE(3), FAKE(4), 2, 256, 128, 4, 0.125f, NULL));

@@ -18,6 +18,8 @@ import numpy as np
 import pytest
 import torch
 
+from ew_shapes import n_by_shape
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U = 2.0 ** -24
@@ -100,8 +102,7 @@ def grad_ref64(Fr, Ff, x, x_t, t, weighting, sd_r=0.5, sd_f=0.5, dist_r=False, d
 
 # ------------------------------------------------------------------------------------------ kernels
 @pytest.mark.parametrize("S", [2, 18])
-@pytest.mark.parametrize("shape", [(3, 16, 16), (3, 12, 11), (3, 64, 64)])
-@pytest.mark.parametrize("N", [1, 7])
+@pytest.mark.parametrize("N,shape", n_by_shape([(3, 16, 16), (3, 12, 11), (3, 64, 64)]))
 @pytest.mark.parametrize("sd_f", [0.5, 0.25])
 def test_kernels_vs_fp64(ops, shape, N, S, sd_f):
     z, noise, Fg, Fr, Ff, idx, tab = operands(N, shape, 31 + N + shape[1] + S, S)

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from ew_shapes import SECOND_TRIP
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U = 2.0 ** -24
@@ -75,10 +77,10 @@ def operands(N, CHW, seed):
 
 
 # ------------------------------------------------------------------------------------------ kernels
-@pytest.mark.parametrize("CHW", [3 * 16 * 16, 3 * 64 * 64, 4 * 3 * 33])
+@pytest.mark.parametrize("CHW", [3 * 16 * 16, 3 * 64 * 64, 4 * 3 * 33, math.prod(SECOND_TRIP)])
 @pytest.mark.parametrize("distill", [False, True])
 def test_dsm_kernels_vs_fp64(ops, CHW, distill):
-    N = 7
+    N = 1 if CHW == math.prod(SECOND_TRIP) else 7
     x0, noise, F, sig = operands(N, CHW, 5 + CHW)
     d = lambda t: t.to(DEV).contiguous()
     x_in, t = ops.edm_dsm_prep(d(x0), d(noise), d(sig))

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+from ew_shapes import n_by_shape
 from test_hip_cm_train import PLAIN, TINY_KW, _cos, build, scal64
 
 pytestmark = pytest.mark.gpu
@@ -113,8 +114,7 @@ def check_huber_kernels(ops, cpu, ws, distill, c, gl):
 
 
 # ------------------------------------------------------------------------------------------ kernels
-@pytest.mark.parametrize("shape", SHAPES)
-@pytest.mark.parametrize("N", [1, 7])
+@pytest.mark.parametrize("N,shape", n_by_shape(SHAPES))
 @pytest.mark.parametrize("distill", [False, True])
 def test_huber_kernels_vs_fp64(ops, shape, N, distill):
     gl = torch.randn(N, generator=torch.Generator().manual_seed(N))

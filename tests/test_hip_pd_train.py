@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 import torch
 
+from ew_shapes import n_by_shape
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U = 2.0 ** -24
@@ -89,8 +91,7 @@ def close(got, ref, M, k=16, floor=1e-30):
 
 # ------------------------------------------------------------------------------------------ kernels
 @pytest.mark.parametrize("S", [1, 18])
-@pytest.mark.parametrize("shape", [(3, 16, 16), (3, 64, 64), (3, 12, 11)])
-@pytest.mark.parametrize("N", [1, 7])
+@pytest.mark.parametrize("N,shape", n_by_shape([(3, 16, 16), (3, 64, 64), (3, 12, 11)]))
 @pytest.mark.parametrize("distill", [False, True])
 def test_solver_vs_fp64(ops, shape, N, distill, S):
     x0, noise, F1, F2, _, idx, tab = operands(N, shape, 11 + N + shape[1] + S, S)
@@ -146,8 +147,7 @@ def _w64(ws, t, sd=0.5):
 
 
 @pytest.mark.parametrize("S", [1, 18])
-@pytest.mark.parametrize("shape", [(3, 16, 16), (3, 64, 64), (3, 12, 11)])
-@pytest.mark.parametrize("N", [1, 7])
+@pytest.mark.parametrize("N,shape", n_by_shape([(3, 16, 16), (3, 64, 64), (3, 12, 11)]))
 @pytest.mark.parametrize("distill", [False, True])
 def test_loss_kernels_vs_fp64(ops, shape, N, distill, S):
     from dxmi_hip import lpips_ops

@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 import torch
 
+from ew_shapes import n_by_shape
 from test_hip_dm_train import (DEV, FAKE_SCALE, GEN_SCALE, NET_Y, N_NET, PKG, S_NET, U, _cos, _diffusion, _flat, _oracle64, build, e,
                                scal64)
 
@@ -108,8 +109,7 @@ FAKES = ((0.5, False), (0.25, False), (0.5, True))
 
 # ------------------------------------------------------------------------------------------ launches
 @pytest.mark.parametrize("S", [2, 18])
-@pytest.mark.parametrize("shape", [(3, 16, 16), (3, 12, 11), (3, 64, 64), (3, 80, 80)])
-@pytest.mark.parametrize("N", [1, 7])
+@pytest.mark.parametrize("N,shape", n_by_shape([(3, 16, 16), (3, 12, 11), (3, 64, 64), (3, 80, 80)]))
 def test_launches_vs_fp64(ops, shape, N, S):
     """3 x 64 x 64 is the largest image of the programs here, 3 x 80 x 80 lies above it (where dxmi_dm_grad_fwd changes kernels;
     the launch here is one pass at every size), 3 x 12 x 11 = 396 elements leaves a partly filled trip."""
