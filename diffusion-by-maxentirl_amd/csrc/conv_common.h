@@ -23,11 +23,11 @@ struct ConvArgs {
     int stagger;             // conv_pipe: start delay (units of s_sleep 127 ~ 8k cycles) of the second resident half
     int RP, SP;              // conv_pipe: LDS pitch of a halo row / of a sub-image, bytes (bank-conflict-free choice)
     float* gn_stats;         // optional: GroupNorm block statistics of the OUTPUT, fp32 [N][P][Cout/2][2] (dxmi_conv_desc.gn_stats)
-    bf16* gn_out;            // optional: fused GroupNorm(+SiLU) of the output (dxmi_conv_desc.gn_out ...): conv_sm_kernel only
+    bf16* gn_out;            // optional: fused GroupNorm(+SiLU) of the output (dxmi_conv_desc.gn_out ...): conv_sm_kernel, conv_ws8_kernel<true>, conv_ws_gn_kernel
     const float* gn_gamma;
     const float* gn_beta;
     float gn_eps;
-    int gn_flags;            // bit 0: SiLU, bit 1: skip the raw output
+    int gn_flags;            // bit 0: SiLU, bit 1: skip the raw output, bit 2: the conv_ws family may serve gn_out (conv_ws_gn_kernel)
     int res_is_mask;         // conv_ws_kernel: `residual` carries the activation-mask source (out *= mask > 0 ? 1 : mask_slope), set by its launcher
     int xcd_order;           // conv_ws_kernel / conv_ws8_kernel (set by their launchers): tiles handed out in XCD-aware order
 };

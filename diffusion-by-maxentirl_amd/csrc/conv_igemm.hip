@@ -474,7 +474,8 @@ int launch_igemm(const ConvPlan& p, hipStream_t st) {
 // can write it; a GroupNorm statistics request does not change the choice (conv_plan checks it against the plan).
 void conv_select(const ConvArgs& a, int variant, ConvPlan* p) {
     auto is = [&](bool (*select)(const ConvArgs&, ConvPlan*)) { *p = ConvPlan{}; p->args = a; return select(a, p); };
-    if (variant == 0 && (a.gn_out ? is(conv_sm_select) || is(conv_ws8_select)
+    // (gn_flags bit 2: the caller also takes the conv_ws family's fused output, conv_ws_gn_kernel)
+    if (variant == 0 && (a.gn_out ? ((a.gn_flags & 4) && is(conv_ws_select)) || is(conv_sm_select) || is(conv_ws8_select)
                                   : is(conv_ws_select) || is(conv1x1_rw8_select) || is(conv1x1_rw_select) || is(conv_head_select) ||
                                         is(conv_sm_select) || is(conv_ws8_select) || is(conv_stem_select) || is(conv_pipe_select)))
         return;
@@ -580,7 +581,8 @@ extern "C" int dxmi_conv2d_gn_stats_partials(const dxmi_conv_desc* d) {
 }
 
 // Whether the selected kernel can write the fused GroupNorm(+SiLU) of its output: conv_sm_kernel<2, 8, 32> (eight whole 4x4
-// images x 32 couts per tile) and conv_ws8_kernel (a whole 8x8 image per wave, instead of the raw output).
+// images x 32 couts per tile), conv_ws8_kernel (a whole 8x8 image per wave, instead of the raw output) and, for callers that set
+// gn_flags bit 2, conv_ws_gn_kernel<16> (a whole 16x16 image x 128 couts per tile, instead of the raw output).
 extern "C" int dxmi_conv2d_gn_fuse_supported(const dxmi_conv_desc* d) {
     if (!d || d->variant != 0 || d->out_mode != DXMI_OUT_NHWC_BF16 || d->gn_groups <= 0 || d->Cout != 8 * d->gn_groups) return 0;
     dxmi_conv_desc q = *d;

@@ -34,6 +34,7 @@
 // Everything else stays on conv_pipe.hip.  Full-width nearest-x2 upsample convs (OW = 2 IW in {16, 32}) run the family's second
 // kernel function, conv_ws_up_kernel (conv_ws_up.hip): same plan kind, id and statistics layout.
 #include "conv_common.h"
+#include "gn_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -91,6 +92,7 @@ constexpr int WS_RO = 256 * 256;             // output / residual tile: 256 px x
 constexpr int WS_TB = 1024;                  // bias[128] | temb[128] fp32
 constexpr int WS_HALO_BLOCKS = 22;           // 1-KiB blocks of a halo image (34x10 or 18x18 pixels x 64 B)
 constexpr int WS_HALO = WS_HALO_BLOCKS * 1024;
+constexpr int WS_GN = 2048;                  // conv_ws_gn_kernel: gamma[128] | beta[128] | partials [2 pixel halves][64 pairs][2] fp32
 
 __device__ uint4 ws_zero16 = {0u, 0u, 0u, 0u};   // source of zero-padding pixels
 
@@ -198,8 +200,17 @@ struct WsValuLoad {
 // (16 couts x 32 channels) of cout block cb16 is lanes (cb16 & 1) * 16 .. + 15 of both lane halves of the two k-step
 // fragments of cout block cb16 >> 1 — a per-lane base plus a compile-time offset as well, bank-conflict free as it lies.
 // (Round 4 carried a second instantiation that wrote GroupNorm(+SiLU) of a 16x16 map's output from this epilogue: parity-green, 4 %
-// slower end to end — two more passes over 128 accumulators on the MFMA waves' critical path — and removed in round 5: DESIGN 5.4 / 5.5.)
-template <int TW>
+// slower end to end — two more passes over 128 accumulators on the MFMA waves' critical path — and removed in round 5: DESIGN 5.4 / 5.5.
+// Round 11 brought the fusion back in a third form, conv_ws_gn_kernel below: the tile is normalised in place in LDS AFTER the
+// epilogue, when no accumulator is live: DESIGN 5.36.)
+//
+// GN (conv_ws_gn_kernel<16>): GroupNorm(+SiLU) of the output written INSTEAD of the raw output (dxmi_conv_desc.gn_out with gn_flags
+// bits 1 and 2).  A 16x16 map's tile is a whole image x 128 couts = 16 whole groups of 8 channels, so nothing crosses workgroups:
+// the epilogue leaves the block-statistics partials of the tile's two pixel halves in LDS as well (the values and the layout
+// gn_stats gets), one more workgroup barrier, and the MFMA waves — the matrix pipe is idle at the tile end anyway — form each
+// lane's (scale, offset) with gn_common.h's arithmetic in gn_apply_kernel's order (same bits as the two-launch path) and transform
+// the 64 KB tile in place, 16 pieces of 16 bytes per lane; the movers drain it as they drain a raw tile.
+template <int TW, bool GN>
 __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
     constexpr int TH = 256 / TW, HP = TW == 32 ? 34 : 18, HH = TH + 2, TWl = TW == 32 ? 5 : 4;
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -207,6 +218,8 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
     char* const aring = smem + 2 * WS_HALO;
     char* const ro = aring + WS_A_RING;
     float* const tb = reinterpret_cast<float*>(ro + WS_RO);
+    float* const gb = tb + WS_TB / 4;                // GN: gamma[128] | beta[128] of the tile's couts (fetched with the bias / temb table)
+    float* const ps = gb + 256;                      // GN: [pixel half][cout pair][sum, sum of squares] of the tile
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -326,9 +339,9 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 // GroupNorm block statistics of the output (optional): this wave's 128 pixels x its 64 couts -> (sum, sum of
                 // squares) per cout PAIR, partial (pixel tile, pixel half) of the image: [pt * 2 + ph][Cout / 2][2].  A lane's
                 // four accumulator values of a (cb, nb) are two pairs of one pixel: 8 pixels in registers, 16 in the DPP row.
-                const bool want_stats = p.gn_stats != nullptr;
+                const bool want_stats = GN || p.gn_stats != nullptr;
                 const int cot_ = q % p.CT;
-                float* const stp = want_stats ? p.gn_stats + ((size_t)((q / p.CT) * 2 + ph) * (p.Cout >> 1) + cot_ * 64 + ch * 32 + kg * 2) * 2 : nullptr;
+                float* const stp = p.gn_stats ? p.gn_stats + ((size_t)((q / p.CT) * 2 + ph) * (p.Cout >> 1) + cot_ * 64 + ch * 32 + kg * 2) * 2 : nullptr;
                 // The run-time switches (residual / mask / activation / statistics) are uniform for the launch: as branches inside
                 // the 32 (cb, nb) bodies they cost ~130 scalar branches and their s_nop shadows per tile and keep hipcc from
                 // batching the LDS traffic (round 4: the epilogue was 9.4 k of a 128-channel tile's 38 k cycles).  The U-Net's
@@ -372,8 +385,10 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                             for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
                             *reinterpret_cast<bf16x4*>(a0 + nb * 4096) = o;
                             if constexpr (kStats) dxmi_stats4(o, st);
+                            if constexpr (!GN) {           // (GN: cleared behind the transform, so that nothing of acc is live in it)
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[cb][nb][e] = 0.f;
+                                for (int e = 0; e < 4; ++e) acc[cb][nb][e] = 0.f;
+                            }
                         }
                         if constexpr (kStats) {
 #pragma unroll
@@ -382,7 +397,8 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                                 f32x4 sv;
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) sv[e] = st[e];
-                                *reinterpret_cast<f32x4*>(stp + cb * 16) = sv;     // pairs (co / 2, co / 2 + 1): 8 pairs per 16-cout block
+                                if (!GN || stp) *reinterpret_cast<f32x4*>(stp + cb * 16) = sv;     // pairs (co / 2, co / 2 + 1): 8 pairs per 16-cout block
+                                if constexpr (GN) *reinterpret_cast<f32x4*>(ps + ph * 128 + co) = sv;   // the same values for this tile's own transform
                             }
                         }
                     }
@@ -404,6 +420,55 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 }
             }
             WS_TSTAMP(166, wave == 0 && q == q0);
+            if constexpr (GN) {
+                ws_barrier();                           // EG: the raw tile and the partials of both pixel halves are in LDS
+                // Lane = channel piece c8 (one whole group: 8 channels per group) of pixels wave * 64 + (lane >> 4) + 4 j, j < 16: a
+                // 16-lane row reads one pixel's 256 bytes (conflict free whatever the slot swizzle).  The group's moments, formed by
+                // every lane for itself (no LDS table, no further barrier): a pair's two partials in partial order (gn_pair_sums), the
+                // group's four pairs in channel order (gn_group_moments), then gn_channel_ab: gn_apply_kernel's prologue, bit for bit.
+                const int c8 = lane & 15;
+                const f32x4 h0a = *reinterpret_cast<const f32x4*>(ps + c8 * 8), h0b = *reinterpret_cast<const f32x4*>(ps + c8 * 8 + 4);
+                const f32x4 h1a = *reinterpret_cast<const f32x4*>(ps + 128 + c8 * 8), h1b = *reinterpret_cast<const f32x4*>(ps + 128 + c8 * 8 + 4);
+                const f32x4 g0 = *reinterpret_cast<const f32x4*>(gb + c8 * 8), g1 = *reinterpret_cast<const f32x4*>(gb + c8 * 8 + 4);
+                const f32x4 b0 = *reinterpret_cast<const f32x4*>(gb + 128 + c8 * 8), b1 = *reinterpret_cast<const f32x4*>(gb + 128 + c8 * 8 + 4);
+                float2 pair_r[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float s0 = k < 2 ? h0a[2 * k] : h0b[2 * k - 4], q0_ = k < 2 ? h0a[2 * k + 1] : h0b[2 * k - 3];
+                    const float s1 = k < 2 ? h1a[2 * k] : h1b[2 * k - 4], q1_ = k < 2 ? h1a[2 * k + 1] : h1b[2 * k - 3];
+                    float s = 0.f, qq = 0.f;
+                    s += s0;
+                    qq += q0_;
+                    s += s1;
+                    qq += q1_;
+                    pair_r[k] = make_float2(s, qq);
+                }
+                float mean, rstd;
+                gn_group_moments(pair_r, 0, 8, p.OH * p.OW, p.gn_eps, &mean, &rstd);
+                float A[8], Bv[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) gn_channel_ab(mean, rstd, e < 4 ? g0[e] : g1[e - 4], e < 4 ? b0[e] : b1[e - 4], A[e], Bv[e]);
+                char* const trow = ro + ((wave * 64 + (lane >> 4)) << 8);
+                auto transform = [&](auto SILU) {
+#pragma unroll
+                    for (int j = 0; j < 16; j += 4) {
+                        bf16x8 v[4];
+                        // pixel & 15 = (lane >> 4) + 4 (j & 3): rows j .. j + 3 are 1 KiB apart
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const bf16x8*>(trow + (j + u) * 1024 + ((c8 ^ ((lane >> 4) + 4 * u)) << 4));
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                            *reinterpret_cast<bf16x8*>(trow + (j + u) * 1024 + ((c8 ^ ((lane >> 4) + 4 * u)) << 4)) = gn_norm8(v[u], A, Bv, decltype(SILU)::value);
+                    }
+                };
+                if (p.gn_flags & 1) transform(std::true_type{}); else transform(std::false_type{});
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+                    for (int nb = 0; nb < 8; ++nb)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[cb][nb][e] = 0.f;
+            }
             ws_barrier();                               // E2: output tile complete, the bulk movers may drain it
             WS_TSTAMP(157, wave == 0 && q == q0);
             if (!more) {
@@ -503,6 +568,12 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                     __builtin_amdgcn_global_load_lds(WS_GPTR(av + co_a), WS_LPTR(tb + 128), 4, 0, 0);
                     __builtin_amdgcn_global_load_lds(WS_GPTR(av + co_b), WS_LPTR(tb + 192), 4, 0, 0);
                 }
+                if constexpr (GN) {                // (the previous tile's transform read gamma / beta before E2)
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_gamma + co_a), WS_LPTR(gb), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_gamma + co_b), WS_LPTR(gb + 64), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_beta + co_a), WS_LPTR(gb + 128), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_beta + co_b), WS_LPTR(gb + 192), 4, 0, 0);
+                }
             }
             // The residual tile of THIS tile (tile switch): the bulk movers drain piece k of the previous tile's output in the
             // group step their schedule gives it; its residual replacement is fetched here one group step later (the group barrier
@@ -558,6 +629,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 load_group(3, nxt.cot, nxt.cot, fq[1]);
             }
             ws_barrier();                                        // E1
+            if constexpr (GN) ws_barrier();                      // EG
             ws_barrier();                                        // E2
             WS_TSTAMP(150, wave == 4 && q == q0);
             if (!more) break;
@@ -632,6 +704,12 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 __builtin_amdgcn_global_load_lds(WS_GPTR(av + co_a), WS_LPTR(tb + 128), 4, 0, 0);
                 __builtin_amdgcn_global_load_lds(WS_GPTR(av + co_b), WS_LPTR(tb + 192), 4, 0, 0);
             }
+            if constexpr (GN) {
+                __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_gamma + co_a), WS_LPTR(gb), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_gamma + co_b), WS_LPTR(gb + 64), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_beta + co_a), WS_LPTR(gb + 128), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(p.gn_beta + co_b), WS_LPTR(gb + 192), 4, 0, 0);
+            }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ws_barrier();                                           // P0
@@ -655,6 +733,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 }
             }
             ws_barrier();                                        // E1
+            if constexpr (GN) ws_barrier();                      // EG
             ws_barrier();                                        // E2
             if (!more) break;
             q += qstride;
@@ -734,6 +813,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
             }
             if (!have_prev) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // first tile: the residual tile of the prologue landed
             ws_barrier();                                        // E1
+            if constexpr (GN) ws_barrier();                      // EG
             ws_barrier();                                        // E2
             out_prev = reinterpret_cast<bf16*>(p.out) + tile_base(cur);
             prev = cur;
@@ -778,7 +858,13 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
 
 template <int TW>
 __global__ __launch_bounds__(512, 1) void conv_ws_kernel(ConvArgs p) {
-    conv_ws_body<TW>(p);
+    conv_ws_body<TW, false>(p);
+}
+
+// The family's third kernel function (plan.t2 = 1): the tile leaves normalised (see conv_ws_body).  Same plan kind and id.
+template <int TW>
+__global__ __launch_bounds__(512, 1) void conv_ws_gn_kernel(ConvArgs p) {
+    conv_ws_body<TW, true>(p);
 }
 
 }  // namespace
@@ -805,8 +891,13 @@ bool conv_ws_select(const ConvArgs& a, ConvPlan* p) {
     if ((long)a.N * (a.OH / TH) * (a.OW / TW) * ((a.Cout + 127) / 128) < min_tiles) return false;
     // 32-bit byte offsets inside either input part (the movers' per-tile source tables)
     if ((long)a.N * a.IH * a.IW * (a.C0 > a.C1 ? a.C0 : a.C1) * 2 >= (1L << 31)) return false;
+    // conv_ws_gn_kernel (gn_flags bit 2 asks for it, bit 1 = the normalised tensor INSTEAD of the raw one): a tile must hold whole
+    // images x whole groups — 16x16 maps, full 128-cout tiles (8 channels per group: conv_plan) — and the plain forward conv only
+    const bool gn_ok = (a.gn_flags & 4) && (a.gn_flags & 2) && a.OW == 16 && a.OH == 16 && a.Cout % 128 == 0 && !a.ups && !a.residual && !a.mask_src;
+    if (a.gn_out && !gn_ok) return false;
     ConvArgs& b = p->args;
     if (a.mask_src) { b.residual = a.mask_src; b.res_is_mask = 1; }
+    if (a.gn_out) b.out = a.gn_out;       // the movers drain the (normalised) tile to the fused output
     b.SUBS = 1;
     b.PT = a.N * (a.OH / TH) * (a.OW / TW);
     b.CT = (a.Cout + 127) / 128;
@@ -818,6 +909,12 @@ bool conv_ws_select(const ConvArgs& a, ConvPlan* p) {
     p->lds = 2 * WS_HALO + WS_A_RING + WS_RO + WS_TB;
     p->id = 400000 + TW;    // conv_ws_kernel<TW>
     p->stats_tile = 128;    // one partial per (pixel tile, pixel half)
+    p->gn_out = gn_ok;
+    if (a.gn_out) {         // third kernel function of the family: conv_ws_gn_kernel<TW> (t2 = 1)
+        p->t2 = 1;
+        p->lds += WS_GN;
+        return true;
+    }
     // the id names a family of two kernel functions: full-width nearest-x2 upsample convs run conv_ws_up_kernel<TW> (t1 = 1)
     conv_ws_up_select(a, p);
     return true;
@@ -837,9 +934,11 @@ int conv_ws_launch(const ConvPlan& p, hipStream_t st) {
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ws_gn_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    if (p.t0 == 32) hipLaunchKernelGGL(conv_ws_kernel<32>, dim3(p.grid), dim3(512), p.lds, st, b);
+    if (p.t2 == 1) hipLaunchKernelGGL(conv_ws_gn_kernel<16>, dim3(p.grid), dim3(512), p.lds, st, b);
+    else if (p.t0 == 32) hipLaunchKernelGGL(conv_ws_kernel<32>, dim3(p.grid), dim3(512), p.lds, st, b);
     else hipLaunchKernelGGL(conv_ws_kernel<16>, dim3(p.grid), dim3(512), p.lds, st, b);
     DXMI_CHECK_LAUNCH("dxmi_conv2d_fwd(ws)");
     return DXMI_OK;

@@ -244,23 +244,31 @@ class BlockStats:
     values per channel PAIR, over the pixels of partial p of the image (dxmi_conv_desc.gn_stats / dxmi_gn_block_stats).
     Travels with the tensor it describes; `groupnorm_silu(..., stats=...)` then runs as one streaming read + write."""
 
-    __slots__ = ("buf", "P")
+    __slots__ = ("buf", "P", "normed")
 
     def __init__(self, buf, P):
         self.buf, self.P = buf, P
+        self.normed = None      # conv2d(norm_next=...): the GroupNorm(+SiLU) of the tensor, written by its producer instead of it
 
 
 _STATS_P = {}
+GN_FLAG_WS = 4      # dxmi_conv_desc.gn_flags bit 2: the conv_ws family's fused GroupNorm output may serve the request
 
 
 def conv2d(x, pw, *, in1=None, bias=None, addvec=None, residual=None, stride=1, pad=None, pad_br=None, upsample=False,
-           act=ACT_NONE, out=None, out_nchw_f32=False, variant=0, mask_src=None, mask_slope=0.0, want_stats=False, fuse_gn=None):
+           act=ACT_NONE, out=None, out_nchw_f32=False, variant=0, mask_src=None, mask_slope=0.0, want_stats=False, fuse_gn=None,
+           gn_ws=False, norm_next=None):
     """x: NHWC bf16 [N,IH,IW,C0] (or NCHW fp32 [N,3,H,W] when pw.k27).
     want_stats: return (out, BlockStats | None) — the output's GroupNorm block statistics written by the conv's own epilogue
     where the selected kernel can (None otherwise: the caller falls back to block_stats() or the one-pass GroupNorm).
     fuse_gn = (gamma, beta, groups, eps, silu, keep_raw): return (out | None, y | None) with y = GroupNorm(+SiLU)(out) written
     by the conv's own epilogue where the selected kernel can (4x4 maps; y None otherwise: the caller normalises `out` itself);
-    keep_raw False drops the un-normalised tensor (out None) when y is produced."""
+    keep_raw False drops the un-normalised tensor (out None) when y is produced.
+    gn_ws (with fuse_gn, keep_raw False): also take the wave-specialised 3x3 kernel's fused output (GN_FLAG_WS: 16x16 maps; y is
+    bitwise groupnorm_silu(out, stats=...) of the two-launch path).
+    norm_next = (gamma, beta, groups, eps, silu), with want_stats: the GroupNorm that is the ONLY reader of the output.  Where the
+    wave-specialised kernel can (GN_FLAG_WS), it writes the statistics and, instead of the raw output, that normalisation: the
+    call returns (None, BlockStats) with BlockStats.normed = y; everywhere else it is the plain want_stats call."""
     _need_cuda(x, in1, bias, addvec, residual, out)
     k = pw.ksize
     if pad is None:
@@ -320,16 +328,24 @@ def conv2d(x, pw, *, in1=None, bias=None, addvec=None, residual=None, stride=1, 
             stats = BlockStats(torch.empty((N, P, Cout // 2, 2), dtype=torch.float32, device=x.device), P)
             d.gn_stats = stats.buf.data_ptr()
     d.gn_out, y = None, None
-    if fuse_gn is not None:
-        assert not want_stats
-        gamma, beta, groups, eps, silu, keep_raw = fuse_gn
+    assert norm_next is None or (fuse_gn is None and want_stats)
+    fuse = fuse_gn if norm_next is None else (tuple(norm_next) + (False,) if stats is not None else None)
+    if fuse is not None:
+        assert not want_stats or norm_next is not None
+        gamma, beta, groups, eps, silu, keep_raw = fuse
+        ws_too = bool(gn_ws) or norm_next is not None
         d.gn_groups = groups
-        d.gn_flags = int(bool(silu)) | (0 if keep_raw else 2)
+        d.gn_flags = int(bool(silu)) | (0 if keep_raw else 2) | (GN_FLAG_WS if ws_too else 0)
         key = ("gn", N, IH, IW, C0, C1, OH, OW, Cout, k, stride, pad, int(upsample), act, d.in_mode, d.out_mode, variant,
-               residual is not None, mask_src is not None, groups, bool(keep_raw))
+               residual is not None, mask_src is not None, groups, bool(keep_raw), ws_too, norm_next is not None)
         ok = _STATS_P.get(key)
         if ok is None:
-            ok = _STATS_P[key] = int(load().dxmi_conv2d_gn_fuse_supported(ctypes.byref(d)))
+            ok = int(load().dxmi_conv2d_gn_fuse_supported(ctypes.byref(d)))
+            if ok and norm_next is not None:      # ... and only that kernel's: it writes the statistics beside the fused output
+                d.gn_flags &= ~GN_FLAG_WS
+                ok = int(not load().dxmi_conv2d_gn_fuse_supported(ctypes.byref(d)))
+                d.gn_flags |= GN_FLAG_WS
+            _STATS_P[key] = ok
         if ok:
             assert gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.numel() == Cout and beta.numel() == Cout
             y = torch.empty((N, OH, OW, Cout), dtype=torch.bfloat16, device=x.device)
@@ -338,10 +354,13 @@ def conv2d(x, pw, *, in1=None, bias=None, addvec=None, residual=None, stride=1, 
         PROFILER.launch_conv(d)
     else:
         check(load().dxmi_conv2d_fwd(ctypes.byref(d), _stream()), "dxmi_conv2d_fwd")
-    if fuse_gn is not None:
-        return (out if (y is None or fuse_gn[5]) else None), y
     if stats is not None and stats.P > MAX_APPLY_PARTIALS:
         stats = fold_stats(stats)
+    if fuse_gn is not None:
+        return (out if (y is None or fuse_gn[5]) else None), y
+    if y is not None:           # norm_next was served: the raw tensor does not exist
+        stats.normed = y
+        return None, stats
     return (out, stats) if want_stats else out
 
 
@@ -375,6 +394,8 @@ class OpProfiler:
         cls = "conv_other" if kid >= 600000 else "conv1x1" if kid >= 500000 else "conv3x3" if kid >= 400000 else "conv_stem" if kid >= 300000 else ("conv1x1" if kid >= 200000 else ("conv3x3" if kid >= 30000 else "conv_other"))
         if kid == 400008 and d.gn_out:
             kid = 400009                                  # conv_ws8_kernel<true> (bench.py kernel_name)
+        if kid == 400016 and d.gn_out:
+            kid = 400116                                  # conv_ws_gn_kernel<16>: GroupNorm time inside (printed as conv_ws_kernel<116>)
         self.bracket(cls, kid, flops, in_b + out_b + res_b + w_b,
                      lambda: check(lib.dxmi_conv2d_fwd(ctypes.byref(d), _stream()), "dxmi_conv2d_fwd"))
 

@@ -218,6 +218,7 @@ class Model(PackedWeights, nn.Module):
     FUSE_GN_SHORTCUT = os.environ.get("DXMI_GN_SHORTCUT", "1") != "0"   # a changing ResnetBlock's norm1 and nin_shortcut from one read of its input (ops.groupnorm_silu_shortcut)
     FUSE_ATTN_BLOCK = True            # the 16x16 AttnBlocks as ONE launch (norm, q|k|v, attention, proj_out, residual: ops.attn_block)
     FUSE_GN_SMALL = True              # norm2 of the 4x4 ResnetBlocks from conv1's epilogue (instance override: A-B timing)
+    FUSE_GN_STREAM = os.environ.get("DXMI_GN_STREAM", "1") != "0"   # norm2 of the 16x16 ResnetBlocks from conv1's tile end (conv_ws_gn_kernel), bitwise the two-launch result
     STREAM_GN_MIN_HW = 256            # instance attribute override (tests / A-B timing): 1 << 30 = one-pass GroupNorm everywhere
 
     def _conv_s(self, x, pw, **kw):
@@ -257,6 +258,12 @@ class Model(PackedWeights, nn.Module):
             sh = None
             if a is None and stream:
                 sh = ops.block_stats(h)
+        elif stream and self.FUSE_GN_STREAM:
+            # streamed maps: where conv1's tile holds whole images and groups (16x16) it leaves normalised (sh.normed), h is never
+            # written; elsewhere the call is the statistics-writing conv of the branch below
+            h, sh = ops.conv2d(a0, pk[id(b), "conv1"], bias=b.conv1.bias, addvec=tp[:, off:off + b.out_channels], want_stats=True,
+                               norm_next=(b.norm2.weight, b.norm2.bias, 32, 1e-6, True))
+            a = sh.normed if sh is not None else None
         else:
             h, sh = ops.conv2d(a0, pk[id(b), "conv1"], bias=b.conv1.bias, addvec=tp[:, off:off + b.out_channels], want_stats=True)
         if a is None:

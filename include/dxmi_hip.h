@@ -118,7 +118,12 @@ typedef struct dxmi_conv_desc {
     const float* gn_beta;    /* [Cout] */
     float        gn_eps;
     int32_t      gn_groups;  /* Cout / gn_groups must be 8 */
-    int32_t      gn_flags;   /* bit 0: SiLU after the affine; bit 1: do not write `out` (the raw tensor has no other reader) */
+    int32_t      gn_flags;   /* bit 0: SiLU after the affine; bit 1: do not write `out` (the raw tensor has no other reader);
+                                bit 2: the caller also takes the wave-specialised 3x3 kernel's fused output (conv_ws_gn_kernel: 16x16
+                                maps, Cout % 128 == 0, no residual / mask / upsample, together with bit 1).  There gn_out is
+                                bitwise what dxmi_groupnorm_apply gives on the conv's output and gn_stats (block statistics in
+                                fp32, a pair's partials in partial order, a group's pairs in channel order).  Without bit 2 the
+                                selection and dxmi_conv2d_gn_fuse_supported answer as they did before the bit existed. */
 } dxmi_conv_desc;
 
 int dxmi_conv2d_fwd(const dxmi_conv_desc* d, void* stream);
