@@ -26,7 +26,6 @@ same state dict) and torch's clip_grad_norm_ stand in, and use_graph=True is ref
 """
 import json
 import os
-import types
 
 import torch
 import torch.distributed as dist
@@ -40,6 +39,7 @@ from dxmi_hip.optim import Adam
 from ..cm.karras_diffusion import _HostTable
 from ..cm.nn import update_ema, update_ema_rates
 from ..cm.train_util import find_ema_checkpoint, parse_resume_step_from_filename
+from .unet_small_train import train_backward, train_forward
 from .var_sampler import calc_diffusion_hyperparams
 
 
@@ -55,23 +55,21 @@ def mean_flat(x):
 
 
 class _DDPMLossFn(torch.autograd.Function):
-    """prep -> U-Net forward (_UNetFn) -> per-sample loss, as one node; the U-Net's tape lives on this node's ctx."""
+    """prep -> U-Net forward (models.DxMI.unet_small_train) -> per-sample loss, as one node."""
 
     @staticmethod
     def forward(ctx, net, x_start, noise, t, tab, *params):
-        from .unet_small_train import _UNetFn
-        x_t, tf = ops.ddpm_prep(x_start, noise, t, tab)
-        eps = _UNetFn.forward(ctx, net, x_t, tf, *params)
+        eps, ctx.tape = train_forward(net, *ops.ddpm_prep(x_start, noise, t, tab))
         ctx.eps, ctx.noise = eps, noise
         return ops.ddpm_loss_fwd(eps, noise)
 
     @staticmethod
     def backward(ctx, g):
-        from .unet_small_train import _UNetFn
         d_eps = ops.ddpm_loss_bwd(g.detach().float().contiguous(), ctx.eps, ctx.noise)
         ctx.eps = None
-        grads = _UNetFn.backward(ctx, d_eps)      # (net, x, t, *params): x is x_start's slot here, which takes no gradient
-        return (None,) * 5 + tuple(grads[3:])
+        grads = train_backward(ctx.tape, d_eps)
+        ctx.tape = None
+        return (None,) * 5 + grads
 
 
 class DDPMSchedule(_HostTable):
@@ -124,8 +122,7 @@ class DDPMSchedule(_HostTable):
         else:
             x_t, tf = ops.ddpm_prep(x_start, noise, t, tab)
             if net.training and net.dropout_p > 0:      # dropout is part of the loss in train mode: the training forward applies it
-                from .unet_small_train import _UNetFn
-                eps = _UNetFn.forward(types.SimpleNamespace(), net, x_t, tf)
+                eps = train_forward(net, x_t, tf)[0]
             else:
                 eps = net.forward_inference(x_t, tf)
             mse = ops.ddpm_loss_fwd(eps, noise)

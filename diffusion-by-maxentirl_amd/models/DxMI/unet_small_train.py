@@ -3,24 +3,29 @@ models/DxMI/trainer.py:361-389 back-propagates the sampler loss through `sample_
 U-Net parameter; reference graph = torch autograd over models/DxMI/unet_small.py:292-332).
 
 One torch.autograd.Function wraps the network.  forward() is the inference program plus saved bf16
-NHWC activations (and one dropout seed per ResnetBlock in train mode); backward() walks it in reverse:
+NHWC activations (and one dropout seed per ResnetBlock in train mode) on a tape; backward() hands the
+tape to models/unet_bwd.py (the reverse walk with its skip-connection rule, head, projection-shortcut
+data gradient, stem, parameter order) and adds what is this net's own:
   conv data gradients   = the forward MFMA kernels on transpose-flipped weight fragments (stride-2:
                           over the zero-stuffed gradient; upsample: full-res gradient then 2x2 sum),
-                          with the skip-connection gradient fused as the epilogue residual;
-  conv weight gradients = MFMA pixel-GEMM (dxmi_conv2d_wgrad, also strided / upsampled / 1x1);
-  GroupNorm(+SiLU)      = dxmi_groupnorm_silu_bwd (dx split back into the two concat sources);
-  attention             = five batched MFMA GEMMs + softmax backward (dxmi_bgemm_bf16);
-  dropout               = dxmi_dropout_bf16 with the forward's seed (no stored mask);
-  temb MLP + temb_proj  = tiny dense layers: re-evaluated and differentiated with torch fp32 matmuls
-                          (<0.05 % of the FLOPs; plain library GEMMs).
-Parameter gradients are returned in `net.parameters()` order as fp32 tensors.
+                          with the shortcut gradient fused as the epilogue residual;
+  conv weight gradients = MFMA pixel-GEMM (ops.conv2d_wgrad, also strided / upsampled / 1x1);
+  GroupNorm(+SiLU)      = ops.groupnorm_silu_bwd (dx split back into the two concat sources);
+  attention             = ops.attention_bwd on the stacked qkv, one head; q / k / v are three convs,
+                          so their weight and bias gradients are row blocks of one wgrad_branch launch;
+  dropout               = ops.dropout with the forward's seed (no stored mask);
+  temb MLP + temb_proj  = dense backward on the HIP kernels (ops.linear_bwd, ops.silu_bwd), the
+                          pre-activations recomputed, every temb_proj as one concatenated operator.
+Parameter gradients are returned in `net.parameters()` order as fp32 tensors.  train_forward /
+train_backward / input_forward / input_backward / input_vjp keep the tape outside autograd.
 """
 import torch
 import torch.nn.functional as F
 
 from dxmi_hip import graph as _graph
 from dxmi_hip import ops
-from dxmi_hip.packs import WeightPacks
+
+from ..unet_bwd import Backward, pack_t, tape_api, up_sum, walk
 
 
 def _build_packs_t(net, ps):
@@ -43,10 +48,7 @@ def _build_packs_t(net, ps):
 
 
 def _pack_t(net):
-    """The transposed set of the net (dxmi_hip.packs.WeightPacks: cached on the net, refreshed with the parameters)."""
-    if net._packs_t is None:
-        net._packs_t = WeightPacks(net, _build_packs_t)
-    return net._packs_t.get()
+    return pack_t(net, _build_packs_t)
 
 
 class _UNetFn(torch.autograd.Function):
@@ -111,7 +113,6 @@ class _UNetFn(torch.autograd.Function):
                 tape.append(("push", None, len(hs)))
                 hs.append(hd)
         h = hs[-1]
-        tape.append(("mid_start", None, len(hs) - 1))
         h = res(net.mid.block_1, h, None)
         h = attn(net.mid.attn_1, h)
         h = res(net.mid.block_2, h, None)
@@ -135,43 +136,25 @@ class _UNetFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_eps):
-        net, tape = ctx.net, ctx.tape
-        pk, pkt = net.packed(), _pack_t(net)
-        grads = {}
-        N = d_eps.shape[0]
-        dev = d_eps.device
-        # input_only (input_vjp): the walk forms the data gradients alone: no weight, bias or embedding gradient is launched
-        params = not getattr(ctx, "input_only", False)
-        d_tp = torch.zeros((N, pk["tproj_bias"].numel()), dtype=torch.float32, device=dev) if params else None
+        net = ctx.net
+        bw = Backward(ctx, _build_packs_t)
+        pk, pkt, grads, params, conv_wb = bw.pk, bw.pkt, bw.grads, bw.params, bw.conv_wb
+        d_tp = torch.zeros((d_eps.shape[0], pk["tproj_bias"].numel()), dtype=torch.float32, device=d_eps.device) if params else None
 
-        def conv_wb(conv, x0, gy, k, x1=None, **kw):
-            if not params:
-                return
-            grads[conv.weight], grads[conv.bias] = ops.conv2d_wgrad(x0, gy, k, in1=x1, with_bias=True, **kw)
+        def gn_bwd(norm, xin, dy, **kw):
+            dx0, dx1, grads[norm.weight], grads[norm.bias] = ops.groupnorm_silu_bwd(xin, dy, norm.weight, norm.bias, **kw)
+            return dx0, dx1
 
         # ---- head: eps = conv_out(silu(gn(h_last)))
-        H = d_eps.shape[2]
-        d_pad = torch.zeros((N, H, H, 64), dtype=torch.bfloat16, device=dev)
-        d_pad[..., : d_eps.shape[1]] = d_eps.permute(0, 2, 3, 1).to(torch.bfloat16)
-        if params:
-            with ops.wgrad_branch((ctx.a_out, d_pad)):       # (captured step: a parallel branch, joined at the end of this backward)
-                wg = ops._conv2d_wgrad(ctx.a_out, d_pad, 3)
-                grads[net.conv_out.weight] = wg[: net.out_ch].contiguous()
-            grads[net.conv_out.bias] = d_eps.float().sum((0, 2, 3))
-        d_a = ops.conv2d(d_pad, pkt["conv_out"])
-        g, _, dg, db = ops.groupnorm_silu_bwd(ctx.h_last, d_a, net.norm_out.weight, net.norm_out.bias, silu=True)
-        grads[net.norm_out.weight], grads[net.norm_out.bias] = dg, db
+        g, _ = gn_bwd(net.norm_out, ctx.h_last, bw.head(net.conv_out, ctx.a_out, d_eps), silu=True)
 
-        gskip = {}
-
-        def res_bwd(entry, g, add0=None, add1=None):
+        def res_bwd(entry, g):
             _, b, x0, x1, a1, h, a2, mask = entry
             conv_wb(b.conv2, a2, g, 3)
             d_a2 = ops.conv2d(g, pkt[id(b), "conv2"])
             if mask is not None:
                 d_a2 = ops.dropout(d_a2, net.dropout_p, mask, out=d_a2)
-            d_h, _, dg2, db2 = ops.groupnorm_silu_bwd(h, d_a2, b.norm2.weight, b.norm2.bias, silu=True)
-            grads[b.norm2.weight], grads[b.norm2.bias] = dg2, db2
+            d_h, _ = gn_bwd(b.norm2, h, d_a2, silu=True)
             off = pk[id(b), "toff"]
             if params:
                 d_tp[:, off:off + b.out_channels] = ops.colsum_per_image(d_h)
@@ -179,26 +162,11 @@ class _UNetFn(torch.autograd.Function):
             d_a1 = ops.conv2d(d_h, pkt[id(b), "conv1"])
             if b.in_channels != b.out_channels:
                 sc_mod = b.conv_shortcut if b.use_conv_shortcut else b.nin_shortcut
-                k = sc_mod.weight.shape[-1]
-                conv_wb(sc_mod, x0, g, k, x1=x1)
-                dxg0, dxg1, dg1, db1 = ops.groupnorm_silu_bwd(x0, d_a1, b.norm1.weight, b.norm1.bias, in1=x1, add0=add0,
-                                                              add1=add1, silu=True)
-                C0 = x0.shape[3]
-                w = pkt[id(b), "short"]
-                # transposed fragments of the shortcut, split per concat source; cached with the other packs
-                w0t, w1t = net._packs_t.on_demand((id(b), "short_t", C0), lambda: (
-                    ops.pack_conv_weight(w[:, :C0].contiguous(), transpose_flip=True),
-                    ops.pack_conv_weight(w[:, C0:].contiguous(), transpose_flip=True) if x1 is not None else None))
-                d_x0 = ops.conv2d(g, w0t, residual=dxg0)
-                d_x1 = None
-                if x1 is not None:
-                    d_x1 = ops.conv2d(g, w1t, residual=dxg1)
-            else:
-                assert x1 is None
-                addin = g if add0 is None else g + add0
-                d_x0, d_x1, dg1, db1 = ops.groupnorm_silu_bwd(x0, d_a1, b.norm1.weight, b.norm1.bias, add0=addin, silu=True)
-            grads[b.norm1.weight], grads[b.norm1.bias] = dg1, db1
-            return d_x0, d_x1
+                conv_wb(sc_mod, x0, g, sc_mod.weight.shape[-1], x1=x1)
+                dxg0, dxg1 = gn_bwd(b.norm1, x0, d_a1, in1=x1, silu=True)
+                return bw.shortcut_dx((id(b), "short_t"), pkt[id(b), "short"], x0, x1, g, dxg0, dxg1)
+            assert x1 is None
+            return gn_bwd(b.norm1, x0, d_a1, add0=g, silu=True)
 
         def attn_bwd(entry, g):
             _, m, xa, hn, qkv, a = entry
@@ -214,111 +182,43 @@ class _UNetFn(torch.autograd.Function):
                         grads[conv.weight] = wq[j * C:(j + 1) * C].contiguous()
                         grads[conv.bias] = bq[j * C:(j + 1) * C].contiguous()
             d_hn = ops.conv2d(d_qkv, pkt[id(m), "qkv"])
-            d_x, _, dgn, dbn = ops.groupnorm_silu_bwd(xa, d_hn, m.norm.weight, m.norm.bias, add0=g, silu=False)
-            grads[m.norm.weight], grads[m.norm.bias] = dgn, dbn
-            return d_x
+            return gn_bwd(m.norm, xa, d_hn, add0=g, silu=False)[0]
 
-        # ---- reverse walk
-        i = len(tape) - 1
-        while i >= 0:
-            e = tape[i]
-            kind = e[0]
-            if kind == "up":
-                _, us, xin = e
-                conv_wb(us.conv, xin, g, 3, upsample=True)
-                d_hi = ops.conv2d(g, pkt[id(us), "conv"])
-                g = ops.pool_act(d_hi, True, ops.ACT_NONE)
-                g.mul_(4.0)  # mean -> sum over the 4 replicated pixels (exact in bf16)
-            elif kind == "attn":
-                g = attn_bwd(e, g)
-            elif kind == "res":
-                x1 = e[3]
-                if x1 is not None:   # up-path block: (h, skip) concat; the preceding "skip" entry names the hs index
-                    d_x0, d_x1 = res_bwd(e, g)
-                    assert tape[i - 1][0] == "skip"
-                    gskip[tape[i - 1][2]] = d_x1
-                    g = d_x0
-                    i -= 1
-                else:
-                    g, _ = res_bwd(e, g)  # down / mid block
-            elif kind == "down":
-                _, ds, xin = e
-                conv_wb(ds.conv, xin, g, 3, stride=2, pad=0)
-                g = ops.conv2d(g, pkt[id(ds), "conv"], pad=2, pad_br=0, upsample=2)
-            elif kind == "push":
-                # h was stored as hs[idx]: the up path may have consumed it as a skip
-                idx = e[2]
-                if idx in gskip:
-                    g = g + gskip.pop(idx)
-            elif kind == "mid_start":
-                pass
-            i -= 1
-        # hs[0] = conv_in output: add its skip gradient, then the stem conv
-        if 0 in gskip:
-            g = g + gskip.pop(0)
+        def up_bwd(entry, g):
+            _, us, xin = entry
+            conv_wb(us.conv, xin, g, 3, upsample=True)
+            return up_sum(ops.conv2d(g, pkt[id(us), "conv"]))
+
+        def down_bwd(entry, g):
+            _, ds, xin = entry
+            conv_wb(ds.conv, xin, g, 3, stride=2, pad=0)
+            return ops.conv2d(g, pkt[id(ds), "conv"], pad=2, pad_br=0, upsample=2)
+
+        dx = bw.stem(net.conv_in, ctx.x, walk(ctx.tape, g, res_bwd, attn_bwd, up_bwd, down_bwd), ctx.needs_input_grad[1])
         if params:
-            grads[net.conv_in.bias] = ops.colsum(g)
-            grads[net.conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
-        dx = None
-        if ctx.needs_input_grad[1]:
-            conv_in_t = net._packs_t.on_demand("conv_in_t", lambda: ops.pack_conv_weight(net.conv_in.weight, transpose_flip=True))
-            dx = ops.conv2d(g, conv_in_t, out_nchw_f32=True)
-        if not params:
-            return (None, dx, None)
-
-        # ---- temb MLP + all temb_proj layers (reference unet_small.py:296-299, :123): dense backward on the HIP kernels
-        # (ops.linear_bwd: transposed-pack linear for dx, the 1x1 weight-gradient kernel for dW), pre-activations recomputed
-        blocks = list(net._resblocks())
-        d0, d1 = net.temb.dense
-        e0 = ops.linear(ctx.emb, pk["dense0"], d0.bias)                        # pre-activation of dense[0]
-        a0 = F.silu(e0)
-        e1 = ops.linear(a0, pk["dense1"], d1.bias)
-        s_t = F.silu(e1)
-        tproj_t = net._packs_t.on_demand("tproj_t", lambda: ops.pack_conv_weight(torch.cat([b.temb_proj.weight for b in blocks], 0),
-                                                                                 transpose_flip=True))
-        dense1_t = net._packs_t.on_demand("dense1_t", lambda: ops.pack_conv_weight(d1.weight, transpose_flip=True))
-        ds, dw_cat, db_cat = ops.linear_bwd(s_t, d_tp, tproj_t)
-        off = 0
-        for b in blocks:
-            grads[b.temb_proj.weight] = dw_cat[off:off + b.out_channels]
-            grads[b.temb_proj.bias] = db_cat[off:off + b.out_channels]
-            off += b.out_channels
-        de1 = ops.silu_bwd(e1, ds)
-        da0, grads[d1.weight], grads[d1.bias] = ops.linear_bwd(a0, de1, dense1_t)
-        de0 = ops.silu_bwd(e0, da0)
-        _, grads[d0.weight], grads[d0.bias] = ops.linear_bwd(ctx.emb, de0, None, need_dx=False)
-
-        ops.wgrad_join()
-        out = [None, dx, None]
-        for prm in net.parameters():
-            out.append(grads.get(prm))
-        return tuple(out)
+            # ---- temb MLP + all temb_proj layers (reference unet_small.py:296-299, :123): dense backward on the HIP kernels
+            # (ops.linear_bwd: transposed-pack linear for dx, the 1x1 weight-gradient kernel for dW), pre-activations recomputed
+            blocks = list(net._resblocks())
+            d0, d1 = net.temb.dense
+            e0 = ops.linear(ctx.emb, pk["dense0"], d0.bias)                        # pre-activation of dense[0]
+            a0 = F.silu(e0)
+            e1 = ops.linear(a0, pk["dense1"], d1.bias)
+            s_t = F.silu(e1)
+            tproj_t = net._packs_t.on_demand("tproj_t", lambda: ops.pack_conv_weight(torch.cat([b.temb_proj.weight for b in blocks], 0),
+                                                                                     transpose_flip=True))
+            dense1_t = net._packs_t.on_demand("dense1_t", lambda: ops.pack_conv_weight(d1.weight, transpose_flip=True))
+            ds, dw_cat, db_cat = ops.linear_bwd(s_t, d_tp, tproj_t)
+            bw.dense_rows([b.temb_proj for b in blocks], dw_cat, db_cat)
+            de1 = ops.silu_bwd(e1, ds)
+            da0, grads[d1.weight], grads[d1.bias] = ops.linear_bwd(a0, de1, dense1_t)
+            de0 = ops.silu_bwd(e0, da0)
+            _, grads[d0.weight], grads[d0.bias] = ops.linear_bwd(ctx.emb, de0, None, need_dx=False)
+        return bw.finish(3, dx)
 
 
 def forward_with_grad(net, x, t):
     return _UNetFn.apply(net, x, t, *ops.fast_parameters(net))
 
 
-class _InputTape:
-    """What _UNetFn.forward keeps for its backward, held outside autograd in the place of the ctx (models.cm.unet_train._Tape's
-    role; this net's loss node keeps its tape on its own ctx, so there is no other tape class here).  input_only is read by the
-    backward with getattr: an autograd ctx has no such attribute, which means False."""
-    needs_input_grad = (False, True, False)
-    input_only = True
-
-
-def input_vjp(net, x, t, v):
-    """The network output F at (x, t) and g = d(v . F)/dx, the vector-Jacobian product of the network at v, with dropout off and no
-    parameter gradient formed (the probability-flow likelihood, models/DxMI/likelihood.py): the training forward with its tape,
-    then the backward walk with its weight, bias and embedding launches switched off.  g is the dx the full backward of
-    forward_with_grad returns, bit for bit.  The net's train / eval mode is left as it was."""
-    was_training = net.training
-    net.eval()
-    try:
-        with torch.no_grad():
-            tape = _InputTape()
-            out = _UNetFn.forward(tape, net, x, t)
-            g = _UNetFn.backward(tape, v.contiguous().float())[1]
-    finally:
-        net.train(was_training)
-    return out, g
+# the tape outside autograd (models.unet_bwd.tape_api): the loss node of models/DxMI/ddpm_train.py and the likelihood's input_vjp
+train_forward, train_backward, input_forward, input_backward, input_vjp = tape_api(_UNetFn, 3)

@@ -3,20 +3,24 @@ models/DxMI/trainer.py:693-746 back-propagates the sampler loss through OpenAIDi
 U-Net parameter; reference graph = torch autograd over models/cm/unet.py:761-790).
 
 One torch.autograd.Function wraps the network.  forward() is the inference program of models/cm/unet.py (this
-package) plus a tape of saved NHWC bf16 activations; backward() walks the tape in reverse:
+package) plus a tape of saved NHWC bf16 activations; backward() hands the tape to models/unet_bwd.py (the reverse walk with
+its skip-connection rule, head, projection-shortcut data gradient, stem, parameter order) and adds what is this net's own:
   conv data gradients   = the forward MFMA kernels on transpose-flipped weight fragments (ResBlock(up) / Upsample:
                           full-resolution gradient then a 2x2 sum; stride-2 Downsample: zero-stuffed gradient);
-  conv weight gradients = MFMA pixel-GEMM (dxmi_conv2d_wgrad), bias gradients = column sums;
-  GroupNorm32 (+FiLM scale-shift, +SiLU) = dxmi_groupnorm_generic_bwd, which also returns the per-image sums the
-                          scale / shift (= emb_layers output) gradients are formed from;
-  attention             = batched MFMA GEMMs + softmax backward (dxmi_bgemm_bf16), any head count;
-  mean pool / nearest x2 = each other's transposes (dxmi_upsample2x, dxmi_pool_act);
-  time_embed, label_emb, emb_layers = tiny dense layers, re-evaluated and differentiated with torch fp32 matmuls.
+  conv weight gradients = MFMA pixel-GEMM (ops.conv2d_wgrad), the bias gradient from the same launch;
+  GroupNorm32 (+FiLM scale-shift, +SiLU) = ops.groupnorm_generic_bwd on the forward's saved statistics, which also returns
+                          the per-image sums the scale / shift (= emb_layers output) gradients are formed from;
+  attention             = ops.attention_bwd on the single qkv, any head count, with the forward's saved log-sum-exp;
+  mean pool / nearest x2 = each other's transposes (unet_bwd.pool_t, unet_bwd.up_sum), in ResBlock(up / down) and in the
+                          Upsample / Downsample without conv;
+  time_embed, label_emb, emb_layers = dense backward on the HIP kernels (ops.linear_bwd, ops.silu_bwd), the pre-activations
+                          recomputed, every emb_layers Linear as one concatenated operator.
 Dropout (ResBlock out_layers: norm, SiLU, Dropout, conv; models/cm/unet.py) runs in train mode as the counter-hash kernel
 dxmi_dropout_bf16 on the conv2 input: one seed per ResBlock per forward, kept on the tape with p, and the backward applies the same
 (seed, p) to the gradient (no mask is stored).  With dropout 0, or in eval mode, nothing of it runs.  Inside a StepGraph capture
 (dxmi_hip/graph.py) every site's seed is a host input of the graph, so a replayed step draws the seeds an eager step would draw.
-Parameter gradients come back in net.parameters() order.
+Parameter gradients come back in net.parameters() order.  train_forward / train_backward / input_forward / input_backward /
+input_vjp keep the tape outside autograd.
 """
 import math
 import os
@@ -27,7 +31,8 @@ import torch.nn.functional as F
 
 from dxmi_hip import graph as _graph
 from dxmi_hip import ops
-from dxmi_hip.packs import WeightPacks
+
+from ..unet_bwd import Backward, pack_t, pool_t, tape_api, up_sum, walk
 
 
 def _build_packs_t(net, ps):
@@ -52,10 +57,7 @@ def _build_packs_t(net, ps):
 
 
 def _pack_t(net):
-    """The transposed set of the net (dxmi_hip.packs.WeightPacks: cached on the net, refreshed with the parameters)."""
-    if net._packs_t is None:
-        net._packs_t = WeightPacks(net, _build_packs_t)
-    return net._packs_t.get()
+    return pack_t(net, _build_packs_t)
 
 
 # Training forward: GroupNorm on the producers' block statistics (streaming apply) where the inference path uses them; 0 = the generic
@@ -63,20 +65,6 @@ def _pack_t(net):
 STREAM_GN = os.environ.get("DXMI_TRAIN_STREAM_GN", "1") == "1"
 # Training forward keeps the attention rows' log-sum-exp for the backward (dxmi_attention_fwd_lse / _bwd_lse); 0 = the backward recomputes it.
 SAVE_LSE = os.environ.get("DXMI_ATTN_SAVE_LSE", "1") == "1"
-
-
-def _up_sum(g):
-    """transpose of nearest x2: sum over each 2x2 block (mean * 4, exact in bf16)."""
-    out = ops.pool_act(g, True, ops.ACT_NONE)
-    out.mul_(4.0)
-    return out
-
-
-def _pool_t(g):
-    """transpose of the 2x2 mean pool: every gradient value to its 4 sources, times 1/4."""
-    out = ops.upsample2x(g)
-    out.mul_(0.25)
-    return out
 
 
 def _next_dropout_seed(net):
@@ -209,28 +197,17 @@ class _EDMUNetFn(torch.autograd.Function):
         a_out, ctx.s_out = gn_fwd(gn, h, sh, silu=True)
         out = ops.conv2d(a_out, pk["conv_out"], bias=net.out[2].bias, out_nchw_f32=True)
         ctx.net, ctx.tape, ctx.h_last, ctx.a_out, ctx.x, ctx.sinus, ctx.y = net, tape, h, a_out, x, sinus, y
-        ctx.emb_all_shape = emb_all.shape
         ctx.emb_all = emb_all
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         from .unet import ResBlock
-        net, tape = ctx.net, ctx.tape
-        pk, pkt = net.packed(), _pack_t(net)
-        grads = {}
-        N = d_out.shape[0]
-        dev = d_out.device
-        # input_only (input_vjp): the walk forms the data gradients alone: no weight, bias or embedding gradient is launched
-        params = not getattr(ctx, "input_only", False)
-        d_emb_all = torch.zeros(ctx.emb_all_shape, dtype=torch.float32, device=dev) if params else None
+        net = ctx.net
+        bw = Backward(ctx, _build_packs_t)
+        pk, pkt, grads, params, conv_wb = bw.pk, bw.pkt, bw.grads, bw.params, bw.conv_wb
         emb_all = ctx.emb_all
-
-        def conv_wb(conv, x0, gy, k, x1=None, **kw):
-            if not params:
-                return
-            dw, grads[conv.bias] = ops.conv2d_wgrad(x0, gy, k, in1=x1, with_bias=True, **kw)
-            grads[conv.weight] = dw.reshape(conv.weight.shape)
+        d_emb_all = torch.zeros(emb_all.shape, dtype=torch.float32, device=d_out.device) if params else None
 
         def gn_bwd(norm, xin, dy, *, in1=None, add0=None, add1=None, silu=True, scale_shift=None, fwd_stats=None):
             dx0, dx1, dg, db, d_ss = ops.groupnorm_generic_bwd(xin, dy, norm.weight, norm.bias, in1=in1, add0=add0, add1=add1,
@@ -239,18 +216,7 @@ class _EDMUNetFn(torch.autograd.Function):
             return dx0, dx1, d_ss
 
         # ---- head: out = conv(silu(gn(h_last)))
-        H, W = d_out.shape[2], d_out.shape[3]
-        d_pad = torch.zeros((N, H, W, 64), dtype=torch.bfloat16, device=dev)
-        d_pad[..., : d_out.shape[1]] = d_out.permute(0, 2, 3, 1).to(torch.bfloat16)
-        if params:
-            with ops.wgrad_branch((ctx.a_out, d_pad)):       # (captured step: a parallel branch, joined at the end of this backward)
-                wg = ops._conv2d_wgrad(ctx.a_out, d_pad, 3)
-                grads[net.out[2].weight] = wg[: net.out_channels].contiguous()
-            grads[net.out[2].bias] = d_out.float().sum((0, 2, 3))
-        d_a = ops.conv2d(d_pad, pkt["conv_out"])
-        g, _, _ = gn_bwd(net.out[0], ctx.h_last, d_a, fwd_stats=ctx.s_out)
-
-        gskip = {}
+        g, _, _ = gn_bwd(net.out[0], ctx.h_last, bw.head(net.out[2], ctx.a_out, d_out), fwd_stats=ctx.s_out)
 
         def res_bwd(entry, g):
             _, b, x0, x1, a1p, h, a2, s1, s2, drop = entry
@@ -271,26 +237,16 @@ class _EDMUNetFn(torch.autograd.Function):
             conv_wb(conv1, a1p, d_h, 3, upsample=b.up)
             d_a1 = ops.conv2d(d_h, pkt[id(b), "conv1"])
             if b.up:
-                d_a1 = _up_sum(d_a1)
+                d_a1 = up_sum(d_a1)
             elif b.down:
-                d_a1 = _pool_t(d_a1)
+                d_a1 = pool_t(d_a1)
             if (id(b), "skip") in pk:
                 sk = b.skip_connection
-                k = sk.weight.shape[-1]
-                conv_wb(sk, x0, g, k, x1=x1)
+                conv_wb(sk, x0, g, sk.weight.shape[-1], x1=x1)
                 dxg0, dxg1, _ = gn_bwd(gn1, x0, d_a1, in1=x1, fwd_stats=s1)
-                C0 = x0.shape[3]
-                w = sk.weight
-                w0t, w1t = net._packs_t.on_demand((id(b), "skip_t", C0), lambda: (      # transposed fragments per concat source
-                    ops.pack_conv_weight(w[:, :C0].contiguous(), transpose_flip=True),
-                    ops.pack_conv_weight(w[:, C0:].contiguous(), transpose_flip=True) if x1 is not None else None))
-                d_x0 = ops.conv2d(g, w0t, residual=dxg0)
-                d_x1 = None
-                if x1 is not None:
-                    d_x1 = ops.conv2d(g, w1t, residual=dxg1)
-                return d_x0, d_x1
+                return bw.shortcut_dx((id(b), "skip_t"), sk.weight, x0, x1, g, dxg0, dxg1)
             assert x1 is None
-            g_id = _up_sum(g) if b.up else (_pool_t(g) if b.down else g)
+            g_id = up_sum(g) if b.up else (pool_t(g) if b.down else g)
             d_x0, _, _ = gn_bwd(gn1, x0, d_a1, add0=g_id, fwd_stats=s1)
             return d_x0, None
 
@@ -306,52 +262,24 @@ class _EDMUNetFn(torch.autograd.Function):
             d_x, _, _ = gn_bwd(m.norm, xa, d_hn, add0=g, silu=False, fwd_stats=sn)
             return d_x
 
-        i = len(tape) - 1
-        while i >= 0:
-            e = tape[i]
-            kind = e[0]
-            if kind == "res":
-                d_x0, d_x1 = res_bwd(e, g)
-                g = d_x0
-                if e[3] is not None:     # first layer of an output block: (h, skip) concat
-                    assert tape[i - 1][0] == "skip"
-                    gskip[tape[i - 1][2]] = d_x1
-                    i -= 1
-            elif kind == "attn":
-                g = attn_bwd(e, g)
-            elif kind == "up":
-                _, m, xin = e
-                if m.use_conv:
-                    conv_wb(m.conv, xin, g, 3, upsample=True)
-                    g = _up_sum(ops.conv2d(g, pkt[id(m), "conv"]))
-                else:
-                    g = _up_sum(g)
-            elif kind == "down":
-                _, m, xin = e
-                if m.use_conv:
-                    conv_wb(m.op, xin, g, 3, stride=2, pad=1)
-                    g = ops.conv2d(g, pkt[id(m), "conv"], pad=1, pad_br=1, upsample=2)
-                else:
-                    g = _pool_t(g)
-            elif kind == "push":
-                idx = e[2]
-                if idx in gskip:
-                    g = g + gskip.pop(idx)
-            elif kind == "skip":
-                raise AssertionError("skip entry must directly precede the ResBlock that consumes it")
-            i -= 1
-        if 0 in gskip:
-            g = g + gskip.pop(0)
-        conv_in = net.input_blocks[0][0]
-        if params:
-            grads[conv_in.bias] = ops.colsum(g)
-            grads[conv_in.weight] = ops.stem_conv_wgrad(ctx.x, g)
-        dx = None
-        if ctx.needs_input_grad[1]:
-            conv_in_t = net._packs_t.on_demand("conv_in_t", lambda: ops.pack_conv_weight(conv_in.weight, transpose_flip=True))
-            dx = ops.conv2d(g, conv_in_t, out_nchw_f32=True)
+        def up_bwd(entry, g):
+            _, m, xin = entry
+            if not m.use_conv:
+                return up_sum(g)
+            conv_wb(m.conv, xin, g, 3, upsample=True)
+            return up_sum(ops.conv2d(g, pkt[id(m), "conv"]))
+
+        def down_bwd(entry, g):
+            _, m, xin = entry
+            if not m.use_conv:
+                return pool_t(g)
+            conv_wb(m.op, xin, g, 3, stride=2, pad=1)
+            return ops.conv2d(g, pkt[id(m), "conv"], pad=1, pad_br=1, upsample=2)
+
+        g = walk(ctx.tape, g, res_bwd, attn_bwd, up_bwd, down_bwd)
+        dx = bw.stem(net.input_blocks[0][0], ctx.x, g, ctx.needs_input_grad[1])
         if not params:
-            return (None, dx, None, None)
+            return bw.finish(4, dx)
 
         # ---- embedding graph (models/cm/unet.py:775-779, :249): time_embed MLP, label embedding, every emb_layers Linear as one
         # operator — dense backward on the HIP kernels (ops.linear_bwd), pre-activations recomputed
@@ -364,84 +292,20 @@ class _EDMUNetFn(torch.autograd.Function):
             emb = emb + net.label_emb.weight.detach()[ctx.y]
         s_e = F.silu(emb)
         ds, dw_cat, db_cat = ops.linear_bwd(s_e, d_emb_all, pkt["emb_t"])
-        off = 0
-        for b in blocks:
-            eo = b.emb_layers[1].out_features
-            grads[b.emb_layers[1].weight] = dw_cat[off:off + eo]
-            grads[b.emb_layers[1].bias] = db_cat[off:off + eo]
-            off += eo
+        bw.dense_rows([b.emb_layers[1] for b in blocks], dw_cat, db_cat)
         d_emb = ops.silu_bwd(emb, ds)
         if net.num_classes is not None:
             grads[net.label_emb.weight] = torch.zeros_like(net.label_emb.weight).index_add_(0, ctx.y, d_emb)
         da0, grads[l2.weight], grads[l2.bias] = ops.linear_bwd(a0, d_emb, pkt["te2_t"])
         de0 = ops.silu_bwd(e0, da0)
         _, grads[l0.weight], grads[l0.bias] = ops.linear_bwd(ctx.sinus, de0, None, need_dx=False)
-
-        ops.wgrad_join()
-        out = [None, dx, None, None]
-        for prm in net.parameters():
-            out.append(grads.get(prm))
-        return tuple(out)
+        return bw.finish(4, dx)
 
 
 def forward_with_grad(net, x, timesteps, y=None):
     return _EDMUNetFn.apply(net, x, timesteps, y, *ops.fast_parameters(net))
 
 
-class _Tape:
-    """What _EDMUNetFn.forward keeps for its backward, held outside autograd: it takes the place of the ctx for a caller that is an
-    autograd node of its own around the network (the loss nodes of models.cm.karras_diffusion), or that keeps no graph at all.
-    No input gradient is formed: such a caller differentiates the parameters only.  input_only (read by the backward with
-    getattr, so an autograd ctx, which has no such attribute, means False): the walk forms the data gradients alone."""
-    needs_input_grad = (False, False, False, False)
-    input_only = False
-
-
-def train_forward(net, x, timesteps, y=None):
-    """The training forward of `net` (dropout applied in train mode; net.dropout_seeds_used lists its seeds) outside autograd
-    -> (model output, tape).  Drop the tape where no backward follows."""
-    tape = _Tape()
-    return _EDMUNetFn.forward(tape, net, x, timesteps, y), tape
-
-
-def train_backward(tape, d_out):
-    """The backward of train_forward -> the gradients of net.parameters(), in that order."""
-    return tuple(_EDMUNetFn.backward(tape, d_out)[4:])
-
-
-class _InputTape(_Tape):
-    """The tape of input_vjp: the backward walks it for the input gradient alone."""
-    needs_input_grad = (False, True, False, False)
-    input_only = True
-
-
-def input_forward(net, x, timesteps, y=None):
-    """The first half of input_vjp -> (F, tape): the training forward with dropout off (eval mode, the net's own mode restored),
-    its tape kept for input_backward.  For a caller whose cotangent is known only after this forward (score identity distillation,
-    KarrasDenoiser.sid_generator_losses, needs both denoisers' outputs first)."""
-    was_training = net.training
-    net.eval()
-    try:
-        with torch.no_grad():
-            tape = _InputTape()
-            out = _EDMUNetFn.forward(tape, net, x, timesteps, y)
-    finally:
-        net.train(was_training)
-    return out, tape
-
-
-def input_backward(tape, v):
-    """The second half of input_vjp -> g = d(v . F)/dx for the tape of input_forward: the backward walk with its weight, bias and
-    embedding launches switched off.  A tape is walked once; drop it afterwards."""
-    with torch.no_grad():
-        return _EDMUNetFn.backward(tape, v.contiguous().float())[1]
-
-
-def input_vjp(net, x, timesteps, v, y=None):
-    """The network output F at (x, timesteps[, y]) and g = d(v . F)/dx, the vector-Jacobian product of the network at v, with
-    dropout off and no parameter gradient formed (the probability-flow likelihood, models/cm/likelihood.py): the training forward
-    with its tape, then the backward walk with its weight, bias and embedding launches switched off (input_forward, then
-    input_backward).  g is the dx the full backward of forward_with_grad returns, bit for bit.  The net's train / eval mode is left
-    as it was."""
-    out, tape = input_forward(net, x, timesteps, y)
-    return out, input_backward(tape, v)
+# the tape outside autograd (models.unet_bwd.tape_api): the loss nodes of models.cm.karras_diffusion, score identity distillation's
+# input_forward / input_backward on both denoisers and the likelihood's input_vjp
+train_forward, train_backward, input_forward, input_backward, input_vjp = tape_api(_EDMUNetFn, 4)
