@@ -16,7 +16,7 @@
 //
 // Reference: AttnBlock.forward models/DxMI/unet_small.py:175-187 (scale C^-0.5, softmax over
 // keys); QKVAttentionLegacy models/cm/unet.py:413-441.
-#include "conv_common.h"
+#include "ws_common.h"
 #include <stdlib.h>
 
 namespace {
@@ -437,10 +437,7 @@ __global__ __launch_bounds__(256, 2) void attention64_kernel(AttnArgs p) {
 //     b128 fragment reads of Q / K (16 rows with distinct r & 15 per lane group) and the transposing b64 reads of V
 //     (4 rows x 64 B per half wave) are both bank-conflict free on that one image;
 //   * the output tile goes back through the (free) ring so that a wave stores whole 512-byte rows.
-#define AT_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define AT_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define AT_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-__device__ __forceinline__ void at_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ int at_swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
 template <bool PROJ>
@@ -463,15 +460,15 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
             const int r = (wave * 4 + i) * 2 + drow;                       // row inside the block
             const int c = dslot ^ at_swz(r);
             const bf16* g = base + (size_t)((b & 3) * 64 + r) * C3 + choff + c * 8;
-            __builtin_amdgcn_global_load_lds(AT_GPTR(g), AT_LPTR(smem + slot * SLOT + (wave * 4 + i) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(smem + slot * SLOT + (wave * 4 + i) * 1024), 16, 0, 0);
         }
     };
     if (PROJ && wave == 0)      // bias[256] -> LDS behind the ring (1 KiB, oldest DMA of wave 0)
-        __builtin_amdgcn_global_load_lds(AT_GPTR(p.pbias + lane * 4), AT_LPTR(smem + 4 * SLOT), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(WS_GPTR(p.pbias + lane * 4), WS_LPTR(smem + 4 * SLOT), 16, 0, 0);
 #pragma unroll
     for (int b = 0; b < 4; ++b) issue_block(b, b);
     AT_WAIT_VM(0);
-    at_barrier();
+    lds_barrier();
     bf16x8 qf[16];      // B operand: lane = query, d = ks*16 + 8h + j
     {
         const int r = (wave & 1) * 32 + (lane & 31);
@@ -480,7 +477,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + (((ks * 2 + h) ^ sw) << 4));
     }
-    at_barrier();       // every wave holds its Q fragments: the four slots are free
+    lds_barrier();       // every wave holds its Q fragments: the four slots are free
 #pragma unroll
     for (int b = 0; b < 4; ++b) issue_block(4 + b, b);
 
@@ -490,7 +487,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
         AT_WAIT_VM(12);         // younger than K(kb): K(kb+1..3) and V(0..kb-1), four DMAs each
-        at_barrier();
+        lds_barrier();
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh) {
             f32x16 a16;
@@ -504,7 +501,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
             }
             s[kb * 2 + kh] = a16;
         }
-        at_barrier();           // every wave is done with K(kb): its slot takes V(kb)
+        lds_barrier();           // every wave is done with K(kb): its slot takes V(kb)
         issue_block(8 + kb, kb);
     }
 
@@ -547,7 +544,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
         for (int i = 0; i < 4; ++i) {
             const int f = wave * 4 + i;
             const char* g = reinterpret_cast<const char*>(p.wproj) + (size_t)((half * 2 + slot) * 32 + f) * 1024 + lane * 16;
-            __builtin_amdgcn_global_load_lds(AT_GPTR(g), AT_LPTR(smem + slot * SLOT + f * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(smem + slot * SLOT + f * 1024), 16, 0, 0);
         }
     };
 #pragma unroll
@@ -561,7 +558,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
             else if (vb == 2) AT_WAIT_VM(4);
             else AT_WAIT_VM(0);
         }
-        at_barrier();
+        lds_barrier();
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
             const int r0 = 16 * st + tr_krow, r1 = r0 + 8;
@@ -580,11 +577,11 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
             }
         }
         if (PROJ && vb < 2) {
-            at_barrier();       // every wave is done with V(vb): its slot takes weight fragments
+            lds_barrier();       // every wave is done with V(vb): its slot takes weight fragments
             issue_w(0, vb);
         }
     }
-    at_barrier();       // every wave is done with the V images: the ring becomes the output tile
+    lds_barrier();       // every wave is done with the V images: the ring becomes the output tile
     if constexpr (PROJ) {
         // ---- Y^T[cout][query] = Wp . O^T (+ bias + x): O^T stays in registers as the B operand — k-step j of the product takes
         // the lane's accumulator registers 8 (j & 1) .. + 7 of o[j >> 1] as they stand (channels 16 j + 8 (i >> 2) + 4 h + (i & 3)),
@@ -601,7 +598,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
             for (int i = 0; i < 8; ++i) {
                 const int r = 4 * i + rrow;
                 const bf16* g = xrows + (size_t)r * 256 + half * 128 + ((rslot ^ at_swz(r)) << 3);
-                __builtin_amdgcn_global_load_lds(AT_GPTR(g), AT_LPTR(rbase + i * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(rbase + i * 1024), 16, 0, 0);
             }
         };
         issue_res(0);
@@ -618,7 +615,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
             if (half == 0) AT_WAIT_VM(8);
             else if (p.gn_stats) AT_WAIT_VM(18);        // + the two statistics stores of half 0
             else AT_WAIT_VM(16);
-            at_barrier();
+            lds_barrier();
             f32x16 y[4];
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
@@ -631,7 +628,7 @@ __global__ __launch_bounds__(512, 1) void attention256_kernel(AttnArgs p) {
                 }
             }
             if (half == 0) {
-                at_barrier();       // every wave is done with the first half of the weights
+                lds_barrier();       // every wave is done with the first half of the weights
                 issue_w(1, 0);
                 issue_w(1, 1);
                 AT_WAIT_VM(8);      // the residual rows of half 0 are older than those 8

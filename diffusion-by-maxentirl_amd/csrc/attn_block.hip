@@ -34,7 +34,7 @@
 // Rounding points: x^ (bf16, as the GroupNorm launch stored it), Y~, P, Z (bf16 MFMA operands, fp32 accumulation), out (one
 // rounding).  q, k, v and the attention output are never rounded on their own: against the fp32 reference the block is no further
 // than the three-launch form (tests/test_hip_round5_kernels.py).
-#include "conv_common.h"
+#include "ws_common.h"
 #include <stdlib.h>
 
 #ifdef DXMI_AB_STAMPS
@@ -60,10 +60,7 @@ namespace {
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define AB_LDS_S16X4(p) ((__attribute__((address_space(3))) s16x4*)(p))
-#define AB_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define AB_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define AB_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-__device__ __forceinline__ void ab_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ int ab_swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
 // one ring step behind its barrier: MFMA, ring write + queue refill, then MFMA / ring read pairs
@@ -186,7 +183,7 @@ __global__ __launch_bounds__(512, 1) void attn_block256_kernel(AttnBlockArgs p) 
     for (int i = 0; i < 16; ++i) {
         const int r = wave * 32 + 2 * i + drow;
         const bf16* g = xn + (size_t)r * 256 + ((dslot ^ ab_swz(r)) << 3);
-        __builtin_amdgcn_global_load_lds(AB_GPTR(g), AB_LPTR(smem + (wave * 32 + 2 * i) * 512), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(smem + (wave * 32 + 2 * i) * 512), 16, 0, 0);
     }
     // Weight streams (G in phase 1, W' in phase 4): 16 slots of 8 fragments through a ring of three 8 KiB LDS slots, wave w moves
     // fragment w of every slot.  An LDS-DMA ring keeps 16 KB in flight against ~1 900 cycles of L2 -> LDS latency: 8.6 B / clk of the
@@ -243,13 +240,13 @@ __global__ __launch_bounds__(512, 1) void attn_block256_kernel(AttnBlockArgs p) 
         }
         auto pack2 = [](float lo, float hi) { return (uint64_t)__builtin_bit_cast(uint32_t, lo) | ((uint64_t)__builtin_bit_cast(uint32_t, hi) << 32); };
         if (tid < 128) {
-            const unsigned ta = (unsigned)reinterpret_cast<uintptr_t>(AB_LPTR(tabA + 2 * tid));
+            const unsigned ta = (unsigned)reinterpret_cast<uintptr_t>(WS_LPTR(tabA + 2 * tid));
             asm volatile("ds_write_b64 %0, %1\n\tds_write_b64 %0, %2 offset:1024\n\tds_write_b64 %0, %3 offset:2048\n\tds_write_b64 %0, %4 offset:3072"
                          :: "v"(ta), "v"(pack2(a[0], a[1])), "v"(pack2(b[0], b[1])), "v"(pack2(ag[0], ag[1])), "v"(pack2(bp[0], bp[1])) : "memory");
         }
     }
     AB_STAMP(1);
-    ab_barrier();
+    lds_barrier();
     AB_WAIT_VM(0);          // this wave's rows of x have landed (hipcc may order the AB_Q weight loads among the DMAs: no count is safe but 0)
 
     // ---- x^ of this wave's queries: B operand of phase 1 (lane = query, channels 16 ks + 8 h .. + 7), rounded to bf16 exactly
@@ -295,7 +292,7 @@ __global__ __launch_bounds__(512, 1) void attn_block256_kernel(AttnBlockArgs p) 
             // NEXT barrier: 1 MFMA between two barriers, 15 behind the second — the matrix pipe idled through every other barrier)
             __builtin_amdgcn_sched_barrier(0);
             if (i < 16) {
-                ab_barrier();                   // slot i is in the ring (written one step ago at the latest); everybody has slot i - 1 in registers
+                lds_barrier();                   // slot i is in the ring (written one step ago at the latest); everybody has slot i - 1 in registers
                 if (i + 2 < 16) store_w(i + 2);
                 if (i + 2 + AB_Q < 16) load_w(p.wG, i + 2 + AB_Q);
                 read_slot(i, fr[i & 1]);
@@ -329,7 +326,7 @@ __global__ __launch_bounds__(512, 1) void attn_block256_kernel(AttnBlockArgs p) 
         }
     }
     AB_STAMP(3);
-    ab_barrier();           // every wave's rows of x have landed (each waited for its own before phase 1) and the ring is free
+    lds_barrier();           // every wave's rows of x have landed (each waited for its own before phase 1) and the ring is free
 
     // ---- phase 2: S^T[key][query] = x . Y~^T, 8 tiles of 32 keys; logits arrive in the log2 domain (scale log2 e folded into G)
     f32x16 s[8];
@@ -421,7 +418,7 @@ __global__ __launch_bounds__(512, 1) void attn_block256_kernel(AttnBlockArgs p) 
     store_w(1);
     load_w(p.wP, AB_Q);
     load_w(p.wP, AB_Q + 1);
-    ab_barrier();           // every wave is done with x as K and V: a wave's own rows become its output tile
+    lds_barrier();           // every wave is done with x as K and V: a wave's own rows become its output tile
 
     // ---- phase 4: y^T[cout][query] = W' Z^T; out = y + b' + x in place in the wave's rows of the image
     {
@@ -432,7 +429,7 @@ __global__ __launch_bounds__(512, 1) void attn_block256_kernel(AttnBlockArgs p) 
         for (int i = 0; i <= 16; ++i) {
             __builtin_amdgcn_sched_barrier(0);
             if (i < 16) {
-                ab_barrier();
+                lds_barrier();
                 if (i + 2 < 16) store_w(i + 2);
                 if (i + 2 + AB_Q < 16) load_w(p.wP, i + 2 + AB_Q);
                 read_slot(i, fr[i & 1]);

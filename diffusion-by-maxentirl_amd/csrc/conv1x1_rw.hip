@@ -26,15 +26,12 @@
 // stream walk the same tiles, so they split each chunk's 64 pixels between them (64 / CT each): every input element is normalised
 // and stored exactly once.  The chunk's 1 KB slice of the table rides the ring as a fifth DMA per wave (256 B each).  The y stores
 // are vector-memory ops too: each chunk wait below also counts those issued after the awaited chunk's DMAs.
-#include "conv_common.h"
+#include "ws_common.h"
 #include "gn_common.h"
 
 namespace {
 
-#define RW_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define RW_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define RW_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-__device__ __forceinline__ void rw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int RW_CHUNK = 64 * 256;      // 64 pixels x 128 channels bf16
 constexpr int RW_RO = 64 * 256;         // 64 pixels x 128 couts bf16 (4 KB per wave)
@@ -115,13 +112,13 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
         const int coff = first ? cbase : cbase - p.C0;
         if constexpr (GN) {          // the chunk's table slice: wave w moves its bytes 256 w .. 256 w + 255, 4 per lane
             const int n = (int)P0 / q.HW;
-            __builtin_amdgcn_global_load_lds(RW_GPTR(q.ab + ((size_t)n * (NCH * 128) + cbase) * 2 + wave * 64 + lane),
-                                             RW_LPTR(tbl + slot * RW_TBL + wave * 256), 4, 0, 0);
+            __builtin_amdgcn_global_load_lds(WS_GPTR(q.ab + ((size_t)n * (NCH * 128) + cbase) * 2 + wave * 64 + lane),
+                                             WS_LPTR(tbl + slot * RW_TBL + wave * 256), 4, 0, 0);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            __builtin_amdgcn_global_load_lds(RW_GPTR(src + (P0 + dpx[u]) * Cs + coff + ds8[u]),
-                                             RW_LPTR(ring + slot * RW_CHUNK + (wave * 4 + u) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(WS_GPTR(src + (P0 + dpx[u]) * Cs + coff + ds8[u]),
+                                             WS_LPTR(ring + slot * RW_CHUNK + (wave * 4 + u) * 1024), 16, 0, 0);
     };
     // wave-private output / residual slice: pixel row = 64 B = 4 slots, cout piece c of pixel px in slot c ^ ((px >> 1) & 3);
     // instruction i (0..3) moves pixels 16 i .. 16 i + 15
@@ -137,7 +134,7 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
     auto issue_residual = [&](int tile) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds(RW_GPTR(p.residual + tile_off(tile, i)), RW_LPTR(ro + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(WS_GPTR(p.residual + tile_off(tile, i)), WS_LPTR(ro + i * 1024), 16, 0, 0);
     };
 
     // ---- prologue: residual of tile 0, then chunks 0 .. R-2 of the stream
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(256, ((NCH > 3 || R > 4) ? 1 : 2)) void conv1x1_rw_
             else if (nbnd == 2) RW_WAIT_VM(NYOUNG + 2 * BOPS);
             else if (nbnd == 3) RW_WAIT_VM(NYOUNG + 3 * BOPS);
             else RW_WAIT_VM(NYOUNG + 4 * BOPS);
-            rw_barrier();                        // every wave's pieces of chunk g landed; every wave is done with chunk g-1
+            lds_barrier();                        // every wave's pieces of chunk g landed; every wave is done with chunk g-1
             {
                 const int gi = g + R - 1;        // refill the slot chunk g-1 vacated
                 const int si = slot == 0 ? R - 1 : slot - 1;

@@ -17,14 +17,11 @@
 //   * Cout % 256 != 0 (multiples of 32): waves past the last cout keep moving data and meeting barriers, run the MFMAs on clamped
 //     fragments (a branch around them makes hipcc shuffle the accumulators between register files) and skip epilogue and stores;
 //   * bias through an LDS table, wave-private 4 KB output / residual slice, exact in-order vmcnt counts (conv1x1_rw_kernel's).
-#include "conv_common.h"
+#include "ws_common.h"
 
 namespace {
 
-#define R8_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define R8_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define R8_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-__device__ __forceinline__ void r8_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int R8_CHUNK = 64 * 256;      // 64 pixels x 128 channels bf16
 constexpr int R8_RMAX = 6;              // ring slots (fewer when a tile has fewer chunks: at most one tile boundary inside the ring)
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_rw8_kernel(ConvArgs p) {
             int ch = c * 128 + (((lane & 15) ^ (dpx & 15)) << 3);
             if (TAIL) ch = ch < K - 8 ? ch : K - 8;              // the empty half of the last chunk: any valid address
             const bf16* g = ch < p.C0 ? p.in0 + (P0 + dpx) * p.C0 + ch : p.in1 + (P0 + dpx) * p.C1 + (ch - p.C0);
-            __builtin_amdgcn_global_load_lds(R8_GPTR(g), R8_LPTR(ring + slot * R8_CHUNK + (wave * 2 + u) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(ring + slot * R8_CHUNK + (wave * 2 + u) * 1024), 16, 0, 0);
         }
     };
     // wave-private output / residual slice: pixel row = 64 B = 4 slots, cout piece c of pixel px in slot c ^ ((px >> 1) & 3);
@@ -92,7 +89,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_rw8_kernel(ConvArgs p) {
     auto issue_residual = [&](int tile) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds(R8_GPTR(p.residual + tile_off(tile, i)), R8_LPTR(ro + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(WS_GPTR(p.residual + tile_off(tile, i)), WS_LPTR(ro + i * 1024), 16, 0, 0);
     };
 
     // ---- prologue: residual of tile 0, then chunks 0 .. R-2 of the stream
@@ -122,7 +119,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_rw8_kernel(ConvArgs p) {
             if (g + R - 2 >= gtot) R8_WAIT_VM(0);
             else if (!bnd) R8_WAIT_VM(NYOUNG);
             else R8_WAIT_VM(NYOUNG + BOPS);
-            r8_barrier();                        // every wave's pieces of chunk g landed; every wave is done with chunk g-1
+            lds_barrier();                        // every wave's pieces of chunk g landed; every wave is done with chunk g-1
             {
                 const int gi = g + R - 1;        // refill the slot chunk g-1 vacated
                 const int si = slot == 0 ? R - 1 : slot - 1;

@@ -10,18 +10,15 @@
 // kernels use (the 16x16x32 A fragment is a lane subset of the 32x32x16 fragments).  Each wave then runs 72
 // v_mfma_f32_16x16x32_bf16 over its 32 pixels (one tile row) with B fragments read by ds_read_b128 at a per-lane base plus
 // a compile-time offset.  Pixel rows are 256 B = 16 slots of 16 B; channel piece s of halo pixel hp sits in slot s ^ (hp & 15).
-#include "conv_common.h"
+#include "ws_common.h"
 
 namespace {
-
-#define HD_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define HD_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int HD_TH = 4;                                          // tile rows (one per wave): 51 KB of LDS, two workgroups per CU (register-limited)
 constexpr int HD_HP = 34, HD_HH = HD_TH + 2, HD_PIX = HD_HP * HD_HH;     // halo pitch / rows / pixels
 constexpr int HD_BLOCKS = (HD_PIX + 3) / 4;                      // 1-KiB DMA blocks (4 pixels each)
 
-__device__ uint4 hd_zero16 = {0u, 0u, 0u, 0u};
+WS_ZERO_PAGE(hd_zero16);
 
 __global__ __launch_bounds__(256, 2) void conv_head_kernel(ConvArgs p) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -39,7 +36,7 @@ __global__ __launch_bounds__(256, 2) void conv_head_kernel(ConvArgs p) {
         const int s = (lane & 15) ^ (hp & 15);
         const bool ok = hp < HD_PIX && iy >= 0 && ix >= 0 && iy < p.IH && ix < p.IW;
         const void* g = ok ? (const void*)(p.in0 + (((size_t)n * p.IH + iy) * p.IW + ix) * 128 + s * 8) : (const void*)&hd_zero16;
-        __builtin_amdgcn_global_load_lds(HD_GPTR(g), HD_LPTR(smem + b * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(smem + b * 1024), 16, 0, 0);
     }
     // ---- weight fragments: A of (tap t, chunk c) for couts 0..15: lane (co = lane & 15, channel group kg = lane >> 4) holds
     // lanes co + 32 (kg & 1) of the packed 32x32x16 fragment of k-step 2c + (kg >> 1), cout block 0

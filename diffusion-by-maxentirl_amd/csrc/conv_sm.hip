@@ -24,7 +24,7 @@
 //
 // Scope: 3x3 / stride 1 / pad 1, no upsample, 4x4 or 8x8 maps, NHWC bf16 in (virtual concat) and out, C0 % 32 == 0,
 // C1 % 32 == 0, Cout % 32 == 0, >= 5 chunks, bias / temb / residual / linear activation.  Everything else: conv_ws8 / conv_pipe.
-#include "conv_common.h"
+#include "ws_common.h"
 #include <stdlib.h>
 
 namespace {
@@ -45,32 +45,7 @@ struct SmCfg {
     static constexpr int LDS = R * SLOT + RES + TB;
 };
 
-__device__ uint4 sm_zero16 = {0u, 0u, 0u, 0u};   // DMA source of out-of-range images and absent bias / temb rows
-
-#define SM_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define SM_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-__device__ __forceinline__ void sm_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n <= 30, rounded DOWN to an even count (waits for more, never less)
-__device__ __forceinline__ void sm_wait_vm(int n) {
-    switch (n >> 1) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-    }
-}
+WS_ZERO_PAGE(sm_zero16);   // DMA source of out-of-range images and absent bias / temb rows
 
 // ML = log2(map width): 2 (4x4, 8 images per tile) or 3 (8x8, 2 images per tile); NL loader waves behind the 4 MFMA waves.
 // Roles are split as in conv_ws.hip: a DMA costs its wave 60-185 cycles of ISSUE, so a wave that both loads and computes spends
@@ -153,8 +128,8 @@ __global__ __launch_bounds__(256 + 64 * NL) void conv_sm_kernel(ConvArgs p) {
                 const int f = l + 8 * k;
                 if (f < Cfg::NWP) {
                     const int tk = f / CBT, cb = f % CBT;
-                    __builtin_amdgcn_global_load_lds(SM_GPTR(wc + (size_t)(tk >> 1) * tap_stride + (size_t)(tk & 1) * ks_stride + cb * 1024),
-                                                     SM_LPTR(slot + f * 1024), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(wc + (size_t)(tk >> 1) * tap_stride + (size_t)(tk & 1) * ks_stride + cb * 1024),
+                                                     WS_LPTR(slot + f * 1024), 16, 0, 0);
                 }
             }
             {
@@ -162,14 +137,14 @@ __global__ __launch_bounds__(256 + 64 * NL) void conv_sm_kernel(ConvArgs p) {
                 const bool first = cbase < p.C0;
                 const char* src = first ? in0_t + cbase * 2 + in_off0 : in1_t + (cbase - p.C0) * 2 + in_off1;
                 if (!img_ok) src = zero_page;
-                __builtin_amdgcn_global_load_lds(SM_GPTR(src), SM_LPTR(slot + SM_WB + l * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(src), WS_LPTR(slot + SM_WB + l * 1024), 16, 0, 0);
             }
             if (ic == nchunks - 1) {
                 if (has_res) {
 #pragma unroll
                     for (int k = 0; k < CBT; ++k) {
                         const char* src = n0 + res_img[k] < p.N ? res_t + res_off[k] : zero_page;
-                        __builtin_amdgcn_global_load_lds(SM_GPTR(src), SM_LPTR(resb + (l + 8 * k) * 1024), 16, 0, 0);
+                        __builtin_amdgcn_global_load_lds(WS_GPTR(src), WS_LPTR(resb + (l + 8 * k) * 1024), 16, 0, 0);
                     }
                 }
                 if (l < NTP) {
@@ -177,7 +152,7 @@ __global__ __launch_bounds__(256 + 64 * NL) void conv_sm_kernel(ConvArgs p) {
                     if (trow == 0) { if (p.bias) src = reinterpret_cast<const char*>(p.bias + cot * MT + tcol); }
                     else if (trow <= IMGS && p.addvec && n0 + trow - 1 < p.N)
                         src = reinterpret_cast<const char*>(p.addvec + (size_t)(n0 + trow - 1) * p.addvec_ld + cot * MT + tcol);
-                    __builtin_amdgcn_global_load_lds(SM_GPTR(src), SM_LPTR(reinterpret_cast<char*>(tb) + l * 1024), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(src), WS_LPTR(reinterpret_cast<char*>(tb) + l * 1024), 16, 0, 0);
                 }
             }
             if (++ic == nchunks) {
@@ -198,8 +173,8 @@ __global__ __launch_bounds__(256 + 64 * NL) void conv_sm_kernel(ConvArgs p) {
         for (int gc = 0; gc < total; ++gc) {
             // this loader's pieces of chunk gc have landed when at most the pieces of the younger issued chunks are outstanding
             // (their ordinary count: the extra pieces of a tile's last chunk only make this wait for a little more)
-            sm_wait_vm((issued - 1 - gc) * NW);
-            sm_barrier();                       // B_gc: chunk gc landed; the MFMA waves are done reading chunk gc - 1
+            ws_wait_vm<26>((issued - 1 - gc) * NW);
+            lds_barrier();                       // B_gc: chunk gc landed; the MFMA waves are done reading chunk gc - 1
             // chunks up to gc + R - 1 may be in the ring now (the slot of chunk gc - 1 is free)
 #pragma unroll 1
             for (int k = 0; k < 2 && issued < total && issued < gc + SM_R; ++k) issue_next();
@@ -244,7 +219,7 @@ __global__ __launch_bounds__(256 + 64 * NL) void conv_sm_kernel(ConvArgs p) {
     }
     int c = 0, ti = 0;
     for (int gc = 0; gc < total; ++gc) {
-        sm_barrier();                           // B_gc
+        lds_barrier();                           // B_gc
         const char* const slot = smem + (gc % SM_R) * SM_SLOT;
         const char* const ab = slot + lane * 16;
         // operand reads run AH taps ahead of the MFMAs that consume them (left to itself hipcc emits read, wait, MFMA per

@@ -17,7 +17,7 @@
 //
 // Replaces autograd's conv weight gradient for models/modules.py:71-101,142-145 and
 // models/DxMI/unet_small.py convs (reference: torch.nn.Conv2d backward).
-#include "conv_common.h"
+#include "ws_common.h"
 #include <stdlib.h>
 
 namespace {
@@ -251,9 +251,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs p) {
 //   * MFMA waves: the transposing reads run four (k-step, tap) pairs ahead of the MFMAs through a rolling window of fragments
 //     (the double-buffered k-step of the kernel above needs 368 registers; eight waves per CU leave 256).
 // Scope: stride 1 (optionally nearest x2 upsampled input), tile rows of >= 8 pixels (maps >= 8x8); other shapes: the kernel above.
-#define WG_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define WG_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-__device__ uint4 wg_zero16 = {0u, 0u, 0u, 0u};
+WS_ZERO_PAGE(wg_zero16);
 
 template <int KS>
 __global__ __launch_bounds__(512) void conv_wgrad_ws_kernel(WgradArgs p, const char* __restrict__ zero_page, int xpieces, int buf_bytes) {
@@ -313,7 +311,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_ws_kernel(WgradArgs p, const c
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const char* src = n0 + dy_sub[k] < p.N ? yb + dy_rel[k] : zero_page;
-                __builtin_amdgcn_global_load_lds(WG_GPTR(src), WG_LPTR(buf + (l + 4 * k) * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(src), WS_LPTR(buf + (l + 4 * k) * 1024), 16, 0, 0);
             }
             // border bits of this tile: rows above the map / below / left / right are zero padding
             const unsigned edge = (unsigned)(oy0 == 0) | ((unsigned)(oy0 + TH == p.OH) << 1) | ((unsigned)(ox0 == 0) << 2) | ((unsigned)(ox0 + TW == p.OW) << 3) | 16u;
@@ -322,7 +320,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_ws_kernel(WgradArgs p, const c
             for (int k = 0; k < MAXXP; ++k) {
                 if (k < nxw) {
                     const char* src = ((x_flag[k] & edge & 31u) || n0 + (int)(x_flag[k] >> 8) >= p.N) ? zero_page : xb + x_rel[k];
-                    __builtin_amdgcn_global_load_lds(WG_GPTR(src), WG_LPTR(buf + DYB + (l + 4 * k) * 1024), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(src), WS_LPTR(buf + DYB + (l + 4 * k) * 1024), 16, 0, 0);
                 }
             }
         };
@@ -460,7 +458,7 @@ __global__ __launch_bounds__(768) void conv_wgrad1x1_b128_kernel(WgradArgs p) {
             for (int k = 0; k < 4; ++k) {
                 const int j = l + 8 * k;
                 const char* src = (j >> 3) < 2 ? yb + rel[k] : xb + rel[k];
-                __builtin_amdgcn_global_load_lds(WG_GPTR(src), WG_LPTR(buf + j * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(src), WS_LPTR(buf + j * 1024), 16, 0, 0);
             }
         };
         for (int it = 0; it < RING - 1 && it < ntile; ++it) issue_tile(it);

@@ -7,16 +7,12 @@
 // CU, persistent over (256-pixel, 128-cout) tiles, and the roles are split (each SIMD hosts one wave of each kind):
 //   waves 0-3  MFMA (v_mfma_f32_16x16x32_bf16): a 64-cout x 128-pixel accumulator tile each.  Operands come from LDS only —
 //              weight fragments from a 6-slot ring, input pixels from a double-buffered halo image — at per-lane bases plus
-//              compile-time offsets (no address arithmetic in the loop), with a half-step software pipeline: the reads of
-//              the next 16 MFMAs fly under the current 16.  No vector-memory instruction is ever issued, so nothing a mover
-//              does can stall them; the only waits are lgkmcnt for LDS reads and ONE barrier per GROUP of three (chunk, tap)
-//              steps (round 4: a barrier per step cost 11-15 % by itself).
-//   waves 4,5  weight loaders, register-staged (round 4): the ring is two groups of three slots; the fragments of group G + 1
-//              are written from registers (ds_write_b128) while the MFMA waves read group G, after having been requested two
-//              group steps earlier by plain global_load_dwordx4 (a `global_load_lds` costs its wave ~2x the issue time and
-//              takes twice the issue slots from the MFMA wave on its SIMD: tools/stage_probe.hip).  They also fetch the bias /
-//              temb table and, from the second tile on, the RESIDUAL tile (LDS DMA, one group step after the drain wave
-//              emptied the piece), and do the next tile's first group step in front of E1.
+//              compile-time offsets (no address arithmetic in the loop), in the half-step software pipeline of ws_k_pair
+//              (ws_common.h).  No vector-memory instruction is ever issued, so nothing a mover does can stall them; the only
+//              waits are lgkmcnt for LDS reads and ONE barrier per GROUP of three (chunk, tap) steps.
+//   waves 4,5  weight loaders: the register-staged stream of ws_common.h (WsWeightStream).  They also fetch the bias / temb
+//              table and, from the second tile on, the RESIDUAL tile (LDS DMA, one group step after the drain wave emptied
+//              the piece), and do the next tile's first group step in front of E1.
 //   wave 6     halo mover: the next 32-channel chunk's halo image (DMA, XOR-swizzled 16-byte slots instead of padding: a
 //              DMA writes 1 KiB linearly), three blocks per step.  Loads only, so its vmcnt(0) at a chunk end waits for
 //              nothing but the image.
@@ -33,7 +29,7 @@
 // Cout % 64 == 0 (half-empty last cout tile masked), an even number (>= 4) of 32-channel chunks, maps >= 16x16 (one image per 256-pixel tile); 8x8 maps: conv_ws8.hip.
 // Everything else stays on conv_pipe.hip.  Full-width nearest-x2 upsample convs (OW = 2 IW in {16, 32}) run the family's second
 // kernel function, conv_ws_up_kernel (conv_ws_up.hip): same plan kind, id and statistics layout.
-#include "conv_common.h"
+#include "ws_common.h"
 #include "gn_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -48,7 +44,7 @@ extern "C" int dxmi_debug_read_ws_stamps(void* dst, int bytes) {
 #define WS_STAMPED_BARRIER(idx)                                                                     \
     do {                                                                                            \
         const unsigned long long t0_ = __builtin_amdgcn_s_memtime();                                \
-        ws_barrier();                                                                               \
+        lds_barrier();                                                                              \
         const unsigned long long t1_ = __builtin_amdgcn_s_memtime();                                \
         if (wave == 0 && lane == 0 && (idx) < 160 && blockIdx.x < 256) g_ws_wait[blockIdx.x][(idx)] = (unsigned)(t1_ - t0_); \
     } while (0)
@@ -63,15 +59,13 @@ extern "C" int dxmi_debug_read_ws_stamps(void* dst, int bytes) {
     do {                                                                                            \
         if ((cond) && lane == 0 && blockIdx.x < 256) g_ws_wait[blockIdx.x][(slot)] = (unsigned)__builtin_amdgcn_s_memtime(); \
     } while (0)
-// timing-only ablations of the diagnostic build (DXMI_CONV_WS_DBG bits: 1 no weight stream, 2 no halo stream, 4 no drain,
-// 8 no residual / table fetch, 16 no step barriers — wrong results); compiled out of the product library
-#define WS_DBG(bit) (p.stagger & (bit))
 #else
-#define WS_STAMPED_BARRIER(idx) ws_barrier()
+#define WS_STAMPED_BARRIER(idx) lds_barrier()
 #define WS_TSTAMP(slot, cond) do {} while (0)
 #define WS_CLOCKSTAMP(slot, cond) do {} while (0)
-#define WS_DBG(bit) 0
 #endif
+// (diagnostic build: DXMI_CONV_WS_DBG bits 2 no halo stream, 4 no drain, 8 no residual / table fetch, 16 no step barriers — wrong
+// results; bit 1, no weight stream, is not available in this kernel)
 
 // Shader clock of the last launch (round 5): workgroup 0 leaves (s_memtime, s_memrealtime) of its first and last instruction
 // here; d s_memtime / d s_memrealtime x 100 MHz is the clock the chip held DURING the kernel (it lowers the clock under this
@@ -94,49 +88,7 @@ constexpr int WS_HALO_BLOCKS = 22;           // 1-KiB blocks of a halo image (34
 constexpr int WS_HALO = WS_HALO_BLOCKS * 1024;
 constexpr int WS_GN = 2048;                  // conv_ws_gn_kernel: gamma[128] | beta[128] | partials [2 pixel halves][64 pairs][2] fp32
 
-__device__ uint4 ws_zero16 = {0u, 0u, 0u, 0u};   // source of zero-padding pixels
-
-#define WS_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define WS_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-__device__ __forceinline__ void ws_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 16 MFMAs (16 cycles each) with 4 / 8 operand reads spread between them
-#define WS_INTERLEAVE_4()                                       \
-    do {                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {      \
-            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);  \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  \
-        }                                                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);      \
-    } while (0)
-#define WS_INTERLEAVE_8()                                       \
-    do {                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {      \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  \
-        }                                                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);      \
-    } while (0)
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate): n is rounded DOWN to an even
-// count, which only waits for more
-__device__ __forceinline__ void ws_wait_vm(int n) {
-    switch (n >> 1) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-    }
-}
+WS_ZERO_PAGE(ws_zero16);   // source of zero-padding pixels
 
 struct WsTile {
     int cot, n0, oy0, ox0;
@@ -295,7 +247,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
 
         // (no s_setprio: giving the MFMA waves priority over the movers that share their SIMDs measured 5 % SLOWER on the
         // residual layers — late movers cost more than contended issue slots — and equal elsewhere)
-        ws_barrier();                                   // P0: tap 0 and the first halo chunk have landed
+        lds_barrier();                                   // P0: tap 0 and the first halo chunk have landed
         WS_CLOCKSTAMP(168, wave == 0);
         read_a(0, A0);
         read_b(0, 0, Bx);
@@ -303,30 +255,11 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
         (void)stamp_i;
         for (;;) {
             const bool more = q + qstride < ntiles;
-            // K loop: two chunks (18 steps) of straight-line code per iteration, no branches inside (a branch makes hipcc wait
-            // lgkmcnt(0) at the join, which exposes the latency of the operand reads just issued).  Every half step (16 MFMAs)
-            // requests the operands of the next one: the other 4 pixel blocks of this step, then — behind the barrier that
-            // says they landed — the weights and first 4 blocks of the next step.  The first operands of the step after the
-            // last one (the next tile's first step, already in LDS when the last barrier of this tile opens) are requested
-            // unconditionally.
-            for (int c = 0; c < nchunks; c += 2) {
-#pragma unroll
-                for (int u = 0; u < 18; ++u) {
-                    read_b(u, 1, By);
-                    if (u & 1) mfma16(A1, Bx, 0); else mfma16(A0, Bx, 0);
-                    WS_INTERLEAVE_4();
-                    // groups of three steps: the loaders hand over three ring slots at a time (register-staged), so the MFMA
-                    // stream is interrupted by a barrier every 96 MFMAs instead of every 32
-                    if (u % 3 == 2) { if (!(WS_DBG(16))) WS_STAMPED_BARRIER(stamp_i + c * 9 + u); }
-                    if (u & 1) read_a(u + 1, A0); else read_a(u + 1, A1);
-                    read_b(u + 1, 0, Bx);
-                    if (u & 1) mfma16(A1, By, 1); else mfma16(A0, By, 1);
-                    WS_INTERLEAVE_8();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+            // K loop (ws_k_pair): 16 MFMAs per half step with 4 / 8 operand reads spread between them
+            for (int c = 0; c < nchunks; c += 2)
+                ws_k_pair<4, 3, 4, 8, 1, 8>(A0, A1, Bx, By, read_a, read_b, mfma16, [&](int u) { if (!(WS_DBG(16))) WS_STAMPED_BARRIER(stamp_i + c * 9 + u); });
             WS_TSTAMP(158, wave == 0 && q == q0);
-            ws_barrier();                               // E1: residual tile + bias / temb table of this tile landed
+            lds_barrier();                               // E1: residual tile + bias / temb table of this tile landed
             WS_TSTAMP(159, wave == 0 && q == q0);
             {
                 // acc + bias + temb (+ residual) -> activation -> bf16 -> output tile, in place, accumulator layout:
@@ -421,7 +354,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
             }
             WS_TSTAMP(166, wave == 0 && q == q0);
             if constexpr (GN) {
-                ws_barrier();                           // EG: the raw tile and the partials of both pixel halves are in LDS
+                lds_barrier();                           // EG: the raw tile and the partials of both pixel halves are in LDS
                 // Lane = channel piece c8 (one whole group: 8 channels per group) of pixels wave * 64 + (lane >> 4) + 4 j, j < 16: a
                 // 16-lane row reads one pixel's 256 bytes (conflict free whatever the slot swizzle).  The group's moments, formed by
                 // every lane for itself (no LDS table, no further barrier): a pair's two partials in partial order (gn_pair_sums), the
@@ -469,7 +402,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) acc[cb][nb][e] = 0.f;
             }
-            ws_barrier();                               // E2: output tile complete, the bulk movers may drain it
+            lds_barrier();                               // E2: output tile complete, the bulk movers may drain it
             WS_TSTAMP(157, wave == 0 && q == q0);
             if (!more) {
                 WS_CLOCKSTAMP(170, wave == 0);
@@ -485,57 +418,12 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
         const char* const wb = reinterpret_cast<const char*>(p.w) + (size_t)lane * 16;
         WsTile cur;
         tile_of(q, cur);
-        // fragments lw*4 .. lw*4+3 of (chunk c, tap t) for cout tile cot -> ring slot
-        auto issue_tap = [&](int cot, int g) {
-            if (WS_DBG(1)) return;                  // timing-only ablation (DXMI_CONV_WS_DBG): no weight stream
-            const int c = g / 9, t = g - c * 9;
-            char* dst = aring + (g % WS_RING) * WS_A_SLOT + lw * 4096;
-            // fragments (ks = lw, cbg = 0..3): contiguous 4 KiB of the packed weights
-            const char* src = wb + ((size_t)(t * p.KST + c * 2 + lw) * p.CB) * 1024;
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                // a half-empty last cout tile (Cout % 128 == 64): its missing fragments re-read the last valid one (results unused)
-                const int cb = cot * 4 + f < p.CB ? cot * 4 + f : p.CB - 1;
-                __builtin_amdgcn_global_load_lds(WS_GPTR(src + (size_t)cb * 1024), WS_LPTR(dst + f * 1024), 16, 0, 0);
-            }
-        };
-        // Round 4: register-staged weight stream, handed over in GROUPS of three steps.  The ring's six slots are two groups: the
-        // MFMA waves read group G (slots of parity G & 1) while this wave writes group G + 1 into the other three slots (last
-        // read in group G - 1: complete at the barrier that ended it) from registers, with ds_write_b128.  The fragments were
-        // requested two group steps earlier by plain global_load_dwordx4 (two register sets of 12 x 4 registers): a
-        // `global_load_lds` costs its wave ~190 cycles of issue (tools/dma_probe.hip, tools/stage_probe.hip), four per step
-        // and loader were more than a 512-cycle step, and one workgroup barrier per step cost 11-15 % by itself
-        // (DXMI_CONV_WS_DBG=15 vs 31).  vmcnt retires in order: each wait leaves the 12 loads of the younger group in flight.
-        u32x4 fq[2][3][4];
-        auto load_tap = [&](int cot, int g, u32x4 (&f)[4]) {
-            const int c = g / 9, t = g - c * 9;
-            const char* src = wb + ((size_t)(t * p.KST + c * 2 + lw) * p.CB) * 1024;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int cb = cot * 4 + k < p.CB ? cot * 4 + k : p.CB - 1;
-                // inline asm: hipcc's own wait-count pass loses the count of loads in flight across the loop's back edge and
-                // drains the queue (s_waitcnt vmcnt(0)) before the first ds_write of every trip; the waits below are exact
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(f[k]) : "v"(src + (size_t)cb * 1024) : "memory");
-            }
-        };
-        auto store_tap = [&](int g, const u32x4 (&f)[4]) {
-            char* dst = aring + (g % WS_RING) * WS_A_SLOT + lw * 4096 + lane * 16;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) *reinterpret_cast<u32x4*>(dst + k * 1024) = f[k];
-        };
+        // register-staged weight stream: four 1-KiB fragments per tap and loader (two register sets of 12 x 4 registers), a
+        // half-empty last cout tile clamped.  Four `global_load_lds` per step and loader were more than a 512-cycle step.
         const int NG = S / 3;                           // groups per tile (even: S = 9 * nchunks, nchunks even)
-        // group G of the current tile, or group G - NG of the next one (past the last tile: the current tile's again, unused)
-        auto load_group = [&](int G, int cot_cur, int cot_nxt, u32x4 (&f)[3][4]) {
-            const bool nx = G >= NG;
-            const int g0 = (nx ? G - NG : G) * 3, cot = nx ? cot_nxt : cot_cur;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) load_tap(cot, g0 + j, f[j]);
-        };
-        auto store_group = [&](int G, const u32x4 (&f)[3][4]) {     // ring slots depend on G's parity only (NG even)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) store_tap((G & 1) * 3 + j, f[j]);
-        };
-        if (WS_DBG(1)) {}                               // (timing-only ablation of the weight stream: not available in this build)
+        u32x4 fq[2][3][4];
+        const WsWeightStream<4, true> ws{p, aring, wb, lw, lane, NG, fq};
+        static_assert(ws.SLOT == WS_A_SLOT && ws.RING == WS_RING, "ring layout");
         // residual pieces (see the bulk movers: piece L = k*128 + t2 with t2 = lw*64 + lane)
         const int t2l = lw * 64 + lane, prl = t2l >> 4;
         const int lpar_l0 = prl * p.Cout + (((t2l & 15) ^ prl) * 8), lpar_l1 = prl * p.Cout + (((t2l & 15) ^ (prl | 8)) * 8);
@@ -543,13 +431,8 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
         const int kpc_l = (32 + nchunks - 2) / (nchunks - 1);
         const char* const zero_page_l = reinterpret_cast<const char*>(p.mask_src);
         bool first_tile_l = true, first_group0 = true;
-        load_group(0, cur.cot, cur.cot, fq[0]);
-        load_group(1, cur.cot, cur.cot, fq[1]);
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        store_group(0, fq[0]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        load_group(2, cur.cot, cur.cot, fq[0]);
-        ws_barrier();                                       // P0 (its lgkmcnt(0): group 0 is in LDS)
+        ws.prologue(cur.cot);
+        lds_barrier();                                       // P0 (its lgkmcnt(0): group 0 is in LDS)
         bool first_tile = true;
         for (;;) {
             const bool more = q + qstride < ntiles;
@@ -591,12 +474,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                     const int G = G0 + j;
                     // group step G (the MFMA waves read group G): group G + 1 sits in set (j + 1) & 1 since group step G - 1.
                     // (Group step 0 of every tile but the first was done ahead, in front of E1 of the previous tile: see below.)
-                    if (G > 0 || first_group0) {
-                        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");   // ... and has landed (group G + 2's loads stay in flight)
-                        store_group(G + 1, fq[(j + 1) & 1]);
-                        // the barrier's lgkmcnt(0) must precede the refill: a ds_write reads its data registers when it executes
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    }
+                    if (G > 0 || first_group0) ws.hand_over(j, G);
                     if (res_here && G > 0) {
                         const int cg = (G - 1) / 3, g3 = (G - 1) - cg * 3;     // the group step whose pieces were drained
                         if (cg + 1 < nchunks) {
@@ -612,10 +490,10 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                             }
                         }
                     }
-                    if (G > 0 || first_group0) load_group(G + 3, cur.cot, more ? nxt.cot : cur.cot, fq[(j + 1) & 1]);
+                    if (G > 0 || first_group0) ws.refill(j, G, cur.cot, more ? nxt.cot : cur.cot);
                     WS_TSTAMP(151, wave == 4 && G == 0 && q == q0 + qstride);
                     WS_VALU_RUN();
-                    if (!(WS_DBG(16))) ws_barrier();                        // end of group step G
+                    if (!(WS_DBG(16))) lds_barrier();                        // end of group step G
                 }
             }
             first_group0 = false;
@@ -623,14 +501,12 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 // group step 0 of the NEXT tile, ahead of time: its ring slots (parity 1) were last read in this tile's last
                 // group step, and after E2 every wave starts at once — the tile-start bookkeeping plus this block made the
                 // loaders 1.1 k cycles late at the next tile's first group barrier (stamp build: 2.7 k cycles after E2)
-                asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-                store_group(1, fq[1]);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                load_group(3, nxt.cot, nxt.cot, fq[1]);
+                ws.hand_over(0, 0);
+                ws.refill(0, 0, nxt.cot, nxt.cot);
             }
-            ws_barrier();                                        // E1
-            if constexpr (GN) ws_barrier();                      // EG
-            ws_barrier();                                        // E2
+            lds_barrier();                                        // E1
+            if constexpr (GN) lds_barrier();                      // EG
+            lds_barrier();                                        // E2
             WS_TSTAMP(150, wave == 4 && q == q0);
             if (!more) break;
             q += qstride;
@@ -712,7 +588,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ws_barrier();                                           // P0
+        lds_barrier();                                           // P0
         WsTile nxt = cur;
         for (;;) {
             const bool more = q + qstride < ntiles;
@@ -729,12 +605,12 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 for (int t = 0; t < 9; ++t) {
                     if (t < 8 && do_halo) halo_issue(hc, hbuf, 3 * t, 3 * t + 3 < HBA ? 3 * t + 3 : HBA);
                     if (t == 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the halo image landed
-                    if (t % 3 == 2) { WS_VALU_RUN(); if (!(WS_DBG(16))) ws_barrier(); }            // end of a group step
+                    if (t % 3 == 2) { WS_VALU_RUN(); if (!(WS_DBG(16))) lds_barrier(); }            // end of a group step
                 }
             }
-            ws_barrier();                                        // E1
-            if constexpr (GN) ws_barrier();                      // EG
-            ws_barrier();                                        // E2
+            lds_barrier();                                        // E1
+            if constexpr (GN) lds_barrier();                      // EG
+            lds_barrier();                                        // E2
             if (!more) break;
             q += qstride;
             cur = nxt;
@@ -768,7 +644,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                 __builtin_amdgcn_global_load_lds(WS_GPTR(gb), WS_LPTR(ro + (k * 128 + 64) * 16), 16, 0, 0);
             }
         }
-        ws_barrier();                                           // P0
+        lds_barrier();                                           // P0
         bool have_prev = false;
         WsTile prev = cur;
         const int kpc = (32 + nchunks - 2) / (nchunks - 1);
@@ -808,13 +684,13 @@ __device__ __forceinline__ void conv_ws_body(const ConvArgs& p) {
                             }
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // the piece is out of LDS before the group barrier
-                    if (t % 3 == 2) { WS_VALU_RUN(); if (!(WS_DBG(16))) ws_barrier(); }            // end of a group step
+                    if (t % 3 == 2) { WS_VALU_RUN(); if (!(WS_DBG(16))) lds_barrier(); }            // end of a group step
                 }
             }
             if (!have_prev) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // first tile: the residual tile of the prologue landed
-            ws_barrier();                                        // E1
-            if constexpr (GN) ws_barrier();                      // EG
-            ws_barrier();                                        // E2
+            lds_barrier();                                        // E1
+            if constexpr (GN) lds_barrier();                      // EG
+            lds_barrier();                                        // E2
             out_prev = reinterpret_cast<bf16*>(p.out) + tile_base(cur);
             prev = cur;
             have_prev = true;

@@ -13,7 +13,7 @@
 //   * everything else as in conv_ws.hip: one barrier per step, movers issue a few DMAs per step, exact in-order vmcnt counts.
 // Scope: 3x3 / stride 1 / pad 1 on 8x8 maps, NHWC bf16 in (virtual concat) and out, any batch, Cout % 64 == 0,
 // an even number (>= 4) of 32-channel chunks.
-#include "conv_common.h"
+#include "ws_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -34,50 +34,10 @@ constexpr int W8_A_RING = W8_RING * W8_A_SLOT;
 constexpr int W8_RO = 256 * 128;                    // 256 px x 64 co bf16
 constexpr int W8_TB = 2048;                         // bias[64] | temb[4][64] fp32
 
-__device__ uint4 w8_zero16 = {0u, 0u, 0u, 0u};
+WS_ZERO_PAGE(w8_zero16);
 
-// timing-only ablations of the diagnostic build (make STAMPS=1; DXMI_CONV_WS8_DBG bits: 1 no weight stream, 2 no halo stream,
-// 4 no step barriers — wrong results); compiled out of the product library (tools/conv_ws8_ab.py)
-#ifdef DXMI_CONV_STAMPS
-#define W8_DBG(bit) (p.stagger & (bit))
-#else
-#define W8_DBG(bit) 0
-#endif
-
-#define W8_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define W8_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-__device__ __forceinline__ void w8_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 8 MFMAs (16 cycles each) with 2 / 6 operand reads spread between them
-#define W8_INTERLEAVE_2()                                       \
-    do {                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {      \
-            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);  \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  \
-        }                                                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);      \
-    } while (0)
-#define W8_INTERLEAVE_6()                                       \
-    do {                                                        \
-        _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) {      \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  \
-        }                                                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);      \
-    } while (0)
-
-__device__ __forceinline__ void w8_wait_vm(int n) {      // s_waitcnt vmcnt(n), n wave-uniform, rounded DOWN to even (waits for more)
-    switch (n >> 1) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    }
-}
+// (diagnostic build, make STAMPS=1: DXMI_CONV_WS8_DBG bits 1 no weight stream, 2 no halo stream, 4 no step barriers — wrong
+// results; tools/conv_ws8_ab.py)
 
 struct W8Tile {
     int cot, n0;
@@ -163,7 +123,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                 *reinterpret_cast<uint4*>(halo0 + b * W8_HALO + wave * W8_IMG + (lane >> 5) * 9 * W8_ROW + (lane & 31) * 16) = z;
             for (int i = wave; i < W8_STRIP / 1024; i += 4) *reinterpret_cast<uint4*>(halo0 + 2 * W8_HALO + i * 1024 + lane * 16) = z;
         }
-        w8_barrier();                                   // P0: tap 0 and the first halo chunk have landed, the padding is written
+        lds_barrier();                                   // P0: tap 0 and the first halo chunk have landed, the padding is written
         read_a(0, A0);
         read_b(0, 0, Bx);
         for (;;) {
@@ -178,20 +138,11 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                 }
             }
             for (int c = 0; c < nchunks; c += 2) {
-#pragma unroll
-                for (int u = 0; u < 18; ++u) {
-                    read_b(u, 1, By);
-                    if (u & 1) mfma8(A1, Bx, 0); else mfma8(A0, Bx, 0);
-                    W8_INTERLEAVE_2();
-                    if (u % 3 == 2 && !(W8_DBG(4))) w8_barrier();       // end of a group of three steps: the next group's weights (at a chunk end: the next halo image) landed
-                    if (u & 1) read_a(u + 1, A0); else read_a(u + 1, A1);
-                    read_b(u + 1, 0, Bx);
-                    if (u & 1) mfma8(A1, By, 1); else mfma8(A0, By, 1);
-                    W8_INTERLEAVE_6();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                // 8 MFMAs per half step with 2 / 6 operand reads spread between them; the barrier ends a group of three steps: the
+                // next group's weights (at a chunk end: the next halo image) landed
+                ws_k_pair<2, 3, 2, 6, 1, 2>(A0, A1, Bx, By, read_a, read_b, mfma8, [&](int) { if (!(WS_DBG(4))) lds_barrier(); });
             }
-            w8_barrier();                               // E1: residual tile + bias / temb table of this tile landed
+            lds_barrier();                               // E1: residual tile + bias / temb table of this tile landed
             {
                 // per-lane base + compile-time offsets, the residual pieces of a cout block requested together, no activation
                 // code when there is none (as conv_ws.hip)
@@ -291,7 +242,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                 else if (has_res) epi(T_{}, F_{}, T_{});
                 else epi(F_{}, F_{}, T_{});
             }
-            w8_barrier();                               // E2: output tile complete, the bulk movers may drain it
+            lds_barrier();                               // E2: output tile complete, the bulk movers may drain it
             if (!more) break;
             q += qstride;
         }
@@ -304,42 +255,11 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
         const char* const wb = reinterpret_cast<const char*>(p.w) + (size_t)lane * 16;
         W8Tile cur;
         tile_of(q, cur);
-        auto issue_tap = [&](int cot, int g) {
-            const int c = g / 9, t = g - c * 9;
-            char* dst = aring + (g % W8_RING) * W8_A_SLOT + lw * 2048;
-            const char* src = wb + ((size_t)(t * p.KST + c * 2 + lw) * p.CB + cot * 2) * 1024;
-#pragma unroll
-            for (int f = 0; f < 2; ++f)
-                __builtin_amdgcn_global_load_lds(W8_GPTR(src + f * 1024), W8_LPTR(dst + f * 1024), 16, 0, 0);
-        };
-        // register-staged weight stream handed over in groups of three steps (see conv_ws.hip, round 4): the ring's six slots are
-        // two groups; group G + 1 is written from registers (ds_write_b128) while the MFMA waves read group G; its fragments were
-        // requested two group steps earlier (two register sets of 6 x 4 registers).  One barrier per three steps.
-        static_assert(W8_RING == 6, "group hand-over needs the six-slot ring");
-        u32x4 fq[2][3][2];
-        auto load_tap = [&](int cot, int g, u32x4 (&f)[2]) {
-            if (W8_DBG(1)) return;
-            const int c = g / 9, t = g - c * 9;
-            const char* src = wb + ((size_t)(t * p.KST + c * 2 + lw) * p.CB + cot * 2) * 1024;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(f[k]) : "v"(src + k * 1024) : "memory");
-        };
-        auto store_tap = [&](int g, const u32x4 (&f)[2]) {
-            char* dst = aring + (g % W8_RING) * W8_A_SLOT + lw * 2048 + lane * 16;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) *reinterpret_cast<u32x4*>(dst + k * 1024) = f[k];
-        };
+        // register-staged weight stream, two 1-KiB fragments per tap and loader, handed over in groups of three steps
         const int NG = S / 3;                           // groups per tile (even)
-        auto load_group = [&](int G, int cot_cur, int cot_nxt, u32x4 (&f)[3][2]) {
-            const bool nx = G >= NG;
-            const int g0 = (nx ? G - NG : G) * 3, cot = nx ? cot_nxt : cot_cur;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) load_tap(cot, g0 + j, f[j]);
-        };
-        auto store_group = [&](int G, const u32x4 (&f)[3][2]) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) store_tap((G & 1) * 3 + j, f[j]);
-        };
+        u32x4 fq[2][3][2];
+        const WsWeightStream<2, false> ws{p, aring, wb, lw, lane, NG, fq};
+        static_assert(ws.SLOT == W8_A_SLOT && ws.RING == W8_RING, "group hand-over needs the six-slot ring");
         // residual pieces of a tile switch (see the bulk movers: piece L = k*128 + t2, t2 = lw*64 + lane): fetched here one
         // group step after the bulk movers drained the piece (conv_ws.hip, round 4)
         const int t2l = lw * 64 + lane;
@@ -353,13 +273,8 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
             return (long)((((size_t)n * 8 + ((lp >> 3) & 7)) * 8 + (lp & 7)) * p.Cout + t.cot * 64 + c8 * 8);
         };
         bool first_tile_l = true;
-        load_group(0, cur.cot, cur.cot, fq[0]);
-        load_group(1, cur.cot, cur.cot, fq[1]);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        store_group(0, fq[0]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        load_group(2, cur.cot, cur.cot, fq[0]);
-        w8_barrier();                                       // P0
+        ws.prologue(cur.cot);
+        lds_barrier();                                       // P0
         for (;;) {
             const bool more = q + qstride < ntiles;
             W8Tile nxt = cur;
@@ -370,9 +285,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int G = G0 + j;
-                    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");        // group G + 1 landed (group G + 2's loads stay in flight)
-                    store_group(G + 1, fq[(j + 1) & 1]);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    ws.hand_over(j, G);
                     if (res_here && G > 0) {
                         const int cg = (G - 1) / 3, g3 = (G - 1) - cg * 3;     // the group step whose pieces were drained
                         if (cg + 1 < nchunks) {
@@ -383,16 +296,16 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                             for (int k = ka; k < kb; ++k) {
                                 const long o = piece_off_l(cur, k);
                                 const void* g = o >= 0 ? (const void*)(p.residual + o) : (const void*)zero_page_l;
-                                __builtin_amdgcn_global_load_lds(W8_GPTR(g), W8_LPTR(ro + (k * 128 + lw * 64) * 16), 16, 0, 0);
+                                __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(ro + (k * 128 + lw * 64) * 16), 16, 0, 0);
                             }
                         }
                     }
-                    load_group(G + 3, cur.cot, more ? nxt.cot : cur.cot, fq[(j + 1) & 1]);
-                    if (!(W8_DBG(4))) w8_barrier();                         // end of group step G
+                    ws.refill(j, G, cur.cot, more ? nxt.cot : cur.cot);
+                    if (!(WS_DBG(4))) lds_barrier();                         // end of group step G
                 }
             }
-            w8_barrier();                                        // E1
-            w8_barrier();                                        // E2
+            lds_barrier();                                        // E1
+            lds_barrier();                                        // E2
             if (!more) break;
             q += qstride;
             cur = nxt;
@@ -425,7 +338,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
             }
         };
         auto halo_issue = [&](int c, char* buf, int ka, int kb) {     // blocks ka .. kb-1 of this wave's share (compile-time range)
-            if (W8_DBG(2)) return;
+            if (WS_DBG(2)) return;
             const int cbase = c * 32;
             const bool first = cbase < p.C0;
             const char* base = reinterpret_cast<const char*>(first ? p.in0 : p.in1) + (first ? cbase : cbase - p.C0) * 2;
@@ -435,7 +348,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                 const int blk = bw + 2 * k;
                 const int off = first ? hoff0[k] : hoff1[k];
                 const char* g = off >= 0 ? base + off : zero_page;
-                __builtin_amdgcn_global_load_lds(W8_GPTR(g), W8_LPTR(buf + (blk >> 2) * W8_IMG + W8_ROW + (blk & 3) * 1024), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(buf + (blk >> 2) * W8_IMG + W8_ROW + (blk & 3) * 1024), 16, 0, 0);
             }
         };
         // output-tile pieces of this thread: L = k*128 + t2 (k = 0..15): pixel lp = k*16 + (t2 >> 3), cout piece (t2 & 7) ^ (lp & 7)
@@ -449,13 +362,13 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
         };
         auto fetch_table = [&](const W8Tile& t) {            // bias[64] and the four images' temb rows: 4-byte DMA, 256 B per instruction
             if (bw != 0) return;
-            if (p.bias) __builtin_amdgcn_global_load_lds(W8_GPTR(p.bias + t.cot * 64 + lane), W8_LPTR(tb), 4, 0, 0);
+            if (p.bias) __builtin_amdgcn_global_load_lds(WS_GPTR(p.bias + t.cot * 64 + lane), WS_LPTR(tb), 4, 0, 0);
             if (p.addvec) {
 #pragma unroll
                 for (int sub = 0; sub < 4; ++sub) {
                     const int n = t.n0 + sub < p.N ? t.n0 + sub : p.N - 1;      // images past the batch: any valid row (results discarded)
-                    __builtin_amdgcn_global_load_lds(W8_GPTR(p.addvec + (size_t)n * p.addvec_ld + t.cot * 64 + lane),
-                                                     W8_LPTR(tb + 64 + sub * 64), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds(WS_GPTR(p.addvec + (size_t)n * p.addvec_ld + t.cot * 64 + lane),
+                                                     WS_LPTR(tb + 64 + sub * 64), 4, 0, 0);
                 }
             }
         };
@@ -466,7 +379,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
             for (int k = k0; k < k1; ++k) {
                 const long o = piece_off(t, k);
                 const void* g = o >= 0 ? (const void*)(p.residual + o) : (const void*)zero_page;
-                __builtin_amdgcn_global_load_lds(W8_GPTR(g), W8_LPTR(ro + (k * 128 + bw * 64) * 16), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(WS_GPTR(g), WS_LPTR(ro + (k * 128 + bw * 64) * 16), 16, 0, 0);
             }
         };
         // pieces k0 .. k1-1 of the tile switch: previous tile's output pieces out, this tile's residual pieces into the same
@@ -508,7 +421,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
         // P0 needs the halo image and the table, not the residual tile (16 younger DMAs; E1's vmcnt(0) covers them)
         if (do_res) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        w8_barrier();                                           // P0
+        lds_barrier();                                           // P0
         do_res = false;
         bool have_prev = false;
         W8Tile prev = cur;
@@ -543,14 +456,14 @@ __global__ __launch_bounds__(512, 1) void conv_ws8_kernel(ConvArgs p) {
                     }
                     if (t == 8) {
                         // halo image (and everything older) landed; at the last chunk E1 needs the whole residual tile
-                        if (wrap) w8_wait_vm(0);
-                        else w8_wait_vm(young);
+                        if (wrap) ws_wait_vm<12>(0);
+                        else ws_wait_vm<12>(young);
                     }
-                    if (t % 3 == 2 && !(W8_DBG(4))) w8_barrier();                // end of a group step
+                    if (t % 3 == 2 && !(WS_DBG(4))) lds_barrier();                // end of a group step
                 }
             }
-            w8_barrier();                                        // E1
-            w8_barrier();                                        // E2
+            lds_barrier();                                        // E1
+            lds_barrier();                                        // E2
             prev = cur;
             have_prev = true;
             if (!more) break;

@@ -30,7 +30,7 @@
 // Scope: ups == 1, OW == 2 IW in {16, 32}, OH == 2 IH, no virtual concat, Cout % 64 == 0, and what conv_ws_select checks
 // (an even number >= 4 of 32-channel chunks, ...).  Everything else with ups == 1 stays on conv_ws_kernel.
 // Block statistics: same partials and layout as conv_ws_kernel ([pixel tile * 2 + pixel half][Cout / 2][2]).
-#include "conv_common.h"
+#include "ws_common.h"
 #include <type_traits>
 
 namespace {
@@ -39,8 +39,6 @@ constexpr int UP_A_CHUNK = 9 * 4096;     // weights of one 32-channel chunk x 64
 constexpr int UP_HALO = 6 * 1024;        // low-res rows of one chunk: 6 rows x 16 px (IW 16) or 10 rows x 8 px (IW 8) x 64 B
 constexpr int UP_RO = 256 * 128;         // output tile: 256 px x 64 couts bf16
 constexpr int UP_LDS = 2 * UP_A_CHUNK + 2 * UP_HALO + UP_RO;
-
-__device__ __forceinline__ void up_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct UpTile {
     int cot, pt, n0, oy0;
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_up_kernel(ConvArgs p) {
         const int lanepix = TW == 32 ? 2 * px : (px >> 3) * 32 + 2 * (px & 7);
         char* const rob = ro + lanepix * 128 + (((w * 2 + (kg >> 1)) ^ (px & 7)) << 4) + (kg & 1) * 8;
 
-        up_barrier();                                   // P0: chunk 0 of the first tile is in LDS
+        lds_barrier();                                   // P0: chunk 0 of the first tile is in LDS
         read_b(0, Bf[0]);
         read_a(0, 0, A[0]);
         for (;;) {
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_up_kernel(ConvArgs p) {
                     if (t < 8) {
                         read_a(P, t + 1, A[(u + 1) & 1]);
                     } else {
-                        up_barrier();
+                        lds_barrier();
                         read_b(P ^ 1, Bf[P ^ 1]);
                         read_a(P ^ 1, 0, A[(u + 1) & 1]);
                     }
@@ -204,7 +202,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_up_kernel(ConvArgs p) {
                 else if (has_res) { if (want_stats) epi(T_{}, F_{}, T_{}); else epi(T_{}, F_{}, F_{}); }
                 else { if (want_stats) epi(F_{}, F_{}, T_{}); else epi(F_{}, F_{}, F_{}); }
             }
-            up_barrier();                               // E: output tile complete
+            lds_barrier();                               // E: output tile complete
             if (!more) break;
             q += qstride;
         }
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_up_kernel(ConvArgs p) {
         fetch();
         store(0);
         fetch();
-        up_barrier();                                   // P0
+        lds_barrier();                                   // P0
         for (;;) {
             const bool more = q + qstride < ntiles;
             for (int c = 0; c < nchunks; c += 2) {
@@ -264,10 +262,10 @@ __global__ __launch_bounds__(512, 1) void conv_ws_up_kernel(ConvArgs p) {
                     store(P ^ 1);                       // chunk g + 1, requested before the previous barrier
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     fetch();                            // chunk g + 2
-                    up_barrier();                       // end of chunk g
+                    lds_barrier();                       // end of chunk g
                 }
             }
-            up_barrier();                               // E
+            lds_barrier();                               // E
             if (!more) break;
             q += qstride;
         }
@@ -281,7 +279,7 @@ __global__ __launch_bounds__(512, 1) void conv_ws_up_kernel(ConvArgs p) {
         bf16* out_prev = reinterpret_cast<bf16*>(p.out);
         for (int i = 0;; ++i) {
             const bool more = q + qstride < ntiles;
-            if (i == 0) up_barrier();                   // P0
+            if (i == 0) lds_barrier();                   // P0
             for (int c = 0; c < nchunks; ++c) {
                 if (have_prev) {
                     const int ka = c * kpc < 32 ? c * kpc : 32, kb = ka + kpc < 32 ? ka + kpc : 32;
@@ -292,9 +290,9 @@ __global__ __launch_bounds__(512, 1) void conv_ws_up_kernel(ConvArgs p) {
                         *reinterpret_cast<bf16x8*>(out_prev + (size_t)pix * p.Cout + (dsl ^ ((pix >> 1) & 7)) * 8) = v;
                     }
                 }
-                up_barrier();                           // end of chunk c (its lgkmcnt(0): the pieces are out of LDS)
+                lds_barrier();                           // end of chunk c (its lgkmcnt(0): the pieces are out of LDS)
             }
-            up_barrier();                               // E
+            lds_barrier();                               // E
             UpTile cur;
             tile_of(q, cur);
             out_prev = reinterpret_cast<bf16*>(p.out) + (((size_t)cur.n0 * p.OH + cur.oy0) * TW) * p.Cout + cur.cot * 64;
