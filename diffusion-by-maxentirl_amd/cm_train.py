@@ -31,7 +31,7 @@ discretised lognormal over the levels; uniform = the reference's randint), --sca
 at once (loss_norm, weight_schedule, scale_mode, target_ema_mode fixed, start_ema 0, start_scales 10, end_scales 1280, index_sampler
 lognormal) and takes --training_mode consistency_training, which it also selects where no --training_mode is given; any other is an error.
 --training_mode dm is distribution matching distillation of the teacher into a ONE-step generator (models.cm.train_util.DMTrainLoop over
-KarrasDenoiser.dm_generator_losses; Diff-Instruct / DMD / DMD2 without its GAN term): generator and fake denoiser start from
+KarrasDenoiser.dm_generator_losses; Diff-Instruct / DMD / DMD2, its GAN term with --dm_gan): generator and fake denoiser start from
 --teacher_model_path, the data are latents and uniform labels from a device generator seeded seed + rank, so neither --data_npz (refused)
 nor --synthetic_data is needed; --gen_update_every (5), --fake_lr (0 = --lr), --dm_weighting dmd|none, --dm_num_scales (1000).  The sigma
 levels of the fake denoiser's loss are EDM's (LogNormalSampler's defaults, as train_edm.py draws them).  --ict, a --loss_norm other than the default and
@@ -40,6 +40,11 @@ levels of the fake denoiser's loss are EDM's (LogNormalSampler's defaults, as tr
 al. 2024: the loss is differentiated through both denoisers' inputs): --sid_alpha (1.2), and --gen_sigma, the generator's input level
 (0 = sigma_max; SiD's runs use 2.5, and generate_large.py must then be given the same --gen_sigma).  --dm_weighting none does not go
 with it, and the three flags are errors outside --training_mode dm.
+--dm_gan True adds DMD2's GAN term (models.cm.gan_head.GANHead on the fake denoiser's bottleneck, sized from the net: its bottleneck
+channels and image_size / 2^(levels - 1); KarrasDenoiser.gan_discriminator_losses on the fake clock, the generator's loss gains
+--gan_gen_weight softplus(-logit)): it needs real images, --data_npz PATH or --synthetic_data True, and does not go with --dm_objective
+sid; --gan_gen_weight (3e-3), --gan_dis_weight (1e-2), --gan_max_step_frac (1.0: the noise levels of the GAN term's inputs reach up to that
+fraction of the ladder).  The gan_* flags are errors without --dm_gan.
 """
 import argparse
 import math
@@ -77,8 +82,12 @@ def latent_batches(batch_size, image_size, class_cond, device, seed, num_classes
         yield z, cond
 
 
-def make_loader(args, device, rank, world):
-    """The `data=` iterator of CMTrainLoop for the parsed flags, and the ImageStore behind it (None for synthetic data)."""
+REAL_SEED_OFFSET = 1 << 20      # --dm_gan: the synthetic real images are drawn from another stream than the latents
+
+
+def make_loader(args, device, rank, world, seed_offset=0):
+    """The `data=` iterator of CMTrainLoop for the parsed flags, and the ImageStore behind it (None for synthetic data).
+    seed_offset: added to the synthetic stream's seed (two device generators of one seed would draw correlated values)."""
     if args.data_npz:
         from dxmi_hip.data import NORM_ADM, ImageStore
         store = ImageStore(args.data_npz, device, NORM_ADM, batch_size=args.batch_size, rank=rank, world=world, seed=args.seed,
@@ -87,7 +96,7 @@ def make_loader(args, device, rank, world):
     if not args.synthetic_data:
         raise NotImplementedError("cm_train.py: image folders are not read by this package; run with --data_npz PATH (an uint8 array "
                                   "file, see make_npz.py) or --synthetic_data True")
-    return synthetic_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + rank), None
+    return synthetic_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + rank + seed_offset), None
 
 
 # what --ict True sets: improved consistency training as its paper runs it
@@ -103,7 +112,8 @@ def parse_args(argv=None):
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
                     fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False,
                     huber_c=0.0, index_sampler="uniform", p_mean=-1.1, p_std=2.0, ict=False, gen_update_every=5, fake_lr=0.0,
-                    dm_weighting="dmd", dm_num_scales=1000, dm_objective="dmd", sid_alpha=1.2, gen_sigma=0.0)
+                    dm_weighting="dmd", dm_num_scales=1000, dm_objective="dmd", sid_alpha=1.2, gen_sigma=0.0, dm_gan=False,
+                    gan_gen_weight=3e-3, gan_dis_weight=1e-2, gan_max_step_frac=1.0)
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
     args = ap.parse_args(argv)
@@ -112,7 +122,15 @@ def parse_args(argv=None):
     if args.synthetic_data and args.data_npz:
         ap.error("--synthetic_data and --data_npz exclude each other")
     if args.training_mode == "dm":
-        if args.data_npz:
+        if args.dm_gan and not (args.data_npz or args.synthetic_data):
+            ap.error("--dm_gan True needs real images: --data_npz PATH or --synthetic_data True")
+        if args.dm_gan and args.dm_objective == "sid":
+            ap.error("--dm_gan True does not go with --dm_objective sid: a discriminator on score identity distillation is SiDA, a "
+                     "different recipe")
+        if args.dm_gan and not (math.isfinite(args.gan_gen_weight) and math.isfinite(args.gan_dis_weight)
+                                and 0.0 <= args.gan_max_step_frac <= 1.0):
+            ap.error("--gan_gen_weight and --gan_dis_weight must be finite and --gan_max_step_frac lie in [0, 1]")
+        if args.data_npz and not args.dm_gan:
             ap.error("--data_npz does not go with --training_mode dm: distribution matching trains on latents alone, it reads no images")
         if args.ict:
             ap.error("--ict True is improved consistency TRAINING: --training_mode dm does not go with it")
@@ -135,9 +153,13 @@ def parse_args(argv=None):
         if not (math.isfinite(args.gen_sigma) and args.gen_sigma >= 0):
             ap.error(f"--gen_sigma {args.gen_sigma}: a positive level, or 0 for sigma_max")
     else:
-        for flag in ("--dm_objective", "--sid_alpha", "--gen_sigma"):
+        for flag in ("--dm_objective", "--sid_alpha", "--gen_sigma", "--dm_gan"):
             if given(flag):
                 ap.error(f"{flag} belongs to --training_mode dm, not to --training_mode {args.training_mode}")
+    if not args.dm_gan:
+        for flag in ("--gan_gen_weight", "--gan_dis_weight", "--gan_max_step_frac"):
+            if given(flag):
+                ap.error(f"{flag} belongs to --dm_gan True")
     if args.ict:
         if given("--training_mode") and args.training_mode != "consistency_training":
             ap.error(f"--ict True is improved consistency TRAINING: --training_mode {args.training_mode} does not go with it")
@@ -258,7 +280,17 @@ def main_dm(args, device, local_rank, world):
     model.to(device).train()
     fake_model.to(device).train()
     data = latent_batches(args.batch_size, args.image_size, args.class_cond, device, args.seed + local_rank)
-    loop = DMTrainLoop(model=model, diffusion=diffusion, real_model=real_model, real_diffusion=real_diffusion, fake_model=fake_model,
+    gan, store = {}, None
+    if args.dm_gan:
+        from models.cm.gan_head import GANHead
+        levels = len(fake_model.channel_mult)
+        head = GANHead(int(fake_model.channel_mult[-1] * fake_model.model_channels), args.image_size // 2 ** (levels - 1))
+        real_data, store = make_loader(args, device, local_rank, world, seed_offset=REAL_SEED_OFFSET)
+        if store is not None:
+            print0(store.describe())
+        gan = dict(gan_head=head.to(device), real_data=real_data, gan_gen_weight=args.gan_gen_weight, gan_dis_weight=args.gan_dis_weight,
+                   gan_max_step_frac=args.gan_max_step_frac)
+    loop = DMTrainLoop(**gan, model=model, diffusion=diffusion, real_model=real_model, real_diffusion=real_diffusion, fake_model=fake_model,
                        num_scales=args.dm_num_scales, gen_update_every=args.gen_update_every, fake_lr=args.fake_lr or None,
                        weighting=args.dm_weighting, objective=args.dm_objective, sid_alpha=args.sid_alpha,
                        gen_sigma=args.gen_sigma or None, data=data, batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr,
@@ -269,10 +301,13 @@ def main_dm(args, device, local_rank, world):
     print0(f"dm: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
            + (f"objective sid (alpha {args.sid_alpha}), " if args.dm_objective == "sid" else f"weighting {args.dm_weighting}, ")
            + f"gen_sigma {args.gen_sigma or diffusion.sigma_max}, "
-           f"generator update every {args.gen_update_every} iterations")
+           f"generator update every {args.gen_update_every} iterations"
+           + (f", GAN term (generator weight {args.gan_gen_weight}, discriminator weight {args.gan_dis_weight})" if args.dm_gan else ""))
     loop.run_loop()
     if loop.logged:
         print0("last log row:", loop.logged[-1])
+    if store is not None:
+        store.close()
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -1,5 +1,5 @@
 // Distribution matching distillation of the EDM teacher into a one-step generator G(z) = D_theta(sigma_G z, sigma_G): Diff-Instruct
-// (Luo et al. 2023, eq. 8 / Algorithm 1), DMD (Yin et al. 2023, eq. 7-8) and DMD2 (Yin et al. 2024, eq. 2-3) without its GAN term.
+// (Luo et al. 2023, eq. 8 / Algorithm 1), DMD (Yin et al. 2023, eq. 7-8) and DMD2 (Yin et al. 2024, eq. 2-3; its GAN term: gan_head.hip).
 // The launches between the three network evaluations of one generator step (KarrasDenoiser.dm_generator_losses):
 //   dxmi_dm_gen_in     latents -> generator: x_in = c_in(sigma_G) (sigma_G z), time = 250 ln(sigma_G + 1e-44)
 //   dxmi_dm_gen_out    generator -> images (sampling): x = c_skip(sigma_G) (sigma_G z) + c_out(sigma_G) F_g, clamped when asked

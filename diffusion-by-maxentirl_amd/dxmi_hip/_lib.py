@@ -147,6 +147,16 @@ SIGNATURES = {
     "dxmi_sid_grad_fwd": (c_int, [c_void_p] * 6 + [c_int, c_float] + [c_void_p] * 5 + [c_int, c_int, c_float, c_float, c_int, c_float,
                                                                                         c_float, c_int, c_void_p]),
     "dxmi_sid_join": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
+    "dxmi_gan_head_supported": (c_int, [c_int, c_int]),
+    "dxmi_gan_conv4s2_slices": (c_int64, [c_int]),
+    "dxmi_gan_conv4s2_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "dxmi_gan_conv4s2_pack": (c_int, [c_void_p] * 3 + [c_int, c_void_p]),
+    "dxmi_gan_conv4s2_fwd": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_void_p]),
+    "dxmi_gan_conv4s2_dgrad": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int, c_void_p]),
+    "dxmi_gan_conv4s2_wgrad": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
+    "dxmi_gan_logit_loss_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p]),
+    "dxmi_gan_logit_loss_bwd": (c_int, [c_void_p] * 5 + [c_float] + [c_void_p] * 3 + [c_int, c_int, c_void_p]),
+    "dxmi_gan_join": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
     "dxmi_karras_stage": (c_int, [c_int, c_int, c_void_p, c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p]),
     "dxmi_cm_stage": (c_int, [c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 10 + [c_int] * 4 + [c_void_p]),
     "dxmi_quantize_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -1394,6 +1394,142 @@ def sid_join(d_dir, g_real, g_fake, s, indices, t_table, real_sigma_data=0.5, fa
     return out
 
 
+# ---- DMD2's GAN head (csrc/gan_head.hip; models/cm/gan_head.py)
+def gan_head_supported(C, map_size):
+    """Raise DxmiError (its message names the value) where the head's kernels do not serve C channels on a map_size^2 bottleneck."""
+    check(load().dxmi_gan_head_supported(int(C), int(map_size)), "dxmi_gan_head_supported")
+
+
+def gan_conv4s2_slices(dgrad=False):
+    """The number of fp32 slabs dxmi_gan_conv4s2_fwd (dgrad: _dgrad) sums per output element."""
+    return int(load().dxmi_gan_conv4s2_slices(int(bool(dgrad))))
+
+
+def gan_conv4s2_pack(w, out=None):
+    """w fp32 [C, C, 4, 4] -> (w_fwd, w_t), the two bf16 forms of the head's 4x4 stride-2 weight: [16 taps][Cout][Cin] and
+    [16 taps][Cin][Cout] (dxmi_gan_conv4s2_pack); out: such a pair to rewrite in place."""
+    _need_cuda(w)
+    if w.dim() != 4 or w.shape[0] != w.shape[1] or tuple(w.shape[2:]) != (4, 4):
+        raise _lib.DxmiError(f"dxmi_gan_conv4s2_pack: a [C, C, 4, 4] weight is needed, got {tuple(w.shape)}")
+    w = w.detach().contiguous().float()
+    C = w.shape[0]
+    if out is None:
+        out = (torch.empty((16, C, C), dtype=torch.bfloat16, device=w.device), torch.empty((16, C, C), dtype=torch.bfloat16, device=w.device))
+    if any(tuple(t.shape) != (16, C, C) or t.dtype != torch.bfloat16 or not t.is_contiguous() for t in out):
+        raise _lib.DxmiError(f"dxmi_gan_conv4s2_pack: out is a pair of contiguous bf16 [16, {C}, {C}] tensors")
+    check(load().dxmi_gan_conv4s2_pack(_ptr(w), _ptr(out[0]), _ptr(out[1]), C, _stream()), "dxmi_gan_conv4s2_pack")
+    return out
+
+
+def _gan_map(what, t, C=None, H=None):
+    _need_cuda(t)
+    if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.dim() != 4 or t.shape[1] != t.shape[2]:
+        raise _lib.DxmiError(f"{what}: a contiguous NHWC bf16 square map is needed, got {tuple(t.shape)} {t.dtype}")
+    if (C is not None and t.shape[3] != C) or (H is not None and t.shape[1] != H):
+        raise _lib.DxmiError(f"{what}: map of shape {tuple(t.shape)} where [N, {H}, {H}, {C}] is needed")
+    return t.shape[0], t.shape[1], t.shape[3]
+
+
+def gan_conv4s2_fwd(x, pw, bias=None):
+    """x NHWC bf16 [N, H, H, C] -> bf16 [N, H/2, H/2, C] = conv(x, w, 4x4, stride 2, pad 1) + bias (dxmi_gan_conv4s2_fwd); pw: the
+    pair of gan_conv4s2_pack."""
+    what = "dxmi_gan_conv4s2_fwd"
+    N, H, C = _gan_map(what, x, pw[0].shape[1])
+    _need_cuda(bias)
+    lib = load()
+    nbytes = lib.dxmi_gan_conv4s2_workspace_bytes(N, H, C, 0)
+    ws = _workspace(max(nbytes, 16), x.device)
+    y = torch.empty((N, H // 2, H // 2, C), dtype=torch.bfloat16, device=x.device)
+    check(lib.dxmi_gan_conv4s2_fwd(_ptr(x), _ptr(pw[0]), _ptr(bias), _ptr(y), _ptr(ws), nbytes, N, H, C, _stream()), what)
+    return y
+
+
+def gan_conv4s2_dgrad(dy, pw):
+    """dy NHWC bf16 [N, H/2, H/2, C] -> dx bf16 [N, H, H, C], the data gradient of gan_conv4s2_fwd (dxmi_gan_conv4s2_dgrad)."""
+    what = "dxmi_gan_conv4s2_dgrad"
+    N, OH, C = _gan_map(what, dy, pw[1].shape[1])
+    H = 2 * OH
+    lib = load()
+    nbytes = lib.dxmi_gan_conv4s2_workspace_bytes(N, H, C, 1)
+    ws = _workspace(max(nbytes, 16), dy.device)
+    dx = torch.empty((N, H, H, C), dtype=torch.bfloat16, device=dy.device)
+    check(lib.dxmi_gan_conv4s2_dgrad(_ptr(dy), _ptr(pw[1]), _ptr(dx), _ptr(ws), nbytes, N, H, C, _stream()), what)
+    return dx
+
+
+def gan_conv4s2_wgrad(x, dy):
+    """-> (dw fp32 [C, C, 4, 4], db fp32 [C]) of gan_conv4s2_fwd from its input x and output gradient dy (dxmi_gan_conv4s2_wgrad)."""
+    what = "dxmi_gan_conv4s2_wgrad"
+    N, H, C = _gan_map(what, x)
+    _gan_map(what, dy, C, H // 2)
+    if dy.shape[0] != N:
+        raise _lib.DxmiError(f"{what}: x holds {N} images, dy {dy.shape[0]}")
+    dw = torch.empty((C, C, 4, 4), dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    check(load().dxmi_gan_conv4s2_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), N, H, C, _stream()), what)
+    return dw, db
+
+
+def _gan_logit_operands(what, a, w, per_sample):
+    _need_cuda(a, w, *per_sample)
+    if a.dtype != torch.bfloat16 or not a.is_contiguous() or a.dim() < 2:
+        raise _lib.DxmiError(f"{what}: a contiguous bf16 [N, C] activation is needed")
+    N, C = a.shape[0], a.numel() // a.shape[0]
+    for t, n in ((w, C),) + tuple((t, N) for t in per_sample):
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise _lib.DxmiError(f"{what}: fp32 contiguous operand of {n} elements needed")
+    return N, C
+
+
+def gan_logit_loss_fwd(a, w, b, sign):
+    """a bf16 [N, C] (or [N, 1, 1, C]), w fp32 [C], b fp32 [1], sign fp32 [N] of -1 / +1 -> (logit [N] = w . a_n + b,
+    loss [N] = softplus(sign_n logit_n)) in one launch (dxmi_gan_logit_loss_fwd)."""
+    what = "dxmi_gan_logit_loss_fwd"
+    N, C = _gan_logit_operands(what, a, w, (sign,))
+    _need_cuda(b)
+    if b.dtype != torch.float32 or b.numel() != 1:
+        raise _lib.DxmiError(f"{what}: b is one fp32 value")
+    logit = torch.empty(N, dtype=torch.float32, device=a.device)
+    loss = torch.empty_like(logit)
+    check(load().dxmi_gan_logit_loss_fwd(_ptr(a), _ptr(w), _ptr(b), _ptr(sign), _ptr(logit), _ptr(loss), N, C, _stream()), what)
+    return logit, loss
+
+
+def gan_logit_loss_bwd(a, w, sign, logit, upstream, weight=1.0, params=True):
+    """-> (d_a bf16 like a, dw [C] | None, db [1] | None) for the per-sample upstream [N] and the weight of the term
+    (dxmi_gan_logit_loss_bwd); params False: the input-only backward."""
+    what = "dxmi_gan_logit_loss_bwd"
+    N, C = _gan_logit_operands(what, a, w, (sign, logit, upstream))
+    weight = float(weight)
+    if not math.isfinite(weight):
+        raise _lib.DxmiError(f"{what}: weight must be finite, got {weight!r}")
+    d_a = torch.empty_like(a)
+    dw = torch.empty(C, dtype=torch.float32, device=a.device) if params else None
+    db = torch.empty(1, dtype=torch.float32, device=a.device) if params else None
+    check(load().dxmi_gan_logit_loss_bwd(_ptr(a), _ptr(w), _ptr(sign), _ptr(logit), _ptr(upstream), weight, _ptr(d_a), _ptr(dw), _ptr(db),
+                                         N, C, _stream()), what)
+    return d_a, dw, db
+
+
+def gan_join(g, d_xin, indices, t_table, weight, sigma_data=0.5, out=None):
+    """-> g + (CHW weight c_in(t)) d_xin, t = t_table[indices] (dxmi_gan_join): the DM direction joined with the GAN term's gradient
+    with respect to the fake denoiser's input.  out: g itself (in place) or a fresh tensor."""
+    what = "dxmi_gan_join"
+    N, CHW, S = _dm_operands(what, g, indices, t_table, same=(d_xin,))
+    weight = float(weight)
+    if not math.isfinite(weight):
+        raise _lib.DxmiError(f"{what}: weight must be finite, got {weight!r}")
+    sd = _dm_scalar(what, "sigma_data", sigma_data)
+    if out is None:
+        out = torch.empty_like(g)
+    elif out is not g:
+        _batch_operands(what, g, same=(out,), chw4=True)
+        if out.data_ptr() == d_xin.data_ptr():
+            raise _lib.DxmiError(f"{what}: out may be g itself or a tensor of its own")
+    check(load().dxmi_gan_join(_ptr(g), _ptr(d_xin), _ptr(indices), _ptr(t_table), S, _ptr(out), N, CHW, weight, sd, _stream()), what)
+    return out
+
+
 EMA_MAX_RATES = 4
 
 

@@ -49,7 +49,7 @@ _PDLossFn): dxmi_cd_prep on the coarse ladder, the online training forward, teac
 evaluation 2, dxmi_pd_solver END (target_x; x_t3 is never stored), dxmi_pd_loss_fwd; its backward is dxmi_pd_loss_bwd and the U-Net
 backward.  Its levels are a host table of 2 S + 1 entries (PDLevels: the coarse ladder, then the half steps); num_scales = 1 is legal.
 lpips goes through dxmi_pd_lpips_images and, backwards, dxmi_cd_lpips_bwd.  The reference has no l2-32 here: refused.
-dm_generator_losses (not in the reference: Diff-Instruct / DMD / DMD2 without its GAN term) trains a ONE-step generator
+dm_generator_losses (not in the reference: Diff-Instruct / DMD / DMD2; gan_head=... adds DMD2's GAN term) trains a ONE-step generator
 G(z) = D_theta(sigma_max z, sigma_max) against a frozen real and an online-trained fake denoiser; on HIP UNetModels it is ONE autograd
 node around the generator (_dm_loss, _DMLossFn): dxmi_dm_gen_in, the generator's training forward, dxmi_dm_gen_prep, the two
 denoisers' forward_inference, dxmi_dm_grad_fwd; its backward is dxmi_dm_gen_bwd and the U-Net backward.  dm_sample is its sampler
@@ -80,7 +80,8 @@ from dxmi_hip import graph as _graph
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
 from .nn import append_dims, append_zero, mean_flat
-from .unet_train import input_backward, input_forward, train_backward, train_forward
+from .unet_train import (encoder_backward, encoder_forward, encoder_input_backward, encoder_input_forward, input_backward,
+                         input_forward, train_backward, train_forward)
 
 
 def get_weightings(weight_schedule, snrs, sigma_data):
@@ -419,17 +420,40 @@ def _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep):
     return (_train_forward_no_grad(net, x_in, t_g, y) if net.training and net.dropout > 0 else net.forward_inference(x_in, t_g, y)), None
 
 
-def _dm_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting, keep):
+def _dm_gan_term(fake, fake_diffusion, x, g, tab, y, gan, keep):
+    """DMD2's GAN term of the generator on the device -> (gan_loss [N], gan_logit [N]); with keep, g becomes the combined direction
+    g + CHW w c_in(t_gan) d_xin in place: the fake net's encoder_input_forward, the head's features and dxmi_gan_logit_loss, the
+    head's input-only backward, encoder_input_backward and dxmi_gan_join.  Both tapes are dropped here."""
+    head, w, gan_noise, gan_indices = gan
+    x_in, _ = ops.edm_dsm_prep(x, gan_noise, tab[gan_indices], fake_diffusion.sigma_data)
+    h, etape = encoder_input_forward(fake, x_in, _denoiser_time(tab, gan_indices), y)
+    with torch.no_grad():
+        a2, saved = head.features(h)
+        sign = torch.full((x.shape[0],), -1.0, dtype=torch.float32, device=x.device)
+        logit, gan_loss = head.logit_loss(a2, sign)
+        if keep:
+            d_h, _ = head.backward(saved, sign, logit, torch.ones_like(sign), 1.0, params=False)
+            d_xin = encoder_input_backward(etape, d_h)
+            ops.gan_join(g, d_xin, gan_indices, tab, w, fake_diffusion.sigma_data, out=g)
+    return gan_loss, logit
+
+
+def _dm_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting, keep, gan=None):
     """dm_gen_in -> generator forward -> dm_gen_prep -> the real and the fake denoiser -> dm_grad_fwd.
     -> (loss, x, s, (tape, g)), the last being what _DMLossFn.backward reads.  keep=False: no backward follows, so the generator
-    runs forward_inference (the training forward where its dropout is live) and no tape is kept."""
+    runs forward_inference (the training forward where its dropout is live) and no tape is kept.
+    gan = (head, weight, gan_noise, gan_indices): DMD2's GAN term (_dm_gan_term) joins the loss and the direction, and the result
+    gains (gan_loss, gan_logit)."""
     F, tape = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
     x, x_t, xr_in, t, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, diffusion.sigma_data, real_diffusion.sigma_data,
                                               fake_diffusion.sigma_data)
     F_r = real.forward_inference(xr_in, t, y)
     F_f = fake.forward_inference(xr_in if xf_in is None else xf_in, t, y)
     g, loss, s = ops.dm_grad_fwd(F_r, F_f, x, x_t, indices, tab, weighting, real=_scal_kw(real_diffusion), fake=_scal_kw(fake_diffusion))
-    return loss, x, s, (tape, g)
+    if gan is None:
+        return loss, x, s, (tape, g)
+    gan_loss, gan_logit = _dm_gan_term(fake, fake_diffusion, x, g, tab, y, gan, keep)
+    return loss + gan[1] * gan_loss, x, s, (tape, g), gan_loss, gan_logit
 
 
 class _DMLossFn(torch.autograd.Function):
@@ -452,7 +476,57 @@ class _DMLossFn(torch.autograd.Function):
         ctx.g = None
         grads = train_backward(ctx.tape, dF)
         ctx.tape = None
-        return (None,) * 13 + grads
+        return (None,) * (len(ctx.needs_input_grad) - len(grads)) + grads
+
+
+class _DMGanLossFn(torch.autograd.Function):
+    """_DMLossFn with DMD2's GAN term: outputs (loss, x, dm_norm, gan_loss, gan_logit), of which only loss is differentiable.  The
+    forward has walked the fake net's encoder and the head backward already (the shape of _SiDLossFn); the backward is _DMLossFn's."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, weighting, gan, *params):
+        loss, x, s, (ctx.tape, ctx.g), gan_loss, gan_logit = _dm_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise,
+                                                                      indices, tab, y, gen_sigma, weighting, keep=True, gan=gan)
+        ctx.gen = (gen_sigma, diffusion.sigma_data)
+        ctx.mark_non_differentiable(x, s, gan_loss, gan_logit)
+        ctx.set_materialize_grads(False)
+        return loss, x, s, gan_loss, gan_logit
+
+    @staticmethod
+    def backward(ctx, g_loss, *rest):
+        return _DMLossFn.backward(ctx, g_loss, None, None)
+
+
+class _GANDisLossFn(torch.autograd.Function):
+    """The discriminator loss of DMD2's GAN term as one node around the fake net's encoder and the head: encoder_forward, the head's
+    features and dxmi_gan_logit_loss forward; the head's full backward, then encoder_backward.  x holds the generated half first;
+    outputs (loss [N], logit_fake [N], logit_real [N])."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, head, x, noise, indices, tab, y, *params):
+        N = x.shape[0] // 2
+        x_in, _ = ops.edm_dsm_prep(x, noise, tab[indices], diffusion.sigma_data)
+        h, ctx.tape = encoder_forward(net, x_in, _denoiser_time(tab, indices), y)
+        a2, saved = head.features(h)
+        sign = torch.ones(2 * N, dtype=torch.float32, device=x.device)
+        sign[N:] = -1.0
+        logit, loss = head.logit_loss(a2, sign)
+        ctx.head, ctx.saved, ctx.sign, ctx.logit = head, saved, sign, logit
+        ctx.set_materialize_grads(False)
+        lf, lr = logit[:N].clone(), logit[N:].clone()
+        ctx.mark_non_differentiable(lf, lr)
+        return loss[:N] + loss[N:], lf, lr
+
+    @staticmethod
+    def backward(ctx, g_loss, g_lf, g_lr):
+        if g_loss is None:
+            return (None,) * len(ctx.needs_input_grad)
+        up = g_loss.detach().float().contiguous()
+        d_h, head_grads = ctx.head.backward(ctx.saved, ctx.sign, ctx.logit, torch.cat([up, up]), 1.0, params=True)
+        ctx.saved = None
+        grads = encoder_backward(ctx.tape, d_h)
+        ctx.tape = None
+        return (None,) * 8 + grads + head_grads
 
 
 def _denoiser_time(tab, indices):
@@ -804,9 +878,10 @@ class KarrasDenoiser:
 
     def dm_generator_losses(self, model, z, num_scales=1000, real_model=None, real_diffusion=None, fake_model=None, fake_diffusion=None,
                             model_kwargs=None, noise=None, indices=None, generator=None, gen_sigma=None, weighting="dmd",
-                            min_step_frac=0.02, max_step_frac=0.98):
+                            min_step_frac=0.02, max_step_frac=0.98, gan_head=None, gan_gen_weight=3e-3, gan_noise=None, gan_indices=None,
+                            gan_min_step_frac=0.0, gan_max_step_frac=1.0):
         """Distribution-matching loss of the one-step generator G(z) = D_theta(sigma_G z, sigma_G) (Diff-Instruct, Luo et al. 2023;
-        DMD, Yin et al. 2023, eq. 7-8; DMD2, Yin et al. 2024, without its GAN term) -> {"loss": [N], "x": [N, C, H, W] detached fp32,
+        DMD, Yin et al. 2023, eq. 7-8; DMD2, Yin et al. 2024, its GAN term under gan_head below) -> {"loss": [N], "x": [N, C, H, W] detached fp32,
         "dm_norm": [N]}.  x = G(z) is diffused to x_t = x + noise t, t = cd_levels(num_scales)[index]; with D_r / D_f the denoised
         images of real_model under real_diffusion (the teacher) and fake_model under fake_diffusion (None: real_diffusion; trained
         online on x by training_losses), s = mean|x - D_r| ("dm_norm") and g = (D_f - D_r) / s (weighting "dmd") or D_f - D_r
@@ -814,15 +889,37 @@ class KarrasDenoiser:
         d loss_n / d x = g_n / CHW: both denoisers are under stop-gradient, neither net receives a gradient, the generator receives
         it through x alone.  `self` is the generator's diffusion (distillation=False).  gen_sigma: None = sigma_max.
         indices: drawn uniformly from [ceil(min_step_frac (S - 1)), floor(max_step_frac (S - 1))] when None, then noise, both from
-        `generator` where given."""
+        `generator` where given.
+        gan_head (models.cm.gan_head.GANHead; None: the code path without it): DMD2's GAN term.  With x_gan = x + gan_noise t_gan,
+        t_gan = levels[gan_indices], logit = gan_head(bottleneck of fake_model at (c_in x_gan, t_gan)) and
+        gan_loss_n = softplus(-logit_n): loss = the DM loss + gan_gen_weight gan_loss, d loss_n / d x = g_n / CHW + gan_gen_weight
+        d gan_loss_n / d x, reaching the generator through x alone (neither the head nor the fake denoiser receives a gradient),
+        and the result gains "gan_loss" and "gan_logit", [N], detached.  gan_indices (uniform over dm_index_range(S, gan_min_step_frac,
+        gan_max_step_frac)) and then gan_noise are drawn after the draws above.  DESIGN 5.39."""
         what = "dm_generator_losses"
         model_kwargs, fake_diffusion = self._dm_refusals(what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs)
         if weighting not in DM_WEIGHTINGS:
             raise ValueError(f"dm_generator_losses: weighting {weighting!r} is not one of {DM_WEIGHTINGS}")
         gen_sigma, indices, noise = self._dm_draws(what, z, num_scales, noise, indices, generator, gen_sigma, min_step_frac, max_step_frac)
+        if gan_head is not None:
+            gan_gen_weight = float(gan_gen_weight)
+            if not math.isfinite(gan_gen_weight):
+                raise ValueError(f"dm_generator_losses: gan_gen_weight must be finite, got {gan_gen_weight!r}")
+            _, gan_indices, gan_noise = self._dm_draws(what, z, num_scales, gan_noise, gan_indices, generator, gen_sigma, gan_min_step_frac,
+                                                       gan_max_step_frac)
+            if gan_noise.requires_grad:
+                raise NotImplementedError("dm_generator_losses differentiates the generator's parameters only: gan_noise must not "
+                                          "require grad")
         nets = [_hip_unet(m) for m in (model, real_model, fake_model)]
         if all(n is not None for n in nets) and z.is_cuda:
             args = self._dm_hip_operands(what, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma)
+            if gan_head is not None:
+                gan = (gan_head, gan_gen_weight) + self._dm_level_operands(what, args[6], gan_noise, gan_indices)
+                if torch.is_grad_enabled():
+                    loss, x, s, gl, lg = _DMGanLossFn.apply(*args, weighting, gan, *ops.fast_parameters(nets[0]))
+                else:
+                    loss, x, s, _, gl, lg = _dm_loss(*args, weighting, keep=False, gan=gan)
+                return {"loss": loss, "x": x, "dm_norm": s, "gan_loss": gl, "gan_logit": lg}
             if torch.is_grad_enabled():
                 loss, x, s = _DMLossFn.apply(*args, weighting, *ops.fast_parameters(nets[0]))
             else:
@@ -831,6 +928,9 @@ class KarrasDenoiser:
         if z.requires_grad or noise.requires_grad:
             raise NotImplementedError("dm_generator_losses differentiates the generator's parameters only: z and noise must not "
                                       "require grad")
+        if gan_head is not None and not hasattr(fake_model, "encode"):
+            raise NotImplementedError("dm_generator_losses with a gan_head: the fake model must offer encode(x_in, t, **kw) -> "
+                                      f"[N, C, h, w], the bottleneck features the head reads; {type(fake_model).__name__} has no encode")
         N, dims = z.shape[0], z.ndim
         levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(z.device)
         t = levels[indices.to(z.device)]
@@ -845,7 +945,70 @@ class KarrasDenoiser:
             if weighting == "dmd":
                 g = g / append_dims(s, dims)
             g = torch.where(append_dims(s, dims) == 0, torch.zeros_like(g), g)
-        return {"loss": _DMSurrogate.apply(x, g), "x": x.detach().float(), "dm_norm": s}
+        if gan_head is None:
+            return {"loss": _DMSurrogate.apply(x, g), "x": x.detach().float(), "dm_norm": s}
+        # the GAN term's d / d x is taken here, with respect to x alone: the head and the fake model see no backward
+        keep = torch.is_grad_enabled()
+        t_gan = levels[gan_indices.to(z.device)]
+        with torch.enable_grad() if keep else torch.no_grad():
+            xd = x.detach().requires_grad_(keep)
+            x_gan = xd + gan_noise * append_dims(t_gan, dims)
+            c_in = append_dims(fake_diffusion.get_scalings(t_gan)[2], dims)
+            logit = gan_head(fake_model.encode(c_in * x_gan, 1000 * 0.25 * torch.log(t_gan + 1e-44), **model_kwargs))
+            gan_loss = torch.nn.functional.softplus(-logit)
+            g_gan = torch.autograd.grad(gan_loss.sum(), xd)[0] if keep else None
+        gan_loss, logit = gan_loss.detach(), logit.detach()
+        value = 0.5 * mean_flat(g ** 2) + gan_gen_weight * gan_loss
+        if keep:
+            value = _SiDSurrogate.apply(x, g + (x[0].numel() * gan_gen_weight) * g_gan, value)
+        return {"loss": value, "x": x.detach().float(), "dm_norm": s, "gan_loss": gan_loss, "gan_logit": logit}
+
+    def gan_discriminator_losses(self, fake_model, gan_head, x_fake, x_real, num_scales, model_kwargs=None, real_kwargs=None, noise=None,
+                                 indices=None, generator=None, gan_min_step_frac=0.0, gan_max_step_frac=1.0):
+        """The discriminator loss of DMD2's GAN term (Yin et al. 2024) -> {"loss": [N], "logit_fake": [N], "logit_real": [N]}.
+        `self` is the fake denoiser's diffusion, as with training_losses.  The generated batch x_fake (model_kwargs) and the real batch
+        x_real (real_kwargs) have one shape and run as one batch of 2N, generated half first: indices [2N] are drawn uniformly over
+        dm_index_range(num_scales, gan_min_step_frac, gan_max_step_frac) when None, then noise [2N, C, H, W]; x_t = x + noise t,
+        logit = gan_head(bottleneck of fake_model at (c_in x_t, t)), loss_n = softplus(logit_fake_n) + softplus(-logit_real_n).
+        Gradients go to the head's parameters and to the fake net's encoder and embedding parameters; its decoder gets none.
+        On the HIP U-Net it is one autograd node (_GANDisLossFn); any other fake model must offer encode(x_in, t, **kw)."""
+        what = "gan_discriminator_losses"
+        if tuple(x_fake.shape) != tuple(x_real.shape):
+            raise ValueError(f"{what}: the generated batch {tuple(x_fake.shape)} and the real batch {tuple(x_real.shape)} must have one shape")
+        model_kwargs, real_kwargs = model_kwargs or {}, real_kwargs or {}
+        if set(model_kwargs) != set(real_kwargs):
+            raise ValueError(f"{what}: model_kwargs {sorted(model_kwargs)} and real_kwargs {sorted(real_kwargs)} must name the same inputs")
+        kw = {k: torch.cat([model_kwargs[k], real_kwargs[k].to(model_kwargs[k].device)]) for k in model_kwargs}
+        x = torch.cat([x_fake.detach(), x_real.detach().to(x_fake.device)]).float()
+        _, indices, noise = self._dm_draws(what, x, num_scales, noise, indices, generator, 1.0, gan_min_step_frac, gan_max_step_frac)
+        N = x_fake.shape[0]
+        if tuple(noise.shape) != tuple(x.shape) or indices.numel() != 2 * N:
+            raise ValueError(f"{what}: noise {tuple(noise.shape)} must match the stacked batch {tuple(x.shape)} and indices "
+                             f"({indices.numel()}) hold one level per sample of it")
+        net = _hip_unet(fake_model)
+        if net is not None and x.is_cuda:
+            extra = set(kw) - {"y"}
+            if extra:
+                raise NotImplementedError(f"{what} on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
+            y = kw.get("y")
+            if (y is not None) != (net.num_classes is not None):
+                raise ValueError("must specify y if and only if the model is class-conditional")
+            x, noise = x.contiguous(), noise.detach().to(torch.float32).contiguous()
+            indices = indices.detach().to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
+            tab = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).device_table(x.device)
+            loss, lf, lr = _GANDisLossFn.apply(self, net, gan_head, x, noise, indices, tab, y, *ops.fast_parameters(net),
+                                               *ops.fast_parameters(gan_head))
+            return {"loss": loss, "logit_fake": lf, "logit_real": lr}
+        if not hasattr(fake_model, "encode"):
+            raise NotImplementedError(f"{what}: the fake model must offer encode(x_in, t, **kw) -> [N, C, h, w], the bottleneck "
+                                      f"features the head reads; {type(fake_model).__name__} has no encode")
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(x.device)
+        t = levels[indices.to(x.device)]
+        x_t = x + noise * append_dims(t, x.ndim)
+        c_in = append_dims(self.get_scalings(t)[2], x.ndim)
+        logit = gan_head(fake_model.encode(c_in * x_t, 1000 * 0.25 * torch.log(t + 1e-44), **kw))
+        sp = torch.nn.functional.softplus
+        return {"loss": sp(logit[:N]) + sp(-logit[N:]), "logit_fake": logit[:N].detach(), "logit_real": logit[N:].detach()}
 
     def _dm_refusals(self, what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs):
         """The refusals dm_generator_losses and sid_generator_losses share -> (model_kwargs, fake_diffusion)."""
@@ -875,6 +1038,16 @@ class KarrasDenoiser:
                 noise = torch.randn_like(z)
         return gen_sigma, indices, noise
 
+    @staticmethod
+    def _dm_level_operands(what, z, noise, indices):
+        """-> (noise fp32 contiguous, indices int64 [N] on z's device), checked against the latents z [N, C, H, W]."""
+        noise = noise.detach().to(torch.float32).contiguous()
+        indices = indices.detach().to(device=z.device, dtype=torch.int64).reshape(-1).contiguous()
+        if noise.shape != z.shape or indices.numel() != z.shape[0] or z.dim() != 4:
+            raise ValueError(f"{what}: noise {tuple(noise.shape)} must match z {tuple(z.shape)} [N, C, H, W] "
+                             f"and indices ({indices.numel()}) hold one level per sample")
+        return noise, indices
+
     def _dm_hip_operands(self, what, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma):
         """The checks of the device path -> the leading arguments of _dm_loss / _sid_loss, up to gen_sigma."""
         net, real, fake = nets
@@ -888,12 +1061,8 @@ class KarrasDenoiser:
         for n in nets:
             if (y is not None) != (n.num_classes is not None):
                 raise ValueError("must specify y if and only if the model is class-conditional")
-        f32 = lambda v: v.detach().to(torch.float32).contiguous()
-        z, noise = f32(z), f32(noise)
-        indices = indices.detach().to(device=z.device, dtype=torch.int64).reshape(-1).contiguous()
-        if noise.shape != z.shape or indices.numel() != z.shape[0] or z.dim() != 4:
-            raise ValueError(f"{what}: noise {tuple(noise.shape)} must match z {tuple(z.shape)} [N, C, H, W] "
-                             f"and indices ({indices.numel()}) hold one level per sample")
+        z = z.detach().to(torch.float32).contiguous()
+        noise, indices = self._dm_level_operands(what, z, noise, indices)
         levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho)
         if _graph.capturing() and not levels.on_device(z.device):
             raise DxmiError(f"{what} inside a StepGraph capture: the {int(num_scales)}-level table is not on {z.device} "

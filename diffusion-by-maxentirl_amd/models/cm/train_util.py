@@ -589,9 +589,18 @@ class CMTrainLoop(TrainLoop):
         self._kv = {"step": self.global_step, "samples": (self.global_step + 1) * self.global_batch}
 
 
+class _FakeWithHead(torch.nn.Module):
+    """(fake denoiser, GAN head): the one module the fake clock's trainer and optimiser see.  It is never saved as such: the
+    fake net and the head keep their own files and their own state-dict keys."""
+
+    def __init__(self, net, head):
+        super().__init__()
+        self.net, self.head = net, head
+
+
 class DMTrainLoop(TrainLoop):
     """Distribution matching distillation of an EDM teacher (`real_model` under `real_diffusion`, frozen) into the one-step
-    generator `model` (KarrasDenoiser.dm_generator_losses; DMD2's two time-scale rule without its GAN term).  Two trainers on two
+    generator `model` (KarrasDenoiser.dm_generator_losses; DMD2's two time-scale rule, its GAN term under gan_head below).  Two trainers on two
     clocks: the generator has TrainLoop's own mp_trainer / opt / EMA series and is updated when step % gen_update_every == 0; the
     fake denoiser `fake_model` has a MixedPrecisionTrainer and RAdam of its own (fake_lr, None = lr; its own loss scale and
     gradient exchange) and is updated at EVERY iteration by denoising score matching on that iteration's generated images, which
@@ -600,11 +609,18 @@ class DMTrainLoop(TrainLoop):
     in one trainer skips that trainer's update alone.  save() adds fake_model%06d.pt and fake_opt%06d.pt to TrainLoop's files; a
     resume reads all of them, and a missing fake_model file is an error.  use_graph=True is refused.
     objective: "dmd" (dm_generator_losses under `weighting`) or "sid" (sid_generator_losses at sid_alpha: score identity distillation,
-    DESIGN 5.34); only the generator's loss differs, everything else of the loop is the same."""
+    DESIGN 5.34); only the generator's loss differs, everything else of the loop is the same.
+    gan_head (models.cm.gan_head.GANHead; None: the loop without it): DMD2's GAN term.  It needs real_data, an iterator
+    of (x_real NCHW fp32 in [-1, 1], cond).  The head trains with the fake denoiser on its clock: one trainer / RAdam / loss scale
+    over (fake net, head), one backward per microbatch of (dsm weights).mean() + gan_dis_weight dis.mean(), dis being
+    gan_discriminator_losses on the generated and the real microbatch; the generator's loss gains gan_gen_weight softplus(-logit).
+    save() adds gan_head%06d.pt (fake_model%06d.pt stays the bare net's state dict); a resume with a head needs that file, and a
+    fake_opt file whose parameter count does not match the run's is an error."""
 
     def __init__(self, *, real_model, real_diffusion, fake_model, fake_diffusion=None, num_scales=1000, gen_update_every=5,
                  fake_lr=None, weighting="dmd", gen_sigma=None, min_step_frac=0.02, max_step_frac=0.98, generator=None, objective="dmd",
-                 sid_alpha=1.2, **kwargs):
+                 sid_alpha=1.2, gan_head=None, real_data=None, gan_gen_weight=3e-3, gan_dis_weight=1e-2, gan_min_step_frac=0.0,
+                 gan_max_step_frac=1.0, **kwargs):
         if kwargs.get("use_graph"):
             raise NotImplementedError("DMTrainLoop: use_graph=True is not supported: the generator and the fake denoiser are updated "
                                       "on two clocks, which needs two captured steps and a graph key per clock; train this mode eagerly")
@@ -616,7 +632,15 @@ class DMTrainLoop(TrainLoop):
             raise ValueError(f"DMTrainLoop: objective {objective!r} is not one of ('dmd', 'sid')")
         if objective == "sid" and not math.isfinite(float(sid_alpha)):
             raise ValueError(f"DMTrainLoop: sid_alpha must be finite, got {sid_alpha!r}")
+        if gan_head is not None and objective == "sid":
+            raise NotImplementedError("DMTrainLoop: objective 'sid' takes no gan_head: a discriminator on score identity distillation "
+                                      "is SiDA, a different recipe (its own loss weighting and schedule), which is not built here")
+        if gan_head is not None and real_data is None:
+            raise ValueError("DMTrainLoop: a gan_head needs real_data, an iterator of (x_real NCHW fp32 in [-1, 1], cond)")
         super().__init__(**kwargs)
+        self.gan_head, self.real_data = gan_head, real_data
+        self.gan_gen_weight, self.gan_dis_weight = float(gan_gen_weight), float(gan_dis_weight)
+        self.gan_min_step_frac, self.gan_max_step_frac = gan_min_step_frac, gan_max_step_frac
         self.real_model, self.real_diffusion, self.fake_model = real_model, real_diffusion, fake_model
         self.fake_diffusion = real_diffusion if fake_diffusion is None else fake_diffusion
         self.num_scales, self.gen_update_every = int(num_scales), int(gen_update_every)
@@ -631,11 +655,29 @@ class DMTrainLoop(TrainLoop):
             if not os.path.exists(ckpt):
                 raise FileNotFoundError(f"DMTrainLoop: resuming needs {ckpt} (the fake denoiser is written at every save)")
             self.fake_model.load_state_dict(torch.load(ckpt, map_location=self.device))
+            if self.gan_head is not None:
+                ckpt = self._side_file("gan_head")
+                if not os.path.exists(ckpt):
+                    raise FileNotFoundError(f"DMTrainLoop: resuming with a gan_head needs {ckpt} (the head is written at every save)")
+                self.gan_head.load_state_dict(torch.load(ckpt, map_location=self.device))
         broadcast_parameters(self.fake_model)
-        self.fake_trainer = MixedPrecisionTrainer(model=self.fake_model, use_fp16=self.use_fp16, fp16_scale_growth=self.fp16_scale_growth)
+        fake_side = self.fake_model
+        if self.gan_head is not None:
+            self.gan_head.to(self.device)
+            broadcast_parameters(self.gan_head)
+            fake_side = _FakeWithHead(self.fake_model, self.gan_head)
+        self.fake_trainer = MixedPrecisionTrainer(model=fake_side, use_fp16=self.use_fp16, fp16_scale_growth=self.fp16_scale_growth)
         self.fake_opt = RAdam(self.fake_trainer.master_params, lr=self.fake_lr, weight_decay=self.weight_decay)
         if self.resume_checkpoint and os.path.exists(self._side_file("fake_opt")):
-            self.fake_opt.load_state_dict(torch.load(self._side_file("fake_opt"), map_location=self.device))
+            state = torch.load(self._side_file("fake_opt"), map_location=self.device)
+            have = [st["exp_avg"].numel() for st in state["state"].values() if "exp_avg" in st]
+            want = [p.numel() for p in self.fake_trainer.master_params]
+            saved = sum(len(g["params"]) for g in state["param_groups"])
+            if saved != len(want) or (len(have) == len(want) and have != want):
+                raise ValueError(f"DMTrainLoop: {self._side_file('fake_opt')} holds the state of {saved} parameters "
+                                 f"({sum(have)} elements), this run's fake clock trains {len(want)} ({sum(want)} elements): "
+                                 "was the checkpoint written with / without a gan_head?")
+            self.fake_opt.load_state_dict(state)
         self.resume_step = 0            # `step` already stands at the resumed step: nothing is added to it again
 
     def _side_file(self, prefix):
@@ -676,6 +718,11 @@ class DMTrainLoop(TrainLoop):
         if gen_turn:
             self.mp_trainer.zero_grad()
         self.fake_trainer.zero_grad()
+        if self.gan_head is not None:
+            x_real, real_cond = next(self.real_data)
+            if x_real.shape[0] != batch.shape[0]:
+                raise ValueError(f"DMTrainLoop: real_data yields batches of {x_real.shape[0]} images, the latents come in {batch.shape[0]}")
+            real_cond = {k: v for k, v in (real_cond or {}).items() if k in cond}
         for i in range(0, batch.shape[0], self.microbatch):
             z = batch[i:i + self.microbatch].to(self.device)
             micro_cond = {k: v[i:i + self.microbatch].to(self.device) for k, v in cond.items()}
@@ -683,6 +730,9 @@ class DMTrainLoop(TrainLoop):
                 gen_loss, how = self.diffusion.sid_generator_losses, dict(alpha=self.sid_alpha)
             else:
                 gen_loss, how = self.diffusion.dm_generator_losses, dict(weighting=self.weighting)
+                if self.gan_head is not None:
+                    how.update(gan_head=self.gan_head, gan_gen_weight=self.gan_gen_weight, gan_min_step_frac=self.gan_min_step_frac,
+                               gan_max_step_frac=self.gan_max_step_frac)
             with torch.enable_grad() if gen_turn else torch.no_grad():
                 terms = gen_loss(
                     self.ddp_model, z, self.num_scales, real_model=self.real_model, real_diffusion=self.real_diffusion,
@@ -693,9 +743,18 @@ class DMTrainLoop(TrainLoop):
             x = terms["x"]
             sigmas, weights = self.schedule_sampler.sample(x.shape[0], self.device)
             losses = self.fake_diffusion.training_losses(self.fake_model, x, sigmas, model_kwargs=micro_cond)
-            self._log_loss_dict({"loss": terms["loss"], "dm_norm": terms["dm_norm"], "fake_mse": losses["mse"] * weights,
-                                 "fake_xs_mse": losses["xs_mse"] * weights})
-            self.fake_trainer.backward((losses["loss"] * weights).mean())
+            logs = {"loss": terms["loss"], "dm_norm": terms["dm_norm"], "fake_mse": losses["mse"] * weights,
+                    "fake_xs_mse": losses["xs_mse"] * weights}
+            fake_loss = (losses["loss"] * weights).mean()
+            if self.gan_head is not None:
+                dis = self.fake_diffusion.gan_discriminator_losses(
+                    self.fake_model, self.gan_head, x, x_real[i:i + self.microbatch].to(self.device), self.num_scales,
+                    model_kwargs=micro_cond, real_kwargs={k: v[i:i + self.microbatch].to(self.device) for k, v in real_cond.items()},
+                    generator=self.generator, gan_min_step_frac=self.gan_min_step_frac, gan_max_step_frac=self.gan_max_step_frac)
+                fake_loss = fake_loss + self.gan_dis_weight * dis["loss"].mean()
+                logs.update(gan_gen=terms["gan_loss"], gan_dis=dis["loss"], logit_fake=dis["logit_fake"], logit_real=dis["logit_real"])
+            self._log_loss_dict(logs)
+            self.fake_trainer.backward(fake_loss)
 
     def _anneal_lr(self):
         if not self.lr_anneal_steps:
@@ -715,6 +774,9 @@ class DMTrainLoop(TrainLoop):
             torch.save({k: v.detach().clone() for k, v in self.fake_model.state_dict().items()},
                        os.path.join(self.log_dir, f"fake_model{self.step:06d}.pt"))
             torch.save(self.fake_opt.state_dict(), os.path.join(self.log_dir, f"fake_opt{self.step:06d}.pt"))
+            if self.gan_head is not None:
+                torch.save({k: v.detach().clone() for k, v in self.gan_head.state_dict().items()},
+                           os.path.join(self.log_dir, f"gan_head{self.step:06d}.pt"))
         super().save()                  # ema, opt, then the model file last
 
 

@@ -275,6 +275,16 @@ class UNetModel(PackedWeights, nn.Module):
             return forward_with_grad(self, x, timesteps, y)
         return self.forward_inference(x, timesteps, y)
 
+    def encode(self, x, timesteps, y=None):
+        """The bottleneck features [N, C, h, w] fp32 (the output of middle_block) of the pass that stops there, in eval mode and
+        without a graph: models.cm.unet_train.encoder_input_forward behind the name the GAN term's torch path asks a fake model for."""
+        assert (y is not None) == (self.num_classes is not None), \
+            "must specify y if and only if the model is class-conditional"
+        if not x.is_cuda:
+            raise DxmiError("models.cm.unet.UNetModel runs only on the HIP device path (no CPU fallback)")
+        from .unet_train import encoder_input_forward
+        return encoder_input_forward(self, x, timesteps, y)[0].permute(0, 3, 1, 2).float()
+
     @torch.no_grad()
     def forward_inference(self, x, timesteps, y=None, trace=None):
         tr = (lambda n, v: trace.append((n, v))) if trace is not None else (lambda n, v: None)

@@ -20,7 +20,9 @@ dxmi_dropout_bf16 on the conv2 input: one seed per ResBlock per forward, kept on
 (seed, p) to the gradient (no mask is stored).  With dropout 0, or in eval mode, nothing of it runs.  Inside a StepGraph capture
 (dxmi_hip/graph.py) every site's seed is a host input of the graph, so a replayed step draws the seeds an eager step would draw.
 Parameter gradients come back in net.parameters() order.  train_forward / train_backward / input_forward / input_backward /
-input_vjp keep the tape outside autograd.
+input_vjp keep the tape outside autograd; encoder_forward / encoder_backward / encoder_input_forward / encoder_input_backward are
+the same pass stopped at the bottleneck: the output of middle_block (NHWC bf16) and its cotangent take the place of the model
+output, and no output_blocks / out launch is issued in either direction.
 """
 import math
 import os
@@ -32,7 +34,7 @@ import torch.nn.functional as F
 from dxmi_hip import graph as _graph
 from dxmi_hip import ops
 
-from ..unet_bwd import Backward, pack_t, pool_t, tape_api, up_sum, walk
+from ..unet_bwd import Backward, encoder_api, pack_t, pool_t, tape_api, up_sum, walk
 
 
 def _build_packs_t(net, ps):
@@ -189,6 +191,9 @@ class _EDMUNetFn(torch.autograd.Function):
             tape.append(("push", None, len(hs)))
             hs.append((h, sh))
         h, sh = seq(net.middle_block, h, None, sh, None)
+        ctx.net, ctx.tape, ctx.x, ctx.sinus, ctx.y, ctx.emb_all = net, tape, x, sinus, y, emb_all
+        if getattr(ctx, "encoder_only", False):      # the pass that stops at the bottleneck (unet_bwd.encoder_api): NHWC bf16
+            return h
         for blk in net.output_blocks:
             tape.append(("skip", None, len(hs) - 1))
             skip, sskip = hs.pop()
@@ -196,8 +201,7 @@ class _EDMUNetFn(torch.autograd.Function):
         gn = net.out[0]
         a_out, ctx.s_out = gn_fwd(gn, h, sh, silu=True)
         out = ops.conv2d(a_out, pk["conv_out"], bias=net.out[2].bias, out_nchw_f32=True)
-        ctx.net, ctx.tape, ctx.h_last, ctx.a_out, ctx.x, ctx.sinus, ctx.y = net, tape, h, a_out, x, sinus, y
-        ctx.emb_all = emb_all
+        ctx.h_last, ctx.a_out = h, a_out
         return out
 
     @staticmethod
@@ -215,8 +219,13 @@ class _EDMUNetFn(torch.autograd.Function):
             grads[norm.weight], grads[norm.bias] = dg, db
             return dx0, dx1, d_ss
 
-        # ---- head: out = conv(silu(gn(h_last)))
-        g, _, _ = gn_bwd(net.out[0], ctx.h_last, bw.head(net.out[2], ctx.a_out, d_out), fwd_stats=ctx.s_out)
+        if getattr(ctx, "encoder_only", False):
+            # the tape ends at the bottleneck and holds no "skip" entry: d_out is the gradient of middle_block's output, and the
+            # rows of d_emb_all that belong to decoder blocks stay zero
+            g = d_out
+        else:
+            # ---- head: out = conv(silu(gn(h_last)))
+            g, _, _ = gn_bwd(net.out[0], ctx.h_last, bw.head(net.out[2], ctx.a_out, d_out), fwd_stats=ctx.s_out)
 
         def res_bwd(entry, g):
             _, b, x0, x1, a1p, h, a2, s1, s2, drop = entry
@@ -309,3 +318,5 @@ def forward_with_grad(net, x, timesteps, y=None):
 # the tape outside autograd (models.unet_bwd.tape_api): the loss nodes of models.cm.karras_diffusion, score identity distillation's
 # input_forward / input_backward on both denoisers and the likelihood's input_vjp
 train_forward, train_backward, input_forward, input_backward, input_vjp = tape_api(_EDMUNetFn, 4)
+# the same, stopped at the bottleneck: the classifier head of models.cm.gan_head reads the fake denoiser's middle_block output
+encoder_forward, encoder_backward, encoder_input_forward, encoder_input_backward = encoder_api(_EDMUNetFn, 4)

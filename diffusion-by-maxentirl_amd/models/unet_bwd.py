@@ -8,7 +8,7 @@ Both training forwards leave a tape: a list of entries (kind, module, saved...),
 walk() runs the tape in reverse and owns the skip-connection rule: the x1 gradient of a concat block is parked under the index
 its "skip" entry names and added where that activation was pushed.  Backward holds the state of one backward and the parts around
 the walk that do not depend on the net: head, shortcut data gradient, stem, the rows of a concatenated dense layer, the
-gradients in net.parameters() order.  tape_api() is the tape kept outside autograd.  Nothing here asks which net it serves: the
+gradients in net.parameters() order.  tape_api() is the tape kept outside autograd, encoder_api() its form that stops at the bottleneck.  Nothing here asks which net it serves: the
 GroupNorm, attention and resampling backwards and the embedding graphs stay in the nets' files and come in as callbacks.
 """
 import torch
@@ -149,17 +149,66 @@ class InputTape(Tape):
     input_only = True
 
 
+class EncoderTape(Tape):
+    """The tape of a forward that stops at the bottleneck (encoder_api): its backward starts from the bottleneck's cotangent."""
+    encoder_only = True
+
+
+class EncoderInputTape(InputTape):
+    encoder_only = True
+
+
+def _forward(fn, n_inputs, tape, net, x, t, cond):
+    """fn.forward on `tape` in place of a ctx -> (output, tape); `cond` the conditioning after t, None where left out."""
+    return fn.forward(tape, net, x, t, *cond, *(None,) * (n_inputs - 3 - len(cond))), tape
+
+
+def _eval_forward(fn, n_inputs, tape, net, x, t, cond):
+    """_forward with dropout off: eval mode under no_grad, the net's own mode restored."""
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            return _forward(fn, n_inputs, tape, net, x, t, cond)
+    finally:
+        net.train(was_training)
+
+
+def encoder_api(fn, n_inputs):
+    """-> (encoder_forward, encoder_backward, encoder_input_forward, encoder_input_backward): tape_api's functions for a net whose
+    Function honours ctx.encoder_only, i.e. returns the bottleneck activation h (NHWC bf16) in place of the model output and takes
+    its cotangent d_h (NHWC bf16) in backward.  The truncated tape has no "skip" entry, so walk() runs it unchanged."""
+
+    def encoder_forward(net, x, t, *cond):
+        """The training forward of `net` up to its bottleneck (dropout live in train mode; net.dropout_seeds_used lists the seeds of
+        the sites that ran) -> (h, tape)."""
+        return _forward(fn, n_inputs, EncoderTape(), net, x, t, cond)
+
+    def encoder_backward(tape, d_h):
+        """-> the gradients of net.parameters(), in that order; None for every parameter downstream of the bottleneck (the rows a
+        concatenated dense operator holds for downstream blocks come back as exact zeros)."""
+        return tuple(fn.backward(tape, d_h.contiguous())[n_inputs:])
+
+    def encoder_input_forward(net, x, t, *cond):
+        """encoder_forward in eval mode under no_grad (the net's own mode restored), its tape kept for encoder_input_backward."""
+        return _eval_forward(fn, n_inputs, EncoderInputTape(), net, x, t, cond)
+
+    def encoder_input_backward(tape, d_h):
+        """-> dx (NCHW fp32) = d(d_h . h)/dx: the walk with no parameter-gradient launch.  A tape is walked once."""
+        with torch.no_grad():
+            return fn.backward(tape, d_h.contiguous())[1]
+
+    return encoder_forward, encoder_backward, encoder_input_forward, encoder_input_backward
+
+
 def tape_api(fn, n_inputs):
     """-> (train_forward, train_backward, input_forward, input_backward, input_vjp) of the autograd Function `fn`, whose forward
     takes (ctx, net, x, t, *cond, *params): n_inputs non-parameter inputs, `cond` the conditioning after t (None where left out)."""
 
-    def forward(tape, net, x, t, cond):
-        return fn.forward(tape, net, x, t, *cond, *(None,) * (n_inputs - 3 - len(cond))), tape
-
     def train_forward(net, x, t, *cond):
         """The training forward of `net` (dropout applied in train mode; net.dropout_seeds_used lists its seeds) outside autograd
         -> (model output, tape).  Drop the tape where no backward follows."""
-        return forward(Tape(), net, x, t, cond)
+        return _forward(fn, n_inputs, Tape(), net, x, t, cond)
 
     def train_backward(tape, d_out):
         """The backward of train_forward -> the gradients of net.parameters(), in that order."""
@@ -168,13 +217,7 @@ def tape_api(fn, n_inputs):
     def input_forward(net, x, t, *cond):
         """The first half of input_vjp -> (F, tape): the training forward with dropout off (eval mode, the net's own mode
         restored), its tape kept for input_backward.  For a caller whose cotangent is known only after this forward."""
-        was_training = net.training
-        net.eval()
-        try:
-            with torch.no_grad():
-                return forward(InputTape(), net, x, t, cond)
-        finally:
-            net.train(was_training)
+        return _eval_forward(fn, n_inputs, InputTape(), net, x, t, cond)
 
     def input_backward(tape, v):
         """The second half of input_vjp -> g = d(v . F)/dx for the tape of input_forward: the backward walk with its weight, bias

@@ -705,7 +705,7 @@ int dxmi_pd_lpips_images(const float* f_online, const float* x_t, const float* t
 
 /* Distribution matching distillation of an EDM teacher into a ONE-step generator G(z) = D_theta(sigma_G z, sigma_G)
  * (KarrasDenoiser.dm_generator_losses; Diff-Instruct, Luo et al. 2023, eq. 8 and Algorithm 1; DMD, Yin et al. 2023, eq. 7-8; DMD2,
- * Yin et al. 2024, eq. 2-3, without its GAN term): the launches between the generator and the "real" (teacher) and "fake" (trained
+ * Yin et al. 2024, eq. 2-3; its GAN term is further down, csrc/gan_head.hip): the launches between the generator and the "real" (teacher) and "fake" (trained
  * online on the generator's samples) denoisers.  Tensors as for dxmi_cd_*: fp32 [N, CHW] contiguous, 16-byte aligned, CHW % 4 == 0.
  * t_table: fp32 [num_scales] on the DEVICE (the ladder of dxmi_cd_*); t = t_table[index], and since no t2 is needed every index
  * in [0, num_scales - 1] is legal.  An index outside gives a NaN level; nothing outside the table is read.  One rounding per written
@@ -1407,6 +1407,53 @@ int dxmi_pf_ll_stage(int32_t mode, const float* tab, int32_t rows, const int32_t
                      float* x, const float* model_out, const float* vjp, const float* eps, const int64_t* sample_index, float* k1,
                      float* xt, float* x_in, float* t_out, float* div1, float* ell, float* prior, float* logp, float* bpd, int32_t N,
                      int32_t CHW, void* stream);
+
+/* ---- DMD2's GAN term (csrc/gan_head.hip) -----------------------------------------------------------------------------------------
+ * Yin et al. 2024, "Improved Distribution Matching Distillation for Fast Image Synthesis" (DMD2), section 4.3: a classifier on the
+ * fake denoiser's bottleneck features, trained with the fake denoiser to tell noised real images from noised generated ones, which
+ * gives the generator one more gradient.  The head (models/cm/gan_head.py) is
+ *   Conv2d(C, C, 4, stride 2, pad 1) - GroupNorm - SiLU - Conv2d(C, C, map/2, stride map/2) - GroupNorm - SiLU - Conv2d(C, 1, 1);
+ * its whole-map conv runs on dxmi_linear_* and its GroupNorms on dxmi_groupnorm_generic_*; the entry points here are the rest.
+ * Activations are NHWC bf16, bf16 MFMA operands with fp32 accumulation.  Every launch is bitwise reproducible: the split
+ * contractions write fp32 slabs into the caller's workspace and a second launch sums them in slice order (no float atomics).
+ * DXMI_EINVAL with a message and no launch: a null pointer (but the optional ones), N outside [1, 4096], H not 4 or 8, a C that
+ * dxmi_gan_head_supported refuses, a workspace smaller than dxmi_gan_conv4s2_workspace_bytes, an activation, pack, gradient or
+ * workspace that is not 16-byte aligned (the fp32 parameters w, bias and b may sit at any 4-byte offset: a trainer keeps them as
+ * views into one flat tensor).
+ *
+ * dxmi_gan_head_supported: DXMI_OK where the kernels serve C channels on a map_size x map_size bottleneck (C a multiple of 64 in
+ *   [64, 1024]: 128, 192, 256, 768 and 1024 among them; map_size 4 or 8), else DXMI_EINVAL and a message that names the value.
+ * dxmi_gan_conv4s2_slices(dgrad): the number of fp32 slabs summed per output element (16 filter taps forward, 4 for the data
+ *   gradient): the depth the error bound of a result adds to its contraction length.
+ * dxmi_gan_conv4s2_workspace_bytes(N, H, C, dgrad): bytes of the slab workspace (0: unsupported shape).
+ * dxmi_gan_conv4s2_pack: w fp32 OIHW [C, C, 4, 4] -> w_fwd bf16 [16][Cout][Cin] and w_t bf16 [16][Cin][Cout] (32 C^2 bytes each).
+ * dxmi_gan_conv4s2_fwd: x [N, H, H, C] -> y [N, H/2, H/2, C] = conv(x, w, stride 2, pad 1) + bias (bias NULL: none).  Rows
+ *   outside the map contribute zero.
+ * dxmi_gan_conv4s2_dgrad: dy [N, H/2, H/2, C] -> dx [N, H, H, C], the transposed conv on w_t.
+ * dxmi_gan_conv4s2_wgrad: dw fp32 OIHW [C, C, 4, 4] and db [C] from x and dy (no workspace: the contraction over the rows is
+ *   not split).
+ * dxmi_gan_logit_loss_fwd: a bf16 [N, C], w [C], b [1], sign [N] (-1 or +1) -> logit[n] = w . a[n] + b and
+ *   loss[n] = softplus(sign[n] logit[n]) in the form max(v, 0) + log1p(exp(-|v|)).
+ * dxmi_gan_logit_loss_bwd: with coef[n] = upstream[n] weight sign[n] sigmoid(sign[n] logit[n]):  d_a[n] = coef[n] w (bf16),
+ *   dw = sum_n coef[n] a[n] and db = sum_n coef[n], summed in sample order.  dw and db NULL: not wanted (the input-only backward).
+ * dxmi_gan_join: out = g + (CHW weight c_in(t)) d_xin, t = t_table[indices[n]], c_in = 1 / sqrt(t^2 + sigma_data^2): the DM
+ *   direction g of dxmi_dm_grad_fwd joined with the GAN term's gradient d_xin with respect to the fake denoiser's input, so that
+ *   dxmi_dm_gen_bwd's g / CHW carries both.  out may be g itself; N, CHW and the table as in dxmi_dm_grad_fwd. */
+int dxmi_gan_head_supported(int32_t C, int32_t map_size);
+int64_t dxmi_gan_conv4s2_slices(int32_t dgrad);
+int64_t dxmi_gan_conv4s2_workspace_bytes(int32_t N, int32_t H, int32_t C, int32_t dgrad);
+int dxmi_gan_conv4s2_pack(const float* w, void* w_fwd, void* w_t, int32_t C, void* stream);
+int dxmi_gan_conv4s2_fwd(const void* x, const void* w_fwd, const float* bias, void* y, void* workspace, int64_t workspace_bytes,
+                         int32_t N, int32_t H, int32_t C, void* stream);
+int dxmi_gan_conv4s2_dgrad(const void* dy, const void* w_t, void* dx, void* workspace, int64_t workspace_bytes, int32_t N, int32_t H,
+                           int32_t C, void* stream);
+int dxmi_gan_conv4s2_wgrad(const void* x, const void* dy, float* dw, float* db, int32_t N, int32_t H, int32_t C, void* stream);
+int dxmi_gan_logit_loss_fwd(const void* a, const float* w, const float* b, const float* sign, float* logit, float* loss, int32_t N,
+                            int32_t C, void* stream);
+int dxmi_gan_logit_loss_bwd(const void* a, const float* w, const float* sign, const float* logit, const float* upstream, float weight,
+                            void* d_a, float* dw, float* db, int32_t N, int32_t C, void* stream);
+int dxmi_gan_join(const float* g, const float* d_xin, const int64_t* indices, const float* t_table, int32_t num_scales, float* out,
+                  int32_t N, int32_t CHW, float weight, float sigma_data, void* stream);
 
 #ifdef __cplusplus
 }
