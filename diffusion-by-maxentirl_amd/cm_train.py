@@ -38,8 +38,10 @@ levels of the fake denoiser's loss are EDM's (LogNormalSampler's defaults, as tr
 --index_sampler lognormal are errors with it.  Its model%06d.pt is what `generate_large.py --karras_sampler dm --pretrained ...` reads.
 --dm_objective sid trains the same generator by score identity distillation instead (KarrasDenoiser.sid_generator_losses; SiD, Zhou et
 al. 2024: the loss is differentiated through both denoisers' inputs): --sid_alpha (1.2), and --gen_sigma, the generator's input level
-(0 = sigma_max; SiD's runs use 2.5, and generate_large.py must then be given the same --gen_sigma).  --dm_weighting none does not go
-with it, and the three flags are errors outside --training_mode dm.
+(0 = sigma_max; SiD's runs use 2.5, and generate_large.py must then be given the same --gen_sigma).  --gen_sigmas 80,5,1,0.3 trains a
+K-step generator on that ladder by backward simulation instead (DMD2 section 4.4-4.5; not with --gen_sigma or --dm_objective sid;
+generate_large.py takes the same --gen_sigmas).  --dm_weighting none does not go
+with it, and these flags are errors outside --training_mode dm.
 --dm_gan True adds DMD2's GAN term (models.cm.gan_head.GANHead on the fake denoiser's bottleneck, sized from the net: its bottleneck
 channels and image_size / 2^(levels - 1); KarrasDenoiser.gan_discriminator_losses on the fake clock, the generator's loss gains
 --gan_gen_weight softplus(-logit)): it needs real images, --data_npz PATH or --synthetic_data True, and does not go with --dm_objective
@@ -104,6 +106,16 @@ ICT_SETTINGS = dict(training_mode="consistency_training", loss_norm="pseudo-hube
                     target_ema_mode="fixed", start_ema=0.0, start_scales=10, end_scales=1280, index_sampler="lognormal")
 
 
+def parse_gen_sigmas(text):
+    """"80,5,1,0.3" -> the checked ladder of a K-step generator, fp32 values as python floats (ValueError with the reason)."""
+    from models.cm.karras_diffusion import gen_ladder
+    try:
+        vals = [float(v) for v in str(text).split(",")]
+    except ValueError:
+        raise ValueError("comma-separated levels, largest first, e.g. 80,5,1,0.3") from None
+    return gen_ladder("--gen_sigmas", vals).sigmas
+
+
 def parse_args(argv=None):
     defaults = dict(model_and_diffusion_defaults())
     defaults.update(cm_train_defaults())
@@ -112,7 +124,7 @@ def parse_args(argv=None):
                     max_iters=0, weight_decay=0.0, lr_anneal_steps=0, log_interval=10, save_interval=10000, resume_checkpoint="",
                     fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False,
                     huber_c=0.0, index_sampler="uniform", p_mean=-1.1, p_std=2.0, ict=False, gen_update_every=5, fake_lr=0.0,
-                    dm_weighting="dmd", dm_num_scales=1000, dm_objective="dmd", sid_alpha=1.2, gen_sigma=0.0, dm_gan=False,
+                    dm_weighting="dmd", dm_num_scales=1000, dm_objective="dmd", sid_alpha=1.2, gen_sigma=0.0, gen_sigmas="", dm_gan=False,
                     gan_gen_weight=3e-3, gan_dis_weight=1e-2, gan_max_step_frac=1.0)
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
@@ -152,8 +164,20 @@ def parse_args(argv=None):
             ap.error(f"--sid_alpha {args.sid_alpha}: a finite number (SiD: 1.2; 1 is its base form)")
         if not (math.isfinite(args.gen_sigma) and args.gen_sigma >= 0):
             ap.error(f"--gen_sigma {args.gen_sigma}: a positive level, or 0 for sigma_max")
+        if args.gen_sigmas:
+            if given("--gen_sigma"):
+                ap.error("--gen_sigmas (the ladder of a K-step generator) does not go with --gen_sigma (the one-step level)")
+            try:
+                args.gen_sigmas = parse_gen_sigmas(args.gen_sigmas)
+            except ValueError as e:
+                ap.error(f"--gen_sigmas {args.gen_sigmas}: {e}")
+            if args.dm_objective == "sid" and len(args.gen_sigmas) > 1:
+                ap.error("--gen_sigmas with more than one level does not go with --dm_objective sid: backward simulation is built for "
+                         "--dm_objective dmd alone")
+        else:
+            args.gen_sigmas = None
     else:
-        for flag in ("--dm_objective", "--sid_alpha", "--gen_sigma", "--dm_gan"):
+        for flag in ("--dm_objective", "--sid_alpha", "--gen_sigma", "--gen_sigmas", "--dm_gan"):
             if given(flag):
                 ap.error(f"{flag} belongs to --training_mode dm, not to --training_mode {args.training_mode}")
     if not args.dm_gan:
@@ -293,15 +317,16 @@ def main_dm(args, device, local_rank, world):
     loop = DMTrainLoop(**gan, model=model, diffusion=diffusion, real_model=real_model, real_diffusion=real_diffusion, fake_model=fake_model,
                        num_scales=args.dm_num_scales, gen_update_every=args.gen_update_every, fake_lr=args.fake_lr or None,
                        weighting=args.dm_weighting, objective=args.dm_objective, sid_alpha=args.sid_alpha,
-                       gen_sigma=args.gen_sigma or None, data=data, batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr,
+                       gen_sigma=args.gen_sigma or None, gen_sigmas=args.gen_sigmas, data=data, batch_size=args.batch_size, microbatch=args.microbatch, lr=args.lr,
                        ema_rate=args.ema_rate, log_interval=args.log_interval, save_interval=args.save_interval,
                        resume_checkpoint=args.resume_checkpoint, use_fp16=args.use_fp16, fp16_scale_growth=args.fp16_scale_growth,
                        schedule_sampler=LogNormalSampler(), weight_decay=args.weight_decay,
                        lr_anneal_steps=args.max_iters if args.max_iters else args.lr_anneal_steps, log_dir=args.log_dir)
     print0(f"dm: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
            + (f"objective sid (alpha {args.sid_alpha}), " if args.dm_objective == "sid" else f"weighting {args.dm_weighting}, ")
-           + f"gen_sigma {args.gen_sigma or diffusion.sigma_max}, "
-           f"generator update every {args.gen_update_every} iterations"
+           + (f"gen_sigmas {args.gen_sigmas} (K = {len(args.gen_sigmas)}), " if args.gen_sigmas
+              else f"gen_sigma {args.gen_sigma or diffusion.sigma_max}, ")
+           + f"generator update every {args.gen_update_every} iterations"
            + (f", GAN term (generator weight {args.gan_gen_weight}, discriminator weight {args.gan_dis_weight})" if args.dm_gan else ""))
     loop.run_loop()
     if loop.logged:

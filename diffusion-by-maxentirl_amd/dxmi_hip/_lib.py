@@ -144,6 +144,13 @@ SIGNATURES = {
     "dxmi_dm_grad_fwd": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_float,
                                                                              c_int, c_void_p]),
     "dxmi_dm_gen_bwd": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_float, c_void_p]),
+    "dxmi_dmms_in": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 3 + [c_int, c_int, c_float, c_void_p]),
+    "dxmi_dmms_stage": (c_int, [c_void_p] * 3 + [ctypes.c_uint32, ctypes.c_uint64] + [c_void_p] * 2 + [c_int, c_int] + [c_void_p] * 3
+                        + [c_int, c_int, c_float, c_void_p]),
+    "dxmi_dmms_prep": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 5 + [c_int, c_int] + [c_float] * 3
+                       + [c_void_p]),
+    "dxmi_dmms_out": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
+    "dxmi_dmms_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_int, c_int, c_float, c_void_p]),
     "dxmi_sid_grad_fwd": (c_int, [c_void_p] * 6 + [c_int, c_float] + [c_void_p] * 5 + [c_int, c_int, c_float, c_float, c_int, c_float,
                                                                                         c_float, c_int, c_void_p]),
     "dxmi_sid_join": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),

@@ -1345,6 +1345,102 @@ def dm_gen_bwd(upstream, g, gen_sigma, sigma_data=0.5):
     return d
 
 
+def _dmms_ladder(what, gen_sigmas, first, steps=None, need_steps=False):
+    """The ladder and the per-image steps of the K-step generator's launches (csrc/dm_train.hip): gen_sigmas fp32 [K >= 1] contiguous
+    on the device of `first`, steps None or int64 [N] contiguous there.  -> K"""
+    if gen_sigmas is None or (need_steps and steps is None):
+        raise _lib.DxmiError(f"{what}: a needed operand is None")
+    _need_cuda(gen_sigmas, steps)
+    if not (gen_sigmas.dtype == torch.float32 and gen_sigmas.is_contiguous() and gen_sigmas.dim() == 1 and gen_sigmas.numel() >= 1
+            and gen_sigmas.device == first.device):
+        raise _lib.DxmiError(f"{what}: gen_sigmas must be a contiguous fp32 [K >= 1] on the operands' device")
+    if steps is not None and not (steps.dtype == torch.int64 and steps.is_contiguous() and steps.dim() == 1
+                                  and steps.numel() == first.shape[0] and steps.device == first.device):
+        raise _lib.DxmiError(f"{what}: steps must be {first.shape[0]} contiguous int64 values on the operands' device")
+    return gen_sigmas.numel()
+
+
+def dmms_in(z, gen_sigmas, sigma_data=0.5):
+    """-> (x = sigma_0 z, x_in = c_in(sigma_0) x, time [N] = 250 ln(sigma_0 + 1e-44)): step 0 of the K-step generator
+    (dxmi_dmms_in).  gen_sigmas: the fp32 device ladder [K]."""
+    what = "dxmi_dmms_in"
+    if z is None:
+        raise _lib.DxmiError(f"{what}: no latents")
+    N, CHW, _ = _batch_operands(what, z, chw4=True)
+    K = _dmms_ladder(what, gen_sigmas, z)
+    sd = _dm_scalar(what, "sigma_data", sigma_data)
+    x, x_in, t = torch.empty_like(z), torch.empty_like(z), torch.empty(N, dtype=torch.float32, device=z.device)
+    check(load().dxmi_dmms_in(_ptr(z), _ptr(gen_sigmas), K, _ptr(x), _ptr(x_in), _ptr(t), N, CHW, sd, _stream()), what)
+    return x, x_in, t
+
+
+def dmms_stage(f_gen, stage, gen_sigmas, x, x_in, t_out, steps=None, eps=None, sample_index=None, seed=0, draw=0, sigma_data=0.5):
+    """ONE launch between generator evaluations `stage` and `stage` + 1, in place (dxmi_dmms_stage): for an image with steps None
+    or steps[n] > stage, x = G_stage(x) + eps sigma_{stage+1}, x_in = c_in(sigma_{stage+1}) x, t_out[n] its time; an image with
+    steps[n] <= stage is frozen (its rows are neither read nor written).  eps [N, ...] given, or sample_index (int64 [N]) with seed /
+    draw: made in the launch, the values of randn_indexed(sample_index, x.shape[1:], seed, draw).  Not both."""
+    what = "dxmi_dmms_stage"
+    if f_gen is None or x is None or x_in is None or t_out is None:
+        raise _lib.DxmiError(f"{what}: a needed operand is None")
+    if (eps is None) == (sample_index is None):
+        raise _lib.DxmiError(f"{what}: noise is either given (eps) or made here (sample_index): exactly one of them")
+    N, CHW, _ = _batch_operands(what, f_gen, same=(x, x_in, eps), per_sample=(t_out,), chw4=True)
+    K = _dmms_ladder(what, gen_sigmas, f_gen, steps)
+    if not (0 <= int(stage) <= K - 2):
+        raise _lib.DxmiError(f"{what}: stage {stage!r} outside [0, K - 2 = {K - 2}]")
+    if sample_index is not None:
+        _need_cuda(sample_index)
+        if not (sample_index.dtype == torch.int64 and sample_index.is_contiguous() and sample_index.shape == (N,)
+                and sample_index.device == f_gen.device):
+            raise _lib.DxmiError(f"{what}: sample_index must be a contiguous int64 [{N}] on the operands' device")
+    sd = _dm_scalar(what, "sigma_data", sigma_data)
+    check(load().dxmi_dmms_stage(_ptr(f_gen), _ptr(eps), _ptr(sample_index), int(draw) & 0xFFFFFFFF, int(seed) & _U64, _ptr(steps),
+                                 _ptr(gen_sigmas), K, int(stage), _ptr(x), _ptr(x_in), _ptr(t_out), N, CHW, sd, _stream()), what)
+
+
+def dmms_prep(f_gen, x_k, noise, steps, gen_sigmas, indices, t_table, sigma_data=0.5, real_sigma_data=0.5, fake_sigma_data=None):
+    """dm_gen_prep of the K-step generator (dxmi_dmms_prep): x = c_skip(sigma_k) x_k + c_out(sigma_k) f_gen with sigma_k =
+    gen_sigmas[steps[n]] -> (x, x_t, x_in_real, time, x_in_fake | None)."""
+    what = "dxmi_dmms_prep"
+    N, CHW, S = _dm_operands(what, f_gen, indices, t_table, same=(x_k, noise))
+    K = _dmms_ladder(what, gen_sigmas, f_gen, steps, need_steps=True)
+    sd, sdr = _dm_scalar(what, "sigma_data", sigma_data), _dm_scalar(what, "sigma_data", real_sigma_data)
+    own = fake_sigma_data is not None and float(fake_sigma_data) != float(real_sigma_data)
+    sdf = _dm_scalar(what, "sigma_data", fake_sigma_data) if own else sdr
+    x, x_t, x_in = torch.empty_like(f_gen), torch.empty_like(f_gen), torch.empty_like(f_gen)
+    t = torch.empty(N, dtype=torch.float32, device=f_gen.device)
+    x_fk = torch.empty_like(f_gen) if own else None
+    check(load().dxmi_dmms_prep(_ptr(f_gen), _ptr(x_k), _ptr(noise), _ptr(steps), _ptr(gen_sigmas), K, _ptr(indices), _ptr(t_table), S,
+                                _ptr(x), _ptr(x_t), _ptr(x_in), _ptr(t), _ptr(x_fk), N, CHW, sd, sdr, sdf, _stream()), what)
+    return x, x_t, x_in, t, x_fk
+
+
+def dmms_out(f_gen, x_k, gen_sigmas, sigma_data=0.5, clip=True, out=None):
+    """-> x = c_skip(sigma_{K-1}) x_k + c_out(sigma_{K-1}) f_gen, clamped to [-1, 1] when `clip` (dxmi_dmms_out)."""
+    what = "dxmi_dmms_out"
+    if f_gen is None or x_k is None:
+        raise _lib.DxmiError(f"{what}: f_gen and x_k are needed")
+    N, CHW, _ = _batch_operands(what, f_gen, same=(x_k, out), chw4=True)
+    K = _dmms_ladder(what, gen_sigmas, f_gen)
+    sd = _dm_scalar(what, "sigma_data", sigma_data)
+    x = torch.empty_like(f_gen) if out is None else out
+    check(load().dxmi_dmms_out(_ptr(f_gen), _ptr(x_k), _ptr(gen_sigmas), K, _ptr(x), N, CHW, sd, int(bool(clip)), _stream()), what)
+    return x
+
+
+def dmms_bwd(upstream, g, steps, gen_sigmas, sigma_data=0.5):
+    """-> d(f_gen) = ((upstream[n] / CHW) g[n]) c_out(gen_sigmas[steps[n]]) for the device upstream gradient [N] (dxmi_dmms_bwd)."""
+    what = "dxmi_dmms_bwd"
+    if upstream is None or g is None:
+        raise _lib.DxmiError(f"{what}: no upstream gradient / no g of the forward")
+    N, CHW, _ = _batch_operands(what, g, per_sample=(upstream,), chw4=True)
+    K = _dmms_ladder(what, gen_sigmas, g, steps, need_steps=True)
+    sd = _dm_scalar(what, "sigma_data", sigma_data)
+    d = torch.empty_like(g)
+    check(load().dxmi_dmms_bwd(_ptr(upstream), _ptr(g), _ptr(steps), _ptr(gen_sigmas), K, _ptr(d), N, CHW, sd, _stream()), what)
+    return d
+
+
 def sid_grad_fwd(f_real, f_fake, x, x_t, indices, t_table, alpha=1.2, real=None, fake=None, outs=None):
     """-> (v_real, v_fake, d_dir [N, ...], loss [N], s [N]) of score identity distillation (dxmi_sid_grad_fwd): with D_r, D_f as in
     dm_grad_fwd, delta = D_r - D_f, e = D_f - x, s = mean|x - D_r|: loss = ((1 - alpha) sum(delta^2) + sum(delta e)) / (CHW s);

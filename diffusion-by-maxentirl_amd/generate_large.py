@@ -14,7 +14,9 @@ outside the accelerated path and runs only when those are present; --skip_fid wr
 `--karras_sampler {heun,dpm,euler,ancestral,progdist}` samples the EDM teacher instead (progdist: a progressively distilled
 student of it, `--pretrained` a model%06d.pt of `cm_train.py --training_mode progdist`, NFE = `--karras_steps`; `--karras_sampler dm`: a
 one-step distribution-matching generator, `--pretrained` a model%06d.pt of `cm_train.py --training_mode dm`, NFE = 1,
-`--gen_sigma` its input level (0 = sigma_max; the level it was trained at, 2.5 for score identity distillation as SiD runs it), and
+`--gen_sigma` its input level (0 = sigma_max; the level it was trained at, 2.5 for score identity distillation as SiD runs it), or
+`--gen_sigmas 80,5,1,0.3` the ladder of a K-step generator (the one given to `cm_train.py --gen_sigmas`; NFE = K; with `--generator
+determ` / `determ-indiv` the noise between the steps is indexed per image, so samples_N.npz is the same whatever the batch size), and
 `--karras_steps`, `--rho` and the churn and solver flags are refused with it) (models.cm.karras_diffusion.karras_sample,
 reference models/cm/karras_diffusion.py:354-420): `--karras_steps` (40), `--rho`, `--s_churn`, `--s_tmin`, `--s_tmax`,
 `--s_noise`.  Weights: `--pretrained [PATH]` loads a plain U-Net state dict (PATH, or the config's training.pretrained_path),
@@ -95,6 +97,8 @@ def build_parser():
     ap.add_argument("--rho", type=float, default=None, help="Karras schedule rho (default 7.0)")
     ap.add_argument("--gen_sigma", type=float, default=None, help="--karras_sampler dm: the generator's input level, the one it was "
                                                                   "trained at (cm_train.py --gen_sigma; default 0 = sigma_max)")
+    ap.add_argument("--gen_sigmas", type=str, default=None, help="--karras_sampler dm: the ladder of a K-step generator, largest level "
+                                                                 "first, e.g. 80,5,1,0.3 (cm_train.py --gen_sigmas); not with --gen_sigma")
     ap.add_argument("--s_churn", type=float, default=None, help="Karras churn (default 0)")
     ap.add_argument("--s_tmin", type=float, default=None, help="churn window lower end (default 0)")
     ap.add_argument("--s_tmax", type=float, default=None, help="churn window upper end (default inf)")
@@ -134,6 +138,8 @@ def parse_args(argv=None):
             ap.error(f"{', '.join(given)} only apply with --karras_sampler dpmpp / sde-dpmpp")
     if args.gen_sigma is not None and args.karras_sampler != "dm":
         ap.error("--gen_sigma only applies with --karras_sampler dm")
+    if args.gen_sigmas is not None and args.karras_sampler != "dm":
+        ap.error("--gen_sigmas only applies with --karras_sampler dm")
     if args.cm_sampler is not None:
         return parse_cm_args(ap, args), unknown
     given = [f"--{k}" for k in CM_FLAGS if getattr(args, k) is not None]
@@ -152,6 +158,14 @@ def parse_args(argv=None):
             given = [f"--{k}" for k in ("karras_steps", "rho") + CHURN_FLAGS if getattr(args, k) is not None]
             if given:
                 ap.error(f"{', '.join(given)}: --karras_sampler dm is one network evaluation at sigma_max, it has no steps, ladder or churn")
+            if args.gen_sigmas is not None:
+                if args.gen_sigma is not None:
+                    ap.error("--gen_sigmas (the ladder of a K-step generator) does not go with --gen_sigma (the one-step level)")
+                from cm_train import parse_gen_sigmas
+                try:
+                    args.gen_sigmas = parse_gen_sigmas(args.gen_sigmas)
+                except ValueError as e:
+                    ap.error(f"--gen_sigmas {args.gen_sigmas}: {e}")
             args.gen_sigma = 0.0 if args.gen_sigma is None else args.gen_sigma
             if not (math.isfinite(args.gen_sigma) and args.gen_sigma >= 0):
                 ap.error(f"--gen_sigma {args.gen_sigma}: a positive level, or 0 for sigma_max")
@@ -382,7 +396,7 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
         extra = dict(algorithm=DPM_SAMPLERS[sampler], order=args.solver_order, solver_type=args.solver_type, skip_type=args.skip_type,
                      lower_order_final=not args.no_lower_order_final, rho=args.rho)
     elif args.karras_sampler == "dm":              # a distribution-matching generator: one evaluation at sigma_max
-        sampler, steps, nfe, extra = "dm", 1, 1, {}
+        sampler, steps, nfe, extra = "dm", len(args.gen_sigmas or (0,)), len(args.gen_sigmas or (0,)), {}
     else:
         sampler, steps, nfe = args.karras_sampler, args.karras_steps, karras_nfe(args.karras_sampler, args.karras_steps)
         extra = dict(rho=args.rho, s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax, s_noise=args.s_noise)
@@ -407,8 +421,8 @@ def main_karras(args, cfg, unet, diffusion, device, local_rank, world, output_pa
             sample = edm_dpm_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
                                     sigma_max=diffusion.sigma_max, use_graph=use_graph, generator=generator, **extra)
         elif sampler == "dm":
-            sample = dm_sample(diffusion, unet, shape, gen_sigma=args.gen_sigma or None, model_kwargs=kw, device=device,
-                               generator=generator)
+            sample = dm_sample(diffusion, unet, shape, gen_sigma=None if args.gen_sigmas else (args.gen_sigma or None), model_kwargs=kw,
+                               device=device, generator=generator, gen_sigmas=args.gen_sigmas)
         elif sampler == "progdist":             # its own entry point: karras_sample keeps refusing this sampler
             sample = progdist_sample(diffusion, unet, shape, steps, model_kwargs=kw, device=device, sigma_min=diffusion.sigma_min,
                                      sigma_max=diffusion.sigma_max, rho=args.rho, use_graph=use_graph, generator=generator)

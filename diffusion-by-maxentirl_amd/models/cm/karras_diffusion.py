@@ -80,6 +80,7 @@ from dxmi_hip import graph as _graph
 from dxmi_hip import ops
 from dxmi_hip._lib import DxmiError
 from .nn import append_dims, append_zero, mean_flat
+from .random_util import DeterministicGenerator
 from .unet_train import (encoder_backward, encoder_forward, encoder_input_backward, encoder_input_forward, input_backward,
                          input_forward, train_backward, train_forward)
 
@@ -379,6 +380,74 @@ def dm_index_range(num_scales, min_step_frac=0.02, max_step_frac=0.98):
     return lo, hi
 
 
+class GenLadder(_HostTable):
+    """The levels sigma_0 > ... > sigma_{K-1} > 0 of a K-step generator (DMD2, Yin et al. 2024, section 4.4), as fp32 values:
+    `sigmas` (python floats that are exactly the fp32 entries) and `table`, fp32 [K]."""
+
+    def __init__(self, what, gen_sigmas):
+        try:
+            vals = [float(v) for v in gen_sigmas]
+        except TypeError:
+            raise ValueError(f"{what}: gen_sigmas must be a sequence of levels, got {gen_sigmas!r}") from None
+        if not vals:
+            raise ValueError(f"{what}: gen_sigmas must hold at least one level")
+        if not all(math.isfinite(v) and v > 0 for v in vals):
+            raise ValueError(f"{what}: every level of gen_sigmas must be positive and finite, got {vals}")
+        table = torch.tensor(vals, dtype=torch.float64).to(torch.float32)
+        self.sigmas = tuple(float(v) for v in table)
+        if not all(math.isfinite(v) and v > 0 for v in self.sigmas) or any(a <= b for a, b in zip(self.sigmas, self.sigmas[1:])):
+            raise ValueError(f"{what}: gen_sigmas must decrease strictly (as fp32 values) and stay positive and finite, got {vals}")
+        super().__init__(table)
+
+    def __len__(self):
+        return len(self.sigmas)
+
+
+_GEN_LADDERS = {}
+
+
+def gen_ladder(what, gen_sigmas):
+    """gen_sigmas checked -> its GenLadder (one per ladder: the device table is uploaded once)."""
+    if isinstance(gen_sigmas, GenLadder):
+        return gen_sigmas
+    if torch.is_tensor(gen_sigmas):
+        gen_sigmas = gen_sigmas.detach().reshape(-1).tolist()
+    try:
+        key = tuple(float(v) for v in gen_sigmas)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: gen_sigmas must be a sequence of levels, got {gen_sigmas!r}") from None
+    return _memo(_GEN_LADDERS, key, 64, lambda: GenLadder(what, key))
+
+
+def dm_step_sigmas(K, sigma_hi, sigma_lo, rho=7.0):
+    """The Karras-spaced ladder of a K-step generator between its two ends -> K fp32 values as python floats, sigma_hi first:
+    (hi^(1/rho) + j / (K - 1) (lo^(1/rho) - hi^(1/rho)))^rho; K = 1 gives (sigma_hi,).  A convenience: no ladder here is tuned."""
+    K, hi, lo, rho = int(K), float(sigma_hi), float(sigma_lo), float(rho)
+    if K < 1:
+        raise ValueError(f"dm_step_sigmas: K must be at least 1, got {K}")
+    if not (math.isfinite(hi) and math.isfinite(lo) and 0 < lo <= hi and math.isfinite(rho) and rho > 0) or (K > 1 and lo == hi):
+        raise ValueError(f"dm_step_sigmas: need 0 < sigma_lo < sigma_hi (finite; equal ends only for K = 1) and rho > 0, got "
+                         f"{sigma_hi}, {sigma_lo}, rho {rho}")
+    a, b = hi ** (1 / rho), lo ** (1 / rho)
+    vals = [(a + (j / (K - 1) if K > 1 else 0.0) * (b - a)) ** rho for j in range(K)]
+    return gen_ladder("dm_step_sigmas", vals).sigmas
+
+
+class _GenSteps:
+    """What stands where gen_sigma stood in _dm_loss and its nodes when the generator has K > 1 steps: the ladder's device table,
+    the per-image graded steps (int64 [N] on the device) and the simulation noise [K - 1, N, C, H, W]."""
+
+    def __init__(self, tab, steps, sim_noise):
+        self.tab, self.steps, self.sim_noise = tab, steps, sim_noise
+
+
+def _dm_gen_bwd(up, g, gen, sigma_data):
+    """dm_gen_bwd at sigma_G, or dmms_bwd at every image's own level."""
+    if isinstance(gen, _GenSteps):
+        return ops.dmms_bwd(up, g, gen.steps, gen.tab, sigma_data)
+    return ops.dm_gen_bwd(up, g, gen, sigma_data)
+
+
 class _DMSurrogate(torch.autograd.Function):
     """The distribution-matching term of x for the stop-gradient direction g (DMD eq. 7): the value is 0.5 mean_flat(g^2), the
     gradient d loss_n / d x = g_n / CHW, that of the surrogate 0.5 mean_flat((x - sg(x - g))^2) without its rounding of x - (x - g)."""
@@ -413,11 +482,31 @@ def _scal_kw(d):
 
 
 def _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep):
-    """dm_gen_in -> the generator's forward -> (F, tape); keep=False as in _dm_loss."""
-    x_in, t_g = ops.dm_gen_in(z, gen_sigma, diffusion.sigma_data)
+    """dm_gen_in -> the generator's forward -> (F, tape, None); keep=False as in _dm_loss.
+    gen_sigma a _GenSteps: backward simulation (DMD2 section 4.5) -> (F, tape, x_k).  dmms_in, then K - 1 x (the no-grad forward of
+    the whole batch, dmms_stage: images whose step is reached are frozen), which leaves x_k[n] = x_{k_n} and the graded
+    evaluation's input and time in place; no tape is kept before the graded evaluation."""
+    def no_grad_forward(x_in, t_g):
+        return _train_forward_no_grad(net, x_in, t_g, y) if net.training and net.dropout > 0 else net.forward_inference(x_in, t_g, y)
+    x_k = None
+    if isinstance(gen_sigma, _GenSteps):
+        ms = gen_sigma
+        x_k, x_in, t_g = ops.dmms_in(z, ms.tab, diffusion.sigma_data)
+        for j in range(ms.tab.numel() - 1):
+            ops.dmms_stage(no_grad_forward(x_in, t_g), j, ms.tab, x_k, x_in, t_g, steps=ms.steps, eps=ms.sim_noise[j],
+                           sigma_data=diffusion.sigma_data)
+    else:
+        x_in, t_g = ops.dm_gen_in(z, gen_sigma, diffusion.sigma_data)
     if keep:
-        return train_forward(net, x_in, t_g, y)
-    return (_train_forward_no_grad(net, x_in, t_g, y) if net.training and net.dropout > 0 else net.forward_inference(x_in, t_g, y)), None
+        return train_forward(net, x_in, t_g, y) + (x_k,)
+    return no_grad_forward(x_in, t_g), None, x_k
+
+
+def _dm_gen_prep(diffusion, F, z, x_k, noise, indices, tab, gen_sigma, sdr, sdf):
+    """dm_gen_prep at sigma_G, or dmms_prep on the simulated states x_k at every image's own level."""
+    if isinstance(gen_sigma, _GenSteps):
+        return ops.dmms_prep(F, x_k, noise, gen_sigma.steps, gen_sigma.tab, indices, tab, diffusion.sigma_data, sdr, sdf)
+    return ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, diffusion.sigma_data, sdr, sdf)
 
 
 def _dm_gan_term(fake, fake_diffusion, x, g, tab, y, gan, keep):
@@ -443,10 +532,10 @@ def _dm_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, nois
     -> (loss, x, s, (tape, g)), the last being what _DMLossFn.backward reads.  keep=False: no backward follows, so the generator
     runs forward_inference (the training forward where its dropout is live) and no tape is kept.
     gan = (head, weight, gan_noise, gan_indices): DMD2's GAN term (_dm_gan_term) joins the loss and the direction, and the result
-    gains (gan_loss, gan_logit)."""
-    F, tape = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
-    x, x_t, xr_in, t, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, diffusion.sigma_data, real_diffusion.sigma_data,
-                                              fake_diffusion.sigma_data)
+    gains (gan_loss, gan_logit).  gen_sigma a _GenSteps: the K-step generator (_dm_gen_forward); from x on nothing differs."""
+    F, tape, x_k = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
+    x, x_t, xr_in, t, xf_in = _dm_gen_prep(diffusion, F, z, x_k, noise, indices, tab, gen_sigma, real_diffusion.sigma_data,
+                                           fake_diffusion.sigma_data)
     F_r = real.forward_inference(xr_in, t, y)
     F_f = fake.forward_inference(xr_in if xf_in is None else xf_in, t, y)
     g, loss, s = ops.dm_grad_fwd(F_r, F_f, x, x_t, indices, tab, weighting, real=_scal_kw(real_diffusion), fake=_scal_kw(fake_diffusion))
@@ -472,7 +561,7 @@ class _DMLossFn(torch.autograd.Function):
     def backward(ctx, g_loss, g_x, g_s):
         if g_loss is None:
             return (None,) * len(ctx.needs_input_grad)
-        dF = ops.dm_gen_bwd(g_loss.detach().float().contiguous(), ctx.g, *ctx.gen)
+        dF = _dm_gen_bwd(g_loss.detach().float().contiguous(), ctx.g, *ctx.gen)
         ctx.g = None
         grads = train_backward(ctx.tape, dF)
         ctx.tape = None
@@ -543,7 +632,7 @@ def _sid_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noi
     dxmi_sid_grad_fwd forms their cotangents, input_backward walks each tape (dropped at once), dxmi_sid_join forms g = CHW
     d loss / d x, which _SiDLossFn.backward hands to dxmi_dm_gen_bwd.  keep=False: no backward follows: the generator as in
     _dm_loss(keep=False), the denoisers' forward_inference, and only loss, x and s are formed."""
-    F, tape = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
+    F, tape, _ = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
     sdr, sdf = real_diffusion.sigma_data, fake_diffusion.sigma_data
     x, x_t, xr_in, _, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, diffusion.sigma_data, sdr, sdf)
     xf_in = xr_in if xf_in is None else xf_in
@@ -879,7 +968,7 @@ class KarrasDenoiser:
     def dm_generator_losses(self, model, z, num_scales=1000, real_model=None, real_diffusion=None, fake_model=None, fake_diffusion=None,
                             model_kwargs=None, noise=None, indices=None, generator=None, gen_sigma=None, weighting="dmd",
                             min_step_frac=0.02, max_step_frac=0.98, gan_head=None, gan_gen_weight=3e-3, gan_noise=None, gan_indices=None,
-                            gan_min_step_frac=0.0, gan_max_step_frac=1.0):
+                            gan_min_step_frac=0.0, gan_max_step_frac=1.0, gen_sigmas=None, steps=None, sim_noise=None):
         """Distribution-matching loss of the one-step generator G(z) = D_theta(sigma_G z, sigma_G) (Diff-Instruct, Luo et al. 2023;
         DMD, Yin et al. 2023, eq. 7-8; DMD2, Yin et al. 2024, its GAN term under gan_head below) -> {"loss": [N], "x": [N, C, H, W] detached fp32,
         "dm_norm": [N]}.  x = G(z) is diffused to x_t = x + noise t, t = cd_levels(num_scales)[index]; with D_r / D_f the denoised
@@ -895,12 +984,25 @@ class KarrasDenoiser:
         gan_loss_n = softplus(-logit_n): loss = the DM loss + gan_gen_weight gan_loss, d loss_n / d x = g_n / CHW + gan_gen_weight
         d gan_loss_n / d x, reaching the generator through x alone (neither the head nor the fake denoiser receives a gradient),
         and the result gains "gan_loss" and "gan_logit", [N], detached.  gan_indices (uniform over dm_index_range(S, gan_min_step_frac,
-        gan_max_step_frac)) and then gan_noise are drawn after the draws above.  DESIGN 5.39."""
+        gan_max_step_frac)) and then gan_noise are drawn after the draws above.  DESIGN 5.39.
+        gen_sigmas (excludes gen_sigma): the ladder sigma_0 > ... > sigma_{K-1} > 0 of a K-step generator trained by backward
+        simulation (DMD2, Yin et al. 2024, section 4.4-4.5).  Step j is G_j(x) = D_theta(x, sigma_j); the sampler's states
+        are x_0 = sigma_0 z and x_{j+1} = G_j(x_j) + sigma_{j+1} eps_j (dm_sample), never clamped.  Image n draws a step k_n uniformly
+        from {0 .. K-1}; x_{k_n} is made by the current generator under no_grad from x_0 with the noise sim_noise[j] of stage j, the
+        graded evaluation is x = G_{k_n}(x_{k_n}), and from x on everything above holds unchanged; no gradient enters the simulation.
+        steps: int64 [N] given, else drawn BEFORE every draw above; sim_noise: [K - 1, N, C, H, W] given, else one draw per stage,
+        in stage order, AFTER every draw above; both from `generator` where given.  The result gains "steps" (int64 [N]).  K = 1
+        makes neither draw and is the one-step call at gen_sigma = gen_sigmas[0]."""
         what = "dm_generator_losses"
         model_kwargs, fake_diffusion = self._dm_refusals(what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs)
         if weighting not in DM_WEIGHTINGS:
             raise ValueError(f"dm_generator_losses: weighting {weighting!r} is not one of {DM_WEIGHTINGS}")
-        gen_sigma, indices, noise = self._dm_draws(what, z, num_scales, noise, indices, generator, gen_sigma, min_step_frac, max_step_frac)
+        ladder, steps = self._dm_ladder(what, z, gen_sigma, gen_sigmas, steps, sim_noise, generator)
+        if ladder is not None and len(ladder) == 1:
+            gen_sigma = ladder.sigmas[0]
+        K = 1 if ladder is None else len(ladder)
+        gen_sigma, indices, noise = self._dm_draws(what, z, num_scales, noise, indices, generator, 1.0 if K > 1 else gen_sigma,
+                                                   min_step_frac, max_step_frac)
         if gan_head is not None:
             gan_gen_weight = float(gan_gen_weight)
             if not math.isfinite(gan_gen_weight):
@@ -910,22 +1012,33 @@ class KarrasDenoiser:
             if gan_noise.requires_grad:
                 raise NotImplementedError("dm_generator_losses differentiates the generator's parameters only: gan_noise must not "
                                           "require grad")
+        if K > 1:
+            sim_noise = self._dm_sim_noise(what, z, K, sim_noise, generator)
+        more = {} if ladder is None else {"steps": steps}
         nets = [_hip_unet(m) for m in (model, real_model, fake_model)]
         if all(n is not None for n in nets) and z.is_cuda:
             args = self._dm_hip_operands(what, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma)
+            if K > 1:
+                if sim_noise.requires_grad:
+                    raise NotImplementedError(f"{what} on the HIP U-Net differentiates the generator's parameters only: "
+                                              "sim_noise must not require grad")
+                z32 = args[6]
+                more["steps"] = steps = steps.to(device=z32.device, dtype=torch.int64).contiguous()
+                args = args[:-1] + (_GenSteps(ladder.device_table(z32.device), steps,
+                                              sim_noise.detach().to(device=z32.device, dtype=torch.float32).contiguous()),)
             if gan_head is not None:
                 gan = (gan_head, gan_gen_weight) + self._dm_level_operands(what, args[6], gan_noise, gan_indices)
                 if torch.is_grad_enabled():
                     loss, x, s, gl, lg = _DMGanLossFn.apply(*args, weighting, gan, *ops.fast_parameters(nets[0]))
                 else:
                     loss, x, s, _, gl, lg = _dm_loss(*args, weighting, keep=False, gan=gan)
-                return {"loss": loss, "x": x, "dm_norm": s, "gan_loss": gl, "gan_logit": lg}
+                return dict({"loss": loss, "x": x, "dm_norm": s, "gan_loss": gl, "gan_logit": lg}, **more)
             if torch.is_grad_enabled():
                 loss, x, s = _DMLossFn.apply(*args, weighting, *ops.fast_parameters(nets[0]))
             else:
                 loss, x, s, _ = _dm_loss(*args, weighting, keep=False)
-            return {"loss": loss, "x": x, "dm_norm": s}
-        if z.requires_grad or noise.requires_grad:
+            return dict({"loss": loss, "x": x, "dm_norm": s}, **more)
+        if z.requires_grad or noise.requires_grad or (K > 1 and sim_noise.requires_grad):
             raise NotImplementedError("dm_generator_losses differentiates the generator's parameters only: z and noise must not "
                                       "require grad")
         if gan_head is not None and not hasattr(fake_model, "encode"):
@@ -934,8 +1047,19 @@ class KarrasDenoiser:
         N, dims = z.shape[0], z.ndim
         levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(z.device)
         t = levels[indices.to(z.device)]
-        sigma_g = torch.full((N,), gen_sigma, dtype=torch.float32, device=z.device)
-        x = self.denoise(model, z * gen_sigma, sigma_g, **model_kwargs)[1]
+        if K > 1:
+            # backward simulation: the sampler's own states under no_grad, an image frozen once its step is reached
+            more["steps"] = steps = steps.to(z.device)
+            sig = ladder.table.to(z.device)
+            x_k = z * ladder.sigmas[0]
+            with torch.no_grad():
+                for j in range(K - 1):
+                    d_j = self.denoise(model, x_k, sig[j].expand(N), **model_kwargs)[1]
+                    x_k = torch.where(append_dims(steps > j, dims), d_j + sim_noise[j].to(z.device) * ladder.sigmas[j + 1], x_k)
+            x = self.denoise(model, x_k, sig[steps], **model_kwargs)[1]
+        else:
+            sigma_g = torch.full((N,), gen_sigma, dtype=torch.float32, device=z.device)
+            x = self.denoise(model, z * gen_sigma, sigma_g, **model_kwargs)[1]
         with torch.no_grad():
             x_t = x + noise * append_dims(t, dims)
             d_real = real_diffusion.denoise(real_model, x_t, t, **model_kwargs)[1]
@@ -946,7 +1070,7 @@ class KarrasDenoiser:
                 g = g / append_dims(s, dims)
             g = torch.where(append_dims(s, dims) == 0, torch.zeros_like(g), g)
         if gan_head is None:
-            return {"loss": _DMSurrogate.apply(x, g), "x": x.detach().float(), "dm_norm": s}
+            return dict({"loss": _DMSurrogate.apply(x, g), "x": x.detach().float(), "dm_norm": s}, **more)
         # the GAN term's d / d x is taken here, with respect to x alone: the head and the fake model see no backward
         keep = torch.is_grad_enabled()
         t_gan = levels[gan_indices.to(z.device)]
@@ -961,7 +1085,7 @@ class KarrasDenoiser:
         value = 0.5 * mean_flat(g ** 2) + gan_gen_weight * gan_loss
         if keep:
             value = _SiDSurrogate.apply(x, g + (x[0].numel() * gan_gen_weight) * g_gan, value)
-        return {"loss": value, "x": x.detach().float(), "dm_norm": s, "gan_loss": gan_loss, "gan_logit": logit}
+        return dict({"loss": value, "x": x.detach().float(), "dm_norm": s, "gan_loss": gan_loss, "gan_logit": logit}, **more)
 
     def gan_discriminator_losses(self, fake_model, gan_head, x_fake, x_real, num_scales, model_kwargs=None, real_kwargs=None, noise=None,
                                  indices=None, generator=None, gan_min_step_frac=0.0, gan_max_step_frac=1.0):
@@ -1019,6 +1143,52 @@ class KarrasDenoiser:
             raise NotImplementedError(f"{what}: Must have a real_model with its real_diffusion and a fake_model")
         return ({} if model_kwargs is None else model_kwargs), (real_diffusion if fake_diffusion is None else fake_diffusion)
 
+    @staticmethod
+    def _dm_ladder(what, z, gen_sigma, gen_sigmas, steps, sim_noise, generator):
+        """The K-step arguments checked -> (GenLadder | None, steps int64 [N] | None).  With K > 1 and no steps given they are drawn
+        here, uniformly over {0 .. K-1}: the first draw of the call.  K = 1 draws nothing (steps are zeros)."""
+        N = z.shape[0]
+        if gen_sigmas is None:
+            if steps is not None or sim_noise is not None:
+                raise ValueError(f"{what}: steps and sim_noise belong to a K-step generator: give gen_sigmas")
+            return None, None
+        if gen_sigma is not None:
+            raise ValueError(f"{what}: gen_sigmas (the K-step ladder) excludes gen_sigma (the one-step level): give one of them")
+        ladder = gen_ladder(what, gen_sigmas)
+        K = len(ladder)
+        if steps is not None:
+            if not torch.is_tensor(steps) or steps.dtype != torch.int64 or steps.dim() != 1 or steps.numel() != N:
+                raise ValueError(f"{what}: steps must be an int64 [N = {N}] tensor, got "
+                                 f"{(steps.dtype, tuple(steps.shape)) if torch.is_tensor(steps) else type(steps).__name__}")
+            lo, hi = int(steps.min()), int(steps.max())
+            if lo < 0 or hi > K - 1:
+                raise ValueError(f"{what}: steps must lie in [0, K - 1 = {K - 1}], got values in [{lo}, {hi}]")
+            steps = steps.detach()
+        elif K == 1:
+            steps = torch.zeros(N, dtype=torch.int64, device=z.device)
+        elif generator is not None:
+            steps = torch.randint(0, K, (N,), generator=generator, device=generator.device).to(z.device)
+        else:
+            steps = torch.randint(0, K, (N,), device=z.device)
+        if K == 1 and sim_noise is not None and (not torch.is_tensor(sim_noise) or tuple(sim_noise.shape) != (0,) + tuple(z.shape)):
+            raise ValueError(f"{what}: sim_noise must be [K - 1, N, C, H, W] = {(0,) + tuple(z.shape)}")
+        return ladder, steps
+
+    @staticmethod
+    def _dm_sim_noise(what, z, K, sim_noise, generator):
+        """The simulation noise [K - 1, *z.shape] of a K-step call: checked, or drawn stage by stage, the last draws of the call."""
+        shape = (K - 1,) + tuple(z.shape)
+        if sim_noise is not None:
+            if not torch.is_tensor(sim_noise) or tuple(sim_noise.shape) != shape:
+                raise ValueError(f"{what}: sim_noise must be [K - 1, N, C, H, W] = {shape}, got "
+                                 f"{tuple(sim_noise.shape) if torch.is_tensor(sim_noise) else type(sim_noise).__name__}")
+            return sim_noise
+        if generator is not None:
+            draws = [torch.randn(z.shape, generator=generator, device=generator.device, dtype=z.dtype).to(z.device) for _ in range(K - 1)]
+        else:
+            draws = [torch.randn_like(z) for _ in range(K - 1)]
+        return torch.stack(draws)
+
     def _dm_draws(self, what, z, num_scales, noise, indices, generator, gen_sigma, min_step_frac, max_step_frac):
         """-> (gen_sigma, indices, noise): sigma_G checked, then the draws of one generator step, indices before noise."""
         gen_sigma = float(self.sigma_max if gen_sigma is None else gen_sigma)
@@ -1072,7 +1242,7 @@ class KarrasDenoiser:
 
     def sid_generator_losses(self, model, z, num_scales=1000, real_model=None, real_diffusion=None, fake_model=None, fake_diffusion=None,
                              model_kwargs=None, noise=None, indices=None, generator=None, gen_sigma=None, alpha=1.2,
-                             min_step_frac=0.02, max_step_frac=0.98):
+                             min_step_frac=0.02, max_step_frac=0.98, gen_sigmas=None):
         """Score identity Distillation loss of the one-step generator of dm_generator_losses (SiD, Zhou et al., ICML 2024: the fused
         loss L~^(alpha) up to the constant 1 / CHW; its released code's (y_real - y_fake) * ((y_real - y) - alpha (y_real - y_fake))
         / weight_factor) -> {"loss": [N], "x": [N, C, H, W] detached fp32, "dm_norm": [N]}.  With x, x_t, D_r, D_f as there,
@@ -1082,8 +1252,18 @@ class KarrasDenoiser:
         net receives a gradient (theirs stay None).  A sample with s == 0 gets loss = 0 and no gradient (SiD's code clips the
         normaliser at 1e-5 instead), and the mean over CHW stands where SiD sums.  alpha: finite, SiD's default 1.2, 1 its base
         form; alpha = 0.5 is NOT dm_generator_losses (that one has no Jacobian paths).  Checks, refusals and draws (indices, then
-        noise) are dm_generator_losses's.  DESIGN 5.34."""
+        noise) are dm_generator_losses's.  DESIGN 5.34.
+        gen_sigmas: a one-level ladder stands for gen_sigma; a K-step generator (K > 1) is refused: backward simulation is built for
+        dm_generator_losses alone."""
         what = "sid_generator_losses"
+        if gen_sigmas is not None:
+            if gen_sigma is not None:
+                raise ValueError(f"{what}: gen_sigmas excludes gen_sigma: give one of them")
+            ladder = gen_ladder(what, gen_sigmas)
+            if len(ladder) > 1:
+                raise NotImplementedError(f"{what}: a K-step generator (gen_sigmas of {len(ladder)} levels) is limited to "
+                                          "dm_generator_losses: score identity distillation is built for K = 1 only")
+            gen_sigma = ladder.sigmas[0]
         model_kwargs, fake_diffusion = self._dm_refusals(what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs)
         alpha = float(alpha)
         if not math.isfinite(alpha):
@@ -1474,30 +1654,57 @@ def progdist_sample(diffusion, model, shape, steps, clip_denoised=True, progress
     return _sample_on_device(schedule, denoiser, shape, device, "progdist_sample", key, use_graph, generator, callback, progress)
 
 
-def dm_sample(diffusion, model, shape, gen_sigma=None, clip_denoised=True, model_kwargs=None, generator=None, device=None):
+def dm_sample(diffusion, model, shape, gen_sigma=None, clip_denoised=True, model_kwargs=None, generator=None, device=None,
+              gen_sigmas=None):
     """Sample the one-step generator that dm_generator_losses trains: x = D_theta(sigma_G z, sigma_G) with the EDM scalings, NFE = 1
     (dxmi_dm_gen_in -> forward_inference -> dxmi_dm_gen_out); clamped to [-1, 1] when clip_denoised.  gen_sigma: None = sigma_max,
     and it must be the one the generator was trained at.  generator: as for karras_sample (its randn draws z: with a
-    DeterministicGenerator image i gets the same latent whatever the batch size); None: drawn on the device."""
+    DeterministicGenerator image i gets the same latent whatever the batch size); None: drawn on the device.
+    gen_sigmas (excludes gen_sigma): the ladder of a K-step generator (dm_generator_losses with gen_sigmas), NFE = K: dxmi_dmms_in,
+    then K - 1 x (forward_inference, dxmi_dmms_stage: x' = G_j(x) + sigma_{j+1} eps, not clamped), forward_inference, dxmi_dmms_out.
+    A DeterministicGenerator's stage noise is made inside the launch, with the draw numbers its randn would take; any other
+    generator's randn, or torch, supplies it.  K = 1 is the one-step sampler at gen_sigmas[0]."""
     if getattr(diffusion, "distillation", False):
         raise NotImplementedError("dm_sample runs a distribution-matching generator, which keeps the EDM scalings (distillation=False); "
                                   "a consistency-distilled model samples in one step with --cm_sampler onestep")
+    ladder = None
+    if gen_sigmas is not None:
+        if gen_sigma is not None:
+            raise ValueError("dm_sample: gen_sigmas (the K-step ladder) excludes gen_sigma (the one-step level): give one of them")
+        ladder = gen_ladder("dm_sample", gen_sigmas)
+        if len(ladder) == 1:
+            gen_sigma, ladder = ladder.sigmas[0], None
     device = _graph.indexed_device(torch.device("cuda") if device is None else device)
     if device.type != "cuda":
         raise DxmiError("dm_sample runs only on the HIP device path (no CPU fallback)")
     kw = {} if model_kwargs is None else model_kwargs
     shape = tuple(int(v) for v in shape)
     gen_sigma = float(diffusion.sigma_max if gen_sigma is None else gen_sigma)
+
+    def evaluate(x_in, t):
+        F = model(x_in, t, **kw)          # under no_grad the HIP UNetModel's forward is forward_inference
+        if F.dtype != torch.float32 or not F.is_contiguous() or F.device != x_in.device:
+            F = _as_f32(F, device)
+        return F
     with torch.no_grad():
         if generator is not None:
             z = _as_f32(generator.randn(*shape, device=device), device)
         else:
             z = torch.randn(shape, dtype=torch.float32, device=device)
+        if ladder is not None:
+            tab, sd = ladder.device_table(device), diffusion.sigma_data
+            x, x_in, t = ops.dmms_in(z, tab, sd)
+            for j in range(len(ladder) - 1):
+                F = evaluate(x_in, t)
+                if isinstance(generator, DeterministicGenerator):
+                    ops.dmms_stage(F, j, tab, x, x_in, t, sample_index=generator.get_indices(shape[0], device), seed=generator.seed,
+                                   draw=generator._next_draw(), sigma_data=sd)
+                else:
+                    eps = _as_f32(generator.randn(*shape, device=device), device) if generator is not None else torch.randn_like(z)
+                    ops.dmms_stage(F, j, tab, x, x_in, t, eps=eps, sigma_data=sd)
+            return ops.dmms_out(evaluate(x_in, t), x, tab, sd, clip=clip_denoised, out=x)
         x_in, t = ops.dm_gen_in(z, gen_sigma, diffusion.sigma_data)
-        F = model(x_in, t, **kw)          # under no_grad the HIP UNetModel's forward is forward_inference
-        if F.dtype != torch.float32 or not F.is_contiguous() or F.device != z.device:
-            F = _as_f32(F, device)
-        return ops.dm_gen_out(F, z, gen_sigma, diffusion.sigma_data, clip=clip_denoised)
+        return ops.dm_gen_out(evaluate(x_in, t), z, gen_sigma, diffusion.sigma_data, clip=clip_denoised)
 
 
 def _sample_on_device(schedule, denoiser, shape, device, name, key, use_graph, generator, callback, progress):

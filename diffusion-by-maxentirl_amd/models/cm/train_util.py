@@ -63,6 +63,7 @@ from dxmi_hip.dist import broadcast_parameters, is_distributed
 from dxmi_hip.optim import RAdam
 
 from .fp16_util import MixedPrecisionTrainer, get_param_groups_and_shapes, make_master_params, master_params_to_model_params
+from .karras_diffusion import gen_ladder
 from .nn import update_ema, update_ema_rates
 
 INITIAL_LOG_LOSS_SCALE = 20.0
@@ -615,12 +616,15 @@ class DMTrainLoop(TrainLoop):
     over (fake net, head), one backward per microbatch of (dsm weights).mean() + gan_dis_weight dis.mean(), dis being
     gan_discriminator_losses on the generated and the real microbatch; the generator's loss gains gan_gen_weight softplus(-logit).
     save() adds gan_head%06d.pt (fake_model%06d.pt stays the bare net's state dict); a resume with a head needs that file, and a
-    fake_opt file whose parameter count does not match the run's is an error."""
+    fake_opt file whose parameter count does not match the run's is an error.
+    gen_sigmas (excludes gen_sigma; None: the one-step generator): the ladder of a K-step generator trained by backward simulation
+    (dm_generator_losses with gen_sigmas).  Objective "sid" takes one level only.  Checkpoints are unchanged: the ladder
+    is an argument of the run, and of dm_sample afterwards."""
 
     def __init__(self, *, real_model, real_diffusion, fake_model, fake_diffusion=None, num_scales=1000, gen_update_every=5,
                  fake_lr=None, weighting="dmd", gen_sigma=None, min_step_frac=0.02, max_step_frac=0.98, generator=None, objective="dmd",
                  sid_alpha=1.2, gan_head=None, real_data=None, gan_gen_weight=3e-3, gan_dis_weight=1e-2, gan_min_step_frac=0.0,
-                 gan_max_step_frac=1.0, **kwargs):
+                 gan_max_step_frac=1.0, gen_sigmas=None, **kwargs):
         if kwargs.get("use_graph"):
             raise NotImplementedError("DMTrainLoop: use_graph=True is not supported: the generator and the fake denoiser are updated "
                                       "on two clocks, which needs two captured steps and a graph key per clock; train this mode eagerly")
@@ -637,7 +641,15 @@ class DMTrainLoop(TrainLoop):
                                       "is SiDA, a different recipe (its own loss weighting and schedule), which is not built here")
         if gan_head is not None and real_data is None:
             raise ValueError("DMTrainLoop: a gan_head needs real_data, an iterator of (x_real NCHW fp32 in [-1, 1], cond)")
+        if gen_sigmas is not None:
+            if gen_sigma is not None:
+                raise ValueError("DMTrainLoop: gen_sigmas (the K-step ladder) excludes gen_sigma (the one-step level): give one of them")
+            gen_sigmas = gen_ladder("DMTrainLoop", gen_sigmas).sigmas
+            if objective == "sid" and len(gen_sigmas) > 1:
+                raise NotImplementedError(f"DMTrainLoop: objective 'sid' is limited to a one-step generator, gen_sigmas has "
+                                          f"{len(gen_sigmas)} levels: backward simulation is built for objective 'dmd' alone")
         super().__init__(**kwargs)
+        self.gen_sigmas = gen_sigmas
         self.gan_head, self.real_data = gan_head, real_data
         self.gan_gen_weight, self.gan_dis_weight = float(gan_gen_weight), float(gan_dis_weight)
         self.gan_min_step_frac, self.gan_max_step_frac = gan_min_step_frac, gan_max_step_frac
@@ -737,7 +749,8 @@ class DMTrainLoop(TrainLoop):
                 terms = gen_loss(
                     self.ddp_model, z, self.num_scales, real_model=self.real_model, real_diffusion=self.real_diffusion,
                     fake_model=self.fake_model, fake_diffusion=self.fake_diffusion, model_kwargs=micro_cond, generator=self.generator,
-                    gen_sigma=self.gen_sigma, min_step_frac=self.min_step_frac, max_step_frac=self.max_step_frac, **how)
+                    gen_sigma=self.gen_sigma, gen_sigmas=self.gen_sigmas, min_step_frac=self.min_step_frac,
+                    max_step_frac=self.max_step_frac, **how)
             if gen_turn:
                 self.mp_trainer.backward(terms["loss"].mean())
             x = terms["x"]

@@ -739,6 +739,36 @@ int dxmi_dm_grad_fwd(const float* f_real, const float* f_fake, const float* x, c
 int dxmi_dm_gen_bwd(const float* upstream, const float* g, float* d_f_gen, int32_t N, int32_t CHW, float gen_sigma, float sigma_data,
                     void* stream);
 
+/* The K-step generator of the same loss, trained by backward simulation (DMD2, Yin et al. 2024, section 4.4-4.5;
+ * KarrasDenoiser.dm_generator_losses with gen_sigmas, dm_sample with gen_sigmas; csrc/dm_train.hip).  gen_sigmas: fp32
+ * [num_steps] on the DEVICE, sigma_0 > ... > sigma_{K-1} > 0 (K = num_steps >= 1).  Step j of the generator is the EDM denoiser
+ * G_j(x) = c_skip(sigma_j) x + c_out(sigma_j) F(c_in(sigma_j) x, 250 ln(sigma_j + 1e-44)); the sampler's states are x_0 = sigma_0 z,
+ * x_{j+1} = G_j(x_j) + sigma_{j+1} eps_j, never clamped.  steps: int64 [N] on the DEVICE, image n's graded step k_n; a step outside
+ * [0, K - 1] gives NaN for that image, and nothing outside the ladder is read.  Tensors, rounding and alignment as dxmi_dm_*.
+ * dxmi_dmms_in:    x = sigma_0 z (kept), x_in = c_in(sigma_0) x, t_out[n] = 250 ln(sigma_0 + 1e-44).
+ * dxmi_dmms_stage: ONE launch between generator evaluations `stage` and `stage` + 1 (0 <= stage <= K - 2), in place.  For image n with
+ *   steps == NULL or steps[n] > stage: x = (c_skip(sigma_j) x + c_out(sigma_j) f_gen) + eps sigma_{j+1}, x_in = c_in(sigma_{j+1}) x,
+ *   t_out[n] = 250 ln(sigma_{j+1} + 1e-44).  An image with steps[n] <= stage is frozen: its x, x_in and t_out rows are neither read
+ *   nor written, so after stages 0 .. K - 2 x[n] = x_{k_n} and x_in / t_out hold the operands of the graded evaluation.  eps is given,
+ *   or made in the launch where sample_index (int64 [N] on the device) is given instead: the bits of
+ *   dxmi_randn_indexed(sample_index, CHW, seed, draw).  Giving both, or neither, is an error.
+ * dxmi_dmms_prep:  dxmi_dm_gen_prep with x_k where sigma_G z stood and sigma_{steps[n]} where gen_sigma stood; x may be x_k.
+ * dxmi_dmms_out:   x = G_{K-1} = c_skip(sigma_{K-1}) x_k + c_out(sigma_{K-1}) f_gen, clamped to [-1, 1] when clip != 0; x may be x_k.
+ * dxmi_dmms_bwd:   d_f_gen[n] = ((upstream[n] / CHW) g[n]) c_out(sigma_{steps[n]}). */
+int dxmi_dmms_in(const float* z, const float* gen_sigmas, int32_t num_steps, float* x, float* x_in, float* t_out, int32_t N, int32_t CHW,
+                 float sigma_data, void* stream);
+int dxmi_dmms_stage(const float* f_gen, const float* eps, const int64_t* sample_index, uint32_t draw, uint64_t seed, const int64_t* steps,
+                    const float* gen_sigmas, int32_t num_steps, int32_t stage, float* x, float* x_in, float* t_out, int32_t N,
+                    int32_t CHW, float sigma_data, void* stream);
+int dxmi_dmms_prep(const float* f_gen, const float* x_k, const float* noise, const int64_t* steps, const float* gen_sigmas,
+                   int32_t num_steps, const int64_t* indices, const float* t_table, int32_t num_scales, float* x, float* x_t,
+                   float* x_in_real, float* t_out, float* x_in_fake, int32_t N, int32_t CHW, float gen_sigma_data,
+                   float real_sigma_data, float fake_sigma_data, void* stream);
+int dxmi_dmms_out(const float* f_gen, const float* x_k, const float* gen_sigmas, int32_t num_steps, float* x, int32_t N, int32_t CHW,
+                  float sigma_data, int32_t clip, void* stream);
+int dxmi_dmms_bwd(const float* upstream, const float* g, const int64_t* steps, const float* gen_sigmas, int32_t num_steps,
+                  float* d_f_gen, int32_t N, int32_t CHW, float sigma_data, void* stream);
+
 /* Score identity Distillation of the same one-step generator (KarrasDenoiser.sid_generator_losses; SiD, Zhou et al., ICML 2024, the
  * fused loss L~^(alpha); csrc/sid_train.hip): the loss is differentiated through both denoisers with respect to their
  * input x_t, and these are the two launches around the two input-only backward walks.  Tensors, table, index rule, rounding and

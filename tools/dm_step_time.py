@@ -13,6 +13,15 @@ Two measurements at [batch, 3, 64, 64], num_scales 1000, weighting dmd:
             alternate, median of --reps after --warmup rounds, device events around each leg and a synchronise at its end.
 Every timed piece runs under its own time limit, kept by a watchdog thread: an overrun ends the script with status 124.  Prints one
 JSON line per measurement and writes both to --out.
+
+    python tools/dm_step_time.py --gen_sigmas 80,5,1,0.3 [--out profiles/dmms_step_time.json]
+
+times the K-step generator of DMD2's backward simulation instead, device path only:
+  launches  dxmi_dmms_stage (noise given, and made in the launch) and the four non-network launches of a K-step generator step
+            (dxmi_dmms_in, dxmi_dmms_prep, dxmi_dm_grad_fwd, dxmi_dmms_bwd) at the same shape, steps cycling through 0 .. K-1;
+  step      the same full iteration with gen_sigmas (steps drawn once, uniform over 0 .. K-1, and injected with the simulation noise)
+            next to the K = 1 leg (gen_sigma = gen_sigmas[0]) of the same run, alternating.  The expected difference is K - 1
+            inference forwards of the generator.
 """
 import argparse
 import json
@@ -105,14 +114,108 @@ def launch_times(ops, d, B, dev, limit):
     return out
 
 
+def ms_launch_times(ops, ladder, B, dev, limit):
+    """us per launch of the K-step generator at [B, 3, 64, 64]."""
+    from models.cm.karras_diffusion import cd_levels
+    K = len(ladder)
+    r = lambda: torch.randn((B, 3, 64, 64), device=dev)
+    z, noise, eps, Fg, Fr, Ff = r(), r(), r(), r(), r(), r()
+    tab = cd_levels(S, 0.002, 80.0, 7.0).device_table(torch.device(dev))
+    sig = torch.tensor(ladder, dtype=torch.float32, device=dev)
+    idx = torch.randint(20, 980, (B,), device=dev)
+    steps = (torch.arange(B, device=dev) % K).contiguous()
+    live = steps.clamp(min=1)                                     # stage 0 with every image live: the launch's full traffic
+    index = torch.arange(B, device=dev)
+    up = torch.rand(B, device=dev)
+    x_k, x_in, tm = ops.dmms_in(z, sig)
+    x, x_t, _, _, _ = ops.dmms_prep(Fg, x_k, noise, steps, sig, idx, tab)
+    g, _, _ = ops.dm_grad_fwd(Fr, Ff, x, x_t, idx, tab, "dmd")
+    cases = {"dmms_in": lambda: ops.dmms_in(z, sig),
+             "dmms_prep": lambda: ops.dmms_prep(Fg, x_k, noise, steps, sig, idx, tab),
+             "grad_fwd": lambda: ops.dm_grad_fwd(Fr, Ff, x, x_t, idx, tab, "dmd"),
+             "dmms_bwd": lambda: ops.dmms_bwd(up, g, steps, sig)}
+    if K > 1:
+        cases.update({"dmms_stage": lambda: ops.dmms_stage(Fg, 0, sig, x_k, x_in, tm, steps=live, eps=eps),
+                      "dmms_stage_own_noise": lambda: ops.dmms_stage(Fg, 0, sig, x_k, x_in, tm, steps=live, sample_index=index, seed=1, draw=0),
+                      "dmms_stage_mixed_steps": lambda: ops.dmms_stage(Fg, 0, sig, x_k, x_in, tm, steps=steps, eps=eps)})
+    out = {}
+    for name, fn in cases.items():
+        timed(fn, limit, 20)
+        out[name] = {"hip_us": round(timed(fn, limit, 200) * 1e3, 2)}
+    out["sum_of_a_step"] = {"hip_us": round(sum(out[k]["hip_us"] for k in ("dmms_in", "dmms_prep", "grad_fwd", "dmms_bwd")), 2)}
+    return out
+
+
+def main_ms(args, ladder):
+    from dxmi_hip import ops
+    from models.cm.script_util import create_model_and_diffusion
+    ops.device_check()
+    dev, B, K = "cuda:0", args.batch, len(ladder)
+    torch.manual_seed(0)
+    gen_net, diffusion = create_model_and_diffusion(**MODEL)
+    fake, fake_diffusion = create_model_and_diffusion(**MODEL)
+    real, real_diffusion = create_model_and_diffusion(**MODEL)
+    with torch.no_grad():
+        for net, seed in ((gen_net, 1), (fake, 2)):
+            net.out[2].weight.normal_(0.0, 0.05, generator=torch.Generator().manual_seed(seed))
+    real.load_state_dict(gen_net.state_dict())
+    gen_net, fake, real = gen_net.to(dev).train(), fake.to(dev).train(), real.to(dev).eval().requires_grad_(False)
+    rows = [{"batch": B, "num_scales": S, "gen_sigmas": list(ladder), "launches": ms_launch_times(ops, ladder, B, dev, args.leg_timeout)}]
+    print(json.dumps(rows[0]), flush=True)
+    r = lambda: torch.randn(B, 3, 64, 64, device=dev)
+    z, noise, dsm_noise = r(), r(), r()
+    sim = torch.randn(K - 1, B, 3, 64, 64, device=dev)
+    steps = torch.randint(0, K, (B,), device=dev)
+    sigmas = (torch.randn(B, device=dev) * 1.2 - 1.2).exp()
+    idx = torch.randint(20, 980, (B,), device=dev)
+    kw = {"y": torch.randint(0, 1000, (B,), device=dev)}
+
+    def leg(**how):
+        def run():
+            for p in list(gen_net.parameters()) + list(fake.parameters()):
+                p.grad = None
+            terms = diffusion.dm_generator_losses(gen_net, z, S, real_model=real, real_diffusion=real_diffusion, fake_model=fake,
+                                                  fake_diffusion=fake_diffusion, model_kwargs=kw, noise=noise, indices=idx, **how)
+            terms["loss"].mean().backward()
+            fake_diffusion.training_losses(fake, terms["x"], sigmas, model_kwargs=kw, noise=dsm_noise)["loss"].mean().backward()
+        return run
+    legs = {"one_step": leg(gen_sigma=ladder[0]), "k_step": leg(gen_sigmas=ladder, steps=steps, sim_noise=sim)}
+    times = {k: [] for k in legs}
+    for rnd in range(args.warmup + args.reps):
+        for k, fn in legs.items():
+            ms = timed(fn, args.leg_timeout)
+            if rnd >= args.warmup:
+                times[k].append(ms)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    x_in, t_g = ops.dm_gen_in(z, ladder[0])
+    fwd = lambda: gen_net.forward_inference(x_in, t_g, kw["y"])
+    timed(fwd, args.leg_timeout, 2)
+    out = {"batch": B, "reps": args.reps, "num_scales": S, "K": K, "steps": steps.tolist()}
+    out.update({f"{k}_ms": round(v, 3) for k, v in med.items()})
+    out.update({f"{k}_ms_all": [round(x, 3) for x in v] for k, v in times.items()})
+    out["k_step_minus_one_step_ms"] = round(med["k_step"] - med["one_step"], 3)
+    out["generator_forward_inference_ms"] = round(timed(fwd, args.leg_timeout, 5), 3)
+    rows.append(out)
+    print(json.dumps(out), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        for row in rows:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)      # the per-rank batch of the ImageNet-64 runs at 8 GPUs
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--leg_timeout", type=int, default=120)
-    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "dm_step_time.json"))
+    ap.add_argument("--gen_sigmas", type=str, default="")  # the ladder of a K-step generator, e.g. 80,5,1,0.3: time that instead
+    ap.add_argument("--out", type=str, default="")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "dmms_step_time.json" if args.gen_sigmas else "dm_step_time.json")
+    if args.gen_sigmas:
+        from models.cm.karras_diffusion import gen_ladder
+        return main_ms(args, gen_ladder("--gen_sigmas", [float(v) for v in args.gen_sigmas.split(",")]).sigmas)
     from dxmi_hip import ops
     from models.cm.script_util import create_model_and_diffusion
     ops.device_check()
