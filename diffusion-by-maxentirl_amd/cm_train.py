@@ -47,6 +47,11 @@ channels and image_size / 2^(levels - 1); KarrasDenoiser.gan_discriminator_losse
 --gan_gen_weight softplus(-logit)): it needs real images, --data_npz PATH or --synthetic_data True, and does not go with --dm_objective
 sid; --gan_gen_weight (3e-3), --gan_dis_weight (1e-2), --gan_max_step_frac (1.0: the noise levels of the GAN term's inputs reach up to that
 fraction of the ladder).  The gan_* flags are errors without --dm_gan.
+--dm_objective sida is adversarial score identity distillation (KarrasDenoiser.sida_generator_losses / sida_discriminator_losses; SiDA,
+Zhou, Zheng et al. 2024): SiD plus a discriminator WITHOUT parameters, the channel mean of the fake denoiser's bottleneck, read from the
+evaluation SiD already makes.  It needs real images (--data_npz PATH or --synthetic_data True) and takes --sid_alpha (1.2),
+--sida_gen_weight (0.01), --sida_dis_weight (1.0) and --gen_sigma; --dm_gan True, --dm_weighting none and a ladder of more than one level
+are errors with it, and the sida_* flags are errors without it.  No file is added to the checkpoints: the discriminator is the fake net.
 """
 import argparse
 import math
@@ -125,7 +130,7 @@ def parse_args(argv=None):
                     fp16_scale_growth=1e-3, seed=42, batch_invariant=False, lpips_vgg16="", lpips_lin="", use_graph=False,
                     huber_c=0.0, index_sampler="uniform", p_mean=-1.1, p_std=2.0, ict=False, gen_update_every=5, fake_lr=0.0,
                     dm_weighting="dmd", dm_num_scales=1000, dm_objective="dmd", sid_alpha=1.2, gen_sigma=0.0, gen_sigmas="", dm_gan=False,
-                    gan_gen_weight=3e-3, gan_dis_weight=1e-2, gan_max_step_frac=1.0)
+                    gan_gen_weight=3e-3, gan_dis_weight=1e-2, gan_max_step_frac=1.0, sida_gen_weight=0.01, sida_dis_weight=1.0)
     ap = argparse.ArgumentParser()
     add_dict_to_argparser(ap, defaults)
     args = ap.parse_args(argv)
@@ -142,7 +147,15 @@ def parse_args(argv=None):
         if args.dm_gan and not (math.isfinite(args.gan_gen_weight) and math.isfinite(args.gan_dis_weight)
                                 and 0.0 <= args.gan_max_step_frac <= 1.0):
             ap.error("--gan_gen_weight and --gan_dis_weight must be finite and --gan_max_step_frac lie in [0, 1]")
-        if args.data_npz and not args.dm_gan:
+        if args.dm_objective == "sida":
+            if args.dm_gan:
+                ap.error("--dm_gan True does not go with --dm_objective sida: SiDA's discriminator has no head, it is the channel mean "
+                         "of the fake denoiser's bottleneck")
+            if not (args.data_npz or args.synthetic_data):
+                ap.error("--dm_objective sida needs real images: --data_npz PATH or --synthetic_data True")
+            if not (math.isfinite(args.sida_gen_weight) and math.isfinite(args.sida_dis_weight)):
+                ap.error("--sida_gen_weight and --sida_dis_weight must be finite")
+        if args.data_npz and not (args.dm_gan or args.dm_objective == "sida"):
             ap.error("--data_npz does not go with --training_mode dm: distribution matching trains on latents alone, it reads no images")
         if args.ict:
             ap.error("--ict True is improved consistency TRAINING: --training_mode dm does not go with it")
@@ -156,9 +169,9 @@ def parse_args(argv=None):
             ap.error("--gen_update_every must be >= 1, --dm_num_scales >= 2 and --fake_lr >= 0 (0: --lr)")
         if args.use_graph:
             ap.error("--use_graph True does not go with --training_mode dm (two update clocks; DMTrainLoop refuses it)")
-        if args.dm_objective not in ("dmd", "sid"):
-            ap.error(f"--dm_objective {args.dm_objective!r}: dmd or sid")
-        if args.dm_objective == "sid" and args.dm_weighting == "none":
+        if args.dm_objective not in ("dmd", "sid", "sida"):
+            ap.error(f"--dm_objective {args.dm_objective!r}: dmd, sid or sida")
+        if args.dm_objective in ("sid", "sida") and args.dm_weighting == "none":
             ap.error("--dm_weighting none belongs to --dm_objective dmd: score identity distillation has its normaliser in the loss")
         if not math.isfinite(args.sid_alpha):
             ap.error(f"--sid_alpha {args.sid_alpha}: a finite number (SiD: 1.2; 1 is its base form)")
@@ -171,8 +184,8 @@ def parse_args(argv=None):
                 args.gen_sigmas = parse_gen_sigmas(args.gen_sigmas)
             except ValueError as e:
                 ap.error(f"--gen_sigmas {args.gen_sigmas}: {e}")
-            if args.dm_objective == "sid" and len(args.gen_sigmas) > 1:
-                ap.error("--gen_sigmas with more than one level does not go with --dm_objective sid: backward simulation is built for "
+            if args.dm_objective in ("sid", "sida") and len(args.gen_sigmas) > 1:
+                ap.error(f"--gen_sigmas with more than one level does not go with --dm_objective {args.dm_objective}: backward simulation is built for "
                          "--dm_objective dmd alone")
         else:
             args.gen_sigmas = None
@@ -180,6 +193,10 @@ def parse_args(argv=None):
         for flag in ("--dm_objective", "--sid_alpha", "--gen_sigma", "--gen_sigmas", "--dm_gan"):
             if given(flag):
                 ap.error(f"{flag} belongs to --training_mode dm, not to --training_mode {args.training_mode}")
+    if not (args.training_mode == "dm" and args.dm_objective == "sida"):
+        for flag in ("--sida_gen_weight", "--sida_dis_weight"):
+            if given(flag):
+                ap.error(f"{flag} belongs to --training_mode dm --dm_objective sida")
     if not args.dm_gan:
         for flag in ("--gan_gen_weight", "--gan_dis_weight", "--gan_max_step_frac"):
             if given(flag):
@@ -314,6 +331,11 @@ def main_dm(args, device, local_rank, world):
             print0(store.describe())
         gan = dict(gan_head=head.to(device), real_data=real_data, gan_gen_weight=args.gan_gen_weight, gan_dis_weight=args.gan_dis_weight,
                    gan_max_step_frac=args.gan_max_step_frac)
+    if args.dm_objective == "sida":
+        real_data, store = make_loader(args, device, local_rank, world, seed_offset=REAL_SEED_OFFSET)
+        if store is not None:
+            print0(store.describe())
+        gan = dict(real_data=real_data, sida_gen_weight=args.sida_gen_weight, sida_dis_weight=args.sida_dis_weight)
     loop = DMTrainLoop(**gan, model=model, diffusion=diffusion, real_model=real_model, real_diffusion=real_diffusion, fake_model=fake_model,
                        num_scales=args.dm_num_scales, gen_update_every=args.gen_update_every, fake_lr=args.fake_lr or None,
                        weighting=args.dm_weighting, objective=args.dm_objective, sid_alpha=args.sid_alpha,
@@ -323,7 +345,9 @@ def main_dm(args, device, local_rank, world):
                        schedule_sampler=LogNormalSampler(), weight_decay=args.weight_decay,
                        lr_anneal_steps=args.max_iters if args.max_iters else args.lr_anneal_steps, log_dir=args.log_dir)
     print0(f"dm: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M parameters, {world} rank(s), "
-           + (f"objective sid (alpha {args.sid_alpha}), " if args.dm_objective == "sid" else f"weighting {args.dm_weighting}, ")
+           + (f"objective sid (alpha {args.sid_alpha}), " if args.dm_objective == "sid"
+              else f"objective sida (alpha {args.sid_alpha}, generator weight {args.sida_gen_weight}, discriminator weight "
+                   f"{args.sida_dis_weight}), " if args.dm_objective == "sida" else f"weighting {args.dm_weighting}, ")
            + (f"gen_sigmas {args.gen_sigmas} (K = {len(args.gen_sigmas)}), " if args.gen_sigmas
               else f"gen_sigma {args.gen_sigma or diffusion.sigma_max}, ")
            + f"generator update every {args.gen_update_every} iterations"

@@ -154,6 +154,8 @@ SIGNATURES = {
     "dxmi_sid_grad_fwd": (c_int, [c_void_p] * 6 + [c_int, c_float] + [c_void_p] * 5 + [c_int, c_int, c_float, c_float, c_int, c_float,
                                                                                         c_float, c_int, c_void_p]),
     "dxmi_sid_join": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
+    "dxmi_sida_map_fwd": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
+    "dxmi_sida_map_bwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
     "dxmi_gan_head_supported": (c_int, [c_int, c_int]),
     "dxmi_gan_conv4s2_slices": (c_int64, [c_int]),
     "dxmi_gan_conv4s2_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),

@@ -1490,6 +1490,64 @@ def sid_join(d_dir, g_real, g_fake, s, indices, t_table, real_sigma_data=0.5, fa
     return out
 
 
+# ---- SiDA's parameter-free discriminator on the fake denoiser's bottleneck (csrc/sida_train.hip)
+def _sida_host(what, values, N, ctype, name):
+    """A per-image host operand (a scalar stands for every image; a sequence or a CPU tensor of N values) -> a ctypes array."""
+    if torch.is_tensor(values):
+        if values.is_cuda:
+            raise _lib.DxmiError(f"{what}: {name} is a host operand (it is checked and passed as a kernel argument), got a device tensor")
+        values = values.reshape(-1).tolist()
+    elif not isinstance(values, (list, tuple)):
+        values = [values] * N
+    if len(values) != N:
+        raise _lib.DxmiError(f"{what}: {name} holds {len(values)} values for {N} images")
+    return (ctype * N)(*values)
+
+
+def _sida_map(what, h):
+    _need_cuda(h)
+    if h is None or h.dtype != torch.bfloat16 or not h.is_contiguous() or h.dim() < 3:
+        raise _lib.DxmiError(f"{what}: a contiguous NHWC bf16 activation [N, ..., Cb] is needed")
+    N, Cb = h.shape[0], h.shape[-1]
+    if N == 0 or h.numel() == 0:
+        raise _lib.DxmiError(f"{what}: empty activation {tuple(h.shape)}")
+    return N, h.numel() // (N * Cb), Cb
+
+
+def sida_map_fwd(h, sign):
+    """h NHWC bf16 [N, hb, wb, Cb] (or [N, P, Cb]), sign: -1 / +1 per image on the HOST (an int for all, or N of them) ->
+    (logit fp32 [N, P] = mean_c h, a fp32 [N] = mean_p softplus(sign_n logit[n, p])) (dxmi_sida_map_fwd)."""
+    what = "dxmi_sida_map_fwd"
+    N, P, Cb = _sida_map(what, h)
+    signs = _sida_host(what, sign, N, ctypes.c_int32, "sign")
+    logit = torch.empty((N, P), dtype=torch.float32, device=h.device)
+    a = torch.empty(N, dtype=torch.float32, device=h.device)
+    check(load().dxmi_sida_map_fwd(_ptr(h), signs, _ptr(logit), _ptr(a), N, P, Cb, _stream()), what)
+    return logit, a
+
+
+def sida_map_bwd(logit, sign, coef, Cb, upstream=None, shape=None):
+    """-> d_h bf16 [N, P, Cb] (of `shape`, e.g. [N, hb, wb, Cb], where given), d_h[n, p, :] = (coef_n upstream_n) sign_n sigmoid(sign_n logit[n, p])
+    / (P Cb), rounded once (dxmi_sida_map_bwd).  sign and coef live on the HOST (a scalar for all images, or N values); upstream:
+    fp32 [N] on the device, or None for 1."""
+    what = "dxmi_sida_map_bwd"
+    _need_cuda(logit, upstream)
+    if logit is None or logit.dtype != torch.float32 or not logit.is_contiguous() or logit.dim() != 2 or logit.numel() == 0:
+        raise _lib.DxmiError(f"{what}: logit is a contiguous fp32 [N, P] tensor")
+    N, P = logit.shape
+    Cb = int(Cb)
+    if upstream is not None and not (upstream.dtype == torch.float32 and upstream.is_contiguous() and upstream.numel() == N):
+        raise _lib.DxmiError(f"{what}: upstream is a contiguous fp32 tensor of {N} elements")
+    signs = _sida_host(what, sign, N, ctypes.c_int32, "sign")
+    coefs = _sida_host(what, coef, N, ctypes.c_float, "coef")
+    shape = (N, P, Cb) if shape is None else tuple(shape)
+    if math.prod(shape) != N * P * Cb or shape[0] != N or shape[-1] != Cb:
+        raise _lib.DxmiError(f"{what}: shape {shape} is not [N = {N}, ..., Cb = {Cb}] with {P} positions")
+    d_h = torch.empty(shape, dtype=torch.bfloat16, device=logit.device)
+    check(load().dxmi_sida_map_bwd(_ptr(logit), signs, coefs, _ptr(upstream), _ptr(d_h), N, P, Cb, _stream()), what)
+    return d_h
+
+
 # ---- DMD2's GAN head (csrc/gan_head.hip; models/cm/gan_head.py)
 def gan_head_supported(C, map_size):
     """Raise DxmiError (its message names the value) where the head's kernels do not serve C channels on a map_size^2 bottleneck."""

@@ -59,6 +59,11 @@ loss differentiated THROUGH both denoisers with respect to their input x_t (no p
 UNetModels it is ONE node around the generator (_sid_loss, _SiDLossFn) whose forward already forms d loss / d x: dxmi_dm_gen_in, the
 generator's training forward, dxmi_dm_gen_prep (the denoisers' time by _denoiser_time), input_forward on both denoisers, dxmi_sid_grad_fwd, input_backward on both,
 dxmi_sid_join; its backward is dxmi_dm_gen_bwd and the U-Net backward, as _DMLossFn's.  DESIGN 5.34.
+sida_generator_losses / sida_discriminator_losses (not in the reference: Adversarial Score identity Distillation, Zhou, Zheng et al.
+2024) add a discriminator without parameters, the channel mean of the fake net's bottleneck: the generator's node (_sida_loss,
+_SiDALossFn) is _SiDLossFn's with the fake net's input_forward(tap=True), dxmi_sida_map_fwd / _bwd and input_backward(d_tap=...), no
+network pass more than SiD; the discriminator's node (_SiDADisLossFn) is encoder_forward, the two map launches, encoder_backward.
+DESIGN 5.41.
 
 The training_losses and consistency_losses nodes run inside a StepGraph capture (models.cm.train_util's use_graph): they read nothing back, allocate from the graph's
 pool only, and their draws (randn_like, the index randint) are torch device RNG, which is graph-aware.  What a capture freezes is
@@ -668,6 +673,95 @@ class _SiDLossFn(torch.autograd.Function):
         return loss, x, s
 
     backward = staticmethod(_DMLossFn.backward)
+
+
+def _sida_value(loss_sid, adv, s, weight):
+    """loss_n = sid_n + weight adv_n / s_n, 0 where s_n == 0 (a few [N]-sized expressions)."""
+    live = s != 0
+    return torch.where(live, loss_sid + weight * adv / torch.where(live, s, torch.ones_like(s)), torch.zeros_like(s))
+
+
+def _sida_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, alpha, weight, keep):
+    """_sid_loss with SiDA's adversarial term from the SAME evaluation of the fake net -> (loss, x, s, (tape, g), adv_loss [N],
+    adv_logit [N, P]).  The fake net runs input_forward(tap=True): its bottleneck h feeds dxmi_sida_map_fwd (logit, adv = a(-1)),
+    dxmi_sida_map_bwd forms the cotangent d_h = -(CHW weight) sigmoid(-logit) / (P Cb) without the 1 / s, and the fake net's ONE
+    input_backward takes v_f at the output and d_h at the bottleneck; dxmi_sid_join's 1 / s covers both (the net is linear in its
+    cotangents).  No network pass is added to _sid_loss.  keep=False: the fake net still runs input_forward(tap=True) (its tape is
+    dropped), so that adv_loss and adv_logit are formed and F_f has the bits of the graded call."""
+    F, tape, _ = _dm_gen_forward(diffusion, net, z, y, gen_sigma, keep)
+    sdr, sdf = real_diffusion.sigma_data, fake_diffusion.sigma_data
+    x, x_t, xr_in, _, xf_in = ops.dm_gen_prep(F, z, noise, indices, tab, gen_sigma, diffusion.sigma_data, sdr, sdf)
+    xf_in = xr_in if xf_in is None else xf_in
+    t = _denoiser_time(tab, indices)
+    if keep:
+        F_r, tape_r = input_forward(real, xr_in, t, y)
+    else:
+        F_r = real.forward_inference(xr_in, t, y)
+    F_f, tape_f = input_forward(fake, xf_in, t, y, tap=True)
+    h = tape_f.bottleneck
+    v_r, v_f, d_dir, loss, s = ops.sid_grad_fwd(F_r, F_f, x, x_t, indices, tab, alpha, real=_scal_kw(real_diffusion),
+                                                fake=_scal_kw(fake_diffusion))
+    logit, adv = ops.sida_map_fwd(h, -1)
+    loss = _sida_value(loss, adv, s, weight)
+    if not keep:
+        return loss, x, s, (None, None), adv, logit
+    d_h = ops.sida_map_bwd(logit, -1, x[0].numel() * weight, h.shape[-1], shape=h.shape)
+    del h
+    g_r = input_backward(tape_r, v_r)
+    del tape_r, v_r
+    g_f = input_backward(tape_f, v_f, d_tap=d_h)
+    del tape_f, v_f, d_h
+    g = ops.sid_join(d_dir, g_r, g_f, s, indices, tab, sdr, sdf, out=d_dir)
+    return loss, x, s, (tape, g), adv, logit
+
+
+class _SiDALossFn(torch.autograd.Function):
+    """_sida_loss as one node around the generator; outputs (loss, x, dm_norm, adv_loss, adv_logit), of which only loss is
+    differentiable.  The forward has walked both denoisers backward already; the backward is _DMLossFn's."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise, indices, tab, y, gen_sigma, alpha, weight,
+                *params):
+        loss, x, s, (ctx.tape, ctx.g), adv, logit = _sida_loss(diffusion, net, real, real_diffusion, fake, fake_diffusion, z, noise,
+                                                               indices, tab, y, gen_sigma, alpha, weight, keep=True)
+        ctx.gen = (gen_sigma, diffusion.sigma_data)
+        ctx.mark_non_differentiable(x, s, adv, logit)
+        ctx.set_materialize_grads(False)
+        return loss, x, s, adv, logit
+
+    @staticmethod
+    def backward(ctx, g_loss, *rest):
+        return _DMLossFn.backward(ctx, g_loss, None, None)
+
+
+class _SiDADisLossFn(torch.autograd.Function):
+    """SiDA's discriminator loss as one node around the fake net's encoder: encoder_forward and dxmi_sida_map_fwd forward;
+    dxmi_sida_map_bwd, then encoder_backward.  x holds the generated half first; outputs (loss [N], logit_fake [N, P],
+    logit_real [N, P]).  The map has no parameters: every gradient is one of the fake net's."""
+
+    @staticmethod
+    def forward(ctx, diffusion, net, x, noise, indices, tab, y, *params):
+        N = x.shape[0] // 2
+        x_in, _ = ops.edm_dsm_prep(x, noise, tab[indices], diffusion.sigma_data)
+        h, ctx.tape = encoder_forward(net, x_in, _denoiser_time(tab, indices), y)
+        ctx.sign = [1] * N + [-1] * N
+        ctx.logit, a = ops.sida_map_fwd(h, ctx.sign)
+        ctx.h_shape = tuple(h.shape)
+        ctx.set_materialize_grads(False)
+        lf, lr = ctx.logit[:N].clone(), ctx.logit[N:].clone()
+        ctx.mark_non_differentiable(lf, lr)
+        return a[:N] + a[N:], lf, lr
+
+    @staticmethod
+    def backward(ctx, g_loss, g_lf, g_lr):
+        if g_loss is None:
+            return (None,) * len(ctx.needs_input_grad)
+        up = g_loss.detach().float().contiguous()
+        d_h = ops.sida_map_bwd(ctx.logit, ctx.sign, 1.0, ctx.h_shape[-1], upstream=torch.cat([up, up]), shape=ctx.h_shape)
+        ctx.logit = None
+        grads = encoder_backward(ctx.tape, d_h)
+        ctx.tape = None
+        return (None,) * 7 + grads
 
 
 class KarrasDenoiser:
@@ -1300,6 +1394,129 @@ class KarrasDenoiser:
             g = torch.autograd.grad(loss.sum(), xd)[0] * xd[0].numel() if keep else None
         loss = loss.detach()
         return {"loss": _SiDSurrogate.apply(x, g, loss) if keep else loss, "x": x.detach().float(), "dm_norm": s}
+
+    def sida_generator_losses(self, model, z, num_scales=1000, real_model=None, real_diffusion=None, fake_model=None, fake_diffusion=None,
+                              model_kwargs=None, noise=None, indices=None, generator=None, gen_sigma=None, alpha=1.2,
+                              sida_gen_weight=0.01, min_step_frac=0.02, max_step_frac=0.98, gen_sigmas=None):
+        """Adversarial Score identity Distillation loss of the one-step generator (SiDA, Zhou, Zheng et al. 2024): the loss of
+        sid_generator_losses plus an adversarial term whose discriminator has no parameters of its own -> {"loss": [N], "x": [N, C, H,
+        W] detached fp32, "dm_norm": [N], "adv_loss": [N], "adv_logit": [N, P]} (the last two detached).  With h the activation of
+        fake_model after its middle block at the SAME point (c_in x_t, t) the SiD term evaluates it at, [N, Cb, hb, wb], P = hb wb:
+            logit[n, p] = mean_c h[n, c, p],  adv_n = mean_p softplus(-logit[n, p]),  loss_n = sid_n + sida_gen_weight adv_n / s_n
+        with sid_n and s_n ("dm_norm", stop-gradient) those of sid_generator_losses; s_n == 0 gives loss 0 and no gradient.  The
+        gradient reaches the generator through x alone: no parameter of the real or the fake net receives one.  sida_gen_weight = 0
+        is sid_generator_losses bit for bit.  On HIP UNetModels it is ONE node (_SiDALossFn) that adds no network pass to SiD's:
+        the fake net's input_forward hands out h, and its one input_backward takes the cotangent of h at the bottleneck next to
+        the one at the output.  Any other fake model must offer encode(x_in, t, **kw) -> [N, Cb, hb, wb] (two calls of it off the
+        device).  Checks, refusals and draws (indices, then noise) are sid_generator_losses's; K > 1 is refused.  DESIGN 5.41."""
+        what = "sida_generator_losses"
+        if gen_sigmas is not None:
+            if gen_sigma is not None:
+                raise ValueError(f"{what}: gen_sigmas excludes gen_sigma: give one of them")
+            ladder = gen_ladder(what, gen_sigmas)
+            if len(ladder) > 1:
+                raise NotImplementedError(f"{what}: a K-step generator (gen_sigmas of {len(ladder)} levels) is limited to "
+                                          "dm_generator_losses: adversarial score identity distillation is built for K = 1 only")
+            gen_sigma = ladder.sigmas[0]
+        model_kwargs, fake_diffusion = self._dm_refusals(what, real_model, real_diffusion, fake_model, fake_diffusion, model_kwargs)
+        alpha, weight = float(alpha), float(sida_gen_weight)
+        if not math.isfinite(alpha):
+            raise ValueError(f"{what}: alpha must be finite, got {alpha!r}")
+        if not math.isfinite(weight):
+            raise ValueError(f"{what}: sida_gen_weight must be finite, got {weight!r}")
+        gen_sigma, indices, noise = self._dm_draws(what, z, num_scales, noise, indices, generator, gen_sigma, min_step_frac, max_step_frac)
+        keys = ("loss", "x", "dm_norm", "adv_loss", "adv_logit")
+        nets = [_hip_unet(m) for m in (model, real_model, fake_model)]
+        if all(n is not None for n in nets) and z.is_cuda:
+            args = self._dm_hip_operands(what, nets, z, num_scales, model_kwargs, real_diffusion, fake_diffusion, noise, indices, gen_sigma)
+            if torch.is_grad_enabled():
+                out = _SiDALossFn.apply(*args, alpha, weight, *ops.fast_parameters(nets[0]))
+            else:
+                loss, x, s, _, adv, logit = _sida_loss(*args, alpha, weight, keep=False)
+                out = (loss, x, s, adv, logit)
+            return dict(zip(keys, out))
+        if z.requires_grad or noise.requires_grad:
+            raise NotImplementedError(f"{what} differentiates the generator's parameters only: z and noise must not require grad")
+        if not hasattr(fake_model, "encode"):
+            raise NotImplementedError(f"{what}: the fake model must offer encode(x_in, t, **kw) -> [N, Cb, hb, wb], the bottleneck "
+                                      f"features the discriminator reads; {type(fake_model).__name__} has no encode")
+        N, dims = z.shape[0], z.ndim
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(z.device)
+        t = levels[indices.to(z.device)]
+        sigma_g = torch.full((N,), gen_sigma, dtype=torch.float32, device=z.device)
+        x = self.denoise(model, z * gen_sigma, sigma_g, **model_kwargs)[1]
+        keep = torch.is_grad_enabled()
+        # d loss / d x is taken here, by autograd.grad with respect to x alone: the denoisers' parameters see no backward at all
+        with torch.enable_grad() if keep else torch.no_grad():
+            xd = x.detach().requires_grad_(keep)
+            x_t = xd + noise * append_dims(t, dims)
+            d_real = real_diffusion.denoise(real_model, x_t, t, **model_kwargs)[1]
+            d_fake = fake_diffusion.denoise(fake_model, x_t, t, **model_kwargs)[1]
+            c_in = append_dims(fake_diffusion.get_scalings(t)[2], dims)
+            h = fake_model.encode(c_in * x_t, 1000 * 0.25 * torch.log(t + 1e-44), **model_kwargs)
+            logit = h.flatten(2).mean(dim=1)
+            adv = torch.nn.functional.softplus(-logit).mean(dim=1)
+            s = mean_flat(torch.abs(xd - d_real)).detach()
+            delta = d_real - d_fake
+            total = ((1 - alpha) * delta ** 2 + delta * (d_fake - xd)).flatten(1).sum(dim=1)
+            live = s != 0
+            safe = torch.where(live, s, torch.ones_like(s))
+            loss = torch.where(live, total / (xd[0].numel() * safe) + weight * adv / safe, torch.zeros_like(s))
+            g = torch.autograd.grad(loss.sum(), xd)[0] * xd[0].numel() if keep else None
+        loss = loss.detach()
+        return {"loss": _SiDSurrogate.apply(x, g, loss) if keep else loss, "x": x.detach().float(), "dm_norm": s,
+                "adv_loss": adv.detach(), "adv_logit": logit.detach()}
+
+    def sida_discriminator_losses(self, fake_model, x_fake, x_real, num_scales, model_kwargs=None, real_kwargs=None, noise=None,
+                                  indices=None, generator=None, min_step_frac=0.0, max_step_frac=1.0):
+        """SiDA's discriminator loss -> {"loss": [N], "logit_fake": [N, P], "logit_real": [N, P]} (logits detached).  `self` is the
+        fake denoiser's diffusion.  The generated batch x_fake (model_kwargs) and the real batch x_real (real_kwargs) run as one batch
+        of 2N, generated half first: indices [2N] are drawn uniformly over dm_index_range(num_scales, min_step_frac, max_step_frac)
+        when None, then noise [2N, C, H, W]; x_t = x + noise t, h = the activation of fake_model after its middle block at
+        (c_in x_t, t), logit = mean_c h, and with a_n(sign) = mean_p softplus(sign logit[n, p]):
+            loss_n = a_n(+1) of the generated image + a_n(-1) of the real image.
+        The discriminator has no parameters of its own: gradients go to the fake net's encoder, middle block and embedding
+        parameters, its decoder gets none.  On the HIP U-Net it is one node (_SiDADisLossFn); any other fake model must offer
+        encode(x_in, t, **kw).  DESIGN 5.41."""
+        what = "sida_discriminator_losses"
+        if tuple(x_fake.shape) != tuple(x_real.shape):
+            raise ValueError(f"{what}: the generated batch {tuple(x_fake.shape)} and the real batch {tuple(x_real.shape)} must have one shape")
+        model_kwargs, real_kwargs = model_kwargs or {}, real_kwargs or {}
+        if set(model_kwargs) != set(real_kwargs):
+            raise ValueError(f"{what}: model_kwargs {sorted(model_kwargs)} and real_kwargs {sorted(real_kwargs)} must name the same inputs")
+        kw = {k: torch.cat([model_kwargs[k], real_kwargs[k].to(model_kwargs[k].device)]) for k in model_kwargs}
+        net = _hip_unet(fake_model)
+        x = torch.cat([x_fake.detach(), x_real.detach().to(x_fake.device)])
+        if net is not None and x.is_cuda:
+            x = x.float()
+        _, indices, noise = self._dm_draws(what, x, num_scales, noise, indices, generator, 1.0, min_step_frac, max_step_frac)
+        N = x_fake.shape[0]
+        if tuple(noise.shape) != tuple(x.shape) or indices.numel() != 2 * N:
+            raise ValueError(f"{what}: noise {tuple(noise.shape)} must match the stacked batch {tuple(x.shape)} and indices "
+                             f"({indices.numel()}) hold one level per sample of it")
+        if net is not None and x.is_cuda:
+            extra = set(kw) - {"y"}
+            if extra:
+                raise NotImplementedError(f"{what} on the HIP U-Net: model_kwargs {sorted(extra)} are not inputs of UNetModel")
+            y = kw.get("y")
+            if (y is not None) != (net.num_classes is not None):
+                raise ValueError("must specify y if and only if the model is class-conditional")
+            x, noise = x.contiguous(), noise.detach().to(torch.float32).contiguous()
+            indices = indices.detach().to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
+            tab = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).device_table(x.device)
+            loss, lf, lr = _SiDADisLossFn.apply(self, net, x, noise, indices, tab, y, *ops.fast_parameters(net))
+            return {"loss": loss, "logit_fake": lf, "logit_real": lr}
+        if not hasattr(fake_model, "encode"):
+            raise NotImplementedError(f"{what}: the fake model must offer encode(x_in, t, **kw) -> [N, Cb, hb, wb], the bottleneck "
+                                      f"features the discriminator reads; {type(fake_model).__name__} has no encode")
+        levels = cd_levels(num_scales, self.sigma_min, self.sigma_max, self.rho).table.to(x.device)
+        t = levels[indices.to(x.device)]
+        x_t = x + noise * append_dims(t, x.ndim)
+        c_in = append_dims(self.get_scalings(t)[2], x.ndim)
+        logit = fake_model.encode(c_in * x_t, 1000 * 0.25 * torch.log(t + 1e-44), **kw).flatten(2).mean(dim=1)
+        sp = torch.nn.functional.softplus
+        return {"loss": sp(logit[:N]).mean(dim=1) + sp(-logit[N:]).mean(dim=1), "logit_fake": logit[:N].detach(),
+                "logit_real": logit[N:].detach()}
 
     def denoise(self, model, x_t, sigmas, **model_kwargs):
         scal = self.get_scalings_for_boundary_condition(sigmas) if self.distillation else self.get_scalings(sigmas)

@@ -610,7 +610,11 @@ class DMTrainLoop(TrainLoop):
     in one trainer skips that trainer's update alone.  save() adds fake_model%06d.pt and fake_opt%06d.pt to TrainLoop's files; a
     resume reads all of them, and a missing fake_model file is an error.  use_graph=True is refused.
     objective: "dmd" (dm_generator_losses under `weighting`) or "sid" (sid_generator_losses at sid_alpha: score identity distillation,
-    DESIGN 5.34); only the generator's loss differs, everything else of the loop is the same.
+    DESIGN 5.34); only the generator's loss differs, everything else of the loop is the same.  "sida" (sida_generator_losses at
+    sid_alpha and sida_gen_weight: adversarial score identity distillation) adds a discriminator WITHOUT parameters,
+    the channel mean of the fake net's bottleneck.  It needs real_data and takes no gan_head; on the fake clock every microbatch
+    backpropagates (dsm weights).mean() + sida_dis_weight dis.mean(), dis being sida_discriminator_losses on the generated and the
+    real microbatch.  The discriminator lives in the fake net: no checkpoint file is added.  One-step generators only.
     gan_head (models.cm.gan_head.GANHead; None: the loop without it): DMD2's GAN term.  It needs real_data, an iterator
     of (x_real NCHW fp32 in [-1, 1], cond).  The head trains with the fake denoiser on its clock: one trainer / RAdam / loss scale
     over (fake net, head), one backward per microbatch of (dsm weights).mean() + gan_dis_weight dis.mean(), dis being
@@ -624,7 +628,7 @@ class DMTrainLoop(TrainLoop):
     def __init__(self, *, real_model, real_diffusion, fake_model, fake_diffusion=None, num_scales=1000, gen_update_every=5,
                  fake_lr=None, weighting="dmd", gen_sigma=None, min_step_frac=0.02, max_step_frac=0.98, generator=None, objective="dmd",
                  sid_alpha=1.2, gan_head=None, real_data=None, gan_gen_weight=3e-3, gan_dis_weight=1e-2, gan_min_step_frac=0.0,
-                 gan_max_step_frac=1.0, gen_sigmas=None, **kwargs):
+                 gan_max_step_frac=1.0, gen_sigmas=None, sida_gen_weight=0.01, sida_dis_weight=1.0, **kwargs):
         if kwargs.get("use_graph"):
             raise NotImplementedError("DMTrainLoop: use_graph=True is not supported: the generator and the fake denoiser are updated "
                                       "on two clocks, which needs two captured steps and a graph key per clock; train this mode eagerly")
@@ -632,10 +636,19 @@ class DMTrainLoop(TrainLoop):
             raise NotImplementedError("DMTrainLoop: must have a real_model with its real_diffusion and a fake_model")
         if int(gen_update_every) < 1:
             raise ValueError(f"DMTrainLoop: gen_update_every must be at least 1, got {gen_update_every}")
-        if objective not in ("dmd", "sid"):
-            raise ValueError(f"DMTrainLoop: objective {objective!r} is not one of ('dmd', 'sid')")
-        if objective == "sid" and not math.isfinite(float(sid_alpha)):
+        if objective not in ("dmd", "sid", "sida"):
+            raise ValueError(f"DMTrainLoop: objective {objective!r} is not one of ('dmd', 'sid', 'sida')")
+        if objective in ("sid", "sida") and not math.isfinite(float(sid_alpha)):
             raise ValueError(f"DMTrainLoop: sid_alpha must be finite, got {sid_alpha!r}")
+        if objective == "sida":
+            if gan_head is not None:
+                raise ValueError("DMTrainLoop: objective 'sida' takes no gan_head: its discriminator is the channel mean of the fake "
+                                 "denoiser's bottleneck and has no parameters of its own")
+            if real_data is None:
+                raise ValueError("DMTrainLoop: objective 'sida' needs real_data, an iterator of (x_real NCHW fp32 in [-1, 1], cond)")
+            for name, v in (("sida_gen_weight", sida_gen_weight), ("sida_dis_weight", sida_dis_weight)):
+                if not math.isfinite(float(v)):
+                    raise ValueError(f"DMTrainLoop: {name} must be finite, got {v!r}")
         if gan_head is not None and objective == "sid":
             raise NotImplementedError("DMTrainLoop: objective 'sid' takes no gan_head: a discriminator on score identity distillation "
                                       "is SiDA, a different recipe (its own loss weighting and schedule), which is not built here")
@@ -645,8 +658,8 @@ class DMTrainLoop(TrainLoop):
             if gen_sigma is not None:
                 raise ValueError("DMTrainLoop: gen_sigmas (the K-step ladder) excludes gen_sigma (the one-step level): give one of them")
             gen_sigmas = gen_ladder("DMTrainLoop", gen_sigmas).sigmas
-            if objective == "sid" and len(gen_sigmas) > 1:
-                raise NotImplementedError(f"DMTrainLoop: objective 'sid' is limited to a one-step generator, gen_sigmas has "
+            if objective in ("sid", "sida") and len(gen_sigmas) > 1:
+                raise NotImplementedError(f"DMTrainLoop: objective {objective!r} is limited to a one-step generator, gen_sigmas has "
                                           f"{len(gen_sigmas)} levels: backward simulation is built for objective 'dmd' alone")
         super().__init__(**kwargs)
         self.gen_sigmas = gen_sigmas
@@ -660,6 +673,7 @@ class DMTrainLoop(TrainLoop):
         self.weighting, self.gen_sigma, self.generator = weighting, gen_sigma, generator
         self.min_step_frac, self.max_step_frac = min_step_frac, max_step_frac
         self.objective, self.sid_alpha = objective, float(sid_alpha)
+        self.sida_gen_weight, self.sida_dis_weight = float(sida_gen_weight), float(sida_dis_weight)
         self.real_model.requires_grad_(False)
         self.real_model.eval()
         if self.resume_checkpoint:      # never restart the fake denoiser from the teacher silently
@@ -730,7 +744,8 @@ class DMTrainLoop(TrainLoop):
         if gen_turn:
             self.mp_trainer.zero_grad()
         self.fake_trainer.zero_grad()
-        if self.gan_head is not None:
+        with_real = self.gan_head is not None or self.objective == "sida"
+        if with_real:
             x_real, real_cond = next(self.real_data)
             if x_real.shape[0] != batch.shape[0]:
                 raise ValueError(f"DMTrainLoop: real_data yields batches of {x_real.shape[0]} images, the latents come in {batch.shape[0]}")
@@ -740,6 +755,8 @@ class DMTrainLoop(TrainLoop):
             micro_cond = {k: v[i:i + self.microbatch].to(self.device) for k, v in cond.items()}
             if self.objective == "sid":
                 gen_loss, how = self.diffusion.sid_generator_losses, dict(alpha=self.sid_alpha)
+            elif self.objective == "sida":
+                gen_loss, how = self.diffusion.sida_generator_losses, dict(alpha=self.sid_alpha, sida_gen_weight=self.sida_gen_weight)
             else:
                 gen_loss, how = self.diffusion.dm_generator_losses, dict(weighting=self.weighting)
                 if self.gan_head is not None:
@@ -766,6 +783,13 @@ class DMTrainLoop(TrainLoop):
                     generator=self.generator, gan_min_step_frac=self.gan_min_step_frac, gan_max_step_frac=self.gan_max_step_frac)
                 fake_loss = fake_loss + self.gan_dis_weight * dis["loss"].mean()
                 logs.update(gan_gen=terms["gan_loss"], gan_dis=dis["loss"], logit_fake=dis["logit_fake"], logit_real=dis["logit_real"])
+            if self.objective == "sida":
+                dis = self.fake_diffusion.sida_discriminator_losses(
+                    self.fake_model, x, x_real[i:i + self.microbatch].to(self.device), self.num_scales, model_kwargs=micro_cond,
+                    real_kwargs={k: v[i:i + self.microbatch].to(self.device) for k, v in real_cond.items()}, generator=self.generator)
+                fake_loss = fake_loss + self.sida_dis_weight * dis["loss"].mean()
+                logs.update(sida_gen=terms["adv_loss"], sida_dis=dis["loss"], logit_fake=dis["logit_fake"].mean(dim=1),
+                            logit_real=dis["logit_real"].mean(dim=1))
             self._log_loss_dict(logs)
             self.fake_trainer.backward(fake_loss)
 

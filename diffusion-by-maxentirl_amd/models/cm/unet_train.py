@@ -20,7 +20,8 @@ dxmi_dropout_bf16 on the conv2 input: one seed per ResBlock per forward, kept on
 (seed, p) to the gradient (no mask is stored).  With dropout 0, or in eval mode, nothing of it runs.  Inside a StepGraph capture
 (dxmi_hip/graph.py) every site's seed is a host input of the graph, so a replayed step draws the seeds an eager step would draw.
 Parameter gradients come back in net.parameters() order.  train_forward / train_backward / input_forward / input_backward /
-input_vjp keep the tape outside autograd; encoder_forward / encoder_backward / encoder_input_forward / encoder_input_backward are
+input_vjp keep the tape outside autograd (input_forward(tap=True) also hands out the bottleneck, and input_backward(d_tap=...) takes
+its cotangent in the same walk: SiDA's discriminator reads SiD's own evaluation of the fake net); encoder_forward / encoder_backward / encoder_input_forward / encoder_input_backward are
 the same pass stopped at the bottleneck: the output of middle_block (NHWC bf16) and its cotangent take the place of the model
 output, and no output_blocks / out launch is issued in either direction.
 """
@@ -194,6 +195,9 @@ class _EDMUNetFn(torch.autograd.Function):
         ctx.net, ctx.tape, ctx.x, ctx.sinus, ctx.y, ctx.emb_all = net, tape, x, sinus, y, emb_all
         if getattr(ctx, "encoder_only", False):      # the pass that stops at the bottleneck (unet_bwd.encoder_api): NHWC bf16
             return h
+        if getattr(ctx, "tap", False):               # input_forward(tap=True): the bottleneck is handed out, and the walk may take
+            ctx.bottleneck = h                       # a cotangent for it where it passes this entry
+            tape.append(("tap", None))
         for blk in net.output_blocks:
             tape.append(("skip", None, len(hs) - 1))
             skip, sskip = hs.pop()
@@ -285,7 +289,7 @@ class _EDMUNetFn(torch.autograd.Function):
             conv_wb(m.op, xin, g, 3, stride=2, pad=1)
             return ops.conv2d(g, pkt[id(m), "conv"], pad=1, pad_br=1, upsample=2)
 
-        g = walk(ctx.tape, g, res_bwd, attn_bwd, up_bwd, down_bwd)
+        g = walk(ctx.tape, g, res_bwd, attn_bwd, up_bwd, down_bwd, d_tap=getattr(ctx, "d_tap", None))
         dx = bw.stem(net.input_blocks[0][0], ctx.x, g, ctx.needs_input_grad[1])
         if not params:
             return bw.finish(4, dx)

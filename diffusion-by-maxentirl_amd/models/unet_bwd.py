@@ -4,7 +4,9 @@ Both training forwards leave a tape: a list of entries (kind, module, saved...),
   "res"   a residual block; slot 3 is x1, the skip tensor an up-path block concatenates to its input (None elsewhere);
   "attn", "up", "down"   an attention block, an upsample, a downsample;
   "push"  (., ., idx): the activation at this point was stored as hs[idx] (hs[0] is the stem's output and has no entry);
-  "skip"  (., ., idx): the "res" entry that follows took hs[idx] as its x1.
+  "skip"  (., ., idx): the "res" entry that follows took hs[idx] as its x1;
+  "tap"   (., .): the activation at this point was handed out by the forward (the EDM net's bottleneck, input_forward(tap=True));
+          a cotangent given for it (walk's d_tap) joins the running gradient here.  A forward without a tap writes no such entry.
 walk() runs the tape in reverse and owns the skip-connection rule: the x1 gradient of a concat block is parked under the index
 its "skip" entry names and added where that activation was pushed.  Backward holds the state of one backward and the parts around
 the walk that do not depend on the net: head, shortcut data gradient, stem, the rows of a concatenated dense layer, the
@@ -38,8 +40,11 @@ def pool_t(g):
     return out
 
 
-def walk(tape, g, res_bwd, attn_bwd, up_bwd, down_bwd):
-    """The tape in reverse -> the gradient of hs[0].  res_bwd(entry, g) -> (d_x0, d_x1); the other callbacks (entry, g) -> g."""
+def walk(tape, g, res_bwd, attn_bwd, up_bwd, down_bwd, d_tap=None):
+    """The tape in reverse -> the gradient of hs[0].  res_bwd(entry, g) -> (d_x0, d_x1); the other callbacks (entry, g) -> g.
+    d_tap: the cotangent of the tapped activation, added where the walk passes its "tap" entry (None: nothing is launched there)."""
+    if d_tap is not None and not any(e[0] == "tap" for e in tape):
+        raise ValueError("walk: a tap cotangent was given, but the forward that wrote this tape handed out no tap")
     gskip = {}
     i = len(tape) - 1
     while i >= 0:
@@ -61,6 +66,12 @@ def walk(tape, g, res_bwd, attn_bwd, up_bwd, down_bwd):
         elif kind == "push":         # h was stored as hs[idx]: the up path may have consumed it as a skip
             if e[2] in gskip:
                 g = g + gskip.pop(e[2])
+        elif kind == "tap":
+            if d_tap is not None:
+                if d_tap.shape != g.shape or d_tap.dtype != g.dtype:
+                    raise ValueError(f"walk: the tap cotangent {tuple(d_tap.shape)} {d_tap.dtype} is not the tapped activation's "
+                                     f"{tuple(g.shape)} {g.dtype}")
+                g = g + d_tap
         elif kind == "skip":
             raise AssertionError("skip entry must directly precede the block that consumes it")
         i -= 1
@@ -214,14 +225,29 @@ def tape_api(fn, n_inputs):
         """The backward of train_forward -> the gradients of net.parameters(), in that order."""
         return tuple(fn.backward(tape, d_out)[n_inputs:])
 
-    def input_forward(net, x, t, *cond):
+    def input_forward(net, x, t, *cond, tap=False):
         """The first half of input_vjp -> (F, tape): the training forward with dropout off (eval mode, the net's own mode
-        restored), its tape kept for input_backward.  For a caller whose cotangent is known only after this forward."""
-        return _eval_forward(fn, n_inputs, InputTape(), net, x, t, cond)
+        restored), its tape kept for input_backward.  For a caller whose cotangent is known only after this forward.
+        tap=True (a net whose Function honours ctx.tap: the EDM U-Net): tape.bottleneck is the activation after middle_block
+        (NHWC bf16), the tensor encoder_input_forward returns, from this same evaluation; F and every launch are unchanged."""
+        tape = InputTape()
+        if tap:
+            tape.tap = True
+        out = _eval_forward(fn, n_inputs, tape, net, x, t, cond)
+        if tap and getattr(tape, "bottleneck", None) is None:
+            raise NotImplementedError(f"input_forward(tap=True): {type(net).__name__} hands out no bottleneck")
+        return out
 
-    def input_backward(tape, v):
+    def input_backward(tape, v, d_tap=None):
         """The second half of input_vjp -> g = d(v . F)/dx for the tape of input_forward: the backward walk with its weight, bias
-        and embedding launches switched off.  A tape is walked once; drop it afterwards."""
+        and embedding launches switched off.  A tape is walked once; drop it afterwards.
+        d_tap (a tape of input_forward(tap=True)): a second cotangent, of tape.bottleneck (NHWC bf16); it is added to the running
+        gradient where the walk passes from the decoder into middle_block, so that g = d(v . F + d_tap . h)/dx comes out of one
+        walk.  None: the walk of today, launch for launch."""
+        if d_tap is not None:
+            if not getattr(tape, "tap", False):
+                raise ValueError("input_backward: d_tap needs the tape of input_forward(tap=True)")
+            tape.d_tap = d_tap.contiguous()
         with torch.no_grad():
             return fn.backward(tape, v.contiguous().float())[1]
 

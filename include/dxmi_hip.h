@@ -789,6 +789,22 @@ int dxmi_sid_join(const float* d_dir, const float* g_real, const float* g_fake, 
                   const float* t_table, int32_t num_scales, float* g, int32_t N, int32_t CHW, float real_sigma_data,
                   float fake_sigma_data, void* stream);
 
+/* Adversarial Score identity Distillation (SiDA, Zhou, Zheng et al. 2024; KarrasDenoiser.sida_generator_losses and
+ * sida_discriminator_losses; csrc/sida_train.hip): a discriminator WITHOUT parameters on the fake denoiser's bottleneck
+ * activation h, NHWC bf16 [N, P, Cb] (P positions, Cb channels, Cb % 8 == 0, Cb <= 4096, P <= 2^20, h and d_h 16-byte aligned):
+ *   logit[n, p] = (1 / Cb) sum_c h[n, p, c],   a[n] = (1 / P) sum_p softplus(sign[n] logit[n, p]),
+ * softplus in the form of dxmi_gan_logit_loss_fwd.  fp32, a fixed sum order that does not depend on N (an image gives the same bits
+ * in every batch), no atomics.  sign (int32, -1 or +1 per image) and coef (fp32, finite) are HOST arrays of N values: they are checked
+ * in the call (DXMI_EINVAL names the first bad index) and travel as kernel arguments, 64 images to a launch; nothing is copied and
+ * nothing waits for the device.
+ * dxmi_sida_map_fwd: h -> logit [N, P] and a [N].
+ * dxmi_sida_map_bwd: d_h[n, p, c] = bf16((coef[n] upstream[n]) sign[n] sigmoid(sign[n] logit[n, p]) / (P Cb)) for every c: the
+ *   cotangent of sum_n coef[n] upstream[n] a[n] with respect to h, rounded once.  upstream: fp32 [N] on the device (the per-image
+ *   gradient an autograd backward receives), or NULL for 1. */
+int dxmi_sida_map_fwd(const void* h, const int32_t* sign, float* logit, float* a, int32_t N, int32_t P, int32_t Cb, void* stream);
+int dxmi_sida_map_bwd(const float* logit, const int32_t* sign, const float* coef, const float* upstream, void* d_h, int32_t N,
+                      int32_t P, int32_t Cb, void* stream);
+
 /* TD step of DxMI_Trainer.update_f_v on the replay ring, data side in one launch (reference trainer.py:271-300, :163-169): rows
  * `state_rows[b]` (and `next_rows[b]`, or the dense re-drawn next states of value_resample) of the ring's fp32 [n_src_rows, CHW]
  * trajectory block are gathered into out_state / out_next — the two halves of the batch [next_state | state] the value net
