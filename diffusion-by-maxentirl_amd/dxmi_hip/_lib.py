@@ -72,7 +72,12 @@ SIGNATURES = {
     "dxmi_knn_radii": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dxmi_pr_membership_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "dxmi_pr_membership": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dxmi_inception_score_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "dxmi_kid_sums_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
+    "dxmi_kid_sums": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, ctypes.c_double,
+                              ctypes.c_double, c_void_p, c_void_p, c_void_p]),
+    "dxmi_dc_counts_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
+    "dxmi_dc_counts": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dxmi_inception_score_workspace_bytes":(c_int64, [c_int64, c_int, c_int]),
     "dxmi_inception_score": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dxmi_packed_conv_weight_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "dxmi_pack_conv_weights": (c_int, [ctypes.POINTER(PackItem), c_int, c_void_p]),

@@ -2191,6 +2191,69 @@ def pr_membership(a, ra, b, rb):
     return a_in_b, b_in_a
 
 
+def kid_sums(x, y, idx_x=None, idx_y=None, gamma=None, coef0=1.0, workspace=None):
+    """Gram sums of the Kernel Inception Distance (Binkowski et al. 2018; include/dxmi_hip.h: dxmi_kid_sums): x fp32 [NX, D], y fp32
+    [NY, D], idx_x int32 [S, mx] and idx_y int32 [S, my] the rows of S subsets (both None: one subset of every row) -> fp64 [S, 3]
+    (device): Sxx = sum_{i != j} k(x_i, x_j), Syy likewise, Sxy = sum_{i, j} k(x_i, y_j), k(u, v) = ((double)(u . v) gamma + coef0)^3
+    with the f32 dot of the evaluator kernels; gamma None: 1 / D.  One launch over all subsets, bitwise reproducible; `workspace`
+    (a uint8 device tensor) does not change the result.  Indices are checked against [0, NX) / [0, NY) before the launch."""
+    NX, D = _rows_f32(x, "kid_sums")
+    NY, DY = _rows_f32(y, "kid_sums")
+    if DY != D:
+        raise ValueError(f"kid_sums: feature sizes differ ({D} vs {DY})")
+    if (idx_x is None) != (idx_y is None):
+        raise ValueError("kid_sums: idx_x and idx_y must both be given or both be None")
+    S, mx, my = 1, NX, NY
+    if idx_x is not None:
+        _need_cuda(idx_x, idx_y)
+        for idx, n, name in ((idx_x, NX, "idx_x"), (idx_y, NY, "idx_y")):
+            if not (idx.dim() == 2 and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() > 0):
+                raise ValueError(f"kid_sums: {name} must be a contiguous non-empty int32 [S, m] device tensor, got {tuple(idx.shape)} {idx.dtype}")
+            lo, hi = int(idx.min()), int(idx.max())
+            if lo < 0 or hi >= n:
+                raise ValueError(f"kid_sums: {name} holds a row index outside [0, {n}) (min {lo}, max {hi})")
+        if idx_x.shape[0] != idx_y.shape[0]:
+            raise ValueError(f"kid_sums: idx_x names {idx_x.shape[0]} subsets, idx_y {idx_y.shape[0]}")
+        S, mx, my = idx_x.shape[0], idx_x.shape[1], idx_y.shape[1]
+    gamma = 1.0 / D if gamma is None else float(gamma)
+    lib = load()
+    sums = torch.empty((S, 3), dtype=torch.float64, device=x.device)
+    need = lib.dxmi_kid_sums_workspace_bytes(S, mx, my, D)
+    if workspace is None:
+        workspace = _workspace(max(256, need), x.device)
+    elif workspace.numel() < need:
+        raise ValueError(f"kid_sums: workspace of {workspace.numel()} bytes, need {need}")
+    pairs = mx * (mx + 1) // 2 + my * (my + 1) // 2 + mx * my
+    _prof("eval_metrics", f"kid_d{D}", 2.0 * S * pairs * D, 4.0 * S * D * (mx + my) * ((mx + my + 127) // 128), lambda: check(
+        lib.dxmi_kid_sums(_ptr(x), NX, _ptr(y), NY, D, _ptr(idx_x), _ptr(idx_y), S, mx, my, gamma, float(coef0), _ptr(sums), _ptr(workspace),
+                          _stream()), "dxmi_kid_sums"))
+    return sums
+
+
+def dc_counts(a, ra, b, splits=0, workspace=None):
+    """Ball counts of density / coverage (Naeem et al. 2020; include/dxmi_hip.h: dxmi_dc_counts): reference rows a fp32 [NA, D] with
+    their k-NN radii ra fp32 [NA], sample rows b fp32 [NB, D] -> int32 [NA], counts[i] = #{j : d(a_i, b_j) < ra[i]} (strict, where
+    pr_membership compares with <=).  `splits` (0: automatic) and `workspace` (a uint8 device tensor) do not change the result."""
+    NA, D = _rows_f32(a, "dc_counts")
+    NB, DB = _rows_f32(b, "dc_counts")
+    if DB != D:
+        raise ValueError(f"dc_counts: feature sizes differ ({D} vs {DB})")
+    _need_cuda(ra)
+    if ra.shape != (NA,) or ra.dtype != torch.float32:
+        raise ValueError("dc_counts: radii must be float32 [NA]")
+    ra = ra.contiguous()
+    lib = load()
+    counts = torch.empty(NA, dtype=torch.int32, device=a.device)
+    need = lib.dxmi_dc_counts_workspace_bytes(NA, NB, splits)
+    if workspace is None:
+        workspace = _workspace(max(256, need), a.device)
+    elif workspace.numel() < need:
+        raise ValueError(f"dc_counts: workspace of {workspace.numel()} bytes, need {need}")
+    _prof("eval_metrics", f"dc_d{D}", 2.0 * NA * NB * D, 4.0 * D * (NA * ((NB + 127) // 128) + NB * ((NA + 127) // 128)), lambda: check(
+        lib.dxmi_dc_counts(_ptr(a), NA, _ptr(ra), _ptr(b), NB, D, splits, _ptr(counts), _ptr(workspace), _stream()), "dxmi_dc_counts"))
+    return counts
+
+
 def inception_score_kl(pool, w, split_size=5000):
     """Per-split mean KL of Evaluator.compute_inception_score (evaluator.py:179-193): pool fp32 [N, D], w fp32 [C, D] (fc.weight
     layout, no bias) -> fp64 [ceil(N / split_size)] (device): mean_r sum_c p (log p - log p_bar), p = softmax(pool . w^T) in f32,

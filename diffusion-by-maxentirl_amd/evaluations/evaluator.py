@@ -17,6 +17,17 @@ as the reference's TensorFlow evaluator does (evaluations/evaluator.py:27-59 the
     FID / sFID    pytorch_fid.fid_score.calculate_frechet_distance (the reference's float64 sqrtm algorithm)
     P / R         dxmi_knn_radii (k = 3) of both sets, then dxmi_pr_membership
 
+Two metrics the reference evaluator does not have are printed after `Recall:` when asked for, on the same pool features:
+
+    --kid         KID: / KID std: the Kernel Inception Distance (Binkowski et al. 2018), the unbiased MMD^2 estimate with the kernel
+                  (x . y / D + 1)^3: mean and standard deviation over `--kid_subsets` (100) subsets of `--kid_subset_size` (1000)
+                  rows of each set drawn with `--kid_seed` (0); `--kid_subsets 0`: one estimate over all rows (std 0).  Unlike FID
+                  it has no bias in the sample count, so a 10 000-image number and a 50 000-image number can be compared.
+                  dxmi_kid_sums: all subsets in one launch, the sums in fp64
+    --prdc        Density: / Coverage: (Naeem et al. 2020) with `--dc_k` (5) nearest neighbours: dxmi_knn_radii of the reference
+                  set, then dxmi_dc_counts (how many samples fall strictly inside each reference ball); density = sum / (k NB),
+                  coverage = the fraction of reference balls that hold a sample.  Robust where precision / recall follow outliers
+
 Not pinned to the TensorFlow numbers: the reference graph resizes with TF's legacy bilinear and normalises (x - 128) / 128, this
 extractor follows pytorch_fid and runs in bf16, and the weight file is not in this image.  The five numbers are comparable to the
 reference evaluator's, not equal to them.  Out of scope: clamp_to_percentile, realism scores and nearest indices
@@ -48,9 +59,19 @@ def parse_args(argv=None):
     ap.add_argument("sample_batch", help="path to sample batch npz file")
     ap.add_argument("--extractor", default=DEFAULT_EXTRACTOR, help="feature extractor 'module:attr' (class or instance)")
     ap.add_argument("--batch_size", type=int, default=64)
+    ap.add_argument("--kid", action="store_true", help="also print the Kernel Inception Distance (KID: / KID std:)")
+    ap.add_argument("--kid_subsets", type=int, default=100, help="number of KID subsets (0: one estimate over all rows)")
+    ap.add_argument("--kid_subset_size", type=int, default=1000, help="rows of each set per KID subset")
+    ap.add_argument("--kid_seed", type=int, default=0, help="seed of the KID subset draw")
+    ap.add_argument("--prdc", action="store_true", help="also print density and coverage (Density: / Coverage:)")
+    ap.add_argument("--dc_k", type=int, default=5, help="nearest neighbours of the density / coverage radii")
     a = ap.parse_args(argv)
     if a.batch_size < 1:
         ap.error("--batch_size must be >= 1")
+    if a.kid_subsets < 0 or a.kid_subset_size < 2:
+        ap.error("--kid_subsets must be >= 0 and --kid_subset_size >= 2")
+    if a.dc_k < 1:
+        ap.error("--dc_k must be >= 1")
     return a
 
 
@@ -184,12 +205,61 @@ def precision_recall(ref_pool, sample_pool, k=NHOOD_K):
     return int(sample_in.sum()) / sample_in.numel(), int(ref_in.sum()) / ref_in.numel()
 
 
-def evaluate(ref_batch, sample_batch, extractor, batch_size=64):
-    """The five numbers, in the order they are printed."""
+def kid_subset_indices(nx, ny, subsets, subset_size, seed):
+    """The rows of the KID subsets: two int32 arrays [subsets, m], m = min(nx, ny, subset_size), drawn without replacement within
+    a subset from one generator, for each subset in order its rows of the first set and then of the second."""
+    m = min(nx, ny, subset_size)
+    rng = np.random.default_rng(seed)
+    ix, iy = np.empty((subsets, m), dtype=np.int32), np.empty((subsets, m), dtype=np.int32)
+    for s in range(subsets):
+        ix[s] = rng.choice(nx, m, replace=False)
+        iy[s] = rng.choice(ny, m, replace=False)
+    return ix, iy
+
+
+def kernel_inception_distance(ref_pool, sample_pool, subsets=100, subset_size=1000, seed=0):
+    """(mean, std) over the subsets of the unbiased MMD^2 estimate with k(u, v) = (u . v / D + 1)^3 (Binkowski et al. 2018):
+    per subset (Sxx + Syy) / (m (m - 1)) - 2 Sxy / m^2 from ops.kid_sums, mean and np.std (ddof 0) on the host in float64.
+    subsets=0: the one estimate over all rows of both sets, Sxx / (nx (nx - 1)) + Syy / (ny (ny - 1)) - 2 Sxy / (nx ny), std 0."""
+    import torch
+    from dxmi_hip import ops
+    nx, ny = ref_pool.shape[0], sample_pool.shape[0]
+    if min(nx, ny) < 2 or (subsets > 0 and subset_size < 2):
+        raise ValueError(f"kernel_inception_distance: need at least 2 rows per set and per subset ({nx}, {ny}, subset_size {subset_size})")
+    D = ref_pool.shape[1]
+    if subsets == 0:
+        sxx, syy, sxy = ops.kid_sums(ref_pool, sample_pool, gamma=1.0 / D, coef0=1.0).cpu().numpy()[0]
+        return float(sxx / (nx * (nx - 1)) + syy / (ny * (ny - 1)) - 2.0 * sxy / (nx * ny)), 0.0
+    ix, iy = kid_subset_indices(nx, ny, subsets, subset_size, seed)
+    m = ix.shape[1]
+    sums = ops.kid_sums(ref_pool, sample_pool, torch.from_numpy(ix).to(ref_pool.device), torch.from_numpy(iy).to(ref_pool.device),
+                        gamma=1.0 / D, coef0=1.0).cpu().numpy()
+    vals = (sums[:, 0] + sums[:, 1]) / (m * (m - 1)) - 2.0 * sums[:, 2] / (m * m)
+    return float(np.mean(vals)), float(np.std(vals))
+
+
+def density_coverage(ref_pool, sample_pool, k=5):
+    """(density, coverage) of Naeem et al. 2020 as the `prdc` package computes them: with r_i the distance of reference row i to its
+    k-th nearest other reference row and c_i the number of sample rows strictly inside that ball, density = sum_i c_i / (k NB)
+    and coverage = mean_i (c_i > 0)."""
+    from dxmi_hip import ops
+    na, nb = ref_pool.shape[0], sample_pool.shape[0]
+    if na < k + 1:
+        raise ValueError(f"density_coverage: {na} reference rows; k = {k} needs at least {k + 1}")
+    r = ops.knn_radii(ref_pool, k)
+    c = ops.dc_counts(ref_pool, r, sample_pool)
+    return int(c.sum()) / (k * nb), int((c > 0).sum()) / na
+
+
+def evaluate(ref_batch, sample_batch, extractor, batch_size=64, kid=None, prdc=None, extra=None):
+    """The five numbers, in the order they are printed.  kid: None or dict(subsets, subset_size, seed); prdc: None or dict(k);
+    what they ask for goes into the dict `extra` under "kid" (mean, std) and "prdc" (density, coverage)."""
     import torch
     from dxmi_hip import ops
     from pytorch_fid.fid_score import calculate_frechet_distance
     ops.device_check()
+    if (kid is not None or prdc is not None) and extra is None:
+        raise ValueError("evaluate: kid / prdc need the dict `extra` to put their results into")
     w = getattr(extractor, "softmax_weight", None)
     if not (torch.is_tensor(w) and w.dim() == 2):
         raise ValueError("the extractor has no softmax_weight [2048, C] tensor (the Inception Score's classifier weight)")
@@ -207,6 +277,10 @@ def evaluate(ref_batch, sample_batch, extractor, batch_size=64):
     fid = calculate_frechet_distance(sample_stats[0], sample_stats[1], ref_stats[0], ref_stats[1])
     sfid = calculate_frechet_distance(sample_stats[2], sample_stats[3], ref_stats[2], ref_stats[3])
     prec, recall = precision_recall(ref_pool, sample_pool)
+    if kid is not None:
+        extra["kid"] = kernel_inception_distance(ref_pool, sample_pool, **kid)
+    if prdc is not None:
+        extra["prdc"] = density_coverage(ref_pool, sample_pool, **prdc)
     return inception_score, float(fid), float(sfid), prec, recall
 
 
@@ -215,12 +289,22 @@ def main(argv=None):
     from pytorch_fid.fid_score import load_extractor
     extractor = load_extractor(a.extractor)
     print(UNPINNED_NOTE)
-    inception_score, fid, sfid, prec, recall = evaluate(a.ref_batch, a.sample_batch, extractor, a.batch_size)
+    extra = {}
+    inception_score, fid, sfid, prec, recall = evaluate(
+        a.ref_batch, a.sample_batch, extractor, a.batch_size,
+        kid=dict(subsets=a.kid_subsets, subset_size=a.kid_subset_size, seed=a.kid_seed) if a.kid else None,
+        prdc=dict(k=a.dc_k) if a.prdc else None, extra=extra)
     print("Inception Score:", inception_score)
     print("FID:", fid)
     print("sFID:", sfid)
     print("Precision:", prec)
     print("Recall:", recall)
+    if a.kid:
+        print("KID:", extra["kid"][0])
+        print("KID std:", extra["kid"][1])
+    if a.prdc:
+        print("Density:", extra["prdc"][0])
+        print("Coverage:", extra["prdc"][1])
     return inception_score, fid, sfid, prec, recall
 
 

@@ -962,6 +962,33 @@ int64_t dxmi_pr_membership_workspace_bytes(int64_t NA, int64_t NB);
 int dxmi_pr_membership(const float* A, int64_t NA, const float* rA, const float* B, int64_t NB, const float* rB, int32_t D,
                        int32_t* a_in_b, int32_t* b_in_a, void* workspace, void* stream);
 
+/* dxmi_kid_sums: the Gram sums of the Kernel Inception Distance (Binkowski, Sutherland, Arbel, Gretton 2018, "Demystifying MMD
+ * GANs", the unbiased MMD^2 estimate with the polynomial kernel).  X fp32 [NX, D], Y fp32 [NY, D]; idx_x int32
+ * [S, mx] and idx_y int32 [S, my] name the rows of S subsets, x_i = X[idx_x[s, i]], y_j = Y[idx_y[s, j]] (device).  Both NULL: S = 1
+ * and the subset is every row (mx = NX, my = NY).  sums fp64 [S, 3] (device):
+ *     sums[s, 0] = Sxx = sum_{i != j} k(x_i, x_j)     sums[s, 1] = Syy = sum_{i != j} k(y_i, y_j)     sums[s, 2] = Sxy = sum_{i, j} k(x_i, y_j)
+ *     k(u, v) = t^3,  t = (double)(u . v) * gamma + coef0     (u . v the f32 dot above; t, the cube and every sum in fp64, no fma)
+ * The estimate is (Sxx / (mx (mx - 1)) + Syy / (my (my - 1)) - 2 Sxy / (mx my)) (host).  One launch covers all subsets (rows are
+ * gathered through the index in the tile loader, no gathered copy), X.X and Y.Y run their upper-triangular tiles only, and a second
+ * launch adds each subset's per-tile partials: no atomics, a summation order that depends on (mx, my, D) alone, bitwise reproducible.
+ * An index outside [0, NX) / [0, NY) is never dereferenced and makes that subset's three sums NaN.  2 <= mx, my.  workspace:
+ * dxmi_kid_sums_workspace_bytes(S, mx, my, D) = one double per tile, S * (Tx (Tx + 1) / 2 + Ty (Ty + 1) / 2 + Tx Ty) with
+ * Tx = ceil(mx / 128), Ty = ceil(my / 128); 0 for shapes dxmi_kid_sums refuses. */
+int64_t dxmi_kid_sums_workspace_bytes(int64_t S, int64_t mx, int64_t my, int32_t D);
+int dxmi_kid_sums(const float* X, int64_t NX, const float* Y, int64_t NY, int32_t D, const int32_t* idx_x, const int32_t* idx_y,
+                  int64_t S, int64_t mx, int64_t my, double gamma, double coef0, double* sums, void* workspace, void* stream);
+
+/* dxmi_dc_counts: the ball counts of density and coverage (Naeem, Oh, Uh, Choi, Yoo 2020, "Reliable Fidelity and Diversity
+ * Metrics for Generative Models", eq. 4 and 5, as the `prdc` package computes them).  Reference set A fp32 [NA, D]
+ * with its k-NN radii rA [NA] (dxmi_knn_radii), sample set B fp32 [NB, D] ->
+ *     counts[i] = #{ j : d(a_i, b_j) < rA[i] }     (int32 [NA]; strict, where dxmi_pr_membership uses <=)
+ * density = sum_i counts[i] / (k NB), coverage = mean_i (counts[i] > 0) (host).  splits: the number of column ranges B is cut
+ * into (0: automatic); the result does not depend on it.  No atomics, nothing NA x NB: workspace
+ * dxmi_dc_counts_workspace_bytes(NA, NB, splits) = the row norms of both sets + splits * NA int32. */
+int64_t dxmi_dc_counts_workspace_bytes(int64_t NA, int64_t NB, int32_t splits);
+int dxmi_dc_counts(const float* A, int64_t NA, const float* rA, const float* B, int64_t NB, int32_t D, int32_t splits, int32_t* counts,
+                   void* workspace, void* stream);
+
 /* dxmi_inception_score: Evaluator.compute_inception_score (evaluator.py:179-193) with the classifier weight only
  * (`softmax/logits/MatMul`, evaluator.py:603-616: no bias).  pool fp32 [N, D], w fp32 [C, D] (fc.weight layout) ->
  * kl_mean fp64 [ceil(N / split)] (device): for each split of `split` rows, mean_r sum_c p (log p - log p_bar) with
